@@ -12,6 +12,7 @@ Synthetic: closed-form weights (utils/synthetic.py), x_T and per-step noise from
         bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...            # no launcher: this file starts the N rank processes itself (launch_ranks)
     python bench.py --gpus N --train-dp     # data-parallel training line: cfg5 optimiser step with the C2 gradient all-reduce
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR    # + DIR/latent.npy, DIR/images.npy of the last timed step
 
 Rank 0 prints ONE JSON line on stdout; diagnostics go to stderr.
 """
@@ -873,6 +874,26 @@ def train_dp(args, rank, world, device, dist_on, fence):
     print(json.dumps(out), flush=True)
 
 
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each tensor as out_dir/<name>.npy in float32.  An array that would take the total past DUMP_BYTES_MAX keeps only its
+    leading entries along dim 0 (the first images of the batch): the same sample on every run with the same arguments."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BYTES_MAX
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        row = a[:1].nbytes
+        n = min(a.shape[0], left // row)
+        assert n > 0, f"--dump-outputs: no room left for {name}"
+        a = np.ascontiguousarray(a[:n])
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+        log(f"dump-outputs: {name} {tuple(a.shape)} float32 -> {out_dir}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -888,11 +909,18 @@ def main():
     ap.add_argument("--train-config", choices=("cfg5", "cfg3"), default="cfg5")
     ap.add_argument("--train-batch", type=int, default=None, help="override -bs of --train-config (tests)")
     ap.add_argument("--train-image-size", type=int, default=None, help="override -is of --train-config (tests)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step produced (rank 0) as DIR/<name>.npy, float32: latent.npy (B, 8, 32, 32) and "
+                         "its decode images.npy (B, 3, 256, 256; the first images only where the whole would pass 64 MB)")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 5 if args.train_dp else 200
     if args.warmup is None:
         args.warmup = 2 if args.train_dp else 10
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.train_dp:
+        ap.error("--dump-outputs applies to the sampling line, not --train-dp")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args, sys.argv[1:]))     # the parent: torch is not even imported in this process
@@ -1033,6 +1061,9 @@ def main():
         run_steps(max(args.warmup, 1))
         decode()
         settled = settle_clock()
+        # the clock settle runs for a TIME, so the latent it leaves differs from run to run: the timed steps start again from the
+        # seeded x_T, and what they compute depends on the arguments alone (--dump-outputs compares it across builds)
+        x.copy_(ops.randn((B, S, S, C), device, seed=1234, step=T_STEPS, stream_id=rank))
         fence()
         clk_steps.probe()
         t0 = time.perf_counter()
@@ -1049,6 +1080,8 @@ def main():
             dec.append(time.perf_counter() - t1)
         t_decode = min(dec)
         assert torch.isfinite(img).all() and img.shape == (B, 3, 256, 256)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"latent": ops.nhwc_to_nchw(x), "images": img})
         # ONE real job unit, not an extrapolation: a full T = 1000 chain from fresh x_T plus its decode (what
         # generate_model_samples.py times per batch, reference generate_model_samples.py:42-58), under a sustained clock
         full_chain_s = None
