@@ -20,6 +20,7 @@
 //   of a reverse step, so the separate prepare / pad kernel disappears.
 #include <type_traits>
 
+#include "cluster_sync.h"
 #include "conv_common.h"
 
 namespace ddk {
@@ -72,12 +73,10 @@ __device__ __forceinline__ float dpp_partner(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
 }
 
-constexpr unsigned long long FIRST_TIMEOUT_TICKS = 2000000ull;   // 20 ms of the 100 MHz s_memrealtime clock
-
 // FUSE (round 6): the Block's GroupNorm + Mish + time shift in the same launch.  A 128-pixel tile's statistics cannot normalise it --
 // the group spans the image's HW / 128 tiles -- so the workgroups of an image (consecutive block ids, dispatched together) exchange
-// their per-group {mean, M2} records exactly as conv3x3_wino2_kernel<.., true> does (row 1 of MI355X_MICROARCH.md's sc1 table: 8-byte
-// sc1 record stores by wave 0, drained, one arrival; one lane polls; workgroup barrier; sc1 loads), keep their 128 x N outputs in
+// their per-group {mean, M2} records exactly as conv3x3_wino2_kernel<.., true> does (cluster_sync.h: 8-byte sc1 record stores by
+// wave 0, drained, one arrival; one lane polls; workgroup barrier; sc1 loads), keep their 128 x N outputs in
 // registers meanwhile, and store the ACTIVATION: the raw tensor (16.8 MB at cfg4) is never written or re-read and the
 // gn_apply_parts_kernel launch behind this kernel disappears (14.6 + 10.1 us -> one launch).  N = 128 only (two channel blocks per wave).
 template <int CIN, bool FUSE = false>
@@ -243,58 +242,23 @@ __global__ __launch_bounds__(512) void conv_first_kernel(const FirstParams p) {
         if constexpr (FUSE) {
             int* gave_up = reinterpret_cast<int*>(bl);       // the bias is consumed: its first word carries this workgroup's give-up flag
             unsigned* cnt = p.cl_cnt + (size_t)bimg * 8 * 16;
-            if (tid < p.groups) {
-                const unsigned long long bits = (unsigned long long)__float_as_uint(gmean) | ((unsigned long long)__float_as_uint(gm2) << 32);
-                __hip_atomic_store(p.cl_rec + (size_t)blockIdx.x * 16 + tid, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            if (tid < p.groups) cl_store_stats(p.cl_rec + (size_t)blockIdx.x * 16 + tid, gmean, gm2);
             if (wave == 0) {              // every record was stored by this wave (groups <= 64): drain, ONE arrival, one lane polls
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 if (lane == 0) {
                     *gave_up = 0;
                     __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned)p.tpi) {
-                        const unsigned long long t_begin = __builtin_amdgcn_s_memrealtime();
-                        for (;;) {
-                            __builtin_amdgcn_s_sleep(2);
-                            if (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= (unsigned)p.tpi) break;
-                            if (__builtin_amdgcn_s_memrealtime() - t_begin > FIRST_TIMEOUT_TICKS) {
-                                if (p.cl_fail) __hip_atomic_fetch_add(p.cl_fail, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                *gave_up = 1;
-                                break;
-                            }
-                        }
-                    }
+                    if (cl_wait_ge<2>(cnt, (unsigned)p.tpi, p.cl_fail)) *gave_up = 1;
                 }
             }
             __syncthreads();
             if (tid < p.groups) {
-                // the image's tiles of this group, equal counts: mean of means, M2 = sum M2_i + n_i sum (mean_i - mean)^2
-                const unsigned long long* r0 = p.cl_rec + (size_t)bimg * p.tpi * 16 + tid;
-                float rm[8], rq[8], ms = 0.f;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    rm[i] = rq[i] = 0.f;
-                    if (i < p.tpi) {
-                        const unsigned long long bits = __hip_atomic_load(r0 + (size_t)i * 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        rm[i] = __uint_as_float((unsigned)bits);
-                        rq[i] = __uint_as_float((unsigned)(bits >> 32));
-                        ms += rm[i];
-                    }
-                }
-                const float mean = *gave_up ? __builtin_nanf("") : ms / (float)p.tpi;
-                float m2 = 0.f, d2 = 0.f;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) if (i < p.tpi) { m2 += rq[i]; d2 += (rm[i] - mean) * (rm[i] - mean); }
-                const float n_i = 128.0f * (float)p.cpg;
-                ts[tid] = make_float2(mean, 1.0f / sqrtf((m2 + n_i * d2) / ((float)p.tpi * n_i) + p.eps));
+                // the image's tiles of this group
+                float rm[8], rq[8];
+                cl_load_stats(p.cl_rec + (size_t)bimg * p.tpi * 16 + tid, 16, p.tpi, rm, rq);
+                ts[tid] = cl_merge_stats(rm, rq, p.tpi, 128.0f * (float)p.cpg, p.eps, *gave_up != 0);
             }
-            if (tid == 0) {               // departure: the last one out re-arms the image's counters for the next launch
-                const unsigned old = __hip_atomic_fetch_add(cnt + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (old == (unsigned)p.tpi - 1u) {
-                    __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(cnt + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
+            if (tid == 0) cl_depart(cnt, cnt + 1, (unsigned)p.tpi);
             __syncthreads();
             const float* trow = nullptr;
             if (p.temb) trow = p.temb + (p.counter ? (long long)t_step : p.temb_rows ? p.temb_rows[bimg] : (long long)bimg) * p.temb_stride;
@@ -400,6 +364,8 @@ int conv_first(const float* x, const float* wp, const float* bias, float* out, f
     }
     return check_launch("conv_first_kernel");
 }
+
+unsigned conv_first_cluster_timeouts() { return cl_timeouts_read(); }
 
 }  // namespace ddk
 

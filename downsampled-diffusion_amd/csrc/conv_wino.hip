@@ -31,6 +31,7 @@
 #include <type_traits>
 #include <utility>
 
+#include "cluster_sync.h"
 #include "conv_common.h"
 #include "pack_elems.h"
 
@@ -142,9 +143,6 @@ __device__ __forceinline__ float4 f4sub(float4 a, float4 b) { return make_float4
 // Diagnostic stamps (DBG = 1, tuning build only): per workgroup {entry, loop start, loop end, end} in 100 MHz ticks and the
 // matrix wave's cycles spent waiting at the stage barriers vs multiplying; written to a buffer nothing else reads.
 __device__ unsigned long long g_wino_stamps[8 * 1024];
-
-__device__ unsigned g_wino_cl_timeouts;       // workgroups that gave up waiting for their cluster (must stay 0; see ddk_debug_cluster_timeouts)
-constexpr unsigned long long CL_TIMEOUT_TICKS = 2000000ull;   // 20 ms of the 100 MHz s_memrealtime clock: a peer is normally < 0.1 ms away
 
 template <int DBG, bool CL = false>
 __global__ __launch_bounds__(512) void conv3x3_wino_kernel(const WinoParams p) {
@@ -499,24 +497,14 @@ __global__ __launch_bounds__(512) void conv3x3_wino_kernel(const WinoParams p) {
         if (!CL) {
             if (tid < 16 && (cq & (qpg - 1)) == 0) p.gn_part[(long long)tile_m * p.groups + n0 / p.cpg + gl] = make_float2(mean, m2);
         } else {
-            // ---- cluster exchange (MI355X_MICROARCH.md, "Valid forms", first row of the sc1 table): every record byte is stored
-            // sc1 by wave 0, which drains its stores (vmcnt(0)) before its lane 0 adds to the cluster's arrival counter (agent
-            // scope); lane 0 polls the counter with sc1 loads, the other waves pass a workgroup barrier behind it, and every record
-            // is read with sc1 loads: row 1 of that table (one lane signals for the workgroup's 8-byte sc1 stores, sc1 poll, the
-            // other waves behind a workgroup barrier, 8-byte sc1 loads, hipMalloc memory, ONE workgroup per CU -- 144 KB of LDS).
-            // Measured form, not an architectural guarantee; a record has its 128-byte line to itself.  The workgroups of a
-            // cluster have consecutive launch indices inside one XCD's run, so they are co-resident whenever the dispatcher works
-            // in order on a whole, otherwise idle device (conv_wino_cluster_device_ok gates on that); the wait is bounded by wall
-            // time anyway, and a give-up is never silent: NaN output + sticky counters (ddk_unet_cluster_check).
+            // ---- cluster exchange (cluster_sync.h): wave 0 stores the records sc1, drains them and makes the one arrival; lane 0
+            // polls, the other waves wait at the barrier behind it (one workgroup per CU: 144 KB of LDS)
             const int image = tile_m / p.cl_np;
             unsigned long long* rec = reinterpret_cast<unsigned long long*>(p.cl_rec) + ((long long)tile_m * gridDim.y + tile_n) * 16;
             unsigned* cnt = p.cl_cnt + ((long long)image * gridDim.y + tile_n) * 16;
             int* gave_up = reinterpret_cast<int*>(red + 256);       // LDS word: this workgroup's wait timed out
             if (tid == 0) *gave_up = 0;                             // ordered before its readers by the barrier below
-            if (tid < 16 && (cq & (qpg - 1)) == 0) {
-                const unsigned long long bits = (unsigned long long)__float_as_uint(mean) | ((unsigned long long)__float_as_uint(m2) << 32);
-                __hip_atomic_store(rec + gl, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            if (tid < 16 && (cq & (qpg - 1)) == 0) cl_store_stats(rec + gl, mean, m2);
             // what the finish needs from memory besides the records is requested BEFORE the wait (waves 1..7; wave 0 right behind
             // its counter add): affine and time shift of this thread's channel quad
             const int gn = n0 + (tid & 15) * 4;
@@ -560,22 +548,8 @@ __global__ __launch_bounds__(512) void conv3x3_wino_kernel(const WinoParams p) {
                 if (lane == 0) __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 load_affine();
                 load_resid();
-                if (lane == 0 && __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned)p.cl_np) {
-                    // peers not all here yet: poll, bounded by WALL time (co-residency of a cluster is an assumption about the
-                    // dispatcher, not a guarantee: a foreign kernel, a CU mask or a partitioned device breaks it).  A give-up is
-                    // sticky and loud: the counters below make ddk_unet_cluster_check() fail and this tile's output is NaN.
-                    const unsigned long long t_begin = __builtin_amdgcn_s_memrealtime();
-                    for (;;) {
-                        __builtin_amdgcn_s_sleep(4);
-                        if (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= (unsigned)p.cl_np) break;
-                        if (__builtin_amdgcn_s_memrealtime() - t_begin > CL_TIMEOUT_TICKS) {
-                            atomicAdd(&g_wino_cl_timeouts, 1u);
-                            if (p.cl_fail) __hip_atomic_fetch_add(p.cl_fail, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            *gave_up = 1;
-                            break;
-                        }
-                    }
-                }
+                // a give-up is sticky and loud: ddk_unet_cluster_check() fails and this tile's output is NaN
+                if (lane == 0 && cl_wait_ge<4>(cnt, (unsigned)p.cl_np, p.cl_fail)) *gave_up = 1;
             }
             __syncthreads();
             // the image's statistics: the np records of this thread's group merged in tile order (the arithmetic of
@@ -584,31 +558,10 @@ __global__ __launch_bounds__(512) void conv3x3_wino_kernel(const WinoParams p) {
                                            ((long long)image * p.cl_np * gridDim.y + tile_n) * 16 + gl;
             const bool poisoned = *gave_up != 0;
             float rm[8], rq[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                rm[i] = 0.f; rq[i] = 0.f;
-                if (i < p.cl_np) {
-                    const unsigned long long bits = __hip_atomic_load(r0 + (long long)i * gridDim.y * 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    rm[i] = __uint_as_float((unsigned)bits);
-                    rq[i] = __uint_as_float((unsigned)(bits >> 32));
-                }
-            }
-            if (tid == 0) {          // departure: the last one out re-arms the counters for the next launch
-                const unsigned old = __hip_atomic_fetch_add(cnt + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (old == (unsigned)p.cl_np - 1u) {
-                    __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(cnt + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-            float ms = 0.f;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) if (i < p.cl_np) ms += rm[i];
-            const float gmean = poisoned ? __builtin_nanf("") : ms / (float)p.cl_np;
-            float gm2 = 0.f, gd2 = 0.f;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) if (i < p.cl_np) { gm2 += rq[i]; gd2 += (rm[i] - gmean) * (rm[i] - gmean); }
-            const float n_i = 128.0f * (float)p.cpg;
-            const float rstd = 1.0f / sqrtf((gm2 + n_i * gd2) / ((float)p.cl_np * n_i) + p.gn_eps);
+            cl_load_stats(r0, (long long)gridDim.y * 16, p.cl_np, rm, rq);
+            if (tid == 0) cl_depart(cnt, cnt + 1, (unsigned)p.cl_np);
+            const float2 st = cl_merge_stats(rm, rq, p.cl_np, 128.0f * (float)p.cpg, p.gn_eps, poisoned);
+            const float gmean = st.x, rstd = st.y;
             auto fin = [&](float4 v) {
                 return make_float4(mish_f((v.x - gmean) * rstd * ga.x + be.x) + ts.x, mish_f((v.y - gmean) * rstd * ga.y + be.y) + ts.y,
                                    mish_f((v.z - gmean) * rstd * ga.z + be.z) + ts.z, mish_f((v.w - gmean) * rstd * ga.w + be.w) + ts.w);
@@ -916,10 +869,16 @@ __global__ __launch_bounds__(256) void occupy_kernel(unsigned long long ticks, u
     if (occupy_lds[(threadIdx.x + 1) & 255] < 0.f && sink) *sink = 1;
 }
 
-unsigned conv_wino_cluster_timeouts() {
+unsigned conv_wino_cluster_timeouts() { return cl_timeouts_read(); }
+
+int cluster_fail_check(unsigned* word, hipStream_t st, const char* who, const char* tail) {
     unsigned v = 0;
-    if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_wino_cl_timeouts), sizeof(v)) != hipSuccess) return ~0u;
-    return v;
+    DDK_HIP(hipMemcpyAsync(&v, word, sizeof(v), hipMemcpyDeviceToHost, st));
+    DDK_HIP(hipStreamSynchronize(st));
+    if (v == 0) return DDK_OK;
+    DDK_HIP(hipMemsetAsync(word, 0, sizeof(v), st));
+    set_error("%s: %u workgroup(s) gave up waiting for their cluster%s", who, v, tail);
+    return DDK_ERR_CLUSTER;
 }
 
 }  // namespace ddk
@@ -1005,14 +964,8 @@ extern "C" size_t ddk_conv3x3_gn_mish_cluster_split_workspace_bytes(int B, int H
 extern "C" int ddk_conv3x3_gn_mish_cluster_check(void* workspace, int B, ddk_stream_t s) {
     using namespace ddk;
     DDK_REQUIRE(workspace && B > 0, "conv3x3_gn_mish_cluster_check: arguments");
-    unsigned* word = reinterpret_cast<unsigned*>(static_cast<float*>(workspace) + (size_t)B * 8 * 16);
-    unsigned v = 0;
-    DDK_HIP(hipMemcpyAsync(&v, word, sizeof(v), hipMemcpyDeviceToHost, as_stream(s)));
-    DDK_HIP(hipStreamSynchronize(as_stream(s)));
-    if (v == 0) return DDK_OK;
-    DDK_HIP(hipMemsetAsync(word, 0, sizeof(v), as_stream(s)));
-    set_error("conv3x3_gn_mish_cluster: %u workgroup(s) gave up waiting for their cluster; the output is invalid (NaN tiles)", v);
-    return DDK_ERR_CLUSTER;
+    return cluster_fail_check(cl_words(static_cast<float*>(workspace), B).fail, as_stream(s), "conv3x3_gn_mish_cluster",
+                              "; the output is invalid (NaN tiles)");
 }
 
 extern "C" int ddk_debug_occupy(int workgroups, int lds_bytes, int microseconds, ddk_stream_t s) {
@@ -1050,8 +1003,8 @@ extern "C" int ddk_conv3x3_gn_mish_cluster(const float* src0, int c0, const floa
     a.resid = addend;
     a.out = out;
     a.B = B; a.H = H; a.W = W; a.N = N;
-    WinoGnFuse f{gamma, beta, temb, nullptr, temb_stride, eps, groups, ws + (size_t)B * 8 * 16 + 16, reinterpret_cast<unsigned*>(ws),
-                 reinterpret_cast<unsigned*>(ws + (size_t)B * 8 * 16)};
+    const ClWords w = cl_words(ws, B);
+    WinoGnFuse f{gamma, beta, temb, nullptr, temb_stride, eps, groups, ws + (size_t)B * 8 * 16 + 16, w.counters, w.fail};
     if (split_bytes) {
         f.pairs = reinterpret_cast<unsigned*>(pairs);
         a.workspace = pairs + conv_wino_cluster_pair_words(B, H, W, N);

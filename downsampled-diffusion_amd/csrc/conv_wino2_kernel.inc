@@ -501,19 +501,7 @@ __global__ __launch_bounds__(768) void conv3x3_wino2_kernel(const WinoParams p) 
         if (tid == 0) {
             *pair_gave_up = 0;
             const unsigned want = (unsigned)p.splits - 1u;
-            if (__hip_atomic_load(pair, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) {
-                const unsigned long long t_begin = __builtin_amdgcn_s_memrealtime();
-                for (;;) {
-                    __builtin_amdgcn_s_sleep(2);
-                    if (__hip_atomic_load(pair, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= want) break;
-                    if (__builtin_amdgcn_s_memrealtime() - t_begin > CL_TIMEOUT_TICKS) {
-                        atomicAdd(&g_wino_cl_timeouts, 1u);
-                        if (p.cl_fail) __hip_atomic_fetch_add(p.cl_fail, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        *pair_gave_up = 1;
-                        break;
-                    }
-                }
-            }
+            if (cl_wait_ge<2>(pair, want, p.cl_fail)) *pair_gave_up = 1;
             __hip_atomic_store(pair, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // its only reader: re-armed for the next launch
         }
         __syncthreads();                 // (also: every thread is done with the staging area the partial tiles came from)
@@ -570,16 +558,13 @@ __global__ __launch_bounds__(768) void conv3x3_wino2_kernel(const WinoParams p) 
         if (!CL) {
             if (tid < QUADS && (cq & (qpg - 1)) == 0) p.gn_part[(long long)tile_m * p.groups + n0 / p.cpg + gl] = make_float2(mean, m2);
         } else {
-            // ---- cluster exchange: see the kernel above (row 1 of the guide's sc1 table; one workgroup per CU: >= 120 KB of LDS)
+            // ---- cluster exchange (cluster_sync.h), as in the kernel above (one workgroup per CU: >= 120 KB of LDS)
             const int image = tile_m / p.cl_np;
             unsigned long long* rec = reinterpret_cast<unsigned long long*>(p.cl_rec) + ((long long)tile_m * gridDim.y + tile_n) * 16;
             unsigned* cnt = p.cl_cnt + ((long long)image * gridDim.y + tile_n) * 16;
             int* gave_up = reinterpret_cast<int*>(red + 256);
             if (tid == 0) *gave_up = 0;
-            if (tid < QUADS && (cq & (qpg - 1)) == 0) {
-                const unsigned long long bits = (unsigned long long)__float_as_uint(mean) | ((unsigned long long)__float_as_uint(m2) << 32);
-                __hip_atomic_store(rec + gl, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            if (tid < QUADS && (cq & (qpg - 1)) == 0) cl_store_stats(rec + gl, mean, m2);
             float4 ga, be, ts = make_float4(0.f, 0.f, 0.f, 0.f);
             auto load_affine = [&] {
                 ga = *reinterpret_cast<const float4*>(p.gn_gamma + gn);
@@ -652,50 +637,17 @@ __global__ __launch_bounds__(768) void conv3x3_wino2_kernel(const WinoParams p) 
                 if (lane == 0) __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 load_affine();
                 load_resid();
-                if (lane == 0 && __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned)p.cl_np) {
-                    const unsigned long long t_begin = __builtin_amdgcn_s_memrealtime();
-                    for (;;) {
-                        __builtin_amdgcn_s_sleep(4);
-                        if (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= (unsigned)p.cl_np) break;
-                        if (__builtin_amdgcn_s_memrealtime() - t_begin > CL_TIMEOUT_TICKS) {
-                            atomicAdd(&g_wino_cl_timeouts, 1u);
-                            if (p.cl_fail) __hip_atomic_fetch_add(p.cl_fail, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            *gave_up = 1;
-                            break;
-                        }
-                    }
-                }
+                if (lane == 0 && cl_wait_ge<4>(cnt, (unsigned)p.cl_np, p.cl_fail)) *gave_up = 1;
             }
             __syncthreads();
             const unsigned long long* r0 = reinterpret_cast<const unsigned long long*>(p.cl_rec) +
                                            ((long long)image * p.cl_np * gridDim.y + tile_n) * 16 + gl;
             const bool poisoned = *gave_up != 0;
             float rm[8], rq[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                rm[i] = 0.f; rq[i] = 0.f;
-                if (i < p.cl_np) {
-                    const unsigned long long bits = __hip_atomic_load(r0 + (long long)i * gridDim.y * 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    rm[i] = __uint_as_float((unsigned)bits);
-                    rq[i] = __uint_as_float((unsigned)(bits >> 32));
-                }
-            }
-            if (tid == 0) {          // departure: the last one out re-arms the counters for the next launch
-                const unsigned old = __hip_atomic_fetch_add(cnt + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (old == (unsigned)p.cl_np - 1u) {
-                    __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(cnt + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-            float ms = 0.f;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) if (i < p.cl_np) ms += rm[i];
-            const float gmean = poisoned ? __builtin_nanf("") : ms / (float)p.cl_np;
-            float gm2 = 0.f, gd2 = 0.f;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) if (i < p.cl_np) { gm2 += rq[i]; gd2 += (rm[i] - gmean) * (rm[i] - gmean); }
-            const float n_i = 128.0f * (float)p.cpg;
-            const float rstd = 1.0f / sqrtf((gm2 + n_i * gd2) / ((float)p.cl_np * n_i) + p.gn_eps);
+            cl_load_stats(r0, (long long)gridDim.y * 16, p.cl_np, rm, rq);
+            if (tid == 0) cl_depart(cnt, cnt + 1, (unsigned)p.cl_np);
+            const float2 st = cl_merge_stats(rm, rq, p.cl_np, 128.0f * (float)p.cpg, p.gn_eps, poisoned);
+            const float gmean = st.x, rstd = st.y;
             auto fin = [&](float4 v) {
                 return make_float4(mish_f((v.x - gmean) * rstd * ga.x + be.x) + ts.x, mish_f((v.y - gmean) * rstd * ga.y + be.y) + ts.y,
                                    mish_f((v.z - gmean) * rstd * ga.z + be.z) + ts.z, mish_f((v.w - gmean) * rstd * ga.w + be.w) + ts.w);

@@ -176,7 +176,17 @@ size_t conv_wino_cluster_pair_words(int B, int H, int W, int N);
 bool conv_wino_variant_new(int B, int H, int W, int N);   // the shape runs on the 8-matrix-wave kernels (they carry the 1x1 addend)
 bool conv_wino_cluster_device_ok();     // a whole MI355X (256 CUs, 8 XCDs, no CU mask): the only place a cluster is co-resident
 size_t conv_wino_cluster_ws_floats(int B, int H, int W, int N);
+// workgroups of each code object's in-launch exchanges that gave up waiting (cluster_sync.h; ~0u: unreadable)
 unsigned conv_wino_cluster_timeouts();
+unsigned conv_first_cluster_timeouts();
+unsigned level_chain_cluster_timeouts();
+// the words of a cluster region `cl` (a plan's, or the front of a ddk_conv3x3_gn_mish_cluster workspace): [B][8 * 16] counters,
+// then the sticky give-up word on a line of its own
+struct ClWords { unsigned* counters; unsigned* fail; };
+inline ClWords cl_words(float* cl, int B) { return {reinterpret_cast<unsigned*>(cl), reinterpret_cast<unsigned*>(cl + (size_t)B * 8 * 16)}; }
+// waits for `st`, then reads and clears a workspace's sticky give-up word: DDK_OK, or DDK_ERR_CLUSTER with the error
+// "<who>: <n> workgroup(s) gave up waiting for their cluster<tail>"
+int cluster_fail_check(unsigned* word, hipStream_t st, const char* who, const char* tail);
 // transpose conv 4x4 stride 2 as Winograd F(2x2, 2x2) per output phase (weight_wino = ddk_pack_convT_weight_wino)
 bool convT_wino_ok(int H, int W, int cin, int N);
 int convT_wino_splits(int B, int H, int W, int cin, int N);

@@ -19,6 +19,7 @@
 // grid are resident at once on a whole, otherwise idle MI355X (<= 256 workgroups, one per CU: 96 KB of LDS); the waits are bounded
 // by wall time anyway, a give-up moves the caller's sticky fail word (ddk_unet_cluster_check) and is never silent.
 #include "level_chain.h"
+#include "cluster_sync.h"
 #include "conv_common.h"
 
 #include <atomic>
@@ -117,21 +118,7 @@ struct ChainCtx {
 // every arrival of the image so far (8 per signalling op); bounded: 20 ms of wall time, then this workgroup stops waiting for good
 __device__ __forceinline__ void chain_wait(const ChainParams& p, ChainCtx& c) {
     int* dead = reinterpret_cast<int*>(c.misc);
-    if (c.tid == 0 && !*dead) {
-        const unsigned need = 8u * c.signals;
-        unsigned* cnt = p.cnt + c.b * 32;
-        if (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need) {
-            const long long t0 = __builtin_amdgcn_s_memrealtime();
-            while (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need) {
-                __builtin_amdgcn_s_sleep(1);
-                if (__builtin_amdgcn_s_memrealtime() - t0 > 2000000LL) {       // 100 MHz ticks
-                    *dead = 1;
-                    atomicAdd(p.fail, 1u);
-                    break;
-                }
-            }
-        }
-    }
+    if (c.tid == 0 && !*dead && cl_wait_ge<1>(p.cnt + c.b * 32, 8u * c.signals, p.fail)) *dead = 1;
     __syncthreads();
 }
 
@@ -703,13 +690,7 @@ __global__ __launch_bounds__(512) void level_chain_kernel(const ChainParams p) {
         }
         // the image's last departure re-arms its counters for the next launch: every one of the eight has passed its last wait
         __syncthreads();              // (every wave has left the last op)
-        if (c.tid == 0) {
-            const unsigned prev = __hip_atomic_fetch_add(p.done + b * 32, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (prev == 7u) {
-                __hip_atomic_store(p.cnt + b * 32, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(p.done + b * 32, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
+        if (c.tid == 0) cl_depart(p.cnt + b * 32, p.done + b * 32, 8u);
     }
 }
 
@@ -1264,17 +1245,12 @@ __global__ __launch_bounds__(1024) void level8_chain_kernel(const ChainParams p)
             else c8_conv3(p, o, c, kp);
         }
         __syncthreads();
-        if (c.tid == 0) {
-            const unsigned prev = __hip_atomic_fetch_add(p.done + b * 32, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (prev == 7u) {
-                __hip_atomic_store(p.cnt + b * 32, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(p.done + b * 32, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
+        if (c.tid == 0) cl_depart(p.cnt + b * 32, p.done + b * 32, 8u);
     }
 }
 
 bool level_chain_device_ok() { return conv_wino_cluster_device_ok(); }
+unsigned level_chain_cluster_timeouts() { return cl_timeouts_read(); }
 
 int level_chain_init_device() {
     DDK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(level_chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));

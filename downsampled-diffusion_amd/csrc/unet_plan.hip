@@ -510,7 +510,14 @@ extern "C" int ddk_unet_set_option(ddk_unet* u, int option, int value) {
     }
     return fail_arg("unet_set_option: unknown option");
 }
-extern "C" unsigned ddk_debug_cluster_timeouts(void) { return ddk::conv_wino_cluster_timeouts(); }
+extern "C" unsigned ddk_debug_cluster_timeouts(void) {
+    unsigned sum = 0;
+    for (unsigned v : {ddk::conv_wino_cluster_timeouts(), ddk::conv_first_cluster_timeouts(), ddk::level_chain_cluster_timeouts()}) {
+        if (v == ~0u) return ~0u;
+        sum += v;
+    }
+    return sum;
+}
 extern "C" int ddk_unet_num_slots(const ddk_unet* u) { return u ? (int)u->slots.size() : 0; }
 extern "C" const char* ddk_unet_slot_name(const ddk_unet* u, int slot) {
     return (u && slot >= 0 && slot < (int)u->slots.size()) ? u->slots[slot].name.c_str() : nullptr;
@@ -642,7 +649,6 @@ static size_t conv3_ws_floats(const ConvW& cw, int B, int H, int W, int cin, int
 // ... and the pair counters of the channel-chunk-split in-launch GroupNorm: <= 128 (m tile, n tile) pairs (256 workgroups, >= 2 splits)
 constexpr size_t CL_PAIR_WORDS = 128 * 16;
 static size_t cl_counter_floats(int B) { return (size_t)B * 8 * 16 + 16 + (size_t)B * 64 + CL_PAIR_WORDS; }
-static size_t cl_fail_offset(int B) { return (size_t)B * 8 * 16; }
 static size_t cl_chain_offset(int B) { return (size_t)B * 8 * 16 + 16; }
 static size_t cl_pair_offset(int B) { return (size_t)B * 8 * 16 + 16 + (size_t)B * 64; }
 constexpr int CHAIN_BUFS = 18;                // activations that cross workgroups inside the level chain, [B][16][256] each
@@ -840,8 +846,8 @@ static int run_conv_gn(Ctx& c, const ConvW& cw, const float* src0, int c0, const
         a.out = out;
         a.B = c.B; a.H = H; a.W = W; a.N = N;
         float* cl = c.W + c.ly.off_cl;
-        const WinoGnFuse f{c.P + n.g, c.P + n.b, temb, c.temb_rows, c.u.temb_total, GN_EPS, GROUPS, cl + cl_counter_floats(c.B),
-                           reinterpret_cast<unsigned*>(cl), reinterpret_cast<unsigned*>(cl + cl_fail_offset(c.B))};
+        const ClWords w = cl_words(cl, c.B);
+        const WinoGnFuse f{c.P + n.g, c.P + n.b, temb, c.temb_rows, c.u.temb_total, GN_EPS, GROUPS, cl + cl_counter_floats(c.B), w.counters, w.fail};
         return conv_forward(a, c.st, nullptr, &f);
     }
     int cls_splits = 1;
@@ -863,8 +869,8 @@ static int run_conv_gn(Ctx& c, const ConvW& cw, const float* src0, int c0, const
         a.workspace = c.W + c.ly.off_splitk;
         a.workspace_bytes = c.ly.splitk * sizeof(float);
         float* cl = c.W + c.ly.off_cl;
-        WinoGnFuse f{c.P + n.g, c.P + n.b, temb, c.temb_rows, c.u.temb_total, GN_EPS, GROUPS, cl + cl_counter_floats(c.B),
-                     reinterpret_cast<unsigned*>(cl), reinterpret_cast<unsigned*>(cl + cl_fail_offset(c.B))};
+        const ClWords w = cl_words(cl, c.B);
+        WinoGnFuse f{c.P + n.g, c.P + n.b, temb, c.temb_rows, c.u.temb_total, GN_EPS, GROUPS, cl + cl_counter_floats(c.B), w.counters, w.fail};
         f.pairs = reinterpret_cast<unsigned*>(cl + cl_pair_offset(c.B));
         return conv_forward(a, c.st, nullptr, &f);
     }
@@ -1149,7 +1155,7 @@ static int run_level_chain(Ctx& c, int part, const float* in, float* skip, float
     float* cl = c.W + c.ly.off_cl;
     p.cnt = reinterpret_cast<unsigned*>(cl + cl_chain_offset(c.B));
     p.done = p.cnt + (size_t)c.B * 32;
-    p.fail = reinterpret_cast<unsigned*>(cl + cl_fail_offset(c.B));
+    p.fail = cl_words(cl, c.B).fail;
     p.gn_eps = GN_EPS;
     p.ln_eps = LN_EPS;
     return level_chain_launch(p, c.st);
@@ -1271,9 +1277,10 @@ static int forward_core(const ddk_unet& u, const float* P, const float* x, int64
                 // round 6: the first Block's GroupNorm + Mish + shift inside the conv's launch (the image's 8 tiles exchange their statistics):
                 // no raw tensor, no GroupNorm-apply launch
                 float* cl = ws + ly.off_cl;
+                const ClWords w = cl_words(cl, B);
                 DDK_TRY(conv_first_gn(x, P + r.c1.wf, r.c1.has_bias ? P + r.c1.b : nullptr, P + r.n1.g, P + r.n1.b, c.temb + r.temb_off,
                                       u.temb_total, c.temb_rows, GN_EPS, a1, B, H, W, r.ci, r.co, GROUPS, cl + cl_counter_floats(B),
-                                      reinterpret_cast<unsigned*>(cl), reinterpret_cast<unsigned*>(cl + cl_fail_offset(B)),
+                                      w.counters, w.fail,
                                       step ? step->state : nullptr, step ? t : nullptr, st));
             } else {
                 DDK_TRY(conv_first(x, P + r.c1.wf, r.c1.has_bias ? P + r.c1.b : nullptr, raw, gnp, B, H, W, r.ci, r.co, GROUPS,
@@ -1294,8 +1301,8 @@ static int forward_core(const ddk_unet& u, const float* P, const float* x, int64
                 // tile statistics; the epilogue evaluates the <= 8-channel 1x1 itself): no raw tensor, no GroupNorm-apply launch
                 a.out = bufB;
                 float* cl = ws + ly.off_cl;
-                WinoGnFuse f{P + r.n2.g, P + r.n2.b, nullptr, nullptr, u.temb_total, GN_EPS, GROUPS, cl + cl_counter_floats(B),
-                             reinterpret_cast<unsigned*>(cl), reinterpret_cast<unsigned*>(cl + cl_fail_offset(B))};
+                const ClWords w = cl_words(cl, B);
+                WinoGnFuse f{P + r.n2.g, P + r.n2.b, nullptr, nullptr, u.temb_total, GN_EPS, GROUPS, cl + cl_counter_floats(B), w.counters, w.fail};
                 f.res_x = x; f.res_w = P + r.res.w; f.res_b = r.res.has_bias ? P + r.res.b : nullptr; f.res_cin = r.ci; f.res_ld = r.res.cin_pad;
                 DDK_TRY(conv_forward(a, st, nullptr, &f));
             } else {
@@ -1456,15 +1463,9 @@ extern "C" int ddk_unet_cluster_check(const ddk_unet* u, void* workspace, int B,
     DDK_TRY(check_shape(u, B, H, W));
     DDK_REQUIRE(workspace, "unet_cluster_check: null workspace");
     const Layout ly = make_layout(*u, B, H, W);
-    unsigned* word = reinterpret_cast<unsigned*>(static_cast<float*>(workspace) + ly.off_cl + cl_fail_offset(B));
-    unsigned v = 0;
-    DDK_HIP(hipMemcpyAsync(&v, word, sizeof(v), hipMemcpyDeviceToHost, as_stream(s)));
-    DDK_HIP(hipStreamSynchronize(as_stream(s)));
-    if (v == 0) return DDK_OK;
-    DDK_HIP(hipMemsetAsync(word, 0, sizeof(v), as_stream(s)));
-    set_error("in-launch GroupNorm: %u workgroup(s) gave up waiting for their cluster (the GPU is shared, masked or partitioned); "
-              "results on this workspace are invalid -- rerun with DDK_OPT_CLUSTER_GROUPNORM = 0", v);
-    return DDK_ERR_CLUSTER;
+    return cluster_fail_check(cl_words(static_cast<float*>(workspace) + ly.off_cl, B).fail, as_stream(s), "in-launch GroupNorm",
+                              " (the GPU is shared, masked or partitioned); results on this workspace are invalid -- rerun with "
+                              "DDK_OPT_CLUSTER_GROUPNORM = 0");
 }
 
 extern "C" double ddk_unet_flops(const ddk_unet* u, int B, int H0, int W0) {
