@@ -301,7 +301,29 @@ int p_sample_update(float* x, const float* eps_hat, const float* noise, long lon
                     const int64_t* chain_state = nullptr, int64_t* dec_counter = nullptr);
 int randn(float* out, long long n, uint64_t seed, uint32_t step, uint32_t stream_id, hipStream_t st);
 // GroupNorm (from conv partials) + Mish + 1x1 projection to n_out <= 8 channels (+ the reverse-step update of x) in one launch
+// likelihood sweep (diffusion.hip, ddk_vlb_sweep_run): one step's operands besides the UNet's
+struct VlbStep {
+    const float* x;               // clean sample, NHWC [B][H][W][n_out]
+    float* xt;                    // q_sample(x, t, eps), the forward's input
+    const float* noise;           // [T][B][H][W][n_out] (draw k at t = t_first - k) or null: Philox on the chain state's key
+    long long noise_step_stride;
+    int t_first;
+    const float *c_recip, *c_recipm1, *c1, *c2, *logvar;
+    float* partials;              // float2 [T][B][nslot]
+    int nslot;                    // tiles of the fused tail, or vlb_sweep_slots_unfused()
+};
+constexpr uint32_t VLB_STREAM_BIT = 0x80000000u;   // Philox stream ids of the sweep: stream_id | this (never the sampler's)
+int vlb_sweep_slots_unfused(int B, long long per);
+int vlb_step_input(const VlbStep& v, const float* sqrt_acp, const float* sqrt_1m_acp, const int64_t* chain_state, int B, long long per,
+                   hipStream_t st);
+int vlb_sweep_terms(const VlbStep& v, const int64_t* t, const float* eps_hat, int B, long long per, const int64_t* chain_state,
+                    hipStream_t st, int64_t* dec_counter);
+int vlb_sweep_finalize(const float* partials, int nslot, float* vlb_t, float* l_simple_t, int T, int B, long long per, hipStream_t st);
+int final_tail_vlb(const float* raw, const float* part, int np, const float* gamma, const float* beta, float eps, const float* w,
+                   const float* bias, int n_out, const VlbStep& v, const int64_t* t, const int64_t* chain_state, int B, int HW, int C,
+                   int groups, hipStream_t st, int64_t* dec_counter);
 bool final_tail_ok(int HW, int C, int groups, int n_out, int np);
+bool final_tail_vlb_ok(int HW, int C, int groups, int n_out, int np);
 int final_tail(const float* raw, const float* part, int np, const float* gamma, const float* beta, float eps, const float* w,
                const float* bias, int n_out, float* eps_out, float* x, const float* noise, long long noise_step_stride, int t_first,
                const int64_t* t, const float* c_recip, const float* c_recipm1, const float* c1, const float* c2, const float* sigma,

@@ -117,6 +117,46 @@ __global__ __launch_bounds__(256) void p_sample_kernel(float* __restrict__ x, co
     }
 }
 
+// ---- the VLB term of one element (reference models/diffusion/ddpm.py:317-366, models/utils/losses.py:17-109) --------------------
+// Shared by vlb_terms_kernel and the likelihood sweep's epilogues (final_tail_kernel<.., true>, vlb_sweep_terms_kernel).
+__device__ __forceinline__ float std_normal_cdf_approx(float v) {
+    return 0.5f * (1.0f + tanhf(0.7978845608028654f * (v + 0.044715f * (v * v * v))));      // sqrt(2/pi)
+}
+
+struct VlbCoef {
+    float cr, crm1, a1, a2, inv_var, inv_std, kl0;
+    bool t0;
+};
+
+__device__ __forceinline__ VlbCoef vlb_coef(int64_t tb, const float* c_recip, const float* c_recipm1, const float* c1, const float* c2,
+                                            const float* logvar) {
+    VlbCoef k;
+    const float lv = logvar[tb];
+    k.cr = c_recip[tb]; k.crm1 = c_recipm1[tb]; k.a1 = c1[tb]; k.a2 = c2[tb];
+    k.inv_var = expf(-lv); k.inv_std = expf(-(0.5f * lv));
+    k.kl0 = (lv - lv - 1.0f) + expf(lv - lv);
+    k.t0 = tb == 0;
+    return k;
+}
+
+// t > 0: KL(q(x_{t-1} | x_t, x) || p(x_{t-1} | x_t)) in nats; t == 0: the discretised-Gaussian NLL of x
+__device__ __forceinline__ float vlb_elem(float xv, float xt, float eh, const VlbCoef& k) {
+    float x0 = __fsub_rn(__fmul_rn(k.cr, xt), __fmul_rn(k.crm1, eh));
+    x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    const float pred = __fadd_rn(__fmul_rn(k.a1, x0), __fmul_rn(k.a2, xt));
+    if (k.t0) {
+        const float c = xv - pred;
+        const float cdf_plus = std_normal_cdf_approx(k.inv_std * (c + 1.0f / 255.0f));
+        const float cdf_min = std_normal_cdf_approx(k.inv_std * (c - 1.0f / 255.0f));
+        const float lp = xv < -0.999f ? logf(fmaxf(cdf_plus, 1e-12f))
+                                      : (xv > 0.999f ? logf(fmaxf(1.0f - cdf_min, 1e-12f)) : logf(fmaxf(cdf_plus - cdf_min, 1e-12f)));
+        return -lp;
+    }
+    const float tm = __fadd_rn(__fmul_rn(k.a1, xv), __fmul_rn(k.a2, xt));
+    const float d = tm - pred;
+    return 0.5f * (k.kl0 + (d * d) * k.inv_var);
+}
+
 // ------------------------------------------------------------------------------------------------
 // The end of a forward in ONE launch (reference models/unet/unet.py:69-72 after the final Block's conv, blocks.py:79-80;
 // in the sampler also models/diffusion/ddpm.py:149-158,177-185,216-227): GroupNorm (statistics from the final conv's per-tile
@@ -146,9 +186,17 @@ struct TailParams {
     int np, HW, C, cpg, n_out;
     float eps;
     int64_t* dec_counter;         // the step counter, decremented HERE (the step's last kernel) when the first kernel left it alone, or null
+    // likelihood sweep (final_tail_kernel<.., true>): x is the clean sample (read only), c_recip .. c2 as above
+    const float* xt;              // q_sample(x, t, eps): what the forward ran on
+    const float* logvar;          // posterior_log_variance_clipped [T]
+    float2* vlb_part;             // [T][B][np] {sum of the VLB terms, sum of (eps - eps_hat)^2} per 128-pixel tile
+    int B;
 };
 
-template <int LPP, int VPL>
+// VLB = false: eps_hat out and / or the reverse-step update of x.  VLB = true (ddk_vlb_sweep_run): phase 2 evaluates, per element,
+// vlb_terms_kernel's term and (eps - eps_hat)^2 with eps the step-input kernel's draw (the same Philox call or injected array), and
+// the workgroup stores the two block sums to its own slot of vlb_part (plain stores, no atomics: the kernel boundary publishes them).
+template <int LPP, int VPL, bool VLB>
 __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
     constexpr int PPW = 64 / LPP;                    // pixels per wave and iteration
     constexpr int PPI = 16 * PPW;                    // ... per iteration of the 16-wave workgroup
@@ -191,14 +239,21 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
     float4 xv0 = make_float4(0.f, 0.f, 0.f, 0.f), zv0 = xv0;
     float cr = 0.f, crm1 = 0.f, a1 = 0.f, a2 = 0.f, sg = 0.f;
     int64_t tb = 0;
-    if (p.x && tid < cnt4) {
+    float4 xt0 = xv0;
+    VlbCoef kc{};
+    if ((VLB || p.x) && tid < cnt4) {
         const uint64_t seed = p.chain_state ? (uint64_t)p.chain_state[1] : p.seed;
         const uint32_t stream = p.chain_state ? (uint32_t)p.chain_state[2] : p.stream;
         tb = p.t[b];
-        cr = p.c_recip[tb]; crm1 = p.c_recipm1[tb]; a1 = p.c1[tb]; a2 = p.c2[tb];
-        sg = tb > 0 ? p.sigma[tb] : 0.0f;
+        if constexpr (VLB) {
+            kc = vlb_coef(tb, p.c_recip, p.c_recipm1, p.c1, p.c2, p.logvar);
+        } else {
+            cr = p.c_recip[tb]; crm1 = p.c_recipm1[tb]; a1 = p.c1[tb]; a2 = p.c2[tb];
+            sg = tb > 0 ? p.sigma[tb] : 0.0f;
+        }
         const long long i = e4 + tid;
         xv0 = reinterpret_cast<const float4*>(p.x)[i];
+        if constexpr (VLB) xt0 = reinterpret_cast<const float4*>(p.xt)[i];
         zv0 = p.noise ? reinterpret_cast<const float4*>(p.noise + (long long)(p.t_first - tb) * p.noise_step_stride)[i]
                       : philox_normal4((unsigned long long)i, (uint32_t)tb, stream, seed);
     }
@@ -257,6 +312,21 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
     }
     __syncthreads();
     // phase 2: the tile's 128 * n_out elements, contiguous in the NHWC latent (cnt4 <= 256: at most one float4 per thread)
+    if constexpr (VLB) {
+        __shared__ float red[32];
+        float acc = 0.f, sq = 0.f;
+        if (tid < cnt4) {
+            const float4 ev = reinterpret_cast<const float4*>(es)[tid];
+            acc = (vlb_elem(xv0.x, xt0.x, ev.x, kc) + vlb_elem(xv0.y, xt0.y, ev.y, kc)) +
+                  (vlb_elem(xv0.z, xt0.z, ev.z, kc) + vlb_elem(xv0.w, xt0.w, ev.w, kc));
+            const float d0 = zv0.x - ev.x, d1 = zv0.y - ev.y, d2 = zv0.z - ev.z, d3 = zv0.w - ev.w;
+            sq = (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+        }
+        acc = block_sum(acc, red);
+        sq = block_sum(sq, red);
+        if (tid == 0) p.vlb_part[((long long)tb * p.B + b) * p.np + tile] = make_float2(acc, sq);
+        return;
+    }
     if (tid < cnt4) {
         const float4 ev = reinterpret_cast<const float4*>(es)[tid];
         if (p.eps_out) reinterpret_cast<float4*>(p.eps_out)[e4 + tid] = ev;
@@ -270,6 +340,20 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
         }
     }
 }
+
+template <bool VLB>
+static int launch_tail(const TailParams& p, int B, hipStream_t st) {
+    const dim3 grid((unsigned)(B * p.np));
+    if (p.C == 32) hipLaunchKernelGGL((final_tail_kernel<8, 1, VLB>), grid, dim3(1024), 0, st, p);
+    else if (p.C == 64) hipLaunchKernelGGL((final_tail_kernel<16, 1, VLB>), grid, dim3(1024), 0, st, p);
+    else if (p.C == 128) hipLaunchKernelGGL((final_tail_kernel<32, 1, VLB>), grid, dim3(1024), 0, st, p);
+    else if constexpr (!VLB) hipLaunchKernelGGL((final_tail_kernel<32, 2, VLB>), grid, dim3(1024), 0, st, p);
+    else DDK_REQUIRE(false, "final_tail_vlb: C = 256 takes the unfused epilogue (final_tail_vlb_ok)");
+    return check_launch("final_tail_kernel");
+}
+
+// the sweep's fused epilogue: final_tail's shapes up to 128 channels (the 256-channel VLB instantiation would spill registers)
+bool final_tail_vlb_ok(int HW, int C, int groups, int n_out, int np) { return C <= 128 && final_tail_ok(HW, C, groups, n_out, np); }
 
 bool final_tail_ok(int HW, int C, int groups, int n_out, int np) {
     if (!(C == 32 || C == 64 || C == 128 || C == 256)) return false;
@@ -295,12 +379,25 @@ int final_tail(const float* raw, const float* part, int np, const float* gamma, 
     p.seed = seed; p.stream = stream_id;
     p.np = np; p.HW = HW; p.C = C; p.cpg = C / groups; p.n_out = n_out; p.eps = eps;
     p.dec_counter = dec_counter;
-    const dim3 grid((unsigned)(B * np));
-    if (C == 32) hipLaunchKernelGGL((final_tail_kernel<8, 1>), grid, dim3(1024), 0, st, p);
-    else if (C == 64) hipLaunchKernelGGL((final_tail_kernel<16, 1>), grid, dim3(1024), 0, st, p);
-    else if (C == 128) hipLaunchKernelGGL((final_tail_kernel<32, 1>), grid, dim3(1024), 0, st, p);
-    else hipLaunchKernelGGL((final_tail_kernel<32, 2>), grid, dim3(1024), 0, st, p);
-    return check_launch("final_tail_kernel");
+    return launch_tail<false>(p, B, st);
+}
+
+int final_tail_vlb(const float* raw, const float* part, int np, const float* gamma, const float* beta, float eps, const float* w,
+                   const float* bias, int n_out, const VlbStep& v, const int64_t* t, const int64_t* chain_state, int B, int HW, int C,
+                   int groups, hipStream_t st, int64_t* dec_counter) {
+    DDK_REQUIRE(raw && part && gamma && beta && w && v.x && v.xt && v.partials && t && chain_state && B > 0, "final_tail_vlb: null pointer");
+    DDK_REQUIRE(final_tail_vlb_ok(HW, C, groups, n_out, np) && v.nslot == np, "final_tail_vlb: shape");
+    DDK_REQUIRE(v.c_recip && v.c_recipm1 && v.c1 && v.c2 && v.logvar, "final_tail_vlb: null schedule table");
+    DDK_REQUIRE(aligned16(raw) && aligned16(gamma) && aligned16(beta) && aligned16(w) && aligned16(v.x) && aligned16(v.xt) &&
+                    aligned16(v.noise) && aligned16(v.partials) && v.noise_step_stride % 4 == 0, "final_tail_vlb: alignment");
+    TailParams p{};
+    p.raw = raw; p.part = reinterpret_cast<const float2*>(part); p.gamma = gamma; p.beta = beta; p.w = w; p.bias = bias;
+    p.x = const_cast<float*>(v.x); p.xt = v.xt; p.noise = v.noise; p.noise_step_stride = v.noise_step_stride; p.t_first = v.t_first;
+    p.t = t; p.c_recip = v.c_recip; p.c_recipm1 = v.c_recipm1; p.c1 = v.c1; p.c2 = v.c2; p.logvar = v.logvar;
+    p.chain_state = chain_state; p.vlb_part = reinterpret_cast<float2*>(v.partials); p.B = B;
+    p.np = np; p.HW = HW; p.C = C; p.cpg = C / groups; p.n_out = n_out; p.eps = eps;
+    p.dec_counter = dec_counter;
+    return launch_tail<true>(p, B, st);
 }
 
 // one workgroup per sample: fixed summation tree -> run-to-run deterministic
@@ -327,9 +424,6 @@ __global__ __launch_bounds__(1024) void sq_err_sum_kernel(const float* __restric
 //   vlb[b] = mean_chw(.) / ln 2 (flat_bits);  sqerr[b] = sum_chw (eps - eps_hat)^2.
 // The reference evaluates ~25 elementwise torch ops + 2 reductions per timestep (and runs the UNet twice on identical
 // inputs); this is one launch, 16 B read per element, one workgroup per sample with a fixed summation tree.
-__device__ __forceinline__ float std_normal_cdf_approx(float v) {
-    return 0.5f * (1.0f + tanhf(0.7978845608028654f * (v + 0.044715f * (v * v * v))));      // sqrt(2/pi)
-}
 
 // Each sample is split over `ns` workgroups (a batch of 8 full-resolution images would otherwise occupy 8 of 256 CUs); a slice
 // leaves {sum of terms, sum of squared errors} in the workspace (sc1 stores), adds to the sample's arrival counter, and the
@@ -345,31 +439,13 @@ __global__ __launch_bounds__(1024) void vlb_terms_kernel(const float* __restrict
     __shared__ float red[32];
     __shared__ unsigned last;
     const int b = blockIdx.y, sl = blockIdx.x;
-    const int64_t tb = t[b];
-    const float cr = c_recip[tb], crm1 = c_recipm1[tb], a1 = c1[tb], a2 = c2[tb], lv = logvar[tb];
-    const float inv_var = expf(-lv), inv_std = expf(-(0.5f * lv));
-    const float kl0 = (lv - lv - 1.0f) + expf(lv - lv);
+    const VlbCoef k = vlb_coef(t[b], c_recip, c_recipm1, c1, c2, logvar);
     const long long base = (long long)b * per;
     const long long chunk = (per + ns - 1) / ns, i0 = sl * chunk, i1 = i0 + chunk < per ? i0 + chunk : per;
     float acc = 0.f, sq = 0.f;
     for (long long i = i0 + threadIdx.x; i < i1; i += blockDim.x) {
         const float xv = x[base + i], xt = x_t[base + i], eh = eps_hat[base + i];
-        float x0 = __fsub_rn(__fmul_rn(cr, xt), __fmul_rn(crm1, eh));
-        x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-        const float pred = __fadd_rn(__fmul_rn(a1, x0), __fmul_rn(a2, xt));
-        float term;
-        if (tb == 0) {
-            const float c = xv - pred;
-            const float cdf_plus = std_normal_cdf_approx(inv_std * (c + 1.0f / 255.0f));
-            const float cdf_min = std_normal_cdf_approx(inv_std * (c - 1.0f / 255.0f));
-            const float lp = xv < -0.999f ? logf(fmaxf(cdf_plus, 1e-12f))
-                                          : (xv > 0.999f ? logf(fmaxf(1.0f - cdf_min, 1e-12f)) : logf(fmaxf(cdf_plus - cdf_min, 1e-12f)));
-            term = -lp;
-        } else {
-            const float tm = __fadd_rn(__fmul_rn(a1, xv), __fmul_rn(a2, xt));
-            const float d = tm - pred;
-            term = 0.5f * (kl0 + (d * d) * inv_var);
-        }
+        const float term = vlb_elem(xv, xt, eh, k);
         acc += term;
         if (eps) { const float e = eps[base + i] - eh; sq += e * e; }
     }
@@ -401,6 +477,111 @@ static int vlb_slices(int B, long long per) {
     if (ns > cap) ns = (int)cap;
     if (ns > 64) ns = 64;
     return ns < 1 ? 1 : ns;
+}
+
+// ---- likelihood sweep (ddk_vlb_sweep_run): test_losses_ of reference models/diffusion/ddpm.py:392-446 as a chain of steps -------
+// A step: vlb_step_input_kernel (x_t = q_sample(x, t, eps)), the UNet forward on x_t, and an epilogue that leaves the step's
+// {sum of VLB terms, sum of (eps - eps_hat)^2} per (t, image, slice) in partials[t][b][slice] -- final_tail_kernel<.., true> where
+// the fused tail takes the shape, else vlb_sweep_terms_kernel behind conv + GroupNorm + 1x1.  t, the Philox seed and stream come
+// from the chain state in device memory, like the sampler's.  vlb_sweep_finalize_kernel sums the partials once, after the last step.
+
+// x_t = sqrt_acp[t] x + sqrt_1m_acp[t] eps (q_sample_kernel's arithmetic), eps = the injected draw k = t_first - t or the Philox draw
+// of (float4 index, t, stream, seed) -- the call final_tail_kernel<.., true> / vlb_sweep_terms_kernel repeat.  Leaves the counter alone.
+__global__ __launch_bounds__(256) void vlb_step_input_kernel(const float* __restrict__ x, float* __restrict__ xt,
+                                                             const float* __restrict__ noise, long long noise_step_stride, int t_first,
+                                                             const float* __restrict__ ca, const float* __restrict__ cb,
+                                                             const int64_t* __restrict__ chain_state, long long total4) {
+    const int64_t tb = chain_state[0];
+    const uint64_t seed = (uint64_t)chain_state[1];
+    const uint32_t stream = (uint32_t)chain_state[2];
+    const float a = ca[tb], b = cb[tb];
+    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total4; i += (long long)gridDim.x * 256) {
+        const float4 xv = reinterpret_cast<const float4*>(x)[i];
+        const float4 ev = noise ? reinterpret_cast<const float4*>(noise + (long long)(t_first - tb) * noise_step_stride)[i]
+                                : philox_normal4((unsigned long long)i, (uint32_t)tb, stream, seed);
+        float4 o;
+        o.x = __fadd_rn(__fmul_rn(a, xv.x), __fmul_rn(b, ev.x));
+        o.y = __fadd_rn(__fmul_rn(a, xv.y), __fmul_rn(b, ev.y));
+        o.z = __fadd_rn(__fmul_rn(a, xv.z), __fmul_rn(b, ev.z));
+        o.w = __fadd_rn(__fmul_rn(a, xv.w), __fmul_rn(b, ev.w));
+        reinterpret_cast<float4*>(xt)[i] = o;
+    }
+}
+
+// the unfused epilogue: eps_hat from conv + GroupNorm + 1x1 in memory; slice sl of image b sums its share of the float4s
+__global__ __launch_bounds__(256) void vlb_sweep_terms_kernel(const VlbStep v, const int64_t* __restrict__ t,
+                                                              const float* __restrict__ eps_hat, long long per4, int B,
+                                                              const int64_t* __restrict__ chain_state, int64_t* dec_counter) {
+    __shared__ float red[32];
+    if (dec_counter && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *dec_counter -= 1;   // nobody reads it here
+    const int b = blockIdx.y, sl = blockIdx.x;
+    const int64_t tb = t[b];
+    const VlbCoef k = vlb_coef(tb, v.c_recip, v.c_recipm1, v.c1, v.c2, v.logvar);
+    const uint64_t seed = (uint64_t)chain_state[1];
+    const uint32_t stream = (uint32_t)chain_state[2];
+    const long long chunk = (per4 + gridDim.x - 1) / gridDim.x, i0 = sl * chunk, i1 = i0 + chunk < per4 ? i0 + chunk : per4;
+    const float4* nz = v.noise ? reinterpret_cast<const float4*>(v.noise + (long long)(v.t_first - tb) * v.noise_step_stride) : nullptr;
+    float acc = 0.f, sq = 0.f;
+    for (long long i = i0 + threadIdx.x; i < i1; i += 256) {
+        const long long g = (long long)b * per4 + i;
+        const float4 xv = reinterpret_cast<const float4*>(v.x)[g], xt = reinterpret_cast<const float4*>(v.xt)[g];
+        const float4 eh = reinterpret_cast<const float4*>(eps_hat)[g];
+        const float4 z = nz ? nz[g] : philox_normal4((unsigned long long)g, (uint32_t)tb, stream, seed);
+        acc += (vlb_elem(xv.x, xt.x, eh.x, k) + vlb_elem(xv.y, xt.y, eh.y, k)) + (vlb_elem(xv.z, xt.z, eh.z, k) + vlb_elem(xv.w, xt.w, eh.w, k));
+        const float d0 = z.x - eh.x, d1 = z.y - eh.y, d2 = z.z - eh.z, d3 = z.w - eh.w;
+        sq += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+    }
+    acc = block_sum(acc, red);
+    sq = block_sum(sq, red);
+    if (threadIdx.x == 0) reinterpret_cast<float2*>(v.partials)[((long long)tb * B + b) * gridDim.x + sl] = make_float2(acc, sq);
+}
+
+// once per sweep, one workgroup per timestep, fixed summation order: vlb_t[b][k] = sum of terms / per / ln 2 (vlb_terms_kernel's
+// flat_bits), L_simple_t[k] = sum over b, slices of sq / (B per); k = T-1-t, the reference's column order
+__global__ __launch_bounds__(256) void vlb_sweep_finalize_kernel(const float2* __restrict__ part, float* __restrict__ vlb_t,
+                                                                 float* __restrict__ l_simple_t, int T, int B, int nslot, long long per) {
+    __shared__ float red[32];
+    const int t = blockIdx.x, k = T - 1 - t;
+    float sq = 0.f;
+    for (int b = threadIdx.x; b < B; b += 256) {
+        const float2* pb = part + ((long long)t * B + b) * nslot;
+        float a = 0.f, s2 = 0.f;
+        for (int j = 0; j < nslot; ++j) {
+            const float2 q = pb[j];
+            a += q.x;
+            s2 += q.y;
+        }
+        vlb_t[(long long)b * T + k] = (a / (float)per) / 0.6931471805599453f;
+        sq += s2;
+    }
+    sq = block_sum(sq, red);
+    if (threadIdx.x == 0) l_simple_t[k] = sq / (float)((long long)B * per);
+}
+
+int vlb_sweep_slots_unfused(int B, long long per) { return vlb_slices(B, per); }
+
+int vlb_step_input(const VlbStep& v, const float* sqrt_acp, const float* sqrt_1m_acp, const int64_t* chain_state, int B, long long per,
+                   hipStream_t st) {
+    DDK_REQUIRE(v.x && v.xt && sqrt_acp && sqrt_1m_acp && chain_state && B > 0 && per % 4 == 0, "vlb_step_input: arguments");
+    const long long total4 = B * per / 4;
+    hipLaunchKernelGGL(vlb_step_input_kernel, dim3(grid1d(total4)), dim3(256), 0, st, v.x, v.xt, v.noise, v.noise_step_stride, v.t_first,
+                       sqrt_acp, sqrt_1m_acp, chain_state, total4);
+    return check_launch("vlb_step_input_kernel");
+}
+
+int vlb_sweep_terms(const VlbStep& v, const int64_t* t, const float* eps_hat, int B, long long per, const int64_t* chain_state,
+                    hipStream_t st, int64_t* dec_counter) {
+    DDK_REQUIRE(v.x && v.xt && v.partials && t && eps_hat && chain_state && B > 0 && per % 4 == 0, "vlb_sweep_terms: arguments");
+    DDK_REQUIRE(v.nslot == vlb_slices(B, per), "vlb_sweep_terms: slot count");
+    hipLaunchKernelGGL(vlb_sweep_terms_kernel, dim3(v.nslot, B), dim3(256), 0, st, v, t, eps_hat, per / 4, B, chain_state, dec_counter);
+    return check_launch("vlb_sweep_terms_kernel");
+}
+
+int vlb_sweep_finalize(const float* partials, int nslot, float* vlb_t, float* l_simple_t, int T, int B, long long per, hipStream_t st) {
+    DDK_REQUIRE(partials && vlb_t && l_simple_t && T > 0 && B > 0 && nslot > 0, "vlb_sweep_finalize: arguments");
+    hipLaunchKernelGGL(vlb_sweep_finalize_kernel, dim3(T), dim3(256), 0, st, reinterpret_cast<const float2*>(partials), vlb_t, l_simple_t,
+                       T, B, nslot, per);
+    return check_launch("vlb_sweep_finalize_kernel");
 }
 
 int p_sample_update(float* x, const float* eps_hat, const float* noise, long long noise_step_stride, int t_first,

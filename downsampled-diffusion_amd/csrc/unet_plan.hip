@@ -77,13 +77,27 @@ struct AttnW {
 
 using namespace ddk;
 
-// One captured reverse step.  A hipGraph bakes in every pointer its kernels were launched with, so an entry is valid for
-// exactly this set of buffers and this shape; t, the Philox seed / stream id and the injected-noise step index are read
-// from device memory by the kernels, so the same graph serves every step of every chain on those buffers.
-struct SamplerGraph {
-    const void *packed, *x, *noise, *ws, *c_recip, *c_recipm1, *c1, *c2, *sigma;
+// One captured step of a chain: a reverse step of the sampler, or a step of the likelihood sweep.  A hipGraph bakes in every
+// pointer its kernels were launched with, so an entry is valid for exactly this kind of chain, this set of buffers and this
+// shape; t, the Philox seed / stream id and the injected-noise step index are read from device memory by the kernels, so the
+// same graph serves every step of every chain on those buffers.
+enum ChainKind { CHAIN_SAMPLER = 0, CHAIN_VLB_SWEEP = 1 };
+struct ChainKey {
+    int kind;
+    const void* bufs[12];                    // every buffer the step's kernels are launched with (unused entries null)
+    const void* ws;
+    const void* noise;                       // also in bufs; injected draws: no 16-step graph (see run_chain)
     int B, H, W, t_start, device;
     unsigned long long pack_epoch;
+    bool operator==(const ChainKey& o) const {
+        for (int i = 0; i < 12; ++i)
+            if (bufs[i] != o.bufs[i]) return false;
+        return kind == o.kind && ws == o.ws && noise == o.noise && B == o.B && H == o.H && W == o.W && t_start == o.t_start &&
+               device == o.device && pack_epoch == o.pack_epoch;
+    }
+};
+struct SamplerGraph {
+    ChainKey key;
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     hipGraph_t graph_multi = nullptr;        // SAMPLER_MULTI consecutive steps in one graph (captured when a chain is long enough)
@@ -418,7 +432,7 @@ extern "C" int ddk_sampler_release_workspace(ddk_unet* u, const void* workspace)
     DDK_REQUIRE(u && workspace, "sampler_release_workspace: arguments");
     std::lock_guard<std::mutex> lock(u->mu);
     for (size_t i = 0; i < u->graphs.size();) {
-        if (u->graphs[i].ws == workspace) {
+        if (u->graphs[i].key.ws == workspace) {
             destroy_entry(u->graphs[i]);
             u->graphs.erase(u->graphs.begin() + (long)i);
         } else {
@@ -1172,7 +1186,17 @@ struct StepArgs {
     int t_first;
     const float *c_recip, *c_recipm1, *c1, *c2, *sigma;
     long long per;
+    const VlbStep* vlb = nullptr;   // likelihood sweep: the forward ran on vlb->xt and ends in the VLB epilogue (x, sigma unused)
 };
+
+// tiles of the final tail when the end of the forward runs as ONE launch (final_tail_kernel), else 0.  cin = the final conv's
+// input channels (dimp[1]).  The sweep's VLB mode takes a subset of the shapes (final_tail_vlb_ok).
+static int fused_tail_parts(const ddk_unet& u, int B, int H, int W, int cin, bool vlb) {
+    const int chan = u.generic ? pad32(u.cfg.chan) : u.cfg.chan, n_out = u.cfg.in_ch;
+    const int npf = u.final_conv.has_wu ? conv_wino_stats_parts(B, H, W, cin, chan, GROUPS) : 0;
+    if (npf <= 0) return 0;
+    return (vlb ? final_tail_vlb_ok(H * W, chan, GROUPS, n_out, npf) : final_tail_ok(H * W, chan, GROUPS, n_out, npf)) ? npf : 0;
+}
 
 // t_cur[b] = counter for every sample, then counter -= 1; also zero-pads x into xpad.  First kernel of a step on shapes the
 // first-layer kernel does not take: the previous step's kernels have all completed (stream order), nobody else reads the counter.
@@ -1382,8 +1406,8 @@ static int forward_core(const ddk_unet& u, const float* P, const float* x, int64
     }
     // final_conv: Block(dim, dim) then 1x1 to in_ch (unet.py:69-72)
     const int chan = u.generic ? pad32(u.cfg.chan) : u.cfg.chan, n_out = u.cfg.in_ch;
-    const int npf = u.final_conv.has_wu ? conv_wino_stats_parts(B, H, W, cur_c, chan, GROUPS) : 0;
-    if (npf > 0 && final_tail_ok(H * W, chan, GROUPS, n_out, npf) && (!step || step->per == (long long)H * W * n_out)) {
+    const int npf = fused_tail_parts(u, B, H, W, cur_c, step && step->vlb);
+    if (npf > 0 && (!step || step->per == (long long)H * W * n_out)) {
         // one-pass Winograd conv with statistics, then GroupNorm + Mish + projection (+ the update of x) in ONE launch
         ddk_conv_args a{};
         a.kind = DDK_CONV3X3_S1;
@@ -1396,6 +1420,9 @@ static int forward_core(const ddk_unet& u, const float* P, const float* x, int64
         a.gn_partials = gnp;
         a.gn_groups = GROUPS;
         DDK_TRY(conv_forward(a, st));
+        if (step && step->vlb)
+            return final_tail_vlb(raw, gnp, npf, P + u.final_norm.g, P + u.final_norm.b, GN_EPS, P + u.final_w, P + u.final_b, n_out,
+                                  *step->vlb, t, step->state, B, H * W, chan, GROUPS, st, dec_counter);
         if (step)
             return final_tail(raw, gnp, npf, P + u.final_norm.g, P + u.final_norm.b, GN_EPS, P + u.final_w, P + u.final_b, n_out, nullptr,
                               step->x, step->noise, step->noise_step_stride, step->t_first, t, step->c_recip, step->c_recipm1, step->c1,
@@ -1407,6 +1434,7 @@ static int forward_core(const ddk_unet& u, const float* P, const float* x, int64
     float* eps_hat = step ? step->eps_hat : out;
     DDK_TRY(conv1x1_small_n(a1, P + u.final_w, P + u.final_b, eps_hat, (long long)B * H * W, chan, n_out, st));
     if (!step) return DDK_OK;
+    if (step->vlb) return vlb_sweep_terms(*step->vlb, t, eps_hat, B, step->per, step->state, st, dec_counter);
     return p_sample_update(step->x, eps_hat, step->noise, step->noise_step_stride, step->t_first, t, step->c_recip, step->c_recipm1,
                            step->c1, step->c2, step->sigma, B, step->per, 0, 0, st, step->state, dec_counter);
 }
@@ -1587,6 +1615,108 @@ extern "C" size_t ddk_sampler_workspace_bytes(const ddk_unet* u, int B, int H, i
     return sampler_layout(*u, B, H, W, t_start).total * sizeof(float);
 }
 
+namespace ddk {
+// Time-shift table for t = 0..t_start: the same two kernels a forward runs, once, with "batch" = all timesteps.  It lives in the
+// caller's workspace (sampler_layout: the sweep's workspace starts with the same layout) and stays valid while neither the weights
+// (pack_epoch) nor the workspace change; a caller that rewrites or frees the workspace between calls says so with
+// ddk_sampler_invalidate().
+static int ensure_temb_table(ddk_unet& u, const float* P, float* ws, const SamplerLayout& sl, int t_start, int B, int H, int W,
+                             hipStream_t st) {
+    if (u.table.ws == ws && u.table.t_start == t_start && u.table.B == B && u.table.H == H && u.table.W == W &&
+        u.table.pack_epoch == u.pack_epoch)
+        return DDK_OK;
+    const int rows = t_start + 1;
+    int64_t* t_all = reinterpret_cast<int64_t*>(ws + sl.off_tall);
+    float* tact_all = ws + sl.off_tact_all;
+    hipLaunchKernelGGL(iota64_kernel, dim3((unsigned)ceil_div(rows, 256)), dim3(256), 0, st, t_all, rows);
+    DDK_TRY(check_launch("iota64_kernel"));
+    DDK_TRY(time_mlp(t_all, P + u.freqs, P + u.w1t, P + u.b1, P + u.w2t, P + u.b2, tact_all, nullptr, rows, u.time_dim, st));
+    DDK_TRY(time_proj(tact_all, P + u.temb_wt, P + u.temb_bias, ws + sl.off_table, rows, u.time_dim, u.temb_total, st));
+    u.table.ws = ws; u.table.t_start = t_start; u.table.B = B; u.table.H = H; u.table.W = W;
+    u.table.pack_epoch = u.pack_epoch;
+    return DDK_OK;
+}
+
+// n_steps steps of a chain whose state (counter, Philox key) is already in device memory, each step issued by one_step():
+// eagerly, or from the plan's graph cache (caller holds u.mu).  A new key runs its first step eagerly and captures a one-step
+// graph (and, for chains that can be long and draw their own noise, a SAMPLER_MULTI-step graph); at most 4 keys stay cached (LRU).
+template <class F>
+static int run_chain(ddk_unet& u, const ChainKey& key, int n_steps, bool use_graph, F&& one_step, hipStream_t st, const char* who) {
+    if (!use_graph || n_steps == 1) {
+        for (int k = 0; k < n_steps; ++k) DDK_TRY(one_step());
+        return DDK_OK;
+    }
+    auto capture = [&](int steps, hipGraph_t& graph, hipGraphExec_t& exec) -> int {
+        hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
+        if (e != hipSuccess) {
+            set_error("%s: hipStreamBeginCapture failed (%s); the legacy NULL stream cannot be captured -- pass a created stream", who,
+                      hipGetErrorString(e));
+            return DDK_ERR_HIP;
+        }
+        int rc = DDK_OK;
+        for (int i = 0; i < steps && rc == DDK_OK; ++i) rc = one_step();
+        e = hipStreamEndCapture(st, &graph);
+        if (rc != DDK_OK) { if (graph) (void)hipGraphDestroy(graph); graph = nullptr; return rc; }
+        if (e != hipSuccess) { graph = nullptr; set_error("%s: hipStreamEndCapture: %s", who, hipGetErrorString(e)); return DDK_ERR_HIP; }
+        e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+        if (e != hipSuccess) {
+            (void)hipGraphDestroy(graph);
+            graph = nullptr; exec = nullptr;
+            set_error("%s: hipGraphInstantiate: %s", who, hipGetErrorString(e));
+            return DDK_ERR_HIP;
+        }
+        return DDK_OK;
+    };
+
+    SamplerGraph* hit = nullptr;
+    for (SamplerGraph& g : u.graphs)
+        if (g.key == key) {
+            hit = &g;
+            break;
+        }
+    int first = 0;
+    if (!hit) {
+        // New buffer set: run the first step eagerly, capture the second, keep the executable graph in the plan.
+        if (u.graphs.size() >= 4) {      // bounded cache: retire the least recently used entry (its launches must have drained)
+            size_t lru = 0;
+            for (size_t i = 1; i < u.graphs.size(); ++i)
+                if (u.graphs[i].last_use < u.graphs[lru].last_use) lru = i;
+            // wait for the evicted entry's own launches only (not the device: another stream may be mid-capture)
+            destroy_entry(u.graphs[lru]);
+            u.graphs.erase(u.graphs.begin() + (long)lru);
+        }
+        DDK_TRY(one_step());
+        first = 1;
+        SamplerGraph g{};
+        g.key = key;
+        DDK_TRY(capture(1, g.graph, g.exec));
+        u.graphs.push_back(g);
+        hit = &u.graphs.back();
+    }
+    hit->last_use = ++u.use_clock;
+    int k = first;
+    // long chains: SAMPLER_MULTI steps per graph launch (t and the Philox counter live in device memory, so a graph of any number
+    // of steps continues the chain); the one-step graph finishes the remainder
+    // (captured with the one-step graph, on the first call for a buffer set whose chain can be that long -- not in a later, timed call)
+    // (not for injected noise: a fresh noise tensor per call means a fresh cache entry per call -- parity tests -- and capturing
+    //  SAMPLER_MULTI x ~80 launches for a chain that is never replayed is pure overhead)
+    if (!hit->exec_multi && !key.noise && (first || n_steps - k >= 2 * SAMPLER_MULTI) && key.t_start + 1 >= 2 * SAMPLER_MULTI)
+        DDK_TRY(capture(SAMPLER_MULTI, hit->graph_multi, hit->exec_multi));
+    if (hit->exec_multi)
+        for (; k + SAMPLER_MULTI <= n_steps; k += SAMPLER_MULTI) {
+            const hipError_t e = hipGraphLaunch(hit->exec_multi, st);
+            if (e != hipSuccess) { set_error("%s: hipGraphLaunch: %s", who, hipGetErrorString(e)); return DDK_ERR_HIP; }
+        }
+    for (; k < n_steps; ++k) {
+        const hipError_t e = hipGraphLaunch(hit->exec, st);
+        if (e != hipSuccess) { set_error("%s: hipGraphLaunch: %s", who, hipGetErrorString(e)); return DDK_ERR_HIP; }
+    }
+    if (!hit->done) DDK_HIP(hipEventCreateWithFlags(&hit->done, hipEventDisableTiming));
+    DDK_HIP(hipEventRecord(hit->done, st));
+    return DDK_OK;
+}
+}  // namespace ddk
+
 extern "C" int ddk_sampler_run(const ddk_sampler_args* a, ddk_stream_t s) {
     DDK_REQUIRE(a && a->unet && a->packed && a->x && a->workspace, "sampler: null pointer");
     DDK_REQUIRE(a->c_recip && a->c_recipm1 && a->c1 && a->c2 && a->sigma, "sampler: null schedule table");
@@ -1619,103 +1749,94 @@ extern "C" int ddk_sampler_run(const ddk_sampler_args* a, ddk_stream_t s) {
         return forward_core(u, P, a->x, t_cur, nullptr, B, H, W, ws, ly, st, u.cluster_gn >= 1, temb_table, &step);
     };
 
-    auto capture = [&](int steps, hipGraph_t& graph, hipGraphExec_t& exec) -> int {
-        hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-        if (e != hipSuccess) {
-            set_error("sampler: hipStreamBeginCapture failed (%s); the legacy NULL stream cannot be captured -- pass a created stream",
-                      hipGetErrorString(e));
-            return DDK_ERR_HIP;
-        }
-        int rc = DDK_OK;
-        for (int i = 0; i < steps && rc == DDK_OK; ++i) rc = one_step();
-        e = hipStreamEndCapture(st, &graph);
-        if (rc != DDK_OK) { if (graph) (void)hipGraphDestroy(graph); graph = nullptr; return rc; }
-        if (e != hipSuccess) { graph = nullptr; set_error("sampler: hipStreamEndCapture: %s", hipGetErrorString(e)); return DDK_ERR_HIP; }
-        e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        if (e != hipSuccess) {
-            (void)hipGraphDestroy(graph);
-            graph = nullptr; exec = nullptr;
-            set_error("sampler: hipGraphInstantiate: %s", hipGetErrorString(e));
-            return DDK_ERR_HIP;
-        }
-        return DDK_OK;
-    };
-
     std::lock_guard<std::mutex> lock(u.mu);
     DDK_HIP(hipMemsetAsync(ws + ly.off_cl, 0, cl_counter_floats(B) * sizeof(float), st));    // cluster GroupNorm counters (outside the graph)
     hipLaunchKernelGGL(set_chain_state_kernel, dim3(1), dim3(1), 0, st, state, (int64_t)a->t_start, a->seed, a->stream_id);
     DDK_TRY(check_launch("set_chain_state_kernel"));
-    // Time-shift table for t = 0..t_start: the same two kernels a forward runs, once, with "batch" = all timesteps.  It
-    // lives in the caller's workspace and stays valid while neither the weights (pack_epoch) nor the workspace change;
-    // a caller that rewrites or frees the workspace between calls says so with ddk_sampler_invalidate().
-    if (!(u.table.ws == a->workspace && u.table.t_start == a->t_start && u.table.B == B && u.table.H == H && u.table.W == W &&
-          u.table.pack_epoch == u.pack_epoch)) {
-        const int rows = a->t_start + 1;
-        int64_t* t_all = reinterpret_cast<int64_t*>(ws + sl.off_tall);
-        float* tact_all = ws + sl.off_tact_all;
-        hipLaunchKernelGGL(iota64_kernel, dim3((unsigned)ceil_div(rows, 256)), dim3(256), 0, st, t_all, rows);
-        DDK_TRY(check_launch("iota64_kernel"));
-        DDK_TRY(time_mlp(t_all, P + u.freqs, P + u.w1t, P + u.b1, P + u.w2t, P + u.b2, tact_all, nullptr, rows, u.time_dim, st));
-        DDK_TRY(time_proj(tact_all, P + u.temb_wt, P + u.temb_bias, ws + sl.off_table, rows, u.time_dim, u.temb_total, st));
-        u.table.ws = a->workspace; u.table.t_start = a->t_start; u.table.B = B; u.table.H = H; u.table.W = W;
-        u.table.pack_epoch = u.pack_epoch;
-    }
+    DDK_TRY(ensure_temb_table(u, P, ws, sl, a->t_start, B, H, W, st));
     const int n_steps = a->t_start - a->t_end + 1;
-    if (!a->use_graph || n_steps == 1) {
-        for (int k = 0; k < n_steps; ++k) DDK_TRY(one_step());
-        return DDK_OK;
-    }
-
     int dev = 0;
-    DDK_HIP(hipGetDevice(&dev));
-    SamplerGraph* hit = nullptr;
-    for (SamplerGraph& g : u.graphs)
-        if (g.packed == a->packed && g.x == a->x && g.noise == a->noise && g.ws == a->workspace && g.c_recip == a->c_recip &&
-            g.c_recipm1 == a->c_recipm1 && g.c1 == a->c1 && g.c2 == a->c2 && g.sigma == a->sigma && g.B == B && g.H == H &&
-            g.W == W && g.t_start == a->t_start && g.device == dev && g.pack_epoch == u.pack_epoch) {
-            hit = &g;
-            break;
-        }
-    int first = 0;
-    if (!hit) {
-        // New buffer set: run the first step eagerly, capture the second, keep the executable graph in the plan.
-        if (u.graphs.size() >= 4) {      // bounded cache: retire the least recently used entry (its launches must have drained)
-            size_t lru = 0;
-            for (size_t i = 1; i < u.graphs.size(); ++i)
-                if (u.graphs[i].last_use < u.graphs[lru].last_use) lru = i;
-            // wait for the evicted entry's own launches only (not the device: another stream may be mid-capture)
-            destroy_entry(u.graphs[lru]);
-            u.graphs.erase(u.graphs.begin() + (long)lru);
-        }
-        DDK_TRY(one_step());
-        first = 1;
-        SamplerGraph g{};
-        g.packed = a->packed; g.x = a->x; g.noise = a->noise; g.ws = a->workspace; g.c_recip = a->c_recip; g.c_recipm1 = a->c_recipm1;
-        g.c1 = a->c1; g.c2 = a->c2; g.sigma = a->sigma; g.B = B; g.H = H; g.W = W; g.t_start = a->t_start; g.device = dev;
-        g.pack_epoch = u.pack_epoch;
-        DDK_TRY(capture(1, g.graph, g.exec));
-        u.graphs.push_back(g);
-        hit = &u.graphs.back();
+    if (a->use_graph && n_steps > 1) DDK_HIP(hipGetDevice(&dev));
+    const ChainKey key{CHAIN_SAMPLER, {a->packed, a->x, a->noise, a->c_recip, a->c_recipm1, a->c1, a->c2, a->sigma}, a->workspace, a->noise,
+                       B, H, W, a->t_start, dev, u.pack_epoch};
+    return run_chain(u, key, n_steps, a->use_graph != 0, one_step, st, "sampler");
+}
+
+// ------------------------------------------------------------------------------------------------ likelihood sweep
+namespace ddk {
+struct SweepLayout {
+    SamplerLayout sl;             // the sampler's layout first (UNet scratch, eps_hat, t_cur + chain state, time-shift table)
+    size_t off_xt, off_part, total;
+    int nslot;
+};
+static SweepLayout sweep_layout(const ddk_unet& u, int B, int H, int W, int T) {
+    SweepLayout s;
+    s.sl = sampler_layout(u, B, H, W, T - 1);
+    const long long per = (long long)H * W * u.cfg.in_ch;
+    const int npf = fused_tail_parts(u, B, H, W, u.dimp[1], true);
+    s.nslot = npf > 0 ? npf : vlb_sweep_slots_unfused(B, per);
+    s.off_xt = s.sl.total;
+    s.off_part = s.off_xt + al4((size_t)B * per);
+    s.total = s.off_part + al4((size_t)T * B * s.nslot * 2);
+    return s;
+}
+}  // namespace ddk
+
+extern "C" size_t ddk_vlb_sweep_workspace_bytes(const ddk_unet* u, int B, int H, int W, int T) {
+    if (check_shape(u, B, H, W) != DDK_OK || T < 1) return 0;
+    return sweep_layout(*u, B, H, W, T).total * sizeof(float);
+}
+
+extern "C" int ddk_vlb_sweep_run(const ddk_vlb_sweep_args* a, ddk_stream_t s) {
+    DDK_REQUIRE(a && a->unet && a->packed && a->x && a->workspace && a->vlb_t && a->l_simple_t, "vlb_sweep: null pointer");
+    DDK_REQUIRE(a->sqrt_acp && a->sqrt_1m_acp && a->c_recip && a->c_recipm1 && a->c1 && a->c2 && a->post_logvar,
+                "vlb_sweep: null schedule table");
+    ddk_unet& u = *const_cast<ddk_unet*>(a->unet);
+    DDK_TRY(check_shape(&u, a->B, a->H, a->W));
+    DDK_REQUIRE(a->T >= 1, "vlb_sweep: need T >= 1");
+    DDK_REQUIRE((a->stream_id & VLB_STREAM_BIT) == 0, "vlb_sweep: stream_id must be < 2^31 (the top bit separates the sweep's draws)");
+    DDK_REQUIRE(aligned16(a->packed) && aligned16(a->workspace) && aligned16(a->x) && aligned16(a->noise), "vlb_sweep: alignment");
+    const int B = a->B, H = a->H, W = a->W, C = u.cfg.in_ch, T = a->T;
+    const long long per = (long long)H * W * C;
+    DDK_REQUIRE(per % 4 == 0, "vlb_sweep: H*W*in_ch must be a multiple of 4");
+    const SweepLayout vl = sweep_layout(u, B, H, W, T);
+    const SamplerLayout& sl = vl.sl;
+    if (a->workspace_bytes < vl.total * sizeof(float)) {
+        set_error("vlb_sweep: workspace too small (%zu < %zu)", a->workspace_bytes, vl.total * sizeof(float));
+        return DDK_ERR_WORKSPACE;
     }
-    hit->last_use = ++u.use_clock;
-    int k = first;
-    // long chains: SAMPLER_MULTI steps per graph launch (t and the Philox counter live in device memory, so a graph of any number
-    // of steps continues the chain); the one-step graph finishes the remainder
-    // (captured with the one-step graph, on the first call for a buffer set whose chain can be that long -- not in a later, timed call)
-    // (not for injected noise: a fresh noise tensor per call means a fresh cache entry per call -- parity tests -- and capturing
-    //  SAMPLER_MULTI x ~80 launches for a chain that is never replayed is pure overhead)
-    if (!hit->exec_multi && !a->noise && (first || n_steps - k >= 2 * SAMPLER_MULTI) && a->t_start + 1 >= 2 * SAMPLER_MULTI)
-        DDK_TRY(capture(SAMPLER_MULTI, hit->graph_multi, hit->exec_multi));
-    if (hit->exec_multi)
-        for (; k + SAMPLER_MULTI <= n_steps; k += SAMPLER_MULTI) {
-            const hipError_t e = hipGraphLaunch(hit->exec_multi, st);
-            if (e != hipSuccess) { set_error("sampler: hipGraphLaunch: %s", hipGetErrorString(e)); return DDK_ERR_HIP; }
-        }
-    for (; k < n_steps; ++k) {
-        const hipError_t e = hipGraphLaunch(hit->exec, st);
-        if (e != hipSuccess) { set_error("sampler: hipGraphLaunch: %s", hipGetErrorString(e)); return DDK_ERR_HIP; }
-    }
-    if (!hit->done) DDK_HIP(hipEventCreateWithFlags(&hit->done, hipEventDisableTiming));
-    DDK_HIP(hipEventRecord(hit->done, st));
-    return DDK_OK;
+    DDK_TRY(ensure_device_init());
+    const Layout ly = make_layout(u, B, H, W);
+    hipStream_t st = as_stream(s);
+    float* ws = static_cast<float*>(a->workspace);
+    int64_t* t_cur = reinterpret_cast<int64_t*>(ws + sl.off_t);
+    int64_t* state = t_cur + B;
+    const float* P = static_cast<const float*>(a->packed);
+    const float* temb_table = ws + sl.off_table;
+    float* xt = ws + vl.off_xt;
+    float* partials = ws + vl.off_part;
+    const VlbStep v{a->x, xt, a->noise, a->noise ? B * per : 0, T - 1, a->c_recip, a->c_recipm1, a->c1, a->c2, a->post_logvar,
+                    partials, vl.nslot};
+    StepArgs step{state, nullptr, ws + sl.off_eps, a->noise, a->noise ? B * per : 0, T - 1, a->c_recip, a->c_recipm1, a->c1, a->c2,
+                  nullptr, per};
+    step.vlb = &v;
+
+    // one step: x_t = q_sample(x, t, eps), UNet(x_t, t) with the counter bookkeeping of a reverse step, the VLB epilogue
+    auto one_step = [&]() -> int {
+        DDK_TRY(vlb_step_input(v, a->sqrt_acp, a->sqrt_1m_acp, state, B, per, st));
+        return forward_core(u, P, xt, t_cur, nullptr, B, H, W, ws, ly, st, u.cluster_gn >= 1, temb_table, &step);
+    };
+
+    std::lock_guard<std::mutex> lock(u.mu);
+    DDK_HIP(hipMemsetAsync(ws + ly.off_cl, 0, cl_counter_floats(B) * sizeof(float), st));
+    hipLaunchKernelGGL(set_chain_state_kernel, dim3(1), dim3(1), 0, st, state, (int64_t)(T - 1), a->seed, a->stream_id | VLB_STREAM_BIT);
+    DDK_TRY(check_launch("set_chain_state_kernel"));
+    DDK_TRY(ensure_temb_table(u, P, ws, sl, T - 1, B, H, W, st));
+    int dev = 0;
+    if (a->use_graph && T > 1) DDK_HIP(hipGetDevice(&dev));
+    const ChainKey key{CHAIN_VLB_SWEEP,
+                       {a->packed, a->x, a->noise, a->sqrt_acp, a->sqrt_1m_acp, a->c_recip, a->c_recipm1, a->c1, a->c2, a->post_logvar},
+                       a->workspace, a->noise, B, H, W, T - 1, dev, u.pack_epoch};
+    DDK_TRY(run_chain(u, key, T, a->use_graph != 0, one_step, st, "vlb_sweep"));
+    return vlb_sweep_finalize(partials, vl.nslot, a->vlb_t, a->l_simple_t, T, B, per, st);
 }

@@ -45,6 +45,16 @@ class SamplerArgs(C.Structure):
     ]
 
 
+class VlbSweepArgs(C.Structure):
+    _fields_ = [
+        ("unet", C.c_void_p), ("packed", C.c_void_p), ("x", C.c_void_p), ("noise", C.c_void_p),
+        ("sqrt_acp", C.c_void_p), ("sqrt_1m_acp", C.c_void_p), ("c_recip", C.c_void_p), ("c_recipm1", C.c_void_p),
+        ("c1", C.c_void_p), ("c2", C.c_void_p), ("post_logvar", C.c_void_p), ("B", C.c_int), ("H", C.c_int), ("W", C.c_int),
+        ("T", C.c_int), ("seed", C.c_uint64), ("stream_id", C.c_uint32), ("use_graph", C.c_int),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("vlb_t", C.c_void_p), ("l_simple_t", C.c_void_p),
+    ]
+
+
 class WgradReduceJob(C.Structure):
     """ddk_wgrad_reduce_job (include/ddk.h)"""
     _fields_ = [("slab", C.c_void_p), ("grad", C.c_void_p), ("bias_slab", C.c_void_p), ("grad_b", C.c_void_p), ("slab_stride", C.c_longlong),
@@ -163,6 +173,8 @@ SIGNATURES = {
     "ddk_sampler_run": (_I, [C.POINTER(SamplerArgs), _P]),
     "ddk_sampler_invalidate": (_I, [_P]),
     "ddk_sampler_release_workspace": (_I, [_P, _P]),
+    "ddk_vlb_sweep_workspace_bytes": (_SZ, [_P, _I, _I, _I, _I]),
+    "ddk_vlb_sweep_run": (_I, [C.POINTER(VlbSweepArgs), _P]),
     "ddk_pack_conv_weight_dgrad": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "ddk_zero_stuff2": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "ddk_conv_wgrad_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I, _I]),

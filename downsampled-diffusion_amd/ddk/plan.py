@@ -77,14 +77,15 @@ class UnetPlan:
         """Scratch per (kind, size, device).  The sampler keeps up to 3 workspaces (LRU): the captured step graphs and the
         time-shift table live in / point into their workspace, so a trainer that alternates sample() (t_start = T-1) and
         reconstruct() (t_start = t_rec_max) at every logging event keeps both sets of graphs instead of re-capturing twice per event.
-        Only an eviction drops the plan's cached graphs (ddk_sampler_invalidate waits for the device)."""
+        Only an eviction drops the plan's cached graphs (ddk_sampler_invalidate waits for the device).  The likelihood sweep's
+        workspaces ("vsw") are kept the same way: its captured steps point into them too."""
         key = (kind, nbytes, str(device))
         hit = self._ws.get(key)
         if hit is not None:
             self._ws[key] = self._ws.pop(key)          # most recently used last
             return hit
-        if kind == "smp":
-            mine = [k for k in self._ws if k[0] == "smp"]       # dict order = least recently used first
+        if kind in ("smp", "vsw"):
+            mine = [k for k in self._ws if k[0] == kind]       # dict order = least recently used first
             if len(mine) >= 3:
                 # evict ONLY the least recently used workspace; the plan drops the graphs that point into it (and waits for
                 # their launches), the other two keep theirs
@@ -227,6 +228,70 @@ class UnetPlan:
         if caller_x.data_ptr() != x.data_ptr():
             caller_x.copy_(x)
         return caller_x
+
+
+    # ---------------------------------------------------------------- likelihood sweep
+    VLB_STREAM_BIT = 1 << 31     # the sweep's Philox stream id is stream_id | this (csrc/ddk_internal.h VLB_STREAM_BIT)
+
+    def vlb_sweep_nhwc(self, x, tables, T, noise=None, seed=0, stream_id=0, use_graph=True):
+        """test_losses_ sweep t = T-1 .. 0 on the clean sample x [B,H,W,in_ch] (not written).
+
+        tables: dict with sqrt_acp, sqrt_1m_acp, c_recip, c_recipm1, c1, c2, post_logvar ([T] fp32 device tensors).
+        noise: optional [T,B,H,W,in_ch] injected draws (draw k at t = T-1-k); else in-kernel Philox on (seed, stream_id | 2^31).
+        Returns (vlb_t [B,T] in bits/dim, L_simple_t [T]), columns in the reference's order (k = T-1-t).
+        """
+        if self.packed is None:
+            raise L.DDKError("UnetPlan.vlb_sweep before pack()")
+        b, h, w, c = x.shape
+        if c != self.in_ch:
+            raise L.DDKError(f"expected {self.in_ch} input channels, got {c}")
+        if not 0 <= int(stream_id) < self.VLB_STREAM_BIT:
+            raise L.DDKError("vlb_sweep: stream_id must be in [0, 2^31)")
+        if noise is not None and tuple(noise.shape) != (T, b, h, w, c):
+            raise L.DDKError(f"injected noise must be {(T, b, h, w, c)}, got {tuple(noise.shape)}")
+        lib = self._lib
+        nbytes = lib.ddk_vlb_sweep_workspace_bytes(self.handle, b, h, w, T)
+        if nbytes == 0:
+            raise L.DDKError(f"vlb_sweep workspace query failed: {L.last_error()}")
+        ws = self._workspace("vsw", nbytes, x.device)
+        # the captured step holds the ADDRESS of x: a plan-owned copy per shape keeps it stable across batches
+        skey = ("vsw", tuple(x.shape), str(x.device))
+        xs = self._state.get(skey)
+        if xs is None:
+            xs = self._state[skey] = torch.empty_like(x)
+        xs.copy_(x)
+        vlb_t = torch.empty((b, T), device=x.device, dtype=torch.float32)
+        l_simple_t = torch.empty((T,), device=x.device, dtype=torch.float32)
+        if self._cluster_dev is None:
+            self._cluster_dev = lib.ddk_conv3x3_gn_mish_cluster_ok(32, 32, 32, 128, 128, 8) > 0
+        guard = self._cluster >= 1 and self._cluster_dev
+
+        def call(stream_ptr):
+            a = L.VlbSweepArgs(self.handle, L.ptr(self.packed), L.ptr(xs), L.ptr(noise), L.ptr(tables["sqrt_acp"]),
+                               L.ptr(tables["sqrt_1m_acp"]), L.ptr(tables["c_recip"]), L.ptr(tables["c_recipm1"]), L.ptr(tables["c1"]),
+                               L.ptr(tables["c2"]), L.ptr(tables["post_logvar"]), b, h, w, T, seed, stream_id, int(use_graph),
+                               L.ptr(ws), nbytes, L.ptr(vlb_t), L.ptr(l_simple_t))
+            L.check(lib.ddk_vlb_sweep_run(C.byref(a), stream_ptr), "vlb_sweep_run")
+
+        def run():
+            """Issues the sweep; with the in-launch GroupNorm on, waits for it and says whether it has to be rerun (x is only read,
+            so a rerun needs no saved input)."""
+            if use_graph and T > 1:
+                cur = torch.cuda.current_stream()
+                side = _side_stream(x.device)
+                side.wait_stream(cur)
+                with torch.cuda.stream(side):
+                    call(side.cuda_stream)
+                    failed = guard and self._cluster >= 1 and self._cluster_failed(ws, b, h, w, side.cuda_stream)
+                cur.wait_stream(side)
+                return failed
+            call(L.stream())
+            return guard and self._cluster >= 1 and self._cluster_failed(ws, b, h, w, L.stream())
+
+        if run():
+            if run():
+                raise L.DDKError("vlb_sweep: in-launch GroupNorm reported a failure with the option off")
+        return vlb_t, l_simple_t
 
 
 _side_streams = {}

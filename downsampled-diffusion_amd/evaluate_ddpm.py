@@ -1,0 +1,98 @@
+#!/usr/bin/env python3
+"""Evaluation driver with the reference's behaviour (reference evaluate_ddpm.py:1-106), likelihood half: load
+``{saved_model}.pt`` from CHECKPOINT_DIR (EMA weights preferred), rebuild the model from the stored config, run
+``compute_test_losses`` over the test loader and print the reference's JSON metrics block.
+
+The reference hard-codes its constants; here they are the defaults of optional flags.  The sample metrics (FID, sFID,
+IS, precision / recall) need the TF-Inception evaluator, which is out of scope: their keys are
+printed as null.  Extensions:
+  * ``--seed S`` runs the native likelihood sweep (in-kernel Philox draws, batch g keyed by S + g; one C call per batch,
+    graph-replayed steps); without it the reference's per-step loop with torch's generator runs;
+  * ``--max_batches N`` stops after N test batches; ``--json OUT`` also writes the metrics to a file;
+  * ``--synthetic CONFIG`` builds deterministic synthetic weights when no checkpoint exists (offline boxes).
+"""
+import argparse
+import json
+import os
+import time
+
+import torch
+
+from models import DDPM, DownsampleDDPM, Unet
+from utils import (CHECKPOINT_DIR, DATA_DIR, compute_test_losses, get_color_channels, get_dataloader, get_model_state_dict,
+                   load_checkpoint_file)
+from utils import synthetic as syn
+
+SAMPLE_METRICS = ('is', 'fid', 'sfid', 'precision', 'recall')
+
+
+def main():
+    ap = argparse.ArgumentParser(description="Test-set likelihood (VLB, L_simple) of a trained DDPM / dDDPM checkpoint.")
+    ap.add_argument("--saved_model", default="celeba_x2")
+    ap.add_argument("--fid_samples", type=int, default=50000, help="kept for the reference's interface (sample metrics are out of scope)")
+    ap.add_argument("--batch_size", type=int, default=None, help="test batch size (default: the checkpoint's)")
+    ap.add_argument("--seed", type=int, default=None, help="native sweep with Philox draws, batch g keyed by seed + g")
+    ap.add_argument("--max_batches", type=int, default=None, help="stop after this many test batches")
+    ap.add_argument("--synthetic", default=None, help="JSON config file: use closed-form synthetic weights, no checkpoint")
+    ap.add_argument("--json", default=None, help="also write the metrics to this file")
+    args = ap.parse_args()
+
+    device = 'cuda'
+    step = 0
+    if args.synthetic:
+        with open(args.synthetic) as f:
+            config = json.load(f)
+        model_state_dict = None
+    else:
+        save_data = load_checkpoint_file(os.path.join(CHECKPOINT_DIR, f'{args.saved_model}.pt'))
+        model_state_dict = get_model_state_dict(save_data)
+        config = save_data['config']
+        step = save_data.get('step', 0)
+    # fix config if missing (reference evaluate_ddpm.py:24-28)
+    if config['model'] == 'dddpm' and 'force_latent' not in config:
+        config['force_latent'] = False
+    if args.batch_size is not None:
+        config['batch_size'] = args.batch_size
+
+    test_loader = get_dataloader(config, data_root=DATA_DIR, device=device, train=False)[0]
+
+    print(f'\nLoading model checkpoint {args.saved_model}')
+    print(f'Trained for {step} steps with configuration dict:')
+    print(json.dumps(config, sort_keys=False, indent=4, default=str) + '\n')
+    latent_model = Unet(config)
+    color_channels = get_color_channels(config['dataset'])
+    if config['model'] == 'ddpm':
+        model = DDPM(config, latent_model, device, color_channels)
+    elif config['model'] == 'dddpm':
+        model = DownsampleDDPM(config, latent_model, device, color_channels)
+    else:
+        raise NotImplementedError(config['model'])
+    if model_state_dict is None:
+        model_state_dict = syn.fill_state_dict(model.state_dict(), skip=syn.SCHEDULE_KEYS)
+    model.load_state_dict(model_state_dict)
+    model = model.to(device)
+    model.eval()
+
+    ### COMPUTE METRICS ###
+    print(f'\nComputing test losses over {args.max_batches if args.max_batches is not None else "all"} test batches')
+    metrics = {}
+    time_start = time.time()
+    vlb, L_simple = compute_test_losses(model, test_loader, device, seed=args.seed, max_batches=args.max_batches)
+    torch.cuda.synchronize()
+    print(f'Test loss time: {time.time() - time_start}')
+    metrics['vlb'] = vlb
+    metrics['L_simple'] = L_simple
+    print('Sample metrics (IS, FID, sFID, precision, recall): the TF-Inception evaluator is out of scope; reported as null.')
+    for k in SAMPLE_METRICS:
+        metrics[k] = None
+
+    # Display resulting metrics
+    print('\nResults:')
+    print(json.dumps(metrics, sort_keys=False, indent=4) + '\n')
+    if args.json:
+        with open(args.json, 'w') as f:
+            json.dump(metrics, f, indent=4)
+
+
+if __name__ == '__main__':
+    main()

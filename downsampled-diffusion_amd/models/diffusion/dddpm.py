@@ -94,8 +94,8 @@ class DownsampleDDPM(DDPM):
         return obj, {'latent': L_ddpm.mean(), 'recon': L_rec.mean()}
 
     @torch.no_grad()
-    def test_losses(self, x):
-        return self.test_losses_(self.rescaled_downsample(x))
+    def test_losses(self, x, **kw):
+        return self.test_losses_(self.rescaled_downsample(x), **kw)
 
 
 RECON_SIDE_STREAM = True          # see DownsampleDDPMAutoencoder.losses; the tests switch it off to compare

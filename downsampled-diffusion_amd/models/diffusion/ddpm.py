@@ -4,7 +4,8 @@ its hot path on HIP kernels.
 Hot path (HIP): q_sample, the UNet call, the fused reverse-step update, the T-step sampling loop (one C
 call, hipGraph-replayed), the per-sample squared-error loss.
 Evaluation path: test_losses_ = T x {q_sample kernel, HIP UNet, one fused VLB kernel
-(normal_kl + discretised NLL + flat_bits + L_simple)}; q_mean_variance / q_posterior / p_mean_variance / calc_prior
+(normal_kl + discretised NLL + flat_bits + L_simple)}, or with seed= / noise= the whole sweep as one native call
+(ddk_vlb_sweep_run: the sampler's graph-replayed step with a q_sample input and a VLB epilogue); q_mean_variance / q_posterior / p_mean_variance / calc_prior
 stay plain torch expressions on device tensors (a few [B] / [T] gathers, init-time cost).
 """
 from functools import partial
@@ -252,12 +253,18 @@ class DDPM(nn.Module):
         return flat_bits(normal_kl(mean, log_var, 0., 0.))
 
     @torch.no_grad()
-    def test_losses_(self, x):
+    def test_losses_(self, x, seed=None, noise=None):
         """ddpm.py:393-442: for t = T-1 .. 0: eps ~ N(0,1) (torch's generator, one draw per step like the reference),
         x_t = q_sample, then the VLB term and L_simple of that step.  The reference calls the UNet twice per step on
         identical inputs (vlb_terms, then L_simple); eval-mode forwards are deterministic, so here ONE UNet call feeds one
-        fused kernel that returns both the VLB term and sum (eps - eps_hat)^2.  Returns the reference's dict."""
+        fused kernel that returns both the VLB term and sum (eps - eps_hat)^2.  Returns the reference's dict.
+
+        With ``seed`` (in-kernel Philox draws) or ``noise`` (injected draws, NCHW [T, B, C, H, W], draw k at t = T-1-k) the
+        whole sweep runs natively instead (UnetPlan.vlb_sweep_nhwc: one C call, graph-replayed steps, the sampler's step
+        with a q_sample input and a VLB epilogue).  Without either keyword the loop below runs, with torch's generator."""
         self._check_device(x)
+        if seed is not None or noise is not None:
+            return self._test_losses_native(x, seed, noise)
         vlb_t, l_simple_t = [], []
         n_el = x.numel()
         for t in reversed(range(self.timesteps)):
@@ -275,8 +282,29 @@ class DDPM(nn.Module):
         return {'vlb_t': vlb_t, 'prior': prior, 'vlb': vlb_t.sum(dim=1) + prior,
                 'L_simple_t': l_simple_t, 'L_simple': l_simple_t.sum()}
 
-    def test_losses(self, x):
-        return self.test_losses_(x)
+    def _test_losses_native(self, x, seed, noise):
+        b = x.shape[0]
+        T = self.timesteps
+        nz = None
+        if noise is not None:
+            if tuple(noise.shape) != (T, *x.shape):
+                raise DDKError(f"test_losses: noise must be {(T, *x.shape)}, got {tuple(noise.shape)}")
+            nz = noise.to(x.device).float().permute(0, 1, 3, 4, 2).contiguous()   # [T,B,C,H,W] -> [T,B,H,W,C]
+        tables = dict(sqrt_acp=self.sqrt_alphas_cumprod, sqrt_1m_acp=self.sqrt_one_minus_alphas_cumprod,
+                      c_recip=self.sqrt_recip_alphas_cumprod, c_recipm1=self.sqrt_recipm1_alphas_cumprod,
+                      c1=self.posterior_mean_coef1, c2=self.posterior_mean_coef2, post_logvar=self.posterior_log_variance_clipped)
+        plan = self._eps_model_nhwc().plan()
+        vlb_t, l_simple_t = plan.vlb_sweep_nhwc(ops.nchw_to_nhwc(x.float().contiguous()), tables, T, noise=nz,
+                                                seed=0 if seed is None else int(seed), stream_id=self.rng_stream_id,
+                                                use_graph=self.use_graph)
+        assert vlb_t.shape == (b, T)
+        prior = self.calc_prior(x)
+        return {'vlb_t': vlb_t, 'prior': prior, 'vlb': vlb_t.sum(dim=1) + prior,
+                'L_simple_t': l_simple_t, 'L_simple': l_simple_t.sum()}
+
+    def test_losses(self, x, **kw):
+        """``seed`` / ``noise``: see test_losses_."""
+        return self.test_losses_(x, **kw)
 
     def t_sample(self, n):
         """ddpm.py:448-450."""

@@ -1,4 +1,5 @@
-"""Sampler output stage (reference utils/eval_helpers.py:37-41, generate_model_samples.py:48-69)."""
+"""Sampler output stage (reference utils/eval_helpers.py:37-41, generate_model_samples.py:48-69) and the test-set losses of
+evaluate_ddpm.py (reference utils/eval_helpers.py:24-34)."""
 import os
 
 import numpy as np
@@ -78,3 +79,21 @@ def merge_rank_shards(base_path, world, remove=False):
         for path in paths:          # exactly the shards that were merged: no glob (metacharacters in the name, stale shards of
             os.remove(path)         # an earlier, larger world are not ours to delete unseen)
     return merged
+
+
+def compute_test_losses(model, test_loader, device, seed=None, max_batches=None):
+    """Reference utils/eval_helpers.py:24-34: model.test_losses over the test set; returns (vlb, L_simple) as Python floats,
+    the mean of the per-image bound and the mean of the per-batch L_simple.  seed=None keeps the reference's draws (torch's
+    generator); with a seed, batch g runs the native sweep with Philox key seed + g.  max_batches stops early (None: all)."""
+    vlb = []
+    L_simple = []
+    for g, (x, _) in enumerate(test_loader):
+        if max_batches is not None and g >= max_batches:
+            break
+        x = x.to(device)
+        losses = model.test_losses(x) if seed is None else model.test_losses(x, seed=seed + g)
+        vlb.append(losses['vlb'])
+        L_simple.append(losses['L_simple'])
+    vlb = torch.stack(vlb, dim=1).mean().cpu().numpy().item()
+    L_simple = torch.stack(L_simple, dim=0).mean().cpu().numpy().item()
+    return vlb, L_simple

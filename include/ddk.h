@@ -426,11 +426,45 @@ size_t ddk_sampler_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t
  * Contract: a caller that frees or overwrites `workspace` (or frees any buffer passed here) between calls must call
  * ddk_sampler_invalidate() first. */
 int ddk_sampler_run(const ddk_sampler_args* a, ddk_stream_t s);
-/* Drops the plan's cached sampler graphs and shift table (waits for the device when graphs exist). */
+/* Drops the plan's cached sampler and likelihood-sweep graphs and shift table (waits for the device when graphs exist). */
 int ddk_sampler_invalidate(ddk_unet* u);
 /* Drops only the cached graphs (and shift table) that live in / point into `workspace`, after waiting for the launches of
  * those graphs alone; what was captured on other workspaces stays cached.  Call it before freeing or reusing one workspace. */
 int ddk_sampler_release_workspace(ddk_unet* u, const void* workspace);
+
+/* ------------------------------------------------------------------ likelihood sweep (ddpm.py:392-446, test_losses_) */
+typedef struct ddk_vlb_sweep_args {
+    const ddk_unet* unet;
+    const void* packed;
+    const float* x;           /* NHWC [B][H][W][in_ch]: the clean sample (read only) */
+    const float* noise;       /* NULL -> in-kernel Philox; else [T][B][H][W][in_ch], draw k used at t = T-1-k */
+    const float* sqrt_acp;    /* sqrt_alphas_cumprod [T] */
+    const float* sqrt_1m_acp; /* sqrt_one_minus_alphas_cumprod [T] */
+    const float* c_recip;     /* sqrt_recip_alphas_cumprod [T] */
+    const float* c_recipm1;   /* sqrt_recipm1_alphas_cumprod [T] */
+    const float* c1;          /* posterior_mean_coef1 [T] */
+    const float* c2;          /* posterior_mean_coef2 [T] */
+    const float* post_logvar; /* posterior_log_variance_clipped [T] */
+    int B, H, W;
+    int T;                    /* the sweep runs t = T-1 .. 0 */
+    uint64_t seed;
+    uint32_t stream_id;       /* < 2^31: the Philox stream is stream_id | 2^31, never one of the sampler's */
+    int use_graph;            /* replay captured steps (as ddk_sampler_run) */
+    void* workspace;
+    size_t workspace_bytes;
+    float* vlb_t;             /* out [B][T]: VLB term of step t in bits/dim, column k = T-1-t */
+    float* l_simple_t;        /* out [T]: mean over the batch of (eps - eps_hat)^2, column k = T-1-t */
+} ddk_vlb_sweep_args;
+
+size_t ddk_vlb_sweep_workspace_bytes(const ddk_unet* u, int B, int H, int W, int T);
+/* The T-step test-loss sweep: for t = T-1 .. 0, x_t = q_sample(x, t, eps) with eps the injected draw or Philox (key seed,
+ * stream_id | 2^31, step t), eps_hat = Unet(x_t, t), and per sample the VLB term of ddk_vlb_terms and sum (eps - eps_hat)^2.
+ * A step is the sampler's step with a different first kernel and epilogue: the same in-launch GroupNorm and level chain
+ * (DDK_OPT_CLUSTER_GROUPNORM >= 1: the caller checks ddk_unet_cluster_check on `workspace` after the call, like after
+ * ddk_sampler_run), the same graph cache (entries keyed by the chain kind as well, so a sweep never replays a sampler graph),
+ * dropped by ddk_sampler_invalidate / ddk_sampler_release_workspace.  Per-step partial sums go to the workspace with plain
+ * stores, one slot per workgroup; one kernel after the last step sums them in a fixed order: run-to-run deterministic. */
+int ddk_vlb_sweep_run(const ddk_vlb_sweep_args* a, ddk_stream_t s);
 
 
 /* ================================================================== training path (backward kernels) ==
