@@ -276,3 +276,47 @@ def test_test_losses_vs_reference():
     for k in ("vlb_t", "prior", "vlb", "L_simple_t", "L_simple"):
         assert rel_err(res[k], g[f"simple_{k}"]) < 2e-5, k
     assert np.array_equal(g["simple_vlb_t"], g["hybrid_vlb_t"])     # the hybrid detach does not change values
+
+
+# ---------------------------------------------------------------- G10 whole T = 1000 chain and sweep
+def _tiny_ddpm_state():
+    """det_load weights of the tiny DDPM (unet_chan 32, 3 channels): the dDDPM tiny UNet's keys with 3-channel ends"""
+    shapes = {k: v for k, v in golden_keys()["dddpm_tiny_x2"].items() if k.startswith("latent_model.")}
+    shapes["latent_model.downs.0.0.block1.block.0.weight"] = [32, 3, 3, 3]
+    shapes["latent_model.downs.0.0.res_conv.weight"] = [32, 3, 1, 1]
+    shapes["latent_model.final_conv.1.weight"] = [3, 32, 1, 1]
+    shapes["latent_model.final_conv.1.bias"] = [3]
+    return det_state(shapes)
+
+
+def g10_x():
+    """tools/gen_golden.py:g10_x -- g9's x with its edge values and the exact +-0.999 branch boundary"""
+    x = syn.synthetic_input((2, 3, 16, 16), "g9.x").clamp(-1, 1)
+    x[0, 0, 0, :6] = torch.tensor([-1.0, 1.0, -0.9995, 0.9995, -0.999, 0.999])
+    return x
+
+
+def test_chain_tiny_1000_steps():
+    """the whole T = 1000 chain (t = 999 .. 0, t == 0 unmasked noise-free last step) vs the reference's own p_sample"""
+    g = golden("g10_long")
+    x, snaps = _chain(_tiny_ddpm_state(), ddpm_cfg(32, 3, 16), (2, 3, 16, 16), "g10.chain", 1000, 1000)
+    for s in (1, 500, 900, 990, 999, 1000):
+        assert np.abs(snaps[s].numpy() - g[f"chain_step{s}"]).max() < 2e-5, s
+    assert np.array_equal(x.reshape(2, -1).argmax(dim=1).numpy(), g["argmax"])
+    fixed = D.fix_samples(x)
+    assert np.abs(fixed - g["fixed"]).max() < 5e-3      # [0,255] scale
+    assert (np.round(fixed) != np.round(g["fixed"])).mean() < 1e-3
+
+
+def test_test_losses_T1000_vs_reference():
+    """oracle test_losses over all 1000 timesteps vs the reference's test_losses_ (one injected draw g10.eps{k} per step)"""
+    g = golden("g10_long")
+    cfg = ddpm_cfg(32, 3, 16)
+    sd = _tiny_ddpm_state()
+    buf = D.schedule_buffers("linear", 1000)
+    noises = [syn.synthetic_normal((2, 3, 16, 16), f"g10.eps{k}") for k in range(1000)]
+    res = D.test_losses(buf, lambda a, b: U.unet_forward(sd, cfg, a, b, pre="latent_model."), g10_x(), noises, 1000)
+    for k in ("vlb_t", "prior", "vlb", "L_simple_t", "L_simple"):
+        assert rel_err(res[k], g[f"losses_{k}"]) < 2e-5, k
+    # the t = 0 column is the only one the discretised NLL decides; on its own it is far smaller than the row max
+    assert rel_err(res["vlb_t"][:, -1], g["losses_vlb_t"][:, -1]) < 2e-5

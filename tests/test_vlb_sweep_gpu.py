@@ -1,6 +1,7 @@
 """The native likelihood sweep (ddk_vlb_sweep_run; DDPM.test_losses(x, seed= / noise=)): test_losses_ of reference
 models/diffusion/ddpm.py:392-446 as one graph-replayed chain -- the sampler's step with a q_sample input and a VLB epilogue --
-against the reference golden (g9), today's per-step loop, itself (Philox, cache isolation) and the evaluate_ddpm.py CLI."""
+against the reference golden (g9), today's per-step loop, the CPU oracle at every final-tail width, itself (Philox, cache
+isolation) and the evaluate_ddpm.py CLI."""
 import json
 import os
 import subprocess
@@ -158,3 +159,107 @@ def test_evaluate_ddpm_cli_end_to_end(tmp_path):
     assert all(metrics[k] is None for k in ("is", "fid", "sfid", "precision", "recall"))
     assert all(isinstance(metrics[k], float) and metrics[k] == metrics[k] and abs(metrics[k]) < float("inf") for k in ("vlb", "L_simple"))
     assert "out of scope" in r.stdout
+
+
+# ---------------------------------------------------------------- every final-tail width vs the CPU oracle
+# (unet_chan, in_ch, size, B): which epilogue the sweep's steps end in.  fused_tail_parts (csrc/unet_plan.hip) fuses only when the
+# final conv has a Winograd form (unet_chan % 64 == 0), runs in one pass (conv_wino_splits == 1: at least 256 workgroups without
+# splitting its 32-channel chunks) and final_tail_vlb_ok admits the width (C <= 128).  Confirmed from the kernel names of one
+# rocprofv3 --kernel-trace --stats run of these five sweeps.
+SWEEP_CASES = {
+    "c128_b32_fused": (128, 8, 32, 32),      # final_tail_kernel<32, 1, true>: cfg4's shape
+    "c64_b32_fused": (64, 8, 32, 32),        # final_tail_kernel<16, 1, true>
+    "c64_b8_unfused": (64, 8, 32, 8),        # 64 workgroups: the final conv splits its 2 chunks -> conv + GroupNorm + 1x1
+    "c256_b32_unfused": (256, 3, 16, 32),    # one-pass final conv (2 tiles per image), but C = 256 > 128: final_tail_vlb_ok
+    "c32_b32_unfused": (32, 3, 16, 32),      # no Winograd final conv; vlb_sweep_terms_kernel over 2 slices per image
+}
+EDGES = torch.tensor([-1.0, 1.0, -0.9995, 0.9995, -0.999, 0.999, -0.9989, 0.9989])
+SWEEP_TOL = 5e-5
+T0_TOL = 5e-6         # the t = 0 column on its own (the discretised NLL): measured <= 5.7e-7 over the five cases
+
+
+def edge_x(shape, key):
+    """x in [-1, 1) with the discretised NLL's branch edges: -1, 1, +-0.9995, exactly +-0.999 and +-0.9989, as the first 8 NHWC
+    elements of image 0 (pixel 0 on), the last 8 of the last image (ending at pixel H*W-1: the last 128-pixel tile), and across
+    the last channel of the middle image."""
+    b, c, h, w = shape
+    v = syn.synthetic_input(shape, key).clamp(-1, 1).permute(0, 2, 3, 1).contiguous()
+    v[0].view(-1)[:8] = EDGES
+    v[-1].view(-1)[-8:] = EDGES
+    x = v.permute(0, 3, 1, 2).contiguous()
+    x[b // 2, c - 1].view(-1)[torch.linspace(0, h * w - 1, 8).long()] = EDGES
+    return x
+
+
+def _oracle_sweep(m, cfg, x, noise):
+    from oracle import diffusion_ref as D
+    from oracle import unet_ref as U
+    sd = {k: v.detach().cpu() for k, v in m.state_dict().items()}
+    T = cfg["T"]
+    with torch.no_grad():
+        return D.test_losses(D.schedule_buffers("linear", T), lambda a, t: U.unet_forward(sd, cfg, a, t, pre="latent_model."),
+                             x, list(noise), T)
+
+
+def _sweep_errors(got, want):
+    errs = {k: rel_err(got[k].cpu(), want[k]) for k in KEYS}
+    errs["t0"] = rel_err(got["vlb_t"][:, -1].cpu(), want["vlb_t"][:, -1])
+    errs["t>0"] = rel_err(got["vlb_t"][:, :-1].cpu(), want["vlb_t"][:, :-1])
+    return errs
+
+
+@pytest.mark.parametrize("case", list(SWEEP_CASES))
+def test_sweep_every_tail_width_vs_oracle(case):
+    """ddk_vlb_sweep_run (T = 50, injected draws) vs oracle/diffusion_ref.test_losses: all five keys at 5e-5 relative, the t = 0
+    column -- the only one the NLL branches decide -- on its own at 5e-6.  Negative control: image 0's +0.9995 moved to 0.9985
+    (the upper branch to the middle one) must move that column past 10x its bar while every t > 0 column still passes.  One
+    element of 8192 moves the column by 6e-5 of its max at 8 channels (7e-4 at 3), hence the tighter bar on that column."""
+    chan, cin, size, bsz = SWEEP_CASES[case]
+    cfg = ddpm_cfg(chan, cin, size, T=50)
+    m = _model(cfg)
+    shape = (bsz, cin, size, size)
+    x = edge_x(shape, f"sweep.edge.{case}")
+    noise = torch.stack([syn.synthetic_normal(shape, f"sweep.edge.{case}.n{k}") for k in range(50)])
+    want = _oracle_sweep(m, cfg, x, noise)
+    got = m.test_losses(x.to(DEV), noise=noise.to(DEV))
+    errs = _sweep_errors(got, want)
+    print(f"sweep {case}: relative errors {errs}")
+    assert all(errs[k] < SWEEP_TOL for k in KEYS), errs
+    assert errs["t0"] < T0_TOL, errs
+    moved = x.permute(0, 2, 3, 1).contiguous()
+    assert float(moved[0].view(-1)[3]) == float(EDGES[3])
+    moved[0].view(-1)[3] = 0.9985
+    bad = _sweep_errors(m.test_losses(moved.permute(0, 3, 1, 2).contiguous().to(DEV), noise=noise.to(DEV)), want)
+    print(f"sweep {case}, x[0] 0.9995 -> 0.9985: relative errors {bad}")
+    assert bad["t0"] > 10 * T0_TOL and bad["t>0"] < SWEEP_TOL and bad["L_simple_t"] < SWEEP_TOL, bad
+
+
+def test_sampler_window_at_256_channels_vs_oracle():
+    """the sampler's final_tail_kernel<32, 2, false> (256 channels, 3x16x16, B = 32: two tiles per image, one-pass final conv):
+    20 steps t = 19 .. 0 of replayed graphs with the in-kernel Philox draws vs the oracle fed the same draws (ops.randn, NHWC at
+    step t).  Bar as for the golden chains: 1e-4 abs (measured 7.5e-6), the same argmax pixel per image."""
+    from ddk import ops
+    from oracle import diffusion_ref as D
+    from oracle import unet_ref as U
+    cfg = ddpm_cfg(256, 3, 16, T=50)
+    m = _model(cfg)
+    sd = {k: v.detach().cpu() for k, v in m.state_dict().items()}
+    bsz, seed = 32, 321
+    x0 = syn.synthetic_normal((bsz, 3, 16, 16), "sampler.c256.x")
+    draw = lambda t: ops.randn((bsz, 16, 16, 3), DEV, seed, step=t, stream_id=0).permute(0, 3, 1, 2).cpu()
+    before = ops.cluster_timeouts()
+    x = ops.nchw_to_nhwc(x0.to(DEV).contiguous())
+    with torch.no_grad():
+        m._eps_model_nhwc().plan().sample_nhwc(x, m._tables(), 19, 0, seed=seed, stream_id=0, use_graph=True)
+    got = ops.nhwc_to_nchw(x).cpu()
+    assert ops.cluster_timeouts() == before
+    buf = D.schedule_buffers("linear", 50)
+    want = x0
+    with torch.no_grad():
+        for i in range(19, -1, -1):
+            t = torch.full((bsz,), i, dtype=torch.long)
+            want = D.p_sample_update(buf, want, t, U.unet_forward(sd, cfg, want, t, pre="latent_model."), draw(i))
+    err = float((got - want).abs().max())
+    print(f"sampler c256 B=32 t=19..0 Philox: max abs error {err:.3g}")
+    assert err <= 1e-4
+    assert torch.equal(got.reshape(bsz, -1).argmax(dim=1), want.reshape(bsz, -1).argmax(dim=1))

@@ -350,9 +350,42 @@ def g9_test_losses():
     save("g9_test_losses", **out)
 
 
+# ---------------------------------------------------------------- G10 whole T = 1000 chain and sweep
+def g10_x():
+    """g9's x (with its row of edge values) plus the exact +-0.999 boundary of the discretised NLL's branches."""
+    x = syn.synthetic_input((2, 3, 16, 16), "g9.x").clamp(-1, 1)
+    x[0, 0, 0, :6] = torch.tensor([-1.0, 1.0, -0.9995, 0.9995, -0.999, 0.999])
+    return x
+
+
+@torch.no_grad()
+def g10_long():
+    """The tiny DDPM (unet_chan 32, 16x16, linear schedule, T = 1000) over its whole chain: the reference's p_sample for all
+    1000 steps (t = 999 .. 0, injected draws g10.chain.n{k}) and its test_losses_ for all 1000 timesteps (one injected draw
+    g10.eps{k} per step, torch.randn_like patched as in g9)."""
+    out = {}
+    cfg = ddpm_cfg(32, 3, 16)
+    m = det_load(DDPM(cfg, Unet(cfg), "cpu", 3).eval())
+    x, got = run_chain(m, (2, 3, 16, 16), "g10.chain", 1000, snaps=(1, 500, 900, 990, 999, 1000))
+    for s, v in got.items():
+        out[f"chain_step{s}"] = v.numpy()
+    out["fixed"] = uu.min_max_norm_image(x).mul(255.).numpy().transpose(0, 2, 3, 1)     # eval_helpers.py:37-41
+    out["argmax"] = x.reshape(2, -1).argmax(dim=1).numpy()
+    draws = iter([syn.synthetic_normal((2, 3, 16, 16), f"g10.eps{k}") for k in range(1000)])
+    orig = torch.randn_like
+    torch.randn_like = lambda z: next(draws)
+    try:
+        res = m.test_losses(g10_x())
+    finally:
+        torch.randn_like = orig
+    for k, v in res.items():
+        out[f"losses_{k}"] = v.numpy()
+    save("g10_long", **out)
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g0", "g1", "g2", "g3", "g4", "g6", "g7", "g8", "g9"]
+    which = sys.argv[1:] or ["g0", "g1", "g2", "g3", "g4", "g6", "g7", "g8", "g9", "g10"]
     table = dict(g0=g0_keys, g1=g1_schedule, g2=g2_blocks, g3=g3_unet, g4=g4_chain, g6=g6_train, g7=g7_qsample_loss,
-                 g8=g8_resamplers, g9=g9_test_losses)
+                 g8=g8_resamplers, g9=g9_test_losses, g10=g10_long)
     for w in which:
         table[w]()
