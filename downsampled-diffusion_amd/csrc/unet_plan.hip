@@ -9,6 +9,7 @@
 // arithmetic step is a HIP kernel from the other translation units.  The sampler captures one reverse step
 // (t bookkeeping + UNet + x update) into a hipGraph and replays it, so the T-step loop costs one
 // hipGraphLaunch per step on the host.
+#include <algorithm>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -113,7 +114,12 @@ struct ddk_unet {
     std::vector<SamplerGraph> graphs;
     unsigned long long use_clock = 0;
     unsigned long long pack_epoch = 0;       // bumped by every pack / finalize: weights changed
-    struct { const void* ws = nullptr; int t_start = -1, B = 0, H = 0, W = 0; unsigned long long pack_epoch = 0; } table;
+    struct {
+        const void* ws = nullptr;
+        int t_start = -1, B = 0, H = 0, W = 0;
+        unsigned long long pack_epoch = 0;
+        std::vector<int64_t> map;            // timestep of each row (ddk_sampler_run_spaced); empty: row k is timestep k
+    } table;
     ddk_unet_config cfg;
     int cluster_gn = 1;                      // GroupNorm finished inside the Winograd conv launch where eligible (ddk_unet_set_option):
                                              // 0 never, 1 in ddk_sampler_run (whose caller checks ddk_unet_cluster_check at the chain's
@@ -1616,20 +1622,32 @@ extern "C" size_t ddk_sampler_workspace_bytes(const ddk_unet* u, int B, int H, i
 }
 
 namespace ddk {
-// Time-shift table for t = 0..t_start: the same two kernels a forward runs, once, with "batch" = all timesteps.  It lives in the
-// caller's workspace (sampler_layout: the sweep's workspace starts with the same layout) and stays valid while neither the weights
-// (pack_epoch) nor the workspace change; a caller that rewrites or frees the workspace between calls says so with
-// ddk_sampler_invalidate().
+// Time-shift table for rows 0..t_start: the same two kernels a forward runs, once, with "batch" = all rows.  Row k holds the shifts
+// of timestep map[k] (map == nullptr: timestep k).  It lives in the caller's workspace (sampler_layout: the sweep's workspace starts
+// with the same layout) and stays valid while neither the weights (pack_epoch), the workspace nor the map change; the key keeps a
+// copy of the map, so a respaced chain and a plain chain of the same length on one workspace never read each other's rows.  A
+// caller that rewrites or frees the workspace between calls says so with ddk_sampler_invalidate().
 static int ensure_temb_table(ddk_unet& u, const float* P, float* ws, const SamplerLayout& sl, int t_start, int B, int H, int W,
-                             hipStream_t st) {
-    if (u.table.ws == ws && u.table.t_start == t_start && u.table.B == B && u.table.H == H && u.table.W == W &&
-        u.table.pack_epoch == u.pack_epoch)
-        return DDK_OK;
+                             hipStream_t st, const int64_t* map = nullptr) {
     const int rows = t_start + 1;
+    const bool same_map = map ? (u.table.map.size() == (size_t)rows && std::equal(map, map + rows, u.table.map.begin()))
+                              : u.table.map.empty();
+    if (u.table.ws == ws && u.table.t_start == t_start && u.table.B == B && u.table.H == H && u.table.W == W &&
+        u.table.pack_epoch == u.pack_epoch && same_map)
+        return DDK_OK;
+    u.table.ws = nullptr;                    // a rebuild that fails half way leaves no valid table behind
     int64_t* t_all = reinterpret_cast<int64_t*>(ws + sl.off_tall);
     float* tact_all = ws + sl.off_tact_all;
-    hipLaunchKernelGGL(iota64_kernel, dim3((unsigned)ceil_div(rows, 256)), dim3(256), 0, st, t_all, rows);
-    DDK_TRY(check_launch("iota64_kernel"));
+    if (map) {
+        // the plan's own copy is the source; the wait keeps it alive (and the caller's array free) until the copy has landed
+        u.table.map.assign(map, map + rows);
+        DDK_HIP(hipMemcpyAsync(t_all, u.table.map.data(), (size_t)rows * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        DDK_HIP(hipStreamSynchronize(st));
+    } else {
+        u.table.map.clear();
+        hipLaunchKernelGGL(iota64_kernel, dim3((unsigned)ceil_div(rows, 256)), dim3(256), 0, st, t_all, rows);
+        DDK_TRY(check_launch("iota64_kernel"));
+    }
     DDK_TRY(time_mlp(t_all, P + u.freqs, P + u.w1t, P + u.b1, P + u.w2t, P + u.b2, tact_all, nullptr, rows, u.time_dim, st));
     DDK_TRY(time_proj(tact_all, P + u.temb_wt, P + u.temb_bias, ws + sl.off_table, rows, u.time_dim, u.temb_total, st));
     u.table.ws = ws; u.table.t_start = t_start; u.table.B = B; u.table.H = H; u.table.W = W;
@@ -1718,12 +1736,28 @@ static int run_chain(ddk_unet& u, const ChainKey& key, int n_steps, bool use_gra
 }  // namespace ddk
 
 extern "C" int ddk_sampler_run(const ddk_sampler_args* a, ddk_stream_t s) {
+    return ddk_sampler_run_spaced(a, nullptr, s);
+}
+
+extern "C" int ddk_sampler_run_spaced(const ddk_sampler_args* a, const int64_t* timestep_map, ddk_stream_t s) {
     DDK_REQUIRE(a && a->unet && a->packed && a->x && a->workspace, "sampler: null pointer");
     DDK_REQUIRE(a->c_recip && a->c_recipm1 && a->c1 && a->c2 && a->sigma, "sampler: null schedule table");
     ddk_unet& u = *const_cast<ddk_unet*>(a->unet);     // the graph / table cache is logically mutable state of the plan
     DDK_TRY(check_shape(&u, a->B, a->H, a->W));
     DDK_REQUIRE(a->t_start >= a->t_end && a->t_end >= 0, "sampler: need t_start >= t_end >= 0");
     DDK_REQUIRE(aligned16(a->packed) && aligned16(a->workspace) && aligned16(a->x) && aligned16(a->noise), "sampler: alignment");
+    if (timestep_map) {
+        if (timestep_map[0] != 0) {
+            set_error("sampler: timestep_map[0] must be 0, got %lld", (long long)timestep_map[0]);
+            return DDK_ERR_ARG;
+        }
+        for (int k = 1; k <= a->t_start; ++k)
+            if (timestep_map[k] <= timestep_map[k - 1] || timestep_map[k] >= (int64_t(1) << 31)) {
+                set_error("sampler: timestep_map must increase strictly and stay below 2^31 (entry %d = %lld after %lld)", k,
+                          (long long)timestep_map[k], (long long)timestep_map[k - 1]);
+                return DDK_ERR_ARG;
+            }
+    }
     const int B = a->B, H = a->H, W = a->W, C = u.cfg.in_ch;
     const long long per = (long long)H * W * C;
     DDK_REQUIRE(per % 4 == 0, "sampler: H*W*in_ch must be a multiple of 4");
@@ -1753,7 +1787,7 @@ extern "C" int ddk_sampler_run(const ddk_sampler_args* a, ddk_stream_t s) {
     DDK_HIP(hipMemsetAsync(ws + ly.off_cl, 0, cl_counter_floats(B) * sizeof(float), st));    // cluster GroupNorm counters (outside the graph)
     hipLaunchKernelGGL(set_chain_state_kernel, dim3(1), dim3(1), 0, st, state, (int64_t)a->t_start, a->seed, a->stream_id);
     DDK_TRY(check_launch("set_chain_state_kernel"));
-    DDK_TRY(ensure_temb_table(u, P, ws, sl, a->t_start, B, H, W, st));
+    DDK_TRY(ensure_temb_table(u, P, ws, sl, a->t_start, B, H, W, st, timestep_map));
     const int n_steps = a->t_start - a->t_end + 1;
     int dev = 0;
     if (a->use_graph && n_steps > 1) DDK_HIP(hipGetDevice(&dev));

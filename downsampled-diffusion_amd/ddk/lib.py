@@ -171,6 +171,7 @@ SIGNATURES = {
     "ddk_unet_flops_executed": (C.c_double, [_P, _I, _I, _I]),
     "ddk_sampler_workspace_bytes": (_SZ, [_P, _I, _I, _I, _I]),
     "ddk_sampler_run": (_I, [C.POINTER(SamplerArgs), _P]),
+    "ddk_sampler_run_spaced": (_I, [C.POINTER(SamplerArgs), C.POINTER(C.c_int64), _P]),
     "ddk_sampler_invalidate": (_I, [_P]),
     "ddk_sampler_release_workspace": (_I, [_P, _P]),
     "ddk_vlb_sweep_workspace_bytes": (_SZ, [_P, _I, _I, _I, _I]),

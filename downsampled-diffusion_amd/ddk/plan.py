@@ -161,16 +161,23 @@ class UnetPlan:
         return out
 
     # ---------------------------------------------------------------- sampler
-    def sample_nhwc(self, x, tables, t_start, t_end=0, noise=None, seed=0, stream_id=0, use_graph=True):
+    def sample_nhwc(self, x, tables, t_start, t_end=0, noise=None, seed=0, stream_id=0, use_graph=True, timesteps=None):
         """Run steps t_start .. t_end (inclusive) of the reverse chain in place on x [B,H,W,in_ch].
 
         tables: dict with c_recip, c_recipm1, c1, c2, sigma ([T] fp32 device tensors).
         noise: optional [n_steps,B,H,W,in_ch] injected draws (parity tests); else in-kernel Philox.
+        timesteps: optional timestep map of a respaced / DDIM chain (t_start + 1 ints, map[0] == 0, increasing): step k runs
+        the UNet at timesteps[k] while the tables and the Philox draws are indexed by k (ddk_sampler_run_spaced).
         """
         if self.packed is None:
             raise L.DDKError("UnetPlan.sample before pack()")
         b, h, w, c = x.shape
         lib = self._lib
+        tmap = None
+        if timesteps is not None:
+            if len(timesteps) != t_start + 1:
+                raise L.DDKError(f"timestep map must have t_start + 1 = {t_start + 1} entries, got {len(timesteps)}")
+            tmap = (C.c_int64 * len(timesteps))(*[int(v) for v in timesteps])
         nbytes = lib.ddk_sampler_workspace_bytes(self.handle, b, h, w, t_start)
         if nbytes == 0:
             raise L.DDKError(f"sampler workspace query failed: {L.last_error()}")
@@ -203,7 +210,10 @@ class UnetPlan:
             a = L.SamplerArgs(self.handle, L.ptr(self.packed), L.ptr(x), L.ptr(noise), L.ptr(tables["c_recip"]),
                               L.ptr(tables["c_recipm1"]), L.ptr(tables["c1"]), L.ptr(tables["c2"]), L.ptr(tables["sigma"]),
                               b, h, w, t_start, t_end, seed, stream_id, int(use_graph), L.ptr(ws), nbytes)
-            L.check(lib.ddk_sampler_run(C.byref(a), stream_ptr), "sampler_run")
+            if tmap is None:
+                L.check(lib.ddk_sampler_run(C.byref(a), stream_ptr), "sampler_run")
+            else:
+                L.check(lib.ddk_sampler_run_spaced(C.byref(a), tmap, stream_ptr), "sampler_run_spaced")
 
         def run():
             """Issues the chain; with the in-launch GroupNorm on, waits for it (the chain's sync point: T steps of work

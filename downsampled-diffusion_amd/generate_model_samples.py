@@ -11,7 +11,10 @@ The reference hard-codes its constants; here they are the defaults of optional f
     (x_T, Philox key) depend only on its GLOBAL batch index, so the merged file is bit-identical to a 1-process run;
   * the device -> host stage is asynchronous (utils.OutputStage: pinned double buffer + events), so a batch's copy
     overlaps the next batch's sampling;
-  * ``--synthetic CONFIG`` builds deterministic synthetic weights when no checkpoint exists (offline boxes).
+  * ``--synthetic CONFIG`` builds deterministic synthetic weights when no checkpoint exists (offline boxes);
+  * ``--timestep_respacing SPEC``, ``--use_ddim`` and ``--eta`` (improved-diffusion's flag names) sample K of the T steps,
+    ancestrally or with DDIM (models/diffusion/respace.py).  With any of them set the output name gains a suffix such as
+    ``_ddim50_ddim_eta0``, so the full-chain samples of the same checkpoint are never overwritten.
 """
 import argparse
 import json
@@ -39,7 +42,18 @@ def main():
     ap.add_argument("--out_dir", default=None)
     ap.add_argument("--seed", type=int, default=1234, help="base seed: batch g of the job draws from seed + g")
     ap.add_argument("--keep_shards", action="store_true", help="keep the per-rank .rank{r}.npy files after the merge")
+    ap.add_argument("--timestep_respacing", default="", help='sample K of the T steps: "ddimN", "N" or "n1,n2,..." sections')
+    ap.add_argument("--use_ddim", action="store_true", help="DDIM steps instead of ancestral ones")
+    ap.add_argument("--eta", type=float, default=0.0, help="DDIM noise scale (0: deterministic)")
     args = ap.parse_args()
+    if args.eta < 0 or (args.eta != 0.0 and not args.use_ddim):
+        ap.error("--eta needs --use_ddim and a value >= 0")
+    spaced = bool(args.timestep_respacing) or args.use_ddim or args.eta != 0.0
+    sample_kw = dict(respacing=args.timestep_respacing or None, ddim=args.use_ddim, eta=args.eta) if spaced else {}
+    # full-chain runs keep the reference's file names; spaced runs write beside them
+    suffix = ""
+    if spaced:
+        suffix = "_" + (args.timestep_respacing.replace(",", "-") or "full") + (f"_ddim_eta{args.eta:g}" if args.use_ddim else "")
 
     rank, world = init_from_env()
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -101,7 +115,7 @@ def main():
     time_start = time.time()
     for g in range(g0, g0 + n_batches):
         torch.manual_seed(args.seed + g)          # x_T and the Philox key of batch g: the same on whichever rank runs it
-        samples = model.sample(bs, args.sample_every, args.early_stop)
+        samples = model.sample(bs, args.sample_every, args.early_stop, **sample_kw)
         if config["model"] == "dddpm":
             samples, latent_samples = samples
             latent_stage.submit(latent_samples)
@@ -127,11 +141,12 @@ def main():
         main_rank_does(lambda: merge_rank_shards(base, world, remove=not args.keep_shards) is None, "merge of the sampling shards")
         return base
 
-    save_path = save(args.out_dir or SAMPLE_DIR, args.saved_model, sample_list)
+    name = args.saved_model + suffix
+    save_path = save(args.out_dir or SAMPLE_DIR, name, sample_list)
     if rank == 0:
         print(f"Samples saved to {save_path}")
     if config["model"] == "dddpm":
-        save_path = save(args.out_dir or SAMPLE_LATENT_DIR, args.saved_model + "_latent" if args.out_dir else args.saved_model, latent_list)
+        save_path = save(args.out_dir or SAMPLE_LATENT_DIR, name + "_latent" if args.out_dir else name, latent_list)
         if rank == 0:
             print(f"Latent samples saved to {save_path}")
 

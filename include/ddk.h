@@ -426,6 +426,15 @@ size_t ddk_sampler_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t
  * Contract: a caller that frees or overwrites `workspace` (or frees any buffer passed here) between calls must call
  * ddk_sampler_invalidate() first. */
 int ddk_sampler_run(const ddk_sampler_args* a, ddk_stream_t s);
+/* A respaced / DDIM chain (improved-diffusion's SpacedDiffusion): ddk_sampler_run with step k (t_start .. t_end, counted in
+ * the spaced chain) running the UNet at the ORIGINAL timestep timestep_map[k].  timestep_map is a HOST array of t_start + 1
+ * entries: map[0] == 0, strictly increasing, every entry < 2^31 (else DDK_ERR_ARG); the caller may free it as soon as the call
+ * returns.  The schedule tables of `a` have t_start + 1 rows and are indexed by k (the spaced DDPM's own buffers, or DDIM's
+ * coefficients written in the same linear form); injected draws are in run order and the in-kernel Philox draw of step k is
+ * keyed by k.  Row k of the shift table in `workspace` holds the shifts of map[k]: the plan keys that table by a copy of the
+ * map and rebuilds it (one upload and a stream wait, outside any captured step) when a call brings a different map.
+ * timestep_map == NULL is the identity: exactly ddk_sampler_run. */
+int ddk_sampler_run_spaced(const ddk_sampler_args* a, const int64_t* timestep_map, ddk_stream_t s);
 /* Drops the plan's cached sampler and likelihood-sweep graphs and shift table (waits for the device when graphs exist). */
 int ddk_sampler_invalidate(ddk_unet* u);
 /* Drops only the cached graphs (and shift table) that live in / point into `workspace`, after waiting for the launches of
