@@ -451,81 +451,39 @@ extern "C" int ddk_sampler_release_workspace(ddk_unet* u, const void* workspace)
 
 extern "C" int ddk_unet_set_option(ddk_unet* u, int option, int value) {
     DDK_REQUIRE(u, "unet_set_option: null plan");
-    if (option == DDK_OPT_CLUSTER_GROUPNORM) {
-        std::lock_guard<std::mutex> lock(u->mu);
-        if (!u->graphs.empty()) DDK_HIP(hipDeviceSynchronize());
-        drop_graphs(u);                          // a captured step bakes the choice in
-        u->cluster_gn = value < 0 ? 0 : value > 2 ? 2 : value;
-        return DDK_OK;
-    }
-    if (option == DDK_OPT_ATTENTION_FOLD) {
-        std::lock_guard<std::mutex> lock(u->mu);
-        if (!u->graphs.empty()) DDK_HIP(hipDeviceSynchronize());
-        drop_graphs(u);
-        u->attn_fold = value != 0;
-        return DDK_OK;
-    }
-    if (option == DDK_OPT_ATTENTION_KV_CONTEXT) {
-        std::lock_guard<std::mutex> lock(u->mu);
-        if (!u->graphs.empty()) DDK_HIP(hipDeviceSynchronize());
-        drop_graphs(u);
-        u->attn_kvctx = value != 0;
-        return DDK_OK;
-    }
-    if (option == DDK_OPT_FIRST_GROUPNORM) {
-        std::lock_guard<std::mutex> lock(u->mu);
-        if (!u->graphs.empty()) DDK_HIP(hipDeviceSynchronize());
-        drop_graphs(u);
-        u->first_gn = value != 0;
-        return DDK_OK;
-    }
-    if (option == DDK_OPT_LEVEL_CHAIN) {
-        std::lock_guard<std::mutex> lock(u->mu);
-        if (!u->graphs.empty()) DDK_HIP(hipDeviceSynchronize());
-        drop_graphs(u);
+    // a captured step bakes every choice in: setting one waits for the cached graphs and drops them first (drops_graphs)
+    static const struct {
+        int option;
+        bool drops_graphs;
+        void (*set)(ddk_unet&, int);
+    } options[] = {
+        {DDK_OPT_CLUSTER_GROUPNORM, true, [](ddk_unet& p, int v) { p.cluster_gn = v < 0 ? 0 : v > 2 ? 2 : v; }},
+        {DDK_OPT_ATTENTION_FOLD, true, [](ddk_unet& p, int v) { p.attn_fold = v != 0; }},
+        {DDK_OPT_ATTENTION_KV_CONTEXT, true, [](ddk_unet& p, int v) { p.attn_kvctx = v != 0; }},
+        {DDK_OPT_FIRST_GROUPNORM, true, [](ddk_unet& p, int v) { p.first_gn = v != 0; }},
         // 0 off, 1 (default): the 4x4 level with its Downsample / Upsample convs, 2: the 4x4 level alone, 3: the 8x8 levels as well,
         // 4: the 8x8 levels only, 8 / 16: only downs[-2] / only ups[1]
-        u->level_chain = value == 1 ? 9 : value == 2 ? 1 : value == 3 ? 15 : value == 4 ? 6 : value == 8 ? 2 : value == 16 ? 4 : value != 0 ? 9 : 0;
-        return DDK_OK;
-    }
-    if (option == DDK_OPT_FOLD_DOWNSAMPLE_REDUCE) {
+        {DDK_OPT_LEVEL_CHAIN, true, [](ddk_unet& p, int v) {
+             p.level_chain = v == 1 ? 9 : v == 2 ? 1 : v == 3 ? 15 : v == 4 ? 6 : v == 8 ? 2 : v == 16 ? 4 : v != 0 ? 9 : 0;
+         }},
+        {DDK_OPT_FOLD_DOWNSAMPLE_REDUCE, true, [](ddk_unet& p, int v) { p.fold_down_reduce = v != 0; }},
+        // diagnostics (not in ddk.h): largest batch the level chain takes; the folded attention block from this many pixels up;
+        // cap on the cluster launches per forward (no graph is dropped); largest cluster size that takes the in-launch GroupNorm;
+        // the in-launch GroupNorm on channel-chunk-split shapes
+        {10, true, [](ddk_unet& p, int v) { p.level_chain_max_batch = v; }},
+        {9, true, [](ddk_unet& p, int v) { p.attn_fold_min_hw = v; }},
+        {2, false, [](ddk_unet& p, int v) { p.cluster_limit = v; }},
+        {4, true, [](ddk_unet& p, int v) { p.cluster_np_max = v; }},
+        {11, true, [](ddk_unet& p, int v) { p.cluster_split = v != 0; }},
+    };
+    for (const auto& o : options) {
+        if (o.option != option) continue;
         std::lock_guard<std::mutex> lock(u->mu);
-        if (!u->graphs.empty()) DDK_HIP(hipDeviceSynchronize());
-        drop_graphs(u);
-        u->fold_down_reduce = value != 0;
-        return DDK_OK;
-    }
-    if (option == 10) {  // diagnostic (not in ddk.h): largest batch the level chain takes
-        std::lock_guard<std::mutex> lock(u->mu);
-        if (!u->graphs.empty()) DDK_HIP(hipDeviceSynchronize());
-        drop_graphs(u);
-        u->level_chain_max_batch = value;
-        return DDK_OK;
-    }
-    if (option == 9) {   // diagnostic (not in ddk.h): the folded attention block from this many pixels up
-        std::lock_guard<std::mutex> lock(u->mu);
-        if (!u->graphs.empty()) DDK_HIP(hipDeviceSynchronize());
-        drop_graphs(u);
-        u->attn_fold_min_hw = value;
-        return DDK_OK;
-    }
-    if (option == 2) {   // diagnostic (not in ddk.h): cap on the cluster launches per forward
-        std::lock_guard<std::mutex> lock(u->mu);
-        u->cluster_limit = value;
-        return DDK_OK;
-    }
-    if (option == 4) {   // diagnostic (not in ddk.h): largest cluster size that takes the in-launch GroupNorm
-        std::lock_guard<std::mutex> lock(u->mu);
-        if (!u->graphs.empty()) DDK_HIP(hipDeviceSynchronize());
-        drop_graphs(u);
-        u->cluster_np_max = value;
-        return DDK_OK;
-    }
-    if (option == 11) {  // diagnostic (not in ddk.h): the in-launch GroupNorm on channel-chunk-split shapes
-        std::lock_guard<std::mutex> lock(u->mu);
-        if (!u->graphs.empty()) DDK_HIP(hipDeviceSynchronize());
-        drop_graphs(u);
-        u->cluster_split = value != 0;
+        if (o.drops_graphs) {
+            if (!u->graphs.empty()) DDK_HIP(hipDeviceSynchronize());
+            drop_graphs(u);
+        }
+        o.set(*u, value);
         return DDK_OK;
     }
     return fail_arg("unet_set_option: unknown option");
@@ -1628,7 +1586,7 @@ namespace ddk {
 // copy of the map, so a respaced chain and a plain chain of the same length on one workspace never read each other's rows.  A
 // caller that rewrites or frees the workspace between calls says so with ddk_sampler_invalidate().
 static int ensure_temb_table(ddk_unet& u, const float* P, float* ws, const SamplerLayout& sl, int t_start, int B, int H, int W,
-                             hipStream_t st, const int64_t* map = nullptr) {
+                             hipStream_t st, const int64_t* map) {
     const int rows = t_start + 1;
     const bool same_map = map ? (u.table.map.size() == (size_t)rows && std::equal(map, map + rows, u.table.map.begin()))
                               : u.table.map.empty();
@@ -1733,6 +1691,63 @@ static int run_chain(ddk_unet& u, const ChainKey& key, int n_steps, bool use_gra
     DDK_HIP(hipEventRecord(hit->done, st));
     return DDK_OK;
 }
+
+// What a chain entry (ddk_sampler_run_spaced, ddk_vlb_sweep_run) hands its steps and run_chain, filled by begin_chain.
+struct ChainRun {
+    ddk_unet* u;
+    int B, H, W;
+    const float* P;
+    float* ws;
+    Layout ly;
+    SamplerLayout sl;                        // the workspace starts with the sampler's layout (the sweep's too)
+    int64_t* t_cur;
+    int64_t* state;                          // [0] step counter, [1] seed, [2] stream id
+    long long per;                           // H * W * in_ch
+    hipStream_t st;
+    int dev = 0;                             // the current device: part of the graph cache key
+    std::unique_lock<std::mutex> lock;       // u->mu, held until the entry returns
+
+    // one UNet forward of a step on `x`: the counter bookkeeping in its first kernel, step->vlb or the reverse update in its last
+    int forward(const float* x, const StepArgs* step) {
+        return forward_core(*u, P, x, t_cur, nullptr, B, H, W, ws, ly, st, u->cluster_gn >= 1, ws + sl.off_table, step);
+    }
+};
+
+// The prologue both chains share, after the entry's own argument checks: shape, alignment and workspace (`workspace_floats`
+// is what the entry needs in all, given the sampler layout), then under the plan's lock the cluster counters' memset, the
+// chain state {t_start, seed, stream_id} and the time-shift table of rows 0..t_start (map: ensure_temb_table).
+template <class Args, class Need>
+static int begin_chain(ChainRun& c, const Args* a, const char* who, int t_start, uint32_t stream_id, const int64_t* map, int n_steps,
+                       Need&& workspace_floats, ddk_stream_t s) {
+    c.u = const_cast<ddk_unet*>(a->unet);   // the graph / table cache is logically mutable state of the plan
+    const int B = a->B, H = a->H, W = a->W;
+    c.B = B; c.H = H; c.W = W;
+    DDK_TRY(check_shape(c.u, B, H, W));
+    if (!(aligned16(a->packed) && aligned16(a->workspace) && aligned16(a->x) && aligned16(a->noise)))
+        return fail_arg((std::string(who) + ": alignment").c_str());
+    c.per = (long long)H * W * c.u->cfg.in_ch;
+    if (c.per % 4) return fail_arg((std::string(who) + ": H*W*in_ch must be a multiple of 4").c_str());
+    c.sl = sampler_layout(*c.u, B, H, W, t_start);
+    const size_t need = workspace_floats(c.sl) * sizeof(float);
+    if (a->workspace_bytes < need) {
+        set_error("%s: workspace too small (%zu < %zu)", who, a->workspace_bytes, need);
+        return DDK_ERR_WORKSPACE;
+    }
+    DDK_TRY(ensure_device_init());
+    c.ly = make_layout(*c.u, B, H, W);
+    c.st = as_stream(s);
+    c.ws = static_cast<float*>(a->workspace);
+    c.P = static_cast<const float*>(a->packed);
+    c.t_cur = reinterpret_cast<int64_t*>(c.ws + c.sl.off_t);
+    c.state = c.t_cur + B;
+    c.lock = std::unique_lock<std::mutex>(c.u->mu);
+    DDK_HIP(hipMemsetAsync(c.ws + c.ly.off_cl, 0, cl_counter_floats(B) * sizeof(float), c.st));  // cluster GroupNorm counters (outside the graph)
+    hipLaunchKernelGGL(set_chain_state_kernel, dim3(1), dim3(1), 0, c.st, c.state, (int64_t)t_start, a->seed, stream_id);
+    DDK_TRY(check_launch("set_chain_state_kernel"));
+    DDK_TRY(ensure_temb_table(*c.u, c.P, c.ws, c.sl, t_start, B, H, W, c.st, map));
+    if (a->use_graph && n_steps > 1) DDK_HIP(hipGetDevice(&c.dev));
+    return DDK_OK;
+}
 }  // namespace ddk
 
 extern "C" int ddk_sampler_run(const ddk_sampler_args* a, ddk_stream_t s) {
@@ -1742,10 +1757,7 @@ extern "C" int ddk_sampler_run(const ddk_sampler_args* a, ddk_stream_t s) {
 extern "C" int ddk_sampler_run_spaced(const ddk_sampler_args* a, const int64_t* timestep_map, ddk_stream_t s) {
     DDK_REQUIRE(a && a->unet && a->packed && a->x && a->workspace, "sampler: null pointer");
     DDK_REQUIRE(a->c_recip && a->c_recipm1 && a->c1 && a->c2 && a->sigma, "sampler: null schedule table");
-    ddk_unet& u = *const_cast<ddk_unet*>(a->unet);     // the graph / table cache is logically mutable state of the plan
-    DDK_TRY(check_shape(&u, a->B, a->H, a->W));
     DDK_REQUIRE(a->t_start >= a->t_end && a->t_end >= 0, "sampler: need t_start >= t_end >= 0");
-    DDK_REQUIRE(aligned16(a->packed) && aligned16(a->workspace) && aligned16(a->x) && aligned16(a->noise), "sampler: alignment");
     if (timestep_map) {
         if (timestep_map[0] != 0) {
             set_error("sampler: timestep_map[0] must be 0, got %lld", (long long)timestep_map[0]);
@@ -1758,42 +1770,19 @@ extern "C" int ddk_sampler_run_spaced(const ddk_sampler_args* a, const int64_t* 
                 return DDK_ERR_ARG;
             }
     }
-    const int B = a->B, H = a->H, W = a->W, C = u.cfg.in_ch;
-    const long long per = (long long)H * W * C;
-    DDK_REQUIRE(per % 4 == 0, "sampler: H*W*in_ch must be a multiple of 4");
-    const SamplerLayout sl = sampler_layout(u, B, H, W, a->t_start);
-    if (a->workspace_bytes < sl.total * sizeof(float)) {
-        set_error("sampler: workspace too small (%zu < %zu)", a->workspace_bytes, sl.total * sizeof(float));
-        return DDK_ERR_WORKSPACE;
-    }
-    DDK_TRY(ensure_device_init());
-    const Layout ly = make_layout(u, B, H, W);
-    hipStream_t st = as_stream(s);
-    float* ws = static_cast<float*>(a->workspace);
-    float* eps_hat = ws + sl.off_eps;
-    int64_t* t_cur = reinterpret_cast<int64_t*>(ws + sl.off_t);
-    int64_t* state = t_cur + B;                        // [0] step counter, [1] seed, [2] stream id
-    const float* P = static_cast<const float*>(a->packed);
-    const float* temb_table = ws + sl.off_table;
-    const StepArgs step{state, a->x, eps_hat, a->noise, a->noise ? B * per : 0, a->t_start, a->c_recip, a->c_recipm1, a->c1, a->c2,
-                        a->sigma, per};
+    const int B = a->B, H = a->H, W = a->W, n_steps = a->t_start - a->t_end + 1;
+    ChainRun c;
+    DDK_TRY(begin_chain(c, a, "sampler", a->t_start, a->stream_id, timestep_map, n_steps,
+                        [](const SamplerLayout& sl) { return sl.total; }, s));
+    const StepArgs step{c.state, a->x, c.ws + c.sl.off_eps, a->noise, a->noise ? B * c.per : 0, a->t_start, a->c_recip, a->c_recipm1,
+                        a->c1, a->c2, a->sigma, c.per};
 
     // one reverse step: bookkeeping (in the forward's first kernel), UNet, update of x (in its last kernel)
-    auto one_step = [&]() -> int {
-        return forward_core(u, P, a->x, t_cur, nullptr, B, H, W, ws, ly, st, u.cluster_gn >= 1, temb_table, &step);
-    };
+    auto one_step = [&]() -> int { return c.forward(a->x, &step); };
 
-    std::lock_guard<std::mutex> lock(u.mu);
-    DDK_HIP(hipMemsetAsync(ws + ly.off_cl, 0, cl_counter_floats(B) * sizeof(float), st));    // cluster GroupNorm counters (outside the graph)
-    hipLaunchKernelGGL(set_chain_state_kernel, dim3(1), dim3(1), 0, st, state, (int64_t)a->t_start, a->seed, a->stream_id);
-    DDK_TRY(check_launch("set_chain_state_kernel"));
-    DDK_TRY(ensure_temb_table(u, P, ws, sl, a->t_start, B, H, W, st, timestep_map));
-    const int n_steps = a->t_start - a->t_end + 1;
-    int dev = 0;
-    if (a->use_graph && n_steps > 1) DDK_HIP(hipGetDevice(&dev));
     const ChainKey key{CHAIN_SAMPLER, {a->packed, a->x, a->noise, a->c_recip, a->c_recipm1, a->c1, a->c2, a->sigma}, a->workspace, a->noise,
-                       B, H, W, a->t_start, dev, u.pack_epoch};
-    return run_chain(u, key, n_steps, a->use_graph != 0, one_step, st, "sampler");
+                       B, H, W, a->t_start, c.dev, c.u->pack_epoch};
+    return run_chain(*c.u, key, n_steps, a->use_graph != 0, one_step, c.st, "sampler");
 }
 
 // ------------------------------------------------------------------------------------------------ likelihood sweep
@@ -1825,52 +1814,31 @@ extern "C" int ddk_vlb_sweep_run(const ddk_vlb_sweep_args* a, ddk_stream_t s) {
     DDK_REQUIRE(a && a->unet && a->packed && a->x && a->workspace && a->vlb_t && a->l_simple_t, "vlb_sweep: null pointer");
     DDK_REQUIRE(a->sqrt_acp && a->sqrt_1m_acp && a->c_recip && a->c_recipm1 && a->c1 && a->c2 && a->post_logvar,
                 "vlb_sweep: null schedule table");
-    ddk_unet& u = *const_cast<ddk_unet*>(a->unet);
-    DDK_TRY(check_shape(&u, a->B, a->H, a->W));
     DDK_REQUIRE(a->T >= 1, "vlb_sweep: need T >= 1");
     DDK_REQUIRE((a->stream_id & VLB_STREAM_BIT) == 0, "vlb_sweep: stream_id must be < 2^31 (the top bit separates the sweep's draws)");
-    DDK_REQUIRE(aligned16(a->packed) && aligned16(a->workspace) && aligned16(a->x) && aligned16(a->noise), "vlb_sweep: alignment");
-    const int B = a->B, H = a->H, W = a->W, C = u.cfg.in_ch, T = a->T;
-    const long long per = (long long)H * W * C;
-    DDK_REQUIRE(per % 4 == 0, "vlb_sweep: H*W*in_ch must be a multiple of 4");
-    const SweepLayout vl = sweep_layout(u, B, H, W, T);
-    const SamplerLayout& sl = vl.sl;
-    if (a->workspace_bytes < vl.total * sizeof(float)) {
-        set_error("vlb_sweep: workspace too small (%zu < %zu)", a->workspace_bytes, vl.total * sizeof(float));
-        return DDK_ERR_WORKSPACE;
-    }
-    DDK_TRY(ensure_device_init());
-    const Layout ly = make_layout(u, B, H, W);
-    hipStream_t st = as_stream(s);
-    float* ws = static_cast<float*>(a->workspace);
-    int64_t* t_cur = reinterpret_cast<int64_t*>(ws + sl.off_t);
-    int64_t* state = t_cur + B;
-    const float* P = static_cast<const float*>(a->packed);
-    const float* temb_table = ws + sl.off_table;
-    float* xt = ws + vl.off_xt;
-    float* partials = ws + vl.off_part;
+    const int B = a->B, H = a->H, W = a->W, T = a->T;
+    ChainRun c;
+    DDK_TRY(begin_chain(c, a, "vlb_sweep", T - 1, a->stream_id | VLB_STREAM_BIT, nullptr, T,
+                        [&](const SamplerLayout&) { return sweep_layout(*a->unet, B, H, W, T).total; }, s));
+    const SweepLayout vl = sweep_layout(*c.u, B, H, W, T);
+    const long long per = c.per;
+    float* xt = c.ws + vl.off_xt;
+    float* partials = c.ws + vl.off_part;
     const VlbStep v{a->x, xt, a->noise, a->noise ? B * per : 0, T - 1, a->c_recip, a->c_recipm1, a->c1, a->c2, a->post_logvar,
                     partials, vl.nslot};
-    StepArgs step{state, nullptr, ws + sl.off_eps, a->noise, a->noise ? B * per : 0, T - 1, a->c_recip, a->c_recipm1, a->c1, a->c2,
+    StepArgs step{c.state, nullptr, c.ws + c.sl.off_eps, a->noise, a->noise ? B * per : 0, T - 1, a->c_recip, a->c_recipm1, a->c1, a->c2,
                   nullptr, per};
     step.vlb = &v;
 
     // one step: x_t = q_sample(x, t, eps), UNet(x_t, t) with the counter bookkeeping of a reverse step, the VLB epilogue
     auto one_step = [&]() -> int {
-        DDK_TRY(vlb_step_input(v, a->sqrt_acp, a->sqrt_1m_acp, state, B, per, st));
-        return forward_core(u, P, xt, t_cur, nullptr, B, H, W, ws, ly, st, u.cluster_gn >= 1, temb_table, &step);
+        DDK_TRY(vlb_step_input(v, a->sqrt_acp, a->sqrt_1m_acp, c.state, B, per, c.st));
+        return c.forward(xt, &step);
     };
 
-    std::lock_guard<std::mutex> lock(u.mu);
-    DDK_HIP(hipMemsetAsync(ws + ly.off_cl, 0, cl_counter_floats(B) * sizeof(float), st));
-    hipLaunchKernelGGL(set_chain_state_kernel, dim3(1), dim3(1), 0, st, state, (int64_t)(T - 1), a->seed, a->stream_id | VLB_STREAM_BIT);
-    DDK_TRY(check_launch("set_chain_state_kernel"));
-    DDK_TRY(ensure_temb_table(u, P, ws, sl, T - 1, B, H, W, st));
-    int dev = 0;
-    if (a->use_graph && T > 1) DDK_HIP(hipGetDevice(&dev));
     const ChainKey key{CHAIN_VLB_SWEEP,
                        {a->packed, a->x, a->noise, a->sqrt_acp, a->sqrt_1m_acp, a->c_recip, a->c_recipm1, a->c1, a->c2, a->post_logvar},
-                       a->workspace, a->noise, B, H, W, T - 1, dev, u.pack_epoch};
-    DDK_TRY(run_chain(u, key, T, a->use_graph != 0, one_step, st, "vlb_sweep"));
-    return vlb_sweep_finalize(partials, vl.nslot, a->vlb_t, a->l_simple_t, T, B, per, st);
+                       a->workspace, a->noise, B, H, W, T - 1, c.dev, c.u->pack_epoch};
+    DDK_TRY(run_chain(*c.u, key, T, a->use_graph != 0, one_step, c.st, "vlb_sweep"));
+    return vlb_sweep_finalize(partials, vl.nslot, a->vlb_t, a->l_simple_t, T, B, per, c.st);
 }

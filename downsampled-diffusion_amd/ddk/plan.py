@@ -127,6 +127,38 @@ class UnetPlan:
         self.set_option(self.OPT_CLUSTER_GROUPNORM, 0)
         return True
 
+    def _chain_guarded(self):
+        """Whether a chain has to be checked for a failed in-launch GroupNorm.  On a device that never takes that path (masked /
+        partitioned: no launch is issued, csrc/unet_plan.hip gates on the same device test) there is nothing to check: no saved
+        input, no stream wait behind the chain.  The device is asked once, at the first chain."""
+        if self._cluster_dev is None:
+            self._cluster_dev = self._lib.ddk_conv3x3_gn_mish_cluster_ok(32, 32, 32, 128, 128, 8) > 0
+        return self._cluster >= 1 and self._cluster_dev
+
+    def _run_chain(self, who, call, ws, b, h, w, graphed, restore=None):
+        """Issues a chain with call(stream_ptr) on workspace `ws` of a [b, h, w] batch.  With the in-launch GroupNorm on, waits for
+        it (the chain's sync point: T steps of work against one stream synchronisation); when it reports a failure, restore()
+        puts the chain's input back and the chain runs again with the option off.  A graphed chain (hipGraph capture is illegal
+        on the legacy NULL stream) runs on a side stream ordered after the current one."""
+        guard = self._chain_guarded()
+        for rerun in (False, True):
+            if rerun and restore is not None:
+                restore()
+            if graphed:
+                cur = torch.cuda.current_stream()
+                side = _side_stream(ws.device)
+                side.wait_stream(cur)
+                with torch.cuda.stream(side):
+                    call(side.cuda_stream)
+                    failed = guard and self._cluster >= 1 and self._cluster_failed(ws, b, h, w, side.cuda_stream)
+                cur.wait_stream(side)
+            else:
+                call(L.stream())
+                failed = guard and self._cluster >= 1 and self._cluster_failed(ws, b, h, w, L.stream())
+            if not failed:
+                return
+        raise L.DDKError(f"{who}: in-launch GroupNorm reported a failure with the option off")
+
     def cluster_timeouts(self):
         return int(self._lib.ddk_debug_cluster_timeouts())
 
@@ -198,13 +230,8 @@ class UnetPlan:
         if mode["buf"] is not None:
             mode["buf"].copy_(x)
             x = mode["buf"]
-        # the in-launch GroupNorm can fail (loudly) when the GPU is shared: keep x_T so the chain can be rerun without it.  On a
-        # device that never takes that path (masked / partitioned: no launch is issued, csrc/unet_plan.hip gates on the same
-        # device test) there is nothing to check: no clone of x_T, no stream wait behind the chain
-        if self._cluster_dev is None:
-            self._cluster_dev = lib.ddk_conv3x3_gn_mish_cluster_ok(32, 32, 32, 128, 128, 8) > 0
-        guard = self._cluster >= 1 and self._cluster_dev
-        x_start = x.clone() if guard else None
+        # the in-launch GroupNorm can fail (loudly) when the GPU is shared: keep x_T so the chain can be rerun without it
+        x_start = x.clone() if self._chain_guarded() else None
 
         def call(stream_ptr):
             a = L.SamplerArgs(self.handle, L.ptr(self.packed), L.ptr(x), L.ptr(noise), L.ptr(tables["c_recip"]),
@@ -215,26 +242,7 @@ class UnetPlan:
             else:
                 L.check(lib.ddk_sampler_run_spaced(C.byref(a), tmap, stream_ptr), "sampler_run_spaced")
 
-        def run():
-            """Issues the chain; with the in-launch GroupNorm on, waits for it (the chain's sync point: T steps of work
-            against one stream synchronisation) and says whether it has to be rerun."""
-            if use_graph and n_steps > 1:
-                # hipGraph capture is illegal on the legacy NULL stream: run on a side stream ordered after the current one
-                cur = torch.cuda.current_stream()
-                side = _side_stream(x.device)
-                side.wait_stream(cur)
-                with torch.cuda.stream(side):
-                    call(side.cuda_stream)
-                    failed = guard and self._cluster >= 1 and self._cluster_failed(ws, b, h, w, side.cuda_stream)
-                cur.wait_stream(side)
-                return failed
-            call(L.stream())
-            return guard and self._cluster >= 1 and self._cluster_failed(ws, b, h, w, L.stream())
-
-        if run():
-            x.copy_(x_start)
-            if run():
-                raise L.DDKError("sampler: in-launch GroupNorm reported a failure with the option off")
+        self._run_chain("sampler", call, ws, b, h, w, use_graph and n_steps > 1, restore=lambda: x.copy_(x_start))
         if caller_x.data_ptr() != x.data_ptr():
             caller_x.copy_(x)
         return caller_x
@@ -272,9 +280,6 @@ class UnetPlan:
         xs.copy_(x)
         vlb_t = torch.empty((b, T), device=x.device, dtype=torch.float32)
         l_simple_t = torch.empty((T,), device=x.device, dtype=torch.float32)
-        if self._cluster_dev is None:
-            self._cluster_dev = lib.ddk_conv3x3_gn_mish_cluster_ok(32, 32, 32, 128, 128, 8) > 0
-        guard = self._cluster >= 1 and self._cluster_dev
 
         def call(stream_ptr):
             a = L.VlbSweepArgs(self.handle, L.ptr(self.packed), L.ptr(xs), L.ptr(noise), L.ptr(tables["sqrt_acp"]),
@@ -283,24 +288,7 @@ class UnetPlan:
                                L.ptr(ws), nbytes, L.ptr(vlb_t), L.ptr(l_simple_t))
             L.check(lib.ddk_vlb_sweep_run(C.byref(a), stream_ptr), "vlb_sweep_run")
 
-        def run():
-            """Issues the sweep; with the in-launch GroupNorm on, waits for it and says whether it has to be rerun (x is only read,
-            so a rerun needs no saved input)."""
-            if use_graph and T > 1:
-                cur = torch.cuda.current_stream()
-                side = _side_stream(x.device)
-                side.wait_stream(cur)
-                with torch.cuda.stream(side):
-                    call(side.cuda_stream)
-                    failed = guard and self._cluster >= 1 and self._cluster_failed(ws, b, h, w, side.cuda_stream)
-                cur.wait_stream(side)
-                return failed
-            call(L.stream())
-            return guard and self._cluster >= 1 and self._cluster_failed(ws, b, h, w, L.stream())
-
-        if run():
-            if run():
-                raise L.DDKError("vlb_sweep: in-launch GroupNorm reported a failure with the option off")
+        self._run_chain("vlb_sweep", call, ws, b, h, w, use_graph and T > 1)     # x is only read: a rerun needs no restore
         return vlb_t, l_simple_t
 
 

@@ -165,47 +165,32 @@ class DDPM(nn.Module):
         DDPM or, with ddim=True, as DDIM steps with noise scale eta.  early_stop then runs the spaced steps whose original
         timestep is >= early_stop; noise holds one draw per spaced step run, in run order; the in-kernel Philox draw of spaced
         step k is keyed by k (not by its original timestep).  The defaults run the plain T-step chain."""
-        if respacing is not None or ddim or eta != 0:
-            return self._p_sample_loop_spaced(shape, early_stop, x_T, noise, seed, respacing, ddim, eta)
-        device = self.betas.device
-        if device.type != 'cuda':
-            raise DDKError("p_sample_loop: move the model to a ROCm device first (no CPU fallback)")
-        t_end = 0 if early_stop is None else early_stop
-        img = torch.randn(shape, device=device) if x_T is None else x_T.to(device).float()
-        if t_end > self.timesteps - 1:
-            return img
-        if not self.native_sampler:
-            for i in reversed(range(t_end, self.timesteps)):      # the reference's own loop shape
-                t = torch.full((shape[0],), i, device=device, dtype=torch.long)
-                img = self.p_sample(img, t)
-            return img
-        unet = self._eps_model_nhwc()
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        x = ops.nchw_to_nhwc(img.contiguous())
-        nz = None
-        if noise is not None:
-            nz = noise.to(device).float().permute(0, 1, 3, 4, 2).contiguous()   # [k,B,C,H,W] -> [k,B,H,W,C]
-        unet.plan().sample_nhwc(x, self._tables(), self.timesteps - 1, t_end, noise=nz, seed=seed,
-                                stream_id=self.rng_stream_id, use_graph=self.use_graph)
-        return ops.nhwc_to_nchw(x)
-
-    def _p_sample_loop_spaced(self, shape, early_stop, x_T, noise, seed, respacing, ddim, eta):
-        if eta < 0 or (eta != 0 and not ddim):
+        spaced = respacing is not None or ddim or eta != 0
+        if spaced and (eta < 0 or (eta != 0 and not ddim)):
             raise ValueError(f"p_sample_loop: eta = {eta} needs ddim=True and eta >= 0")
         device = self.betas.device
         if device.type != 'cuda':
             raise DDKError("p_sample_loop: move the model to a ROCm device first (no CPU fallback)")
-        tables, use = self._spaced_tables(respacing, ddim, eta)
-        k_start = len(use) - 1
-        k_end = 0 if early_stop is None else next((k for k, t in enumerate(use) if t >= early_stop), len(use))
+        # the chain runs steps k_start .. k_end of its tables; a spaced chain's step k runs the UNet at timestep use[k]
+        if spaced:
+            tables, use = self._spaced_tables(respacing, ddim, eta)
+            k_start = len(use) - 1
+            k_end = 0 if early_stop is None else next((k for k, t in enumerate(use) if t >= early_stop), len(use))
+        else:
+            tables, use = self._tables(), None
+            k_start, k_end = self.timesteps - 1, 0 if early_stop is None else early_stop
         img = torch.randn(shape, device=device) if x_T is None else x_T.to(device).float()
         if k_end > k_start:
             return img
         n_steps = k_start - k_end + 1
-        if noise is not None and tuple(noise.shape) != (n_steps, *shape):
+        if spaced and noise is not None and tuple(noise.shape) != (n_steps, *shape):
             raise DDKError(f"p_sample_loop: noise must be {(n_steps, *shape)} (one draw per spaced step), got {tuple(noise.shape)}")
         if not self.native_sampler:
+            if not spaced:
+                for i in reversed(range(k_end, k_start + 1)):      # the reference's own loop shape
+                    t = torch.full((shape[0],), i, device=device, dtype=torch.long)
+                    img = self.p_sample(img, t)
+                return img
             # the same update as a Python loop: UNet at the original timestep, the fused update at the spaced index k
             for j, k in enumerate(range(k_start, k_end - 1, -1)):
                 self._check_device(img)

@@ -1,8 +1,9 @@
 // plan_walk.cpp -- driver of the host-sanitizer build (csrc/host_sanitize.h, `make -C downsampled-diffusion_amd/csrc asan`).
 // No GPU: libddk's host half runs under ASan + UBSan with every kernel launch replaced by a checker that validates the launch
 // geometry and that every pointer it would hand to the device lies inside an arena registered here.  For each BASELINE.json
-// configuration (reference models/unet/unet.py:19-72 shapes): create the plan, pack every slot, run one ddk_unet_forward and a
-// three-step eager ddk_sampler_run, and check the size queries against the arenas they size.
+// configuration (reference models/unet/unet.py:19-72 shapes): create the plan, pack every slot, run one ddk_unet_forward, a
+// three-step eager ddk_sampler_run, a respaced ddk_sampler_run_spaced and a T = 3 ddk_vlb_sweep_run, and check the size queries
+// against the arenas they size.
 #include <sys/mman.h>
 
 #include <cstdio>
@@ -83,6 +84,31 @@ static void walk(const char* name, int in_ch, int chan, std::vector<int> mults, 
     CHECK(rc == DDK_OK, "%s: sampler_run: %s", name, ddk_last_error());
     a.workspace_bytes = smp_bytes - 4;
     CHECK(ddk_sampler_run(&a, nullptr) == DDK_ERR_WORKSPACE, "%s: short sampler workspace accepted", name);
+    {   // a three-step respaced chain on a workspace sized for it (the shift table of the map's rows, uploaded from the host)
+        const int64_t map[3] = {0, T / 2, T - 1};
+        const size_t sp_bytes = ddk_sampler_workspace_bytes(u, B, H, W, 2);
+        Arena sp(sp_bytes, "spaced sampler workspace");
+        a.t_start = 2; a.t_end = 0; a.workspace = sp.p; a.workspace_bytes = sp_bytes;
+        rc = ddk_sampler_run_spaced(&a, map, nullptr);
+        CHECK(rc == DDK_OK, "%s: sampler_run_spaced: %s", name, ddk_last_error());
+        a.workspace_bytes = sp_bytes - 4;
+        CHECK(ddk_sampler_run_spaced(&a, map, nullptr) == DDK_ERR_WORKSPACE, "%s: short spaced sampler workspace accepted", name);
+    }
+    {   // a three-step likelihood sweep (q_sample input, VLB epilogue, the final sum)
+        const int VT = 3;
+        const size_t vsw_bytes = ddk_vlb_sweep_workspace_bytes(u, B, H, W, VT);
+        Arena vsw(vsw_bytes, "sweep workspace"), vtab((size_t)7 * VT * 4, "sweep tables"), vout((size_t)(B + 1) * VT * 4, "sweep out");
+        ddk_vlb_sweep_args v{};
+        v.unet = u; v.packed = packed.p; v.x = x.f(); v.noise = nullptr;
+        v.sqrt_acp = vtab.f(); v.sqrt_1m_acp = vtab.f() + VT; v.c_recip = vtab.f() + 2 * VT; v.c_recipm1 = vtab.f() + 3 * VT;
+        v.c1 = vtab.f() + 4 * VT; v.c2 = vtab.f() + 5 * VT; v.post_logvar = vtab.f() + 6 * VT;
+        v.B = B; v.H = H; v.W = W; v.T = VT; v.seed = 1; v.stream_id = 0; v.use_graph = 0;
+        v.workspace = vsw.p; v.workspace_bytes = vsw_bytes; v.vlb_t = vout.f(); v.l_simple_t = vout.f() + (size_t)B * VT;
+        rc = ddk_vlb_sweep_run(&v, nullptr);
+        CHECK(rc == DDK_OK, "%s: vlb_sweep_run: %s", name, ddk_last_error());
+        v.workspace_bytes = vsw_bytes - 4;
+        CHECK(ddk_vlb_sweep_run(&v, nullptr) == DDK_ERR_WORKSPACE, "%s: short sweep workspace accepted", name);
+    }
     CHECK(ddk_unet_flops(u, B, H, W) > 0 && ddk_unet_flops_executed(u, B, H, W) > 0, "%s: flops", name);
     CHECK(ddk_unet_workspace_bytes(u, B, H + 1, W) == 0, "%s: indivisible map accepted", name);
     ddk_unet_destroy(u);
