@@ -299,6 +299,10 @@ int p_sample_update(float* x, const float* eps_hat, const float* noise, long lon
                     const int64_t* t, const float* c_recip, const float* c_recipm1, const float* c1, const float* c2,
                     const float* sigma, int B, long long per, uint64_t seed, uint32_t stream_id, hipStream_t st,
                     const int64_t* chain_state = nullptr, int64_t* dec_counter = nullptr);
+// DPM-Solver++(2M): x_prev = (c1 x0 + c2 x) + c3 x0_hist, x0_hist <- x0 (the sampler's last kernel of a step when unfused)
+int p_sample_update_ms(float* x, const float* eps_hat, float* x0_hist, const int64_t* t, const float* c_recip, const float* c_recipm1,
+                       const float* c1, const float* c2, const float* c3, int B, long long per, hipStream_t st,
+                       int64_t* dec_counter = nullptr);
 int randn(float* out, long long n, uint64_t seed, uint32_t step, uint32_t stream_id, hipStream_t st);
 // GroupNorm (from conv partials) + Mish + 1x1 projection to n_out <= 8 channels (+ the reverse-step update of x) in one launch
 // likelihood sweep (diffusion.hip, ddk_vlb_sweep_run): one step's operands besides the UNet's
@@ -324,10 +328,12 @@ int final_tail_vlb(const float* raw, const float* part, int np, const float* gam
                    int groups, hipStream_t st, int64_t* dec_counter);
 bool final_tail_ok(int HW, int C, int groups, int n_out, int np);
 bool final_tail_vlb_ok(int HW, int C, int groups, int n_out, int np);
+bool final_tail_ms_ok(int HW, int C, int groups, int n_out, int np);
 int final_tail(const float* raw, const float* part, int np, const float* gamma, const float* beta, float eps, const float* w,
                const float* bias, int n_out, float* eps_out, float* x, const float* noise, long long noise_step_stride, int t_first,
                const int64_t* t, const float* c_recip, const float* c_recipm1, const float* c1, const float* c2, const float* sigma,
                const int64_t* chain_state, uint64_t seed, uint32_t stream_id, int B, int HW, int C, int groups, hipStream_t st,
-               int64_t* dec_counter = nullptr);     // dec_counter: the sampler's step counter, decremented by this (last) kernel of the step
+               int64_t* dec_counter = nullptr,      // dec_counter: the sampler's step counter, decremented by this (last) kernel of the step
+               float* x0_hist = nullptr, const float* c3 = nullptr);   // both given: the multistep update (final_tail_ms_ok shapes, no noise)
 
 }  // namespace ddk

@@ -87,6 +87,27 @@ __device__ __forceinline__ float p_step(float x, float e, float z, float cr, flo
     return __fadd_rn(mean, __fmul_rn(sg, z));                       // ddpm.py:227 (sg already carries the t>0 mask)
 }
 
+// DPM-Solver++(2M) (models/diffusion/respace.py dpm_solver_tables): the same clamped x0, then
+// x_prev = (c1 x0 + c2 x) + c3 h with h the previous step's x0, which the step leaves in h.  One function for the fused and the
+// unfused tail, so given the same eps_hat they are bit-identical.
+__device__ __forceinline__ float ms_step(float x, float e, float& h, float cr, float crm1, float c1, float c2, float c3) {
+    float x0 = __fsub_rn(__fmul_rn(cr, x), __fmul_rn(crm1, e));
+    x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    const float mean = __fadd_rn(__fmul_rn(c1, x0), __fmul_rn(c2, x));
+    const float out = __fadd_rn(mean, __fmul_rn(c3, h));
+    h = x0;
+    return out;
+}
+
+__device__ __forceinline__ float4 ms_step4(float4 xv, float4 ev, float4& h, float cr, float crm1, float c1, float c2, float c3) {
+    float4 o;
+    o.x = ms_step(xv.x, ev.x, h.x, cr, crm1, c1, c2, c3);
+    o.y = ms_step(xv.y, ev.y, h.y, cr, crm1, c1, c2, c3);
+    o.z = ms_step(xv.z, ev.z, h.z, cr, crm1, c1, c2, c3);
+    o.w = ms_step(xv.w, ev.w, h.w, cr, crm1, c1, c2, c3);
+    return o;
+}
+
 __global__ __launch_bounds__(256) void p_sample_kernel(float* __restrict__ x, const float* __restrict__ eps_hat,
                                                        const float* __restrict__ noise, long long noise_step_stride, int t_first,
                                                        const int64_t* __restrict__ t,
@@ -114,6 +135,25 @@ __global__ __launch_bounds__(256) void p_sample_kernel(float* __restrict__ x, co
         o.z = p_step(xv.z, ev.z, zv.z, cr, crm1, a1, a2, sg);
         o.w = p_step(xv.w, ev.w, zv.w, cr, crm1, a1, a2, sg);
         reinterpret_cast<float4*>(x)[i] = o;
+    }
+}
+
+// The multistep update of the unfused tail: no draw, the history x0_hist (same layout as x) read and rewritten element by element.
+// It is the step's last kernel in the sampler, so it takes over p_sample_kernel's counter decrement.
+__global__ __launch_bounds__(256) void p_sample_ms_kernel(float* __restrict__ x, const float* __restrict__ eps_hat,
+                                                          float* __restrict__ x0_hist, const int64_t* __restrict__ t,
+                                                          const float* __restrict__ c_recip, const float* __restrict__ c_recipm1,
+                                                          const float* __restrict__ c1, const float* __restrict__ c2,
+                                                          const float* __restrict__ c3, long long per4, long long total4,
+                                                          int64_t* dec_counter) {
+    if (dec_counter && blockIdx.x == 0 && threadIdx.x == 0) *dec_counter -= 1;     // the step counter, by the step's last kernel (see final_tail)
+    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total4; i += (long long)gridDim.x * 256) {
+        const int64_t tb = t[i / per4];
+        const float cr = c_recip[tb], crm1 = c_recipm1[tb], a1 = c1[tb], a2 = c2[tb], a3 = c3[tb];
+        const float4 xv = reinterpret_cast<const float4*>(x)[i], ev = reinterpret_cast<const float4*>(eps_hat)[i];
+        float4 h = reinterpret_cast<const float4*>(x0_hist)[i];
+        reinterpret_cast<float4*>(x)[i] = ms_step4(xv, ev, h, cr, crm1, a1, a2, a3);
+        reinterpret_cast<float4*>(x0_hist)[i] = h;
     }
 }
 
@@ -191,12 +231,17 @@ struct TailParams {
     const float* logvar;          // posterior_log_variance_clipped [T]
     float2* vlb_part;             // [T][B][np] {sum of the VLB terms, sum of (eps - eps_hat)^2} per 128-pixel tile
     int B;
+    // multistep (final_tail_kernel<.., .., false, true>): the previous step's clipped x0, same layout as x, read and rewritten
+    float* x0_hist;
+    const float* c3;
 };
 
 // VLB = false: eps_hat out and / or the reverse-step update of x.  VLB = true (ddk_vlb_sweep_run): phase 2 evaluates, per element,
 // vlb_terms_kernel's term and (eps - eps_hat)^2 with eps the step-input kernel's draw (the same Philox call or injected array), and
 // the workgroup stores the two block sums to its own slot of vlb_part (plain stores, no atomics: the kernel boundary publishes them).
-template <int LPP, int VPL, bool VLB>
+// MS = true (ddk_sampler_run_multistep, x given): the DPM-Solver++(2M) update of p_sample_ms_kernel; the history float4 is
+// requested where the other modes draw their noise (no Philox rounds), and the thread that read it writes it back.
+template <int LPP, int VPL, bool VLB, bool MS = false>
 __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
     constexpr int PPW = 64 / LPP;                    // pixels per wave and iteration
     constexpr int PPI = 16 * PPW;                    // ... per iteration of the 16-wave workgroup
@@ -237,7 +282,7 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
     const int cnt4 = 128 * p.n_out / 4;
     const long long e4 = pix0 * p.n_out / 4;          // host: (128 * n_out) % 4 == 0
     float4 xv0 = make_float4(0.f, 0.f, 0.f, 0.f), zv0 = xv0;
-    float cr = 0.f, crm1 = 0.f, a1 = 0.f, a2 = 0.f, sg = 0.f;
+    float cr = 0.f, crm1 = 0.f, a1 = 0.f, a2 = 0.f, sg = 0.f, a3 = 0.f;
     int64_t tb = 0;
     float4 xt0 = xv0;
     VlbCoef kc{};
@@ -249,13 +294,15 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
             kc = vlb_coef(tb, p.c_recip, p.c_recipm1, p.c1, p.c2, p.logvar);
         } else {
             cr = p.c_recip[tb]; crm1 = p.c_recipm1[tb]; a1 = p.c1[tb]; a2 = p.c2[tb];
-            sg = tb > 0 ? p.sigma[tb] : 0.0f;
+            if constexpr (MS) a3 = p.c3[tb];
+            else sg = tb > 0 ? p.sigma[tb] : 0.0f;
         }
         const long long i = e4 + tid;
         xv0 = reinterpret_cast<const float4*>(p.x)[i];
         if constexpr (VLB) xt0 = reinterpret_cast<const float4*>(p.xt)[i];
-        zv0 = p.noise ? reinterpret_cast<const float4*>(p.noise + (long long)(p.t_first - tb) * p.noise_step_stride)[i]
-                      : philox_normal4((unsigned long long)i, (uint32_t)tb, stream, seed);
+        if constexpr (MS) zv0 = reinterpret_cast<const float4*>(p.x0_hist)[i];      // MS: zv0 holds the history, not a draw
+        else zv0 = p.noise ? reinterpret_cast<const float4*>(p.noise + (long long)(p.t_first - tb) * p.noise_step_stride)[i]
+                           : philox_normal4((unsigned long long)i, (uint32_t)tb, stream, seed);
     }
     __syncthreads();
     if (tid < G) {          // the same fixed-order merge as gn_apply_parts_kernel
@@ -330,7 +377,10 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
     if (tid < cnt4) {
         const float4 ev = reinterpret_cast<const float4*>(es)[tid];
         if (p.eps_out) reinterpret_cast<float4*>(p.eps_out)[e4 + tid] = ev;
-        if (p.x) {
+        if constexpr (MS) {
+            reinterpret_cast<float4*>(p.x)[e4 + tid] = ms_step4(xv0, ev, zv0, cr, crm1, a1, a2, a3);
+            reinterpret_cast<float4*>(p.x0_hist)[e4 + tid] = zv0;
+        } else if (p.x) {
             float4 o;
             o.x = p_step(xv0.x, ev.x, zv0.x, cr, crm1, a1, a2, sg);
             o.y = p_step(xv0.y, ev.y, zv0.y, cr, crm1, a1, a2, sg);
@@ -341,19 +391,21 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
     }
 }
 
-template <bool VLB>
+template <bool VLB, bool MS = false>
 static int launch_tail(const TailParams& p, int B, hipStream_t st) {
     const dim3 grid((unsigned)(B * p.np));
-    if (p.C == 32) hipLaunchKernelGGL((final_tail_kernel<8, 1, VLB>), grid, dim3(1024), 0, st, p);
-    else if (p.C == 64) hipLaunchKernelGGL((final_tail_kernel<16, 1, VLB>), grid, dim3(1024), 0, st, p);
-    else if (p.C == 128) hipLaunchKernelGGL((final_tail_kernel<32, 1, VLB>), grid, dim3(1024), 0, st, p);
-    else if constexpr (!VLB) hipLaunchKernelGGL((final_tail_kernel<32, 2, VLB>), grid, dim3(1024), 0, st, p);
-    else DDK_REQUIRE(false, "final_tail_vlb: C = 256 takes the unfused epilogue (final_tail_vlb_ok)");
+    if (p.C == 32) hipLaunchKernelGGL((final_tail_kernel<8, 1, VLB, MS>), grid, dim3(1024), 0, st, p);
+    else if (p.C == 64) hipLaunchKernelGGL((final_tail_kernel<16, 1, VLB, MS>), grid, dim3(1024), 0, st, p);
+    else if (p.C == 128) hipLaunchKernelGGL((final_tail_kernel<32, 1, VLB, MS>), grid, dim3(1024), 0, st, p);
+    else if constexpr (!VLB && !MS) hipLaunchKernelGGL((final_tail_kernel<32, 2, VLB>), grid, dim3(1024), 0, st, p);
+    else DDK_REQUIRE(false, "final_tail: C = 256 takes the unfused epilogue in the VLB and multistep modes (final_tail_vlb_ok / final_tail_ms_ok)");
     return check_launch("final_tail_kernel");
 }
 
 // the sweep's fused epilogue: final_tail's shapes up to 128 channels (the 256-channel VLB instantiation would spill registers)
 bool final_tail_vlb_ok(int HW, int C, int groups, int n_out, int np) { return C <= 128 && final_tail_ok(HW, C, groups, n_out, np); }
+// the multistep update: the same subset (the 256-channel instantiation spills already without it)
+bool final_tail_ms_ok(int HW, int C, int groups, int n_out, int np) { return C <= 128 && final_tail_ok(HW, C, groups, n_out, np); }
 
 bool final_tail_ok(int HW, int C, int groups, int n_out, int np) {
     if (!(C == 32 || C == 64 || C == 128 || C == 256)) return false;
@@ -366,12 +418,14 @@ int final_tail(const float* raw, const float* part, int np, const float* gamma, 
                const float* bias, int n_out, float* eps_out, float* x, const float* noise, long long noise_step_stride, int t_first,
                const int64_t* t, const float* c_recip, const float* c_recipm1, const float* c1, const float* c2, const float* sigma,
                const int64_t* chain_state, uint64_t seed, uint32_t stream_id, int B, int HW, int C, int groups, hipStream_t st,
-               int64_t* dec_counter) {
+               int64_t* dec_counter, float* x0_hist, const float* c3) {
     DDK_REQUIRE(raw && part && gamma && beta && w && (eps_out || x) && B > 0, "final_tail: null pointer");
     DDK_REQUIRE(final_tail_ok(HW, C, groups, n_out, np), "final_tail: needs C in {32,64,128,256}, n_out <= 8, H*W == tiles * 128");
+    DDK_REQUIRE(!x0_hist || (x && c3 && !noise && aligned16(x0_hist) && final_tail_ms_ok(HW, C, groups, n_out, np)),
+                "final_tail: the multistep update needs x, c3, no injected noise, an aligned history and C <= 128");
     DDK_REQUIRE(aligned16(raw) && aligned16(gamma) && aligned16(beta) && aligned16(w) && aligned16(eps_out) && aligned16(x) &&
                     aligned16(noise) && noise_step_stride % 4 == 0, "final_tail: alignment");
-    DDK_REQUIRE(!x || (t && c_recip && c_recipm1 && c1 && c2 && sigma), "final_tail: the update needs t and the schedule tables");
+    DDK_REQUIRE(!x || (t && c_recip && c_recipm1 && c1 && c2 && (sigma || x0_hist)), "final_tail: the update needs t and the schedule tables");
     TailParams p{};
     p.raw = raw; p.part = reinterpret_cast<const float2*>(part); p.gamma = gamma; p.beta = beta; p.w = w; p.bias = bias;
     p.eps_out = eps_out; p.x = x; p.noise = noise; p.noise_step_stride = noise_step_stride; p.t_first = t_first; p.t = t;
@@ -379,7 +433,8 @@ int final_tail(const float* raw, const float* part, int np, const float* gamma, 
     p.seed = seed; p.stream = stream_id;
     p.np = np; p.HW = HW; p.C = C; p.cpg = C / groups; p.n_out = n_out; p.eps = eps;
     p.dec_counter = dec_counter;
-    return launch_tail<false>(p, B, st);
+    p.x0_hist = x0_hist; p.c3 = c3;
+    return x0_hist ? launch_tail<false, true>(p, B, st) : launch_tail<false>(p, B, st);
 }
 
 int final_tail_vlb(const float* raw, const float* part, int np, const float* gamma, const float* beta, float eps, const float* w,
@@ -597,6 +652,17 @@ int p_sample_update(float* x, const float* eps_hat, const float* noise, long lon
     return check_launch("p_sample_kernel");
 }
 
+int p_sample_update_ms(float* x, const float* eps_hat, float* x0_hist, const int64_t* t, const float* c_recip, const float* c_recipm1,
+                       const float* c1, const float* c2, const float* c3, int B, long long per, hipStream_t st, int64_t* dec_counter) {
+    DDK_REQUIRE(x && eps_hat && x0_hist && t && c_recip && c_recipm1 && c1 && c2 && c3, "p_sample_update_multistep: null pointer");
+    DDK_REQUIRE(B > 0 && per > 0 && per % 4 == 0, "p_sample_update_multistep: per-sample element count must be a multiple of 4");
+    DDK_REQUIRE(aligned16(x) && aligned16(eps_hat) && aligned16(x0_hist), "p_sample_update_multistep: alignment");
+    const long long total4 = B * per / 4;
+    hipLaunchKernelGGL(p_sample_ms_kernel, dim3(grid1d(total4)), dim3(256), 0, st, x, eps_hat, x0_hist, t, c_recip, c_recipm1, c1, c2, c3,
+                       per / 4, total4, dec_counter);
+    return check_launch("p_sample_ms_kernel");
+}
+
 int randn(float* out, long long n, uint64_t seed, uint32_t step, uint32_t stream_id, hipStream_t st) {
     DDK_REQUIRE(out && n > 0 && aligned16(out), "randn: arguments");
     const long long n4 = (n + 3) / 4;
@@ -648,6 +714,12 @@ int ddk_p_sample_update(float* x, const float* eps_hat, const float* noise, cons
                         const float* c_recipm1, const float* c1, const float* c2, const float* sigma, int B, long long per,
                         uint64_t seed, uint32_t stream_id, ddk_stream_t s) {
     return p_sample_update(x, eps_hat, noise, 0, 0, t, c_recip, c_recipm1, c1, c2, sigma, B, per, seed, stream_id, as_stream(s));
+}
+
+int ddk_p_sample_update_multistep(float* x, const float* eps_hat, float* x0_hist, const int64_t* t, const float* c_recip,
+                                  const float* c_recipm1, const float* c1, const float* c2, const float* c3, int B, long long per,
+                                  ddk_stream_t s) {
+    return p_sample_update_ms(x, eps_hat, x0_hist, t, c_recip, c_recipm1, c1, c2, c3, B, per, as_stream(s));
 }
 
 int ddk_final_tail(const float* raw, const float* partials, int tiles_per_image, const float* gamma, const float* beta, float eps,

@@ -82,7 +82,7 @@ using namespace ddk;
 // pointer its kernels were launched with, so an entry is valid for exactly this kind of chain, this set of buffers and this
 // shape; t, the Philox seed / stream id and the injected-noise step index are read from device memory by the kernels, so the
 // same graph serves every step of every chain on those buffers.
-enum ChainKind { CHAIN_SAMPLER = 0, CHAIN_VLB_SWEEP = 1 };
+enum ChainKind { CHAIN_SAMPLER = 0, CHAIN_VLB_SWEEP = 1, CHAIN_SAMPLER_MULTISTEP = 2 };
 struct ChainKey {
     int kind;
     const void* bufs[12];                    // every buffer the step's kernels are launched with (unused entries null)
@@ -1151,15 +1151,20 @@ struct StepArgs {
     const float *c_recip, *c_recipm1, *c1, *c2, *sigma;
     long long per;
     const VlbStep* vlb = nullptr;   // likelihood sweep: the forward ran on vlb->xt and ends in the VLB epilogue (x, sigma unused)
+    float* x0_hist = nullptr;       // multistep sampler: the previous step's clipped x0 (read and rewritten), with c3; sigma, noise unused
+    const float* c3 = nullptr;
 };
 
 // tiles of the final tail when the end of the forward runs as ONE launch (final_tail_kernel), else 0.  cin = the final conv's
-// input channels (dimp[1]).  The sweep's VLB mode takes a subset of the shapes (final_tail_vlb_ok).
-static int fused_tail_parts(const ddk_unet& u, int B, int H, int W, int cin, bool vlb) {
+// input channels (dimp[1]).  The sweep's VLB mode and the multistep update take a subset of the shapes (final_tail_vlb_ok,
+// final_tail_ms_ok).
+static int fused_tail_parts(const ddk_unet& u, int B, int H, int W, int cin, bool vlb, bool ms = false) {
     const int chan = u.generic ? pad32(u.cfg.chan) : u.cfg.chan, n_out = u.cfg.in_ch;
     const int npf = u.final_conv.has_wu ? conv_wino_stats_parts(B, H, W, cin, chan, GROUPS) : 0;
     if (npf <= 0) return 0;
-    return (vlb ? final_tail_vlb_ok(H * W, chan, GROUPS, n_out, npf) : final_tail_ok(H * W, chan, GROUPS, n_out, npf)) ? npf : 0;
+    const int HW = H * W;
+    return (vlb ? final_tail_vlb_ok(HW, chan, GROUPS, n_out, npf)
+                : ms ? final_tail_ms_ok(HW, chan, GROUPS, n_out, npf) : final_tail_ok(HW, chan, GROUPS, n_out, npf)) ? npf : 0;
 }
 
 // t_cur[b] = counter for every sample, then counter -= 1; also zero-pads x into xpad.  First kernel of a step on shapes the
@@ -1370,7 +1375,7 @@ static int forward_core(const ddk_unet& u, const float* P, const float* x, int64
     }
     // final_conv: Block(dim, dim) then 1x1 to in_ch (unet.py:69-72)
     const int chan = u.generic ? pad32(u.cfg.chan) : u.cfg.chan, n_out = u.cfg.in_ch;
-    const int npf = fused_tail_parts(u, B, H, W, cur_c, step && step->vlb);
+    const int npf = fused_tail_parts(u, B, H, W, cur_c, step && step->vlb, step && step->x0_hist);
     if (npf > 0 && (!step || step->per == (long long)H * W * n_out)) {
         // one-pass Winograd conv with statistics, then GroupNorm + Mish + projection (+ the update of x) in ONE launch
         ddk_conv_args a{};
@@ -1390,7 +1395,7 @@ static int forward_core(const ddk_unet& u, const float* P, const float* x, int64
         if (step)
             return final_tail(raw, gnp, npf, P + u.final_norm.g, P + u.final_norm.b, GN_EPS, P + u.final_w, P + u.final_b, n_out, nullptr,
                               step->x, step->noise, step->noise_step_stride, step->t_first, t, step->c_recip, step->c_recipm1, step->c1,
-                              step->c2, step->sigma, step->state, 0, 0, B, H * W, chan, GROUPS, st, dec_counter);
+                              step->c2, step->sigma, step->state, 0, 0, B, H * W, chan, GROUPS, st, dec_counter, step->x0_hist, step->c3);
         return final_tail(raw, gnp, npf, P + u.final_norm.g, P + u.final_norm.b, GN_EPS, P + u.final_w, P + u.final_b, n_out, out, nullptr,
                           nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, B, H * W, chan, GROUPS, st);
     }
@@ -1399,6 +1404,9 @@ static int forward_core(const ddk_unet& u, const float* P, const float* x, int64
     DDK_TRY(conv1x1_small_n(a1, P + u.final_w, P + u.final_b, eps_hat, (long long)B * H * W, chan, n_out, st));
     if (!step) return DDK_OK;
     if (step->vlb) return vlb_sweep_terms(*step->vlb, t, eps_hat, B, step->per, step->state, st, dec_counter);
+    if (step->x0_hist)
+        return p_sample_update_ms(step->x, eps_hat, step->x0_hist, t, step->c_recip, step->c_recipm1, step->c1, step->c2, step->c3, B,
+                                  step->per, st, dec_counter);
     return p_sample_update(step->x, eps_hat, step->noise, step->noise_step_stride, step->t_first, t, step->c_recip, step->c_recipm1,
                            step->c1, step->c2, step->sigma, B, step->per, 0, 0, st, step->state, dec_counter);
 }
@@ -1754,22 +1762,29 @@ extern "C" int ddk_sampler_run(const ddk_sampler_args* a, ddk_stream_t s) {
     return ddk_sampler_run_spaced(a, nullptr, s);
 }
 
+namespace ddk {
+// a host timestep map of t_start + 1 entries: map[0] == 0, strictly increasing, below 2^31 (null: the identity)
+static int check_timestep_map(const int64_t* map, int t_start, const char* who) {
+    if (!map) return DDK_OK;
+    if (map[0] != 0) {
+        set_error("%s: timestep_map[0] must be 0, got %lld", who, (long long)map[0]);
+        return DDK_ERR_ARG;
+    }
+    for (int k = 1; k <= t_start; ++k)
+        if (map[k] <= map[k - 1] || map[k] >= (int64_t(1) << 31)) {
+            set_error("%s: timestep_map must increase strictly and stay below 2^31 (entry %d = %lld after %lld)", who, k,
+                      (long long)map[k], (long long)map[k - 1]);
+            return DDK_ERR_ARG;
+        }
+    return DDK_OK;
+}
+}  // namespace ddk
+
 extern "C" int ddk_sampler_run_spaced(const ddk_sampler_args* a, const int64_t* timestep_map, ddk_stream_t s) {
     DDK_REQUIRE(a && a->unet && a->packed && a->x && a->workspace, "sampler: null pointer");
     DDK_REQUIRE(a->c_recip && a->c_recipm1 && a->c1 && a->c2 && a->sigma, "sampler: null schedule table");
     DDK_REQUIRE(a->t_start >= a->t_end && a->t_end >= 0, "sampler: need t_start >= t_end >= 0");
-    if (timestep_map) {
-        if (timestep_map[0] != 0) {
-            set_error("sampler: timestep_map[0] must be 0, got %lld", (long long)timestep_map[0]);
-            return DDK_ERR_ARG;
-        }
-        for (int k = 1; k <= a->t_start; ++k)
-            if (timestep_map[k] <= timestep_map[k - 1] || timestep_map[k] >= (int64_t(1) << 31)) {
-                set_error("sampler: timestep_map must increase strictly and stay below 2^31 (entry %d = %lld after %lld)", k,
-                          (long long)timestep_map[k], (long long)timestep_map[k - 1]);
-                return DDK_ERR_ARG;
-            }
-    }
+    DDK_TRY(check_timestep_map(timestep_map, a->t_start, "sampler"));
     const int B = a->B, H = a->H, W = a->W, n_steps = a->t_start - a->t_end + 1;
     ChainRun c;
     DDK_TRY(begin_chain(c, a, "sampler", a->t_start, a->stream_id, timestep_map, n_steps,
@@ -1783,6 +1798,45 @@ extern "C" int ddk_sampler_run_spaced(const ddk_sampler_args* a, const int64_t* 
     const ChainKey key{CHAIN_SAMPLER, {a->packed, a->x, a->noise, a->c_recip, a->c_recipm1, a->c1, a->c2, a->sigma}, a->workspace, a->noise,
                        B, H, W, a->t_start, c.dev, c.u->pack_epoch};
     return run_chain(*c.u, key, n_steps, a->use_graph != 0, one_step, c.st, "sampler");
+}
+
+// ------------------------------------------------------------------------------------------------ multistep sampler
+// DPM-Solver++(2M): the sampler's chain with the update x_prev = (c1 x0 + c2 x) + c3 x0_hist, x0_hist <- x0.
+// The history [B][H][W][in_ch] sits behind the sampler layout and is zeroed (outside any captured step) by every call, so no chain
+// sees another's; c3[t_start] == 0 makes the first step first order whatever the zeroed history would hold.
+namespace ddk {
+static size_t multistep_floats(const ddk_unet& u, int B, int H, int W, int t_start) {
+    return sampler_layout(u, B, H, W, t_start).total + al4((size_t)B * H * W * u.cfg.in_ch);
+}
+}  // namespace ddk
+
+extern "C" size_t ddk_sampler_multistep_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start) {
+    if (check_shape(u, B, H, W) != DDK_OK || t_start < 0) return 0;
+    return multistep_floats(*u, B, H, W, t_start) * sizeof(float);
+}
+
+extern "C" int ddk_sampler_run_multistep(const ddk_sampler_args* a, const int64_t* timestep_map, const float* c3, ddk_stream_t s) {
+    DDK_REQUIRE(a && a->unet && a->packed && a->x && a->workspace, "sampler_multistep: null pointer");
+    DDK_REQUIRE(a->c_recip && a->c_recipm1 && a->c1 && a->c2 && c3, "sampler_multistep: null schedule table");
+    DDK_REQUIRE(!a->noise, "sampler_multistep: the solver is deterministic, noise must be NULL");
+    DDK_REQUIRE(a->t_start >= a->t_end && a->t_end >= 0, "sampler_multistep: need t_start >= t_end >= 0");
+    DDK_TRY(check_timestep_map(timestep_map, a->t_start, "sampler_multistep"));
+    const int B = a->B, H = a->H, W = a->W, n_steps = a->t_start - a->t_end + 1;
+    ChainRun c;
+    DDK_TRY(begin_chain(c, a, "sampler_multistep", a->t_start, a->stream_id, timestep_map, n_steps,
+                        [&](const SamplerLayout&) { return multistep_floats(*a->unet, B, H, W, a->t_start); }, s));
+    float* hist = c.ws + c.sl.total;
+    DDK_HIP(hipMemsetAsync(hist, 0, (size_t)B * c.per * sizeof(float), c.st));
+    StepArgs step{c.state, a->x, c.ws + c.sl.off_eps, nullptr, 0, a->t_start, a->c_recip, a->c_recipm1, a->c1, a->c2, nullptr, c.per};
+    step.x0_hist = hist;
+    step.c3 = c3;
+
+    auto one_step = [&]() -> int { return c.forward(a->x, &step); };
+
+    // a kind of its own and c3 in the key: a DDIM chain on the same buffers never replays this graph, nor this one a DDIM graph
+    const ChainKey key{CHAIN_SAMPLER_MULTISTEP, {a->packed, a->x, a->c_recip, a->c_recipm1, a->c1, a->c2, c3}, a->workspace, nullptr,
+                       B, H, W, a->t_start, c.dev, c.u->pack_epoch};
+    return run_chain(*c.u, key, n_steps, a->use_graph != 0, one_step, c.st, "sampler_multistep");
 }
 
 // ------------------------------------------------------------------------------------------------ likelihood sweep

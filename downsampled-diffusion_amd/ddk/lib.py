@@ -142,6 +142,7 @@ SIGNATURES = {
     "ddk_conv1x1_small_n": (_I, [_P, _P, _P, _P, _LL, _I, _I, _P]),
     "ddk_q_sample": (_I, [_P, _P, _P, _P, _P, _P, _I, _LL, _P]),
     "ddk_p_sample_update": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _LL, C.c_uint64, C.c_uint32, _P]),
+    "ddk_p_sample_update_multistep": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _LL, _P]),
     "ddk_randn": (_I, [_P, _LL, C.c_uint64, C.c_uint32, C.c_uint32, _P]),
     "ddk_fix_samples": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "ddk_sq_err_sum": (_I, [_P, _P, _P, _I, _LL, _P]),
@@ -172,6 +173,8 @@ SIGNATURES = {
     "ddk_sampler_workspace_bytes": (_SZ, [_P, _I, _I, _I, _I]),
     "ddk_sampler_run": (_I, [C.POINTER(SamplerArgs), _P]),
     "ddk_sampler_run_spaced": (_I, [C.POINTER(SamplerArgs), C.POINTER(C.c_int64), _P]),
+    "ddk_sampler_multistep_workspace_bytes": (_SZ, [_P, _I, _I, _I, _I]),
+    "ddk_sampler_run_multistep": (_I, [C.POINTER(SamplerArgs), C.POINTER(C.c_int64), _P, _P]),
     "ddk_sampler_invalidate": (_I, [_P]),
     "ddk_sampler_release_workspace": (_I, [_P, _P]),
     "ddk_vlb_sweep_workspace_bytes": (_SZ, [_P, _I, _I, _I, _I]),

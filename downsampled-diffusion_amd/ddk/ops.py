@@ -750,6 +750,16 @@ def p_sample_update_(x, eps_hat, t, c_recip, c_recipm1, c1, c2, sigma, noise=Non
     return x
 
 
+def p_sample_update_multistep_(x, eps_hat, x0_hist, t, c_recip, c_recipm1, c1, c2, c3):
+    """In-place DPM-Solver++(2M) update of x and of the history x0_hist (the previous step's clipped x0; zeros before a chain's
+    first step); x / eps_hat / x0_hist share one layout."""
+    b = x.shape[0]
+    L.check(L.load().ddk_p_sample_update_multistep(L.ptr(_f32(x)), L.ptr(_f32(eps_hat)), L.ptr(_f32(x0_hist)), L.ptr(t), L.ptr(c_recip),
+                                                   L.ptr(c_recipm1), L.ptr(c1), L.ptr(c2), L.ptr(c3), b, x.numel() // b, L.stream()),
+            "p_sample_update_multistep")
+    return x
+
+
 def randn(shape, device, seed, step, stream_id=0):
     out = torch.empty(shape, device=device, dtype=torch.float32)
     L.check(L.load().ddk_randn(L.ptr(out), out.numel(), seed, step, stream_id, L.stream()), "randn")

@@ -78,13 +78,13 @@ class UnetPlan:
         time-shift table live in / point into their workspace, so a trainer that alternates sample() (t_start = T-1) and
         reconstruct() (t_start = t_rec_max) at every logging event keeps both sets of graphs instead of re-capturing twice per event.
         Only an eviction drops the plan's cached graphs (ddk_sampler_invalidate waits for the device).  The likelihood sweep's
-        workspaces ("vsw") are kept the same way: its captured steps point into them too."""
+        workspaces ("vsw") and the multistep sampler's ("sms") are kept the same way: their captured steps point into them too."""
         key = (kind, nbytes, str(device))
         hit = self._ws.get(key)
         if hit is not None:
             self._ws[key] = self._ws.pop(key)          # most recently used last
             return hit
-        if kind in ("smp", "vsw"):
+        if kind in ("smp", "vsw", "sms"):
             mine = [k for k in self._ws if k[0] == kind]       # dict order = least recently used first
             if len(mine) >= 3:
                 # evict ONLY the least recently used workspace; the plan drops the graphs that point into it (and waits for
@@ -217,19 +217,7 @@ class UnetPlan:
         n_steps = t_start - t_end + 1
         if noise is not None and tuple(noise.shape) != (n_steps, b, h, w, c):
             raise L.DDKError(f"injected noise must be {(n_steps, b, h, w, c)}, got {tuple(noise.shape)}")
-        # The captured graph holds the ADDRESS of the chain state.  A caller that keeps passing the same tensor (bench, a
-        # serving loop) is run in place; once a different address shows up for this shape (p_sample_loop builds a fresh
-        # tensor per call) the chain moves to a plan-owned state buffer, so later calls hit the cached graph again.
-        skey = (tuple(x.shape), str(x.device))
-        mode = self._state.get(skey)
-        if mode is None:
-            mode = self._state[skey] = {"ptr": x.data_ptr(), "buf": None}
-        caller_x = x
-        if mode["buf"] is None and mode["ptr"] != x.data_ptr():
-            mode["buf"] = torch.empty_like(x)
-        if mode["buf"] is not None:
-            mode["buf"].copy_(x)
-            x = mode["buf"]
+        caller_x, x = x, self._chain_x(x)
         # the in-launch GroupNorm can fail (loudly) when the GPU is shared: keep x_T so the chain can be rerun without it
         x_start = x.clone() if self._chain_guarded() else None
 
@@ -243,6 +231,57 @@ class UnetPlan:
                 L.check(lib.ddk_sampler_run_spaced(C.byref(a), tmap, stream_ptr), "sampler_run_spaced")
 
         self._run_chain("sampler", call, ws, b, h, w, use_graph and n_steps > 1, restore=lambda: x.copy_(x_start))
+        if caller_x.data_ptr() != x.data_ptr():
+            caller_x.copy_(x)
+        return caller_x
+
+    def _chain_x(self, x):
+        """The buffer a sampler chain runs on.  The captured graph holds the ADDRESS of the chain state.  A caller that keeps
+        passing the same tensor (bench, a serving loop) is run in place; once a different address shows up for this shape
+        (p_sample_loop builds a fresh tensor per call) the chain moves to a plan-owned state buffer, so later calls hit the
+        cached graph again."""
+        skey = (tuple(x.shape), str(x.device))
+        mode = self._state.get(skey)
+        if mode is None:
+            mode = self._state[skey] = {"ptr": x.data_ptr(), "buf": None}
+        if mode["buf"] is None and mode["ptr"] != x.data_ptr():
+            mode["buf"] = torch.empty_like(x)
+        if mode["buf"] is not None:
+            mode["buf"].copy_(x)
+            return mode["buf"]
+        return x
+
+    def sample_multistep_nhwc(self, x, tables, t_start, t_end=0, stream_id=0, use_graph=True, timesteps=None):
+        """DPM-Solver++(2M) steps t_start .. t_end (inclusive) in place on x [B,H,W,in_ch] (ddk_sampler_run_multistep).
+
+        tables: dict with c_recip, c_recipm1, c1, c2, c3 (K-row fp32 device tensors of models/diffusion/respace.py
+        dpm_solver_tables; c3[t_start] == 0).  timesteps: the chain's timestep map (t_start + 1 ints, map[0] == 0, increasing) or
+        None for the identity.  Deterministic: no noise, no seed.  The solver's history lives in the plan's "sms" workspace and is
+        zeroed by every call."""
+        if self.packed is None:
+            raise L.DDKError("UnetPlan.sample_multistep before pack()")
+        b, h, w, c = x.shape
+        lib = self._lib
+        tmap = None
+        if timesteps is not None:
+            if len(timesteps) != t_start + 1:
+                raise L.DDKError(f"timestep map must have t_start + 1 = {t_start + 1} entries, got {len(timesteps)}")
+            tmap = (C.c_int64 * len(timesteps))(*[int(v) for v in timesteps])
+        nbytes = lib.ddk_sampler_multistep_workspace_bytes(self.handle, b, h, w, t_start)
+        if nbytes == 0:
+            raise L.DDKError(f"multistep sampler workspace query failed: {L.last_error()}")
+        ws = self._workspace("sms", nbytes, x.device)
+        n_steps = t_start - t_end + 1
+        caller_x, x = x, self._chain_x(x)
+        x_start = x.clone() if self._chain_guarded() else None
+
+        def call(stream_ptr):
+            a = L.SamplerArgs(self.handle, L.ptr(self.packed), L.ptr(x), None, L.ptr(tables["c_recip"]), L.ptr(tables["c_recipm1"]),
+                              L.ptr(tables["c1"]), L.ptr(tables["c2"]), None, b, h, w, t_start, t_end, 0, stream_id, int(use_graph),
+                              L.ptr(ws), nbytes)
+            L.check(lib.ddk_sampler_run_multistep(C.byref(a), tmap, L.ptr(tables["c3"]), stream_ptr), "sampler_run_multistep")
+
+        self._run_chain("sampler_multistep", call, ws, b, h, w, use_graph and n_steps > 1, restore=lambda: x.copy_(x_start))
         if caller_x.data_ptr() != x.data_ptr():
             caller_x.copy_(x)
         return caller_x

@@ -14,7 +14,9 @@ The reference hard-codes its constants; here they are the defaults of optional f
   * ``--synthetic CONFIG`` builds deterministic synthetic weights when no checkpoint exists (offline boxes);
   * ``--timestep_respacing SPEC``, ``--use_ddim`` and ``--eta`` (improved-diffusion's flag names) sample K of the T steps,
     ancestrally or with DDIM (models/diffusion/respace.py).  With any of them set the output name gains a suffix such as
-    ``_ddim50_ddim_eta0``, so the full-chain samples of the same checkpoint are never overwritten.
+    ``_ddim50_ddim_eta0``, so the full-chain samples of the same checkpoint are never overwritten;
+  * ``--dpm_solver`` samples with DPM-Solver++(2M) over the ``--timestep_respacing`` steps (best on a log-SNR grid, e.g.
+    ``logsnr20``); it excludes ``--use_ddim`` and ``--eta`` and writes e.g. ``{saved_model}_logsnr20_dpmpp2m.npy``.
 """
 import argparse
 import json
@@ -45,15 +47,24 @@ def main():
     ap.add_argument("--timestep_respacing", default="", help='sample K of the T steps: "ddimN", "N" or "n1,n2,..." sections')
     ap.add_argument("--use_ddim", action="store_true", help="DDIM steps instead of ancestral ones")
     ap.add_argument("--eta", type=float, default=0.0, help="DDIM noise scale (0: deterministic)")
+    ap.add_argument("--dpm_solver", action="store_true",
+                    help='DPM-Solver++(2M) steps over the --timestep_respacing grid (e.g. "logsnr20"); not with --use_ddim / --eta')
     args = ap.parse_args()
+    if args.dpm_solver and (args.use_ddim or args.eta != 0.0):
+        ap.error("--dpm_solver is its own deterministic update: it cannot be combined with --use_ddim or --eta")
     if args.eta < 0 or (args.eta != 0.0 and not args.use_ddim):
         ap.error("--eta needs --use_ddim and a value >= 0")
-    spaced = bool(args.timestep_respacing) or args.use_ddim or args.eta != 0.0
-    sample_kw = dict(respacing=args.timestep_respacing or None, ddim=args.use_ddim, eta=args.eta) if spaced else {}
+    spaced = bool(args.timestep_respacing) or args.use_ddim or args.eta != 0.0 or args.dpm_solver
+    sample_kw = {}
+    if args.dpm_solver:
+        sample_kw = dict(respacing=args.timestep_respacing or None, solver="dpm++2m")
+    elif spaced:
+        sample_kw = dict(respacing=args.timestep_respacing or None, ddim=args.use_ddim, eta=args.eta)
     # full-chain runs keep the reference's file names; spaced runs write beside them
     suffix = ""
     if spaced:
         suffix = "_" + (args.timestep_respacing.replace(",", "-") or "full") + (f"_ddim_eta{args.eta:g}" if args.use_ddim else "")
+        suffix += "_dpmpp2m" if args.dpm_solver else ""
 
     rank, world = init_from_env()
     local = int(os.environ.get("LOCAL_RANK", "0"))

@@ -53,8 +53,9 @@ class DownsampleDDPM(DDPM):
 
     # ------------------------------------------------------------------ sampling (dddpm.py:76-90)
     @torch.no_grad()
-    def sample(self, batch_size=16, every=1, early_stop=None, *, respacing=None, ddim=False, eta=0.0):
-        z_sample = self.p_sample_loop((batch_size, *self.sample_shape), every, early_stop, respacing=respacing, ddim=ddim, eta=eta)
+    def sample(self, batch_size=16, every=1, early_stop=None, *, respacing=None, ddim=False, eta=0.0, solver=None):
+        z_sample = self.p_sample_loop((batch_size, *self.sample_shape), every, early_stop, respacing=respacing, ddim=ddim, eta=eta,
+                                      solver=solver)
         x_sample = self.rescaled_upsample(z_sample)
         assert list(z_sample.shape)[1:] == self.sample_shape
         assert list(x_sample.shape)[1:] == self.x_shape

@@ -22,6 +22,7 @@ from . import respace
 from .beta_schedule import make_beta_schedule
 
 OBJETIVE_NAMES = ['simple', 'hybrid', 'vlb']
+SOLVERS = ('dpm++2m',)
 
 
 class DDPM(nn.Module):
@@ -65,7 +66,7 @@ class DDPM(nn.Module):
         assert not torch.isnan(self.vlb_weights).all()
         # exp(0.5 * logvar) of ddpm.py:227 evaluated once with the same fp32 torch ops (non-persistent)
         self.register_buffer('posterior_sigma', f32_tables['posterior_sigma'], persistent=False)
-        self._spaced = {}      # (respacing, ddim, eta, device) -> (tables, timestep map): see _spaced_tables
+        self._spaced = {}      # (respacing, ddim, eta, device) -> (tables, timestep map): see _spaced_tables (and _solver_tables)
 
         # sampler knobs (not in the reference): native hipGraph loop + in-kernel Philox noise by default
         self.native_sampler = True
@@ -153,9 +154,20 @@ class DDPM(nn.Module):
             hit = self._spaced[key] = ({k: v.to(device) for k, v in tables.items()}, use)
         return hit
 
+    def _solver_tables(self, respacing, solver):
+        """(tables c_recip, c_recipm1, c1, c2, c3 on the model's device, timestep map) of a DPM-Solver++(2M) chain
+        (respace.dpm_solver_tables), made once per (respacing, solver, device) like _spaced_tables."""
+        device = self.betas.device
+        key = ('solver', respacing, solver, str(device))
+        hit = self._spaced.get(key)
+        if hit is None:
+            tables, use = respace.dpm_solver_tables(self._betas64, respacing, order=2)
+            hit = self._spaced[key] = ({k: v.to(device) for k, v in tables.items()}, use)
+        return hit
+
     @torch.no_grad()
     def p_sample_loop(self, shape, every=1, early_stop=None, x_T=None, noise=None, seed=None, *, respacing=None, ddim=False,
-                      eta=0.0):
+                      eta=0.0, solver=None):
         """ddpm.py:229-249.  ``every`` is unused (as in the reference).  Extra keyword-only style arguments:
         x_T / noise inject the start state and the per-step draws ([n_steps, *shape]) for parity tests;
         seed fixes the in-kernel Philox stream (default: drawn from torch's generator).
@@ -164,7 +176,17 @@ class DDPM(nn.Module):
         (respace.space_timesteps spec, e.g. "ddim50", "250", "10,10,10"; None keeps all T), as ancestral steps of the respaced
         DDPM or, with ddim=True, as DDIM steps with noise scale eta.  early_stop then runs the spaced steps whose original
         timestep is >= early_stop; noise holds one draw per spaced step run, in run order; the in-kernel Philox draw of spaced
-        step k is keyed by k (not by its original timestep).  The defaults run the plain T-step chain."""
+        step k is keyed by k (not by its original timestep).  The defaults run the plain T-step chain.
+
+        solver="dpm++2m": DPM-Solver++(2M) steps over the respacing's timesteps (use "logsnrN").  The
+        solver is deterministic: it cannot be combined with ddim, eta or noise (ValueError, before any device work); seed is
+        unused.  early_stop cuts the bottom of the chain as for DDIM."""
+        if solver is not None:
+            if solver not in SOLVERS:
+                raise ValueError(f"p_sample_loop: solver must be one of {SOLVERS} or None, got {solver!r}")
+            if ddim or eta != 0 or noise is not None:
+                raise ValueError(f"p_sample_loop: solver={solver!r} is deterministic and its own update: no ddim, eta or noise")
+            return self._solver_loop(shape, early_stop, x_T, respacing, solver)
         spaced = respacing is not None or ddim or eta != 0
         if spaced and (eta < 0 or (eta != 0 and not ddim)):
             raise ValueError(f"p_sample_loop: eta = {eta} needs ddim=True and eta >= 0")
@@ -211,10 +233,37 @@ class DDPM(nn.Module):
                                 use_graph=self.use_graph, timesteps=use)
         return ops.nhwc_to_nchw(x)
 
+    def _solver_loop(self, shape, early_stop, x_T, respacing, solver):
+        """p_sample_loop(solver=...): steps k_start .. k_end of the solver's tables, step k at timestep use[k]; native
+        (UnetPlan.sample_multistep_nhwc) or, with native_sampler off, the same update as a Python loop."""
+        device = self.betas.device
+        if device.type != 'cuda':
+            raise DDKError("p_sample_loop: move the model to a ROCm device first (no CPU fallback)")
+        tables, use = self._solver_tables(respacing, solver)
+        k_start = len(use) - 1
+        k_end = 0 if early_stop is None else next((k for k, t in enumerate(use) if t >= early_stop), len(use))
+        img = torch.randn(shape, device=device) if x_T is None else x_T.to(device).float()
+        if k_end > k_start:
+            return img
+        if not self.native_sampler:
+            hist = torch.zeros_like(img).contiguous()
+            for k in range(k_start, k_end - 1, -1):
+                self._check_device(img)
+                eps_hat = self.latent_model(img, torch.full((shape[0],), use[k], device=device, dtype=torch.long))
+                img = img.contiguous().clone()
+                ops.p_sample_update_multistep_(img, eps_hat.contiguous(), hist, torch.full((shape[0],), k, device=device, dtype=torch.long),
+                                               **tables)
+            return img
+        x = ops.nchw_to_nhwc(img.contiguous())
+        self._eps_model_nhwc().plan().sample_multistep_nhwc(x, tables, k_start, k_end, stream_id=self.rng_stream_id,
+                                                            use_graph=self.use_graph, timesteps=use)
+        return ops.nhwc_to_nchw(x)
+
     @torch.no_grad()
-    def sample(self, batch_size=16, every=1, early_stop=None, *, respacing=None, ddim=False, eta=0.0):
-        """ddpm.py:251-254 (respacing / ddim / eta: see p_sample_loop)."""
-        return self.p_sample_loop((batch_size, *self.sample_shape), every, early_stop, respacing=respacing, ddim=ddim, eta=eta)
+    def sample(self, batch_size=16, every=1, early_stop=None, *, respacing=None, ddim=False, eta=0.0, solver=None):
+        """ddpm.py:251-254 (respacing / ddim / eta / solver: see p_sample_loop)."""
+        return self.p_sample_loop((batch_size, *self.sample_shape), every, early_stop, respacing=respacing, ddim=ddim, eta=eta,
+                                  solver=solver)
 
     @torch.no_grad()
     def reconstruct(self, x, n):

@@ -285,6 +285,12 @@ int ddk_p_sample_update(float* x, const float* eps_hat, const float* noise, cons
                         const float* c_recip, const float* c_recipm1, const float* c1, const float* c2,
                         const float* sigma, int B, long long per, uint64_t seed, uint32_t stream_id,
                         ddk_stream_t s);
+/* The DPM-Solver++(2M) update of ddk_sampler_run_multistep on its own: x0 = clamp(c_recip[t] x - c_recipm1[t] eps_hat, -1, 1),
+ * x = (c1[t] x0 + c2[t] x) + c3[t] x0_hist, then x0_hist = x0, per sample b with t[b]; x, eps_hat and x0_hist share one layout
+ * (per % 4 == 0, 16-byte aligned).  Start a chain with x0_hist zeroed. */
+int ddk_p_sample_update_multistep(float* x, const float* eps_hat, float* x0_hist, const int64_t* t, const float* c_recip,
+                                  const float* c_recipm1, const float* c1, const float* c2, const float* c3, int B, long long per,
+                                  ddk_stream_t s);
 /* The end of a forward in one launch (unet.py:69-72 behind the final Block's conv; ddpm.py:203-227): GroupNorm from the conv's
  * partials -> Mish -> 1x1 projection to n_out <= 8 channels (w [n_out][C], bias [n_out]) -> eps_hat; eps_out and / or x may be
  * given: eps_out [B][HW][n_out] receives eps_hat, x [B][HW][n_out] gets the reverse-step update of ddk_p_sample_update in place
@@ -435,6 +441,16 @@ int ddk_sampler_run(const ddk_sampler_args* a, ddk_stream_t s);
  * map and rebuilds it (one upload and a stream wait, outside any captured step) when a call brings a different map.
  * timestep_map == NULL is the identity: exactly ddk_sampler_run. */
 int ddk_sampler_run_spaced(const ddk_sampler_args* a, const int64_t* timestep_map, ddk_stream_t s);
+/* DPM-Solver++(2M) (Lu et al. 2022, Algorithm 2, data prediction with clipping): a chain like ddk_sampler_run_spaced whose update
+ * also takes the previous step's clipped x0,
+ *     x0 = clamp(c_recip[k] x - c_recipm1[k] eps_hat, -1, 1);  x_prev = (c1[k] x0 + c2[k] x) + c3[k] x0_prev,
+ * with the K-row tables of models/diffusion/respace.py dpm_solver_tables.  The history (B * H * W * in_ch floats) lives in
+ * `workspace` behind the sampler's layout, so the workspace is ddk_sampler_multistep_workspace_bytes; every call zeroes it
+ * before its first step (outside any captured step).  a->sigma and a->seed are ignored; a->noise must be NULL (DDK_ERR_ARG).
+ * c3[t_start] must be 0: the tables are built for the map given, whose last row is the chain's first, first-order step.
+ * Graphs are cached as for ddk_sampler_run, under a chain kind of their own with c3 in the key. */
+size_t ddk_sampler_multistep_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start);
+int ddk_sampler_run_multistep(const ddk_sampler_args* a, const int64_t* timestep_map, const float* c3, ddk_stream_t s);
 /* Drops the plan's cached sampler and likelihood-sweep graphs and shift table (waits for the device when graphs exist). */
 int ddk_sampler_invalidate(ddk_unet* u);
 /* Drops only the cached graphs (and shift table) that live in / point into `workspace`, after waiting for the launches of

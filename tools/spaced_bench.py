@@ -7,7 +7,11 @@ plain chain of the same K steps (t = 999 .. 1000 - K, the benchmark's own call) 
 each, every chain from the same x_T and bracketed by device synchronisation; the per-step figure is the median.  The clock is
 settled first by running plain steps for a while (measuring-on-mi355x: warm up by time).  images/s = B / (K * ms_step + t_decode),
 with the x3 decode (tanh(upsample(z))) timed in the same run; T = 1000 is the plain chain's per-step time x 1000.  One JSON line on
-stdout.  GPU-box tool."""
+stdout.  GPU-box tool.
+
+--solver: the cost of a DPM-Solver++(2M) step against a DDIM (eta 0) step on the same "logsnrK" grid, K in {20, 50}, timed
+alternately the same way (the two chains differ only in the step's last kernel: a history load and store instead of a draw)."""
+import argparse
 import json
 import os
 import statistics
@@ -26,10 +30,14 @@ from utils import synthetic as syn
 DEV = "cuda"
 B, C, S, T = 32, 8, 32, 1000
 KS = (50, 100, 250)
+SOLVER_KS = (20, 50)
 REPS = 5
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--solver", action="store_true", help="2M step against DDIM step on logsnrK grids")
+    args = ap.parse_args()
     torch.cuda.set_device(0)
     cfg = bench.cfg4()
     model = DownsampleDDPM(cfg, Unet(cfg), DEV, 3)
@@ -46,6 +54,12 @@ def main():
         t0 = time.perf_counter()
         if kind == "plain":
             plan.sample_nhwc(x, tables, T - 1, T - K, seed=1234, stream_id=0)
+        elif kind == "ddim_logsnr":
+            sp, use = model._spaced_tables(f"logsnr{K}", True, 0.0)
+            plan.sample_nhwc(x, sp, K - 1, 0, seed=1234, stream_id=0, timesteps=use)
+        elif kind == "2m":
+            sp, use = model._solver_tables(f"logsnr{K}", "dpm++2m")
+            plan.sample_multistep_nhwc(x, sp, K - 1, 0, stream_id=0, timesteps=use)
         else:
             sp, use = model._spaced_tables(f"ddim{K}", True, 0.0)
             plan.sample_nhwc(x, sp, K - 1, 0, seed=1234, stream_id=0, timesteps=use)
@@ -59,6 +73,9 @@ def main():
         torch.cuda.synchronize()
         assert torch.isfinite(img).all() and img.shape == (B, 3, 256, 256)
         return (time.perf_counter() - t0) * 1e3
+
+    if args.solver:
+        return solver_ab(chain, decode)
 
     res = {"shape": f"cfg4 unet_chan 128, {C}x{S}x{S} latents, B={B}, T={T}, DDIM eta 0", "reps": REPS, "per_K": {}}
     with torch.no_grad():
@@ -85,6 +102,31 @@ def main():
         res["decode_ms"] = round(decode_ms, 3)
         res["T1000_images_per_sec"] = round(B / ((T * p_all + decode_ms) / 1e3), 2)
         res["max_spaced_over_plain"] = max(v["spaced_over_plain"] for v in res["per_K"].values())
+    print(json.dumps(res), flush=True)
+
+
+def solver_ab(chain, decode):
+    res = {"shape": f"cfg4 unet_chan 128, {C}x{S}x{S} latents, B={B}, T={T}, logsnrK grids, DPM-Solver++(2M) vs DDIM eta 0",
+           "reps": REPS, "per_K": {}}
+    with torch.no_grad():
+        t_settle = time.perf_counter()
+        while time.perf_counter() - t_settle < 2.0:
+            chain("plain", 96)
+        decode_ms = min(decode() for _ in range(3))
+        for K in SOLVER_KS:
+            chain("ddim_logsnr", K)                      # captures both chains' graphs outside the timed calls
+            chain("2m", K)
+            ddim, ms = [], []
+            for _ in range(REPS):
+                ddim.append(chain("ddim_logsnr", K) / K)
+                ms.append(chain("2m", K) / K)
+            d, m = statistics.median(ddim), statistics.median(ms)
+            res["per_K"][str(K)] = {"ddim_ms_per_step": round(d, 4), "dpm2m_ms_per_step": round(m, 4), "dpm2m_over_ddim": round(m / d, 4),
+                                    "ddim_min_max_ms": [round(min(ddim), 4), round(max(ddim), 4)],
+                                    "dpm2m_min_max_ms": [round(min(ms), 4), round(max(ms), 4)],
+                                    "dpm2m_images_per_sec": round(B / ((K * m + decode_ms) / 1e3), 2)}
+        res["decode_ms"] = round(decode_ms, 3)
+        res["max_dpm2m_over_ddim"] = max(v["dpm2m_over_ddim"] for v in res["per_K"].values())
     print(json.dumps(res), flush=True)
 
 
