@@ -303,6 +303,20 @@ int p_sample_update(float* x, const float* eps_hat, const float* noise, long lon
 int p_sample_update_ms(float* x, const float* eps_hat, float* x0_hist, const int64_t* t, const float* c_recip, const float* c_recipm1,
                        const float* c1, const float* c2, const float* c3, int B, long long per, hipStream_t st,
                        int64_t* dec_counter = nullptr);
+// RePaint inpainting: the known latent, its mask and the per-row tables of one reverse op
+struct InpaintOps {
+    const float* known;           // x0 of the known image, same layout as x
+    const float* mask;            // same layout as x: nonzero = known
+    const float *ka, *kb;         // per row: x_kn = ka x0 + kb z2 (sqrt(abar_{tau-1}), sqrt(1 - abar_{tau-1}))
+    const float *ja, *jb;         // per row: the forward jump after the op, x = ja x + jb z3 (jb == 0: no jump)
+};
+constexpr uint32_t INPAINT_Z2_BIT = 0x40000000u;   // Philox stream of the known region's draw: stream_id | this
+constexpr uint32_t INPAINT_Z3_BIT = 0x20000000u;   // ... and of the jump's: stream_id | this (so stream_id < 2^29)
+// p_sample_update's op, then x = mask ? x_kn : x, then the optional jump (the sampler's last kernel of a step when unfused)
+int p_sample_update_inpaint(float* x, const float* eps_hat, const InpaintOps& ip, const int64_t* t, const float* c_recip,
+                            const float* c_recipm1, const float* c1, const float* c2, const float* sigma, int B, long long per,
+                            uint64_t seed, uint32_t stream_id, hipStream_t st, const int64_t* chain_state = nullptr,
+                            int64_t* dec_counter = nullptr);
 int randn(float* out, long long n, uint64_t seed, uint32_t step, uint32_t stream_id, hipStream_t st);
 // GroupNorm (from conv partials) + Mish + 1x1 projection to n_out <= 8 channels (+ the reverse-step update of x) in one launch
 // likelihood sweep (diffusion.hip, ddk_vlb_sweep_run): one step's operands besides the UNet's
@@ -329,11 +343,13 @@ int final_tail_vlb(const float* raw, const float* part, int np, const float* gam
 bool final_tail_ok(int HW, int C, int groups, int n_out, int np);
 bool final_tail_vlb_ok(int HW, int C, int groups, int n_out, int np);
 bool final_tail_ms_ok(int HW, int C, int groups, int n_out, int np);
+bool final_tail_inp_ok(int HW, int C, int groups, int n_out, int np);
 int final_tail(const float* raw, const float* part, int np, const float* gamma, const float* beta, float eps, const float* w,
                const float* bias, int n_out, float* eps_out, float* x, const float* noise, long long noise_step_stride, int t_first,
                const int64_t* t, const float* c_recip, const float* c_recipm1, const float* c1, const float* c2, const float* sigma,
                const int64_t* chain_state, uint64_t seed, uint32_t stream_id, int B, int HW, int C, int groups, hipStream_t st,
                int64_t* dec_counter = nullptr,      // dec_counter: the sampler's step counter, decremented by this (last) kernel of the step
-               float* x0_hist = nullptr, const float* c3 = nullptr);   // both given: the multistep update (final_tail_ms_ok shapes, no noise)
+               float* x0_hist = nullptr, const float* c3 = nullptr,    // both given: the multistep update (final_tail_ms_ok shapes, no noise)
+               const InpaintOps* inp = nullptr);                        // given: RePaint's op (final_tail_inp_ok shapes, Philox only)
 
 }  // namespace ddk

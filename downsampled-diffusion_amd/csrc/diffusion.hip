@@ -157,6 +157,65 @@ __global__ __launch_bounds__(256) void p_sample_ms_kernel(float* __restrict__ x,
     }
 }
 
+// RePaint (models/diffusion/respace.py repaint_tables).  One reverse op at spaced timestep tau:
+//   x_unk = p_step(x, eps_hat, z1);  x_kn = ka x0_known + kb z2 (ka = 1, kb = 0 at tau = 0: exactly x0_known);
+//   x = mask ? x_kn : x_unk (a select, not a blend: the known region stays exact and NaN-free);  jump: x = ja x + jb z3.
+// inp_known and inp_step are the arithmetic of both tails, so given the same eps_hat they are bit-identical.
+__device__ __forceinline__ float4 inp_known4(float4 k, float4 z2, float ka, float kb) {
+    float4 o;
+    o.x = __fadd_rn(__fmul_rn(ka, k.x), __fmul_rn(kb, z2.x));
+    o.y = __fadd_rn(__fmul_rn(ka, k.y), __fmul_rn(kb, z2.y));
+    o.z = __fadd_rn(__fmul_rn(ka, k.z), __fmul_rn(kb, z2.z));
+    o.w = __fadd_rn(__fmul_rn(ka, k.w), __fmul_rn(kb, z2.w));
+    return o;
+}
+
+__device__ __forceinline__ float inp_step(float x, float e, float z1, float xk, float m, float z3, float cr, float crm1, float c1,
+                                          float c2, float sg, float ja, float jb, bool jump) {
+    const float o = m != 0.0f ? xk : p_step(x, e, z1, cr, crm1, c1, c2, sg);
+    return jump ? __fadd_rn(__fmul_rn(ja, o), __fmul_rn(jb, z3)) : o;
+}
+
+__device__ __forceinline__ float4 inp_step4(float4 xv, float4 ev, float4 z1, float4 xk, float4 m, float4 z3, float cr, float crm1,
+                                            float c1, float c2, float sg, float ja, float jb, bool jump) {
+    float4 o;
+    o.x = inp_step(xv.x, ev.x, z1.x, xk.x, m.x, z3.x, cr, crm1, c1, c2, sg, ja, jb, jump);
+    o.y = inp_step(xv.y, ev.y, z1.y, xk.y, m.y, z3.y, cr, crm1, c1, c2, sg, ja, jb, jump);
+    o.z = inp_step(xv.z, ev.z, z1.z, xk.z, m.z, z3.z, cr, crm1, c1, c2, sg, ja, jb, jump);
+    o.w = inp_step(xv.w, ev.w, z1.w, xk.w, m.w, z3.w, cr, crm1, c1, c2, sg, ja, jb, jump);
+    return o;
+}
+
+// The inpainting op of the unfused tail: three Philox draws per float4, keyed (index, row t, stream / | 2^30 / | 2^29, seed); the
+// jump's draw only where the row has one.  It is the step's last kernel in the sampler, so it takes over the counter decrement.
+__global__ __launch_bounds__(256) void p_sample_inpaint_kernel(float* __restrict__ x, const float* __restrict__ eps_hat,
+                                                               const InpaintOps ip, const int64_t* __restrict__ t,
+                                                               const float* __restrict__ c_recip, const float* __restrict__ c_recipm1,
+                                                               const float* __restrict__ c1, const float* __restrict__ c2,
+                                                               const float* __restrict__ sigma, long long per4, long long total4,
+                                                               uint64_t seed, uint32_t stream, const int64_t* __restrict__ chain_state,
+                                                               int64_t* dec_counter) {
+    if (dec_counter && blockIdx.x == 0 && threadIdx.x == 0) *dec_counter -= 1;     // the step counter, by the step's last kernel (see final_tail)
+    if (chain_state) {
+        seed = (uint64_t)chain_state[1];
+        stream = (uint32_t)chain_state[2];
+    }
+    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total4; i += (long long)gridDim.x * 256) {
+        const int64_t tb = t[i / per4];
+        const float cr = c_recip[tb], crm1 = c_recipm1[tb], a1 = c1[tb], a2 = c2[tb];
+        const float sg = tb > 0 ? sigma[tb] : 0.0f;
+        const float ka = ip.ka[tb], kb = ip.kb[tb], ja = ip.ja[tb], jb = ip.jb[tb];
+        const bool jump = jb != 0.0f;
+        const float4 xv = reinterpret_cast<const float4*>(x)[i], ev = reinterpret_cast<const float4*>(eps_hat)[i];
+        const float4 kv = reinterpret_cast<const float4*>(ip.known)[i], mv = reinterpret_cast<const float4*>(ip.mask)[i];
+        const float4 z1 = philox_normal4((unsigned long long)i, (uint32_t)tb, stream, seed);
+        const float4 xk = inp_known4(kv, philox_normal4((unsigned long long)i, (uint32_t)tb, stream | INPAINT_Z2_BIT, seed), ka, kb);
+        const float4 z3 = jump ? philox_normal4((unsigned long long)i, (uint32_t)tb, stream | INPAINT_Z3_BIT, seed)
+                               : make_float4(0.f, 0.f, 0.f, 0.f);
+        reinterpret_cast<float4*>(x)[i] = inp_step4(xv, ev, z1, xk, mv, z3, cr, crm1, a1, a2, sg, ja, jb, jump);
+    }
+}
+
 // ---- the VLB term of one element (reference models/diffusion/ddpm.py:317-366, models/utils/losses.py:17-109) --------------------
 // Shared by vlb_terms_kernel and the likelihood sweep's epilogues (final_tail_kernel<.., true>, vlb_sweep_terms_kernel).
 __device__ __forceinline__ float std_normal_cdf_approx(float v) {
@@ -234,6 +293,8 @@ struct TailParams {
     // multistep (final_tail_kernel<.., .., false, true>): the previous step's clipped x0, same layout as x, read and rewritten
     float* x0_hist;
     const float* c3;
+    // inpainting (final_tail_kernel<.., .., false, false, true>): the known latent, its mask and the per-row tables
+    InpaintOps inp;
 };
 
 // VLB = false: eps_hat out and / or the reverse-step update of x.  VLB = true (ddk_vlb_sweep_run): phase 2 evaluates, per element,
@@ -241,7 +302,9 @@ struct TailParams {
 // the workgroup stores the two block sums to its own slot of vlb_part (plain stores, no atomics: the kernel boundary publishes them).
 // MS = true (ddk_sampler_run_multistep, x given): the DPM-Solver++(2M) update of p_sample_ms_kernel; the history float4 is
 // requested where the other modes draw their noise (no Philox rounds), and the thread that read it writes it back.
-template <int LPP, int VPL, bool VLB, bool MS = false>
+// INP = true (ddk_sampler_run_inpaint, x given, Philox only): RePaint's op of p_sample_inpaint_kernel; the known float4, the mask
+// float4 and the two extra draws are requested in the same prologue, and x_kn is formed there (4 registers live, not 8).
+template <int LPP, int VPL, bool VLB, bool MS = false, bool INP = false>
 __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
     constexpr int PPW = 64 / LPP;                    // pixels per wave and iteration
     constexpr int PPI = 16 * PPW;                    // ... per iteration of the 16-wave workgroup
@@ -285,6 +348,9 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
     float cr = 0.f, crm1 = 0.f, a1 = 0.f, a2 = 0.f, sg = 0.f, a3 = 0.f;
     int64_t tb = 0;
     float4 xt0 = xv0;
+    float4 xk0 = xv0, mk0 = xv0, z30 = xv0;           // INP: x_kn, the mask, the jump's draw
+    float ja = 0.f, jb = 0.f;
+    bool jump = false;
     VlbCoef kc{};
     if ((VLB || p.x) && tid < cnt4) {
         const uint64_t seed = p.chain_state ? (uint64_t)p.chain_state[1] : p.seed;
@@ -303,6 +369,15 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
         if constexpr (MS) zv0 = reinterpret_cast<const float4*>(p.x0_hist)[i];      // MS: zv0 holds the history, not a draw
         else zv0 = p.noise ? reinterpret_cast<const float4*>(p.noise + (long long)(p.t_first - tb) * p.noise_step_stride)[i]
                            : philox_normal4((unsigned long long)i, (uint32_t)tb, stream, seed);
+        if constexpr (INP) {
+            const float ka = p.inp.ka[tb], kb = p.inp.kb[tb];
+            ja = p.inp.ja[tb]; jb = p.inp.jb[tb];
+            jump = jb != 0.0f;                         // one row per launch: uniform
+            mk0 = reinterpret_cast<const float4*>(p.inp.mask)[i];
+            xk0 = inp_known4(reinterpret_cast<const float4*>(p.inp.known)[i],
+                             philox_normal4((unsigned long long)i, (uint32_t)tb, stream | INPAINT_Z2_BIT, seed), ka, kb);
+            if (jump) z30 = philox_normal4((unsigned long long)i, (uint32_t)tb, stream | INPAINT_Z3_BIT, seed);
+        }
     }
     __syncthreads();
     if (tid < G) {          // the same fixed-order merge as gn_apply_parts_kernel
@@ -380,6 +455,8 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
         if constexpr (MS) {
             reinterpret_cast<float4*>(p.x)[e4 + tid] = ms_step4(xv0, ev, zv0, cr, crm1, a1, a2, a3);
             reinterpret_cast<float4*>(p.x0_hist)[e4 + tid] = zv0;
+        } else if constexpr (INP) {
+            reinterpret_cast<float4*>(p.x)[e4 + tid] = inp_step4(xv0, ev, zv0, xk0, mk0, z30, cr, crm1, a1, a2, sg, ja, jb, jump);
         } else if (p.x) {
             float4 o;
             o.x = p_step(xv0.x, ev.x, zv0.x, cr, crm1, a1, a2, sg);
@@ -391,14 +468,15 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
     }
 }
 
-template <bool VLB, bool MS = false>
+template <bool VLB, bool MS = false, bool INP = false>
 static int launch_tail(const TailParams& p, int B, hipStream_t st) {
     const dim3 grid((unsigned)(B * p.np));
-    if (p.C == 32) hipLaunchKernelGGL((final_tail_kernel<8, 1, VLB, MS>), grid, dim3(1024), 0, st, p);
-    else if (p.C == 64) hipLaunchKernelGGL((final_tail_kernel<16, 1, VLB, MS>), grid, dim3(1024), 0, st, p);
-    else if (p.C == 128) hipLaunchKernelGGL((final_tail_kernel<32, 1, VLB, MS>), grid, dim3(1024), 0, st, p);
-    else if constexpr (!VLB && !MS) hipLaunchKernelGGL((final_tail_kernel<32, 2, VLB>), grid, dim3(1024), 0, st, p);
-    else DDK_REQUIRE(false, "final_tail: C = 256 takes the unfused epilogue in the VLB and multistep modes (final_tail_vlb_ok / final_tail_ms_ok)");
+    if (p.C == 32) hipLaunchKernelGGL((final_tail_kernel<8, 1, VLB, MS, INP>), grid, dim3(1024), 0, st, p);
+    else if (p.C == 64) hipLaunchKernelGGL((final_tail_kernel<16, 1, VLB, MS, INP>), grid, dim3(1024), 0, st, p);
+    else if (p.C == 128) hipLaunchKernelGGL((final_tail_kernel<32, 1, VLB, MS, INP>), grid, dim3(1024), 0, st, p);
+    else if constexpr (!VLB && !MS && !INP) hipLaunchKernelGGL((final_tail_kernel<32, 2, VLB>), grid, dim3(1024), 0, st, p);
+    else DDK_REQUIRE(false, "final_tail: C = 256 takes the unfused epilogue in the VLB, multistep and inpainting modes "
+                            "(final_tail_vlb_ok / final_tail_ms_ok / final_tail_inp_ok)");
     return check_launch("final_tail_kernel");
 }
 
@@ -406,6 +484,8 @@ static int launch_tail(const TailParams& p, int B, hipStream_t st) {
 bool final_tail_vlb_ok(int HW, int C, int groups, int n_out, int np) { return C <= 128 && final_tail_ok(HW, C, groups, n_out, np); }
 // the multistep update: the same subset (the 256-channel instantiation spills already without it)
 bool final_tail_ms_ok(int HW, int C, int groups, int n_out, int np) { return C <= 128 && final_tail_ok(HW, C, groups, n_out, np); }
+// the inpainting op: the same subset (its prologue holds three float4 more than the plain update's)
+bool final_tail_inp_ok(int HW, int C, int groups, int n_out, int np) { return C <= 128 && final_tail_ok(HW, C, groups, n_out, np); }
 
 bool final_tail_ok(int HW, int C, int groups, int n_out, int np) {
     if (!(C == 32 || C == 64 || C == 128 || C == 256)) return false;
@@ -418,11 +498,14 @@ int final_tail(const float* raw, const float* part, int np, const float* gamma, 
                const float* bias, int n_out, float* eps_out, float* x, const float* noise, long long noise_step_stride, int t_first,
                const int64_t* t, const float* c_recip, const float* c_recipm1, const float* c1, const float* c2, const float* sigma,
                const int64_t* chain_state, uint64_t seed, uint32_t stream_id, int B, int HW, int C, int groups, hipStream_t st,
-               int64_t* dec_counter, float* x0_hist, const float* c3) {
+               int64_t* dec_counter, float* x0_hist, const float* c3, const InpaintOps* inp) {
     DDK_REQUIRE(raw && part && gamma && beta && w && (eps_out || x) && B > 0, "final_tail: null pointer");
     DDK_REQUIRE(final_tail_ok(HW, C, groups, n_out, np), "final_tail: needs C in {32,64,128,256}, n_out <= 8, H*W == tiles * 128");
     DDK_REQUIRE(!x0_hist || (x && c3 && !noise && aligned16(x0_hist) && final_tail_ms_ok(HW, C, groups, n_out, np)),
                 "final_tail: the multistep update needs x, c3, no injected noise, an aligned history and C <= 128");
+    DDK_REQUIRE(!inp || (x && !x0_hist && !noise && inp->known && inp->mask && inp->ka && inp->kb && inp->ja && inp->jb &&
+                         aligned16(inp->known) && aligned16(inp->mask) && final_tail_inp_ok(HW, C, groups, n_out, np)),
+                "final_tail: the inpainting op needs x, its operands, no injected noise or history, aligned known / mask and C <= 128");
     DDK_REQUIRE(aligned16(raw) && aligned16(gamma) && aligned16(beta) && aligned16(w) && aligned16(eps_out) && aligned16(x) &&
                     aligned16(noise) && noise_step_stride % 4 == 0, "final_tail: alignment");
     DDK_REQUIRE(!x || (t && c_recip && c_recipm1 && c1 && c2 && (sigma || x0_hist)), "final_tail: the update needs t and the schedule tables");
@@ -434,6 +517,10 @@ int final_tail(const float* raw, const float* part, int np, const float* gamma, 
     p.np = np; p.HW = HW; p.C = C; p.cpg = C / groups; p.n_out = n_out; p.eps = eps;
     p.dec_counter = dec_counter;
     p.x0_hist = x0_hist; p.c3 = c3;
+    if (inp) {
+        p.inp = *inp;
+        return launch_tail<false, false, true>(p, B, st);
+    }
     return x0_hist ? launch_tail<false, true>(p, B, st) : launch_tail<false>(p, B, st);
 }
 
@@ -663,6 +750,20 @@ int p_sample_update_ms(float* x, const float* eps_hat, float* x0_hist, const int
     return check_launch("p_sample_ms_kernel");
 }
 
+int p_sample_update_inpaint(float* x, const float* eps_hat, const InpaintOps& ip, const int64_t* t, const float* c_recip,
+                            const float* c_recipm1, const float* c1, const float* c2, const float* sigma, int B, long long per,
+                            uint64_t seed, uint32_t stream_id, hipStream_t st, const int64_t* chain_state, int64_t* dec_counter) {
+    DDK_REQUIRE(x && eps_hat && ip.known && ip.mask && ip.ka && ip.kb && ip.ja && ip.jb && t && c_recip && c_recipm1 && c1 && c2 && sigma,
+                "p_sample_update_inpaint: null pointer");
+    DDK_REQUIRE(B > 0 && per > 0 && per % 4 == 0, "p_sample_update_inpaint: per-sample element count must be a multiple of 4");
+    DDK_REQUIRE(aligned16(x) && aligned16(eps_hat) && aligned16(ip.known) && aligned16(ip.mask), "p_sample_update_inpaint: alignment");
+    DDK_REQUIRE(chain_state || stream_id < INPAINT_Z3_BIT, "p_sample_update_inpaint: stream_id must be < 2^29 (bits 29, 30 key the extra draws)");
+    const long long total4 = B * per / 4;
+    hipLaunchKernelGGL(p_sample_inpaint_kernel, dim3(grid1d(total4)), dim3(256), 0, st, x, eps_hat, ip, t, c_recip, c_recipm1, c1, c2,
+                       sigma, per / 4, total4, seed, stream_id, chain_state, dec_counter);
+    return check_launch("p_sample_inpaint_kernel");
+}
+
 int randn(float* out, long long n, uint64_t seed, uint32_t step, uint32_t stream_id, hipStream_t st) {
     DDK_REQUIRE(out && n > 0 && aligned16(out), "randn: arguments");
     const long long n4 = (n + 3) / 4;
@@ -720,6 +821,14 @@ int ddk_p_sample_update_multistep(float* x, const float* eps_hat, float* x0_hist
                                   const float* c_recipm1, const float* c1, const float* c2, const float* c3, int B, long long per,
                                   ddk_stream_t s) {
     return p_sample_update_ms(x, eps_hat, x0_hist, t, c_recip, c_recipm1, c1, c2, c3, B, per, as_stream(s));
+}
+
+int ddk_p_sample_update_inpaint(float* x, const float* eps_hat, const float* known, const float* mask, const int64_t* t,
+                                const float* c_recip, const float* c_recipm1, const float* c1, const float* c2, const float* sigma,
+                                const float* ka, const float* kb, const float* ja, const float* jb, int B, long long per, uint64_t seed,
+                                uint32_t stream_id, ddk_stream_t s) {
+    const InpaintOps ip{known, mask, ka, kb, ja, jb};
+    return p_sample_update_inpaint(x, eps_hat, ip, t, c_recip, c_recipm1, c1, c2, sigma, B, per, seed, stream_id, as_stream(s));
 }
 
 int ddk_final_tail(const float* raw, const float* partials, int tiles_per_image, const float* gamma, const float* beta, float eps,

@@ -82,7 +82,7 @@ using namespace ddk;
 // pointer its kernels were launched with, so an entry is valid for exactly this kind of chain, this set of buffers and this
 // shape; t, the Philox seed / stream id and the injected-noise step index are read from device memory by the kernels, so the
 // same graph serves every step of every chain on those buffers.
-enum ChainKind { CHAIN_SAMPLER = 0, CHAIN_VLB_SWEEP = 1, CHAIN_SAMPLER_MULTISTEP = 2 };
+enum ChainKind { CHAIN_SAMPLER = 0, CHAIN_VLB_SWEEP = 1, CHAIN_SAMPLER_MULTISTEP = 2, CHAIN_SAMPLER_INPAINT = 3 };
 struct ChainKey {
     int kind;
     const void* bufs[12];                    // every buffer the step's kernels are launched with (unused entries null)
@@ -1153,18 +1153,20 @@ struct StepArgs {
     const VlbStep* vlb = nullptr;   // likelihood sweep: the forward ran on vlb->xt and ends in the VLB epilogue (x, sigma unused)
     float* x0_hist = nullptr;       // multistep sampler: the previous step's clipped x0 (read and rewritten), with c3; sigma, noise unused
     const float* c3 = nullptr;
+    const InpaintOps* inp = nullptr;  // inpainting sampler: RePaint's op (known latent, mask, row tables); noise unused
 };
 
 // tiles of the final tail when the end of the forward runs as ONE launch (final_tail_kernel), else 0.  cin = the final conv's
-// input channels (dimp[1]).  The sweep's VLB mode and the multistep update take a subset of the shapes (final_tail_vlb_ok,
-// final_tail_ms_ok).
-static int fused_tail_parts(const ddk_unet& u, int B, int H, int W, int cin, bool vlb, bool ms = false) {
+// input channels (dimp[1]).  The sweep's VLB mode, the multistep update and the inpainting op take a subset of the shapes
+// (final_tail_vlb_ok, final_tail_ms_ok, final_tail_inp_ok).
+static int fused_tail_parts(const ddk_unet& u, int B, int H, int W, int cin, bool vlb, bool ms = false, bool inp = false) {
     const int chan = u.generic ? pad32(u.cfg.chan) : u.cfg.chan, n_out = u.cfg.in_ch;
     const int npf = u.final_conv.has_wu ? conv_wino_stats_parts(B, H, W, cin, chan, GROUPS) : 0;
     if (npf <= 0) return 0;
     const int HW = H * W;
     return (vlb ? final_tail_vlb_ok(HW, chan, GROUPS, n_out, npf)
-                : ms ? final_tail_ms_ok(HW, chan, GROUPS, n_out, npf) : final_tail_ok(HW, chan, GROUPS, n_out, npf)) ? npf : 0;
+                : ms ? final_tail_ms_ok(HW, chan, GROUPS, n_out, npf)
+                : inp ? final_tail_inp_ok(HW, chan, GROUPS, n_out, npf) : final_tail_ok(HW, chan, GROUPS, n_out, npf)) ? npf : 0;
 }
 
 // t_cur[b] = counter for every sample, then counter -= 1; also zero-pads x into xpad.  First kernel of a step on shapes the
@@ -1375,7 +1377,7 @@ static int forward_core(const ddk_unet& u, const float* P, const float* x, int64
     }
     // final_conv: Block(dim, dim) then 1x1 to in_ch (unet.py:69-72)
     const int chan = u.generic ? pad32(u.cfg.chan) : u.cfg.chan, n_out = u.cfg.in_ch;
-    const int npf = fused_tail_parts(u, B, H, W, cur_c, step && step->vlb, step && step->x0_hist);
+    const int npf = fused_tail_parts(u, B, H, W, cur_c, step && step->vlb, step && step->x0_hist, step && step->inp);
     if (npf > 0 && (!step || step->per == (long long)H * W * n_out)) {
         // one-pass Winograd conv with statistics, then GroupNorm + Mish + projection (+ the update of x) in ONE launch
         ddk_conv_args a{};
@@ -1395,7 +1397,8 @@ static int forward_core(const ddk_unet& u, const float* P, const float* x, int64
         if (step)
             return final_tail(raw, gnp, npf, P + u.final_norm.g, P + u.final_norm.b, GN_EPS, P + u.final_w, P + u.final_b, n_out, nullptr,
                               step->x, step->noise, step->noise_step_stride, step->t_first, t, step->c_recip, step->c_recipm1, step->c1,
-                              step->c2, step->sigma, step->state, 0, 0, B, H * W, chan, GROUPS, st, dec_counter, step->x0_hist, step->c3);
+                              step->c2, step->sigma, step->state, 0, 0, B, H * W, chan, GROUPS, st, dec_counter, step->x0_hist, step->c3,
+                              step->inp);
         return final_tail(raw, gnp, npf, P + u.final_norm.g, P + u.final_norm.b, GN_EPS, P + u.final_w, P + u.final_b, n_out, out, nullptr,
                           nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, B, H * W, chan, GROUPS, st);
     }
@@ -1407,6 +1410,9 @@ static int forward_core(const ddk_unet& u, const float* P, const float* x, int64
     if (step->x0_hist)
         return p_sample_update_ms(step->x, eps_hat, step->x0_hist, t, step->c_recip, step->c_recipm1, step->c1, step->c2, step->c3, B,
                                   step->per, st, dec_counter);
+    if (step->inp)
+        return p_sample_update_inpaint(step->x, eps_hat, *step->inp, t, step->c_recip, step->c_recipm1, step->c1, step->c2, step->sigma, B,
+                                       step->per, 0, 0, st, step->state, dec_counter);
     return p_sample_update(step->x, eps_hat, step->noise, step->noise_step_stride, step->t_first, t, step->c_recip, step->c_recipm1,
                            step->c1, step->c2, step->sigma, B, step->per, 0, 0, st, step->state, dec_counter);
 }
@@ -1837,6 +1843,66 @@ extern "C" int ddk_sampler_run_multistep(const ddk_sampler_args* a, const int64_
     const ChainKey key{CHAIN_SAMPLER_MULTISTEP, {a->packed, a->x, a->c_recip, a->c_recipm1, a->c1, a->c2, c3}, a->workspace, nullptr,
                        B, H, W, a->t_start, c.dev, c.u->pack_epoch};
     return run_chain(*c.u, key, n_steps, a->use_graph != 0, one_step, c.st, "sampler_multistep");
+}
+
+// ------------------------------------------------------------------------------------------------ inpainting sampler
+// RePaint: N reverse ops, row k at timestep map[k]; every op ends in RePaint's select and optional forward
+// jump (p_sample_update_inpaint / final_tail's inpainting mode).  known and mask [B][H][W][in_ch] are copied behind the sampler
+// layout before the first op, outside any captured step, so the cached graph points only into the workspace.
+namespace ddk {
+static size_t inpaint_floats(const ddk_unet& u, int B, int H, int W, int t_start) {
+    return sampler_layout(u, B, H, W, t_start).total + 2 * al4((size_t)B * H * W * u.cfg.in_ch);
+}
+
+// RePaint's map revisits timesteps, so it is not monotone: map[0] == 0 (the only op at tau = 0) and 0 < map[k] < 2^31 for k > 0
+static int check_inpaint_map(const int64_t* map, int t_start, const char* who) {
+    if (map[0] != 0) {
+        set_error("%s: timestep_map[0] must be 0, got %lld", who, (long long)map[0]);
+        return DDK_ERR_ARG;
+    }
+    for (int k = 1; k <= t_start; ++k)
+        if (map[k] <= 0 || map[k] >= (int64_t(1) << 31)) {
+            set_error("%s: timestep_map[%d] = %lld must lie in (0, 2^31)", who, k, (long long)map[k]);
+            return DDK_ERR_ARG;
+        }
+    return DDK_OK;
+}
+}  // namespace ddk
+
+extern "C" size_t ddk_sampler_inpaint_workspace_bytes(const ddk_unet* u, int B, int H, int W, int n_ops) {
+    if (check_shape(u, B, H, W) != DDK_OK || n_ops < 1) return 0;
+    return inpaint_floats(*u, B, H, W, n_ops - 1) * sizeof(float);
+}
+
+extern "C" int ddk_sampler_run_inpaint(const ddk_sampler_args* a, const ddk_inpaint_args* ip, ddk_stream_t s) {
+    DDK_REQUIRE(a && ip && a->unet && a->packed && a->x && a->workspace, "sampler_inpaint: null pointer");
+    DDK_REQUIRE(a->c_recip && a->c_recipm1 && a->c1 && a->c2 && a->sigma, "sampler_inpaint: null schedule table");
+    DDK_REQUIRE(ip->timestep_map && ip->known && ip->mask && ip->ka && ip->kb && ip->ja && ip->jb, "sampler_inpaint: null inpainting operand");
+    DDK_REQUIRE(!a->noise, "sampler_inpaint: injected noise is not supported, noise must be NULL (Philox only)");
+    DDK_REQUIRE(a->stream_id < INPAINT_Z3_BIT, "sampler_inpaint: stream_id must be < 2^29 (bits 29, 30 key the extra draws)");
+    DDK_REQUIRE(a->t_start >= a->t_end && a->t_end >= 0, "sampler_inpaint: need t_start >= t_end >= 0");
+    DDK_REQUIRE(aligned16(ip->known) && aligned16(ip->mask), "sampler_inpaint: alignment");
+    DDK_TRY(check_inpaint_map(ip->timestep_map, a->t_start, "sampler_inpaint"));
+    const int B = a->B, H = a->H, W = a->W, n_steps = a->t_start - a->t_end + 1;
+    ChainRun c;
+    DDK_TRY(begin_chain(c, a, "sampler_inpaint", a->t_start, a->stream_id, ip->timestep_map, n_steps,
+                        [&](const SamplerLayout&) { return inpaint_floats(*a->unet, B, H, W, a->t_start); }, s));
+    const size_t n = (size_t)B * c.per;
+    float* known = c.ws + c.sl.total;
+    float* mask = known + al4(n);
+    DDK_HIP(hipMemcpyAsync(known, ip->known, n * sizeof(float), hipMemcpyDeviceToDevice, c.st));
+    DDK_HIP(hipMemcpyAsync(mask, ip->mask, n * sizeof(float), hipMemcpyDeviceToDevice, c.st));
+    const InpaintOps ops{known, mask, ip->ka, ip->kb, ip->ja, ip->jb};
+    StepArgs step{c.state, a->x, c.ws + c.sl.off_eps, nullptr, 0, a->t_start, a->c_recip, a->c_recipm1, a->c1, a->c2, a->sigma, c.per};
+    step.inp = &ops;
+
+    auto one_step = [&]() -> int { return c.forward(a->x, &step); };
+
+    // a kind of its own and the row tables in the key; known / mask live in the workspace, so they are not
+    const ChainKey key{CHAIN_SAMPLER_INPAINT,
+                       {a->packed, a->x, a->c_recip, a->c_recipm1, a->c1, a->c2, a->sigma, ip->ka, ip->kb, ip->ja, ip->jb},
+                       a->workspace, nullptr, B, H, W, a->t_start, c.dev, c.u->pack_epoch};
+    return run_chain(*c.u, key, n_steps, a->use_graph != 0, one_step, c.st, "sampler_inpaint");
 }
 
 // ------------------------------------------------------------------------------------------------ likelihood sweep

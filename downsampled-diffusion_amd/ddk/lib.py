@@ -45,6 +45,14 @@ class SamplerArgs(C.Structure):
     ]
 
 
+class InpaintArgs(C.Structure):
+    """ddk_inpaint_args (include/ddk.h)"""
+    _fields_ = [
+        ("timestep_map", C.POINTER(C.c_int64)), ("known", C.c_void_p), ("mask", C.c_void_p), ("ka", C.c_void_p), ("kb", C.c_void_p),
+        ("ja", C.c_void_p), ("jb", C.c_void_p),
+    ]
+
+
 class VlbSweepArgs(C.Structure):
     _fields_ = [
         ("unet", C.c_void_p), ("packed", C.c_void_p), ("x", C.c_void_p), ("noise", C.c_void_p),
@@ -143,6 +151,7 @@ SIGNATURES = {
     "ddk_q_sample": (_I, [_P, _P, _P, _P, _P, _P, _I, _LL, _P]),
     "ddk_p_sample_update": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _LL, C.c_uint64, C.c_uint32, _P]),
     "ddk_p_sample_update_multistep": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _LL, _P]),
+    "ddk_p_sample_update_inpaint": (_I, [_P] * 14 + [_I, _LL, C.c_uint64, C.c_uint32, _P]),
     "ddk_randn": (_I, [_P, _LL, C.c_uint64, C.c_uint32, C.c_uint32, _P]),
     "ddk_fix_samples": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "ddk_sq_err_sum": (_I, [_P, _P, _P, _I, _LL, _P]),
@@ -175,6 +184,8 @@ SIGNATURES = {
     "ddk_sampler_run_spaced": (_I, [C.POINTER(SamplerArgs), C.POINTER(C.c_int64), _P]),
     "ddk_sampler_multistep_workspace_bytes": (_SZ, [_P, _I, _I, _I, _I]),
     "ddk_sampler_run_multistep": (_I, [C.POINTER(SamplerArgs), C.POINTER(C.c_int64), _P, _P]),
+    "ddk_sampler_inpaint_workspace_bytes": (_SZ, [_P, _I, _I, _I, _I]),
+    "ddk_sampler_run_inpaint": (_I, [C.POINTER(SamplerArgs), C.POINTER(InpaintArgs), _P]),
     "ddk_sampler_invalidate": (_I, [_P]),
     "ddk_sampler_release_workspace": (_I, [_P, _P]),
     "ddk_vlb_sweep_workspace_bytes": (_SZ, [_P, _I, _I, _I, _I]),

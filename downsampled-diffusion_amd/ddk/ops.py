@@ -760,6 +760,17 @@ def p_sample_update_multistep_(x, eps_hat, x0_hist, t, c_recip, c_recipm1, c1, c
     return x
 
 
+def p_sample_update_inpaint_(x, eps_hat, known, mask, t, c_recip, c_recipm1, c1, c2, sigma, ka, kb, ja, jb, seed=0, stream_id=0):
+    """In-place RePaint op of x per sample row t[b]: the ancestral update with Philox draws, then
+    x = mask != 0 ? ka x_known + kb z2 : x, then the row's forward jump where jb != 0; x / eps_hat / known / mask share one layout."""
+    b = x.shape[0]
+    L.check(L.load().ddk_p_sample_update_inpaint(L.ptr(_f32(x)), L.ptr(_f32(eps_hat)), L.ptr(_f32(known)), L.ptr(_f32(mask)), L.ptr(t),
+                                                 L.ptr(c_recip), L.ptr(c_recipm1), L.ptr(c1), L.ptr(c2), L.ptr(sigma), L.ptr(ka),
+                                                 L.ptr(kb), L.ptr(ja), L.ptr(jb), b, x.numel() // b, seed, stream_id, L.stream()),
+            "p_sample_update_inpaint")
+    return x
+
+
 def randn(shape, device, seed, step, stream_id=0):
     out = torch.empty(shape, device=device, dtype=torch.float32)
     L.check(L.load().ddk_randn(L.ptr(out), out.numel(), seed, step, stream_id, L.stream()), "randn")

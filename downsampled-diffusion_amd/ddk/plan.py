@@ -78,13 +78,14 @@ class UnetPlan:
         time-shift table live in / point into their workspace, so a trainer that alternates sample() (t_start = T-1) and
         reconstruct() (t_start = t_rec_max) at every logging event keeps both sets of graphs instead of re-capturing twice per event.
         Only an eviction drops the plan's cached graphs (ddk_sampler_invalidate waits for the device).  The likelihood sweep's
-        workspaces ("vsw") and the multistep sampler's ("sms") are kept the same way: their captured steps point into them too."""
+        workspaces ("vsw"), the multistep sampler's ("sms") and the inpainting sampler's ("sin") are kept the same way: their
+        captured steps point into them too."""
         key = (kind, nbytes, str(device))
         hit = self._ws.get(key)
         if hit is not None:
             self._ws[key] = self._ws.pop(key)          # most recently used last
             return hit
-        if kind in ("smp", "vsw", "sms"):
+        if kind in ("smp", "vsw", "sms", "sin"):
             mine = [k for k in self._ws if k[0] == kind]       # dict order = least recently used first
             if len(mine) >= 3:
                 # evict ONLY the least recently used workspace; the plan drops the graphs that point into it (and waits for
@@ -282,6 +283,44 @@ class UnetPlan:
             L.check(lib.ddk_sampler_run_multistep(C.byref(a), tmap, L.ptr(tables["c3"]), stream_ptr), "sampler_run_multistep")
 
         self._run_chain("sampler_multistep", call, ws, b, h, w, use_graph and n_steps > 1, restore=lambda: x.copy_(x_start))
+        if caller_x.data_ptr() != x.data_ptr():
+            caller_x.copy_(x)
+        return caller_x
+
+    def sample_inpaint_nhwc(self, x, known, mask, tables, timesteps, t_end=0, seed=0, stream_id=0, use_graph=True):
+        """RePaint ops N-1 .. t_end (inclusive) in place on x [B,H,W,in_ch] (ddk_sampler_run_inpaint).
+
+        known, mask: [B,H,W,in_ch] fp32 device tensors (mask nonzero = known), copied into the plan's "sin" workspace by every call,
+        so a loop over images replays one cached graph.  tables: dict with c_recip, c_recipm1, c1, c2, sigma, ka, kb, ja, jb (N-row
+        fp32 device tensors of models/diffusion/respace.py repaint_tables).  timesteps: the N-entry timestep map (map[0] == 0, not
+        monotone).  Philox only: no injected noise; stream_id < 2^29."""
+        if self.packed is None:
+            raise L.DDKError("UnetPlan.sample_inpaint before pack()")
+        b, h, w, c = x.shape
+        for name, v in (("known", known), ("mask", mask)):
+            if tuple(v.shape) != (b, h, w, c) or v.dtype != torch.float32 or not v.is_contiguous():
+                raise L.DDKError(f"{name} must be a contiguous fp32 [{b},{h},{w},{c}] tensor, got {tuple(v.shape)} {v.dtype}")
+        lib = self._lib
+        n_ops = len(timesteps)
+        t_start = n_ops - 1
+        tmap = (C.c_int64 * n_ops)(*[int(v) for v in timesteps])
+        nbytes = lib.ddk_sampler_inpaint_workspace_bytes(self.handle, b, h, w, n_ops)
+        if nbytes == 0:
+            raise L.DDKError(f"inpainting sampler workspace query failed: {L.last_error()}")
+        ws = self._workspace("sin", nbytes, x.device)
+        n_steps = t_start - t_end + 1
+        caller_x, x = x, self._chain_x(x)
+        x_start = x.clone() if self._chain_guarded() else None
+
+        def call(stream_ptr):
+            a = L.SamplerArgs(self.handle, L.ptr(self.packed), L.ptr(x), None, L.ptr(tables["c_recip"]), L.ptr(tables["c_recipm1"]),
+                              L.ptr(tables["c1"]), L.ptr(tables["c2"]), L.ptr(tables["sigma"]), b, h, w, t_start, t_end, seed, stream_id,
+                              int(use_graph), L.ptr(ws), nbytes)
+            ip = L.InpaintArgs(tmap, L.ptr(known), L.ptr(mask), L.ptr(tables["ka"]), L.ptr(tables["kb"]), L.ptr(tables["ja"]),
+                               L.ptr(tables["jb"]))
+            L.check(lib.ddk_sampler_run_inpaint(C.byref(a), C.byref(ip), stream_ptr), "sampler_run_inpaint")
+
+        self._run_chain("sampler_inpaint", call, ws, b, h, w, use_graph and n_steps > 1, restore=lambda: x.copy_(x_start))
         if caller_x.data_ptr() != x.data_ptr():
             caller_x.copy_(x)
         return caller_x

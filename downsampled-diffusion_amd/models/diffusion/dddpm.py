@@ -62,6 +62,25 @@ class DownsampleDDPM(DDPM):
         return x_sample, z_sample
 
     @torch.no_grad()
+    def inpaint(self, x, mask, *, respacing=None, jump_length=10, jump_n_sample=10, x_T=None, seed=None, paste=True, **unsupported):
+        """RePaint in the latent (DDPM.inpaint).  The hidden pixels are zeroed before the encoder, so
+        z0 = rescaled_downsample(x * m) carries nothing of them.  A latent pixel is known only if its whole dim_reduc x dim_reduc
+        block is known in every channel (a min-pool of the mask), and all latent channels share that mask.  The decoded result
+        gets the known pixels of x put back when paste is set.  Returns (x_out, z) like sample; x_T is a latent start state."""
+        x, m = self._inpaint_args(x, mask, self.x_shape, jump_length, jump_n_sample, unsupported)
+        x, m = x.to(self.betas.device), m.to(self.betas.device)
+        self._check_device(x)
+        z0 = self.rescaled_downsample(torch.where(m != 0, x, torch.zeros_like(x)))
+        d = int(self.dim_reduc)
+        m_lat = -torch.nn.functional.max_pool2d(-m.amin(dim=1, keepdim=True), d)
+        m_lat = m_lat.expand(-1, self.sample_shape[0], -1, -1).contiguous()
+        z = self._inpaint_loop(z0, m_lat, respacing, jump_length, jump_n_sample, x_T, seed)
+        x_out = self.rescaled_upsample(z)
+        if paste:
+            x_out = torch.where(m != 0, x, x_out)
+        return x_out, z
+
+    @torch.no_grad()
     def reconstruct(self, x, n):
         """dddpm.py:33-74 (visualisation only)."""
         assert x.shape[0] >= n, f'batch size ({x.shape[0]}) is below {n}'

@@ -265,6 +265,90 @@ class DDPM(nn.Module):
         return self.p_sample_loop((batch_size, *self.sample_shape), every, early_stop, respacing=respacing, ddim=ddim, eta=eta,
                                   solver=solver)
 
+    # ------------------------------------------------------------------ RePaint inpainting (not in the reference)
+    INPAINT_UNSUPPORTED = ('ddim', 'solver', 'eta', 'noise', 'early_stop')
+
+    def _inpaint_args(self, x, mask, shape, jump_length, jump_n_sample, unsupported):
+        """ValueError for anything inpaint cannot take, before any device work.  Returns (x as float, mask as a float {0, 1}
+        tensor broadcast to [B, C, H, W]), both on x's device.  ``shape`` is [C, H, W] of the image."""
+        if unsupported:
+            raise ValueError(f"inpaint: {sorted(unsupported)} not accepted (RePaint runs ancestral steps with Philox draws over the "
+                             f"whole schedule: no {', '.join(self.INPAINT_UNSUPPORTED)})")
+        for name, v in (("jump_length", jump_length), ("jump_n_sample", jump_n_sample)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+                raise ValueError(f"inpaint: {name} must be an int >= 1, got {v!r}")
+        if not (0 <= int(self.rng_stream_id) < 2 ** 29):
+            raise ValueError(f"inpaint: rng_stream_id must be < 2^29 (bits 29, 30 key the extra draws), got {self.rng_stream_id}")
+        if not torch.is_tensor(x) or x.dim() != 4 or list(x.shape[1:]) != list(shape) or not x.is_floating_point():
+            raise ValueError(f"inpaint: x must be a float [B, {', '.join(map(str, shape))}] tensor, got "
+                             f"{tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}")
+        if not torch.is_tensor(mask) or mask.is_complex():
+            raise ValueError("inpaint: mask must be a real or bool tensor")
+        B, C, H, W = x.shape
+        m = mask
+        if m.dim() > 4:
+            raise ValueError(f"inpaint: mask must broadcast to [B, 1|C, H, W], got {tuple(m.shape)}")
+        while m.dim() < 4:
+            m = m.unsqueeze(0)
+        if m.shape[0] not in (1, B) or m.shape[1] not in (1, C) or tuple(m.shape[2:]) != (H, W):
+            raise ValueError(f"inpaint: mask must broadcast to [{B}, 1|{C}, {H}, {W}], got {tuple(mask.shape)}")
+        if m.dtype != torch.bool and not bool(((m == 0) | (m == 1)).all()):
+            raise ValueError("inpaint: mask values must be 0 or 1 (or bool)")
+        m = m.to(device=x.device, dtype=torch.float32).expand(B, C, H, W).contiguous()
+        if not bool(torch.isfinite(x[m != 0]).all()):
+            raise ValueError("inpaint: the known pixels of x must be finite")
+        return x.float(), m
+
+    def _inpaint_tables(self, respacing, jump_length, jump_n_sample):
+        """(tables c_recip .. sigma, ka, kb, ja, jb on the model's device, timestep map) of a RePaint chain
+        (respace.repaint_tables), made once per (respacing, j, r, device) like _spaced_tables."""
+        device = self.betas.device
+        key = ('repaint', respacing, int(jump_length), int(jump_n_sample), str(device))
+        hit = self._spaced.get(key)
+        if hit is None:
+            tables, use = respace.repaint_tables(self._betas64, respacing, int(jump_length), int(jump_n_sample))
+            hit = self._spaced[key] = ({k: v.to(device) for k, v in tables.items()}, use)
+        return hit
+
+    def _inpaint_loop(self, z0, m, respacing, jump_length, jump_n_sample, x_T, seed):
+        """RePaint over the latent z0 [B, *sample_shape] with mask m (same shape, {0, 1}): native (UnetPlan.sample_inpaint_nhwc) or,
+        with native_sampler off, the same op as a Python loop in the same NHWC layout, so both draw the same Philox numbers."""
+        device = self.betas.device
+        if device.type != 'cuda':
+            raise DDKError("inpaint: move the model to a ROCm device first (no CPU fallback)")
+        tables, use = self._inpaint_tables(respacing, jump_length, jump_n_sample)
+        shape = tuple(z0.shape)
+        if x_T is not None and tuple(x_T.shape) != shape:
+            raise ValueError(f"inpaint: x_T must be {shape}, got {tuple(x_T.shape)}")
+        img = torch.randn(shape, device=device) if x_T is None else x_T.to(device).float()
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        z0, m = z0.to(device).float(), m.to(device)
+        known = ops.nchw_to_nhwc(torch.where(m != 0, z0, torch.zeros_like(z0)).contiguous())   # nothing hidden reaches the chain
+        mk = ops.nchw_to_nhwc(m.contiguous())
+        x = ops.nchw_to_nhwc(img.contiguous())
+        if not self.native_sampler:
+            for k in range(len(use) - 1, -1, -1):
+                eps_hat = self.latent_model(ops.nhwc_to_nchw(x), torch.full((shape[0],), use[k], device=device, dtype=torch.long))
+                ops.p_sample_update_inpaint_(x, ops.nchw_to_nhwc(eps_hat.contiguous()), known, mk,
+                                             torch.full((shape[0],), k, device=device, dtype=torch.long), **tables, seed=seed,
+                                             stream_id=int(self.rng_stream_id))
+            return ops.nhwc_to_nchw(x)
+        self._eps_model_nhwc().plan().sample_inpaint_nhwc(x, known, mk, tables, use, seed=seed, stream_id=int(self.rng_stream_id),
+                                                          use_graph=self.use_graph)
+        return ops.nhwc_to_nchw(x)
+
+    @torch.no_grad()
+    def inpaint(self, x, mask, *, respacing=None, jump_length=10, jump_n_sample=10, x_T=None, seed=None, **unsupported):
+        """RePaint inpainting (Lugmayr et al. 2022): fill the pixels of x [B, C, H, W] (in [-1, 1]) where
+        mask is 0; mask broadcasts to [B, 1|C, H, W] with values in {0, 1} or bool (1 = known).  Runs the RePaint schedule
+        (respace.repaint_schedule) over the respacing's K steps (None: all T) with jumps of jump_length, each resampled
+        jump_n_sample times.  x_T: the start state; seed: the Philox key (default: drawn from torch's generator).  The known pixels
+        of the result equal x exactly; the hidden pixels of x are never read.  ddim / solver / eta / noise / early_stop raise
+        ValueError, as do bad masks, before any device work."""
+        x, m = self._inpaint_args(x, mask, self.sample_shape, jump_length, jump_n_sample, unsupported)
+        return self._inpaint_loop(x, m, respacing, jump_length, jump_n_sample, x_T, seed)
+
     @torch.no_grad()
     def reconstruct(self, x, n):
         """ddpm.py:126-147."""

@@ -19,6 +19,10 @@ step's clipped x0 (``dpm_solver_tables``):
     x_prev = c1[k] * x0_k + c2[k] * x + c3[k] * x0_{k+1}
 
 and ``"logsnrN"`` spaces its N steps evenly in log-SNR, the grid on which the second order pays off.
+
+RePaint inpainting (Lugmayr et al. 2022, arXiv:2201.09865) walks the K spaced steps with forward jumps back
+up (``repaint_schedule``); each of its N reverse ops is one row of ``repaint_tables``: the ancestral update's columns at the op's
+spaced index tau, plus ka / kb (the known image noised to abar_{tau-1}) and ja / jb (the closed-form forward jump after the op).
 """
 import numpy as np
 import torch
@@ -205,3 +209,59 @@ def spaced_tables(betas, spec=None, ddim=False, eta=0.0):
     else:
         tables.update(c1=f['posterior_mean_coef1'], c2=f['posterior_mean_coef2'], sigma=f['posterior_sigma'])
     return tables, use
+
+
+def repaint_schedule(K, jump_length, jump_n_sample):
+    """RePaint's get_schedule_jump over K spaced steps, as (tau of each reverse op in run order, jump length after each op).
+
+    jumps = {s: r - 1 for s in range(0, K - j, j)}; the state starts at s = K - 1 (x_T); a reverse op at tau = s leaves state
+    s - 1, and while jumps[s - 1] > 0 it is decremented and the state jumps forward to s - 1 + j.  N = K + (r - 1) j |jumps|
+    ops; tau = 0 occurs once, as the last op; r = 1 is the plain replacement method."""
+    if K < 1 or jump_length < 1 or jump_n_sample < 1:
+        raise ValueError(f"RePaint schedule needs K, jump_length, jump_n_sample >= 1, got {K}, {jump_length}, {jump_n_sample}")
+    jumps = {s: jump_n_sample - 1 for s in range(0, K - jump_length, jump_length)}
+    taus, jl = [], []
+    s = K - 1
+    while s >= 0:
+        taus.append(s)
+        jl.append(0)
+        s -= 1
+        if jumps.get(s, 0) > 0:
+            jumps[s] -= 1
+            jl[-1] = jump_length
+            s += jump_length
+    return taus, jl
+
+
+def repaint_coefficients(alphas_cumprod, taus, jumps):
+    """float64 (ka, kb, ja, jb) per op (run order) over a (respaced) abar, abar_{-1} = 1: ka = sqrt(abar_{tau-1}),
+    kb = sqrt(1 - abar_{tau-1}); after an op with a jump of length j, ja = sqrt(abar_{tau-1+j} / abar_{tau-1}) and
+    jb = sqrt(1 - abar_{tau-1+j} / abar_{tau-1}) (q(x_{s+j} | x_s) in closed form); ja = 1, jb = 0 without one."""
+    a = np.asarray(alphas_cumprod, dtype=np.float64)
+    ab = lambda i: 1.0 if i < 0 else float(a[i])
+    n = len(taus)
+    ka, kb, ja, jb = np.zeros(n), np.zeros(n), np.ones(n), np.zeros(n)
+    for i, (tau, j) in enumerate(zip(taus, jumps)):
+        ka[i], kb[i] = np.sqrt(ab(tau - 1)), np.sqrt(1. - ab(tau - 1))
+        if j:
+            ratio = ab(tau - 1 + j) / ab(tau - 1)
+            ja[i], jb[i] = np.sqrt(ratio), np.sqrt(1. - ratio)
+    return ka, kb, ja, jb
+
+
+def repaint_tables(betas, spec=None, jump_length=10, jump_n_sample=10):
+    """(fp32 tables c_recip, c_recipm1, c1, c2, sigma, ka, kb, ja, jb of N rows, timestep map of N entries) of a RePaint chain over
+    the float64 ``betas`` of the model.  Row k is op N-1-k of repaint_schedule (row 0 is the last op, at tau = 0); the ancestral
+    columns are the respaced DDPM's fp32 tables gathered at the op's tau (bit for bit spaced_tables'), ka .. jb are
+    repaint_coefficients cast once.  map[k] = the trained timestep of the op's tau, so map[0] == 0 and map is not monotone."""
+    sched, use = _respaced_schedule(betas, spec)
+    f = fp32_tables(sched)
+    taus, jl = repaint_schedule(len(use), jump_length, jump_n_sample)
+    taus, jl = taus[::-1], jl[::-1]                     # row order: row 0 = the last op
+    idx = torch.tensor(taus, dtype=torch.long)
+    ka, kb, ja, jb = repaint_coefficients(sched['alphas_cumprod'], taus, jl)
+    f32 = lambda v: torch.tensor(v, dtype=torch.float32)
+    tables = dict(c_recip=f['sqrt_recip_alphas_cumprod'][idx], c_recipm1=f['sqrt_recipm1_alphas_cumprod'][idx],
+                  c1=f['posterior_mean_coef1'][idx], c2=f['posterior_mean_coef2'][idx], sigma=f['posterior_sigma'][idx],
+                  ka=f32(ka), kb=f32(kb), ja=f32(ja), jb=f32(jb))
+    return tables, [use[t] for t in taus]

@@ -291,6 +291,14 @@ int ddk_p_sample_update(float* x, const float* eps_hat, const float* noise, cons
 int ddk_p_sample_update_multistep(float* x, const float* eps_hat, float* x0_hist, const int64_t* t, const float* c_recip,
                                   const float* c_recipm1, const float* c1, const float* c2, const float* c3, int B, long long per,
                                   ddk_stream_t s);
+/* RePaint's reverse op (ddk_sampler_run_inpaint) on its own, per sample b with row t[b]: x_unk = the update of ddk_p_sample_update
+ * with Philox draw z1; x_kn = ka[t] known + kb[t] z2; x = mask != 0 ? x_kn : x_unk; where jb[t] != 0 also x = ja[t] x + jb[t] z3.
+ * z1 / z2 / z3 are Philox on (element / 4, t[b], stream_id / stream_id | 2^30 / stream_id | 2^29, seed); stream_id must be < 2^29.
+ * x, eps_hat, known and mask share one layout (per % 4 == 0, 16-byte aligned); the row tables have one entry per row. */
+int ddk_p_sample_update_inpaint(float* x, const float* eps_hat, const float* known, const float* mask, const int64_t* t,
+                                const float* c_recip, const float* c_recipm1, const float* c1, const float* c2, const float* sigma,
+                                const float* ka, const float* kb, const float* ja, const float* jb, int B, long long per, uint64_t seed,
+                                uint32_t stream_id, ddk_stream_t s);
 /* The end of a forward in one launch (unet.py:69-72 behind the final Block's conv; ddpm.py:203-227): GroupNorm from the conv's
  * partials -> Mish -> 1x1 projection to n_out <= 8 channels (w [n_out][C], bias [n_out]) -> eps_hat; eps_out and / or x may be
  * given: eps_out [B][HW][n_out] receives eps_hat, x [B][HW][n_out] gets the reverse-step update of ddk_p_sample_update in place
@@ -451,6 +459,24 @@ int ddk_sampler_run_spaced(const ddk_sampler_args* a, const int64_t* timestep_ma
  * Graphs are cached as for ddk_sampler_run, under a chain kind of their own with c3 in the key. */
 size_t ddk_sampler_multistep_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start);
 int ddk_sampler_run_multistep(const ddk_sampler_args* a, const int64_t* timestep_map, const float* c3, ddk_stream_t s);
+/* RePaint inpainting (Lugmayr et al. 2022): N reverse ops, rows a->t_start = N-1 .. a->t_end (0 for the whole
+ * schedule), row k at the trained timestep ip->timestep_map[k] (host, N entries, NOT monotone: RePaint revisits timesteps; map[0]
+ * must be 0 and every other entry in (0, 2^31), else DDK_ERR_ARG).  Each op is ddk_p_sample_update_inpaint's with the ancestral
+ * tables in a (c_recip .. sigma, N rows) and the row tables in ip.  known / mask [B][H][W][in_ch] fp32 are copied into the
+ * workspace (ddk_sampler_inpaint_workspace_bytes) before the first op, outside any captured step, so the graph cache holds only
+ * workspace pointers: a loop over many images on one workspace replays one cached graph.  a->noise must be NULL (Philox only);
+ * a->stream_id must be < 2^29.  Graphs are cached under a chain kind of their own with the row tables in the key. */
+typedef struct ddk_inpaint_args {
+    const int64_t* timestep_map;   /* host [N] */
+    const float* known;            /* device [B][H][W][in_ch]: the known latent x0 */
+    const float* mask;             /* device [B][H][W][in_ch]: nonzero = known */
+    const float* ka;               /* device [N]: sqrt(abar_{tau-1}) */
+    const float* kb;               /* device [N]: sqrt(1 - abar_{tau-1}) */
+    const float* ja;               /* device [N]: the jump after the op, sqrt(abar_{tau-1+j} / abar_{tau-1}) */
+    const float* jb;               /* device [N]: sqrt(1 - abar_{tau-1+j} / abar_{tau-1}); 0 = no jump */
+} ddk_inpaint_args;
+size_t ddk_sampler_inpaint_workspace_bytes(const ddk_unet* u, int B, int H, int W, int n_ops);
+int ddk_sampler_run_inpaint(const ddk_sampler_args* a, const ddk_inpaint_args* ip, ddk_stream_t s);
 /* Drops the plan's cached sampler and likelihood-sweep graphs and shift table (waits for the device when graphs exist). */
 int ddk_sampler_invalidate(ddk_unet* u);
 /* Drops only the cached graphs (and shift table) that live in / point into `workspace`, after waiting for the launches of
