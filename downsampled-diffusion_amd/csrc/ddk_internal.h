@@ -207,7 +207,7 @@ int conv_first_gn(const float* x, const float* wp, const float* bias, const floa
                   int temb_stride, const long long* temb_rows, float eps, float* out, int B, int H, int W, int cin, int N, int groups,
                   float* records, unsigned* counters, unsigned* fail, int64_t* counter, int64_t* t_cur, hipStream_t st);
 // (in the sampler this kernel reads the step counter in EVERY workgroup -- the time shift's row -- so it must not decrement it: the
-//  step's last kernel does, final_tail / p_sample_update with dec_counter)
+//  step's last kernel does, final_tail / p_update with ChainHooks::dec_counter)
 // conv1x1_ws.hip: 1x1 conv with 128 input channels on a large map as a weights-stationary, pixel-streaming GEMM
 // (w = the packed 1x1 weight [N][128]; ln as in conv_forward)
 // conv1x1_sm.hip: 1x1 conv + bias + residual on small maps (32x32 tiles, the four waves split K, no ring)
@@ -295,14 +295,6 @@ int time_proj(const float* act, const float* wt, const float* bias, float* out, 
 // layout_pack.hip
 int conv1x1_small_n(const float* x, const float* w, const float* bias, float* out, long long M, int C, int n_out, hipStream_t st);
 // diffusion.hip
-int p_sample_update(float* x, const float* eps_hat, const float* noise, long long noise_step_stride, int t_first,
-                    const int64_t* t, const float* c_recip, const float* c_recipm1, const float* c1, const float* c2,
-                    const float* sigma, int B, long long per, uint64_t seed, uint32_t stream_id, hipStream_t st,
-                    const int64_t* chain_state = nullptr, int64_t* dec_counter = nullptr);
-// DPM-Solver++(2M): x_prev = (c1 x0 + c2 x) + c3 x0_hist, x0_hist <- x0 (the sampler's last kernel of a step when unfused)
-int p_sample_update_ms(float* x, const float* eps_hat, float* x0_hist, const int64_t* t, const float* c_recip, const float* c_recipm1,
-                       const float* c1, const float* c2, const float* c3, int B, long long per, hipStream_t st,
-                       int64_t* dec_counter = nullptr);
 // RePaint inpainting: the known latent, its mask and the per-row tables of one reverse op
 struct InpaintOps {
     const float* known;           // x0 of the known image, same layout as x
@@ -312,14 +304,7 @@ struct InpaintOps {
 };
 constexpr uint32_t INPAINT_Z2_BIT = 0x40000000u;   // Philox stream of the known region's draw: stream_id | this
 constexpr uint32_t INPAINT_Z3_BIT = 0x20000000u;   // ... and of the jump's: stream_id | this (so stream_id < 2^29)
-// p_sample_update's op, then x = mask ? x_kn : x, then the optional jump (the sampler's last kernel of a step when unfused)
-int p_sample_update_inpaint(float* x, const float* eps_hat, const InpaintOps& ip, const int64_t* t, const float* c_recip,
-                            const float* c_recipm1, const float* c1, const float* c2, const float* sigma, int B, long long per,
-                            uint64_t seed, uint32_t stream_id, hipStream_t st, const int64_t* chain_state = nullptr,
-                            int64_t* dec_counter = nullptr);
-int randn(float* out, long long n, uint64_t seed, uint32_t step, uint32_t stream_id, hipStream_t st);
-// GroupNorm (from conv partials) + Mish + 1x1 projection to n_out <= 8 channels (+ the reverse-step update of x) in one launch
-// likelihood sweep (diffusion.hip, ddk_vlb_sweep_run): one step's operands besides the UNet's
+// likelihood sweep (ddk_vlb_sweep_run): one step's operands besides the UNet's
 struct VlbStep {
     const float* x;               // clean sample, NHWC [B][H][W][n_out]
     float* xt;                    // q_sample(x, t, eps), the forward's input
@@ -331,25 +316,67 @@ struct VlbStep {
     int nslot;                    // tiles of the fused tail, or vlb_sweep_slots_unfused()
 };
 constexpr uint32_t VLB_STREAM_BIT = 0x80000000u;   // Philox stream ids of the sweep: stream_id | this (never the sampler's)
+
+// How a forward ends.  The kind is the one thing a chain entry hands forward_core, and forward_core hands the fused tail
+// (final_tail) or the unfused update (p_update); each kind reads the members listed with it and no others.
+enum class StepKind {
+    Eps,          // plain forward: eps_hat to eps_out, no update
+    Ancestral,    // x <- p_step(x, eps_hat, z): tables c_recip .. sigma; z = injected noise or Philox; eps_out optional
+    Multistep,    // DPM-Solver++(2M): x <- (c1 x0 + c2 x) + c3 x0_hist, x0_hist <- x0: c_recip .. c2, c3, x0_hist; no draw
+    Inpaint,      // RePaint: Ancestral's op, then x = mask ? x_kn : x, then the optional jump: c_recip .. sigma, inp; Philox only
+    Vlb           // likelihood sweep: no update, the step's VLB terms to vlb->partials (vlb_rule() fills the rest from *vlb)
+};
+struct StepRule {
+    StepKind kind;
+    float* eps_out;               // [B][HW][n_out] or null (fused tail only; the unfused tail's eps_hat is its input)
+    float* x;                     // [B][HW][n_out] chain state, updated in place (Vlb: the clean sample, read only)
+    const float* noise;           // injected draws: draw k = t_first - t of a [n_steps][...] array (stride 0: a single tensor), or null
+    long long noise_step_stride;
+    int t_first;
+    const float *c_recip, *c_recipm1, *c1, *c2, *sigma;     // per row t[b]
+    float* x0_hist;               // Multistep: the previous step's clipped x0, same layout as x, read and rewritten
+    const float* c3;
+    InpaintOps inp;
+    const VlbStep* vlb;           // host side only
+};
+inline StepRule vlb_rule(const VlbStep& v) {
+    StepRule r{};
+    r.kind = StepKind::Vlb;
+    r.x = const_cast<float*>(v.x); r.noise = v.noise; r.noise_step_stride = v.noise_step_stride; r.t_first = v.t_first;
+    r.c_recip = v.c_recip; r.c_recipm1 = v.c_recipm1; r.c1 = v.c1; r.c2 = v.c2;
+    r.vlb = &v;
+    return r;
+}
+// What a step's last kernel does for its chain besides the rule (all optional: a lone call has a host seed / stream id)
+struct ChainHooks {
+    const int64_t* chain_state;   // {counter, Philox seed, stream id} in device memory: one captured graph serves every seed
+    int64_t* dec_counter;         // the step counter, decremented by this (last) kernel of the step when the first kernel left it alone
+    uint64_t seed;                // without chain_state
+    uint32_t stream_id;
+};
+// the unfused tail's last kernel, given eps_hat in memory: the rule's update of x (Ancestral, Multistep, Inpaint) or the sweep's
+// reduction of the step's terms (Vlb); `who` names the caller in messages
+int p_update(const StepRule& r, const float* eps_hat, const int64_t* t, int B, long long per, const ChainHooks& h, hipStream_t st,
+             const char* who = "p_update");
+int randn(float* out, long long n, uint64_t seed, uint32_t step, uint32_t stream_id, hipStream_t st);
 int vlb_sweep_slots_unfused(int B, long long per);
 int vlb_step_input(const VlbStep& v, const float* sqrt_acp, const float* sqrt_1m_acp, const int64_t* chain_state, int B, long long per,
                    hipStream_t st);
-int vlb_sweep_terms(const VlbStep& v, const int64_t* t, const float* eps_hat, int B, long long per, const int64_t* chain_state,
-                    hipStream_t st, int64_t* dec_counter);
 int vlb_sweep_finalize(const float* partials, int nslot, float* vlb_t, float* l_simple_t, int T, int B, long long per, hipStream_t st);
-int final_tail_vlb(const float* raw, const float* part, int np, const float* gamma, const float* beta, float eps, const float* w,
-                   const float* bias, int n_out, const VlbStep& v, const int64_t* t, const int64_t* chain_state, int B, int HW, int C,
-                   int groups, hipStream_t st, int64_t* dec_counter);
-bool final_tail_ok(int HW, int C, int groups, int n_out, int np);
-bool final_tail_vlb_ok(int HW, int C, int groups, int n_out, int np);
-bool final_tail_ms_ok(int HW, int C, int groups, int n_out, int np);
-bool final_tail_inp_ok(int HW, int C, int groups, int n_out, int np);
-int final_tail(const float* raw, const float* part, int np, const float* gamma, const float* beta, float eps, const float* w,
-               const float* bias, int n_out, float* eps_out, float* x, const float* noise, long long noise_step_stride, int t_first,
-               const int64_t* t, const float* c_recip, const float* c_recipm1, const float* c1, const float* c2, const float* sigma,
-               const int64_t* chain_state, uint64_t seed, uint32_t stream_id, int B, int HW, int C, int groups, hipStream_t st,
-               int64_t* dec_counter = nullptr,      // dec_counter: the sampler's step counter, decremented by this (last) kernel of the step
-               float* x0_hist = nullptr, const float* c3 = nullptr,    // both given: the multistep update (final_tail_ms_ok shapes, no noise)
-               const InpaintOps* inp = nullptr);                        // given: RePaint's op (final_tail_inp_ok shapes, Philox only)
+// GroupNorm (from conv partials) + Mish + 1x1 projection to n_out <= 8 channels, then the rule, in one launch (final_tail_kernel)
+struct TailIn {
+    const float* raw;             // [B][HW][C] output of the final Block's conv
+    const float* part;            // [B*np][G] {mean, M2} per (128-pixel tile, group)
+    int np;
+    const float *gamma, *beta;
+    float eps;
+    const float* w;               // [n_out][C]
+    const float* bias;            // [n_out] or null
+    int n_out, B, HW, C, groups;
+};
+// the shapes the fused tail takes: C in {32,64,128,256}; the Multistep, Inpaint and Vlb instantiations stop at C = 128 (at 256 the
+// plain one spills already, and theirs hold more in the prologue)
+bool final_tail_ok(int HW, int C, int groups, int n_out, int np, StepKind kind);
+int final_tail(const TailIn& in, const StepRule& r, const int64_t* t, const ChainHooks& h, hipStream_t st);
 
 }  // namespace ddk

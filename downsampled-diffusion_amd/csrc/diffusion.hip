@@ -108,55 +108,6 @@ __device__ __forceinline__ float4 ms_step4(float4 xv, float4 ev, float4& h, floa
     return o;
 }
 
-__global__ __launch_bounds__(256) void p_sample_kernel(float* __restrict__ x, const float* __restrict__ eps_hat,
-                                                       const float* __restrict__ noise, long long noise_step_stride, int t_first,
-                                                       const int64_t* __restrict__ t,
-                                                       const float* __restrict__ c_recip, const float* __restrict__ c_recipm1,
-                                                       const float* __restrict__ c1, const float* __restrict__ c2,
-                                                       const float* __restrict__ sigma, long long per4, long long total4,
-                                                       uint64_t seed, uint32_t stream, const int64_t* __restrict__ chain_state,
-                                                       int64_t* dec_counter) {
-    if (dec_counter && blockIdx.x == 0 && threadIdx.x == 0) *dec_counter -= 1;     // the step counter, by the step's last kernel (see final_tail)
-    if (chain_state) {   // sampler: the Philox key lives in device memory, so one captured graph serves every seed
-        seed = (uint64_t)chain_state[1];
-        stream = (uint32_t)chain_state[2];
-    }
-    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total4; i += (long long)gridDim.x * 256) {
-        const int64_t tb = t[i / per4];
-        const float cr = c_recip[tb], crm1 = c_recipm1[tb], a1 = c1[tb], a2 = c2[tb];
-        const float sg = tb > 0 ? sigma[tb] : 0.0f;  // nonzero_mask * exp(0.5 logvar), ddpm.py:220-227
-        const float4 xv = reinterpret_cast<const float4*>(x)[i], ev = reinterpret_cast<const float4*>(eps_hat)[i];
-        // injected noise: draw k = t_first - t of a [n_steps][...] array (stride 0: a single tensor)
-        const float4 zv = noise ? reinterpret_cast<const float4*>(noise + (long long)(t_first - tb) * noise_step_stride)[i]
-                                : philox_normal4((unsigned long long)i, (uint32_t)tb, stream, seed);
-        float4 o;
-        o.x = p_step(xv.x, ev.x, zv.x, cr, crm1, a1, a2, sg);
-        o.y = p_step(xv.y, ev.y, zv.y, cr, crm1, a1, a2, sg);
-        o.z = p_step(xv.z, ev.z, zv.z, cr, crm1, a1, a2, sg);
-        o.w = p_step(xv.w, ev.w, zv.w, cr, crm1, a1, a2, sg);
-        reinterpret_cast<float4*>(x)[i] = o;
-    }
-}
-
-// The multistep update of the unfused tail: no draw, the history x0_hist (same layout as x) read and rewritten element by element.
-// It is the step's last kernel in the sampler, so it takes over p_sample_kernel's counter decrement.
-__global__ __launch_bounds__(256) void p_sample_ms_kernel(float* __restrict__ x, const float* __restrict__ eps_hat,
-                                                          float* __restrict__ x0_hist, const int64_t* __restrict__ t,
-                                                          const float* __restrict__ c_recip, const float* __restrict__ c_recipm1,
-                                                          const float* __restrict__ c1, const float* __restrict__ c2,
-                                                          const float* __restrict__ c3, long long per4, long long total4,
-                                                          int64_t* dec_counter) {
-    if (dec_counter && blockIdx.x == 0 && threadIdx.x == 0) *dec_counter -= 1;     // the step counter, by the step's last kernel (see final_tail)
-    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total4; i += (long long)gridDim.x * 256) {
-        const int64_t tb = t[i / per4];
-        const float cr = c_recip[tb], crm1 = c_recipm1[tb], a1 = c1[tb], a2 = c2[tb], a3 = c3[tb];
-        const float4 xv = reinterpret_cast<const float4*>(x)[i], ev = reinterpret_cast<const float4*>(eps_hat)[i];
-        float4 h = reinterpret_cast<const float4*>(x0_hist)[i];
-        reinterpret_cast<float4*>(x)[i] = ms_step4(xv, ev, h, cr, crm1, a1, a2, a3);
-        reinterpret_cast<float4*>(x0_hist)[i] = h;
-    }
-}
-
 // RePaint (models/diffusion/respace.py repaint_tables).  One reverse op at spaced timestep tau:
 //   x_unk = p_step(x, eps_hat, z1);  x_kn = ka x0_known + kb z2 (ka = 1, kb = 0 at tau = 0: exactly x0_known);
 //   x = mask ? x_kn : x_unk (a select, not a blend: the known region stays exact and NaN-free);  jump: x = ja x + jb z3.
@@ -186,38 +137,62 @@ __device__ __forceinline__ float4 inp_step4(float4 xv, float4 ev, float4 z1, flo
     return o;
 }
 
-// The inpainting op of the unfused tail: three Philox draws per float4, keyed (index, row t, stream / | 2^30 / | 2^29, seed); the
-// jump's draw only where the row has one.  It is the step's last kernel in the sampler, so it takes over the counter decrement.
-__global__ __launch_bounds__(256) void p_sample_inpaint_kernel(float* __restrict__ x, const float* __restrict__ eps_hat,
-                                                               const InpaintOps ip, const int64_t* __restrict__ t,
-                                                               const float* __restrict__ c_recip, const float* __restrict__ c_recipm1,
-                                                               const float* __restrict__ c1, const float* __restrict__ c2,
-                                                               const float* __restrict__ sigma, long long per4, long long total4,
-                                                               uint64_t seed, uint32_t stream, const int64_t* __restrict__ chain_state,
-                                                               int64_t* dec_counter) {
-    if (dec_counter && blockIdx.x == 0 && threadIdx.x == 0) *dec_counter -= 1;     // the step counter, by the step's last kernel (see final_tail)
+// The last kernel of an unfused step: the rule's update of x given eps_hat in memory, one template for the three sampler kinds.
+// Shared: the grid-stride loop over float4s, row t[i / per4] of the tables, the counter decrement (in the sampler this is the step's
+// last kernel; see final_tail_kernel) and the Philox key, which a chain keeps in device memory so that one captured graph serves
+// every seed.  Per kind: the operands fetched and the device function called.
+//   Ancestral: the draw is injected (draw k = t_first - t of a [n_steps][...] array; stride 0: a single tensor) or Philox's
+//   Multistep: no draw; the history x0_hist (same layout as x) is read and rewritten element by element
+//   Inpaint:   three Philox draws per float4, keyed (index, row t, stream / | 2^30 / | 2^29, seed); the jump's only where the row has one
+// (vlb_sweep_terms_kernel, the sweep's unfused epilogue, reduces per slice instead of updating x and stays a kernel of its own)
+// (the chain hooks arrive as scalars: as a by-value ChainHooks the Ancestral instantiation takes two VGPRs more)
+template <StepKind K>
+__global__ __launch_bounds__(256) void p_update_kernel(const StepRule r, const float* __restrict__ eps_hat, const int64_t* __restrict__ t,
+                                                       long long per4, long long total4, uint64_t seed, uint32_t stream,
+                                                       const int64_t* __restrict__ chain_state, int64_t* dec_counter) {
+    if (dec_counter && blockIdx.x == 0 && threadIdx.x == 0) *dec_counter -= 1;
     if (chain_state) {
         seed = (uint64_t)chain_state[1];
         stream = (uint32_t)chain_state[2];
     }
+    float4* __restrict__ x = reinterpret_cast<float4*>(r.x);
     for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total4; i += (long long)gridDim.x * 256) {
         const int64_t tb = t[i / per4];
-        const float cr = c_recip[tb], crm1 = c_recipm1[tb], a1 = c1[tb], a2 = c2[tb];
-        const float sg = tb > 0 ? sigma[tb] : 0.0f;
-        const float ka = ip.ka[tb], kb = ip.kb[tb], ja = ip.ja[tb], jb = ip.jb[tb];
-        const bool jump = jb != 0.0f;
-        const float4 xv = reinterpret_cast<const float4*>(x)[i], ev = reinterpret_cast<const float4*>(eps_hat)[i];
-        const float4 kv = reinterpret_cast<const float4*>(ip.known)[i], mv = reinterpret_cast<const float4*>(ip.mask)[i];
-        const float4 z1 = philox_normal4((unsigned long long)i, (uint32_t)tb, stream, seed);
-        const float4 xk = inp_known4(kv, philox_normal4((unsigned long long)i, (uint32_t)tb, stream | INPAINT_Z2_BIT, seed), ka, kb);
-        const float4 z3 = jump ? philox_normal4((unsigned long long)i, (uint32_t)tb, stream | INPAINT_Z3_BIT, seed)
-                               : make_float4(0.f, 0.f, 0.f, 0.f);
-        reinterpret_cast<float4*>(x)[i] = inp_step4(xv, ev, z1, xk, mv, z3, cr, crm1, a1, a2, sg, ja, jb, jump);
+        const float cr = r.c_recip[tb], crm1 = r.c_recipm1[tb], a1 = r.c1[tb], a2 = r.c2[tb];
+        // the fifth coefficient: c3 of the multistep rule, else sigma = nonzero_mask * exp(0.5 logvar), ddpm.py:220-227
+        const float a5 = K == StepKind::Multistep ? r.c3[tb] : (tb > 0 ? r.sigma[tb] : 0.0f);
+        const float4 xv = x[i], ev = reinterpret_cast<const float4*>(eps_hat)[i];
+        if constexpr (K == StepKind::Multistep) {
+            float4 hv = reinterpret_cast<const float4*>(r.x0_hist)[i];
+            x[i] = ms_step4(xv, ev, hv, cr, crm1, a1, a2, a5);
+            reinterpret_cast<float4*>(r.x0_hist)[i] = hv;
+        } else {
+            const float sg = a5;
+            if constexpr (K == StepKind::Inpaint) {
+                const float ka = r.inp.ka[tb], kb = r.inp.kb[tb], ja = r.inp.ja[tb], jb = r.inp.jb[tb];
+                const bool jump = jb != 0.0f;
+                const float4 kv = reinterpret_cast<const float4*>(r.inp.known)[i], mv = reinterpret_cast<const float4*>(r.inp.mask)[i];
+                const float4 z1 = philox_normal4((unsigned long long)i, (uint32_t)tb, stream, seed);
+                const float4 xk = inp_known4(kv, philox_normal4((unsigned long long)i, (uint32_t)tb, stream | INPAINT_Z2_BIT, seed), ka, kb);
+                const float4 z3 = jump ? philox_normal4((unsigned long long)i, (uint32_t)tb, stream | INPAINT_Z3_BIT, seed)
+                                       : make_float4(0.f, 0.f, 0.f, 0.f);
+                x[i] = inp_step4(xv, ev, z1, xk, mv, z3, cr, crm1, a1, a2, sg, ja, jb, jump);
+            } else {
+                const float4 zv = r.noise ? reinterpret_cast<const float4*>(r.noise + (long long)(r.t_first - tb) * r.noise_step_stride)[i]
+                                          : philox_normal4((unsigned long long)i, (uint32_t)tb, stream, seed);
+                float4 o;
+                o.x = p_step(xv.x, ev.x, zv.x, cr, crm1, a1, a2, sg);
+                o.y = p_step(xv.y, ev.y, zv.y, cr, crm1, a1, a2, sg);
+                o.z = p_step(xv.z, ev.z, zv.z, cr, crm1, a1, a2, sg);
+                o.w = p_step(xv.w, ev.w, zv.w, cr, crm1, a1, a2, sg);
+                x[i] = o;
+            }
+        }
     }
 }
 
 // ---- the VLB term of one element (reference models/diffusion/ddpm.py:317-366, models/utils/losses.py:17-109) --------------------
-// Shared by vlb_terms_kernel and the likelihood sweep's epilogues (final_tail_kernel<.., true>, vlb_sweep_terms_kernel).
+// Shared by vlb_terms_kernel and the likelihood sweep's epilogues (final_tail_kernel<.., StepKind::Vlb>, vlb_sweep_terms_kernel).
 __device__ __forceinline__ float std_normal_cdf_approx(float v) {
     return 0.5f * (1.0f + tanhf(0.7978845608028654f * (v + 0.044715f * (v * v * v))));      // sqrt(2/pi)
 }
@@ -260,10 +235,10 @@ __device__ __forceinline__ float vlb_elem(float xv, float xt, float eh, const Vl
 // The end of a forward in ONE launch (reference models/unet/unet.py:69-72 after the final Block's conv, blocks.py:79-80;
 // in the sampler also models/diffusion/ddpm.py:149-158,177-185,216-227): GroupNorm (statistics from the final conv's per-tile
 // partials) -> Mish -> 1x1 projection to n_out <= 8 channels -> eps_hat, and -- when x is given -- the reverse-step update of x
-// in place.  Replaces gn_apply_parts_kernel + conv1x1_n8_kernel + p_sample_kernel: the normalised activation (16.8 MB at
+// in place.  Replaces gn_apply_parts_kernel + conv1x1_n8_kernel + p_update_kernel: the normalised activation (16.8 MB at
 // cfg4) and eps_hat never go to memory.
 //   workgroup (16 waves) = one 128-pixel tile of one image; phase 1: LPP lanes share a pixel (conv1x1_n8_kernel's butterfly), eps_hat of
-//   the tile goes to LDS; phase 2: the tile's 128 * n_out latent elements are updated with p_sample_kernel's exact arithmetic
+//   the tile goes to LDS; phase 2: the tile's 128 * n_out latent elements are updated with p_update_kernel's exact arithmetic
 //   and Philox indexing (bit-identical given the same eps_hat).
 struct TailParams {
     const float* raw;          // [B][HW][C] output of the final Block's conv
@@ -285,27 +260,31 @@ struct TailParams {
     int np, HW, C, cpg, n_out;
     float eps;
     int64_t* dec_counter;         // the step counter, decremented HERE (the step's last kernel) when the first kernel left it alone, or null
-    // likelihood sweep (final_tail_kernel<.., true>): x is the clean sample (read only), c_recip .. c2 as above
+    // StepKind::Vlb: x is the clean sample (read only), c_recip .. c2 as above
     const float* xt;              // q_sample(x, t, eps): what the forward ran on
     const float* logvar;          // posterior_log_variance_clipped [T]
     float2* vlb_part;             // [T][B][np] {sum of the VLB terms, sum of (eps - eps_hat)^2} per 128-pixel tile
     int B;
-    // multistep (final_tail_kernel<.., .., false, true>): the previous step's clipped x0, same layout as x, read and rewritten
+    // StepKind::Multistep: the previous step's clipped x0, same layout as x, read and rewritten
     float* x0_hist;
     const float* c3;
-    // inpainting (final_tail_kernel<.., .., false, false, true>): the known latent, its mask and the per-row tables
+    // StepKind::Inpaint: the known latent, its mask and the per-row tables
     InpaintOps inp;
 };
 
-// VLB = false: eps_hat out and / or the reverse-step update of x.  VLB = true (ddk_vlb_sweep_run): phase 2 evaluates, per element,
-// vlb_terms_kernel's term and (eps - eps_hat)^2 with eps the step-input kernel's draw (the same Philox call or injected array), and
-// the workgroup stores the two block sums to its own slot of vlb_part (plain stores, no atomics: the kernel boundary publishes them).
-// MS = true (ddk_sampler_run_multistep, x given): the DPM-Solver++(2M) update of p_sample_ms_kernel; the history float4 is
-// requested where the other modes draw their noise (no Philox rounds), and the thread that read it writes it back.
-// INP = true (ddk_sampler_run_inpaint, x given, Philox only): RePaint's op of p_sample_inpaint_kernel; the known float4, the mask
-// float4 and the two extra draws are requested in the same prologue, and x_kn is formed there (4 registers live, not 8).
-template <int LPP, int VPL, bool VLB, bool MS = false, bool INP = false>
+// K says how the launch ends (StepRule).  Eps and Ancestral are ONE instantiation, <.., StepKind::Ancestral>: eps_hat out and / or
+// the reverse-step update of x, whichever of p.eps_out / p.x is given.  The other kinds exist for C <= 128 only (final_tail_ok).
+// Vlb (ddk_vlb_sweep_run): phase 2 evaluates, per element, vlb_terms_kernel's term and (eps - eps_hat)^2 with eps the step-input
+// kernel's draw (the same Philox call or injected array), and the workgroup stores the two block sums to its own slot of vlb_part
+// (plain stores, no atomics: the kernel boundary publishes them).
+// Multistep (ddk_sampler_run_multistep, x given): the DPM-Solver++(2M) update of p_update_kernel; the history float4 is requested
+// where the other kinds draw their noise (no Philox rounds), and the thread that read it writes it back.
+// Inpaint (ddk_sampler_run_inpaint, x given, Philox only): RePaint's op of p_update_kernel; the known float4, the mask float4 and
+// the two extra draws are requested in the same prologue, and x_kn is formed there (4 registers live, not 8).
+template <int LPP, int VPL, StepKind K>
 __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
+    static_assert(K != StepKind::Eps, "the plain forward runs the Ancestral instantiation with p.x null");
+    constexpr bool VLB = K == StepKind::Vlb, MS = K == StepKind::Multistep, INP = K == StepKind::Inpaint;
     constexpr int PPW = 64 / LPP;                    // pixels per wave and iteration
     constexpr int PPI = 16 * PPW;                    // ... per iteration of the 16-wave workgroup
     constexpr int NIT = 128 / PPI;                   // 4 at C = 128 / 256, 2 at C = 64, 1 at C = 32
@@ -468,78 +447,67 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
     }
 }
 
-template <bool VLB, bool MS = false, bool INP = false>
+template <StepKind K>
 static int launch_tail(const TailParams& p, int B, hipStream_t st) {
     const dim3 grid((unsigned)(B * p.np));
-    if (p.C == 32) hipLaunchKernelGGL((final_tail_kernel<8, 1, VLB, MS, INP>), grid, dim3(1024), 0, st, p);
-    else if (p.C == 64) hipLaunchKernelGGL((final_tail_kernel<16, 1, VLB, MS, INP>), grid, dim3(1024), 0, st, p);
-    else if (p.C == 128) hipLaunchKernelGGL((final_tail_kernel<32, 1, VLB, MS, INP>), grid, dim3(1024), 0, st, p);
-    else if constexpr (!VLB && !MS && !INP) hipLaunchKernelGGL((final_tail_kernel<32, 2, VLB>), grid, dim3(1024), 0, st, p);
-    else DDK_REQUIRE(false, "final_tail: C = 256 takes the unfused epilogue in the VLB, multistep and inpainting modes "
-                            "(final_tail_vlb_ok / final_tail_ms_ok / final_tail_inp_ok)");
+    if (p.C == 32) hipLaunchKernelGGL((final_tail_kernel<8, 1, K>), grid, dim3(1024), 0, st, p);
+    else if (p.C == 64) hipLaunchKernelGGL((final_tail_kernel<16, 1, K>), grid, dim3(1024), 0, st, p);
+    else if (p.C == 128) hipLaunchKernelGGL((final_tail_kernel<32, 1, K>), grid, dim3(1024), 0, st, p);
+    else if constexpr (K == StepKind::Ancestral) hipLaunchKernelGGL((final_tail_kernel<32, 2, K>), grid, dim3(1024), 0, st, p);
+    else DDK_REQUIRE(false, "final_tail: C = 256 takes the unfused epilogue in the VLB, multistep and inpainting kinds (final_tail_ok)");
     return check_launch("final_tail_kernel");
 }
 
-// the sweep's fused epilogue: final_tail's shapes up to 128 channels (the 256-channel VLB instantiation would spill registers)
-bool final_tail_vlb_ok(int HW, int C, int groups, int n_out, int np) { return C <= 128 && final_tail_ok(HW, C, groups, n_out, np); }
-// the multistep update: the same subset (the 256-channel instantiation spills already without it)
-bool final_tail_ms_ok(int HW, int C, int groups, int n_out, int np) { return C <= 128 && final_tail_ok(HW, C, groups, n_out, np); }
-// the inpainting op: the same subset (its prologue holds three float4 more than the plain update's)
-bool final_tail_inp_ok(int HW, int C, int groups, int n_out, int np) { return C <= 128 && final_tail_ok(HW, C, groups, n_out, np); }
-
-bool final_tail_ok(int HW, int C, int groups, int n_out, int np) {
+bool final_tail_ok(int HW, int C, int groups, int n_out, int np, StepKind kind) {
     if (!(C == 32 || C == 64 || C == 128 || C == 256)) return false;
+    // the 256-channel instantiation spills registers already in the plain kinds; the others hold more in the prologue
+    if (C > 128 && kind != StepKind::Eps && kind != StepKind::Ancestral) return false;
     if (groups <= 0 || groups > 64 || C % groups || (C / groups) % 4) return false;
     if (n_out < 1 || n_out > 8 || (128 * n_out) % 4) return false;
     return np > 0 && HW == np * 128 && np * groups <= 1024;
 }
 
-int final_tail(const float* raw, const float* part, int np, const float* gamma, const float* beta, float eps, const float* w,
-               const float* bias, int n_out, float* eps_out, float* x, const float* noise, long long noise_step_stride, int t_first,
-               const int64_t* t, const float* c_recip, const float* c_recipm1, const float* c1, const float* c2, const float* sigma,
-               const int64_t* chain_state, uint64_t seed, uint32_t stream_id, int B, int HW, int C, int groups, hipStream_t st,
-               int64_t* dec_counter, float* x0_hist, const float* c3, const InpaintOps* inp) {
-    DDK_REQUIRE(raw && part && gamma && beta && w && (eps_out || x) && B > 0, "final_tail: null pointer");
-    DDK_REQUIRE(final_tail_ok(HW, C, groups, n_out, np), "final_tail: needs C in {32,64,128,256}, n_out <= 8, H*W == tiles * 128");
-    DDK_REQUIRE(!x0_hist || (x && c3 && !noise && aligned16(x0_hist) && final_tail_ms_ok(HW, C, groups, n_out, np)),
-                "final_tail: the multistep update needs x, c3, no injected noise, an aligned history and C <= 128");
-    DDK_REQUIRE(!inp || (x && !x0_hist && !noise && inp->known && inp->mask && inp->ka && inp->kb && inp->ja && inp->jb &&
-                         aligned16(inp->known) && aligned16(inp->mask) && final_tail_inp_ok(HW, C, groups, n_out, np)),
-                "final_tail: the inpainting op needs x, its operands, no injected noise or history, aligned known / mask and C <= 128");
-    DDK_REQUIRE(aligned16(raw) && aligned16(gamma) && aligned16(beta) && aligned16(w) && aligned16(eps_out) && aligned16(x) &&
-                    aligned16(noise) && noise_step_stride % 4 == 0, "final_tail: alignment");
-    DDK_REQUIRE(!x || (t && c_recip && c_recipm1 && c1 && c2 && (sigma || x0_hist)), "final_tail: the update needs t and the schedule tables");
+int final_tail(const TailIn& in, const StepRule& r, const int64_t* t, const ChainHooks& h, hipStream_t st) {
+    DDK_REQUIRE(in.raw && in.part && in.gamma && in.beta && in.w && in.B > 0, "final_tail: null pointer");
+    DDK_REQUIRE(final_tail_ok(in.HW, in.C, in.groups, in.n_out, in.np, r.kind),
+                "final_tail: needs C in {32,64,128,256} (the VLB, multistep and inpainting kinds: C <= 128), n_out <= 8, H*W == tiles * 128");
+    DDK_REQUIRE(aligned16(in.raw) && aligned16(in.gamma) && aligned16(in.beta) && aligned16(in.w) && aligned16(r.eps_out) && aligned16(r.x) &&
+                    aligned16(r.noise) && r.noise_step_stride % 4 == 0, "final_tail: alignment");
+    const bool tables = r.x && t && r.c_recip && r.c_recipm1 && r.c1 && r.c2;     // what every kind but Eps reads
     TailParams p{};
-    p.raw = raw; p.part = reinterpret_cast<const float2*>(part); p.gamma = gamma; p.beta = beta; p.w = w; p.bias = bias;
-    p.eps_out = eps_out; p.x = x; p.noise = noise; p.noise_step_stride = noise_step_stride; p.t_first = t_first; p.t = t;
-    p.c_recip = c_recip; p.c_recipm1 = c_recipm1; p.c1 = c1; p.c2 = c2; p.sigma = sigma; p.chain_state = chain_state;
-    p.seed = seed; p.stream = stream_id;
-    p.np = np; p.HW = HW; p.C = C; p.cpg = C / groups; p.n_out = n_out; p.eps = eps;
-    p.dec_counter = dec_counter;
-    p.x0_hist = x0_hist; p.c3 = c3;
-    if (inp) {
-        p.inp = *inp;
-        return launch_tail<false, false, true>(p, B, st);
+    p.raw = in.raw; p.part = reinterpret_cast<const float2*>(in.part); p.gamma = in.gamma; p.beta = in.beta; p.w = in.w; p.bias = in.bias;
+    p.eps_out = r.eps_out; p.x = r.x; p.noise = r.noise; p.noise_step_stride = r.noise_step_stride; p.t_first = r.t_first; p.t = t;
+    p.c_recip = r.c_recip; p.c_recipm1 = r.c_recipm1; p.c1 = r.c1; p.c2 = r.c2; p.sigma = r.sigma;
+    p.chain_state = h.chain_state; p.seed = h.seed; p.stream = h.stream_id; p.dec_counter = h.dec_counter;
+    p.np = in.np; p.HW = in.HW; p.C = in.C; p.cpg = in.C / in.groups; p.n_out = in.n_out; p.eps = in.eps;
+    switch (r.kind) {
+        case StepKind::Eps:
+            DDK_REQUIRE(r.eps_out && !r.x, "final_tail: the plain forward needs eps_out and takes no x");
+            return launch_tail<StepKind::Ancestral>(p, in.B, st);
+        case StepKind::Ancestral:
+            DDK_REQUIRE(tables && r.sigma, "final_tail: the update needs x, t and the schedule tables");
+            return launch_tail<StepKind::Ancestral>(p, in.B, st);
+        case StepKind::Multistep:
+            DDK_REQUIRE(tables && r.c3 && r.x0_hist && !r.noise && aligned16(r.x0_hist),
+                        "final_tail: the multistep update needs x, t, the tables with c3, no injected noise and an aligned history");
+            p.x0_hist = r.x0_hist; p.c3 = r.c3;
+            return launch_tail<StepKind::Multistep>(p, in.B, st);
+        case StepKind::Inpaint:
+            DDK_REQUIRE(tables && r.sigma && !r.noise && r.inp.known && r.inp.mask && r.inp.ka && r.inp.kb && r.inp.ja && r.inp.jb &&
+                            aligned16(r.inp.known) && aligned16(r.inp.mask),
+                        "final_tail: the inpainting op needs x, t, the tables, its operands, no injected noise and aligned known / mask");
+            p.inp = r.inp;
+            return launch_tail<StepKind::Inpaint>(p, in.B, st);
+        case StepKind::Vlb: {
+            DDK_REQUIRE(r.vlb && tables && !r.eps_out && h.chain_state, "final_tail: the VLB epilogue needs the sweep's step, x, t, the tables and the chain state");
+            const VlbStep& v = *r.vlb;
+            DDK_REQUIRE(v.xt && v.logvar && v.partials && v.nslot == in.np && aligned16(v.xt) && aligned16(v.partials),
+                        "final_tail: the VLB epilogue needs aligned x_t and partials, logvar and one slot per tile");
+            p.xt = v.xt; p.logvar = v.logvar; p.vlb_part = reinterpret_cast<float2*>(v.partials); p.B = in.B;
+            return launch_tail<StepKind::Vlb>(p, in.B, st);
+        }
     }
-    return x0_hist ? launch_tail<false, true>(p, B, st) : launch_tail<false>(p, B, st);
-}
-
-int final_tail_vlb(const float* raw, const float* part, int np, const float* gamma, const float* beta, float eps, const float* w,
-                   const float* bias, int n_out, const VlbStep& v, const int64_t* t, const int64_t* chain_state, int B, int HW, int C,
-                   int groups, hipStream_t st, int64_t* dec_counter) {
-    DDK_REQUIRE(raw && part && gamma && beta && w && v.x && v.xt && v.partials && t && chain_state && B > 0, "final_tail_vlb: null pointer");
-    DDK_REQUIRE(final_tail_vlb_ok(HW, C, groups, n_out, np) && v.nslot == np, "final_tail_vlb: shape");
-    DDK_REQUIRE(v.c_recip && v.c_recipm1 && v.c1 && v.c2 && v.logvar, "final_tail_vlb: null schedule table");
-    DDK_REQUIRE(aligned16(raw) && aligned16(gamma) && aligned16(beta) && aligned16(w) && aligned16(v.x) && aligned16(v.xt) &&
-                    aligned16(v.noise) && aligned16(v.partials) && v.noise_step_stride % 4 == 0, "final_tail_vlb: alignment");
-    TailParams p{};
-    p.raw = raw; p.part = reinterpret_cast<const float2*>(part); p.gamma = gamma; p.beta = beta; p.w = w; p.bias = bias;
-    p.x = const_cast<float*>(v.x); p.xt = v.xt; p.noise = v.noise; p.noise_step_stride = v.noise_step_stride; p.t_first = v.t_first;
-    p.t = t; p.c_recip = v.c_recip; p.c_recipm1 = v.c_recipm1; p.c1 = v.c1; p.c2 = v.c2; p.logvar = v.logvar;
-    p.chain_state = chain_state; p.vlb_part = reinterpret_cast<float2*>(v.partials); p.B = B;
-    p.np = np; p.HW = HW; p.C = C; p.cpg = C / groups; p.n_out = n_out; p.eps = eps;
-    p.dec_counter = dec_counter;
-    return launch_tail<true>(p, B, st);
+    return fail_arg("final_tail: unknown step kind");
 }
 
 // one workgroup per sample: fixed summation tree -> run-to-run deterministic
@@ -623,12 +591,12 @@ static int vlb_slices(int B, long long per) {
 
 // ---- likelihood sweep (ddk_vlb_sweep_run): test_losses_ of reference models/diffusion/ddpm.py:392-446 as a chain of steps -------
 // A step: vlb_step_input_kernel (x_t = q_sample(x, t, eps)), the UNet forward on x_t, and an epilogue that leaves the step's
-// {sum of VLB terms, sum of (eps - eps_hat)^2} per (t, image, slice) in partials[t][b][slice] -- final_tail_kernel<.., true> where
+// {sum of VLB terms, sum of (eps - eps_hat)^2} per (t, image, slice) in partials[t][b][slice] -- final_tail_kernel<.., StepKind::Vlb> where
 // the fused tail takes the shape, else vlb_sweep_terms_kernel behind conv + GroupNorm + 1x1.  t, the Philox seed and stream come
 // from the chain state in device memory, like the sampler's.  vlb_sweep_finalize_kernel sums the partials once, after the last step.
 
 // x_t = sqrt_acp[t] x + sqrt_1m_acp[t] eps (q_sample_kernel's arithmetic), eps = the injected draw k = t_first - t or the Philox draw
-// of (float4 index, t, stream, seed) -- the call final_tail_kernel<.., true> / vlb_sweep_terms_kernel repeat.  Leaves the counter alone.
+// of (float4 index, t, stream, seed) -- the call final_tail_kernel<.., StepKind::Vlb> / vlb_sweep_terms_kernel repeat.  Leaves the counter alone.
 __global__ __launch_bounds__(256) void vlb_step_input_kernel(const float* __restrict__ x, float* __restrict__ xt,
                                                              const float* __restrict__ noise, long long noise_step_stride, int t_first,
                                                              const float* __restrict__ ca, const float* __restrict__ cb,
@@ -711,8 +679,8 @@ int vlb_step_input(const VlbStep& v, const float* sqrt_acp, const float* sqrt_1m
     return check_launch("vlb_step_input_kernel");
 }
 
-int vlb_sweep_terms(const VlbStep& v, const int64_t* t, const float* eps_hat, int B, long long per, const int64_t* chain_state,
-                    hipStream_t st, int64_t* dec_counter) {
+static int vlb_sweep_terms(const VlbStep& v, const int64_t* t, const float* eps_hat, int B, long long per, const int64_t* chain_state,
+                           hipStream_t st, int64_t* dec_counter) {
     DDK_REQUIRE(v.x && v.xt && v.partials && t && eps_hat && chain_state && B > 0 && per % 4 == 0, "vlb_sweep_terms: arguments");
     DDK_REQUIRE(v.nslot == vlb_slices(B, per), "vlb_sweep_terms: slot count");
     hipLaunchKernelGGL(vlb_sweep_terms_kernel, dim3(v.nslot, B), dim3(256), 0, st, v, t, eps_hat, per / 4, B, chain_state, dec_counter);
@@ -726,42 +694,40 @@ int vlb_sweep_finalize(const float* partials, int nslot, float* vlb_t, float* l_
     return check_launch("vlb_sweep_finalize_kernel");
 }
 
-int p_sample_update(float* x, const float* eps_hat, const float* noise, long long noise_step_stride, int t_first,
-                    const int64_t* t, const float* c_recip, const float* c_recipm1, const float* c1, const float* c2,
-                    const float* sigma, int B, long long per, uint64_t seed, uint32_t stream_id, hipStream_t st,
-                    const int64_t* chain_state, int64_t* dec_counter) {
-    DDK_REQUIRE(x && eps_hat && t && c_recip && c_recipm1 && c1 && c2 && sigma, "p_sample_update: null pointer");
-    DDK_REQUIRE(B > 0 && per > 0 && per % 4 == 0, "p_sample_update: per-sample element count must be a multiple of 4");
-    DDK_REQUIRE(aligned16(x) && aligned16(eps_hat) && aligned16(noise) && noise_step_stride % 4 == 0, "p_sample_update: alignment");
+int p_update(const StepRule& r, const float* eps_hat, const int64_t* t, int B, long long per, const ChainHooks& h, hipStream_t st,
+             const char* who) {
+    auto bad = [who](const char* what) {
+        set_error("bad argument: %s: %s", who, what);
+        return DDK_ERR_ARG;
+    };
+    if (!(r.x && eps_hat && t && r.c_recip && r.c_recipm1 && r.c1 && r.c2)) return bad("null pointer");
+    if (!(B > 0 && per > 0 && per % 4 == 0)) return bad("per-sample element count must be a multiple of 4");
+    if (!(aligned16(r.x) && aligned16(eps_hat) && aligned16(r.noise) && r.noise_step_stride % 4 == 0)) return bad("alignment");
     const long long total4 = B * per / 4;
-    hipLaunchKernelGGL(p_sample_kernel, dim3(grid1d(total4)), dim3(256), 0, st, x, eps_hat, noise, noise_step_stride, t_first, t,
-                       c_recip, c_recipm1, c1, c2, sigma, per / 4, total4, seed, stream_id, chain_state, dec_counter);
-    return check_launch("p_sample_kernel");
-}
-
-int p_sample_update_ms(float* x, const float* eps_hat, float* x0_hist, const int64_t* t, const float* c_recip, const float* c_recipm1,
-                       const float* c1, const float* c2, const float* c3, int B, long long per, hipStream_t st, int64_t* dec_counter) {
-    DDK_REQUIRE(x && eps_hat && x0_hist && t && c_recip && c_recipm1 && c1 && c2 && c3, "p_sample_update_multistep: null pointer");
-    DDK_REQUIRE(B > 0 && per > 0 && per % 4 == 0, "p_sample_update_multistep: per-sample element count must be a multiple of 4");
-    DDK_REQUIRE(aligned16(x) && aligned16(eps_hat) && aligned16(x0_hist), "p_sample_update_multistep: alignment");
-    const long long total4 = B * per / 4;
-    hipLaunchKernelGGL(p_sample_ms_kernel, dim3(grid1d(total4)), dim3(256), 0, st, x, eps_hat, x0_hist, t, c_recip, c_recipm1, c1, c2, c3,
-                       per / 4, total4, dec_counter);
-    return check_launch("p_sample_ms_kernel");
-}
-
-int p_sample_update_inpaint(float* x, const float* eps_hat, const InpaintOps& ip, const int64_t* t, const float* c_recip,
-                            const float* c_recipm1, const float* c1, const float* c2, const float* sigma, int B, long long per,
-                            uint64_t seed, uint32_t stream_id, hipStream_t st, const int64_t* chain_state, int64_t* dec_counter) {
-    DDK_REQUIRE(x && eps_hat && ip.known && ip.mask && ip.ka && ip.kb && ip.ja && ip.jb && t && c_recip && c_recipm1 && c1 && c2 && sigma,
-                "p_sample_update_inpaint: null pointer");
-    DDK_REQUIRE(B > 0 && per > 0 && per % 4 == 0, "p_sample_update_inpaint: per-sample element count must be a multiple of 4");
-    DDK_REQUIRE(aligned16(x) && aligned16(eps_hat) && aligned16(ip.known) && aligned16(ip.mask), "p_sample_update_inpaint: alignment");
-    DDK_REQUIRE(chain_state || stream_id < INPAINT_Z3_BIT, "p_sample_update_inpaint: stream_id must be < 2^29 (bits 29, 30 key the extra draws)");
-    const long long total4 = B * per / 4;
-    hipLaunchKernelGGL(p_sample_inpaint_kernel, dim3(grid1d(total4)), dim3(256), 0, st, x, eps_hat, ip, t, c_recip, c_recipm1, c1, c2,
-                       sigma, per / 4, total4, seed, stream_id, chain_state, dec_counter);
-    return check_launch("p_sample_inpaint_kernel");
+    const dim3 grid(grid1d(total4));
+    switch (r.kind) {
+        case StepKind::Ancestral:
+            if (!r.sigma) return bad("null pointer");
+            hipLaunchKernelGGL(p_update_kernel<StepKind::Ancestral>, grid, dim3(256), 0, st, r, eps_hat, t, per / 4, total4, h.seed, h.stream_id, h.chain_state, h.dec_counter);
+            break;
+        case StepKind::Multistep:
+            if (!(r.x0_hist && r.c3)) return bad("null pointer");
+            if (r.noise || !aligned16(r.x0_hist)) return bad("no injected noise, an aligned history");
+            hipLaunchKernelGGL(p_update_kernel<StepKind::Multistep>, grid, dim3(256), 0, st, r, eps_hat, t, per / 4, total4, h.seed, h.stream_id, h.chain_state, h.dec_counter);
+            break;
+        case StepKind::Inpaint:
+            if (!(r.sigma && r.inp.known && r.inp.mask && r.inp.ka && r.inp.kb && r.inp.ja && r.inp.jb)) return bad("null pointer");
+            if (r.noise || !(aligned16(r.inp.known) && aligned16(r.inp.mask))) return bad("no injected noise, aligned known / mask");
+            if (!(h.chain_state || h.stream_id < INPAINT_Z3_BIT)) return bad("stream_id must be < 2^29 (bits 29, 30 key the extra draws)");
+            hipLaunchKernelGGL(p_update_kernel<StepKind::Inpaint>, grid, dim3(256), 0, st, r, eps_hat, t, per / 4, total4, h.seed, h.stream_id, h.chain_state, h.dec_counter);
+            break;
+        case StepKind::Vlb:       // no update: the sweep's reduction of the step's terms, a kernel of its own
+            if (!r.vlb) return bad("null pointer");
+            return vlb_sweep_terms(*r.vlb, t, eps_hat, B, per, h.chain_state, st, h.dec_counter);
+        case StepKind::Eps:
+            return bad("a plain forward has no update of x");
+    }
+    return check_launch("p_update_kernel");
 }
 
 int randn(float* out, long long n, uint64_t seed, uint32_t step, uint32_t stream_id, hipStream_t st) {
@@ -814,29 +780,33 @@ int ddk_q_sample(const float* x, const float* eps, const int64_t* t, const float
 int ddk_p_sample_update(float* x, const float* eps_hat, const float* noise, const int64_t* t, const float* c_recip,
                         const float* c_recipm1, const float* c1, const float* c2, const float* sigma, int B, long long per,
                         uint64_t seed, uint32_t stream_id, ddk_stream_t s) {
-    return p_sample_update(x, eps_hat, noise, 0, 0, t, c_recip, c_recipm1, c1, c2, sigma, B, per, seed, stream_id, as_stream(s));
+    const StepRule r{StepKind::Ancestral, nullptr, x, noise, 0, 0, c_recip, c_recipm1, c1, c2, sigma};
+    return p_update(r, eps_hat, t, B, per, ChainHooks{nullptr, nullptr, seed, stream_id}, as_stream(s), "p_sample_update");
 }
 
 int ddk_p_sample_update_multistep(float* x, const float* eps_hat, float* x0_hist, const int64_t* t, const float* c_recip,
                                   const float* c_recipm1, const float* c1, const float* c2, const float* c3, int B, long long per,
                                   ddk_stream_t s) {
-    return p_sample_update_ms(x, eps_hat, x0_hist, t, c_recip, c_recipm1, c1, c2, c3, B, per, as_stream(s));
+    const StepRule r{StepKind::Multistep, nullptr, x, nullptr, 0, 0, c_recip, c_recipm1, c1, c2, nullptr, x0_hist, c3};
+    return p_update(r, eps_hat, t, B, per, ChainHooks{}, as_stream(s), "p_sample_update_multistep");
 }
 
 int ddk_p_sample_update_inpaint(float* x, const float* eps_hat, const float* known, const float* mask, const int64_t* t,
                                 const float* c_recip, const float* c_recipm1, const float* c1, const float* c2, const float* sigma,
                                 const float* ka, const float* kb, const float* ja, const float* jb, int B, long long per, uint64_t seed,
                                 uint32_t stream_id, ddk_stream_t s) {
-    const InpaintOps ip{known, mask, ka, kb, ja, jb};
-    return p_sample_update_inpaint(x, eps_hat, ip, t, c_recip, c_recipm1, c1, c2, sigma, B, per, seed, stream_id, as_stream(s));
+    const StepRule r{StepKind::Inpaint, nullptr, x, nullptr, 0, 0, c_recip, c_recipm1, c1, c2, sigma, nullptr, nullptr,
+                     InpaintOps{known, mask, ka, kb, ja, jb}};
+    return p_update(r, eps_hat, t, B, per, ChainHooks{nullptr, nullptr, seed, stream_id}, as_stream(s), "p_sample_update_inpaint");
 }
 
 int ddk_final_tail(const float* raw, const float* partials, int tiles_per_image, const float* gamma, const float* beta, float eps,
                    const float* w, const float* bias, int n_out, float* eps_out, float* x, const float* noise, const int64_t* t,
                    const float* c_recip, const float* c_recipm1, const float* c1, const float* c2, const float* sigma, uint64_t seed,
                    uint32_t stream_id, int B, int HW, int C, int groups, ddk_stream_t s) {
-    return final_tail(raw, partials, tiles_per_image, gamma, beta, eps, w, bias, n_out, eps_out, x, noise, 0, 0, t, c_recip, c_recipm1, c1,
-                      c2, sigma, nullptr, seed, stream_id, B, HW, C, groups, as_stream(s));
+    const StepRule r{x ? StepKind::Ancestral : StepKind::Eps, eps_out, x, noise, 0, 0, c_recip, c_recipm1, c1, c2, sigma};
+    return final_tail(TailIn{raw, partials, tiles_per_image, gamma, beta, eps, w, bias, n_out, B, HW, C, groups}, r, t,
+                      ChainHooks{nullptr, nullptr, seed, stream_id}, as_stream(s));
 }
 
 int ddk_randn(float* out, long long n, uint64_t seed, uint32_t step, uint32_t stream_id, ddk_stream_t s) {

@@ -82,9 +82,8 @@ using namespace ddk;
 // pointer its kernels were launched with, so an entry is valid for exactly this kind of chain, this set of buffers and this
 // shape; t, the Philox seed / stream id and the injected-noise step index are read from device memory by the kernels, so the
 // same graph serves every step of every chain on those buffers.
-enum ChainKind { CHAIN_SAMPLER = 0, CHAIN_VLB_SWEEP = 1, CHAIN_SAMPLER_MULTISTEP = 2, CHAIN_SAMPLER_INPAINT = 3 };
 struct ChainKey {
-    int kind;
+    StepKind kind;                           // how the chain's steps end: one kind per chain entry
     const void* bufs[12];                    // every buffer the step's kernels are launched with (unused entries null)
     const void* ws;
     const void* noise;                       // also in bufs; injected draws: no 16-step graph (see run_chain)
@@ -1143,30 +1142,18 @@ static int run_level_chain(Ctx& c, int part, const float* in, float* skip, float
 // update of x behind it (ddpm.py:203-227).  Both ride on the forward's own first / last kernel where the shape allows.
 struct StepArgs {
     int64_t* state;               // [0] step counter, [1] Philox seed, [2] stream id
-    float* x;                     // chain state, updated in place
     float* eps_hat;               // scratch for the unfused tail
-    const float* noise;
-    long long noise_step_stride;
-    int t_first;
-    const float *c_recip, *c_recipm1, *c1, *c2, *sigma;
     long long per;
-    const VlbStep* vlb = nullptr;   // likelihood sweep: the forward ran on vlb->xt and ends in the VLB epilogue (x, sigma unused)
-    float* x0_hist = nullptr;       // multistep sampler: the previous step's clipped x0 (read and rewritten), with c3; sigma, noise unused
-    const float* c3 = nullptr;
-    const InpaintOps* inp = nullptr;  // inpainting sampler: RePaint's op (known latent, mask, row tables); noise unused
+    StepRule rule;                // how the step ends (never StepKind::Eps; Vlb: the forward ran on rule.vlb->xt)
 };
 
 // tiles of the final tail when the end of the forward runs as ONE launch (final_tail_kernel), else 0.  cin = the final conv's
-// input channels (dimp[1]).  The sweep's VLB mode, the multistep update and the inpainting op take a subset of the shapes
-// (final_tail_vlb_ok, final_tail_ms_ok, final_tail_inp_ok).
-static int fused_tail_parts(const ddk_unet& u, int B, int H, int W, int cin, bool vlb, bool ms = false, bool inp = false) {
+// input channels (dimp[1]).  The Vlb, Multistep and Inpaint kinds take a subset of the shapes (final_tail_ok).
+static int fused_tail_parts(const ddk_unet& u, int B, int H, int W, int cin, StepKind kind) {
     const int chan = u.generic ? pad32(u.cfg.chan) : u.cfg.chan, n_out = u.cfg.in_ch;
     const int npf = u.final_conv.has_wu ? conv_wino_stats_parts(B, H, W, cin, chan, GROUPS) : 0;
     if (npf <= 0) return 0;
-    const int HW = H * W;
-    return (vlb ? final_tail_vlb_ok(HW, chan, GROUPS, n_out, npf)
-                : ms ? final_tail_ms_ok(HW, chan, GROUPS, n_out, npf)
-                : inp ? final_tail_inp_ok(HW, chan, GROUPS, n_out, npf) : final_tail_ok(HW, chan, GROUPS, n_out, npf)) ? npf : 0;
+    return final_tail_ok(H * W, chan, GROUPS, n_out, npf, kind) ? npf : 0;
 }
 
 // t_cur[b] = counter for every sample, then counter -= 1; also zero-pads x into xpad.  First kernel of a step on shapes the
@@ -1377,9 +1364,18 @@ static int forward_core(const ddk_unet& u, const float* P, const float* x, int64
     }
     // final_conv: Block(dim, dim) then 1x1 to in_ch (unet.py:69-72)
     const int chan = u.generic ? pad32(u.cfg.chan) : u.cfg.chan, n_out = u.cfg.in_ch;
-    const int npf = fused_tail_parts(u, B, H, W, cur_c, step && step->vlb, step && step->x0_hist, step && step->inp);
+    StepRule plain{};             // a lone forward: eps_hat to `out`, no chain
+    plain.kind = StepKind::Eps;
+    plain.eps_out = out;
+    const StepRule& rule = step ? step->rule : plain;
+    ChainHooks hooks{};           // a chain keeps its Philox key in its state; a lone forward draws nothing
+    if (step) {
+        hooks.chain_state = step->state;
+        hooks.dec_counter = dec_counter;
+    }
+    const int npf = fused_tail_parts(u, B, H, W, cur_c, rule.kind);
     if (npf > 0 && (!step || step->per == (long long)H * W * n_out)) {
-        // one-pass Winograd conv with statistics, then GroupNorm + Mish + projection (+ the update of x) in ONE launch
+        // one-pass Winograd conv with statistics, then GroupNorm + Mish + projection (+ the rule) in ONE launch
         ddk_conv_args a{};
         a.kind = DDK_CONV3X3_S1;
         a.src0 = cur; a.c0 = cur_c;
@@ -1391,30 +1387,13 @@ static int forward_core(const ddk_unet& u, const float* P, const float* x, int64
         a.gn_partials = gnp;
         a.gn_groups = GROUPS;
         DDK_TRY(conv_forward(a, st));
-        if (step && step->vlb)
-            return final_tail_vlb(raw, gnp, npf, P + u.final_norm.g, P + u.final_norm.b, GN_EPS, P + u.final_w, P + u.final_b, n_out,
-                                  *step->vlb, t, step->state, B, H * W, chan, GROUPS, st, dec_counter);
-        if (step)
-            return final_tail(raw, gnp, npf, P + u.final_norm.g, P + u.final_norm.b, GN_EPS, P + u.final_w, P + u.final_b, n_out, nullptr,
-                              step->x, step->noise, step->noise_step_stride, step->t_first, t, step->c_recip, step->c_recipm1, step->c1,
-                              step->c2, step->sigma, step->state, 0, 0, B, H * W, chan, GROUPS, st, dec_counter, step->x0_hist, step->c3,
-                              step->inp);
-        return final_tail(raw, gnp, npf, P + u.final_norm.g, P + u.final_norm.b, GN_EPS, P + u.final_w, P + u.final_b, n_out, out, nullptr,
-                          nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, B, H * W, chan, GROUPS, st);
+        const TailIn in{raw, gnp, npf, P + u.final_norm.g, P + u.final_norm.b, GN_EPS, P + u.final_w, P + u.final_b, n_out, B, H * W, chan, GROUPS};
+        return final_tail(in, rule, t, hooks, st);
     }
     DDK_TRY(run_conv_gn(c, u.final_conv, cur, cur_c, nullptr, 0, raw, u.final_norm, nullptr, nullptr, a1, H, W, chan));
     float* eps_hat = step ? step->eps_hat : out;
     DDK_TRY(conv1x1_small_n(a1, P + u.final_w, P + u.final_b, eps_hat, (long long)B * H * W, chan, n_out, st));
-    if (!step) return DDK_OK;
-    if (step->vlb) return vlb_sweep_terms(*step->vlb, t, eps_hat, B, step->per, step->state, st, dec_counter);
-    if (step->x0_hist)
-        return p_sample_update_ms(step->x, eps_hat, step->x0_hist, t, step->c_recip, step->c_recipm1, step->c1, step->c2, step->c3, B,
-                                  step->per, st, dec_counter);
-    if (step->inp)
-        return p_sample_update_inpaint(step->x, eps_hat, *step->inp, t, step->c_recip, step->c_recipm1, step->c1, step->c2, step->sigma, B,
-                                       step->per, 0, 0, st, step->state, dec_counter);
-    return p_sample_update(step->x, eps_hat, step->noise, step->noise_step_stride, step->t_first, t, step->c_recip, step->c_recipm1,
-                           step->c1, step->c2, step->sigma, B, step->per, 0, 0, st, step->state, dec_counter);
+    return step ? p_update(rule, eps_hat, t, B, step->per, hooks, st) : DDK_OK;
 }
 
 static int check_shape(const ddk_unet* u, int B, int H, int W) {
@@ -1588,10 +1567,6 @@ __global__ void iota64_kernel(int64_t* out, int n) {
 }
 }  // namespace ddk
 
-extern "C" size_t ddk_sampler_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start) {
-    if (check_shape(u, B, H, W) != DDK_OK || t_start < 0) return 0;
-    return sampler_layout(*u, B, H, W, t_start).total * sizeof(float);
-}
 
 namespace ddk {
 // Time-shift table for rows 0..t_start: the same two kernels a forward runs, once, with "batch" = all rows.  Row k holds the shifts
@@ -1706,7 +1681,7 @@ static int run_chain(ddk_unet& u, const ChainKey& key, int n_steps, bool use_gra
     return DDK_OK;
 }
 
-// What a chain entry (ddk_sampler_run_spaced, ddk_vlb_sweep_run) hands its steps and run_chain, filled by begin_chain.
+// What a chain entry (sampler_chain, ddk_vlb_sweep_run) hands its steps and run_chain, filled by begin_chain.
 struct ChainRun {
     ddk_unet* u;
     int B, H, W;
@@ -1721,7 +1696,7 @@ struct ChainRun {
     int dev = 0;                             // the current device: part of the graph cache key
     std::unique_lock<std::mutex> lock;       // u->mu, held until the entry returns
 
-    // one UNet forward of a step on `x`: the counter bookkeeping in its first kernel, step->vlb or the reverse update in its last
+    // one UNet forward of a step on `x`: the counter bookkeeping in its first kernel, step->rule in its last
     int forward(const float* x, const StepArgs* step) {
         return forward_core(*u, P, x, t_cur, nullptr, B, H, W, ws, ly, st, u->cluster_gn >= 1, ws + sl.off_table, step);
     }
@@ -1786,39 +1761,75 @@ static int check_timestep_map(const int64_t* map, int t_start, const char* who) 
 }
 }  // namespace ddk
 
+namespace ddk {
+// floats a chain keeps behind the sampler layout, by its rule: the multistep history [B][H][W][in_ch]; the inpainting op's known
+// latent and mask.  The size queries and sampler_chain's carve-up both come from here.
+static size_t chain_extra_floats(const ddk_unet& u, int B, int H, int W, StepKind kind) {
+    const size_t n = al4((size_t)B * H * W * u.cfg.in_ch);
+    return kind == StepKind::Multistep ? n : kind == StepKind::Inpaint ? 2 * n : 0;
+}
+static size_t sampler_bytes(const ddk_unet* u, int B, int H, int W, int t_start, StepKind kind) {
+    if (check_shape(u, B, H, W) != DDK_OK || t_start < 0) return 0;
+    return (sampler_layout(*u, B, H, W, t_start).total + chain_extra_floats(*u, B, H, W, kind)) * sizeof(float);
+}
+
+// What the sampler entries share once their own arguments are checked: n_steps reverse steps on a->x, step k at timestep map[k],
+// each ending in `rule`.  The entry sets rule.kind and the operands only its kind has (c3; inp, with the CALLER's known / mask);
+// x, the noise and the tables c_recip .. sigma come from *a here.  What a kind keeps in the workspace is staged after begin_chain
+// and outside any captured step, so no chain sees another's and the cached graph points only into the workspace:
+//   Multistep: the history, zeroed by every call (c3[t_start] == 0 makes the first step first order whatever it would hold)
+//   Inpaint:   known and mask, copied in before the first op
+// The graph key: the kind and every table the step reads; the staged operands live in the workspace, which is in the key.
+static int sampler_chain(const ddk_sampler_args* a, const char* who, const int64_t* map, StepRule rule, ddk_stream_t s) {
+    const int B = a->B, H = a->H, W = a->W, n_steps = a->t_start - a->t_end + 1;
+    ChainRun c;
+    DDK_TRY(begin_chain(c, a, who, a->t_start, a->stream_id, map, n_steps,
+                        [&](const SamplerLayout& sl) { return sl.total + chain_extra_floats(*a->unet, B, H, W, rule.kind); }, s));
+    rule.x = a->x; rule.noise = a->noise; rule.noise_step_stride = a->noise ? B * c.per : 0; rule.t_first = a->t_start;
+    rule.c_recip = a->c_recip; rule.c_recipm1 = a->c_recipm1; rule.c1 = a->c1; rule.c2 = a->c2; rule.sigma = a->sigma;
+    const size_t n = (size_t)B * c.per;
+    float* extra = c.ws + c.sl.total;
+    if (rule.kind == StepKind::Multistep) {
+        DDK_HIP(hipMemsetAsync(extra, 0, n * sizeof(float), c.st));
+        rule.x0_hist = extra;
+    } else if (rule.kind == StepKind::Inpaint) {
+        DDK_HIP(hipMemcpyAsync(extra, rule.inp.known, n * sizeof(float), hipMemcpyDeviceToDevice, c.st));
+        DDK_HIP(hipMemcpyAsync(extra + al4(n), rule.inp.mask, n * sizeof(float), hipMemcpyDeviceToDevice, c.st));
+        rule.inp.known = extra;
+        rule.inp.mask = extra + al4(n);
+    }
+    const StepArgs step{c.state, c.ws + c.sl.off_eps, c.per, rule};
+
+    // one reverse step: bookkeeping (in the forward's first kernel), UNet, the rule (in its last kernel)
+    auto one_step = [&]() -> int { return c.forward(a->x, &step); };
+
+    const ChainKey key{rule.kind,
+                       {a->packed, a->x, rule.c_recip, rule.c_recipm1, rule.c1, rule.c2, rule.sigma, rule.c3, rule.inp.ka, rule.inp.kb,
+                        rule.inp.ja, rule.inp.jb},
+                       a->workspace, a->noise, B, H, W, a->t_start, c.dev, c.u->pack_epoch};
+    return run_chain(*c.u, key, n_steps, a->use_graph != 0, one_step, c.st, who);
+}
+}  // namespace ddk
+
+extern "C" size_t ddk_sampler_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start) {
+    return sampler_bytes(u, B, H, W, t_start, StepKind::Ancestral);
+}
+
 extern "C" int ddk_sampler_run_spaced(const ddk_sampler_args* a, const int64_t* timestep_map, ddk_stream_t s) {
     DDK_REQUIRE(a && a->unet && a->packed && a->x && a->workspace, "sampler: null pointer");
     DDK_REQUIRE(a->c_recip && a->c_recipm1 && a->c1 && a->c2 && a->sigma, "sampler: null schedule table");
     DDK_REQUIRE(a->t_start >= a->t_end && a->t_end >= 0, "sampler: need t_start >= t_end >= 0");
     DDK_TRY(check_timestep_map(timestep_map, a->t_start, "sampler"));
-    const int B = a->B, H = a->H, W = a->W, n_steps = a->t_start - a->t_end + 1;
-    ChainRun c;
-    DDK_TRY(begin_chain(c, a, "sampler", a->t_start, a->stream_id, timestep_map, n_steps,
-                        [](const SamplerLayout& sl) { return sl.total; }, s));
-    const StepArgs step{c.state, a->x, c.ws + c.sl.off_eps, a->noise, a->noise ? B * c.per : 0, a->t_start, a->c_recip, a->c_recipm1,
-                        a->c1, a->c2, a->sigma, c.per};
-
-    // one reverse step: bookkeeping (in the forward's first kernel), UNet, update of x (in its last kernel)
-    auto one_step = [&]() -> int { return c.forward(a->x, &step); };
-
-    const ChainKey key{CHAIN_SAMPLER, {a->packed, a->x, a->noise, a->c_recip, a->c_recipm1, a->c1, a->c2, a->sigma}, a->workspace, a->noise,
-                       B, H, W, a->t_start, c.dev, c.u->pack_epoch};
-    return run_chain(*c.u, key, n_steps, a->use_graph != 0, one_step, c.st, "sampler");
+    StepRule rule{};
+    rule.kind = StepKind::Ancestral;
+    return sampler_chain(a, "sampler", timestep_map, rule, s);
 }
 
 // ------------------------------------------------------------------------------------------------ multistep sampler
 // DPM-Solver++(2M): the sampler's chain with the update x_prev = (c1 x0 + c2 x) + c3 x0_hist, x0_hist <- x0.
-// The history [B][H][W][in_ch] sits behind the sampler layout and is zeroed (outside any captured step) by every call, so no chain
-// sees another's; c3[t_start] == 0 makes the first step first order whatever the zeroed history would hold.
-namespace ddk {
-static size_t multistep_floats(const ddk_unet& u, int B, int H, int W, int t_start) {
-    return sampler_layout(u, B, H, W, t_start).total + al4((size_t)B * H * W * u.cfg.in_ch);
-}
-}  // namespace ddk
-
+// A kind of its own and c3 in the graph key: a DDIM chain on the same buffers never replays this graph, nor this one a DDIM graph.
 extern "C" size_t ddk_sampler_multistep_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start) {
-    if (check_shape(u, B, H, W) != DDK_OK || t_start < 0) return 0;
-    return multistep_floats(*u, B, H, W, t_start) * sizeof(float);
+    return sampler_bytes(u, B, H, W, t_start, StepKind::Multistep);
 }
 
 extern "C" int ddk_sampler_run_multistep(const ddk_sampler_args* a, const int64_t* timestep_map, const float* c3, ddk_stream_t s) {
@@ -1827,33 +1838,16 @@ extern "C" int ddk_sampler_run_multistep(const ddk_sampler_args* a, const int64_
     DDK_REQUIRE(!a->noise, "sampler_multistep: the solver is deterministic, noise must be NULL");
     DDK_REQUIRE(a->t_start >= a->t_end && a->t_end >= 0, "sampler_multistep: need t_start >= t_end >= 0");
     DDK_TRY(check_timestep_map(timestep_map, a->t_start, "sampler_multistep"));
-    const int B = a->B, H = a->H, W = a->W, n_steps = a->t_start - a->t_end + 1;
-    ChainRun c;
-    DDK_TRY(begin_chain(c, a, "sampler_multistep", a->t_start, a->stream_id, timestep_map, n_steps,
-                        [&](const SamplerLayout&) { return multistep_floats(*a->unet, B, H, W, a->t_start); }, s));
-    float* hist = c.ws + c.sl.total;
-    DDK_HIP(hipMemsetAsync(hist, 0, (size_t)B * c.per * sizeof(float), c.st));
-    StepArgs step{c.state, a->x, c.ws + c.sl.off_eps, nullptr, 0, a->t_start, a->c_recip, a->c_recipm1, a->c1, a->c2, nullptr, c.per};
-    step.x0_hist = hist;
-    step.c3 = c3;
-
-    auto one_step = [&]() -> int { return c.forward(a->x, &step); };
-
-    // a kind of its own and c3 in the key: a DDIM chain on the same buffers never replays this graph, nor this one a DDIM graph
-    const ChainKey key{CHAIN_SAMPLER_MULTISTEP, {a->packed, a->x, a->c_recip, a->c_recipm1, a->c1, a->c2, c3}, a->workspace, nullptr,
-                       B, H, W, a->t_start, c.dev, c.u->pack_epoch};
-    return run_chain(*c.u, key, n_steps, a->use_graph != 0, one_step, c.st, "sampler_multistep");
+    StepRule rule{};
+    rule.kind = StepKind::Multistep;
+    rule.c3 = c3;
+    return sampler_chain(a, "sampler_multistep", timestep_map, rule, s);
 }
 
 // ------------------------------------------------------------------------------------------------ inpainting sampler
 // RePaint: N reverse ops, row k at timestep map[k]; every op ends in RePaint's select and optional forward
-// jump (p_sample_update_inpaint / final_tail's inpainting mode).  known and mask [B][H][W][in_ch] are copied behind the sampler
-// layout before the first op, outside any captured step, so the cached graph points only into the workspace.
+// jump (StepKind::Inpaint).
 namespace ddk {
-static size_t inpaint_floats(const ddk_unet& u, int B, int H, int W, int t_start) {
-    return sampler_layout(u, B, H, W, t_start).total + 2 * al4((size_t)B * H * W * u.cfg.in_ch);
-}
-
 // RePaint's map revisits timesteps, so it is not monotone: map[0] == 0 (the only op at tau = 0) and 0 < map[k] < 2^31 for k > 0
 static int check_inpaint_map(const int64_t* map, int t_start, const char* who) {
     if (map[0] != 0) {
@@ -1870,8 +1864,7 @@ static int check_inpaint_map(const int64_t* map, int t_start, const char* who) {
 }  // namespace ddk
 
 extern "C" size_t ddk_sampler_inpaint_workspace_bytes(const ddk_unet* u, int B, int H, int W, int n_ops) {
-    if (check_shape(u, B, H, W) != DDK_OK || n_ops < 1) return 0;
-    return inpaint_floats(*u, B, H, W, n_ops - 1) * sizeof(float);
+    return sampler_bytes(u, B, H, W, n_ops - 1, StepKind::Inpaint);
 }
 
 extern "C" int ddk_sampler_run_inpaint(const ddk_sampler_args* a, const ddk_inpaint_args* ip, ddk_stream_t s) {
@@ -1883,26 +1876,10 @@ extern "C" int ddk_sampler_run_inpaint(const ddk_sampler_args* a, const ddk_inpa
     DDK_REQUIRE(a->t_start >= a->t_end && a->t_end >= 0, "sampler_inpaint: need t_start >= t_end >= 0");
     DDK_REQUIRE(aligned16(ip->known) && aligned16(ip->mask), "sampler_inpaint: alignment");
     DDK_TRY(check_inpaint_map(ip->timestep_map, a->t_start, "sampler_inpaint"));
-    const int B = a->B, H = a->H, W = a->W, n_steps = a->t_start - a->t_end + 1;
-    ChainRun c;
-    DDK_TRY(begin_chain(c, a, "sampler_inpaint", a->t_start, a->stream_id, ip->timestep_map, n_steps,
-                        [&](const SamplerLayout&) { return inpaint_floats(*a->unet, B, H, W, a->t_start); }, s));
-    const size_t n = (size_t)B * c.per;
-    float* known = c.ws + c.sl.total;
-    float* mask = known + al4(n);
-    DDK_HIP(hipMemcpyAsync(known, ip->known, n * sizeof(float), hipMemcpyDeviceToDevice, c.st));
-    DDK_HIP(hipMemcpyAsync(mask, ip->mask, n * sizeof(float), hipMemcpyDeviceToDevice, c.st));
-    const InpaintOps ops{known, mask, ip->ka, ip->kb, ip->ja, ip->jb};
-    StepArgs step{c.state, a->x, c.ws + c.sl.off_eps, nullptr, 0, a->t_start, a->c_recip, a->c_recipm1, a->c1, a->c2, a->sigma, c.per};
-    step.inp = &ops;
-
-    auto one_step = [&]() -> int { return c.forward(a->x, &step); };
-
-    // a kind of its own and the row tables in the key; known / mask live in the workspace, so they are not
-    const ChainKey key{CHAIN_SAMPLER_INPAINT,
-                       {a->packed, a->x, a->c_recip, a->c_recipm1, a->c1, a->c2, a->sigma, ip->ka, ip->kb, ip->ja, ip->jb},
-                       a->workspace, nullptr, B, H, W, a->t_start, c.dev, c.u->pack_epoch};
-    return run_chain(*c.u, key, n_steps, a->use_graph != 0, one_step, c.st, "sampler_inpaint");
+    StepRule rule{};
+    rule.kind = StepKind::Inpaint;
+    rule.inp = InpaintOps{ip->known, ip->mask, ip->ka, ip->kb, ip->ja, ip->jb};
+    return sampler_chain(a, "sampler_inpaint", ip->timestep_map, rule, s);
 }
 
 // ------------------------------------------------------------------------------------------------ likelihood sweep
@@ -1916,7 +1893,7 @@ static SweepLayout sweep_layout(const ddk_unet& u, int B, int H, int W, int T) {
     SweepLayout s;
     s.sl = sampler_layout(u, B, H, W, T - 1);
     const long long per = (long long)H * W * u.cfg.in_ch;
-    const int npf = fused_tail_parts(u, B, H, W, u.dimp[1], true);
+    const int npf = fused_tail_parts(u, B, H, W, u.dimp[1], StepKind::Vlb);
     s.nslot = npf > 0 ? npf : vlb_sweep_slots_unfused(B, per);
     s.off_xt = s.sl.total;
     s.off_part = s.off_xt + al4((size_t)B * per);
@@ -1946,9 +1923,7 @@ extern "C" int ddk_vlb_sweep_run(const ddk_vlb_sweep_args* a, ddk_stream_t s) {
     float* partials = c.ws + vl.off_part;
     const VlbStep v{a->x, xt, a->noise, a->noise ? B * per : 0, T - 1, a->c_recip, a->c_recipm1, a->c1, a->c2, a->post_logvar,
                     partials, vl.nslot};
-    StepArgs step{c.state, nullptr, c.ws + c.sl.off_eps, a->noise, a->noise ? B * per : 0, T - 1, a->c_recip, a->c_recipm1, a->c1, a->c2,
-                  nullptr, per};
-    step.vlb = &v;
+    const StepArgs step{c.state, c.ws + c.sl.off_eps, per, vlb_rule(v)};
 
     // one step: x_t = q_sample(x, t, eps), UNet(x_t, t) with the counter bookkeeping of a reverse step, the VLB epilogue
     auto one_step = [&]() -> int {
@@ -1956,7 +1931,7 @@ extern "C" int ddk_vlb_sweep_run(const ddk_vlb_sweep_args* a, ddk_stream_t s) {
         return c.forward(xt, &step);
     };
 
-    const ChainKey key{CHAIN_VLB_SWEEP,
+    const ChainKey key{StepKind::Vlb,
                        {a->packed, a->x, a->noise, a->sqrt_acp, a->sqrt_1m_acp, a->c_recip, a->c_recipm1, a->c1, a->c2, a->post_logvar},
                        a->workspace, a->noise, B, H, W, T - 1, c.dev, c.u->pack_epoch};
     DDK_TRY(run_chain(*c.u, key, T, a->use_graph != 0, one_step, c.st, "vlb_sweep"));

@@ -21,6 +21,14 @@ def sinusoidal_freqs(dim):
     return torch.exp(torch.arange(half) * -step)
 
 
+# the sampler entries by workspace kind: (method, chain name in messages, name of the workspace in messages)
+SAMPLERS = {"smp": ("sample", "sampler", "sampler"), "sms": ("sample_multistep", "sampler_multistep", "multistep sampler"),
+            "sin": ("sample_inpaint", "sampler_inpaint", "inpainting sampler")}
+# workspace kinds whose captured step graphs point into them (the samplers', the likelihood sweep's): UnetPlan._workspace keeps up
+# to 3 of each
+CHAIN_WORKSPACES = (*SAMPLERS, "vsw")
+
+
 class UnetPlan:
     def __init__(self, in_ch, chan, mults):
         lib = L.load()
@@ -85,7 +93,7 @@ class UnetPlan:
         if hit is not None:
             self._ws[key] = self._ws.pop(key)          # most recently used last
             return hit
-        if kind in ("smp", "vsw", "sms", "sin"):
+        if kind in CHAIN_WORKSPACES:
             mine = [k for k in self._ws if k[0] == kind]       # dict order = least recently used first
             if len(mine) >= 3:
                 # evict ONLY the least recently used workspace; the plan drops the graphs that point into it (and waits for
@@ -194,6 +202,43 @@ class UnetPlan:
         return out
 
     # ---------------------------------------------------------------- sampler
+    def _need_packed(self, kind):
+        if self.packed is None:
+            raise L.DDKError(f"UnetPlan.{SAMPLERS[kind][0]} before pack()")
+
+    def _run_sampler(self, kind, x, t_start, t_end, bytes_query, call, use_graph):
+        """What the sampler entries share once their own arguments are checked: steps t_start .. t_end in place on x [B,H,W,in_ch].
+        kind: the entry's key in SAMPLERS, also its workspace kind; bytes_query(b, h, w): its workspace size query;
+        call(x, ws, nbytes, stream_ptr): the C call, x being the buffer the chain runs on (_chain_x)."""
+        _, who, label = SAMPLERS[kind]
+        b, h, w, _ = x.shape
+        nbytes = bytes_query(b, h, w)
+        if nbytes == 0:
+            raise L.DDKError(f"{label} workspace query failed: {L.last_error()}")
+        ws = self._workspace(kind, nbytes, x.device)
+        caller_x, x = x, self._chain_x(x)
+        # the in-launch GroupNorm can fail (loudly) when the GPU is shared: keep x_T so the chain can be rerun without it
+        x_start = x.clone() if self._chain_guarded() else None
+        self._run_chain(who, lambda stream_ptr: call(x, ws, nbytes, stream_ptr), ws, b, h, w, use_graph and t_start - t_end + 1 > 1,
+                        restore=lambda: x.copy_(x_start))
+        if caller_x.data_ptr() != x.data_ptr():
+            caller_x.copy_(x)
+        return caller_x
+
+    @staticmethod
+    def _timestep_map(timesteps, t_start):
+        if timesteps is None:
+            return None
+        if len(timesteps) != t_start + 1:
+            raise L.DDKError(f"timestep map must have t_start + 1 = {t_start + 1} entries, got {len(timesteps)}")
+        return (C.c_int64 * len(timesteps))(*[int(v) for v in timesteps])
+
+    def _sampler_args(self, x, noise, tables, t_start, t_end, seed, stream_id, use_graph, ws, nbytes):
+        b, h, w, _ = x.shape
+        return L.SamplerArgs(self.handle, L.ptr(self.packed), L.ptr(x), L.ptr(noise), L.ptr(tables["c_recip"]),
+                             L.ptr(tables["c_recipm1"]), L.ptr(tables["c1"]), L.ptr(tables["c2"]), L.ptr(tables.get("sigma")),
+                             b, h, w, t_start, t_end, seed, stream_id, int(use_graph), L.ptr(ws), nbytes)
+
     def sample_nhwc(self, x, tables, t_start, t_end=0, noise=None, seed=0, stream_id=0, use_graph=True, timesteps=None):
         """Run steps t_start .. t_end (inclusive) of the reverse chain in place on x [B,H,W,in_ch].
 
@@ -202,39 +247,22 @@ class UnetPlan:
         timesteps: optional timestep map of a respaced / DDIM chain (t_start + 1 ints, map[0] == 0, increasing): step k runs
         the UNet at timesteps[k] while the tables and the Philox draws are indexed by k (ddk_sampler_run_spaced).
         """
-        if self.packed is None:
-            raise L.DDKError("UnetPlan.sample before pack()")
-        b, h, w, c = x.shape
+        self._need_packed("smp")
         lib = self._lib
-        tmap = None
-        if timesteps is not None:
-            if len(timesteps) != t_start + 1:
-                raise L.DDKError(f"timestep map must have t_start + 1 = {t_start + 1} entries, got {len(timesteps)}")
-            tmap = (C.c_int64 * len(timesteps))(*[int(v) for v in timesteps])
-        nbytes = lib.ddk_sampler_workspace_bytes(self.handle, b, h, w, t_start)
-        if nbytes == 0:
-            raise L.DDKError(f"sampler workspace query failed: {L.last_error()}")
-        ws = self._workspace("smp", nbytes, x.device)
+        tmap = self._timestep_map(timesteps, t_start)
         n_steps = t_start - t_end + 1
-        if noise is not None and tuple(noise.shape) != (n_steps, b, h, w, c):
-            raise L.DDKError(f"injected noise must be {(n_steps, b, h, w, c)}, got {tuple(noise.shape)}")
-        caller_x, x = x, self._chain_x(x)
-        # the in-launch GroupNorm can fail (loudly) when the GPU is shared: keep x_T so the chain can be rerun without it
-        x_start = x.clone() if self._chain_guarded() else None
+        if noise is not None and tuple(noise.shape) != (n_steps, *x.shape):
+            raise L.DDKError(f"injected noise must be {(n_steps, *x.shape)}, got {tuple(noise.shape)}")
 
-        def call(stream_ptr):
-            a = L.SamplerArgs(self.handle, L.ptr(self.packed), L.ptr(x), L.ptr(noise), L.ptr(tables["c_recip"]),
-                              L.ptr(tables["c_recipm1"]), L.ptr(tables["c1"]), L.ptr(tables["c2"]), L.ptr(tables["sigma"]),
-                              b, h, w, t_start, t_end, seed, stream_id, int(use_graph), L.ptr(ws), nbytes)
+        def call(x, ws, nbytes, stream_ptr):
+            a = self._sampler_args(x, noise, tables, t_start, t_end, seed, stream_id, use_graph, ws, nbytes)
             if tmap is None:
                 L.check(lib.ddk_sampler_run(C.byref(a), stream_ptr), "sampler_run")
             else:
                 L.check(lib.ddk_sampler_run_spaced(C.byref(a), tmap, stream_ptr), "sampler_run_spaced")
 
-        self._run_chain("sampler", call, ws, b, h, w, use_graph and n_steps > 1, restore=lambda: x.copy_(x_start))
-        if caller_x.data_ptr() != x.data_ptr():
-            caller_x.copy_(x)
-        return caller_x
+        return self._run_sampler("smp", x, t_start, t_end,
+                                 lambda b, h, w: lib.ddk_sampler_workspace_bytes(self.handle, b, h, w, t_start), call, use_graph)
 
     def _chain_x(self, x):
         """The buffer a sampler chain runs on.  The captured graph holds the ADDRESS of the chain state.  A caller that keeps
@@ -259,33 +287,16 @@ class UnetPlan:
         dpm_solver_tables; c3[t_start] == 0).  timesteps: the chain's timestep map (t_start + 1 ints, map[0] == 0, increasing) or
         None for the identity.  Deterministic: no noise, no seed.  The solver's history lives in the plan's "sms" workspace and is
         zeroed by every call."""
-        if self.packed is None:
-            raise L.DDKError("UnetPlan.sample_multistep before pack()")
-        b, h, w, c = x.shape
+        self._need_packed("sms")
         lib = self._lib
-        tmap = None
-        if timesteps is not None:
-            if len(timesteps) != t_start + 1:
-                raise L.DDKError(f"timestep map must have t_start + 1 = {t_start + 1} entries, got {len(timesteps)}")
-            tmap = (C.c_int64 * len(timesteps))(*[int(v) for v in timesteps])
-        nbytes = lib.ddk_sampler_multistep_workspace_bytes(self.handle, b, h, w, t_start)
-        if nbytes == 0:
-            raise L.DDKError(f"multistep sampler workspace query failed: {L.last_error()}")
-        ws = self._workspace("sms", nbytes, x.device)
-        n_steps = t_start - t_end + 1
-        caller_x, x = x, self._chain_x(x)
-        x_start = x.clone() if self._chain_guarded() else None
+        tmap = self._timestep_map(timesteps, t_start)
 
-        def call(stream_ptr):
-            a = L.SamplerArgs(self.handle, L.ptr(self.packed), L.ptr(x), None, L.ptr(tables["c_recip"]), L.ptr(tables["c_recipm1"]),
-                              L.ptr(tables["c1"]), L.ptr(tables["c2"]), None, b, h, w, t_start, t_end, 0, stream_id, int(use_graph),
-                              L.ptr(ws), nbytes)
+        def call(x, ws, nbytes, stream_ptr):
+            a = self._sampler_args(x, None, tables, t_start, t_end, 0, stream_id, use_graph, ws, nbytes)
             L.check(lib.ddk_sampler_run_multistep(C.byref(a), tmap, L.ptr(tables["c3"]), stream_ptr), "sampler_run_multistep")
 
-        self._run_chain("sampler_multistep", call, ws, b, h, w, use_graph and n_steps > 1, restore=lambda: x.copy_(x_start))
-        if caller_x.data_ptr() != x.data_ptr():
-            caller_x.copy_(x)
-        return caller_x
+        return self._run_sampler("sms", x, t_start, t_end,
+                                 lambda b, h, w: lib.ddk_sampler_multistep_workspace_bytes(self.handle, b, h, w, t_start), call, use_graph)
 
     def sample_inpaint_nhwc(self, x, known, mask, tables, timesteps, t_end=0, seed=0, stream_id=0, use_graph=True):
         """RePaint ops N-1 .. t_end (inclusive) in place on x [B,H,W,in_ch] (ddk_sampler_run_inpaint).
@@ -294,8 +305,7 @@ class UnetPlan:
         so a loop over images replays one cached graph.  tables: dict with c_recip, c_recipm1, c1, c2, sigma, ka, kb, ja, jb (N-row
         fp32 device tensors of models/diffusion/respace.py repaint_tables).  timesteps: the N-entry timestep map (map[0] == 0, not
         monotone).  Philox only: no injected noise; stream_id < 2^29."""
-        if self.packed is None:
-            raise L.DDKError("UnetPlan.sample_inpaint before pack()")
+        self._need_packed("sin")
         b, h, w, c = x.shape
         for name, v in (("known", known), ("mask", mask)):
             if tuple(v.shape) != (b, h, w, c) or v.dtype != torch.float32 or not v.is_contiguous():
@@ -304,27 +314,15 @@ class UnetPlan:
         n_ops = len(timesteps)
         t_start = n_ops - 1
         tmap = (C.c_int64 * n_ops)(*[int(v) for v in timesteps])
-        nbytes = lib.ddk_sampler_inpaint_workspace_bytes(self.handle, b, h, w, n_ops)
-        if nbytes == 0:
-            raise L.DDKError(f"inpainting sampler workspace query failed: {L.last_error()}")
-        ws = self._workspace("sin", nbytes, x.device)
-        n_steps = t_start - t_end + 1
-        caller_x, x = x, self._chain_x(x)
-        x_start = x.clone() if self._chain_guarded() else None
 
-        def call(stream_ptr):
-            a = L.SamplerArgs(self.handle, L.ptr(self.packed), L.ptr(x), None, L.ptr(tables["c_recip"]), L.ptr(tables["c_recipm1"]),
-                              L.ptr(tables["c1"]), L.ptr(tables["c2"]), L.ptr(tables["sigma"]), b, h, w, t_start, t_end, seed, stream_id,
-                              int(use_graph), L.ptr(ws), nbytes)
+        def call(x, ws, nbytes, stream_ptr):
+            a = self._sampler_args(x, None, tables, t_start, t_end, seed, stream_id, use_graph, ws, nbytes)
             ip = L.InpaintArgs(tmap, L.ptr(known), L.ptr(mask), L.ptr(tables["ka"]), L.ptr(tables["kb"]), L.ptr(tables["ja"]),
                                L.ptr(tables["jb"]))
             L.check(lib.ddk_sampler_run_inpaint(C.byref(a), C.byref(ip), stream_ptr), "sampler_run_inpaint")
 
-        self._run_chain("sampler_inpaint", call, ws, b, h, w, use_graph and n_steps > 1, restore=lambda: x.copy_(x_start))
-        if caller_x.data_ptr() != x.data_ptr():
-            caller_x.copy_(x)
-        return caller_x
-
+        return self._run_sampler("sin", x, t_start, t_end,
+                                 lambda b, h, w: lib.ddk_sampler_inpaint_workspace_bytes(self.handle, b, h, w, n_ops), call, use_graph)
 
     # ---------------------------------------------------------------- likelihood sweep
     VLB_STREAM_BIT = 1 << 31     # the sweep's Philox stream id is stream_id | this (csrc/ddk_internal.h VLB_STREAM_BIT)

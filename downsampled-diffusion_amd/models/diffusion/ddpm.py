@@ -66,7 +66,7 @@ class DDPM(nn.Module):
         assert not torch.isnan(self.vlb_weights).all()
         # exp(0.5 * logvar) of ddpm.py:227 evaluated once with the same fp32 torch ops (non-persistent)
         self.register_buffer('posterior_sigma', f32_tables['posterior_sigma'], persistent=False)
-        self._spaced = {}      # (respacing, ddim, eta, device) -> (tables, timestep map): see _spaced_tables (and _solver_tables)
+        self._spaced = {}      # (chain's key, device) -> (tables, timestep map): see _cached_tables
 
         # sampler knobs (not in the reference): native hipGraph loop + in-kernel Philox noise by default
         self.native_sampler = True
@@ -143,27 +143,41 @@ class DDPM(nn.Module):
         x = x_t.contiguous().clone()
         return ops.p_sample_update_(x, eps_hat.contiguous(), t.contiguous(), noise=z.contiguous(), **self._tables())
 
-    def _spaced_tables(self, respacing, ddim, eta):
-        """(tables on the model's device, timestep map) of a respaced / DDIM chain (models/diffusion/respace.py), made once per
-        (respacing, ddim, eta, device): repeated calls pass the same table tensors, so they hit the plan's graph cache."""
+    def _cached_tables(self, key, build):
+        """build() -> (tables, timestep map), made once per (key, device) and kept with the tables on the model's device:
+        repeated calls pass the same table tensors, so they hit the plan's graph cache."""
         device = self.betas.device
-        key = (respacing, bool(ddim), float(eta), str(device))
+        key = (*key, str(device))
         hit = self._spaced.get(key)
         if hit is None:
-            tables, use = respace.spaced_tables(self._betas64, respacing, ddim, eta)
+            tables, use = build()
             hit = self._spaced[key] = ({k: v.to(device) for k, v in tables.items()}, use)
         return hit
 
+    def _spaced_tables(self, respacing, ddim, eta):
+        """(tables, timestep map) of a respaced / DDIM chain (respace.spaced_tables); see _cached_tables."""
+        return self._cached_tables((respacing, bool(ddim), float(eta)),
+                                   lambda: respace.spaced_tables(self._betas64, respacing, ddim, eta))
+
     def _solver_tables(self, respacing, solver):
-        """(tables c_recip, c_recipm1, c1, c2, c3 on the model's device, timestep map) of a DPM-Solver++(2M) chain
-        (respace.dpm_solver_tables), made once per (respacing, solver, device) like _spaced_tables."""
+        """(tables c_recip, c_recipm1, c1, c2, c3, timestep map) of a DPM-Solver++(2M) chain (respace.dpm_solver_tables)."""
+        return self._cached_tables(('solver', respacing, solver), lambda: respace.dpm_solver_tables(self._betas64, respacing, order=2))
+
+    def _chain_start(self, shape, x_T, early_stop, get_tables):
+        """(device, tables, use, start state, k_start, k_end) of a chain with (tables, use) = get_tables(), asked for once the
+        device is known to be a GPU.  `use` is the timestep map (None: all T timesteps): the chain runs steps k_start .. k_end of
+        its tables, step k at timestep use[k]; early_stop keeps the steps whose timestep is >= early_stop."""
         device = self.betas.device
-        key = ('solver', respacing, solver, str(device))
-        hit = self._spaced.get(key)
-        if hit is None:
-            tables, use = respace.dpm_solver_tables(self._betas64, respacing, order=2)
-            hit = self._spaced[key] = ({k: v.to(device) for k, v in tables.items()}, use)
-        return hit
+        if device.type != 'cuda':
+            raise DDKError("p_sample_loop: move the model to a ROCm device first (no CPU fallback)")
+        tables, use = get_tables()
+        if use is None:
+            k_start, k_end = self.timesteps - 1, 0 if early_stop is None else early_stop
+        else:
+            k_start = len(use) - 1
+            k_end = 0 if early_stop is None else next((k for k, t in enumerate(use) if t >= early_stop), len(use))
+        img = torch.randn(shape, device=device) if x_T is None else x_T.to(device).float()
+        return device, tables, use, img, k_start, k_end
 
     @torch.no_grad()
     def p_sample_loop(self, shape, every=1, early_stop=None, x_T=None, noise=None, seed=None, *, respacing=None, ddim=False,
@@ -190,18 +204,8 @@ class DDPM(nn.Module):
         spaced = respacing is not None or ddim or eta != 0
         if spaced and (eta < 0 or (eta != 0 and not ddim)):
             raise ValueError(f"p_sample_loop: eta = {eta} needs ddim=True and eta >= 0")
-        device = self.betas.device
-        if device.type != 'cuda':
-            raise DDKError("p_sample_loop: move the model to a ROCm device first (no CPU fallback)")
-        # the chain runs steps k_start .. k_end of its tables; a spaced chain's step k runs the UNet at timestep use[k]
-        if spaced:
-            tables, use = self._spaced_tables(respacing, ddim, eta)
-            k_start = len(use) - 1
-            k_end = 0 if early_stop is None else next((k for k, t in enumerate(use) if t >= early_stop), len(use))
-        else:
-            tables, use = self._tables(), None
-            k_start, k_end = self.timesteps - 1, 0 if early_stop is None else early_stop
-        img = torch.randn(shape, device=device) if x_T is None else x_T.to(device).float()
+        device, tables, use, img, k_start, k_end = self._chain_start(
+            shape, x_T, early_stop, lambda: self._spaced_tables(respacing, ddim, eta) if spaced else (self._tables(), None))
         if k_end > k_start:
             return img
         n_steps = k_start - k_end + 1
@@ -236,13 +240,8 @@ class DDPM(nn.Module):
     def _solver_loop(self, shape, early_stop, x_T, respacing, solver):
         """p_sample_loop(solver=...): steps k_start .. k_end of the solver's tables, step k at timestep use[k]; native
         (UnetPlan.sample_multistep_nhwc) or, with native_sampler off, the same update as a Python loop."""
-        device = self.betas.device
-        if device.type != 'cuda':
-            raise DDKError("p_sample_loop: move the model to a ROCm device first (no CPU fallback)")
-        tables, use = self._solver_tables(respacing, solver)
-        k_start = len(use) - 1
-        k_end = 0 if early_stop is None else next((k for k, t in enumerate(use) if t >= early_stop), len(use))
-        img = torch.randn(shape, device=device) if x_T is None else x_T.to(device).float()
+        device, tables, use, img, k_start, k_end = self._chain_start(shape, x_T, early_stop,
+                                                                     lambda: self._solver_tables(respacing, solver))
         if k_end > k_start:
             return img
         if not self.native_sampler:
@@ -300,15 +299,9 @@ class DDPM(nn.Module):
         return x.float(), m
 
     def _inpaint_tables(self, respacing, jump_length, jump_n_sample):
-        """(tables c_recip .. sigma, ka, kb, ja, jb on the model's device, timestep map) of a RePaint chain
-        (respace.repaint_tables), made once per (respacing, j, r, device) like _spaced_tables."""
-        device = self.betas.device
-        key = ('repaint', respacing, int(jump_length), int(jump_n_sample), str(device))
-        hit = self._spaced.get(key)
-        if hit is None:
-            tables, use = respace.repaint_tables(self._betas64, respacing, int(jump_length), int(jump_n_sample))
-            hit = self._spaced[key] = ({k: v.to(device) for k, v in tables.items()}, use)
-        return hit
+        """(tables c_recip .. sigma, ka, kb, ja, jb, timestep map) of a RePaint chain (respace.repaint_tables)."""
+        j, r = int(jump_length), int(jump_n_sample)
+        return self._cached_tables(('repaint', respacing, j, r), lambda: respace.repaint_tables(self._betas64, respacing, j, r))
 
     def _inpaint_loop(self, z0, m, respacing, jump_length, jump_n_sample, x_T, seed):
         """RePaint over the latent z0 [B, *sample_shape] with mask m (same shape, {0, 1}): native (UnetPlan.sample_inpaint_nhwc) or,

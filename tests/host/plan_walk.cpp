@@ -2,8 +2,8 @@
 // No GPU: libddk's host half runs under ASan + UBSan with every kernel launch replaced by a checker that validates the launch
 // geometry and that every pointer it would hand to the device lies inside an arena registered here.  For each BASELINE.json
 // configuration (reference models/unet/unet.py:19-72 shapes): create the plan, pack every slot, run one ddk_unet_forward, a
-// three-step eager ddk_sampler_run, a respaced ddk_sampler_run_spaced and a T = 3 ddk_vlb_sweep_run, and check the size queries
-// against the arenas they size.
+// three-step eager ddk_sampler_run, a respaced ddk_sampler_run_spaced, a three-step ddk_sampler_run_multistep, three ops of
+// ddk_sampler_run_inpaint and a T = 3 ddk_vlb_sweep_run, and check the size queries against the arenas they size.
 #include <sys/mman.h>
 
 #include <cstdio>
@@ -93,6 +93,34 @@ static void walk(const char* name, int in_ch, int chan, std::vector<int> mults, 
         CHECK(rc == DDK_OK, "%s: sampler_run_spaced: %s", name, ddk_last_error());
         a.workspace_bytes = sp_bytes - 4;
         CHECK(ddk_sampler_run_spaced(&a, map, nullptr) == DDK_ERR_WORKSPACE, "%s: short spaced sampler workspace accepted", name);
+    }
+    {   // a three-step DPM-Solver++(2M) chain: the history sits behind the sampler layout, sized by the entry's own query
+        const int64_t map[3] = {0, T / 2, T - 1};
+        const size_t ms_bytes = ddk_sampler_multistep_workspace_bytes(u, B, H, W, 2);
+        CHECK(ms_bytes >= ddk_sampler_workspace_bytes(u, B, H, W, 2) + xb, "%s: multistep workspace query %zu", name, ms_bytes);
+        Arena ms(ms_bytes, "multistep sampler workspace"), c3((size_t)3 * 4, "c3");
+        a.t_start = 2; a.t_end = 0; a.workspace = ms.p; a.workspace_bytes = ms_bytes;
+        rc = ddk_sampler_run_multistep(&a, map, c3.f(), nullptr);
+        CHECK(rc == DDK_OK, "%s: sampler_run_multistep: %s", name, ddk_last_error());
+        a.workspace_bytes = ms_bytes - 4;
+        CHECK(ddk_sampler_run_multistep(&a, map, c3.f(), nullptr) == DDK_ERR_WORKSPACE, "%s: short multistep sampler workspace accepted", name);
+    }
+    {   // three RePaint ops on a map that revisits a timestep: known and mask are copied behind the sampler layout
+        const int64_t map[3] = {0, T / 2, T / 2}, bad_map[3] = {1, T / 2, T / 2};
+        const size_t in_bytes = ddk_sampler_inpaint_workspace_bytes(u, B, H, W, 3);
+        CHECK(in_bytes >= ddk_sampler_workspace_bytes(u, B, H, W, 2) + 2 * xb, "%s: inpainting workspace query %zu", name, in_bytes);
+        Arena inw(in_bytes, "inpainting sampler workspace"), known(xb, "known"), mask(xb, "mask"), rows((size_t)4 * 3 * 4, "inpainting row tables");
+        ddk_inpaint_args ip{};
+        ip.timestep_map = map; ip.known = known.f(); ip.mask = mask.f();
+        ip.ka = rows.f(); ip.kb = rows.f() + 3; ip.ja = rows.f() + 6; ip.jb = rows.f() + 9;
+        a.t_start = 2; a.t_end = 0; a.workspace = inw.p; a.workspace_bytes = in_bytes;
+        rc = ddk_sampler_run_inpaint(&a, &ip, nullptr);
+        CHECK(rc == DDK_OK, "%s: sampler_run_inpaint: %s", name, ddk_last_error());
+        a.workspace_bytes = in_bytes - 4;
+        CHECK(ddk_sampler_run_inpaint(&a, &ip, nullptr) == DDK_ERR_WORKSPACE, "%s: short inpainting sampler workspace accepted", name);
+        a.workspace_bytes = in_bytes;
+        ip.timestep_map = bad_map;
+        CHECK(ddk_sampler_run_inpaint(&a, &ip, nullptr) == DDK_ERR_ARG, "%s: inpainting map with a non-zero entry 0 accepted", name);
     }
     {   // a three-step likelihood sweep (q_sample input, VLB epilogue, the final sum)
         const int VT = 3;

@@ -1,8 +1,8 @@
-"""DPM-Solver++(2M) on the GPU (DDPM.p_sample_loop(solver="dpm++2m"), ddk_sampler_run_multistep, p_sample_ms_kernel and
+"""DPM-Solver++(2M) on the GPU (DDPM.p_sample_loop(solver="dpm++2m"), ddk_sampler_run_multistep, p_update_kernel<StepKind::Multistep> and
 final_tail_kernel's multistep mode) against tests/dpm_solver_ref.py, Algorithm 2 in its direct form around oracle/unet_ref at map[k].
 
 The tiny DDPM (unet_chan 32, 3x16x16, linear schedule, T = 1000) has no Winograd final conv, so its steps end in the unfused
-p_sample_ms_kernel; the cfg4 window at B = 32 ends in final_tail_kernel's multistep instantiation.  Bars as for the spaced chains:
+p_update_kernel<StepKind::Multistep>; the cfg4 window at B = 32 ends in final_tail_kernel's multistep instantiation.  Bars as for the spaced chains:
 1e-4 abs against the restatement with the same argmax, 1e-5 between the Python loop and the native sampler."""
 import json
 import os

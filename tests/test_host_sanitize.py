@@ -5,7 +5,8 @@ every translation unit as usual with the host side instrumented and every kernel
 GPU -- including the pointer words inside by-value parameter blocks, and base + extent for the conv and GroupNorm launchers --
 must lie inside an arena of exactly the size the library's own size queries returned.  tests/host/plan_walk.cpp walks all five
 BASELINE configurations (packing, forward with and without the in-launch GroupNorm, a three-step eager sampler chain, a
-respaced chain and a T = 3 likelihood sweep, each also with a short workspace) plus off-config widths / depths / odd batches."""
+respaced chain, a DPM-Solver++(2M) chain, three RePaint ops -- also with a map whose entry 0 is not 0 -- and a T = 3 likelihood
+sweep, each also with a short workspace) plus off-config widths / depths / odd batches."""
 import os
 import shutil
 import subprocess

@@ -1,8 +1,8 @@
-"""RePaint inpainting on the GPU (DDPM.inpaint, DownsampleDDPM.inpaint, ddk_sampler_run_inpaint, p_sample_inpaint_kernel and
+"""RePaint inpainting on the GPU (DDPM.inpaint, DownsampleDDPM.inpaint, ddk_sampler_run_inpaint, p_update_kernel<StepKind::Inpaint> and
 final_tail_kernel's inpainting mode) against tests/repaint_ref.py, RePaint restated around oracle/unet_ref with oracle/philox_ref
 draws in NHWC order.
 
-The tiny DDPM (unet_chan 32, 3x16x16) has no Winograd final conv, so its ops end in the unfused p_sample_inpaint_kernel; its
+The tiny DDPM (unet_chan 32, 3x16x16) has no Winograd final conv, so its ops end in the unfused p_update_kernel<StepKind::Inpaint>; its
 "20", j = 5, r = 3 chain has 50 ops, so the one-step and the 16-step graphs both run.  The cfg4 latent at B = 32 ends in
 final_tail_kernel's inpainting instantiation.  Bars as for the spaced chains: 1e-4 abs against the restatement, 1e-5 between the
 Python loop and the native sampler."""

@@ -2,7 +2,7 @@
 tests/spaced_ref.py, improved-diffusion's SpacedDiffusion / ddim_sample in their direct form around oracle/unet_ref at map[k].
 
 The tiny DDPM (unet_chan 32, 3x16x16, linear schedule, T = 1000) has no Winograd final conv, so its steps end in the unfused
-p_sample_kernel; the cfg4 window at B = 32 ends in final_tail_kernel.  Bars as for the plain chains: 1e-4 abs against the
+p_update_kernel; the cfg4 window at B = 32 ends in final_tail_kernel.  Bars as for the plain chains: 1e-4 abs against the
 restatement with the same argmax, 1e-6 between full respacing and the plain chain, 1e-5 between the Python loop and the
 native sampler.  Each comparison with injected draws has a negative control."""
 import json
@@ -204,7 +204,7 @@ def test_plain_and_ddim_chains_share_a_workspace_without_sharing_rows(tiny, draw
 
 
 def test_unfused_tail_ddim_b4(tiny):
-    """B = 4 on the tiny UNet (no Winograd final conv: p_sample_kernel ends every step), ddim50 eta 0.5 vs the restatement"""
+    """B = 4 on the tiny UNet (no Winograd final conv: p_update_kernel ends every step), ddim50 eta 0.5 vs the restatement"""
     m, eps = tiny
     shape = (4, 3, 16, 16)
     x_T = syn.synthetic_normal(shape, "spaced.b4.xT")

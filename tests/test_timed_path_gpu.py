@@ -2,10 +2,10 @@
 T = 1000) at B = 32, called as bench.py calls it -- plan.sample_nhwc(x, m._tables(), t_start, t_end, seed=, stream_id=3,
 use_graph=True), default plan options.  At B = 32 the 3x3 convs run one workgroup per CU, the in-launch GroupNorm, the
 first-Block GroupNorm and the level chain exchange data inside their launches, and every step ends in
-final_tail_kernel<32, 1, false>; no B <= 8 test reaches that occupancy.
+final_tail_kernel<32, 1, StepKind::Ancestral>; no B <= 8 test reaches that occupancy.
 
 Two 40-step windows, each 16 + 16 + 8 steps of replayed graphs: t = 999 .. 960 with the in-kernel Philox draws (the oracle gets
-the same draws from ops.randn, NHWC [B,H,W,C] at step t: p_sample_kernel's and final_tail_kernel's indexing), and t = 39 .. 0
+the same draws from ops.randn, NHWC [B,H,W,C] at step t: p_update_kernel's and final_tail_kernel's indexing), and t = 39 .. 0
 with injected draws, which includes the noise-free t == 0 step.  The oracle is oracle/diffusion_ref.p_sample_update around
 oracle/unet_ref.unet_forward, started at t_start.  Bar, as for the golden chains: max abs difference <= 1e-4 and the same argmax
 pixel per image (measured 4.8e-7 and 9.5e-7; the decoder 1.8e-6; a changed draw in image 17 misses by 0.11).  Every call must

@@ -63,7 +63,7 @@ def test_sweep_vs_reference_golden_unfused_epilogue(loss_type):
 
 
 def test_sweep_fused_tail_matches_loop_at_cfg4_shape():
-    """unet_chan 128, 8-channel 32x32 latents, B = 32: the final tail runs as final_tail_kernel<32, 1, true>, and the steps use
+    """unet_chan 128, 8-channel 32x32 latents, B = 32: the final tail runs as final_tail_kernel<32, 1, StepKind::Vlb>, and the steps use
     the in-launch GroupNorm and the level chain (the single forwards of the loop do not: close, not bitwise)."""
     m = _model(ddpm_cfg(128, 8, 32, T=100))
     x = syn.synthetic_input((32, 8, 32, 32), "sweep.cfg4.x").clamp(-1, 1).to(DEV)
@@ -164,13 +164,13 @@ def test_evaluate_ddpm_cli_end_to_end(tmp_path):
 # ---------------------------------------------------------------- every final-tail width vs the CPU oracle
 # (unet_chan, in_ch, size, B): which epilogue the sweep's steps end in.  fused_tail_parts (csrc/unet_plan.hip) fuses only when the
 # final conv has a Winograd form (unet_chan % 64 == 0), runs in one pass (conv_wino_splits == 1: at least 256 workgroups without
-# splitting its 32-channel chunks) and final_tail_vlb_ok admits the width (C <= 128).  Confirmed from the kernel names of one
+# splitting its 32-channel chunks) and final_tail_ok admits the width for StepKind::Vlb (C <= 128).  Confirmed from the kernel names of one
 # rocprofv3 --kernel-trace --stats run of these five sweeps.
 SWEEP_CASES = {
-    "c128_b32_fused": (128, 8, 32, 32),      # final_tail_kernel<32, 1, true>: cfg4's shape
-    "c64_b32_fused": (64, 8, 32, 32),        # final_tail_kernel<16, 1, true>
+    "c128_b32_fused": (128, 8, 32, 32),      # final_tail_kernel<32, 1, StepKind::Vlb>: cfg4's shape
+    "c64_b32_fused": (64, 8, 32, 32),        # final_tail_kernel<16, 1, StepKind::Vlb>
     "c64_b8_unfused": (64, 8, 32, 8),        # 64 workgroups: the final conv splits its 2 chunks -> conv + GroupNorm + 1x1
-    "c256_b32_unfused": (256, 3, 16, 32),    # one-pass final conv (2 tiles per image), but C = 256 > 128: final_tail_vlb_ok
+    "c256_b32_unfused": (256, 3, 16, 32),    # one-pass final conv (2 tiles per image), but C = 256 > 128: final_tail_ok(.., StepKind::Vlb)
     "c32_b32_unfused": (32, 3, 16, 32),      # no Winograd final conv; vlb_sweep_terms_kernel over 2 slices per image
 }
 EDGES = torch.tensor([-1.0, 1.0, -0.9995, 0.9995, -0.999, 0.999, -0.9989, 0.9989])
@@ -235,7 +235,7 @@ def test_sweep_every_tail_width_vs_oracle(case):
 
 
 def test_sampler_window_at_256_channels_vs_oracle():
-    """the sampler's final_tail_kernel<32, 2, false> (256 channels, 3x16x16, B = 32: two tiles per image, one-pass final conv):
+    """the sampler's final_tail_kernel<32, 2, StepKind::Ancestral> (256 channels, 3x16x16, B = 32: two tiles per image, one-pass final conv):
     20 steps t = 19 .. 0 of replayed graphs with the in-kernel Philox draws vs the oracle fed the same draws (ops.randn, NHWC at
     step t).  Bar as for the golden chains: 1e-4 abs (measured 7.5e-6), the same argmax pixel per image."""
     from ddk import ops
