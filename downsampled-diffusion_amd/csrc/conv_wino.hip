@@ -951,7 +951,7 @@ extern "C" int ddk_conv3x3_gn_mish_cluster_ok(int B, int H, int W, int cin, int 
 }
 extern "C" size_t ddk_conv3x3_gn_mish_cluster_workspace_bytes(int B, int H, int W, int N) {
     if (B <= 0 || H <= 0 || W <= 0 || N <= 0 || N % ddk::WBN) return 0;
-    return ((size_t)B * 8 * 16 + 16 + ddk::conv_wino_cluster_ws_floats(B, H, W, N)) * sizeof(float);
+    return (ddk::cl_front_floats(B) + ddk::conv_wino_cluster_ws_floats(B, H, W, N)) * sizeof(float);
 }
 /* a shape whose channel chunks are split over workgroups (ddk_conv_wino_splits() > 1) needs the pair counters and (splits - 1) slabs
  * of partial tiles behind that: the whole workspace in bytes, or 0 when the shape is not of that kind */
@@ -991,7 +991,7 @@ extern "C" int ddk_conv3x3_gn_mish_cluster(const float* src0, int c0, const floa
     DDK_REQUIRE(workspace_bytes >= (split_bytes ? split_bytes : plain_bytes) && aligned16(workspace), "conv3x3_gn_mish_cluster: workspace");
     float* ws = static_cast<float*>(workspace);
     // counters + the sticky give-up word behind them: zeroed per call here (a plan zeroes them once per forward / chain)
-    DDK_HIP(hipMemsetAsync(ws, 0, ((size_t)B * 8 * 16 + 16) * sizeof(float), as_stream(s)));
+    DDK_HIP(hipMemsetAsync(ws, 0, cl_front_floats(B) * sizeof(float), as_stream(s)));
     float* pairs = ws + plain_bytes / sizeof(float);
     if (split_bytes) DDK_HIP(hipMemsetAsync(pairs, 0, conv_wino_cluster_pair_words(B, H, W, N) * sizeof(float), as_stream(s)));
     ddk_conv_args a{};
@@ -1004,7 +1004,7 @@ extern "C" int ddk_conv3x3_gn_mish_cluster(const float* src0, int c0, const floa
     a.out = out;
     a.B = B; a.H = H; a.W = W; a.N = N;
     const ClWords w = cl_words(ws, B);
-    WinoGnFuse f{gamma, beta, temb, nullptr, temb_stride, eps, groups, ws + (size_t)B * 8 * 16 + 16, w.counters, w.fail};
+    WinoGnFuse f{gamma, beta, temb, nullptr, temb_stride, eps, groups, ws + cl_front_floats(B), w.counters, w.fail};
     if (split_bytes) {
         f.pairs = reinterpret_cast<unsigned*>(pairs);
         a.workspace = pairs + conv_wino_cluster_pair_words(B, H, W, N);

@@ -45,6 +45,7 @@ int ensure_device_init() {
 
 #ifdef DDK_HOST_SANITIZE
 // ---- state of the host-sanitizer build (host_sanitize.h)
+#include <cstdlib>
 #include <string>
 #include <vector>
 namespace ddk { namespace san {
@@ -75,9 +76,25 @@ bool near_arenas(uint64_t v) {
     return v + slack >= lo && v <= hi + slack;
 }
 void count_launch() { ++g_launches; }
+FILE* trace_file() {
+    static FILE* f = std::getenv("DDK_SAN_TRACE") ? std::fopen(std::getenv("DDK_SAN_TRACE"), "w") : nullptr;
+    return f;
+}
+bool trace_addr(FILE* f, uint64_t v) {
+    const Arena* hit = nullptr;                  // an arena's interior wins over another's one-past-the-end
+    for (const Arena& r : g_arenas)
+        if (v >= r.base && v <= r.base + r.bytes && (!hit || v < r.base + r.bytes)) hit = &r;
+    if (hit) std::fprintf(f, " [%s+%llu]", hit->name.c_str(), (unsigned long long)(v - hit->base));
+    return hit != nullptr;
+}
 }}  // namespace ddk::san
 extern "C" void ddk_san_register(const void* base, size_t bytes, const char* name) {
     ddk::san::g_arenas.push_back({reinterpret_cast<uintptr_t>(base), bytes, name ? name : ""});
+}
+extern "C" void ddk_san_unregister(const void* base) {     // the arena is about to be unmapped: its addresses may come back as another's
+    auto& v = ddk::san::g_arenas;
+    for (size_t i = v.size(); i-- > 0;)
+        if (v[i].base == reinterpret_cast<uintptr_t>(base)) { v.erase(v.begin() + (long)i); return; }
 }
 extern "C" void ddk_san_clear(void) { ddk::san::g_arenas.clear(); }
 extern "C" void ddk_san_stats(long* launches, long* errors) { *launches = ddk::san::g_launches; *errors = ddk::san::g_errors; }

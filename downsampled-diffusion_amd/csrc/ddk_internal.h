@@ -180,10 +180,19 @@ size_t conv_wino_cluster_ws_floats(int B, int H, int W, int N);
 unsigned conv_wino_cluster_timeouts();
 unsigned conv_first_cluster_timeouts();
 unsigned level_chain_cluster_timeouts();
-// the words of a cluster region `cl` (a plan's, or the front of a ddk_conv3x3_gn_mish_cluster workspace): [B][8 * 16] counters,
-// then the sticky give-up word on a line of its own
+// The cluster counter area `cl` of a plan's workspace (unet_plan.hip), in 4-byte words and in this order: [B][8 * 16] counters of the
+// in-launch GroupNorm (16 per (image, n tile), N <= 512: every layer re-arms the same words); one line for the workspace's sticky give-up
+// count (ddk_unet_cluster_check); [B][64] the level chain's arrival and departure counters, a 128-byte line per image each; CL_PAIR_WORDS
+// pair counters of the channel-chunk-split in-launch GroupNorm (<= 128 (m tile, n tile) pairs: 256 workgroups, >= 2 splits); the records.
+// A ddk_conv3x3_gn_mish_cluster workspace has the first two only: its records start at cl_front_floats().
+constexpr size_t CL_PAIR_WORDS = 128 * 16;
+inline size_t cl_fail_offset(int B) { return (size_t)B * 8 * 16; }
+inline size_t cl_front_floats(int B) { return cl_fail_offset(B) + 16; }
+inline size_t cl_chain_offset(int B) { return cl_front_floats(B); }
+inline size_t cl_pair_offset(int B) { return cl_chain_offset(B) + (size_t)B * 64; }
+inline size_t cl_counter_floats(int B) { return cl_pair_offset(B) + CL_PAIR_WORDS; }      // everything in front of a plan's records
 struct ClWords { unsigned* counters; unsigned* fail; };
-inline ClWords cl_words(float* cl, int B) { return {reinterpret_cast<unsigned*>(cl), reinterpret_cast<unsigned*>(cl + (size_t)B * 8 * 16)}; }
+inline ClWords cl_words(float* cl, int B) { return {reinterpret_cast<unsigned*>(cl), reinterpret_cast<unsigned*>(cl + cl_fail_offset(B))}; }
 // waits for `st`, then reads and clears a workspace's sticky give-up word: DDK_OK, or DDK_ERR_CLUSTER with the error
 // "<who>: <n> workgroup(s) gave up waiting for their cluster<tail>"
 int cluster_fail_check(unsigned* word, hipStream_t st, const char* who, const char* tail);

@@ -27,6 +27,10 @@ void fail(const char* fmt, ...);                       // counts an error, keeps
 bool inside(const void* p, size_t bytes);              // [p, p + bytes) lies in ONE registered arena
 bool near_arenas(uint64_t v);                          // v is within 1 GiB of the registered address range
 void count_launch();
+// opt-in launch trace: the environment variable DDK_SAN_TRACE names a file; every launch (and memset) writes one line to it, with
+// addresses as "[arena+offset]" (the arenas are mapped at varying addresses), so two builds' traces compare line for line
+FILE* trace_file();
+bool trace_addr(FILE* f, uint64_t v);                  // writes " [arena+offset]" if v lies in a registered arena
 
 inline void extent(const char* what, const void* p, long long bytes) {
     if (p && bytes > 0 && !inside(p, (size_t)bytes)) fail("%s: [%p, +%lld) leaves its arena", what, p, bytes);
@@ -49,6 +53,23 @@ void check_arg(const char* kernel, int idx, const T& v) {
     }
 }
 
+// an argument's bytes as 8-byte hex words (a shorter scalar or tail as one); a word that points into an arena is written as
+// "[arena+offset]", a stray address near the arenas (check_arg has flagged it) as "?": neither compares across runs otherwise
+template <class T>
+void trace_arg(FILE* f, const T& v) {
+    static_assert(std::is_trivially_copyable_v<T>, "kernel arguments are passed by value");
+    if (std::is_class_v<T>) std::fputs(" {", f);
+    for (size_t o = 0; o < sizeof(T); o += 8) {
+        const size_t n = sizeof(T) - o < 8 ? sizeof(T) - o : 8;
+        uint64_t w = 0;
+        std::memcpy(&w, reinterpret_cast<const unsigned char*>(&v) + o, n);
+        if (n == 8 && w != 0 && trace_addr(f, w)) continue;
+        if (n == 8 && w != 0 && near_arenas(w)) std::fputs(" ?", f);
+        else std::fprintf(f, " %llx", (unsigned long long)w);
+    }
+    if (std::is_class_v<T>) std::fputs(" }", f);
+}
+
 template <class... A>
 void launch(const char* kernel, dim3 grid, dim3 block, size_t lds, hipStream_t, const A&... args) {
     count_launch();
@@ -58,11 +79,17 @@ void launch(const char* kernel, dim3 grid, dim3 block, size_t lds, hipStream_t, 
     if (lds > 160u * 1024u) fail("%s: %zu bytes of dynamic LDS", kernel, lds);
     int idx = 0;
     (check_arg(kernel, idx++, args), ...);
+    if (FILE* f = trace_file()) {
+        std::fprintf(f, "%s <%u %u %u> <%u %u %u> lds %zu :", kernel, grid.x, grid.y, grid.z, block.x, block.y, block.z, lds);
+        (trace_arg(f, args), ...);
+        std::fputc('\n', f);
+    }
 }
 
 inline hipError_t memset_async(void* p, int v, size_t n) {
     if (!inside(p, n)) { fail("hipMemsetAsync: [%p, +%zu) leaves its arena", p, n); return hipSuccess; }
     std::memset(p, v, n);
+    if (FILE* f = trace_file()) { std::fputs("hipMemsetAsync :", f); trace_addr(f, reinterpret_cast<uint64_t>(p)); std::fprintf(f, " %d %zu\n", v, n); }
     return hipSuccess;
 }
 inline hipError_t memcpy_async(void* d, const void* s, size_t n, hipMemcpyKind kind) {

@@ -611,23 +611,13 @@ static bool convT_wino_use(int B, int H, int W, int cin, int N) {
 static bool use_wino(const ConvW& cw, int H, int W, int cin, int N) {
     return cw.has_wu && conv_wino_ok(DDK_CONV3X3_S1, H, W, cin, N);
 }
-static int conv3_splits(const ConvW& cw, int B, int H, int W, int cin, int N) {
-    return use_wino(cw, H, W, cin, N) ? conv_wino_splits(B, H, W, cin, N) : conv_splits(DDK_CONV3X3_S1, B, H, W, cin, N);
-}
 static size_t conv3_ws_floats(const ConvW& cw, int B, int H, int W, int cin, int N) {
     if (!use_wino(cw, H, W, cin, N)) return conv_workspace_bytes(DDK_CONV3X3_S1, B, H, W, cin, N) / 4;
     const int s = conv_wino_splits(B, H, W, cin, N);
     return s > 1 ? (size_t)s * B * H * W * N : 0;
 }
 
-// counters of the cluster GroupNorm: fixed place (16 words per (image, n tile), N <= 512) so every layer re-arms the same words
-// ... and behind them one line for the sticky give-up count of this workspace (ddk_unet_cluster_check)
-// ... and behind that the level chain's arrival and departure counters, one 128-byte line per image each
-// ... and the pair counters of the channel-chunk-split in-launch GroupNorm: <= 128 (m tile, n tile) pairs (256 workgroups, >= 2 splits)
-constexpr size_t CL_PAIR_WORDS = 128 * 16;
-static size_t cl_counter_floats(int B) { return (size_t)B * 8 * 16 + 16 + (size_t)B * 64 + CL_PAIR_WORDS; }
-static size_t cl_chain_offset(int B) { return (size_t)B * 8 * 16 + 16; }
-static size_t cl_pair_offset(int B) { return (size_t)B * 8 * 16 + 16 + (size_t)B * 64; }
+// (the cluster counter area in front of the records: cl_counter_floats() and its offsets, ddk_internal.h)
 constexpr int CHAIN_BUFS = 18;                // activations that cross workgroups inside the level chain, [B][16][256] each
 constexpr int CHAIN8_BUFS = 5;                // ... inside an 8x8 chain, [B][64][256] each
 
@@ -749,158 +739,167 @@ struct Ctx {
     int n_cluster = 0;            // cluster launches issued so far in this forward
     const float* x_first = nullptr;   // the network input, unpadded, and its padded copy: the first conv may take the small-C_in
     const float* x_padded = nullptr;  // kernel on maps the one-launch first block does not cover (run_conv_gn)
+
+    // The arguments of one conv of this forward: kind, sources, weight, its Winograd form where the shape takes it, bias, shape and the
+    // split-K workspace.  A site adds only what is special to it: resid, gn_partials, defer_reduce (whose slabs' reader adds the bias).
+    ddk_conv_args conv_args(int kind, const ConvW& cw, const float* src0, int c0, const float* src1, int c1, float* out, int H, int Wd, int N,
+                            const float* weight_override = nullptr) const {
+        ddk_conv_args a{};
+        a.kind = kind;
+        a.src0 = src0; a.src1 = src1; a.c0 = c0; a.c1 = c1;
+        a.weight = weight_override ? weight_override : P + cw.w;
+        a.bias = cw.has_bias ? P + cw.b : nullptr;
+        a.out = out;
+        a.B = B; a.H = H; a.W = Wd; a.N = N;
+        a.workspace = W + ly.off_splitk;
+        a.workspace_bytes = ly.splitk * sizeof(float);
+        if (kind == DDK_CONV3X3_S1 && !weight_override && use_wino(cw, H, Wd, c0 + c1, N)) a.weight_wino = P + cw.wu;
+        // (measured, B = 32: 128 ch 16 -> 32: 47.8 -> 28.0 us; 256 ch 8 -> 16 (2 slabs): 49.4 -> 37.0; 256 ch 4 -> 8 would need 8 slabs of one
+        //  chunk each and loses, 20.7 -> 21.9: the direct kernel keeps the maps that small)
+        if (kind == DDK_CONVT4X4_S2 && !weight_override && cw.has_wu && !src1 && convT_wino_use(B, H, Wd, c0, N)) a.weight_wino = P + cw.wu;
+        return a;
+    }
+    // GroupNorm + Mish (+ time shift, its rows) finished inside a conv's launch, exchanging through this workspace's cluster area
+    WinoGnFuse gn_fuse(const NormW& n, const float* temb_shift, const long long* rows) const {
+        float* cl = W + ly.off_cl;
+        const ClWords w = cl_words(cl, B);
+        return WinoGnFuse{P + n.g, P + n.b, temb_shift, rows, u.temb_total, GN_EPS, GROUPS, cl + cl_counter_floats(B), w.counters, w.fail};
+    }
 };
 
 static int run_conv(Ctx& c, int kind, const ConvW& cw, const float* src0, int c0, const float* src1, int c1, const float* resid,
                     float* out, int H, int W, int N, const float* weight_override = nullptr, const ConvLnFold* ln = nullptr) {
-    ddk_conv_args a{};
-    a.kind = kind;
-    a.src0 = src0; a.src1 = src1; a.c0 = c0; a.c1 = c1;
-    a.weight = weight_override ? weight_override : c.P + cw.w;
-    a.bias = cw.has_bias ? c.P + cw.b : nullptr;
+    ddk_conv_args a = c.conv_args(kind, cw, src0, c0, src1, c1, out, H, W, N, weight_override);
     a.resid = resid;
-    a.out = out;
-    a.B = c.B; a.H = H; a.W = W; a.N = N;
-    a.pre_mish = 0;
-    a.post_mish = 0;
-    a.defer_reduce = 0;
-    a.workspace = c.W + c.ly.off_splitk;
-    a.workspace_bytes = c.ly.splitk * sizeof(float);
-    if (kind == DDK_CONV3X3_S1 && !weight_override && use_wino(cw, H, W, c0 + c1, N)) a.weight_wino = c.P + cw.wu;
-    // (measured, B = 32: 128 ch 16 -> 32: 47.8 -> 28.0 us; 256 ch 8 -> 16 (2 slabs): 49.4 -> 37.0; 256 ch 4 -> 8 would need 8 slabs of one
-    //  chunk each and loses, 20.7 -> 21.9: the direct kernel keeps the maps that small)
-    if (kind == DDK_CONVT4X4_S2 && !weight_override && cw.has_wu && !src1 && convT_wino_use(c.B, H, W, c0, N)) a.weight_wino = c.P + cw.wu;
     return conv_forward(a, c.st, ln);
 }
+// ... leaving its `splits` split-K slabs in the workspace (`out` is not written) for a reader that sums them and adds the bias: `left`
+static int run_conv_slabs(Ctx& c, int kind, const ConvW& cw, const float* src0, int c0, const float* src1, int c1, float* out, int H, int W, int N,
+                          int splits, AddendSlabs& left) {
+    ddk_conv_args a = c.conv_args(kind, cw, src0, c0, src1, c1, out, H, W, N);
+    a.bias = nullptr;
+    a.defer_reduce = 1;
+    const int s = kind == DDK_CONV3X3_S2 ? 2 : 1;
+    left = AddendSlabs{splits, (long long)c.B * (H / s) * (W / s) * N, cw.has_bias ? c.P + cw.b : nullptr};
+    return conv_forward(a, c.st);
+}
+// ... as a one-pass Winograd conv whose epilogue leaves per-tile {mean, M2} in the GroupNorm area (shapes with conv_wino_stats_parts() > 0)
+static int run_conv_parts(Ctx& c, const ConvW& cw, const float* src0, int c0, const float* src1, int c1, float* raw, int H, int W, int N) {
+    ddk_conv_args a = c.conv_args(DDK_CONV3X3_S1, cw, src0, c0, src1, c1, raw, H, W, N);
+    a.gn_partials = c.W + c.ly.off_gn;
+    a.gn_groups = GROUPS;
+    return conv_forward(a, c.st);
+}
 
-// conv3x3 -> GroupNorm+Mish(+shift)(+residual).  When the conv splits k, its slabs stay in the workspace and the
-// GroupNorm kernel sums them (plus the conv bias) while loading: one kernel and one HBM round trip fewer.
-static bool conv_gn_is_local(const ConvW& cw, int B, int H, int W, int c0, int c1, int N) {
-    return (cw.has_wl && (H * W == 16 || (H * W == 4 && B % 4 == 0)) && conv_gn_local_ok(H, W, c0 + c1, c0, N, GROUPS)) ||
-           (cw.has_wwl && H * W == 64 && conv_gn_wlocal_ok(H, W, c0 + c1, c0, N, GROUPS));
+// conv3x3 -> GroupNorm + Mish (+ shift) (+ residual): the kernels it can run on, in the order of precedence classify_conv_gn tests them
+enum ConvGnPath {
+    CG_GENERIC,        // widths that are not multiples of 32: plain conv over the zero-padded weights, then GroupNorm over the REAL channels
+    CG_LOCAL,          // 4x4 maps (and 2x2 maps, four images to a block): one image x 32 channels per workgroup, k reduced inside it ->
+                       // statistics, Mish, shift and residual in the conv's own epilogue, no slabs, no GroupNorm launch (conv_local.hip)
+    CG_WLOCAL,         // 8x8 maps: the same image-local tiling in Winograd form
+    CG_FIRST,          // the network's first conv on a map too large for the one-launch first block (256x256: 512 statistics tiles per
+                       // image): the K = 9 C_in kernel on the unpadded input, not a 32-channel im2col conv (724 -> ~70 us at 8 x 256 x 256)
+    CG_CLUSTER,        // one launch: the workgroups of an image exchange their tile statistics and normalise their own tile in registers
+    CG_CLUSTER_SPLIT,  // ... on a shape whose channel chunks are split over workgroups (16x16 maps of 64-channel tiles at batch 32): a
+                       // tile's first workgroup sums its partners' partial tiles in the launch -- no slabs left, no GroupNorm launch
+    CG_PARTS,          // one-pass Winograd conv: its epilogue leaves per-tile {mean, M2}; GroupNorm then is a single streaming read + write
+    CG_SLABS,          // the conv splits k, the GroupNorm is register-resident: the slabs stay in the workspace and the GroupNorm kernel
+                       // sums them (plus the conv bias) while loading -- one kernel and one HBM round trip fewer
+    CG_PLAIN           // conv, then GroupNorm
+};
+struct ConvGnChoice {
+    ConvGnPath path = CG_PLAIN;
+    int np = 0;            // statistics tiles per image (CG_CLUSTER, CG_CLUSTER_SPLIT: the cluster's workgroups; CG_PARTS)
+    int cl_splits = 1;     // CG_CLUSTER_SPLIT: channel-chunk splits
+    int splits = 1;        // CG_SLABS, CG_PLAIN: split-K slabs
+    bool wino = false;     // past the image-local paths: the conv is a Winograd F(2x2,3x3) launch (what ddk_unet_flops_executed prices)
+    bool local() const { return path == CG_LOCAL || path == CG_WLOCAL; }
+};
+// No side effects.  first_input: the source is the padded copy of the network input (and the unpadded one is at hand).  cluster: an
+// in-launch GroupNorm may still be issued by this call -- the caller passes allow_cluster && n_cluster < cluster_limit and counts the
+// launch when a cluster path comes back.  (The ladder this replaces tested `n_cluster++ < cluster_limit` last in each cluster
+// condition; a count that has reached the limit can only fail that test, so not counting past the limit changes nothing.)
+// splitk_floats: the workspace's split-K area, which CG_CLUSTER_SPLIT's partial tiles must fit.
+static ConvGnChoice classify_conv_gn(const ddk_unet& u, const ConvW& cw, int B, int H, int W, int c0, int c1, int N, bool first_input,
+                                     bool cluster, size_t splitk_floats) {
+    ConvGnChoice k;
+    const int cin = c0 + c1;
+    auto is = [&](ConvGnPath p) { k.path = p; return k; };
+    if (u.generic) return is(CG_GENERIC);
+    if (cw.has_wl && (H * W == 16 || (H * W == 4 && B % 4 == 0)) && conv_gn_local_ok(H, W, cin, c0, N, GROUPS)) return is(CG_LOCAL);
+    if (cw.has_wwl && H * W == 64 && conv_gn_wlocal_ok(H, W, cin, c0, N, GROUPS)) return is(CG_WLOCAL);
+    k.wino = use_wino(cw, H, W, cin, N);
+    if (cw.has_wf && first_input && conv_first_ok(u.cfg.in_ch, N, H, W, GROUPS)) return is(CG_FIRST);
+    cluster = cluster && cw.has_wu && conv_wino_cluster_device_ok();
+    k.np = cluster ? conv_wino_cluster_np(B, H, W, cin, N, GROUPS) : 0;
+    if (k.np > 0 && k.np <= u.cluster_np_max) return is(CG_CLUSTER);
+    k.np = cluster && u.cluster_split ? conv_wino_cluster_split_np(B, H, W, cin, N, GROUPS, &k.cl_splits) : 0;
+    if (k.np > 0 && k.np <= u.cluster_np_max && (size_t)k.cl_splits * B * H * W * N <= splitk_floats &&
+        conv_wino_cluster_pair_words(B, H, W, N) <= CL_PAIR_WORDS)
+        return is(CG_CLUSTER_SPLIT);
+    k.np = cw.has_wu ? conv_wino_stats_parts(B, H, W, cin, N, GROUPS) : 0;
+    if (k.np > 0) return is(CG_PARTS);
+    k.splits = k.wino ? conv_wino_splits(B, H, W, cin, N) : conv_splits(DDK_CONV3X3_S1, B, H, W, cin, N);
+    return is(k.splits > 1 && groupnorm_workspace_bytes(B, H * W, N, GROUPS) == 0 ? CG_SLABS : CG_PLAIN);
+}
+static bool conv_gn_is_local(const ddk_unet& u, const ConvW& cw, int B, int H, int W, int c0, int c1, int N) {
+    return classify_conv_gn(u, cw, B, H, W, c0, c1, N, false, false, 0).local();
 }
 
 static int run_conv_gn(Ctx& c, const ConvW& cw, const float* src0, int c0, const float* src1, int c1, float* raw, const NormW& n,
                        const float* temb, const float* addend, float* out, int H, int W, int N, const AddendSlabs& as = AddendSlabs(),
                        const AddendSlabs& ss = AddendSlabs()) {
-    if (ss.n > 1 && !conv_gn_is_local(cw, c.B, H, W, c0, c1, N)) return fail_arg("run_conv_gn: slab source on a path that cannot sum it");
-    if (c.u.generic) {
-        // widths that are not multiples of 32: plain conv over the zero-padded weights, then GroupNorm over the REAL channels
-        if (as.n > 1 || ss.n > 1) return fail_arg("run_conv_gn: slab addend / source on the generic path");
-        DDK_TRY(run_conv(c, DDK_CONV3X3_S1, cw, src0, c0, src1, c1, nullptr, raw, H, W, N));
-        return groupnorm_mish_generic(raw, c.P + n.g, c.P + n.b, temb, c.u.temb_total, addend, out, c.B, H * W, N, n.c_real, GROUPS, GN_EPS,
-                                      c.st, c.temb_rows);
+    const ConvGnChoice k = classify_conv_gn(c.u, cw, c.B, H, W, c0, c1, N, c.x_first && src0 == c.x_padded && !src1,
+                                            c.allow_cluster && c.n_cluster < c.u.cluster_limit, c.ly.splitk);
+    if (ss.n > 1 && !k.local()) return fail_arg("run_conv_gn: slab source on a path that cannot sum it");
+    if (as.n > 1 && !k.local())
+        return fail_arg(k.path == CG_GENERIC ? "run_conv_gn: slab addend / source on the generic path"
+                                             : "run_conv_gn: slab addend on a path that cannot sum it");
+    const float* bias = cw.has_bias ? c.P + cw.b : nullptr;
+    const float *g = c.P + n.g, *b = c.P + n.b;
+    float* gnp = c.W + c.ly.off_gn;
+    switch (k.path) {
+        case CG_GENERIC:
+            DDK_TRY(run_conv(c, DDK_CONV3X3_S1, cw, src0, c0, src1, c1, nullptr, raw, H, W, N));
+            return groupnorm_mish_generic(raw, g, b, temb, c.u.temb_total, addend, out, c.B, H * W, N, n.c_real, GROUPS, GN_EPS, c.st, c.temb_rows);
+        case CG_LOCAL:
+        case CG_WLOCAL:
+            return (k.path == CG_LOCAL ? conv_gn_local : conv_gn_wlocal)(src0, c0, src1, c1, c.P + (k.path == CG_LOCAL ? cw.wl : cw.wwl), bias, g, b,
+                       temb, c.u.temb_total, c.temb_rows, addend, out, c.B, H, W, N, GROUPS, GN_EPS, c.st, as, ss);
+        case CG_FIRST:
+            DDK_TRY(conv_first(c.x_first, c.P + cw.wf, bias, raw, nullptr, c.B, H, W, c.u.cfg.in_ch, N, GROUPS, nullptr, nullptr, c.st));
+            break;
+        case CG_CLUSTER:
+        case CG_CLUSTER_SPLIT: {
+            ++c.n_cluster;
+            ddk_conv_args a = c.conv_args(DDK_CONV3X3_S1, cw, src0, c0, src1, c1, out, H, W, N);
+            a.resid = addend;
+            WinoGnFuse f = c.gn_fuse(n, temb, c.temb_rows);
+            if (k.path == CG_CLUSTER_SPLIT) f.pairs = reinterpret_cast<unsigned*>(c.W + c.ly.off_cl + cl_pair_offset(c.B));
+            return conv_forward(a, c.st, nullptr, &f);
+        }
+        case CG_PARTS:
+            DDK_TRY(run_conv_parts(c, cw, src0, c0, src1, c1, raw, H, W, N));
+            return groupnorm_mish_parts(raw, gnp, k.np, g, b, temb, c.u.temb_total, addend, out, c.B, H * W, N, GROUPS, GN_EPS, c.st, c.temb_rows);
+        case CG_SLABS: {
+            AddendSlabs sl;
+            DDK_TRY(run_conv_slabs(c, DDK_CONV3X3_S1, cw, src0, c0, src1, c1, raw, H, W, N, k.splits, sl));
+            return groupnorm_mish_ex(c.W + c.ly.off_splitk, sl.n, sl.stride, sl.bias, g, b, temb, c.u.temb_total, addend, out, c.B, H * W, N,
+                                     GROUPS, GN_EPS, nullptr, 0, c.st, c.temb_rows);
+        }
+        case CG_PLAIN:
+            DDK_TRY(run_conv(c, DDK_CONV3X3_S1, cw, src0, c0, src1, c1, nullptr, raw, H, W, N));
+            break;
     }
-    if (cw.has_wl && (H * W == 16 || (H * W == 4 && c.B % 4 == 0)) && conv_gn_local_ok(H, W, c0 + c1, c0, N, GROUPS))
-        // 4x4 maps (and 2x2 maps, four images to a block): one image x 32 channels per workgroup, k reduced inside it -> statistics, Mish, shift and residual in the
-        // conv's own epilogue, no slabs and no GroupNorm launch (conv_local.hip)
-        return conv_gn_local(src0, c0, src1, c1, c.P + cw.wl, cw.has_bias ? c.P + cw.b : nullptr, c.P + n.g, c.P + n.b, temb,
-                             c.u.temb_total, c.temb_rows, addend, out, c.B, H, W, N, GROUPS, GN_EPS, c.st, as, ss);
-    if (cw.has_wwl && H * W == 64 && conv_gn_wlocal_ok(H, W, c0 + c1, c0, N, GROUPS))
-        // 8x8 maps: the same image-local tiling in Winograd form
-        return conv_gn_wlocal(src0, c0, src1, c1, c.P + cw.wwl, cw.has_bias ? c.P + cw.b : nullptr, c.P + n.g, c.P + n.b, temb,
-                              c.u.temb_total, c.temb_rows, addend, out, c.B, H, W, N, GROUPS, GN_EPS, c.st, as, ss);
-    if (as.n > 1) return fail_arg("run_conv_gn: slab addend on a path that cannot sum it");
-    if (cw.has_wf && c.x_first && src0 == c.x_padded && !src1 && conv_first_ok(c.u.cfg.in_ch, N, H, W, GROUPS)) {
-        // the network's first conv on a map too large for the one-launch first block (256x256: 512 statistics tiles per image):
-        // still the K = 9 C_in kernel on the unpadded input instead of a 32-channel im2col conv (724 -> ~70 us at 8 x 256 x 256),
-        // followed by the generic GroupNorm
-        DDK_TRY(conv_first(c.x_first, c.P + cw.wf, cw.has_bias ? c.P + cw.b : nullptr, raw, nullptr, c.B, H, W, c.u.cfg.in_ch, N, GROUPS,
-                           nullptr, nullptr, c.st));
-        return groupnorm_mish(raw, c.P + n.g, c.P + n.b, temb, c.u.temb_total, addend, out, c.B, H * W, N, GROUPS, GN_EPS,
-                              c.W + c.ly.off_gn, c.ly.gn_ws * sizeof(float), c.st, c.temb_rows);
-    }
-    const int cl_np = c.allow_cluster && cw.has_wu && conv_wino_cluster_device_ok() ? conv_wino_cluster_np(c.B, H, W, c0 + c1, N, GROUPS) : 0;
-    if (cl_np > 0 && cl_np <= c.u.cluster_np_max && c.n_cluster++ < c.u.cluster_limit) {
-        // one launch: the workgroups of an image exchange their tile statistics and normalise their own tile in registers
-        ddk_conv_args a{};
-        a.kind = DDK_CONV3X3_S1;
-        a.src0 = src0; a.src1 = src1; a.c0 = c0; a.c1 = c1;
-        a.weight = c.P + cw.w;
-        a.weight_wino = c.P + cw.wu;
-        a.bias = cw.has_bias ? c.P + cw.b : nullptr;
-        a.resid = addend;
-        a.out = out;
-        a.B = c.B; a.H = H; a.W = W; a.N = N;
-        float* cl = c.W + c.ly.off_cl;
-        const ClWords w = cl_words(cl, c.B);
-        const WinoGnFuse f{c.P + n.g, c.P + n.b, temb, c.temb_rows, c.u.temb_total, GN_EPS, GROUPS, cl + cl_counter_floats(c.B), w.counters, w.fail};
-        return conv_forward(a, c.st, nullptr, &f);
-    }
-    int cls_splits = 1;
-    const int cls_np = c.allow_cluster && c.u.cluster_split && cw.has_wu && conv_wino_cluster_device_ok()
-                           ? conv_wino_cluster_split_np(c.B, H, W, c0 + c1, N, GROUPS, &cls_splits) : 0;
-    if (cls_np > 0 && cls_np <= c.u.cluster_np_max && (size_t)cls_splits * c.B * H * W * N <= c.ly.splitk &&
-        conv_wino_cluster_pair_words(c.B, H, W, N) <= CL_PAIR_WORDS && c.n_cluster++ < c.u.cluster_limit) {
-        // the same on a shape whose channel chunks are split over workgroups (16x16 maps of 64-channel tiles at batch 32): a tile's first
-        // workgroup sums its partners' partial tiles in the launch -- no slabs left for a GroupNorm launch to sum, no GroupNorm launch
-        ddk_conv_args a{};
-        a.kind = DDK_CONV3X3_S1;
-        a.src0 = src0; a.src1 = src1; a.c0 = c0; a.c1 = c1;
-        a.weight = c.P + cw.w;
-        a.weight_wino = c.P + cw.wu;
-        a.bias = cw.has_bias ? c.P + cw.b : nullptr;
-        a.resid = addend;
-        a.out = out;
-        a.B = c.B; a.H = H; a.W = W; a.N = N;
-        a.workspace = c.W + c.ly.off_splitk;
-        a.workspace_bytes = c.ly.splitk * sizeof(float);
-        float* cl = c.W + c.ly.off_cl;
-        const ClWords w = cl_words(cl, c.B);
-        WinoGnFuse f{c.P + n.g, c.P + n.b, temb, c.temb_rows, c.u.temb_total, GN_EPS, GROUPS, cl + cl_counter_floats(c.B), w.counters, w.fail};
-        f.pairs = reinterpret_cast<unsigned*>(cl + cl_pair_offset(c.B));
-        return conv_forward(a, c.st, nullptr, &f);
-    }
-    const int np = cw.has_wu ? conv_wino_stats_parts(c.B, H, W, c0 + c1, N, GROUPS) : 0;
-    if (np > 0) {
-        // one-pass Winograd conv: its epilogue leaves per-tile {mean, M2}; GroupNorm then is a single streaming read + write
-        ddk_conv_args a{};
-        a.kind = DDK_CONV3X3_S1;
-        a.src0 = src0; a.src1 = src1; a.c0 = c0; a.c1 = c1;
-        a.weight = c.P + cw.w;
-        a.weight_wino = c.P + cw.wu;
-        a.bias = cw.has_bias ? c.P + cw.b : nullptr;
-        a.out = raw;
-        a.B = c.B; a.H = H; a.W = W; a.N = N;
-        a.gn_partials = c.W + c.ly.off_gn;
-        a.gn_groups = GROUPS;
-        DDK_TRY(conv_forward(a, c.st));
-        return groupnorm_mish_parts(raw, c.W + c.ly.off_gn, np, c.P + n.g, c.P + n.b, temb, c.u.temb_total, addend, out, c.B, H * W, N,
-                                    GROUPS, GN_EPS, c.st, c.temb_rows);
-    }
-    const int splits = conv3_splits(cw, c.B, H, W, c0 + c1, N);
-    const bool resident = groupnorm_workspace_bytes(c.B, H * W, N, GROUPS) == 0;
-    if (splits > 1 && resident) {
-        ddk_conv_args a{};
-        a.kind = DDK_CONV3X3_S1;
-        a.src0 = src0; a.src1 = src1; a.c0 = c0; a.c1 = c1;
-        a.weight = c.P + cw.w;
-        if (use_wino(cw, H, W, c0 + c1, N)) a.weight_wino = c.P + cw.wu;
-        a.out = raw;  // unused: the slabs are the result
-        a.B = c.B; a.H = H; a.W = W; a.N = N;
-        a.defer_reduce = 1;
-        a.workspace = c.W + c.ly.off_splitk;
-        a.workspace_bytes = c.ly.splitk * sizeof(float);
-        DDK_TRY(conv_forward(a, c.st));
-        return groupnorm_mish_ex(c.W + c.ly.off_splitk, splits, (long long)c.B * H * W * N, cw.has_bias ? c.P + cw.b : nullptr,
-                                 c.P + n.g, c.P + n.b, temb, c.u.temb_total, addend, out, c.B, H * W, N, GROUPS, GN_EPS, nullptr, 0,
-                                 c.st, c.temb_rows);
-    }
-    DDK_TRY(run_conv(c, DDK_CONV3X3_S1, cw, src0, c0, src1, c1, nullptr, raw, H, W, N));
-    return groupnorm_mish(raw, c.P + n.g, c.P + n.b, temb, c.u.temb_total, addend, out, c.B, H * W, N, GROUPS, GN_EPS,
-                          c.W + c.ly.off_gn, c.ly.gn_ws * sizeof(float), c.st, c.temb_rows);
-}
-
-static int run_gn(Ctx& c, const float* x, const NormW& n, const float* temb, const float* addend, float* out, int HW, int C) {
-    return groupnorm_mish(x, c.P + n.g, c.P + n.b, temb, c.u.temb_total, addend, out, c.B, HW, C, GROUPS, GN_EPS,
-                          c.W + c.ly.off_gn, c.ly.gn_ws * sizeof(float), c.st, c.temb_rows);
+    return groupnorm_mish(raw, g, b, temb, c.u.temb_total, addend, out, c.B, H * W, N, GROUPS, GN_EPS, gnp, c.ly.gn_ws * sizeof(float), c.st,
+                          c.temb_rows);
 }
 
 // blocks.py:105-115 (eval): out = Mish(GN(conv2(Mish(GN(conv1(x))) + temb))) + res(x)
 // ss.n > 1 (res_takes_slab_source only): src0 is the split-K slab area the stride-2 conv in front left; both its readers -- the first
 // Block's staging loop and the second Block's residual -- sum the slabs (+ that conv's bias) in splitk_reduce_kernel's order
 static bool res_takes_slab_source(const ddk_unet& u, const ResW& r, int B, int H, int W, int c0) {
-    return !u.generic && !r.has_res && conv_gn_is_local(r.c1, B, H, W, c0, 0, r.co) && conv_gn_is_local(r.c2, B, H, W, r.co, 0, r.co);
+    return !u.generic && !r.has_res && conv_gn_is_local(u, r.c1, B, H, W, c0, 0, r.co) && conv_gn_is_local(u, r.c2, B, H, W, r.co, 0, r.co);
 }
 
 static int run_res(Ctx& c, const ResW& r, const float* src0, int c0, const float* src1, int c1, float* out, int H, int W,
@@ -917,24 +916,12 @@ static int run_res(Ctx& c, const ResW& r, const float* src0, int c0, const float
     }
     if (r.has_res) {
         const int rs = conv_splits(DDK_CONV1X1, c.B, H, W, c0 + c1, r.co);
-        if (rs > 1 && !conv1x1_sm_ok((long long)c.B * H * W, c0, c1, r.co) && conv_gn_is_local(r.c1, c.B, H, W, c0, c1, r.co) &&
-            conv_gn_is_local(r.c2, c.B, H, W, r.co, 0, r.co)) {
+        if (rs > 1 && !conv1x1_sm_ok((long long)c.B * H * W, c0, c1, r.co) && conv_gn_is_local(c.u, r.c1, c.B, H, W, c0, c1, r.co) &&
+            conv_gn_is_local(c.u, r.c2, c.B, H, W, r.co, 0, r.co)) {
             // neither Block conv touches the split-K workspace on these maps: the skip conv leaves its slabs there and the
             // second Block's epilogue sums them (+ bias) while it adds the residual -- no reduce launch
-            ddk_conv_args a{};
-            a.kind = DDK_CONV1X1;
-            a.src0 = src0; a.src1 = src1; a.c0 = c0; a.c1 = c1;
-            a.weight = c.P + r.res.w;
-            a.out = res;                      // unused: the slabs are the result
-            a.B = c.B; a.H = H; a.W = W; a.N = r.co;
-            a.defer_reduce = 1;
-            a.workspace = c.W + c.ly.off_splitk;
-            a.workspace_bytes = c.ly.splitk * sizeof(float);
-            DDK_TRY(conv_forward(a, c.st));
+            DDK_TRY(run_conv_slabs(c, DDK_CONV1X1, r.res, src0, c0, src1, c1, res, H, W, r.co, rs, as));
             addend = c.W + c.ly.off_splitk;
-            as.n = rs;
-            as.stride = (long long)c.B * H * W * r.co;
-            as.bias = r.res.has_bias ? c.P + r.res.b : nullptr;
         } else {
             DDK_TRY(run_conv(c, DDK_CONV1X1, r.res, src0, c0, src1, c1, nullptr, res, H, W, r.co));
             addend = res;
@@ -958,26 +945,14 @@ static int run_attn(Ctx& c, const AttnW& a, const float* x, float* out, int H, i
     float* ctx = c.W + c.ly.off_ctx;
     float* o = c.W + c.ly.off_o;
     const long long M = (long long)c.B * H * W;
-    if (c.u.generic) {
-        // LayerNorm over the real channels, then the plain projections over zero-padded weights
-        DDK_TRY(chan_layernorm_generic(x, c.P + a.ln.g, c.P + a.ln.b, xn, M, a.c, a.c_real, LN_EPS, c.st));
-        DDK_TRY(run_conv(c, DDK_CONV1X1, a.qkv, xn, a.c, nullptr, 0, nullptr, qkv, H, W, 3 * HIDDEN));
-        if (H * W <= 256) {
-            DDK_TRY(linattn_fused_small(qkv, ctx, o, c.B, H * W, HEADS, c.st));
-        } else {
-            DDK_TRY(linattn_context(qkv, ctx, c.B, H * W, HEADS, c.W + c.ly.off_splitk, c.ly.splitk * sizeof(float), c.st));
-            DDK_TRY(linattn_apply(qkv, ctx, o, c.B, H * W, HEADS, c.st));
-        }
-        return run_conv(c, DDK_CONV1X1, a.out, o, HIDDEN, nullptr, 0, x, out, H, W, a.c);
-    }
-    if (H * W <= 16 && a.c % 32 == 0 && linattn_small_qkv_ok(H * W, a.c)) {
+    if (!c.u.generic && H * W <= 16 && a.c % 32 == 0 && linattn_small_qkv_ok(H * W, a.c)) {
         // 4x4 maps: projection (LayerNorm folded), context and apply of one (image, head) in one workgroup -- no qkv tensor,
         // 14.6 us instead of 11.0 + 5.2.  (On 8x8 maps the projection is 4x the work on the same 128 workgroups -- half the
         // chip, one wave per SIMD: 25.5 us against 12.5 + 5.7 for the two launches, so those keep the im2col kernel.)
         DDK_TRY(linattn_small_qkv(x, c.P + a.qkv_op, c.P + a.ln_c1, c.P + a.ln_c2, LN_EPS, ctx, o, c.B, H * W, a.c, HEADS, c.st));
         return run_conv(c, DDK_CONV1X1, a.out, o, HIDDEN, nullptr, 0, x, out, H, W, a.c);
     }
-    if (attn_fold_eligible(c.u, a, c.B, H, W)) {
+    if (!c.u.generic && attn_fold_eligible(c.u, a, c.B, H, W)) {
         // q is linear in this attention: project k and v only, build the context, fold to_out . ctx^T . W_q (and the LayerNorm)
         // into one C x C matrix per image and apply it to x as a per-image 1x1 conv with the residual -- no q third of to_qkv, no
         // apply kernel, no separate to_out
@@ -1001,12 +976,14 @@ static int run_attn(Ctx& c, const AttnW& a, const float* x, float* out, int H, i
         const ConvLnFold lnA{a1, a2, LN_EPS};
         return conv1x1_ws(x, A, nullptr, x, out, M, a.c, &lnA, c.st, c.B);
     }
-    if (conv_ln_fold_ok(c.B, H, W, a.c, 3 * HIDDEN)) {
+    if (!c.u.generic && conv_ln_fold_ok(c.B, H, W, a.c, 3 * HIDDEN)) {
         // LayerNorm folded into the projection: no LayerNorm launch, no normalised copy of x
         const ConvLnFold ln{c.P + a.ln_c1, c.P + a.ln_c2, LN_EPS};
         DDK_TRY(run_conv(c, DDK_CONV1X1, a.qkv, x, a.c, nullptr, 0, nullptr, qkv, H, W, 3 * HIDDEN, c.P + a.qkv_lnw, &ln));
     } else {
-        DDK_TRY(chan_layernorm(x, c.P + a.ln.g, c.P + a.ln.b, xn, M, a.c, LN_EPS, c.st));
+        // (generic widths: LayerNorm over the real channels, then the plain projection over zero-padded weights)
+        DDK_TRY(c.u.generic ? chan_layernorm_generic(x, c.P + a.ln.g, c.P + a.ln.b, xn, M, a.c, a.c_real, LN_EPS, c.st)
+                            : chan_layernorm(x, c.P + a.ln.g, c.P + a.ln.b, xn, M, a.c, LN_EPS, c.st));
         DDK_TRY(run_conv(c, DDK_CONV1X1, a.qkv, xn, a.c, nullptr, 0, nullptr, qkv, H, W, 3 * HIDDEN));
     }
     if (H * W <= 256) {      // 16x16 and smaller: k, v, q of one (image, head) fit the LDS -- context, merge and apply in one launch
@@ -1024,12 +1001,10 @@ static int run_attn(Ctx& c, const AttnW& a, const float* x, float* out, int H, i
 // Levels as persistent launches (level_chain.hip; unet.py:83-101).  part 0: the last level whole -- downs[-1], mid, ups[0] -- on 4x4 maps:
 // `in` = the Downsample conv's output, `skip` receives the level's skip tensor (unet.py:87), `out` the up attention block's output.
 // part 1: downs[-2] on 8x8 maps (in -> skip).  part 2: ups[1] on 8x8 maps (cat(in, skip) -> out).
-static bool level_chain_use(const Ctx& c, int H0, int W0) {
-    return c.allow_cluster && (c.u.level_chain & 1) && c.B <= c.u.level_chain_max_batch && c.ly.chain > 0 && level_chain_shape_ok(c.u, H0, W0) &&
-           level_chain_device_ok();
-}
-static bool level8_chain_use(const Ctx& c, int H0, int W0, int bit) {
-    return c.allow_cluster && (c.u.level_chain & bit) && c.B <= c.u.level_chain_max_batch && c.ly.chain > 0 && level8_chain_shape_ok(c.u, H0, W0) && level_chain_device_ok();
+// bit of ddk_unet::level_chain: 1 = part 0, 2 = part 1, 4 = part 2
+static bool level_chain_use(const Ctx& c, int H0, int W0, int bit) {
+    return c.allow_cluster && (c.u.level_chain & bit) && c.B <= c.u.level_chain_max_batch && c.ly.chain > 0 &&
+           (bit == 1 ? level_chain_shape_ok(c.u, H0, W0) : level8_chain_shape_ok(c.u, H0, W0)) && level_chain_device_ok();
 }
 
 // down_src != null (part 0): `in` is not used -- the chain starts with the Downsample conv on the 8x8 map down_src (blocks.py:41-47);
@@ -1187,6 +1162,40 @@ static bool first_fast(const ddk_unet& u, int B, int H, int W) {
     return conv_wino_stats_parts(B, H, W, r.co, r.co, GROUPS) > 0;
 }
 
+// ... as launches, x the unpadded input.  fused: the first GroupNorm + Mish + shift inside conv_first's launch (the image's 8 tiles exchange
+// their statistics: no raw tensor, no GroupNorm-apply launch).  counter / t_cur (sampler): the step's bookkeeping rides on the first kernel.
+static int run_first_res(Ctx& c, const float* x, bool fused, int64_t* counter, int64_t* t_cur, float* out, int H, int W) {
+    const ResW& r = c.u.down_res[0];
+    const float* P = c.P;
+    float* raw = c.W + c.ly.off_raw;
+    float* a1 = c.W + c.ly.off_a1;
+    float* gnp = c.W + c.ly.off_gn;
+    const float* bias1 = r.c1.has_bias ? P + r.c1.b : nullptr;
+    const float* res_b = r.res.has_bias ? P + r.res.b : nullptr;
+    if (fused) {
+        const WinoGnFuse f = c.gn_fuse(r.n1, c.temb + r.temb_off, c.temb_rows);
+        DDK_TRY(conv_first_gn(x, P + r.c1.wf, bias1, f.gamma, f.beta, f.temb, f.temb_stride, f.temb_rows, f.eps, a1, c.B, H, W, r.ci, r.co,
+                              f.groups, f.records, f.counters, f.fail, counter, t_cur, c.st));
+    } else {
+        DDK_TRY(conv_first(x, P + r.c1.wf, bias1, raw, gnp, c.B, H, W, r.ci, r.co, GROUPS, counter, t_cur, c.st));
+        DDK_TRY(groupnorm_mish_parts(raw, gnp, H * W / 128, P + r.n1.g, P + r.n1.b, c.temb + r.temb_off, c.u.temb_total, nullptr, a1, c.B,
+                                     H * W, r.co, GROUPS, GN_EPS, c.st, c.temb_rows));
+    }
+    const int cl_np = c.allow_cluster && conv_wino_cluster_device_ok() && r.ci <= 8 ? conv_wino_cluster_np(c.B, H, W, r.co, r.co, GROUPS) : 0;
+    if (cl_np > 0 && cl_np <= c.u.cluster_np_max && conv_wino_variant_new(c.B, H, W, r.co) && c.n_cluster < c.u.cluster_limit) {
+        // GroupNorm + Mish + the 1x1 res_conv of the input finished in the second conv's own launch (in-launch exchange of the tile
+        // statistics; the epilogue evaluates the <= 8-channel 1x1 itself): no raw tensor, no GroupNorm-apply launch
+        ++c.n_cluster;                // (counted as in run_conv_gn: see classify_conv_gn)
+        const ddk_conv_args a = c.conv_args(DDK_CONV3X3_S1, r.c2, a1, r.co, nullptr, 0, out, H, W, r.co);
+        WinoGnFuse f = c.gn_fuse(r.n2, nullptr, nullptr);
+        f.res_x = x; f.res_w = P + r.res.w; f.res_b = res_b; f.res_cin = r.ci; f.res_ld = r.res.cin_pad;
+        return conv_forward(a, c.st, nullptr, &f);
+    }
+    DDK_TRY(run_conv_parts(c, r.c2, a1, r.co, nullptr, 0, raw, H, W, r.co));
+    return groupnorm_mish_parts(raw, gnp, conv_wino_stats_parts(c.B, H, W, r.co, r.co, GROUPS), P + r.n2.g, P + r.n2.b, nullptr, c.u.temb_total,
+                                nullptr, out, c.B, H * W, r.co, GROUPS, GN_EPS, c.st, nullptr, x, P + r.res.w, res_b, r.ci, r.res.cin_pad);
+}
+
 // x: NHWC input, unpadded ([B][H0][W0][in_ch]).
 // temb_table != nullptr (sampler): the per-block time shifts of EVERY timestep were computed once up front
 // (build_temb_table); row t[b] of the table is read directly by the GroupNorm kernels and no time kernel runs per step.
@@ -1234,11 +1243,11 @@ static int forward_core(const ddk_unet& u, const float* P, const float* x, int64
     const bool first_fused = fast0 && c.allow_cluster && u.first_gn && conv_wino_cluster_device_ok() &&
                              conv_first_gn_ok(u.down_res[0].ci, u.down_res[0].co, H0, W0, GROUPS) && u.cluster_limit > 0;
     int64_t* dec_counter = (first_fused && step) ? step->state : nullptr;
-    const bool chained = level_chain_use(c, H0, W0);    // the last level (4x4 maps) as one persistent launch
+    const bool chained = level_chain_use(c, H0, W0, 1); // the last level (4x4 maps) as one persistent launch
     const bool chain_edges = chained && (u.level_chain & 8) && u.L >= 2 && u.down_conv[u.L - 2].has_wl && u.down_conv[u.L - 2].has_bias &&
                              u.up_conv[0].has_wtl && u.up_conv[0].cin == 256 && u.down_conv[u.L - 2].cin == 256;
-    const bool chained8 = level8_chain_use(c, H0, W0, 2);   // the level above it (8x8 maps): downs[-2] as one launch,
-    const bool chained8u = level8_chain_use(c, H0, W0, 4);  // ups[1] as another
+    const bool chained8 = level_chain_use(c, H0, W0, 2);   // the level above it (8x8 maps): downs[-2] as one launch,
+    const bool chained8u = level_chain_use(c, H0, W0, 4);  // ups[1] as another
     for (int l = 0; l < u.L; ++l) {
         float* skip = ws + ly.off_skip[l];
         const int co = u.dimp[l + 1];
@@ -1254,48 +1263,7 @@ static int forward_core(const ddk_unet& u, const float* P, const float* x, int64
             // downs[-2] on 8x8 maps (2 ResnetBlocks + attention): 7 launches in one
             DDK_TRY(run_level_chain(c, 1, cur, skip, nullptr));
         } else if (l == 0 && fast0) {
-            const ResW& r = u.down_res[0];
-            if (first_fused) {
-                // round 6: the first Block's GroupNorm + Mish + shift inside the conv's launch (the image's 8 tiles exchange their statistics):
-                // no raw tensor, no GroupNorm-apply launch
-                float* cl = ws + ly.off_cl;
-                const ClWords w = cl_words(cl, B);
-                DDK_TRY(conv_first_gn(x, P + r.c1.wf, r.c1.has_bias ? P + r.c1.b : nullptr, P + r.n1.g, P + r.n1.b, c.temb + r.temb_off,
-                                      u.temb_total, c.temb_rows, GN_EPS, a1, B, H, W, r.ci, r.co, GROUPS, cl + cl_counter_floats(B),
-                                      w.counters, w.fail,
-                                      step ? step->state : nullptr, step ? t : nullptr, st));
-            } else {
-                DDK_TRY(conv_first(x, P + r.c1.wf, r.c1.has_bias ? P + r.c1.b : nullptr, raw, gnp, B, H, W, r.ci, r.co, GROUPS,
-                                   step ? step->state : nullptr, step ? t : nullptr, st));
-                DDK_TRY(groupnorm_mish_parts(raw, gnp, H * W / 128, P + r.n1.g, P + r.n1.b, c.temb + r.temb_off, u.temb_total, nullptr, a1, B,
-                                             H * W, r.co, GROUPS, GN_EPS, st, c.temb_rows));
-            }
-            ddk_conv_args a{};
-            a.kind = DDK_CONV3X3_S1;
-            a.src0 = a1; a.c0 = r.co;
-            a.weight = P + r.c2.w;
-            a.weight_wino = P + r.c2.wu;
-            a.bias = r.c2.has_bias ? P + r.c2.b : nullptr;
-            a.B = B; a.H = H; a.W = W; a.N = r.co;
-            const int cl_np = c.allow_cluster && conv_wino_cluster_device_ok() && r.ci <= 8 ? conv_wino_cluster_np(B, H, W, r.co, r.co, GROUPS) : 0;
-            if (cl_np > 0 && cl_np <= u.cluster_np_max && conv_wino_variant_new(B, H, W, r.co) && c.n_cluster++ < u.cluster_limit) {
-                // round 4: GroupNorm + Mish + the 1x1 res_conv of the input finished in the conv's own launch (in-launch exchange of the
-                // tile statistics; the epilogue evaluates the <= 8-channel 1x1 itself): no raw tensor, no GroupNorm-apply launch
-                a.out = bufB;
-                float* cl = ws + ly.off_cl;
-                const ClWords w = cl_words(cl, B);
-                WinoGnFuse f{P + r.n2.g, P + r.n2.b, nullptr, nullptr, u.temb_total, GN_EPS, GROUPS, cl + cl_counter_floats(B), w.counters, w.fail};
-                f.res_x = x; f.res_w = P + r.res.w; f.res_b = r.res.has_bias ? P + r.res.b : nullptr; f.res_cin = r.ci; f.res_ld = r.res.cin_pad;
-                DDK_TRY(conv_forward(a, st, nullptr, &f));
-            } else {
-                a.out = raw;
-                a.gn_partials = gnp;
-                a.gn_groups = GROUPS;
-                DDK_TRY(conv_forward(a, st));
-                DDK_TRY(groupnorm_mish_parts(raw, gnp, conv_wino_stats_parts(B, H, W, r.co, r.co, GROUPS), P + r.n2.g, P + r.n2.b, nullptr,
-                                             u.temb_total, nullptr, bufB, B, H * W, r.co, GROUPS, GN_EPS, st, nullptr, x, P + r.res.w,
-                                             r.res.has_bias ? P + r.res.b : nullptr, r.ci, r.res.cin_pad));
-            }
+            DDK_TRY(run_first_res(c, x, first_fused, step ? step->state : nullptr, step ? t : nullptr, bufB, H, W));
         } else {
             DDK_TRY(run_res(c, u.down_res[2 * l], cur, cur_c, nullptr, 0, bufB, H, W, cur_ss));
             cur_ss = AddendSlabs();
@@ -1313,19 +1281,7 @@ static int forward_core(const ddk_unet& u, const float* P, const float* x, int64
                 res_takes_slab_source(u, u.down_res[2 * l + 2], B, H / 2, W / 2, co)) {
                 // the Downsample conv splits k and the ResnetBlock behind it is image-local (8x8 / 4x4 maps, no skip conv): the conv leaves
                 // its slabs in the split-K area and that block's two readers sum them -- no reduce launch, no reduced tensor
-                ddk_conv_args a{};
-                a.kind = DDK_CONV3X3_S2;
-                a.src0 = skip; a.c0 = co;
-                a.weight = P + u.down_conv[l].w;
-                a.out = bufA;                 // unused: the slabs are the result
-                a.B = B; a.H = H; a.W = W; a.N = co;
-                a.defer_reduce = 1;
-                a.workspace = ws + ly.off_splitk;
-                a.workspace_bytes = ly.splitk * sizeof(float);
-                DDK_TRY(conv_forward(a, st));
-                cur_ss.n = s2;
-                cur_ss.stride = (long long)B * (H / 2) * (W / 2) * co;
-                cur_ss.bias = u.down_conv[l].has_bias ? P + u.down_conv[l].b : nullptr;
+                DDK_TRY(run_conv_slabs(c, DDK_CONV3X3_S2, u.down_conv[l], skip, co, nullptr, 0, bufA, H, W, co, s2, cur_ss));
                 H /= 2; W /= 2;
                 cur = ws + ly.off_splitk;
             } else {
@@ -1376,17 +1332,7 @@ static int forward_core(const ddk_unet& u, const float* P, const float* x, int64
     const int npf = fused_tail_parts(u, B, H, W, cur_c, rule.kind);
     if (npf > 0 && (!step || step->per == (long long)H * W * n_out)) {
         // one-pass Winograd conv with statistics, then GroupNorm + Mish + projection (+ the rule) in ONE launch
-        ddk_conv_args a{};
-        a.kind = DDK_CONV3X3_S1;
-        a.src0 = cur; a.c0 = cur_c;
-        a.weight = P + u.final_conv.w;
-        a.weight_wino = P + u.final_conv.wu;
-        a.bias = u.final_conv.has_bias ? P + u.final_conv.b : nullptr;
-        a.out = raw;
-        a.B = B; a.H = H; a.W = W; a.N = chan;
-        a.gn_partials = gnp;
-        a.gn_groups = GROUPS;
-        DDK_TRY(conv_forward(a, st));
+        DDK_TRY(run_conv_parts(c, u.final_conv, cur, cur_c, nullptr, 0, raw, H, W, chan));
         const TailIn in{raw, gnp, npf, P + u.final_norm.g, P + u.final_norm.b, GN_EPS, P + u.final_w, P + u.final_b, n_out, B, H * W, chan, GROUPS};
         return final_tail(in, rule, t, hooks, st);
     }
@@ -1488,12 +1434,12 @@ extern "C" double ddk_unet_flops(const ddk_unet* u, int B, int H0, int W0) {
 extern "C" double ddk_unet_flops_executed(const ddk_unet* u, int B, int H0, int W0) {
     if (check_shape(u, B, H0, W0) != DDK_OK) return 0;
     double f = 0;
-    auto conv3 = [&](const ConvW& cw, int H, int W, int c0, int c1, int N, bool gn) {
+    auto conv3 = [&](const ConvW& cw, int H, int W, int c0, int c1, int N) {
+        // by the path run_conv_gn takes (the cluster paths are Winograd launches like the ones they replace: same price)
+        const ConvGnChoice k = classify_conv_gn(*u, cw, B, H, W, c0, c1, N, false, false, 0);
         const int cin = c0 + c1;
-        if (gn && cw.has_wl && (H * W == 16 || (H * W == 4 && B % 4 == 0)) && conv_gn_local_ok(H, W, cin, c0, N, GROUPS))
-            return 2.0 * B * H * W * 9.0 * cin * N;
-        if (gn && cw.has_wwl && H * W == 64 && conv_gn_wlocal_ok(H, W, cin, c0, N, GROUPS)) return 2.0 * B * (H * W / 4) * 16.0 * cin * N;
-        if (use_wino(cw, H, W, cin, N)) return 2.0 * (double)(ceil_div((long long)B * (H / 2) * (W / 2), 32) * 32) * 16.0 * cin * N;
+        if (k.path == CG_WLOCAL) return 2.0 * B * (H * W / 4) * 16.0 * cin * N;
+        if (k.wino) return 2.0 * (double)(ceil_div((long long)B * (H / 2) * (W / 2), 32) * 32) * 16.0 * cin * N;
         return 2.0 * B * H * W * 9.0 * cin * N;
     };
     auto res = [&](const ResW& r, int H, int W, int c0, int c1, bool fast) {
@@ -1501,10 +1447,10 @@ extern "C" double ddk_unet_flops_executed(const ddk_unet* u, int B, int H0, int 
             f += 2.0 * B * H * W * (2.0 * ((9 * r.ci + 1) / 2)) * r.co;        // conv_first: K = 9 * C_in rounded up to even
             f += 2.0 * B * H * W * (double)r.ci * r.co;                        // res_conv inside the GroupNorm launch (FMA)
         } else {
-            f += conv3(r.c1, H, W, c0, c1, r.co, true);
+            f += conv3(r.c1, H, W, c0, c1, r.co);
             if (r.has_res) f += conv_flops(DDK_CONV1X1, B, H, W, c0 + c1, r.co);
         }
-        f += conv3(r.c2, H, W, r.co, 0, r.co, true);
+        f += conv3(r.c2, H, W, r.co, 0, r.co);
     };
     auto attn = [&](const AttnW& a, int H, int W) {
         if (attn_fold_eligible(*u, a, B, H, W)) {
@@ -1538,7 +1484,7 @@ extern "C" double ddk_unet_flops_executed(const ddk_unet* u, int B, int H0, int 
         H *= 2; W *= 2;
         cur_c = din;
     }
-    f += conv3(u->final_conv, H, W, cur_c, 0, u->cfg.chan, true) + 2.0 * B * H * W * (double)u->cfg.chan * u->cfg.in_ch;
+    f += conv3(u->final_conv, H, W, cur_c, 0, u->cfg.chan) + 2.0 * B * H * W * (double)u->cfg.chan * u->cfg.in_ch;
     return f;
 }
 

@@ -3,7 +3,9 @@
 // geometry and that every pointer it would hand to the device lies inside an arena registered here.  For each BASELINE.json
 // configuration (reference models/unet/unet.py:19-72 shapes): create the plan, pack every slot, run one ddk_unet_forward, a
 // three-step eager ddk_sampler_run, a respaced ddk_sampler_run_spaced, a three-step ddk_sampler_run_multistep, three ops of
-// ddk_sampler_run_inpaint and a T = 3 ddk_vlb_sweep_run, and check the size queries against the arenas they size.
+// ddk_sampler_run_inpaint and a T = 3 ddk_vlb_sweep_run, and check the size queries against the arenas they size.  Each configuration
+// also prints its exact workspace sizes and FLOP counts; with DDK_SAN_TRACE=<file> every launch is written there (host_sanitize.h), so
+// a change to the plan's host code can be compared against its parent line for line.
 #include <sys/mman.h>
 
 #include <cstdio>
@@ -15,6 +17,7 @@
 #include "ddk.h"
 
 extern "C" void ddk_san_register(const void* base, size_t bytes, const char* name);
+extern "C" void ddk_san_unregister(const void* base);
 extern "C" void ddk_san_clear(void);
 extern "C" void ddk_san_stats(long* launches, long* errors);
 extern "C" const char* ddk_san_first_error(void);
@@ -28,7 +31,7 @@ struct Arena {
         if (p == MAP_FAILED) { std::perror("mmap"); std::exit(2); }
         ddk_san_register(p, bytes, name);
     }
-    ~Arena() { munmap(p, bytes); }
+    ~Arena() { ddk_san_unregister(p); munmap(p, bytes); }
     float* f() const { return static_cast<float*>(p); }
 };
 
@@ -137,13 +140,15 @@ static void walk(const char* name, int in_ch, int chan, std::vector<int> mults, 
         v.workspace_bytes = vsw_bytes - 4;
         CHECK(ddk_vlb_sweep_run(&v, nullptr) == DDK_ERR_WORKSPACE, "%s: short sweep workspace accepted", name);
     }
-    CHECK(ddk_unet_flops(u, B, H, W) > 0 && ddk_unet_flops_executed(u, B, H, W) > 0, "%s: flops", name);
+    const double flops = ddk_unet_flops(u, B, H, W), flops_exec = ddk_unet_flops_executed(u, B, H, W);
+    CHECK(flops > 0 && flops_exec > 0, "%s: flops", name);
     CHECK(ddk_unet_workspace_bytes(u, B, H + 1, W) == 0, "%s: indivisible map accepted", name);
     ddk_unet_destroy(u);
     long launches = 0, errors = 0;
     ddk_san_stats(&launches, &errors);
     std::printf("%-34s packed %8.1f MB  workspace %9.1f MB  sampler %9.1f MB  launches so far %ld  errors %ld\n", name, packed_bytes / 1e6,
                 ws_bytes / 1e6, smp_bytes / 1e6, launches, errors);
+    std::printf("%-34s workspace %zu B  sampler %zu B  flops %.17g  executed %.17g\n", name, ws_bytes, smp_bytes, flops, flops_exec);
 }
 
 // The training-side entry points added in round 4 (job-table launches, deferred reduces, the 32-channel and small-map conv kernels):
