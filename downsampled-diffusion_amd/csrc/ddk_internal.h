@@ -313,6 +313,12 @@ struct InpaintOps {
 };
 constexpr uint32_t INPAINT_Z2_BIT = 0x40000000u;   // Philox stream of the known region's draw: stream_id | this
 constexpr uint32_t INPAINT_Z3_BIT = 0x20000000u;   // ... and of the jump's: stream_id | this (so stream_id < 2^29)
+// zero-shot super-resolution (DDNM for A = n x n average pooling): the low-resolution image and the block
+struct RestoreOps {
+    const float* y;               // NHWC [B][H/n][W/n][n_out]: what the n x n block means of x0 are set to
+    int n;                        // 2, 4 or 8, dividing H and W
+    int H, W;                     // the map the blocks lie in (filled by the chain entry / the lone op; the other kinds need only `per`)
+};
 // likelihood sweep (ddk_vlb_sweep_run): one step's operands besides the UNet's
 struct VlbStep {
     const float* x;               // clean sample, NHWC [B][H][W][n_out]
@@ -333,6 +339,7 @@ enum class StepKind {
     Ancestral,    // x <- p_step(x, eps_hat, z): tables c_recip .. sigma; z = injected noise or Philox; eps_out optional
     Multistep,    // DPM-Solver++(2M): x <- (c1 x0 + c2 x) + c3 x0_hist, x0_hist <- x0: c_recip .. c2, c3, x0_hist; no draw
     Inpaint,      // RePaint: Ancestral's op, then x = mask ? x_kn : x, then the optional jump: c_recip .. sigma, inp; Philox only
+    Restore,      // DDNM super-resolution: Ancestral's x0 shifted so its n x n block means equal y, then the update: c_recip .. sigma, rst; Philox only
     Vlb           // likelihood sweep: no update, the step's VLB terms to vlb->partials (vlb_rule() fills the rest from *vlb)
 };
 struct StepRule {
@@ -347,6 +354,7 @@ struct StepRule {
     const float* c3;
     InpaintOps inp;
     const VlbStep* vlb;           // host side only
+    RestoreOps rst;
 };
 inline StepRule vlb_rule(const VlbStep& v) {
     StepRule r{};
@@ -363,7 +371,7 @@ struct ChainHooks {
     uint64_t seed;                // without chain_state
     uint32_t stream_id;
 };
-// the unfused tail's last kernel, given eps_hat in memory: the rule's update of x (Ancestral, Multistep, Inpaint) or the sweep's
+// the unfused tail's last kernel, given eps_hat in memory: the rule's update of x (Ancestral, Multistep, Inpaint, Restore) or the sweep's
 // reduction of the step's terms (Vlb); `who` names the caller in messages
 int p_update(const StepRule& r, const float* eps_hat, const int64_t* t, int B, long long per, const ChainHooks& h, hipStream_t st,
              const char* who = "p_update");
@@ -383,9 +391,11 @@ struct TailIn {
     const float* bias;            // [n_out] or null
     int n_out, B, HW, C, groups;
 };
-// the shapes the fused tail takes: C in {32,64,128,256}; the Multistep, Inpaint and Vlb instantiations stop at C = 128 (at 256 the
-// plain one spills already, and theirs hold more in the prologue)
-bool final_tail_ok(int HW, int C, int groups, int n_out, int np, StepKind kind);
+// the shapes the fused tail takes: C in {32,64,128,256}; the Multistep, Inpaint, Restore and Vlb instantiations stop at C = 128 (at
+// 256 the plain one spills already, and theirs hold more in the prologue).  Restore also needs every 128-pixel tile to hold whole
+// rows of blocks, 128 % (W n) == 0 with W, n = restore_w, restore_n (W = 32: n <= 4; W = 16: n <= 8; W = 64: n = 2); the other
+// kinds ignore the two.  The one predicate of fused_tail_parts (unet_plan.hip) and final_tail.
+bool final_tail_ok(int HW, int C, int groups, int n_out, int np, StepKind kind, int restore_w = 0, int restore_n = 0);
 int final_tail(const TailIn& in, const StepRule& r, const int64_t* t, const ChainHooks& h, hipStream_t st);
 
 }  // namespace ddk

@@ -9,6 +9,8 @@
 // same eps_hat and noise the update is bit-identical to the torch expression.
 #include "ddk_internal.h"
 
+#include <climits>
+
 // hipcc contracts a*b+c into an FMA by default (-ffp-contract=fast), even through __fmul_rn/__fadd_rn; the
 // schedule arithmetic below must round every product like the reference's separate torch ops do, so this
 // file is compiled with -ffp-contract=off (see Makefile).
@@ -191,6 +193,75 @@ __global__ __launch_bounds__(256) void p_update_kernel(const StepRule r, const f
     }
 }
 
+// DDNM super-resolution (Wang, Yu, Zhang, ICLR 2023, Algorithm 1) for A = n x n average pooling, A+ = n x n
+// replication (A A+ = I): the clipped x0 of p_step, shifted by its block's y - mean(x0) (x0' = x0 - A+ A x0 + A+ y, not re-clamped),
+// then p_step's posterior mean and draw on x0'.  At row 0 (c1 = 1, c2 = 0, no draw) the result is x0', whose block means equal y up to
+// fp32 rounding.  rst_x0, rst_block_mean and rst_finish are the arithmetic of both tails, every operation rounded on its own and the
+// block summed in row-major order, so given the same eps_hat the tails are bit-identical.
+__device__ __forceinline__ float rst_x0(float x, float e, float cr, float crm1) {
+    const float x0 = __fsub_rn(__fmul_rn(cr, x), __fmul_rn(crm1, e));     // as p_step
+    return fminf(fmaxf(x0, -1.0f), 1.0f);
+}
+
+// x0_at(i, j): the clipped x0 at row i, column j of the element's block (same image, same channel)
+template <class F>
+__device__ __forceinline__ float rst_block_mean(F&& x0_at, int n) {
+    float s = 0.0f;
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) s = __fadd_rn(s, x0_at(i, j));
+    return __fmul_rn(s, 1.0f / (float)(n * n));                           // n a power of two: exact
+}
+
+__device__ __forceinline__ float rst_finish(float x, float x0, float m, float y, float z, float c1, float c2, float sg) {
+    const float x0p = __fadd_rn(x0, __fsub_rn(y, m));
+    const float mean = __fadd_rn(__fmul_rn(c1, x0p), __fmul_rn(c2, x));
+    return __fadd_rn(mean, __fmul_rn(sg, z));
+}
+
+__device__ __forceinline__ float comp4(float4 v, int k) { return k == 0 ? v.x : k == 1 ? v.y : k == 2 ? v.z : v.w; }
+
+// The last kernel of an unfused Restore step.  p_update_kernel's flat float4 loop cannot see an element's neighbours, so here a
+// thread owns one (image, block, channel): it sums the block's n x n clipped x0 from x and eps_hat, then updates those n x n
+// elements of x in place (nobody else reads them).  Any n_out, any H, W that n divides.  Element e of the NHWC latent takes
+// component e & 3 of the Philox draw of float4 e >> 2, the Ancestral kind's keying; the counter and the key as in p_update_kernel.
+__global__ __launch_bounds__(256) void p_update_restore_kernel(const StepRule r, const float* __restrict__ eps_hat,
+                                                               const int64_t* __restrict__ t, int B, int n_out, uint64_t seed,
+                                                               uint32_t stream, const int64_t* __restrict__ chain_state,
+                                                               int64_t* dec_counter) {
+    if (dec_counter && blockIdx.x == 0 && threadIdx.x == 0) *dec_counter -= 1;
+    if (chain_state) {
+        seed = (uint64_t)chain_state[1];
+        stream = (uint32_t)chain_state[2];
+    }
+    const int n = r.rst.n, H = r.rst.H, W = r.rst.W, Hn = H / n, Wn = W / n;
+    const long long total = (long long)B * Hn * Wn * n_out;
+    float* __restrict__ x = r.x;
+    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const int c = (int)(i % n_out);
+        long long q = i / n_out;
+        const int bc = (int)(q % Wn);
+        q /= Wn;
+        const int br = (int)(q % Hn), b = (int)(q / Hn);
+        const int64_t tb = t[b];
+        const float cr = r.c_recip[tb], crm1 = r.c_recipm1[tb], a1 = r.c1[tb], a2 = r.c2[tb], sg = tb > 0 ? r.sigma[tb] : 0.0f;
+        const long long e0 = (((long long)b * H + br * n) * W + bc * n) * n_out + c;       // the block's first element
+        const float m = rst_block_mean(
+            [&](int bi, int bj) {
+                const long long e = e0 + ((long long)bi * W + bj) * n_out;
+                return rst_x0(x[e], eps_hat[e], cr, crm1);
+            },
+            n);
+        const float yv = r.rst.y[i];                                      // y is [B][H/n][W/n][n_out]: this thread's index
+        for (int bi = 0; bi < n; ++bi)
+            for (int bj = 0; bj < n; ++bj) {
+                const long long e = e0 + ((long long)bi * W + bj) * n_out;
+                const float xv = x[e];
+                const float z = comp4(philox_normal4((unsigned long long)(e >> 2), (uint32_t)tb, stream, seed), (int)(e & 3));
+                x[e] = rst_finish(xv, rst_x0(xv, eps_hat[e], cr, crm1), m, yv, z, a1, a2, sg);
+            }
+    }
+}
+
 // ---- the VLB term of one element (reference models/diffusion/ddpm.py:317-366, models/utils/losses.py:17-109) --------------------
 // Shared by vlb_terms_kernel and the likelihood sweep's epilogues (final_tail_kernel<.., StepKind::Vlb>, vlb_sweep_terms_kernel).
 __device__ __forceinline__ float std_normal_cdf_approx(float v) {
@@ -270,6 +341,8 @@ struct TailParams {
     const float* c3;
     // StepKind::Inpaint: the known latent, its mask and the per-row tables
     InpaintOps inp;
+    // StepKind::Restore: the low-resolution image, the block and the map's height and width
+    RestoreOps rst;
 };
 
 // K says how the launch ends (StepRule).  Eps and Ancestral are ONE instantiation, <.., StepKind::Ancestral>: eps_hat out and / or
@@ -281,10 +354,14 @@ struct TailParams {
 // where the other kinds draw their noise (no Philox rounds), and the thread that read it writes it back.
 // Inpaint (ddk_sampler_run_inpaint, x given, Philox only): RePaint's op of p_update_kernel; the known float4, the mask float4 and
 // the two extra draws are requested in the same prologue, and x_kn is formed there (4 registers live, not 8).
+// Restore (ddk_sampler_run_restore, x given, Philox only, 128 % (W n) == 0 so that the tile holds whole rows of blocks): the y of
+// each of the thread's four elements is requested in the prologue; in phase 2 the owners write their clipped x0 over eps_hat in LDS,
+// and one barrier later every owner sums its elements' blocks from LDS (rst_block_mean) and finishes the update of
+// p_update_restore_kernel: neither x0 nor eps_hat goes through memory.
 template <int LPP, int VPL, StepKind K>
 __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
     static_assert(K != StepKind::Eps, "the plain forward runs the Ancestral instantiation with p.x null");
-    constexpr bool VLB = K == StepKind::Vlb, MS = K == StepKind::Multistep, INP = K == StepKind::Inpaint;
+    constexpr bool VLB = K == StepKind::Vlb, MS = K == StepKind::Multistep, INP = K == StepKind::Inpaint, RST = K == StepKind::Restore;
     constexpr int PPW = 64 / LPP;                    // pixels per wave and iteration
     constexpr int PPI = 16 * PPW;                    // ... per iteration of the 16-wave workgroup
     constexpr int NIT = 128 / PPI;                   // 4 at C = 128 / 256, 2 at C = 64, 1 at C = 32
@@ -330,6 +407,7 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
     float4 xk0 = xv0, mk0 = xv0, z30 = xv0;           // INP: x_kn, the mask, the jump's draw
     float ja = 0.f, jb = 0.f;
     bool jump = false;
+    float yv0[4] = {0.f, 0.f, 0.f, 0.f};              // RST: y of the block of each of the thread's four elements
     VlbCoef kc{};
     if ((VLB || p.x) && tid < cnt4) {
         const uint64_t seed = p.chain_state ? (uint64_t)p.chain_state[1] : p.seed;
@@ -356,6 +434,15 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
             xk0 = inp_known4(reinterpret_cast<const float4*>(p.inp.known)[i],
                              philox_normal4((unsigned long long)i, (uint32_t)tb, stream | INPAINT_Z2_BIT, seed), ka, kb);
             if (jump) z30 = philox_normal4((unsigned long long)i, (uint32_t)tb, stream | INPAINT_Z3_BIT, seed);
+        }
+        if constexpr (RST) {
+            const int W = p.rst.W, n = p.rst.n, Wn = W / n;
+            const long long yrow0 = ((long long)b * p.HW + tile * 128) / (W * n);     // the tile's first row of blocks, over all images
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int lp = (tid * 4 + j) / p.n_out, c = tid * 4 + j - lp * p.n_out, row = lp / W, col = lp - row * W;
+                yv0[j] = p.rst.y[((yrow0 + row / n) * Wn + col / n) * p.n_out + c];
+            }
         }
     }
     __syncthreads();
@@ -428,6 +515,31 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
         if (tid == 0) p.vlb_part[((long long)tb * p.B + b) * p.np + tile] = make_float2(acc, sq);
         return;
     }
+    if constexpr (RST) {
+        float x0v[4] = {0.f, 0.f, 0.f, 0.f};
+        if (tid < cnt4) {
+            const float4 ev = reinterpret_cast<const float4*>(es)[tid];
+            if (p.eps_out) reinterpret_cast<float4*>(p.eps_out)[e4 + tid] = ev;
+            x0v[0] = rst_x0(xv0.x, ev.x, cr, crm1); x0v[1] = rst_x0(xv0.y, ev.y, cr, crm1);
+            x0v[2] = rst_x0(xv0.z, ev.z, cr, crm1); x0v[3] = rst_x0(xv0.w, ev.w, cr, crm1);
+            reinterpret_cast<float4*>(es)[tid] = make_float4(x0v[0], x0v[1], x0v[2], x0v[3]);      // only its owner read this eps_hat
+        }
+        __syncthreads();
+        if (tid < cnt4) {
+            const int W = p.rst.W, n = p.rst.n;
+            const float xa[4] = {xv0.x, xv0.y, xv0.z, xv0.w}, za[4] = {zv0.x, zv0.y, zv0.z, zv0.w};
+            float o[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int lp = (tid * 4 + j) / p.n_out, c = tid * 4 + j - lp * p.n_out, row = lp / W, col = lp - row * W;
+                const float* blk = es + ((row & ~(n - 1)) * W + (col & ~(n - 1))) * p.n_out + c;
+                const float m = rst_block_mean([&](int bi, int bj) { return blk[(bi * W + bj) * p.n_out]; }, n);
+                o[j] = rst_finish(xa[j], x0v[j], m, yv0[j], za[j], a1, a2, sg);
+            }
+            reinterpret_cast<float4*>(p.x)[e4 + tid] = make_float4(o[0], o[1], o[2], o[3]);
+        }
+        return;
+    }
     if (tid < cnt4) {
         const float4 ev = reinterpret_cast<const float4*>(es)[tid];
         if (p.eps_out) reinterpret_cast<float4*>(p.eps_out)[e4 + tid] = ev;
@@ -447,6 +559,10 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
     }
 }
 
+static bool restore_block_ok(const RestoreOps& o) {
+    return (o.n == 2 || o.n == 4 || o.n == 8) && o.H > 0 && o.W > 0 && o.H % o.n == 0 && o.W % o.n == 0;
+}
+
 template <StepKind K>
 static int launch_tail(const TailParams& p, int B, hipStream_t st) {
     const dim3 grid((unsigned)(B * p.np));
@@ -454,23 +570,26 @@ static int launch_tail(const TailParams& p, int B, hipStream_t st) {
     else if (p.C == 64) hipLaunchKernelGGL((final_tail_kernel<16, 1, K>), grid, dim3(1024), 0, st, p);
     else if (p.C == 128) hipLaunchKernelGGL((final_tail_kernel<32, 1, K>), grid, dim3(1024), 0, st, p);
     else if constexpr (K == StepKind::Ancestral) hipLaunchKernelGGL((final_tail_kernel<32, 2, K>), grid, dim3(1024), 0, st, p);
-    else DDK_REQUIRE(false, "final_tail: C = 256 takes the unfused epilogue in the VLB, multistep and inpainting kinds (final_tail_ok)");
+    else DDK_REQUIRE(false, "final_tail: C = 256 takes the unfused epilogue in the VLB, multistep, inpainting and restore kinds (final_tail_ok)");
     return check_launch("final_tail_kernel");
 }
 
-bool final_tail_ok(int HW, int C, int groups, int n_out, int np, StepKind kind) {
+bool final_tail_ok(int HW, int C, int groups, int n_out, int np, StepKind kind, int restore_w, int restore_n) {
     if (!(C == 32 || C == 64 || C == 128 || C == 256)) return false;
     // the 256-channel instantiation spills registers already in the plain kinds; the others hold more in the prologue
     if (C > 128 && kind != StepKind::Eps && kind != StepKind::Ancestral) return false;
     if (groups <= 0 || groups > 64 || C % groups || (C / groups) % 4) return false;
     if (n_out < 1 || n_out > 8 || (128 * n_out) % 4) return false;
+    // the restore tail forms block means from the tile's x0 in LDS: the 128-pixel tile must hold whole rows of n x n blocks
+    if (kind == StepKind::Restore && !(restore_w > 0 && restore_n > 0 && 128 % (restore_w * restore_n) == 0)) return false;
     return np > 0 && HW == np * 128 && np * groups <= 1024;
 }
 
 int final_tail(const TailIn& in, const StepRule& r, const int64_t* t, const ChainHooks& h, hipStream_t st) {
     DDK_REQUIRE(in.raw && in.part && in.gamma && in.beta && in.w && in.B > 0, "final_tail: null pointer");
-    DDK_REQUIRE(final_tail_ok(in.HW, in.C, in.groups, in.n_out, in.np, r.kind),
-                "final_tail: needs C in {32,64,128,256} (the VLB, multistep and inpainting kinds: C <= 128), n_out <= 8, H*W == tiles * 128");
+    DDK_REQUIRE(final_tail_ok(in.HW, in.C, in.groups, in.n_out, in.np, r.kind, r.rst.W, r.rst.n),
+                "final_tail: needs C in {32,64,128,256} (the VLB, multistep, inpainting and restore kinds: C <= 128), n_out <= 8, "
+                "H*W == tiles * 128 (restore: 128 % (W n) == 0)");
     DDK_REQUIRE(aligned16(in.raw) && aligned16(in.gamma) && aligned16(in.beta) && aligned16(in.w) && aligned16(r.eps_out) && aligned16(r.x) &&
                     aligned16(r.noise) && r.noise_step_stride % 4 == 0, "final_tail: alignment");
     const bool tables = r.x && t && r.c_recip && r.c_recipm1 && r.c1 && r.c2;     // what every kind but Eps reads
@@ -498,6 +617,11 @@ int final_tail(const TailIn& in, const StepRule& r, const int64_t* t, const Chai
                         "final_tail: the inpainting op needs x, t, the tables, its operands, no injected noise and aligned known / mask");
             p.inp = r.inp;
             return launch_tail<StepKind::Inpaint>(p, in.B, st);
+        case StepKind::Restore:
+            DDK_REQUIRE(tables && r.sigma && !r.noise && r.rst.y && restore_block_ok(r.rst) && (long long)r.rst.H * r.rst.W == in.HW,
+                        "final_tail: the restore step needs x, t, the tables, y, n in {2,4,8} dividing H and W, H*W of the map and no injected noise");
+            p.rst = r.rst;
+            return launch_tail<StepKind::Restore>(p, in.B, st);
         case StepKind::Vlb: {
             DDK_REQUIRE(r.vlb && tables && !r.eps_out && h.chain_state, "final_tail: the VLB epilogue needs the sweep's step, x, t, the tables and the chain state");
             const VlbStep& v = *r.vlb;
@@ -721,6 +845,17 @@ int p_update(const StepRule& r, const float* eps_hat, const int64_t* t, int B, l
             if (!(h.chain_state || h.stream_id < INPAINT_Z3_BIT)) return bad("stream_id must be < 2^29 (bits 29, 30 key the extra draws)");
             hipLaunchKernelGGL(p_update_kernel<StepKind::Inpaint>, grid, dim3(256), 0, st, r, eps_hat, t, per / 4, total4, h.seed, h.stream_id, h.chain_state, h.dec_counter);
             break;
+        case StepKind::Restore: {  // blocks, not float4s: a kernel of its own
+            if (!(r.sigma && r.rst.y)) return bad("null pointer");
+            if (r.noise) return bad("no injected noise (Philox only)");
+            if (!restore_block_ok(r.rst)) return bad("n must be 2, 4 or 8 and divide H and W");
+            const long long hw = (long long)r.rst.H * r.rst.W;
+            if (per % hw || per / hw > INT_MAX) return bad("per must be H * W * channels");
+            const int n_out = (int)(per / hw);
+            hipLaunchKernelGGL(p_update_restore_kernel, dim3(grid1d(B * per / (r.rst.n * r.rst.n))), dim3(256), 0, st, r, eps_hat, t, B, n_out,
+                               h.seed, h.stream_id, h.chain_state, h.dec_counter);
+            return check_launch("p_update_restore_kernel");
+        }
         case StepKind::Vlb:       // no update: the sweep's reduction of the step's terms, a kernel of its own
             if (!r.vlb) return bad("null pointer");
             return vlb_sweep_terms(*r.vlb, t, eps_hat, B, per, h.chain_state, st, h.dec_counter);
@@ -798,6 +933,16 @@ int ddk_p_sample_update_inpaint(float* x, const float* eps_hat, const float* kno
     const StepRule r{StepKind::Inpaint, nullptr, x, nullptr, 0, 0, c_recip, c_recipm1, c1, c2, sigma, nullptr, nullptr,
                      InpaintOps{known, mask, ka, kb, ja, jb}};
     return p_update(r, eps_hat, t, B, per, ChainHooks{nullptr, nullptr, seed, stream_id}, as_stream(s), "p_sample_update_inpaint");
+}
+
+int ddk_p_sample_update_restore(float* x, const float* eps_hat, const float* y, int n, const int64_t* t, const float* c_recip,
+                                const float* c_recipm1, const float* c1, const float* c2, const float* sigma, int B, int H, int W,
+                                int channels, uint64_t seed, uint32_t stream_id, ddk_stream_t s) {
+    DDK_REQUIRE(B > 0 && H > 0 && W > 0 && channels > 0, "p_sample_update_restore: B / H / W / channels must be positive");
+    StepRule r{StepKind::Restore, nullptr, x, nullptr, 0, 0, c_recip, c_recipm1, c1, c2, sigma};
+    r.rst = RestoreOps{y, n, H, W};
+    return p_update(r, eps_hat, t, B, (long long)H * W * channels, ChainHooks{nullptr, nullptr, seed, stream_id}, as_stream(s),
+                    "p_sample_update_restore");
 }
 
 int ddk_final_tail(const float* raw, const float* partials, int tiles_per_image, const float* gamma, const float* beta, float eps,

@@ -89,11 +89,12 @@ struct ChainKey {
     const void* noise;                       // also in bufs; injected draws: no 16-step graph (see run_chain)
     int B, H, W, t_start, device;
     unsigned long long pack_epoch;
+    int restore_n = 0;                       // StepKind::Restore: the block (y itself is staged in the workspace)
     bool operator==(const ChainKey& o) const {
         for (int i = 0; i < 12; ++i)
             if (bufs[i] != o.bufs[i]) return false;
         return kind == o.kind && ws == o.ws && noise == o.noise && B == o.B && H == o.H && W == o.W && t_start == o.t_start &&
-               device == o.device && pack_epoch == o.pack_epoch;
+               device == o.device && pack_epoch == o.pack_epoch && restore_n == o.restore_n;
     }
 };
 struct SamplerGraph {
@@ -131,6 +132,7 @@ struct ddk_unet {
     bool fold_down_reduce = false;           // Downsample conv's split-K slabs summed by the image-local ResnetBlock behind it (no reduce launch).
                                              // OFF by default: measured 6 us per step SLOWER (each of an image's eight workgroups re-sums the slabs:
                                              // +6.3 / +5.9 us on the two consumers against reduce launches of 5.2 / 4.9 us; tools/fold_ab.py)
+    bool restore_fused = true;               // the Restore kind's fused tail where eligible (DDK_OPT_RESTORE_FUSED_TAIL; 0: always the unfused tail)
     bool first_gn = true;                    // the first Block's GroupNorm + Mish + shift inside conv_first_kernel's launch (DDK_OPT_FIRST_GROUPNORM),
                                              // wherever the in-launch GroupNorm of the Winograd convs may run
     int level_chain = 9;                     // bit 0: the whole 4x4 level (ResnetBlocks + attention of downs[-1], mid, ups[0]) as ONE persistent launch
@@ -460,6 +462,7 @@ extern "C" int ddk_unet_set_option(ddk_unet* u, int option, int value) {
         {DDK_OPT_ATTENTION_FOLD, true, [](ddk_unet& p, int v) { p.attn_fold = v != 0; }},
         {DDK_OPT_ATTENTION_KV_CONTEXT, true, [](ddk_unet& p, int v) { p.attn_kvctx = v != 0; }},
         {DDK_OPT_FIRST_GROUPNORM, true, [](ddk_unet& p, int v) { p.first_gn = v != 0; }},
+        {DDK_OPT_RESTORE_FUSED_TAIL, true, [](ddk_unet& p, int v) { p.restore_fused = v != 0; }},
         // 0 off, 1 (default): the 4x4 level with its Downsample / Upsample convs, 2: the 4x4 level alone, 3: the 8x8 levels as well,
         // 4: the 8x8 levels only, 8 / 16: only downs[-2] / only ups[1]
         {DDK_OPT_LEVEL_CHAIN, true, [](ddk_unet& p, int v) {
@@ -1123,12 +1126,13 @@ struct StepArgs {
 };
 
 // tiles of the final tail when the end of the forward runs as ONE launch (final_tail_kernel), else 0.  cin = the final conv's
-// input channels (dimp[1]).  The Vlb, Multistep and Inpaint kinds take a subset of the shapes (final_tail_ok).
-static int fused_tail_parts(const ddk_unet& u, int B, int H, int W, int cin, StepKind kind) {
+// input channels (dimp[1]).  The Vlb, Multistep, Inpaint and Restore kinds take a subset of the shapes (final_tail_ok; Restore's
+// depends on its block, restore_n).
+static int fused_tail_parts(const ddk_unet& u, int B, int H, int W, int cin, StepKind kind, int restore_n = 0) {
     const int chan = u.generic ? pad32(u.cfg.chan) : u.cfg.chan, n_out = u.cfg.in_ch;
     const int npf = u.final_conv.has_wu ? conv_wino_stats_parts(B, H, W, cin, chan, GROUPS) : 0;
-    if (npf <= 0) return 0;
-    return final_tail_ok(H * W, chan, GROUPS, n_out, npf, kind) ? npf : 0;
+    if (npf <= 0 || (kind == StepKind::Restore && !u.restore_fused)) return 0;
+    return final_tail_ok(H * W, chan, GROUPS, n_out, npf, kind, W, restore_n) ? npf : 0;
 }
 
 // t_cur[b] = counter for every sample, then counter -= 1; also zero-pads x into xpad.  First kernel of a step on shapes the
@@ -1329,12 +1333,20 @@ static int forward_core(const ddk_unet& u, const float* P, const float* x, int64
         hooks.chain_state = step->state;
         hooks.dec_counter = dec_counter;
     }
-    const int npf = fused_tail_parts(u, B, H, W, cur_c, rule.kind);
-    if (npf > 0 && (!step || step->per == (long long)H * W * n_out)) {
+    const int npf = fused_tail_parts(u, B, H, W, cur_c, rule.kind, rule.rst.n);
+    // a Restore step whose blocks do not fit the tail's tile (or with its fused tail switched off) still ends the forward in the plain
+    // tail's one launch, eps_hat to the step's scratch, and updates x behind it: the same eps_hat, bit for bit, as its fused tail sees
+    const int npe = (npf == 0 && step && rule.kind == StepKind::Restore) ? fused_tail_parts(u, B, H, W, cur_c, StepKind::Eps) : 0;
+    if ((npf > 0 || npe > 0) && (!step || step->per == (long long)H * W * n_out)) {
         // one-pass Winograd conv with statistics, then GroupNorm + Mish + projection (+ the rule) in ONE launch
         DDK_TRY(run_conv_parts(c, u.final_conv, cur, cur_c, nullptr, 0, raw, H, W, chan));
-        const TailIn in{raw, gnp, npf, P + u.final_norm.g, P + u.final_norm.b, GN_EPS, P + u.final_w, P + u.final_b, n_out, B, H * W, chan, GROUPS};
-        return final_tail(in, rule, t, hooks, st);
+        const TailIn in{raw, gnp, npf > 0 ? npf : npe, P + u.final_norm.g, P + u.final_norm.b, GN_EPS, P + u.final_w, P + u.final_b, n_out, B, H * W, chan, GROUPS};
+        if (npf > 0) return final_tail(in, rule, t, hooks, st);
+        StepRule eps_only{};
+        eps_only.kind = StepKind::Eps;
+        eps_only.eps_out = step->eps_hat;
+        DDK_TRY(final_tail(in, eps_only, t, ChainHooks{}, st));
+        return p_update(rule, step->eps_hat, t, B, step->per, hooks, st);
     }
     DDK_TRY(run_conv_gn(c, u.final_conv, cur, cur_c, nullptr, 0, raw, u.final_norm, nullptr, nullptr, a1, H, W, chan));
     float* eps_hat = step ? step->eps_hat : out;
@@ -1709,10 +1721,11 @@ static int check_timestep_map(const int64_t* map, int t_start, const char* who) 
 
 namespace ddk {
 // floats a chain keeps behind the sampler layout, by its rule: the multistep history [B][H][W][in_ch]; the inpainting op's known
-// latent and mask.  The size queries and sampler_chain's carve-up both come from here.
+// latent and mask; the restore step's low-resolution image (room for n = 2, a quarter of the latent: every n fits).  The size
+// queries and sampler_chain's carve-up both come from here.
 static size_t chain_extra_floats(const ddk_unet& u, int B, int H, int W, StepKind kind) {
     const size_t n = al4((size_t)B * H * W * u.cfg.in_ch);
-    return kind == StepKind::Multistep ? n : kind == StepKind::Inpaint ? 2 * n : 0;
+    return kind == StepKind::Multistep ? n : kind == StepKind::Inpaint ? 2 * n : kind == StepKind::Restore ? al4(n / 4) : 0;
 }
 static size_t sampler_bytes(const ddk_unet* u, int B, int H, int W, int t_start, StepKind kind) {
     if (check_shape(u, B, H, W) != DDK_OK || t_start < 0) return 0;
@@ -1720,12 +1733,14 @@ static size_t sampler_bytes(const ddk_unet* u, int B, int H, int W, int t_start,
 }
 
 // What the sampler entries share once their own arguments are checked: n_steps reverse steps on a->x, step k at timestep map[k],
-// each ending in `rule`.  The entry sets rule.kind and the operands only its kind has (c3; inp, with the CALLER's known / mask);
+// each ending in `rule`.  The entry sets rule.kind and the operands only its kind has (c3; inp, with the CALLER's known / mask; rst, with the CALLER's y);
 // x, the noise and the tables c_recip .. sigma come from *a here.  What a kind keeps in the workspace is staged after begin_chain
 // and outside any captured step, so no chain sees another's and the cached graph points only into the workspace:
 //   Multistep: the history, zeroed by every call (c3[t_start] == 0 makes the first step first order whatever it would hold)
 //   Inpaint:   known and mask, copied in before the first op
-// The graph key: the kind and every table the step reads; the staged operands live in the workspace, which is in the key.
+//   Restore:   y, copied in before the first step
+// The graph key: the kind, every table the step reads and the restore block; the staged operands live in the workspace, which is
+// in the key.
 static int sampler_chain(const ddk_sampler_args* a, const char* who, const int64_t* map, StepRule rule, ddk_stream_t s) {
     const int B = a->B, H = a->H, W = a->W, n_steps = a->t_start - a->t_end + 1;
     ChainRun c;
@@ -1743,6 +1758,10 @@ static int sampler_chain(const ddk_sampler_args* a, const char* who, const int64
         DDK_HIP(hipMemcpyAsync(extra + al4(n), rule.inp.mask, n * sizeof(float), hipMemcpyDeviceToDevice, c.st));
         rule.inp.known = extra;
         rule.inp.mask = extra + al4(n);
+    } else if (rule.kind == StepKind::Restore) {
+        rule.rst.H = H; rule.rst.W = W;
+        DDK_HIP(hipMemcpyAsync(extra, rule.rst.y, n / ((size_t)rule.rst.n * rule.rst.n) * sizeof(float), hipMemcpyDeviceToDevice, c.st));
+        rule.rst.y = extra;
     }
     const StepArgs step{c.state, c.ws + c.sl.off_eps, c.per, rule};
 
@@ -1752,7 +1771,7 @@ static int sampler_chain(const ddk_sampler_args* a, const char* who, const int64
     const ChainKey key{rule.kind,
                        {a->packed, a->x, rule.c_recip, rule.c_recipm1, rule.c1, rule.c2, rule.sigma, rule.c3, rule.inp.ka, rule.inp.kb,
                         rule.inp.ja, rule.inp.jb},
-                       a->workspace, a->noise, B, H, W, a->t_start, c.dev, c.u->pack_epoch};
+                       a->workspace, a->noise, B, H, W, a->t_start, c.dev, c.u->pack_epoch, rule.kind == StepKind::Restore ? rule.rst.n : 0};
     return run_chain(*c.u, key, n_steps, a->use_graph != 0, one_step, c.st, who);
 }
 }  // namespace ddk
@@ -1826,6 +1845,33 @@ extern "C" int ddk_sampler_run_inpaint(const ddk_sampler_args* a, const ddk_inpa
     rule.kind = StepKind::Inpaint;
     rule.inp = InpaintOps{ip->known, ip->mask, ip->ka, ip->kb, ip->ja, ip->jb};
     return sampler_chain(a, "sampler_inpaint", ip->timestep_map, rule, s);
+}
+
+// ------------------------------------------------------------------------------------------------ super-resolution sampler
+// DDNM for n x n average pooling: the spaced sampler's chain and tables, every step ending in
+// StepKind::Restore.  A kind of its own and n in the graph key: an ancestral chain on the same buffers never replays this graph,
+// nor this one an ancestral graph, nor a chain with another block.
+extern "C" size_t ddk_sampler_restore_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start) {
+    return sampler_bytes(u, B, H, W, t_start, StepKind::Restore);
+}
+
+extern "C" int ddk_sampler_restore_tail_parts(const ddk_unet* u, int B, int H, int W, int n) {
+    if (check_shape(u, B, H, W) != DDK_OK) return -1;
+    return fused_tail_parts(*u, B, H, W, u->dimp[1], StepKind::Restore, n);
+}
+
+extern "C" int ddk_sampler_run_restore(const ddk_sampler_args* a, const int64_t* timestep_map, const float* y, int n, ddk_stream_t s) {
+    DDK_REQUIRE(a && a->unet && a->packed && a->x && a->workspace && y, "sampler_restore: null pointer");
+    DDK_REQUIRE(a->c_recip && a->c_recipm1 && a->c1 && a->c2 && a->sigma, "sampler_restore: null schedule table");
+    DDK_REQUIRE(!a->noise, "sampler_restore: injected noise is not supported, noise must be NULL (Philox only)");
+    DDK_REQUIRE(a->t_start >= a->t_end && a->t_end >= 0, "sampler_restore: need t_start >= t_end >= 0");
+    DDK_REQUIRE((n == 2 || n == 4 || n == 8) && a->H > 0 && a->W > 0 && a->H % n == 0 && a->W % n == 0,
+                "sampler_restore: n must be 2, 4 or 8 and divide H and W");
+    DDK_TRY(check_timestep_map(timestep_map, a->t_start, "sampler_restore"));
+    StepRule rule{};
+    rule.kind = StepKind::Restore;
+    rule.rst = RestoreOps{y, n, a->H, a->W};
+    return sampler_chain(a, "sampler_restore", timestep_map, rule, s);
 }
 
 // ------------------------------------------------------------------------------------------------ likelihood sweep

@@ -771,6 +771,18 @@ def p_sample_update_inpaint_(x, eps_hat, known, mask, t, c_recip, c_recipm1, c1,
     return x
 
 
+def p_sample_update_restore_(x, eps_hat, y, n, t, c_recip, c_recipm1, c1, c2, sigma, seed=0, stream_id=0):
+    """In-place DDNM super-resolution step of x [B,H,W,C] (NHWC) per sample row t[b]: the clipped x0 is
+    shifted so that its n x n block means equal y [B,H/n,W/n,C], then the ancestral update with Philox draws runs on it."""
+    b, h, w, c = x.shape
+    if tuple(y.shape) != (b, h // n, w // n, c) or tuple(eps_hat.shape) != tuple(x.shape):
+        raise L.DDKError(f"p_sample_update_restore: x {tuple(x.shape)}, eps_hat {tuple(eps_hat.shape)}, y {tuple(y.shape)}, n = {n}")
+    L.check(L.load().ddk_p_sample_update_restore(L.ptr(_f32(x)), L.ptr(_f32(eps_hat)), L.ptr(_f32(y)), int(n), L.ptr(t), L.ptr(c_recip),
+                                                 L.ptr(c_recipm1), L.ptr(c1), L.ptr(c2), L.ptr(sigma), b, h, w, c, seed, stream_id,
+                                                 L.stream()), "p_sample_update_restore")
+    return x
+
+
 def randn(shape, device, seed, step, stream_id=0):
     out = torch.empty(shape, device=device, dtype=torch.float32)
     L.check(L.load().ddk_randn(L.ptr(out), out.numel(), seed, step, stream_id, L.stream()), "randn")

@@ -4,6 +4,7 @@ The plan is created from the reference config keys (models/unet/unet.py:19-22), 
 state_dict tensors it needs (names = reference keys), repacks them into one device arena and then
 runs a whole forward -- or the whole T-step sampling loop -- from a single C call.
 """
+import contextlib
 import ctypes as C
 import math
 import warnings
@@ -23,7 +24,8 @@ def sinusoidal_freqs(dim):
 
 # the sampler entries by workspace kind: (method, chain name in messages, name of the workspace in messages)
 SAMPLERS = {"smp": ("sample", "sampler", "sampler"), "sms": ("sample_multistep", "sampler_multistep", "multistep sampler"),
-            "sin": ("sample_inpaint", "sampler_inpaint", "inpainting sampler")}
+            "sin": ("sample_inpaint", "sampler_inpaint", "inpainting sampler"),
+            "srs": ("sample_restore", "sampler_restore", "super-resolution sampler")}
 # workspace kinds whose captured step graphs point into them (the samplers', the likelihood sweep's): UnetPlan._workspace keeps up
 # to 3 of each
 CHAIN_WORKSPACES = (*SAMPLERS, "vsw")
@@ -86,8 +88,8 @@ class UnetPlan:
         time-shift table live in / point into their workspace, so a trainer that alternates sample() (t_start = T-1) and
         reconstruct() (t_start = t_rec_max) at every logging event keeps both sets of graphs instead of re-capturing twice per event.
         Only an eviction drops the plan's cached graphs (ddk_sampler_invalidate waits for the device).  The likelihood sweep's
-        workspaces ("vsw"), the multistep sampler's ("sms") and the inpainting sampler's ("sin") are kept the same way: their
-        captured steps point into them too."""
+        workspaces ("vsw"), the multistep sampler's ("sms"), the inpainting sampler's ("sin") and the super-resolution sampler's
+        ("srs") are kept the same way: their captured steps point into them too."""
         key = (kind, nbytes, str(device))
         hit = self._ws.get(key)
         if hit is not None:
@@ -114,6 +116,7 @@ class UnetPlan:
     OPT_ATTENTION_KV_CONTEXT = 6
     OPT_LEVEL_CHAIN = 7
     OPT_FIRST_GROUPNORM = 8
+    OPT_RESTORE_FUSED_TAIL = 12
 
     def set_option(self, option, value):
         """ddk_unet_set_option: e.g. (OPT_CLUSTER_GROUPNORM, 0) keeps conv + GroupNorm-apply as two launches
@@ -121,6 +124,23 @@ class UnetPlan:
         L.check(self._lib.ddk_unet_set_option(self.handle, option, int(value)), "unet_set_option")
         if option == self.OPT_CLUSTER_GROUPNORM:
             self._cluster = max(0, min(2, int(value)))
+
+    @contextlib.contextmanager
+    def forwards_as_in_chain(self):
+        """While open, single forwards choose their kernels as a sampler step does: with the option at its default (1) the chain
+        runs the in-launch GroupNorm and a lone forward the two-launch one, whose other summation order moves eps_hat by a few
+        1e-6 at the cfg4 shape -- more per step than a Python loop may differ from the native chain over a whole run.  Sets the
+        option to 2 (each forward then waits for its own check) and puts 1 back on leaving, unless a failed check has switched the
+        option off meanwhile.  Values 0 and 2 already agree with the chain and are left alone.  Setting the option drops the
+        plan's cached graphs: this is for the Python loops that tests and debugging compare with the native sampler."""
+        raised = self._cluster == 1
+        if raised:
+            self.set_option(self.OPT_CLUSTER_GROUPNORM, 2)
+        try:
+            yield
+        finally:
+            if raised and self._cluster == 2:
+                self.set_option(self.OPT_CLUSTER_GROUPNORM, 1)
 
     def _cluster_failed(self, ws, b, h, w, stream_ptr):
         """ddk_unet_cluster_check at a sync point.  True when an in-launch GroupNorm exchange timed out on `ws` (the GPU was
@@ -323,6 +343,33 @@ class UnetPlan:
 
         return self._run_sampler("sin", x, t_start, t_end,
                                  lambda b, h, w: lib.ddk_sampler_inpaint_workspace_bytes(self.handle, b, h, w, n_ops), call, use_graph)
+
+    def restore_tail_parts(self, b, h, w, n):
+        """Tiles per image of the fused tail of a super-resolution step on [b, h, w] with block n, or 0: the unfused tail."""
+        return int(self._lib.ddk_sampler_restore_tail_parts(self.handle, b, h, w, int(n)))
+
+    def sample_restore_nhwc(self, x, y, n, tables, t_start, t_end=0, seed=0, stream_id=0, use_graph=True, timesteps=None):
+        """DDNM super-resolution steps t_start .. t_end (inclusive) in place on x [B,H,W,in_ch] (ddk_sampler_run_restore; DESIGN.md
+        section 3.6).
+
+        y: [B,H/n,W/n,in_ch] fp32 device tensor, copied into the plan's "srs" workspace by every call, so a loop over images replays
+        one cached graph; n in {2, 4, 8} divides H and W.  tables / timesteps: as for sample_nhwc (plain, respaced or DDIM).
+        Philox only: no injected noise."""
+        self._need_packed("srs")
+        b, h, w, c = x.shape
+        if n not in (2, 4, 8) or h % n or w % n:
+            raise L.DDKError(f"sample_restore: n must be 2, 4 or 8 and divide H = {h} and W = {w}, got {n}")
+        if tuple(y.shape) != (b, h // n, w // n, c) or y.dtype != torch.float32 or not y.is_contiguous():
+            raise L.DDKError(f"y must be a contiguous fp32 [{b},{h // n},{w // n},{c}] tensor, got {tuple(y.shape)} {y.dtype}")
+        lib = self._lib
+        tmap = self._timestep_map(timesteps, t_start)
+
+        def call(x, ws, nbytes, stream_ptr):
+            a = self._sampler_args(x, None, tables, t_start, t_end, seed, stream_id, use_graph, ws, nbytes)
+            L.check(lib.ddk_sampler_run_restore(C.byref(a), tmap, L.ptr(y), int(n), stream_ptr), "sampler_run_restore")
+
+        return self._run_sampler("srs", x, t_start, t_end,
+                                 lambda b, h, w: lib.ddk_sampler_restore_workspace_bytes(self.handle, b, h, w, t_start), call, use_graph)
 
     # ---------------------------------------------------------------- likelihood sweep
     VLB_STREAM_BIT = 1 << 31     # the sweep's Philox stream id is stream_id | this (csrc/ddk_internal.h VLB_STREAM_BIT)

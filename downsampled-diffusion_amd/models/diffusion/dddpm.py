@@ -81,6 +81,23 @@ class DownsampleDDPM(DDPM):
         return x_out, z
 
     @torch.no_grad()
+    def super_resolve(self, y, scale, *, respacing=None, ddim=False, eta=0.0, x_T=None, seed=None, **unsupported):
+        """DDNM super-resolution in the latent (DDPM.super_resolve) of y [B, C, H/scale, W/scale].  The
+        constraint is the latent's: z_ref = rescaled_downsample(y replicated scale x scale), y_lat = the n_lat x n_lat average
+        pooling of z_ref with n_lat = scale / dim_reduc in {2, 4, 8}, and the chain keeps the latent's n_lat x n_lat block means
+        equal to y_lat.  That is exact in the latent (up to fp32 rounding) and only approximate in pixels: the decoder is not
+        linear, so the pooled x_out is close to y, not equal to it.  Returns (x_out, z) like sample; x_T is a latent start state."""
+        d = int(self.dim_reduc)
+        y = self._restore_args(y, scale, self.x_shape, ddim, eta, unsupported, block=d)
+        y = y.to(self.betas.device)
+        self._check_device(y)
+        s, n_lat = int(scale), int(scale) // d
+        z_ref = self.rescaled_downsample(y.repeat_interleave(s, dim=2).repeat_interleave(s, dim=3))
+        y_lat = torch.nn.functional.avg_pool2d(z_ref, n_lat)
+        z = self._restore_loop(y_lat, n_lat, respacing, ddim, eta, x_T, seed)
+        return self.rescaled_upsample(z), z
+
+    @torch.no_grad()
     def reconstruct(self, x, n):
         """dddpm.py:33-74 (visualisation only)."""
         assert x.shape[0] >= n, f'batch size ({x.shape[0]}) is below {n}'

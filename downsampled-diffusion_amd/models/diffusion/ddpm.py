@@ -342,6 +342,73 @@ class DDPM(nn.Module):
         x, m = self._inpaint_args(x, mask, self.sample_shape, jump_length, jump_n_sample, unsupported)
         return self._inpaint_loop(x, m, respacing, jump_length, jump_n_sample, x_T, seed)
 
+    # ------------------------------------------------------------------ DDNM super-resolution (not in the reference)
+    RESTORE_UNSUPPORTED = ('solver', 'noise', 'early_stop')
+    RESTORE_BLOCKS = (2, 4, 8)
+
+    def _restore_args(self, y, scale, shape, ddim, eta, unsupported, block=1):
+        """ValueError for anything super_resolve cannot take, before any device work.  Returns y as float.  ``shape`` is [C, H, W]
+        of the full-resolution image; the chain's block is scale / block (the dDDPM runs it in a latent dim_reduc times smaller)."""
+        if unsupported:
+            raise ValueError(f"super_resolve: {sorted(unsupported)} not accepted (DDNM runs ancestral or DDIM steps with Philox draws "
+                             f"over the whole schedule: no {', '.join(self.RESTORE_UNSUPPORTED)})")
+        if isinstance(scale, bool) or not isinstance(scale, (int, np.integer)) or scale % block or scale // block not in self.RESTORE_BLOCKS:
+            raise ValueError(f"super_resolve: scale must be an int in {tuple(block * n for n in self.RESTORE_BLOCKS)}, got {scale!r}")
+        if eta < 0 or (eta != 0 and not ddim):
+            raise ValueError(f"super_resolve: eta = {eta} needs ddim=True and eta >= 0")
+        C, H, W = shape
+        if H % scale or W % scale:
+            raise ValueError(f"super_resolve: scale = {scale} must divide the image size {H} x {W}")
+        if not torch.is_tensor(y) or y.dim() != 4 or list(y.shape[1:]) != [C, H // scale, W // scale] or not y.is_floating_point():
+            raise ValueError(f"super_resolve: y must be a float [B, {C}, {H // scale}, {W // scale}] tensor, got "
+                             f"{tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
+        if not bool(torch.isfinite(y).all()):
+            raise ValueError("super_resolve: y must be finite")
+        return y.float()
+
+    def _restore_loop(self, y, n, respacing, ddim, eta, x_T, seed):
+        """DDNM over the latent whose n x n block means are held at y [B, C, H/n, W/n]: native (UnetPlan.sample_restore_nhwc) or,
+        with native_sampler off, the same op as a Python loop in the same NHWC layout, so both draw the same Philox numbers."""
+        device = self.betas.device
+        if device.type != 'cuda':
+            raise DDKError("super_resolve: move the model to a ROCm device first (no CPU fallback)")
+        spaced = respacing is not None or ddim or eta != 0
+        tables, use = self._spaced_tables(respacing, ddim, eta) if spaced else (self._tables(), None)
+        shape = (y.shape[0], *self.sample_shape)
+        if x_T is not None and tuple(x_T.shape) != shape:
+            raise ValueError(f"super_resolve: x_T must be {shape}, got {tuple(x_T.shape)}")
+        img = torch.randn(shape, device=device) if x_T is None else x_T.to(device).float()
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        k_start = (self.timesteps if use is None else len(use)) - 1
+        yl = ops.nchw_to_nhwc(y.to(device).float().contiguous())
+        x = ops.nchw_to_nhwc(img.contiguous())
+        if not self.native_sampler:
+            # the loop's forwards pick their kernels as the chain's steps do (UnetPlan.forwards_as_in_chain): the two GroupNorm
+            # paths sum in another order, and a few 1e-6 of eps_hat per step is more than the loop may differ from the chain
+            with self._eps_model_nhwc().plan().forwards_as_in_chain():
+                for k in range(k_start, -1, -1):
+                    t_model = k if use is None else use[k]
+                    eps_hat = self.latent_model(ops.nhwc_to_nchw(x), torch.full((shape[0],), t_model, device=device, dtype=torch.long))
+                    ops.p_sample_update_restore_(x, ops.nchw_to_nhwc(eps_hat.contiguous()), yl, n,
+                                                 torch.full((shape[0],), k, device=device, dtype=torch.long), **tables, seed=seed,
+                                                 stream_id=int(self.rng_stream_id))
+            return ops.nhwc_to_nchw(x)
+        self._eps_model_nhwc().plan().sample_restore_nhwc(x, yl, n, tables, k_start, seed=seed, stream_id=int(self.rng_stream_id),
+                                                          use_graph=self.use_graph, timesteps=use)
+        return ops.nhwc_to_nchw(x)
+
+    @torch.no_grad()
+    def super_resolve(self, y, scale, *, respacing=None, ddim=False, eta=0.0, x_T=None, seed=None, **unsupported):
+        """Zero-shot super-resolution with DDNM (Wang, Yu, Zhang 2023): an image [B, C, H, W] whose
+        scale x scale average pooling is y [B, C, H/scale, W/scale] (in [-1, 1]); scale in {2, 4, 8}.  Every step of the chain
+        (all T steps, or respacing's K; ancestral, or DDIM with eta) shifts its clipped x0 so that its block means equal y before the
+        update; the block means of the result equal y up to fp32 rounding.  x_T: the start state; seed: the Philox key (default:
+        drawn from torch's generator).  solver / noise / early_stop raise ValueError, as do a bad scale, a non-finite or misshapen y
+        and eta without ddim, before any device work."""
+        y = self._restore_args(y, scale, self.sample_shape, ddim, eta, unsupported)
+        return self._restore_loop(y, int(scale), respacing, ddim, eta, x_T, seed)
+
     @torch.no_grad()
     def reconstruct(self, x, n):
         """ddpm.py:126-147."""

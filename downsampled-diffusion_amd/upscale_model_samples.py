@@ -1,0 +1,106 @@
+"""Upscale low-resolution images with a trained, unconditional DDPM / dDDPM checkpoint: zero-shot super-resolution with DDNM
+(Wang, Yu, Zhang, ICLR 2023), DESIGN.md section 3.6.
+
+Loads the checkpoint as generate_model_samples.py does (``--synthetic CONFIG`` builds closed-form weights instead), reads
+``--images file.npy`` (uint8 [N, h, w, C]) and runs ``model.super_resolve`` on it:
+
+  * images of the model's size divided by ``--scale`` are taken as the low-resolution input; images of the model's full size
+    are first average-pooled by ``--scale`` (so a test set can be degraded and restored in one go);
+  * ``--scale`` is 2, 4 or 8 for a DDPM; a dDDPM holds the constraint in its latent and takes 2, 4 or 8 times its reduction;
+  * ``--timestep_respacing``, ``--use_ddim`` and ``--eta`` choose the chain as in generate_model_samples.py;
+  * batch g draws x_T and its Philox key from ``--seed`` + g.
+
+Writes ``{saved_model}_sr{scale}_{spec}.npy`` through the sampling driver's output stage (utils.OutputStage: float32
+[N, H, W, C], each image min-max scaled to [0, 255] like the sample files) and ``..._lowres.npy``, the uint8 low-resolution
+images it started from.  One process, one GPU.
+"""
+import argparse
+import json
+import os
+import time
+
+import numpy as np
+import torch
+
+from models import DDPM, DownsampleDDPM, Unet
+from utils import CHECKPOINT_DIR, SAMPLE_DIR, OutputStage, get_color_channels, get_model_state_dict, load_checkpoint_file
+from utils import synthetic as syn
+
+
+def main():
+    ap = argparse.ArgumentParser(description="Upscale images with a trained DDPM / dDDPM checkpoint (DDNM super-resolution).")
+    ap.add_argument("--saved_model", default="celeba_x2")
+    ap.add_argument("--synthetic", default=None, help="JSON config file: use closed-form synthetic weights, no checkpoint")
+    ap.add_argument("--images", required=True, help="uint8 .npy [N, h, w, C]: low-resolution, or full-resolution to be pooled first")
+    ap.add_argument("--scale", type=int, default=4)
+    ap.add_argument("--timestep_respacing", default="", help='run K of the T steps: "ddimN", "N" or "n1,n2,..." sections')
+    ap.add_argument("--use_ddim", action="store_true", help="DDIM steps instead of ancestral ones")
+    ap.add_argument("--eta", type=float, default=0.0, help="DDIM noise scale (0: deterministic)")
+    ap.add_argument("--batch_size", type=int, default=32)
+    ap.add_argument("--seed", type=int, default=1234, help="base seed: batch g draws from seed + g")
+    ap.add_argument("--out_dir", default=None)
+    args = ap.parse_args()
+    if args.eta < 0 or (args.eta != 0.0 and not args.use_ddim):
+        ap.error("--eta needs --use_ddim and a value >= 0")
+    if args.batch_size < 1 or args.scale < 2:
+        ap.error("--batch_size must be >= 1 and --scale >= 2")
+
+    device = "cuda:0"
+    torch.cuda.set_device(0)
+    if args.synthetic:
+        with open(args.synthetic) as f:
+            config = json.load(f)
+        model_state_dict = None
+    else:
+        save_data = load_checkpoint_file(os.path.join(CHECKPOINT_DIR, f"{args.saved_model}.pt"))
+        model_state_dict = get_model_state_dict(save_data)
+        config = save_data["config"]
+    config["batch_size"] = args.batch_size
+    color_channels = get_color_channels(config["dataset"])
+    if config["model"] == "ddpm":
+        model = DDPM(config, Unet(config), device, color_channels)
+    elif config["model"] == "dddpm":
+        model = DownsampleDDPM(config, Unet(config), device, color_channels)
+    else:
+        raise NotImplementedError(config["model"])
+    if model_state_dict is None:
+        model_state_dict = syn.fill_state_dict(model.state_dict(), skip=syn.SCHEDULE_KEYS)
+    model.load_state_dict(model_state_dict)
+    model = model.to(device).eval()
+    model.rng_stream_id = 0
+
+    c, size, s = color_channels, int(config["image_size"]), args.scale
+    if size % s:
+        raise SystemExit(f"--scale {s} does not divide the model's image size {size}")
+    imgs = np.load(args.images)
+    if imgs.dtype != np.uint8 or imgs.ndim != 4 or imgs.shape[3] != c or imgs.shape[1:3] not in ((size, size), (size // s, size // s)):
+        raise SystemExit(f"--images: expected uint8 [N, {size // s}, {size // s}, {c}] or [N, {size}, {size}, {c}], got {imgs.dtype} {imgs.shape}")
+    y_all = torch.from_numpy(imgs.astype(np.float32)).permute(0, 3, 1, 2) / 255 * 2 - 1
+    if imgs.shape[1] == size:
+        y_all = torch.nn.functional.avg_pool2d(y_all, s)
+    n = y_all.shape[0]
+    lowres = ((y_all + 1) * 127.5).round().clamp(0, 255).permute(0, 2, 3, 1).numpy().astype(np.uint8)
+
+    spec = (args.timestep_respacing.replace(",", "-") or "full") + (f"_ddim_eta{args.eta:g}" if args.use_ddim else "")
+    kw = dict(respacing=args.timestep_respacing or None, ddim=args.use_ddim, eta=args.eta)
+    print(f"Upscaling {n} images x{s} ({spec} steps) with {args.saved_model}.")
+    stage = OutputStage()
+    t0 = time.time()
+    for g, i in enumerate(range(0, n, args.batch_size)):
+        torch.manual_seed(args.seed + g)          # x_T and the Philox key of batch g
+        out = model.super_resolve(y_all[i:i + args.batch_size].to(device), s, **kw)
+        stage.submit(out[0] if config["model"] == "dddpm" else out)
+    batches = stage.finish()
+    torch.cuda.synchronize()
+    print(f"Total time: {time.time() - t0:.2f} s")
+
+    out_dir = args.out_dir or SAMPLE_DIR
+    os.makedirs(out_dir, exist_ok=True)
+    base = os.path.join(out_dir, f"{args.saved_model}_sr{s}_{spec}")
+    np.save(base + ".npy", np.concatenate(batches).astype(np.float32), allow_pickle=False)
+    np.save(base + "_lowres.npy", lowres, allow_pickle=False)
+    print(f"Upscaled images saved to {base}.npy, low-resolution inputs to {base}_lowres.npy")
+
+
+if __name__ == "__main__":
+    main()

@@ -299,6 +299,15 @@ int ddk_p_sample_update_inpaint(float* x, const float* eps_hat, const float* kno
                                 const float* c_recip, const float* c_recipm1, const float* c1, const float* c2, const float* sigma,
                                 const float* ka, const float* kb, const float* ja, const float* jb, int B, long long per, uint64_t seed,
                                 uint32_t stream_id, ddk_stream_t s);
+/* One DDNM super-resolution step (ddk_sampler_run_restore) on its own, per sample b with row t[b], for A = n x n average pooling:
+ * x0 = clamp(c_recip x - c_recipm1 eps_hat, -1, 1); m = the mean of x0 over the element's n x n block (same image and channel);
+ * x0' = x0 + (y[block] - m), not clamped again; x = (c1 x0' + c2 x) + [t > 0] sigma z.  Every product, sum and difference is
+ * rounded on its own and the block is summed in row-major order.  x, eps_hat are NHWC [B][H][W][channels], y is
+ * [B][H/n][W/n][channels]; n is 2, 4 or 8 and divides H and W; any channel count.  z is Philox: element e takes component e & 3 of
+ * the draw of (e / 4, t[b], stream_id, seed), as in ddk_p_sample_update.  x and eps_hat 16-byte aligned. */
+int ddk_p_sample_update_restore(float* x, const float* eps_hat, const float* y, int n, const int64_t* t, const float* c_recip,
+                                const float* c_recipm1, const float* c1, const float* c2, const float* sigma, int B, int H, int W,
+                                int channels, uint64_t seed, uint32_t stream_id, ddk_stream_t s);
 /* The end of a forward in one launch (unet.py:69-72 behind the final Block's conv; ddpm.py:203-227): GroupNorm from the conv's
  * partials -> Mish -> 1x1 projection to n_out <= 8 channels (w [n_out][C], bias [n_out]) -> eps_hat; eps_out and / or x may be
  * given: eps_out [B][HW][n_out] receives eps_hat, x [B][HW][n_out] gets the reverse-step update of ddk_p_sample_update in place
@@ -389,6 +398,11 @@ int ddk_unet_forward(const ddk_unet* u, const void* packed, const float* x, cons
  * finishes its GroupNorm + Mish + time shift inside the conv's own launch -- the eight 128-pixel tiles of an image exchange their statistics
  * as the Winograd convs of DDK_OPT_CLUSTER_GROUPNORM do -- wherever that option lets the exchange run; 0 keeps conv + GroupNorm-apply. */
 #define DDK_OPT_FIRST_GROUPNORM 8
+/* DDK_OPT_RESTORE_FUSED_TAIL (default 1): a step of ddk_sampler_run_restore ends inside the forward's last launch wherever
+ * ddk_sampler_restore_tail_parts says it can; 0 ends every step in ddk_p_sample_update_restore's kernel behind the forward, as the
+ * shapes that cannot do (where the plain forward ends in one launch, that launch leaves eps_hat in the workspace first, so the
+ * update sees the same eps_hat).  Bit-identical results either way (tests/test_restore_gpu.py). */
+#define DDK_OPT_RESTORE_FUSED_TAIL 12
 int ddk_unet_set_option(ddk_unet* u, int option, int value);
 /* Waits for `s`, then reads and clears the sticky give-up count of the launches issued on `workspace` (a ddk_unet_forward or
  * ddk_sampler_run workspace of this shape): DDK_OK, or DDK_ERR_CLUSTER when any in-launch GroupNorm exchange timed out. */
@@ -477,6 +491,19 @@ typedef struct ddk_inpaint_args {
 } ddk_inpaint_args;
 size_t ddk_sampler_inpaint_workspace_bytes(const ddk_unet* u, int B, int H, int W, int n_ops);
 int ddk_sampler_run_inpaint(const ddk_sampler_args* a, const ddk_inpaint_args* ip, ddk_stream_t s);
+/* Zero-shot super-resolution of a low-resolution image with an unconditional model (DDNM, Wang et al. 2023, for n x n average
+ * pooling): the chain of ddk_sampler_run_spaced (same arguments, tables and timestep_map, which may be
+ * NULL), every step being ddk_p_sample_update_restore's.  y, device [B][H/n][W/n][in_ch] fp32, is copied into the workspace
+ * (ddk_sampler_restore_workspace_bytes) before the first step, outside any captured step, so a loop over many images on one
+ * workspace replays one cached graph.  n is 2, 4 or 8 and divides H and W.  a->noise must be NULL (Philox only).  After the
+ * step at row 0 the n x n block means of x equal y up to fp32 rounding.  Graphs are cached under a chain kind of their own
+ * with n in the key. */
+size_t ddk_sampler_restore_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start);
+/* 128-pixel tiles per image of the fused tail when a step of ddk_sampler_run_restore on this shape ends in ONE launch (at most 128
+ * channels in front of the projection and whole rows of blocks per tile: 128 % (W n) == 0), 0 when it takes the unfused tail, < 0 for
+ * a shape the plan does not take. */
+int ddk_sampler_restore_tail_parts(const ddk_unet* u, int B, int H, int W, int n);
+int ddk_sampler_run_restore(const ddk_sampler_args* a, const int64_t* timestep_map, const float* y, int n, ddk_stream_t s);
 /* Drops the plan's cached sampler and likelihood-sweep graphs and shift table (waits for the device when graphs exist). */
 int ddk_sampler_invalidate(ddk_unet* u);
 /* Drops only the cached graphs (and shift table) that live in / point into `workspace`, after waiting for the launches of

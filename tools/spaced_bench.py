@@ -10,7 +10,11 @@ with the x3 decode (tanh(upsample(z))) timed in the same run; T = 1000 is the pl
 stdout.  GPU-box tool.
 
 --solver: the cost of a DPM-Solver++(2M) step against a DDIM (eta 0) step on the same "logsnrK" grid, K in {20, 50}, timed
-alternately the same way (the two chains differ only in the step's last kernel: a history load and store instead of a draw)."""
+alternately the same way (the two chains differ only in the step's last kernel: a history load and store instead of a draw).
+
+--restore: the cost of a DDNM super-resolution step against an ancestral step of the same respaced "50"
+chain, n = 2 and 4 (the fused tail) and, for the record, the same two with the fused tail switched off and n = 8 (always the
+unfused tail), timed alternately the same way (the chains differ only in the step's last kernel)."""
 import argparse
 import json
 import os
@@ -37,6 +41,7 @@ REPS = 5
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--solver", action="store_true", help="2M step against DDIM step on logsnrK grids")
+    ap.add_argument("--restore", action="store_true", help="DDNM super-resolution step against an ancestral step, respacing 50")
     args = ap.parse_args()
     torch.cuda.set_device(0)
     cfg = bench.cfg4()
@@ -47,6 +52,8 @@ def main():
     tables = model._tables()
     x0 = ops.randn((B, S, S, C), DEV, seed=1234, step=T, stream_id=0)
     x = x0.clone()
+
+    ys = {n: torch.nn.functional.avg_pool2d(ops.nhwc_to_nchw(x0).clamp(-1, 1), n).permute(0, 2, 3, 1).contiguous() for n in (2, 4, 8)}
 
     def chain(kind, K):
         x.copy_(x0)
@@ -60,6 +67,13 @@ def main():
         elif kind == "2m":
             sp, use = model._solver_tables(f"logsnr{K}", "dpm++2m")
             plan.sample_multistep_nhwc(x, sp, K - 1, 0, stream_id=0, timesteps=use)
+        elif kind == "anc":
+            sp, use = model._spaced_tables(str(K), False, 0.0)
+            plan.sample_nhwc(x, sp, K - 1, 0, seed=1234, stream_id=0, timesteps=use)
+        elif kind.startswith("restore"):
+            n = int(kind[len("restore"):])
+            sp, use = model._spaced_tables(str(K), False, 0.0)
+            plan.sample_restore_nhwc(x, ys[n], n, sp, K - 1, seed=1234, stream_id=0, timesteps=use)
         else:
             sp, use = model._spaced_tables(f"ddim{K}", True, 0.0)
             plan.sample_nhwc(x, sp, K - 1, 0, seed=1234, stream_id=0, timesteps=use)
@@ -76,6 +90,8 @@ def main():
 
     if args.solver:
         return solver_ab(chain, decode)
+    if args.restore:
+        return restore_ab(chain, plan)
 
     res = {"shape": f"cfg4 unet_chan 128, {C}x{S}x{S} latents, B={B}, T={T}, DDIM eta 0", "reps": REPS, "per_K": {}}
     with torch.no_grad():
@@ -127,6 +143,32 @@ def solver_ab(chain, decode):
                                     "dpm2m_images_per_sec": round(B / ((K * m + decode_ms) / 1e3), 2)}
         res["decode_ms"] = round(decode_ms, 3)
         res["max_dpm2m_over_ddim"] = max(v["dpm2m_over_ddim"] for v in res["per_K"].values())
+    print(json.dumps(res), flush=True)
+
+
+def restore_ab(chain, plan):
+    K = 50
+    res = {"shape": f"cfg4 unet_chan 128, {C}x{S}x{S} latents, B={B}, T={T}, respacing {K}, DDNM restore step vs ancestral step",
+           "reps": REPS, "per_n": {}}
+    with torch.no_grad():
+        t_settle = time.perf_counter()
+        while time.perf_counter() - t_settle < 2.0:
+            chain("plain", 96)
+        for n, fused in ((2, True), (4, True), (2, False), (4, False), (8, True)):
+            plan.set_option(plan.OPT_RESTORE_FUSED_TAIL, int(fused))
+            tail = "fused" if plan.restore_tail_parts(B, S, S, n) > 0 else "unfused"
+            chain("anc", K)                              # captures both chains' graphs outside the timed calls
+            chain(f"restore{n}", K)
+            anc, rst = [], []
+            for _ in range(REPS):
+                anc.append(chain("anc", K) / K)
+                rst.append(chain(f"restore{n}", K) / K)
+            a, r = statistics.median(anc), statistics.median(rst)
+            res["per_n"][f"{n}_{tail}"] = {"ancestral_ms_per_step": round(a, 4), "restore_ms_per_step": round(r, 4),
+                                           "restore_over_ancestral": round(r / a, 4),
+                                           "ancestral_min_max_ms": [round(min(anc), 4), round(max(anc), 4)],
+                                           "restore_min_max_ms": [round(min(rst), 4), round(max(rst), 4)]}
+        plan.set_option(plan.OPT_RESTORE_FUSED_TAIL, 1)
     print(json.dumps(res), flush=True)
 
 
