@@ -158,6 +158,8 @@ SIGNATURES = {
     "ddk_sq_err_sum": (_I, [_P, _P, _P, _I, _LL, _P]),
     "ddk_vlb_terms_workspace_bytes": (_SZ, [_I, _LL]),
     "ddk_vlb_terms": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _LL, _P, _SZ, _P]),
+    "ddk_image_metrics_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "ddk_image_metrics": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
     "ddk_unet_create": (_P, [C.POINTER(UnetConfig)]),
     "ddk_unet_destroy": (None, [_P]),
     "ddk_unet_num_slots": (_I, [_P]),

@@ -811,6 +811,50 @@ def sq_err_sum(a, b):
     return out
 
 
+SSIM_WINDOW = 11
+
+
+def image_metrics(a, b, mask=None):
+    """PSNR, SSIM and MSE per image of two uint8 device tensors [N, H, W, C] (C in 1..4, H, W >= 11).
+    mask: optional uint8 / bool [N, H, W]; the squared error then covers only the pixels where it is nonzero (all channels);
+    SSIM always covers the whole image.  Returns host tensors: psnr [N] float64 (inf for identical images, nan when the mask
+    selects nothing), ssim [N] float32, mse [N] float64, and the exact integers behind them, sq_sum and count [N] int64.
+    Wrong dtypes, mismatched shapes and images smaller than one SSIM window raise ValueError before any device work."""
+    for name, t in (("a", a), ("b", b)):
+        if not torch.is_tensor(t) or t.dtype != torch.uint8:
+            raise ValueError(f"image_metrics: {name} must be a uint8 tensor, got {getattr(t, 'dtype', type(t))}")
+    if a.dim() != 4 or a.shape != b.shape:
+        raise ValueError(f"image_metrics: a and b must share one [N, H, W, C] shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    n, h, w, c = a.shape
+    if n < 1 or not 1 <= c <= 4:
+        raise ValueError(f"image_metrics: N must be positive and C in 1..4, got {tuple(a.shape)}")
+    if h < SSIM_WINDOW or w < SSIM_WINDOW:
+        raise ValueError(f"image_metrics: H and W must be at least {SSIM_WINDOW} (one SSIM window), got {h} x {w}")
+    if mask is not None:
+        if not torch.is_tensor(mask) or mask.dtype not in (torch.uint8, torch.bool):
+            raise ValueError(f"image_metrics: mask must be a uint8 or bool tensor, got {getattr(mask, 'dtype', type(mask))}")
+        if tuple(mask.shape) != (n, h, w):
+            raise ValueError(f"image_metrics: mask must be [N, H, W] = {(n, h, w)}, got {tuple(mask.shape)}")
+    if not (a.is_cuda and b.is_cuda and (mask is None or mask.is_cuda)):
+        raise L.DDKError("image_metrics: HIP kernels need ROCm device tensors; there is no CPU fallback")
+    if mask is not None:
+        mask = mask.to(torch.uint8).contiguous()
+    a, b = a.contiguous(), b.contiguous()
+    lib = L.load()
+    sq = torch.empty((n, 2), device=a.device, dtype=torch.int64)      # the kernel's unsigned 64-bit pairs; both stay far below 2^63
+    ssim = torch.empty((n,), device=a.device, dtype=torch.float32)
+    nbytes = lib.ddk_image_metrics_workspace_bytes(n, h, w, c)
+    ws = _ws(a.device, nbytes, "image_metrics")
+    L.check(lib.ddk_image_metrics(L.ptr(a), L.ptr(b), L.ptr(mask), n, h, w, c, L.ptr(sq), L.ptr(ssim), L.ptr(ws), nbytes, L.stream()),
+            "image_metrics")
+    sq = sq.cpu()
+    sq_sum, count = sq[:, 0].contiguous(), sq[:, 1].contiguous()
+    s, k = sq_sum.double(), count.double()
+    mse = s / k                                                        # 0 / 0 = nan: an empty mask has no error to report
+    psnr = 10.0 * torch.log10(255.0 ** 2 * k / s)                      # k / 0 = inf, 0 / 0 = nan
+    return dict(psnr=psnr, ssim=ssim.cpu(), mse=mse, sq_sum=sq_sum, count=count)
+
+
 # ================================================================== training path (backward kernels)
 CONV4X4_S2 = 4
 _scratch = {}

@@ -1,0 +1,153 @@
+#!/usr/bin/env python3
+"""Score the restoration paths of a trained DDPM / dDDPM checkpoint against ground truth: degrade a test
+set, restore it with RePaint inpainting (``--task inpaint``, section 3.5) or DDNM super-resolution (``--task sr``, section 3.6) and
+report PSNR and SSIM of the result and of network-free baselines, as mean and standard error over the images.
+
+Loads the checkpoint as evaluate_ddpm.py does (``--synthetic CONFIG`` builds closed-form weights instead; their scores mean
+nothing).  The images are ``--images file.npy`` (uint8 [N, H, W, C] of the model's size) or, by default, the dataset's test split
+through utils/data.py; ``--max_batches`` keeps the first max_batches * batch_size of them.
+
+  * ``--task inpaint``: ``--mask`` as in inpaint_model_samples.py, chain options ``--timestep_respacing``, ``--jump_length``,
+    ``--jump_n_sample``.  Baseline: hidden pixels filled with the mean of the known ones.  Also the PSNR over the hidden pixels only.
+  * ``--task sr``: the images are average-pooled by ``--scale``, chain options ``--timestep_respacing``, ``--use_ddim``, ``--eta``
+    as in upscale_model_samples.py.  Baselines: replication and bicubic upsampling.  Also the consistency max |pool(x_out) - y| in
+    uint8 levels, of the chain's float output and of the uint8 image that is scored.
+  * batch g draws x_T and its Philox key from ``--seed`` + g.
+
+Prints one JSON object, the settings that produced it beside the metrics; ``--json OUT`` also writes it to a file.  One process,
+one GPU.
+"""
+import argparse
+import json
+import os
+import time
+
+import numpy as np
+import torch
+
+from utils.restoration_metrics import MASKS, TASKS, evaluate_restoration, load_mask, report, to_u8
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description="PSNR / SSIM of RePaint inpainting or DDNM super-resolution against ground truth.")
+    ap.add_argument("--saved_model", default="celeba_x2")
+    ap.add_argument("--synthetic", default=None, help="JSON config file: use closed-form synthetic weights, no checkpoint")
+    ap.add_argument("--images", default=None, help="uint8 [N, H, W, C] .npy of the model's size (default: the dataset's test split)")
+    ap.add_argument("--task", required=True, choices=TASKS)
+    ap.add_argument("--mask", default="center", help=f"inpaint: one of {', '.join(MASKS)} or a .npy file of {{0, 1}} (1 = known)")
+    ap.add_argument("--scale", type=int, default=4, help="sr: the pooling factor")
+    ap.add_argument("--timestep_respacing", default="", help='run K of the T steps: "N", "n1,n2,..." sections or (sr) "ddimN"')
+    ap.add_argument("--use_ddim", action="store_true", help="sr: DDIM steps instead of ancestral ones")
+    ap.add_argument("--eta", type=float, default=0.0, help="sr: DDIM noise scale (0: deterministic)")
+    ap.add_argument("--jump_length", type=int, default=10, help="inpaint: RePaint jump length")
+    ap.add_argument("--jump_n_sample", type=int, default=10, help="inpaint: RePaint resamplings per jump")
+    ap.add_argument("--batch_size", type=int, default=32)
+    ap.add_argument("--max_batches", type=int, default=None, help="stop after this many batches of images")
+    ap.add_argument("--seed", type=int, default=1234, help="base seed: batch g draws from seed + g")
+    ap.add_argument("--json", default=None, help="also write the result to this file")
+    args = ap.parse_args(argv)
+    if args.batch_size < 1 or (args.max_batches is not None and args.max_batches < 1):
+        ap.error("--batch_size and --max_batches must be >= 1")
+    if args.task == "sr":
+        if args.scale < 2:
+            ap.error("--scale must be >= 2")
+        if args.eta < 0 or (args.eta != 0.0 and not args.use_ddim):
+            ap.error("--eta needs --use_ddim and a value >= 0")
+    else:
+        if args.use_ddim or args.eta != 0.0:
+            ap.error("--use_ddim and --eta belong to --task sr (RePaint runs ancestral steps)")
+        if args.jump_length < 1 or args.jump_n_sample < 1:
+            ap.error("--jump_length and --jump_n_sample must be >= 1")
+    return args
+
+
+def chain_options(args):
+    """the task's keywords for evaluate_restoration, also the chain settings the result records"""
+    kw = dict(respacing=args.timestep_respacing or None)
+    if args.task == "sr":
+        kw.update(scale=args.scale, ddim=args.use_ddim, eta=args.eta)
+    else:
+        kw.update(jump_length=args.jump_length, jump_n_sample=args.jump_n_sample)
+    return kw
+
+
+def load_model(args, device):
+    from models import DDPM, DownsampleDDPM, Unet
+    from utils import CHECKPOINT_DIR, get_color_channels, get_model_state_dict, load_checkpoint_file
+    from utils import synthetic as syn
+    if args.synthetic:
+        with open(args.synthetic) as f:
+            config = json.load(f)
+        model_state_dict = None
+    else:
+        save_data = load_checkpoint_file(os.path.join(CHECKPOINT_DIR, f"{args.saved_model}.pt"))
+        model_state_dict = get_model_state_dict(save_data)
+        config = save_data["config"]
+    if config["model"] == "dddpm" and "force_latent" not in config:
+        config["force_latent"] = False
+    config["batch_size"] = args.batch_size
+    color_channels = get_color_channels(config["dataset"])
+    if config["model"] == "ddpm":
+        model = DDPM(config, Unet(config), device, color_channels)
+    elif config["model"] == "dddpm":
+        model = DownsampleDDPM(config, Unet(config), device, color_channels)
+    else:
+        raise NotImplementedError(config["model"])
+    if model_state_dict is None:
+        model_state_dict = syn.fill_state_dict(model.state_dict(), skip=syn.SCHEDULE_KEYS)
+    model.load_state_dict(model_state_dict)
+    model = model.to(device).eval()
+    model.rng_stream_id = 0
+    return model, config, color_channels
+
+
+def load_images(args, config, channels):
+    """uint8 [N, H, W, C]: the file, or the test split (floats in [-1, 1], rounded to the uint8 grid the metrics are defined on)"""
+    size = int(config["image_size"])
+    limit = None if args.max_batches is None else args.max_batches * args.batch_size
+    if args.images:
+        imgs = np.load(args.images)
+        if imgs.dtype != np.uint8 or imgs.ndim != 4 or imgs.shape[1:] != (size, size, channels):
+            raise SystemExit(f"--images: expected uint8 [N, {size}, {size}, {channels}], got {imgs.dtype} {imgs.shape}")
+        return imgs[:limit]
+    from utils import DATA_DIR, get_dataloader
+    loader = get_dataloader(config, data_root=DATA_DIR, device="cpu", train=False)[0]
+    out = []
+    for g, (x, _) in enumerate(loader):
+        if args.max_batches is not None and g >= args.max_batches:
+            break
+        out.append(to_u8(x).numpy())
+    return np.concatenate(out)
+
+
+def main():
+    args = parse_args()
+    device = "cuda:0"
+    torch.cuda.set_device(0)
+    model, config, channels = load_model(args, device)
+    images = load_images(args, config, channels)
+    n, h, w, _ = images.shape
+    kw = chain_options(args)
+    if args.task == "inpaint":
+        kw["mask"] = args.mask if args.mask in MASKS else load_mask(args.mask, n, h, w, channels)
+
+    print(f"Scoring {args.task} on {n} images with {'synthetic weights' if args.synthetic else args.saved_model}.")
+    t0 = time.time()
+    result = evaluate_restoration(model, images, args.task, batch_size=args.batch_size, seed=args.seed, **kw)
+    torch.cuda.synchronize()
+    print(f"Total time: {time.time() - t0:.2f} s")
+
+    settings = dict(checkpoint=None if args.synthetic else args.saved_model, synthetic=args.synthetic, model=config["model"],
+                    task=args.task, images=args.images or f"{config['dataset']} test split", n_images=n, batch_size=args.batch_size,
+                    seed=args.seed, **chain_options(args))
+    if args.task == "inpaint":
+        settings["mask"] = args.mask
+    out = dict(settings=settings, metrics=report(result))
+    print(json.dumps(out, indent=4))
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(out, f, indent=4)
+
+
+if __name__ == "__main__":
+    main()

@@ -23,35 +23,7 @@ import torch
 from models import DDPM, DownsampleDDPM, Unet
 from utils import CHECKPOINT_DIR, SAMPLE_DIR, get_color_channels, get_model_state_dict, load_checkpoint_file
 from utils import synthetic as syn
-
-MASKS = ("center", "left", "half", "lines")
-
-
-def make_mask(kind, n, h, w):
-    """[N, 1, H, W] float {0, 1}, 1 = known."""
-    m = torch.ones(n, 1, h, w)
-    if kind == "center":
-        m[:, :, h // 4:h - h // 4, w // 4:w - w // 4] = 0
-    elif kind == "left":
-        m[:, :, :, :w // 2] = 0
-    elif kind == "half":
-        m[:, :, h // 2:, :] = 0
-    elif kind == "lines":
-        m[:, :, 1::2, :] = 0
-    else:
-        raise ValueError(f"unknown mask {kind!r}: one of {MASKS} or a .npy file")
-    return m
-
-
-def load_mask(path, n, h, w, c):
-    a = np.load(path)
-    if a.ndim == 2:
-        a = a[None]
-    if a.ndim == 3:
-        a = a[..., None]
-    if a.ndim != 4 or a.shape[1:3] != (h, w) or a.shape[3] not in (1, c) or a.shape[0] not in (1, n):
-        raise ValueError(f"mask file {path}: expected [H, W], [N, H, W] or [N, H, W, 1|C] with H, W = {h}, {w}, got {a.shape}")
-    return torch.from_numpy(np.ascontiguousarray(a.transpose(0, 3, 1, 2))).float().expand(n, -1, -1, -1)
+from utils.restoration_metrics import MASKS, load_mask, make_mask
 
 
 def to_u8_range(x):

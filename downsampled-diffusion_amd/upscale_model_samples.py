@@ -25,6 +25,7 @@ import torch
 from models import DDPM, DownsampleDDPM, Unet
 from utils import CHECKPOINT_DIR, SAMPLE_DIR, OutputStage, get_color_channels, get_model_state_dict, load_checkpoint_file
 from utils import synthetic as syn
+from utils.restoration_metrics import pool
 
 
 def main():
@@ -77,7 +78,7 @@ def main():
         raise SystemExit(f"--images: expected uint8 [N, {size // s}, {size // s}, {c}] or [N, {size}, {size}, {c}], got {imgs.dtype} {imgs.shape}")
     y_all = torch.from_numpy(imgs.astype(np.float32)).permute(0, 3, 1, 2) / 255 * 2 - 1
     if imgs.shape[1] == size:
-        y_all = torch.nn.functional.avg_pool2d(y_all, s)
+        y_all = pool(y_all, s)
     n = y_all.shape[0]
     lowres = ((y_all + 1) * 127.5).round().clamp(0, 255).permute(0, 2, 3, 1).numpy().astype(np.uint8)
 

@@ -1,0 +1,161 @@
+"""Full-reference scoring of the two restoration paths: degrade a set of ground-truth images, restore them
+with ``model.inpaint`` (RePaint, section 3.5) or ``model.super_resolve`` (DDNM, section 3.6) and measure PSNR and SSIM of the result
+and of network-free baselines against the originals.  The metrics are ``ddk.ops.image_metrics`` (HIP); torch does the degradations,
+the baselines and the bookkeeping.
+
+Images travel as uint8 [N, H, W, C], the format the CLIs write; a model sees u8 / 255 * 2 - 1 in NCHW, as the training data is
+mapped.  The mask kinds and the pooling live here and the CLIs (inpaint_model_samples.py, upscale_model_samples.py,
+evaluate_restoration.py) import them, so a score is of the degradation the sampling CLIs apply.
+"""
+import math
+
+import numpy as np
+import torch
+
+MASKS = ("center", "left", "half", "lines")
+TASKS = ("inpaint", "sr")
+
+
+# ------------------------------------------------------------------ degradations
+def make_mask(kind, n, h, w):
+    """[N, 1, H, W] float {0, 1}, 1 = known."""
+    m = torch.ones(n, 1, h, w)
+    if kind == "center":
+        m[:, :, h // 4:h - h // 4, w // 4:w - w // 4] = 0
+    elif kind == "left":
+        m[:, :, :, :w // 2] = 0
+    elif kind == "half":
+        m[:, :, h // 2:, :] = 0
+    elif kind == "lines":
+        m[:, :, 1::2, :] = 0
+    else:
+        raise ValueError(f"unknown mask {kind!r}: one of {MASKS} or a .npy file")
+    return m
+
+
+def load_mask(path, n, h, w, c):
+    a = np.load(path)
+    if a.ndim == 2:
+        a = a[None]
+    if a.ndim == 3:
+        a = a[..., None]
+    if a.ndim != 4 or a.shape[1:3] != (h, w) or a.shape[3] not in (1, c) or a.shape[0] not in (1, n):
+        raise ValueError(f"mask file {path}: expected [H, W], [N, H, W] or [N, H, W, 1|C] with H, W = {h}, {w}, got {a.shape}")
+    return torch.from_numpy(np.ascontiguousarray(a.transpose(0, 3, 1, 2))).float().expand(n, -1, -1, -1)
+
+
+def pool(x, scale):
+    """scale x scale average pooling of [N, C, H, W]: the degradation of the super-resolution task (A of section 3.6)."""
+    return torch.nn.functional.avg_pool2d(x, scale)
+
+
+# ------------------------------------------------------------------ uint8 <-> model range
+def from_u8(images):
+    """uint8 [N, H, W, C] (numpy or torch) -> float32 [N, C, H, W] in [-1, 1]."""
+    t = torch.as_tensor(images)
+    if t.dtype != torch.uint8 or t.dim() != 4:
+        raise ValueError(f"images must be uint8 [N, H, W, C], got {t.dtype} {tuple(t.shape)}")
+    return t.float().permute(0, 3, 1, 2) / 255 * 2 - 1
+
+
+def to_u8(x):
+    """[N, C, H, W] in [-1, 1] (values outside are clamped) -> uint8 [N, H, W, C], rounded to nearest; inverts from_u8 exactly."""
+    return ((x.float() + 1) * 127.5).round().clamp(0, 255).permute(0, 2, 3, 1).to(torch.uint8).contiguous()
+
+
+# ------------------------------------------------------------------ baselines (no network)
+def replicate(y, scale):
+    """nearest upsampling: every low-resolution pixel repeated scale x scale (A+ of section 3.6)."""
+    return y.repeat_interleave(scale, dim=2).repeat_interleave(scale, dim=3)
+
+
+def bicubic(y, scale):
+    return torch.nn.functional.interpolate(y, scale_factor=scale, mode="bicubic", align_corners=False)
+
+
+def mean_fill(x, mask):
+    """hidden pixels (mask 0) take their image's per-channel mean over the known pixels (0 if nothing is known)."""
+    m = mask.expand_as(x)
+    mean = (x * m).sum(dim=(2, 3), keepdim=True) / m.sum(dim=(2, 3), keepdim=True).clamp(min=1)
+    return torch.where(m != 0, x, mean.expand_as(x))
+
+
+# ------------------------------------------------------------------ scoring
+def summarise(values):
+    """mean and standard error of the mean (sample standard deviation / sqrt(n); nan for one image) of per-image values; images
+    without a value (nan, e.g. the hidden-pixel PSNR of an image with nothing hidden) are left out."""
+    v = np.asarray(values, dtype=np.float64)
+    v = v[~np.isnan(v)]
+    if v.size == 0:
+        return dict(mean=math.nan, stderr=math.nan, n=0)
+    with np.errstate(invalid="ignore"):            # inf - inf: identical images have no spread to report
+        stderr = float(v.std(ddof=1) / math.sqrt(v.size)) if v.size > 1 else math.nan
+    return dict(mean=float(v.mean()), stderr=stderr, n=int(v.size))
+
+
+def _score(ops, cand_u8, ref_u8, hidden, device):
+    m = ops.image_metrics(cand_u8.to(device), ref_u8.to(device))
+    out = dict(psnr=m["psnr"].numpy(), ssim=m["ssim"].double().numpy())
+    if hidden is not None:
+        out["psnr_hidden"] = ops.image_metrics(cand_u8.to(device), ref_u8.to(device), mask=hidden.to(device))["psnr"].numpy()
+    return out
+
+
+@torch.no_grad()
+def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234, mask="center", scale=4, **chain):
+    """Degrade, restore and score ``images_uint8`` (uint8 [N, H, W, C] of the model's size).
+
+    task "inpaint": ``mask`` is one of MASKS or a {0, 1} tensor broadcastable to [N, 1|C, H, W] (1 = known); ``chain`` goes to
+    ``model.inpaint`` (respacing, jump_length, jump_n_sample).  Baseline: mean_fill.  Every method also gets psnr_hidden, the PSNR
+    over the hidden pixels only.
+    task "sr": the images are average-pooled by ``scale``; ``chain`` goes to ``model.super_resolve`` (respacing, ddim, eta).
+    Baselines: replicate, bicubic.  consistency: per image max |pool(x_out) - y| * 127.5 (uint8 levels) of the model's float output,
+    consistency_u8 the same of the uint8 image that is scored (rounding alone may cost 0.5, clamping to [0, 255] more).
+    Batch g draws x_T and its Philox key from seed + g, as the sampling CLIs do.
+
+    Returns {"n_images", "methods": {name: {"psnr": [N], "ssim": [N], ...}}, "images": {name: uint8 [N, H, W, C]}} and, for "sr",
+    "consistency" / "consistency_u8" [N]; "restored" is the model's entry."""
+    from ddk import ops
+    if task not in TASKS:
+        raise ValueError(f"unknown task {task!r}: one of {TASKS}")
+    x_all = from_u8(images_uint8)
+    ref = torch.as_tensor(images_uint8).contiguous()
+    n, c, h, w = x_all.shape
+    if n < 1 or batch_size < 1:
+        raise ValueError("evaluate_restoration needs at least one image and batch_size >= 1")
+    device = model.betas.device
+    images, extra, hidden = {}, {}, None
+    if task == "inpaint":
+        m_all = make_mask(mask, n, h, w) if isinstance(mask, str) else torch.as_tensor(mask).float().expand(n, -1, h, w)
+        restore = lambda i: model.inpaint(x_all[i:i + batch_size].to(device), m_all[i:i + batch_size].to(device), **chain)
+        images["mean_fill"] = to_u8(mean_fill(x_all, m_all))
+        hidden = (m_all.amin(dim=1) == 0).to(torch.uint8).contiguous()
+    else:
+        scale = int(scale)
+        if scale < 2 or h % scale or w % scale:
+            raise ValueError(f"scale {scale} must be >= 2 and divide the image size {h} x {w}")
+        y_all = pool(x_all, scale)
+        restore = lambda i: model.super_resolve(y_all[i:i + batch_size].to(device), scale, **chain)
+        images["replicate"] = to_u8(replicate(y_all, scale))
+        images["bicubic"] = to_u8(bicubic(y_all, scale))
+    outs = []
+    for g, i in enumerate(range(0, n, batch_size)):
+        torch.manual_seed(seed + g)               # x_T and the Philox key of batch g
+        out = restore(i)
+        outs.append((out[0] if isinstance(out, tuple) else out).float().cpu())      # a dDDPM returns (x_out, z)
+    x_out = torch.cat(outs)
+    images = dict(restored=to_u8(x_out), **images)
+    if task == "sr":
+        extra["consistency"] = ((pool(x_out, scale) - y_all).abs().amax(dim=(1, 2, 3)) * 127.5).double().numpy()
+        extra["consistency_u8"] = ((pool(from_u8(images["restored"]), scale) - y_all).abs().amax(dim=(1, 2, 3)) * 127.5).double().numpy()
+    methods = {name: _score(ops, img, ref, hidden, device) for name, img in images.items()}
+    return dict(n_images=n, methods=methods, images={k: v.numpy() for k, v in images.items()}, **extra)
+
+
+def report(result):
+    """evaluate_restoration's per-image arrays as {"mean", "stderr", "n"} entries, JSON-ready."""
+    out = {name: {k: summarise(v) for k, v in m.items()} for name, m in result["methods"].items()}
+    for k in ("consistency", "consistency_u8"):
+        if k in result:
+            out[k] = dict(summarise(result[k]), max=float(np.max(result[k])))
+    return out

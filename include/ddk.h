@@ -335,6 +335,17 @@ int ddk_vlb_terms(const float* x, const float* x_t, const float* eps_hat, const 
                   size_t workspace_bytes, ddk_stream_t s);
 /* per_sample[b] = sum_i (a - b)^2 over the sample's `per` elements (ddpm.py:279, utils/utils.py:34-40). */
 int ddk_sq_err_sum(const float* a, const float* b, float* per_sample, int B, long long per, ddk_stream_t s);
+/* Full-reference quality of uint8 images a, b [N][H][W][C] (C in 1..4, H, W >= 11), per image n:
+ *   sq_sum_count[n] = {sum (a - b)^2, number of elements summed}, exact unsigned 64-bit integers, over every element or, with
+ *     mask [N][H][W] (uint8, may be null), over all channels of the pixels whose mask is nonzero.  The caller forms
+ *     PSNR = 10 log10(255^2 count / sum) in double (sum == 0: inf, count == 0: nan).
+ *   ssim[n] = SSIM of Wang et al. 2004: 11 x 11 Gaussian window (sigma 1.5), the (H - 10) x (W - 10) valid windows of every channel,
+ *     population moments, C1 = (0.01 255)^2, C2 = (0.03 255)^2, the mean over windows and channels; the mask does not apply.
+ *     fp32 on values shifted by 128, taps and partial sums in a fixed order: the same bits from run to run and for any N.
+ * workspace: ddk_image_metrics_workspace_bytes; workspace and sq_sum_count 8-byte aligned. */
+size_t ddk_image_metrics_workspace_bytes(int N, int H, int W, int C);
+int ddk_image_metrics(const uint8_t* a, const uint8_t* b, const uint8_t* mask, int N, int H, int W, int C,
+                      unsigned long long* sq_sum_count, float* ssim, void* workspace, size_t workspace_bytes, ddk_stream_t s);
 
 /* ------------------------------------------------------------------ whole-UNet plan (unet.py:74-104, eval mode) */
 typedef struct ddk_unet_config {
