@@ -318,6 +318,7 @@ struct RestoreOps {
     const float* y;               // NHWC [B][H/n][W/n][n_out]: what the n x n block means of x0 are set to
     int n;                        // 2, 4 or 8, dividing H and W
     int H, W;                     // the map the blocks lie in (filled by the chain entry / the lone op; the other kinds need only `per`)
+    const float* mask;            // StepKind::RestoreMasked only: [B][H/n][W/n], nonzero = measured, shared by the channels; n may be 1
 };
 // likelihood sweep (ddk_vlb_sweep_run): one step's operands besides the UNet's
 struct VlbStep {
@@ -340,6 +341,8 @@ enum class StepKind {
     Multistep,    // DPM-Solver++(2M): x <- (c1 x0 + c2 x) + c3 x0_hist, x0_hist <- x0: c_recip .. c2, c3, x0_hist; no draw
     Inpaint,      // RePaint: Ancestral's op, then x = mask ? x_kn : x, then the optional jump: c_recip .. sigma, inp; Philox only
     Restore,      // DDNM super-resolution: Ancestral's x0 shifted so its n x n block means equal y, then the update: c_recip .. sigma, rst; Philox only
+    RestoreMasked,  // DDNM for A = mask o pool_n, n in {1, 2, 4, 8}: Restore's step where the block's rst.mask is nonzero,
+                  // Ancestral's where it is zero (a select; n = 1: x0' = y, no arithmetic): c_recip .. sigma, rst with mask; Philox only
     Vlb           // likelihood sweep: no update, the step's VLB terms to vlb->partials (vlb_rule() fills the rest from *vlb)
 };
 struct StepRule {
@@ -371,7 +374,7 @@ struct ChainHooks {
     uint64_t seed;                // without chain_state
     uint32_t stream_id;
 };
-// the unfused tail's last kernel, given eps_hat in memory: the rule's update of x (Ancestral, Multistep, Inpaint, Restore) or the sweep's
+// the unfused tail's last kernel, given eps_hat in memory: the rule's update of x (Ancestral, Multistep, Inpaint, Restore, RestoreMasked) or the sweep's
 // reduction of the step's terms (Vlb); `who` names the caller in messages
 int p_update(const StepRule& r, const float* eps_hat, const int64_t* t, int B, long long per, const ChainHooks& h, hipStream_t st,
              const char* who = "p_update");
@@ -394,7 +397,8 @@ struct TailIn {
 // the shapes the fused tail takes: C in {32,64,128,256}; the Multistep, Inpaint, Restore and Vlb instantiations stop at C = 128 (at
 // 256 the plain one spills already, and theirs hold more in the prologue).  Restore also needs every 128-pixel tile to hold whole
 // rows of blocks, 128 % (W n) == 0 with W, n = restore_w, restore_n (W = 32: n <= 4; W = 16: n <= 8; W = 64: n = 2); the other
-// kinds ignore the two.  The one predicate of fused_tail_parts (unet_plan.hip) and final_tail.
+// kinds ignore the two.  RestoreMasked: as Restore for n >= 2; n = 1 is pointwise and needs no whole blocks, so every shape of the
+// Multistep / Inpaint kinds is taken.  The one predicate of fused_tail_parts (unet_plan.hip) and final_tail.
 bool final_tail_ok(int HW, int C, int groups, int n_out, int np, StepKind kind, int restore_w = 0, int restore_n = 0);
 int final_tail(const TailIn& in, const StepRule& r, const int64_t* t, const ChainHooks& h, hipStream_t st);
 

@@ -218,12 +218,50 @@ __device__ __forceinline__ float rst_finish(float x, float x0, float m, float y,
     return __fadd_rn(mean, __fmul_rn(sg, z));
 }
 
+// DDNM with a mask over the measurements, A = M o pool_n: a measured block takes rst_finish's x0', a block that
+// is not measured keeps its clipped x0 -- a select on the mask, so whatever y holds there (NaN included) reaches no result.  n = 1
+// (inpainting): x0' = y where measured, no arithmetic, so at row 0 (c1 = 1, c2 = 0, no draw) known pixels come back bit for bit.
+// With every block measured rstm_finish is rst_finish.  The arithmetic of both tails, as rst_* above.
+__device__ __forceinline__ float rstm_finish(float x, float x0, float m, float y, float mk, float z, float c1, float c2, float sg) {
+    const float x0p = mk != 0.0f ? __fadd_rn(x0, __fsub_rn(y, m)) : x0;
+    const float mean = __fadd_rn(__fmul_rn(c1, x0p), __fmul_rn(c2, x));
+    return __fadd_rn(mean, __fmul_rn(sg, z));
+}
+
+__device__ __forceinline__ float rstm_point(float x, float e, float y, float mk, float z, float cr, float crm1, float c1, float c2, float sg) {
+    const float x0p = mk != 0.0f ? y : rst_x0(x, e, cr, crm1);
+    const float mean = __fadd_rn(__fmul_rn(c1, x0p), __fmul_rn(c2, x));
+    return __fadd_rn(mean, __fmul_rn(sg, z));
+}
+
+__device__ __forceinline__ float4 rstm_point4(float4 xv, float4 ev, float4 yv, float4 mv, float4 zv, float cr, float crm1, float c1, float c2,
+                                              float sg) {
+    float4 o;
+    o.x = rstm_point(xv.x, ev.x, yv.x, mv.x, zv.x, cr, crm1, c1, c2, sg);
+    o.y = rstm_point(xv.y, ev.y, yv.y, mv.y, zv.y, cr, crm1, c1, c2, sg);
+    o.z = rstm_point(xv.z, ev.z, yv.z, mv.z, zv.z, cr, crm1, c1, c2, sg);
+    o.w = rstm_point(xv.w, ev.w, yv.w, mv.w, zv.w, cr, crm1, c1, c2, sg);
+    return o;
+}
+
+// the n = 1 mask values of elements e0 .. e0 + 3 (e0 % 4 == 0) of an NHWC map with C channels, mk pointing at the map's first pixel:
+// one pixel when 4 divides C, else up to three (a 3-channel pixel model)
+__device__ __forceinline__ float4 rstm_mask4(const float* __restrict__ mk, unsigned e0, unsigned C) {
+    if ((C & 3u) == 0u) {
+        const float m = mk[e0 / C];
+        return make_float4(m, m, m, m);
+    }
+    return make_float4(mk[e0 / C], mk[(e0 + 1u) / C], mk[(e0 + 2u) / C], mk[(e0 + 3u) / C]);
+}
+
 __device__ __forceinline__ float comp4(float4 v, int k) { return k == 0 ? v.x : k == 1 ? v.y : k == 2 ? v.z : v.w; }
 
 // The last kernel of an unfused Restore step.  p_update_kernel's flat float4 loop cannot see an element's neighbours, so here a
 // thread owns one (image, block, channel): it sums the block's n x n clipped x0 from x and eps_hat, then updates those n x n
 // elements of x in place (nobody else reads them).  Any n_out, any H, W that n divides.  Element e of the NHWC latent takes
 // component e & 3 of the Philox draw of float4 e >> 2, the Ancestral kind's keying; the counter and the key as in p_update_kernel.
+// MASKED (StepKind::RestoreMasked, n >= 2): the block's mask value, uniform per thread, selects rstm_finish's x0'.
+template <bool MASKED>
 __global__ __launch_bounds__(256) void p_update_restore_kernel(const StepRule r, const float* __restrict__ eps_hat,
                                                                const int64_t* __restrict__ t, int B, int n_out, uint64_t seed,
                                                                uint32_t stream, const int64_t* __restrict__ chain_state,
@@ -252,13 +290,40 @@ __global__ __launch_bounds__(256) void p_update_restore_kernel(const StepRule r,
             },
             n);
         const float yv = r.rst.y[i];                                      // y is [B][H/n][W/n][n_out]: this thread's index
+        float mk = 1.0f;
+        if constexpr (MASKED) mk = r.rst.mask[i / n_out];                 // the mask is [B][H/n][W/n]
         for (int bi = 0; bi < n; ++bi)
             for (int bj = 0; bj < n; ++bj) {
                 const long long e = e0 + ((long long)bi * W + bj) * n_out;
                 const float xv = x[e];
                 const float z = comp4(philox_normal4((unsigned long long)(e >> 2), (uint32_t)tb, stream, seed), (int)(e & 3));
-                x[e] = rst_finish(xv, rst_x0(xv, eps_hat[e], cr, crm1), m, yv, z, a1, a2, sg);
+                if constexpr (MASKED) x[e] = rstm_finish(xv, rst_x0(xv, eps_hat[e], cr, crm1), m, yv, mk, z, a1, a2, sg);
+                else x[e] = rst_finish(xv, rst_x0(xv, eps_hat[e], cr, crm1), m, yv, z, a1, a2, sg);
             }
+    }
+}
+
+// The last kernel of an unfused RestoreMasked step with n = 1 (inpainting): pointwise, so p_update_kernel's flat float4 loop with one
+// Philox call per float4; y has x's layout, the mask is [B][H][W] and the float4's elements look up their own pixels (rstm_mask4).
+__global__ __launch_bounds__(256) void p_update_restore_point_kernel(const StepRule r, const float* __restrict__ eps_hat,
+                                                                     const int64_t* __restrict__ t, long long per4, long long total4,
+                                                                     int n_out, uint64_t seed, uint32_t stream,
+                                                                     const int64_t* __restrict__ chain_state, int64_t* dec_counter) {
+    if (dec_counter && blockIdx.x == 0 && threadIdx.x == 0) *dec_counter -= 1;
+    if (chain_state) {
+        seed = (uint64_t)chain_state[1];
+        stream = (uint32_t)chain_state[2];
+    }
+    float4* __restrict__ x = reinterpret_cast<float4*>(r.x);
+    const long long hw = (long long)r.rst.H * r.rst.W;
+    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total4; i += (long long)gridDim.x * 256) {
+        const long long b = i / per4;
+        const int64_t tb = t[b];
+        const float cr = r.c_recip[tb], crm1 = r.c_recipm1[tb], a1 = r.c1[tb], a2 = r.c2[tb], sg = tb > 0 ? r.sigma[tb] : 0.0f;
+        const float4 xv = x[i], ev = reinterpret_cast<const float4*>(eps_hat)[i], yv = reinterpret_cast<const float4*>(r.rst.y)[i];
+        const float4 mv = rstm_mask4(r.rst.mask + b * hw, (unsigned)(i - b * per4) * 4u, (unsigned)n_out);      // host: per < 2^31
+        const float4 zv = philox_normal4((unsigned long long)i, (uint32_t)tb, stream, seed);
+        x[i] = rstm_point4(xv, ev, yv, mv, zv, cr, crm1, a1, a2, sg);
     }
 }
 
@@ -341,7 +406,7 @@ struct TailParams {
     const float* c3;
     // StepKind::Inpaint: the known latent, its mask and the per-row tables
     InpaintOps inp;
-    // StepKind::Restore: the low-resolution image, the block and the map's height and width
+    // StepKind::Restore / RestoreMasked: the low-resolution image, the block, the map's height and width and (RestoreMasked) the mask
     RestoreOps rst;
 };
 
@@ -358,10 +423,14 @@ struct TailParams {
 // each of the thread's four elements is requested in the prologue; in phase 2 the owners write their clipped x0 over eps_hat in LDS,
 // and one barrier later every owner sums its elements' blocks from LDS (rst_block_mean) and finishes the update of
 // p_update_restore_kernel: neither x0 nor eps_hat goes through memory.
+// RestoreMasked (ddk_sampler_run_restore_masked, x given, Philox only): n >= 2 is Restore's tail with the mask value of each element's
+// block requested beside its y; n = 1 (uniform per launch) needs no whole blocks in the tile: the y float4 and the mask are requested where
+// Inpaint requests known and mask, and phase 2 is p_update_restore_point_kernel's select, with no second barrier.  No LDS beyond Restore's.
 template <int LPP, int VPL, StepKind K>
 __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
     static_assert(K != StepKind::Eps, "the plain forward runs the Ancestral instantiation with p.x null");
-    constexpr bool VLB = K == StepKind::Vlb, MS = K == StepKind::Multistep, INP = K == StepKind::Inpaint, RST = K == StepKind::Restore;
+    constexpr bool VLB = K == StepKind::Vlb, MS = K == StepKind::Multistep, INP = K == StepKind::Inpaint, RST = K == StepKind::Restore,
+                   RSTM = K == StepKind::RestoreMasked;
     constexpr int PPW = 64 / LPP;                    // pixels per wave and iteration
     constexpr int PPI = 16 * PPW;                    // ... per iteration of the 16-wave workgroup
     constexpr int NIT = 128 / PPI;                   // 4 at C = 128 / 256, 2 at C = 64, 1 at C = 32
@@ -407,7 +476,8 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
     float4 xk0 = xv0, mk0 = xv0, z30 = xv0;           // INP: x_kn, the mask, the jump's draw
     float ja = 0.f, jb = 0.f;
     bool jump = false;
-    float yv0[4] = {0.f, 0.f, 0.f, 0.f};              // RST: y of the block of each of the thread's four elements
+    float yv0[4] = {0.f, 0.f, 0.f, 0.f};              // RST, RSTM: y of the block of each of the thread's four elements
+    float mv0[4] = {0.f, 0.f, 0.f, 0.f};              // RSTM: ... and its mask value
     VlbCoef kc{};
     if ((VLB || p.x) && tid < cnt4) {
         const uint64_t seed = p.chain_state ? (uint64_t)p.chain_state[1] : p.seed;
@@ -434,6 +504,24 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
             xk0 = inp_known4(reinterpret_cast<const float4*>(p.inp.known)[i],
                              philox_normal4((unsigned long long)i, (uint32_t)tb, stream | INPAINT_Z2_BIT, seed), ka, kb);
             if (jump) z30 = philox_normal4((unsigned long long)i, (uint32_t)tb, stream | INPAINT_Z3_BIT, seed);
+        }
+        if constexpr (RSTM) {
+            if (p.rst.n == 1) {                        // one block per launch: uniform
+                const float4 yv = reinterpret_cast<const float4*>(p.rst.y)[i];
+                const float4 mv = rstm_mask4(p.rst.mask + pix0, (unsigned)tid * 4u, (unsigned)p.n_out);
+                yv0[0] = yv.x; yv0[1] = yv.y; yv0[2] = yv.z; yv0[3] = yv.w;
+                mv0[0] = mv.x; mv0[1] = mv.y; mv0[2] = mv.z; mv0[3] = mv.w;
+            } else {
+                const int W = p.rst.W, n = p.rst.n, Wn = W / n;
+                const long long yrow0 = ((long long)b * p.HW + tile * 128) / (W * n);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int lp = (tid * 4 + j) / p.n_out, c = tid * 4 + j - lp * p.n_out, row = lp / W, col = lp - row * W;
+                    const long long blk = (yrow0 + row / n) * Wn + col / n;
+                    yv0[j] = p.rst.y[blk * p.n_out + c];
+                    mv0[j] = p.rst.mask[blk];
+                }
+            }
         }
         if constexpr (RST) {
             const int W = p.rst.W, n = p.rst.n, Wn = W / n;
@@ -515,7 +603,19 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
         if (tid == 0) p.vlb_part[((long long)tb * p.B + b) * p.np + tile] = make_float2(acc, sq);
         return;
     }
-    if constexpr (RST) {
+    if constexpr (RSTM) {
+        if (p.rst.n == 1) {
+            if (tid < cnt4) {
+                const float4 ev = reinterpret_cast<const float4*>(es)[tid];
+                if (p.eps_out) reinterpret_cast<float4*>(p.eps_out)[e4 + tid] = ev;
+                reinterpret_cast<float4*>(p.x)[e4 + tid] =
+                    rstm_point4(xv0, ev, make_float4(yv0[0], yv0[1], yv0[2], yv0[3]), make_float4(mv0[0], mv0[1], mv0[2], mv0[3]), zv0, cr, crm1,
+                                a1, a2, sg);
+            }
+            return;
+        }
+    }
+    if constexpr (RST || RSTM) {
         float x0v[4] = {0.f, 0.f, 0.f, 0.f};
         if (tid < cnt4) {
             const float4 ev = reinterpret_cast<const float4*>(es)[tid];
@@ -534,7 +634,8 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
                 const int lp = (tid * 4 + j) / p.n_out, c = tid * 4 + j - lp * p.n_out, row = lp / W, col = lp - row * W;
                 const float* blk = es + ((row & ~(n - 1)) * W + (col & ~(n - 1))) * p.n_out + c;
                 const float m = rst_block_mean([&](int bi, int bj) { return blk[(bi * W + bj) * p.n_out]; }, n);
-                o[j] = rst_finish(xa[j], x0v[j], m, yv0[j], za[j], a1, a2, sg);
+                if constexpr (RSTM) o[j] = rstm_finish(xa[j], x0v[j], m, yv0[j], mv0[j], za[j], a1, a2, sg);
+                else o[j] = rst_finish(xa[j], x0v[j], m, yv0[j], za[j], a1, a2, sg);
             }
             reinterpret_cast<float4*>(p.x)[e4 + tid] = make_float4(o[0], o[1], o[2], o[3]);
         }
@@ -559,8 +660,8 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
     }
 }
 
-static bool restore_block_ok(const RestoreOps& o) {
-    return (o.n == 2 || o.n == 4 || o.n == 8) && o.H > 0 && o.W > 0 && o.H % o.n == 0 && o.W % o.n == 0;
+static bool restore_block_ok(const RestoreOps& o, bool point_ok = false) {
+    return (o.n == 2 || o.n == 4 || o.n == 8 || (point_ok && o.n == 1)) && o.H > 0 && o.W > 0 && o.H % o.n == 0 && o.W % o.n == 0;
 }
 
 template <StepKind K>
@@ -581,7 +682,9 @@ bool final_tail_ok(int HW, int C, int groups, int n_out, int np, StepKind kind, 
     if (groups <= 0 || groups > 64 || C % groups || (C / groups) % 4) return false;
     if (n_out < 1 || n_out > 8 || (128 * n_out) % 4) return false;
     // the restore tail forms block means from the tile's x0 in LDS: the 128-pixel tile must hold whole rows of n x n blocks
-    if (kind == StepKind::Restore && !(restore_w > 0 && restore_n > 0 && 128 % (restore_w * restore_n) == 0)) return false;
+    // (the masked kind the same for n >= 2; its n = 1 is pointwise)
+    const bool blocks = kind == StepKind::Restore || (kind == StepKind::RestoreMasked && restore_n != 1);
+    if (blocks && !(restore_w > 0 && restore_n > 0 && 128 % (restore_w * restore_n) == 0)) return false;
     return np > 0 && HW == np * 128 && np * groups <= 1024;
 }
 
@@ -589,7 +692,7 @@ int final_tail(const TailIn& in, const StepRule& r, const int64_t* t, const Chai
     DDK_REQUIRE(in.raw && in.part && in.gamma && in.beta && in.w && in.B > 0, "final_tail: null pointer");
     DDK_REQUIRE(final_tail_ok(in.HW, in.C, in.groups, in.n_out, in.np, r.kind, r.rst.W, r.rst.n),
                 "final_tail: needs C in {32,64,128,256} (the VLB, multistep, inpainting and restore kinds: C <= 128), n_out <= 8, "
-                "H*W == tiles * 128 (restore: 128 % (W n) == 0)");
+                "H*W == tiles * 128 (restore with n >= 2: 128 % (W n) == 0)");
     DDK_REQUIRE(aligned16(in.raw) && aligned16(in.gamma) && aligned16(in.beta) && aligned16(in.w) && aligned16(r.eps_out) && aligned16(r.x) &&
                     aligned16(r.noise) && r.noise_step_stride % 4 == 0, "final_tail: alignment");
     const bool tables = r.x && t && r.c_recip && r.c_recipm1 && r.c1 && r.c2;     // what every kind but Eps reads
@@ -622,6 +725,13 @@ int final_tail(const TailIn& in, const StepRule& r, const int64_t* t, const Chai
                         "final_tail: the restore step needs x, t, the tables, y, n in {2,4,8} dividing H and W, H*W of the map and no injected noise");
             p.rst = r.rst;
             return launch_tail<StepKind::Restore>(p, in.B, st);
+        case StepKind::RestoreMasked:
+            DDK_REQUIRE(tables && r.sigma && !r.noise && r.rst.y && r.rst.mask && restore_block_ok(r.rst, true) &&
+                            (long long)r.rst.H * r.rst.W == in.HW && (r.rst.n != 1 || aligned16(r.rst.y)),
+                        "final_tail: the masked restore step needs x, t, the tables, y (aligned at n = 1), the mask, n in {1,2,4,8} dividing H and W, "
+                        "H*W of the map and no injected noise");
+            p.rst = r.rst;
+            return launch_tail<StepKind::RestoreMasked>(p, in.B, st);
         case StepKind::Vlb: {
             DDK_REQUIRE(r.vlb && tables && !r.eps_out && h.chain_state, "final_tail: the VLB epilogue needs the sweep's step, x, t, the tables and the chain state");
             const VlbStep& v = *r.vlb;
@@ -852,8 +962,25 @@ int p_update(const StepRule& r, const float* eps_hat, const int64_t* t, int B, l
             const long long hw = (long long)r.rst.H * r.rst.W;
             if (per % hw || per / hw > INT_MAX) return bad("per must be H * W * channels");
             const int n_out = (int)(per / hw);
-            hipLaunchKernelGGL(p_update_restore_kernel, dim3(grid1d(B * per / (r.rst.n * r.rst.n))), dim3(256), 0, st, r, eps_hat, t, B, n_out,
-                               h.seed, h.stream_id, h.chain_state, h.dec_counter);
+            hipLaunchKernelGGL(p_update_restore_kernel<false>, dim3(grid1d(B * per / (r.rst.n * r.rst.n))), dim3(256), 0, st, r, eps_hat, t, B,
+                               n_out, h.seed, h.stream_id, h.chain_state, h.dec_counter);
+            return check_launch("p_update_restore_kernel");
+        }
+        case StepKind::RestoreMasked: {  // n >= 2: Restore's kernel with the mask test; n = 1: pointwise float4s
+            if (!(r.sigma && r.rst.y && r.rst.mask)) return bad("null pointer");
+            if (r.noise) return bad("no injected noise (Philox only)");
+            if (!restore_block_ok(r.rst, true)) return bad("n must be 1, 2, 4 or 8 and divide H and W");
+            const long long hw = (long long)r.rst.H * r.rst.W;
+            if (per % hw || per / hw > INT_MAX || per > INT_MAX) return bad("per must be H * W * channels, below 2^31");
+            const int n_out = (int)(per / hw);
+            if (r.rst.n == 1) {
+                if (!aligned16(r.rst.y)) return bad("alignment");
+                hipLaunchKernelGGL(p_update_restore_point_kernel, grid, dim3(256), 0, st, r, eps_hat, t, per / 4, total4, n_out, h.seed, h.stream_id,
+                                   h.chain_state, h.dec_counter);
+                return check_launch("p_update_restore_point_kernel");
+            }
+            hipLaunchKernelGGL(p_update_restore_kernel<true>, dim3(grid1d(B * per / (r.rst.n * r.rst.n))), dim3(256), 0, st, r, eps_hat, t, B,
+                               n_out, h.seed, h.stream_id, h.chain_state, h.dec_counter);
             return check_launch("p_update_restore_kernel");
         }
         case StepKind::Vlb:       // no update: the sweep's reduction of the step's terms, a kernel of its own
@@ -943,6 +1070,18 @@ int ddk_p_sample_update_restore(float* x, const float* eps_hat, const float* y, 
     r.rst = RestoreOps{y, n, H, W};
     return p_update(r, eps_hat, t, B, (long long)H * W * channels, ChainHooks{nullptr, nullptr, seed, stream_id}, as_stream(s),
                     "p_sample_update_restore");
+}
+
+int ddk_p_sample_update_restore_masked(float* x, const float* eps_hat, const float* y, const float* mask, int n, const int64_t* t,
+                                       const float* c_recip, const float* c_recipm1, const float* c1, const float* c2, const float* sigma,
+                                       int B, int H, int W, int channels, uint64_t seed, uint32_t stream_id, ddk_stream_t s) {
+    DDK_REQUIRE(B > 0 && H > 0 && W > 0 && channels > 0, "p_sample_update_restore_masked: B / H / W / channels must be positive");
+    DDK_REQUIRE(mask || n != 1, "p_sample_update_restore_masked: n = 1 needs a mask (nothing would be constrained)");
+    // no mask: every block is measured, which is the Restore kind, its kernel and its bits
+    StepRule r{mask ? StepKind::RestoreMasked : StepKind::Restore, nullptr, x, nullptr, 0, 0, c_recip, c_recipm1, c1, c2, sigma};
+    r.rst = RestoreOps{y, n, H, W, mask};
+    return p_update(r, eps_hat, t, B, (long long)H * W * channels, ChainHooks{nullptr, nullptr, seed, stream_id}, as_stream(s),
+                    "p_sample_update_restore_masked");
 }
 
 int ddk_final_tail(const float* raw, const float* partials, int tiles_per_image, const float* gamma, const float* beta, float eps,

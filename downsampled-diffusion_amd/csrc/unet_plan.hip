@@ -89,7 +89,8 @@ struct ChainKey {
     const void* noise;                       // also in bufs; injected draws: no 16-step graph (see run_chain)
     int B, H, W, t_start, device;
     unsigned long long pack_epoch;
-    int restore_n = 0;                       // StepKind::Restore: the block (y itself is staged in the workspace)
+    int restore_n = 0;                       // StepKind::Restore, RestoreMasked: the block (y and the mask are staged in the workspace; the kind
+                                             // says whether a mask is present, so a masked and an unmasked chain never share a graph)
     bool operator==(const ChainKey& o) const {
         for (int i = 0; i < 12; ++i)
             if (bufs[i] != o.bufs[i]) return false;
@@ -1126,12 +1127,12 @@ struct StepArgs {
 };
 
 // tiles of the final tail when the end of the forward runs as ONE launch (final_tail_kernel), else 0.  cin = the final conv's
-// input channels (dimp[1]).  The Vlb, Multistep, Inpaint and Restore kinds take a subset of the shapes (final_tail_ok; Restore's
+// input channels (dimp[1]).  The Vlb, Multistep, Inpaint, Restore and RestoreMasked kinds take a subset of the shapes (final_tail_ok; the last two's
 // depends on its block, restore_n).
 static int fused_tail_parts(const ddk_unet& u, int B, int H, int W, int cin, StepKind kind, int restore_n = 0) {
     const int chan = u.generic ? pad32(u.cfg.chan) : u.cfg.chan, n_out = u.cfg.in_ch;
     const int npf = u.final_conv.has_wu ? conv_wino_stats_parts(B, H, W, cin, chan, GROUPS) : 0;
-    if (npf <= 0 || (kind == StepKind::Restore && !u.restore_fused)) return 0;
+    if (npf <= 0 || ((kind == StepKind::Restore || kind == StepKind::RestoreMasked) && !u.restore_fused)) return 0;
     return final_tail_ok(H * W, chan, GROUPS, n_out, npf, kind, W, restore_n) ? npf : 0;
 }
 
@@ -1336,7 +1337,8 @@ static int forward_core(const ddk_unet& u, const float* P, const float* x, int64
     const int npf = fused_tail_parts(u, B, H, W, cur_c, rule.kind, rule.rst.n);
     // a Restore step whose blocks do not fit the tail's tile (or with its fused tail switched off) still ends the forward in the plain
     // tail's one launch, eps_hat to the step's scratch, and updates x behind it: the same eps_hat, bit for bit, as its fused tail sees
-    const int npe = (npf == 0 && step && rule.kind == StepKind::Restore) ? fused_tail_parts(u, B, H, W, cur_c, StepKind::Eps) : 0;
+    // (the masked kind likewise)
+    const int npe = (npf == 0 && step && (rule.kind == StepKind::Restore || rule.kind == StepKind::RestoreMasked)) ? fused_tail_parts(u, B, H, W, cur_c, StepKind::Eps) : 0;
     if ((npf > 0 || npe > 0) && (!step || step->per == (long long)H * W * n_out)) {
         // one-pass Winograd conv with statistics, then GroupNorm + Mish + projection (+ the rule) in ONE launch
         DDK_TRY(run_conv_parts(c, u.final_conv, cur, cur_c, nullptr, 0, raw, H, W, chan));
@@ -1722,14 +1724,20 @@ static int check_timestep_map(const int64_t* map, int t_start, const char* who) 
 namespace ddk {
 // floats a chain keeps behind the sampler layout, by its rule: the multistep history [B][H][W][in_ch]; the inpainting op's known
 // latent and mask; the restore step's low-resolution image (room for n = 2, a quarter of the latent: every n fits).  The size
-// queries and sampler_chain's carve-up both come from here.
-static size_t chain_extra_floats(const ddk_unet& u, int B, int H, int W, StepKind kind) {
+// queries and sampler_chain's carve-up both come from here.  The masked restore step (restore_n = its block, 1 included): y of
+// that block, [B][H/n][W/n][in_ch], and the mask [B][H/n][W/n] behind it, and never less than the Restore kind's, whose chain a
+// call without a mask is (n = 1: a whole latent plus B H W; n = 2: a quarter of each; n = 4, 8: the Restore kind's quarter latent).
+static size_t chain_extra_floats(const ddk_unet& u, int B, int H, int W, StepKind kind, int restore_n = 0) {
     const size_t n = al4((size_t)B * H * W * u.cfg.in_ch);
+    if (kind == StepKind::RestoreMasked) {
+        const size_t nn = (size_t)restore_n * restore_n, m = al4(n / nn) + al4((size_t)B * H * W / nn);
+        return restore_n > 1 && m < al4(n / 4) ? al4(n / 4) : m;
+    }
     return kind == StepKind::Multistep ? n : kind == StepKind::Inpaint ? 2 * n : kind == StepKind::Restore ? al4(n / 4) : 0;
 }
-static size_t sampler_bytes(const ddk_unet* u, int B, int H, int W, int t_start, StepKind kind) {
+static size_t sampler_bytes(const ddk_unet* u, int B, int H, int W, int t_start, StepKind kind, int restore_n = 0) {
     if (check_shape(u, B, H, W) != DDK_OK || t_start < 0) return 0;
-    return (sampler_layout(*u, B, H, W, t_start).total + chain_extra_floats(*u, B, H, W, kind)) * sizeof(float);
+    return (sampler_layout(*u, B, H, W, t_start).total + chain_extra_floats(*u, B, H, W, kind, restore_n)) * sizeof(float);
 }
 
 // What the sampler entries share once their own arguments are checked: n_steps reverse steps on a->x, step k at timestep map[k],
@@ -1739,13 +1747,14 @@ static size_t sampler_bytes(const ddk_unet* u, int B, int H, int W, int t_start,
 //   Multistep: the history, zeroed by every call (c3[t_start] == 0 makes the first step first order whatever it would hold)
 //   Inpaint:   known and mask, copied in before the first op
 //   Restore:   y, copied in before the first step
+//   RestoreMasked: y and, behind it, the mask, copied in before the first step
 // The graph key: the kind, every table the step reads and the restore block; the staged operands live in the workspace, which is
 // in the key.
 static int sampler_chain(const ddk_sampler_args* a, const char* who, const int64_t* map, StepRule rule, ddk_stream_t s) {
     const int B = a->B, H = a->H, W = a->W, n_steps = a->t_start - a->t_end + 1;
     ChainRun c;
     DDK_TRY(begin_chain(c, a, who, a->t_start, a->stream_id, map, n_steps,
-                        [&](const SamplerLayout& sl) { return sl.total + chain_extra_floats(*a->unet, B, H, W, rule.kind); }, s));
+                        [&](const SamplerLayout& sl) { return sl.total + chain_extra_floats(*a->unet, B, H, W, rule.kind, rule.rst.n); }, s));
     rule.x = a->x; rule.noise = a->noise; rule.noise_step_stride = a->noise ? B * c.per : 0; rule.t_first = a->t_start;
     rule.c_recip = a->c_recip; rule.c_recipm1 = a->c_recipm1; rule.c1 = a->c1; rule.c2 = a->c2; rule.sigma = a->sigma;
     const size_t n = (size_t)B * c.per;
@@ -1762,6 +1771,13 @@ static int sampler_chain(const ddk_sampler_args* a, const char* who, const int64
         rule.rst.H = H; rule.rst.W = W;
         DDK_HIP(hipMemcpyAsync(extra, rule.rst.y, n / ((size_t)rule.rst.n * rule.rst.n) * sizeof(float), hipMemcpyDeviceToDevice, c.st));
         rule.rst.y = extra;
+    } else if (rule.kind == StepKind::RestoreMasked) {
+        const size_t nn = (size_t)rule.rst.n * rule.rst.n, ny = n / nn, nm = (size_t)B * H * W / nn;
+        rule.rst.H = H; rule.rst.W = W;
+        DDK_HIP(hipMemcpyAsync(extra, rule.rst.y, ny * sizeof(float), hipMemcpyDeviceToDevice, c.st));
+        DDK_HIP(hipMemcpyAsync(extra + al4(ny), rule.rst.mask, nm * sizeof(float), hipMemcpyDeviceToDevice, c.st));
+        rule.rst.y = extra;
+        rule.rst.mask = extra + al4(ny);
     }
     const StepArgs step{c.state, c.ws + c.sl.off_eps, c.per, rule};
 
@@ -1771,7 +1787,8 @@ static int sampler_chain(const ddk_sampler_args* a, const char* who, const int64
     const ChainKey key{rule.kind,
                        {a->packed, a->x, rule.c_recip, rule.c_recipm1, rule.c1, rule.c2, rule.sigma, rule.c3, rule.inp.ka, rule.inp.kb,
                         rule.inp.ja, rule.inp.jb},
-                       a->workspace, a->noise, B, H, W, a->t_start, c.dev, c.u->pack_epoch, rule.kind == StepKind::Restore ? rule.rst.n : 0};
+                       a->workspace, a->noise, B, H, W, a->t_start, c.dev, c.u->pack_epoch,
+                       rule.kind == StepKind::Restore || rule.kind == StepKind::RestoreMasked ? rule.rst.n : 0};
     return run_chain(*c.u, key, n_steps, a->use_graph != 0, one_step, c.st, who);
 }
 }  // namespace ddk
@@ -1872,6 +1889,41 @@ extern "C" int ddk_sampler_run_restore(const ddk_sampler_args* a, const int64_t*
     rule.kind = StepKind::Restore;
     rule.rst = RestoreOps{y, n, a->H, a->W};
     return sampler_chain(a, "sampler_restore", timestep_map, rule, s);
+}
+
+// ------------------------------------------------------------------------------------------------ masked restoration sampler
+// DDNM for A = mask o pool_n: n = 1 is inpainting on the spaced / DDIM tables, an all-measured mask at n >= 2
+// is ddk_sampler_run_restore, in between is super-resolution of a low-resolution image with holes.  With a mask the steps end in
+// StepKind::RestoreMasked; without one (n >= 2 only) the chain IS the Restore kind's: its rule, its kernels, its graph key.
+extern "C" size_t ddk_sampler_restore_masked_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start, int n) {
+    if (!(n == 1 || n == 2 || n == 4 || n == 8)) return 0;
+    return sampler_bytes(u, B, H, W, t_start, StepKind::RestoreMasked, n);
+}
+
+extern "C" int ddk_sampler_restore_masked_tail_parts(const ddk_unet* u, int B, int H, int W, int n) {
+    if (check_shape(u, B, H, W) != DDK_OK || !(n == 1 || n == 2 || n == 4 || n == 8)) return -1;
+    return fused_tail_parts(*u, B, H, W, u->dimp[1], StepKind::RestoreMasked, n);
+}
+
+extern "C" int ddk_sampler_run_restore_masked(const ddk_sampler_args* a, const int64_t* timestep_map, const float* y, const float* mask, int n,
+                                              ddk_stream_t s) {
+    DDK_REQUIRE(a && a->unet && a->packed && a->x && a->workspace && y, "sampler_restore_masked: null pointer");
+    DDK_REQUIRE(a->c_recip && a->c_recipm1 && a->c1 && a->c2 && a->sigma, "sampler_restore_masked: null schedule table");
+    DDK_REQUIRE(!a->noise, "sampler_restore_masked: injected noise is not supported, noise must be NULL (Philox only)");
+    DDK_REQUIRE(a->t_start >= a->t_end && a->t_end >= 0, "sampler_restore_masked: need t_start >= t_end >= 0");
+    DDK_REQUIRE((n == 1 || n == 2 || n == 4 || n == 8) && a->H > 0 && a->W > 0 && a->H % n == 0 && a->W % n == 0,
+                "sampler_restore_masked: n must be 1, 2, 4 or 8 and divide H and W");
+    DDK_REQUIRE(mask || n != 1, "sampler_restore_masked: n = 1 needs a mask (nothing would be constrained)");
+    DDK_TRY(check_timestep_map(timestep_map, a->t_start, "sampler_restore_masked"));
+    // the workspace is held to the masked query's size either way (never less than the Restore kind's, chain_extra_floats)
+    if (a->workspace_bytes < ddk_sampler_restore_masked_workspace_bytes(a->unet, a->B, a->H, a->W, a->t_start, n)) {
+        set_error("sampler_restore_masked: workspace too small (ddk_sampler_restore_masked_workspace_bytes)");
+        return DDK_ERR_WORKSPACE;
+    }
+    StepRule rule{};
+    rule.kind = mask ? StepKind::RestoreMasked : StepKind::Restore;
+    rule.rst = RestoreOps{y, n, a->H, a->W, mask};
+    return sampler_chain(a, "sampler_restore_masked", timestep_map, rule, s);
 }
 
 // ------------------------------------------------------------------------------------------------ likelihood sweep

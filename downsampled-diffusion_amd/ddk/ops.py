@@ -783,6 +783,24 @@ def p_sample_update_restore_(x, eps_hat, y, n, t, c_recip, c_recipm1, c1, c2, si
     return x
 
 
+def p_sample_update_restore_masked_(x, eps_hat, y, mask, n, t, c_recip, c_recipm1, c1, c2, sigma, seed=0, stream_id=0):
+    """In-place DDNM step for A = mask o (n x n average pooling) of x [B,H,W,C] (NHWC) per sample row t[b]:
+    where mask [B,H/n,W/n] is nonzero the clipped x0 is shifted so that its block mean equals y [B,H/n,W/n,C] (n = 1: replaced by
+    y), elsewhere it is kept; then the ancestral update with Philox draws.  n in {1, 2, 4, 8}; mask None (n >= 2 only): every
+    block is measured, p_sample_update_restore_ bit for bit."""
+    b, h, w, c = x.shape
+    n = int(n)
+    if n < 1 or tuple(y.shape) != (b, h // n, w // n, c) or tuple(eps_hat.shape) != tuple(x.shape) or \
+            (mask is not None and tuple(mask.shape) != (b, h // n, w // n)):
+        raise L.DDKError(f"p_sample_update_restore_masked: x {tuple(x.shape)}, eps_hat {tuple(eps_hat.shape)}, y {tuple(y.shape)}, "
+                         f"mask {None if mask is None else tuple(mask.shape)}, n = {n}")
+    L.check(L.load().ddk_p_sample_update_restore_masked(L.ptr(_f32(x)), L.ptr(_f32(eps_hat)), L.ptr(_f32(y)),
+                                                        L.ptr(None if mask is None else _f32(mask)), n, L.ptr(t), L.ptr(c_recip),
+                                                        L.ptr(c_recipm1), L.ptr(c1), L.ptr(c2), L.ptr(sigma), b, h, w, c, seed, stream_id,
+                                                        L.stream()), "p_sample_update_restore_masked")
+    return x
+
+
 def randn(shape, device, seed, step, stream_id=0):
     out = torch.empty(shape, device=device, dtype=torch.float32)
     L.check(L.load().ddk_randn(L.ptr(out), out.numel(), seed, step, stream_id, L.stream()), "randn")

@@ -12,9 +12,13 @@ through utils/data.py; ``--max_batches`` keeps the first max_batches * batch_siz
   * ``--task sr``: the images are average-pooled by ``--scale``, chain options ``--timestep_respacing``, ``--use_ddim``, ``--eta``
     as in upscale_model_samples.py.  Baselines: replication and bicubic upsampling.  Also the consistency max |pool(x_out) - y| in
     uint8 levels, of the chain's float output and of the uint8 image that is scored.
+  * ``--task inpaint --method ddnm``: DDNM for a mask (section 3.8) instead of RePaint, with ``--use_ddim`` / ``--eta`` and without
+    the ``--jump_*`` options; ``--task sr --mask KIND``: masked super-resolution, the mask applied to the pooled image, restored
+    with ``model.restore``; the baselines mean-fill the same holes before they upsample.
   * batch g draws x_T and its Philox key from ``--seed`` + g.
 
-Prints one JSON object, the settings that produced it beside the metrics; ``--json OUT`` also writes it to a file.  One process,
+Prints one JSON object, the settings that produced it (among them ``method`` and ``unet_forwards``, the UNet forwards per image, so
+that two runs compare on cost as well as on PSNR) beside the metrics; ``--json OUT`` also writes it to a file.  One process,
 one GPU.
 """
 import argparse
@@ -25,7 +29,7 @@ import time
 import numpy as np
 import torch
 
-from utils.restoration_metrics import MASKS, TASKS, evaluate_restoration, load_mask, report, to_u8
+from utils.restoration_metrics import MASKS, METHODS, TASKS, evaluate_restoration, load_mask, report, to_u8
 
 
 def parse_args(argv=None):
@@ -34,7 +38,9 @@ def parse_args(argv=None):
     ap.add_argument("--synthetic", default=None, help="JSON config file: use closed-form synthetic weights, no checkpoint")
     ap.add_argument("--images", default=None, help="uint8 [N, H, W, C] .npy of the model's size (default: the dataset's test split)")
     ap.add_argument("--task", required=True, choices=TASKS)
-    ap.add_argument("--mask", default="center", help=f"inpaint: one of {', '.join(MASKS)} or a .npy file of {{0, 1}} (1 = known)")
+    ap.add_argument("--mask", default=None, help=f"one of {', '.join(MASKS)} or a .npy file of {{0, 1}} (1 = known); inpaint: default "
+                                                 "center; sr: masked super-resolution, the mask is of the pooled image (default: none)")
+    ap.add_argument("--method", default=None, choices=METHODS, help="inpaint: repaint (default) or ddnm; sr: ddnm")
     ap.add_argument("--scale", type=int, default=4, help="sr: the pooling factor")
     ap.add_argument("--timestep_respacing", default="", help='run K of the T steps: "N", "n1,n2,..." sections or (sr) "ddimN"')
     ap.add_argument("--use_ddim", action="store_true", help="sr: DDIM steps instead of ancestral ones")
@@ -48,14 +54,23 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.batch_size < 1 or (args.max_batches is not None and args.max_batches < 1):
         ap.error("--batch_size and --max_batches must be >= 1")
+    if args.method is None:
+        args.method = "repaint" if args.task == "inpaint" else "ddnm"
     if args.task == "sr":
+        if args.method != "ddnm":
+            ap.error("--task sr has one method, ddnm")
         if args.scale < 2:
             ap.error("--scale must be >= 2")
+    elif args.mask is None:
+        args.mask = "center"
+    if args.method == "ddnm":
         if args.eta < 0 or (args.eta != 0.0 and not args.use_ddim):
             ap.error("--eta needs --use_ddim and a value >= 0")
+        if args.jump_length != ap.get_default("jump_length") or args.jump_n_sample != ap.get_default("jump_n_sample"):
+            ap.error("--jump_length and --jump_n_sample belong to --method repaint (DDNM has no jumps)")
     else:
         if args.use_ddim or args.eta != 0.0:
-            ap.error("--use_ddim and --eta belong to --task sr (RePaint runs ancestral steps)")
+            ap.error("--use_ddim and --eta belong to DDNM (RePaint runs ancestral steps)")
         if args.jump_length < 1 or args.jump_n_sample < 1:
             ap.error("--jump_length and --jump_n_sample must be >= 1")
     return args
@@ -66,6 +81,8 @@ def chain_options(args):
     kw = dict(respacing=args.timestep_respacing or None)
     if args.task == "sr":
         kw.update(scale=args.scale, ddim=args.use_ddim, eta=args.eta)
+    elif args.method == "ddnm":
+        kw.update(ddim=args.use_ddim, eta=args.eta)
     else:
         kw.update(jump_length=args.jump_length, jump_n_sample=args.jump_n_sample)
     return kw
@@ -130,17 +147,19 @@ def main():
     kw = chain_options(args)
     if args.task == "inpaint":
         kw["mask"] = args.mask if args.mask in MASKS else load_mask(args.mask, n, h, w, channels)
+    elif args.mask is not None:
+        kw["sr_mask"] = args.mask if args.mask in MASKS else load_mask(args.mask, n, h // args.scale, w // args.scale, 1)
 
     print(f"Scoring {args.task} on {n} images with {'synthetic weights' if args.synthetic else args.saved_model}.")
     t0 = time.time()
-    result = evaluate_restoration(model, images, args.task, batch_size=args.batch_size, seed=args.seed, **kw)
+    result = evaluate_restoration(model, images, args.task, batch_size=args.batch_size, seed=args.seed, method=args.method, **kw)
     torch.cuda.synchronize()
     print(f"Total time: {time.time() - t0:.2f} s")
 
     settings = dict(checkpoint=None if args.synthetic else args.saved_model, synthetic=args.synthetic, model=config["model"],
                     task=args.task, images=args.images or f"{config['dataset']} test split", n_images=n, batch_size=args.batch_size,
-                    seed=args.seed, **chain_options(args))
-    if args.task == "inpaint":
+                    seed=args.seed, method=result["method"], unet_forwards=result["unet_forwards"], **chain_options(args))
+    if args.mask is not None:
         settings["mask"] = args.mask
     out = dict(settings=settings, metrics=report(result))
     print(json.dumps(out, indent=4))

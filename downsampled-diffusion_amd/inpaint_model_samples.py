@@ -1,4 +1,5 @@
-"""Inpaint images with a trained DDPM / dDDPM checkpoint: RePaint (Lugmayr et al., CVPR 2022), DESIGN.md section 3.5.
+"""Inpaint images with a trained DDPM / dDDPM checkpoint: RePaint (Lugmayr et al., CVPR 2022), DESIGN.md section 3.5, or with
+``--method ddnm`` DDNM for a mask (Wang et al., ICLR 2023), section 3.8: K UNet forwards instead of RePaint's K + (r - 1) j ... .
 
 Loads the checkpoint as generate_model_samples.py does (``--synthetic CONFIG`` builds closed-form weights instead), reads
 ``--images file.npy`` (uint8 or float [N, H, W, C] in [0, 255], the on-disk format of the sample files; mapped by
@@ -7,10 +8,14 @@ u8 / 255 * 2 - 1 as the training data is), hides the region given by ``--mask`` 
   * ``--mask center|left|half|lines`` (1 = known): hide the central square of half the side, the left half, the bottom half,
     or every second row; or ``--mask file.npy``: {0, 1} of shape [H, W], [N, H, W] or [N, H, W, 1|C];
   * ``--timestep_respacing`` (e.g. "250"), ``--jump_length`` and ``--jump_n_sample`` set the RePaint schedule;
+  * ``--method ddnm`` fills with ``model.restore`` (scale 1) instead: ``--use_ddim`` and ``--eta`` choose DDIM steps, the
+    ``--jump_*`` options must stay at their defaults, and a mask that differs between the channels counts a pixel as known only
+    where every channel is;
   * batch g draws x_T and its Philox key from ``--seed`` + g.
 
-Writes ``{saved_model}_inpaint_{mask}_{spec}_j{j}r{r}.npy`` (float32 [N, H, W, C] in [0, 255]) and, beside it, the masked
-inputs for viewing (``..._masked.npy``, hidden pixels 0).  One process, one GPU.
+Writes ``{saved_model}_inpaint_{mask}_{spec}_j{j}r{r}.npy`` (float32 [N, H, W, C] in [0, 255]; with ``--method ddnm``
+``{saved_model}_inpaint_{mask}_{spec}_ddnm[_ddim_eta{eta}].npy``) and, beside it, the masked inputs for viewing
+(``..._masked.npy``, hidden pixels 0).  One process, one GPU.
 """
 import argparse
 import json
@@ -39,6 +44,9 @@ def main():
     ap.add_argument("--n_images", type=int, default=4, help="number of synthetic images when --images is not given")
     ap.add_argument("--mask", default="center", help=f"one of {', '.join(MASKS)} or a .npy file of {{0, 1}} (1 = known)")
     ap.add_argument("--timestep_respacing", default="", help='run the schedule over K of the T steps, e.g. "250" (default: all T)')
+    ap.add_argument("--method", default="repaint", choices=("repaint", "ddnm"), help="repaint (section 3.5) or ddnm (section 3.8)")
+    ap.add_argument("--use_ddim", action="store_true", help="ddnm: DDIM steps instead of ancestral ones")
+    ap.add_argument("--eta", type=float, default=0.0, help="ddnm: DDIM noise scale (0: deterministic)")
     ap.add_argument("--jump_length", type=int, default=10)
     ap.add_argument("--jump_n_sample", type=int, default=10)
     ap.add_argument("--batch_size", type=int, default=32)
@@ -47,6 +55,13 @@ def main():
     args = ap.parse_args()
     if args.jump_length < 1 or args.jump_n_sample < 1 or args.batch_size < 1:
         ap.error("--jump_length, --jump_n_sample and --batch_size must be >= 1")
+    if args.method == "ddnm":
+        if args.jump_length != ap.get_default("jump_length") or args.jump_n_sample != ap.get_default("jump_n_sample"):
+            ap.error("--jump_length and --jump_n_sample belong to --method repaint (DDNM has no jumps)")
+        if args.eta < 0 or (args.eta != 0.0 and not args.use_ddim):
+            ap.error("--eta needs --use_ddim and a value >= 0")
+    elif args.use_ddim or args.eta != 0.0:
+        ap.error("--use_ddim and --eta belong to --method ddnm (RePaint runs ancestral steps)")
     if args.images is None and not args.synthetic:
         ap.error("--images is required unless --synthetic is given")
 
@@ -89,15 +104,23 @@ def main():
         mask_all, mask_name = load_mask(args.mask, n, h, w, c), os.path.splitext(os.path.basename(args.mask))[0]
 
     spec = args.timestep_respacing.replace(",", "-") or "full"
-    kw = dict(respacing=args.timestep_respacing or None, jump_length=args.jump_length, jump_n_sample=args.jump_n_sample)
-    print(f"Inpainting {n} images ({mask_name} mask, {spec} steps, j = {args.jump_length}, r = {args.jump_n_sample}) "
-          f"with {args.saved_model}.")
+    ddnm = args.method == "ddnm"
+    if ddnm:
+        kw = dict(respacing=args.timestep_respacing or None, ddim=args.use_ddim, eta=args.eta)
+        tail = "_ddnm" + (f"_ddim_eta{args.eta:g}" if args.use_ddim else "")
+        print(f"Inpainting {n} images ({mask_name} mask, {spec} steps, DDNM{', DDIM eta ' + format(args.eta, 'g') if args.use_ddim else ''}) "
+              f"with {args.saved_model}.")
+    else:
+        kw = dict(respacing=args.timestep_respacing or None, jump_length=args.jump_length, jump_n_sample=args.jump_n_sample)
+        tail = f"_j{args.jump_length}r{args.jump_n_sample}"
+        print(f"Inpainting {n} images ({mask_name} mask, {spec} steps, j = {args.jump_length}, r = {args.jump_n_sample}) "
+              f"with {args.saved_model}.")
     outs = []
     t0 = time.time()
     for g, i in enumerate(range(0, n, args.batch_size)):
         torch.manual_seed(args.seed + g)          # x_T and the Philox key of batch g
         x, m = x_all[i:i + args.batch_size].to(device), mask_all[i:i + args.batch_size].to(device)
-        out = model.inpaint(x, m, **kw)
+        out = model.restore(x, m.amin(dim=1), 1, **kw) if ddnm else model.inpaint(x, m, **kw)
         if config["model"] == "dddpm":
             out = out[0]
         outs.append(to_u8_range(out))
@@ -106,7 +129,7 @@ def main():
 
     out_dir = args.out_dir or SAMPLE_DIR
     os.makedirs(out_dir, exist_ok=True)
-    base = os.path.join(out_dir, f"{args.saved_model}_inpaint_{mask_name}_{spec}_j{args.jump_length}r{args.jump_n_sample}")
+    base = os.path.join(out_dir, f"{args.saved_model}_inpaint_{mask_name}_{spec}{tail}")
     np.save(base + ".npy", np.concatenate(outs), allow_pickle=False)
     masked = to_u8_range(x_all) * mask_all.expand(-1, c, -1, -1).permute(0, 2, 3, 1).numpy()
     np.save(base + "_masked.npy", masked.astype(np.float32), allow_pickle=False)

@@ -98,6 +98,45 @@ class DownsampleDDPM(DDPM):
         return self.rescaled_upsample(z), z
 
     @torch.no_grad()
+    def restore(self, y, mask=None, scale=1, *, respacing=None, ddim=False, eta=0.0, x_T=None, seed=None, paste=True, **unsupported):
+        """DDNM with a mask in the latent (DDPM.restore).  The pixels of y [B, C, H/scale, W/scale] that are
+        not measured are zeroed before the encoder, so z_ref = rescaled_downsample(y * m replicated scale x scale) carries nothing
+        of them, and the constraint is the latent's, as in inpaint and super_resolve (exact there up to fp32 rounding, approximate
+        in pixels: the decoder is not linear).
+          scale = 1 (inpainting): a latent pixel is measured only if its whole dim_reduc x dim_reduc footprint is (a min-pool of the
+            mask), the block is n_lat = 1 and measured latent pixels are set to z_ref; paste puts the measured pixels of y back.
+          scale a multiple of dim_reduc with n_lat = scale / dim_reduc in {1, 2, 4, 8}: a low-resolution pixel is the footprint of
+            exactly one n_lat x n_lat latent block, so the mask is the latent's as it stands, and measured blocks keep the mean
+            y_lat = avg_pool(z_ref, n_lat).  paste has no meaning here (y is not an image of the output's size) and is ignored.
+        scale = 1 needs a mask, and so does scale = dim_reduc (n_lat = 1).  Returns (x_out, z) like sample; x_T is a latent start."""
+        d = int(self.dim_reduc)
+        scales = (1,) + tuple(d * n for n in (1,) + self.RESTORE_BLOCKS)
+        y, m = self._restore_masked_args(y, mask, scale, self.x_shape, ddim, eta, unsupported, scales)
+        s = int(scale)
+        if m is None and s == d:
+            raise ValueError(f"restore: scale = {d} is one latent pixel per measurement and needs a mask (nothing would be constrained)")
+        m_lat = None
+        if s == 1:
+            m_lat = -torch.nn.functional.max_pool2d(-m.unsqueeze(1), d)[:, 0]
+            if not bool((m_lat.reshape(m_lat.shape[0], -1).amax(dim=1) > 0).all()):
+                raise ValueError(f"restore: no {d} x {d} latent footprint of some image is wholly measured")
+        y = y.to(self.betas.device)
+        self._check_device(y)
+        if s == 1:
+            m = m.to(y.device)
+            z_ref = self.rescaled_downsample(y)                       # _restore_masked_args zeroed what is not measured
+            z = self._restore_loop(z_ref, 1, respacing, ddim, eta, x_T, seed, mask=m_lat, who="restore")
+            x_out = self.rescaled_upsample(z)
+            if paste:
+                x_out = torch.where(m.unsqueeze(1) != 0, y, x_out)
+            return x_out, z
+        n_lat = s // d
+        z_ref = self.rescaled_downsample(y.repeat_interleave(s, dim=2).repeat_interleave(s, dim=3))
+        y_lat = torch.nn.functional.avg_pool2d(z_ref, n_lat) if n_lat > 1 else z_ref
+        z = self._restore_loop(y_lat, n_lat, respacing, ddim, eta, x_T, seed, mask=None if m is None else m.to(y.device), who="restore")
+        return self.rescaled_upsample(z), z
+
+    @torch.no_grad()
     def reconstruct(self, x, n):
         """dddpm.py:33-74 (visualisation only)."""
         assert x.shape[0] >= n, f'batch size ({x.shape[0]}) is below {n}'

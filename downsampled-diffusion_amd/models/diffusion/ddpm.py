@@ -366,23 +366,40 @@ class DDPM(nn.Module):
             raise ValueError("super_resolve: y must be finite")
         return y.float()
 
-    def _restore_loop(self, y, n, respacing, ddim, eta, x_T, seed):
+    def _restore_loop(self, y, n, respacing, ddim, eta, x_T, seed, mask=None, who="super_resolve"):
         """DDNM over the latent whose n x n block means are held at y [B, C, H/n, W/n]: native (UnetPlan.sample_restore_nhwc) or,
-        with native_sampler off, the same op as a Python loop in the same NHWC layout, so both draw the same Philox numbers."""
+        with native_sampler off, the same op as a Python loop in the same NHWC layout, so both draw the same Philox numbers.
+        mask [B, H/n, W/n] ({0, 1} floats, restore() only): the blocks that are held (n = 1: the pixels that are set to y); the
+        masked op and UnetPlan.sample_restore_masked_nhwc then take the place of the two above."""
         device = self.betas.device
         if device.type != 'cuda':
-            raise DDKError("super_resolve: move the model to a ROCm device first (no CPU fallback)")
+            raise DDKError(f"{who}: move the model to a ROCm device first (no CPU fallback)")
         spaced = respacing is not None or ddim or eta != 0
         tables, use = self._spaced_tables(respacing, ddim, eta) if spaced else (self._tables(), None)
         shape = (y.shape[0], *self.sample_shape)
         if x_T is not None and tuple(x_T.shape) != shape:
-            raise ValueError(f"super_resolve: x_T must be {shape}, got {tuple(x_T.shape)}")
+            raise ValueError(f"{who}: x_T must be {shape}, got {tuple(x_T.shape)}")
         img = torch.randn(shape, device=device) if x_T is None else x_T.to(device).float()
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         k_start = (self.timesteps if use is None else len(use)) - 1
         yl = ops.nchw_to_nhwc(y.to(device).float().contiguous())
         x = ops.nchw_to_nhwc(img.contiguous())
+        if mask is not None:
+            mk = mask.to(device).float().contiguous()
+            if not self.native_sampler:
+                with self._eps_model_nhwc().plan().forwards_as_in_chain():
+                    for k in range(k_start, -1, -1):
+                        t_model = k if use is None else use[k]
+                        eps_hat = self.latent_model(ops.nhwc_to_nchw(x), torch.full((shape[0],), t_model, device=device, dtype=torch.long))
+                        ops.p_sample_update_restore_masked_(x, ops.nchw_to_nhwc(eps_hat.contiguous()), yl, mk, n,
+                                                            torch.full((shape[0],), k, device=device, dtype=torch.long), **tables,
+                                                            seed=seed, stream_id=int(self.rng_stream_id))
+                return ops.nhwc_to_nchw(x)
+            self._eps_model_nhwc().plan().sample_restore_masked_nhwc(x, yl, mk, n, tables, k_start, seed=seed,
+                                                                     stream_id=int(self.rng_stream_id), use_graph=self.use_graph,
+                                                                     timesteps=use)
+            return ops.nhwc_to_nchw(x)
         if not self.native_sampler:
             # the loop's forwards pick their kernels as the chain's steps do (UnetPlan.forwards_as_in_chain): the two GroupNorm
             # paths sum in another order, and a few 1e-6 of eps_hat per step is more than the loop may differ from the chain
@@ -408,6 +425,68 @@ class DDPM(nn.Module):
         and eta without ddim, before any device work."""
         y = self._restore_args(y, scale, self.sample_shape, ddim, eta, unsupported)
         return self._restore_loop(y, int(scale), respacing, ddim, eta, x_T, seed)
+
+    # ------------------------------------------------------------------ DDNM with a mask: inpainting and masked super-resolution
+    RESTORE_SCALES = (1, 2, 4, 8)
+
+    def _restore_masked_args(self, y, mask, scale, shape, ddim, eta, unsupported, scales):
+        """ValueError for anything restore cannot take, before any device work.  ``shape`` is [C, H, W] of the full-resolution
+        image, ``scales`` the scales the caller takes.  Returns (y as float with the pixels that are not measured set to 0, the
+        mask as {0, 1} floats [B, H/scale, W/scale] or None), on y's device."""
+        if unsupported:
+            raise ValueError(f"restore: {sorted(unsupported)} not accepted (DDNM runs ancestral or DDIM steps with Philox draws "
+                             f"over the whole schedule: no {', '.join(self.RESTORE_UNSUPPORTED)})")
+        if isinstance(scale, bool) or not isinstance(scale, (int, np.integer)) or scale not in scales:
+            raise ValueError(f"restore: scale must be an int in {tuple(scales)}, got {scale!r}")
+        if isinstance(eta, bool) or not isinstance(eta, (int, float, np.integer, np.floating)) or eta < 0 or (eta != 0 and not ddim):
+            raise ValueError(f"restore: eta = {eta!r} needs ddim=True and eta >= 0")
+        if mask is None and scale == 1:
+            raise ValueError("restore: scale = 1 needs a mask (nothing would be constrained)")
+        C, H, W = shape
+        if H % scale or W % scale:
+            raise ValueError(f"restore: scale = {scale} must divide the image size {H} x {W}")
+        h, w = H // scale, W // scale
+        if not torch.is_tensor(y) or y.dim() != 4 or list(y.shape[1:]) != [C, h, w] or not y.is_floating_point():
+            raise ValueError(f"restore: y must be a float [B, {C}, {h}, {w}] tensor, got "
+                             f"{tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
+        B = y.shape[0]
+        y = y.float()
+        if mask is None:
+            if not bool(torch.isfinite(y).all()):
+                raise ValueError("restore: y must be finite")
+            return y, None
+        if not torch.is_tensor(mask) or mask.is_complex():
+            raise ValueError("restore: mask must be a real or bool tensor")
+        m = mask
+        if m.dim() == 4 and m.shape[1] == 1:
+            m = m[:, 0]
+        elif m.dim() == 2:
+            m = m.unsqueeze(0)
+        if m.dim() != 3 or m.shape[0] not in (1, B) or tuple(m.shape[1:]) != (h, w):
+            raise ValueError(f"restore: mask must be [{h}, {w}], [{B}, {h}, {w}] or [{B}, 1, {h}, {w}], got {tuple(mask.shape)}")
+        if m.dtype != torch.bool and not bool(((m == 0) | (m == 1)).all()):
+            raise ValueError("restore: mask values must be 0 or 1 (or bool)")
+        m = m.to(device=y.device, dtype=torch.float32).expand(B, h, w).contiguous()
+        if not bool((m.reshape(B, -1).amax(dim=1) > 0).all()):
+            raise ValueError("restore: every image needs at least one measured pixel (an all-zero mask constrains nothing)")
+        sel = (m != 0).unsqueeze(1).expand_as(y)
+        if not bool(torch.isfinite(y[sel]).all()):
+            raise ValueError("restore: the measured pixels of y must be finite")
+        return torch.where(sel, y, torch.zeros_like(y)), m
+
+    @torch.no_grad()
+    def restore(self, y, mask=None, scale=1, *, respacing=None, ddim=False, eta=0.0, x_T=None, seed=None, **unsupported):
+        """Zero-shot restoration with DDNM for A = mask o (scale x scale average pooling): an image
+        [B, C, H, W] whose pooling equals y [B, C, H/scale, W/scale] (in [-1, 1]) wherever mask is 1.  mask is [H/scale, W/scale],
+        [B, H/scale, W/scale] or [B, 1, H/scale, W/scale] with values in {0, 1} or bool (1 = measured), shared by the channels.
+        scale = 1 is inpainting in K = the respacing's steps (ancestral, or DDIM with eta): the measured pixels of the result equal
+        y exactly and the others of y are never read.  scale in {2, 4, 8} with a mask upscales a low-resolution image with holes:
+        the measured block means of the result equal y up to fp32 rounding; without a mask it is super_resolve.  x_T: the start
+        state; seed: the Philox key (default: drawn from torch's generator).  solver / noise / early_stop raise ValueError, as do
+        scale = 1 without a mask, a mask that is not {0, 1} or is all zero in some image, a misshapen y or mask, non-finite measured
+        pixels and eta without ddim, before any device work."""
+        y, m = self._restore_masked_args(y, mask, scale, self.sample_shape, ddim, eta, unsupported, self.RESTORE_SCALES)
+        return self._restore_loop(y, int(scale), respacing, ddim, eta, x_T, seed, mask=m, who="restore")
 
     @torch.no_grad()
     def reconstruct(self, x, n):

@@ -14,6 +14,7 @@ import torch
 
 MASKS = ("center", "left", "half", "lines")
 TASKS = ("inpaint", "sr")
+METHODS = ("repaint", "ddnm")
 
 
 # ------------------------------------------------------------------ degradations
@@ -102,7 +103,7 @@ def _score(ops, cand_u8, ref_u8, hidden, device):
 
 
 @torch.no_grad()
-def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234, mask="center", scale=4, **chain):
+def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234, mask="center", scale=4, method=None, sr_mask=None, **chain):
     """Degrade, restore and score ``images_uint8`` (uint8 [N, H, W, C] of the model's size).
 
     task "inpaint": ``mask`` is one of MASKS or a {0, 1} tensor broadcastable to [N, 1|C, H, W] (1 = known); ``chain`` goes to
@@ -111,8 +112,15 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
     task "sr": the images are average-pooled by ``scale``; ``chain`` goes to ``model.super_resolve`` (respacing, ddim, eta).
     Baselines: replicate, bicubic.  consistency: per image max |pool(x_out) - y| * 127.5 (uint8 levels) of the model's float output,
     consistency_u8 the same of the uint8 image that is scored (rounding alone may cost 0.5, clamping to [0, 255] more).
+    method (default: "repaint" for inpaint, "ddnm" for sr): "ddnm" with task "inpaint" fills with ``model.restore`` at scale 1
+    (DDNM for a mask, section 3.8; ``chain``: respacing, ddim, eta; a pixel counts as known where every channel is).  Task "sr"
+    with ``sr_mask`` is masked super-resolution: the mask (a kind of MASKS or a {0, 1} tensor broadcastable to
+    [N, 1, H/scale, W/scale]) applies to the pooled image, ``model.restore`` upscales it, and the baselines mean-fill the pooled
+    image's holes before they upsample it, so they are scored on the same degraded input.  The consistency is then over the
+    measured pixels.  Without a mask, task "sr" is ``model.super_resolve`` as before.
     Batch g draws x_T and its Philox key from seed + g, as the sampling CLIs do.
 
+    "method" and "unet_forwards" (UNet forwards per image: the chain's steps; the batch shares each forward) are returned too.
     Returns {"n_images", "methods": {name: {"psnr": [N], "ssim": [N], ...}}, "images": {name: uint8 [N, H, W, C]}} and, for "sr",
     "consistency" / "consistency_u8" [N]; "restored" is the model's entry."""
     from ddk import ops
@@ -125,9 +133,22 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
         raise ValueError("evaluate_restoration needs at least one image and batch_size >= 1")
     device = model.betas.device
     images, extra, hidden = {}, {}, None
+    if method is None:
+        method = "repaint" if task == "inpaint" else "ddnm"
+    if method not in METHODS or (task == "sr" and method != "ddnm"):
+        raise ValueError(f"unknown method {method!r} for task {task!r}: one of {METHODS} (sr: ddnm only)")
+    K = len(model._spaced_tables(chain.get("respacing"), chain.get("ddim", False), chain.get("eta", 0.0))[1]) \
+        if chain.get("respacing") is not None or chain.get("ddim") else int(model.timesteps)
     if task == "inpaint":
         m_all = make_mask(mask, n, h, w) if isinstance(mask, str) else torch.as_tensor(mask).float().expand(n, -1, h, w)
-        restore = lambda i: model.inpaint(x_all[i:i + batch_size].to(device), m_all[i:i + batch_size].to(device), **chain)
+        if method == "ddnm":
+            m_all = m_all.amin(dim=1, keepdim=True)
+            restore = lambda i: model.restore(x_all[i:i + batch_size].to(device), m_all[i:i + batch_size, 0].to(device), 1, **chain)
+            extra["unet_forwards"] = K
+        else:
+            restore = lambda i: model.inpaint(x_all[i:i + batch_size].to(device), m_all[i:i + batch_size].to(device), **chain)
+            extra["unet_forwards"] = len(model._inpaint_tables(chain.get("respacing"), chain.get("jump_length", 10),
+                                                               chain.get("jump_n_sample", 10))[1])
         images["mean_fill"] = to_u8(mean_fill(x_all, m_all))
         hidden = (m_all.amin(dim=1) == 0).to(torch.uint8).contiguous()
     else:
@@ -135,9 +156,19 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
         if scale < 2 or h % scale or w % scale:
             raise ValueError(f"scale {scale} must be >= 2 and divide the image size {h} x {w}")
         y_all = pool(x_all, scale)
-        restore = lambda i: model.super_resolve(y_all[i:i + batch_size].to(device), scale, **chain)
-        images["replicate"] = to_u8(replicate(y_all, scale))
-        images["bicubic"] = to_u8(bicubic(y_all, scale))
+        extra["unet_forwards"] = K
+        my_all = None
+        if sr_mask is None:
+            restore = lambda i: model.super_resolve(y_all[i:i + batch_size].to(device), scale, **chain)
+            y_base = y_all
+        else:
+            hs, ws = h // scale, w // scale
+            my_all = make_mask(sr_mask, n, hs, ws) if isinstance(sr_mask, str) else torch.as_tensor(sr_mask).float().expand(n, -1, hs, ws)
+            my_all = my_all.amin(dim=1, keepdim=True)
+            restore = lambda i: model.restore(y_all[i:i + batch_size].to(device), my_all[i:i + batch_size, 0].to(device), scale, **chain)
+            y_base = mean_fill(y_all, my_all)             # the baselines see the same holes
+        images["replicate"] = to_u8(replicate(y_base, scale))
+        images["bicubic"] = to_u8(bicubic(y_base, scale))
     outs = []
     for g, i in enumerate(range(0, n, batch_size)):
         torch.manual_seed(seed + g)               # x_T and the Philox key of batch g
@@ -146,10 +177,11 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
     x_out = torch.cat(outs)
     images = dict(restored=to_u8(x_out), **images)
     if task == "sr":
-        extra["consistency"] = ((pool(x_out, scale) - y_all).abs().amax(dim=(1, 2, 3)) * 127.5).double().numpy()
-        extra["consistency_u8"] = ((pool(from_u8(images["restored"]), scale) - y_all).abs().amax(dim=(1, 2, 3)) * 127.5).double().numpy()
+        meas = 1.0 if my_all is None else my_all      # the constraint holds where y is measured
+        extra["consistency"] = (((pool(x_out, scale) - y_all) * meas).abs().amax(dim=(1, 2, 3)) * 127.5).double().numpy()
+        extra["consistency_u8"] = (((pool(from_u8(images["restored"]), scale) - y_all) * meas).abs().amax(dim=(1, 2, 3)) * 127.5).double().numpy()
     methods = {name: _score(ops, img, ref, hidden, device) for name, img in images.items()}
-    return dict(n_images=n, methods=methods, images={k: v.numpy() for k, v in images.items()}, **extra)
+    return dict(n_images=n, method=method, methods=methods, images={k: v.numpy() for k, v in images.items()}, **extra)
 
 
 def report(result):

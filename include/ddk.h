@@ -308,6 +308,18 @@ int ddk_p_sample_update_inpaint(float* x, const float* eps_hat, const float* kno
 int ddk_p_sample_update_restore(float* x, const float* eps_hat, const float* y, int n, const int64_t* t, const float* c_recip,
                                 const float* c_recipm1, const float* c1, const float* c2, const float* sigma, int B, int H, int W,
                                 int channels, uint64_t seed, uint32_t stream_id, ddk_stream_t s);
+/* One DDNM step for A = mask o (n x n average pooling) on its own (ddk_sampler_run_restore_masked).  mask is
+ * [B][H/n][W/n] fp32, nonzero = measured, shared by the channels; n is 1, 2, 4 or 8 and divides H and W.
+ *   x0 = clamp(c_recip x - c_recipm1 eps_hat, -1, 1);
+ *   n >= 2, block measured:   x0' = x0 + (y[block] - m), m and every rounding as in ddk_p_sample_update_restore;
+ *   n == 1, pixel measured:   x0' = y, a select with no arithmetic (at row 0, where c1 = 1 and c2 = 0, x is y there bit for bit);
+ *   not measured:             x0' = x0; y there is only ever selected against and may hold anything, NaN included;
+ *   x = (c1 x0' + c2 x) + [t > 0] sigma z, z Philox keyed as in ddk_p_sample_update_restore.
+ * mask may be NULL for n >= 2: every block is measured, and the call is ddk_p_sample_update_restore, bit for bit.  n == 1 without
+ * a mask is DDK_ERR_ARG.  H * W * channels must be a multiple of 4 (below 2^31); x, eps_hat and, at n == 1, y 16-byte aligned. */
+int ddk_p_sample_update_restore_masked(float* x, const float* eps_hat, const float* y, const float* mask, int n, const int64_t* t,
+                                       const float* c_recip, const float* c_recipm1, const float* c1, const float* c2, const float* sigma,
+                                       int B, int H, int W, int channels, uint64_t seed, uint32_t stream_id, ddk_stream_t s);
 /* The end of a forward in one launch (unet.py:69-72 behind the final Block's conv; ddpm.py:203-227): GroupNorm from the conv's
  * partials -> Mish -> 1x1 projection to n_out <= 8 channels (w [n_out][C], bias [n_out]) -> eps_hat; eps_out and / or x may be
  * given: eps_out [B][HW][n_out] receives eps_hat, x [B][HW][n_out] gets the reverse-step update of ddk_p_sample_update in place
@@ -515,6 +527,22 @@ size_t ddk_sampler_restore_workspace_bytes(const ddk_unet* u, int B, int H, int 
  * a shape the plan does not take. */
 int ddk_sampler_restore_tail_parts(const ddk_unet* u, int B, int H, int W, int n);
 int ddk_sampler_run_restore(const ddk_sampler_args* a, const int64_t* timestep_map, const float* y, int n, ddk_stream_t s);
+/* Inpainting and masked super-resolution with DDNM for A = mask o (n x n average pooling): the chain of
+ * ddk_sampler_run_restore, every step being ddk_p_sample_update_restore_masked's.  n = 1 is inpainting on the spaced / DDIM tables
+ * (K UNet forwards); n >= 2 with a mask over the low-resolution pixels upscales an image with holes.  y [B][H/n][W/n][in_ch] and mask
+ * [B][H/n][W/n] (device fp32, nonzero = measured) are copied into the workspace before the first step, outside any captured step,
+ * so a loop over images and masks on one workspace replays one cached graph.  mask may be NULL for n >= 2: the call then is
+ * ddk_sampler_run_restore (its kernels, its graph key, its bits); n = 1 without a mask is DDK_ERR_ARG.  a->noise must be NULL.
+ * Graphs are cached under a chain kind of their own with n in the key, so a masked and an unmasked chain on the same buffers never
+ * replay each other's graph.  DDK_OPT_RESTORE_FUSED_TAIL = 0 forces the unfused tail here too; the two tails are bit-identical.
+ * The workspace: the sampler's layout, then y and the mask for this n (n = 1: a whole latent plus B H W floats), never less than
+ * ddk_sampler_restore_workspace_bytes for n >= 2. */
+size_t ddk_sampler_restore_masked_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start, int n);
+/* As ddk_sampler_restore_tail_parts, for a step WITH a mask: n >= 2 has that entry's eligibility; n = 1 is pointwise and is fused
+ * wherever the forward ends in the one-launch tail with at most 128 channels in front of the projection. */
+int ddk_sampler_restore_masked_tail_parts(const ddk_unet* u, int B, int H, int W, int n);
+int ddk_sampler_run_restore_masked(const ddk_sampler_args* a, const int64_t* timestep_map, const float* y, const float* mask, int n,
+                                   ddk_stream_t s);
 /* Drops the plan's cached sampler and likelihood-sweep graphs and shift table (waits for the device when graphs exist). */
 int ddk_sampler_invalidate(ddk_unet* u);
 /* Drops only the cached graphs (and shift table) that live in / point into `workspace`, after waiting for the launches of

@@ -14,7 +14,11 @@ alternately the same way (the two chains differ only in the step's last kernel: 
 
 --restore: the cost of a DDNM super-resolution step against an ancestral step of the same respaced "50"
 chain, n = 2 and 4 (the fused tail) and, for the record, the same two with the fused tail switched off and n = 8 (always the
-unfused tail), timed alternately the same way (the chains differ only in the step's last kernel)."""
+unfused tail), timed alternately the same way (the chains differ only in the step's last kernel).
+
+--restore-masked: the cost of a masked DDNM step at n = 1 (inpainting, the fused tail; and with the fused
+tail switched off) and n = 2 with a mask, against an ancestral step of the same respaced "50" chain, timed the same way, and the
+images/s of "100"-step DDIM (eta 0) DDNM inpainting with the decode, for the comparison with RePaint's 2410 ops."""
 import argparse
 import json
 import os
@@ -42,6 +46,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--solver", action="store_true", help="2M step against DDIM step on logsnrK grids")
     ap.add_argument("--restore", action="store_true", help="DDNM super-resolution step against an ancestral step, respacing 50")
+    ap.add_argument("--restore-masked", action="store_true", help="masked DDNM step (n = 1, 2) against an ancestral step, respacing 50")
     args = ap.parse_args()
     torch.cuda.set_device(0)
     cfg = bench.cfg4()
@@ -54,6 +59,11 @@ def main():
     x = x0.clone()
 
     ys = {n: torch.nn.functional.avg_pool2d(ops.nhwc_to_nchw(x0).clamp(-1, 1), n).permute(0, 2, 3, 1).contiguous() for n in (2, 4, 8)}
+
+    ys[1] = ops.nhwc_to_nchw(x0).clamp(-1, 1).permute(0, 2, 3, 1).contiguous()
+    ii, jj = torch.meshgrid(torch.arange(S, device=DEV), torch.arange(S, device=DEV), indexing="ij")
+    center = ((ii < S // 4) | (ii >= S - S // 4) | (jj < S // 4) | (jj >= S - S // 4)).float()      # the CLI's "center" mask
+    mks = {n: center[::n, ::n].expand(B, -1, -1).contiguous() for n in (1, 2)}
 
     def chain(kind, K):
         x.copy_(x0)
@@ -70,6 +80,11 @@ def main():
         elif kind == "anc":
             sp, use = model._spaced_tables(str(K), False, 0.0)
             plan.sample_nhwc(x, sp, K - 1, 0, seed=1234, stream_id=0, timesteps=use)
+        elif kind.startswith("masked"):                  # "masked<n>" ancestral, "maskedddim<n>" DDIM eta 0
+            ddim = kind.startswith("maskedddim")
+            n = int(kind[len("maskedddim" if ddim else "masked"):])
+            sp, use = model._spaced_tables(str(K), ddim, 0.0)
+            plan.sample_restore_masked_nhwc(x, ys[n], mks[n], n, sp, K - 1, seed=1234, stream_id=0, timesteps=use)
         elif kind.startswith("restore"):
             n = int(kind[len("restore"):])
             sp, use = model._spaced_tables(str(K), False, 0.0)
@@ -92,6 +107,8 @@ def main():
         return solver_ab(chain, decode)
     if args.restore:
         return restore_ab(chain, plan)
+    if args.restore_masked:
+        return restore_masked_ab(chain, plan, decode)
 
     res = {"shape": f"cfg4 unet_chan 128, {C}x{S}x{S} latents, B={B}, T={T}, DDIM eta 0", "reps": REPS, "per_K": {}}
     with torch.no_grad():
@@ -169,6 +186,41 @@ def restore_ab(chain, plan):
                                            "ancestral_min_max_ms": [round(min(anc), 4), round(max(anc), 4)],
                                            "restore_min_max_ms": [round(min(rst), 4), round(max(rst), 4)]}
         plan.set_option(plan.OPT_RESTORE_FUSED_TAIL, 1)
+    print(json.dumps(res), flush=True)
+
+
+def restore_masked_ab(chain, plan, decode):
+    K = 50
+    res = {"shape": f"cfg4 unet_chan 128, {C}x{S}x{S} latents, B={B}, T={T}, respacing {K}, masked DDNM step vs ancestral step, center mask",
+           "reps": REPS, "per_n": {}}
+    with torch.no_grad():
+        t_settle = time.perf_counter()
+        while time.perf_counter() - t_settle < 2.0:
+            chain("plain", 96)
+        for n, fused in ((1, True), (2, True), (1, False)):
+            plan.set_option(plan.OPT_RESTORE_FUSED_TAIL, int(fused))
+            tail = "fused" if plan.restore_masked_tail_parts(B, S, S, n) > 0 else "unfused"
+            chain("anc", K)                              # captures both chains' graphs outside the timed calls
+            chain(f"masked{n}", K)
+            anc, rst = [], []
+            for _ in range(REPS):
+                anc.append(chain("anc", K) / K)
+                rst.append(chain(f"masked{n}", K) / K)
+            a, r = statistics.median(anc), statistics.median(rst)
+            res["per_n"][f"{n}_{tail}"] = {"ancestral_ms_per_step": round(a, 4), "masked_ms_per_step": round(r, 4),
+                                           "masked_over_ancestral": round(r / a, 4),
+                                           "ancestral_min_max_ms": [round(min(anc), 4), round(max(anc), 4)],
+                                           "masked_min_max_ms": [round(min(rst), 4), round(max(rst), 4)]}
+        plan.set_option(plan.OPT_RESTORE_FUSED_TAIL, 1)
+        # "100" DDIM eta 0 DDNM inpainting, end to end with the decode: what a user runs instead of RePaint's 2410 ops
+        K = 100
+        chain("maskedddim1", K)
+        runs = [chain("maskedddim1", K) for _ in range(REPS)]
+        decode_ms = min(decode() for _ in range(3))
+        ms = statistics.median(runs)
+        res["ddim100_inpaint"] = {"chain_ms": round(ms, 3), "chain_min_max_ms": [round(min(runs), 3), round(max(runs), 3)],
+                                  "decode_ms": round(decode_ms, 3), "unet_forwards": K,
+                                  "images_per_sec": round(B / ((ms + decode_ms) / 1e3), 2)}
     print(json.dumps(res), flush=True)
 
 
