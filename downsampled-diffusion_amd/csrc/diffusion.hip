@@ -327,6 +327,92 @@ __global__ __launch_bounds__(256) void p_update_restore_point_kernel(const StepR
     }
 }
 
+// DDNM on the DPM-Solver++(2M) chain: rst_x0's clipped x0, its DDNM projection x0' (the x0' of rst_finish /
+// rstm_finish at n >= 2 and of rstm_point at n = 1, restated here so that those kernels keep their instructions), then ms_step's update
+// on x0' with the history holding x0': x_prev = (c1 x0' + c2 x) + c3 h, h <- x0'.  No draw.  mk is the block's (n = 1: the pixel's) mask
+// value, 1 without a mask; an unmeasured y is only ever selected against.  The arithmetic of both tails.
+__device__ __forceinline__ float rsm_x0p(float x0, float m, float y, float mk) { return mk != 0.0f ? __fadd_rn(x0, __fsub_rn(y, m)) : x0; }
+
+__device__ __forceinline__ float rsm_point_x0p(float x0, float y, float mk) { return mk != 0.0f ? y : x0; }
+
+__device__ __forceinline__ float rsm_finish(float x, float x0p, float& h, float c1, float c2, float c3) {
+    const float mean = __fadd_rn(__fmul_rn(c1, x0p), __fmul_rn(c2, x));
+    const float out = __fadd_rn(mean, __fmul_rn(c3, h));
+    h = x0p;
+    return out;
+}
+
+__device__ __forceinline__ float rsm_point(float x, float e, float y, float mk, float& h, float cr, float crm1, float c1, float c2, float c3) {
+    return rsm_finish(x, rsm_point_x0p(rst_x0(x, e, cr, crm1), y, mk), h, c1, c2, c3);
+}
+
+__device__ __forceinline__ float4 rsm_point4(float4 xv, float4 ev, float4 yv, float4 mv, float4& h, float cr, float crm1, float c1, float c2,
+                                             float c3) {
+    float4 o;
+    o.x = rsm_point(xv.x, ev.x, yv.x, mv.x, h.x, cr, crm1, c1, c2, c3);
+    o.y = rsm_point(xv.y, ev.y, yv.y, mv.y, h.y, cr, crm1, c1, c2, c3);
+    o.z = rsm_point(xv.z, ev.z, yv.z, mv.z, h.z, cr, crm1, c1, c2, c3);
+    o.w = rsm_point(xv.w, ev.w, yv.w, mv.w, h.w, cr, crm1, c1, c2, c3);
+    return o;
+}
+
+// The last kernel of an unfused RestoreMultistep step with n >= 2: p_update_restore_kernel's block owner, which also reads and
+// rewrites the history of the n x n elements it owns.  r.rst.mask may be null (every block measured).  No draw, so no Philox key.
+__global__ __launch_bounds__(256) void p_update_restore_ms_kernel(const StepRule r, const float* __restrict__ eps_hat,
+                                                                  const int64_t* __restrict__ t, int B, int n_out, int64_t* dec_counter) {
+    if (dec_counter && blockIdx.x == 0 && threadIdx.x == 0) *dec_counter -= 1;
+    const int n = r.rst.n, H = r.rst.H, W = r.rst.W, Hn = H / n, Wn = W / n;
+    const long long total = (long long)B * Hn * Wn * n_out;
+    float* __restrict__ x = r.x;
+    float* __restrict__ hist = r.x0_hist;
+    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const int c = (int)(i % n_out);
+        long long q = i / n_out;
+        const int bc = (int)(q % Wn);
+        q /= Wn;
+        const int br = (int)(q % Hn), b = (int)(q / Hn);
+        const int64_t tb = t[b];
+        const float cr = r.c_recip[tb], crm1 = r.c_recipm1[tb], a1 = r.c1[tb], a2 = r.c2[tb], a3 = r.c3[tb];
+        const long long e0 = (((long long)b * H + br * n) * W + bc * n) * n_out + c;       // the block's first element
+        const float m = rst_block_mean(
+            [&](int bi, int bj) {
+                const long long e = e0 + ((long long)bi * W + bj) * n_out;
+                return rst_x0(x[e], eps_hat[e], cr, crm1);
+            },
+            n);
+        const float yv = r.rst.y[i];                                      // y is [B][H/n][W/n][n_out]: this thread's index
+        const float mk = r.rst.mask ? r.rst.mask[i / n_out] : 1.0f;       // the mask is [B][H/n][W/n]
+        for (int bi = 0; bi < n; ++bi)
+            for (int bj = 0; bj < n; ++bj) {
+                const long long e = e0 + ((long long)bi * W + bj) * n_out;
+                const float xv = x[e];
+                float hv = hist[e];
+                x[e] = rsm_finish(xv, rsm_x0p(rst_x0(xv, eps_hat[e], cr, crm1), m, yv, mk), hv, a1, a2, a3);
+                hist[e] = hv;
+            }
+    }
+}
+
+// ... and with n = 1 (inpainting): p_update_restore_point_kernel's flat float4 loop with the history float4 read and rewritten
+__global__ __launch_bounds__(256) void p_update_restore_ms_point_kernel(const StepRule r, const float* __restrict__ eps_hat,
+                                                                        const int64_t* __restrict__ t, long long per4, long long total4,
+                                                                        int n_out, int64_t* dec_counter) {
+    if (dec_counter && blockIdx.x == 0 && threadIdx.x == 0) *dec_counter -= 1;
+    float4* __restrict__ x = reinterpret_cast<float4*>(r.x);
+    float4* __restrict__ hist = reinterpret_cast<float4*>(r.x0_hist);
+    const long long hw = (long long)r.rst.H * r.rst.W;
+    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total4; i += (long long)gridDim.x * 256) {
+        const long long b = i / per4;
+        const int64_t tb = t[b];
+        const float cr = r.c_recip[tb], crm1 = r.c_recipm1[tb], a1 = r.c1[tb], a2 = r.c2[tb], a3 = r.c3[tb];
+        const float4 xv = x[i], ev = reinterpret_cast<const float4*>(eps_hat)[i], yv = reinterpret_cast<const float4*>(r.rst.y)[i];
+        const float4 mv = rstm_mask4(r.rst.mask + b * hw, (unsigned)(i - b * per4) * 4u, (unsigned)n_out);      // host: per < 2^31
+        float4 hv = hist[i];
+        x[i] = rsm_point4(xv, ev, yv, mv, hv, cr, crm1, a1, a2, a3);
+        hist[i] = hv;
+    }
+}
+
 // ---- the VLB term of one element (reference models/diffusion/ddpm.py:317-366, models/utils/losses.py:17-109) --------------------
 // Shared by vlb_terms_kernel and the likelihood sweep's epilogues (final_tail_kernel<.., StepKind::Vlb>, vlb_sweep_terms_kernel).
 __device__ __forceinline__ float std_normal_cdf_approx(float v) {
@@ -426,11 +512,14 @@ struct TailParams {
 // RestoreMasked (ddk_sampler_run_restore_masked, x given, Philox only): n >= 2 is Restore's tail with the mask value of each element's
 // block requested beside its y; n = 1 (uniform per launch) needs no whole blocks in the tile: the y float4 and the mask are requested where
 // Inpaint requests known and mask, and phase 2 is p_update_restore_point_kernel's select, with no second barrier.  No LDS beyond Restore's.
+// RestoreMultistep (ddk_sampler_run_restore_multistep, x given, no draw): RestoreMasked's requests and phase 2 with the history float4
+// requested where Multistep requests it; the owner writes x0' back to the history (n >= 2: after the block means are formed from LDS).
+// rst.mask may be null at n >= 2 (every block measured).
 template <int LPP, int VPL, StepKind K>
 __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
     static_assert(K != StepKind::Eps, "the plain forward runs the Ancestral instantiation with p.x null");
     constexpr bool VLB = K == StepKind::Vlb, MS = K == StepKind::Multistep, INP = K == StepKind::Inpaint, RST = K == StepKind::Restore,
-                   RSTM = K == StepKind::RestoreMasked;
+                   RSTM = K == StepKind::RestoreMasked, RSMS = K == StepKind::RestoreMultistep;
     constexpr int PPW = 64 / LPP;                    // pixels per wave and iteration
     constexpr int PPI = 16 * PPW;                    // ... per iteration of the 16-wave workgroup
     constexpr int NIT = 128 / PPI;                   // 4 at C = 128 / 256, 2 at C = 64, 1 at C = 32
@@ -487,13 +576,13 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
             kc = vlb_coef(tb, p.c_recip, p.c_recipm1, p.c1, p.c2, p.logvar);
         } else {
             cr = p.c_recip[tb]; crm1 = p.c_recipm1[tb]; a1 = p.c1[tb]; a2 = p.c2[tb];
-            if constexpr (MS) a3 = p.c3[tb];
+            if constexpr (MS || RSMS) a3 = p.c3[tb];
             else sg = tb > 0 ? p.sigma[tb] : 0.0f;
         }
         const long long i = e4 + tid;
         xv0 = reinterpret_cast<const float4*>(p.x)[i];
         if constexpr (VLB) xt0 = reinterpret_cast<const float4*>(p.xt)[i];
-        if constexpr (MS) zv0 = reinterpret_cast<const float4*>(p.x0_hist)[i];      // MS: zv0 holds the history, not a draw
+        if constexpr (MS || RSMS) zv0 = reinterpret_cast<const float4*>(p.x0_hist)[i];      // MS, RSMS: zv0 holds the history, not a draw
         else zv0 = p.noise ? reinterpret_cast<const float4*>(p.noise + (long long)(p.t_first - tb) * p.noise_step_stride)[i]
                            : philox_normal4((unsigned long long)i, (uint32_t)tb, stream, seed);
         if constexpr (INP) {
@@ -520,6 +609,24 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
                     const long long blk = (yrow0 + row / n) * Wn + col / n;
                     yv0[j] = p.rst.y[blk * p.n_out + c];
                     mv0[j] = p.rst.mask[blk];
+                }
+            }
+        }
+        if constexpr (RSMS) {                          // RSTM's requests; no mask: every block is measured
+            if (p.rst.n == 1) {
+                const float4 yv = reinterpret_cast<const float4*>(p.rst.y)[i];
+                const float4 mv = rstm_mask4(p.rst.mask + pix0, (unsigned)tid * 4u, (unsigned)p.n_out);
+                yv0[0] = yv.x; yv0[1] = yv.y; yv0[2] = yv.z; yv0[3] = yv.w;
+                mv0[0] = mv.x; mv0[1] = mv.y; mv0[2] = mv.z; mv0[3] = mv.w;
+            } else {
+                const int W = p.rst.W, n = p.rst.n, Wn = W / n;
+                const long long yrow0 = ((long long)b * p.HW + tile * 128) / (W * n);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int lp = (tid * 4 + j) / p.n_out, c = tid * 4 + j - lp * p.n_out, row = lp / W, col = lp - row * W;
+                    const long long blk = (yrow0 + row / n) * Wn + col / n;
+                    yv0[j] = p.rst.y[blk * p.n_out + c];
+                    mv0[j] = p.rst.mask ? p.rst.mask[blk] : 1.0f;
                 }
             }
         }
@@ -615,7 +722,20 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
             return;
         }
     }
-    if constexpr (RST || RSTM) {
+    if constexpr (RSMS) {
+        if (p.rst.n == 1) {
+            if (tid < cnt4) {
+                const float4 ev = reinterpret_cast<const float4*>(es)[tid];
+                if (p.eps_out) reinterpret_cast<float4*>(p.eps_out)[e4 + tid] = ev;
+                reinterpret_cast<float4*>(p.x)[e4 + tid] =
+                    rsm_point4(xv0, ev, make_float4(yv0[0], yv0[1], yv0[2], yv0[3]), make_float4(mv0[0], mv0[1], mv0[2], mv0[3]), zv0, cr, crm1,
+                               a1, a2, a3);
+                reinterpret_cast<float4*>(p.x0_hist)[e4 + tid] = zv0;
+            }
+            return;
+        }
+    }
+    if constexpr (RST || RSTM || RSMS) {
         float x0v[4] = {0.f, 0.f, 0.f, 0.f};
         if (tid < cnt4) {
             const float4 ev = reinterpret_cast<const float4*>(es)[tid];
@@ -627,17 +747,20 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
         __syncthreads();
         if (tid < cnt4) {
             const int W = p.rst.W, n = p.rst.n;
-            const float xa[4] = {xv0.x, xv0.y, xv0.z, xv0.w}, za[4] = {zv0.x, zv0.y, zv0.z, zv0.w};
+            const float xa[4] = {xv0.x, xv0.y, xv0.z, xv0.w};
+            float za[4] = {zv0.x, zv0.y, zv0.z, zv0.w};      // RSMS: the history, rewritten by rsm_finish
             float o[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int lp = (tid * 4 + j) / p.n_out, c = tid * 4 + j - lp * p.n_out, row = lp / W, col = lp - row * W;
                 const float* blk = es + ((row & ~(n - 1)) * W + (col & ~(n - 1))) * p.n_out + c;
                 const float m = rst_block_mean([&](int bi, int bj) { return blk[(bi * W + bj) * p.n_out]; }, n);
-                if constexpr (RSTM) o[j] = rstm_finish(xa[j], x0v[j], m, yv0[j], mv0[j], za[j], a1, a2, sg);
+                if constexpr (RSMS) o[j] = rsm_finish(xa[j], rsm_x0p(x0v[j], m, yv0[j], mv0[j]), za[j], a1, a2, a3);
+                else if constexpr (RSTM) o[j] = rstm_finish(xa[j], x0v[j], m, yv0[j], mv0[j], za[j], a1, a2, sg);
                 else o[j] = rst_finish(xa[j], x0v[j], m, yv0[j], za[j], a1, a2, sg);
             }
             reinterpret_cast<float4*>(p.x)[e4 + tid] = make_float4(o[0], o[1], o[2], o[3]);
+            if constexpr (RSMS) reinterpret_cast<float4*>(p.x0_hist)[e4 + tid] = make_float4(za[0], za[1], za[2], za[3]);
         }
         return;
     }
@@ -683,7 +806,7 @@ bool final_tail_ok(int HW, int C, int groups, int n_out, int np, StepKind kind, 
     if (n_out < 1 || n_out > 8 || (128 * n_out) % 4) return false;
     // the restore tail forms block means from the tile's x0 in LDS: the 128-pixel tile must hold whole rows of n x n blocks
     // (the masked kind the same for n >= 2; its n = 1 is pointwise)
-    const bool blocks = kind == StepKind::Restore || (kind == StepKind::RestoreMasked && restore_n != 1);
+    const bool blocks = kind == StepKind::Restore || ((kind == StepKind::RestoreMasked || kind == StepKind::RestoreMultistep) && restore_n != 1);
     if (blocks && !(restore_w > 0 && restore_n > 0 && 128 % (restore_w * restore_n) == 0)) return false;
     return np > 0 && HW == np * 128 && np * groups <= 1024;
 }
@@ -732,6 +855,13 @@ int final_tail(const TailIn& in, const StepRule& r, const int64_t* t, const Chai
                         "H*W of the map and no injected noise");
             p.rst = r.rst;
             return launch_tail<StepKind::RestoreMasked>(p, in.B, st);
+        case StepKind::RestoreMultistep:
+            DDK_REQUIRE(tables && r.c3 && r.x0_hist && aligned16(r.x0_hist) && !r.noise && r.rst.y && (r.rst.mask || r.rst.n != 1) &&
+                            restore_block_ok(r.rst, true) && (long long)r.rst.H * r.rst.W == in.HW && (r.rst.n != 1 || aligned16(r.rst.y)),
+                        "final_tail: the restore multistep step needs x, t, the tables with c3, an aligned history, y (aligned at n = 1), a mask at "
+                        "n = 1, n in {1,2,4,8} dividing H and W, H*W of the map and no injected noise");
+            p.rst = r.rst; p.x0_hist = r.x0_hist; p.c3 = r.c3;
+            return launch_tail<StepKind::RestoreMultistep>(p, in.B, st);
         case StepKind::Vlb: {
             DDK_REQUIRE(r.vlb && tables && !r.eps_out && h.chain_state, "final_tail: the VLB epilogue needs the sweep's step, x, t, the tables and the chain state");
             const VlbStep& v = *r.vlb;
@@ -983,6 +1113,23 @@ int p_update(const StepRule& r, const float* eps_hat, const int64_t* t, int B, l
                                n_out, h.seed, h.stream_id, h.chain_state, h.dec_counter);
             return check_launch("p_update_restore_kernel");
         }
+        case StepKind::RestoreMultistep: {  // RestoreMasked's two kernels with the history; the mask is optional at n >= 2
+            if (!(r.c3 && r.x0_hist && r.rst.y)) return bad("null pointer");
+            if (r.noise || !aligned16(r.x0_hist)) return bad("no injected noise, an aligned history");
+            if (!restore_block_ok(r.rst, true)) return bad("n must be 1, 2, 4 or 8 and divide H and W");
+            if (r.rst.n == 1 && !r.rst.mask) return bad("n = 1 needs a mask (nothing would be constrained)");
+            const long long hw = (long long)r.rst.H * r.rst.W;
+            if (per % hw || per / hw > INT_MAX || per > INT_MAX) return bad("per must be H * W * channels, below 2^31");
+            const int n_out = (int)(per / hw);
+            if (r.rst.n == 1) {
+                if (!aligned16(r.rst.y)) return bad("alignment");
+                hipLaunchKernelGGL(p_update_restore_ms_point_kernel, grid, dim3(256), 0, st, r, eps_hat, t, per / 4, total4, n_out, h.dec_counter);
+                return check_launch("p_update_restore_ms_point_kernel");
+            }
+            hipLaunchKernelGGL(p_update_restore_ms_kernel, dim3(grid1d(B * per / (r.rst.n * r.rst.n))), dim3(256), 0, st, r, eps_hat, t, B, n_out,
+                               h.dec_counter);
+            return check_launch("p_update_restore_ms_kernel");
+        }
         case StepKind::Vlb:       // no update: the sweep's reduction of the step's terms, a kernel of its own
             if (!r.vlb) return bad("null pointer");
             return vlb_sweep_terms(*r.vlb, t, eps_hat, B, per, h.chain_state, st, h.dec_counter);
@@ -1082,6 +1229,16 @@ int ddk_p_sample_update_restore_masked(float* x, const float* eps_hat, const flo
     r.rst = RestoreOps{y, n, H, W, mask};
     return p_update(r, eps_hat, t, B, (long long)H * W * channels, ChainHooks{nullptr, nullptr, seed, stream_id}, as_stream(s),
                     "p_sample_update_restore_masked");
+}
+
+int ddk_p_sample_update_restore_multistep(float* x, const float* eps_hat, float* x0_hist, const float* y, const float* mask, int n,
+                                          const int64_t* t, const float* c_recip, const float* c_recipm1, const float* c1, const float* c2,
+                                          const float* c3, int B, int H, int W, int channels, ddk_stream_t s) {
+    DDK_REQUIRE(B > 0 && H > 0 && W > 0 && channels > 0, "p_sample_update_restore_multistep: B / H / W / channels must be positive");
+    DDK_REQUIRE(mask || n != 1, "p_sample_update_restore_multistep: n = 1 needs a mask (nothing would be constrained)");
+    StepRule r{StepKind::RestoreMultistep, nullptr, x, nullptr, 0, 0, c_recip, c_recipm1, c1, c2, nullptr, x0_hist, c3};
+    r.rst = RestoreOps{y, n, H, W, mask};
+    return p_update(r, eps_hat, t, B, (long long)H * W * channels, ChainHooks{}, as_stream(s), "p_sample_update_restore_multistep");
 }
 
 int ddk_final_tail(const float* raw, const float* partials, int tiles_per_image, const float* gamma, const float* beta, float eps,

@@ -801,6 +801,24 @@ def p_sample_update_restore_masked_(x, eps_hat, y, mask, n, t, c_recip, c_recipm
     return x
 
 
+def p_sample_update_restore_multistep_(x, eps_hat, x0_hist, y, mask, n, t, c_recip, c_recipm1, c1, c2, c3):
+    """In-place DDNM step on the DPM-Solver++(2M) chain of x [B,H,W,C] (NHWC) and of the history x0_hist
+    (same layout; zeros before a chain's first step) per sample row t[b]: p_sample_update_restore_masked_'s x0' for y, mask and n,
+    then x = (c1 x0' + c2 x) + c3 x0_hist and x0_hist = x0'.  No draw.  n in {1, 2, 4, 8}; mask None (n >= 2 only): every block is
+    measured."""
+    b, h, w, c = x.shape
+    n = int(n)
+    if n < 1 or tuple(y.shape) != (b, h // n, w // n, c) or tuple(eps_hat.shape) != tuple(x.shape) or \
+            tuple(x0_hist.shape) != tuple(x.shape) or (mask is not None and tuple(mask.shape) != (b, h // n, w // n)):
+        raise L.DDKError(f"p_sample_update_restore_multistep: x {tuple(x.shape)}, eps_hat {tuple(eps_hat.shape)}, x0_hist "
+                         f"{tuple(x0_hist.shape)}, y {tuple(y.shape)}, mask {None if mask is None else tuple(mask.shape)}, n = {n}")
+    L.check(L.load().ddk_p_sample_update_restore_multistep(L.ptr(_f32(x)), L.ptr(_f32(eps_hat)), L.ptr(_f32(x0_hist)), L.ptr(_f32(y)),
+                                                           L.ptr(None if mask is None else _f32(mask)), n, L.ptr(t), L.ptr(c_recip),
+                                                           L.ptr(c_recipm1), L.ptr(c1), L.ptr(c2), L.ptr(c3), b, h, w, c, L.stream()),
+            "p_sample_update_restore_multistep")
+    return x
+
+
 def randn(shape, device, seed, step, stream_id=0):
     out = torch.empty(shape, device=device, dtype=torch.float32)
     L.check(L.load().ddk_randn(L.ptr(out), out.numel(), seed, step, stream_id, L.stream()), "randn")

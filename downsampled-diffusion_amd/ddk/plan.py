@@ -26,7 +26,8 @@ def sinusoidal_freqs(dim):
 SAMPLERS = {"smp": ("sample", "sampler", "sampler"), "sms": ("sample_multistep", "sampler_multistep", "multistep sampler"),
             "sin": ("sample_inpaint", "sampler_inpaint", "inpainting sampler"),
             "srs": ("sample_restore", "sampler_restore", "super-resolution sampler"),
-            "srm": ("sample_restore_masked", "sampler_restore_masked", "masked restoration sampler")}
+            "srm": ("sample_restore_masked", "sampler_restore_masked", "masked restoration sampler"),
+            "srx": ("sample_restore_multistep", "sampler_restore_multistep", "restoration solver")}
 # workspace kinds whose captured step graphs point into them (the samplers', the likelihood sweep's): UnetPlan._workspace keeps up
 # to 3 of each
 CHAIN_WORKSPACES = (*SAMPLERS, "vsw")
@@ -90,7 +91,8 @@ class UnetPlan:
         reconstruct() (t_start = t_rec_max) at every logging event keeps both sets of graphs instead of re-capturing twice per event.
         Only an eviction drops the plan's cached graphs (ddk_sampler_invalidate waits for the device).  The likelihood sweep's
         workspaces ("vsw"), the multistep sampler's ("sms"), the inpainting sampler's ("sin"), the super-resolution sampler's
-        ("srs") and the masked restoration sampler's ("srm") are kept the same way: their captured steps point into them too."""
+        ("srs"), the masked restoration sampler's ("srm") and the restoration solver's ("srx") are kept the same way: their captured
+        steps point into them too."""
         key = (kind, nbytes, str(device))
         hit = self._ws.get(key)
         if hit is not None:
@@ -403,6 +405,39 @@ class UnetPlan:
 
         return self._run_sampler("srm", x, t_start, t_end,
                                  lambda b, h, w: lib.ddk_sampler_restore_masked_workspace_bytes(self.handle, b, h, w, t_start, int(n)),
+                                 call, use_graph)
+
+    def restore_multistep_tail_parts(self, b, h, w, n):
+        """Tiles per image of the fused tail of a restoration-solver step on [b, h, w] with block n (1 included), or 0."""
+        return int(self._lib.ddk_sampler_restore_multistep_tail_parts(self.handle, b, h, w, int(n)))
+
+    def sample_restore_multistep_nhwc(self, x, y, mask, n, tables, t_start, t_end=0, stream_id=0, use_graph=True, timesteps=None):
+        """DDNM for A = mask o (n x n average pooling) on DPM-Solver++(2M) steps t_start .. t_end (inclusive), in place on x
+        [B,H,W,in_ch] (ddk_sampler_run_restore_multistep).
+
+        y, mask, n: as for sample_restore_masked_nhwc (mask None at n >= 2: every block measured); they are copied into the plan's
+        "srx" workspace by every call, so a loop over images and masks replays one cached graph.  tables / timesteps: as for
+        sample_multistep_nhwc.  Deterministic: no noise, no seed; the history is zeroed by every call."""
+        self._need_packed("srx")
+        b, h, w, c = x.shape
+        if n not in (1, 2, 4, 8) or h % n or w % n:
+            raise L.DDKError(f"sample_restore_multistep: n must be 1, 2, 4 or 8 and divide H = {h} and W = {w}, got {n}")
+        if mask is None and n == 1:
+            raise L.DDKError("sample_restore_multistep: n = 1 needs a mask (nothing would be constrained)")
+        if tuple(y.shape) != (b, h // n, w // n, c) or y.dtype != torch.float32 or not y.is_contiguous():
+            raise L.DDKError(f"y must be a contiguous fp32 [{b},{h // n},{w // n},{c}] tensor, got {tuple(y.shape)} {y.dtype}")
+        if mask is not None and (tuple(mask.shape) != (b, h // n, w // n) or mask.dtype != torch.float32 or not mask.is_contiguous()):
+            raise L.DDKError(f"mask must be a contiguous fp32 [{b},{h // n},{w // n}] tensor, got {tuple(mask.shape)} {mask.dtype}")
+        lib = self._lib
+        tmap = self._timestep_map(timesteps, t_start)
+
+        def call(x, ws, nbytes, stream_ptr):
+            a = self._sampler_args(x, None, tables, t_start, t_end, 0, stream_id, use_graph, ws, nbytes)
+            L.check(lib.ddk_sampler_run_restore_multistep(C.byref(a), tmap, L.ptr(tables["c3"]), L.ptr(y), L.ptr(mask), int(n), stream_ptr),
+                    "sampler_run_restore_multistep")
+
+        return self._run_sampler("srx", x, t_start, t_end,
+                                 lambda b, h, w: lib.ddk_sampler_restore_multistep_workspace_bytes(self.handle, b, h, w, t_start, int(n)),
                                  call, use_graph)
 
     # ---------------------------------------------------------------- likelihood sweep

@@ -15,6 +15,8 @@ through utils/data.py; ``--max_batches`` keeps the first max_batches * batch_siz
   * ``--task inpaint --method ddnm``: DDNM for a mask (section 3.8) instead of RePaint, with ``--use_ddim`` / ``--eta`` and without
     the ``--jump_*`` options; ``--task sr --mask KIND``: masked super-resolution, the mask applied to the pooled image, restored
     with ``model.restore``; the baselines mean-fill the same holes before they upsample.
+  * ``--dpm_solver`` (DDNM only, not with ``--use_ddim`` / ``--eta``): DDNM on the DPM-Solver++(2M) chain (section 3.9,
+    ``model.restore_solver``) over the ``--timestep_respacing`` grid (e.g. ``logsnr20``); ``method`` then reads ``ddnm_dpmpp2m``.
   * batch g draws x_T and its Philox key from ``--seed`` + g.
 
 Prints one JSON object, the settings that produced it (among them ``method`` and ``unet_forwards``, the UNet forwards per image, so
@@ -45,6 +47,8 @@ def parse_args(argv=None):
     ap.add_argument("--timestep_respacing", default="", help='run K of the T steps: "N", "n1,n2,..." sections or (sr) "ddimN"')
     ap.add_argument("--use_ddim", action="store_true", help="sr: DDIM steps instead of ancestral ones")
     ap.add_argument("--eta", type=float, default=0.0, help="sr: DDIM noise scale (0: deterministic)")
+    ap.add_argument("--dpm_solver", action="store_true",
+                    help='ddnm: DPM-Solver++(2M) steps over the --timestep_respacing grid (e.g. "logsnr20"); not with --use_ddim / --eta')
     ap.add_argument("--jump_length", type=int, default=10, help="inpaint: RePaint jump length")
     ap.add_argument("--jump_n_sample", type=int, default=10, help="inpaint: RePaint resamplings per jump")
     ap.add_argument("--batch_size", type=int, default=32)
@@ -64,13 +68,15 @@ def parse_args(argv=None):
     elif args.mask is None:
         args.mask = "center"
     if args.method == "ddnm":
+        if args.dpm_solver and (args.use_ddim or args.eta != 0.0):
+            ap.error("--dpm_solver is its own deterministic update: it cannot be combined with --use_ddim or --eta")
         if args.eta < 0 or (args.eta != 0.0 and not args.use_ddim):
             ap.error("--eta needs --use_ddim and a value >= 0")
         if args.jump_length != ap.get_default("jump_length") or args.jump_n_sample != ap.get_default("jump_n_sample"):
             ap.error("--jump_length and --jump_n_sample belong to --method repaint (DDNM has no jumps)")
     else:
-        if args.use_ddim or args.eta != 0.0:
-            ap.error("--use_ddim and --eta belong to DDNM (RePaint runs ancestral steps)")
+        if args.use_ddim or args.eta != 0.0 or args.dpm_solver:
+            ap.error("--use_ddim, --eta and --dpm_solver belong to DDNM (RePaint runs ancestral steps)")
         if args.jump_length < 1 or args.jump_n_sample < 1:
             ap.error("--jump_length and --jump_n_sample must be >= 1")
     return args
@@ -80,7 +86,9 @@ def chain_options(args):
     """the task's keywords for evaluate_restoration, also the chain settings the result records"""
     kw = dict(respacing=args.timestep_respacing or None)
     if args.task == "sr":
-        kw.update(scale=args.scale, ddim=args.use_ddim, eta=args.eta)
+        kw.update(scale=args.scale)
+    if args.dpm_solver:
+        kw.update(dpm_solver=True)
     elif args.method == "ddnm":
         kw.update(ddim=args.use_ddim, eta=args.eta)
     else:

@@ -10,11 +10,12 @@ u8 / 255 * 2 - 1 as the training data is), hides the region given by ``--mask`` 
   * ``--timestep_respacing`` (e.g. "250"), ``--jump_length`` and ``--jump_n_sample`` set the RePaint schedule;
   * ``--method ddnm`` fills with ``model.restore`` (scale 1) instead: ``--use_ddim`` and ``--eta`` choose DDIM steps, the
     ``--jump_*`` options must stay at their defaults, and a mask that differs between the channels counts a pixel as known only
-    where every channel is;
+    where every channel is; ``--dpm_solver`` (with ``--method ddnm`` only, not with ``--use_ddim`` / ``--eta``) fills with
+    ``model.restore_solver``, DDNM on the DPM-Solver++(2M) chain (section 3.9; use a log-SNR grid, e.g. ``logsnr20``);
   * batch g draws x_T and its Philox key from ``--seed`` + g.
 
 Writes ``{saved_model}_inpaint_{mask}_{spec}_j{j}r{r}.npy`` (float32 [N, H, W, C] in [0, 255]; with ``--method ddnm``
-``{saved_model}_inpaint_{mask}_{spec}_ddnm[_ddim_eta{eta}].npy``) and, beside it, the masked inputs for viewing
+``{saved_model}_inpaint_{mask}_{spec}_ddnm[_ddim_eta{eta}|_dpmpp2m].npy``) and, beside it, the masked inputs for viewing
 (``..._masked.npy``, hidden pixels 0).  One process, one GPU.
 """
 import argparse
@@ -47,6 +48,8 @@ def main():
     ap.add_argument("--method", default="repaint", choices=("repaint", "ddnm"), help="repaint (section 3.5) or ddnm (section 3.8)")
     ap.add_argument("--use_ddim", action="store_true", help="ddnm: DDIM steps instead of ancestral ones")
     ap.add_argument("--eta", type=float, default=0.0, help="ddnm: DDIM noise scale (0: deterministic)")
+    ap.add_argument("--dpm_solver", action="store_true",
+                    help='ddnm: DPM-Solver++(2M) steps over the --timestep_respacing grid (e.g. "logsnr20"); not with --use_ddim / --eta')
     ap.add_argument("--jump_length", type=int, default=10)
     ap.add_argument("--jump_n_sample", type=int, default=10)
     ap.add_argument("--batch_size", type=int, default=32)
@@ -58,10 +61,12 @@ def main():
     if args.method == "ddnm":
         if args.jump_length != ap.get_default("jump_length") or args.jump_n_sample != ap.get_default("jump_n_sample"):
             ap.error("--jump_length and --jump_n_sample belong to --method repaint (DDNM has no jumps)")
+        if args.dpm_solver and (args.use_ddim or args.eta != 0.0):
+            ap.error("--dpm_solver is its own deterministic update: it cannot be combined with --use_ddim or --eta")
         if args.eta < 0 or (args.eta != 0.0 and not args.use_ddim):
             ap.error("--eta needs --use_ddim and a value >= 0")
-    elif args.use_ddim or args.eta != 0.0:
-        ap.error("--use_ddim and --eta belong to --method ddnm (RePaint runs ancestral steps)")
+    elif args.use_ddim or args.eta != 0.0 or args.dpm_solver:
+        ap.error("--use_ddim, --eta and --dpm_solver belong to --method ddnm (RePaint runs ancestral steps)")
     if args.images is None and not args.synthetic:
         ap.error("--images is required unless --synthetic is given")
 
@@ -105,7 +110,11 @@ def main():
 
     spec = args.timestep_respacing.replace(",", "-") or "full"
     ddnm = args.method == "ddnm"
-    if ddnm:
+    if ddnm and args.dpm_solver:
+        kw = dict(respacing=args.timestep_respacing or None, solver="dpm++2m")
+        tail = "_ddnm_dpmpp2m"
+        print(f"Inpainting {n} images ({mask_name} mask, {spec} steps, DDNM on DPM-Solver++(2M)) with {args.saved_model}.")
+    elif ddnm:
         kw = dict(respacing=args.timestep_respacing or None, ddim=args.use_ddim, eta=args.eta)
         tail = "_ddnm" + (f"_ddim_eta{args.eta:g}" if args.use_ddim else "")
         print(f"Inpainting {n} images ({mask_name} mask, {spec} steps, DDNM{', DDIM eta ' + format(args.eta, 'g') if args.use_ddim else ''}) "
@@ -120,7 +129,10 @@ def main():
     for g, i in enumerate(range(0, n, args.batch_size)):
         torch.manual_seed(args.seed + g)          # x_T and the Philox key of batch g
         x, m = x_all[i:i + args.batch_size].to(device), mask_all[i:i + args.batch_size].to(device)
-        out = model.restore(x, m.amin(dim=1), 1, **kw) if ddnm else model.inpaint(x, m, **kw)
+        if ddnm:
+            out = (model.restore_solver if args.dpm_solver else model.restore)(x, m.amin(dim=1), 1, **kw)
+        else:
+            out = model.inpaint(x, m, **kw)
         if config["model"] == "dddpm":
             out = out[0]
         outs.append(to_u8_range(out))

@@ -112,20 +112,26 @@ class DownsampleDDPM(DDPM):
         d = int(self.dim_reduc)
         scales = (1,) + tuple(d * n for n in (1,) + self.RESTORE_BLOCKS)
         y, m = self._restore_masked_args(y, mask, scale, self.x_shape, ddim, eta, unsupported, scales)
-        s = int(scale)
+        return self._latent_restore(y, m, int(scale), paste, "restore",
+                                    lambda y_lat, n_lat, m_lat: self._restore_loop(y_lat, n_lat, respacing, ddim, eta, x_T, seed, mask=m_lat,
+                                                                                   who="restore"))
+
+    def _latent_restore(self, y, m, s, paste, who, loop):
+        """What restore and restore_solver share once their arguments are checked: the latent constraint of y, mask m and scale s
+        (see restore), the chain loop(y_lat, n_lat, m_lat) in the latent, the decoder and the paste.  Returns (x_out, z)."""
+        d = int(self.dim_reduc)
         if m is None and s == d:
-            raise ValueError(f"restore: scale = {d} is one latent pixel per measurement and needs a mask (nothing would be constrained)")
+            raise ValueError(f"{who}: scale = {d} is one latent pixel per measurement and needs a mask (nothing would be constrained)")
         m_lat = None
         if s == 1:
             m_lat = -torch.nn.functional.max_pool2d(-m.unsqueeze(1), d)[:, 0]
             if not bool((m_lat.reshape(m_lat.shape[0], -1).amax(dim=1) > 0).all()):
-                raise ValueError(f"restore: no {d} x {d} latent footprint of some image is wholly measured")
+                raise ValueError(f"{who}: no {d} x {d} latent footprint of some image is wholly measured")
         y = y.to(self.betas.device)
         self._check_device(y)
         if s == 1:
             m = m.to(y.device)
-            z_ref = self.rescaled_downsample(y)                       # _restore_masked_args zeroed what is not measured
-            z = self._restore_loop(z_ref, 1, respacing, ddim, eta, x_T, seed, mask=m_lat, who="restore")
+            z = loop(self.rescaled_downsample(y), 1, m_lat)               # the argument check zeroed what is not measured
             x_out = self.rescaled_upsample(z)
             if paste:
                 x_out = torch.where(m.unsqueeze(1) != 0, y, x_out)
@@ -133,8 +139,18 @@ class DownsampleDDPM(DDPM):
         n_lat = s // d
         z_ref = self.rescaled_downsample(y.repeat_interleave(s, dim=2).repeat_interleave(s, dim=3))
         y_lat = torch.nn.functional.avg_pool2d(z_ref, n_lat) if n_lat > 1 else z_ref
-        z = self._restore_loop(y_lat, n_lat, respacing, ddim, eta, x_T, seed, mask=None if m is None else m.to(y.device), who="restore")
+        z = loop(y_lat, n_lat, None if m is None else m.to(y.device))
         return self.rescaled_upsample(z), z
+
+    @torch.no_grad()
+    def restore_solver(self, y, mask=None, scale=1, *, respacing=None, solver="dpm++2m", order=2, x_T=None, paste=True, **unsupported):
+        """DDPM.restore_solver with the constraint held in the latent exactly as restore holds it (same scales, same mask rules, same
+        paste).  Returns (x_out, z); x_T is a latent start."""
+        d = int(self.dim_reduc)
+        scales = (1,) + tuple(d * n for n in (1,) + self.RESTORE_BLOCKS)
+        y, m = self._restore_solver_args(y, mask, scale, self.x_shape, solver, order, unsupported, scales)
+        return self._latent_restore(y, m, int(scale), paste, "restore_solver",
+                                    lambda y_lat, n_lat, m_lat: self._restore_solver_loop(y_lat, n_lat, respacing, solver, order, x_T, mask=m_lat))
 
     @torch.no_grad()
     def reconstruct(self, x, n):

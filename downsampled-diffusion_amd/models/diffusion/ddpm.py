@@ -159,9 +159,11 @@ class DDPM(nn.Module):
         return self._cached_tables((respacing, bool(ddim), float(eta)),
                                    lambda: respace.spaced_tables(self._betas64, respacing, ddim, eta))
 
-    def _solver_tables(self, respacing, solver):
-        """(tables c_recip, c_recipm1, c1, c2, c3, timestep map) of a DPM-Solver++(2M) chain (respace.dpm_solver_tables)."""
-        return self._cached_tables(('solver', respacing, solver), lambda: respace.dpm_solver_tables(self._betas64, respacing, order=2))
+    def _solver_tables(self, respacing, solver, order=2):
+        """(tables c_recip, c_recipm1, c1, c2, c3, timestep map) of a DPM-Solver++(2M) chain (respace.dpm_solver_tables); order 1
+        (restore_solver only) is the same chain with c3 = 0 in every row."""
+        key = ('solver', respacing, solver) if order == 2 else ('solver', respacing, solver, order)
+        return self._cached_tables(key, lambda: respace.dpm_solver_tables(self._betas64, respacing, order=order))
 
     def _chain_start(self, shape, x_T, early_stop, get_tables):
         """(device, tables, use, start state, k_start, k_end) of a chain with (tables, use) = get_tables(), asked for once the
@@ -487,6 +489,60 @@ class DDPM(nn.Module):
         pixels and eta without ddim, before any device work."""
         y, m = self._restore_masked_args(y, mask, scale, self.sample_shape, ddim, eta, unsupported, self.RESTORE_SCALES)
         return self._restore_loop(y, int(scale), respacing, ddim, eta, x_T, seed, mask=m, who="restore")
+
+    # ------------------------------------------------------------------ DDNM on the DPM-Solver++(2M) chain
+    RESTORE_SOLVER_UNSUPPORTED = ('ddim', 'eta', 'seed', 'noise', 'early_stop')
+
+    def _restore_solver_args(self, y, mask, scale, shape, solver, order, unsupported, scales):
+        """ValueError for anything restore_solver cannot take, before any device work; then _restore_masked_args' checks and
+        return value."""
+        if unsupported:
+            raise ValueError(f"restore_solver: {sorted(unsupported)} not accepted (the solver is deterministic and its own update over "
+                             f"the whole grid: no {', '.join(self.RESTORE_SOLVER_UNSUPPORTED)})")
+        if solver not in SOLVERS:
+            raise ValueError(f"restore_solver: solver must be one of {SOLVERS}, got {solver!r}")
+        if isinstance(order, bool) or not isinstance(order, (int, np.integer)) or order not in (1, 2):
+            raise ValueError(f"restore_solver: order must be 1 or 2, got {order!r}")
+        return self._restore_masked_args(y, mask, scale, shape, False, 0.0, {}, scales)
+
+    def _restore_solver_loop(self, y, n, respacing, solver, order, x_T, mask=None):
+        """DDNM on the solver's chain over the latent whose n x n block means are held at y [B, C, H/n, W/n] where mask [B, H/n, W/n]
+        (None: everywhere) is 1: native (UnetPlan.sample_restore_multistep_nhwc) or, with native_sampler off, the same op as a Python
+        loop in the same NHWC layout."""
+        device = self.betas.device
+        if device.type != 'cuda':
+            raise DDKError("restore_solver: move the model to a ROCm device first (no CPU fallback)")
+        tables, use = self._solver_tables(respacing, solver, int(order))
+        shape = (y.shape[0], *self.sample_shape)
+        if x_T is not None and tuple(x_T.shape) != shape:
+            raise ValueError(f"restore_solver: x_T must be {shape}, got {tuple(x_T.shape)}")
+        img = torch.randn(shape, device=device) if x_T is None else x_T.to(device).float()
+        k_start = len(use) - 1
+        yl = ops.nchw_to_nhwc(y.to(device).float().contiguous())
+        mk = None if mask is None else mask.to(device).float().contiguous()
+        x = ops.nchw_to_nhwc(img.contiguous())
+        if not self.native_sampler:
+            hist = torch.zeros_like(x)
+            with self._eps_model_nhwc().plan().forwards_as_in_chain():
+                for k in range(k_start, -1, -1):
+                    eps_hat = self.latent_model(ops.nhwc_to_nchw(x), torch.full((shape[0],), use[k], device=device, dtype=torch.long))
+                    ops.p_sample_update_restore_multistep_(x, ops.nchw_to_nhwc(eps_hat.contiguous()), hist, yl, mk, n,
+                                                           torch.full((shape[0],), k, device=device, dtype=torch.long), **tables)
+            return ops.nhwc_to_nchw(x)
+        self._eps_model_nhwc().plan().sample_restore_multistep_nhwc(x, yl, mk, n, tables, k_start, stream_id=int(self.rng_stream_id),
+                                                                    use_graph=self.use_graph, timesteps=use)
+        return ops.nhwc_to_nchw(x)
+
+    @torch.no_grad()
+    def restore_solver(self, y, mask=None, scale=1, *, respacing=None, solver="dpm++2m", order=2, x_T=None, **unsupported):
+        """restore() in few steps: DDNM for A = mask o (scale x scale average pooling) on the
+        DPM-Solver++(2M) chain over the respacing's timesteps (use "logsnrN").  Every step projects its clipped x0 onto
+        {A x0 = y} and hands the solver that x0', as its data prediction and as its history.  y, mask, scale and their
+        ValueErrors: as restore.  order = 1 drops the history term (DDNM on DDIM eta 0 in the solver's form).  Deterministic
+        given x_T: ddim / eta / seed / noise / early_stop raise ValueError, as do an unknown solver and an order not in {1, 2},
+        before any device work.  The measured pixels (scale 1) equal y exactly; measured block means equal y up to fp32 rounding."""
+        y, m = self._restore_solver_args(y, mask, scale, self.sample_shape, solver, order, unsupported, self.RESTORE_SCALES)
+        return self._restore_solver_loop(y, int(scale), respacing, solver, order, x_T, mask=m)
 
     @torch.no_grad()
     def reconstruct(self, x, n):

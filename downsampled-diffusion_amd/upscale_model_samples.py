@@ -7,7 +7,9 @@ Loads the checkpoint as generate_model_samples.py does (``--synthetic CONFIG`` b
   * images of the model's size divided by ``--scale`` are taken as the low-resolution input; images of the model's full size
     are first average-pooled by ``--scale`` (so a test set can be degraded and restored in one go);
   * ``--scale`` is 2, 4 or 8 for a DDPM; a dDDPM holds the constraint in its latent and takes 2, 4 or 8 times its reduction;
-  * ``--timestep_respacing``, ``--use_ddim`` and ``--eta`` choose the chain as in generate_model_samples.py;
+  * ``--timestep_respacing``, ``--use_ddim`` and ``--eta`` choose the chain as in generate_model_samples.py; ``--dpm_solver``
+    (not with ``--use_ddim`` / ``--eta``) runs ``model.restore_solver`` instead, DDNM on the DPM-Solver++(2M) chain (section 3.9;
+    use a log-SNR grid, e.g. ``logsnr20``), and adds ``_dpmpp2m`` to the file names;
   * batch g draws x_T and its Philox key from ``--seed`` + g.
 
 Writes ``{saved_model}_sr{scale}_{spec}.npy`` through the sampling driver's output stage (utils.OutputStage: float32
@@ -37,10 +39,14 @@ def main():
     ap.add_argument("--timestep_respacing", default="", help='run K of the T steps: "ddimN", "N" or "n1,n2,..." sections')
     ap.add_argument("--use_ddim", action="store_true", help="DDIM steps instead of ancestral ones")
     ap.add_argument("--eta", type=float, default=0.0, help="DDIM noise scale (0: deterministic)")
+    ap.add_argument("--dpm_solver", action="store_true",
+                    help='DPM-Solver++(2M) steps over the --timestep_respacing grid (e.g. "logsnr20"); not with --use_ddim / --eta')
     ap.add_argument("--batch_size", type=int, default=32)
     ap.add_argument("--seed", type=int, default=1234, help="base seed: batch g draws from seed + g")
     ap.add_argument("--out_dir", default=None)
     args = ap.parse_args()
+    if args.dpm_solver and (args.use_ddim or args.eta != 0.0):
+        ap.error("--dpm_solver is its own deterministic update: it cannot be combined with --use_ddim or --eta")
     if args.eta < 0 or (args.eta != 0.0 and not args.use_ddim):
         ap.error("--eta needs --use_ddim and a value >= 0")
     if args.batch_size < 1 or args.scale < 2:
@@ -82,14 +88,19 @@ def main():
     n = y_all.shape[0]
     lowres = ((y_all + 1) * 127.5).round().clamp(0, 255).permute(0, 2, 3, 1).numpy().astype(np.uint8)
 
-    spec = (args.timestep_respacing.replace(",", "-") or "full") + (f"_ddim_eta{args.eta:g}" if args.use_ddim else "")
-    kw = dict(respacing=args.timestep_respacing or None, ddim=args.use_ddim, eta=args.eta)
+    spec = (args.timestep_respacing.replace(",", "-") or "full") + (f"_ddim_eta{args.eta:g}" if args.use_ddim else "") + \
+        ("_dpmpp2m" if args.dpm_solver else "")
+    if args.dpm_solver:
+        kw = dict(respacing=args.timestep_respacing or None, solver="dpm++2m")
+    else:
+        kw = dict(respacing=args.timestep_respacing or None, ddim=args.use_ddim, eta=args.eta)
     print(f"Upscaling {n} images x{s} ({spec} steps) with {args.saved_model}.")
     stage = OutputStage()
     t0 = time.time()
     for g, i in enumerate(range(0, n, args.batch_size)):
         torch.manual_seed(args.seed + g)          # x_T and the Philox key of batch g
-        out = model.super_resolve(y_all[i:i + args.batch_size].to(device), s, **kw)
+        y = y_all[i:i + args.batch_size].to(device)
+        out = model.restore_solver(y, None, s, **kw) if args.dpm_solver else model.super_resolve(y, s, **kw)
         stage.submit(out[0] if config["model"] == "dddpm" else out)
     batches = stage.finish()
     torch.cuda.synchronize()

@@ -103,7 +103,8 @@ def _score(ops, cand_u8, ref_u8, hidden, device):
 
 
 @torch.no_grad()
-def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234, mask="center", scale=4, method=None, sr_mask=None, **chain):
+def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234, mask="center", scale=4, method=None, sr_mask=None,
+                         dpm_solver=False, **chain):
     """Degrade, restore and score ``images_uint8`` (uint8 [N, H, W, C] of the model's size).
 
     task "inpaint": ``mask`` is one of MASKS or a {0, 1} tensor broadcastable to [N, 1|C, H, W] (1 = known); ``chain`` goes to
@@ -118,6 +119,8 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
     [N, 1, H/scale, W/scale]) applies to the pooled image, ``model.restore`` upscales it, and the baselines mean-fill the pooled
     image's holes before they upsample it, so they are scored on the same degraded input.  The consistency is then over the
     measured pixels.  Without a mask, task "sr" is ``model.super_resolve`` as before.
+    dpm_solver (method "ddnm" only; ``chain``: respacing alone, no ddim / eta): DDNM on the DPM-Solver++(2M) chain (section 3.9),
+    ``model.restore_solver`` in place of ``restore`` / ``super_resolve``; the returned method is then "ddnm_dpmpp2m".
     Batch g draws x_T and its Philox key from seed + g, as the sampling CLIs do.
 
     "method" and "unet_forwards" (UNet forwards per image: the chain's steps; the batch shares each forward) are returned too.
@@ -137,13 +140,21 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
         method = "repaint" if task == "inpaint" else "ddnm"
     if method not in METHODS or (task == "sr" and method != "ddnm"):
         raise ValueError(f"unknown method {method!r} for task {task!r}: one of {METHODS} (sr: ddnm only)")
-    K = len(model._spaced_tables(chain.get("respacing"), chain.get("ddim", False), chain.get("eta", 0.0))[1]) \
-        if chain.get("respacing") is not None or chain.get("ddim") else int(model.timesteps)
+    if dpm_solver:
+        if method != "ddnm" or chain.get("ddim") or chain.get("eta", 0.0) != 0.0:
+            raise ValueError("dpm_solver runs DDNM on its own deterministic update: method 'ddnm', no ddim, no eta")
+        chain = dict({k: v for k, v in chain.items() if k not in ("ddim", "eta")}, solver="dpm++2m")
+        K = len(model._solver_tables(chain.get("respacing"), "dpm++2m")[1])
+        run = model.restore_solver
+    else:
+        K = len(model._spaced_tables(chain.get("respacing"), chain.get("ddim", False), chain.get("eta", 0.0))[1]) \
+            if chain.get("respacing") is not None or chain.get("ddim") else int(model.timesteps)
+        run = model.restore
     if task == "inpaint":
         m_all = make_mask(mask, n, h, w) if isinstance(mask, str) else torch.as_tensor(mask).float().expand(n, -1, h, w)
         if method == "ddnm":
             m_all = m_all.amin(dim=1, keepdim=True)
-            restore = lambda i: model.restore(x_all[i:i + batch_size].to(device), m_all[i:i + batch_size, 0].to(device), 1, **chain)
+            restore = lambda i: run(x_all[i:i + batch_size].to(device), m_all[i:i + batch_size, 0].to(device), 1, **chain)
             extra["unet_forwards"] = K
         else:
             restore = lambda i: model.inpaint(x_all[i:i + batch_size].to(device), m_all[i:i + batch_size].to(device), **chain)
@@ -159,13 +170,14 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
         extra["unet_forwards"] = K
         my_all = None
         if sr_mask is None:
-            restore = lambda i: model.super_resolve(y_all[i:i + batch_size].to(device), scale, **chain)
+            restore = (lambda i: run(y_all[i:i + batch_size].to(device), None, scale, **chain)) if dpm_solver else \
+                (lambda i: model.super_resolve(y_all[i:i + batch_size].to(device), scale, **chain))
             y_base = y_all
         else:
             hs, ws = h // scale, w // scale
             my_all = make_mask(sr_mask, n, hs, ws) if isinstance(sr_mask, str) else torch.as_tensor(sr_mask).float().expand(n, -1, hs, ws)
             my_all = my_all.amin(dim=1, keepdim=True)
-            restore = lambda i: model.restore(y_all[i:i + batch_size].to(device), my_all[i:i + batch_size, 0].to(device), scale, **chain)
+            restore = lambda i: run(y_all[i:i + batch_size].to(device), my_all[i:i + batch_size, 0].to(device), scale, **chain)
             y_base = mean_fill(y_all, my_all)             # the baselines see the same holes
         images["replicate"] = to_u8(replicate(y_base, scale))
         images["bicubic"] = to_u8(bicubic(y_base, scale))
@@ -181,7 +193,7 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
         extra["consistency"] = (((pool(x_out, scale) - y_all) * meas).abs().amax(dim=(1, 2, 3)) * 127.5).double().numpy()
         extra["consistency_u8"] = (((pool(from_u8(images["restored"]), scale) - y_all) * meas).abs().amax(dim=(1, 2, 3)) * 127.5).double().numpy()
     methods = {name: _score(ops, img, ref, hidden, device) for name, img in images.items()}
-    return dict(n_images=n, method=method, methods=methods, images={k: v.numpy() for k, v in images.items()}, **extra)
+    return dict(n_images=n, method=method + ("_dpmpp2m" if dpm_solver else ""), methods=methods, images={k: v.numpy() for k, v in images.items()}, **extra)
 
 
 def report(result):

@@ -320,6 +320,17 @@ int ddk_p_sample_update_restore(float* x, const float* eps_hat, const float* y, 
 int ddk_p_sample_update_restore_masked(float* x, const float* eps_hat, const float* y, const float* mask, int n, const int64_t* t,
                                        const float* c_recip, const float* c_recipm1, const float* c1, const float* c2, const float* sigma,
                                        int B, int H, int W, int channels, uint64_t seed, uint32_t stream_id, ddk_stream_t s);
+/* One DDNM step on the DPM-Solver++(2M) chain on its own (ddk_sampler_run_restore_multistep), per sample b with
+ * row t[b] of the tables of ddk_sampler_run_multistep:
+ *   x0  = clamp(c_recip x - c_recipm1 eps_hat, -1, 1);
+ *   x0' = the x0' of ddk_p_sample_update_restore_masked for this y, mask and n (a select on the mask; NaN in unmeasured y reaches nothing);
+ *   x   = (c1 x0' + c2 x) + c3 x0_hist;   x0_hist = x0'.
+ * No draw.  x0_hist has x's layout.  mask may be NULL for n >= 2 (every block measured); n == 1 without a mask is DDK_ERR_ARG.
+ * H * W * channels must be a multiple of 4 (below 2^31); x, eps_hat, x0_hist and, at n == 1, y 16-byte aligned.  On an error neither x
+ * nor x0_hist is touched. */
+int ddk_p_sample_update_restore_multistep(float* x, const float* eps_hat, float* x0_hist, const float* y, const float* mask, int n,
+                                          const int64_t* t, const float* c_recip, const float* c_recipm1, const float* c1, const float* c2,
+                                          const float* c3, int B, int H, int W, int channels, ddk_stream_t s);
 /* The end of a forward in one launch (unet.py:69-72 behind the final Block's conv; ddpm.py:203-227): GroupNorm from the conv's
  * partials -> Mish -> 1x1 projection to n_out <= 8 channels (w [n_out][C], bias [n_out]) -> eps_hat; eps_out and / or x may be
  * given: eps_out [B][HW][n_out] receives eps_hat, x [B][HW][n_out] gets the reverse-step update of ddk_p_sample_update in place
@@ -424,7 +435,8 @@ int ddk_unet_forward(const ddk_unet* u, const void* packed, const float* x, cons
 /* DDK_OPT_RESTORE_FUSED_TAIL (default 1): a step of ddk_sampler_run_restore ends inside the forward's last launch wherever
  * ddk_sampler_restore_tail_parts says it can; 0 ends every step in ddk_p_sample_update_restore's kernel behind the forward, as the
  * shapes that cannot do (where the plain forward ends in one launch, that launch leaves eps_hat in the workspace first, so the
- * update sees the same eps_hat).  Bit-identical results either way (tests/test_restore_gpu.py). */
+ * update sees the same eps_hat).  Bit-identical results either way (tests/test_restore_gpu.py).  The masked chain
+ * (ddk_sampler_run_restore_masked) and the solver's (ddk_sampler_run_restore_multistep) obey it too. */
 #define DDK_OPT_RESTORE_FUSED_TAIL 12
 int ddk_unet_set_option(ddk_unet* u, int option, int value);
 /* Waits for `s`, then reads and clears the sticky give-up count of the launches issued on `workspace` (a ddk_unet_forward or
@@ -543,6 +555,19 @@ size_t ddk_sampler_restore_masked_workspace_bytes(const ddk_unet* u, int B, int 
 int ddk_sampler_restore_masked_tail_parts(const ddk_unet* u, int B, int H, int W, int n);
 int ddk_sampler_run_restore_masked(const ddk_sampler_args* a, const int64_t* timestep_map, const float* y, const float* mask, int n,
                                    ddk_stream_t s);
+/* Zero-shot restoration in few steps: DDNM for A = mask o (n x n average pooling) on the DPM-Solver++(2M) chain (DESIGN.md section
+ * 3.9).  The chain, tables (c3 included) and zeroed history of ddk_sampler_run_multistep, every step being
+ * ddk_p_sample_update_restore_multistep's, on the y and mask of ddk_sampler_run_restore_masked (mask NULL at n >= 2: every block
+ * measured; n = 1 without a mask is DDK_ERR_ARG).  The workspace (ddk_sampler_restore_multistep_workspace_bytes) is the sampler's
+ * layout, then the history, then y and the mask, which are copied in before the first step, outside any captured step: a loop over
+ * images and masks on one workspace replays one cached graph.  a->noise must be NULL; a->sigma and a->seed are ignored.  Graphs are
+ * cached under a chain kind of their own, with c3, n and the presence of a mask in the key.  DDK_OPT_RESTORE_FUSED_TAIL = 0 forces the
+ * unfused tail here too; the two tails are bit-identical.  ddk_sampler_restore_multistep_tail_parts: as
+ * ddk_sampler_restore_masked_tail_parts. */
+size_t ddk_sampler_restore_multistep_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start, int n);
+int ddk_sampler_restore_multistep_tail_parts(const ddk_unet* u, int B, int H, int W, int n);
+int ddk_sampler_run_restore_multistep(const ddk_sampler_args* a, const int64_t* timestep_map, const float* c3, const float* y,
+                                      const float* mask, int n, ddk_stream_t s);
 /* Drops the plan's cached sampler and likelihood-sweep graphs and shift table (waits for the device when graphs exist). */
 int ddk_sampler_invalidate(ddk_unet* u);
 /* Drops only the cached graphs (and shift table) that live in / point into `workspace`, after waiting for the launches of

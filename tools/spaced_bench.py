@@ -18,7 +18,11 @@ unfused tail), timed alternately the same way (the chains differ only in the ste
 
 --restore-masked: the cost of a masked DDNM step at n = 1 (inpainting, the fused tail; and with the fused
 tail switched off) and n = 2 with a mask, against an ancestral step of the same respaced "50" chain, timed the same way, and the
-images/s of "100"-step DDIM (eta 0) DDNM inpainting with the decode, for the comparison with RePaint's 2410 ops."""
+images/s of "100"-step DDIM (eta 0) DDNM inpainting with the decode, for the comparison with RePaint's 2410 ops.
+
+--restore-solver: the cost of a DDNM step on the DPM-Solver++(2M) chain at n = 1 with the center mask and n = 2
+without a mask, against a plain 2M step on the same "logsnr20" grid, timed alternately the same way, and the end-to-end images/s of
+each with the decode."""
 import argparse
 import json
 import os
@@ -47,6 +51,7 @@ def main():
     ap.add_argument("--solver", action="store_true", help="2M step against DDIM step on logsnrK grids")
     ap.add_argument("--restore", action="store_true", help="DDNM super-resolution step against an ancestral step, respacing 50")
     ap.add_argument("--restore-masked", action="store_true", help="masked DDNM step (n = 1, 2) against an ancestral step, respacing 50")
+    ap.add_argument("--restore-solver", action="store_true", help="DDNM step on the 2M chain (n = 1 center mask, n = 2) against a 2M step, logsnr20")
     args = ap.parse_args()
     torch.cuda.set_device(0)
     cfg = bench.cfg4()
@@ -80,6 +85,10 @@ def main():
         elif kind == "anc":
             sp, use = model._spaced_tables(str(K), False, 0.0)
             plan.sample_nhwc(x, sp, K - 1, 0, seed=1234, stream_id=0, timesteps=use)
+        elif kind.startswith("rsolver"):                 # DDNM on the 2M chain: n = 1 with the center mask, n >= 2 without a mask
+            n = int(kind[len("rsolver"):])
+            sp, use = model._solver_tables(f"logsnr{K}", "dpm++2m")
+            plan.sample_restore_multistep_nhwc(x, ys[n], mks[n] if n == 1 else None, n, sp, K - 1, stream_id=0, timesteps=use)
         elif kind.startswith("masked"):                  # "masked<n>" ancestral, "maskedddim<n>" DDIM eta 0
             ddim = kind.startswith("maskedddim")
             n = int(kind[len("maskedddim" if ddim else "masked"):])
@@ -109,6 +118,8 @@ def main():
         return restore_ab(chain, plan)
     if args.restore_masked:
         return restore_masked_ab(chain, plan, decode)
+    if args.restore_solver:
+        return restore_solver_ab(chain, plan, decode)
 
     res = {"shape": f"cfg4 unet_chan 128, {C}x{S}x{S} latents, B={B}, T={T}, DDIM eta 0", "reps": REPS, "per_K": {}}
     with torch.no_grad():
@@ -221,6 +232,34 @@ def restore_masked_ab(chain, plan, decode):
         res["ddim100_inpaint"] = {"chain_ms": round(ms, 3), "chain_min_max_ms": [round(min(runs), 3), round(max(runs), 3)],
                                   "decode_ms": round(decode_ms, 3), "unet_forwards": K,
                                   "images_per_sec": round(B / ((ms + decode_ms) / 1e3), 2)}
+    print(json.dumps(res), flush=True)
+
+
+def restore_solver_ab(chain, plan, decode):
+    K = 20
+    res = {"shape": f"cfg4 unet_chan 128, {C}x{S}x{S} latents, B={B}, T={T}, logsnr{K}, DDNM on DPM-Solver++(2M) step vs plain 2M step; "
+                    "n = 1: center mask, n = 2: no mask", "reps": REPS, "per_n": {}}
+    with torch.no_grad():
+        t_settle = time.perf_counter()
+        while time.perf_counter() - t_settle < 2.0:
+            chain("plain", 96)
+        decode_ms = min(decode() for _ in range(3))
+        for n in (1, 2):
+            tail = "fused" if plan.restore_multistep_tail_parts(B, S, S, n) > 0 else "unfused"
+            chain("2m", K)                               # captures both chains' graphs outside the timed calls
+            chain(f"rsolver{n}", K)
+            ms, rs = [], []
+            for _ in range(REPS):
+                ms.append(chain("2m", K) / K)
+                rs.append(chain(f"rsolver{n}", K) / K)
+            m, r = statistics.median(ms), statistics.median(rs)
+            res["per_n"][f"{n}_{tail}"] = {"dpm2m_ms_per_step": round(m, 4), "restore_solver_ms_per_step": round(r, 4),
+                                           "restore_solver_over_dpm2m": round(r / m, 4),
+                                           "dpm2m_min_max_ms": [round(min(ms), 4), round(max(ms), 4)],
+                                           "restore_solver_min_max_ms": [round(min(rs), 4), round(max(rs), 4)],
+                                           "unet_forwards": K, "images_per_sec": round(B / ((K * r + decode_ms) / 1e3), 2),
+                                           "dpm2m_images_per_sec": round(B / ((K * m + decode_ms) / 1e3), 2)}
+        res["decode_ms"] = round(decode_ms, 3)
     print(json.dumps(res), flush=True)
 
 
