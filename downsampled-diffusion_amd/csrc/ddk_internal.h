@@ -311,6 +311,10 @@ struct InpaintOps {
     const float *ka, *kb;         // per row: x_kn = ka x0 + kb z2 (sqrt(abar_{tau-1}), sqrt(1 - abar_{tau-1}))
     const float *ja, *jb;         // per row: the forward jump after the op, x = ja x + jb z3 (jb == 0: no jump)
 };
+// DDNM+ for a noisy measurement, per row t[b]: the correction's scale and the draw's scale on measured elements
+struct NoisyTables {
+    const float *lam, *sgm;
+};
 constexpr uint32_t INPAINT_Z2_BIT = 0x40000000u;   // Philox stream of the known region's draw: stream_id | this
 constexpr uint32_t INPAINT_Z3_BIT = 0x20000000u;   // ... and of the jump's: stream_id | this (so stream_id < 2^29)
 // zero-shot super-resolution (DDNM for A = n x n average pooling): the low-resolution image and the block
@@ -318,8 +322,8 @@ struct RestoreOps {
     const float* y;               // NHWC [B][H/n][W/n][n_out]: what the n x n block means of x0 are set to
     int n;                        // 2, 4 or 8, dividing H and W
     int H, W;                     // the map the blocks lie in (filled by the chain entry / the lone op; the other kinds need only `per`)
-    const float* mask;            // StepKind::RestoreMasked, RestoreMultistep: [B][H/n][W/n], nonzero = measured, shared by the channels; n may be 1
-                                  // (RestoreMultistep at n >= 2: may be null, every block measured)
+    const float* mask;            // StepKind::RestoreMasked, RestoreMultistep, RestoreNoisy: [B][H/n][W/n], nonzero = measured, shared by the channels; n may be 1
+                                  // (RestoreMultistep, RestoreNoisy at n >= 2: may be null, every block measured)
 };
 // likelihood sweep (ddk_vlb_sweep_run): one step's operands besides the UNet's
 struct VlbStep {
@@ -345,8 +349,11 @@ enum class StepKind {
     RestoreMasked,  // DDNM for A = mask o pool_n, n in {1, 2, 4, 8}: Restore's step where the block's rst.mask is nonzero,
                   // Ancestral's where it is zero (a select; n = 1: x0' = y, no arithmetic): c_recip .. sigma, rst with mask; Philox only
     Vlb,          // likelihood sweep: no update, the step's VLB terms to vlb->partials (vlb_rule() fills the rest from *vlb)
-    RestoreMultistep  // DDNM on the DPM-Solver++(2M) chain, n in {1, 2, 4, 8}: RestoreMasked's x0' (rst.mask null at n >= 2:
+    RestoreMultistep,  // DDNM on the DPM-Solver++(2M) chain, n in {1, 2, 4, 8}: RestoreMasked's x0' (rst.mask null at n >= 2:
                   // every block measured), then Multistep's update on it, x0_hist <- x0': c_recip .. c2, c3, x0_hist, rst; no draw
+    RestoreNoisy  // DDNM+ for a measurement with noise of standard deviation sigma_y, n in {1, 2, 4, 8}: RestoreMasked's
+                  // step with the correction scaled by lam and the draw of measured elements by sgm instead of sigma (rst.mask null at
+                  // n >= 2: every block measured): c_recip .. sigma, lam, sgm, rst; Philox only
                   // (last, so that the kinds above keep their values and their kernels' names)
 };
 struct StepRule {
@@ -359,7 +366,12 @@ struct StepRule {
     const float *c_recip, *c_recipm1, *c1, *c2, *sigma;     // per row t[b]
     float* x0_hist;               // Multistep: the previous step's clipped x0 (RestoreMultistep: its x0'), same layout as x, read and rewritten
     const float* c3;
-    InpaintOps inp;
+    // A rule has one kind, so the Inpaint kind's operands and the RestoreNoisy kind's tables share their storage: the unfused kernels
+    // take a StepRule by value, and a larger one would move every argument behind it and with that the instructions of the older kernels.
+    union {
+        InpaintOps inp;
+        NoisyTables nsy;
+    };
     const VlbStep* vlb;           // host side only
     RestoreOps rst;
 };
@@ -379,7 +391,7 @@ struct ChainHooks {
     uint32_t stream_id;
 };
 // the unfused tail's last kernel, given eps_hat in memory: the rule's update of x (Ancestral, Multistep, Inpaint, Restore, RestoreMasked,
-// RestoreMultistep) or the sweep's
+// RestoreMultistep, RestoreNoisy) or the sweep's
 // reduction of the step's terms (Vlb); `who` names the caller in messages
 int p_update(const StepRule& r, const float* eps_hat, const int64_t* t, int B, long long per, const ChainHooks& h, hipStream_t st,
              const char* who = "p_update");
@@ -403,7 +415,7 @@ struct TailIn {
 // 256 the plain one spills already, and theirs hold more in the prologue).  Restore also needs every 128-pixel tile to hold whole
 // rows of blocks, 128 % (W n) == 0 with W, n = restore_w, restore_n (W = 32: n <= 4; W = 16: n <= 8; W = 64: n = 2); the other
 // kinds ignore the two.  RestoreMasked: as Restore for n >= 2; n = 1 is pointwise and needs no whole blocks, so every shape of the
-// Multistep / Inpaint kinds is taken.  RestoreMultistep: as RestoreMasked.  The one predicate of fused_tail_parts (unet_plan.hip) and
+// Multistep / Inpaint kinds is taken.  RestoreMultistep, RestoreNoisy: as RestoreMasked.  The one predicate of fused_tail_parts (unet_plan.hip) and
 // final_tail.
 bool final_tail_ok(int HW, int C, int groups, int n_out, int np, StepKind kind, int restore_w = 0, int restore_n = 0);
 int final_tail(const TailIn& in, const StepRule& r, const int64_t* t, const ChainHooks& h, hipStream_t st);

@@ -413,6 +413,102 @@ __global__ __launch_bounds__(256) void p_update_restore_ms_point_kernel(const St
     }
 }
 
+// DDNM+ for a noisy measurement (Wang, Yu, Zhang 2023, section 3.3): rst_x0's clipped x0, the DDNM correction of
+// rstm_finish scaled by the row's lam (n = 1: the correction is y - x0, so m = x0), then rst_finish's update with the draw of a measured
+// element scaled by the row's sgm instead of sigma: the noise that enters through y, c1 lam sigma_y, and the draw add up to sigma^2.  mk is
+// the block's (n = 1: the pixel's) mask value, 1 without a mask; both uses of it are selects, so an unmeasured y reaches no result.
+// Restated beside rstm_* / rsm_* so that those kernels keep their instructions.  The arithmetic of both tails.
+__device__ __forceinline__ float rsn_x0p(float x0, float m, float y, float mk, float lam) {
+    return mk != 0.0f ? __fadd_rn(x0, __fmul_rn(lam, __fsub_rn(y, m))) : x0;
+}
+
+__device__ __forceinline__ float rsn_finish(float x, float x0p, float mk, float z, float c1, float c2, float sg, float sgm) {
+    const float mean = __fadd_rn(__fmul_rn(c1, x0p), __fmul_rn(c2, x));
+    return __fadd_rn(mean, __fmul_rn(mk != 0.0f ? sgm : sg, z));
+}
+
+__device__ __forceinline__ float rsn_point(float x, float e, float y, float mk, float z, float cr, float crm1, float c1, float c2, float sg,
+                                           float lam, float sgm) {
+    const float x0 = rst_x0(x, e, cr, crm1);
+    return rsn_finish(x, rsn_x0p(x0, x0, y, mk, lam), mk, z, c1, c2, sg, sgm);
+}
+
+__device__ __forceinline__ float4 rsn_point4(float4 xv, float4 ev, float4 yv, float4 mv, float4 zv, float cr, float crm1, float c1, float c2,
+                                             float sg, float lam, float sgm) {
+    float4 o;
+    o.x = rsn_point(xv.x, ev.x, yv.x, mv.x, zv.x, cr, crm1, c1, c2, sg, lam, sgm);
+    o.y = rsn_point(xv.y, ev.y, yv.y, mv.y, zv.y, cr, crm1, c1, c2, sg, lam, sgm);
+    o.z = rsn_point(xv.z, ev.z, yv.z, mv.z, zv.z, cr, crm1, c1, c2, sg, lam, sgm);
+    o.w = rsn_point(xv.w, ev.w, yv.w, mv.w, zv.w, cr, crm1, c1, c2, sg, lam, sgm);
+    return o;
+}
+
+// The last kernel of an unfused RestoreNoisy step with n >= 2: p_update_restore_kernel's block owner with the row's lam and sgm.
+// r.rst.mask may be null (every block measured).  The draw, the counter and the key as there.
+__global__ __launch_bounds__(256) void p_update_restore_noisy_kernel(const StepRule r, const float* __restrict__ eps_hat,
+                                                                     const int64_t* __restrict__ t, int B, int n_out, uint64_t seed,
+                                                                     uint32_t stream, const int64_t* __restrict__ chain_state,
+                                                                     int64_t* dec_counter) {
+    if (dec_counter && blockIdx.x == 0 && threadIdx.x == 0) *dec_counter -= 1;
+    if (chain_state) {
+        seed = (uint64_t)chain_state[1];
+        stream = (uint32_t)chain_state[2];
+    }
+    const int n = r.rst.n, H = r.rst.H, W = r.rst.W, Hn = H / n, Wn = W / n;
+    const long long total = (long long)B * Hn * Wn * n_out;
+    float* __restrict__ x = r.x;
+    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const int c = (int)(i % n_out);
+        long long q = i / n_out;
+        const int bc = (int)(q % Wn);
+        q /= Wn;
+        const int br = (int)(q % Hn), b = (int)(q / Hn);
+        const int64_t tb = t[b];
+        const float cr = r.c_recip[tb], crm1 = r.c_recipm1[tb], a1 = r.c1[tb], a2 = r.c2[tb], sg = tb > 0 ? r.sigma[tb] : 0.0f;
+        const float lam = r.nsy.lam[tb], sgm = r.nsy.sgm[tb];
+        const long long e0 = (((long long)b * H + br * n) * W + bc * n) * n_out + c;       // the block's first element
+        const float m = rst_block_mean(
+            [&](int bi, int bj) {
+                const long long e = e0 + ((long long)bi * W + bj) * n_out;
+                return rst_x0(x[e], eps_hat[e], cr, crm1);
+            },
+            n);
+        const float yv = r.rst.y[i];                                      // y is [B][H/n][W/n][n_out]: this thread's index
+        const float mk = r.rst.mask ? r.rst.mask[i / n_out] : 1.0f;       // the mask is [B][H/n][W/n]
+        for (int bi = 0; bi < n; ++bi)
+            for (int bj = 0; bj < n; ++bj) {
+                const long long e = e0 + ((long long)bi * W + bj) * n_out;
+                const float xv = x[e];
+                const float z = comp4(philox_normal4((unsigned long long)(e >> 2), (uint32_t)tb, stream, seed), (int)(e & 3));
+                x[e] = rsn_finish(xv, rsn_x0p(rst_x0(xv, eps_hat[e], cr, crm1), m, yv, mk, lam), mk, z, a1, a2, sg, sgm);
+            }
+    }
+}
+
+// ... and with n = 1: p_update_restore_point_kernel's flat float4 loop with the row's lam and sgm (the mask is required)
+__global__ __launch_bounds__(256) void p_update_restore_noisy_point_kernel(const StepRule r, const float* __restrict__ eps_hat,
+                                                                           const int64_t* __restrict__ t, long long per4, long long total4,
+                                                                           int n_out, uint64_t seed, uint32_t stream,
+                                                                           const int64_t* __restrict__ chain_state, int64_t* dec_counter) {
+    if (dec_counter && blockIdx.x == 0 && threadIdx.x == 0) *dec_counter -= 1;
+    if (chain_state) {
+        seed = (uint64_t)chain_state[1];
+        stream = (uint32_t)chain_state[2];
+    }
+    float4* __restrict__ x = reinterpret_cast<float4*>(r.x);
+    const long long hw = (long long)r.rst.H * r.rst.W;
+    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total4; i += (long long)gridDim.x * 256) {
+        const long long b = i / per4;
+        const int64_t tb = t[b];
+        const float cr = r.c_recip[tb], crm1 = r.c_recipm1[tb], a1 = r.c1[tb], a2 = r.c2[tb], sg = tb > 0 ? r.sigma[tb] : 0.0f;
+        const float lam = r.nsy.lam[tb], sgm = r.nsy.sgm[tb];
+        const float4 xv = x[i], ev = reinterpret_cast<const float4*>(eps_hat)[i], yv = reinterpret_cast<const float4*>(r.rst.y)[i];
+        const float4 mv = rstm_mask4(r.rst.mask + b * hw, (unsigned)(i - b * per4) * 4u, (unsigned)n_out);      // host: per < 2^31
+        const float4 zv = philox_normal4((unsigned long long)i, (uint32_t)tb, stream, seed);
+        x[i] = rsn_point4(xv, ev, yv, mv, zv, cr, crm1, a1, a2, sg, lam, sgm);
+    }
+}
+
 // ---- the VLB term of one element (reference models/diffusion/ddpm.py:317-366, models/utils/losses.py:17-109) --------------------
 // Shared by vlb_terms_kernel and the likelihood sweep's epilogues (final_tail_kernel<.., StepKind::Vlb>, vlb_sweep_terms_kernel).
 __device__ __forceinline__ float std_normal_cdf_approx(float v) {
@@ -490,8 +586,13 @@ struct TailParams {
     // StepKind::Multistep: the previous step's clipped x0, same layout as x, read and rewritten
     float* x0_hist;
     const float* c3;
-    // StepKind::Inpaint: the known latent, its mask and the per-row tables
-    InpaintOps inp;
+    // StepKind::Inpaint: the known latent, its mask and the per-row tables; StepKind::RestoreNoisy: the per-row scale of the correction and
+    // of the draw on measured elements, in the same storage (as in StepRule: the struct keeps its size, and the older kernels the offsets
+    // of what follows their arguments)
+    union {
+        InpaintOps inp;
+        NoisyTables nsy;
+    };
     // StepKind::Restore / RestoreMasked: the low-resolution image, the block, the map's height and width and (RestoreMasked) the mask
     RestoreOps rst;
 };
@@ -515,11 +616,13 @@ struct TailParams {
 // RestoreMultistep (ddk_sampler_run_restore_multistep, x given, no draw): RestoreMasked's requests and phase 2 with the history float4
 // requested where Multistep requests it; the owner writes x0' back to the history (n >= 2: after the block means are formed from LDS).
 // rst.mask may be null at n >= 2 (every block measured).
+// RestoreNoisy (ddk_sampler_run_restore_noisy, x given, Philox only): RestoreMultistep's requests of y and the optional mask (RestoreMasked's
+// places), the row's lam and sgm loaded with its other coefficients, and RestoreMasked's phase 2 with rsn_x0p / rsn_finish (n = 1: rsn_point4).
 template <int LPP, int VPL, StepKind K>
 __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
     static_assert(K != StepKind::Eps, "the plain forward runs the Ancestral instantiation with p.x null");
     constexpr bool VLB = K == StepKind::Vlb, MS = K == StepKind::Multistep, INP = K == StepKind::Inpaint, RST = K == StepKind::Restore,
-                   RSTM = K == StepKind::RestoreMasked, RSMS = K == StepKind::RestoreMultistep;
+                   RSTM = K == StepKind::RestoreMasked, RSMS = K == StepKind::RestoreMultistep, RSN = K == StepKind::RestoreNoisy;
     constexpr int PPW = 64 / LPP;                    // pixels per wave and iteration
     constexpr int PPI = 16 * PPW;                    // ... per iteration of the 16-wave workgroup
     constexpr int NIT = 128 / PPI;                   // 4 at C = 128 / 256, 2 at C = 64, 1 at C = 32
@@ -560,6 +663,7 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
     const long long e4 = pix0 * p.n_out / 4;          // host: (128 * n_out) % 4 == 0
     float4 xv0 = make_float4(0.f, 0.f, 0.f, 0.f), zv0 = xv0;
     float cr = 0.f, crm1 = 0.f, a1 = 0.f, a2 = 0.f, sg = 0.f, a3 = 0.f;
+    float lam = 0.f, sgm = 0.f;                       // RSN
     int64_t tb = 0;
     float4 xt0 = xv0;
     float4 xk0 = xv0, mk0 = xv0, z30 = xv0;           // INP: x_kn, the mask, the jump's draw
@@ -578,6 +682,7 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
             cr = p.c_recip[tb]; crm1 = p.c_recipm1[tb]; a1 = p.c1[tb]; a2 = p.c2[tb];
             if constexpr (MS || RSMS) a3 = p.c3[tb];
             else sg = tb > 0 ? p.sigma[tb] : 0.0f;
+            if constexpr (RSN) { lam = p.nsy.lam[tb]; sgm = p.nsy.sgm[tb]; }
         }
         const long long i = e4 + tid;
         xv0 = reinterpret_cast<const float4*>(p.x)[i];
@@ -612,7 +717,7 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
                 }
             }
         }
-        if constexpr (RSMS) {                          // RSTM's requests; no mask: every block is measured
+        if constexpr (RSMS || RSN) {                   // RSTM's requests; no mask: every block is measured
             if (p.rst.n == 1) {
                 const float4 yv = reinterpret_cast<const float4*>(p.rst.y)[i];
                 const float4 mv = rstm_mask4(p.rst.mask + pix0, (unsigned)tid * 4u, (unsigned)p.n_out);
@@ -735,7 +840,19 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
             return;
         }
     }
-    if constexpr (RST || RSTM || RSMS) {
+    if constexpr (RSN) {
+        if (p.rst.n == 1) {
+            if (tid < cnt4) {
+                const float4 ev = reinterpret_cast<const float4*>(es)[tid];
+                if (p.eps_out) reinterpret_cast<float4*>(p.eps_out)[e4 + tid] = ev;
+                reinterpret_cast<float4*>(p.x)[e4 + tid] =
+                    rsn_point4(xv0, ev, make_float4(yv0[0], yv0[1], yv0[2], yv0[3]), make_float4(mv0[0], mv0[1], mv0[2], mv0[3]), zv0, cr, crm1,
+                               a1, a2, sg, lam, sgm);
+            }
+            return;
+        }
+    }
+    if constexpr (RST || RSTM || RSMS || RSN) {
         float x0v[4] = {0.f, 0.f, 0.f, 0.f};
         if (tid < cnt4) {
             const float4 ev = reinterpret_cast<const float4*>(es)[tid];
@@ -755,7 +872,8 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
                 const int lp = (tid * 4 + j) / p.n_out, c = tid * 4 + j - lp * p.n_out, row = lp / W, col = lp - row * W;
                 const float* blk = es + ((row & ~(n - 1)) * W + (col & ~(n - 1))) * p.n_out + c;
                 const float m = rst_block_mean([&](int bi, int bj) { return blk[(bi * W + bj) * p.n_out]; }, n);
-                if constexpr (RSMS) o[j] = rsm_finish(xa[j], rsm_x0p(x0v[j], m, yv0[j], mv0[j]), za[j], a1, a2, a3);
+                if constexpr (RSN) o[j] = rsn_finish(xa[j], rsn_x0p(x0v[j], m, yv0[j], mv0[j], lam), mv0[j], za[j], a1, a2, sg, sgm);
+                else if constexpr (RSMS) o[j] = rsm_finish(xa[j], rsm_x0p(x0v[j], m, yv0[j], mv0[j]), za[j], a1, a2, a3);
                 else if constexpr (RSTM) o[j] = rstm_finish(xa[j], x0v[j], m, yv0[j], mv0[j], za[j], a1, a2, sg);
                 else o[j] = rst_finish(xa[j], x0v[j], m, yv0[j], za[j], a1, a2, sg);
             }
@@ -806,7 +924,8 @@ bool final_tail_ok(int HW, int C, int groups, int n_out, int np, StepKind kind, 
     if (n_out < 1 || n_out > 8 || (128 * n_out) % 4) return false;
     // the restore tail forms block means from the tile's x0 in LDS: the 128-pixel tile must hold whole rows of n x n blocks
     // (the masked kind the same for n >= 2; its n = 1 is pointwise)
-    const bool blocks = kind == StepKind::Restore || ((kind == StepKind::RestoreMasked || kind == StepKind::RestoreMultistep) && restore_n != 1);
+    const bool blocks = kind == StepKind::Restore ||
+                        ((kind == StepKind::RestoreMasked || kind == StepKind::RestoreMultistep || kind == StepKind::RestoreNoisy) && restore_n != 1);
     if (blocks && !(restore_w > 0 && restore_n > 0 && 128 % (restore_w * restore_n) == 0)) return false;
     return np > 0 && HW == np * 128 && np * groups <= 1024;
 }
@@ -862,6 +981,13 @@ int final_tail(const TailIn& in, const StepRule& r, const int64_t* t, const Chai
                         "n = 1, n in {1,2,4,8} dividing H and W, H*W of the map and no injected noise");
             p.rst = r.rst; p.x0_hist = r.x0_hist; p.c3 = r.c3;
             return launch_tail<StepKind::RestoreMultistep>(p, in.B, st);
+        case StepKind::RestoreNoisy:
+            DDK_REQUIRE(tables && r.sigma && r.nsy.lam && r.nsy.sgm && !r.noise && r.rst.y && (r.rst.mask || r.rst.n != 1) && restore_block_ok(r.rst, true) &&
+                            (long long)r.rst.H * r.rst.W == in.HW && (r.rst.n != 1 || aligned16(r.rst.y)),
+                        "final_tail: the noisy restore step needs x, t, the tables with lam and sgm, y (aligned at n = 1), a mask at n = 1, "
+                        "n in {1,2,4,8} dividing H and W, H*W of the map and no injected noise");
+            p.rst = r.rst; p.nsy = r.nsy;
+            return launch_tail<StepKind::RestoreNoisy>(p, in.B, st);
         case StepKind::Vlb: {
             DDK_REQUIRE(r.vlb && tables && !r.eps_out && h.chain_state, "final_tail: the VLB epilogue needs the sweep's step, x, t, the tables and the chain state");
             const VlbStep& v = *r.vlb;
@@ -1130,6 +1256,24 @@ int p_update(const StepRule& r, const float* eps_hat, const int64_t* t, int B, l
                                h.dec_counter);
             return check_launch("p_update_restore_ms_kernel");
         }
+        case StepKind::RestoreNoisy: {  // RestoreMasked's two kernels with lam and sgm; the mask is optional at n >= 2
+            if (!(r.sigma && r.nsy.lam && r.nsy.sgm && r.rst.y)) return bad("null pointer");
+            if (r.noise) return bad("no injected noise (Philox only)");
+            if (!restore_block_ok(r.rst, true)) return bad("n must be 1, 2, 4 or 8 and divide H and W");
+            if (r.rst.n == 1 && !r.rst.mask) return bad("n = 1 needs a mask (nothing would be constrained)");
+            const long long hw = (long long)r.rst.H * r.rst.W;
+            if (per % hw || per / hw > INT_MAX || per > INT_MAX) return bad("per must be H * W * channels, below 2^31");
+            const int n_out = (int)(per / hw);
+            if (r.rst.n == 1) {
+                if (!aligned16(r.rst.y)) return bad("alignment");
+                hipLaunchKernelGGL(p_update_restore_noisy_point_kernel, grid, dim3(256), 0, st, r, eps_hat, t, per / 4, total4, n_out, h.seed,
+                                   h.stream_id, h.chain_state, h.dec_counter);
+                return check_launch("p_update_restore_noisy_point_kernel");
+            }
+            hipLaunchKernelGGL(p_update_restore_noisy_kernel, dim3(grid1d(B * per / (r.rst.n * r.rst.n))), dim3(256), 0, st, r, eps_hat, t, B,
+                               n_out, h.seed, h.stream_id, h.chain_state, h.dec_counter);
+            return check_launch("p_update_restore_noisy_kernel");
+        }
         case StepKind::Vlb:       // no update: the sweep's reduction of the step's terms, a kernel of its own
             if (!r.vlb) return bad("null pointer");
             return vlb_sweep_terms(*r.vlb, t, eps_hat, B, per, h.chain_state, st, h.dec_counter);
@@ -1205,7 +1349,7 @@ int ddk_p_sample_update_inpaint(float* x, const float* eps_hat, const float* kno
                                 const float* ka, const float* kb, const float* ja, const float* jb, int B, long long per, uint64_t seed,
                                 uint32_t stream_id, ddk_stream_t s) {
     const StepRule r{StepKind::Inpaint, nullptr, x, nullptr, 0, 0, c_recip, c_recipm1, c1, c2, sigma, nullptr, nullptr,
-                     InpaintOps{known, mask, ka, kb, ja, jb}};
+                     {InpaintOps{known, mask, ka, kb, ja, jb}}};
     return p_update(r, eps_hat, t, B, per, ChainHooks{nullptr, nullptr, seed, stream_id}, as_stream(s), "p_sample_update_inpaint");
 }
 
@@ -1239,6 +1383,19 @@ int ddk_p_sample_update_restore_multistep(float* x, const float* eps_hat, float*
     StepRule r{StepKind::RestoreMultistep, nullptr, x, nullptr, 0, 0, c_recip, c_recipm1, c1, c2, nullptr, x0_hist, c3};
     r.rst = RestoreOps{y, n, H, W, mask};
     return p_update(r, eps_hat, t, B, (long long)H * W * channels, ChainHooks{}, as_stream(s), "p_sample_update_restore_multistep");
+}
+
+int ddk_p_sample_update_restore_noisy(float* x, const float* eps_hat, const float* y, const float* mask, int n, const int64_t* t,
+                                      const float* c_recip, const float* c_recipm1, const float* c1, const float* c2, const float* sigma,
+                                      const float* lam, const float* sgm, int B, int H, int W, int channels, uint64_t seed, uint32_t stream_id,
+                                      ddk_stream_t s) {
+    DDK_REQUIRE(B > 0 && H > 0 && W > 0 && channels > 0, "p_sample_update_restore_noisy: B / H / W / channels must be positive");
+    DDK_REQUIRE(mask || n != 1, "p_sample_update_restore_noisy: n = 1 needs a mask (nothing would be constrained)");
+    StepRule r{StepKind::RestoreNoisy, nullptr, x, nullptr, 0, 0, c_recip, c_recipm1, c1, c2, sigma};
+    r.rst = RestoreOps{y, n, H, W, mask};
+    r.nsy = NoisyTables{lam, sgm};
+    return p_update(r, eps_hat, t, B, (long long)H * W * channels, ChainHooks{nullptr, nullptr, seed, stream_id}, as_stream(s),
+                    "p_sample_update_restore_noisy");
 }
 
 int ddk_final_tail(const float* raw, const float* partials, int tiles_per_image, const float* gamma, const float* beta, float eps,

@@ -84,16 +84,16 @@ using namespace ddk;
 // same graph serves every step of every chain on those buffers.
 struct ChainKey {
     StepKind kind;                           // how the chain's steps end: one kind per chain entry
-    const void* bufs[12];                    // every buffer the step's kernels are launched with (unused entries null)
+    const void* bufs[14];                    // every buffer the step's kernels are launched with (unused entries null)
     const void* ws;
     const void* noise;                       // also in bufs; injected draws: no 16-step graph (see run_chain)
     int B, H, W, t_start, device;
     unsigned long long pack_epoch;
     int restore_n = 0;                       // StepKind::Restore, RestoreMasked: the block (y and the mask are staged in the workspace; the kind
                                              // says whether a mask is present, so a masked and an unmasked chain never share a graph)
-    bool restore_mask = false;               // StepKind::RestoreMultistep, one kind with or without a mask: whether its kernels were given one
+    bool restore_mask = false;               // StepKind::RestoreMultistep, RestoreNoisy, one kind with or without a mask: whether its kernels were given one
     bool operator==(const ChainKey& o) const {
-        for (int i = 0; i < 12; ++i)
+        for (int i = 0; i < 14; ++i)
             if (bufs[i] != o.bufs[i]) return false;
         return kind == o.kind && ws == o.ws && noise == o.noise && B == o.B && H == o.H && W == o.W && t_start == o.t_start &&
                device == o.device && pack_epoch == o.pack_epoch && restore_n == o.restore_n && restore_mask == o.restore_mask;
@@ -1128,12 +1128,15 @@ struct StepArgs {
 };
 
 // tiles of the final tail when the end of the forward runs as ONE launch (final_tail_kernel), else 0.  cin = the final conv's
-// input channels (dimp[1]).  The Vlb, Multistep, Inpaint, Restore, RestoreMasked and RestoreMultistep kinds take a subset of the shapes
-// (final_tail_ok; the last three's depends on its block, restore_n).
+// input channels (dimp[1]).  The Vlb, Multistep, Inpaint, Restore, RestoreMasked, RestoreMultistep and RestoreNoisy kinds take a subset of
+// the shapes (final_tail_ok; the last four's depends on its block, restore_n).
+static bool restore_kind(StepKind k) {       // the kinds whose step carries a DDNM constraint (RestoreOps)
+    return k == StepKind::Restore || k == StepKind::RestoreMasked || k == StepKind::RestoreMultistep || k == StepKind::RestoreNoisy;
+}
 static int fused_tail_parts(const ddk_unet& u, int B, int H, int W, int cin, StepKind kind, int restore_n = 0) {
     const int chan = u.generic ? pad32(u.cfg.chan) : u.cfg.chan, n_out = u.cfg.in_ch;
     const int npf = u.final_conv.has_wu ? conv_wino_stats_parts(B, H, W, cin, chan, GROUPS) : 0;
-    if (npf <= 0 || ((kind == StepKind::Restore || kind == StepKind::RestoreMasked || kind == StepKind::RestoreMultistep) && !u.restore_fused)) return 0;
+    if (npf <= 0 || (restore_kind(kind) && !u.restore_fused)) return 0;
     return final_tail_ok(H * W, chan, GROUPS, n_out, npf, kind, W, restore_n) ? npf : 0;
 }
 
@@ -1338,8 +1341,8 @@ static int forward_core(const ddk_unet& u, const float* P, const float* x, int64
     const int npf = fused_tail_parts(u, B, H, W, cur_c, rule.kind, rule.rst.n);
     // a Restore step whose blocks do not fit the tail's tile (or with its fused tail switched off) still ends the forward in the plain
     // tail's one launch, eps_hat to the step's scratch, and updates x behind it: the same eps_hat, bit for bit, as its fused tail sees
-    // (the masked kind and the restore multistep kind likewise)
-    const int npe = (npf == 0 && step && (rule.kind == StepKind::Restore || rule.kind == StepKind::RestoreMasked || rule.kind == StepKind::RestoreMultistep)) ? fused_tail_parts(u, B, H, W, cur_c, StepKind::Eps) : 0;
+    // (the masked, the restore multistep and the noisy kind likewise)
+    const int npe = (npf == 0 && step && restore_kind(rule.kind)) ? fused_tail_parts(u, B, H, W, cur_c, StepKind::Eps) : 0;
     if ((npf > 0 || npe > 0) && (!step || step->per == (long long)H * W * n_out)) {
         // one-pass Winograd conv with statistics, then GroupNorm + Mish + projection (+ the rule) in ONE launch
         DDK_TRY(run_conv_parts(c, u.final_conv, cur, cur_c, nullptr, 0, raw, H, W, chan));
@@ -1730,7 +1733,7 @@ namespace ddk {
 // call without a mask is (n = 1: a whole latent plus B H W; n = 2: a quarter of each; n = 4, 8: the Restore kind's quarter latent).
 static size_t chain_extra_floats(const ddk_unet& u, int B, int H, int W, StepKind kind, int restore_n = 0) {
     const size_t n = al4((size_t)B * H * W * u.cfg.in_ch);
-    if (kind == StepKind::RestoreMasked) {
+    if (kind == StepKind::RestoreMasked || kind == StepKind::RestoreNoisy) {      // the noisy kind keeps RestoreMasked's layout and size
         const size_t nn = (size_t)restore_n * restore_n, m = al4(n / nn) + al4((size_t)B * H * W / nn);
         return restore_n > 1 && m < al4(n / 4) ? al4(n / 4) : m;
     }
@@ -1754,6 +1757,7 @@ static size_t sampler_bytes(const ddk_unet* u, int B, int H, int W, int t_start,
 //   Restore:   y, copied in before the first step
 //   RestoreMasked: y and, behind it, the mask, copied in before the first step
 //   RestoreMultistep: the history, zeroed by every call as Multistep's, then y and (when given) the mask, copied in as RestoreMasked's
+//   RestoreNoisy: y and (when given) the mask, where RestoreMasked keeps them
 // The graph key: the kind, every table the step reads and the restore block; the staged operands live in the workspace, which is
 // in the key.
 static int sampler_chain(const ddk_sampler_args* a, const char* who, const int64_t* map, StepRule rule, ddk_stream_t s) {
@@ -1784,6 +1788,15 @@ static int sampler_chain(const ddk_sampler_args* a, const char* who, const int64
         DDK_HIP(hipMemcpyAsync(extra + al4(ny), rule.rst.mask, nm * sizeof(float), hipMemcpyDeviceToDevice, c.st));
         rule.rst.y = extra;
         rule.rst.mask = extra + al4(ny);
+    } else if (rule.kind == StepKind::RestoreNoisy) {
+        const size_t nn = (size_t)rule.rst.n * rule.rst.n, ny = n / nn, nm = (size_t)B * H * W / nn;
+        rule.rst.H = H; rule.rst.W = W;
+        DDK_HIP(hipMemcpyAsync(extra, rule.rst.y, ny * sizeof(float), hipMemcpyDeviceToDevice, c.st));
+        if (rule.rst.mask) {
+            DDK_HIP(hipMemcpyAsync(extra + al4(ny), rule.rst.mask, nm * sizeof(float), hipMemcpyDeviceToDevice, c.st));
+            rule.rst.mask = extra + al4(ny);
+        }
+        rule.rst.y = extra;
     } else if (rule.kind == StepKind::RestoreMultistep) {
         const size_t nn = (size_t)rule.rst.n * rule.rst.n, ny = n / nn, nm = (size_t)B * H * W / nn;
         float* ystage = extra + al4(n);
@@ -1802,12 +1815,15 @@ static int sampler_chain(const ddk_sampler_args* a, const char* who, const int64
     // one reverse step: bookkeeping (in the forward's first kernel), UNet, the rule (in its last kernel)
     auto one_step = [&]() -> int { return c.forward(a->x, &step); };
 
+    // the RestoreNoisy tables share the Inpaint operands' storage (StepRule): each kind's key names its own
+    const bool noisy = rule.kind == StepKind::RestoreNoisy;
+    const InpaintOps ik = noisy ? InpaintOps{} : rule.inp;
+    const NoisyTables nk = noisy ? rule.nsy : NoisyTables{};
     const ChainKey key{rule.kind,
-                       {a->packed, a->x, rule.c_recip, rule.c_recipm1, rule.c1, rule.c2, rule.sigma, rule.c3, rule.inp.ka, rule.inp.kb,
-                        rule.inp.ja, rule.inp.jb},
-                       a->workspace, a->noise, B, H, W, a->t_start, c.dev, c.u->pack_epoch,
-                       rule.kind == StepKind::Restore || rule.kind == StepKind::RestoreMasked || rule.kind == StepKind::RestoreMultistep ? rule.rst.n : 0,
-                       rule.kind == StepKind::RestoreMultistep && rule.rst.mask != nullptr};
+                       {a->packed, a->x, rule.c_recip, rule.c_recipm1, rule.c1, rule.c2, rule.sigma, rule.c3, ik.ka, ik.kb, ik.ja, ik.jb, nk.lam,
+                        nk.sgm},
+                       a->workspace, a->noise, B, H, W, a->t_start, c.dev, c.u->pack_epoch, restore_kind(rule.kind) ? rule.rst.n : 0,
+                       (rule.kind == StepKind::RestoreMultistep || rule.kind == StepKind::RestoreNoisy) && rule.rst.mask != nullptr};
     return run_chain(*c.u, key, n_steps, a->use_graph != 0, one_step, c.st, who);
 }
 }  // namespace ddk
@@ -1974,6 +1990,37 @@ extern "C" int ddk_sampler_run_restore_multistep(const ddk_sampler_args* a, cons
     rule.c3 = c3;
     rule.rst = RestoreOps{y, n, a->H, a->W, mask};
     return sampler_chain(a, "sampler_restore_multistep", timestep_map, rule, s);
+}
+
+// ------------------------------------------------------------------------------------------------ restoration of a noisy measurement
+// DDNM+: ddk_sampler_run_restore_masked's chain, tables and workspace layout, every step ending in
+// StepKind::RestoreNoisy with the per-row tables lam and sgm.  One kind with or without a mask; the graph key carries the kind, lam and
+// sgm (among its buffers), n and whether a mask was given.
+extern "C" size_t ddk_sampler_restore_noisy_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start, int n) {
+    if (!(n == 1 || n == 2 || n == 4 || n == 8)) return 0;
+    return sampler_bytes(u, B, H, W, t_start, StepKind::RestoreNoisy, n);
+}
+
+extern "C" int ddk_sampler_restore_noisy_tail_parts(const ddk_unet* u, int B, int H, int W, int n) {
+    if (check_shape(u, B, H, W) != DDK_OK || !(n == 1 || n == 2 || n == 4 || n == 8)) return -1;
+    return fused_tail_parts(*u, B, H, W, u->dimp[1], StepKind::RestoreNoisy, n);
+}
+
+extern "C" int ddk_sampler_run_restore_noisy(const ddk_sampler_args* a, const int64_t* timestep_map, const float* lam, const float* sgm,
+                                             const float* y, const float* mask, int n, ddk_stream_t s) {
+    DDK_REQUIRE(a && a->unet && a->packed && a->x && a->workspace && y, "sampler_restore_noisy: null pointer");
+    DDK_REQUIRE(a->c_recip && a->c_recipm1 && a->c1 && a->c2 && a->sigma && lam && sgm, "sampler_restore_noisy: null schedule table");
+    DDK_REQUIRE(!a->noise, "sampler_restore_noisy: injected noise is not supported, noise must be NULL (Philox only)");
+    DDK_REQUIRE(a->t_start >= a->t_end && a->t_end >= 0, "sampler_restore_noisy: need t_start >= t_end >= 0");
+    DDK_REQUIRE((n == 1 || n == 2 || n == 4 || n == 8) && a->H > 0 && a->W > 0 && a->H % n == 0 && a->W % n == 0,
+                "sampler_restore_noisy: n must be 1, 2, 4 or 8 and divide H and W");
+    DDK_REQUIRE(mask || n != 1, "sampler_restore_noisy: n = 1 needs a mask (nothing would be constrained)");
+    DDK_TRY(check_timestep_map(timestep_map, a->t_start, "sampler_restore_noisy"));
+    StepRule rule{};
+    rule.kind = StepKind::RestoreNoisy;
+    rule.nsy = NoisyTables{lam, sgm};
+    rule.rst = RestoreOps{y, n, a->H, a->W, mask};
+    return sampler_chain(a, "sampler_restore_noisy", timestep_map, rule, s);
 }
 
 // ------------------------------------------------------------------------------------------------ likelihood sweep

@@ -819,6 +819,24 @@ def p_sample_update_restore_multistep_(x, eps_hat, x0_hist, y, mask, n, t, c_rec
     return x
 
 
+def p_sample_update_restore_noisy_(x, eps_hat, y, mask, n, t, c_recip, c_recipm1, c1, c2, sigma, lam, sgm, seed=0, stream_id=0):
+    """In-place DDNM+ step for a noisy measurement of x [B,H,W,C] (NHWC) per sample row t[b]:
+    p_sample_update_restore_masked_'s step with the correction of a measured block (n = 1: pixel) scaled by lam[t] and its draw by
+    sgm[t] instead of sigma[t]; what is not measured keeps its clipped x0 and the full draw.  n in {1, 2, 4, 8}; mask None (n >= 2
+    only): every block is measured."""
+    b, h, w, c = x.shape
+    n = int(n)
+    if n < 1 or tuple(y.shape) != (b, h // n, w // n, c) or tuple(eps_hat.shape) != tuple(x.shape) or \
+            (mask is not None and tuple(mask.shape) != (b, h // n, w // n)):
+        raise L.DDKError(f"p_sample_update_restore_noisy: x {tuple(x.shape)}, eps_hat {tuple(eps_hat.shape)}, y {tuple(y.shape)}, "
+                         f"mask {None if mask is None else tuple(mask.shape)}, n = {n}")
+    L.check(L.load().ddk_p_sample_update_restore_noisy(L.ptr(_f32(x)), L.ptr(_f32(eps_hat)), L.ptr(_f32(y)),
+                                                       L.ptr(None if mask is None else _f32(mask)), n, L.ptr(t), L.ptr(c_recip),
+                                                       L.ptr(c_recipm1), L.ptr(c1), L.ptr(c2), L.ptr(sigma), L.ptr(lam), L.ptr(sgm), b, h, w, c,
+                                                       seed, stream_id, L.stream()), "p_sample_update_restore_noisy")
+    return x
+
+
 def randn(shape, device, seed, step, stream_id=0):
     out = torch.empty(shape, device=device, dtype=torch.float32)
     L.check(L.load().ddk_randn(L.ptr(out), out.numel(), seed, step, stream_id, L.stream()), "randn")

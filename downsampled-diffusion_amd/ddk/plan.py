@@ -27,7 +27,8 @@ SAMPLERS = {"smp": ("sample", "sampler", "sampler"), "sms": ("sample_multistep",
             "sin": ("sample_inpaint", "sampler_inpaint", "inpainting sampler"),
             "srs": ("sample_restore", "sampler_restore", "super-resolution sampler"),
             "srm": ("sample_restore_masked", "sampler_restore_masked", "masked restoration sampler"),
-            "srx": ("sample_restore_multistep", "sampler_restore_multistep", "restoration solver")}
+            "srx": ("sample_restore_multistep", "sampler_restore_multistep", "restoration solver"),
+            "srn": ("sample_restore_noisy", "sampler_restore_noisy", "noisy restoration sampler")}
 # workspace kinds whose captured step graphs point into them (the samplers', the likelihood sweep's): UnetPlan._workspace keeps up
 # to 3 of each
 CHAIN_WORKSPACES = (*SAMPLERS, "vsw")
@@ -91,8 +92,8 @@ class UnetPlan:
         reconstruct() (t_start = t_rec_max) at every logging event keeps both sets of graphs instead of re-capturing twice per event.
         Only an eviction drops the plan's cached graphs (ddk_sampler_invalidate waits for the device).  The likelihood sweep's
         workspaces ("vsw"), the multistep sampler's ("sms"), the inpainting sampler's ("sin"), the super-resolution sampler's
-        ("srs"), the masked restoration sampler's ("srm") and the restoration solver's ("srx") are kept the same way: their captured
-        steps point into them too."""
+        ("srs"), the masked restoration sampler's ("srm"), the restoration solver's ("srx") and the noisy restoration sampler's ("srn")
+        are kept the same way: their captured steps point into them too."""
         key = (kind, nbytes, str(device))
         hit = self._ws.get(key)
         if hit is not None:
@@ -438,6 +439,42 @@ class UnetPlan:
 
         return self._run_sampler("srx", x, t_start, t_end,
                                  lambda b, h, w: lib.ddk_sampler_restore_multistep_workspace_bytes(self.handle, b, h, w, t_start, int(n)),
+                                 call, use_graph)
+
+    def restore_noisy_tail_parts(self, b, h, w, n):
+        """Tiles per image of the fused tail of a noisy restoration step on [b, h, w] with block n (1 included), or 0."""
+        return int(self._lib.ddk_sampler_restore_noisy_tail_parts(self.handle, b, h, w, int(n)))
+
+    def sample_restore_noisy_nhwc(self, x, y, mask, n, tables, t_start, t_end=0, seed=0, stream_id=0, use_graph=True, timesteps=None):
+        """DDNM+ steps for a noisy measurement of A = mask o (n x n average pooling), t_start .. t_end (inclusive), in place on x
+        [B,H,W,in_ch] (ddk_sampler_run_restore_noisy).
+
+        y, mask, n: as for sample_restore_masked_nhwc (mask None at n >= 2: every block measured); they are copied into the plan's
+        "srn" workspace by every call.  tables: sample_restore_masked_nhwc's plus the per-row "lam" and "sgm" (respace.noisy_tables);
+        they are in the graph key, so chains with different noise levels never replay each other's graph.  Philox only."""
+        self._need_packed("srn")
+        b, h, w, c = x.shape
+        if n not in (1, 2, 4, 8) or h % n or w % n:
+            raise L.DDKError(f"sample_restore_noisy: n must be 1, 2, 4 or 8 and divide H = {h} and W = {w}, got {n}")
+        if mask is None and n == 1:
+            raise L.DDKError("sample_restore_noisy: n = 1 needs a mask (nothing would be constrained)")
+        if tuple(y.shape) != (b, h // n, w // n, c) or y.dtype != torch.float32 or not y.is_contiguous():
+            raise L.DDKError(f"y must be a contiguous fp32 [{b},{h // n},{w // n},{c}] tensor, got {tuple(y.shape)} {y.dtype}")
+        if mask is not None and (tuple(mask.shape) != (b, h // n, w // n) or mask.dtype != torch.float32 or not mask.is_contiguous()):
+            raise L.DDKError(f"mask must be a contiguous fp32 [{b},{h // n},{w // n}] tensor, got {tuple(mask.shape)} {mask.dtype}")
+        for name in ("lam", "sgm"):
+            if tuple(tables[name].shape) != tuple(tables["c1"].shape) or tables[name].dtype != torch.float32:
+                raise L.DDKError(f"tables[{name!r}] must be an fp32 tensor with one entry per row of c1, got {tuple(tables[name].shape)}")
+        lib = self._lib
+        tmap = self._timestep_map(timesteps, t_start)
+
+        def call(x, ws, nbytes, stream_ptr):
+            a = self._sampler_args(x, None, tables, t_start, t_end, seed, stream_id, use_graph, ws, nbytes)
+            L.check(lib.ddk_sampler_run_restore_noisy(C.byref(a), tmap, L.ptr(tables["lam"]), L.ptr(tables["sgm"]), L.ptr(y), L.ptr(mask),
+                                                      int(n), stream_ptr), "sampler_run_restore_noisy")
+
+        return self._run_sampler("srn", x, t_start, t_end,
+                                 lambda b, h, w: lib.ddk_sampler_restore_noisy_workspace_bytes(self.handle, b, h, w, t_start, int(n)),
                                  call, use_graph)
 
     # ---------------------------------------------------------------- likelihood sweep

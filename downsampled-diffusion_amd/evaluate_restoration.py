@@ -17,6 +17,10 @@ through utils/data.py; ``--max_batches`` keeps the first max_batches * batch_siz
     with ``model.restore``; the baselines mean-fill the same holes before they upsample.
   * ``--dpm_solver`` (DDNM only, not with ``--use_ddim`` / ``--eta``): DDNM on the DPM-Solver++(2M) chain (section 3.9,
     ``model.restore_solver``) over the ``--timestep_respacing`` grid (e.g. ``logsnr20``); ``method`` then reads ``ddnm_dpmpp2m``.
+  * ``--sigma_y S`` (DDNM only, not with ``--dpm_solver``): the measurement is noisy (section 3.10).  N(0, S^2) noise, seeded by
+    ``--seed``, is added to the measurement in its [-1, 1] scale after degrading; ``model.restore_noisy`` (DDNM+) restores it, the
+    baselines see the same noisy measurement, ``method`` reads ``ddnm_plus``, the settings gain ``sigma_y``, and the consistency
+    becomes the RMS of pool(x_out) - y_clean over the measured pixels in uint8 levels.  ``--sigma_y 0`` changes nothing.
   * batch g draws x_T and its Philox key from ``--seed`` + g.
 
 Prints one JSON object, the settings that produced it (among them ``method`` and ``unet_forwards``, the UNet forwards per image, so
@@ -49,6 +53,8 @@ def parse_args(argv=None):
     ap.add_argument("--eta", type=float, default=0.0, help="sr: DDIM noise scale (0: deterministic)")
     ap.add_argument("--dpm_solver", action="store_true",
                     help='ddnm: DPM-Solver++(2M) steps over the --timestep_respacing grid (e.g. "logsnr20"); not with --use_ddim / --eta')
+    ap.add_argument("--sigma_y", type=float, default=0.0,
+                    help="ddnm: add N(0, sigma_y^2) noise to the measurement ([-1, 1] scale) and restore with DDNM+; not with --dpm_solver")
     ap.add_argument("--jump_length", type=int, default=10, help="inpaint: RePaint jump length")
     ap.add_argument("--jump_n_sample", type=int, default=10, help="inpaint: RePaint resamplings per jump")
     ap.add_argument("--batch_size", type=int, default=32)
@@ -67,16 +73,22 @@ def parse_args(argv=None):
             ap.error("--scale must be >= 2")
     elif args.mask is None:
         args.mask = "center"
+    if not np.isfinite(args.sigma_y) or args.sigma_y < 0:
+        ap.error("--sigma_y must be a finite number >= 0")
     if args.method == "ddnm":
         if args.dpm_solver and (args.use_ddim or args.eta != 0.0):
             ap.error("--dpm_solver is its own deterministic update: it cannot be combined with --use_ddim or --eta")
+        if args.sigma_y != 0.0 and args.dpm_solver:
+            ap.error("--sigma_y and --dpm_solver are exclusive (the solver draws nothing, so there is no variance to trade)")
+        if args.sigma_y != 0.0 and args.use_ddim and args.eta == 0.0:
+            ap.error("--sigma_y needs a chain that draws: ancestral steps, or --use_ddim with --eta > 0")
         if args.eta < 0 or (args.eta != 0.0 and not args.use_ddim):
             ap.error("--eta needs --use_ddim and a value >= 0")
         if args.jump_length != ap.get_default("jump_length") or args.jump_n_sample != ap.get_default("jump_n_sample"):
             ap.error("--jump_length and --jump_n_sample belong to --method repaint (DDNM has no jumps)")
     else:
-        if args.use_ddim or args.eta != 0.0 or args.dpm_solver:
-            ap.error("--use_ddim, --eta and --dpm_solver belong to DDNM (RePaint runs ancestral steps)")
+        if args.use_ddim or args.eta != 0.0 or args.dpm_solver or args.sigma_y != 0.0:
+            ap.error("--use_ddim, --eta, --dpm_solver and --sigma_y belong to DDNM (RePaint runs ancestral steps)")
         if args.jump_length < 1 or args.jump_n_sample < 1:
             ap.error("--jump_length and --jump_n_sample must be >= 1")
     return args
@@ -93,6 +105,8 @@ def chain_options(args):
         kw.update(ddim=args.use_ddim, eta=args.eta)
     else:
         kw.update(jump_length=args.jump_length, jump_n_sample=args.jump_n_sample)
+    if args.sigma_y != 0.0:
+        kw.update(sigma_y=args.sigma_y)
     return kw
 
 

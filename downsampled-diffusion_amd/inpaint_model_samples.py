@@ -12,10 +12,13 @@ u8 / 255 * 2 - 1 as the training data is), hides the region given by ``--mask`` 
     ``--jump_*`` options must stay at their defaults, and a mask that differs between the channels counts a pixel as known only
     where every channel is; ``--dpm_solver`` (with ``--method ddnm`` only, not with ``--use_ddim`` / ``--eta``) fills with
     ``model.restore_solver``, DDNM on the DPM-Solver++(2M) chain (section 3.9; use a log-SNR grid, e.g. ``logsnr20``);
+  * ``--sigma_y S`` (with ``--method ddnm`` only, not with ``--dpm_solver``) declares that the known pixels of the given images
+    carry noise of standard deviation S in the model's [-1, 1] scale (S = 2 s / 255 for s uint8 levels): the fill is
+    ``model.restore_noisy`` (DDNM+, section 3.10), which never pastes the noisy pixels back, and the names gain ``_sy{S}``;
   * batch g draws x_T and its Philox key from ``--seed`` + g.
 
 Writes ``{saved_model}_inpaint_{mask}_{spec}_j{j}r{r}.npy`` (float32 [N, H, W, C] in [0, 255]; with ``--method ddnm``
-``{saved_model}_inpaint_{mask}_{spec}_ddnm[_ddim_eta{eta}|_dpmpp2m].npy``) and, beside it, the masked inputs for viewing
+``{saved_model}_inpaint_{mask}_{spec}_ddnm[_ddim_eta{eta}|_dpmpp2m][_sy{S}].npy``) and, beside it, the masked inputs for viewing
 (``..._masked.npy``, hidden pixels 0).  One process, one GPU.
 """
 import argparse
@@ -50,6 +53,8 @@ def main():
     ap.add_argument("--eta", type=float, default=0.0, help="ddnm: DDIM noise scale (0: deterministic)")
     ap.add_argument("--dpm_solver", action="store_true",
                     help='ddnm: DPM-Solver++(2M) steps over the --timestep_respacing grid (e.g. "logsnr20"); not with --use_ddim / --eta')
+    ap.add_argument("--sigma_y", type=float, default=0.0,
+                    help="ddnm: the noise level of the known pixels in the [-1, 1] scale (DDNM+); not with --dpm_solver")
     ap.add_argument("--jump_length", type=int, default=10)
     ap.add_argument("--jump_n_sample", type=int, default=10)
     ap.add_argument("--batch_size", type=int, default=32)
@@ -58,15 +63,21 @@ def main():
     args = ap.parse_args()
     if args.jump_length < 1 or args.jump_n_sample < 1 or args.batch_size < 1:
         ap.error("--jump_length, --jump_n_sample and --batch_size must be >= 1")
+    if not np.isfinite(args.sigma_y) or args.sigma_y < 0:
+        ap.error("--sigma_y must be a finite number >= 0")
     if args.method == "ddnm":
         if args.jump_length != ap.get_default("jump_length") or args.jump_n_sample != ap.get_default("jump_n_sample"):
             ap.error("--jump_length and --jump_n_sample belong to --method repaint (DDNM has no jumps)")
+        if args.sigma_y != 0.0 and args.dpm_solver:
+            ap.error("--sigma_y and --dpm_solver are exclusive (the solver draws nothing, so there is no variance to trade)")
+        if args.sigma_y != 0.0 and args.use_ddim and args.eta == 0.0:
+            ap.error("--sigma_y needs a chain that draws: ancestral steps, or --use_ddim with --eta > 0")
         if args.dpm_solver and (args.use_ddim or args.eta != 0.0):
             ap.error("--dpm_solver is its own deterministic update: it cannot be combined with --use_ddim or --eta")
         if args.eta < 0 or (args.eta != 0.0 and not args.use_ddim):
             ap.error("--eta needs --use_ddim and a value >= 0")
-    elif args.use_ddim or args.eta != 0.0 or args.dpm_solver:
-        ap.error("--use_ddim, --eta and --dpm_solver belong to --method ddnm (RePaint runs ancestral steps)")
+    elif args.use_ddim or args.eta != 0.0 or args.dpm_solver or args.sigma_y != 0.0:
+        ap.error("--use_ddim, --eta, --dpm_solver and --sigma_y belong to --method ddnm (RePaint runs ancestral steps)")
     if args.images is None and not args.synthetic:
         ap.error("--images is required unless --synthetic is given")
 
@@ -117,7 +128,12 @@ def main():
     elif ddnm:
         kw = dict(respacing=args.timestep_respacing or None, ddim=args.use_ddim, eta=args.eta)
         tail = "_ddnm" + (f"_ddim_eta{args.eta:g}" if args.use_ddim else "")
-        print(f"Inpainting {n} images ({mask_name} mask, {spec} steps, DDNM{', DDIM eta ' + format(args.eta, 'g') if args.use_ddim else ''}) "
+        what = "DDNM"
+        if args.sigma_y != 0.0:
+            kw.update(sigma_y=args.sigma_y)
+            tail += f"_sy{args.sigma_y:g}"
+            what = f"DDNM+ for sigma_y = {args.sigma_y:g}"
+        print(f"Inpainting {n} images ({mask_name} mask, {spec} steps, {what}{', DDIM eta ' + format(args.eta, 'g') if args.use_ddim else ''}) "
               f"with {args.saved_model}.")
     else:
         kw = dict(respacing=args.timestep_respacing or None, jump_length=args.jump_length, jump_n_sample=args.jump_n_sample)
@@ -130,7 +146,8 @@ def main():
         torch.manual_seed(args.seed + g)          # x_T and the Philox key of batch g
         x, m = x_all[i:i + args.batch_size].to(device), mask_all[i:i + args.batch_size].to(device)
         if ddnm:
-            out = (model.restore_solver if args.dpm_solver else model.restore)(x, m.amin(dim=1), 1, **kw)
+            run = model.restore_solver if args.dpm_solver else model.restore_noisy if args.sigma_y != 0.0 else model.restore
+            out = run(x, m.amin(dim=1), 1, **kw)
         else:
             out = model.inpaint(x, m, **kw)
         if config["model"] == "dddpm":

@@ -117,7 +117,7 @@ class DownsampleDDPM(DDPM):
                                                                                    who="restore"))
 
     def _latent_restore(self, y, m, s, paste, who, loop):
-        """What restore and restore_solver share once their arguments are checked: the latent constraint of y, mask m and scale s
+        """What restore, restore_solver and restore_noisy share once their arguments are checked: the latent constraint of y, mask m and scale s
         (see restore), the chain loop(y_lat, n_lat, m_lat) in the latent, the decoder and the paste.  Returns (x_out, z)."""
         d = int(self.dim_reduc)
         if m is None and s == d:
@@ -151,6 +151,25 @@ class DownsampleDDPM(DDPM):
         y, m = self._restore_solver_args(y, mask, scale, self.x_shape, solver, order, unsupported, scales)
         return self._latent_restore(y, m, int(scale), paste, "restore_solver",
                                     lambda y_lat, n_lat, m_lat: self._restore_solver_loop(y_lat, n_lat, respacing, solver, order, x_T, mask=m_lat))
+
+    @torch.no_grad()
+    def restore_noisy(self, y, mask=None, scale=1, *, sigma_y, respacing=None, ddim=False, eta=0.0, x_T=None, seed=None, **unsupported):
+        """DDPM.restore_noisy with the constraint held in the latent as restore holds it (same scales, same mask rules).  There is no
+        paste: a noisy measurement is never put back into the result (sigma_y == 0 is restore with paste off).  sigma_y is used as
+        the latent's noise level unchanged.  That is an approximation: the encoder is not linear, so noise of standard deviation
+        sigma_y on the pixels of y is not noise of exactly that level, nor exactly Gaussian, on z_ref.  Returns (x_out, z); x_T is a
+        latent start."""
+        sigma_y = self._sigma_y_arg(sigma_y, "restore_noisy")
+        if 'paste' in unsupported:
+            raise ValueError("restore_noisy: paste is not accepted (a noisy measurement is never put back into the result)")
+        if sigma_y == 0:
+            return self.restore(y, mask, scale, respacing=respacing, ddim=ddim, eta=eta, x_T=x_T, seed=seed, paste=False, **unsupported)
+        d = int(self.dim_reduc)
+        scales = (1,) + tuple(d * n for n in (1,) + self.RESTORE_BLOCKS)
+        y, m = self._restore_noisy_args(y, mask, scale, self.x_shape, sigma_y, ddim, eta, unsupported, scales)
+        return self._latent_restore(y, m, int(scale), False, "restore_noisy",
+                                    lambda y_lat, n_lat, m_lat: self._restore_noisy_loop(y_lat, n_lat, sigma_y, respacing, ddim, eta, x_T, seed,
+                                                                                         mask=m_lat))
 
     @torch.no_grad()
     def reconstruct(self, x, n):

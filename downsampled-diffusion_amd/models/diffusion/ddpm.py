@@ -544,6 +544,82 @@ class DDPM(nn.Module):
         y, m = self._restore_solver_args(y, mask, scale, self.sample_shape, solver, order, unsupported, self.RESTORE_SCALES)
         return self._restore_solver_loop(y, int(scale), respacing, solver, order, x_T, mask=m)
 
+    # ------------------------------------------------------------------ DDNM+ for a noisy measurement
+    @staticmethod
+    def _sigma_y_arg(sigma_y, who):
+        """ValueError unless sigma_y is a finite real number >= 0; returns it as a float."""
+        if isinstance(sigma_y, bool) or not isinstance(sigma_y, (int, float, np.integer, np.floating)) or \
+                not np.isfinite(sigma_y) or sigma_y < 0:
+            raise ValueError(f"{who}: sigma_y must be a finite real number >= 0, got {sigma_y!r}")
+        return float(sigma_y)
+
+    def _noisy_tables(self, respacing, ddim, eta, sigma_y):
+        """(restore's tables plus the per-row lam and sgm of respace.noisy_coefficients, timestep map or None) for this sigma_y,
+        cached like _spaced_tables.  The plain chain keeps the model's own tables, as restore does."""
+        if respacing is not None or ddim or eta != 0:
+            return self._cached_tables(('noisy', respacing, bool(ddim), float(eta), sigma_y),
+                                       lambda: respace.noisy_tables(self._betas64, respacing, ddim, eta, sigma_y))
+
+        def plain():
+            lam, sgm = respace.noisy_coefficients(respace.schedule_arrays(self._betas64)['posterior_mean_coef1'],
+                                                  self.posterior_sigma.detach().double().cpu().numpy(), sigma_y)
+            return dict(self._tables(), lam=torch.tensor(lam, dtype=torch.float32), sgm=torch.tensor(sgm, dtype=torch.float32)), None
+        return self._cached_tables(('noisy', None, False, 0.0, sigma_y), plain)
+
+    def _restore_noisy_loop(self, y, n, sigma_y, respacing, ddim, eta, x_T, seed, mask=None):
+        """DDNM+ over the latent whose n x n block means are measured as y [B, C, H/n, W/n], with noise of standard deviation
+        sigma_y, where mask [B, H/n, W/n] (None: everywhere) is 1: native (UnetPlan.sample_restore_noisy_nhwc) or, with
+        native_sampler off, the same op as a Python loop in the same NHWC layout, so both draw the same Philox numbers."""
+        device = self.betas.device
+        if device.type != 'cuda':
+            raise DDKError("restore_noisy: move the model to a ROCm device first (no CPU fallback)")
+        tables, use = self._noisy_tables(respacing, ddim, eta, sigma_y)
+        shape = (y.shape[0], *self.sample_shape)
+        if x_T is not None and tuple(x_T.shape) != shape:
+            raise ValueError(f"restore_noisy: x_T must be {shape}, got {tuple(x_T.shape)}")
+        img = torch.randn(shape, device=device) if x_T is None else x_T.to(device).float()
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        k_start = (self.timesteps if use is None else len(use)) - 1
+        yl = ops.nchw_to_nhwc(y.to(device).float().contiguous())
+        mk = None if mask is None else mask.to(device).float().contiguous()
+        x = ops.nchw_to_nhwc(img.contiguous())
+        if not self.native_sampler:
+            with self._eps_model_nhwc().plan().forwards_as_in_chain():
+                for k in range(k_start, -1, -1):
+                    t_model = k if use is None else use[k]
+                    eps_hat = self.latent_model(ops.nhwc_to_nchw(x), torch.full((shape[0],), t_model, device=device, dtype=torch.long))
+                    ops.p_sample_update_restore_noisy_(x, ops.nchw_to_nhwc(eps_hat.contiguous()), yl, mk, n,
+                                                       torch.full((shape[0],), k, device=device, dtype=torch.long), **tables,
+                                                       seed=seed, stream_id=int(self.rng_stream_id))
+            return ops.nhwc_to_nchw(x)
+        self._eps_model_nhwc().plan().sample_restore_noisy_nhwc(x, yl, mk, n, tables, k_start, seed=seed, stream_id=int(self.rng_stream_id),
+                                                                use_graph=self.use_graph, timesteps=use)
+        return ops.nhwc_to_nchw(x)
+
+    def _restore_noisy_args(self, y, mask, scale, shape, sigma_y, ddim, eta, unsupported, scales):
+        """restore's ValueErrors (_restore_masked_args, whose return value this returns), then the chain whose draws are all zero."""
+        y, m = self._restore_masked_args(y, mask, scale, shape, ddim, eta, unsupported, scales)
+        if ddim and eta == 0:
+            raise ValueError("restore_noisy: sigma_y > 0 needs a chain that draws (ancestral steps, or ddim with eta > 0): with eta = 0 "
+                             "every row's lam is 0 and nothing would be constrained")
+        return y, m
+
+    @torch.no_grad()
+    def restore_noisy(self, y, mask=None, scale=1, *, sigma_y, respacing=None, ddim=False, eta=0.0, x_T=None, seed=None, **unsupported):
+        """restore() for a measurement that is only known to +- sigma_y (DDNM+, Wang, Yu, Zhang 2023, section 3.3; DESIGN.md
+        section 3.10): y = A x + noise of standard deviation sigma_y, in y's own [-1, 1] scale.  Every step scales its correction
+        of x0 by the row's lam <= 1 and the draw on measured elements by the row's sgm <= sigma, so that the noise entering through
+        y and the drawn noise add up to the chain's own variance; the last step returns the model's own x0, so y is never pasted
+        into the result.  y, mask, scale, the other keywords and their ValueErrors: as restore.  sigma_y must be a finite real
+        number >= 0; sigma_y == 0 is restore itself.  With sigma_y > 0 a chain that draws nothing (ddim=True with eta == 0) raises
+        ValueError: lam would be 0 in every row.  All before any device work."""
+        sigma_y = self._sigma_y_arg(sigma_y, "restore_noisy")
+        if sigma_y == 0:
+            return self.restore(y, mask, scale, respacing=respacing, ddim=ddim, eta=eta, x_T=x_T, seed=seed, **unsupported)
+        y, m = self._restore_noisy_args(y, mask, scale, self.sample_shape, sigma_y, ddim, eta, unsupported, self.RESTORE_SCALES)
+        return self._restore_noisy_loop(y, int(scale), sigma_y, respacing, ddim, eta, x_T, seed, mask=m)
+
     @torch.no_grad()
     def reconstruct(self, x, n):
         """ddpm.py:126-147."""

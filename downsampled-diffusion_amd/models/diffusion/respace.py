@@ -23,6 +23,9 @@ and ``"logsnrN"`` spaces its N steps evenly in log-SNR, the grid on which the se
 RePaint inpainting (Lugmayr et al. 2022, arXiv:2201.09865) walks the K spaced steps with forward jumps back
 up (``repaint_schedule``); each of its N reverse ops is one row of ``repaint_tables``: the ancestral update's columns at the op's
 spaced index tau, plus ka / kb (the known image noised to abar_{tau-1}) and ja / jb (the closed-form forward jump after the op).
+
+DDNM+ for a noisy measurement (Wang, Yu, Zhang 2023, section 3.3) adds two per-row tables to a spaced chain,
+``lam`` and ``sgm`` (``noisy_coefficients``): the scale of the DDNM correction and of the draw on measured elements.
 """
 import numpy as np
 import torch
@@ -208,6 +211,39 @@ def spaced_tables(betas, spec=None, ddim=False, eta=0.0):
                       sigma=torch.tensor(sigma, dtype=torch.float32))
     else:
         tables.update(c1=f['posterior_mean_coef1'], c2=f['posterior_mean_coef2'], sigma=f['posterior_sigma'])
+    return tables, use
+
+
+def noisy_coefficients(c1, sigma, sigma_y):
+    """float64 (lam, sgm) of DDNM+ (Wang, Yu, Zhang 2023, section 3.3, eq. 19 with a_t = c1 and sigma_t = s; DESIGN.md section
+    3.10) for a chain in the linear form above whose measurement carries noise of standard deviation ``sigma_y``.  With
+    s_k = (k > 0 ? sigma[k] : 0), the draw's scale as the kernels apply it:
+
+        lam[k] = 1 if s_k >= |c1[k]| sigma_y else s_k / (|c1[k]| sigma_y)         (row 0: lam = 0)
+        sgm[k] = sqrt(max(s_k^2 - (c1[k] lam[k] sigma_y)^2, 0))                   (0 where lam < 1)
+
+    so that the noise of y that reaches x_prev, c1 lam sigma_y, and the draw on a measured element, sgm, add up to s_k^2."""
+    c1 = np.asarray(c1, dtype=np.float64)
+    s = np.array(sigma, dtype=np.float64)
+    s[0] = 0.
+    a = np.abs(c1) * float(sigma_y)
+    lam = np.where(s >= a, 1., s / np.where(a > 0, a, 1.))
+    lam[0] = 0.
+    sgm = np.sqrt(np.maximum(s ** 2 - (c1 * lam * float(sigma_y)) ** 2, 0.))
+    return lam, np.where(lam < 1., 0., sgm)
+
+
+def noisy_tables(betas, spec=None, ddim=False, eta=0.0, sigma_y=0.0):
+    """(spaced_tables' fp32 tables plus the per-row lam and sgm of noisy_coefficients, timestep map) of a DDNM+ chain.  lam and sgm
+    are formed in float64 from the float64 c1 and from the fp32 sigma the kernels apply, widened (so at sigma_y = 0 sgm is that
+    sigma bit for bit, row 0 apart), and cast once."""
+    if not np.isfinite(sigma_y) or sigma_y < 0:
+        raise ValueError(f"sigma_y must be a finite number >= 0, got {sigma_y}")
+    tables, use = spaced_tables(betas, spec, ddim, eta)
+    sched, _ = _respaced_schedule(betas, spec)
+    c1 = ddim_coefficients(sched['alphas_cumprod'], eta)[0] if ddim else sched['posterior_mean_coef1']
+    lam, sgm = noisy_coefficients(c1, tables['sigma'].double().numpy(), sigma_y)
+    tables.update(lam=torch.tensor(lam, dtype=torch.float32), sgm=torch.tensor(sgm, dtype=torch.float32))
     return tables, use
 
 

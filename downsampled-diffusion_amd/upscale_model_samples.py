@@ -10,6 +10,9 @@ Loads the checkpoint as generate_model_samples.py does (``--synthetic CONFIG`` b
   * ``--timestep_respacing``, ``--use_ddim`` and ``--eta`` choose the chain as in generate_model_samples.py; ``--dpm_solver``
     (not with ``--use_ddim`` / ``--eta``) runs ``model.restore_solver`` instead, DDNM on the DPM-Solver++(2M) chain (section 3.9;
     use a log-SNR grid, e.g. ``logsnr20``), and adds ``_dpmpp2m`` to the file names;
+  * ``--sigma_y S`` (not with ``--dpm_solver``) declares that the low-resolution images carry noise of standard deviation S in the
+    model's [-1, 1] scale (S = 2 s / 255 for s uint8 levels): ``model.restore_noisy`` (DDNM+, section 3.10) runs instead, and the
+    file names gain ``_sy{S}``;
   * batch g draws x_T and its Philox key from ``--seed`` + g.
 
 Writes ``{saved_model}_sr{scale}_{spec}.npy`` through the sampling driver's output stage (utils.OutputStage: float32
@@ -41,6 +44,8 @@ def main():
     ap.add_argument("--eta", type=float, default=0.0, help="DDIM noise scale (0: deterministic)")
     ap.add_argument("--dpm_solver", action="store_true",
                     help='DPM-Solver++(2M) steps over the --timestep_respacing grid (e.g. "logsnr20"); not with --use_ddim / --eta')
+    ap.add_argument("--sigma_y", type=float, default=0.0,
+                    help="the noise level of the low-resolution images in the [-1, 1] scale (DDNM+); not with --dpm_solver")
     ap.add_argument("--batch_size", type=int, default=32)
     ap.add_argument("--seed", type=int, default=1234, help="base seed: batch g draws from seed + g")
     ap.add_argument("--out_dir", default=None)
@@ -49,6 +54,12 @@ def main():
         ap.error("--dpm_solver is its own deterministic update: it cannot be combined with --use_ddim or --eta")
     if args.eta < 0 or (args.eta != 0.0 and not args.use_ddim):
         ap.error("--eta needs --use_ddim and a value >= 0")
+    if not np.isfinite(args.sigma_y) or args.sigma_y < 0:
+        ap.error("--sigma_y must be a finite number >= 0")
+    if args.sigma_y != 0.0 and args.dpm_solver:
+        ap.error("--sigma_y and --dpm_solver are exclusive (the solver draws nothing, so there is no variance to trade)")
+    if args.sigma_y != 0.0 and args.use_ddim and args.eta == 0.0:
+        ap.error("--sigma_y needs a chain that draws: ancestral steps, or --use_ddim with --eta > 0")
     if args.batch_size < 1 or args.scale < 2:
         ap.error("--batch_size must be >= 1 and --scale >= 2")
 
@@ -89,7 +100,7 @@ def main():
     lowres = ((y_all + 1) * 127.5).round().clamp(0, 255).permute(0, 2, 3, 1).numpy().astype(np.uint8)
 
     spec = (args.timestep_respacing.replace(",", "-") or "full") + (f"_ddim_eta{args.eta:g}" if args.use_ddim else "") + \
-        ("_dpmpp2m" if args.dpm_solver else "")
+        ("_dpmpp2m" if args.dpm_solver else "") + (f"_sy{args.sigma_y:g}" if args.sigma_y != 0.0 else "")
     if args.dpm_solver:
         kw = dict(respacing=args.timestep_respacing or None, solver="dpm++2m")
     else:
@@ -100,7 +111,10 @@ def main():
     for g, i in enumerate(range(0, n, args.batch_size)):
         torch.manual_seed(args.seed + g)          # x_T and the Philox key of batch g
         y = y_all[i:i + args.batch_size].to(device)
-        out = model.restore_solver(y, None, s, **kw) if args.dpm_solver else model.super_resolve(y, s, **kw)
+        if args.sigma_y != 0.0:
+            out = model.restore_noisy(y, None, s, sigma_y=args.sigma_y, **kw)
+        else:
+            out = model.restore_solver(y, None, s, **kw) if args.dpm_solver else model.super_resolve(y, s, **kw)
         stage.submit(out[0] if config["model"] == "dddpm" else out)
     batches = stage.finish()
     torch.cuda.synchronize()

@@ -104,7 +104,7 @@ def _score(ops, cand_u8, ref_u8, hidden, device):
 
 @torch.no_grad()
 def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234, mask="center", scale=4, method=None, sr_mask=None,
-                         dpm_solver=False, **chain):
+                         dpm_solver=False, sigma_y=0.0, **chain):
     """Degrade, restore and score ``images_uint8`` (uint8 [N, H, W, C] of the model's size).
 
     task "inpaint": ``mask`` is one of MASKS or a {0, 1} tensor broadcastable to [N, 1|C, H, W] (1 = known); ``chain`` goes to
@@ -121,6 +121,13 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
     measured pixels.  Without a mask, task "sr" is ``model.super_resolve`` as before.
     dpm_solver (method "ddnm" only; ``chain``: respacing alone, no ddim / eta): DDNM on the DPM-Solver++(2M) chain (section 3.9),
     ``model.restore_solver`` in place of ``restore`` / ``super_resolve``; the returned method is then "ddnm_dpmpp2m".
+    sigma_y > 0 (method "ddnm" only, not with dpm_solver): the measurement is noisy (section 3.10).  N(0, sigma_y^2) noise from a
+    generator seeded with ``seed`` is added to the float measurement (the image of task "inpaint", the pooled image of task "sr")
+    after degrading and before restoring; ``model.restore_noisy`` restores it and the baselines are built from the same noisy
+    measurement.  The returned method is "ddnm_plus" and "sigma_y" is returned; "consistency" / "consistency_u8" are then, per
+    image, the RMS of pool(x_out) - y_clean over the measured pixels in uint8 levels (how far the result is from the clean
+    measurement; task "inpaint" gets them too), since the result is not meant to reproduce the noisy one.  sigma_y = 0: exactly
+    the result without it.
     Batch g draws x_T and its Philox key from seed + g, as the sampling CLIs do.
 
     "method" and "unet_forwards" (UNet forwards per image: the chain's steps; the batch shares each forward) are returned too.
@@ -140,6 +147,11 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
         method = "repaint" if task == "inpaint" else "ddnm"
     if method not in METHODS or (task == "sr" and method != "ddnm"):
         raise ValueError(f"unknown method {method!r} for task {task!r}: one of {METHODS} (sr: ddnm only)")
+    if isinstance(sigma_y, bool) or not isinstance(sigma_y, (int, float, np.integer, np.floating)) or not math.isfinite(sigma_y) or sigma_y < 0:
+        raise ValueError(f"sigma_y must be a finite real number >= 0, got {sigma_y!r}")
+    sigma_y = float(sigma_y)
+    if sigma_y and (method != "ddnm" or dpm_solver):
+        raise ValueError("sigma_y needs method 'ddnm' on ancestral or DDIM (eta > 0) steps: not RePaint, not dpm_solver")
     if dpm_solver:
         if method != "ddnm" or chain.get("ddim") or chain.get("eta", 0.0) != 0.0:
             raise ValueError("dpm_solver runs DDNM on its own deterministic update: method 'ddnm', no ddim, no eta")
@@ -150,35 +162,41 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
         K = len(model._spaced_tables(chain.get("respacing"), chain.get("ddim", False), chain.get("eta", 0.0))[1]) \
             if chain.get("respacing") is not None or chain.get("ddim") else int(model.timesteps)
         run = model.restore
+    noise = None
+    if sigma_y:
+        run = lambda y, m, s, **kw: model.restore_noisy(y, m, s, sigma_y=sigma_y, **kw)
+        noise = lambda like: sigma_y * torch.randn(like.shape, generator=torch.Generator().manual_seed(seed))
     if task == "inpaint":
         m_all = make_mask(mask, n, h, w) if isinstance(mask, str) else torch.as_tensor(mask).float().expand(n, -1, h, w)
         if method == "ddnm":
             m_all = m_all.amin(dim=1, keepdim=True)
-            restore = lambda i: run(x_all[i:i + batch_size].to(device), m_all[i:i + batch_size, 0].to(device), 1, **chain)
+            x_meas = x_all + noise(x_all) if sigma_y else x_all
+            restore = lambda i: run(x_meas[i:i + batch_size].to(device), m_all[i:i + batch_size, 0].to(device), 1, **chain)
             extra["unet_forwards"] = K
         else:
             restore = lambda i: model.inpaint(x_all[i:i + batch_size].to(device), m_all[i:i + batch_size].to(device), **chain)
             extra["unet_forwards"] = len(model._inpaint_tables(chain.get("respacing"), chain.get("jump_length", 10),
                                                                chain.get("jump_n_sample", 10))[1])
-        images["mean_fill"] = to_u8(mean_fill(x_all, m_all))
+        images["mean_fill"] = to_u8(mean_fill(x_meas if sigma_y else x_all, m_all))
         hidden = (m_all.amin(dim=1) == 0).to(torch.uint8).contiguous()
     else:
         scale = int(scale)
         if scale < 2 or h % scale or w % scale:
             raise ValueError(f"scale {scale} must be >= 2 and divide the image size {h} x {w}")
         y_all = pool(x_all, scale)
+        y_meas = y_all + noise(y_all) if sigma_y else y_all
         extra["unet_forwards"] = K
         my_all = None
         if sr_mask is None:
-            restore = (lambda i: run(y_all[i:i + batch_size].to(device), None, scale, **chain)) if dpm_solver else \
+            restore = (lambda i: run(y_meas[i:i + batch_size].to(device), None, scale, **chain)) if dpm_solver or sigma_y else \
                 (lambda i: model.super_resolve(y_all[i:i + batch_size].to(device), scale, **chain))
-            y_base = y_all
+            y_base = y_meas
         else:
             hs, ws = h // scale, w // scale
             my_all = make_mask(sr_mask, n, hs, ws) if isinstance(sr_mask, str) else torch.as_tensor(sr_mask).float().expand(n, -1, hs, ws)
             my_all = my_all.amin(dim=1, keepdim=True)
-            restore = lambda i: run(y_all[i:i + batch_size].to(device), my_all[i:i + batch_size, 0].to(device), scale, **chain)
-            y_base = mean_fill(y_all, my_all)             # the baselines see the same holes
+            restore = lambda i: run(y_meas[i:i + batch_size].to(device), my_all[i:i + batch_size, 0].to(device), scale, **chain)
+            y_base = mean_fill(y_meas, my_all)            # the baselines see the same holes
         images["replicate"] = to_u8(replicate(y_base, scale))
         images["bicubic"] = to_u8(bicubic(y_base, scale))
     outs = []
@@ -188,12 +206,20 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
         outs.append((out[0] if isinstance(out, tuple) else out).float().cpu())      # a dDDPM returns (x_out, z)
     x_out = torch.cat(outs)
     images = dict(restored=to_u8(x_out), **images)
-    if task == "sr":
+    if sigma_y:
+        # the result is not meant to reproduce the noisy measurement: its RMS distance from the CLEAN one over the measured pixels
+        s1, y_clean = (1, x_all) if task == "inpaint" else (scale, y_all)
+        meas = (m_all if task == "inpaint" else torch.ones_like(y_all[:, :1]) if my_all is None else my_all).expand_as(y_clean)
+        rms = lambda x: ((((pool(x, s1) if s1 > 1 else x) - y_clean) ** 2 * meas).sum(dim=(1, 2, 3)) / meas.sum(dim=(1, 2, 3)).clamp(min=1)).sqrt() * 127.5
+        extra["consistency"] = rms(x_out).double().numpy()
+        extra["consistency_u8"] = rms(from_u8(images["restored"])).double().numpy()
+        extra["sigma_y"] = sigma_y
+    elif task == "sr":
         meas = 1.0 if my_all is None else my_all      # the constraint holds where y is measured
         extra["consistency"] = (((pool(x_out, scale) - y_all) * meas).abs().amax(dim=(1, 2, 3)) * 127.5).double().numpy()
         extra["consistency_u8"] = (((pool(from_u8(images["restored"]), scale) - y_all) * meas).abs().amax(dim=(1, 2, 3)) * 127.5).double().numpy()
     methods = {name: _score(ops, img, ref, hidden, device) for name, img in images.items()}
-    return dict(n_images=n, method=method + ("_dpmpp2m" if dpm_solver else ""), methods=methods, images={k: v.numpy() for k, v in images.items()}, **extra)
+    return dict(n_images=n, method=method + ("_dpmpp2m" if dpm_solver else "_plus" if sigma_y else ""), methods=methods, images={k: v.numpy() for k, v in images.items()}, **extra)
 
 
 def report(result):

@@ -331,6 +331,18 @@ int ddk_p_sample_update_restore_masked(float* x, const float* eps_hat, const flo
 int ddk_p_sample_update_restore_multistep(float* x, const float* eps_hat, float* x0_hist, const float* y, const float* mask, int n,
                                           const int64_t* t, const float* c_recip, const float* c_recipm1, const float* c1, const float* c2,
                                           const float* c3, int B, int H, int W, int channels, ddk_stream_t s);
+/* One DDNM+ step for a noisy measurement on its own (ddk_sampler_run_restore_noisy), per sample b with row t[b] of
+ * the tables of ddk_sampler_run_restore_masked and of lam, sgm (the correction's scale and the draw's scale on measured elements):
+ *   x0  = clamp(c_recip x - c_recipm1 eps_hat, -1, 1);  s = t > 0 ? sigma : 0;
+ *   measured:      x0' = x0 + lam (y[block] - mean_block(x0))   (n == 1: x0 + lam (y - x0));   x = (c1 x0' + c2 x) + sgm z;
+ *   not measured:  x0' = x0;                                                                   x = (c1 x0' + c2 x) + s z.
+ * Both arms are selects on the mask: NaN in unmeasured y reaches nothing.  Every operation is rounded on its own; z is the Philox draw of
+ * ddk_p_sample_update_restore.  mask may be NULL for n >= 2 (every block measured); n == 1 without a mask is DDK_ERR_ARG.
+ * H * W * channels must be a multiple of 4 (below 2^31); x, eps_hat and, at n == 1, y 16-byte aligned.  On an error x is not touched. */
+int ddk_p_sample_update_restore_noisy(float* x, const float* eps_hat, const float* y, const float* mask, int n, const int64_t* t,
+                                      const float* c_recip, const float* c_recipm1, const float* c1, const float* c2, const float* sigma,
+                                      const float* lam, const float* sgm, int B, int H, int W, int channels, uint64_t seed, uint32_t stream_id,
+                                      ddk_stream_t s);
 /* The end of a forward in one launch (unet.py:69-72 behind the final Block's conv; ddpm.py:203-227): GroupNorm from the conv's
  * partials -> Mish -> 1x1 projection to n_out <= 8 channels (w [n_out][C], bias [n_out]) -> eps_hat; eps_out and / or x may be
  * given: eps_out [B][HW][n_out] receives eps_hat, x [B][HW][n_out] gets the reverse-step update of ddk_p_sample_update in place
@@ -436,7 +448,8 @@ int ddk_unet_forward(const ddk_unet* u, const void* packed, const float* x, cons
  * ddk_sampler_restore_tail_parts says it can; 0 ends every step in ddk_p_sample_update_restore's kernel behind the forward, as the
  * shapes that cannot do (where the plain forward ends in one launch, that launch leaves eps_hat in the workspace first, so the
  * update sees the same eps_hat).  Bit-identical results either way (tests/test_restore_gpu.py).  The masked chain
- * (ddk_sampler_run_restore_masked) and the solver's (ddk_sampler_run_restore_multistep) obey it too. */
+ * (ddk_sampler_run_restore_masked), the solver's (ddk_sampler_run_restore_multistep) and the noisy chain
+ * (ddk_sampler_run_restore_noisy) obey it too. */
 #define DDK_OPT_RESTORE_FUSED_TAIL 12
 int ddk_unet_set_option(ddk_unet* u, int option, int value);
 /* Waits for `s`, then reads and clears the sticky give-up count of the launches issued on `workspace` (a ddk_unet_forward or
@@ -568,6 +581,18 @@ size_t ddk_sampler_restore_multistep_workspace_bytes(const ddk_unet* u, int B, i
 int ddk_sampler_restore_multistep_tail_parts(const ddk_unet* u, int B, int H, int W, int n);
 int ddk_sampler_run_restore_multistep(const ddk_sampler_args* a, const int64_t* timestep_map, const float* c3, const float* y,
                                       const float* mask, int n, ddk_stream_t s);
+/* Zero-shot restoration of a noisy measurement: DDNM+ for A = mask o (n x n average pooling).  The chain and
+ * tables of ddk_sampler_run_restore_masked, every step being ddk_p_sample_update_restore_noisy's with the per-row device tables lam and
+ * sgm (t_start + 1 floats each, formed by the caller from sigma_y).  mask NULL at n >= 2: every block measured; n = 1 without a mask is
+ * DDK_ERR_ARG.  The workspace (ddk_sampler_restore_noisy_workspace_bytes) has ddk_sampler_run_restore_masked's layout; y and the mask
+ * are copied in before the first step, outside any captured step.  a->noise must be NULL.  Graphs are cached under a chain kind of their
+ * own, with lam, sgm, n and the presence of a mask in the key: this chain never replays another kind's graph on the same buffers.
+ * DDK_OPT_RESTORE_FUSED_TAIL = 0 forces the unfused tail here too; the two tails are bit-identical.
+ * ddk_sampler_restore_noisy_tail_parts: as ddk_sampler_restore_masked_tail_parts. */
+size_t ddk_sampler_restore_noisy_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start, int n);
+int ddk_sampler_restore_noisy_tail_parts(const ddk_unet* u, int B, int H, int W, int n);
+int ddk_sampler_run_restore_noisy(const ddk_sampler_args* a, const int64_t* timestep_map, const float* lam, const float* sgm, const float* y,
+                                  const float* mask, int n, ddk_stream_t s);
 /* Drops the plan's cached sampler and likelihood-sweep graphs and shift table (waits for the device when graphs exist). */
 int ddk_sampler_invalidate(ddk_unet* u);
 /* Drops only the cached graphs (and shift table) that live in / point into `workspace`, after waiting for the launches of

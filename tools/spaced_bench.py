@@ -22,7 +22,11 @@ images/s of "100"-step DDIM (eta 0) DDNM inpainting with the decode, for the com
 
 --restore-solver: the cost of a DDNM step on the DPM-Solver++(2M) chain at n = 1 with the center mask and n = 2
 without a mask, against a plain 2M step on the same "logsnr20" grid, timed alternately the same way, and the end-to-end images/s of
-each with the decode."""
+each with the decode.
+
+--restore-noisy: the cost of a DDNM+ step for a noisy measurement (sigma_y = 0.1) at n = 1 with the center
+mask (the fused tail; and with the fused tail switched off) and n = 2 with the mask, against an ancestral step of the same respaced
+"50" chain, timed alternately the same way."""
 import argparse
 import json
 import os
@@ -44,6 +48,7 @@ B, C, S, T = 32, 8, 32, 1000
 KS = (50, 100, 250)
 SOLVER_KS = (20, 50)
 REPS = 5
+NOISY_SIGMA_Y = 0.1
 
 
 def main():
@@ -51,6 +56,7 @@ def main():
     ap.add_argument("--solver", action="store_true", help="2M step against DDIM step on logsnrK grids")
     ap.add_argument("--restore", action="store_true", help="DDNM super-resolution step against an ancestral step, respacing 50")
     ap.add_argument("--restore-masked", action="store_true", help="masked DDNM step (n = 1, 2) against an ancestral step, respacing 50")
+    ap.add_argument("--restore-noisy", action="store_true", help="DDNM+ step (n = 1, 2; sigma_y 0.1) against an ancestral step, respacing 50")
     ap.add_argument("--restore-solver", action="store_true", help="DDNM step on the 2M chain (n = 1 center mask, n = 2) against a 2M step, logsnr20")
     args = ap.parse_args()
     torch.cuda.set_device(0)
@@ -89,6 +95,10 @@ def main():
             n = int(kind[len("rsolver"):])
             sp, use = model._solver_tables(f"logsnr{K}", "dpm++2m")
             plan.sample_restore_multistep_nhwc(x, ys[n], mks[n] if n == 1 else None, n, sp, K - 1, stream_id=0, timesteps=use)
+        elif kind.startswith("noisy"):                   # DDNM+ on ancestral steps, the center mask
+            n = int(kind[len("noisy"):])
+            sp, use = model._noisy_tables(str(K), False, 0.0, NOISY_SIGMA_Y)
+            plan.sample_restore_noisy_nhwc(x, ys[n], mks[n], n, sp, K - 1, seed=1234, stream_id=0, timesteps=use)
         elif kind.startswith("masked"):                  # "masked<n>" ancestral, "maskedddim<n>" DDIM eta 0
             ddim = kind.startswith("maskedddim")
             n = int(kind[len("maskedddim" if ddim else "masked"):])
@@ -120,6 +130,8 @@ def main():
         return restore_masked_ab(chain, plan, decode)
     if args.restore_solver:
         return restore_solver_ab(chain, plan, decode)
+    if args.restore_noisy:
+        return restore_noisy_ab(chain, plan)
 
     res = {"shape": f"cfg4 unet_chan 128, {C}x{S}x{S} latents, B={B}, T={T}, DDIM eta 0", "reps": REPS, "per_K": {}}
     with torch.no_grad():
@@ -232,6 +244,32 @@ def restore_masked_ab(chain, plan, decode):
         res["ddim100_inpaint"] = {"chain_ms": round(ms, 3), "chain_min_max_ms": [round(min(runs), 3), round(max(runs), 3)],
                                   "decode_ms": round(decode_ms, 3), "unet_forwards": K,
                                   "images_per_sec": round(B / ((ms + decode_ms) / 1e3), 2)}
+    print(json.dumps(res), flush=True)
+
+
+def restore_noisy_ab(chain, plan):
+    K = 50
+    res = {"shape": f"cfg4 unet_chan 128, {C}x{S}x{S} latents, B={B}, T={T}, respacing {K}, DDNM+ step (sigma_y {NOISY_SIGMA_Y}) vs ancestral "
+                    "step, center mask", "reps": REPS, "per_n": {}}
+    with torch.no_grad():
+        t_settle = time.perf_counter()
+        while time.perf_counter() - t_settle < 2.0:
+            chain("plain", 96)
+        for n, fused in ((1, True), (2, True), (1, False)):
+            plan.set_option(plan.OPT_RESTORE_FUSED_TAIL, int(fused))
+            tail = "fused" if plan.restore_noisy_tail_parts(B, S, S, n) > 0 else "unfused"
+            chain("anc", K)                              # captures both chains' graphs outside the timed calls
+            chain(f"noisy{n}", K)
+            anc, rst = [], []
+            for _ in range(REPS):
+                anc.append(chain("anc", K) / K)
+                rst.append(chain(f"noisy{n}", K) / K)
+            a, r = statistics.median(anc), statistics.median(rst)
+            res["per_n"][f"{n}_{tail}"] = {"ancestral_ms_per_step": round(a, 4), "noisy_ms_per_step": round(r, 4),
+                                           "noisy_over_ancestral": round(r / a, 4),
+                                           "ancestral_min_max_ms": [round(min(anc), 4), round(max(anc), 4)],
+                                           "noisy_min_max_ms": [round(min(rst), 4), round(max(rst), 4)]}
+        plan.set_option(plan.OPT_RESTORE_FUSED_TAIL, 1)
     print(json.dumps(res), flush=True)
 
 
