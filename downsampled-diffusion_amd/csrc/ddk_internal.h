@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 
@@ -322,9 +323,15 @@ struct RestoreOps {
     const float* y;               // NHWC [B][H/n][W/n][n_out]: what the n x n block means of x0 are set to
     int n;                        // 2, 4 or 8, dividing H and W
     int H, W;                     // the map the blocks lie in (filled by the chain entry / the lone op; the other kinds need only `per`)
-    const float* mask;            // StepKind::RestoreMasked, RestoreMultistep, RestoreNoisy: [B][H/n][W/n], nonzero = measured, shared by the channels; n may be 1
-                                  // (RestoreMultistep, RestoreNoisy at n >= 2: may be null, every block measured)
+    int gray;                     // StepKind::RestoreGray: the channel weights, GRAY_MEAN or GRAY_LUMA; 0 in every other kind.  y is then
+                                  // [B][H/n][W/n] (one channel).  In the four bytes that were padding in front of `mask`
+    const float* mask;            // StepKind::RestoreMasked, RestoreMultistep, RestoreNoisy, RestoreGray: [B][H/n][W/n], nonzero = measured, shared by the
+                                  // channels; n may be 1 (RestoreMultistep, RestoreNoisy at n >= 2, RestoreGray at every n: may be null, all measured)
 };
+// the kernels take RestoreOps by value inside StepRule / TailParams: neither its size nor the place of `mask` may move
+static_assert(sizeof(RestoreOps) == 32 && offsetof(RestoreOps, mask) == 24, "RestoreOps: gray fills the padding, nothing moves");
+constexpr int GRAY_MEAN = 1;      // w = (1/3, 1/3, 1/3): DDNM's colourisation operator
+constexpr int GRAY_LUMA = 2;      // w = (0.299, 0.587, 0.114): BT.601 luma
 // likelihood sweep (ddk_vlb_sweep_run): one step's operands besides the UNet's
 struct VlbStep {
     const float* x;               // clean sample, NHWC [B][H][W][n_out]
@@ -351,9 +358,12 @@ enum class StepKind {
     Vlb,          // likelihood sweep: no update, the step's VLB terms to vlb->partials (vlb_rule() fills the rest from *vlb)
     RestoreMultistep,  // DDNM on the DPM-Solver++(2M) chain, n in {1, 2, 4, 8}: RestoreMasked's x0' (rst.mask null at n >= 2:
                   // every block measured), then Multistep's update on it, x0_hist <- x0': c_recip .. c2, c3, x0_hist, rst; no draw
-    RestoreNoisy  // DDNM+ for a measurement with noise of standard deviation sigma_y, n in {1, 2, 4, 8}: RestoreMasked's
+    RestoreNoisy,  // DDNM+ for a measurement with noise of standard deviation sigma_y, n in {1, 2, 4, 8}: RestoreMasked's
                   // step with the correction scaled by lam and the draw of measured elements by sgm instead of sigma (rst.mask null at
                   // n >= 2: every block measured): c_recip .. sigma, lam, sgm, rst; Philox only
+    RestoreGray   // DDNM / DDNM+ for A = mask o pool_n o grey_w on a 3-channel map, n in {1, 2, 4, 8}: RestoreNoisy's step
+                  // with the block mean replaced by the weighted mean of the n x n x 3 group and the correction spread by A+'s per-channel
+                  // factor (rst.gray names w; rst.mask may be null at every n): c_recip .. sigma, nsy, rst; Philox only
                   // (last, so that the kinds above keep their values and their kernels' names)
 };
 struct StepRule {
@@ -370,7 +380,7 @@ struct StepRule {
     // take a StepRule by value, and a larger one would move every argument behind it and with that the instructions of the older kernels.
     union {
         InpaintOps inp;
-        NoisyTables nsy;
+        NoisyTables nsy;          // RestoreNoisy, RestoreGray
     };
     const VlbStep* vlb;           // host side only
     RestoreOps rst;
@@ -391,7 +401,7 @@ struct ChainHooks {
     uint32_t stream_id;
 };
 // the unfused tail's last kernel, given eps_hat in memory: the rule's update of x (Ancestral, Multistep, Inpaint, Restore, RestoreMasked,
-// RestoreMultistep, RestoreNoisy) or the sweep's
+// RestoreMultistep, RestoreNoisy, RestoreGray) or the sweep's
 // reduction of the step's terms (Vlb); `who` names the caller in messages
 int p_update(const StepRule& r, const float* eps_hat, const int64_t* t, int B, long long per, const ChainHooks& h, hipStream_t st,
              const char* who = "p_update");
@@ -415,8 +425,9 @@ struct TailIn {
 // 256 the plain one spills already, and theirs hold more in the prologue).  Restore also needs every 128-pixel tile to hold whole
 // rows of blocks, 128 % (W n) == 0 with W, n = restore_w, restore_n (W = 32: n <= 4; W = 16: n <= 8; W = 64: n = 2); the other
 // kinds ignore the two.  RestoreMasked: as Restore for n >= 2; n = 1 is pointwise and needs no whole blocks, so every shape of the
-// Multistep / Inpaint kinds is taken.  RestoreMultistep, RestoreNoisy: as RestoreMasked.  The one predicate of fused_tail_parts (unet_plan.hip) and
-// final_tail.
+// Multistep / Inpaint kinds is taken.  RestoreMultistep, RestoreNoisy: as RestoreMasked.  RestoreGray: n_out == 3, and as RestoreMasked
+// (its n = 1 sums the pixel's three channels, which lie in the tile whatever W is).  The one predicate of fused_tail_parts
+// (unet_plan.hip) and final_tail.
 bool final_tail_ok(int HW, int C, int groups, int n_out, int np, StepKind kind, int restore_w = 0, int restore_n = 0);
 int final_tail(const TailIn& in, const StepRule& r, const int64_t* t, const ChainHooks& h, hipStream_t st);
 

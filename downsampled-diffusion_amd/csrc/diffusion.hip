@@ -509,6 +509,86 @@ __global__ __launch_bounds__(256) void p_update_restore_noisy_point_kernel(const
     }
 }
 
+// DDNM / DDNM+ for a grey measurement of a 3-channel map: A = mask o pool_n o grey_w.  The group of an element
+// is its n x n block over all three channels; the group value is the weighted sum in row-major order, channel innermost, times NORM;
+// the correction d = y - m goes to channel c scaled by A+'s factor a_c (and by the row's lam), then rsn_finish.  mean: w = a = 1 and
+// NORM = 1 / (3 n n) (the products by 1 are exact); luma (BT.601): w_c, NORM = 1 / (n n), a_c = w_c / (w . w) formed in double.  Every
+// operation is rounded on its own; the arithmetic of both tails.
+struct GrayCoef {
+    float w0, w1, w2, a0, a1, a2, norm;
+};
+__device__ __forceinline__ GrayCoef gry_coef(int gray, int n) {
+    constexpr double w0 = 0.299, w1 = 0.587, w2 = 0.114, ww = (w0 * w0 + w1 * w1) + w2 * w2;
+    const bool luma = gray == GRAY_LUMA;
+    GrayCoef k;
+    k.w0 = luma ? (float)w0 : 1.0f; k.w1 = luma ? (float)w1 : 1.0f; k.w2 = luma ? (float)w2 : 1.0f;
+    k.a0 = luma ? (float)(w0 / ww) : 1.0f; k.a1 = luma ? (float)(w1 / ww) : 1.0f; k.a2 = luma ? (float)(w2 / ww) : 1.0f;
+    k.norm = __fmul_rn(luma ? 1.0f : (float)(1.0 / 3.0), 1.0f / (float)(n * n));      // n a power of two: (float)(1.0 / (3 n n)) exactly
+    return k;
+}
+
+// x0_at(i, j, c): the clipped x0 at row i, column j, channel c of the element's group (same image)
+template <class F>
+__device__ __forceinline__ float gry_group(F&& x0_at, int n, const GrayCoef& k) {
+    float g = 0.0f;
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) {
+            g = __fadd_rn(g, __fmul_rn(k.w0, x0_at(i, j, 0)));
+            g = __fadd_rn(g, __fmul_rn(k.w1, x0_at(i, j, 1)));
+            g = __fadd_rn(g, __fmul_rn(k.w2, x0_at(i, j, 2)));
+        }
+    return __fmul_rn(g, k.norm);
+}
+
+// d = y[group] - m; ac = a_c of the element's channel.  A select on the mask: an unmeasured y (d may be NaN) reaches no result.
+__device__ __forceinline__ float gry_x0p(float x0, float d, float mk, float lam, float ac) {
+    return mk != 0.0f ? __fadd_rn(x0, __fmul_rn(lam, __fmul_rn(ac, d))) : x0;
+}
+
+// The last kernel of an unfused RestoreGray step, n in {1, 2, 4, 8}: a thread owns one (image, block) with all three channels, forms the
+// group value from x and eps_hat, then updates the block's n n 3 elements in place (no other thread touches them).  r.rst.y and
+// r.rst.mask are [B][H/n][W/n]; the mask may be null (every block measured).  The draw, the counter and the key as p_update_restore_kernel's.
+__global__ __launch_bounds__(256) void p_update_restore_gray_kernel(const StepRule r, const float* __restrict__ eps_hat,
+                                                                    const int64_t* __restrict__ t, int B, uint64_t seed, uint32_t stream,
+                                                                    const int64_t* __restrict__ chain_state, int64_t* dec_counter) {
+    if (dec_counter && blockIdx.x == 0 && threadIdx.x == 0) *dec_counter -= 1;
+    if (chain_state) {
+        seed = (uint64_t)chain_state[1];
+        stream = (uint32_t)chain_state[2];
+    }
+    const int n = r.rst.n, H = r.rst.H, W = r.rst.W, Hn = H / n, Wn = W / n;
+    const long long total = (long long)B * Hn * Wn;
+    const GrayCoef k = gry_coef(r.rst.gray, n);
+    float* __restrict__ x = r.x;
+    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const int bc = (int)(i % Wn);
+        const long long q = i / Wn;
+        const int br = (int)(q % Hn), b = (int)(q / Hn);
+        const int64_t tb = t[b];
+        const float cr = r.c_recip[tb], crm1 = r.c_recipm1[tb], a1 = r.c1[tb], a2 = r.c2[tb], sg = tb > 0 ? r.sigma[tb] : 0.0f;
+        const float lam = r.nsy.lam[tb], sgm = r.nsy.sgm[tb];
+        const long long e0 = (((long long)b * H + br * n) * W + bc * n) * 3;       // the group's first element
+        const float m = gry_group(
+            [&](int bi, int bj, int c) {
+                const long long e = e0 + ((long long)bi * W + bj) * 3 + c;
+                return rst_x0(x[e], eps_hat[e], cr, crm1);
+            },
+            n, k);
+        const float mk = r.rst.mask ? r.rst.mask[i] : 1.0f;
+        const float d = __fsub_rn(r.rst.y[i], m);
+        for (int bi = 0; bi < n; ++bi)
+            for (int bj = 0; bj < n; ++bj)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const long long e = e0 + ((long long)bi * W + bj) * 3 + c;
+                    const float xv = x[e];
+                    const float z = comp4(philox_normal4((unsigned long long)(e >> 2), (uint32_t)tb, stream, seed), (int)(e & 3));
+                    const float ac = c == 0 ? k.a0 : c == 1 ? k.a1 : k.a2;
+                    x[e] = rsn_finish(xv, gry_x0p(rst_x0(xv, eps_hat[e], cr, crm1), d, mk, lam, ac), mk, z, a1, a2, sg, sgm);
+                }
+    }
+}
+
 // ---- the VLB term of one element (reference models/diffusion/ddpm.py:317-366, models/utils/losses.py:17-109) --------------------
 // Shared by vlb_terms_kernel and the likelihood sweep's epilogues (final_tail_kernel<.., StepKind::Vlb>, vlb_sweep_terms_kernel).
 __device__ __forceinline__ float std_normal_cdf_approx(float v) {
@@ -593,7 +673,8 @@ struct TailParams {
         InpaintOps inp;
         NoisyTables nsy;
     };
-    // StepKind::Restore / RestoreMasked: the low-resolution image, the block, the map's height and width and (RestoreMasked) the mask
+    // StepKind::Restore / RestoreMasked: the low-resolution image, the block, the map's height and width and (RestoreMasked) the mask;
+    // StepKind::RestoreGray: the grey image, and the weights in rst.gray
     RestoreOps rst;
 };
 
@@ -618,11 +699,16 @@ struct TailParams {
 // rst.mask may be null at n >= 2 (every block measured).
 // RestoreNoisy (ddk_sampler_run_restore_noisy, x given, Philox only): RestoreMultistep's requests of y and the optional mask (RestoreMasked's
 // places), the row's lam and sgm loaded with its other coefficients, and RestoreMasked's phase 2 with rsn_x0p / rsn_finish (n = 1: rsn_point4).
+// RestoreGray (ddk_sampler_run_restore_gray, x given, Philox only, n_out == 3): y and the optional mask of each element's block are
+// requested in the prologue (both [B][H/n][W/n]; n = 1: the element's pixel), lam and sgm as RestoreNoisy's; phase 2 is Restore's x0-over-
+// eps_hat exchange and second barrier at every n, n = 1 included (a pixel's three channels straddle float4s), then each element's thread
+// sums its n x n x 3 group from LDS (gry_group) and finishes with gry_x0p / rsn_finish.
 template <int LPP, int VPL, StepKind K>
 __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
     static_assert(K != StepKind::Eps, "the plain forward runs the Ancestral instantiation with p.x null");
     constexpr bool VLB = K == StepKind::Vlb, MS = K == StepKind::Multistep, INP = K == StepKind::Inpaint, RST = K == StepKind::Restore,
-                   RSTM = K == StepKind::RestoreMasked, RSMS = K == StepKind::RestoreMultistep, RSN = K == StepKind::RestoreNoisy;
+                   RSTM = K == StepKind::RestoreMasked, RSMS = K == StepKind::RestoreMultistep, RSN = K == StepKind::RestoreNoisy,
+                   RSG = K == StepKind::RestoreGray;
     constexpr int PPW = 64 / LPP;                    // pixels per wave and iteration
     constexpr int PPI = 16 * PPW;                    // ... per iteration of the 16-wave workgroup
     constexpr int NIT = 128 / PPI;                   // 4 at C = 128 / 256, 2 at C = 64, 1 at C = 32
@@ -663,7 +749,7 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
     const long long e4 = pix0 * p.n_out / 4;          // host: (128 * n_out) % 4 == 0
     float4 xv0 = make_float4(0.f, 0.f, 0.f, 0.f), zv0 = xv0;
     float cr = 0.f, crm1 = 0.f, a1 = 0.f, a2 = 0.f, sg = 0.f, a3 = 0.f;
-    float lam = 0.f, sgm = 0.f;                       // RSN
+    float lam = 0.f, sgm = 0.f;                       // RSN, RSG
     int64_t tb = 0;
     float4 xt0 = xv0;
     float4 xk0 = xv0, mk0 = xv0, z30 = xv0;           // INP: x_kn, the mask, the jump's draw
@@ -682,7 +768,7 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
             cr = p.c_recip[tb]; crm1 = p.c_recipm1[tb]; a1 = p.c1[tb]; a2 = p.c2[tb];
             if constexpr (MS || RSMS) a3 = p.c3[tb];
             else sg = tb > 0 ? p.sigma[tb] : 0.0f;
-            if constexpr (RSN) { lam = p.nsy.lam[tb]; sgm = p.nsy.sgm[tb]; }
+            if constexpr (RSN || RSG) { lam = p.nsy.lam[tb]; sgm = p.nsy.sgm[tb]; }
         }
         const long long i = e4 + tid;
         xv0 = reinterpret_cast<const float4*>(p.x)[i];
@@ -733,6 +819,17 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
                     yv0[j] = p.rst.y[blk * p.n_out + c];
                     mv0[j] = p.rst.mask ? p.rst.mask[blk] : 1.0f;
                 }
+            }
+        }
+        if constexpr (RSG) {                           // y and the mask have one value per block, shared by the three channels
+            const int W = p.rst.W, n = p.rst.n, Wn = W / n;
+            const long long yrow0 = pix0 / (W * n);    // n >= 2: the tile holds whole rows of blocks; n = 1: not used
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int lp = (tid * 4 + j) / 3, row = lp / W, col = lp - row * W;
+                const long long blk = n == 1 ? pix0 + lp : (yrow0 + row / n) * Wn + col / n;
+                yv0[j] = p.rst.y[blk];
+                mv0[j] = p.rst.mask ? p.rst.mask[blk] : 1.0f;
             }
         }
         if constexpr (RST) {
@@ -852,7 +949,7 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
             return;
         }
     }
-    if constexpr (RST || RSTM || RSMS || RSN) {
+    if constexpr (RST || RSTM || RSMS || RSN || RSG) {
         float x0v[4] = {0.f, 0.f, 0.f, 0.f};
         if (tid < cnt4) {
             const float4 ev = reinterpret_cast<const float4*>(es)[tid];
@@ -870,6 +967,14 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int lp = (tid * 4 + j) / p.n_out, c = tid * 4 + j - lp * p.n_out, row = lp / W, col = lp - row * W;
+                if constexpr (RSG) {                   // n_out == 3 (final_tail_ok)
+                    const GrayCoef k = gry_coef(p.rst.gray, n);
+                    const float* grp = es + ((row & ~(n - 1)) * W + (col & ~(n - 1))) * 3;
+                    const float m = gry_group([&](int bi, int bj, int ch) { return grp[(bi * W + bj) * 3 + ch]; }, n, k);
+                    const float ac = c == 0 ? k.a0 : c == 1 ? k.a1 : k.a2;
+                    o[j] = rsn_finish(xa[j], gry_x0p(x0v[j], __fsub_rn(yv0[j], m), mv0[j], lam, ac), mv0[j], za[j], a1, a2, sg, sgm);
+                    continue;
+                }
                 const float* blk = es + ((row & ~(n - 1)) * W + (col & ~(n - 1))) * p.n_out + c;
                 const float m = rst_block_mean([&](int bi, int bj) { return blk[(bi * W + bj) * p.n_out]; }, n);
                 if constexpr (RSN) o[j] = rsn_finish(xa[j], rsn_x0p(x0v[j], m, yv0[j], mv0[j], lam), mv0[j], za[j], a1, a2, sg, sgm);
@@ -922,10 +1027,12 @@ bool final_tail_ok(int HW, int C, int groups, int n_out, int np, StepKind kind, 
     if (C > 128 && kind != StepKind::Eps && kind != StepKind::Ancestral) return false;
     if (groups <= 0 || groups > 64 || C % groups || (C / groups) % 4) return false;
     if (n_out < 1 || n_out > 8 || (128 * n_out) % 4) return false;
+    if (kind == StepKind::RestoreGray && n_out != 3) return false;       // the grey operator is over a pixel's three colours
     // the restore tail forms block means from the tile's x0 in LDS: the 128-pixel tile must hold whole rows of n x n blocks
     // (the masked kind the same for n >= 2; its n = 1 is pointwise)
     const bool blocks = kind == StepKind::Restore ||
-                        ((kind == StepKind::RestoreMasked || kind == StepKind::RestoreMultistep || kind == StepKind::RestoreNoisy) && restore_n != 1);
+                        ((kind == StepKind::RestoreMasked || kind == StepKind::RestoreMultistep || kind == StepKind::RestoreNoisy ||
+                          kind == StepKind::RestoreGray) && restore_n != 1);
     if (blocks && !(restore_w > 0 && restore_n > 0 && 128 % (restore_w * restore_n) == 0)) return false;
     return np > 0 && HW == np * 128 && np * groups <= 1024;
 }
@@ -988,6 +1095,13 @@ int final_tail(const TailIn& in, const StepRule& r, const int64_t* t, const Chai
                         "n in {1,2,4,8} dividing H and W, H*W of the map and no injected noise");
             p.rst = r.rst; p.nsy = r.nsy;
             return launch_tail<StepKind::RestoreNoisy>(p, in.B, st);
+        case StepKind::RestoreGray:
+            DDK_REQUIRE(tables && r.sigma && r.nsy.lam && r.nsy.sgm && !r.noise && r.rst.y && restore_block_ok(r.rst, true) &&
+                            (long long)r.rst.H * r.rst.W == in.HW && (r.rst.gray == GRAY_MEAN || r.rst.gray == GRAY_LUMA),
+                        "final_tail: the grey restore step needs x, t, the tables with lam and sgm, y, n in {1,2,4,8} dividing H and W, H*W of the "
+                        "map, weights 1 or 2 and no injected noise");
+            p.rst = r.rst; p.nsy = r.nsy;
+            return launch_tail<StepKind::RestoreGray>(p, in.B, st);
         case StepKind::Vlb: {
             DDK_REQUIRE(r.vlb && tables && !r.eps_out && h.chain_state, "final_tail: the VLB epilogue needs the sweep's step, x, t, the tables and the chain state");
             const VlbStep& v = *r.vlb;
@@ -1274,6 +1388,17 @@ int p_update(const StepRule& r, const float* eps_hat, const int64_t* t, int B, l
                                n_out, h.seed, h.stream_id, h.chain_state, h.dec_counter);
             return check_launch("p_update_restore_noisy_kernel");
         }
+        case StepKind::RestoreGray: {  // groups of n n 3 elements: a kernel of its own at every n; the mask is optional
+            if (!(r.sigma && r.nsy.lam && r.nsy.sgm && r.rst.y)) return bad("null pointer");
+            if (r.noise) return bad("no injected noise (Philox only)");
+            if (!restore_block_ok(r.rst, true)) return bad("n must be 1, 2, 4 or 8 and divide H and W");
+            if (!(r.rst.gray == GRAY_MEAN || r.rst.gray == GRAY_LUMA)) return bad("weights must be 1 (mean) or 2 (luma)");
+            const long long hw = (long long)r.rst.H * r.rst.W;
+            if (per != hw * 3 || per > INT_MAX) return bad("per must be H * W * 3, below 2^31");
+            hipLaunchKernelGGL(p_update_restore_gray_kernel, dim3(grid1d(B * hw / (r.rst.n * r.rst.n))), dim3(256), 0, st, r, eps_hat, t, B,
+                               h.seed, h.stream_id, h.chain_state, h.dec_counter);
+            return check_launch("p_update_restore_gray_kernel");
+        }
         case StepKind::Vlb:       // no update: the sweep's reduction of the step's terms, a kernel of its own
             if (!r.vlb) return bad("null pointer");
             return vlb_sweep_terms(*r.vlb, t, eps_hat, B, per, h.chain_state, st, h.dec_counter);
@@ -1358,7 +1483,7 @@ int ddk_p_sample_update_restore(float* x, const float* eps_hat, const float* y, 
                                 int channels, uint64_t seed, uint32_t stream_id, ddk_stream_t s) {
     DDK_REQUIRE(B > 0 && H > 0 && W > 0 && channels > 0, "p_sample_update_restore: B / H / W / channels must be positive");
     StepRule r{StepKind::Restore, nullptr, x, nullptr, 0, 0, c_recip, c_recipm1, c1, c2, sigma};
-    r.rst = RestoreOps{y, n, H, W};
+    r.rst = RestoreOps{y, n, H, W, 0, nullptr};
     return p_update(r, eps_hat, t, B, (long long)H * W * channels, ChainHooks{nullptr, nullptr, seed, stream_id}, as_stream(s),
                     "p_sample_update_restore");
 }
@@ -1370,7 +1495,7 @@ int ddk_p_sample_update_restore_masked(float* x, const float* eps_hat, const flo
     DDK_REQUIRE(mask || n != 1, "p_sample_update_restore_masked: n = 1 needs a mask (nothing would be constrained)");
     // no mask: every block is measured, which is the Restore kind, its kernel and its bits
     StepRule r{mask ? StepKind::RestoreMasked : StepKind::Restore, nullptr, x, nullptr, 0, 0, c_recip, c_recipm1, c1, c2, sigma};
-    r.rst = RestoreOps{y, n, H, W, mask};
+    r.rst = RestoreOps{y, n, H, W, 0, mask};
     return p_update(r, eps_hat, t, B, (long long)H * W * channels, ChainHooks{nullptr, nullptr, seed, stream_id}, as_stream(s),
                     "p_sample_update_restore_masked");
 }
@@ -1381,7 +1506,7 @@ int ddk_p_sample_update_restore_multistep(float* x, const float* eps_hat, float*
     DDK_REQUIRE(B > 0 && H > 0 && W > 0 && channels > 0, "p_sample_update_restore_multistep: B / H / W / channels must be positive");
     DDK_REQUIRE(mask || n != 1, "p_sample_update_restore_multistep: n = 1 needs a mask (nothing would be constrained)");
     StepRule r{StepKind::RestoreMultistep, nullptr, x, nullptr, 0, 0, c_recip, c_recipm1, c1, c2, nullptr, x0_hist, c3};
-    r.rst = RestoreOps{y, n, H, W, mask};
+    r.rst = RestoreOps{y, n, H, W, 0, mask};
     return p_update(r, eps_hat, t, B, (long long)H * W * channels, ChainHooks{}, as_stream(s), "p_sample_update_restore_multistep");
 }
 
@@ -1392,10 +1517,24 @@ int ddk_p_sample_update_restore_noisy(float* x, const float* eps_hat, const floa
     DDK_REQUIRE(B > 0 && H > 0 && W > 0 && channels > 0, "p_sample_update_restore_noisy: B / H / W / channels must be positive");
     DDK_REQUIRE(mask || n != 1, "p_sample_update_restore_noisy: n = 1 needs a mask (nothing would be constrained)");
     StepRule r{StepKind::RestoreNoisy, nullptr, x, nullptr, 0, 0, c_recip, c_recipm1, c1, c2, sigma};
-    r.rst = RestoreOps{y, n, H, W, mask};
+    r.rst = RestoreOps{y, n, H, W, 0, mask};
     r.nsy = NoisyTables{lam, sgm};
     return p_update(r, eps_hat, t, B, (long long)H * W * channels, ChainHooks{nullptr, nullptr, seed, stream_id}, as_stream(s),
                     "p_sample_update_restore_noisy");
+}
+
+int ddk_p_sample_update_restore_gray(float* x, const float* eps_hat, const float* y, const float* mask, int n, int weights, const int64_t* t,
+                                     const float* c_recip, const float* c_recipm1, const float* c1, const float* c2, const float* sigma,
+                                     const float* lam, const float* sgm, int B, int H, int W, int channels, uint64_t seed, uint32_t stream_id,
+                                     ddk_stream_t s) {
+    DDK_REQUIRE(B > 0 && H > 0 && W > 0, "p_sample_update_restore_gray: B / H / W must be positive");
+    DDK_REQUIRE(channels == 3, "p_sample_update_restore_gray: the grey operator needs a 3-channel map");
+    DDK_REQUIRE(weights == GRAY_MEAN || weights == GRAY_LUMA, "p_sample_update_restore_gray: weights must be 1 (mean) or 2 (luma)");
+    StepRule r{StepKind::RestoreGray, nullptr, x, nullptr, 0, 0, c_recip, c_recipm1, c1, c2, sigma};
+    r.rst = RestoreOps{y, n, H, W, weights, mask};
+    r.nsy = NoisyTables{lam, sgm};
+    return p_update(r, eps_hat, t, B, (long long)H * W * 3, ChainHooks{nullptr, nullptr, seed, stream_id}, as_stream(s),
+                    "p_sample_update_restore_gray");
 }
 
 int ddk_final_tail(const float* raw, const float* partials, int tiles_per_image, const float* gamma, const float* beta, float eps,

@@ -92,11 +92,12 @@ struct ChainKey {
     int restore_n = 0;                       // StepKind::Restore, RestoreMasked: the block (y and the mask are staged in the workspace; the kind
                                              // says whether a mask is present, so a masked and an unmasked chain never share a graph)
     bool restore_mask = false;               // StepKind::RestoreMultistep, RestoreNoisy, one kind with or without a mask: whether its kernels were given one
+    int restore_gray = 0;                    // StepKind::RestoreGray: the weights (rst.gray), so "mean" and "luma" chains never share a graph
     bool operator==(const ChainKey& o) const {
         for (int i = 0; i < 14; ++i)
             if (bufs[i] != o.bufs[i]) return false;
         return kind == o.kind && ws == o.ws && noise == o.noise && B == o.B && H == o.H && W == o.W && t_start == o.t_start &&
-               device == o.device && pack_epoch == o.pack_epoch && restore_n == o.restore_n && restore_mask == o.restore_mask;
+               device == o.device && pack_epoch == o.pack_epoch && restore_n == o.restore_n && restore_mask == o.restore_mask && restore_gray == o.restore_gray;
     }
 };
 struct SamplerGraph {
@@ -1128,10 +1129,11 @@ struct StepArgs {
 };
 
 // tiles of the final tail when the end of the forward runs as ONE launch (final_tail_kernel), else 0.  cin = the final conv's
-// input channels (dimp[1]).  The Vlb, Multistep, Inpaint, Restore, RestoreMasked, RestoreMultistep and RestoreNoisy kinds take a subset of
-// the shapes (final_tail_ok; the last four's depends on its block, restore_n).
+// input channels (dimp[1]).  The Vlb, Multistep, Inpaint, Restore, RestoreMasked, RestoreMultistep, RestoreNoisy and RestoreGray kinds take
+// a subset of the shapes (final_tail_ok; the last five's depends on its block, restore_n).
 static bool restore_kind(StepKind k) {       // the kinds whose step carries a DDNM constraint (RestoreOps)
-    return k == StepKind::Restore || k == StepKind::RestoreMasked || k == StepKind::RestoreMultistep || k == StepKind::RestoreNoisy;
+    return k == StepKind::Restore || k == StepKind::RestoreMasked || k == StepKind::RestoreMultistep || k == StepKind::RestoreNoisy ||
+           k == StepKind::RestoreGray;
 }
 static int fused_tail_parts(const ddk_unet& u, int B, int H, int W, int cin, StepKind kind, int restore_n = 0) {
     const int chan = u.generic ? pad32(u.cfg.chan) : u.cfg.chan, n_out = u.cfg.in_ch;
@@ -1733,7 +1735,8 @@ namespace ddk {
 // call without a mask is (n = 1: a whole latent plus B H W; n = 2: a quarter of each; n = 4, 8: the Restore kind's quarter latent).
 static size_t chain_extra_floats(const ddk_unet& u, int B, int H, int W, StepKind kind, int restore_n = 0) {
     const size_t n = al4((size_t)B * H * W * u.cfg.in_ch);
-    if (kind == StepKind::RestoreMasked || kind == StepKind::RestoreNoisy) {      // the noisy kind keeps RestoreMasked's layout and size
+    // the noisy and the grey kind keep RestoreMasked's layout and size (the grey y is a third of the place it is given)
+    if (kind == StepKind::RestoreMasked || kind == StepKind::RestoreNoisy || kind == StepKind::RestoreGray) {
         const size_t nn = (size_t)restore_n * restore_n, m = al4(n / nn) + al4((size_t)B * H * W / nn);
         return restore_n > 1 && m < al4(n / 4) ? al4(n / 4) : m;
     }
@@ -1758,6 +1761,7 @@ static size_t sampler_bytes(const ddk_unet* u, int B, int H, int W, int t_start,
 //   RestoreMasked: y and, behind it, the mask, copied in before the first step
 //   RestoreMultistep: the history, zeroed by every call as Multistep's, then y and (when given) the mask, copied in as RestoreMasked's
 //   RestoreNoisy: y and (when given) the mask, where RestoreMasked keeps them
+//   RestoreGray: the one-channel y at the head of RestoreMasked's y, and (when given) the mask where RestoreMasked keeps it
 // The graph key: the kind, every table the step reads and the restore block; the staged operands live in the workspace, which is
 // in the key.
 static int sampler_chain(const ddk_sampler_args* a, const char* who, const int64_t* map, StepRule rule, ddk_stream_t s) {
@@ -1797,6 +1801,15 @@ static int sampler_chain(const ddk_sampler_args* a, const char* who, const int64
             rule.rst.mask = extra + al4(ny);
         }
         rule.rst.y = extra;
+    } else if (rule.kind == StepKind::RestoreGray) {
+        const size_t nn = (size_t)rule.rst.n * rule.rst.n, nm = (size_t)B * H * W / nn;      // y and the mask: one float per block
+        rule.rst.H = H; rule.rst.W = W;
+        DDK_HIP(hipMemcpyAsync(extra, rule.rst.y, nm * sizeof(float), hipMemcpyDeviceToDevice, c.st));
+        if (rule.rst.mask) {
+            DDK_HIP(hipMemcpyAsync(extra + al4(n / nn), rule.rst.mask, nm * sizeof(float), hipMemcpyDeviceToDevice, c.st));
+            rule.rst.mask = extra + al4(n / nn);
+        }
+        rule.rst.y = extra;
     } else if (rule.kind == StepKind::RestoreMultistep) {
         const size_t nn = (size_t)rule.rst.n * rule.rst.n, ny = n / nn, nm = (size_t)B * H * W / nn;
         float* ystage = extra + al4(n);
@@ -1815,15 +1828,16 @@ static int sampler_chain(const ddk_sampler_args* a, const char* who, const int64
     // one reverse step: bookkeeping (in the forward's first kernel), UNet, the rule (in its last kernel)
     auto one_step = [&]() -> int { return c.forward(a->x, &step); };
 
-    // the RestoreNoisy tables share the Inpaint operands' storage (StepRule): each kind's key names its own
-    const bool noisy = rule.kind == StepKind::RestoreNoisy;
+    // the RestoreNoisy / RestoreGray tables share the Inpaint operands' storage (StepRule): each kind's key names its own
+    const bool noisy = rule.kind == StepKind::RestoreNoisy || rule.kind == StepKind::RestoreGray;
     const InpaintOps ik = noisy ? InpaintOps{} : rule.inp;
     const NoisyTables nk = noisy ? rule.nsy : NoisyTables{};
     const ChainKey key{rule.kind,
                        {a->packed, a->x, rule.c_recip, rule.c_recipm1, rule.c1, rule.c2, rule.sigma, rule.c3, ik.ka, ik.kb, ik.ja, ik.jb, nk.lam,
                         nk.sgm},
                        a->workspace, a->noise, B, H, W, a->t_start, c.dev, c.u->pack_epoch, restore_kind(rule.kind) ? rule.rst.n : 0,
-                       (rule.kind == StepKind::RestoreMultistep || rule.kind == StepKind::RestoreNoisy) && rule.rst.mask != nullptr};
+                       (rule.kind == StepKind::RestoreMultistep || noisy) && rule.rst.mask != nullptr,
+                       rule.kind == StepKind::RestoreGray ? rule.rst.gray : 0};
     return run_chain(*c.u, key, n_steps, a->use_graph != 0, one_step, c.st, who);
 }
 }  // namespace ddk
@@ -1922,7 +1936,7 @@ extern "C" int ddk_sampler_run_restore(const ddk_sampler_args* a, const int64_t*
     DDK_TRY(check_timestep_map(timestep_map, a->t_start, "sampler_restore"));
     StepRule rule{};
     rule.kind = StepKind::Restore;
-    rule.rst = RestoreOps{y, n, a->H, a->W};
+    rule.rst = RestoreOps{y, n, a->H, a->W, 0, nullptr};
     return sampler_chain(a, "sampler_restore", timestep_map, rule, s);
 }
 
@@ -1957,7 +1971,7 @@ extern "C" int ddk_sampler_run_restore_masked(const ddk_sampler_args* a, const i
     }
     StepRule rule{};
     rule.kind = mask ? StepKind::RestoreMasked : StepKind::Restore;
-    rule.rst = RestoreOps{y, n, a->H, a->W, mask};
+    rule.rst = RestoreOps{y, n, a->H, a->W, 0, mask};
     return sampler_chain(a, "sampler_restore_masked", timestep_map, rule, s);
 }
 
@@ -1988,7 +2002,7 @@ extern "C" int ddk_sampler_run_restore_multistep(const ddk_sampler_args* a, cons
     StepRule rule{};
     rule.kind = StepKind::RestoreMultistep;
     rule.c3 = c3;
-    rule.rst = RestoreOps{y, n, a->H, a->W, mask};
+    rule.rst = RestoreOps{y, n, a->H, a->W, 0, mask};
     return sampler_chain(a, "sampler_restore_multistep", timestep_map, rule, s);
 }
 
@@ -2019,8 +2033,40 @@ extern "C" int ddk_sampler_run_restore_noisy(const ddk_sampler_args* a, const in
     StepRule rule{};
     rule.kind = StepKind::RestoreNoisy;
     rule.nsy = NoisyTables{lam, sgm};
-    rule.rst = RestoreOps{y, n, a->H, a->W, mask};
+    rule.rst = RestoreOps{y, n, a->H, a->W, 0, mask};
     return sampler_chain(a, "sampler_restore_noisy", timestep_map, rule, s);
+}
+
+// ------------------------------------------------------------------------------------------------ colourisation, grey super-resolution
+// DDNM / DDNM+ for A = mask o pool_n o grey_w on a 3-channel pixel model: ddk_sampler_run_restore_noisy's chain,
+// tables and workspace, every step ending in StepKind::RestoreGray.  y and the mask are [B][H/n][W/n]; the mask is optional at every n.
+// The graph key carries the kind, lam and sgm (among its buffers), n, whether a mask was given and the weights.
+extern "C" size_t ddk_sampler_restore_gray_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start, int n) {
+    if (!(n == 1 || n == 2 || n == 4 || n == 8)) return 0;
+    return sampler_bytes(u, B, H, W, t_start, StepKind::RestoreGray, n);
+}
+
+extern "C" int ddk_sampler_restore_gray_tail_parts(const ddk_unet* u, int B, int H, int W, int n) {
+    if (check_shape(u, B, H, W) != DDK_OK || !(n == 1 || n == 2 || n == 4 || n == 8)) return -1;
+    return fused_tail_parts(*u, B, H, W, u->dimp[1], StepKind::RestoreGray, n);
+}
+
+extern "C" int ddk_sampler_run_restore_gray(const ddk_sampler_args* a, const int64_t* timestep_map, const float* lam, const float* sgm,
+                                            const float* y, const float* mask, int n, int weights, ddk_stream_t s) {
+    DDK_REQUIRE(a && a->unet && a->packed && a->x && a->workspace && y, "sampler_restore_gray: null pointer");
+    DDK_REQUIRE(a->c_recip && a->c_recipm1 && a->c1 && a->c2 && a->sigma && lam && sgm, "sampler_restore_gray: null schedule table");
+    DDK_REQUIRE(!a->noise, "sampler_restore_gray: injected noise is not supported, noise must be NULL (Philox only)");
+    DDK_REQUIRE(a->unet->cfg.in_ch == 3, "sampler_restore_gray: the grey operator needs a 3-channel model");
+    DDK_REQUIRE(weights == GRAY_MEAN || weights == GRAY_LUMA, "sampler_restore_gray: weights must be 1 (mean) or 2 (luma)");
+    DDK_REQUIRE(a->t_start >= a->t_end && a->t_end >= 0, "sampler_restore_gray: need t_start >= t_end >= 0");
+    DDK_REQUIRE((n == 1 || n == 2 || n == 4 || n == 8) && a->H > 0 && a->W > 0 && a->H % n == 0 && a->W % n == 0,
+                "sampler_restore_gray: n must be 1, 2, 4 or 8 and divide H and W");
+    DDK_TRY(check_timestep_map(timestep_map, a->t_start, "sampler_restore_gray"));
+    StepRule rule{};
+    rule.kind = StepKind::RestoreGray;
+    rule.nsy = NoisyTables{lam, sgm};
+    rule.rst = RestoreOps{y, n, a->H, a->W, weights, mask};
+    return sampler_chain(a, "sampler_restore_gray", timestep_map, rule, s);
 }
 
 // ------------------------------------------------------------------------------------------------ likelihood sweep

@@ -85,6 +85,8 @@ class PackJob(C.Structure):
 _P, _I, _LL, _F, _SZ = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_size_t
 
 # name -> (restype, argtypes); every symbol include/ddk.h declares
+GRAY_WEIGHTS = {"mean": 1, "luma": 2}      # the `weights` argument of the restore_gray entries (csrc/ddk_internal.h GRAY_MEAN, GRAY_LUMA)
+
 SIGNATURES = {
     "ddk_version": (_I, []),
     "ddk_last_error": (C.c_char_p, []),
@@ -156,6 +158,7 @@ SIGNATURES = {
     "ddk_p_sample_update_restore_masked": (_I, [_P, _P, _P, _P, _I] + [_P] * 6 + [_I, _I, _I, _I, C.c_uint64, C.c_uint32, _P]),
     "ddk_p_sample_update_restore_multistep": (_I, [_P, _P, _P, _P, _P, _I] + [_P] * 6 + [_I, _I, _I, _I, _P]),
     "ddk_p_sample_update_restore_noisy": (_I, [_P, _P, _P, _P, _I] + [_P] * 8 + [_I, _I, _I, _I, C.c_uint64, C.c_uint32, _P]),
+    "ddk_p_sample_update_restore_gray": (_I, [_P, _P, _P, _P, _I, _I] + [_P] * 8 + [_I, _I, _I, _I, C.c_uint64, C.c_uint32, _P]),
     "ddk_randn": (_I, [_P, _LL, C.c_uint64, C.c_uint32, C.c_uint32, _P]),
     "ddk_fix_samples": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "ddk_sq_err_sum": (_I, [_P, _P, _P, _I, _LL, _P]),
@@ -204,6 +207,9 @@ SIGNATURES = {
     "ddk_sampler_restore_noisy_workspace_bytes": (_SZ, [_P, _I, _I, _I, _I, _I]),
     "ddk_sampler_restore_noisy_tail_parts": (_I, [_P, _I, _I, _I, _I]),
     "ddk_sampler_run_restore_noisy": (_I, [C.POINTER(SamplerArgs), C.POINTER(C.c_int64), _P, _P, _P, _P, _I, _P]),
+    "ddk_sampler_restore_gray_workspace_bytes": (_SZ, [_P, _I, _I, _I, _I, _I]),
+    "ddk_sampler_restore_gray_tail_parts": (_I, [_P, _I, _I, _I, _I]),
+    "ddk_sampler_run_restore_gray": (_I, [C.POINTER(SamplerArgs), C.POINTER(C.c_int64), _P, _P, _P, _P, _I, _I, _P]),
     "ddk_sampler_invalidate": (_I, [_P]),
     "ddk_sampler_release_workspace": (_I, [_P, _P]),
     "ddk_vlb_sweep_workspace_bytes": (_SZ, [_P, _I, _I, _I, _I]),

@@ -837,6 +837,26 @@ def p_sample_update_restore_noisy_(x, eps_hat, y, mask, n, t, c_recip, c_recipm1
     return x
 
 
+def p_sample_update_restore_gray_(x, eps_hat, y, mask, n, weights, t, c_recip, c_recipm1, c1, c2, sigma, lam, sgm, seed=0, stream_id=0):
+    """In-place DDNM / DDNM+ step for a grey measurement of x [B,H,W,3] (NHWC) per sample row t[b]:
+    p_sample_update_restore_noisy_'s step with the block mean replaced by the weighted mean of the n x n x 3 group and the correction
+    spread over the channels by A+.  y and mask are [B,H/n,W/n]; mask None: every block measured.  n in {1, 2, 4, 8}; weights "mean"
+    (1/3 each) or "luma" (BT.601)."""
+    b, h, w, c = x.shape
+    n = int(n)
+    if weights not in L.GRAY_WEIGHTS:
+        raise L.DDKError(f"p_sample_update_restore_gray: weights must be 'mean' or 'luma', got {weights!r}")
+    if n < 1 or tuple(y.shape) != (b, h // n, w // n) or tuple(eps_hat.shape) != tuple(x.shape) or \
+            (mask is not None and tuple(mask.shape) != (b, h // n, w // n)):
+        raise L.DDKError(f"p_sample_update_restore_gray: x {tuple(x.shape)}, eps_hat {tuple(eps_hat.shape)}, y {tuple(y.shape)}, "
+                         f"mask {None if mask is None else tuple(mask.shape)}, n = {n}")
+    L.check(L.load().ddk_p_sample_update_restore_gray(L.ptr(_f32(x)), L.ptr(_f32(eps_hat)), L.ptr(_f32(y)),
+                                                      L.ptr(None if mask is None else _f32(mask)), n, L.GRAY_WEIGHTS[weights], L.ptr(t),
+                                                      L.ptr(c_recip), L.ptr(c_recipm1), L.ptr(c1), L.ptr(c2), L.ptr(sigma), L.ptr(lam),
+                                                      L.ptr(sgm), b, h, w, c, seed, stream_id, L.stream()), "p_sample_update_restore_gray")
+    return x
+
+
 def randn(shape, device, seed, step, stream_id=0):
     out = torch.empty(shape, device=device, dtype=torch.float32)
     L.check(L.load().ddk_randn(L.ptr(out), out.numel(), seed, step, stream_id, L.stream()), "randn")

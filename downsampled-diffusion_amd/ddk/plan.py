@@ -28,7 +28,8 @@ SAMPLERS = {"smp": ("sample", "sampler", "sampler"), "sms": ("sample_multistep",
             "srs": ("sample_restore", "sampler_restore", "super-resolution sampler"),
             "srm": ("sample_restore_masked", "sampler_restore_masked", "masked restoration sampler"),
             "srx": ("sample_restore_multistep", "sampler_restore_multistep", "restoration solver"),
-            "srn": ("sample_restore_noisy", "sampler_restore_noisy", "noisy restoration sampler")}
+            "srn": ("sample_restore_noisy", "sampler_restore_noisy", "noisy restoration sampler"),
+            "srg": ("sample_restore_gray", "sampler_restore_gray", "colourisation sampler")}
 # workspace kinds whose captured step graphs point into them (the samplers', the likelihood sweep's): UnetPlan._workspace keeps up
 # to 3 of each
 CHAIN_WORKSPACES = (*SAMPLERS, "vsw")
@@ -92,8 +93,8 @@ class UnetPlan:
         reconstruct() (t_start = t_rec_max) at every logging event keeps both sets of graphs instead of re-capturing twice per event.
         Only an eviction drops the plan's cached graphs (ddk_sampler_invalidate waits for the device).  The likelihood sweep's
         workspaces ("vsw"), the multistep sampler's ("sms"), the inpainting sampler's ("sin"), the super-resolution sampler's
-        ("srs"), the masked restoration sampler's ("srm"), the restoration solver's ("srx") and the noisy restoration sampler's ("srn")
-        are kept the same way: their captured steps point into them too."""
+        ("srs"), the masked restoration sampler's ("srm"), the restoration solver's ("srx"), the noisy restoration sampler's ("srn") and the
+        colourisation sampler's ("srg") are kept the same way: their captured steps point into them too."""
         key = (kind, nbytes, str(device))
         hit = self._ws.get(key)
         if hit is not None:
@@ -475,6 +476,45 @@ class UnetPlan:
 
         return self._run_sampler("srn", x, t_start, t_end,
                                  lambda b, h, w: lib.ddk_sampler_restore_noisy_workspace_bytes(self.handle, b, h, w, t_start, int(n)),
+                                 call, use_graph)
+
+    def restore_gray_tail_parts(self, b, h, w, n):
+        """Tiles per image of the fused tail of a colourisation step on [b, h, w] with block n (1 included), or 0 (always 0 for a
+        model that does not have 3 channels)."""
+        return int(self._lib.ddk_sampler_restore_gray_tail_parts(self.handle, b, h, w, int(n)))
+
+    def sample_restore_gray_nhwc(self, x, y, mask, n, weights, tables, t_start, t_end=0, seed=0, stream_id=0, use_graph=True,
+                                 timesteps=None):
+        """DDNM / DDNM+ steps for a grey measurement, A = mask o (n x n average pooling) o grey_w, t_start .. t_end (inclusive), in
+        place on x [B,H,W,3] (ddk_sampler_run_restore_gray).
+
+        y, mask: contiguous fp32 [B,H/n,W/n] (mask None: every block measured, at any n); weights "mean" or "luma"; they are copied
+        into the plan's "srg" workspace by every call.  tables: sample_restore_noisy_nhwc's, "lam" and "sgm" included
+        (respace.gray_tables); the tables, n, the mask's presence and the weights are in the graph key.  Philox only."""
+        self._need_packed("srg")
+        b, h, w, c = x.shape
+        if c != 3:
+            raise L.DDKError(f"sample_restore_gray: the grey operator needs a 3-channel map, got {c} channels")
+        if weights not in L.GRAY_WEIGHTS:
+            raise L.DDKError(f"sample_restore_gray: weights must be 'mean' or 'luma', got {weights!r}")
+        if n not in (1, 2, 4, 8) or h % n or w % n:
+            raise L.DDKError(f"sample_restore_gray: n must be 1, 2, 4 or 8 and divide H = {h} and W = {w}, got {n}")
+        for name, v in (("y", y), ("mask", mask)):
+            if v is not None and (tuple(v.shape) != (b, h // n, w // n) or v.dtype != torch.float32 or not v.is_contiguous()):
+                raise L.DDKError(f"{name} must be a contiguous fp32 [{b},{h // n},{w // n}] tensor, got {tuple(v.shape)} {v.dtype}")
+        for name in ("lam", "sgm"):
+            if tuple(tables[name].shape) != tuple(tables["c1"].shape) or tables[name].dtype != torch.float32:
+                raise L.DDKError(f"tables[{name!r}] must be an fp32 tensor with one entry per row of c1, got {tuple(tables[name].shape)}")
+        lib = self._lib
+        tmap = self._timestep_map(timesteps, t_start)
+
+        def call(x, ws, nbytes, stream_ptr):
+            a = self._sampler_args(x, None, tables, t_start, t_end, seed, stream_id, use_graph, ws, nbytes)
+            L.check(lib.ddk_sampler_run_restore_gray(C.byref(a), tmap, L.ptr(tables["lam"]), L.ptr(tables["sgm"]), L.ptr(y), L.ptr(mask),
+                                                     int(n), L.GRAY_WEIGHTS[weights], stream_ptr), "sampler_run_restore_gray")
+
+        return self._run_sampler("srg", x, t_start, t_end,
+                                 lambda b, h, w: lib.ddk_sampler_restore_gray_workspace_bytes(self.handle, b, h, w, t_start, int(n)),
                                  call, use_graph)
 
     # ---------------------------------------------------------------- likelihood sweep

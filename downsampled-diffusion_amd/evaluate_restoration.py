@@ -21,6 +21,11 @@ through utils/data.py; ``--max_batches`` keeps the first max_batches * batch_siz
     ``--seed``, is added to the measurement in its [-1, 1] scale after degrading; ``model.restore_noisy`` (DDNM+) restores it, the
     baselines see the same noisy measurement, ``method`` reads ``ddnm_plus``, the settings gain ``sigma_y``, and the consistency
     becomes the RMS of pool(x_out) - y_clean over the measured pixels in uint8 levels.  ``--sigma_y 0`` changes nothing.
+  * ``--task colorize`` (3-channel DDPM checkpoints; section 3.11): the images are greyed with ``--weights`` (``mean`` or ``luma``)
+    and average-pooled by ``--scale`` (default 1: plain colourisation), ``--mask`` applies to that measurement, ``model.colorize``
+    restores it with ``--timestep_respacing``, ``--use_ddim``, ``--eta`` and ``--sigma_y``.  Baselines: the grey image copied into
+    the three channels, replicated or bicubic-upsampled at ``--scale`` > 1.  The consistency is max |A(x_out) - y| in uint8 levels
+    (with ``--sigma_y``: the RMS against the clean y); ``method`` reads ``ddnm_gray`` and the settings gain ``weights``.
   * batch g draws x_T and its Philox key from ``--seed`` + g.
 
 Prints one JSON object, the settings that produced it (among them ``method`` and ``unet_forwards``, the UNet forwards per image, so
@@ -35,7 +40,7 @@ import time
 import numpy as np
 import torch
 
-from utils.restoration_metrics import MASKS, METHODS, TASKS, evaluate_restoration, load_mask, report, to_u8
+from utils.restoration_metrics import GRAY_WEIGHTS, MASKS, METHODS, TASKS, evaluate_restoration, load_mask, report, to_u8
 
 
 def parse_args(argv=None):
@@ -47,7 +52,8 @@ def parse_args(argv=None):
     ap.add_argument("--mask", default=None, help=f"one of {', '.join(MASKS)} or a .npy file of {{0, 1}} (1 = known); inpaint: default "
                                                  "center; sr: masked super-resolution, the mask is of the pooled image (default: none)")
     ap.add_argument("--method", default=None, choices=METHODS, help="inpaint: repaint (default) or ddnm; sr: ddnm")
-    ap.add_argument("--scale", type=int, default=4, help="sr: the pooling factor")
+    ap.add_argument("--scale", type=int, default=None, help="sr: the pooling factor (default 4); colorize: default 1")
+    ap.add_argument("--weights", default=None, choices=tuple(GRAY_WEIGHTS), help="colorize: the grey image's channel weights (default mean)")
     ap.add_argument("--timestep_respacing", default="", help='run K of the T steps: "N", "n1,n2,..." sections or (sr) "ddimN"')
     ap.add_argument("--use_ddim", action="store_true", help="sr: DDIM steps instead of ancestral ones")
     ap.add_argument("--eta", type=float, default=0.0, help="sr: DDIM noise scale (0: deterministic)")
@@ -66,13 +72,29 @@ def parse_args(argv=None):
         ap.error("--batch_size and --max_batches must be >= 1")
     if args.method is None:
         args.method = "repaint" if args.task == "inpaint" else "ddnm"
+    if args.weights is not None and args.task != "colorize":
+        ap.error("--weights belongs to --task colorize")
     if args.task == "sr":
+        if args.scale is None:
+            args.scale = 4
         if args.method != "ddnm":
             ap.error("--task sr has one method, ddnm")
         if args.scale < 2:
             ap.error("--scale must be >= 2")
-    elif args.mask is None:
-        args.mask = "center"
+    elif args.task == "colorize":
+        if args.scale is None:
+            args.scale = 1
+        if args.weights is None:
+            args.weights = "mean"
+        if args.method != "ddnm" or args.dpm_solver:
+            ap.error("--task colorize has one method, ddnm on ancestral or DDIM steps")
+        if args.scale not in (1, 2, 4, 8):
+            ap.error("--scale must be 1, 2, 4 or 8")
+    else:
+        if args.scale is None:
+            args.scale = 4
+        if args.mask is None:
+            args.mask = "center"
     if not np.isfinite(args.sigma_y) or args.sigma_y < 0:
         ap.error("--sigma_y must be a finite number >= 0")
     if args.method == "ddnm":
@@ -97,8 +119,10 @@ def parse_args(argv=None):
 def chain_options(args):
     """the task's keywords for evaluate_restoration, also the chain settings the result records"""
     kw = dict(respacing=args.timestep_respacing or None)
-    if args.task == "sr":
+    if args.task in ("sr", "colorize"):
         kw.update(scale=args.scale)
+    if args.task == "colorize":
+        kw.update(weights=args.weights)
     if args.dpm_solver:
         kw.update(dpm_solver=True)
     elif args.method == "ddnm":

@@ -171,6 +171,12 @@ class DownsampleDDPM(DDPM):
                                     lambda y_lat, n_lat, m_lat: self._restore_noisy_loop(y_lat, n_lat, sigma_y, respacing, ddim, eta, x_T, seed,
                                                                                          mask=m_lat))
 
+    def colorize(self, y, mask=None, scale=1, **kwargs):
+        """Not available: the chain runs in the autoencoder's latent, whose channels are not colours, so the grey operator of
+        DDPM.colorize has no meaning there.  A stated limitation, not an approximation: always ValueError."""
+        raise ValueError("colorize: a DownsampleDDPM samples in a latent whose channels are not colours; colourisation needs a "
+                         "3-channel pixel model (DDPM)")
+
     @torch.no_grad()
     def reconstruct(self, x, n):
         """dddpm.py:33-74 (visualisation only)."""

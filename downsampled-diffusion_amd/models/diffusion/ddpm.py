@@ -451,29 +451,34 @@ class DDPM(nn.Module):
         if not torch.is_tensor(y) or y.dim() != 4 or list(y.shape[1:]) != [C, h, w] or not y.is_floating_point():
             raise ValueError(f"restore: y must be a float [B, {C}, {h}, {w}] tensor, got "
                              f"{tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
+        return self._measured_args(y.float(), mask, h, w, "restore")
+
+    @staticmethod
+    def _measured_args(y, mask, h, w, who):
+        """The mask's and the measured pixels' ValueErrors of restore (and of colorize, which takes the same masks): returns (y with
+        the pixels that are not measured set to 0, the mask as {0, 1} floats [B, h, w] or None), on y's device."""
         B = y.shape[0]
-        y = y.float()
         if mask is None:
             if not bool(torch.isfinite(y).all()):
-                raise ValueError("restore: y must be finite")
+                raise ValueError(f"{who}: y must be finite")
             return y, None
         if not torch.is_tensor(mask) or mask.is_complex():
-            raise ValueError("restore: mask must be a real or bool tensor")
+            raise ValueError(f"{who}: mask must be a real or bool tensor")
         m = mask
         if m.dim() == 4 and m.shape[1] == 1:
             m = m[:, 0]
         elif m.dim() == 2:
             m = m.unsqueeze(0)
         if m.dim() != 3 or m.shape[0] not in (1, B) or tuple(m.shape[1:]) != (h, w):
-            raise ValueError(f"restore: mask must be [{h}, {w}], [{B}, {h}, {w}] or [{B}, 1, {h}, {w}], got {tuple(mask.shape)}")
+            raise ValueError(f"{who}: mask must be [{h}, {w}], [{B}, {h}, {w}] or [{B}, 1, {h}, {w}], got {tuple(mask.shape)}")
         if m.dtype != torch.bool and not bool(((m == 0) | (m == 1)).all()):
-            raise ValueError("restore: mask values must be 0 or 1 (or bool)")
+            raise ValueError(f"{who}: mask values must be 0 or 1 (or bool)")
         m = m.to(device=y.device, dtype=torch.float32).expand(B, h, w).contiguous()
         if not bool((m.reshape(B, -1).amax(dim=1) > 0).all()):
-            raise ValueError("restore: every image needs at least one measured pixel (an all-zero mask constrains nothing)")
+            raise ValueError(f"{who}: every image needs at least one measured pixel (an all-zero mask constrains nothing)")
         sel = (m != 0).unsqueeze(1).expand_as(y)
         if not bool(torch.isfinite(y[sel]).all()):
-            raise ValueError("restore: the measured pixels of y must be finite")
+            raise ValueError(f"{who}: the measured pixels of y must be finite")
         return torch.where(sel, y, torch.zeros_like(y)), m
 
     @torch.no_grad()
@@ -619,6 +624,98 @@ class DDPM(nn.Module):
             return self.restore(y, mask, scale, respacing=respacing, ddim=ddim, eta=eta, x_T=x_T, seed=seed, **unsupported)
         y, m = self._restore_noisy_args(y, mask, scale, self.sample_shape, sigma_y, ddim, eta, unsupported, self.RESTORE_SCALES)
         return self._restore_noisy_loop(y, int(scale), sigma_y, respacing, ddim, eta, x_T, seed, mask=m)
+
+    # ------------------------------------------------------------------ DDNM colourisation and grey super-resolution
+    GRAY_WEIGHTS = ("mean", "luma")
+    COLORIZE_UNSUPPORTED = ('solver', 'noise', 'early_stop', 'paste')
+
+    def _gray_tables(self, respacing, ddim, eta, sigma_y):
+        """(restore's tables plus the per-row lam and sgm of a colourisation chain, timestep map or None), cached like _noisy_tables,
+        whose tables these are for sigma_y > 0.  sigma_y == 0: lam = 1 in every row and sgm = the fp32 sigma with row 0 zero
+        (respace.exact_coefficients)."""
+        if sigma_y > 0:
+            return self._noisy_tables(respacing, ddim, eta, sigma_y)
+        if respacing is not None or ddim or eta != 0:
+            return self._cached_tables(('gray', respacing, bool(ddim), float(eta)),
+                                       lambda: respace.gray_tables(self._betas64, respacing, ddim, eta, 0.0))
+
+        def plain():
+            lam, sgm = respace.exact_coefficients(self.posterior_sigma)
+            return dict(self._tables(), lam=lam, sgm=sgm), None
+        return self._cached_tables(('gray', None, False, 0.0), plain)
+
+    def _colorize_args(self, y, mask, scale, weights, sigma_y, ddim, eta, unsupported):
+        """ValueError for anything colorize cannot take, before any device work.  Returns (y as float [B, H/scale, W/scale] with the
+        pixels that are not measured set to 0, the mask as {0, 1} floats of that shape or None, sigma_y as a float)."""
+        if unsupported:
+            raise ValueError(f"colorize: {sorted(unsupported)} not accepted (DDNM runs ancestral or DDIM steps with Philox draws over "
+                             f"the whole schedule and never pastes: no {', '.join(self.COLORIZE_UNSUPPORTED)})")
+        C, H, W = self.sample_shape
+        if C != 3:
+            raise ValueError(f"colorize: needs a 3-channel pixel model, this one has {C} channels")
+        if weights not in self.GRAY_WEIGHTS:
+            raise ValueError(f"colorize: weights must be one of {self.GRAY_WEIGHTS}, got {weights!r}")
+        sigma_y = self._sigma_y_arg(sigma_y, "colorize")
+        if isinstance(scale, bool) or not isinstance(scale, (int, np.integer)) or scale not in self.RESTORE_SCALES:
+            raise ValueError(f"colorize: scale must be an int in {self.RESTORE_SCALES}, got {scale!r}")
+        if isinstance(eta, bool) or not isinstance(eta, (int, float, np.integer, np.floating)) or eta < 0 or (eta != 0 and not ddim):
+            raise ValueError(f"colorize: eta = {eta!r} needs ddim=True and eta >= 0")
+        if sigma_y > 0 and ddim and eta == 0:
+            raise ValueError("colorize: sigma_y > 0 needs a chain that draws (ancestral steps, or ddim with eta > 0): with eta = 0 every "
+                             "row's lam is 0 and nothing would be constrained")
+        if H % scale or W % scale:
+            raise ValueError(f"colorize: scale = {scale} must divide the image size {H} x {W}")
+        h, w = H // scale, W // scale
+        if not torch.is_tensor(y) or y.dim() != 4 or list(y.shape[1:]) != [1, h, w] or not y.is_floating_point():
+            raise ValueError(f"colorize: y must be a float [B, 1, {h}, {w}] tensor, got "
+                             f"{tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
+        y, m = self._measured_args(y.float(), mask, h, w, "colorize")
+        return y[:, 0].contiguous(), m, sigma_y
+
+    def _colorize_loop(self, y, mask, n, weights, sigma_y, respacing, ddim, eta, x_T, seed):
+        """The colourisation chain on y, mask [B, H/n, W/n] (mask None: everywhere): native (UnetPlan.sample_restore_gray_nhwc) or,
+        with native_sampler off, the same op as a Python loop in the same NHWC layout, so both draw the same Philox numbers."""
+        device = self.betas.device
+        if device.type != 'cuda':
+            raise DDKError("colorize: move the model to a ROCm device first (no CPU fallback)")
+        tables, use = self._gray_tables(respacing, ddim, eta, sigma_y)
+        shape = (y.shape[0], *self.sample_shape)
+        if x_T is not None and tuple(x_T.shape) != shape:
+            raise ValueError(f"colorize: x_T must be {shape}, got {tuple(x_T.shape)}")
+        img = torch.randn(shape, device=device) if x_T is None else x_T.to(device).float()
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        k_start = (self.timesteps if use is None else len(use)) - 1
+        yl = y.to(device).float().contiguous()
+        mk = None if mask is None else mask.to(device).float().contiguous()
+        x = ops.nchw_to_nhwc(img.contiguous())
+        if not self.native_sampler:
+            with self._eps_model_nhwc().plan().forwards_as_in_chain():
+                for k in range(k_start, -1, -1):
+                    t_model = k if use is None else use[k]
+                    eps_hat = self.latent_model(ops.nhwc_to_nchw(x), torch.full((shape[0],), t_model, device=device, dtype=torch.long))
+                    ops.p_sample_update_restore_gray_(x, ops.nchw_to_nhwc(eps_hat.contiguous()), yl, mk, n, weights,
+                                                      torch.full((shape[0],), k, device=device, dtype=torch.long), **tables,
+                                                      seed=seed, stream_id=int(self.rng_stream_id))
+            return ops.nhwc_to_nchw(x)
+        self._eps_model_nhwc().plan().sample_restore_gray_nhwc(x, yl, mk, n, weights, tables, k_start, seed=seed,
+                                                               stream_id=int(self.rng_stream_id), use_graph=self.use_graph, timesteps=use)
+        return ops.nhwc_to_nchw(x)
+
+    @torch.no_grad()
+    def colorize(self, y, mask=None, scale=1, *, weights="mean", sigma_y=0.0, respacing=None, ddim=False, eta=0.0, x_T=None, seed=None,
+                 **unsupported):
+        """Zero-shot colourisation and grey super-resolution with DDNM (Wang, Yu, Zhang 2023), for 3-channel
+        pixel models: an image [B, 3, H, W] whose grey value, averaged over scale x scale blocks, equals y [B, 1, H/scale, W/scale]
+        (in [-1, 1]) wherever mask is 1.  weights: "mean" (the three channels averaged, DDNM's own operator) or "luma" (BT.601,
+        0.299 R + 0.587 G + 0.114 B).  scale in {1, 2, 4, 8}; mask as restore's, optional at every scale (None: every pixel of y is
+        measured).  sigma_y > 0: y carries noise of that standard deviation and the steps are DDNM+'s (restore_noisy's tables);
+        with sigma_y == 0 the grey image of the result equals y up to fp32 rounding.  respacing, ddim, eta, x_T, seed: as restore.
+        ValueError, before any device work, for a model that does not have 3 channels, solver / noise / early_stop / paste, unknown
+        weights, a bad sigma_y, scale or eta, sigma_y > 0 on a chain without draws (ddim with eta == 0), a misshapen or non-float y,
+        non-finite measured pixels and every mask restore rejects."""
+        y, m, sigma_y = self._colorize_args(y, mask, scale, weights, sigma_y, ddim, eta, unsupported)
+        return self._colorize_loop(y, m, int(scale), weights, sigma_y, respacing, ddim, eta, x_T, seed)
 
     @torch.no_grad()
     def reconstruct(self, x, n):

@@ -26,6 +26,8 @@ spaced index tau, plus ka / kb (the known image noised to abar_{tau-1}) and ja /
 
 DDNM+ for a noisy measurement (Wang, Yu, Zhang 2023, section 3.3) adds two per-row tables to a spaced chain,
 ``lam`` and ``sgm`` (``noisy_coefficients``): the scale of the DDNM correction and of the draw on measured elements.
+Colourisation and grey super-resolution run on the same two tables (``gray_tables``); for an exact
+measurement they are lam = 1 in every row and sgm = sigma with row 0 zero (``exact_coefficients``).
 """
 import numpy as np
 import torch
@@ -244,6 +246,28 @@ def noisy_tables(betas, spec=None, ddim=False, eta=0.0, sigma_y=0.0):
     c1 = ddim_coefficients(sched['alphas_cumprod'], eta)[0] if ddim else sched['posterior_mean_coef1']
     lam, sgm = noisy_coefficients(c1, tables['sigma'].double().numpy(), sigma_y)
     tables.update(lam=torch.tensor(lam, dtype=torch.float32), sgm=torch.tensor(sgm, dtype=torch.float32))
+    return tables, use
+
+
+def exact_coefficients(sigma32):
+    """fp32 (lam, sgm) with which the step of DESIGN.md section 3.11 holds an exact measurement: lam = 1 in every row, row 0 included
+    (row 0 then returns x0', whose image under A is y up to rounding), and sgm = the fp32 sigma the kernels apply, bit for bit, with
+    row 0 set to 0."""
+    sgm = torch.as_tensor(sigma32, dtype=torch.float32).detach().cpu().clone()
+    sgm[0] = 0.
+    return torch.ones_like(sgm), sgm
+
+
+def gray_tables(betas, spec=None, ddim=False, eta=0.0, sigma_y=0.0):
+    """(spaced_tables' fp32 tables plus the per-row lam and sgm, timestep map) of a colourisation chain:
+    noisy_tables' for sigma_y > 0, exact_coefficients' for sigma_y == 0."""
+    if not np.isfinite(sigma_y) or sigma_y < 0:
+        raise ValueError(f"sigma_y must be a finite number >= 0, got {sigma_y}")
+    if sigma_y > 0:
+        return noisy_tables(betas, spec, ddim, eta, sigma_y)
+    tables, use = spaced_tables(betas, spec, ddim, eta)
+    lam, sgm = exact_coefficients(tables['sigma'])
+    tables.update(lam=lam, sgm=sgm)
     return tables, use
 
 

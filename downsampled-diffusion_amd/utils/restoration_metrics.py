@@ -13,8 +13,9 @@ import numpy as np
 import torch
 
 MASKS = ("center", "left", "half", "lines")
-TASKS = ("inpaint", "sr")
+TASKS = ("inpaint", "sr", "colorize")
 METHODS = ("repaint", "ddnm")
+GRAY_WEIGHTS = {"mean": (1.0 / 3.0, 1.0 / 3.0, 1.0 / 3.0), "luma": (0.299, 0.587, 0.114)}     # DDPM.colorize's two operators
 
 
 # ------------------------------------------------------------------ degradations
@@ -48,6 +49,15 @@ def load_mask(path, n, h, w, c):
 def pool(x, scale):
     """scale x scale average pooling of [N, C, H, W]: the degradation of the super-resolution task (A of section 3.6)."""
     return torch.nn.functional.avg_pool2d(x, scale)
+
+
+def gray(x, weights):
+    """the grey image [N, 1, H, W] of [N, 3, H, W]: the channels' weighted sum (the grey_w of section 3.11)"""
+    if weights not in GRAY_WEIGHTS:
+        raise ValueError(f"unknown weights {weights!r}: one of {tuple(GRAY_WEIGHTS)}")
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError(f"a grey image needs 3 channels, got {tuple(x.shape)}")
+    return (x * x.new_tensor(GRAY_WEIGHTS[weights]).reshape(1, 3, 1, 1)).sum(dim=1, keepdim=True)
 
 
 # ------------------------------------------------------------------ uint8 <-> model range
@@ -103,14 +113,14 @@ def _score(ops, cand_u8, ref_u8, hidden, device):
 
 
 @torch.no_grad()
-def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234, mask="center", scale=4, method=None, sr_mask=None,
+def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234, mask="center", scale=None, method=None, sr_mask=None,
                          dpm_solver=False, sigma_y=0.0, **chain):
     """Degrade, restore and score ``images_uint8`` (uint8 [N, H, W, C] of the model's size).
 
     task "inpaint": ``mask`` is one of MASKS or a {0, 1} tensor broadcastable to [N, 1|C, H, W] (1 = known); ``chain`` goes to
     ``model.inpaint`` (respacing, jump_length, jump_n_sample).  Baseline: mean_fill.  Every method also gets psnr_hidden, the PSNR
     over the hidden pixels only.
-    task "sr": the images are average-pooled by ``scale``; ``chain`` goes to ``model.super_resolve`` (respacing, ddim, eta).
+    task "sr": the images are average-pooled by ``scale`` (default 4); ``chain`` goes to ``model.super_resolve`` (respacing, ddim, eta).
     Baselines: replicate, bicubic.  consistency: per image max |pool(x_out) - y| * 127.5 (uint8 levels) of the model's float output,
     consistency_u8 the same of the uint8 image that is scored (rounding alone may cost 0.5, clamping to [0, 255] more).
     method (default: "repaint" for inpaint, "ddnm" for sr): "ddnm" with task "inpaint" fills with ``model.restore`` at scale 1
@@ -128,6 +138,12 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
     image, the RMS of pool(x_out) - y_clean over the measured pixels in uint8 levels (how far the result is from the clean
     measurement; task "inpaint" gets them too), since the result is not meant to reproduce the noisy one.  sigma_y = 0: exactly
     the result without it.
+    task "colorize" (3-channel pixel models; section 3.11): the images are greyed with ``weights`` ("mean" or "luma") and
+    average-pooled by ``scale`` (1, the default there: plain colourisation); ``sr_mask`` applies to that measurement as in task
+    "sr"; ``model.colorize`` restores it (``chain``: respacing, ddim, eta), with ``sigma_y`` as above.  Baselines: "replicate", the
+    grey image copied into the three channels (and every pixel repeated scale x scale), and at scale > 1 "bicubic".  consistency /
+    consistency_u8: max |A(x_out) - y| over the measured pixels in uint8 levels (with sigma_y: the RMS against the clean y).  The
+    returned method is "ddnm_gray", and "weights" is returned.
     Batch g draws x_T and its Philox key from seed + g, as the sampling CLIs do.
 
     "method" and "unet_forwards" (UNet forwards per image: the chain's steps; the batch shares each forward) are returned too.
@@ -136,6 +152,11 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
     from ddk import ops
     if task not in TASKS:
         raise ValueError(f"unknown task {task!r}: one of {TASKS}")
+    if task == "colorize":
+        return _evaluate_colorize(model, images_uint8, batch_size=batch_size, seed=seed, scale=1 if scale is None else scale, method=method,
+                                  sr_mask=sr_mask, dpm_solver=dpm_solver, sigma_y=sigma_y, **chain)
+    if "weights" in chain:
+        raise ValueError("weights belongs to task 'colorize'")
     x_all = from_u8(images_uint8)
     ref = torch.as_tensor(images_uint8).contiguous()
     n, c, h, w = x_all.shape
@@ -180,7 +201,7 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
         images["mean_fill"] = to_u8(mean_fill(x_meas if sigma_y else x_all, m_all))
         hidden = (m_all.amin(dim=1) == 0).to(torch.uint8).contiguous()
     else:
-        scale = int(scale)
+        scale = 4 if scale is None else int(scale)
         if scale < 2 or h % scale or w % scale:
             raise ValueError(f"scale {scale} must be >= 2 and divide the image size {h} x {w}")
         y_all = pool(x_all, scale)
@@ -220,6 +241,57 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
         extra["consistency_u8"] = (((pool(from_u8(images["restored"]), scale) - y_all) * meas).abs().amax(dim=(1, 2, 3)) * 127.5).double().numpy()
     methods = {name: _score(ops, img, ref, hidden, device) for name, img in images.items()}
     return dict(n_images=n, method=method + ("_dpmpp2m" if dpm_solver else "_plus" if sigma_y else ""), methods=methods, images={k: v.numpy() for k, v in images.items()}, **extra)
+
+
+@torch.no_grad()
+def _evaluate_colorize(model, images_uint8, *, batch_size, seed, scale, method, sr_mask, dpm_solver, sigma_y, weights="mean", **chain):
+    """evaluate_restoration's task "colorize" (see there)"""
+    from ddk import ops
+    x_all = from_u8(images_uint8)
+    ref = torch.as_tensor(images_uint8).contiguous()
+    n, c, h, w = x_all.shape
+    if n < 1 or batch_size < 1:
+        raise ValueError("evaluate_restoration needs at least one image and batch_size >= 1")
+    if method not in (None, "ddnm") or dpm_solver:
+        raise ValueError("task 'colorize' has one method, ddnm on ancestral or DDIM steps (no RePaint, no dpm_solver)")
+    if isinstance(sigma_y, bool) or not isinstance(sigma_y, (int, float, np.integer, np.floating)) or not math.isfinite(sigma_y) or sigma_y < 0:
+        raise ValueError(f"sigma_y must be a finite real number >= 0, got {sigma_y!r}")
+    sigma_y = float(sigma_y)
+    scale = int(scale)
+    if scale < 1 or h % scale or w % scale:
+        raise ValueError(f"scale {scale} must be >= 1 and divide the image size {h} x {w}")
+    device = model.betas.device
+    A = lambda x: pool(gray(x, weights), scale) if scale > 1 else gray(x, weights)
+    y_all = A(x_all)
+    y_meas = y_all + sigma_y * torch.randn(y_all.shape, generator=torch.Generator().manual_seed(seed)) if sigma_y else y_all
+    K = len(model._spaced_tables(chain.get("respacing"), chain.get("ddim", False), chain.get("eta", 0.0))[1]) \
+        if chain.get("respacing") is not None or chain.get("ddim") else int(model.timesteps)
+    my_all, y_base = None, y_meas
+    if sr_mask is not None:
+        hs, ws = h // scale, w // scale
+        my_all = make_mask(sr_mask, n, hs, ws) if isinstance(sr_mask, str) else torch.as_tensor(sr_mask).float().expand(n, -1, hs, ws)
+        my_all = my_all.amin(dim=1, keepdim=True)
+        y_base = mean_fill(y_meas, my_all)                # the baselines see the same holes
+    images = {"replicate": to_u8(replicate(y_base, scale).expand(-1, 3, -1, -1))}
+    if scale > 1:
+        images["bicubic"] = to_u8(bicubic(y_base, scale).expand(-1, 3, -1, -1))
+    outs = []
+    for g, i in enumerate(range(0, n, batch_size)):
+        torch.manual_seed(seed + g)               # x_T and the Philox key of batch g
+        mk = None if my_all is None else my_all[i:i + batch_size, 0].to(device)
+        outs.append(model.colorize(y_meas[i:i + batch_size].to(device), mk, scale, weights=weights, sigma_y=sigma_y, **chain).float().cpu())
+    x_out = torch.cat(outs)
+    images = dict(restored=to_u8(x_out), **images)
+    meas = torch.ones_like(y_all) if my_all is None else my_all
+    extra = dict(unet_forwards=K, weights=weights)
+    if sigma_y:
+        rms = lambda x: (((A(x) - y_all) ** 2 * meas).sum(dim=(1, 2, 3)) / meas.sum(dim=(1, 2, 3)).clamp(min=1)).sqrt() * 127.5
+        extra.update(consistency=rms(x_out).double().numpy(), consistency_u8=rms(from_u8(images["restored"])).double().numpy(), sigma_y=sigma_y)
+    else:
+        dev = lambda x: (((A(x) - y_all) * meas).abs().amax(dim=(1, 2, 3)) * 127.5).double().numpy()
+        extra.update(consistency=dev(x_out), consistency_u8=dev(from_u8(images["restored"])))
+    methods = {name: _score(ops, img, ref, None, device) for name, img in images.items()}
+    return dict(n_images=n, method="ddnm_gray", methods=methods, images={k: v.numpy() for k, v in images.items()}, **extra)
 
 
 def report(result):

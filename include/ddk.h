@@ -343,6 +343,22 @@ int ddk_p_sample_update_restore_noisy(float* x, const float* eps_hat, const floa
                                       const float* c_recip, const float* c_recipm1, const float* c1, const float* c2, const float* sigma,
                                       const float* lam, const float* sgm, int B, int H, int W, int channels, uint64_t seed, uint32_t stream_id,
                                       ddk_stream_t s);
+/* One DDNM / DDNM+ step for a grey measurement of a 3-channel map on its own (ddk_sampler_run_restore_gray):
+ * A = mask o (n x n average pooling) o grey_w, y and mask [B][H/n][W/n], weights 1 ("mean", w = 1/3 each) or 2 ("luma", BT.601
+ * w = 0.299, 0.587, 0.114).  Per sample b with row t[b] of the tables of ddk_p_sample_update_restore_noisy:
+ *   x0_c = clamp(c_recip x - c_recipm1 eps_hat, -1, 1);  s = t > 0 ? sigma : 0;
+ *   g = sum over the block, row-major, channel innermost, of W_c x0_c;  m = g NORM;  d = y[block] - m;
+ *   measured:      x0'_c = x0_c + lam (A_c d);   x = (c1 x0'_c + c2 x) + sgm z;
+ *   not measured:  x0'_c = x0_c;                 x = (c1 x0'_c + c2 x) + s z.
+ *   mean: W_c = A_c = 1, NORM = 1 / (3 n n);  luma: W_c = w_c, NORM = 1 / (n n), A_c = w_c / (w . w).
+ * Both arms are selects on the mask: NaN in unmeasured y reaches nothing.  Every operation is rounded on its own; z is the Philox draw
+ * of ddk_p_sample_update_restore.  n in {1, 2, 4, 8}; mask may be NULL at every n (every block measured).  channels != 3, weights
+ * outside {1, 2} and any other n are DDK_ERR_ARG.  H * W * 3 must be a multiple of 4 (below 2^31); x and eps_hat 16-byte aligned.  On
+ * an error x is not touched. */
+int ddk_p_sample_update_restore_gray(float* x, const float* eps_hat, const float* y, const float* mask, int n, int weights, const int64_t* t,
+                                     const float* c_recip, const float* c_recipm1, const float* c1, const float* c2, const float* sigma,
+                                     const float* lam, const float* sgm, int B, int H, int W, int channels, uint64_t seed, uint32_t stream_id,
+                                     ddk_stream_t s);
 /* The end of a forward in one launch (unet.py:69-72 behind the final Block's conv; ddpm.py:203-227): GroupNorm from the conv's
  * partials -> Mish -> 1x1 projection to n_out <= 8 channels (w [n_out][C], bias [n_out]) -> eps_hat; eps_out and / or x may be
  * given: eps_out [B][HW][n_out] receives eps_hat, x [B][HW][n_out] gets the reverse-step update of ddk_p_sample_update in place
@@ -448,8 +464,8 @@ int ddk_unet_forward(const ddk_unet* u, const void* packed, const float* x, cons
  * ddk_sampler_restore_tail_parts says it can; 0 ends every step in ddk_p_sample_update_restore's kernel behind the forward, as the
  * shapes that cannot do (where the plain forward ends in one launch, that launch leaves eps_hat in the workspace first, so the
  * update sees the same eps_hat).  Bit-identical results either way (tests/test_restore_gpu.py).  The masked chain
- * (ddk_sampler_run_restore_masked), the solver's (ddk_sampler_run_restore_multistep) and the noisy chain
- * (ddk_sampler_run_restore_noisy) obey it too. */
+ * (ddk_sampler_run_restore_masked), the solver's (ddk_sampler_run_restore_multistep), the noisy chain
+ * (ddk_sampler_run_restore_noisy) and the grey chain (ddk_sampler_run_restore_gray) obey it too. */
 #define DDK_OPT_RESTORE_FUSED_TAIL 12
 int ddk_unet_set_option(ddk_unet* u, int option, int value);
 /* Waits for `s`, then reads and clears the sticky give-up count of the launches issued on `workspace` (a ddk_unet_forward or
@@ -593,6 +609,19 @@ size_t ddk_sampler_restore_noisy_workspace_bytes(const ddk_unet* u, int B, int H
 int ddk_sampler_restore_noisy_tail_parts(const ddk_unet* u, int B, int H, int W, int n);
 int ddk_sampler_run_restore_noisy(const ddk_sampler_args* a, const int64_t* timestep_map, const float* lam, const float* sgm, const float* y,
                                   const float* mask, int n, ddk_stream_t s);
+/* Zero-shot colourisation and grey super-resolution on a 3-channel pixel model: DDNM / DDNM+ for A = mask o (n x n average pooling) o
+ * grey_w.  The chain and tables of ddk_sampler_run_restore_noisy, every step being
+ * ddk_p_sample_update_restore_gray's; y and mask are device arrays [B][H/n][W/n], mask NULL at any n: every block measured; weights 1
+ * ("mean") or 2 ("luma").  lam and sgm: t_start + 1 floats each, formed by the caller (exact y: lam = 1 in every row, sgm = sigma with
+ * row 0 zero).  A model with other than 3 channels, weights outside {1, 2} and n outside {1, 2, 4, 8} are DDK_ERR_ARG.  The workspace
+ * (ddk_sampler_restore_gray_workspace_bytes) has ddk_sampler_run_restore_masked's size; y and the mask are copied in before the first
+ * step, outside any captured step.  a->noise must be NULL.  Graphs are cached under a chain kind of their own, with lam, sgm, n, the
+ * presence of a mask and the weights in the key.  DDK_OPT_RESTORE_FUSED_TAIL = 0 forces the unfused tail here too; the two tails are
+ * bit-identical.  ddk_sampler_restore_gray_tail_parts: tiles of the fused tail or 0 (always 0 unless the model has 3 channels). */
+size_t ddk_sampler_restore_gray_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start, int n);
+int ddk_sampler_restore_gray_tail_parts(const ddk_unet* u, int B, int H, int W, int n);
+int ddk_sampler_run_restore_gray(const ddk_sampler_args* a, const int64_t* timestep_map, const float* lam, const float* sgm, const float* y,
+                                 const float* mask, int n, int weights, ddk_stream_t s);
 /* Drops the plan's cached sampler and likelihood-sweep graphs and shift table (waits for the device when graphs exist). */
 int ddk_sampler_invalidate(ddk_unet* u);
 /* Drops only the cached graphs (and shift table) that live in / point into `workspace`, after waiting for the launches of

@@ -26,7 +26,11 @@ each with the decode.
 
 --restore-noisy: the cost of a DDNM+ step for a noisy measurement (sigma_y = 0.1) at n = 1 with the center
 mask (the fused tail; and with the fused tail switched off) and n = 2 with the mask, against an ancestral step of the same respaced
-"50" chain, timed alternately the same way."""
+"50" chain, timed alternately the same way.
+
+--restore-gray: the cost of a colourisation step ("luma" weights, sigma_y = 0, no mask) on a 128-wide
+3-channel pixel DDPM with 32 x 32 images at n = 1 (the fused tail; and with the fused tail switched off) and n = 2, against an
+ancestral step of the same model's respaced "50" chain, timed alternately the same way."""
 import argparse
 import json
 import os
@@ -40,7 +44,7 @@ import torch
 
 import bench
 from ddk import ops
-from models import DownsampleDDPM, Unet
+from models import DDPM, DownsampleDDPM, Unet
 from utils import synthetic as syn
 
 DEV = "cuda"
@@ -57,9 +61,12 @@ def main():
     ap.add_argument("--restore", action="store_true", help="DDNM super-resolution step against an ancestral step, respacing 50")
     ap.add_argument("--restore-masked", action="store_true", help="masked DDNM step (n = 1, 2) against an ancestral step, respacing 50")
     ap.add_argument("--restore-noisy", action="store_true", help="DDNM+ step (n = 1, 2; sigma_y 0.1) against an ancestral step, respacing 50")
+    ap.add_argument("--restore-gray", action="store_true", help="colourisation step (n = 1, 2; luma) against an ancestral step, respacing 50, on a 3-channel pixel model")
     ap.add_argument("--restore-solver", action="store_true", help="DDNM step on the 2M chain (n = 1 center mask, n = 2) against a 2M step, logsnr20")
     args = ap.parse_args()
     torch.cuda.set_device(0)
+    if args.restore_gray:
+        return restore_gray_ab()
     cfg = bench.cfg4()
     model = DownsampleDDPM(cfg, Unet(cfg), DEV, 3)
     model.load_state_dict(syn.fill_state_dict(model.state_dict(), skip=syn.SCHEDULE_KEYS))
@@ -270,6 +277,60 @@ def restore_noisy_ab(chain, plan):
                                            "ancestral_min_max_ms": [round(min(anc), 4), round(max(anc), 4)],
                                            "noisy_min_max_ms": [round(min(rst), 4), round(max(rst), 4)]}
         plan.set_option(plan.OPT_RESTORE_FUSED_TAIL, 1)
+    print(json.dumps(res), flush=True)
+
+
+def restore_gray_ab():
+    """its own model: the grey operator needs three colour channels, which cfg4's 8-channel latent does not have"""
+    K, weights = 50, "luma"
+    cfg = dict(unet_chan=128, unet_in=3, unet_dims=(1, 2, 2, 2), unet_dropout=0.0, image_size=S, T=T, loss_type="simple",
+               beta_schedule="linear", loss_flat="sum")
+    model = DDPM(cfg, Unet(cfg), DEV, 3)
+    model.load_state_dict(syn.fill_state_dict(model.state_dict(), skip=syn.SCHEDULE_KEYS))
+    model = model.to(DEV).eval()
+    plan = model.latent_model.plan()
+    x0 = ops.randn((B, S, S, 3), DEV, seed=1234, step=T, stream_id=0)
+    x = x0.clone()
+    w = torch.tensor([0.299, 0.587, 0.114], device=DEV)
+    g = (x0.clamp(-1, 1) * w).sum(dim=3)                                                    # [B, S, S]
+    ys = {1: g.contiguous(), 2: torch.nn.functional.avg_pool2d(g.unsqueeze(1), 2)[:, 0].contiguous()}
+
+    def chain(kind):
+        x.copy_(x0)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if kind == "anc":
+            sp, use = model._spaced_tables(str(K), False, 0.0)
+            plan.sample_nhwc(x, sp, K - 1, 0, seed=1234, stream_id=0, timesteps=use)
+        else:
+            n = int(kind[len("gray"):])
+            sp, use = model._gray_tables(str(K), False, 0.0, 0.0)
+            plan.sample_restore_gray_nhwc(x, ys[n], None, n, weights, sp, K - 1, seed=1234, stream_id=0, timesteps=use)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    res = {"shape": f"DDPM unet_chan 128, 3x{S}x{S} images, B={B}, T={T}, respacing {K}, colourisation step ({weights}, sigma_y 0, no mask) vs "
+                    "ancestral step", "reps": REPS, "per_n": {}}
+    with torch.no_grad():
+        t_settle = time.perf_counter()
+        while time.perf_counter() - t_settle < 2.0:
+            chain("anc")
+        for n, fused in ((1, True), (2, True), (1, False)):
+            plan.set_option(plan.OPT_RESTORE_FUSED_TAIL, int(fused))
+            tail = "fused" if plan.restore_gray_tail_parts(B, S, S, n) > 0 else "unfused"
+            chain("anc")                                 # captures both chains' graphs outside the timed calls
+            chain(f"gray{n}")
+            anc, rst = [], []
+            for _ in range(REPS):
+                anc.append(chain("anc") / K)
+                rst.append(chain(f"gray{n}") / K)
+            a, r = statistics.median(anc), statistics.median(rst)
+            res["per_n"][f"{n}_{tail}"] = {"ancestral_ms_per_step": round(a, 4), "gray_ms_per_step": round(r, 4),
+                                           "gray_over_ancestral": round(r / a, 4),
+                                           "ancestral_min_max_ms": [round(min(anc), 4), round(max(anc), 4)],
+                                           "gray_min_max_ms": [round(min(rst), 4), round(max(rst), 4)]}
+        plan.set_option(plan.OPT_RESTORE_FUSED_TAIL, 1)
+    assert torch.isfinite(x).all()
     print(json.dumps(res), flush=True)
 
 
