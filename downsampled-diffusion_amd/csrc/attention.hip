@@ -8,6 +8,7 @@
 // to_qkv / to_out run on the MFMA implicit-GEMM kernel (conv_igemm.hip); this file is the part between.
 #include <cstdlib>
 
+#include "cluster_sync.h"
 #include "conv_common.h"
 
 namespace ddk {
@@ -734,6 +735,335 @@ __global__ __launch_bounds__(256) void linattn_small_qkv_kernel(const float* __r
     linattn_small_core<ROWS>(ks, vs, qs, cs, smax, ctx, out, b, h, HW, heads);
 }
 
+// ------------------------------------------------------------------------------------------------
+// to_qkv + core in ONE launch on the 16x16 and 8x8 maps, an (image, head) SPLIT over the pixels: workgroup (half, head, image) does
+// everything between x and the attention output o (blocks.py:57-60, 123, 126-131) for its half of the image's pixels, so all 256 CUs
+// take part at batch 32 and the [M][384] qkv tensor is never written.  Per workgroup (512 threads, ROWS = HW / 2 pixel rows):
+//   * LayerNorm statistics per pixel row, two passes over the row held in registers by four threads (E[x^2] - mean^2 cancels on the
+//     residual stream: linattn_small_qkv_kernel);
+//   * [ROWS x C] x [C x 96] -- the head's q, k, v rows of the LayerNorm-folded weight as the MFMA row operand -- with K streamed in
+//     32-channel chunks through a ring of AS_RING slots by LDS-DMA (the library's XOR swizzle, three chunks in flight); the waves
+//     split K in two inside a chunk (ROWS = 128: wave = (32 pixels, K half), all three of q | k | v; ROWS = 32: wave = (one of
+//     q | k | v, K half), six waves) and the upper half's partial sums meet the lower half's in LDS, lower + upper; then the fold
+//     r acc - r mean c1 + c2;
+//   * the core of linattn_small_kernel on these rows: column maxima of k, __expf, denominators, the unnormalised 32 x 32 context on
+//     the matrix pipe (wave = ROWS / 8 rows, summed in wave order);
+//   * the ONE cross-workgroup step: the half's record {max[32], den[32], ctx[32][32]} goes to memory in the form of cluster_sync.h
+//     (every word stored sc1 by wave 0, which drains before its lane 0 adds to the pair's counter; lane 0 polls with cl_wait_ge, a
+//     workgroup barrier, the partner's record read with sc1 loads, cl_depart re-arms), and BOTH workgroups merge the two records
+//     with linattn_merge_kernel's arithmetic in split order (half 0, then half 1): the same bits in both, stable from run to run;
+//   * o = q ctx for the workgroup's own rows on the matrix pipe; half 0 also writes the normalised context.
+// A give-up (the partner never arrived: cl_wait_ge moved the sticky word and the process-wide count) poisons ctx and o with NaN.
+constexpr int AS_REC = 1152;    // floats per record: 1088 used, whole 128-byte lines
+constexpr int AS_CNT = 32;      // words per (image, head) pair: arrive, depart -- a 128-byte line of their own
+constexpr int AS_RING = 4;
+
+template <int ROWS>
+struct AttnSplitGeom {
+    static_assert(ROWS == 128 || ROWS == 32, "half of a 16x16 or of an 8x8 map");
+    static constexpr int XP = ROWS / 8;                     // 1-KiB DMA pieces of a chunk: the x rows, then the 96 weight rows
+    static constexpr int NP = XP + 12;
+    static constexpr int SLOT = (ROWS + 96) * 32;           // floats per ring slot: x [ROWS][32] | w [96][32]
+    static constexpr int NB = ROWS == 128 ? 3 : 1;          // 32 x 32 blocks per wave
+    static constexpr int UNITS = ROWS == 128 ? 4 : 3;       // waves per K half
+    static constexpr int KPART = UNITS * NB * 16 * 64;      // the upper K half's accumulators
+    static constexpr int SCR = KPART > 8 * 32 * 33 ? KPART : 8 * 32 * 33;   // ... later the eight waves' context partials
+    static constexpr int RING_FL = AS_RING * SLOT;
+    static_assert(SCR + 2 * ROWS * DH + ROWS * (DH + 1) <= RING_FL, "k, v, q of the half live behind the scratch area in the drained ring");
+    static constexpr int TAIL = DH * (DH + 4) + 2 * ROWS + 16 * DH + 16 * DH + DH + 192 + AS_REC + 32;
+    static constexpr int LDS_FL = RING_FL + TAIL;
+};
+
+struct AttnSplitParams {
+    const float* x;      // [B * HW][C]
+    const float* w;      // [384][C]: the LayerNorm-folded to_qkv weight (q rows, k rows, v rows; 4 heads x 32 each)
+    const float* c1;     // [384] fold vectors W g and W b
+    const float* c2;
+    float eps;
+    float* ctx;          // [B][4][32][32]
+    float* out;          // [B * HW][128]
+    unsigned* cnt;       // [B * 4][AS_CNT], zero before the first launch; they re-arm themselves
+    float* rec;          // [B * 4][2][AS_REC]
+    unsigned* fail;      // sticky give-up count (may be null)
+    int C;
+};
+
+__device__ __forceinline__ void wait_vmcnt_le(int n) {      // n wave-uniform; rounds down (waits for more), never up
+    if (n >= 8) wait_vmcnt<8>();
+    else if (n >= 6) wait_vmcnt<6>();
+    else if (n >= 4) wait_vmcnt<4>();
+    else if (n >= 3) wait_vmcnt<3>();
+    else if (n >= 2) wait_vmcnt<2>();
+    else wait_vmcnt<0>();
+}
+
+template <int ROWS>
+__global__ __launch_bounds__(512) void attn_split_kernel(const AttnSplitParams p) {
+    using G = AttnSplitGeom<ROWS>;
+    constexpr int HW = 2 * ROWS, HC = 4 * DH;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* scr = smem;                                  // the drained ring: K-half partials, then the context partials [8][32][33]
+    float* ks = smem + G::SCR;                          // [ROWS][32]
+    float* vs = ks + ROWS * DH;                         // [ROWS][32]
+    float* qs = vs + ROWS * DH;                         // [ROWS][33]
+    float* cs = smem + G::RING_FL;                      // [32][36] the merged, normalised context
+    float* rowstat = cs + DH * (DH + 4);                // [ROWS][2]: r, r * mean
+    float* smax = rowstat + 2 * ROWS;                   // [16][32] column-maximum partials
+    float* dpart = smax + 16 * DH;                      // [16][32] denominator partials
+    float* mx = dpart + 16 * DH;                        // [32]
+    float* cfold = mx + DH;                             // [96] W g | [96] W b of this head's q | k | v columns
+    float* own = cfold + 192;                           // this half's record
+    int* gave_up = reinterpret_cast<int*>(own + AS_REC);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int half = blockIdx.x, h = blockIdx.y, b = blockIdx.z;        // grid (2, 4, B): scalar without a division
+    const int C = p.C, nch = C >> 5;
+    const float* xb = p.x + ((long long)b * HW + half * ROWS) * C;
+    const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) float*)smem;
+
+    // ---- the chunk ring: piece wid + 8 j of a chunk's NP pieces is this wave's
+    const int prow = lane >> 3, ppos = lane & 7;
+    const int npw = (G::NP - wid + 7) >> 3;             // pieces per chunk of this wave
+    unsigned voff[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int pj = wid + 8 * j;
+        const int r = 8 * (pj < G::XP ? pj : pj - G::XP) + prow;                           // row of x, or of the 96-row weight slice
+        const int src = pj < G::XP ? r : (r >> 5) * HC + h * DH + (r & 31);
+        voff[j] = (unsigned)((src * C + ((ppos ^ ((r >> 1) & 7)) << 2)) * 4);
+    }
+    auto issue = [&](int chunk) {
+        const unsigned dst = lds_base + (unsigned)(((chunk & (AS_RING - 1)) * G::SLOT) * 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int pj = wid + 8 * j;
+            if (pj < G::NP) lds_dma16_s(pj < G::XP ? xb : p.w, voff[j] + (unsigned)(chunk * 128), dst + (unsigned)(pj * 1024));
+        }
+    };
+    for (int c = 0; c < AS_RING - 1 && c < nch; ++c) issue(c);
+    if (tid < 192) {
+        const int n = tid % 96;
+        const int col = (n >> 5) * HC + h * DH + (n & 31);
+        cfold[tid] = tid < 96 ? p.c1[col] : p.c2[col];
+    }
+    if (tid < 4 * ROWS) {   // LayerNorm statistics (biased variance, eps added to the std: blocks.py:57-60): 4 threads per row
+        const int row = tid >> 2, sub = tid & 3, n16 = C >> 4;
+        const float4* rp = reinterpret_cast<const float4*>(xb + (long long)row * C);
+        float4 v[16];
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+            if (i < n16) {
+                v[i] = rp[sub + 4 * i];
+                s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
+            }
+        s += __shfl_xor(s, 1, 64);
+        s += __shfl_xor(s, 2, 64);
+        const float inv_c = 1.0f / (float)C;
+        const float mean = s * inv_c;
+        float qq = 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+            if (i < n16) {
+                const float a0 = v[i].x - mean, a1 = v[i].y - mean, a2 = v[i].z - mean, a3 = v[i].w - mean;
+                qq += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
+            }
+        qq += __shfl_xor(qq, 1, 64);
+        qq += __shfl_xor(qq, 2, 64);
+        if (sub == 0) {
+            const float r = 1.0f / (sqrtf(qq * inv_c) + p.eps);
+            rowstat[2 * row] = r;
+            rowstat[2 * row + 1] = r * mean;
+        }
+    }
+
+    // ---- projection: D[slice row][pixel] += W[row][k] X[pixel][k]; accumulator register 4 q + i = slice row 8 q + 4 hl + i of pixel pl
+    const int pl = lane & 31, hl = lane >> 5;
+    const bool active = ROWS == 128 || wid < 6;
+    const int kh = ROWS == 128 ? wid >> 2 : (wid >= 3 ? 1 : 0);        // K half of this wave
+    const int unit = ROWS == 128 ? (wid & 3) : (wid >= 3 ? wid - 3 : wid);      // ROWS = 128: block of 32 pixels; 32: one of q | k | v
+    const int pb = ROWS == 128 ? unit : 0, blk0 = ROWS == 128 ? 0 : unit;
+    f32x16 acc[G::NB];
+#pragma unroll
+    for (int i = 0; i < G::NB; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+    const int fsw = (pl >> 1) & 7;
+    for (int c = 0; c < nch; ++c) {
+        const int later = nch - 1 - c < AS_RING - 2 ? nch - 1 - c : AS_RING - 2;      // chunks behind this one already in flight
+        wait_vmcnt_le(later * npw);
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");               // chunk c has landed; chunk c - 1 is consumed
+        if (c + AS_RING - 1 < nch) issue(c + AS_RING - 1);
+        if (active) {
+            const float* Xs = smem + (c & (AS_RING - 1)) * G::SLOT + pb * (32 * 32);
+            const float* Ws = smem + (c & (AS_RING - 1)) * G::SLOT + ROWS * 32 + blk0 * (32 * 32);
+#pragma unroll
+            for (int q2 = 0; q2 < 2; ++q2) {
+                const int off = pl * 32 + (((2 * (2 * kh + q2) + hl) ^ fsw) << 2);
+                const float4 xv = *reinterpret_cast<const float4*>(Xs + off);
+                float4 wv[G::NB];
+#pragma unroll
+                for (int i = 0; i < G::NB; ++i) wv[i] = *reinterpret_cast<const float4*>(Ws + i * (32 * 32) + off);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float xe = e == 0 ? xv.x : e == 1 ? xv.y : e == 2 ? xv.z : xv.w;
+#pragma unroll
+                    for (int i = 0; i < G::NB; ++i)
+                        acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(e == 0 ? wv[i].x : e == 1 ? wv[i].y : e == 2 ? wv[i].z : wv[i].w, xe, acc[i], 0, 0, 0);
+                }
+            }
+        }
+    }
+    __syncthreads();                                    // the ring is drained
+    if (active && kh == 1) {
+#pragma unroll
+        for (int i = 0; i < G::NB; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) scr[((unit * G::NB + i) * 16 + r) * 64 + lane] = acc[i][r];
+    }
+    __syncthreads();
+    if (active && kh == 0) {   // lower + upper K half, the LayerNorm fold -> q | k | v of the core
+        const int n = pb * 32 + pl;
+        const float r = rowstat[2 * n], rm = rowstat[2 * n + 1];
+#pragma unroll
+        for (int i = 0; i < G::NB; ++i) {
+            const int blk = blk0 + i;                   // 0: q, 1: k, 2: v
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int d0 = 8 * q + 4 * hl;
+                float o4[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float a = acc[i][4 * q + e] + scr[((unit * G::NB + i) * 16 + 4 * q + e) * 64 + lane];
+                    o4[e] = r * a - rm * cfold[blk * 32 + d0 + e] + cfold[96 + blk * 32 + d0 + e];
+                }
+                if (blk == 0) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) qs[n * (DH + 1) + d0 + e] = o4[e];
+                } else {
+                    *reinterpret_cast<float4*>((blk == 1 ? ks : vs) + n * DH + d0) = make_float4(o4[0], o4[1], o4[2], o4[3]);
+                }
+            }
+        }
+    }
+    __syncthreads();
+
+    // ---- the core on this half's rows
+    {
+        const int d = tid & 31, ng = tid >> 5;
+        float m = -INFINITY;
+        for (int n = ng; n < ROWS; n += 16) m = fmaxf(m, ks[n * DH + d]);
+        smax[ng * DH + d] = m;
+        __syncthreads();
+        if (tid < DH) {
+            float mm = smax[tid];
+#pragma unroll
+            for (int j = 1; j < 16; ++j) mm = fmaxf(mm, smax[j * DH + tid]);
+            mx[tid] = mm;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < ROWS / 16; ++j) {
+            const int i = tid + j * 512;
+            ks[i] = __expf(ks[i] - mx[i & 31]);
+        }
+        __syncthreads();
+        float t = 0.f;
+        for (int n = ng; n < ROWS; n += 16) t += ks[n * DH + d];
+        dpart[ng * DH + d] = t;
+    }
+    {   // unnormalised context of this half: wave = ROWS / 8 rows
+        constexpr int RPW = ROWS / 8;
+        f32x16 cacc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) cacc[r] = 0.f;
+        const float* kp = ks + (wid * RPW + hl) * DH + pl;
+        const float* vp = vs + (wid * RPW + hl) * DH + pl;
+#pragma unroll
+        for (int j = 0; j < RPW / 2; ++j) cacc = __builtin_amdgcn_mfma_f32_32x32x2f32(kp[j * 2 * DH], vp[j * 2 * DH], cacc, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) scr[(wid * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl) * 33 + pl] = cacc[r];
+    }
+    __syncthreads();
+    const int md = (tid >> 3) & 31, me0 = (tid & 7) * 4;       // merge threads (the first 256): (d, 4 consecutive e)
+    if (tid < 256) {
+        float den = 0.f;
+#pragma unroll
+        for (int g = 0; g < 16; ++g) den += dpart[g * DH + md];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float t = scr[md * 33 + me0 + e];
+#pragma unroll
+            for (int w = 1; w < 8; ++w) t += scr[(w * 32 + md) * 33 + me0 + e];
+            own[2 * DH + md * DH + me0 + e] = t;
+        }
+        if (me0 == 0) { own[md] = mx[md]; own[DH + md] = den; }
+    }
+    __syncthreads();
+    // ---- the exchange (cluster_sync.h)
+    unsigned* cnt = p.cnt + (b * 4 + h) * AS_CNT;
+    float* rec = p.rec + (long long)(b * 4 + h) * 2 * AS_REC;
+    if (wid == 0) {
+        unsigned* mine = reinterpret_cast<unsigned*>(rec + half * AS_REC);
+#pragma unroll
+        for (int i = 0; i < (2 * DH + DH * DH) / 64; ++i)
+            __hip_atomic_store(mine + lane + 64 * i, __float_as_uint(own[lane + 64 * i]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (lane == 0) {
+            __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            *gave_up = cl_wait_ge<2>(cnt, 2u, p.fail) ? 1 : 0;
+        }
+    }
+    __syncthreads();
+    const bool poisoned = *gave_up != 0;
+    if (tid < 256) {   // linattn_merge_kernel's arithmetic over (half 0, half 1), in both workgroups
+        const unsigned* theirs = reinterpret_cast<const unsigned*>(rec + (half ^ 1) * AS_REC);
+        const float tm = __uint_as_float(__hip_atomic_load(theirs + md, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        const float td = __uint_as_float(__hip_atomic_load(theirs + DH + md, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        float ta[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            ta[e] = __uint_as_float(__hip_atomic_load(theirs + 2 * DH + md * DH + me0 + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        if (tid == 0) cl_depart(cnt, cnt + 1, 2u);
+        const float om = own[md], od = own[DH + md];
+        const float m0 = half ? tm : om, m1 = half ? om : tm;
+        const float d0 = half ? td : od, d1 = half ? od : td;
+        const float M = fmaxf(m0, m1);
+        const float w0 = expf(m0 - M), w1 = expf(m1 - M);
+        float den = 0.f;
+        den += d0 * w0;
+        den += d1 * w1;
+        const float inv = poisoned ? __builtin_nanf("") : 1.0f / den;
+        float c4[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float oa = own[2 * DH + md * DH + me0 + e];
+            const float a0 = half ? ta[e] : oa, a1 = half ? oa : ta[e];
+            float a = 0.f;
+            a += a0 * w0;
+            a += a1 * w1;
+            c4[e] = a * inv;
+            cs[md * (DH + 4) + me0 + e] = c4[e];
+        }
+        if (half == 0) *reinterpret_cast<float4*>(p.ctx + (((long long)b * 4 + h) * DH + md) * DH + me0) = make_float4(c4[0], c4[1], c4[2], c4[3]);
+    }
+    __syncthreads();
+    // ---- o[n][h 32 + e] = sum_d q[n][d] ctx[d][e]: one 32-pixel block per wave
+    if (wid < ROWS / 32) {
+        const int n0 = wid * 32;
+        f32x16 oacc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) oacc[r] = 0.f;
+        const float* qp = qs + (n0 + pl) * (DH + 1) + hl;
+        const float* cp = cs + hl * (DH + 4) + pl;
+#pragma unroll
+        for (int j = 0; j < DH / 2; ++j) oacc = __builtin_amdgcn_mfma_f32_32x32x2f32(qp[2 * j], cp[2 * j * (DH + 4)], oacc, 0, 0, 0);
+        float* op = p.out + ((long long)b * HW + half * ROWS + n0) * HC + h * DH + pl;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) op[((r & 3) + 8 * (r >> 2) + 4 * hl) * HC] = oacc[r];
+    }
+}
+
 // wop[head][chunk][n block 0..5][k half][lane][j] = lnw[o][i]: o = (nb / 2) * HC + head * 32 + (nb % 2) * 16 + lane % 16 (q, k, v
 // columns of the head), i = 32 chunk + 8 (lane / 16) + 4 half + j; lnw = [3 HC][cp] (the LayerNorm-folded to_qkv weight)
 __global__ __launch_bounds__(256) void qkv_operand_pack_kernel(const float* __restrict__ lnw, float* __restrict__ wop, int heads, int cp,
@@ -965,6 +1295,10 @@ int linattn_small_qkv_init_device() {
     DDK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(linattn_small_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     DDK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(linattn_small_qkv_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     DDK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(linattn_small_qkv_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    DDK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_split_kernel<128>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)(AttnSplitGeom<128>::LDS_FL * sizeof(float))));
+    DDK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_split_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)(AttnSplitGeom<32>::LDS_FL * sizeof(float))));
     return DDK_OK;
 }
 
@@ -1023,6 +1357,36 @@ int attn_kvctx(const float* x, const float* w_kv, const float* c1, const float* 
     return check_launch("linattn_merge_kernel");
 }
 
+// ---- to_qkv + core split over the pixels (attn_split_kernel)
+// One dispatch round with a workgroup per CU: the two halves of a pair wait for each other, so every workgroup must be resident
+// (a whole MI355X, conv_wino_cluster_device_ok, and 8 B workgroups <= its 256 CUs)
+constexpr int AS_CUS = 256;
+bool attn_split_ok(int B, int HW, int C, int heads) {
+    return B > 0 && (HW == 64 || HW == 256) && C >= 32 && C <= 256 && C % 32 == 0 && heads == 4 && 8 * (long long)B <= AS_CUS &&
+           conv_wino_cluster_device_ok();
+}
+size_t attn_split_counter_words(int B) { return (size_t)B * 4 * AS_CNT; }
+size_t attn_split_record_floats(int B) { return (size_t)B * 4 * 2 * AS_REC; }
+// a stand-alone workspace: one line for the sticky give-up count, the pair counters, the records
+size_t attn_split_workspace_bytes(int B) { return B > 0 ? (32 + attn_split_counter_words(B) + attn_split_record_floats(B)) * sizeof(float) : 0; }
+unsigned attention_cluster_timeouts() { return cl_timeouts_read(); }
+
+// x [B*HW][C]; w [384][C] the LayerNorm-folded to_qkv weight, c1 / c2 [384] its fold vectors -> ctx [B][4][32][32], out [B*HW][128];
+// counters: attn_split_counter_words(B) words, zero before the first launch (they re-arm); records: attn_split_record_floats(B)
+int attn_split(const float* x, const float* w, const float* c1, const float* c2, float ln_eps, float* ctx, float* out, int B, int HW, int C,
+               unsigned* counters, float* records, unsigned* fail, hipStream_t st) {
+    DDK_REQUIRE(x && w && c1 && c2 && ctx && out && counters && records, "attn_split: null pointer");
+    DDK_REQUIRE(attn_split_ok(B, HW, C, 4), "attn_split: needs H*W of 64 or 256, C % 32 == 0, C <= 256, 4 heads, 8 * B <= the CU count of a whole MI355X");
+    DDK_REQUIRE(aligned16(x) && aligned16(w) && aligned16(ctx) && aligned16(out) && aligned16(counters) && aligned16(records), "attn_split: alignment");
+    DDK_TRY(ensure_device_init());
+    const AttnSplitParams p{x, w, c1, c2, ln_eps, ctx, out, counters, records, fail, C};
+    if (HW == 256)
+        hipLaunchKernelGGL(attn_split_kernel<128>, dim3(2, 4, (unsigned)B), dim3(512), AttnSplitGeom<128>::LDS_FL * sizeof(float), st, p);
+    else
+        hipLaunchKernelGGL(attn_split_kernel<32>, dim3(2, 4, (unsigned)B), dim3(512), AttnSplitGeom<32>::LDS_FL * sizeof(float), st, p);
+    return check_launch("attn_split_kernel");
+}
+
 bool attn_fold_ok(int C, int heads) { return C == FOLD_C && heads * DH == FOLD_C; }
 size_t attn_fold_out_floats(int B) { return (size_t)B * (FOLD_C * FOLD_C + 2 * FOLD_C); }
 
@@ -1063,6 +1427,20 @@ int ddk_attention_kv_context_ok(int B, int HW, int C, int heads) { return ddk::a
 int ddk_attention_kv_context(const float* x, const float* w_kv, const float* c1, const float* c2, float ln_eps, float* ctx, int B, int HW,
                              void* workspace, size_t workspace_bytes, ddk_stream_t s) {
     return ddk::attn_kvctx(x, w_kv, c1, c2, ln_eps, ctx, B, HW, workspace, workspace_bytes, ddk::as_stream(s));
+}
+size_t ddk_attention_split_workspace_bytes(int B) { return ddk::attn_split_workspace_bytes(B); }
+int ddk_attention_split_ok(int B, int HW, int C, int heads) { return ddk::attn_split_ok(B, HW, C, heads) ? 1 : 0; }
+int ddk_attention_split_from_x(const float* x, const float* w_folded, const float* c1, const float* c2, float ln_eps, float* ctx, float* out,
+                               int B, int HW, int C, int heads, void* workspace, size_t workspace_bytes, ddk_stream_t s) {
+    using namespace ddk;
+    DDK_REQUIRE(workspace && B > 0 && heads == 4, "attention_split_from_x: arguments (4 heads)");
+    if (workspace_bytes < attn_split_workspace_bytes(B)) {
+        set_error("attention_split_from_x: workspace too small (%zu < %zu)", workspace_bytes, attn_split_workspace_bytes(B));
+        return DDK_ERR_WORKSPACE;
+    }
+    unsigned* words = static_cast<unsigned*>(workspace);
+    return attn_split(x, w_folded, c1, c2, ln_eps, ctx, out, B, HW, C, words + 32, static_cast<float*>(workspace) + 32 + attn_split_counter_words(B),
+                      words, as_stream(s));
 }
 int ddk_attention_fold(const float* ctx, const float* wqg, const float* c1q, const float* c2q, const float* wout, const float* bout, float* A,
                        float* a1, float* a2, int B, int C, int heads, ddk_stream_t s) {

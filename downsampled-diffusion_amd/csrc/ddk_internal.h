@@ -181,17 +181,20 @@ size_t conv_wino_cluster_ws_floats(int B, int H, int W, int N);
 unsigned conv_wino_cluster_timeouts();
 unsigned conv_first_cluster_timeouts();
 unsigned level_chain_cluster_timeouts();
+unsigned attention_cluster_timeouts();
 // The cluster counter area `cl` of a plan's workspace (unet_plan.hip), in 4-byte words and in this order: [B][8 * 16] counters of the
 // in-launch GroupNorm (16 per (image, n tile), N <= 512: every layer re-arms the same words); one line for the workspace's sticky give-up
 // count (ddk_unet_cluster_check); [B][64] the level chain's arrival and departure counters, a 128-byte line per image each; CL_PAIR_WORDS
-// pair counters of the channel-chunk-split in-launch GroupNorm (<= 128 (m tile, n tile) pairs: 256 workgroups, >= 2 splits); the records.
+// pair counters of the channel-chunk-split in-launch GroupNorm (<= 128 (m tile, n tile) pairs: 256 workgroups, >= 2 splits); [B][4] lines of
+// 32 words, the (image, head) pair counters of the pixel-split attention launch (attn_split_kernel); the records.
 // A ddk_conv3x3_gn_mish_cluster workspace has the first two only: its records start at cl_front_floats().
 constexpr size_t CL_PAIR_WORDS = 128 * 16;
 inline size_t cl_fail_offset(int B) { return (size_t)B * 8 * 16; }
 inline size_t cl_front_floats(int B) { return cl_fail_offset(B) + 16; }
 inline size_t cl_chain_offset(int B) { return cl_front_floats(B); }
 inline size_t cl_pair_offset(int B) { return cl_chain_offset(B) + (size_t)B * 64; }
-inline size_t cl_counter_floats(int B) { return cl_pair_offset(B) + CL_PAIR_WORDS; }      // everything in front of a plan's records
+inline size_t cl_attn_offset(int B) { return cl_pair_offset(B) + CL_PAIR_WORDS; }
+inline size_t cl_counter_floats(int B) { return cl_attn_offset(B) + (size_t)B * 4 * 32; }   // everything in front of a plan's records
 struct ClWords { unsigned* counters; unsigned* fail; };
 inline ClWords cl_words(float* cl, int B) { return {reinterpret_cast<unsigned*>(cl), reinterpret_cast<unsigned*>(cl + cl_fail_offset(B))}; }
 // waits for `st`, then reads and clears a workspace's sticky give-up word: DDK_OK, or DDK_ERR_CLUSTER with the error
@@ -293,6 +296,12 @@ int attn_fold(const float* ctx, const float* wqg, const float* c1q, const float*
               float* a1, float* a2, int B, int C, int heads, hipStream_t st);
 int linattn_apply(const float* qkv, const float* ctx, float* out, int B, int HW, int heads, hipStream_t st);
 int linattn_fused_small(const float* qkv, float* ctx, float* out, int B, int HW, int heads, hipStream_t st);
+// to_qkv + core of one (image, head, half of the pixels) per workgroup on 16x16 / 8x8 maps (attention.hip, attn_split_kernel)
+bool attn_split_ok(int B, int HW, int C, int heads);
+size_t attn_split_counter_words(int B);     // == B * 4 * 32: the plan keeps them at cl_attn_offset()
+size_t attn_split_record_floats(int B);
+int attn_split(const float* x, const float* w, const float* c1, const float* c2, float ln_eps, float* ctx, float* out, int B, int HW, int C,
+               unsigned* counters, float* records, unsigned* fail, hipStream_t st);
 bool linattn_small_qkv_ok(int HW, int C);
 int linattn_small_qkv_init_device();
 int qkv_operand_pack(const float* lnw, float* wop, int heads, int cp, hipStream_t st);

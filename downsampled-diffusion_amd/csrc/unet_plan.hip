@@ -132,6 +132,9 @@ struct ddk_unet {
     bool cluster_split = true;               // ... also on shapes whose channel chunks are split over 2-4 workgroups (conv_wino_cluster_split_np):
                                              // a tile's first workgroup sums its partners' partial tiles in the launch (diagnostic option 11)
     bool attn_kvctx = true;                  // folded attention block: k, v projection + context in one launch (no kv tensor)
+    bool attn_split = true;                  // 16x16 / 8x8 maps: to_qkv + core in one launch, an (image, head) split over two workgroups that
+                                             // exchange their context partials in the launch (DDK_OPT_ATTENTION_SPLIT) -- wherever the
+                                             // in-launch GroupNorm may run; 0: the projection and linattn_small_kernel as two launches
     bool fold_down_reduce = false;           // Downsample conv's split-K slabs summed by the image-local ResnetBlock behind it (no reduce launch).
                                              // OFF by default: measured 6 us per step SLOWER (each of an image's eight workgroups re-sums the slabs:
                                              // +6.3 / +5.9 us on the two consumers against reduce launches of 5.2 / 4.9 us; tools/fold_ab.py)
@@ -466,6 +469,7 @@ extern "C" int ddk_unet_set_option(ddk_unet* u, int option, int value) {
         {DDK_OPT_ATTENTION_KV_CONTEXT, true, [](ddk_unet& p, int v) { p.attn_kvctx = v != 0; }},
         {DDK_OPT_FIRST_GROUPNORM, true, [](ddk_unet& p, int v) { p.first_gn = v != 0; }},
         {DDK_OPT_RESTORE_FUSED_TAIL, true, [](ddk_unet& p, int v) { p.restore_fused = v != 0; }},
+        {DDK_OPT_ATTENTION_SPLIT, true, [](ddk_unet& p, int v) { p.attn_split = v != 0; }},
         // 0 off, 1 (default): the 4x4 level with its Downsample / Upsample convs, 2: the 4x4 level alone, 3: the 8x8 levels as well,
         // 4: the 8x8 levels only, 8 / 16: only downs[-2] / only ups[1]
         {DDK_OPT_LEVEL_CHAIN, true, [](ddk_unet& p, int v) {
@@ -495,7 +499,8 @@ extern "C" int ddk_unet_set_option(ddk_unet* u, int option, int value) {
 }
 extern "C" unsigned ddk_debug_cluster_timeouts(void) {
     unsigned sum = 0;
-    for (unsigned v : {ddk::conv_wino_cluster_timeouts(), ddk::conv_first_cluster_timeouts(), ddk::level_chain_cluster_timeouts()}) {
+    for (unsigned v : {ddk::conv_wino_cluster_timeouts(), ddk::conv_first_cluster_timeouts(), ddk::level_chain_cluster_timeouts(),
+                       ddk::attention_cluster_timeouts()}) {
         if (v == ~0u) return ~0u;
         sum += v;
     }
@@ -649,6 +654,7 @@ static void attn_sizes(const AttnW& a, int B, int H, int W, Layout& ly) {
     if (attn_kvctx_ok(B, H * W, a.c, HEADS)) upd(ly.splitk, attn_kvctx_workspace_bytes(B, H * W) / 4);
     upd(ly.splitk, conv_workspace_bytes(DDK_CONV1X1, B, H, W, a.c, 3 * HIDDEN) / 4);
     upd(ly.splitk, conv_workspace_bytes(DDK_CONV1X1, B, H, W, HIDDEN, a.c) / 4);
+    if ((H * W == 64 || H * W == 256) && B <= 32) upd(ly.cl, cl_counter_floats(B) + attn_split_record_floats(B));   // the pixel-split launch's records
 }
 
 // The level chain (level_chain.hip) takes the last level when it is a 4x4 map of 256 channels whose neighbours are 256 wide too (cfg1,
@@ -953,8 +959,9 @@ static int run_attn(Ctx& c, const AttnW& a, const float* x, float* out, int H, i
     const long long M = (long long)c.B * H * W;
     if (!c.u.generic && H * W <= 16 && a.c % 32 == 0 && linattn_small_qkv_ok(H * W, a.c)) {
         // 4x4 maps: projection (LayerNorm folded), context and apply of one (image, head) in one workgroup -- no qkv tensor,
-        // 14.6 us instead of 11.0 + 5.2.  (On 8x8 maps the projection is 4x the work on the same 128 workgroups -- half the
-        // chip, one wave per SIMD: 25.5 us against 12.5 + 5.7 for the two launches, so those keep the im2col kernel.)
+        // 14.6 us instead of 11.0 + 5.2.  (On 8x8 maps the same kernel does 4x the work on the same 128 workgroups -- half the
+        // chip, one wave per SIMD: 25.5 us against 12.5 + 5.7 for the two launches.  Those maps and the 16x16 ones take the
+        // pixel-split launch below where the in-launch exchanges may run, and the im2col kernel + linattn_small_kernel elsewhere.)
         DDK_TRY(linattn_small_qkv(x, c.P + a.qkv_op, c.P + a.ln_c1, c.P + a.ln_c2, LN_EPS, ctx, o, c.B, H * W, a.c, HEADS, c.st));
         return run_conv(c, DDK_CONV1X1, a.out, o, HIDDEN, nullptr, 0, x, out, H, W, a.c);
     }
@@ -981,6 +988,15 @@ static int run_attn(Ctx& c, const AttnW& a, const float* x, float* out, int H, i
                           a2, c.B, a.c, HEADS, c.st));
         const ConvLnFold lnA{a1, a2, LN_EPS};
         return conv1x1_ws(x, A, nullptr, x, out, M, a.c, &lnA, c.st, c.B);
+    }
+    if (!c.u.generic && c.u.attn_split && c.allow_cluster && a.c >= 128 && attn_split_ok(c.B, H * W, a.c, HEADS)) {
+        // 16x16 and 8x8 maps, up to batch 32: projection (LayerNorm folded) and core of one (image, head, half of the pixels) per
+        // workgroup -- 8 B workgroups, no qkv tensor; the two halves exchange their context partials inside the launch.
+        // (Measured at C = 128 and 256 only; narrower sites -- at most three K chunks -- keep the two launches.)
+        float* cl = c.W + c.ly.off_cl;
+        DDK_TRY(attn_split(x, c.P + a.qkv_lnw, c.P + a.ln_c1, c.P + a.ln_c2, LN_EPS, ctx, o, c.B, H * W, a.c,
+                           reinterpret_cast<unsigned*>(cl + cl_attn_offset(c.B)), cl + cl_counter_floats(c.B), cl_words(cl, c.B).fail, c.st));
+        return run_conv(c, DDK_CONV1X1, a.out, o, HIDDEN, nullptr, 0, x, out, H, W, a.c);
     }
     if (!c.u.generic && conv_ln_fold_ok(c.B, H, W, a.c, 3 * HIDDEN)) {
         // LayerNorm folded into the projection: no LayerNorm launch, no normalised copy of x

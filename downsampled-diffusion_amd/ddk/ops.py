@@ -1341,6 +1341,35 @@ def linattn_small_from_x(x, w_qkv, ln_g, ln_b, heads=4, eps=LN_EPS):
     return out, ctx
 
 
+def attention_split_workspace(batch, device):
+    """a zeroed workspace for attention_split_from_x (its counters re-arm themselves: zero it once, reuse it)"""
+    nbytes = L.load().ddk_attention_split_workspace_bytes(batch)
+    return torch.zeros(max(nbytes, 128) // 4, device=device, dtype=torch.float32)
+
+
+def attention_split_from_x(x, w_qkv, ln_g, ln_b, heads=4, eps=LN_EPS, workspace=None):
+    """PreNorm(LinearAttention) up to (not including) to_out on a 16x16 or 8x8 map in ONE launch, every (image, head) split over two
+    workgroups that exchange their softmax partials in the launch (ddk_attention_split_from_x): x [B,H,W,C]; w_qkv the canonical
+    to_qkv weight [3*heads*32, C(,1,1)]; ln_g / ln_b the channel LayerNorm's g, b (blocks.py:57-60, 123-134).
+    -> (out [B,H,W,heads*32], ctx [B,heads,32,32]).  The folded weights are derived here (the UNet plan caches them)."""
+    b, h, w, c = x.shape
+    lib = L.load()
+    if not lib.ddk_attention_split_ok(b, h * w, c, heads):
+        raise L.DDKError(f"attention_split_from_x: shape {tuple(x.shape)} with {heads} heads not eligible "
+                         "(H*W of 64 or 256, C % 32 == 0, C <= 256, 4 heads, 8 * B <= the CU count)")
+    wq = w_qkv.reshape(w_qkv.shape[0], -1).to(torch.float32)
+    g, bb = ln_g.reshape(-1).to(torch.float32), ln_b.reshape(-1).to(torch.float32)
+    lnw = (wq * g[None, :]).contiguous()
+    c1 = lnw.sum(dim=1).contiguous()
+    c2 = (wq * bb[None, :]).sum(dim=1).contiguous()
+    ws = attention_split_workspace(b, x.device) if workspace is None else workspace
+    ctx = torch.empty((b, heads, 32, 32), device=x.device, dtype=torch.float32)
+    out = torch.empty((b, h, w, heads * 32), device=x.device, dtype=torch.float32)
+    L.check(lib.ddk_attention_split_from_x(L.ptr(_f32(x)), L.ptr(lnw), L.ptr(c1), L.ptr(c2), eps, L.ptr(ctx), L.ptr(out), b, h * w, c, heads,
+                                           L.ptr(ws), ws.numel() * 4, L.stream()), "attention_split_from_x")
+    return out, ctx
+
+
 def linattn_train(qkv, heads=4):
     out, ctx = linattn(qkv, heads)
     b, h, w, _ = qkv.shape

@@ -122,6 +122,7 @@ class UnetPlan:
     OPT_LEVEL_CHAIN = 7
     OPT_FIRST_GROUPNORM = 8
     OPT_RESTORE_FUSED_TAIL = 12
+    OPT_ATTENTION_SPLIT = 13
 
     def set_option(self, option, value):
         """ddk_unet_set_option: e.g. (OPT_CLUSTER_GROUPNORM, 0) keeps conv + GroupNorm-apply as two launches

@@ -249,6 +249,17 @@ size_t ddk_attention_kv_context_workspace_bytes(int B, int HW);
 int ddk_attention_kv_context_ok(int B, int HW, int C, int heads);
 int ddk_attention_kv_context(const float* x, const float* w_kv, const float* c1, const float* c2, float ln_eps, float* ctx, int B, int HW,
                              void* workspace, size_t workspace_bytes, ddk_stream_t s);
+/* to_qkv (PreNorm LayerNorm folded in) + the attention core in ONE launch on 16x16 and 8x8 maps (H*W = 256 or 64; C % 32 == 0, C <= 256,
+ * 4 heads, 8 * B <= the 256 CUs of a whole MI355X): workgroup = (image, head, half of the pixels); the two halves exchange their softmax
+ * partials inside the launch and merge them in a fixed order, so the result is bit-stable (blocks.py:57-60, 123, 126-131).  No qkv tensor.
+ * x [B*HW][C]; w_folded [384][C] = W o g, c1 / c2 [384] = W g / W b; ctx [B][4][32][32]; out [B*HW][128] (to_out's input).
+ * workspace: ddk_attention_split_workspace_bytes(B) bytes, 128-byte aligned, ZERO before its first use (the counters in it re-arm
+ * themselves; word 0 is a sticky count of workgroups that gave up waiting for their partner -- their output is NaN, see
+ * ddk_debug_cluster_timeouts).  _ok() == 0: the entry returns an error and launches nothing. */
+size_t ddk_attention_split_workspace_bytes(int B);
+int ddk_attention_split_ok(int B, int HW, int C, int heads);
+int ddk_attention_split_from_x(const float* x, const float* w_folded, const float* c1, const float* c2, float ln_eps, float* ctx, float* out,
+                               int B, int HW, int C, int heads, void* workspace, size_t workspace_bytes, ddk_stream_t s);
 int ddk_linattn_fused_small(const float* qkv, float* ctx, float* out, int B, int HW, int heads, ddk_stream_t s);
 /* out[b][n][h*32+e] = sum_d ctx[b][h][d][e] * q[b][n][h*32+d]. */
 int ddk_linattn_apply(const float* qkv, const float* ctx, float* out, int B, int HW, int heads, ddk_stream_t s);
@@ -467,6 +478,10 @@ int ddk_unet_forward(const ddk_unet* u, const void* packed, const float* x, cons
  * (ddk_sampler_run_restore_masked), the solver's (ddk_sampler_run_restore_multistep), the noisy chain
  * (ddk_sampler_run_restore_noisy) and the grey chain (ddk_sampler_run_restore_gray) obey it too. */
 #define DDK_OPT_RESTORE_FUSED_TAIL 12
+/* DDK_OPT_ATTENTION_SPLIT (default 1): on 16x16 and 8x8 maps, up to batch 32, the attention block's to_qkv and core run as one launch
+ * (ddk_attention_split_from_x) wherever DDK_OPT_CLUSTER_GROUPNORM lets the in-launch exchanges run; 0 keeps the projection and the
+ * core as two launches with the qkv tensor between them.  Same arithmetic up to summation order. */
+#define DDK_OPT_ATTENTION_SPLIT 13
 int ddk_unet_set_option(ddk_unet* u, int option, int value);
 /* Waits for `s`, then reads and clears the sticky give-up count of the launches issued on `workspace` (a ddk_unet_forward or
  * ddk_sampler_run workspace of this shape): DDK_OK, or DDK_ERR_CLUSTER when any in-launch GroupNorm exchange timed out. */

@@ -5,7 +5,8 @@ cases: cls16 (the k-split in-launch GroupNorm conv of the 16x16 up level), wino 
 one launch, 256->256 @4x4), wlocal8 (the same @8x8, Winograd form), first (conv_first 8->128 @32x32), tail (final_tail_kernel),
 cluster16 (conv3x3 256->256 @16x16 with GroupNorm finished in the launch), ws (to_out 1x1 128->128 + bias + residual @32x32,
 weights-stationary kernel), fold (attn_fold_kernel), halo32 (wgrad3x3_halo32_kernel), gnbig (gn_apply_kernel on the 256x256 tensor),
-kvctx (attn_kvctx_kernel: k, v projection + context @32x32), c32 (conv3x3 32->32 @64x64 B=64 with the filter in registers), stream (conv1x1 32->64 @64x64 B=64 with Mish' and residual: conv1x1_stream.hip)."""
+kvctx (attn_kvctx_kernel: k, v projection + context @32x32), c32 (conv3x3 32->32 @64x64 B=64 with the filter in registers), stream (conv1x1 32->64 @64x64 B=64 with Mish' and residual: conv1x1_stream.hip), attnsplit (attn_split_kernel: to_qkv + attention core
+@16x16, C = 256)."""
 import os
 import sys
 
@@ -129,6 +130,11 @@ elif case == "unet":           # the whole cfg4 UNet forward, in-launch paths on
     def fn():
         with torch.no_grad():
             return net(xin, tt)
+elif case == "attnsplit":      # to_qkv + attention core in one launch, every (image, head) split over two workgroups: 32 images, 16x16, C = 256
+    x = torch.randn(B, 16, 16, 256, device=dev)
+    wq, g, be = torch.randn(384, 256, device=dev) * 256 ** -0.5, torch.ones(256, device=dev), torch.zeros(256, device=dev)
+    ws = ops.attention_split_workspace(B, dev)
+    fn = lambda: ops.attention_split_from_x(x, wq, g, be, workspace=ws)
 else:
     raise SystemExit(f"unknown case {case}")
 for _ in range(20):
