@@ -687,3 +687,55 @@ class TimeEmbedFn(torch.autograd.Function):
             ops.multi_add_(G, segs)
             return (None,) * (6 + len(grads))
         return (None, None, gw1, gb1, gw2, gb2, *grads)
+
+
+# ---------------------------------------------------------------- the 'deterministic' / 'convolutional' resamplers (NCHW, csrc/resample.hip)
+class BicubicResizeFn(torch.autograd.Function):
+    """F.interpolate(mode='bicubic', align_corners=True): linear in x, so the backward needs only the input's size."""
+
+    @staticmethod
+    def forward(ctx, x, size):
+        ctx.in_size = tuple(x.shape[2:])
+        return ops.bicubic_resize(x, size)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ops.bicubic_resize_grad(_c(dy), ctx.in_size), None
+
+
+class ConvSmallS2Fn(torch.autograd.Function):
+    """nn.Conv2d(k3, s2, p1) with 1..32 channels (SimpleDownConv)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        ctx.save_for_backward(x, weight)
+        return ops.conv_small_s2(x, _c(weight.detach()), _c(bias.detach()))
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        dy = _c(dy)
+        dx = ops.conv_small_s2_dgrad(dy, _c(weight.detach()), x.shape[2:]) if ctx.needs_input_grad[0] else None
+        dw = db = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            dw, db = ops.conv_small_s2_wgrad(x, dy, want_bias=ctx.needs_input_grad[2])
+        return dx, dw if ctx.needs_input_grad[1] else None, db
+
+
+class ConvTSmallS2Fn(torch.autograd.Function):
+    """nn.ConvTranspose2d(k4, s2, p1) with 1..32 channels (SimpleUpConv)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        ctx.save_for_backward(x, weight)
+        return ops.convt_small_s2(x, _c(weight.detach()), _c(bias.detach()))
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        dy = _c(dy)
+        dx = ops.convt_small_s2_dgrad(dy, _c(weight.detach())) if ctx.needs_input_grad[0] else None
+        dw = db = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            dw, db = ops.convt_small_s2_wgrad(x, dy, want_bias=ctx.needs_input_grad[2])
+        return dx, dw if ctx.needs_input_grad[1] else None, db

@@ -265,6 +265,16 @@ SIGNATURES = {
     "ddk_grad_norm_clip": (_I, [_P, _LL, _F, _P, _P, _SZ, _P]),
     "ddk_adam_step": (_I, [_P, _P, _P, _P, _LL, C.c_double, C.c_double, C.c_double, C.c_double, _I, _P, _P]),
     "ddk_ema_update": (_I, [_P, _P, _LL, _F, _P]),
+    "ddk_bicubic_resize": (_I, [_P, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _I, _P]),
+    "ddk_bicubic_resize_grad": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _LL, _I, _I, _I, _I, _P]),
+    "ddk_conv_small_s2": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "ddk_conv_small_s2_dgrad": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "ddk_conv_small_s2_wgrad_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
+    "ddk_conv_small_s2_wgrad": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _SZ, _P]),
+    "ddk_convt_small_s2": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "ddk_convt_small_s2_dgrad": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "ddk_convt_small_s2_wgrad_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
+    "ddk_convt_small_s2_wgrad": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _SZ, _P]),
 }
 
 _lib = None

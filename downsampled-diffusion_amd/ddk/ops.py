@@ -1518,3 +1518,183 @@ def adam_step_(p, g, m, v, lr, step, clip=None, betas=(0.9, 0.999), eps=1e-8):
 
 def ema_update_(p_ema, p, decay):
     L.check(L.load().ddk_ema_update(L.ptr(p_ema), L.ptr(p), p.numel(), float(decay), L.stream()), "ema_update")
+
+
+# ================================================================== the 'deterministic' / 'convolutional' resamplers (csrc/resample.hip)
+# NCHW tensors throughout: the callers hold NCHW and the channel counts are 1..8, so there is no channel padding and no layout change.
+BICUBIC_A = -0.75
+_bicubic_cache = {}            # (n_in, n_out, device, transposed) -> tuple of device tensors
+
+
+def bicubic_taps(n_in, n_out):
+    """The 1-D taps of torch's upsample_bicubic2d with align_corners=True, as numpy (idx int32 [n_out, 4], w float32 [n_out, 4]):
+    source coordinate o (n_in - 1) / (n_out - 1) (0 when n_out == 1), i = its floor, t = its fraction, taps i-1 .. i+2 with the
+    cubic-convolution weights c2(t+1), c1(t), c1(1-t), c2(2-t) for A = -0.75; indices clamped to [0, n_in - 1] -- a clamped tap
+    keeps its weight.  Everything in float64, cast once."""
+    import numpy as np
+    a = BICUBIC_A
+    o = np.arange(n_out, dtype=np.float64)
+    src = o * ((n_in - 1) / (n_out - 1)) if n_out > 1 else np.zeros(1)
+    i = np.floor(src)
+    t = src - i
+    c1 = lambda x: ((a + 2.0) * x - (a + 3.0)) * x * x + 1.0               # |x| <= 1
+    c2 = lambda x: ((a * x - 5.0 * a) * x + 8.0 * a) * x - 4.0 * a         # 1 < |x| < 2
+    w = np.stack([c2(t + 1.0), c1(t), c1(1.0 - t), c2(2.0 - t)], axis=1)
+    idx = np.clip(i[:, None].astype(np.int64) + np.arange(-1, 3)[None, :], 0, n_in - 1)
+    return idx.astype(np.int32), w.astype(np.float32)
+
+
+def bicubic_taps_transposed(n_in, n_out):
+    """The same taps listed per INPUT index (the gather form of the gradient): (start int32 [n_in + 1], out_idx int32 [nnz],
+    w float32 [nnz]); entries start[i] .. start[i+1]-1 are the outputs that tap i, ascending.  Taps of one output that coincide after
+    clamping are one entry with their (fp32) weights added in float64."""
+    import numpy as np
+    idx, w = bicubic_taps(n_in, n_out)
+    lists = [dict() for _ in range(n_in)]
+    for o in range(n_out):
+        for k in range(4):
+            d = lists[int(idx[o, k])]
+            d[o] = d.get(o, 0.0) + float(w[o, k])
+    start, oi, ww = [0], [], []
+    for d in lists:
+        for o in sorted(d):
+            oi.append(o)
+            ww.append(d[o])
+        start.append(len(oi))
+    return np.asarray(start, np.int32), np.asarray(oi, np.int32), np.asarray(ww, np.float32)
+
+
+def _bicubic_tables(n_in, n_out, device, transposed=False):
+    """Device copies of the tap tables, made once per (n_in, n_out, device) (like DDPM._cached_tables: a graph capture finds them
+    ready, its warm-up passes made them)."""
+    key = (int(n_in), int(n_out), str(device), transposed)
+    tabs = _bicubic_cache.get(key)
+    if tabs is None:
+        host = bicubic_taps_transposed(n_in, n_out) if transposed else bicubic_taps(n_in, n_out)
+        tabs = tuple(torch.from_numpy(h).contiguous().to(device) for h in host)
+        if transposed:
+            tabs += (int((host[0][1:] - host[0][:-1]).max()),)           # the longest list: how the gradient kernel shares its work
+        _bicubic_cache[key] = tabs
+    return tabs
+
+
+def _nchw(x, what):
+    if x.dim() != 4:
+        raise L.DDKError(f"{what}: expected an NCHW tensor, got {x.dim()} dimensions")
+    return _f32(x)
+
+
+def bicubic_resize(x, size):
+    """F.interpolate(x, size, mode='bicubic', align_corners=True) of an NCHW tensor; size = (Hout, Wout)."""
+    b, c, h, w = _nchw(x, "bicubic_resize").shape
+    ho, wo = int(size[0]), int(size[1])
+    xp = L.ptr(x)
+    ih, wh = _bicubic_tables(h, ho, x.device)
+    iw, ww = _bicubic_tables(w, wo, x.device)
+    out = torch.empty((b, c, ho, wo), device=x.device, dtype=torch.float32)
+    L.check(L.load().ddk_bicubic_resize(xp, L.ptr(out), L.ptr(ih), L.ptr(wh), L.ptr(iw), L.ptr(ww), b * c, h, w, ho, wo, L.stream()),
+            "bicubic_resize")
+    return out
+
+
+def bicubic_resize_grad(dy, in_size):
+    """Gradient of bicubic_resize with respect to its input: dy [B, C, Hout, Wout] -> [B, C, *in_size]."""
+    b, c, ho, wo = _nchw(dy, "bicubic_resize_grad").shape
+    h, w = int(in_size[0]), int(in_size[1])
+    dyp = L.ptr(dy)
+    sh, oh, wh, _ = _bicubic_tables(h, ho, dy.device, transposed=True)
+    sw, ow, ww, longest_w = _bicubic_tables(w, wo, dy.device, transposed=True)
+    dx = torch.empty((b, c, h, w), device=dy.device, dtype=torch.float32)
+    L.check(L.load().ddk_bicubic_resize_grad(dyp, L.ptr(dx), L.ptr(sh), L.ptr(oh), L.ptr(wh), L.ptr(sw), L.ptr(ow), L.ptr(ww), longest_w,
+                                             b * c, h, w, ho, wo, L.stream()), "bicubic_resize_grad")
+    return dx
+
+
+def _small_conv_shapes(x, w, what, transpose):
+    b, c, h, wd = _nchw(x, what).shape
+    if w.dim() != 4 or tuple(w.shape[2:]) != ((4, 4) if transpose else (3, 3)):
+        raise L.DDKError(f"{what}: the weight must be [{'C_in, C_out, 4, 4' if transpose else 'C_out, C_in, 3, 3'}], got {tuple(w.shape)}")
+    cin, cout = (w.shape[0], w.shape[1]) if transpose else (w.shape[1], w.shape[0])
+    if not (1 <= cin <= 32 and 1 <= cout <= 32):
+        raise L.DDKError(f"{what}: 1 <= channels <= 32 (got {cin} -> {cout})")
+    return b, c, h, wd, int(cin), int(cout)
+
+
+def conv_small_s2(x, w, bias=None):
+    """nn.Conv2d(C_in, C_out, 3, stride=2, padding=1) on NCHW, 1 <= C <= 32, any H, W >= 1."""
+    b, c, h, wd, cin, cout = _small_conv_shapes(x, w, "conv_small_s2", False)
+    if c != cin:
+        raise L.DDKError(f"conv_small_s2: the input has {c} channels, the weight takes {cin}")
+    out = torch.empty((b, cout, (h + 1) // 2, (wd + 1) // 2), device=x.device, dtype=torch.float32)
+    L.check(L.load().ddk_conv_small_s2(L.ptr(x), L.ptr(_f32(w)), L.ptr(bias), L.ptr(out), b, cin, cout, h, wd, L.stream()), "conv_small_s2")
+    return out
+
+
+def conv_small_s2_dgrad(dy, w, in_size):
+    """Input gradient of conv_small_s2: dy [B, C_out, ceil(H/2), ceil(W/2)] -> [B, C_in, H, W] with (H, W) = in_size."""
+    b, c, ho, wo, cin, cout = _small_conv_shapes(dy, w, "conv_small_s2_dgrad", False)
+    h, wd = int(in_size[0]), int(in_size[1])
+    if c != cout or (ho, wo) != ((h + 1) // 2, (wd + 1) // 2):
+        raise L.DDKError(f"conv_small_s2_dgrad: dy {tuple(dy.shape)} is not the output of a [{cin}, {h}, {wd}] input")
+    dx = torch.empty((b, cin, h, wd), device=dy.device, dtype=torch.float32)
+    L.check(L.load().ddk_conv_small_s2_dgrad(L.ptr(dy), L.ptr(_f32(w)), L.ptr(dx), b, cin, cout, h, wd, L.stream()), "conv_small_s2_dgrad")
+    return dx
+
+
+def conv_small_s2_wgrad(x, dy, want_bias=True):
+    """(dW [C_out, C_in, 3, 3], db [C_out] or None) of conv_small_s2."""
+    b, cin, h, wd = _nchw(x, "conv_small_s2_wgrad").shape
+    cout = _nchw(dy, "conv_small_s2_wgrad").shape[1]
+    if tuple(dy.shape) != (b, cout, (h + 1) // 2, (wd + 1) // 2):
+        raise L.DDKError(f"conv_small_s2_wgrad: dy {tuple(dy.shape)} is not the output of x {tuple(x.shape)}")
+    xp, dyp = L.ptr(x), L.ptr(dy)
+    lib = L.load()
+    nbytes = lib.ddk_conv_small_s2_wgrad_workspace_bytes(b, cin, cout, h, wd)
+    if nbytes == 0:
+        raise L.DDKError(f"conv_small_s2_wgrad: 1 <= channels <= 32 (got {cin} -> {cout})")
+    ws = _ws(x.device, nbytes, "small_wgrad")
+    dw = torch.empty((cout, cin, 3, 3), device=x.device, dtype=torch.float32)
+    db = torch.empty(cout, device=x.device, dtype=torch.float32) if want_bias else None
+    L.check(lib.ddk_conv_small_s2_wgrad(xp, dyp, L.ptr(dw), L.ptr(db), b, cin, cout, h, wd, L.ptr(ws), ws.numel() * 4, L.stream()),
+            "conv_small_s2_wgrad")
+    return dw, db
+
+
+def convt_small_s2(x, w, bias=None):
+    """nn.ConvTranspose2d(C_in, C_out, 4, stride=2, padding=1) on NCHW, 1 <= C <= 32: [B, C_in, H, W] -> [B, C_out, 2H, 2W]."""
+    b, c, h, wd, cin, cout = _small_conv_shapes(x, w, "convt_small_s2", True)
+    if c != cin:
+        raise L.DDKError(f"convt_small_s2: the input has {c} channels, the weight takes {cin}")
+    out = torch.empty((b, cout, 2 * h, 2 * wd), device=x.device, dtype=torch.float32)
+    L.check(L.load().ddk_convt_small_s2(L.ptr(x), L.ptr(_f32(w)), L.ptr(bias), L.ptr(out), b, cin, cout, h, wd, L.stream()), "convt_small_s2")
+    return out
+
+
+def convt_small_s2_dgrad(dy, w):
+    """Input gradient of convt_small_s2: dy [B, C_out, 2H, 2W] -> [B, C_in, H, W]."""
+    b, c, ho, wo, cin, cout = _small_conv_shapes(dy, w, "convt_small_s2_dgrad", True)
+    if c != cout or ho % 2 or wo % 2:
+        raise L.DDKError(f"convt_small_s2_dgrad: dy {tuple(dy.shape)} is not an output of a [{cin} -> {cout}] layer")
+    dx = torch.empty((b, cin, ho // 2, wo // 2), device=dy.device, dtype=torch.float32)
+    L.check(L.load().ddk_convt_small_s2_dgrad(L.ptr(dy), L.ptr(_f32(w)), L.ptr(dx), b, cin, cout, ho // 2, wo // 2, L.stream()),
+            "convt_small_s2_dgrad")
+    return dx
+
+
+def convt_small_s2_wgrad(x, dy, want_bias=True):
+    """(dW [C_in, C_out, 4, 4], db [C_out] or None) of convt_small_s2."""
+    b, cin, h, wd = _nchw(x, "convt_small_s2_wgrad").shape
+    cout = _nchw(dy, "convt_small_s2_wgrad").shape[1]
+    if tuple(dy.shape) != (b, cout, 2 * h, 2 * wd):
+        raise L.DDKError(f"convt_small_s2_wgrad: dy {tuple(dy.shape)} is not the output of x {tuple(x.shape)}")
+    xp, dyp = L.ptr(x), L.ptr(dy)
+    lib = L.load()
+    nbytes = lib.ddk_convt_small_s2_wgrad_workspace_bytes(b, cin, cout, h, wd)
+    if nbytes == 0:
+        raise L.DDKError(f"convt_small_s2_wgrad: 1 <= channels <= 32 (got {cin} -> {cout})")
+    ws = _ws(x.device, nbytes, "small_wgrad")
+    dw = torch.empty((cin, cout, 4, 4), device=x.device, dtype=torch.float32)
+    db = torch.empty(cout, device=x.device, dtype=torch.float32) if want_bias else None
+    L.check(lib.ddk_convt_small_s2_wgrad(xp, dyp, L.ptr(dw), L.ptr(db), b, cin, cout, h, wd, L.ptr(ws), ws.numel() * 4, L.stream()),
+            "convt_small_s2_wgrad")
+    return dw, db

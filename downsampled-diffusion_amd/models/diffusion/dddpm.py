@@ -1,5 +1,6 @@
-"""Downsampled DDPM (dDDPM): a DDPM over tanh-squashed latents produced by a learned ConvResNet encoder,
-decoded by a ConvResNet decoder (reference models/diffusion/dddpm.py:11-177).  Same constructor and
+"""Downsampled DDPM (dDDPM): a DDPM over tanh-squashed latents produced by an encoder and decoded by a decoder, each of
+config['d_mode'] / config['u_mode']: a learned ConvResNet, a plain stack of stride-2 convs, or a bicubic resize (reference
+models/diffusion/dddpm.py:11-177, models/downsampled/wrapper.py).  Same constructor and
 return conventions: ``sample`` -> (x, z), ``forward`` -> (objective, {'latent', 'recon'}).
 """
 import math
@@ -10,6 +11,7 @@ import torch.nn as nn
 
 from ddk import ops
 from models.downsampled import get_downsampling, get_upsampling
+from models.downsampled.convblocks import ConvResNet
 from .ddpm import DDPM
 
 
@@ -29,25 +31,43 @@ class DownsampleDDPM(DDPM):
         self.upsample = get_upsampling(config, self.x_shape)
 
     # ------------------------------------------------------------------ encoder / decoder (dddpm.py:92-112)
+    def _resample_nchw(self, net, x):
+        """Interpolate / SimpleDownConv / SimpleUpConv on the NCHW tensor as it stands (no channel padding, no layout change), then
+        the tanh.  Differentiable when gradients are enabled and a parameter OR the input wants one: an Interpolate decoder has no
+        parameters, yet the non-autoencoder loss needs d(loss) / d(z_hat) through it."""
+        x = x.contiguous().float()
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in net.parameters())):
+            from ddk import autograd as AG
+            y = net.forward_autograd(x)
+            return AG.TanhFn.apply(y) if self.force_latent else y
+        y = net(x)
+        return ops.tanh(y) if self.force_latent else y
+
     def rescaled_downsample(self, x):
         """z = tanh(downsample(x)) (tanh only when force_latent)."""
         self._check_device(x)
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.downsample.parameters()):
+        if not isinstance(self.downsample, ConvResNet):
+            z = self._resample_nchw(self.downsample, x)
+        elif torch.is_grad_enabled() and any(p.requires_grad for p in self.downsample.parameters()):
             from trainers.autograd_unet import resnet_forward_autograd
             return resnet_forward_autograd(self.downsample, x, self.force_latent)
-        z = ops.nhwc_to_nchw(self.downsample.forward_nhwc(ops.nchw_to_nhwc(x.contiguous().float(), ops.pad32(x.shape[1])),
-                                                          final_tanh=self.force_latent))
+        else:
+            z = ops.nhwc_to_nchw(self.downsample.forward_nhwc(ops.nchw_to_nhwc(x.contiguous().float(), ops.pad32(x.shape[1])),
+                                                              final_tanh=self.force_latent))
         assert list(z.shape)[1:] == self.sample_shape, f'mismatch between {list(z.shape)[1:]} and {self.sample_shape}'
         return z
 
     def rescaled_upsample(self, z):
         """x = tanh(upsample(z))."""
         self._check_device(z)
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.upsample.parameters()):
+        if not isinstance(self.upsample, ConvResNet):
+            x = self._resample_nchw(self.upsample, z)
+        elif torch.is_grad_enabled() and any(p.requires_grad for p in self.upsample.parameters()):
             from trainers.autograd_unet import resnet_forward_autograd
             return resnet_forward_autograd(self.upsample, z, self.force_latent)
-        x = ops.nhwc_to_nchw(self.upsample.forward_nhwc(ops.nchw_to_nhwc(z.contiguous().float(), ops.pad32(z.shape[1])),
-                                                        final_tanh=self.force_latent))
+        else:
+            x = ops.nhwc_to_nchw(self.upsample.forward_nhwc(ops.nchw_to_nhwc(z.contiguous().float(), ops.pad32(z.shape[1])),
+                                                            final_tanh=self.force_latent))
         assert list(x.shape)[1:] == self.x_shape, f'mismatch between {list(x.shape)[1:]} and {self.x_shape}'
         return x
 

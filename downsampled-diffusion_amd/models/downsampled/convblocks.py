@@ -1,14 +1,17 @@
-"""dDDPM encoder / decoder networks (reference models/downsampled/convblocks.py:92-159), HIP-backed.
+"""dDDPM encoder / decoder networks (reference models/downsampled/convblocks.py:8-159), HIP-backed.
 
-Only the 'convolutional_res' mode that train.py:34-35 selects is built (the reference's unused
-SimpleDownConv / SimpleUpConv / interpolate modes are out of scope).  Parameter names
-(`conv.{i}.c1..c4`, `conv.0`, `conv.{last}`) match the reference so checkpoints load strictly.
+All three resampler modes of the reference's factories are built: 'convolutional_res' (ConvResNet, the mode train.py:34-35
+selects), 'convolutional' (SimpleDownConv / SimpleUpConv: stride-2 3x3 convs down, 4x4 stride-2 transpose convs up) and
+'deterministic' (Interpolate: bicubic, align_corners=True, no parameters).  Parameter names (`conv.{i}.c1..c4`, `conv.0`,
+`conv.{last}`; `conv.{i}.weight / bias` for the simple stacks) match the reference so checkpoints load strictly.
 
 Kernel mapping of one ConvResBlock (convblocks.py:112-130), NHWC:
     c1: 1x1 on Mish(x)         -> igemm with Mish applied while staging the input, Mish in the epilogue
     c2, c3: 3x3                -> igemm, Mish in the epilogue (each activation is computed exactly once)
     c4: 1x1 (+ x residual)     -> igemm with the residual added in the epilogue
     avg_pool2d(2) / nearest x2 -> one elementwise kernel
+The simple stacks and Interpolate work on NCHW planes directly (csrc/resample.hip): their channel counts
+are 1..8, which the 32-channel NHWC pitch of the ConvResNet path would pad up to tenfold.
 """
 import torch.nn as nn
 
@@ -23,6 +26,103 @@ def get_3x3(in_dim, out_dim, stride=1, padding=1, padding_mode='zeros'):
 
 def get_1x1(in_dim, out_dim):
     return nn.Conv2d(in_dim, out_dim, kernel_size=1, stride=1, padding=0)
+
+
+def get_4x4_transpose(in_dim, out_dim, stride=2, padding=1):
+    return nn.ConvTranspose2d(in_dim, out_dim, kernel_size=4, stride=stride, padding=padding)
+
+
+class Interpolate(nn.Module):
+    """F.interpolate(x, size, mode='bicubic', align_corners=True) (convblocks.py:8-26: the reference returns a functools.partial, so
+    there is nothing in the state_dict; neither is there here: no parameters, no buffers -- the tap tables are cached in ddk.ops per
+    (in, out, device)).  Serves both directions.  `channels` is only what flops() prices."""
+
+    def __init__(self, size, channels=3):
+        super().__init__()
+        self.size = (int(size[0]), int(size[1]))
+        self.channels = int(channels)
+
+    def flops(self, batch, height, width):
+        """2 x 16 taps per output element (the input size does not enter)."""
+        return 2 * 16 * batch * self.channels * self.size[0] * self.size[1]
+
+    def forward(self, x):
+        return ops.bicubic_resize(x.contiguous().float(), self.size)
+
+    def forward_autograd(self, x):
+        from ddk import autograd as AG
+        return AG.BicubicResizeFn.apply(x.contiguous().float(), self.size)
+
+    def extra_repr(self):
+        return f"size={self.size}, mode='bicubic', align_corners=True"
+
+
+class _SimpleConv(nn.Module):
+    """convblocks.py:60-67 (BaseConv): the channel chain in_channels -> dim -> dim ..., one step per resampling."""
+
+    def __init__(self, dim=8, in_channels=3, n_downsamples=1):
+        super().__init__()
+        dims = [int(in_channels)] + [int(dim)] * int(n_downsamples)
+        self.in_out = list(zip(dims[:-1], dims[1:]))
+        if not all(1 <= c <= 32 for c in dims):
+            raise DDKError(f"{type(self).__name__}: the small-channel resampler kernels take 1..32 channels (got {dims})")
+
+
+class SimpleDownConv(_SimpleConv):
+    """n_downsamples x Conv2d(3x3, stride 2, padding 1), no activation in between (convblocks.py:70-78)."""
+
+    def __init__(self, dim=8, in_channels=3, n_downsamples=1):
+        super().__init__(dim, in_channels, n_downsamples)
+        self.conv = nn.Sequential(*[get_3x3(i, o, stride=2) for i, o in self.in_out])
+
+    def flops(self, batch, height, width):
+        total, h, w = 0, height, width
+        for c in self.conv:
+            h, w = (h + 1) // 2, (w + 1) // 2
+            total += 2 * batch * h * w * 9 * c.in_channels * c.out_channels
+        return total
+
+    def forward(self, x):
+        x = x.contiguous().float()
+        for c in self.conv:
+            x = ops.conv_small_s2(x, c.weight.detach(), c.bias.detach())
+        return x
+
+    def forward_autograd(self, x):
+        from ddk import autograd as AG
+        x = x.contiguous().float()
+        for c in self.conv:
+            x = AG.ConvSmallS2Fn.apply(x, c.weight, c.bias)
+        return x
+
+
+class SimpleUpConv(_SimpleConv):
+    """n_downsamples x ConvTranspose2d(4x4, stride 2, padding 1) along the reversed chain dim -> ... -> dim -> in_channels
+    (convblocks.py:81-89)."""
+
+    def __init__(self, dim=8, in_channels=3, n_downsamples=1):
+        super().__init__(dim, in_channels, n_downsamples)
+        self.conv = nn.Sequential(*[get_4x4_transpose(o, i) for i, o in self.in_out[::-1]])
+
+    def flops(self, batch, height, width):
+        total, h, w = 0, height, width
+        for c in self.conv:
+            h, w = 2 * h, 2 * w
+            total += 2 * batch * h * w * 4 * c.in_channels * c.out_channels
+        return total
+
+    def forward(self, x):
+        x = x.contiguous().float()
+        for c in self.conv:
+            x = ops.convt_small_s2(x, c.weight.detach(), c.bias.detach())
+        return x
+
+    def forward_autograd(self, x):
+        from ddk import autograd as AG
+        x = x.contiguous().float()
+        for c in self.conv:
+            x = AG.ConvTSmallS2Fn.apply(x, c.weight, c.bias)
+        return x
 
 
 class ConvResBlock(nn.Module):

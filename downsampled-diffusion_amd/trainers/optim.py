@@ -25,20 +25,24 @@ class FlatParams:
             raise RuntimeError("FlatParams: move the model to the ROCm device before building optimiser state")
         self.params = params
         self.names = [n for n, _ in module.named_parameters()]
-        self.numel = sum(p.numel() for p in params)
-        self.flat = torch.empty(self.numel, device=dev, dtype=torch.float32)
+        # Every parameter starts on a 16-byte boundary: the kernels read weights and biases in place with 16-byte loads.  A 3-element
+        # bias in the middle of the model (a dDDPM with unet_in = 3: the UNet's last bias, in front of the resamplers) would otherwise
+        # misalign everything behind it.  The gap elements are zero in every buffer and stay zero (zero gradient, zero Adam update).
+        self.offsets, off = [], 0
+        for p in params:
+            off = (off + 3) // 4 * 4
+            self.offsets.append(off)
+            off += p.numel()
+        self.numel = off
+        self.flat = torch.zeros(self.numel, device=dev, dtype=torch.float32)
         self.grad = torch.zeros(self.numel, device=dev, dtype=torch.float32) if with_grad else None
-        self.offsets = []
-        off = 0
         with torch.no_grad():
-            for p in params:
+            for p, off in zip(params, self.offsets):
                 n = p.numel()
                 self.flat[off:off + n].copy_(p.detach().reshape(-1))
                 p.data = self.flat[off:off + n].view_as(p)
                 if with_grad:
                     p.grad = self.grad[off:off + n].view_as(p)
-                self.offsets.append(off)
-                off += n
 
     def views(self, flat):
         return [flat[o:o + p.numel()].view_as(p) for o, p in zip(self.offsets, self.params)]

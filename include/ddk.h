@@ -857,6 +857,38 @@ int ddk_adam_step(float* p, const float* g, float* m, float* v, long long n, dou
                   double eps, int step, const float* clip2, ddk_stream_t s);
 int ddk_ema_update(float* p_ema, const float* p, long long n, float decay, ddk_stream_t s);
 
+/* ---- the dDDPM's 'deterministic' and 'convolutional' resamplers (csrc/resample.hip; reference models/downsampled/convblocks.py:8-89).
+ * NCHW planes, fp32, 1 <= channels <= 32 for the convs; no atomics: results are bit-stable from run to run.
+ *
+ * Bicubic resize, F.interpolate(mode='bicubic', align_corners=True), of `planes` = B*C planes [Hin][Win] -> [Hout][Wout].  The caller
+ * supplies the tap tables (16-byte aligned): idx_* [out][4] source indices already clamped to [0, in-1], w_* [out][4] the cubic-
+ * convolution weights (A = -0.75) of the taps floor(src)-1 .. floor(src)+2, src = o (in-1)/(out-1) (0 when out == 1).
+ * out = sum_a sum_b (w_h[a] w_w[b]) x[idx_h[a]][idx_w[b]], a outer, b inner. */
+int ddk_bicubic_resize(const float* x, float* out, const int* idx_h, const float* w_h, const int* idx_w, const float* w_w, long long planes,
+                       int Hin, int Win, int Hout, int Wout, ddk_stream_t s);
+/* Its gradient with respect to x, in gather form.  Per dimension the transposed tap list: entries start[i] .. start[i+1]-1 of
+ * (out_idx, w) are the outputs that tap input index i, ascending (start has in+1 entries).  dx [planes][Hin][Win].
+ * longest_w: the longest column list, max_i start_w[i+1] - start_w[i], which the caller knows from building the tables; above 8,
+ * sixteen lanes share an input element (fixed summation order either way). */
+int ddk_bicubic_resize_grad(const float* dy, float* dx, const int* start_h, const int* out_h, const float* w_h, const int* start_w,
+                            const int* out_w, const float* w_w, int longest_w, long long planes, int Hin, int Win, int Hout, int Wout,
+                            ddk_stream_t s);
+/* nn.Conv2d(cin, cout, 3, stride=2, padding=1): x [B][cin][H][W], w [cout][cin][3][3], bias [cout] or NULL -> out [B][cout][ceil(H/2)][ceil(W/2)].
+ * _dgrad: dy -> dx [B][cin][H][W].  _wgrad: dw [cout][cin][3][3] and db [cout] (NULL: not wanted), overwritten; two launches
+ * (per-workgroup partial sums, then an ordered finish) through `workspace`. */
+int ddk_conv_small_s2(const float* x, const float* w, const float* bias, float* out, int B, int cin, int cout, int H, int W, ddk_stream_t s);
+int ddk_conv_small_s2_dgrad(const float* dy, const float* w, float* dx, int B, int cin, int cout, int H, int W, ddk_stream_t s);
+size_t ddk_conv_small_s2_wgrad_workspace_bytes(int B, int cin, int cout, int H, int W);
+int ddk_conv_small_s2_wgrad(const float* x, const float* dy, float* dw, float* db, int B, int cin, int cout, int H, int W, void* workspace,
+                            size_t workspace_bytes, ddk_stream_t s);
+/* nn.ConvTranspose2d(cin, cout, 4, stride=2, padding=1): x [B][cin][H][W], w [cin][cout][4][4], bias [cout] or NULL -> out [B][cout][2H][2W].
+ * _dgrad: dy [B][cout][2H][2W] -> dx [B][cin][H][W].  _wgrad: dw [cin][cout][4][4], db [cout] (NULL: not wanted), as above. */
+int ddk_convt_small_s2(const float* x, const float* w, const float* bias, float* out, int B, int cin, int cout, int H, int W, ddk_stream_t s);
+int ddk_convt_small_s2_dgrad(const float* dy, const float* w, float* dx, int B, int cin, int cout, int H, int W, ddk_stream_t s);
+size_t ddk_convt_small_s2_wgrad_workspace_bytes(int B, int cin, int cout, int H, int W);
+int ddk_convt_small_s2_wgrad(const float* x, const float* dy, float* dw, float* db, int B, int cin, int cout, int H, int W, void* workspace,
+                             size_t workspace_bytes, ddk_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

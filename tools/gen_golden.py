@@ -383,9 +383,40 @@ def g10_long():
     save("g10_long", **out)
 
 
+# ---------------------------------------------------------------- G11 'deterministic' / 'convolutional' resampler modes
+G11_CASES = [("deterministic", 3, 2), ("deterministic", 3, 3), ("convolutional", 3, 2), ("convolutional", 3, 3),
+             ("convolutional", 8, 2), ("convolutional", 8, 3)]
+
+
+@torch.no_grad()
+def g11_resampler_modes():
+    """The reference's dDDPM with d_mode = u_mode in {'deterministic', 'convolutional'} (models/downsampled/wrapper.py:22-26,49-55)
+    at 3x32x32, B = 2: downsample(x), rescaled_downsample(x), rescaled_upsample(z), and the model's state_dict keys."""
+    import json
+    out, keys = {}, {}
+    for mode, unet_in, n_down in G11_CASES:
+        tag = f"{mode}_u{unet_in}_n{n_down}"
+        cfg = dddpm_cfg(32, 32, n_down)
+        cfg.update(d_mode=mode, u_mode=mode, unet_in=unet_in)
+        m = det_load(DownsampleDDPM(cfg, Unet(cfg), "cpu", 3).eval())
+        x = syn.synthetic_input((2, 3, 32, 32), f"g11.x{n_down}")
+        z = m.rescaled_downsample(x)
+        out[f"{tag}_raw"] = m.downsample(x).numpy()
+        out[f"{tag}_z"] = z.numpy()
+        out[f"{tag}_x"] = m.rescaled_upsample(z).numpy()
+        # the UNet's keys do not depend on the mode (only its in / out convs' shapes on unet_in): listed once per unet_in
+        unet = {k: list(v.shape) for k, v in m.state_dict().items() if k.startswith("latent_model.")}
+        assert keys.setdefault(f"latent_model_u{unet_in}", unet) == unet
+        keys[tag] = {k: list(v.shape) for k, v in m.state_dict().items() if not k.startswith("latent_model.")}
+    save("g11_resampler_modes", **out)
+    with open(os.path.join(OUT, "g11_state_dict_keys.json"), "w") as f:
+        json.dump(keys, f, separators=(",", ":"), sort_keys=True)
+        f.write("\n")
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g0", "g1", "g2", "g3", "g4", "g6", "g7", "g8", "g9", "g10"]
+    which = sys.argv[1:] or ["g0", "g1", "g2", "g3", "g4", "g6", "g7", "g8", "g9", "g10", "g11"]
     table = dict(g0=g0_keys, g1=g1_schedule, g2=g2_blocks, g3=g3_unet, g4=g4_chain, g6=g6_train, g7=g7_qsample_loss,
-                 g8=g8_resamplers, g9=g9_test_losses, g10=g10_long)
+                 g8=g8_resamplers, g9=g9_test_losses, g10=g10_long, g11=g11_resampler_modes)
     for w in which:
         table[w]()
