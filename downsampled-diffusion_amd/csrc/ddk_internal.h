@@ -375,6 +375,10 @@ enum class StepKind {
                   // factor (rst.gray names w; rst.mask may be null at every n): c_recip .. sigma, nsy, rst; Philox only
                   // (last, so that the kinds above keep their values and their kernels' names)
 };
+inline bool restore_kind(StepKind k) {       // the kinds whose step carries a DDNM constraint (RestoreOps)
+    return k == StepKind::Restore || k == StepKind::RestoreMasked || k == StepKind::RestoreMultistep || k == StepKind::RestoreNoisy ||
+           k == StepKind::RestoreGray;
+}
 struct StepRule {
     StepKind kind;
     float* eps_out;               // [B][HW][n_out] or null (fused tail only; the unfused tail's eps_hat is its input)

@@ -101,13 +101,19 @@ __device__ __forceinline__ float ms_step(float x, float e, float& h, float cr, f
     return out;
 }
 
-__device__ __forceinline__ float4 ms_step4(float4 xv, float4 ev, float4& h, float cr, float crm1, float c1, float c2, float c3) {
+// f applied to the x, y, z and w components of its float4 operands in turn (a float4& operand hands f a float& it may rewrite)
+template <class F, class... V>
+__device__ __forceinline__ float4 each4(F&& f, V&&... v) {
     float4 o;
-    o.x = ms_step(xv.x, ev.x, h.x, cr, crm1, c1, c2, c3);
-    o.y = ms_step(xv.y, ev.y, h.y, cr, crm1, c1, c2, c3);
-    o.z = ms_step(xv.z, ev.z, h.z, cr, crm1, c1, c2, c3);
-    o.w = ms_step(xv.w, ev.w, h.w, cr, crm1, c1, c2, c3);
+    o.x = f(v.x...);
+    o.y = f(v.y...);
+    o.z = f(v.z...);
+    o.w = f(v.w...);
     return o;
+}
+
+__device__ __forceinline__ float4 ms_step4(float4 xv, float4 ev, float4& h, float cr, float crm1, float c1, float c2, float c3) {
+    return each4([=](float x, float e, float& hh) { return ms_step(x, e, hh, cr, crm1, c1, c2, c3); }, xv, ev, h);
 }
 
 // RePaint (models/diffusion/respace.py repaint_tables).  One reverse op at spaced timestep tau:
@@ -115,12 +121,7 @@ __device__ __forceinline__ float4 ms_step4(float4 xv, float4 ev, float4& h, floa
 //   x = mask ? x_kn : x_unk (a select, not a blend: the known region stays exact and NaN-free);  jump: x = ja x + jb z3.
 // inp_known and inp_step are the arithmetic of both tails, so given the same eps_hat they are bit-identical.
 __device__ __forceinline__ float4 inp_known4(float4 k, float4 z2, float ka, float kb) {
-    float4 o;
-    o.x = __fadd_rn(__fmul_rn(ka, k.x), __fmul_rn(kb, z2.x));
-    o.y = __fadd_rn(__fmul_rn(ka, k.y), __fmul_rn(kb, z2.y));
-    o.z = __fadd_rn(__fmul_rn(ka, k.z), __fmul_rn(kb, z2.z));
-    o.w = __fadd_rn(__fmul_rn(ka, k.w), __fmul_rn(kb, z2.w));
-    return o;
+    return each4([=](float kn, float z) { return __fadd_rn(__fmul_rn(ka, kn), __fmul_rn(kb, z)); }, k, z2);
 }
 
 __device__ __forceinline__ float inp_step(float x, float e, float z1, float xk, float m, float z3, float cr, float crm1, float c1,
@@ -131,12 +132,8 @@ __device__ __forceinline__ float inp_step(float x, float e, float z1, float xk, 
 
 __device__ __forceinline__ float4 inp_step4(float4 xv, float4 ev, float4 z1, float4 xk, float4 m, float4 z3, float cr, float crm1,
                                             float c1, float c2, float sg, float ja, float jb, bool jump) {
-    float4 o;
-    o.x = inp_step(xv.x, ev.x, z1.x, xk.x, m.x, z3.x, cr, crm1, c1, c2, sg, ja, jb, jump);
-    o.y = inp_step(xv.y, ev.y, z1.y, xk.y, m.y, z3.y, cr, crm1, c1, c2, sg, ja, jb, jump);
-    o.z = inp_step(xv.z, ev.z, z1.z, xk.z, m.z, z3.z, cr, crm1, c1, c2, sg, ja, jb, jump);
-    o.w = inp_step(xv.w, ev.w, z1.w, xk.w, m.w, z3.w, cr, crm1, c1, c2, sg, ja, jb, jump);
-    return o;
+    return each4([=](float x, float e, float z, float k, float mk, float zj) { return inp_step(x, e, z, k, mk, zj, cr, crm1, c1, c2, sg, ja, jb, jump); },
+                 xv, ev, z1, xk, m, z3);
 }
 
 // The last kernel of an unfused step: the rule's update of x given eps_hat in memory, one template for the three sampler kinds.
@@ -193,11 +190,35 @@ __global__ __launch_bounds__(256) void p_update_kernel(const StepRule r, const f
     }
 }
 
-// DDNM super-resolution (Wang, Yu, Zhang, ICLR 2023, Algorithm 1) for A = n x n average pooling, A+ = n x n
-// replication (A A+ = I): the clipped x0 of p_step, shifted by its block's y - mean(x0) (x0' = x0 - A+ A x0 + A+ y, not re-clamped),
-// then p_step's posterior mean and draw on x0'.  At row 0 (c1 = 1, c2 = 0, no draw) the result is x0', whose block means equal y up to
-// fp32 rounding.  rst_x0, rst_block_mean and rst_finish are the arithmetic of both tails, every operation rounded on its own and the
-// block summed in row-major order, so given the same eps_hat the tails are bit-identical.
+// ---- DDNM restoration (Wang, Yu, Zhang, ICLR 2023, Algorithm 1 and section 3.3; DESIGN.md sections 3.6, 3.8 - 3.11) -------------
+// One step for the five restore kinds: the clipped x0 of p_step (rst_x0), its projection onto the measurement x0' = x0 + A+ (y - A x0)
+// (rst_x0p, not re-clamped), then the rule's update on x0' (rst_finish).  A = mask o pool_n [o grey_w]: m is A x0 of the element's n x n
+// block (rst_block_mean) or n x n x 3 group (gry_group), summed in row-major order.  What a kind adds is a compile-time flag:
+//   kind              MASK      HIST  NOISY  GRAY  n = 1
+//   Restore           absent    -     -      -     -
+//   RestoreMasked     required  -     -      -     pointwise
+//   RestoreMultistep  optional  yes   -      -     pointwise
+//   RestoreNoisy      optional  -     yes    -     pointwise
+//   RestoreGray       optional  -     yes    yes   a group of three
+// MASK: the block's (n = 1: the pixel's) mask value, 1 where no mask was given, selects between x0' and x0 -- a select, never a blend,
+// so whatever an unmeasured y holds (NaN included) reaches no result.  HIST: DPM-Solver++(2M)'s history term in the place of the draw,
+// the history then holding x0'.  NOISY (DDNM+): the correction scaled by the row's lam and the draw of a measured element by the row's
+// sgm instead of sigma.  GRAY: the correction also scaled by A+'s factor a_c of the element's channel.  Pointwise n = 1: the block is
+// the element, so x0' = y where measured with no arithmetic (known pixels come back bit for bit at row 0), under NOISY x0 + lam (y - x0).
+// These functions are the arithmetic of both tails, every operation rounded on its own, so given the same eps_hat the tails are
+// bit-identical.
+template <StepKind K>
+struct RestoreTraits {
+    static constexpr bool RESTORE = K == StepKind::Restore || K == StepKind::RestoreMasked || K == StepKind::RestoreMultistep ||
+                                    K == StepKind::RestoreNoisy || K == StepKind::RestoreGray;
+    static constexpr bool MASK = RESTORE && K != StepKind::Restore;
+    static constexpr bool MASK_REQUIRED = K == StepKind::RestoreMasked;
+    static constexpr bool HIST = K == StepKind::RestoreMultistep;
+    static constexpr bool NOISY = K == StepKind::RestoreNoisy || K == StepKind::RestoreGray;
+    static constexpr bool GRAY = K == StepKind::RestoreGray;
+    static constexpr bool POINT = MASK && !GRAY;      // n = 1 is pointwise
+};
+
 __device__ __forceinline__ float rst_x0(float x, float e, float cr, float crm1) {
     const float x0 = __fsub_rn(__fmul_rn(cr, x), __fmul_rn(crm1, e));     // as p_step
     return fminf(fmaxf(x0, -1.0f), 1.0f);
@@ -212,36 +233,39 @@ __device__ __forceinline__ float rst_block_mean(F&& x0_at, int n) {
     return __fmul_rn(s, 1.0f / (float)(n * n));                           // n a power of two: exact
 }
 
-__device__ __forceinline__ float rst_finish(float x, float x0, float m, float y, float z, float c1, float c2, float sg) {
-    const float x0p = __fadd_rn(x0, __fsub_rn(y, m));
-    const float mean = __fadd_rn(__fmul_rn(c1, x0p), __fmul_rn(c2, x));
-    return __fadd_rn(mean, __fmul_rn(sg, z));
+// m: A x0 of the element's block or group (POINT: not read); mk: its mask value; lam: NOISY; ac: GRAY
+template <StepKind K, bool POINT = false>
+__device__ __forceinline__ float rst_x0p(float x0, float m, float y, float mk, float lam, float ac) {
+    using T = RestoreTraits<K>;
+    float x0p = y;
+    if constexpr (!POINT || T::NOISY) {
+        float d = __fsub_rn(y, POINT ? x0 : m);
+        if constexpr (T::GRAY) d = __fmul_rn(ac, d);
+        if constexpr (T::NOISY) d = __fmul_rn(lam, d);
+        x0p = __fadd_rn(x0, d);
+    }
+    if constexpr (T::MASK) return mk != 0.0f ? x0p : x0;
+    return x0p;
 }
 
-// DDNM with a mask over the measurements, A = M o pool_n: a measured block takes rst_finish's x0', a block that
-// is not measured keeps its clipped x0 -- a select on the mask, so whatever y holds there (NaN included) reaches no result.  n = 1
-// (inpainting): x0' = y where measured, no arithmetic, so at row 0 (c1 = 1, c2 = 0, no draw) known pixels come back bit for bit.
-// With every block measured rstm_finish is rst_finish.  The arithmetic of both tails, as rst_* above.
-__device__ __forceinline__ float rstm_finish(float x, float x0, float m, float y, float mk, float z, float c1, float c2, float sg) {
-    const float x0p = mk != 0.0f ? __fadd_rn(x0, __fsub_rn(y, m)) : x0;
+// zh: the draw, or (HIST) the history, which leaves holding x0'; a5: sigma, or (HIST) c3; sgm: NOISY
+template <StepKind K>
+__device__ __forceinline__ float rst_finish(float x, float x0p, float mk, float& zh, float c1, float c2, float a5, float sgm) {
+    using T = RestoreTraits<K>;
     const float mean = __fadd_rn(__fmul_rn(c1, x0p), __fmul_rn(c2, x));
-    return __fadd_rn(mean, __fmul_rn(sg, z));
+    float sc = a5;
+    if constexpr (T::NOISY) sc = mk != 0.0f ? sgm : a5;
+    const float out = __fadd_rn(mean, __fmul_rn(sc, zh));
+    if constexpr (T::HIST) zh = x0p;
+    return out;
 }
 
-__device__ __forceinline__ float rstm_point(float x, float e, float y, float mk, float z, float cr, float crm1, float c1, float c2, float sg) {
-    const float x0p = mk != 0.0f ? y : rst_x0(x, e, cr, crm1);
-    const float mean = __fadd_rn(__fmul_rn(c1, x0p), __fmul_rn(c2, x));
-    return __fadd_rn(mean, __fmul_rn(sg, z));
-}
-
-__device__ __forceinline__ float4 rstm_point4(float4 xv, float4 ev, float4 yv, float4 mv, float4 zv, float cr, float crm1, float c1, float c2,
-                                              float sg) {
-    float4 o;
-    o.x = rstm_point(xv.x, ev.x, yv.x, mv.x, zv.x, cr, crm1, c1, c2, sg);
-    o.y = rstm_point(xv.y, ev.y, yv.y, mv.y, zv.y, cr, crm1, c1, c2, sg);
-    o.z = rstm_point(xv.z, ev.z, yv.z, mv.z, zv.z, cr, crm1, c1, c2, sg);
-    o.w = rstm_point(xv.w, ev.w, yv.w, mv.w, zv.w, cr, crm1, c1, c2, sg);
-    return o;
+// the pointwise step (n = 1) of one element
+template <StepKind K>
+__device__ __forceinline__ float rst_point(float x, float e, float y, float mk, float& zh, float cr, float crm1, float c1, float c2, float a5,
+                                           float lam, float sgm) {
+    const float x0 = rst_x0(x, e, cr, crm1);
+    return rst_finish<K>(x, rst_x0p<K, true>(x0, x0, y, mk, lam, 1.0f), mk, zh, c1, c2, a5, sgm);
 }
 
 // the n = 1 mask values of elements e0 .. e0 + 3 (e0 % 4 == 0) of an NHWC map with C channels, mk pointing at the map's first pixel:
@@ -256,111 +280,40 @@ __device__ __forceinline__ float4 rstm_mask4(const float* __restrict__ mk, unsig
 
 __device__ __forceinline__ float comp4(float4 v, int k) { return k == 0 ? v.x : k == 1 ? v.y : k == 2 ? v.z : v.w; }
 
-// The last kernel of an unfused Restore step.  p_update_kernel's flat float4 loop cannot see an element's neighbours, so here a
-// thread owns one (image, block, channel): it sums the block's n x n clipped x0 from x and eps_hat, then updates those n x n
-// elements of x in place (nobody else reads them).  Any n_out, any H, W that n divides.  Element e of the NHWC latent takes
-// component e & 3 of the Philox draw of float4 e >> 2, the Ancestral kind's keying; the counter and the key as in p_update_kernel.
-// MASKED (StepKind::RestoreMasked, n >= 2): the block's mask value, uniform per thread, selects rstm_finish's x0'.
-template <bool MASKED>
+// what the unfused restore kernels begin with: the counter decrement and the chain's Philox key, as in p_update_kernel
+__device__ __forceinline__ void rst_prologue(int64_t* dec_counter, const int64_t* __restrict__ chain_state, uint64_t& seed, uint32_t& stream) {
+    if (dec_counter && blockIdx.x == 0 && threadIdx.x == 0) *dec_counter -= 1;
+    if (chain_state) {
+        seed = (uint64_t)chain_state[1];
+        stream = (uint32_t)chain_state[2];
+    }
+}
+
+// the row's coefficients of a restore step: c_recip, c_recipm1, c1, c2, the fifth (sigma with its t > 0 mask, or HIST: c3), NOISY: lam, sgm
+struct RestoreCoef {
+    float cr, crm1, a1, a2, a5, lam, sgm;
+};
+template <StepKind K>
+__device__ __forceinline__ RestoreCoef rst_coef(const StepRule& r, int64_t tb) {
+    RestoreCoef k{r.c_recip[tb], r.c_recipm1[tb], r.c1[tb], r.c2[tb], 0.0f, 0.0f, 0.0f};
+    if constexpr (RestoreTraits<K>::HIST) k.a5 = r.c3[tb];
+    else k.a5 = tb > 0 ? r.sigma[tb] : 0.0f;
+    if constexpr (RestoreTraits<K>::NOISY) { k.lam = r.nsy.lam[tb]; k.sgm = r.nsy.sgm[tb]; }
+    return k;
+}
+
+// The last kernel of an unfused restore step with n >= 2 (Restore, RestoreMasked, RestoreMultistep, RestoreNoisy).  p_update_kernel's flat
+// float4 loop cannot see an element's neighbours, so here a thread owns one (image, block, channel): it sums the block's n x n clipped
+// x0 from x and eps_hat, then updates those n x n elements of x (HIST: and of the history) in place; nobody else reads them.  Any
+// n_out, any H, W that n divides.  y is [B][H/n][W/n][n_out], the mask [B][H/n][W/n].  Element e of the NHWC latent takes component
+// e & 3 of the Philox draw of float4 e >> 2, the Ancestral kind's keying.
+template <StepKind K>
 __global__ __launch_bounds__(256) void p_update_restore_kernel(const StepRule r, const float* __restrict__ eps_hat,
                                                                const int64_t* __restrict__ t, int B, int n_out, uint64_t seed,
                                                                uint32_t stream, const int64_t* __restrict__ chain_state,
                                                                int64_t* dec_counter) {
-    if (dec_counter && blockIdx.x == 0 && threadIdx.x == 0) *dec_counter -= 1;
-    if (chain_state) {
-        seed = (uint64_t)chain_state[1];
-        stream = (uint32_t)chain_state[2];
-    }
-    const int n = r.rst.n, H = r.rst.H, W = r.rst.W, Hn = H / n, Wn = W / n;
-    const long long total = (long long)B * Hn * Wn * n_out;
-    float* __restrict__ x = r.x;
-    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-        const int c = (int)(i % n_out);
-        long long q = i / n_out;
-        const int bc = (int)(q % Wn);
-        q /= Wn;
-        const int br = (int)(q % Hn), b = (int)(q / Hn);
-        const int64_t tb = t[b];
-        const float cr = r.c_recip[tb], crm1 = r.c_recipm1[tb], a1 = r.c1[tb], a2 = r.c2[tb], sg = tb > 0 ? r.sigma[tb] : 0.0f;
-        const long long e0 = (((long long)b * H + br * n) * W + bc * n) * n_out + c;       // the block's first element
-        const float m = rst_block_mean(
-            [&](int bi, int bj) {
-                const long long e = e0 + ((long long)bi * W + bj) * n_out;
-                return rst_x0(x[e], eps_hat[e], cr, crm1);
-            },
-            n);
-        const float yv = r.rst.y[i];                                      // y is [B][H/n][W/n][n_out]: this thread's index
-        float mk = 1.0f;
-        if constexpr (MASKED) mk = r.rst.mask[i / n_out];                 // the mask is [B][H/n][W/n]
-        for (int bi = 0; bi < n; ++bi)
-            for (int bj = 0; bj < n; ++bj) {
-                const long long e = e0 + ((long long)bi * W + bj) * n_out;
-                const float xv = x[e];
-                const float z = comp4(philox_normal4((unsigned long long)(e >> 2), (uint32_t)tb, stream, seed), (int)(e & 3));
-                if constexpr (MASKED) x[e] = rstm_finish(xv, rst_x0(xv, eps_hat[e], cr, crm1), m, yv, mk, z, a1, a2, sg);
-                else x[e] = rst_finish(xv, rst_x0(xv, eps_hat[e], cr, crm1), m, yv, z, a1, a2, sg);
-            }
-    }
-}
-
-// The last kernel of an unfused RestoreMasked step with n = 1 (inpainting): pointwise, so p_update_kernel's flat float4 loop with one
-// Philox call per float4; y has x's layout, the mask is [B][H][W] and the float4's elements look up their own pixels (rstm_mask4).
-__global__ __launch_bounds__(256) void p_update_restore_point_kernel(const StepRule r, const float* __restrict__ eps_hat,
-                                                                     const int64_t* __restrict__ t, long long per4, long long total4,
-                                                                     int n_out, uint64_t seed, uint32_t stream,
-                                                                     const int64_t* __restrict__ chain_state, int64_t* dec_counter) {
-    if (dec_counter && blockIdx.x == 0 && threadIdx.x == 0) *dec_counter -= 1;
-    if (chain_state) {
-        seed = (uint64_t)chain_state[1];
-        stream = (uint32_t)chain_state[2];
-    }
-    float4* __restrict__ x = reinterpret_cast<float4*>(r.x);
-    const long long hw = (long long)r.rst.H * r.rst.W;
-    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total4; i += (long long)gridDim.x * 256) {
-        const long long b = i / per4;
-        const int64_t tb = t[b];
-        const float cr = r.c_recip[tb], crm1 = r.c_recipm1[tb], a1 = r.c1[tb], a2 = r.c2[tb], sg = tb > 0 ? r.sigma[tb] : 0.0f;
-        const float4 xv = x[i], ev = reinterpret_cast<const float4*>(eps_hat)[i], yv = reinterpret_cast<const float4*>(r.rst.y)[i];
-        const float4 mv = rstm_mask4(r.rst.mask + b * hw, (unsigned)(i - b * per4) * 4u, (unsigned)n_out);      // host: per < 2^31
-        const float4 zv = philox_normal4((unsigned long long)i, (uint32_t)tb, stream, seed);
-        x[i] = rstm_point4(xv, ev, yv, mv, zv, cr, crm1, a1, a2, sg);
-    }
-}
-
-// DDNM on the DPM-Solver++(2M) chain: rst_x0's clipped x0, its DDNM projection x0' (the x0' of rst_finish /
-// rstm_finish at n >= 2 and of rstm_point at n = 1, restated here so that those kernels keep their instructions), then ms_step's update
-// on x0' with the history holding x0': x_prev = (c1 x0' + c2 x) + c3 h, h <- x0'.  No draw.  mk is the block's (n = 1: the pixel's) mask
-// value, 1 without a mask; an unmeasured y is only ever selected against.  The arithmetic of both tails.
-__device__ __forceinline__ float rsm_x0p(float x0, float m, float y, float mk) { return mk != 0.0f ? __fadd_rn(x0, __fsub_rn(y, m)) : x0; }
-
-__device__ __forceinline__ float rsm_point_x0p(float x0, float y, float mk) { return mk != 0.0f ? y : x0; }
-
-__device__ __forceinline__ float rsm_finish(float x, float x0p, float& h, float c1, float c2, float c3) {
-    const float mean = __fadd_rn(__fmul_rn(c1, x0p), __fmul_rn(c2, x));
-    const float out = __fadd_rn(mean, __fmul_rn(c3, h));
-    h = x0p;
-    return out;
-}
-
-__device__ __forceinline__ float rsm_point(float x, float e, float y, float mk, float& h, float cr, float crm1, float c1, float c2, float c3) {
-    return rsm_finish(x, rsm_point_x0p(rst_x0(x, e, cr, crm1), y, mk), h, c1, c2, c3);
-}
-
-__device__ __forceinline__ float4 rsm_point4(float4 xv, float4 ev, float4 yv, float4 mv, float4& h, float cr, float crm1, float c1, float c2,
-                                             float c3) {
-    float4 o;
-    o.x = rsm_point(xv.x, ev.x, yv.x, mv.x, h.x, cr, crm1, c1, c2, c3);
-    o.y = rsm_point(xv.y, ev.y, yv.y, mv.y, h.y, cr, crm1, c1, c2, c3);
-    o.z = rsm_point(xv.z, ev.z, yv.z, mv.z, h.z, cr, crm1, c1, c2, c3);
-    o.w = rsm_point(xv.w, ev.w, yv.w, mv.w, h.w, cr, crm1, c1, c2, c3);
-    return o;
-}
-
-// The last kernel of an unfused RestoreMultistep step with n >= 2: p_update_restore_kernel's block owner, which also reads and
-// rewrites the history of the n x n elements it owns.  r.rst.mask may be null (every block measured).  No draw, so no Philox key.
-__global__ __launch_bounds__(256) void p_update_restore_ms_kernel(const StepRule r, const float* __restrict__ eps_hat,
-                                                                  const int64_t* __restrict__ t, int B, int n_out, int64_t* dec_counter) {
-    if (dec_counter && blockIdx.x == 0 && threadIdx.x == 0) *dec_counter -= 1;
+    using T = RestoreTraits<K>;
+    rst_prologue(dec_counter, chain_state, seed, stream);
     const int n = r.rst.n, H = r.rst.H, W = r.rst.W, Hn = H / n, Wn = W / n;
     const long long total = (long long)B * Hn * Wn * n_out;
     float* __restrict__ x = r.x;
@@ -372,148 +325,62 @@ __global__ __launch_bounds__(256) void p_update_restore_ms_kernel(const StepRule
         q /= Wn;
         const int br = (int)(q % Hn), b = (int)(q / Hn);
         const int64_t tb = t[b];
-        const float cr = r.c_recip[tb], crm1 = r.c_recipm1[tb], a1 = r.c1[tb], a2 = r.c2[tb], a3 = r.c3[tb];
+        const RestoreCoef k = rst_coef<K>(r, tb);
         const long long e0 = (((long long)b * H + br * n) * W + bc * n) * n_out + c;       // the block's first element
         const float m = rst_block_mean(
             [&](int bi, int bj) {
                 const long long e = e0 + ((long long)bi * W + bj) * n_out;
-                return rst_x0(x[e], eps_hat[e], cr, crm1);
+                return rst_x0(x[e], eps_hat[e], k.cr, k.crm1);
             },
             n);
-        const float yv = r.rst.y[i];                                      // y is [B][H/n][W/n][n_out]: this thread's index
-        const float mk = r.rst.mask ? r.rst.mask[i / n_out] : 1.0f;       // the mask is [B][H/n][W/n]
+        const float yv = r.rst.y[i];                                      // this thread's index
+        float mk = 1.0f;
+        if constexpr (T::MASK) mk = T::MASK_REQUIRED || r.rst.mask ? r.rst.mask[i / n_out] : 1.0f;
         for (int bi = 0; bi < n; ++bi)
             for (int bj = 0; bj < n; ++bj) {
                 const long long e = e0 + ((long long)bi * W + bj) * n_out;
                 const float xv = x[e];
-                float hv = hist[e];
-                x[e] = rsm_finish(xv, rsm_x0p(rst_x0(xv, eps_hat[e], cr, crm1), m, yv, mk), hv, a1, a2, a3);
-                hist[e] = hv;
+                float zh;
+                if constexpr (T::HIST) zh = hist[e];
+                else zh = comp4(philox_normal4((unsigned long long)(e >> 2), (uint32_t)tb, stream, seed), (int)(e & 3));
+                x[e] = rst_finish<K>(xv, rst_x0p<K>(rst_x0(xv, eps_hat[e], k.cr, k.crm1), m, yv, mk, k.lam, 1.0f), mk, zh, k.a1, k.a2, k.a5, k.sgm);
+                if constexpr (T::HIST) hist[e] = zh;
             }
     }
 }
 
-// ... and with n = 1 (inpainting): p_update_restore_point_kernel's flat float4 loop with the history float4 read and rewritten
-__global__ __launch_bounds__(256) void p_update_restore_ms_point_kernel(const StepRule r, const float* __restrict__ eps_hat,
-                                                                        const int64_t* __restrict__ t, long long per4, long long total4,
-                                                                        int n_out, int64_t* dec_counter) {
-    if (dec_counter && blockIdx.x == 0 && threadIdx.x == 0) *dec_counter -= 1;
+// ... and with n = 1 (RestoreMasked, RestoreMultistep, RestoreNoisy; the mask is required): pointwise, so p_update_kernel's flat float4
+// loop with one Philox call (HIST: one history float4, read and rewritten) per float4; y has x's layout, the mask is [B][H][W] and the
+// float4's elements look up their own pixels (rstm_mask4).
+template <StepKind K>
+__global__ __launch_bounds__(256) void p_update_restore_point_kernel(const StepRule r, const float* __restrict__ eps_hat,
+                                                                     const int64_t* __restrict__ t, long long per4, long long total4,
+                                                                     int n_out, uint64_t seed, uint32_t stream,
+                                                                     const int64_t* __restrict__ chain_state, int64_t* dec_counter) {
+    using T = RestoreTraits<K>;
+    static_assert(T::POINT, "the kinds whose n = 1 is pointwise");
+    rst_prologue(dec_counter, chain_state, seed, stream);
     float4* __restrict__ x = reinterpret_cast<float4*>(r.x);
     float4* __restrict__ hist = reinterpret_cast<float4*>(r.x0_hist);
     const long long hw = (long long)r.rst.H * r.rst.W;
     for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total4; i += (long long)gridDim.x * 256) {
         const long long b = i / per4;
         const int64_t tb = t[b];
-        const float cr = r.c_recip[tb], crm1 = r.c_recipm1[tb], a1 = r.c1[tb], a2 = r.c2[tb], a3 = r.c3[tb];
+        const RestoreCoef k = rst_coef<K>(r, tb);
         const float4 xv = x[i], ev = reinterpret_cast<const float4*>(eps_hat)[i], yv = reinterpret_cast<const float4*>(r.rst.y)[i];
         const float4 mv = rstm_mask4(r.rst.mask + b * hw, (unsigned)(i - b * per4) * 4u, (unsigned)n_out);      // host: per < 2^31
-        float4 hv = hist[i];
-        x[i] = rsm_point4(xv, ev, yv, mv, hv, cr, crm1, a1, a2, a3);
-        hist[i] = hv;
+        float4 zh;
+        if constexpr (T::HIST) zh = hist[i];
+        else zh = philox_normal4((unsigned long long)i, (uint32_t)tb, stream, seed);
+        x[i] = each4([&](float xe, float e, float y, float mk, float& z) { return rst_point<K>(xe, e, y, mk, z, k.cr, k.crm1, k.a1, k.a2, k.a5, k.lam, k.sgm); },
+                     xv, ev, yv, mv, zh);
+        if constexpr (T::HIST) hist[i] = zh;
     }
 }
 
-// DDNM+ for a noisy measurement (Wang, Yu, Zhang 2023, section 3.3): rst_x0's clipped x0, the DDNM correction of
-// rstm_finish scaled by the row's lam (n = 1: the correction is y - x0, so m = x0), then rst_finish's update with the draw of a measured
-// element scaled by the row's sgm instead of sigma: the noise that enters through y, c1 lam sigma_y, and the draw add up to sigma^2.  mk is
-// the block's (n = 1: the pixel's) mask value, 1 without a mask; both uses of it are selects, so an unmeasured y reaches no result.
-// Restated beside rstm_* / rsm_* so that those kernels keep their instructions.  The arithmetic of both tails.
-__device__ __forceinline__ float rsn_x0p(float x0, float m, float y, float mk, float lam) {
-    return mk != 0.0f ? __fadd_rn(x0, __fmul_rn(lam, __fsub_rn(y, m))) : x0;
-}
-
-__device__ __forceinline__ float rsn_finish(float x, float x0p, float mk, float z, float c1, float c2, float sg, float sgm) {
-    const float mean = __fadd_rn(__fmul_rn(c1, x0p), __fmul_rn(c2, x));
-    return __fadd_rn(mean, __fmul_rn(mk != 0.0f ? sgm : sg, z));
-}
-
-__device__ __forceinline__ float rsn_point(float x, float e, float y, float mk, float z, float cr, float crm1, float c1, float c2, float sg,
-                                           float lam, float sgm) {
-    const float x0 = rst_x0(x, e, cr, crm1);
-    return rsn_finish(x, rsn_x0p(x0, x0, y, mk, lam), mk, z, c1, c2, sg, sgm);
-}
-
-__device__ __forceinline__ float4 rsn_point4(float4 xv, float4 ev, float4 yv, float4 mv, float4 zv, float cr, float crm1, float c1, float c2,
-                                             float sg, float lam, float sgm) {
-    float4 o;
-    o.x = rsn_point(xv.x, ev.x, yv.x, mv.x, zv.x, cr, crm1, c1, c2, sg, lam, sgm);
-    o.y = rsn_point(xv.y, ev.y, yv.y, mv.y, zv.y, cr, crm1, c1, c2, sg, lam, sgm);
-    o.z = rsn_point(xv.z, ev.z, yv.z, mv.z, zv.z, cr, crm1, c1, c2, sg, lam, sgm);
-    o.w = rsn_point(xv.w, ev.w, yv.w, mv.w, zv.w, cr, crm1, c1, c2, sg, lam, sgm);
-    return o;
-}
-
-// The last kernel of an unfused RestoreNoisy step with n >= 2: p_update_restore_kernel's block owner with the row's lam and sgm.
-// r.rst.mask may be null (every block measured).  The draw, the counter and the key as there.
-__global__ __launch_bounds__(256) void p_update_restore_noisy_kernel(const StepRule r, const float* __restrict__ eps_hat,
-                                                                     const int64_t* __restrict__ t, int B, int n_out, uint64_t seed,
-                                                                     uint32_t stream, const int64_t* __restrict__ chain_state,
-                                                                     int64_t* dec_counter) {
-    if (dec_counter && blockIdx.x == 0 && threadIdx.x == 0) *dec_counter -= 1;
-    if (chain_state) {
-        seed = (uint64_t)chain_state[1];
-        stream = (uint32_t)chain_state[2];
-    }
-    const int n = r.rst.n, H = r.rst.H, W = r.rst.W, Hn = H / n, Wn = W / n;
-    const long long total = (long long)B * Hn * Wn * n_out;
-    float* __restrict__ x = r.x;
-    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-        const int c = (int)(i % n_out);
-        long long q = i / n_out;
-        const int bc = (int)(q % Wn);
-        q /= Wn;
-        const int br = (int)(q % Hn), b = (int)(q / Hn);
-        const int64_t tb = t[b];
-        const float cr = r.c_recip[tb], crm1 = r.c_recipm1[tb], a1 = r.c1[tb], a2 = r.c2[tb], sg = tb > 0 ? r.sigma[tb] : 0.0f;
-        const float lam = r.nsy.lam[tb], sgm = r.nsy.sgm[tb];
-        const long long e0 = (((long long)b * H + br * n) * W + bc * n) * n_out + c;       // the block's first element
-        const float m = rst_block_mean(
-            [&](int bi, int bj) {
-                const long long e = e0 + ((long long)bi * W + bj) * n_out;
-                return rst_x0(x[e], eps_hat[e], cr, crm1);
-            },
-            n);
-        const float yv = r.rst.y[i];                                      // y is [B][H/n][W/n][n_out]: this thread's index
-        const float mk = r.rst.mask ? r.rst.mask[i / n_out] : 1.0f;       // the mask is [B][H/n][W/n]
-        for (int bi = 0; bi < n; ++bi)
-            for (int bj = 0; bj < n; ++bj) {
-                const long long e = e0 + ((long long)bi * W + bj) * n_out;
-                const float xv = x[e];
-                const float z = comp4(philox_normal4((unsigned long long)(e >> 2), (uint32_t)tb, stream, seed), (int)(e & 3));
-                x[e] = rsn_finish(xv, rsn_x0p(rst_x0(xv, eps_hat[e], cr, crm1), m, yv, mk, lam), mk, z, a1, a2, sg, sgm);
-            }
-    }
-}
-
-// ... and with n = 1: p_update_restore_point_kernel's flat float4 loop with the row's lam and sgm (the mask is required)
-__global__ __launch_bounds__(256) void p_update_restore_noisy_point_kernel(const StepRule r, const float* __restrict__ eps_hat,
-                                                                           const int64_t* __restrict__ t, long long per4, long long total4,
-                                                                           int n_out, uint64_t seed, uint32_t stream,
-                                                                           const int64_t* __restrict__ chain_state, int64_t* dec_counter) {
-    if (dec_counter && blockIdx.x == 0 && threadIdx.x == 0) *dec_counter -= 1;
-    if (chain_state) {
-        seed = (uint64_t)chain_state[1];
-        stream = (uint32_t)chain_state[2];
-    }
-    float4* __restrict__ x = reinterpret_cast<float4*>(r.x);
-    const long long hw = (long long)r.rst.H * r.rst.W;
-    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total4; i += (long long)gridDim.x * 256) {
-        const long long b = i / per4;
-        const int64_t tb = t[b];
-        const float cr = r.c_recip[tb], crm1 = r.c_recipm1[tb], a1 = r.c1[tb], a2 = r.c2[tb], sg = tb > 0 ? r.sigma[tb] : 0.0f;
-        const float lam = r.nsy.lam[tb], sgm = r.nsy.sgm[tb];
-        const float4 xv = x[i], ev = reinterpret_cast<const float4*>(eps_hat)[i], yv = reinterpret_cast<const float4*>(r.rst.y)[i];
-        const float4 mv = rstm_mask4(r.rst.mask + b * hw, (unsigned)(i - b * per4) * 4u, (unsigned)n_out);      // host: per < 2^31
-        const float4 zv = philox_normal4((unsigned long long)i, (uint32_t)tb, stream, seed);
-        x[i] = rsn_point4(xv, ev, yv, mv, zv, cr, crm1, a1, a2, sg, lam, sgm);
-    }
-}
-
-// DDNM / DDNM+ for a grey measurement of a 3-channel map: A = mask o pool_n o grey_w.  The group of an element
-// is its n x n block over all three channels; the group value is the weighted sum in row-major order, channel innermost, times NORM;
-// the correction d = y - m goes to channel c scaled by A+'s factor a_c (and by the row's lam), then rsn_finish.  mean: w = a = 1 and
-// NORM = 1 / (3 n n) (the products by 1 are exact); luma (BT.601): w_c, NORM = 1 / (n n), a_c = w_c / (w . w) formed in double.  Every
-// operation is rounded on its own; the arithmetic of both tails.
+// The grey measurement of a 3-channel map: the group of an element is its n x n block over all three channels;
+// the group value is the weighted sum in row-major order, channel innermost, times NORM.  mean: w = a = 1 and NORM = 1 / (3 n n) (the
+// products by 1 are exact); luma (BT.601): w_c, NORM = 1 / (n n), a_c = w_c / (w . w) formed in double.
 struct GrayCoef {
     float w0, w1, w2, a0, a1, a2, norm;
 };
@@ -540,51 +407,42 @@ __device__ __forceinline__ float gry_group(F&& x0_at, int n, const GrayCoef& k) 
     return __fmul_rn(g, k.norm);
 }
 
-// d = y[group] - m; ac = a_c of the element's channel.  A select on the mask: an unmeasured y (d may be NaN) reaches no result.
-__device__ __forceinline__ float gry_x0p(float x0, float d, float mk, float lam, float ac) {
-    return mk != 0.0f ? __fadd_rn(x0, __fmul_rn(lam, __fmul_rn(ac, d))) : x0;
-}
-
 // The last kernel of an unfused RestoreGray step, n in {1, 2, 4, 8}: a thread owns one (image, block) with all three channels, forms the
 // group value from x and eps_hat, then updates the block's n n 3 elements in place (no other thread touches them).  r.rst.y and
-// r.rst.mask are [B][H/n][W/n]; the mask may be null (every block measured).  The draw, the counter and the key as p_update_restore_kernel's.
+// r.rst.mask are [B][H/n][W/n]; the mask may be null (every block measured).  The draw as p_update_restore_kernel's.
 __global__ __launch_bounds__(256) void p_update_restore_gray_kernel(const StepRule r, const float* __restrict__ eps_hat,
                                                                     const int64_t* __restrict__ t, int B, uint64_t seed, uint32_t stream,
                                                                     const int64_t* __restrict__ chain_state, int64_t* dec_counter) {
-    if (dec_counter && blockIdx.x == 0 && threadIdx.x == 0) *dec_counter -= 1;
-    if (chain_state) {
-        seed = (uint64_t)chain_state[1];
-        stream = (uint32_t)chain_state[2];
-    }
+    constexpr StepKind K = StepKind::RestoreGray;
+    rst_prologue(dec_counter, chain_state, seed, stream);
     const int n = r.rst.n, H = r.rst.H, W = r.rst.W, Hn = H / n, Wn = W / n;
     const long long total = (long long)B * Hn * Wn;
-    const GrayCoef k = gry_coef(r.rst.gray, n);
+    const GrayCoef g = gry_coef(r.rst.gray, n);
     float* __restrict__ x = r.x;
     for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
         const int bc = (int)(i % Wn);
         const long long q = i / Wn;
         const int br = (int)(q % Hn), b = (int)(q / Hn);
         const int64_t tb = t[b];
-        const float cr = r.c_recip[tb], crm1 = r.c_recipm1[tb], a1 = r.c1[tb], a2 = r.c2[tb], sg = tb > 0 ? r.sigma[tb] : 0.0f;
-        const float lam = r.nsy.lam[tb], sgm = r.nsy.sgm[tb];
+        const RestoreCoef k = rst_coef<K>(r, tb);
         const long long e0 = (((long long)b * H + br * n) * W + bc * n) * 3;       // the group's first element
         const float m = gry_group(
             [&](int bi, int bj, int c) {
                 const long long e = e0 + ((long long)bi * W + bj) * 3 + c;
-                return rst_x0(x[e], eps_hat[e], cr, crm1);
+                return rst_x0(x[e], eps_hat[e], k.cr, k.crm1);
             },
-            n, k);
+            n, g);
         const float mk = r.rst.mask ? r.rst.mask[i] : 1.0f;
-        const float d = __fsub_rn(r.rst.y[i], m);
+        const float yv = r.rst.y[i];
         for (int bi = 0; bi < n; ++bi)
             for (int bj = 0; bj < n; ++bj)
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
                     const long long e = e0 + ((long long)bi * W + bj) * 3 + c;
                     const float xv = x[e];
-                    const float z = comp4(philox_normal4((unsigned long long)(e >> 2), (uint32_t)tb, stream, seed), (int)(e & 3));
-                    const float ac = c == 0 ? k.a0 : c == 1 ? k.a1 : k.a2;
-                    x[e] = rsn_finish(xv, gry_x0p(rst_x0(xv, eps_hat[e], cr, crm1), d, mk, lam, ac), mk, z, a1, a2, sg, sgm);
+                    float z = comp4(philox_normal4((unsigned long long)(e >> 2), (uint32_t)tb, stream, seed), (int)(e & 3));
+                    const float ac = c == 0 ? g.a0 : c == 1 ? g.a1 : g.a2;
+                    x[e] = rst_finish<K>(xv, rst_x0p<K>(rst_x0(xv, eps_hat[e], k.cr, k.crm1), m, yv, mk, k.lam, ac), mk, z, k.a1, k.a2, k.a5, k.sgm);
                 }
     }
 }
@@ -687,28 +545,22 @@ struct TailParams {
 // where the other kinds draw their noise (no Philox rounds), and the thread that read it writes it back.
 // Inpaint (ddk_sampler_run_inpaint, x given, Philox only): RePaint's op of p_update_kernel; the known float4, the mask float4 and
 // the two extra draws are requested in the same prologue, and x_kn is formed there (4 registers live, not 8).
-// Restore (ddk_sampler_run_restore, x given, Philox only, 128 % (W n) == 0 so that the tile holds whole rows of blocks): the y of
-// each of the thread's four elements is requested in the prologue; in phase 2 the owners write their clipped x0 over eps_hat in LDS,
-// and one barrier later every owner sums its elements' blocks from LDS (rst_block_mean) and finishes the update of
-// p_update_restore_kernel: neither x0 nor eps_hat goes through memory.
-// RestoreMasked (ddk_sampler_run_restore_masked, x given, Philox only): n >= 2 is Restore's tail with the mask value of each element's
-// block requested beside its y; n = 1 (uniform per launch) needs no whole blocks in the tile: the y float4 and the mask are requested where
-// Inpaint requests known and mask, and phase 2 is p_update_restore_point_kernel's select, with no second barrier.  No LDS beyond Restore's.
-// RestoreMultistep (ddk_sampler_run_restore_multistep, x given, no draw): RestoreMasked's requests and phase 2 with the history float4
-// requested where Multistep requests it; the owner writes x0' back to the history (n >= 2: after the block means are formed from LDS).
-// rst.mask may be null at n >= 2 (every block measured).
-// RestoreNoisy (ddk_sampler_run_restore_noisy, x given, Philox only): RestoreMultistep's requests of y and the optional mask (RestoreMasked's
-// places), the row's lam and sgm loaded with its other coefficients, and RestoreMasked's phase 2 with rsn_x0p / rsn_finish (n = 1: rsn_point4).
-// RestoreGray (ddk_sampler_run_restore_gray, x given, Philox only, n_out == 3): y and the optional mask of each element's block are
-// requested in the prologue (both [B][H/n][W/n]; n = 1: the element's pixel), lam and sgm as RestoreNoisy's; phase 2 is Restore's x0-over-
-// eps_hat exchange and second barrier at every n, n = 1 included (a pixel's three channels straddle float4s), then each element's thread
-// sums its n x n x 3 group from LDS (gry_group) and finishes with gry_x0p / rsn_finish.
+// The restore kinds (ddk_sampler_run_restore*, x given, Philox only or -- RestoreMultistep -- no draw; flags as RestoreTraits): the y
+// and, where the kind has one, the mask value of the block of each of the thread's four elements are requested in the prologue; in
+// phase 2 the owners write their clipped x0 over eps_hat in LDS, and one barrier later every owner forms its elements' block values
+// from LDS (rst_block_mean; GRAY: gry_group) and finishes with rst_x0p / rst_finish: neither x0 nor eps_hat goes through memory.  The
+// 128-pixel tile must hold whole rows of blocks, 128 % (W n) == 0.  Per kind:
+//   MASK, n = 1 (uniform per launch; RestoreMasked, RestoreMultistep, RestoreNoisy): pointwise, so no whole blocks needed: the y float4
+//     and the mask are requested where Inpaint requests known and mask, and phase 2 is rst_point, with no second barrier
+//   HIST: the history float4 is requested where Multistep requests it, and the owner writes x0' back to it
+//   NOISY: the row's lam and sgm are loaded with its other coefficients
+//   GRAY (n_out == 3): y and the mask have one value per block; the exchange and the second barrier at every n, n = 1 included (a
+//     pixel's three channels straddle float4s)
 template <int LPP, int VPL, StepKind K>
 __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
     static_assert(K != StepKind::Eps, "the plain forward runs the Ancestral instantiation with p.x null");
-    constexpr bool VLB = K == StepKind::Vlb, MS = K == StepKind::Multistep, INP = K == StepKind::Inpaint, RST = K == StepKind::Restore,
-                   RSTM = K == StepKind::RestoreMasked, RSMS = K == StepKind::RestoreMultistep, RSN = K == StepKind::RestoreNoisy,
-                   RSG = K == StepKind::RestoreGray;
+    using RT = RestoreTraits<K>;
+    constexpr bool VLB = K == StepKind::Vlb, MS = K == StepKind::Multistep, INP = K == StepKind::Inpaint, HIST = MS || RT::HIST;
     constexpr int PPW = 64 / LPP;                    // pixels per wave and iteration
     constexpr int PPI = 16 * PPW;                    // ... per iteration of the 16-wave workgroup
     constexpr int NIT = 128 / PPI;                   // 4 at C = 128 / 256, 2 at C = 64, 1 at C = 32
@@ -749,14 +601,14 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
     const long long e4 = pix0 * p.n_out / 4;          // host: (128 * n_out) % 4 == 0
     float4 xv0 = make_float4(0.f, 0.f, 0.f, 0.f), zv0 = xv0;
     float cr = 0.f, crm1 = 0.f, a1 = 0.f, a2 = 0.f, sg = 0.f, a3 = 0.f;
-    float lam = 0.f, sgm = 0.f;                       // RSN, RSG
+    float lam = 0.f, sgm = 0.f;                       // restore, NOISY
     int64_t tb = 0;
     float4 xt0 = xv0;
     float4 xk0 = xv0, mk0 = xv0, z30 = xv0;           // INP: x_kn, the mask, the jump's draw
     float ja = 0.f, jb = 0.f;
     bool jump = false;
-    float yv0[4] = {0.f, 0.f, 0.f, 0.f};              // RST, RSTM: y of the block of each of the thread's four elements
-    float mv0[4] = {0.f, 0.f, 0.f, 0.f};              // RSTM: ... and its mask value
+    float yv0[4] = {0.f, 0.f, 0.f, 0.f};              // restore: y of the block of each of the thread's four elements
+    float mv0[4] = {0.f, 0.f, 0.f, 0.f};              // restore, MASK: ... and its mask value
     VlbCoef kc{};
     if ((VLB || p.x) && tid < cnt4) {
         const uint64_t seed = p.chain_state ? (uint64_t)p.chain_state[1] : p.seed;
@@ -766,14 +618,14 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
             kc = vlb_coef(tb, p.c_recip, p.c_recipm1, p.c1, p.c2, p.logvar);
         } else {
             cr = p.c_recip[tb]; crm1 = p.c_recipm1[tb]; a1 = p.c1[tb]; a2 = p.c2[tb];
-            if constexpr (MS || RSMS) a3 = p.c3[tb];
+            if constexpr (HIST) a3 = p.c3[tb];
             else sg = tb > 0 ? p.sigma[tb] : 0.0f;
-            if constexpr (RSN || RSG) { lam = p.nsy.lam[tb]; sgm = p.nsy.sgm[tb]; }
+            if constexpr (RT::NOISY) { lam = p.nsy.lam[tb]; sgm = p.nsy.sgm[tb]; }
         }
         const long long i = e4 + tid;
         xv0 = reinterpret_cast<const float4*>(p.x)[i];
         if constexpr (VLB) xt0 = reinterpret_cast<const float4*>(p.xt)[i];
-        if constexpr (MS || RSMS) zv0 = reinterpret_cast<const float4*>(p.x0_hist)[i];      // MS, RSMS: zv0 holds the history, not a draw
+        if constexpr (HIST) zv0 = reinterpret_cast<const float4*>(p.x0_hist)[i];      // zv0 holds the history, not a draw
         else zv0 = p.noise ? reinterpret_cast<const float4*>(p.noise + (long long)(p.t_first - tb) * p.noise_step_stride)[i]
                            : philox_normal4((unsigned long long)i, (uint32_t)tb, stream, seed);
         if constexpr (INP) {
@@ -785,60 +637,22 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
                              philox_normal4((unsigned long long)i, (uint32_t)tb, stream | INPAINT_Z2_BIT, seed), ka, kb);
             if (jump) z30 = philox_normal4((unsigned long long)i, (uint32_t)tb, stream | INPAINT_Z3_BIT, seed);
         }
-        if constexpr (RSTM) {
-            if (p.rst.n == 1) {                        // one block per launch: uniform
+        if constexpr (RT::RESTORE) {
+            if (RT::POINT && p.rst.n == 1) {           // one block per launch: uniform
                 const float4 yv = reinterpret_cast<const float4*>(p.rst.y)[i];
                 const float4 mv = rstm_mask4(p.rst.mask + pix0, (unsigned)tid * 4u, (unsigned)p.n_out);
                 yv0[0] = yv.x; yv0[1] = yv.y; yv0[2] = yv.z; yv0[3] = yv.w;
                 mv0[0] = mv.x; mv0[1] = mv.y; mv0[2] = mv.z; mv0[3] = mv.w;
             } else {
-                const int W = p.rst.W, n = p.rst.n, Wn = W / n;
-                const long long yrow0 = ((long long)b * p.HW + tile * 128) / (W * n);
+                const int W = p.rst.W, n = p.rst.n, Wn = W / n, no = RT::GRAY ? 3 : p.n_out;      // GRAY: n_out == 3 (final_tail_ok)
+                const long long yrow0 = pix0 / (W * n);          // the tile's first row of blocks, over all images (GRAY, n = 1: not used)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const int lp = (tid * 4 + j) / p.n_out, c = tid * 4 + j - lp * p.n_out, row = lp / W, col = lp - row * W;
-                    const long long blk = (yrow0 + row / n) * Wn + col / n;
-                    yv0[j] = p.rst.y[blk * p.n_out + c];
-                    mv0[j] = p.rst.mask[blk];
+                    const int lp = (tid * 4 + j) / no, c = tid * 4 + j - lp * no, row = lp / W, col = lp - row * W;
+                    const long long blk = RT::GRAY && n == 1 ? pix0 + lp : (yrow0 + row / n) * Wn + col / n;
+                    yv0[j] = p.rst.y[RT::GRAY ? blk : blk * no + c];      // GRAY: one value per block, shared by the three channels
+                    if constexpr (RT::MASK) mv0[j] = RT::MASK_REQUIRED || p.rst.mask ? p.rst.mask[blk] : 1.0f;
                 }
-            }
-        }
-        if constexpr (RSMS || RSN) {                   // RSTM's requests; no mask: every block is measured
-            if (p.rst.n == 1) {
-                const float4 yv = reinterpret_cast<const float4*>(p.rst.y)[i];
-                const float4 mv = rstm_mask4(p.rst.mask + pix0, (unsigned)tid * 4u, (unsigned)p.n_out);
-                yv0[0] = yv.x; yv0[1] = yv.y; yv0[2] = yv.z; yv0[3] = yv.w;
-                mv0[0] = mv.x; mv0[1] = mv.y; mv0[2] = mv.z; mv0[3] = mv.w;
-            } else {
-                const int W = p.rst.W, n = p.rst.n, Wn = W / n;
-                const long long yrow0 = ((long long)b * p.HW + tile * 128) / (W * n);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int lp = (tid * 4 + j) / p.n_out, c = tid * 4 + j - lp * p.n_out, row = lp / W, col = lp - row * W;
-                    const long long blk = (yrow0 + row / n) * Wn + col / n;
-                    yv0[j] = p.rst.y[blk * p.n_out + c];
-                    mv0[j] = p.rst.mask ? p.rst.mask[blk] : 1.0f;
-                }
-            }
-        }
-        if constexpr (RSG) {                           // y and the mask have one value per block, shared by the three channels
-            const int W = p.rst.W, n = p.rst.n, Wn = W / n;
-            const long long yrow0 = pix0 / (W * n);    // n >= 2: the tile holds whole rows of blocks; n = 1: not used
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int lp = (tid * 4 + j) / 3, row = lp / W, col = lp - row * W;
-                const long long blk = n == 1 ? pix0 + lp : (yrow0 + row / n) * Wn + col / n;
-                yv0[j] = p.rst.y[blk];
-                mv0[j] = p.rst.mask ? p.rst.mask[blk] : 1.0f;
-            }
-        }
-        if constexpr (RST) {
-            const int W = p.rst.W, n = p.rst.n, Wn = W / n;
-            const long long yrow0 = ((long long)b * p.HW + tile * 128) / (W * n);     // the tile's first row of blocks, over all images
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int lp = (tid * 4 + j) / p.n_out, c = tid * 4 + j - lp * p.n_out, row = lp / W, col = lp - row * W;
-                yv0[j] = p.rst.y[((yrow0 + row / n) * Wn + col / n) * p.n_out + c];
             }
         }
     }
@@ -912,44 +726,19 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
         if (tid == 0) p.vlb_part[((long long)tb * p.B + b) * p.np + tile] = make_float2(acc, sq);
         return;
     }
-    if constexpr (RSTM) {
-        if (p.rst.n == 1) {
+    if constexpr (RT::RESTORE) {
+        const float a5 = RT::HIST ? a3 : sg;             // zv0: the draw, HIST: the history, which rst_finish rewrites
+        if (RT::POINT && p.rst.n == 1) {
             if (tid < cnt4) {
                 const float4 ev = reinterpret_cast<const float4*>(es)[tid];
                 if (p.eps_out) reinterpret_cast<float4*>(p.eps_out)[e4 + tid] = ev;
                 reinterpret_cast<float4*>(p.x)[e4 + tid] =
-                    rstm_point4(xv0, ev, make_float4(yv0[0], yv0[1], yv0[2], yv0[3]), make_float4(mv0[0], mv0[1], mv0[2], mv0[3]), zv0, cr, crm1,
-                                a1, a2, sg);
+                    each4([&](float x, float e, float y, float mk, float& z) { return rst_point<K>(x, e, y, mk, z, cr, crm1, a1, a2, a5, lam, sgm); },
+                          xv0, ev, make_float4(yv0[0], yv0[1], yv0[2], yv0[3]), make_float4(mv0[0], mv0[1], mv0[2], mv0[3]), zv0);
+                if constexpr (RT::HIST) reinterpret_cast<float4*>(p.x0_hist)[e4 + tid] = zv0;
             }
             return;
         }
-    }
-    if constexpr (RSMS) {
-        if (p.rst.n == 1) {
-            if (tid < cnt4) {
-                const float4 ev = reinterpret_cast<const float4*>(es)[tid];
-                if (p.eps_out) reinterpret_cast<float4*>(p.eps_out)[e4 + tid] = ev;
-                reinterpret_cast<float4*>(p.x)[e4 + tid] =
-                    rsm_point4(xv0, ev, make_float4(yv0[0], yv0[1], yv0[2], yv0[3]), make_float4(mv0[0], mv0[1], mv0[2], mv0[3]), zv0, cr, crm1,
-                               a1, a2, a3);
-                reinterpret_cast<float4*>(p.x0_hist)[e4 + tid] = zv0;
-            }
-            return;
-        }
-    }
-    if constexpr (RSN) {
-        if (p.rst.n == 1) {
-            if (tid < cnt4) {
-                const float4 ev = reinterpret_cast<const float4*>(es)[tid];
-                if (p.eps_out) reinterpret_cast<float4*>(p.eps_out)[e4 + tid] = ev;
-                reinterpret_cast<float4*>(p.x)[e4 + tid] =
-                    rsn_point4(xv0, ev, make_float4(yv0[0], yv0[1], yv0[2], yv0[3]), make_float4(mv0[0], mv0[1], mv0[2], mv0[3]), zv0, cr, crm1,
-                               a1, a2, sg, lam, sgm);
-            }
-            return;
-        }
-    }
-    if constexpr (RST || RSTM || RSMS || RSN || RSG) {
         float x0v[4] = {0.f, 0.f, 0.f, 0.f};
         if (tid < cnt4) {
             const float4 ev = reinterpret_cast<const float4*>(es)[tid];
@@ -960,30 +749,26 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
         }
         __syncthreads();
         if (tid < cnt4) {
-            const int W = p.rst.W, n = p.rst.n;
+            const int W = p.rst.W, n = p.rst.n, no = RT::GRAY ? 3 : p.n_out;
             const float xa[4] = {xv0.x, xv0.y, xv0.z, xv0.w};
-            float za[4] = {zv0.x, zv0.y, zv0.z, zv0.w};      // RSMS: the history, rewritten by rsm_finish
+            float za[4] = {zv0.x, zv0.y, zv0.z, zv0.w};
             float o[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int lp = (tid * 4 + j) / p.n_out, c = tid * 4 + j - lp * p.n_out, row = lp / W, col = lp - row * W;
-                if constexpr (RSG) {                   // n_out == 3 (final_tail_ok)
+                const float* blk = es + ((row & ~(n - 1)) * W + (col & ~(n - 1))) * no;      // the block's first pixel
+                float m, ac = 1.0f;
+                if constexpr (RT::GRAY) {
                     const GrayCoef k = gry_coef(p.rst.gray, n);
-                    const float* grp = es + ((row & ~(n - 1)) * W + (col & ~(n - 1))) * 3;
-                    const float m = gry_group([&](int bi, int bj, int ch) { return grp[(bi * W + bj) * 3 + ch]; }, n, k);
-                    const float ac = c == 0 ? k.a0 : c == 1 ? k.a1 : k.a2;
-                    o[j] = rsn_finish(xa[j], gry_x0p(x0v[j], __fsub_rn(yv0[j], m), mv0[j], lam, ac), mv0[j], za[j], a1, a2, sg, sgm);
-                    continue;
+                    m = gry_group([&](int bi, int bj, int ch) { return blk[(bi * W + bj) * 3 + ch]; }, n, k);
+                    ac = c == 0 ? k.a0 : c == 1 ? k.a1 : k.a2;
+                } else {
+                    m = rst_block_mean([&](int bi, int bj) { return blk[(bi * W + bj) * p.n_out + c]; }, n);
                 }
-                const float* blk = es + ((row & ~(n - 1)) * W + (col & ~(n - 1))) * p.n_out + c;
-                const float m = rst_block_mean([&](int bi, int bj) { return blk[(bi * W + bj) * p.n_out]; }, n);
-                if constexpr (RSN) o[j] = rsn_finish(xa[j], rsn_x0p(x0v[j], m, yv0[j], mv0[j], lam), mv0[j], za[j], a1, a2, sg, sgm);
-                else if constexpr (RSMS) o[j] = rsm_finish(xa[j], rsm_x0p(x0v[j], m, yv0[j], mv0[j]), za[j], a1, a2, a3);
-                else if constexpr (RSTM) o[j] = rstm_finish(xa[j], x0v[j], m, yv0[j], mv0[j], za[j], a1, a2, sg);
-                else o[j] = rst_finish(xa[j], x0v[j], m, yv0[j], za[j], a1, a2, sg);
+                o[j] = rst_finish<K>(xa[j], rst_x0p<K>(x0v[j], m, yv0[j], mv0[j], lam, ac), mv0[j], za[j], a1, a2, a5, sgm);
             }
             reinterpret_cast<float4*>(p.x)[e4 + tid] = make_float4(o[0], o[1], o[2], o[3]);
-            if constexpr (RSMS) reinterpret_cast<float4*>(p.x0_hist)[e4 + tid] = make_float4(za[0], za[1], za[2], za[3]);
+            if constexpr (RT::HIST) reinterpret_cast<float4*>(p.x0_hist)[e4 + tid] = make_float4(za[0], za[1], za[2], za[3]);
         }
         return;
     }
@@ -1006,8 +791,27 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
     }
 }
 
-static bool restore_block_ok(const RestoreOps& o, bool point_ok = false) {
-    return (o.n == 2 || o.n == 4 || o.n == 8 || (point_ok && o.n == 1)) && o.H > 0 && o.W > 0 && o.H % o.n == 0 && o.W % o.n == 0;
+// What both tails ask of a restore kind's rule beyond x, t and the four common tables, `per` being the elements of one image: null
+// when the rule is sound, else what is wrong with it.  By kind (RestoreTraits): Restore has no n = 1; RestoreMasked needs its mask, the
+// other pointwise kinds need one at n = 1 only (nothing would be constrained), where y is read as float4s.
+static const char* restore_rule_fault(const StepRule& r, long long per) {
+    const RestoreOps& o = r.rst;
+    const bool hist = r.kind == StepKind::RestoreMultistep, gray = r.kind == StepKind::RestoreGray,
+               noisy = gray || r.kind == StepKind::RestoreNoisy, n1 = r.kind != StepKind::Restore;
+    if (!(o.y && (hist ? r.c3 && r.x0_hist : r.sigma != nullptr) && (!noisy || (r.nsy.lam && r.nsy.sgm)) &&
+          (r.kind != StepKind::RestoreMasked || o.mask)))
+        return "null pointer";
+    if (hist && (r.noise || !aligned16(r.x0_hist))) return "no injected noise, an aligned history";
+    if (r.noise) return "no injected noise (Philox only)";
+    if (!((o.n == 2 || o.n == 4 || o.n == 8 || (n1 && o.n == 1)) && o.H > 0 && o.W > 0 && o.H % o.n == 0 && o.W % o.n == 0))
+        return n1 ? "n must be 1, 2, 4 or 8 and divide H and W" : "n must be 2, 4 or 8 and divide H and W";
+    if (o.n == 1 && !o.mask && !gray) return "n = 1 needs a mask (nothing would be constrained)";
+    if (gray && !(o.gray == GRAY_MEAN || o.gray == GRAY_LUMA)) return "weights must be 1 (mean) or 2 (luma)";
+    const long long hw = (long long)o.H * o.W;
+    if (gray && (per != hw * 3 || per > INT_MAX)) return "per must be H * W * 3, below 2^31";
+    if (per % hw || per / hw > INT_MAX || (n1 && per > INT_MAX)) return n1 ? "per must be H * W * channels, below 2^31" : "per must be H * W * channels";
+    if (o.n == 1 && !gray && !aligned16(o.y)) return "alignment";
+    return nullptr;
 }
 
 template <StepKind K>
@@ -1030,9 +834,7 @@ bool final_tail_ok(int HW, int C, int groups, int n_out, int np, StepKind kind, 
     if (kind == StepKind::RestoreGray && n_out != 3) return false;       // the grey operator is over a pixel's three colours
     // the restore tail forms block means from the tile's x0 in LDS: the 128-pixel tile must hold whole rows of n x n blocks
     // (the masked kind the same for n >= 2; its n = 1 is pointwise)
-    const bool blocks = kind == StepKind::Restore ||
-                        ((kind == StepKind::RestoreMasked || kind == StepKind::RestoreMultistep || kind == StepKind::RestoreNoisy ||
-                          kind == StepKind::RestoreGray) && restore_n != 1);
+    const bool blocks = kind == StepKind::Restore || (restore_kind(kind) && restore_n != 1);
     if (blocks && !(restore_w > 0 && restore_n > 0 && 128 % (restore_w * restore_n) == 0)) return false;
     return np > 0 && HW == np * 128 && np * groups <= 1024;
 }
@@ -1051,6 +853,16 @@ int final_tail(const TailIn& in, const StepRule& r, const int64_t* t, const Chai
     p.c_recip = r.c_recip; p.c_recipm1 = r.c_recipm1; p.c1 = r.c1; p.c2 = r.c2; p.sigma = r.sigma;
     p.chain_state = h.chain_state; p.seed = h.seed; p.stream = h.stream_id; p.dec_counter = h.dec_counter;
     p.np = in.np; p.HW = in.HW; p.C = in.C; p.cpg = in.C / in.groups; p.n_out = in.n_out; p.eps = in.eps;
+    if (restore_kind(r.kind)) {      // the operands of every restore kind; the null ones are those its instantiation does not read
+        const char* fault = tables ? restore_rule_fault(r, (long long)in.HW * in.n_out) : "needs x, t and the schedule tables";
+        if (!fault && (long long)r.rst.H * r.rst.W != in.HW) fault = "H * W must be the map's";
+        if (fault) {
+            set_error("bad argument: final_tail: the restore step: %s", fault);
+            return DDK_ERR_ARG;
+        }
+        p.rst = r.rst; p.x0_hist = r.x0_hist; p.c3 = r.c3;
+        if (r.kind == StepKind::RestoreNoisy || r.kind == StepKind::RestoreGray) p.nsy = r.nsy;
+    }
     switch (r.kind) {
         case StepKind::Eps:
             DDK_REQUIRE(r.eps_out && !r.x, "final_tail: the plain forward needs eps_out and takes no x");
@@ -1070,37 +882,14 @@ int final_tail(const TailIn& in, const StepRule& r, const int64_t* t, const Chai
             p.inp = r.inp;
             return launch_tail<StepKind::Inpaint>(p, in.B, st);
         case StepKind::Restore:
-            DDK_REQUIRE(tables && r.sigma && !r.noise && r.rst.y && restore_block_ok(r.rst) && (long long)r.rst.H * r.rst.W == in.HW,
-                        "final_tail: the restore step needs x, t, the tables, y, n in {2,4,8} dividing H and W, H*W of the map and no injected noise");
-            p.rst = r.rst;
             return launch_tail<StepKind::Restore>(p, in.B, st);
         case StepKind::RestoreMasked:
-            DDK_REQUIRE(tables && r.sigma && !r.noise && r.rst.y && r.rst.mask && restore_block_ok(r.rst, true) &&
-                            (long long)r.rst.H * r.rst.W == in.HW && (r.rst.n != 1 || aligned16(r.rst.y)),
-                        "final_tail: the masked restore step needs x, t, the tables, y (aligned at n = 1), the mask, n in {1,2,4,8} dividing H and W, "
-                        "H*W of the map and no injected noise");
-            p.rst = r.rst;
             return launch_tail<StepKind::RestoreMasked>(p, in.B, st);
         case StepKind::RestoreMultistep:
-            DDK_REQUIRE(tables && r.c3 && r.x0_hist && aligned16(r.x0_hist) && !r.noise && r.rst.y && (r.rst.mask || r.rst.n != 1) &&
-                            restore_block_ok(r.rst, true) && (long long)r.rst.H * r.rst.W == in.HW && (r.rst.n != 1 || aligned16(r.rst.y)),
-                        "final_tail: the restore multistep step needs x, t, the tables with c3, an aligned history, y (aligned at n = 1), a mask at "
-                        "n = 1, n in {1,2,4,8} dividing H and W, H*W of the map and no injected noise");
-            p.rst = r.rst; p.x0_hist = r.x0_hist; p.c3 = r.c3;
             return launch_tail<StepKind::RestoreMultistep>(p, in.B, st);
         case StepKind::RestoreNoisy:
-            DDK_REQUIRE(tables && r.sigma && r.nsy.lam && r.nsy.sgm && !r.noise && r.rst.y && (r.rst.mask || r.rst.n != 1) && restore_block_ok(r.rst, true) &&
-                            (long long)r.rst.H * r.rst.W == in.HW && (r.rst.n != 1 || aligned16(r.rst.y)),
-                        "final_tail: the noisy restore step needs x, t, the tables with lam and sgm, y (aligned at n = 1), a mask at n = 1, "
-                        "n in {1,2,4,8} dividing H and W, H*W of the map and no injected noise");
-            p.rst = r.rst; p.nsy = r.nsy;
             return launch_tail<StepKind::RestoreNoisy>(p, in.B, st);
         case StepKind::RestoreGray:
-            DDK_REQUIRE(tables && r.sigma && r.nsy.lam && r.nsy.sgm && !r.noise && r.rst.y && restore_block_ok(r.rst, true) &&
-                            (long long)r.rst.H * r.rst.W == in.HW && (r.rst.gray == GRAY_MEAN || r.rst.gray == GRAY_LUMA),
-                        "final_tail: the grey restore step needs x, t, the tables with lam and sgm, y, n in {1,2,4,8} dividing H and W, H*W of the "
-                        "map, weights 1 or 2 and no injected noise");
-            p.rst = r.rst; p.nsy = r.nsy;
             return launch_tail<StepKind::RestoreGray>(p, in.B, st);
         case StepKind::Vlb: {
             DDK_REQUIRE(r.vlb && tables && !r.eps_out && h.chain_state, "final_tail: the VLB epilogue needs the sweep's step, x, t, the tables and the chain state");
@@ -1298,6 +1087,28 @@ int vlb_sweep_finalize(const float* partials, int nslot, float* vlb_t, float* l_
     return check_launch("vlb_sweep_finalize_kernel");
 }
 
+// the unfused restore step's one kernel: blocks (GRAY: groups) of n x n elements per thread, or float4s where n = 1 is pointwise
+template <StepKind K>
+static int launch_restore(const StepRule& r, const float* eps_hat, const int64_t* t, int B, long long per, const ChainHooks& h, hipStream_t st) {
+    const long long hw = (long long)r.rst.H * r.rst.W, nn = r.rst.n * r.rst.n;
+    if constexpr (K == StepKind::RestoreGray) {
+        hipLaunchKernelGGL(p_update_restore_gray_kernel, dim3(grid1d(B * hw / nn)), dim3(256), 0, st, r, eps_hat, t, B, h.seed, h.stream_id,
+                           h.chain_state, h.dec_counter);
+        return check_launch("p_update_restore_gray_kernel");
+    } else {
+        const int n_out = (int)(per / hw);
+        if constexpr (RestoreTraits<K>::POINT)
+            if (r.rst.n == 1) {
+                hipLaunchKernelGGL(p_update_restore_point_kernel<K>, dim3(grid1d(B * per / 4)), dim3(256), 0, st, r, eps_hat, t, per / 4,
+                                   B * per / 4, n_out, h.seed, h.stream_id, h.chain_state, h.dec_counter);
+                return check_launch("p_update_restore_point_kernel");
+            }
+        hipLaunchKernelGGL(p_update_restore_kernel<K>, dim3(grid1d(B * per / nn)), dim3(256), 0, st, r, eps_hat, t, B, n_out, h.seed,
+                           h.stream_id, h.chain_state, h.dec_counter);
+        return check_launch("p_update_restore_kernel");
+    }
+}
+
 int p_update(const StepRule& r, const float* eps_hat, const int64_t* t, int B, long long per, const ChainHooks& h, hipStream_t st,
              const char* who) {
     auto bad = [who](const char* what) {
@@ -1307,6 +1118,8 @@ int p_update(const StepRule& r, const float* eps_hat, const int64_t* t, int B, l
     if (!(r.x && eps_hat && t && r.c_recip && r.c_recipm1 && r.c1 && r.c2)) return bad("null pointer");
     if (!(B > 0 && per > 0 && per % 4 == 0)) return bad("per-sample element count must be a multiple of 4");
     if (!(aligned16(r.x) && aligned16(eps_hat) && aligned16(r.noise) && r.noise_step_stride % 4 == 0)) return bad("alignment");
+    if (restore_kind(r.kind))
+        if (const char* fault = restore_rule_fault(r, per)) return bad(fault);
     const long long total4 = B * per / 4;
     const dim3 grid(grid1d(total4));
     switch (r.kind) {
@@ -1325,80 +1138,16 @@ int p_update(const StepRule& r, const float* eps_hat, const int64_t* t, int B, l
             if (!(h.chain_state || h.stream_id < INPAINT_Z3_BIT)) return bad("stream_id must be < 2^29 (bits 29, 30 key the extra draws)");
             hipLaunchKernelGGL(p_update_kernel<StepKind::Inpaint>, grid, dim3(256), 0, st, r, eps_hat, t, per / 4, total4, h.seed, h.stream_id, h.chain_state, h.dec_counter);
             break;
-        case StepKind::Restore: {  // blocks, not float4s: a kernel of its own
-            if (!(r.sigma && r.rst.y)) return bad("null pointer");
-            if (r.noise) return bad("no injected noise (Philox only)");
-            if (!restore_block_ok(r.rst)) return bad("n must be 2, 4 or 8 and divide H and W");
-            const long long hw = (long long)r.rst.H * r.rst.W;
-            if (per % hw || per / hw > INT_MAX) return bad("per must be H * W * channels");
-            const int n_out = (int)(per / hw);
-            hipLaunchKernelGGL(p_update_restore_kernel<false>, dim3(grid1d(B * per / (r.rst.n * r.rst.n))), dim3(256), 0, st, r, eps_hat, t, B,
-                               n_out, h.seed, h.stream_id, h.chain_state, h.dec_counter);
-            return check_launch("p_update_restore_kernel");
-        }
-        case StepKind::RestoreMasked: {  // n >= 2: Restore's kernel with the mask test; n = 1: pointwise float4s
-            if (!(r.sigma && r.rst.y && r.rst.mask)) return bad("null pointer");
-            if (r.noise) return bad("no injected noise (Philox only)");
-            if (!restore_block_ok(r.rst, true)) return bad("n must be 1, 2, 4 or 8 and divide H and W");
-            const long long hw = (long long)r.rst.H * r.rst.W;
-            if (per % hw || per / hw > INT_MAX || per > INT_MAX) return bad("per must be H * W * channels, below 2^31");
-            const int n_out = (int)(per / hw);
-            if (r.rst.n == 1) {
-                if (!aligned16(r.rst.y)) return bad("alignment");
-                hipLaunchKernelGGL(p_update_restore_point_kernel, grid, dim3(256), 0, st, r, eps_hat, t, per / 4, total4, n_out, h.seed, h.stream_id,
-                                   h.chain_state, h.dec_counter);
-                return check_launch("p_update_restore_point_kernel");
-            }
-            hipLaunchKernelGGL(p_update_restore_kernel<true>, dim3(grid1d(B * per / (r.rst.n * r.rst.n))), dim3(256), 0, st, r, eps_hat, t, B,
-                               n_out, h.seed, h.stream_id, h.chain_state, h.dec_counter);
-            return check_launch("p_update_restore_kernel");
-        }
-        case StepKind::RestoreMultistep: {  // RestoreMasked's two kernels with the history; the mask is optional at n >= 2
-            if (!(r.c3 && r.x0_hist && r.rst.y)) return bad("null pointer");
-            if (r.noise || !aligned16(r.x0_hist)) return bad("no injected noise, an aligned history");
-            if (!restore_block_ok(r.rst, true)) return bad("n must be 1, 2, 4 or 8 and divide H and W");
-            if (r.rst.n == 1 && !r.rst.mask) return bad("n = 1 needs a mask (nothing would be constrained)");
-            const long long hw = (long long)r.rst.H * r.rst.W;
-            if (per % hw || per / hw > INT_MAX || per > INT_MAX) return bad("per must be H * W * channels, below 2^31");
-            const int n_out = (int)(per / hw);
-            if (r.rst.n == 1) {
-                if (!aligned16(r.rst.y)) return bad("alignment");
-                hipLaunchKernelGGL(p_update_restore_ms_point_kernel, grid, dim3(256), 0, st, r, eps_hat, t, per / 4, total4, n_out, h.dec_counter);
-                return check_launch("p_update_restore_ms_point_kernel");
-            }
-            hipLaunchKernelGGL(p_update_restore_ms_kernel, dim3(grid1d(B * per / (r.rst.n * r.rst.n))), dim3(256), 0, st, r, eps_hat, t, B, n_out,
-                               h.dec_counter);
-            return check_launch("p_update_restore_ms_kernel");
-        }
-        case StepKind::RestoreNoisy: {  // RestoreMasked's two kernels with lam and sgm; the mask is optional at n >= 2
-            if (!(r.sigma && r.nsy.lam && r.nsy.sgm && r.rst.y)) return bad("null pointer");
-            if (r.noise) return bad("no injected noise (Philox only)");
-            if (!restore_block_ok(r.rst, true)) return bad("n must be 1, 2, 4 or 8 and divide H and W");
-            if (r.rst.n == 1 && !r.rst.mask) return bad("n = 1 needs a mask (nothing would be constrained)");
-            const long long hw = (long long)r.rst.H * r.rst.W;
-            if (per % hw || per / hw > INT_MAX || per > INT_MAX) return bad("per must be H * W * channels, below 2^31");
-            const int n_out = (int)(per / hw);
-            if (r.rst.n == 1) {
-                if (!aligned16(r.rst.y)) return bad("alignment");
-                hipLaunchKernelGGL(p_update_restore_noisy_point_kernel, grid, dim3(256), 0, st, r, eps_hat, t, per / 4, total4, n_out, h.seed,
-                                   h.stream_id, h.chain_state, h.dec_counter);
-                return check_launch("p_update_restore_noisy_point_kernel");
-            }
-            hipLaunchKernelGGL(p_update_restore_noisy_kernel, dim3(grid1d(B * per / (r.rst.n * r.rst.n))), dim3(256), 0, st, r, eps_hat, t, B,
-                               n_out, h.seed, h.stream_id, h.chain_state, h.dec_counter);
-            return check_launch("p_update_restore_noisy_kernel");
-        }
-        case StepKind::RestoreGray: {  // groups of n n 3 elements: a kernel of its own at every n; the mask is optional
-            if (!(r.sigma && r.nsy.lam && r.nsy.sgm && r.rst.y)) return bad("null pointer");
-            if (r.noise) return bad("no injected noise (Philox only)");
-            if (!restore_block_ok(r.rst, true)) return bad("n must be 1, 2, 4 or 8 and divide H and W");
-            if (!(r.rst.gray == GRAY_MEAN || r.rst.gray == GRAY_LUMA)) return bad("weights must be 1 (mean) or 2 (luma)");
-            const long long hw = (long long)r.rst.H * r.rst.W;
-            if (per != hw * 3 || per > INT_MAX) return bad("per must be H * W * 3, below 2^31");
-            hipLaunchKernelGGL(p_update_restore_gray_kernel, dim3(grid1d(B * hw / (r.rst.n * r.rst.n))), dim3(256), 0, st, r, eps_hat, t, B,
-                               h.seed, h.stream_id, h.chain_state, h.dec_counter);
-            return check_launch("p_update_restore_gray_kernel");
-        }
+        case StepKind::Restore:
+            return launch_restore<StepKind::Restore>(r, eps_hat, t, B, per, h, st);
+        case StepKind::RestoreMasked:
+            return launch_restore<StepKind::RestoreMasked>(r, eps_hat, t, B, per, h, st);
+        case StepKind::RestoreMultistep:
+            return launch_restore<StepKind::RestoreMultistep>(r, eps_hat, t, B, per, h, st);
+        case StepKind::RestoreNoisy:
+            return launch_restore<StepKind::RestoreNoisy>(r, eps_hat, t, B, per, h, st);
+        case StepKind::RestoreGray:
+            return launch_restore<StepKind::RestoreGray>(r, eps_hat, t, B, per, h, st);
         case StepKind::Vlb:       // no update: the sweep's reduction of the step's terms, a kernel of its own
             if (!r.vlb) return bad("null pointer");
             return vlb_sweep_terms(*r.vlb, t, eps_hat, B, per, h.chain_state, st, h.dec_counter);
@@ -1478,49 +1227,58 @@ int ddk_p_sample_update_inpaint(float* x, const float* eps_hat, const float* kno
     return p_update(r, eps_hat, t, B, per, ChainHooks{nullptr, nullptr, seed, stream_id}, as_stream(s), "p_sample_update_inpaint");
 }
 
+}  // extern "C"
+
+// What the restore ops share: the shape check in the entry's name, the rule of its kind and p_update.  c5: sigma, or the solver's c3.
+static int restore_op(const char* who, StepKind kind, float* x, const float* eps_hat, float* x0_hist, const RestoreOps& rst, const int64_t* t,
+                      const float* c_recip, const float* c_recipm1, const float* c1, const float* c2, const float* c5, const float* lam,
+                      const float* sgm, int B, int channels, uint64_t seed, uint32_t stream_id, ddk_stream_t s) {
+    if (!(B > 0 && rst.H > 0 && rst.W > 0 && channels > 0)) {
+        set_error("bad argument: %s: B / H / W / channels must be positive", who);
+        return DDK_ERR_ARG;
+    }
+    if (!(rst.mask || rst.n != 1 || kind == StepKind::Restore || kind == StepKind::RestoreGray)) {      // Restore: p_update rejects n = 1
+        set_error("bad argument: %s: n = 1 needs a mask (nothing would be constrained)", who);
+        return DDK_ERR_ARG;
+    }
+    const bool hist = kind == StepKind::RestoreMultistep;
+    StepRule r{kind, nullptr, x, nullptr, 0, 0, c_recip, c_recipm1, c1, c2, hist ? nullptr : c5, x0_hist, hist ? c5 : nullptr};
+    r.rst = rst;
+    if (lam || sgm) r.nsy = NoisyTables{lam, sgm};
+    return p_update(r, eps_hat, t, B, (long long)rst.H * rst.W * channels, hist ? ChainHooks{} : ChainHooks{nullptr, nullptr, seed, stream_id},
+                    as_stream(s), who);
+}
+
+extern "C" {
+
 int ddk_p_sample_update_restore(float* x, const float* eps_hat, const float* y, int n, const int64_t* t, const float* c_recip,
                                 const float* c_recipm1, const float* c1, const float* c2, const float* sigma, int B, int H, int W,
                                 int channels, uint64_t seed, uint32_t stream_id, ddk_stream_t s) {
-    DDK_REQUIRE(B > 0 && H > 0 && W > 0 && channels > 0, "p_sample_update_restore: B / H / W / channels must be positive");
-    StepRule r{StepKind::Restore, nullptr, x, nullptr, 0, 0, c_recip, c_recipm1, c1, c2, sigma};
-    r.rst = RestoreOps{y, n, H, W, 0, nullptr};
-    return p_update(r, eps_hat, t, B, (long long)H * W * channels, ChainHooks{nullptr, nullptr, seed, stream_id}, as_stream(s),
-                    "p_sample_update_restore");
+    return restore_op("p_sample_update_restore", StepKind::Restore, x, eps_hat, nullptr, RestoreOps{y, n, H, W, 0, nullptr}, t, c_recip,
+                      c_recipm1, c1, c2, sigma, nullptr, nullptr, B, channels, seed, stream_id, s);
 }
 
 int ddk_p_sample_update_restore_masked(float* x, const float* eps_hat, const float* y, const float* mask, int n, const int64_t* t,
                                        const float* c_recip, const float* c_recipm1, const float* c1, const float* c2, const float* sigma,
                                        int B, int H, int W, int channels, uint64_t seed, uint32_t stream_id, ddk_stream_t s) {
-    DDK_REQUIRE(B > 0 && H > 0 && W > 0 && channels > 0, "p_sample_update_restore_masked: B / H / W / channels must be positive");
-    DDK_REQUIRE(mask || n != 1, "p_sample_update_restore_masked: n = 1 needs a mask (nothing would be constrained)");
-    // no mask: every block is measured, which is the Restore kind, its kernel and its bits
-    StepRule r{mask ? StepKind::RestoreMasked : StepKind::Restore, nullptr, x, nullptr, 0, 0, c_recip, c_recipm1, c1, c2, sigma};
-    r.rst = RestoreOps{y, n, H, W, 0, mask};
-    return p_update(r, eps_hat, t, B, (long long)H * W * channels, ChainHooks{nullptr, nullptr, seed, stream_id}, as_stream(s),
-                    "p_sample_update_restore_masked");
+    // no mask (n >= 2): every block is measured, which is the Restore kind, its kernel and its bits
+    return restore_op("p_sample_update_restore_masked", mask || n == 1 ? StepKind::RestoreMasked : StepKind::Restore, x, eps_hat, nullptr,
+                      RestoreOps{y, n, H, W, 0, mask}, t, c_recip, c_recipm1, c1, c2, sigma, nullptr, nullptr, B, channels, seed, stream_id, s);
 }
 
 int ddk_p_sample_update_restore_multistep(float* x, const float* eps_hat, float* x0_hist, const float* y, const float* mask, int n,
                                           const int64_t* t, const float* c_recip, const float* c_recipm1, const float* c1, const float* c2,
                                           const float* c3, int B, int H, int W, int channels, ddk_stream_t s) {
-    DDK_REQUIRE(B > 0 && H > 0 && W > 0 && channels > 0, "p_sample_update_restore_multistep: B / H / W / channels must be positive");
-    DDK_REQUIRE(mask || n != 1, "p_sample_update_restore_multistep: n = 1 needs a mask (nothing would be constrained)");
-    StepRule r{StepKind::RestoreMultistep, nullptr, x, nullptr, 0, 0, c_recip, c_recipm1, c1, c2, nullptr, x0_hist, c3};
-    r.rst = RestoreOps{y, n, H, W, 0, mask};
-    return p_update(r, eps_hat, t, B, (long long)H * W * channels, ChainHooks{}, as_stream(s), "p_sample_update_restore_multistep");
+    return restore_op("p_sample_update_restore_multistep", StepKind::RestoreMultistep, x, eps_hat, x0_hist, RestoreOps{y, n, H, W, 0, mask}, t,
+                      c_recip, c_recipm1, c1, c2, c3, nullptr, nullptr, B, channels, 0, 0, s);
 }
 
 int ddk_p_sample_update_restore_noisy(float* x, const float* eps_hat, const float* y, const float* mask, int n, const int64_t* t,
                                       const float* c_recip, const float* c_recipm1, const float* c1, const float* c2, const float* sigma,
                                       const float* lam, const float* sgm, int B, int H, int W, int channels, uint64_t seed, uint32_t stream_id,
                                       ddk_stream_t s) {
-    DDK_REQUIRE(B > 0 && H > 0 && W > 0 && channels > 0, "p_sample_update_restore_noisy: B / H / W / channels must be positive");
-    DDK_REQUIRE(mask || n != 1, "p_sample_update_restore_noisy: n = 1 needs a mask (nothing would be constrained)");
-    StepRule r{StepKind::RestoreNoisy, nullptr, x, nullptr, 0, 0, c_recip, c_recipm1, c1, c2, sigma};
-    r.rst = RestoreOps{y, n, H, W, 0, mask};
-    r.nsy = NoisyTables{lam, sgm};
-    return p_update(r, eps_hat, t, B, (long long)H * W * channels, ChainHooks{nullptr, nullptr, seed, stream_id}, as_stream(s),
-                    "p_sample_update_restore_noisy");
+    return restore_op("p_sample_update_restore_noisy", StepKind::RestoreNoisy, x, eps_hat, nullptr, RestoreOps{y, n, H, W, 0, mask}, t, c_recip,
+                      c_recipm1, c1, c2, sigma, lam, sgm, B, channels, seed, stream_id, s);
 }
 
 int ddk_p_sample_update_restore_gray(float* x, const float* eps_hat, const float* y, const float* mask, int n, int weights, const int64_t* t,
@@ -1530,11 +1288,8 @@ int ddk_p_sample_update_restore_gray(float* x, const float* eps_hat, const float
     DDK_REQUIRE(B > 0 && H > 0 && W > 0, "p_sample_update_restore_gray: B / H / W must be positive");
     DDK_REQUIRE(channels == 3, "p_sample_update_restore_gray: the grey operator needs a 3-channel map");
     DDK_REQUIRE(weights == GRAY_MEAN || weights == GRAY_LUMA, "p_sample_update_restore_gray: weights must be 1 (mean) or 2 (luma)");
-    StepRule r{StepKind::RestoreGray, nullptr, x, nullptr, 0, 0, c_recip, c_recipm1, c1, c2, sigma};
-    r.rst = RestoreOps{y, n, H, W, weights, mask};
-    r.nsy = NoisyTables{lam, sgm};
-    return p_update(r, eps_hat, t, B, (long long)H * W * 3, ChainHooks{nullptr, nullptr, seed, stream_id}, as_stream(s),
-                    "p_sample_update_restore_gray");
+    return restore_op("p_sample_update_restore_gray", StepKind::RestoreGray, x, eps_hat, nullptr, RestoreOps{y, n, H, W, weights, mask}, t,
+                      c_recip, c_recipm1, c1, c2, sigma, lam, sgm, B, 3, seed, stream_id, s);
 }
 
 int ddk_final_tail(const float* raw, const float* partials, int tiles_per_image, const float* gamma, const float* beta, float eps,

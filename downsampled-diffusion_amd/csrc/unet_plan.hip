@@ -1147,10 +1147,6 @@ struct StepArgs {
 // tiles of the final tail when the end of the forward runs as ONE launch (final_tail_kernel), else 0.  cin = the final conv's
 // input channels (dimp[1]).  The Vlb, Multistep, Inpaint, Restore, RestoreMasked, RestoreMultistep, RestoreNoisy and RestoreGray kinds take
 // a subset of the shapes (final_tail_ok; the last five's depends on its block, restore_n).
-static bool restore_kind(StepKind k) {       // the kinds whose step carries a DDNM constraint (RestoreOps)
-    return k == StepKind::Restore || k == StepKind::RestoreMasked || k == StepKind::RestoreMultistep || k == StepKind::RestoreNoisy ||
-           k == StepKind::RestoreGray;
-}
 static int fused_tail_parts(const ddk_unet& u, int B, int H, int W, int cin, StepKind kind, int restore_n = 0) {
     const int chan = u.generic ? pad32(u.cfg.chan) : u.cfg.chan, n_out = u.cfg.in_ch;
     const int npf = u.final_conv.has_wu ? conv_wino_stats_parts(B, H, W, cin, chan, GROUPS) : 0;
@@ -1745,22 +1741,27 @@ static int check_timestep_map(const int64_t* map, int t_start, const char* who) 
 
 namespace ddk {
 // floats a chain keeps behind the sampler layout, by its rule: the multistep history [B][H][W][in_ch]; the inpainting op's known
-// latent and mask; the restore step's low-resolution image (room for n = 2, a quarter of the latent: every n fits).  The size
-// queries and sampler_chain's carve-up both come from here.  The masked restore step (restore_n = its block, 1 included): y of
-// that block, [B][H/n][W/n][in_ch], and the mask [B][H/n][W/n] behind it, and never less than the Restore kind's, whose chain a
-// call without a mask is (n = 1: a whole latent plus B H W; n = 2: a quarter of each; n = 4, 8: the Restore kind's quarter latent).
+// latent and mask; a restore kind's measurement.  The size queries and sampler_chain's carve-up both come from here.
+// The restore kinds (restore_n = the block, 1 included): (RestoreMultistep: the history, then) y of that block, [B][H/n][W/n][in_ch]
+// (the grey y is a third of that place), and behind it the mask [B][H/n][W/n], reserved with or without one.  Restore itself keeps
+// room for n = 2 without a mask, a quarter of the latent, whatever its n; RestoreMasked, RestoreNoisy and RestoreGray never keep less
+// than that at n >= 2, since a masked call without a mask is the Restore kind's chain.
+struct RestoreStage {
+    size_t hist, y, mask;         // the floats of each part, 4-float aligned; y starts at hist, the mask at hist + y
+};
+static RestoreStage restore_stage(size_t n, int B, int H, int W, StepKind kind, int restore_n) {
+    const size_t nn = (size_t)restore_n * restore_n;
+    return {kind == StepKind::RestoreMultistep ? al4(n) : 0, al4(n / nn), al4((size_t)B * H * W / nn)};
+}
 static size_t chain_extra_floats(const ddk_unet& u, int B, int H, int W, StepKind kind, int restore_n = 0) {
     const size_t n = al4((size_t)B * H * W * u.cfg.in_ch);
-    // the noisy and the grey kind keep RestoreMasked's layout and size (the grey y is a third of the place it is given)
-    if (kind == StepKind::RestoreMasked || kind == StepKind::RestoreNoisy || kind == StepKind::RestoreGray) {
-        const size_t nn = (size_t)restore_n * restore_n, m = al4(n / nn) + al4((size_t)B * H * W / nn);
-        return restore_n > 1 && m < al4(n / 4) ? al4(n / 4) : m;
+    if (kind == StepKind::Restore) return al4(n / 4);
+    if (restore_kind(kind)) {
+        const RestoreStage g = restore_stage(n, B, H, W, kind, restore_n);
+        const size_t m = g.hist + g.y + g.mask;
+        return kind != StepKind::RestoreMultistep && restore_n > 1 && m < al4(n / 4) ? al4(n / 4) : m;
     }
-    if (kind == StepKind::RestoreMultistep) {   // the history, then y and room for the mask (reserved with or without one)
-        const size_t nn = (size_t)restore_n * restore_n;
-        return n + al4(n / nn) + al4((size_t)B * H * W / nn);
-    }
-    return kind == StepKind::Multistep ? n : kind == StepKind::Inpaint ? 2 * n : kind == StepKind::Restore ? al4(n / 4) : 0;
+    return kind == StepKind::Multistep ? n : kind == StepKind::Inpaint ? 2 * n : 0;
 }
 static size_t sampler_bytes(const ddk_unet* u, int B, int H, int W, int t_start, StepKind kind, int restore_n = 0) {
     if (check_shape(u, B, H, W) != DDK_OK || t_start < 0) return 0;
@@ -1773,11 +1774,8 @@ static size_t sampler_bytes(const ddk_unet* u, int B, int H, int W, int t_start,
 // and outside any captured step, so no chain sees another's and the cached graph points only into the workspace:
 //   Multistep: the history, zeroed by every call (c3[t_start] == 0 makes the first step first order whatever it would hold)
 //   Inpaint:   known and mask, copied in before the first op
-//   Restore:   y, copied in before the first step
-//   RestoreMasked: y and, behind it, the mask, copied in before the first step
-//   RestoreMultistep: the history, zeroed by every call as Multistep's, then y and (when given) the mask, copied in as RestoreMasked's
-//   RestoreNoisy: y and (when given) the mask, where RestoreMasked keeps them
-//   RestoreGray: the one-channel y at the head of RestoreMasked's y, and (when given) the mask where RestoreMasked keeps it
+//   the restore kinds: (RestoreMultistep: the history, zeroed by every call as Multistep's, then) y and, when given, the mask,
+//              copied in before the first step (restore_stage's layout)
 // The graph key: the kind, every table the step reads and the restore block; the staged operands live in the workspace, which is
 // in the key.
 static int sampler_chain(const ddk_sampler_args* a, const char* who, const int64_t* map, StepRule rule, ddk_stream_t s) {
@@ -1797,47 +1795,22 @@ static int sampler_chain(const ddk_sampler_args* a, const char* who, const int64
         DDK_HIP(hipMemcpyAsync(extra + al4(n), rule.inp.mask, n * sizeof(float), hipMemcpyDeviceToDevice, c.st));
         rule.inp.known = extra;
         rule.inp.mask = extra + al4(n);
-    } else if (rule.kind == StepKind::Restore) {
+    } else if (restore_kind(rule.kind)) {
+        const RestoreStage g = restore_stage(n, B, H, W, rule.kind, rule.rst.n);
+        const size_t nn = (size_t)rule.rst.n * rule.rst.n, nm = (size_t)B * H * W / nn;      // one float per block: the mask, and the grey y
         rule.rst.H = H; rule.rst.W = W;
-        DDK_HIP(hipMemcpyAsync(extra, rule.rst.y, n / ((size_t)rule.rst.n * rule.rst.n) * sizeof(float), hipMemcpyDeviceToDevice, c.st));
-        rule.rst.y = extra;
-    } else if (rule.kind == StepKind::RestoreMasked) {
-        const size_t nn = (size_t)rule.rst.n * rule.rst.n, ny = n / nn, nm = (size_t)B * H * W / nn;
-        rule.rst.H = H; rule.rst.W = W;
-        DDK_HIP(hipMemcpyAsync(extra, rule.rst.y, ny * sizeof(float), hipMemcpyDeviceToDevice, c.st));
-        DDK_HIP(hipMemcpyAsync(extra + al4(ny), rule.rst.mask, nm * sizeof(float), hipMemcpyDeviceToDevice, c.st));
-        rule.rst.y = extra;
-        rule.rst.mask = extra + al4(ny);
-    } else if (rule.kind == StepKind::RestoreNoisy) {
-        const size_t nn = (size_t)rule.rst.n * rule.rst.n, ny = n / nn, nm = (size_t)B * H * W / nn;
-        rule.rst.H = H; rule.rst.W = W;
-        DDK_HIP(hipMemcpyAsync(extra, rule.rst.y, ny * sizeof(float), hipMemcpyDeviceToDevice, c.st));
-        if (rule.rst.mask) {
-            DDK_HIP(hipMemcpyAsync(extra + al4(ny), rule.rst.mask, nm * sizeof(float), hipMemcpyDeviceToDevice, c.st));
-            rule.rst.mask = extra + al4(ny);
+        if (g.hist) {
+            DDK_HIP(hipMemsetAsync(extra, 0, n * sizeof(float), c.st));
+            rule.x0_hist = extra;
         }
-        rule.rst.y = extra;
-    } else if (rule.kind == StepKind::RestoreGray) {
-        const size_t nn = (size_t)rule.rst.n * rule.rst.n, nm = (size_t)B * H * W / nn;      // y and the mask: one float per block
-        rule.rst.H = H; rule.rst.W = W;
-        DDK_HIP(hipMemcpyAsync(extra, rule.rst.y, nm * sizeof(float), hipMemcpyDeviceToDevice, c.st));
-        if (rule.rst.mask) {
-            DDK_HIP(hipMemcpyAsync(extra + al4(n / nn), rule.rst.mask, nm * sizeof(float), hipMemcpyDeviceToDevice, c.st));
-            rule.rst.mask = extra + al4(n / nn);
-        }
-        rule.rst.y = extra;
-    } else if (rule.kind == StepKind::RestoreMultistep) {
-        const size_t nn = (size_t)rule.rst.n * rule.rst.n, ny = n / nn, nm = (size_t)B * H * W / nn;
-        float* ystage = extra + al4(n);
-        rule.rst.H = H; rule.rst.W = W;
-        DDK_HIP(hipMemsetAsync(extra, 0, n * sizeof(float), c.st));
-        DDK_HIP(hipMemcpyAsync(ystage, rule.rst.y, ny * sizeof(float), hipMemcpyDeviceToDevice, c.st));
-        if (rule.rst.mask) {
-            DDK_HIP(hipMemcpyAsync(ystage + al4(ny), rule.rst.mask, nm * sizeof(float), hipMemcpyDeviceToDevice, c.st));
-            rule.rst.mask = ystage + al4(ny);
-        }
-        rule.x0_hist = extra;
+        float* ystage = extra + g.hist;
+        DDK_HIP(hipMemcpyAsync(ystage, rule.rst.y, (rule.kind == StepKind::RestoreGray ? nm : n / nn) * sizeof(float),
+                               hipMemcpyDeviceToDevice, c.st));
         rule.rst.y = ystage;
+        if (rule.rst.mask) {
+            DDK_HIP(hipMemcpyAsync(ystage + g.y, rule.rst.mask, nm * sizeof(float), hipMemcpyDeviceToDevice, c.st));
+            rule.rst.mask = ystage + g.y;
+        }
     }
     const StepArgs step{c.state, c.ws + c.sl.off_eps, c.per, rule};
 
@@ -1929,160 +1902,120 @@ extern "C" int ddk_sampler_run_inpaint(const ddk_sampler_args* a, const ddk_inpa
     return sampler_chain(a, "sampler_inpaint", ip->timestep_map, rule, s);
 }
 
-// ------------------------------------------------------------------------------------------------ super-resolution sampler
-// DDNM for n x n average pooling: the spaced sampler's chain and tables, every step ending in
-// StepKind::Restore.  A kind of its own and n in the graph key: an ancestral chain on the same buffers never replays this graph,
-// nor this one an ancestral graph, nor a chain with another block.
+// ------------------------------------------------------------------------------------------------ restoration samplers
+// DDNM (DESIGN.md sections 3.6, 3.8 - 3.11): the spaced sampler's chain and tables, every step ending in one of the restore kinds.  A
+// kind of its own, n, whether a mask was given and the grey weights in the graph key: no chain replays another's graph.
+namespace ddk {
+static bool restore_n_ok(int n, bool n1) { return n == 2 || n == 4 || n == 8 || (n1 && n == 1); }
+
+static size_t restore_bytes(const ddk_unet* u, int B, int H, int W, int t_start, StepKind kind, int n) {
+    return restore_n_ok(n, true) ? sampler_bytes(u, B, H, W, t_start, kind, n) : 0;
+}
+
+static int restore_tail_parts(const ddk_unet* u, int B, int H, int W, StepKind kind, int n) {
+    if (check_shape(u, B, H, W) != DDK_OK || !restore_n_ok(n, true)) return -1;
+    return fused_tail_parts(*u, B, H, W, u->dimp[1], kind, n);
+}
+
+// What the restore entries share: the checks, the rule and the chain.  The kind says which tables the step reads (sigma, or
+// RestoreMultistep's c3; RestoreNoisy's and RestoreGray's lam and sgm); n1: whether the entry takes n = 1, which every kind but the grey
+// one constrains through a mask only.
+static int restore_chain(const ddk_sampler_args* a, const char* who, const int64_t* map, StepKind kind, bool n1, bool masked_ws, const float* c3,
+                         NoisyTables nsy, const float* y, const float* mask, int n, int weights, ddk_stream_t s) {
+    auto bad = [who](const char* what) {
+        set_error("bad argument: %s: %s", who, what);
+        return DDK_ERR_ARG;
+    };
+    const bool hist = kind == StepKind::RestoreMultistep, gray = kind == StepKind::RestoreGray, noisy = gray || kind == StepKind::RestoreNoisy;
+    if (!(a && a->unet && a->packed && a->x && a->workspace && y)) return bad("null pointer");
+    if (!(a->c_recip && a->c_recipm1 && a->c1 && a->c2 && (hist ? c3 : a->sigma) && (!noisy || (nsy.lam && nsy.sgm)))) return bad("null schedule table");
+    if (a->noise) return bad(hist ? "the solver is deterministic, noise must be NULL" : "injected noise is not supported, noise must be NULL (Philox only)");
+    if (gray && a->unet->cfg.in_ch != 3) return bad("the grey operator needs a 3-channel model");
+    if (gray && !(weights == GRAY_MEAN || weights == GRAY_LUMA)) return bad("weights must be 1 (mean) or 2 (luma)");
+    if (!(a->t_start >= a->t_end && a->t_end >= 0)) return bad("need t_start >= t_end >= 0");
+    if (!(restore_n_ok(n, n1) && a->H > 0 && a->W > 0 && a->H % n == 0 && a->W % n == 0))
+        return bad(n1 ? "n must be 1, 2, 4 or 8 and divide H and W" : "n must be 2, 4 or 8 and divide H and W");
+    if (!(mask || n != 1 || gray)) return bad("n = 1 needs a mask (nothing would be constrained)");
+    DDK_TRY(check_timestep_map(map, a->t_start, who));
+    // masked_ws: the entry holds the workspace to the masked query's size with or without a mask (never less than the Restore kind's)
+    if (masked_ws && a->workspace_bytes < sampler_bytes(a->unet, a->B, a->H, a->W, a->t_start, StepKind::RestoreMasked, n)) {
+        set_error("%s: workspace too small (ddk_%s_workspace_bytes)", who, who);
+        return DDK_ERR_WORKSPACE;
+    }
+    StepRule rule{};
+    rule.kind = kind;
+    rule.c3 = c3;
+    if (noisy) rule.nsy = nsy;
+    rule.rst = RestoreOps{y, n, a->H, a->W, weights, mask};
+    return sampler_chain(a, who, map, rule, s);
+}
+}  // namespace ddk
+
 extern "C" size_t ddk_sampler_restore_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start) {
     return sampler_bytes(u, B, H, W, t_start, StepKind::Restore);
+}
+extern "C" size_t ddk_sampler_restore_masked_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start, int n) {
+    return restore_bytes(u, B, H, W, t_start, StepKind::RestoreMasked, n);
+}
+extern "C" size_t ddk_sampler_restore_multistep_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start, int n) {
+    return restore_bytes(u, B, H, W, t_start, StepKind::RestoreMultistep, n);
+}
+extern "C" size_t ddk_sampler_restore_noisy_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start, int n) {
+    return restore_bytes(u, B, H, W, t_start, StepKind::RestoreNoisy, n);
+}
+extern "C" size_t ddk_sampler_restore_gray_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start, int n) {
+    return restore_bytes(u, B, H, W, t_start, StepKind::RestoreGray, n);
 }
 
 extern "C" int ddk_sampler_restore_tail_parts(const ddk_unet* u, int B, int H, int W, int n) {
     if (check_shape(u, B, H, W) != DDK_OK) return -1;
-    return fused_tail_parts(*u, B, H, W, u->dimp[1], StepKind::Restore, n);
+    return fused_tail_parts(*u, B, H, W, u->dimp[1], StepKind::Restore, n);      // any n: what final_tail_ok makes of it
 }
-
-extern "C" int ddk_sampler_run_restore(const ddk_sampler_args* a, const int64_t* timestep_map, const float* y, int n, ddk_stream_t s) {
-    DDK_REQUIRE(a && a->unet && a->packed && a->x && a->workspace && y, "sampler_restore: null pointer");
-    DDK_REQUIRE(a->c_recip && a->c_recipm1 && a->c1 && a->c2 && a->sigma, "sampler_restore: null schedule table");
-    DDK_REQUIRE(!a->noise, "sampler_restore: injected noise is not supported, noise must be NULL (Philox only)");
-    DDK_REQUIRE(a->t_start >= a->t_end && a->t_end >= 0, "sampler_restore: need t_start >= t_end >= 0");
-    DDK_REQUIRE((n == 2 || n == 4 || n == 8) && a->H > 0 && a->W > 0 && a->H % n == 0 && a->W % n == 0,
-                "sampler_restore: n must be 2, 4 or 8 and divide H and W");
-    DDK_TRY(check_timestep_map(timestep_map, a->t_start, "sampler_restore"));
-    StepRule rule{};
-    rule.kind = StepKind::Restore;
-    rule.rst = RestoreOps{y, n, a->H, a->W, 0, nullptr};
-    return sampler_chain(a, "sampler_restore", timestep_map, rule, s);
-}
-
-// ------------------------------------------------------------------------------------------------ masked restoration sampler
-// DDNM for A = mask o pool_n: n = 1 is inpainting on the spaced / DDIM tables, an all-measured mask at n >= 2
-// is ddk_sampler_run_restore, in between is super-resolution of a low-resolution image with holes.  With a mask the steps end in
-// StepKind::RestoreMasked; without one (n >= 2 only) the chain IS the Restore kind's: its rule, its kernels, its graph key.
-extern "C" size_t ddk_sampler_restore_masked_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start, int n) {
-    if (!(n == 1 || n == 2 || n == 4 || n == 8)) return 0;
-    return sampler_bytes(u, B, H, W, t_start, StepKind::RestoreMasked, n);
-}
-
 extern "C" int ddk_sampler_restore_masked_tail_parts(const ddk_unet* u, int B, int H, int W, int n) {
-    if (check_shape(u, B, H, W) != DDK_OK || !(n == 1 || n == 2 || n == 4 || n == 8)) return -1;
-    return fused_tail_parts(*u, B, H, W, u->dimp[1], StepKind::RestoreMasked, n);
+    return restore_tail_parts(u, B, H, W, StepKind::RestoreMasked, n);
+}
+extern "C" int ddk_sampler_restore_multistep_tail_parts(const ddk_unet* u, int B, int H, int W, int n) {
+    return restore_tail_parts(u, B, H, W, StepKind::RestoreMultistep, n);
+}
+extern "C" int ddk_sampler_restore_noisy_tail_parts(const ddk_unet* u, int B, int H, int W, int n) {
+    return restore_tail_parts(u, B, H, W, StepKind::RestoreNoisy, n);
+}
+extern "C" int ddk_sampler_restore_gray_tail_parts(const ddk_unet* u, int B, int H, int W, int n) {
+    return restore_tail_parts(u, B, H, W, StepKind::RestoreGray, n);
 }
 
+// super-resolution, A = pool_n (section 3.6)
+extern "C" int ddk_sampler_run_restore(const ddk_sampler_args* a, const int64_t* timestep_map, const float* y, int n, ddk_stream_t s) {
+    return restore_chain(a, "sampler_restore", timestep_map, StepKind::Restore, false, false, nullptr, {}, y, nullptr, n, 0, s);
+}
+
+// A = mask o pool_n (section 3.8): n = 1 is inpainting on the spaced / DDIM tables, an all-measured mask at n >= 2 is
+// ddk_sampler_run_restore, in between is super-resolution of a low-resolution image with holes.  With a mask the steps end in
+// StepKind::RestoreMasked; without one (n >= 2 only) the chain IS the Restore kind's: its rule, its kernels, its graph key.
 extern "C" int ddk_sampler_run_restore_masked(const ddk_sampler_args* a, const int64_t* timestep_map, const float* y, const float* mask, int n,
                                               ddk_stream_t s) {
-    DDK_REQUIRE(a && a->unet && a->packed && a->x && a->workspace && y, "sampler_restore_masked: null pointer");
-    DDK_REQUIRE(a->c_recip && a->c_recipm1 && a->c1 && a->c2 && a->sigma, "sampler_restore_masked: null schedule table");
-    DDK_REQUIRE(!a->noise, "sampler_restore_masked: injected noise is not supported, noise must be NULL (Philox only)");
-    DDK_REQUIRE(a->t_start >= a->t_end && a->t_end >= 0, "sampler_restore_masked: need t_start >= t_end >= 0");
-    DDK_REQUIRE((n == 1 || n == 2 || n == 4 || n == 8) && a->H > 0 && a->W > 0 && a->H % n == 0 && a->W % n == 0,
-                "sampler_restore_masked: n must be 1, 2, 4 or 8 and divide H and W");
-    DDK_REQUIRE(mask || n != 1, "sampler_restore_masked: n = 1 needs a mask (nothing would be constrained)");
-    DDK_TRY(check_timestep_map(timestep_map, a->t_start, "sampler_restore_masked"));
-    // the workspace is held to the masked query's size either way (never less than the Restore kind's, chain_extra_floats)
-    if (a->workspace_bytes < ddk_sampler_restore_masked_workspace_bytes(a->unet, a->B, a->H, a->W, a->t_start, n)) {
-        set_error("sampler_restore_masked: workspace too small (ddk_sampler_restore_masked_workspace_bytes)");
-        return DDK_ERR_WORKSPACE;
-    }
-    StepRule rule{};
-    rule.kind = mask ? StepKind::RestoreMasked : StepKind::Restore;
-    rule.rst = RestoreOps{y, n, a->H, a->W, 0, mask};
-    return sampler_chain(a, "sampler_restore_masked", timestep_map, rule, s);
+    return restore_chain(a, "sampler_restore_masked", timestep_map, mask ? StepKind::RestoreMasked : StepKind::Restore, true, true, nullptr, {}, y,
+                         mask, n, 0, s);
 }
 
-// ------------------------------------------------------------------------------------------------ restoration on the solver
-// DDNM on the DPM-Solver++(2M) chain: ddk_sampler_run_multistep's chain, tables and zeroed history, every
-// step ending in StepKind::RestoreMultistep on y and the optional mask of ddk_sampler_run_restore_masked.  One kind with or without a
-// mask; the graph key carries the kind, c3, n and whether a mask was given.
-extern "C" size_t ddk_sampler_restore_multistep_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start, int n) {
-    if (!(n == 1 || n == 2 || n == 4 || n == 8)) return 0;
-    return sampler_bytes(u, B, H, W, t_start, StepKind::RestoreMultistep, n);
-}
-
-extern "C" int ddk_sampler_restore_multistep_tail_parts(const ddk_unet* u, int B, int H, int W, int n) {
-    if (check_shape(u, B, H, W) != DDK_OK || !(n == 1 || n == 2 || n == 4 || n == 8)) return -1;
-    return fused_tail_parts(*u, B, H, W, u->dimp[1], StepKind::RestoreMultistep, n);
-}
-
+// the DPM-Solver++(2M) chain (section 3.9): ddk_sampler_run_multistep's tables and zeroed history, y and the optional mask of
+// ddk_sampler_run_restore_masked
 extern "C" int ddk_sampler_run_restore_multistep(const ddk_sampler_args* a, const int64_t* timestep_map, const float* c3, const float* y,
                                                  const float* mask, int n, ddk_stream_t s) {
-    DDK_REQUIRE(a && a->unet && a->packed && a->x && a->workspace && y, "sampler_restore_multistep: null pointer");
-    DDK_REQUIRE(a->c_recip && a->c_recipm1 && a->c1 && a->c2 && c3, "sampler_restore_multistep: null schedule table");
-    DDK_REQUIRE(!a->noise, "sampler_restore_multistep: the solver is deterministic, noise must be NULL");
-    DDK_REQUIRE(a->t_start >= a->t_end && a->t_end >= 0, "sampler_restore_multistep: need t_start >= t_end >= 0");
-    DDK_REQUIRE((n == 1 || n == 2 || n == 4 || n == 8) && a->H > 0 && a->W > 0 && a->H % n == 0 && a->W % n == 0,
-                "sampler_restore_multistep: n must be 1, 2, 4 or 8 and divide H and W");
-    DDK_REQUIRE(mask || n != 1, "sampler_restore_multistep: n = 1 needs a mask (nothing would be constrained)");
-    DDK_TRY(check_timestep_map(timestep_map, a->t_start, "sampler_restore_multistep"));
-    StepRule rule{};
-    rule.kind = StepKind::RestoreMultistep;
-    rule.c3 = c3;
-    rule.rst = RestoreOps{y, n, a->H, a->W, 0, mask};
-    return sampler_chain(a, "sampler_restore_multistep", timestep_map, rule, s);
+    return restore_chain(a, "sampler_restore_multistep", timestep_map, StepKind::RestoreMultistep, true, false, c3, {}, y, mask, n, 0, s);
 }
 
-// ------------------------------------------------------------------------------------------------ restoration of a noisy measurement
-// DDNM+: ddk_sampler_run_restore_masked's chain, tables and workspace layout, every step ending in
-// StepKind::RestoreNoisy with the per-row tables lam and sgm.  One kind with or without a mask; the graph key carries the kind, lam and
-// sgm (among its buffers), n and whether a mask was given.
-extern "C" size_t ddk_sampler_restore_noisy_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start, int n) {
-    if (!(n == 1 || n == 2 || n == 4 || n == 8)) return 0;
-    return sampler_bytes(u, B, H, W, t_start, StepKind::RestoreNoisy, n);
-}
-
-extern "C" int ddk_sampler_restore_noisy_tail_parts(const ddk_unet* u, int B, int H, int W, int n) {
-    if (check_shape(u, B, H, W) != DDK_OK || !(n == 1 || n == 2 || n == 4 || n == 8)) return -1;
-    return fused_tail_parts(*u, B, H, W, u->dimp[1], StepKind::RestoreNoisy, n);
-}
-
+// DDNM+ for a noisy measurement (section 3.10): ddk_sampler_run_restore_masked's chain with the per-row tables lam and sgm
 extern "C" int ddk_sampler_run_restore_noisy(const ddk_sampler_args* a, const int64_t* timestep_map, const float* lam, const float* sgm,
                                              const float* y, const float* mask, int n, ddk_stream_t s) {
-    DDK_REQUIRE(a && a->unet && a->packed && a->x && a->workspace && y, "sampler_restore_noisy: null pointer");
-    DDK_REQUIRE(a->c_recip && a->c_recipm1 && a->c1 && a->c2 && a->sigma && lam && sgm, "sampler_restore_noisy: null schedule table");
-    DDK_REQUIRE(!a->noise, "sampler_restore_noisy: injected noise is not supported, noise must be NULL (Philox only)");
-    DDK_REQUIRE(a->t_start >= a->t_end && a->t_end >= 0, "sampler_restore_noisy: need t_start >= t_end >= 0");
-    DDK_REQUIRE((n == 1 || n == 2 || n == 4 || n == 8) && a->H > 0 && a->W > 0 && a->H % n == 0 && a->W % n == 0,
-                "sampler_restore_noisy: n must be 1, 2, 4 or 8 and divide H and W");
-    DDK_REQUIRE(mask || n != 1, "sampler_restore_noisy: n = 1 needs a mask (nothing would be constrained)");
-    DDK_TRY(check_timestep_map(timestep_map, a->t_start, "sampler_restore_noisy"));
-    StepRule rule{};
-    rule.kind = StepKind::RestoreNoisy;
-    rule.nsy = NoisyTables{lam, sgm};
-    rule.rst = RestoreOps{y, n, a->H, a->W, 0, mask};
-    return sampler_chain(a, "sampler_restore_noisy", timestep_map, rule, s);
+    return restore_chain(a, "sampler_restore_noisy", timestep_map, StepKind::RestoreNoisy, true, false, nullptr, {lam, sgm}, y, mask, n, 0, s);
 }
 
-// ------------------------------------------------------------------------------------------------ colourisation, grey super-resolution
-// DDNM / DDNM+ for A = mask o pool_n o grey_w on a 3-channel pixel model: ddk_sampler_run_restore_noisy's chain,
-// tables and workspace, every step ending in StepKind::RestoreGray.  y and the mask are [B][H/n][W/n]; the mask is optional at every n.
-// The graph key carries the kind, lam and sgm (among its buffers), n, whether a mask was given and the weights.
-extern "C" size_t ddk_sampler_restore_gray_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start, int n) {
-    if (!(n == 1 || n == 2 || n == 4 || n == 8)) return 0;
-    return sampler_bytes(u, B, H, W, t_start, StepKind::RestoreGray, n);
-}
-
-extern "C" int ddk_sampler_restore_gray_tail_parts(const ddk_unet* u, int B, int H, int W, int n) {
-    if (check_shape(u, B, H, W) != DDK_OK || !(n == 1 || n == 2 || n == 4 || n == 8)) return -1;
-    return fused_tail_parts(*u, B, H, W, u->dimp[1], StepKind::RestoreGray, n);
-}
-
+// A = mask o pool_n o grey_w on a 3-channel pixel model (section 3.11): ddk_sampler_run_restore_noisy's chain; y and the mask are
+// [B][H/n][W/n], the mask optional at every n
 extern "C" int ddk_sampler_run_restore_gray(const ddk_sampler_args* a, const int64_t* timestep_map, const float* lam, const float* sgm,
                                             const float* y, const float* mask, int n, int weights, ddk_stream_t s) {
-    DDK_REQUIRE(a && a->unet && a->packed && a->x && a->workspace && y, "sampler_restore_gray: null pointer");
-    DDK_REQUIRE(a->c_recip && a->c_recipm1 && a->c1 && a->c2 && a->sigma && lam && sgm, "sampler_restore_gray: null schedule table");
-    DDK_REQUIRE(!a->noise, "sampler_restore_gray: injected noise is not supported, noise must be NULL (Philox only)");
-    DDK_REQUIRE(a->unet->cfg.in_ch == 3, "sampler_restore_gray: the grey operator needs a 3-channel model");
-    DDK_REQUIRE(weights == GRAY_MEAN || weights == GRAY_LUMA, "sampler_restore_gray: weights must be 1 (mean) or 2 (luma)");
-    DDK_REQUIRE(a->t_start >= a->t_end && a->t_end >= 0, "sampler_restore_gray: need t_start >= t_end >= 0");
-    DDK_REQUIRE((n == 1 || n == 2 || n == 4 || n == 8) && a->H > 0 && a->W > 0 && a->H % n == 0 && a->W % n == 0,
-                "sampler_restore_gray: n must be 1, 2, 4 or 8 and divide H and W");
-    DDK_TRY(check_timestep_map(timestep_map, a->t_start, "sampler_restore_gray"));
-    StepRule rule{};
-    rule.kind = StepKind::RestoreGray;
-    rule.nsy = NoisyTables{lam, sgm};
-    rule.rst = RestoreOps{y, n, a->H, a->W, weights, mask};
-    return sampler_chain(a, "sampler_restore_gray", timestep_map, rule, s);
+    return restore_chain(a, "sampler_restore_gray", timestep_map, StepKind::RestoreGray, true, false, nullptr, {lam, sgm}, y, mask, n, weights, s);
 }
 
 // ------------------------------------------------------------------------------------------------ likelihood sweep

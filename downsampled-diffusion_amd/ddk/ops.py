@@ -771,15 +771,25 @@ def p_sample_update_inpaint_(x, eps_hat, known, mask, t, c_recip, c_recipm1, c1,
     return x
 
 
+def _restore_operands(who, x, eps_hat, y, mask, n, x0_hist=None, takes_mask=True, y_channels=True):
+    """What the DDNM step ops share: the shape check of x [B,H,W,C], eps_hat, (x0_hist,) y [B,H/n,W/n(,C)] and mask [B,H/n,W/n] or None
+    with its message, then the pointers every C entry starts with and its shape arguments: (x, eps_hat), (y, mask), n, (b, h, w, c)."""
+    b, h, w, c = x.shape
+    n = int(n)
+    if n < 1 or tuple(y.shape) != ((b, h // n, w // n, c) if y_channels else (b, h // n, w // n)) or tuple(eps_hat.shape) != tuple(x.shape) or \
+            (x0_hist is not None and tuple(x0_hist.shape) != tuple(x.shape)) or (mask is not None and tuple(mask.shape) != (b, h // n, w // n)):
+        hist = "" if x0_hist is None else f"x0_hist {tuple(x0_hist.shape)}, "
+        msk = f"mask {None if mask is None else tuple(mask.shape)}, " if takes_mask else ""
+        raise L.DDKError(f"{who}: x {tuple(x.shape)}, eps_hat {tuple(eps_hat.shape)}, {hist}y {tuple(y.shape)}, {msk}n = {n}")
+    return (L.ptr(_f32(x)), L.ptr(_f32(eps_hat))), (L.ptr(_f32(y)), L.ptr(None if mask is None else _f32(mask))), n, (b, h, w, c)
+
+
 def p_sample_update_restore_(x, eps_hat, y, n, t, c_recip, c_recipm1, c1, c2, sigma, seed=0, stream_id=0):
     """In-place DDNM super-resolution step of x [B,H,W,C] (NHWC) per sample row t[b]: the clipped x0 is
     shifted so that its n x n block means equal y [B,H/n,W/n,C], then the ancestral update with Philox draws runs on it."""
-    b, h, w, c = x.shape
-    if tuple(y.shape) != (b, h // n, w // n, c) or tuple(eps_hat.shape) != tuple(x.shape):
-        raise L.DDKError(f"p_sample_update_restore: x {tuple(x.shape)}, eps_hat {tuple(eps_hat.shape)}, y {tuple(y.shape)}, n = {n}")
-    L.check(L.load().ddk_p_sample_update_restore(L.ptr(_f32(x)), L.ptr(_f32(eps_hat)), L.ptr(_f32(y)), int(n), L.ptr(t), L.ptr(c_recip),
-                                                 L.ptr(c_recipm1), L.ptr(c1), L.ptr(c2), L.ptr(sigma), b, h, w, c, seed, stream_id,
-                                                 L.stream()), "p_sample_update_restore")
+    xe, (yp, _), n, shape = _restore_operands("p_sample_update_restore", x, eps_hat, y, None, n, takes_mask=False)
+    L.check(L.load().ddk_p_sample_update_restore(*xe, yp, n, L.ptr(t), L.ptr(c_recip), L.ptr(c_recipm1), L.ptr(c1), L.ptr(c2), L.ptr(sigma),
+                                                 *shape, seed, stream_id, L.stream()), "p_sample_update_restore")
     return x
 
 
@@ -788,16 +798,9 @@ def p_sample_update_restore_masked_(x, eps_hat, y, mask, n, t, c_recip, c_recipm
     where mask [B,H/n,W/n] is nonzero the clipped x0 is shifted so that its block mean equals y [B,H/n,W/n,C] (n = 1: replaced by
     y), elsewhere it is kept; then the ancestral update with Philox draws.  n in {1, 2, 4, 8}; mask None (n >= 2 only): every
     block is measured, p_sample_update_restore_ bit for bit."""
-    b, h, w, c = x.shape
-    n = int(n)
-    if n < 1 or tuple(y.shape) != (b, h // n, w // n, c) or tuple(eps_hat.shape) != tuple(x.shape) or \
-            (mask is not None and tuple(mask.shape) != (b, h // n, w // n)):
-        raise L.DDKError(f"p_sample_update_restore_masked: x {tuple(x.shape)}, eps_hat {tuple(eps_hat.shape)}, y {tuple(y.shape)}, "
-                         f"mask {None if mask is None else tuple(mask.shape)}, n = {n}")
-    L.check(L.load().ddk_p_sample_update_restore_masked(L.ptr(_f32(x)), L.ptr(_f32(eps_hat)), L.ptr(_f32(y)),
-                                                        L.ptr(None if mask is None else _f32(mask)), n, L.ptr(t), L.ptr(c_recip),
-                                                        L.ptr(c_recipm1), L.ptr(c1), L.ptr(c2), L.ptr(sigma), b, h, w, c, seed, stream_id,
-                                                        L.stream()), "p_sample_update_restore_masked")
+    xe, ym, n, shape = _restore_operands("p_sample_update_restore_masked", x, eps_hat, y, mask, n)
+    L.check(L.load().ddk_p_sample_update_restore_masked(*xe, *ym, n, L.ptr(t), L.ptr(c_recip), L.ptr(c_recipm1), L.ptr(c1), L.ptr(c2),
+                                                        L.ptr(sigma), *shape, seed, stream_id, L.stream()), "p_sample_update_restore_masked")
     return x
 
 
@@ -806,15 +809,9 @@ def p_sample_update_restore_multistep_(x, eps_hat, x0_hist, y, mask, n, t, c_rec
     (same layout; zeros before a chain's first step) per sample row t[b]: p_sample_update_restore_masked_'s x0' for y, mask and n,
     then x = (c1 x0' + c2 x) + c3 x0_hist and x0_hist = x0'.  No draw.  n in {1, 2, 4, 8}; mask None (n >= 2 only): every block is
     measured."""
-    b, h, w, c = x.shape
-    n = int(n)
-    if n < 1 or tuple(y.shape) != (b, h // n, w // n, c) or tuple(eps_hat.shape) != tuple(x.shape) or \
-            tuple(x0_hist.shape) != tuple(x.shape) or (mask is not None and tuple(mask.shape) != (b, h // n, w // n)):
-        raise L.DDKError(f"p_sample_update_restore_multistep: x {tuple(x.shape)}, eps_hat {tuple(eps_hat.shape)}, x0_hist "
-                         f"{tuple(x0_hist.shape)}, y {tuple(y.shape)}, mask {None if mask is None else tuple(mask.shape)}, n = {n}")
-    L.check(L.load().ddk_p_sample_update_restore_multistep(L.ptr(_f32(x)), L.ptr(_f32(eps_hat)), L.ptr(_f32(x0_hist)), L.ptr(_f32(y)),
-                                                           L.ptr(None if mask is None else _f32(mask)), n, L.ptr(t), L.ptr(c_recip),
-                                                           L.ptr(c_recipm1), L.ptr(c1), L.ptr(c2), L.ptr(c3), b, h, w, c, L.stream()),
+    xe, ym, n, shape = _restore_operands("p_sample_update_restore_multistep", x, eps_hat, y, mask, n, x0_hist=x0_hist)
+    L.check(L.load().ddk_p_sample_update_restore_multistep(*xe, L.ptr(_f32(x0_hist)), *ym, n, L.ptr(t), L.ptr(c_recip), L.ptr(c_recipm1),
+                                                           L.ptr(c1), L.ptr(c2), L.ptr(c3), *shape, L.stream()),
             "p_sample_update_restore_multistep")
     return x
 
@@ -824,16 +821,10 @@ def p_sample_update_restore_noisy_(x, eps_hat, y, mask, n, t, c_recip, c_recipm1
     p_sample_update_restore_masked_'s step with the correction of a measured block (n = 1: pixel) scaled by lam[t] and its draw by
     sgm[t] instead of sigma[t]; what is not measured keeps its clipped x0 and the full draw.  n in {1, 2, 4, 8}; mask None (n >= 2
     only): every block is measured."""
-    b, h, w, c = x.shape
-    n = int(n)
-    if n < 1 or tuple(y.shape) != (b, h // n, w // n, c) or tuple(eps_hat.shape) != tuple(x.shape) or \
-            (mask is not None and tuple(mask.shape) != (b, h // n, w // n)):
-        raise L.DDKError(f"p_sample_update_restore_noisy: x {tuple(x.shape)}, eps_hat {tuple(eps_hat.shape)}, y {tuple(y.shape)}, "
-                         f"mask {None if mask is None else tuple(mask.shape)}, n = {n}")
-    L.check(L.load().ddk_p_sample_update_restore_noisy(L.ptr(_f32(x)), L.ptr(_f32(eps_hat)), L.ptr(_f32(y)),
-                                                       L.ptr(None if mask is None else _f32(mask)), n, L.ptr(t), L.ptr(c_recip),
-                                                       L.ptr(c_recipm1), L.ptr(c1), L.ptr(c2), L.ptr(sigma), L.ptr(lam), L.ptr(sgm), b, h, w, c,
-                                                       seed, stream_id, L.stream()), "p_sample_update_restore_noisy")
+    xe, ym, n, shape = _restore_operands("p_sample_update_restore_noisy", x, eps_hat, y, mask, n)
+    L.check(L.load().ddk_p_sample_update_restore_noisy(*xe, *ym, n, L.ptr(t), L.ptr(c_recip), L.ptr(c_recipm1), L.ptr(c1), L.ptr(c2),
+                                                       L.ptr(sigma), L.ptr(lam), L.ptr(sgm), *shape, seed, stream_id, L.stream()),
+            "p_sample_update_restore_noisy")
     return x
 
 
@@ -842,18 +833,12 @@ def p_sample_update_restore_gray_(x, eps_hat, y, mask, n, weights, t, c_recip, c
     p_sample_update_restore_noisy_'s step with the block mean replaced by the weighted mean of the n x n x 3 group and the correction
     spread over the channels by A+.  y and mask are [B,H/n,W/n]; mask None: every block measured.  n in {1, 2, 4, 8}; weights "mean"
     (1/3 each) or "luma" (BT.601)."""
-    b, h, w, c = x.shape
-    n = int(n)
     if weights not in L.GRAY_WEIGHTS:
         raise L.DDKError(f"p_sample_update_restore_gray: weights must be 'mean' or 'luma', got {weights!r}")
-    if n < 1 or tuple(y.shape) != (b, h // n, w // n) or tuple(eps_hat.shape) != tuple(x.shape) or \
-            (mask is not None and tuple(mask.shape) != (b, h // n, w // n)):
-        raise L.DDKError(f"p_sample_update_restore_gray: x {tuple(x.shape)}, eps_hat {tuple(eps_hat.shape)}, y {tuple(y.shape)}, "
-                         f"mask {None if mask is None else tuple(mask.shape)}, n = {n}")
-    L.check(L.load().ddk_p_sample_update_restore_gray(L.ptr(_f32(x)), L.ptr(_f32(eps_hat)), L.ptr(_f32(y)),
-                                                      L.ptr(None if mask is None else _f32(mask)), n, L.GRAY_WEIGHTS[weights], L.ptr(t),
-                                                      L.ptr(c_recip), L.ptr(c_recipm1), L.ptr(c1), L.ptr(c2), L.ptr(sigma), L.ptr(lam),
-                                                      L.ptr(sgm), b, h, w, c, seed, stream_id, L.stream()), "p_sample_update_restore_gray")
+    xe, ym, n, shape = _restore_operands("p_sample_update_restore_gray", x, eps_hat, y, mask, n, y_channels=False)
+    L.check(L.load().ddk_p_sample_update_restore_gray(*xe, *ym, n, L.GRAY_WEIGHTS[weights], L.ptr(t), L.ptr(c_recip), L.ptr(c_recipm1),
+                                                      L.ptr(c1), L.ptr(c2), L.ptr(sigma), L.ptr(lam), L.ptr(sgm), *shape, seed, stream_id,
+                                                      L.stream()), "p_sample_update_restore_gray")
     return x
 
 

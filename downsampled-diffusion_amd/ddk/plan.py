@@ -350,9 +350,60 @@ class UnetPlan:
         return self._run_sampler("sin", x, t_start, t_end,
                                  lambda b, h, w: lib.ddk_sampler_inpaint_workspace_bytes(self.handle, b, h, w, n_ops), call, use_graph)
 
+    # the restoration samplers (DDNM; DESIGN.md sections 3.6, 3.8 - 3.11): the C entries of each workspace kind (run, workspace query, tail query), less their ddk_ prefix
+    RESTORE_ENTRIES = {
+        "srs": ("sampler_run_restore", "sampler_restore_workspace_bytes", "sampler_restore_tail_parts"),
+        "srm": ("sampler_run_restore_masked", "sampler_restore_masked_workspace_bytes", "sampler_restore_masked_tail_parts"),
+        "srx": ("sampler_run_restore_multistep", "sampler_restore_multistep_workspace_bytes",
+                "sampler_restore_multistep_tail_parts"),
+        "srn": ("sampler_run_restore_noisy", "sampler_restore_noisy_workspace_bytes", "sampler_restore_noisy_tail_parts"),
+        "srg": ("sampler_run_restore_gray", "sampler_restore_gray_workspace_bytes", "sampler_restore_gray_tail_parts")}
+
+    def _restore_tail_parts(self, kind, b, h, w, n):
+        return int(getattr(self._lib, "ddk_" + self.RESTORE_ENTRIES[kind][2])(self.handle, b, h, w, int(n)))
+
+    def _sample_restore(self, kind, x, y, mask, n, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, head=(), masked=True,
+                        weights=None):
+        """What the restoration samplers share: the checks on n, y, mask and the lam / sgm tables, then the chain.
+        kind: the entry's key in SAMPLERS and RESTORE_ENTRIES; head: the names of the tables the C entry takes before y; masked: the
+        entry takes a mask and n = 1 (which then needs one), and its workspace query takes n; weights: the grey entry's, whose y is
+        [B,H/n,W/n] and whose n = 1 needs no mask."""
+        self._need_packed(kind)
+        name = SAMPLERS[kind][0]
+        gray = weights is not None
+        b, h, w, c = x.shape
+        if gray and c != 3:
+            raise L.DDKError(f"{name}: the grey operator needs a 3-channel map, got {c} channels")
+        if gray and weights not in L.GRAY_WEIGHTS:
+            raise L.DDKError(f"{name}: weights must be 'mean' or 'luma', got {weights!r}")
+        if n not in ((1, 2, 4, 8) if masked else (2, 4, 8)) or h % n or w % n:
+            raise L.DDKError(f"{name}: n must be {'1, ' if masked else ''}2, 4 or 8 and divide H = {h} and W = {w}, got {n}")
+        if mask is None and n == 1 and not gray:
+            raise L.DDKError(f"{name}: n = 1 needs a mask (nothing would be constrained)")
+        for what, v, shape in (("y", y, (b, h // n, w // n) if gray else (b, h // n, w // n, c)), ("mask", mask, (b, h // n, w // n))):
+            if v is not None and (tuple(v.shape) != shape or v.dtype != torch.float32 or not v.is_contiguous()):
+                raise L.DDKError(f"{what} must be a contiguous fp32 [{','.join(map(str, shape))}] tensor, got {tuple(v.shape)} {v.dtype}")
+        for t in head:
+            if t != "c3" and (tuple(tables[t].shape) != tuple(tables["c1"].shape) or tables[t].dtype != torch.float32):      # c3: the solver's own
+                raise L.DDKError(f"tables[{t!r}] must be an fp32 tensor with one entry per row of c1, got {tuple(tables[t].shape)}")
+        run_name = self.RESTORE_ENTRIES[kind][0]
+        run, workspace_bytes = (getattr(self._lib, "ddk_" + f) for f in self.RESTORE_ENTRIES[kind][:2])
+        tmap = self._timestep_map(timesteps, t_start)
+        operands = (L.ptr(y), L.ptr(mask), int(n)) if masked else (L.ptr(y), int(n))
+        if gray:
+            operands += (L.GRAY_WEIGHTS[weights],)
+
+        def call(x, ws, nbytes, stream_ptr):
+            a = self._sampler_args(x, None, tables, t_start, t_end, seed, stream_id, use_graph, ws, nbytes)
+            L.check(run(C.byref(a), tmap, *(L.ptr(tables[t]) for t in head), *operands, stream_ptr), run_name)
+
+        return self._run_sampler(kind, x, t_start, t_end,
+                                 lambda b, h, w: workspace_bytes(self.handle, b, h, w, t_start, *((int(n),) if masked else ())), call,
+                                 use_graph)
+
     def restore_tail_parts(self, b, h, w, n):
         """Tiles per image of the fused tail of a super-resolution step on [b, h, w] with block n, or 0: the unfused tail."""
-        return int(self._lib.ddk_sampler_restore_tail_parts(self.handle, b, h, w, int(n)))
+        return self._restore_tail_parts("srs", b, h, w, n)
 
     def sample_restore_nhwc(self, x, y, n, tables, t_start, t_end=0, seed=0, stream_id=0, use_graph=True, timesteps=None):
         """DDNM super-resolution steps t_start .. t_end (inclusive) in place on x [B,H,W,in_ch] (ddk_sampler_run_restore; DESIGN.md
@@ -361,25 +412,11 @@ class UnetPlan:
         y: [B,H/n,W/n,in_ch] fp32 device tensor, copied into the plan's "srs" workspace by every call, so a loop over images replays
         one cached graph; n in {2, 4, 8} divides H and W.  tables / timesteps: as for sample_nhwc (plain, respaced or DDIM).
         Philox only: no injected noise."""
-        self._need_packed("srs")
-        b, h, w, c = x.shape
-        if n not in (2, 4, 8) or h % n or w % n:
-            raise L.DDKError(f"sample_restore: n must be 2, 4 or 8 and divide H = {h} and W = {w}, got {n}")
-        if tuple(y.shape) != (b, h // n, w // n, c) or y.dtype != torch.float32 or not y.is_contiguous():
-            raise L.DDKError(f"y must be a contiguous fp32 [{b},{h // n},{w // n},{c}] tensor, got {tuple(y.shape)} {y.dtype}")
-        lib = self._lib
-        tmap = self._timestep_map(timesteps, t_start)
-
-        def call(x, ws, nbytes, stream_ptr):
-            a = self._sampler_args(x, None, tables, t_start, t_end, seed, stream_id, use_graph, ws, nbytes)
-            L.check(lib.ddk_sampler_run_restore(C.byref(a), tmap, L.ptr(y), int(n), stream_ptr), "sampler_run_restore")
-
-        return self._run_sampler("srs", x, t_start, t_end,
-                                 lambda b, h, w: lib.ddk_sampler_restore_workspace_bytes(self.handle, b, h, w, t_start), call, use_graph)
+        return self._sample_restore("srs", x, y, None, n, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, masked=False)
 
     def restore_masked_tail_parts(self, b, h, w, n):
         """Tiles per image of the fused tail of a masked restoration step on [b, h, w] with block n (1 included), or 0."""
-        return int(self._lib.ddk_sampler_restore_masked_tail_parts(self.handle, b, h, w, int(n)))
+        return self._restore_tail_parts("srm", b, h, w, n)
 
     def sample_restore_masked_nhwc(self, x, y, mask, n, tables, t_start, t_end=0, seed=0, stream_id=0, use_graph=True, timesteps=None):
         """DDNM steps for A = mask o (n x n average pooling), t_start .. t_end (inclusive), in place on x [B,H,W,in_ch]
@@ -388,31 +425,11 @@ class UnetPlan:
         y: [B,H/n,W/n,in_ch], mask: [B,H/n,W/n] (nonzero = measured) fp32 device tensors, copied into the plan's "srm" workspace by
         every call, so a loop over images and masks replays one cached graph; n in {1, 2, 4, 8} divides H and W.  mask None (n >= 2
         only) is sample_restore_nhwc's chain.  tables / timesteps: as for sample_nhwc (plain, respaced or DDIM).  Philox only."""
-        self._need_packed("srm")
-        b, h, w, c = x.shape
-        if n not in (1, 2, 4, 8) or h % n or w % n:
-            raise L.DDKError(f"sample_restore_masked: n must be 1, 2, 4 or 8 and divide H = {h} and W = {w}, got {n}")
-        if mask is None and n == 1:
-            raise L.DDKError("sample_restore_masked: n = 1 needs a mask (nothing would be constrained)")
-        if tuple(y.shape) != (b, h // n, w // n, c) or y.dtype != torch.float32 or not y.is_contiguous():
-            raise L.DDKError(f"y must be a contiguous fp32 [{b},{h // n},{w // n},{c}] tensor, got {tuple(y.shape)} {y.dtype}")
-        if mask is not None and (tuple(mask.shape) != (b, h // n, w // n) or mask.dtype != torch.float32 or not mask.is_contiguous()):
-            raise L.DDKError(f"mask must be a contiguous fp32 [{b},{h // n},{w // n}] tensor, got {tuple(mask.shape)} {mask.dtype}")
-        lib = self._lib
-        tmap = self._timestep_map(timesteps, t_start)
-
-        def call(x, ws, nbytes, stream_ptr):
-            a = self._sampler_args(x, None, tables, t_start, t_end, seed, stream_id, use_graph, ws, nbytes)
-            L.check(lib.ddk_sampler_run_restore_masked(C.byref(a), tmap, L.ptr(y), L.ptr(mask), int(n), stream_ptr),
-                    "sampler_run_restore_masked")
-
-        return self._run_sampler("srm", x, t_start, t_end,
-                                 lambda b, h, w: lib.ddk_sampler_restore_masked_workspace_bytes(self.handle, b, h, w, t_start, int(n)),
-                                 call, use_graph)
+        return self._sample_restore("srm", x, y, mask, n, tables, t_start, t_end, seed, stream_id, use_graph, timesteps)
 
     def restore_multistep_tail_parts(self, b, h, w, n):
         """Tiles per image of the fused tail of a restoration-solver step on [b, h, w] with block n (1 included), or 0."""
-        return int(self._lib.ddk_sampler_restore_multistep_tail_parts(self.handle, b, h, w, int(n)))
+        return self._restore_tail_parts("srx", b, h, w, n)
 
     def sample_restore_multistep_nhwc(self, x, y, mask, n, tables, t_start, t_end=0, stream_id=0, use_graph=True, timesteps=None):
         """DDNM for A = mask o (n x n average pooling) on DPM-Solver++(2M) steps t_start .. t_end (inclusive), in place on x
@@ -421,31 +438,11 @@ class UnetPlan:
         y, mask, n: as for sample_restore_masked_nhwc (mask None at n >= 2: every block measured); they are copied into the plan's
         "srx" workspace by every call, so a loop over images and masks replays one cached graph.  tables / timesteps: as for
         sample_multistep_nhwc.  Deterministic: no noise, no seed; the history is zeroed by every call."""
-        self._need_packed("srx")
-        b, h, w, c = x.shape
-        if n not in (1, 2, 4, 8) or h % n or w % n:
-            raise L.DDKError(f"sample_restore_multistep: n must be 1, 2, 4 or 8 and divide H = {h} and W = {w}, got {n}")
-        if mask is None and n == 1:
-            raise L.DDKError("sample_restore_multistep: n = 1 needs a mask (nothing would be constrained)")
-        if tuple(y.shape) != (b, h // n, w // n, c) or y.dtype != torch.float32 or not y.is_contiguous():
-            raise L.DDKError(f"y must be a contiguous fp32 [{b},{h // n},{w // n},{c}] tensor, got {tuple(y.shape)} {y.dtype}")
-        if mask is not None and (tuple(mask.shape) != (b, h // n, w // n) or mask.dtype != torch.float32 or not mask.is_contiguous()):
-            raise L.DDKError(f"mask must be a contiguous fp32 [{b},{h // n},{w // n}] tensor, got {tuple(mask.shape)} {mask.dtype}")
-        lib = self._lib
-        tmap = self._timestep_map(timesteps, t_start)
-
-        def call(x, ws, nbytes, stream_ptr):
-            a = self._sampler_args(x, None, tables, t_start, t_end, 0, stream_id, use_graph, ws, nbytes)
-            L.check(lib.ddk_sampler_run_restore_multistep(C.byref(a), tmap, L.ptr(tables["c3"]), L.ptr(y), L.ptr(mask), int(n), stream_ptr),
-                    "sampler_run_restore_multistep")
-
-        return self._run_sampler("srx", x, t_start, t_end,
-                                 lambda b, h, w: lib.ddk_sampler_restore_multistep_workspace_bytes(self.handle, b, h, w, t_start, int(n)),
-                                 call, use_graph)
+        return self._sample_restore("srx", x, y, mask, n, tables, t_start, t_end, 0, stream_id, use_graph, timesteps, head=("c3",))
 
     def restore_noisy_tail_parts(self, b, h, w, n):
         """Tiles per image of the fused tail of a noisy restoration step on [b, h, w] with block n (1 included), or 0."""
-        return int(self._lib.ddk_sampler_restore_noisy_tail_parts(self.handle, b, h, w, int(n)))
+        return self._restore_tail_parts("srn", b, h, w, n)
 
     def sample_restore_noisy_nhwc(self, x, y, mask, n, tables, t_start, t_end=0, seed=0, stream_id=0, use_graph=True, timesteps=None):
         """DDNM+ steps for a noisy measurement of A = mask o (n x n average pooling), t_start .. t_end (inclusive), in place on x
@@ -454,35 +451,12 @@ class UnetPlan:
         y, mask, n: as for sample_restore_masked_nhwc (mask None at n >= 2: every block measured); they are copied into the plan's
         "srn" workspace by every call.  tables: sample_restore_masked_nhwc's plus the per-row "lam" and "sgm" (respace.noisy_tables);
         they are in the graph key, so chains with different noise levels never replay each other's graph.  Philox only."""
-        self._need_packed("srn")
-        b, h, w, c = x.shape
-        if n not in (1, 2, 4, 8) or h % n or w % n:
-            raise L.DDKError(f"sample_restore_noisy: n must be 1, 2, 4 or 8 and divide H = {h} and W = {w}, got {n}")
-        if mask is None and n == 1:
-            raise L.DDKError("sample_restore_noisy: n = 1 needs a mask (nothing would be constrained)")
-        if tuple(y.shape) != (b, h // n, w // n, c) or y.dtype != torch.float32 or not y.is_contiguous():
-            raise L.DDKError(f"y must be a contiguous fp32 [{b},{h // n},{w // n},{c}] tensor, got {tuple(y.shape)} {y.dtype}")
-        if mask is not None and (tuple(mask.shape) != (b, h // n, w // n) or mask.dtype != torch.float32 or not mask.is_contiguous()):
-            raise L.DDKError(f"mask must be a contiguous fp32 [{b},{h // n},{w // n}] tensor, got {tuple(mask.shape)} {mask.dtype}")
-        for name in ("lam", "sgm"):
-            if tuple(tables[name].shape) != tuple(tables["c1"].shape) or tables[name].dtype != torch.float32:
-                raise L.DDKError(f"tables[{name!r}] must be an fp32 tensor with one entry per row of c1, got {tuple(tables[name].shape)}")
-        lib = self._lib
-        tmap = self._timestep_map(timesteps, t_start)
-
-        def call(x, ws, nbytes, stream_ptr):
-            a = self._sampler_args(x, None, tables, t_start, t_end, seed, stream_id, use_graph, ws, nbytes)
-            L.check(lib.ddk_sampler_run_restore_noisy(C.byref(a), tmap, L.ptr(tables["lam"]), L.ptr(tables["sgm"]), L.ptr(y), L.ptr(mask),
-                                                      int(n), stream_ptr), "sampler_run_restore_noisy")
-
-        return self._run_sampler("srn", x, t_start, t_end,
-                                 lambda b, h, w: lib.ddk_sampler_restore_noisy_workspace_bytes(self.handle, b, h, w, t_start, int(n)),
-                                 call, use_graph)
+        return self._sample_restore("srn", x, y, mask, n, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, head=("lam", "sgm"))
 
     def restore_gray_tail_parts(self, b, h, w, n):
         """Tiles per image of the fused tail of a colourisation step on [b, h, w] with block n (1 included), or 0 (always 0 for a
         model that does not have 3 channels)."""
-        return int(self._lib.ddk_sampler_restore_gray_tail_parts(self.handle, b, h, w, int(n)))
+        return self._restore_tail_parts("srg", b, h, w, n)
 
     def sample_restore_gray_nhwc(self, x, y, mask, n, weights, tables, t_start, t_end=0, seed=0, stream_id=0, use_graph=True,
                                  timesteps=None):
@@ -492,31 +466,8 @@ class UnetPlan:
         y, mask: contiguous fp32 [B,H/n,W/n] (mask None: every block measured, at any n); weights "mean" or "luma"; they are copied
         into the plan's "srg" workspace by every call.  tables: sample_restore_noisy_nhwc's, "lam" and "sgm" included
         (respace.gray_tables); the tables, n, the mask's presence and the weights are in the graph key.  Philox only."""
-        self._need_packed("srg")
-        b, h, w, c = x.shape
-        if c != 3:
-            raise L.DDKError(f"sample_restore_gray: the grey operator needs a 3-channel map, got {c} channels")
-        if weights not in L.GRAY_WEIGHTS:
-            raise L.DDKError(f"sample_restore_gray: weights must be 'mean' or 'luma', got {weights!r}")
-        if n not in (1, 2, 4, 8) or h % n or w % n:
-            raise L.DDKError(f"sample_restore_gray: n must be 1, 2, 4 or 8 and divide H = {h} and W = {w}, got {n}")
-        for name, v in (("y", y), ("mask", mask)):
-            if v is not None and (tuple(v.shape) != (b, h // n, w // n) or v.dtype != torch.float32 or not v.is_contiguous()):
-                raise L.DDKError(f"{name} must be a contiguous fp32 [{b},{h // n},{w // n}] tensor, got {tuple(v.shape)} {v.dtype}")
-        for name in ("lam", "sgm"):
-            if tuple(tables[name].shape) != tuple(tables["c1"].shape) or tables[name].dtype != torch.float32:
-                raise L.DDKError(f"tables[{name!r}] must be an fp32 tensor with one entry per row of c1, got {tuple(tables[name].shape)}")
-        lib = self._lib
-        tmap = self._timestep_map(timesteps, t_start)
-
-        def call(x, ws, nbytes, stream_ptr):
-            a = self._sampler_args(x, None, tables, t_start, t_end, seed, stream_id, use_graph, ws, nbytes)
-            L.check(lib.ddk_sampler_run_restore_gray(C.byref(a), tmap, L.ptr(tables["lam"]), L.ptr(tables["sgm"]), L.ptr(y), L.ptr(mask),
-                                                     int(n), L.GRAY_WEIGHTS[weights], stream_ptr), "sampler_run_restore_gray")
-
-        return self._run_sampler("srg", x, t_start, t_end,
-                                 lambda b, h, w: lib.ddk_sampler_restore_gray_workspace_bytes(self.handle, b, h, w, t_start, int(n)),
-                                 call, use_graph)
+        return self._sample_restore("srg", x, y, mask, n, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, head=("lam", "sgm"),
+                                    weights=weights)
 
     # ---------------------------------------------------------------- likelihood sweep
     VLB_STREAM_BIT = 1 << 31     # the sweep's Philox stream id is stream_id | this (csrc/ddk_internal.h VLB_STREAM_BIT)

@@ -368,16 +368,16 @@ class DDPM(nn.Module):
             raise ValueError("super_resolve: y must be finite")
         return y.float()
 
-    def _restore_loop(self, y, n, respacing, ddim, eta, x_T, seed, mask=None, who="super_resolve"):
-        """DDNM over the latent whose n x n block means are held at y [B, C, H/n, W/n]: native (UnetPlan.sample_restore_nhwc) or,
-        with native_sampler off, the same op as a Python loop in the same NHWC layout, so both draw the same Philox numbers.
-        mask [B, H/n, W/n] ({0, 1} floats, restore() only): the blocks that are held (n = 1: the pixels that are set to y); the
-        masked op and UnetPlan.sample_restore_masked_nhwc then take the place of the two above."""
+    def _ddnm_loop(self, who, y, mask, get_tables, x_T, seed, op, chain):
+        """What the DDNM chains share, over the latent measured as y ([B, C, h, w], or the grey [B, h, w]) where mask [B, h, w] (None:
+        everywhere) is 1: the device check, (tables, timestep map or None) = get_tables(), x_T, the Philox seed (drawn from torch's
+        generator when None), then all the tables' steps, native or -- with native_sampler off -- as a Python loop over the same op in
+        the same NHWC layout, so both draw the same Philox numbers.  chain(plan, x, y, mask, tables, k_start, seed, use) runs the
+        native chain in place on the NHWC x; op(x, eps_hat, y, mask, t, tables, seed) is one step of it."""
         device = self.betas.device
         if device.type != 'cuda':
             raise DDKError(f"{who}: move the model to a ROCm device first (no CPU fallback)")
-        spaced = respacing is not None or ddim or eta != 0
-        tables, use = self._spaced_tables(respacing, ddim, eta) if spaced else (self._tables(), None)
+        tables, use = get_tables()
         shape = (y.shape[0], *self.sample_shape)
         if x_T is not None and tuple(x_T.shape) != shape:
             raise ValueError(f"{who}: x_T must be {shape}, got {tuple(x_T.shape)}")
@@ -385,37 +385,44 @@ class DDPM(nn.Module):
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         k_start = (self.timesteps if use is None else len(use)) - 1
-        yl = ops.nchw_to_nhwc(y.to(device).float().contiguous())
+        yl = y.to(device).float().contiguous()
+        if yl.dim() == 4:
+            yl = ops.nchw_to_nhwc(yl)
+        mk = None if mask is None else mask.to(device).float().contiguous()
         x = ops.nchw_to_nhwc(img.contiguous())
-        if mask is not None:
-            mk = mask.to(device).float().contiguous()
-            if not self.native_sampler:
-                with self._eps_model_nhwc().plan().forwards_as_in_chain():
-                    for k in range(k_start, -1, -1):
-                        t_model = k if use is None else use[k]
-                        eps_hat = self.latent_model(ops.nhwc_to_nchw(x), torch.full((shape[0],), t_model, device=device, dtype=torch.long))
-                        ops.p_sample_update_restore_masked_(x, ops.nchw_to_nhwc(eps_hat.contiguous()), yl, mk, n,
-                                                            torch.full((shape[0],), k, device=device, dtype=torch.long), **tables,
-                                                            seed=seed, stream_id=int(self.rng_stream_id))
-                return ops.nhwc_to_nchw(x)
-            self._eps_model_nhwc().plan().sample_restore_masked_nhwc(x, yl, mk, n, tables, k_start, seed=seed,
-                                                                     stream_id=int(self.rng_stream_id), use_graph=self.use_graph,
-                                                                     timesteps=use)
+        plan = self._eps_model_nhwc().plan()
+        if self.native_sampler:
+            chain(plan, x, yl, mk, tables, k_start, seed, use)
             return ops.nhwc_to_nchw(x)
-        if not self.native_sampler:
-            # the loop's forwards pick their kernels as the chain's steps do (UnetPlan.forwards_as_in_chain): the two GroupNorm
-            # paths sum in another order, and a few 1e-6 of eps_hat per step is more than the loop may differ from the chain
-            with self._eps_model_nhwc().plan().forwards_as_in_chain():
-                for k in range(k_start, -1, -1):
-                    t_model = k if use is None else use[k]
-                    eps_hat = self.latent_model(ops.nhwc_to_nchw(x), torch.full((shape[0],), t_model, device=device, dtype=torch.long))
-                    ops.p_sample_update_restore_(x, ops.nchw_to_nhwc(eps_hat.contiguous()), yl, n,
-                                                 torch.full((shape[0],), k, device=device, dtype=torch.long), **tables, seed=seed,
-                                                 stream_id=int(self.rng_stream_id))
-            return ops.nhwc_to_nchw(x)
-        self._eps_model_nhwc().plan().sample_restore_nhwc(x, yl, n, tables, k_start, seed=seed, stream_id=int(self.rng_stream_id),
-                                                          use_graph=self.use_graph, timesteps=use)
+        # the loop's forwards pick their kernels as the chain's steps do (UnetPlan.forwards_as_in_chain): the two GroupNorm
+        # paths sum in another order, and a few 1e-6 of eps_hat per step is more than the loop may differ from the chain
+        with plan.forwards_as_in_chain():
+            for k in range(k_start, -1, -1):
+                t_model = k if use is None else use[k]
+                eps_hat = self.latent_model(ops.nhwc_to_nchw(x), torch.full((shape[0],), t_model, device=device, dtype=torch.long))
+                op(x, ops.nchw_to_nhwc(eps_hat.contiguous()), yl, mk, torch.full((shape[0],), k, device=device, dtype=torch.long), tables, seed)
         return ops.nhwc_to_nchw(x)
+
+    def _restore_loop(self, y, n, respacing, ddim, eta, x_T, seed, mask=None, who="super_resolve"):
+        """DDNM over the latent whose n x n block means are held at y [B, C, H/n, W/n] (UnetPlan.sample_restore_nhwc).  mask
+        [B, H/n, W/n] ({0, 1} floats, restore() only): the blocks that are held (n = 1: the pixels that are set to y), by the masked
+        op and UnetPlan.sample_restore_masked_nhwc."""
+        spaced = respacing is not None or ddim or eta != 0
+        sid, graph = int(self.rng_stream_id), self.use_graph
+        if mask is None:
+            def op(x, e, yl, mk, t, tables, seed):
+                ops.p_sample_update_restore_(x, e, yl, n, t, **tables, seed=seed, stream_id=sid)
+
+            def chain(plan, x, yl, mk, tables, k_start, seed, use):
+                plan.sample_restore_nhwc(x, yl, n, tables, k_start, seed=seed, stream_id=sid, use_graph=graph, timesteps=use)
+        else:
+            def op(x, e, yl, mk, t, tables, seed):
+                ops.p_sample_update_restore_masked_(x, e, yl, mk, n, t, **tables, seed=seed, stream_id=sid)
+
+            def chain(plan, x, yl, mk, tables, k_start, seed, use):
+                plan.sample_restore_masked_nhwc(x, yl, mk, n, tables, k_start, seed=seed, stream_id=sid, use_graph=graph, timesteps=use)
+        return self._ddnm_loop(who, y, mask, lambda: self._spaced_tables(respacing, ddim, eta) if spaced else (self._tables(), None), x_T,
+                               seed, op, chain)
 
     @torch.no_grad()
     def super_resolve(self, y, scale, *, respacing=None, ddim=False, eta=0.0, x_T=None, seed=None, **unsupported):
@@ -512,31 +519,17 @@ class DDPM(nn.Module):
 
     def _restore_solver_loop(self, y, n, respacing, solver, order, x_T, mask=None):
         """DDNM on the solver's chain over the latent whose n x n block means are held at y [B, C, H/n, W/n] where mask [B, H/n, W/n]
-        (None: everywhere) is 1: native (UnetPlan.sample_restore_multistep_nhwc) or, with native_sampler off, the same op as a Python
-        loop in the same NHWC layout."""
-        device = self.betas.device
-        if device.type != 'cuda':
-            raise DDKError("restore_solver: move the model to a ROCm device first (no CPU fallback)")
-        tables, use = self._solver_tables(respacing, solver, int(order))
-        shape = (y.shape[0], *self.sample_shape)
-        if x_T is not None and tuple(x_T.shape) != shape:
-            raise ValueError(f"restore_solver: x_T must be {shape}, got {tuple(x_T.shape)}")
-        img = torch.randn(shape, device=device) if x_T is None else x_T.to(device).float()
-        k_start = len(use) - 1
-        yl = ops.nchw_to_nhwc(y.to(device).float().contiguous())
-        mk = None if mask is None else mask.to(device).float().contiguous()
-        x = ops.nchw_to_nhwc(img.contiguous())
-        if not self.native_sampler:
-            hist = torch.zeros_like(x)
-            with self._eps_model_nhwc().plan().forwards_as_in_chain():
-                for k in range(k_start, -1, -1):
-                    eps_hat = self.latent_model(ops.nhwc_to_nchw(x), torch.full((shape[0],), use[k], device=device, dtype=torch.long))
-                    ops.p_sample_update_restore_multistep_(x, ops.nchw_to_nhwc(eps_hat.contiguous()), hist, yl, mk, n,
-                                                           torch.full((shape[0],), k, device=device, dtype=torch.long), **tables)
-            return ops.nhwc_to_nchw(x)
-        self._eps_model_nhwc().plan().sample_restore_multistep_nhwc(x, yl, mk, n, tables, k_start, stream_id=int(self.rng_stream_id),
-                                                                    use_graph=self.use_graph, timesteps=use)
-        return ops.nhwc_to_nchw(x)
+        (None: everywhere) is 1 (UnetPlan.sample_restore_multistep_nhwc).  No draws: the seed is not used."""
+        C, H, W = self.sample_shape
+        # the Python loop's history, NHWC like x: zeros before its first step
+        hist = None if self.native_sampler else torch.zeros(y.shape[0], H, W, C, device=self.betas.device)
+
+        def op(x, e, yl, mk, t, tables, seed):
+            ops.p_sample_update_restore_multistep_(x, e, hist, yl, mk, n, t, **tables)
+        return self._ddnm_loop(
+            "restore_solver", y, mask, lambda: self._solver_tables(respacing, solver, int(order)), x_T, 0, op,
+            lambda plan, x, yl, mk, tables, k_start, seed, use: plan.sample_restore_multistep_nhwc(
+                x, yl, mk, n, tables, k_start, stream_id=int(self.rng_stream_id), use_graph=self.use_graph, timesteps=use))
 
     @torch.no_grad()
     def restore_solver(self, y, mask=None, scale=1, *, respacing=None, solver="dpm++2m", order=2, x_T=None, **unsupported):
@@ -573,34 +566,13 @@ class DDPM(nn.Module):
 
     def _restore_noisy_loop(self, y, n, sigma_y, respacing, ddim, eta, x_T, seed, mask=None):
         """DDNM+ over the latent whose n x n block means are measured as y [B, C, H/n, W/n], with noise of standard deviation
-        sigma_y, where mask [B, H/n, W/n] (None: everywhere) is 1: native (UnetPlan.sample_restore_noisy_nhwc) or, with
-        native_sampler off, the same op as a Python loop in the same NHWC layout, so both draw the same Philox numbers."""
-        device = self.betas.device
-        if device.type != 'cuda':
-            raise DDKError("restore_noisy: move the model to a ROCm device first (no CPU fallback)")
-        tables, use = self._noisy_tables(respacing, ddim, eta, sigma_y)
-        shape = (y.shape[0], *self.sample_shape)
-        if x_T is not None and tuple(x_T.shape) != shape:
-            raise ValueError(f"restore_noisy: x_T must be {shape}, got {tuple(x_T.shape)}")
-        img = torch.randn(shape, device=device) if x_T is None else x_T.to(device).float()
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        k_start = (self.timesteps if use is None else len(use)) - 1
-        yl = ops.nchw_to_nhwc(y.to(device).float().contiguous())
-        mk = None if mask is None else mask.to(device).float().contiguous()
-        x = ops.nchw_to_nhwc(img.contiguous())
-        if not self.native_sampler:
-            with self._eps_model_nhwc().plan().forwards_as_in_chain():
-                for k in range(k_start, -1, -1):
-                    t_model = k if use is None else use[k]
-                    eps_hat = self.latent_model(ops.nhwc_to_nchw(x), torch.full((shape[0],), t_model, device=device, dtype=torch.long))
-                    ops.p_sample_update_restore_noisy_(x, ops.nchw_to_nhwc(eps_hat.contiguous()), yl, mk, n,
-                                                       torch.full((shape[0],), k, device=device, dtype=torch.long), **tables,
-                                                       seed=seed, stream_id=int(self.rng_stream_id))
-            return ops.nhwc_to_nchw(x)
-        self._eps_model_nhwc().plan().sample_restore_noisy_nhwc(x, yl, mk, n, tables, k_start, seed=seed, stream_id=int(self.rng_stream_id),
-                                                                use_graph=self.use_graph, timesteps=use)
-        return ops.nhwc_to_nchw(x)
+        sigma_y, where mask [B, H/n, W/n] (None: everywhere) is 1 (UnetPlan.sample_restore_noisy_nhwc)."""
+        sid = int(self.rng_stream_id)
+        return self._ddnm_loop(
+            "restore_noisy", y, mask, lambda: self._noisy_tables(respacing, ddim, eta, sigma_y), x_T, seed,
+            lambda x, e, yl, mk, t, tables, seed: ops.p_sample_update_restore_noisy_(x, e, yl, mk, n, t, **tables, seed=seed, stream_id=sid),
+            lambda plan, x, yl, mk, tables, k_start, seed, use: plan.sample_restore_noisy_nhwc(
+                x, yl, mk, n, tables, k_start, seed=seed, stream_id=sid, use_graph=self.use_graph, timesteps=use))
 
     def _restore_noisy_args(self, y, mask, scale, shape, sigma_y, ddim, eta, unsupported, scales):
         """restore's ValueErrors (_restore_masked_args, whose return value this returns), then the chain whose draws are all zero."""
@@ -673,34 +645,14 @@ class DDPM(nn.Module):
         return y[:, 0].contiguous(), m, sigma_y
 
     def _colorize_loop(self, y, mask, n, weights, sigma_y, respacing, ddim, eta, x_T, seed):
-        """The colourisation chain on y, mask [B, H/n, W/n] (mask None: everywhere): native (UnetPlan.sample_restore_gray_nhwc) or,
-        with native_sampler off, the same op as a Python loop in the same NHWC layout, so both draw the same Philox numbers."""
-        device = self.betas.device
-        if device.type != 'cuda':
-            raise DDKError("colorize: move the model to a ROCm device first (no CPU fallback)")
-        tables, use = self._gray_tables(respacing, ddim, eta, sigma_y)
-        shape = (y.shape[0], *self.sample_shape)
-        if x_T is not None and tuple(x_T.shape) != shape:
-            raise ValueError(f"colorize: x_T must be {shape}, got {tuple(x_T.shape)}")
-        img = torch.randn(shape, device=device) if x_T is None else x_T.to(device).float()
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        k_start = (self.timesteps if use is None else len(use)) - 1
-        yl = y.to(device).float().contiguous()
-        mk = None if mask is None else mask.to(device).float().contiguous()
-        x = ops.nchw_to_nhwc(img.contiguous())
-        if not self.native_sampler:
-            with self._eps_model_nhwc().plan().forwards_as_in_chain():
-                for k in range(k_start, -1, -1):
-                    t_model = k if use is None else use[k]
-                    eps_hat = self.latent_model(ops.nhwc_to_nchw(x), torch.full((shape[0],), t_model, device=device, dtype=torch.long))
-                    ops.p_sample_update_restore_gray_(x, ops.nchw_to_nhwc(eps_hat.contiguous()), yl, mk, n, weights,
-                                                      torch.full((shape[0],), k, device=device, dtype=torch.long), **tables,
-                                                      seed=seed, stream_id=int(self.rng_stream_id))
-            return ops.nhwc_to_nchw(x)
-        self._eps_model_nhwc().plan().sample_restore_gray_nhwc(x, yl, mk, n, weights, tables, k_start, seed=seed,
-                                                               stream_id=int(self.rng_stream_id), use_graph=self.use_graph, timesteps=use)
-        return ops.nhwc_to_nchw(x)
+        """The colourisation chain on y, mask [B, H/n, W/n] (mask None: everywhere) (UnetPlan.sample_restore_gray_nhwc)."""
+        sid = int(self.rng_stream_id)
+        return self._ddnm_loop(
+            "colorize", y, mask, lambda: self._gray_tables(respacing, ddim, eta, sigma_y), x_T, seed,
+            lambda x, e, yl, mk, t, tables, seed: ops.p_sample_update_restore_gray_(x, e, yl, mk, n, weights, t, **tables, seed=seed,
+                                                                                   stream_id=sid),
+            lambda plan, x, yl, mk, tables, k_start, seed, use: plan.sample_restore_gray_nhwc(
+                x, yl, mk, n, weights, tables, k_start, seed=seed, stream_id=sid, use_graph=self.use_graph, timesteps=use))
 
     @torch.no_grad()
     def colorize(self, y, mask=None, scale=1, *, weights="mean", sigma_y=0.0, respacing=None, ddim=False, eta=0.0, x_T=None, seed=None,

@@ -1,5 +1,5 @@
-"""DDNM with a mask on the GPU (DDPM.restore, DownsampleDDPM.restore, ddk_sampler_run_restore_masked, p_update_restore_kernel<true>,
-p_update_restore_point_kernel and final_tail_kernel<.., StepKind::RestoreMasked>) against tests/restore_masked_ref.py, the method
+"""DDNM with a mask on the GPU (DDPM.restore, DownsampleDDPM.restore, ddk_sampler_run_restore_masked, p_update_restore_kernel<RestoreMasked>,
+p_update_restore_point_kernel<RestoreMasked> and final_tail_kernel<.., StepKind::RestoreMasked>) against tests/restore_masked_ref.py, the method
 restated around oracle/unet_ref with oracle/philox_ref draws in NHWC order.
 
 The tiny DDPM (unet_chan 32, 3x16x16) has no Winograd final conv, so its steps end in the unfused kernels; a 128-channel UNet on
@@ -242,7 +242,7 @@ def wide():
 
 @pytest.mark.parametrize("n", [1, 2, 8])
 def test_fused_tail_equals_unfused_bit_for_bit(wide, n):
-    """ "6" steps: n = 1 and n = 2 end in final_tail_kernel<.., RestoreMasked>, n = 8 (W n = 256 > 128) in p_update_restore_kernel<true>
+    """ "6" steps: n = 1 and n = 2 end in final_tail_kernel<.., RestoreMasked>, n = 8 (W n = 256 > 128) in p_update_restore_kernel<RestoreMasked>
     whatever the option says; with DDK_OPT_RESTORE_FUSED_TAIL = 0 all end in the unfused kernels, with the same bits"""
     from ddk import ops
     m = wide

@@ -1,5 +1,5 @@
 """DDNM+ for a noisy measurement on the GPU (DDPM.restore_noisy, DownsampleDDPM.restore_noisy, ddk_sampler_run_restore_noisy,
-p_update_restore_noisy_kernel, p_update_restore_noisy_point_kernel and final_tail_kernel<.., StepKind::RestoreNoisy>) against
+p_update_restore_kernel<RestoreNoisy>, p_update_restore_point_kernel<RestoreNoisy> and final_tail_kernel<.., StepKind::RestoreNoisy>) against
 tests/restore_noisy_ref.py, the method restated around oracle/unet_ref with oracle/philox_ref draws in NHWC order.
 
 Shapes and bars are those of tests/test_restore_masked_gpu.py for the corresponding cases: the lone op bit for bit on [3, c, 16, 16] and
@@ -274,7 +274,7 @@ def wide():
 @pytest.mark.parametrize("n,masked", [(1, True), (2, True), (2, False), (8, True)], ids=["n1", "n2", "n2_nomask", "n8"])
 def test_fused_tail_equals_unfused_bit_for_bit(wide, n, masked):
     """ "6" steps, DDIM eta 0.5: n = 1 and n = 2 (with and without a mask) end in final_tail_kernel<.., RestoreNoisy>, n = 8 (W n = 256 >
-    128) in p_update_restore_noisy_kernel whatever the option says; with DDK_OPT_RESTORE_FUSED_TAIL = 0 all end in the unfused kernels,
+    128) in p_update_restore_kernel<RestoreNoisy> whatever the option says; with DDK_OPT_RESTORE_FUSED_TAIL = 0 all end in the unfused kernels,
     with the same bits.  ddk_sampler_restore_noisy_tail_parts says which tail runs."""
     from ddk import ops
     m = wide

@@ -1,5 +1,5 @@
 """DDNM on the DPM-Solver++(2M) chain on the GPU (DDPM.restore_solver, DownsampleDDPM.restore_solver,
-ddk_sampler_run_restore_multistep, p_update_restore_ms_kernel, p_update_restore_ms_point_kernel and
+ddk_sampler_run_restore_multistep, p_update_restore_kernel<RestoreMultistep>, p_update_restore_point_kernel<RestoreMultistep> and
 final_tail_kernel<.., StepKind::RestoreMultistep>) against tests/restore_solver_ref.py, the method restated around oracle/unet_ref.
 
 The shapes of tests/test_restore_masked_gpu.py: the tiny DDPM (unet_chan 32, 3x16x16, B = 2) ends its steps in the unfused kernels, the
@@ -229,7 +229,7 @@ def wide():
 
 @pytest.mark.parametrize("n", [1, 2, 8])
 def test_fused_tail_equals_unfused_bit_for_bit(wide, n):
-    """logsnr6: n = 1 and n = 2 end in final_tail_kernel<.., RestoreMultistep>, n = 8 (W n = 256 > 128) in p_update_restore_ms_kernel
+    """logsnr6: n = 1 and n = 2 end in final_tail_kernel<.., RestoreMultistep>, n = 8 (W n = 256 > 128) in p_update_restore_kernel<RestoreMultistep>
     whatever the option says; with DDK_OPT_RESTORE_FUSED_TAIL = 0 all end in the unfused kernels, with the same bits"""
     from ddk import ops
     m = wide
