@@ -38,6 +38,7 @@ int ensure_device_init() {
     DDK_TRY(conv1x1_sm_init_device());
     DDK_TRY(linattn_small_qkv_init_device());
     DDK_TRY(wgrad_init_device());
+    DDK_TRY(separable_init_device());
     done.fetch_or(bit, std::memory_order_release);
     return DDK_OK;
 }

@@ -325,6 +325,14 @@ struct InpaintOps {
 struct NoisyTables {
     const float *lam, *sgm;
 };
+// DDNM deblurring: the symmetric projections of the two axes and the two-launch form's scratch
+struct BlurOps {
+    const float* ph;              // [H][H] row-major, P_h = A_h+ A_h
+    const float* pw;              // [W][W] row-major
+    float* tmp;                   // T = P_h X0, x's layout; read and written only when an image is too large for the one-launch form
+    const float *qh, *qw;         // host side only: A+ of the two axes, from which the chain entry forms Yp = Q_h y Q_w^T before the first step
+};
+static_assert(sizeof(BlurOps) <= sizeof(InpaintOps), "BlurOps shares the Inpaint operands' storage: StepRule must not grow");
 constexpr uint32_t INPAINT_Z2_BIT = 0x40000000u;   // Philox stream of the known region's draw: stream_id | this
 constexpr uint32_t INPAINT_Z3_BIT = 0x20000000u;   // ... and of the jump's: stream_id | this (so stream_id < 2^29)
 // zero-shot super-resolution (DDNM for A = n x n average pooling): the low-resolution image and the block
@@ -370,14 +378,17 @@ enum class StepKind {
     RestoreNoisy,  // DDNM+ for a measurement with noise of standard deviation sigma_y, n in {1, 2, 4, 8}: RestoreMasked's
                   // step with the correction scaled by lam and the draw of measured elements by sgm instead of sigma (rst.mask null at
                   // n >= 2: every block measured): c_recip .. sigma, lam, sgm, rst; Philox only
-    RestoreGray   // DDNM / DDNM+ for A = mask o pool_n o grey_w on a 3-channel map, n in {1, 2, 4, 8}: RestoreNoisy's step
+    RestoreGray,  // DDNM / DDNM+ for A = mask o pool_n o grey_w on a 3-channel map, n in {1, 2, 4, 8}: RestoreNoisy's step
                   // with the block mean replaced by the weighted mean of the n x n x 3 group and the correction spread by A+'s per-channel
                   // factor (rst.gray names w; rst.mask may be null at every n): c_recip .. sigma, nsy, rst; Philox only
+    RestoreBlur   // DDNM for a separable blur A(X) = A_h X A_w^T per channel: x0' = (x0 - P_h x0 P_w^T) + Yp with the
+                  // projections P = A+ A of the two axes and Yp = A+ y, then Restore's update.  The only plane-wide kind: separable.hip's
+                  // kernels, never the fused tail: c_recip .. sigma, blr, rst.y = Yp (x's layout), rst.H, rst.W; Philox only
                   // (last, so that the kinds above keep their values and their kernels' names)
 };
 inline bool restore_kind(StepKind k) {       // the kinds whose step carries a DDNM constraint (RestoreOps)
     return k == StepKind::Restore || k == StepKind::RestoreMasked || k == StepKind::RestoreMultistep || k == StepKind::RestoreNoisy ||
-           k == StepKind::RestoreGray;
+           k == StepKind::RestoreGray || k == StepKind::RestoreBlur;
 }
 struct StepRule {
     StepKind kind;
@@ -394,6 +405,7 @@ struct StepRule {
     union {
         InpaintOps inp;
         NoisyTables nsy;          // RestoreNoisy, RestoreGray
+        BlurOps blr;              // RestoreBlur
     };
     const VlbStep* vlb;           // host side only
     RestoreOps rst;
@@ -414,10 +426,16 @@ struct ChainHooks {
     uint32_t stream_id;
 };
 // the unfused tail's last kernel, given eps_hat in memory: the rule's update of x (Ancestral, Multistep, Inpaint, Restore, RestoreMasked,
-// RestoreMultistep, RestoreNoisy, RestoreGray) or the sweep's
+// RestoreMultistep, RestoreNoisy, RestoreGray, RestoreBlur) or the sweep's
 // reduction of the step's terms (Vlb); `who` names the caller in messages
 int p_update(const StepRule& r, const float* eps_hat, const int64_t* t, int B, long long per, const ChainHooks& h, hipStream_t st,
              const char* who = "p_update");
+// separable.hip: the RestoreBlur kind's step (p_update hands it over once restore_rule_fault has passed the rule), and whether an
+// image of this shape takes the one-launch form (else the rule needs blr.tmp)
+int p_update_restore_blur(const StepRule& r, const float* eps_hat, const int64_t* t, int B, int channels, const ChainHooks& h, hipStream_t st);
+bool restore_blur_shape_ok(int H, int W, int channels);
+bool restore_blur_one_launch(int H, int W, int channels);
+int separable_init_device();
 int randn(float* out, long long n, uint64_t seed, uint32_t step, uint32_t stream_id, hipStream_t st);
 int vlb_sweep_slots_unfused(int B, long long per);
 int vlb_step_input(const VlbStep& v, const float* sqrt_acp, const float* sqrt_1m_acp, const int64_t* chain_state, int B, long long per,

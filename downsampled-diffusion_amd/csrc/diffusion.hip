@@ -8,6 +8,7 @@
 // sums use __fmul_rn/__fadd_rn in the reference's evaluation order (no FMA contraction), so given the
 // same eps_hat and noise the update is bit-identical to the torch expression.
 #include "ddk_internal.h"
+#include "diffusion_step.h"      // Philox, RestoreTraits, rst_x0, rst_finish, comp4, rst_prologue
 
 #include <climits>
 
@@ -16,36 +17,6 @@
 // file is compiled with -ffp-contract=off (see Makefile).
 
 namespace ddk {
-
-// ---- Philox4x32-10 (Salmon et al. SC'11; Random123 philox4x32_R(10)) -----------------------------
-struct U4 { uint32_t x, y, z, w; };
-
-__device__ __forceinline__ U4 philox4x32_10(U4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        if (r > 0) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-        c = U4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
-    }
-    return c;
-}
-
-__device__ __forceinline__ float u01(uint32_t r) { return ((float)(r >> 8) + 0.5f) * 5.9604644775390625e-8f; }  // 2^-24
-
-__device__ __forceinline__ float4 philox_normal4(unsigned long long idx4, uint32_t step, uint32_t stream, uint64_t seed) {
-    const U4 r = philox4x32_10(U4{(uint32_t)idx4, (uint32_t)(idx4 >> 32), step, stream}, (uint32_t)seed, (uint32_t)(seed >> 32));
-    const float two_pi = 6.283185307179586f;
-    float4 z;
-    float sn, cs;
-    float rad = sqrtf(-2.0f * logf(u01(r.x)));
-    sincosf(two_pi * u01(r.y), &sn, &cs);
-    z.x = rad * cs; z.y = rad * sn;
-    rad = sqrtf(-2.0f * logf(u01(r.z)));
-    sincosf(two_pi * u01(r.w), &sn, &cs);
-    z.z = rad * cs; z.w = rad * sn;
-    return z;
-}
 
 static int grid1d(long long n) {
     const long long b = ceil_div(n > 0 ? n : 1, 256);
@@ -200,6 +171,7 @@ __global__ __launch_bounds__(256) void p_update_kernel(const StepRule r, const f
 //   RestoreMultistep  optional  yes   -      -     pointwise
 //   RestoreNoisy      optional  -     yes    -     pointwise
 //   RestoreGray       optional  -     yes    yes   a group of three
+//   RestoreBlur       PLANE: no block at all -- A is a separable blur, x0' = (x0 - P_h x0 P_w^T) + Yp, the kernels in separable.hip
 // MASK: the block's (n = 1: the pixel's) mask value, 1 where no mask was given, selects between x0' and x0 -- a select, never a blend,
 // so whatever an unmeasured y holds (NaN included) reaches no result.  HIST: DPM-Solver++(2M)'s history term in the place of the draw,
 // the history then holding x0'.  NOISY (DDNM+): the correction scaled by the row's lam and the draw of a measured element by the row's
@@ -207,23 +179,7 @@ __global__ __launch_bounds__(256) void p_update_kernel(const StepRule r, const f
 // the element, so x0' = y where measured with no arithmetic (known pixels come back bit for bit at row 0), under NOISY x0 + lam (y - x0).
 // These functions are the arithmetic of both tails, every operation rounded on its own, so given the same eps_hat the tails are
 // bit-identical.
-template <StepKind K>
-struct RestoreTraits {
-    static constexpr bool RESTORE = K == StepKind::Restore || K == StepKind::RestoreMasked || K == StepKind::RestoreMultistep ||
-                                    K == StepKind::RestoreNoisy || K == StepKind::RestoreGray;
-    static constexpr bool MASK = RESTORE && K != StepKind::Restore;
-    static constexpr bool MASK_REQUIRED = K == StepKind::RestoreMasked;
-    static constexpr bool HIST = K == StepKind::RestoreMultistep;
-    static constexpr bool NOISY = K == StepKind::RestoreNoisy || K == StepKind::RestoreGray;
-    static constexpr bool GRAY = K == StepKind::RestoreGray;
-    static constexpr bool POINT = MASK && !GRAY;      // n = 1 is pointwise
-};
-
-__device__ __forceinline__ float rst_x0(float x, float e, float cr, float crm1) {
-    const float x0 = __fsub_rn(__fmul_rn(cr, x), __fmul_rn(crm1, e));     // as p_step
-    return fminf(fmaxf(x0, -1.0f), 1.0f);
-}
-
+// (RestoreTraits, rst_x0, rst_finish, comp4, rst_prologue and the Philox draws live in diffusion_step.h, shared with separable.hip.)
 // x0_at(i, j): the clipped x0 at row i, column j of the element's block (same image, same channel)
 template <class F>
 __device__ __forceinline__ float rst_block_mean(F&& x0_at, int n) {
@@ -248,18 +204,6 @@ __device__ __forceinline__ float rst_x0p(float x0, float m, float y, float mk, f
     return x0p;
 }
 
-// zh: the draw, or (HIST) the history, which leaves holding x0'; a5: sigma, or (HIST) c3; sgm: NOISY
-template <StepKind K>
-__device__ __forceinline__ float rst_finish(float x, float x0p, float mk, float& zh, float c1, float c2, float a5, float sgm) {
-    using T = RestoreTraits<K>;
-    const float mean = __fadd_rn(__fmul_rn(c1, x0p), __fmul_rn(c2, x));
-    float sc = a5;
-    if constexpr (T::NOISY) sc = mk != 0.0f ? sgm : a5;
-    const float out = __fadd_rn(mean, __fmul_rn(sc, zh));
-    if constexpr (T::HIST) zh = x0p;
-    return out;
-}
-
 // the pointwise step (n = 1) of one element
 template <StepKind K>
 __device__ __forceinline__ float rst_point(float x, float e, float y, float mk, float& zh, float cr, float crm1, float c1, float c2, float a5,
@@ -276,17 +220,6 @@ __device__ __forceinline__ float4 rstm_mask4(const float* __restrict__ mk, unsig
         return make_float4(m, m, m, m);
     }
     return make_float4(mk[e0 / C], mk[(e0 + 1u) / C], mk[(e0 + 2u) / C], mk[(e0 + 3u) / C]);
-}
-
-__device__ __forceinline__ float comp4(float4 v, int k) { return k == 0 ? v.x : k == 1 ? v.y : k == 2 ? v.z : v.w; }
-
-// what the unfused restore kernels begin with: the counter decrement and the chain's Philox key, as in p_update_kernel
-__device__ __forceinline__ void rst_prologue(int64_t* dec_counter, const int64_t* __restrict__ chain_state, uint64_t& seed, uint32_t& stream) {
-    if (dec_counter && blockIdx.x == 0 && threadIdx.x == 0) *dec_counter -= 1;
-    if (chain_state) {
-        seed = (uint64_t)chain_state[1];
-        stream = (uint32_t)chain_state[2];
-    }
 }
 
 // the row's coefficients of a restore step: c_recip, c_recipm1, c1, c2, the fifth (sigma with its t > 0 mask, or HIST: c3), NOISY: lam, sgm
@@ -796,6 +729,16 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
 // other pointwise kinds need one at n = 1 only (nothing would be constrained), where y is read as float4s.
 static const char* restore_rule_fault(const StepRule& r, long long per) {
     const RestoreOps& o = r.rst;
+    if (r.kind == StepKind::RestoreBlur) {       // plane-wide: no block; rst.y is Yp in x's layout, the projections and the scratch in blr
+        if (!(o.y && r.sigma && r.blr.ph && r.blr.pw)) return "null pointer";
+        if (r.noise) return "no injected noise (Philox only)";
+        if (!(o.H > 0 && o.W > 0) || per % ((long long)o.H * o.W)) return "per must be H * W * channels";
+        const long long ch = per / ((long long)o.H * o.W);
+        if (ch > 8 || !restore_blur_shape_ok(o.H, o.W, (int)ch)) return "the blur step needs H and W multiples of 16 in [16, 256] and 1 to 8 channels";
+        if (!restore_blur_one_launch(o.H, o.W, (int)ch) && !r.blr.tmp) return "an image above 64 KB needs the scratch for T";
+        if (!(aligned16(o.y) && aligned16(r.blr.ph) && aligned16(r.blr.pw) && aligned16(r.blr.tmp))) return "alignment";
+        return nullptr;
+    }
     const bool hist = r.kind == StepKind::RestoreMultistep, gray = r.kind == StepKind::RestoreGray,
                noisy = gray || r.kind == StepKind::RestoreNoisy, n1 = r.kind != StepKind::Restore;
     if (!(o.y && (hist ? r.c3 && r.x0_hist : r.sigma != nullptr) && (!noisy || (r.nsy.lam && r.nsy.sgm)) &&
@@ -831,6 +774,7 @@ bool final_tail_ok(int HW, int C, int groups, int n_out, int np, StepKind kind, 
     if (C > 128 && kind != StepKind::Eps && kind != StepKind::Ancestral) return false;
     if (groups <= 0 || groups > 64 || C % groups || (C / groups) % 4) return false;
     if (n_out < 1 || n_out > 8 || (128 * n_out) % 4) return false;
+    if (kind == StepKind::RestoreBlur) return false;                     // plane-wide: a 128-pixel tile cannot form P_h x0 P_w^T
     if (kind == StepKind::RestoreGray && n_out != 3) return false;       // the grey operator is over a pixel's three colours
     // the restore tail forms block means from the tile's x0 in LDS: the 128-pixel tile must hold whole rows of n x n blocks
     // (the masked kind the same for n >= 2; its n = 1 is pointwise)
@@ -891,6 +835,8 @@ int final_tail(const TailIn& in, const StepRule& r, const int64_t* t, const Chai
             return launch_tail<StepKind::RestoreNoisy>(p, in.B, st);
         case StepKind::RestoreGray:
             return launch_tail<StepKind::RestoreGray>(p, in.B, st);
+        case StepKind::RestoreBlur:
+            return fail_arg("final_tail: the blur step has no fused tail (final_tail_ok)");
         case StepKind::Vlb: {
             DDK_REQUIRE(r.vlb && tables && !r.eps_out && h.chain_state, "final_tail: the VLB epilogue needs the sweep's step, x, t, the tables and the chain state");
             const VlbStep& v = *r.vlb;
@@ -1148,6 +1094,9 @@ int p_update(const StepRule& r, const float* eps_hat, const int64_t* t, int B, l
             return launch_restore<StepKind::RestoreNoisy>(r, eps_hat, t, B, per, h, st);
         case StepKind::RestoreGray:
             return launch_restore<StepKind::RestoreGray>(r, eps_hat, t, B, per, h, st);
+        case StepKind::RestoreBlur:       // separable.hip: one launch, or two through blr.tmp
+            if (B > 65535) return bad("at most 65535 images");
+            return p_update_restore_blur(r, eps_hat, t, B, (int)(per / ((long long)r.rst.H * r.rst.W)), h, st);
         case StepKind::Vlb:       // no update: the sweep's reduction of the step's terms, a kernel of its own
             if (!r.vlb) return bad("null pointer");
             return vlb_sweep_terms(*r.vlb, t, eps_hat, B, per, h.chain_state, st, h.dec_counter);

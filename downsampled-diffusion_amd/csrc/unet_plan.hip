@@ -1753,8 +1753,18 @@ static RestoreStage restore_stage(size_t n, int B, int H, int W, StepKind kind, 
     const size_t nn = (size_t)restore_n * restore_n;
     return {kind == StepKind::RestoreMultistep ? al4(n) : 0, al4(n / nn), al4((size_t)B * H * W / nn)};
 }
+// RestoreBlur (plane-wide, no block): P_h [H][H], P_w [W][W], Yp and T, the last two of the latent's size; each part is a multiple of
+// four floats, so each starts on a 16-byte boundary.  Q_h and Q_w are only read while Yp is formed, from the caller's buffers.
+struct BlurStage {
+    size_t ph, pw, yp, tmp;       // offsets in floats from the chain's extra area; total = tmp + al4(n)
+};
+static BlurStage blur_stage(size_t n, int H, int W) {
+    const size_t ph = 0, pw = ph + al4((size_t)H * H), yp = pw + al4((size_t)W * W);
+    return {ph, pw, yp, yp + al4(n)};
+}
 static size_t chain_extra_floats(const ddk_unet& u, int B, int H, int W, StepKind kind, int restore_n = 0) {
     const size_t n = al4((size_t)B * H * W * u.cfg.in_ch);
+    if (kind == StepKind::RestoreBlur) return blur_stage(n, H, W).tmp + al4(n);
     if (kind == StepKind::Restore) return al4(n / 4);
     if (restore_kind(kind)) {
         const RestoreStage g = restore_stage(n, B, H, W, kind, restore_n);
@@ -1795,6 +1805,15 @@ static int sampler_chain(const ddk_sampler_args* a, const char* who, const int64
         DDK_HIP(hipMemcpyAsync(extra + al4(n), rule.inp.mask, n * sizeof(float), hipMemcpyDeviceToDevice, c.st));
         rule.inp.known = extra;
         rule.inp.mask = extra + al4(n);
+    } else if (rule.kind == StepKind::RestoreBlur) {
+        // the projections copied in and Yp = Q_h y Q_w^T formed here, before the first step and outside any captured one: rule.rst.y is
+        // the CALLER's y, rule.blr holds the caller's matrices
+        const BlurStage g = blur_stage(al4(n), H, W);
+        DDK_HIP(hipMemcpyAsync(extra + g.ph, rule.blr.ph, (size_t)H * H * sizeof(float), hipMemcpyDeviceToDevice, c.st));
+        DDK_HIP(hipMemcpyAsync(extra + g.pw, rule.blr.pw, (size_t)W * W * sizeof(float), hipMemcpyDeviceToDevice, c.st));
+        DDK_TRY(ddk_separable_apply(rule.rst.y, rule.blr.qh, rule.blr.qw, extra + g.yp, B, H, W, c.u->cfg.in_ch, s));
+        rule.blr = BlurOps{extra + g.ph, extra + g.pw, extra + g.tmp, nullptr, nullptr};
+        rule.rst = RestoreOps{extra + g.yp, 0, H, W, 0, nullptr};
     } else if (restore_kind(rule.kind)) {
         const RestoreStage g = restore_stage(n, B, H, W, rule.kind, rule.rst.n);
         const size_t nn = (size_t)rule.rst.n * rule.rst.n, nm = (size_t)B * H * W / nn;      // one float per block: the mask, and the grey y
@@ -1819,12 +1838,12 @@ static int sampler_chain(const ddk_sampler_args* a, const char* who, const int64
 
     // the RestoreNoisy / RestoreGray tables share the Inpaint operands' storage (StepRule): each kind's key names its own
     const bool noisy = rule.kind == StepKind::RestoreNoisy || rule.kind == StepKind::RestoreGray;
-    const InpaintOps ik = noisy ? InpaintOps{} : rule.inp;
+    const InpaintOps ik = noisy || rule.kind == StepKind::RestoreBlur ? InpaintOps{} : rule.inp;      // (the blur operands are staged: the workspace names them)
     const NoisyTables nk = noisy ? rule.nsy : NoisyTables{};
     const ChainKey key{rule.kind,
                        {a->packed, a->x, rule.c_recip, rule.c_recipm1, rule.c1, rule.c2, rule.sigma, rule.c3, ik.ka, ik.kb, ik.ja, ik.jb, nk.lam,
                         nk.sgm},
-                       a->workspace, a->noise, B, H, W, a->t_start, c.dev, c.u->pack_epoch, restore_kind(rule.kind) ? rule.rst.n : 0,
+                       a->workspace, a->noise, B, H, W, a->t_start, c.dev, c.u->pack_epoch, restore_kind(rule.kind) ? rule.rst.n : 0,      // RestoreBlur: 0, the kind says it
                        (rule.kind == StepKind::RestoreMultistep || noisy) && rule.rst.mask != nullptr,
                        rule.kind == StepKind::RestoreGray ? rule.rst.gray : 0};
     return run_chain(*c.u, key, n_steps, a->use_graph != 0, one_step, c.st, who);
@@ -2016,6 +2035,39 @@ extern "C" int ddk_sampler_run_restore_noisy(const ddk_sampler_args* a, const in
 extern "C" int ddk_sampler_run_restore_gray(const ddk_sampler_args* a, const int64_t* timestep_map, const float* lam, const float* sgm,
                                             const float* y, const float* mask, int n, int weights, ddk_stream_t s) {
     return restore_chain(a, "sampler_restore_gray", timestep_map, StepKind::RestoreGray, true, false, nullptr, {lam, sgm}, y, mask, n, weights, s);
+}
+
+// DDNM deblurring, A(X) = A_h X A_w^T per channel of a pixel-space model (section 3.14): the spaced sampler's chain, every step ending in
+// StepKind::RestoreBlur.  P = A+ A and Q = A+ of the two axes are the caller's (models/diffusion/blur.py), row-major [H][H] and [W][W]
+// device arrays; y is the blurred image in x's layout.  The kind is plane-wide, so no step takes the fused tail: the forward writes
+// eps_hat to the step's scratch and separable.hip's update follows.
+extern "C" size_t ddk_sampler_restore_blur_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start) {
+    if (check_shape(u, B, H, W) != DDK_OK || !restore_blur_shape_ok(H, W, u->cfg.in_ch)) return 0;
+    return sampler_bytes(u, B, H, W, t_start, StepKind::RestoreBlur);
+}
+extern "C" int ddk_sampler_restore_blur_tail_parts(const ddk_unet* u, int B, int H, int W) {
+    if (check_shape(u, B, H, W) != DDK_OK) return -1;
+    return fused_tail_parts(*u, B, H, W, u->dimp[1], StepKind::RestoreBlur);      // 0: final_tail_ok takes no plane-wide kind
+}
+extern "C" int ddk_sampler_run_restore_blur(const ddk_sampler_args* a, const int64_t* timestep_map, const float* P_h, const float* P_w,
+                                            const float* Q_h, const float* Q_w, const float* y, ddk_stream_t s) {
+    const char* who = "sampler_restore_blur";
+    auto bad = [who](const char* what) {
+        set_error("bad argument: %s: %s", who, what);
+        return DDK_ERR_ARG;
+    };
+    if (!(a && a->unet && a->packed && a->x && a->workspace && y && P_h && P_w && Q_h && Q_w)) return bad("null pointer");
+    if (!(a->c_recip && a->c_recipm1 && a->c1 && a->c2 && a->sigma)) return bad("null schedule table");
+    if (a->noise) return bad("injected noise is not supported, noise must be NULL (Philox only)");
+    if (!(a->t_start >= a->t_end && a->t_end >= 0)) return bad("need t_start >= t_end >= 0");
+    if (!restore_blur_shape_ok(a->H, a->W, a->unet->cfg.in_ch)) return bad("H and W must be multiples of 16 in [16, 256], the model's channels 1 to 8");
+    if (!(aligned16(P_h) && aligned16(P_w) && aligned16(Q_h) && aligned16(Q_w) && aligned16(y))) return bad("alignment");
+    DDK_TRY(check_timestep_map(timestep_map, a->t_start, who));
+    StepRule rule{};
+    rule.kind = StepKind::RestoreBlur;
+    rule.blr = BlurOps{P_h, P_w, nullptr, Q_h, Q_w};
+    rule.rst.y = y;
+    return sampler_chain(a, who, timestep_map, rule, s);
 }
 
 // ------------------------------------------------------------------------------------------------ likelihood sweep

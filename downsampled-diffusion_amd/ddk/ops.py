@@ -842,6 +842,45 @@ def p_sample_update_restore_gray_(x, eps_hat, y, mask, n, weights, t, c_recip, c
     return x
 
 
+def separable_apply(x, L_mat, R_mat, out=None):
+    """out[b,:,:,c] = L_mat . x[b,:,:,c] . R_mat^T for every image and channel of x [B,H,W,C] (NHWC): L_mat [H,H], R_mat [W,W] fp32
+    (DESIGN.md section 3.14).  With (A_h, A_w) of models/diffusion/blur.py it blurs, with (Q_h, Q_w) it forms A+ y.  H and W multiples
+    of 16 in [16, 256], C in 1..8.  out may be x."""
+    b, h, w, c = x.shape
+    if tuple(L_mat.shape) != (h, h) or tuple(R_mat.shape) != (w, w):
+        raise L.DDKError(f"separable_apply: x {tuple(x.shape)} needs L [{h},{h}] and R [{w},{w}], got {tuple(L_mat.shape)} and {tuple(R_mat.shape)}")
+    if out is None:
+        out = torch.empty_like(x)
+    elif tuple(out.shape) != tuple(x.shape):
+        raise L.DDKError(f"separable_apply: out {tuple(out.shape)} must have x's shape {tuple(x.shape)}")
+    L.check(L.load().ddk_separable_apply(L.ptr(_f32(x)), L.ptr(_f32(L_mat)), L.ptr(_f32(R_mat)), L.ptr(_f32(out)), b, h, w, c, L.stream()),
+            "separable_apply")
+    return out
+
+
+def p_sample_update_restore_blur_(x, eps_hat, P_h, P_w, Yp, t, c_recip, c_recipm1, c1, c2, sigma, seed=0, stream_id=0, scratch=None):
+    """In-place DDNM deblurring step of x [B,H,W,C] (NHWC) per sample row t[b]: the clipped x0 loses its
+    range-space part and gains the measurement's, x0' = (x0 - P_h x0 P_w^T) + Yp per channel, then the ancestral update with Philox
+    draws runs on it.  P_h [H,H], P_w [W,W]: the projections A+ A of the two axes; Yp = A+ y in x's layout.  An image above 64 KB takes
+    two launches through `scratch` (x's shape; allocated here when None)."""
+    b, h, w, c = x.shape
+    if tuple(eps_hat.shape) != tuple(x.shape) or Yp is None or tuple(Yp.shape) != tuple(x.shape) or \
+            (scratch is not None and tuple(scratch.shape) != tuple(x.shape)):
+        raise L.DDKError(f"p_sample_update_restore_blur: x {tuple(x.shape)}, eps_hat {tuple(eps_hat.shape)}, "
+                         f"Yp {None if Yp is None else tuple(Yp.shape)}, scratch {None if scratch is None else tuple(scratch.shape)}")
+    for what, m, side in (("P_h", P_h, h), ("P_w", P_w, w)):
+        if m is not None and tuple(m.shape) != (side, side):
+            raise L.DDKError(f"p_sample_update_restore_blur: {what} must be [{side},{side}], got {tuple(m.shape)}")
+    if scratch is None and h * w * c * 4 > 65536:
+        scratch = torch.empty_like(x)
+    mats = [L.ptr(None if m is None else _f32(m)) for m in (P_h, P_w)]
+    L.check(L.load().ddk_p_sample_update_restore_blur(L.ptr(_f32(x)), L.ptr(_f32(eps_hat)), *mats, L.ptr(_f32(Yp)),
+                                                      L.ptr(None if scratch is None else _f32(scratch)), L.ptr(t), L.ptr(c_recip),
+                                                      L.ptr(c_recipm1), L.ptr(c1), L.ptr(c2), L.ptr(sigma), b, h, w, c, seed, stream_id,
+                                                      L.stream()), "p_sample_update_restore_blur")
+    return x
+
+
 def randn(shape, device, seed, step, stream_id=0):
     out = torch.empty(shape, device=device, dtype=torch.float32)
     L.check(L.load().ddk_randn(L.ptr(out), out.numel(), seed, step, stream_id, L.stream()), "randn")

@@ -29,7 +29,8 @@ SAMPLERS = {"smp": ("sample", "sampler", "sampler"), "sms": ("sample_multistep",
             "srm": ("sample_restore_masked", "sampler_restore_masked", "masked restoration sampler"),
             "srx": ("sample_restore_multistep", "sampler_restore_multistep", "restoration solver"),
             "srn": ("sample_restore_noisy", "sampler_restore_noisy", "noisy restoration sampler"),
-            "srg": ("sample_restore_gray", "sampler_restore_gray", "colourisation sampler")}
+            "srg": ("sample_restore_gray", "sampler_restore_gray", "colourisation sampler"),
+            "srb": ("sample_restore_blur", "sampler_restore_blur", "deblurring sampler")}
 # workspace kinds whose captured step graphs point into them (the samplers', the likelihood sweep's): UnetPlan._workspace keeps up
 # to 3 of each
 CHAIN_WORKSPACES = (*SAMPLERS, "vsw")
@@ -357,17 +358,19 @@ class UnetPlan:
         "srx": ("sampler_run_restore_multistep", "sampler_restore_multistep_workspace_bytes",
                 "sampler_restore_multistep_tail_parts"),
         "srn": ("sampler_run_restore_noisy", "sampler_restore_noisy_workspace_bytes", "sampler_restore_noisy_tail_parts"),
-        "srg": ("sampler_run_restore_gray", "sampler_restore_gray_workspace_bytes", "sampler_restore_gray_tail_parts")}
+        "srg": ("sampler_run_restore_gray", "sampler_restore_gray_workspace_bytes", "sampler_restore_gray_tail_parts"),
+        "srb": ("sampler_run_restore_blur", "sampler_restore_blur_workspace_bytes", "sampler_restore_blur_tail_parts")}
 
     def _restore_tail_parts(self, kind, b, h, w, n):
-        return int(getattr(self._lib, "ddk_" + self.RESTORE_ENTRIES[kind][2])(self.handle, b, h, w, int(n)))
+        return int(getattr(self._lib, "ddk_" + self.RESTORE_ENTRIES[kind][2])(self.handle, b, h, w, *(() if n is None else (int(n),))))
 
     def _sample_restore(self, kind, x, y, mask, n, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, head=(), masked=True,
-                        weights=None):
+                        weights=None, blur=None):
         """What the restoration samplers share: the checks on n, y, mask and the lam / sgm tables, then the chain.
         kind: the entry's key in SAMPLERS and RESTORE_ENTRIES; head: the names of the tables the C entry takes before y; masked: the
         entry takes a mask and n = 1 (which then needs one), and its workspace query takes n; weights: the grey entry's, whose y is
-        [B,H/n,W/n] and whose n = 1 needs no mask."""
+        [B,H/n,W/n] and whose n = 1 needs no mask; blur: the deblurring entry's matrices (P_h, P_w, Q_h, Q_w), whose operator has no
+        block (n is None, no mask) and whose y has x's shape."""
         self._need_packed(kind)
         name = SAMPLERS[kind][0]
         gray = weights is not None
@@ -376,9 +379,16 @@ class UnetPlan:
             raise L.DDKError(f"{name}: the grey operator needs a 3-channel map, got {c} channels")
         if gray and weights not in L.GRAY_WEIGHTS:
             raise L.DDKError(f"{name}: weights must be 'mean' or 'luma', got {weights!r}")
-        if n not in ((1, 2, 4, 8) if masked else (2, 4, 8)) or h % n or w % n:
+        if blur is not None:
+            if not (h % 16 == 0 and w % 16 == 0 and 16 <= h <= 256 and 16 <= w <= 256 and 1 <= c <= 8):
+                raise L.DDKError(f"{name}: H and W must be multiples of 16 in [16, 256] and the channels 1 to 8, got [{h},{w},{c}]")
+            for what, v, side in zip(("P_h", "P_w", "Q_h", "Q_w"), blur, (h, w, h, w)):
+                if v is None or tuple(v.shape) != (side, side) or v.dtype != torch.float32 or not v.is_contiguous() or v.device != x.device:
+                    raise L.DDKError(f"{name}: {what} must be a contiguous fp32 [{side},{side}] tensor on x's device")
+            n = 1                 # y has x's shape
+        elif n not in ((1, 2, 4, 8) if masked else (2, 4, 8)) or h % n or w % n:
             raise L.DDKError(f"{name}: n must be {'1, ' if masked else ''}2, 4 or 8 and divide H = {h} and W = {w}, got {n}")
-        if mask is None and n == 1 and not gray:
+        if mask is None and n == 1 and not gray and blur is None:
             raise L.DDKError(f"{name}: n = 1 needs a mask (nothing would be constrained)")
         for what, v, shape in (("y", y, (b, h // n, w // n) if gray else (b, h // n, w // n, c)), ("mask", mask, (b, h // n, w // n))):
             if v is not None and (tuple(v.shape) != shape or v.dtype != torch.float32 or not v.is_contiguous()):
@@ -390,6 +400,8 @@ class UnetPlan:
         run, workspace_bytes = (getattr(self._lib, "ddk_" + f) for f in self.RESTORE_ENTRIES[kind][:2])
         tmap = self._timestep_map(timesteps, t_start)
         operands = (L.ptr(y), L.ptr(mask), int(n)) if masked else (L.ptr(y), int(n))
+        if blur is not None:
+            operands = (*(L.ptr(m) for m in blur), L.ptr(y))
         if gray:
             operands += (L.GRAY_WEIGHTS[weights],)
 
@@ -468,6 +480,23 @@ class UnetPlan:
         (respace.gray_tables); the tables, n, the mask's presence and the weights are in the graph key.  Philox only."""
         return self._sample_restore("srg", x, y, mask, n, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, head=("lam", "sgm"),
                                     weights=weights)
+
+    def restore_blur_tail_parts(self, b, h, w):
+        """Tiles per image of the fused tail of a deblurring step on [b, h, w]: 0 for every shape (the operator couples a whole
+        plane, the tail owns 128-pixel tiles), -1 for a shape the plan does not take."""
+        return self._restore_tail_parts("srb", b, h, w, None)
+
+    def sample_restore_blur_nhwc(self, x, y, P_h, P_w, Q_h, Q_w, tables, t_start, t_end=0, seed=0, stream_id=0, use_graph=True,
+                                 timesteps=None):
+        """DDNM deblurring steps for a separable blur A(X) = A_h X A_w^T, t_start .. t_end (inclusive), in place on x [B,H,W,in_ch]
+        (ddk_sampler_run_restore_blur).
+
+        y: the blurred image, contiguous fp32 [B,H,W,in_ch]; P_h, Q_h [H,H] and P_w, Q_w [W,W]: the fp32 projections and truncated
+        pseudo-inverses of the two axes (models/diffusion/blur.py blur_operands).  P_h and P_w are copied into the plan's "srb"
+        workspace and Yp = Q_h y Q_w^T is formed there by every call, so a loop over images replays one cached graph.  H and W
+        multiples of 16 in [16, 256].  tables / timesteps: as for sample_nhwc (plain, respaced or DDIM).  Philox only."""
+        return self._sample_restore("srb", x, y, None, None, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, masked=False,
+                                    blur=(P_h, P_w, Q_h, Q_w))
 
     # ---------------------------------------------------------------- likelihood sweep
     VLB_STREAM_BIT = 1 << 31     # the sweep's Philox stream id is stream_id | this (csrc/ddk_internal.h VLB_STREAM_BIT)

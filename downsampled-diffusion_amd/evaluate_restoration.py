@@ -26,6 +26,10 @@ through utils/data.py; ``--max_batches`` keeps the first max_batches * batch_siz
     restores it with ``--timestep_respacing``, ``--use_ddim``, ``--eta`` and ``--sigma_y``.  Baselines: the grey image copied into
     the three channels, replicated or bicubic-upsampled at ``--scale`` > 1.  The consistency is max |A(x_out) - y| in uint8 levels
     (with ``--sigma_y``: the RMS against the clean y); ``method`` reads ``ddnm_gray`` and the settings gain ``weights``.
+  * ``--task deblur --kernel K`` (DDPM checkpoints; section 3.14): the images are blurred with the separable kernel K (``uniform``,
+    ``gauss`` or ``aniso``; zero padding; the task has no default kernel) and ``model.deblur`` restores them with ``--tol``, ``--timestep_respacing``, ``--use_ddim`` and
+    ``--eta``.  Baselines: the blurred image itself and A+ y clipped to [-1, 1].  The consistency is max |A(x_out) - y| in uint8
+    levels; ``method`` reads ``ddnm_blur`` and the settings gain ``kernel`` and ``tol``.
   * batch g draws x_T and its Philox key from ``--seed`` + g.
 
 Prints one JSON object, the settings that produced it (among them ``method`` and ``unet_forwards``, the UNet forwards per image, so
@@ -40,7 +44,7 @@ import time
 import numpy as np
 import torch
 
-from utils.restoration_metrics import GRAY_WEIGHTS, MASKS, METHODS, TASKS, evaluate_restoration, load_mask, report, to_u8
+from utils.restoration_metrics import BLUR_KERNELS, DEBLUR_TASK, GRAY_WEIGHTS, MASKS, METHODS, TASKS, evaluate_restoration, load_mask, report, to_u8
 
 
 def parse_args(argv=None):
@@ -48,12 +52,14 @@ def parse_args(argv=None):
     ap.add_argument("--saved_model", default="celeba_x2")
     ap.add_argument("--synthetic", default=None, help="JSON config file: use closed-form synthetic weights, no checkpoint")
     ap.add_argument("--images", default=None, help="uint8 [N, H, W, C] .npy of the model's size (default: the dataset's test split)")
-    ap.add_argument("--task", required=True, choices=TASKS)
+    ap.add_argument("--task", required=True, choices=(*TASKS, DEBLUR_TASK))
     ap.add_argument("--mask", default=None, help=f"one of {', '.join(MASKS)} or a .npy file of {{0, 1}} (1 = known); inpaint: default "
                                                  "center; sr: masked super-resolution, the mask is of the pooled image (default: none)")
     ap.add_argument("--method", default=None, choices=METHODS, help="inpaint: repaint (default) or ddnm; sr: ddnm")
     ap.add_argument("--scale", type=int, default=None, help="sr: the pooling factor (default 4); colorize: default 1")
     ap.add_argument("--weights", default=None, choices=tuple(GRAY_WEIGHTS), help="colorize: the grey image's channel weights (default mean)")
+    ap.add_argument("--kernel", default=None, choices=BLUR_KERNELS, help="deblur: the separable blur (required there)")
+    ap.add_argument("--tol", type=float, default=None, help="deblur: singular values below tol * s_max are dropped, per axis (default 0.03)")
     ap.add_argument("--timestep_respacing", default="", help='run K of the T steps: "N", "n1,n2,..." sections or (sr) "ddimN"')
     ap.add_argument("--use_ddim", action="store_true", help="sr: DDIM steps instead of ancestral ones")
     ap.add_argument("--eta", type=float, default=0.0, help="sr: DDIM noise scale (0: deterministic)")
@@ -74,7 +80,18 @@ def parse_args(argv=None):
         args.method = "repaint" if args.task == "inpaint" else "ddnm"
     if args.weights is not None and args.task != "colorize":
         ap.error("--weights belongs to --task colorize")
-    if args.task == "sr":
+    if (args.kernel is not None or args.tol is not None) and args.task != DEBLUR_TASK:
+        ap.error("--kernel and --tol belong to --task deblur")
+    if args.task == DEBLUR_TASK:
+        if args.kernel is None:
+            ap.error("--task deblur needs --kernel: the blur is part of the task, there is no default")
+        if args.tol is None:
+            args.tol = 3e-2
+        if not (0 <= args.tol < 1):
+            ap.error("--tol must be in [0, 1)")
+        if args.method != "ddnm" or args.dpm_solver or args.sigma_y != 0.0 or args.mask is not None or args.scale is not None:
+            ap.error("--task deblur has one method, ddnm on ancestral or DDIM steps, and takes no --mask, --scale or --sigma_y")
+    elif args.task == "sr":
         if args.scale is None:
             args.scale = 4
         if args.method != "ddnm":
@@ -123,6 +140,8 @@ def chain_options(args):
         kw.update(scale=args.scale)
     if args.task == "colorize":
         kw.update(weights=args.weights)
+    if args.task == DEBLUR_TASK:
+        kw.update(kernel=args.kernel, tol=args.tol)
     if args.dpm_solver:
         kw.update(dpm_solver=True)
     elif args.method == "ddnm":
@@ -193,7 +212,7 @@ def main():
     kw = chain_options(args)
     if args.task == "inpaint":
         kw["mask"] = args.mask if args.mask in MASKS else load_mask(args.mask, n, h, w, channels)
-    elif args.mask is not None:
+    elif args.mask is not None and args.task != DEBLUR_TASK:
         kw["sr_mask"] = args.mask if args.mask in MASKS else load_mask(args.mask, n, h // args.scale, w // args.scale, 1)
 
     print(f"Scoring {args.task} on {n} images with {'synthetic weights' if args.synthetic else args.saved_model}.")

@@ -197,6 +197,12 @@ class DownsampleDDPM(DDPM):
         raise ValueError("colorize: a DownsampleDDPM samples in a latent whose channels are not colours; colourisation needs a "
                          "3-channel pixel model (DDPM)")
 
+    def deblur(self, y, kernel="gauss", **kwargs):
+        """Not available: the chain runs in the autoencoder's latent, and a blur of the latent is not a blur of the image, so the
+        operator of DDPM.deblur has no separable form there.  A stated limitation, not an approximation: always ValueError."""
+        raise ValueError("deblur: a DownsampleDDPM samples in a latent, and a blur of the latent is not a blur of the image; deblurring "
+                         "needs a pixel model (DDPM)")
+
     @torch.no_grad()
     def reconstruct(self, x, n):
         """dddpm.py:33-74 (visualisation only)."""

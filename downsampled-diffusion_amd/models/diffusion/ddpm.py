@@ -18,7 +18,7 @@ from ddk import ops
 from ddk.lib import DDKError
 from utils import flat_bits, reduce_mean, reduce_sum
 from models.utils import discretized_gaussian_log_likelihood, extract, l2_loss, noise_like, normal_kl
-from . import respace
+from . import blur, respace
 from .beta_schedule import make_beta_schedule
 
 OBJETIVE_NAMES = ['simple', 'hybrid', 'vlb']
@@ -668,6 +668,64 @@ class DDPM(nn.Module):
         non-finite measured pixels and every mask restore rejects."""
         y, m, sigma_y = self._colorize_args(y, mask, scale, weights, sigma_y, ddim, eta, unsupported)
         return self._colorize_loop(y, m, int(scale), weights, sigma_y, respacing, ddim, eta, x_T, seed)
+
+    # ------------------------------------------------------------------ DDNM deblurring (separable blur)
+    DEBLUR_UNSUPPORTED = ('solver', 'noise', 'early_stop', 'paste', 'mask', 'sigma_y')
+
+    def _blur_operands(self, kernel, tol):
+        """{A_h, A_w, Q_h, Q_w, P_h, P_w} of blur.blur_operands on the model's device, cached per (taps, tol, device) like the spaced
+        tables: repeated calls pass the same tensors."""
+        C, H, W = self.sample_shape
+        names = ("A_h", "A_w", "Q_h", "Q_w", "P_h", "P_w")
+        return self._cached_tables(('blur', *blur._key(kernel), float(tol)),
+                                   lambda: (dict(zip(names, blur.blur_operands(kernel, H, W, tol))), None))[0]
+
+    def _deblur_args(self, y, kernel, tol, ddim, eta, unsupported):
+        """ValueError for anything deblur cannot take, before any device work.  Returns y as float."""
+        if unsupported:
+            raise ValueError(f"deblur: {sorted(unsupported)} not accepted (DDNM runs ancestral or DDIM steps with Philox draws over the "
+                             f"whole schedule on an exact, unmasked measurement: no {', '.join(self.DEBLUR_UNSUPPORTED)})")
+        blur.blur_kernel(kernel)      # its own ValueErrors
+        if isinstance(tol, bool) or not isinstance(tol, (int, float, np.integer, np.floating)) or not (0 <= tol < 1):
+            raise ValueError(f"deblur: tol must be a real number in [0, 1), got {tol!r}")
+        if isinstance(eta, bool) or not isinstance(eta, (int, float, np.integer, np.floating)) or eta < 0 or (eta != 0 and not ddim):
+            raise ValueError(f"deblur: eta = {eta!r} needs ddim=True and eta >= 0")
+        C, H, W = self.sample_shape
+        if H % 16 or W % 16 or not (16 <= H <= 256 and 16 <= W <= 256 and 1 <= C <= 8):
+            raise ValueError(f"deblur: the image size must be multiples of 16 in [16, 256] with 1 to 8 channels, this model's is {C} x {H} x {W}")
+        if not torch.is_tensor(y) or y.dim() != 4 or list(y.shape[1:]) != [C, H, W] or not y.is_floating_point():
+            raise ValueError(f"deblur: y must be a float [B, {C}, {H}, {W}] tensor, got "
+                             f"{tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
+        if not bool(torch.isfinite(y).all()):
+            raise ValueError("deblur: y must be finite")
+        return y.float()
+
+    @torch.no_grad()
+    def deblur(self, y, kernel="gauss", *, tol=blur.DEFAULT_TOL, respacing=None, ddim=False, eta=0.0, x_T=None, seed=None, **unsupported):
+        """Zero-shot deblurring with DDNM (Wang, Yu, Zhang 2023): an image [B, C, H, W] whose separable blur
+        with zero padding, A(X) = A_h X A_w^T per channel, is y [B, C, H, W] (in [-1, 1]).  kernel: "uniform" (9 x 9 box), "gauss"
+        (5 x 5, sigma 10), "aniso" (9 taps, sigma 20 down the rows, sigma 1 along them), an odd-length 1-D array or a pair
+        (k_h, k_w).  tol: singular values of each axis below tol * s_max are dropped from the pseudo-inverse.  Every step of the chain
+        (all T steps, or respacing's K; ancestral, or DDIM with eta) replaces the range-space part of its clipped x0 by A+ y before
+        the update, so the result's projection P_h x P_w^T equals A+ y up to fp32 rounding, and A(x) = y as far as the truncation
+        allows.  x_T: the start state; seed: the Philox key (default: drawn from torch's generator).  H and W multiples of 16 in
+        [16, 256].  solver / noise / early_stop / paste / mask / sigma_y raise ValueError, as do an unknown kernel, a bad tol or eta
+        and a non-finite or misshapen y, before any device work."""
+        y = self._deblur_args(y, kernel, tol, ddim, eta, unsupported)
+        spaced = respacing is not None or ddim or eta != 0
+        sid = int(self.rng_stream_id)
+        m = self._blur_operands(kernel, tol)
+        yp = []                   # the Python loop's Yp = A+ y, formed at its first step
+
+        def op(x, e, yl, mk, t, tables, seed):
+            if not yp:
+                yp.append(ops.separable_apply(yl, m["Q_h"], m["Q_w"]))
+            ops.p_sample_update_restore_blur_(x, e, m["P_h"], m["P_w"], yp[0], t, **tables, seed=seed, stream_id=sid)
+        return self._ddnm_loop(
+            "deblur", y, None, lambda: self._spaced_tables(respacing, ddim, eta) if spaced else (self._tables(), None), x_T, seed, op,
+            lambda plan, x, yl, mk, tables, k_start, seed, use: plan.sample_restore_blur_nhwc(
+                x, yl, m["P_h"], m["P_w"], m["Q_h"], m["Q_w"], tables, k_start, seed=seed, stream_id=sid, use_graph=self.use_graph,
+                timesteps=use))
 
     @torch.no_grad()
     def reconstruct(self, x, n):

@@ -14,6 +14,8 @@ import torch
 
 MASKS = ("center", "left", "half", "lines")
 TASKS = ("inpaint", "sr", "colorize")
+DEBLUR_TASK = "deblur"          # evaluate_restoration's fourth task (section 3.14), with kernels of its own instead of masks and scales
+BLUR_KERNELS = ("uniform", "gauss", "aniso")
 METHODS = ("repaint", "ddnm")
 GRAY_WEIGHTS = {"mean": (1.0 / 3.0, 1.0 / 3.0, 1.0 / 3.0), "luma": (0.299, 0.587, 0.114)}     # DDPM.colorize's two operators
 
@@ -144,14 +146,27 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
     grey image copied into the three channels (and every pixel repeated scale x scale), and at scale > 1 "bicubic".  consistency /
     consistency_u8: max |A(x_out) - y| over the measured pixels in uint8 levels (with sigma_y: the RMS against the clean y).  The
     returned method is "ddnm_gray", and "weights" is returned.
+    task "deblur" (pixel models; section 3.14): the images are blurred with the separable ``kernel`` (required: "uniform", "gauss",
+    "aniso"; zero padding) and ``model.deblur`` restores them (``chain``: tol, respacing, ddim, eta).  Baselines: "blurred", the measurement
+    itself, and "pinv", A+ y clipped to [-1, 1] (the truncated pseudo-inverse alone, no network).  consistency / consistency_u8:
+    max |A(x_out) - y| in uint8 levels, which the truncation keeps above zero.  The returned method is "ddnm_blur", and "kernel" and
+    "tol" are returned.
     Batch g draws x_T and its Philox key from seed + g, as the sampling CLIs do.
 
     "method" and "unet_forwards" (UNet forwards per image: the chain's steps; the batch shares each forward) are returned too.
     Returns {"n_images", "methods": {name: {"psnr": [N], "ssim": [N], ...}}, "images": {name: uint8 [N, H, W, C]}} and, for "sr",
     "consistency" / "consistency_u8" [N]; "restored" is the model's entry."""
     from ddk import ops
+    if task == DEBLUR_TASK:
+        if method not in (None, "ddnm") or dpm_solver or sigma_y or sr_mask is not None or scale is not None:
+            raise ValueError("task 'deblur' has one method, ddnm on ancestral or DDIM steps, and no mask, scale or sigma_y")
+        if "kernel" not in chain or not hasattr(model, "deblur"):
+            raise ValueError("task 'deblur' needs a kernel and a model with a deblur method (a pixel DDPM)")
+        return _evaluate_deblur(model, images_uint8, batch_size=batch_size, seed=seed, **chain)
+    if "kernel" in chain or "tol" in chain:
+        raise ValueError("kernel and tol belong to task 'deblur'")
     if task not in TASKS:
-        raise ValueError(f"unknown task {task!r}: one of {TASKS}")
+        raise ValueError(f"unknown task {task!r}: one of {(*TASKS, DEBLUR_TASK)}")
     if task == "colorize":
         return _evaluate_colorize(model, images_uint8, batch_size=batch_size, seed=seed, scale=1 if scale is None else scale, method=method,
                                   sr_mask=sr_mask, dpm_solver=dpm_solver, sigma_y=sigma_y, **chain)
@@ -292,6 +307,36 @@ def _evaluate_colorize(model, images_uint8, *, batch_size, seed, scale, method, 
         extra.update(consistency=dev(x_out), consistency_u8=dev(from_u8(images["restored"])))
     methods = {name: _score(ops, img, ref, None, device) for name, img in images.items()}
     return dict(n_images=n, method="ddnm_gray", methods=methods, images={k: v.numpy() for k, v in images.items()}, **extra)
+
+
+@torch.no_grad()
+def _evaluate_deblur(model, images_uint8, *, batch_size, seed, kernel, tol=3e-2, **chain):
+    """evaluate_restoration's task "deblur" (see there)"""
+    from ddk import ops
+    from models.diffusion import blur
+    x_all = from_u8(images_uint8)
+    ref = torch.as_tensor(images_uint8).contiguous()
+    n, c, h, w = x_all.shape
+    if n < 1 or batch_size < 1:
+        raise ValueError("evaluate_restoration needs at least one image and batch_size >= 1")
+    device = model.betas.device
+    A_h, A_w, Q_h, Q_w = blur.blur_operands(kernel, h, w, tol)[:4]
+    sep = lambda x, L, R: torch.einsum("ih,bchw,jw->bcij", L, x, R)
+    y_all = sep(x_all, A_h, A_w)
+    K = len(model._spaced_tables(chain.get("respacing"), chain.get("ddim", False), chain.get("eta", 0.0))[1]) \
+        if chain.get("respacing") is not None or chain.get("ddim") else int(model.timesteps)
+    images = {"blurred": to_u8(y_all), "pinv": to_u8(sep(y_all, Q_h, Q_w).clamp(-1, 1))}
+    outs = []
+    for g, i in enumerate(range(0, n, batch_size)):
+        torch.manual_seed(seed + g)               # x_T and the Philox key of batch g
+        outs.append(model.deblur(y_all[i:i + batch_size].to(device), kernel, tol=tol, **chain).float().cpu())
+    x_out = torch.cat(outs)
+    images = dict(restored=to_u8(x_out), **images)
+    dev = lambda x: ((sep(x, A_h, A_w) - y_all).abs().amax(dim=(1, 2, 3)) * 127.5).double().numpy()
+    extra = dict(unet_forwards=K, kernel=kernel if isinstance(kernel, str) else "custom", tol=float(tol), consistency=dev(x_out),
+                 consistency_u8=dev(from_u8(images["restored"])))
+    methods = {name: _score(ops, img, ref, None, device) for name, img in images.items()}
+    return dict(n_images=n, method="ddnm_blur", methods=methods, images={k: v.numpy() for k, v in images.items()}, **extra)
 
 
 def report(result):

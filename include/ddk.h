@@ -370,6 +370,26 @@ int ddk_p_sample_update_restore_gray(float* x, const float* eps_hat, const float
                                      const float* c_recip, const float* c_recipm1, const float* c1, const float* c2, const float* sigma,
                                      const float* lam, const float* sgm, int B, int H, int W, int channels, uint64_t seed, uint32_t stream_id,
                                      ddk_stream_t s);
+/* out[b, :, :, c] = L . in[b, :, :, c] . R^T for every image b and channel c of an NHWC fp32 tensor [B][H][W][channels]; L is [H][H], R is
+ * [W][W], both row-major device arrays.  With (A_h, A_w) of a separable blur this blurs images; with (Q_h, Q_w) it forms A+ y (DESIGN.md
+ * section 3.14).  Two launches on the fp32 MFMA (rows, then columns in place on out), no atomics, no workspace: results are bit-identical
+ * run to run.  out may be `in`.  H and W multiples of 16 in [16, 256], channels in 1..8, B <= 65535; all four pointers 16-byte aligned.
+ * Anything else is DDK_ERR_ARG and runs no kernel. */
+int ddk_separable_apply(const float* in, const float* L, const float* R, float* out, int B, int H, int W, int channels, ddk_stream_t s);
+/* One DDNM deblurring step on its own (ddk_sampler_run_restore_blur): A(X) = A_h X A_w^T per channel, P_h [H][H]
+ * and P_w [W][W] the symmetric projections A+ A of the two axes, Yp = A+ y in x's layout.  Per sample b with row t[b] of the tables:
+ *   x0  = clamp(c_recip x - c_recipm1 eps_hat, -1, 1);  s = t > 0 ? sigma : 0;
+ *   x0' = (x0 - P_h x0 P_w^T) + Yp                     (per channel; not clamped again)
+ *   x   = (c1 x0' + c2 x) + s z.
+ * The two products run on the fp32 MFMA in a fixed order (first P_h x0 over rows, then P_w over columns); the elementwise operations are
+ * each rounded on their own; z is the Philox draw of ddk_p_sample_update_restore (element e takes component e & 3 of float4 e >> 2, keyed
+ * (row t, stream_id, seed)).  An image of at most 64 KB (H W channels 4 bytes) takes one launch, a workgroup per image; a larger one takes
+ * two launches through `scratch`, a device array of x's size that may be NULL for the smaller images.  H and W multiples of 16 in
+ * [16, 256], channels in 1..8, B <= 65535; x, eps_hat, P_h, P_w, Yp and scratch 16-byte aligned.  Anything else is DDK_ERR_ARG; on an
+ * error x is not touched. */
+int ddk_p_sample_update_restore_blur(float* x, const float* eps_hat, const float* P_h, const float* P_w, const float* Yp, float* scratch,
+                                     const int64_t* t, const float* c_recip, const float* c_recipm1, const float* c1, const float* c2,
+                                     const float* sigma, int B, int H, int W, int channels, uint64_t seed, uint32_t stream_id, ddk_stream_t s);
 /* The end of a forward in one launch (unet.py:69-72 behind the final Block's conv; ddpm.py:203-227): GroupNorm from the conv's
  * partials -> Mish -> 1x1 projection to n_out <= 8 channels (w [n_out][C], bias [n_out]) -> eps_hat; eps_out and / or x may be
  * given: eps_out [B][HW][n_out] receives eps_hat, x [B][HW][n_out] gets the reverse-step update of ddk_p_sample_update in place
@@ -637,6 +657,21 @@ size_t ddk_sampler_restore_gray_workspace_bytes(const ddk_unet* u, int B, int H,
 int ddk_sampler_restore_gray_tail_parts(const ddk_unet* u, int B, int H, int W, int n);
 int ddk_sampler_run_restore_gray(const ddk_sampler_args* a, const int64_t* timestep_map, const float* lam, const float* sgm, const float* y,
                                  const float* mask, int n, int weights, ddk_stream_t s);
+/* Zero-shot deblurring on a pixel-space model: DDNM for a separable blur with zero padding, A(X) = A_h X A_w^T per channel (DESIGN.md
+ * section 3.14).  The chain and tables of ddk_sampler_run_spaced (plain, respaced ancestral or DDIM), every step being
+ * ddk_p_sample_update_restore_blur's.  P_h, Q_h [H][H] and P_w, Q_w [W][W] are row-major device arrays formed by the caller (Q = A+ with
+ * the singular values below tol s_max dropped per axis, P = Q A); y is the blurred image, a device array in x's layout.  The matrices and y
+ * are read before the first step only: P_h and P_w are copied into the workspace and Yp = Q_h y Q_w^T is formed there, outside any
+ * captured step, so a loop over image batches replays one cached graph.  The workspace (ddk_sampler_restore_blur_workspace_bytes; 0 for a
+ * shape the kind does not take) holds ddk_sampler_workspace_bytes plus P_h, P_w, Yp and the two-launch form's T, each starting on a
+ * 16-byte boundary.  a->noise must be NULL (Philox only).  H and W multiples of 16 in [16, 256] and a model of 1..8 channels, else
+ * DDK_ERR_ARG.  The kind couples a whole plane, so no step takes the fused tail: ddk_sampler_restore_blur_tail_parts is 0 for every
+ * shape (-1 for a shape the plan does not take), the forward ends in the plain tail writing eps_hat and the update follows.  Graphs
+ * are cached under a chain kind of their own. */
+size_t ddk_sampler_restore_blur_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start);
+int ddk_sampler_restore_blur_tail_parts(const ddk_unet* u, int B, int H, int W);
+int ddk_sampler_run_restore_blur(const ddk_sampler_args* a, const int64_t* timestep_map, const float* P_h, const float* P_w, const float* Q_h,
+                                 const float* Q_w, const float* y, ddk_stream_t s);
 /* Drops the plan's cached sampler and likelihood-sweep graphs and shift table (waits for the device when graphs exist). */
 int ddk_sampler_invalidate(ddk_unet* u);
 /* Drops only the cached graphs (and shift table) that live in / point into `workspace`, after waiting for the launches of

@@ -30,7 +30,13 @@ mask (the fused tail; and with the fused tail switched off) and n = 2 with the m
 
 --restore-gray: the cost of a colourisation step ("luma" weights, sigma_y = 0, no mask) on a 128-wide
 3-channel pixel DDPM with 32 x 32 images at n = 1 (the fused tail; and with the fused tail switched off) and n = 2, against an
-ancestral step of the same model's respaced "50" chain, timed alternately the same way."""
+ancestral step of the same model's respaced "50" chain, timed alternately the same way.
+
+--restore-blur: the cost of a DDNM deblurring step ("gauss" kernel) against an ancestral step of the same
+respaced chain, timed alternately the same way, on a 128-wide 3-channel pixel DDPM with 32 x 32 images at B = 32 ("50" steps; the
+one-launch form of the update) and on a 32-wide one with 256 x 256 images at B = 8 ("20" steps; the two-launch form).  Every
+deblurring step ends in the unfused tail (the operator couples a whole plane), so the ratio holds the plain tail's extra launch as
+well as the two matrix products."""
 import argparse
 import json
 import os
@@ -62,11 +68,14 @@ def main():
     ap.add_argument("--restore-masked", action="store_true", help="masked DDNM step (n = 1, 2) against an ancestral step, respacing 50")
     ap.add_argument("--restore-noisy", action="store_true", help="DDNM+ step (n = 1, 2; sigma_y 0.1) against an ancestral step, respacing 50")
     ap.add_argument("--restore-gray", action="store_true", help="colourisation step (n = 1, 2; luma) against an ancestral step, respacing 50, on a 3-channel pixel model")
+    ap.add_argument("--restore-blur", action="store_true", help="deblurring step (gauss) against an ancestral step on 3x32x32 (B 32) and 3x256x256 (B 8) pixel models")
     ap.add_argument("--restore-solver", action="store_true", help="DDNM step on the 2M chain (n = 1 center mask, n = 2) against a 2M step, logsnr20")
     args = ap.parse_args()
     torch.cuda.set_device(0)
     if args.restore_gray:
         return restore_gray_ab()
+    if args.restore_blur:
+        return restore_blur_ab()
     cfg = bench.cfg4()
     model = DownsampleDDPM(cfg, Unet(cfg), DEV, 3)
     model.load_state_dict(syn.fill_state_dict(model.state_dict(), skip=syn.SCHEDULE_KEYS))
@@ -331,6 +340,53 @@ def restore_gray_ab():
                                            "gray_min_max_ms": [round(min(rst), 4), round(max(rst), 4)]}
         plan.set_option(plan.OPT_RESTORE_FUSED_TAIL, 1)
     assert torch.isfinite(x).all()
+    print(json.dumps(res), flush=True)
+
+
+def restore_blur_ab():
+    """its own models: the blur is an operator on pixels, which cfg4's latent is not"""
+    from models.diffusion import blur
+    res = {"shape": f"pixel DDPMs, T={T}, deblurring step (gauss kernel, tol 3e-2) vs ancestral step of the same respaced chain", "reps": REPS,
+           "per_case": {}}
+    for name, chan, size, b, K in (("3x32x32_B32_chan128_one_launch", 128, 32, 32, 50), ("3x256x256_B8_chan32_two_launches", 32, 256, 8, 20)):
+        cfg = dict(unet_chan=chan, unet_in=3, unet_dims=(1, 2, 2, 2), unet_dropout=0.0, image_size=size, T=T, loss_type="simple",
+                   beta_schedule="linear", loss_flat="sum")
+        model = DDPM(cfg, Unet(cfg), DEV, 3)
+        model.load_state_dict(syn.fill_state_dict(model.state_dict(), skip=syn.SCHEDULE_KEYS))
+        model = model.to(DEV).eval()
+        plan = model.latent_model.plan()
+        x0 = ops.randn((b, size, size, 3), DEV, seed=1234, step=T, stream_id=0)
+        x = x0.clone()
+        m = {k: v.to(DEV) for k, v in zip(("A_h", "A_w", "Q_h", "Q_w", "P_h", "P_w"), blur.blur_operands("gauss", size, size))}
+        y = ops.separable_apply(x0.clamp(-1, 1), m["A_h"], m["A_w"])
+        sp, use = model._spaced_tables(str(K), False, 0.0)
+
+        def chain(kind):
+            x.copy_(x0)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            if kind == "anc":
+                plan.sample_nhwc(x, sp, K - 1, 0, seed=1234, stream_id=0, timesteps=use)
+            else:
+                plan.sample_restore_blur_nhwc(x, y, m["P_h"], m["P_w"], m["Q_h"], m["Q_w"], sp, K - 1, seed=1234, stream_id=0, timesteps=use)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3
+
+        with torch.no_grad():
+            t_settle = time.perf_counter()
+            while time.perf_counter() - t_settle < 2.0:
+                chain("anc")
+            chain("blur")                                # both chains' graphs are captured outside the timed calls
+            anc, rst = [], []
+            for _ in range(REPS):
+                anc.append(chain("anc") / K)
+                rst.append(chain("blur") / K)
+        assert torch.isfinite(x).all() and plan.restore_blur_tail_parts(b, size, size) == 0
+        a, r = statistics.median(anc), statistics.median(rst)
+        res["per_case"][name] = {"ancestral_ms_per_step": round(a, 4), "blur_ms_per_step": round(r, 4), "blur_over_ancestral": round(r / a, 4),
+                                 "ancestral_min_max_ms": [round(min(anc), 4), round(max(anc), 4)],
+                                 "blur_min_max_ms": [round(min(rst), 4), round(max(rst), 4)], "steps": K}
+        del model, plan
     print(json.dumps(res), flush=True)
 
 
