@@ -181,6 +181,88 @@ __global__ __launch_bounds__(1024) void restore_blur_image_kernel(const BlurStep
     }
 }
 
+// ---------------------------------------------------------------------------------------------- the size-changing form (section 3.15)
+// out = L . in . R^T with L [Ho][Hi] and R [Wo][Wi]: the same tile and the same [K][16] operand, for what the square form never meets.
+// Every size is a multiple of 4, so a matrix row is still whole float4s; the rest is guarded here:
+//   K not a multiple of 16   the last super-step's lanes with 16 s + 4 g >= K feed zeros on both sides, and read neither M nor S there
+//   a partial last tile      lanes whose matrix row is past `rows` load nothing; the caller guards its stores in both tile coordinates
+//   a partial strip / group  the caller stages zeros into S's columns past the end
+// With K a multiple of 16 and whole tiles this is sep_tile's sum, term by term.
+__device__ __forceinline__ f32x4 sep_tile_rect(const float* __restrict__ Mrows, int K, int rows, const float* S, int lane) {
+    const int i = lane & 15, g = lane >> 4;
+    const bool row = i < rows;
+    const float4* __restrict__ a = reinterpret_cast<const float4*>(Mrows + (size_t)(row ? i : 0) * K) + g;
+    const float* b = S + 4 * g * SP + i;
+    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+    for (int s = 0; s < (K + 15) / 16; ++s) {
+        const bool kin = 16 * s + 4 * g < K;
+        const float4 av = row && kin ? a[4 * s] : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float* bs = b + 16 * s * SP;
+        const float b0 = kin ? bs[0] : 0.f, b1 = kin ? bs[SP] : 0.f, b2 = kin ? bs[2 * SP] : 0.f, b3 = kin ? bs[3 * SP] : 0.f;
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.x, b0, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.y, b1, acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.z, b2, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.w, b3, acc1, 0, 0, 0);
+    }
+    return acc0 + acc1;
+}
+
+struct RectShape {
+    int Hi, Wi, Ho, Wo, C;
+};
+
+// Rows: T[b][:, strip] = L . in[b][:, strip], in as the matrix [Hi][Wi C], T [Ho][Wi C] (grid: ceil(Wi C / 16), B)
+__global__ __launch_bounds__(256) void sep_rows_rect_kernel(const RectShape p, const float* __restrict__ in, const float* __restrict__ M,
+                                                            float* __restrict__ T) {
+    __shared__ __attribute__((aligned(16))) float S[SEP_MAX * SP];
+    const int Hi = p.Hi, Ho = p.Ho, N = p.Wi * p.C, n0 = blockIdx.x * 16, b = blockIdx.y;
+    const int cols = min(16, N - n0);
+    const float* __restrict__ src = in + (long long)b * Hi * N + n0;
+    for (int idx = threadIdx.x; idx < Hi * 16; idx += 256) {
+        const int h = idx >> 4, j = idx & 15;
+        S[h * SP + j] = j < cols ? src[(long long)h * N + j] : 0.f;
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, g = lane >> 4;
+    float* __restrict__ dst = T + (long long)b * Ho * N + n0;
+    for (int m = wave; 16 * m < Ho; m += 4) {
+        const f32x4 acc = sep_tile_rect(M + (size_t)m * 16 * Hi, Hi, Ho - 16 * m, S, lane);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int h = 16 * m + 4 * g + r;
+            if (h < Ho && i < cols) dst[(long long)h * N + i] = acc[r];
+        }
+    }
+}
+
+// Columns: 16 rows of one image's T per workgroup (grid: ceil(Ho / 16), B), channel by channel: S[k][n] = T[h0 + n][k][c], the tile is
+// out[h0 + n][16 j + m][c]; out is another tensor than T ([Ho][Wo] against [Ho][Wi])
+__global__ __launch_bounds__(256) void sep_cols_rect_kernel(const RectShape p, const float* __restrict__ T, const float* __restrict__ M,
+                                                            float* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) float S[SEP_MAX * SP];
+    const int Wi = p.Wi, Ho = p.Ho, Wo = p.Wo, C = p.C, h0 = blockIdx.x * 16, b = blockIdx.y;
+    const int rows = min(16, Ho - h0);
+    const float* __restrict__ src = T + ((long long)b * Ho + h0) * Wi * C;
+    float* __restrict__ dst = out + ((long long)b * Ho + h0) * Wo * C;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, g = lane >> 4;
+    for (int c = 0; c < C; ++c) {
+        __syncthreads();          // the previous channel's tiles are done with S
+        for (int idx = threadIdx.x; idx < 16 * Wi; idx += 256) {
+            const int n = idx / Wi, k = idx - n * Wi;
+            S[k * SP + n] = n < rows ? src[((long long)n * Wi + k) * C + c] : 0.f;
+        }
+        __syncthreads();
+        for (int j = wave; 16 * j < Wo; j += 4) {
+            const f32x4 acc = sep_tile_rect(M + (size_t)j * 16 * Wi, Wi, Wo - 16 * j, S, lane);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int w = 16 * j + 4 * g + r;
+                if (i < rows && w < Wo) dst[((long long)i * Wo + w) * C + c] = acc[r];
+            }
+        }
+    }
+}
+
 static size_t one_launch_lds(int H, int W, int C) { return (size_t)10 * H * W * C; }
 
 bool restore_blur_shape_ok(int H, int W, int channels) {
@@ -202,6 +284,16 @@ static int separable_apply(const float* in, const float* L, const float* R, floa
     hipLaunchKernelGGL(sep_cols_kernel<false>, dim3(H / 16, B), dim3(256), 0, st, p, out, R, (uint64_t)0, (uint32_t)0, (const int64_t*)nullptr,
                        (int64_t*)nullptr);
     return check_launch("sep_cols_kernel");
+}
+
+bool separable_rect_size_ok(int n) { return n >= 4 && n <= SEP_MAX && n % 4 == 0; }
+
+static int separable_apply_rect(const float* in, const float* L, const float* R, float* out, float* scratch, int B, const RectShape& p,
+                                hipStream_t st) {
+    hipLaunchKernelGGL(sep_rows_rect_kernel, dim3((p.Wi * p.C + 15) / 16, B), dim3(256), 0, st, p, in, L, scratch);
+    DDK_TRY(check_launch("sep_rows_rect_kernel"));
+    hipLaunchKernelGGL(sep_cols_rect_kernel, dim3((p.Ho + 15) / 16, B), dim3(256), 0, st, p, (const float*)scratch, R, out);
+    return check_launch("sep_cols_rect_kernel");
 }
 
 int p_update_restore_blur(const StepRule& r, const float* eps_hat, const int64_t* t, int B, int channels, const ChainHooks& h, hipStream_t st) {
@@ -232,6 +324,22 @@ int ddk_separable_apply(const float* in, const float* L, const float* R, float* 
                 "separable_apply: H and W must be multiples of 16 in [16, 256], channels in 1..8, B in 1..65535");
     DDK_REQUIRE(aligned16(in) && aligned16(L) && aligned16(R) && aligned16(out), "separable_apply: alignment");
     return separable_apply(in, L, R, out, B, H, W, channels, as_stream(s));
+}
+
+int ddk_separable_apply_rect(const float* in, const float* L, const float* R, float* out, float* scratch, int B, int Hi, int Wi, int Ho, int Wo,
+                             int channels, ddk_stream_t s) {
+    DDK_REQUIRE(in && L && R && out && scratch, "separable_apply_rect: null pointer");
+    DDK_REQUIRE(B > 0 && B <= 65535 && separable_rect_size_ok(Hi) && separable_rect_size_ok(Wi) && separable_rect_size_ok(Ho) &&
+                    separable_rect_size_ok(Wo) && channels >= 1 && channels <= 8,
+                "separable_apply_rect: Hi, Wi, Ho and Wo must be multiples of 4 in [4, 256], channels in 1..8, B in 1..65535");
+    DDK_REQUIRE(aligned16(in) && aligned16(L) && aligned16(R) && aligned16(out) && aligned16(scratch), "separable_apply_rect: alignment");
+    const size_t bc = (size_t)B * channels;
+    const char *i0 = (const char*)in, *o0 = (const char*)out, *t0 = (const char*)scratch;
+    const size_t ni = bc * Hi * Wi * sizeof(float), no = bc * Ho * Wo * sizeof(float), nt = bc * Ho * Wi * sizeof(float);
+    auto overlap = [](const char* a, size_t na, const char* b, size_t nb) { return a < b + nb && b < a + na; };
+    DDK_REQUIRE(!overlap(o0, no, i0, ni) && !overlap(o0, no, t0, nt) && !overlap(t0, nt, i0, ni),
+                "separable_apply_rect: in, scratch and out must not overlap (the two products have different shapes: nothing runs in place)");
+    return separable_apply_rect(in, L, R, out, scratch, B, RectShape{Hi, Wi, Ho, Wo, channels}, as_stream(s));
 }
 
 int ddk_p_sample_update_restore_blur(float* x, const float* eps_hat, const float* P_h, const float* P_w, const float* Yp, float* scratch,

@@ -1811,7 +1811,13 @@ static int sampler_chain(const ddk_sampler_args* a, const char* who, const int64
         const BlurStage g = blur_stage(al4(n), H, W);
         DDK_HIP(hipMemcpyAsync(extra + g.ph, rule.blr.ph, (size_t)H * H * sizeof(float), hipMemcpyDeviceToDevice, c.st));
         DDK_HIP(hipMemcpyAsync(extra + g.pw, rule.blr.pw, (size_t)W * W * sizeof(float), hipMemcpyDeviceToDevice, c.st));
-        DDK_TRY(ddk_separable_apply(rule.rst.y, rule.blr.qh, rule.blr.qw, extra + g.yp, B, H, W, c.u->cfg.in_ch, s));
+        // rule.rst.H x rule.rst.W is the size of that y (the entry's h, w): the plane's own takes the square form, in place on Yp; a smaller
+        // one the size-changing form with T as its scratch, [B][H][w][C] never exceeding it
+        if (rule.rst.H == H && rule.rst.W == W)
+            DDK_TRY(ddk_separable_apply(rule.rst.y, rule.blr.qh, rule.blr.qw, extra + g.yp, B, H, W, c.u->cfg.in_ch, s));
+        else
+            DDK_TRY(ddk_separable_apply_rect(rule.rst.y, rule.blr.qh, rule.blr.qw, extra + g.yp, extra + g.tmp, B, rule.rst.H, rule.rst.W, H, W,
+                                             c.u->cfg.in_ch, s));
         rule.blr = BlurOps{extra + g.ph, extra + g.pw, extra + g.tmp, nullptr, nullptr};
         rule.rst = RestoreOps{extra + g.yp, 0, H, W, 0, nullptr};
     } else if (restore_kind(rule.kind)) {
@@ -2049,9 +2055,9 @@ extern "C" int ddk_sampler_restore_blur_tail_parts(const ddk_unet* u, int B, int
     if (check_shape(u, B, H, W) != DDK_OK) return -1;
     return fused_tail_parts(*u, B, H, W, u->dimp[1], StepKind::RestoreBlur);      // 0: final_tail_ok takes no plane-wide kind
 }
-extern "C" int ddk_sampler_run_restore_blur(const ddk_sampler_args* a, const int64_t* timestep_map, const float* P_h, const float* P_w,
-                                            const float* Q_h, const float* Q_w, const float* y, ddk_stream_t s) {
-    const char* who = "sampler_restore_blur";
+// (both entries: y is [B][h][w][C], Q_h [H][h], Q_w [W][w]; the deblurring entry's h, w are the plane's)
+static int restore_blur_chain(const ddk_sampler_args* a, const char* who, const int64_t* timestep_map, const float* P_h, const float* P_w,
+                              const float* Q_h, const float* Q_w, const float* y, bool sized, int h, int w, ddk_stream_t s) {
     auto bad = [who](const char* what) {
         set_error("bad argument: %s: %s", who, what);
         return DDK_ERR_ARG;
@@ -2061,13 +2067,25 @@ extern "C" int ddk_sampler_run_restore_blur(const ddk_sampler_args* a, const int
     if (a->noise) return bad("injected noise is not supported, noise must be NULL (Philox only)");
     if (!(a->t_start >= a->t_end && a->t_end >= 0)) return bad("need t_start >= t_end >= 0");
     if (!restore_blur_shape_ok(a->H, a->W, a->unet->cfg.in_ch)) return bad("H and W must be multiples of 16 in [16, 256], the model's channels 1 to 8");
+    if (!sized) { h = a->H; w = a->W; }
+    if (!(h >= 4 && h <= a->H && h % 4 == 0 && w >= 4 && w <= a->W && w % 4 == 0)) return bad("h and w must be multiples of 4 in [4, H] and [4, W]");
     if (!(aligned16(P_h) && aligned16(P_w) && aligned16(Q_h) && aligned16(Q_w) && aligned16(y))) return bad("alignment");
     DDK_TRY(check_timestep_map(timestep_map, a->t_start, who));
     StepRule rule{};
     rule.kind = StepKind::RestoreBlur;
     rule.blr = BlurOps{P_h, P_w, nullptr, Q_h, Q_w};
     rule.rst.y = y;
+    rule.rst.H = h; rule.rst.W = w;      // of the caller's y, until sampler_chain has formed Yp
     return sampler_chain(a, who, timestep_map, rule, s);
+}
+extern "C" int ddk_sampler_run_restore_blur(const ddk_sampler_args* a, const int64_t* timestep_map, const float* P_h, const float* P_w,
+                                            const float* Q_h, const float* Q_w, const float* y, ddk_stream_t s) {
+    return restore_blur_chain(a, "sampler_restore_blur", timestep_map, P_h, P_w, Q_h, Q_w, y, false, 0, 0, s);
+}
+// DDNM for a size-changing separable operator (section 3.15): the same chain with y [B][h][w][C] and Q_h [H][h], Q_w [W][w]
+extern "C" int ddk_sampler_run_restore_sep(const ddk_sampler_args* a, const int64_t* timestep_map, const float* P_h, const float* P_w,
+                                           const float* Q_h, const float* Q_w, const float* y, int h, int w, ddk_stream_t s) {
+    return restore_blur_chain(a, "sampler_restore_sep", timestep_map, P_h, P_w, Q_h, Q_w, y, true, h, w, s);
 }
 
 // ------------------------------------------------------------------------------------------------ likelihood sweep

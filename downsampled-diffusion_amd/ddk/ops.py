@@ -858,6 +858,26 @@ def separable_apply(x, L_mat, R_mat, out=None):
     return out
 
 
+def separable_apply_rect(x, L_mat, R_mat, out=None):
+    """out[b,:,:,c] = L_mat . x[b,:,:,c] . R_mat^T for every image and channel of x [B,Hi,Wi,C] (NHWC) with L_mat [Ho,Hi] and R_mat
+    [Wo,Wi] fp32: the size-changing form of separable_apply.  With blur.resize_matrix on both axes it is the
+    antialiased bicubic reduction, with (Q_h, Q_w) of blur.separable_operands it forms A+ y.  Every size a multiple of 4 in [4, 256], C
+    in 1..8.  Returns out [B,Ho,Wo,C], which must not be x; the scratch [B,Ho,Wi,C] is allocated here."""
+    b, hi, wi, c = x.shape
+    if L_mat.dim() != 2 or R_mat.dim() != 2 or L_mat.shape[1] != hi or R_mat.shape[1] != wi:
+        raise L.DDKError(f"separable_apply_rect: x {tuple(x.shape)} needs L [Ho,{hi}] and R [Wo,{wi}], got {tuple(L_mat.shape)} and "
+                         f"{tuple(R_mat.shape)}")
+    ho, wo = int(L_mat.shape[0]), int(R_mat.shape[0])
+    if out is None:
+        out = torch.empty((b, ho, wo, c), device=x.device, dtype=torch.float32)
+    elif tuple(out.shape) != (b, ho, wo, c):
+        raise L.DDKError(f"separable_apply_rect: out {tuple(out.shape)} must be {(b, ho, wo, c)}")
+    scratch = torch.empty((b, ho, wi, c), device=x.device, dtype=torch.float32)
+    L.check(L.load().ddk_separable_apply_rect(L.ptr(_f32(x)), L.ptr(_f32(L_mat)), L.ptr(_f32(R_mat)), L.ptr(_f32(out)), L.ptr(scratch),
+                                              b, hi, wi, ho, wo, c, L.stream()), "separable_apply_rect")
+    return out
+
+
 def p_sample_update_restore_blur_(x, eps_hat, P_h, P_w, Yp, t, c_recip, c_recipm1, c1, c2, sigma, seed=0, stream_id=0, scratch=None):
     """In-place DDNM deblurring step of x [B,H,W,C] (NHWC) per sample row t[b]: the clipped x0 loses its
     range-space part and gains the measurement's, x0' = (x0 - P_h x0 P_w^T) + Yp per channel, then the ancestral update with Philox

@@ -30,7 +30,8 @@ SAMPLERS = {"smp": ("sample", "sampler", "sampler"), "sms": ("sample_multistep",
             "srx": ("sample_restore_multistep", "sampler_restore_multistep", "restoration solver"),
             "srn": ("sample_restore_noisy", "sampler_restore_noisy", "noisy restoration sampler"),
             "srg": ("sample_restore_gray", "sampler_restore_gray", "colourisation sampler"),
-            "srb": ("sample_restore_blur", "sampler_restore_blur", "deblurring sampler")}
+            "srb": ("sample_restore_blur", "sampler_restore_blur", "deblurring sampler"),
+            "srq": ("sample_restore_sep", "sampler_restore_sep", "separable restoration sampler")}
 # workspace kinds whose captured step graphs point into them (the samplers', the likelihood sweep's): UnetPlan._workspace keeps up
 # to 3 of each
 CHAIN_WORKSPACES = (*SAMPLERS, "vsw")
@@ -359,18 +360,21 @@ class UnetPlan:
                 "sampler_restore_multistep_tail_parts"),
         "srn": ("sampler_run_restore_noisy", "sampler_restore_noisy_workspace_bytes", "sampler_restore_noisy_tail_parts"),
         "srg": ("sampler_run_restore_gray", "sampler_restore_gray_workspace_bytes", "sampler_restore_gray_tail_parts"),
-        "srb": ("sampler_run_restore_blur", "sampler_restore_blur_workspace_bytes", "sampler_restore_blur_tail_parts")}
+        "srb": ("sampler_run_restore_blur", "sampler_restore_blur_workspace_bytes", "sampler_restore_blur_tail_parts"),
+        # the size-changing entry is the deblurring chain with a y of its own size: its workspace and tail queries serve both
+        "srq": ("sampler_run_restore_sep", "sampler_restore_blur_workspace_bytes", "sampler_restore_blur_tail_parts")}
 
     def _restore_tail_parts(self, kind, b, h, w, n):
         return int(getattr(self._lib, "ddk_" + self.RESTORE_ENTRIES[kind][2])(self.handle, b, h, w, *(() if n is None else (int(n),))))
 
     def _sample_restore(self, kind, x, y, mask, n, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, head=(), masked=True,
-                        weights=None, blur=None):
+                        weights=None, blur=None, y_size=None):
         """What the restoration samplers share: the checks on n, y, mask and the lam / sgm tables, then the chain.
         kind: the entry's key in SAMPLERS and RESTORE_ENTRIES; head: the names of the tables the C entry takes before y; masked: the
         entry takes a mask and n = 1 (which then needs one), and its workspace query takes n; weights: the grey entry's, whose y is
         [B,H/n,W/n] and whose n = 1 needs no mask; blur: the deblurring entry's matrices (P_h, P_w, Q_h, Q_w), whose operator has no
-        block (n is None, no mask) and whose y has x's shape."""
+        block (n is None, no mask) and whose y has x's shape -- or, for the size-changing entry, y_size = (h, w) of y [B,h,w,in_ch],
+        with Q_h [H,h] and Q_w [W,w]."""
         self._need_packed(kind)
         name = SAMPLERS[kind][0]
         gray = weights is not None
@@ -382,15 +386,19 @@ class UnetPlan:
         if blur is not None:
             if not (h % 16 == 0 and w % 16 == 0 and 16 <= h <= 256 and 16 <= w <= 256 and 1 <= c <= 8):
                 raise L.DDKError(f"{name}: H and W must be multiples of 16 in [16, 256] and the channels 1 to 8, got [{h},{w},{c}]")
-            for what, v, side in zip(("P_h", "P_w", "Q_h", "Q_w"), blur, (h, w, h, w)):
-                if v is None or tuple(v.shape) != (side, side) or v.dtype != torch.float32 or not v.is_contiguous() or v.device != x.device:
-                    raise L.DDKError(f"{name}: {what} must be a contiguous fp32 [{side},{side}] tensor on x's device")
-            n = 1                 # y has x's shape
+            yh, yw = (h, w) if y_size is None else y_size
+            if not (yh % 4 == 0 and yw % 4 == 0 and 4 <= yh <= h and 4 <= yw <= w):
+                raise L.DDKError(f"{name}: y's size must be multiples of 4 in [4, {h}] and [4, {w}], got {yh} x {yw}")
+            for what, v, shape in zip(("P_h", "P_w", "Q_h", "Q_w"), blur, ((h, h), (w, w), (h, yh), (w, yw))):
+                if v is None or tuple(v.shape) != shape or v.dtype != torch.float32 or not v.is_contiguous() or v.device != x.device:
+                    raise L.DDKError(f"{name}: {what} must be a contiguous fp32 [{shape[0]},{shape[1]}] tensor on x's device")
+            n = 1                 # y has x's shape, or y_size
         elif n not in ((1, 2, 4, 8) if masked else (2, 4, 8)) or h % n or w % n:
             raise L.DDKError(f"{name}: n must be {'1, ' if masked else ''}2, 4 or 8 and divide H = {h} and W = {w}, got {n}")
         if mask is None and n == 1 and not gray and blur is None:
             raise L.DDKError(f"{name}: n = 1 needs a mask (nothing would be constrained)")
-        for what, v, shape in (("y", y, (b, h // n, w // n) if gray else (b, h // n, w // n, c)), ("mask", mask, (b, h // n, w // n))):
+        y_shape = (b, *y_size, c) if y_size is not None else (b, h // n, w // n) if gray else (b, h // n, w // n, c)
+        for what, v, shape in (("y", y, y_shape), ("mask", mask, (b, h // n, w // n))):
             if v is not None and (tuple(v.shape) != shape or v.dtype != torch.float32 or not v.is_contiguous()):
                 raise L.DDKError(f"{what} must be a contiguous fp32 [{','.join(map(str, shape))}] tensor, got {tuple(v.shape)} {v.dtype}")
         for t in head:
@@ -401,7 +409,7 @@ class UnetPlan:
         tmap = self._timestep_map(timesteps, t_start)
         operands = (L.ptr(y), L.ptr(mask), int(n)) if masked else (L.ptr(y), int(n))
         if blur is not None:
-            operands = (*(L.ptr(m) for m in blur), L.ptr(y))
+            operands = (*(L.ptr(m) for m in blur), L.ptr(y), *(() if y_size is None else (int(y_size[0]), int(y_size[1]))))
         if gray:
             operands += (L.GRAY_WEIGHTS[weights],)
 
@@ -497,6 +505,20 @@ class UnetPlan:
         multiples of 16 in [16, 256].  tables / timesteps: as for sample_nhwc (plain, respaced or DDIM).  Philox only."""
         return self._sample_restore("srb", x, y, None, None, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, masked=False,
                                     blur=(P_h, P_w, Q_h, Q_w))
+
+    def sample_restore_sep_nhwc(self, x, y, P_h, P_w, Q_h, Q_w, tables, t_start, t_end=0, seed=0, stream_id=0, use_graph=True,
+                                timesteps=None):
+        """DDNM steps for a size-changing separable operator A(X) = A_h X A_w^T, A_h [h,H] and A_w [w,W] (antialiased bicubic
+        reduction, blur-then-decimate), t_start .. t_end (inclusive), in place on x [B,H,W,in_ch] (ddk_sampler_run_restore_sep;
+        DESIGN.md section 3.15).
+
+        y: the measurement, contiguous fp32 [B,h,w,in_ch]; P_h [H,H], P_w [W,W], Q_h [H,h], Q_w [W,w]: the fp32 projections and
+        pseudo-inverses of the two axes (models/diffusion/blur.py separable_operands).  The steps are sample_restore_blur_nhwc's;
+        Yp = Q_h y Q_w^T is formed in the plan's "srq" workspace by every call, so a loop over images replays one cached graph.
+        H and W multiples of 16 in [16, 256], h and w multiples of 4 in [4, H] and [4, W].  Philox only."""
+        y_size = tuple(int(q.shape[1]) if q is not None and q.dim() == 2 else 0 for q in (Q_h, Q_w))      # 0: refused below
+        return self._sample_restore("srq", x, y, None, None, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, masked=False,
+                                    blur=(P_h, P_w, Q_h, Q_w), y_size=y_size)
 
     # ---------------------------------------------------------------- likelihood sweep
     VLB_STREAM_BIT = 1 << 31     # the sweep's Philox stream id is stream_id | this (csrc/ddk_internal.h VLB_STREAM_BIT)

@@ -12,6 +12,10 @@ through utils/data.py; ``--max_batches`` keeps the first max_batches * batch_siz
   * ``--task sr``: the images are average-pooled by ``--scale``, chain options ``--timestep_respacing``, ``--use_ddim``, ``--eta``
     as in upscale_model_samples.py.  Baselines: replication and bicubic upsampling.  Also the consistency max |pool(x_out) - y| in
     uint8 levels, of the chain's float output and of the uint8 image that is scored.
+  * ``--task sr --downsample bicubic`` (DDPM checkpoints; section 3.15): the images are reduced by antialiased bicubic downsampling,
+    the degradation of the super-resolution benchmarks, instead of pooled, and ``model.super_resolve(downsample="bicubic")`` restores
+    them.  Same baselines; the consistency is max |A(x_out) - y| in uint8 levels with that operator; the settings gain ``downsample``.
+    Not with ``--mask``, ``--dpm_solver`` or ``--sigma_y``.
   * ``--task inpaint --method ddnm``: DDNM for a mask (section 3.8) instead of RePaint, with ``--use_ddim`` / ``--eta`` and without
     the ``--jump_*`` options; ``--task sr --mask KIND``: masked super-resolution, the mask applied to the pooled image, restored
     with ``model.restore``; the baselines mean-fill the same holes before they upsample.
@@ -44,7 +48,7 @@ import time
 import numpy as np
 import torch
 
-from utils.restoration_metrics import BLUR_KERNELS, DEBLUR_TASK, GRAY_WEIGHTS, MASKS, METHODS, TASKS, evaluate_restoration, load_mask, report, to_u8
+from utils.restoration_metrics import BLUR_KERNELS, DEBLUR_TASK, DOWNSAMPLES, GRAY_WEIGHTS, MASKS, METHODS, TASKS, evaluate_restoration, load_mask, report, to_u8
 
 
 def parse_args(argv=None):
@@ -57,6 +61,7 @@ def parse_args(argv=None):
                                                  "center; sr: masked super-resolution, the mask is of the pooled image (default: none)")
     ap.add_argument("--method", default=None, choices=METHODS, help="inpaint: repaint (default) or ddnm; sr: ddnm")
     ap.add_argument("--scale", type=int, default=None, help="sr: the pooling factor (default 4); colorize: default 1")
+    ap.add_argument("--downsample", default=None, choices=DOWNSAMPLES, help="sr: how the images are reduced (default mean: average pooling)")
     ap.add_argument("--weights", default=None, choices=tuple(GRAY_WEIGHTS), help="colorize: the grey image's channel weights (default mean)")
     ap.add_argument("--kernel", default=None, choices=BLUR_KERNELS, help="deblur: the separable blur (required there)")
     ap.add_argument("--tol", type=float, default=None, help="deblur: singular values below tol * s_max are dropped, per axis (default 0.03)")
@@ -78,6 +83,10 @@ def parse_args(argv=None):
         ap.error("--batch_size and --max_batches must be >= 1")
     if args.method is None:
         args.method = "repaint" if args.task == "inpaint" else "ddnm"
+    if args.downsample is not None and args.task != "sr":
+        ap.error("--downsample belongs to --task sr")
+    if args.downsample == "bicubic" and (args.mask is not None or args.dpm_solver or args.sigma_y != 0.0):
+        ap.error("--downsample bicubic takes no --mask, --dpm_solver or --sigma_y")
     if args.weights is not None and args.task != "colorize":
         ap.error("--weights belongs to --task colorize")
     if (args.kernel is not None or args.tol is not None) and args.task != DEBLUR_TASK:
@@ -140,6 +149,8 @@ def chain_options(args):
         kw.update(scale=args.scale)
     if args.task == "colorize":
         kw.update(weights=args.weights)
+    if args.downsample == "bicubic":
+        kw.update(downsample="bicubic")
     if args.task == DEBLUR_TASK:
         kw.update(kernel=args.kernel, tol=args.tol)
     if args.dpm_solver:

@@ -101,12 +101,17 @@ class DownsampleDDPM(DDPM):
         return x_out, z
 
     @torch.no_grad()
-    def super_resolve(self, y, scale, *, respacing=None, ddim=False, eta=0.0, x_T=None, seed=None, **unsupported):
+    def super_resolve(self, y, scale, *, downsample="mean", respacing=None, ddim=False, eta=0.0, x_T=None, seed=None, **unsupported):
         """DDNM super-resolution in the latent (DDPM.super_resolve) of y [B, C, H/scale, W/scale].  The
         constraint is the latent's: z_ref = rescaled_downsample(y replicated scale x scale), y_lat = the n_lat x n_lat average
         pooling of z_ref with n_lat = scale / dim_reduc in {2, 4, 8}, and the chain keeps the latent's n_lat x n_lat block means
         equal to y_lat.  That is exact in the latent (up to fp32 rounding) and only approximate in pixels: the decoder is not
-        linear, so the pooled x_out is close to y, not equal to it.  Returns (x_out, z) like sample; x_T is a latent start state."""
+        linear, so the pooled x_out is close to y, not equal to it.  Returns (x_out, z) like sample; x_T is a latent start state.
+        downsample: "mean" only -- a bicubic reduction of the image is no separable operator of the latent (restore_separable):
+        anything else is a ValueError."""
+        if downsample != "mean":
+            raise ValueError(f"super_resolve: a DownsampleDDPM samples in a latent and holds block means there: downsample must be "
+                             f"'mean', got {downsample!r} (bicubic super-resolution needs a pixel model, DDPM)")
         d = int(self.dim_reduc)
         y = self._restore_args(y, scale, self.x_shape, ddim, eta, unsupported, block=d)
         y = y.to(self.betas.device)
@@ -202,6 +207,11 @@ class DownsampleDDPM(DDPM):
         operator of DDPM.deblur has no separable form there.  A stated limitation, not an approximation: always ValueError."""
         raise ValueError("deblur: a DownsampleDDPM samples in a latent, and a blur of the latent is not a blur of the image; deblurring "
                          "needs a pixel model (DDPM)")
+
+    def restore_separable(self, y, A_h, A_w, **kwargs):
+        """Not available, for deblur's reason: an operator on the image is not one on the latent.  Always ValueError."""
+        raise ValueError("restore_separable: a DownsampleDDPM samples in a latent, and a separable operator on the image has no separable "
+                         "form there; it needs a pixel model (DDPM)")
 
     @torch.no_grad()
     def reconstruct(self, x, n):

@@ -425,14 +425,26 @@ class DDPM(nn.Module):
                                seed, op, chain)
 
     @torch.no_grad()
-    def super_resolve(self, y, scale, *, respacing=None, ddim=False, eta=0.0, x_T=None, seed=None, **unsupported):
+    def super_resolve(self, y, scale, *, downsample="mean", respacing=None, ddim=False, eta=0.0, x_T=None, seed=None, **unsupported):
         """Zero-shot super-resolution with DDNM (Wang, Yu, Zhang 2023): an image [B, C, H, W] whose
-        scale x scale average pooling is y [B, C, H/scale, W/scale] (in [-1, 1]); scale in {2, 4, 8}.  Every step of the chain
+        scale x scale average pooling is y [B, C, H/scale, W/scale] (in [-1, 1]); scale in {2, 4, 8}.  downsample="bicubic": y is
+        the antialiased bicubic reduction instead (blur.resize_matrix on both axes, what image libraries and the SR benchmarks
+        make), restored by restore_separable: H and W multiples of 16 in [16, 256], H/scale and W/scale
+        multiples of 4, and A(x_out) = y up to fp32 rounding.  Every step of the chain
         (all T steps, or respacing's K; ancestral, or DDIM with eta) shifts its clipped x0 so that its block means equal y before the
         update; the block means of the result equal y up to fp32 rounding.  x_T: the start state; seed: the Philox key (default:
         drawn from torch's generator).  solver / noise / early_stop raise ValueError, as do a bad scale, a non-finite or misshapen y
         and eta without ddim, before any device work."""
+        if downsample not in ("mean", "bicubic"):
+            raise ValueError(f"super_resolve: downsample must be 'mean' or 'bicubic', got {downsample!r}")
         y = self._restore_args(y, scale, self.sample_shape, ddim, eta, unsupported)
+        if downsample == "bicubic":
+            C, H, W = self.sample_shape
+            if H % 16 or W % 16 or not (16 <= H <= 256 and 16 <= W <= 256) or (H // scale) % 4 or (W // scale) % 4:
+                raise ValueError(f"super_resolve: downsample='bicubic' needs an image size of multiples of 16 in [16, 256] whose "
+                                 f"{scale}-fold reduction is a multiple of 4, this model's is {H} x {W}")
+            return self.restore_separable(y, blur.resize_matrix(H, int(scale)), blur.resize_matrix(W, int(scale)), respacing=respacing,
+                                          ddim=ddim, eta=eta, x_T=x_T, seed=seed)
         return self._restore_loop(y, int(scale), respacing, ddim, eta, x_T, seed)
 
     # ------------------------------------------------------------------ DDNM with a mask: inpainting and masked super-resolution
@@ -724,6 +736,76 @@ class DDPM(nn.Module):
         return self._ddnm_loop(
             "deblur", y, None, lambda: self._spaced_tables(respacing, ddim, eta) if spaced else (self._tables(), None), x_T, seed, op,
             lambda plan, x, yl, mk, tables, k_start, seed, use: plan.sample_restore_blur_nhwc(
+                x, yl, m["P_h"], m["P_w"], m["Q_h"], m["Q_w"], tables, k_start, seed=seed, stream_id=sid, use_graph=self.use_graph,
+                timesteps=use))
+
+    # ------------------------------------------------------------------ DDNM for any separable operator (size-changing included)
+    def _sep_operands(self, A_h, A_w, tol):
+        """{A_h, A_w, Q_h, Q_w, P_h, P_w} of blur.separable_operands on the model's device, cached like _blur_operands."""
+        names = ("A_h", "A_w", "Q_h", "Q_w", "P_h", "P_w")
+        return self._cached_tables(('sep', A_h.tobytes(), A_w.tobytes(), A_h.shape, A_w.shape, float(tol)),
+                                   lambda: (dict(zip(names, blur.separable_operands(A_h, A_w, tol)[:6])), None))[0]
+
+    def _separable_args(self, y, A_h, A_w, tol, ddim, eta, unsupported):
+        """ValueError for anything restore_separable cannot take, before any device work.  Returns (y as float, A_h, A_w as float64
+        arrays)."""
+        who = "restore_separable"
+        if unsupported:
+            raise ValueError(f"{who}: {sorted(unsupported)} not accepted (DDNM runs ancestral or DDIM steps with Philox draws over the "
+                             f"whole schedule on an exact, unmasked measurement: no {', '.join(self.DEBLUR_UNSUPPORTED)})")
+        if isinstance(tol, bool) or not isinstance(tol, (int, float, np.integer, np.floating)) or not (0 <= tol < 1):
+            raise ValueError(f"{who}: tol must be a real number in [0, 1), got {tol!r}")
+        if isinstance(eta, bool) or not isinstance(eta, (int, float, np.integer, np.floating)) or eta < 0 or (eta != 0 and not ddim):
+            raise ValueError(f"{who}: eta = {eta!r} needs ddim=True and eta >= 0")
+        C, H, W = self.sample_shape
+        if H % 16 or W % 16 or not (16 <= H <= 256 and 16 <= W <= 256 and 1 <= C <= 8):
+            raise ValueError(f"{who}: the image size must be multiples of 16 in [16, 256] with 1 to 8 channels, this model's is {C} x {H} x {W}")
+        mats = []
+        for what, A, side in (("A_h", A_h, H), ("A_w", A_w, W)):
+            if torch.is_tensor(A):
+                A = A.detach().cpu().numpy()
+            try:
+                A = np.ascontiguousarray(np.asarray(A, dtype=np.float64))
+            except (TypeError, ValueError):
+                raise ValueError(f"{who}: {what} must be a real matrix") from None
+            if A.ndim != 2 or A.shape[1] != side or not np.all(np.isfinite(A)):
+                raise ValueError(f"{who}: {what} must be a finite [n, {side}] matrix, got shape {A.shape}")
+            if A.shape[0] % 4 or not (4 <= A.shape[0] <= side):
+                raise ValueError(f"{who}: {what} must have a multiple of 4 in [4, {side}] rows, got {A.shape[0]}")
+            mats.append(A)
+        h, w = mats[0].shape[0], mats[1].shape[0]
+        if not torch.is_tensor(y) or y.dim() != 4 or list(y.shape[1:]) != [C, h, w] or not y.is_floating_point():
+            raise ValueError(f"{who}: y must be a float [B, {C}, {h}, {w}] tensor, got "
+                             f"{tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
+        if not bool(torch.isfinite(y).all()):
+            raise ValueError(f"{who}: y must be finite")
+        return y.float(), mats[0], mats[1]
+
+    @torch.no_grad()
+    def restore_separable(self, y, A_h, A_w, *, tol=blur.DEFAULT_TOL, respacing=None, ddim=False, eta=0.0, x_T=None, seed=None,
+                          **unsupported):
+        """Zero-shot restoration with DDNM for any separable linear operator: an image [B, C, H, W] with
+        A_h x A_w^T = y per channel, y [B, C, h, w] (in [-1, 1]), A_h [h, H] and A_w [w, W] real matrices -- blur.resize_matrix for
+        the antialiased bicubic reduction, a decimated blur matrix for blur-then-decimate with a known PSF.  The pseudo-inverse is
+        taken per axis with the singular values below tol * s_max dropped (blur.separable_operands); the steps are deblur's.  With
+        full row rank (nothing dropped) A(x_out) = y up to fp32 rounding.  h and w multiples of 4 in [4, H] and [4, W]; H and W
+        multiples of 16 in [16, 256].  respacing, ddim, eta, x_T, seed: as deblur.  solver / noise / early_stop / paste / mask /
+        sigma_y raise ValueError, as do misshapen or non-finite matrices, sizes off that grid, a bad tol or eta and a non-finite or
+        misshapen y, before any device work."""
+        y, A_h, A_w = self._separable_args(y, A_h, A_w, tol, ddim, eta, unsupported)
+        spaced = respacing is not None or ddim or eta != 0
+        sid = int(self.rng_stream_id)
+        m = self._sep_operands(A_h, A_w, tol)
+        yp = []                   # the Python loop's Yp = A+ y, formed at its first step
+
+        def op(x, e, yl, mk, t, tables, seed):
+            if not yp:
+                yp.append(ops.separable_apply_rect(yl, m["Q_h"], m["Q_w"]))
+            ops.p_sample_update_restore_blur_(x, e, m["P_h"], m["P_w"], yp[0], t, **tables, seed=seed, stream_id=sid)
+        return self._ddnm_loop(
+            "restore_separable", y, None, lambda: self._spaced_tables(respacing, ddim, eta) if spaced else (self._tables(), None), x_T,
+            seed, op,
+            lambda plan, x, yl, mk, tables, k_start, seed, use: plan.sample_restore_sep_nhwc(
                 x, yl, m["P_h"], m["P_w"], m["Q_h"], m["Q_w"], tables, k_start, seed=seed, stream_id=sid, use_graph=self.use_graph,
                 timesteps=use))
 

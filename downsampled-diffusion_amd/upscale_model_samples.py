@@ -13,6 +13,10 @@ Loads the checkpoint as generate_model_samples.py does (``--synthetic CONFIG`` b
   * ``--sigma_y S`` (not with ``--dpm_solver``) declares that the low-resolution images carry noise of standard deviation S in the
     model's [-1, 1] scale (S = 2 s / 255 for s uint8 levels): ``model.restore_noisy`` (DDNM+, section 3.10) runs instead, and the
     file names gain ``_sy{S}``;
+  * ``--downsample bicubic`` (DDPM checkpoints; not with ``--dpm_solver`` / ``--sigma_y``): the low-resolution images are antialiased
+    bicubic reductions, what image libraries and the super-resolution benchmarks make, and ``model.super_resolve(downsample="bicubic")``
+    holds that constraint instead of block means (section 3.15); full-size inputs are reduced by the same matrix, and the file names
+    gain ``_bicubic`` behind the scale;
   * batch g draws x_T and its Philox key from ``--seed`` + g.
 
 Writes ``{saved_model}_sr{scale}_{spec}.npy`` through the sampling driver's output stage (utils.OutputStage: float32
@@ -30,15 +34,22 @@ import torch
 from models import DDPM, DownsampleDDPM, Unet
 from utils import CHECKPOINT_DIR, SAMPLE_DIR, OutputStage, get_color_channels, get_model_state_dict, load_checkpoint_file
 from utils import synthetic as syn
-from utils.restoration_metrics import pool
+from utils.restoration_metrics import DOWNSAMPLES, pool, resize
 
 
-def main():
+def output_base(saved_model, scale, downsample, spec):
+    """the output files' name without directory and extension"""
+    return f"{saved_model}_sr{scale}{'_bicubic' if downsample == 'bicubic' else ''}_{spec}"
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description="Upscale images with a trained DDPM / dDDPM checkpoint (DDNM super-resolution).")
     ap.add_argument("--saved_model", default="celeba_x2")
     ap.add_argument("--synthetic", default=None, help="JSON config file: use closed-form synthetic weights, no checkpoint")
     ap.add_argument("--images", required=True, help="uint8 .npy [N, h, w, C]: low-resolution, or full-resolution to be pooled first")
     ap.add_argument("--scale", type=int, default=4)
+    ap.add_argument("--downsample", default="mean", choices=DOWNSAMPLES,
+                    help="what the low-resolution images are: block means (default) or antialiased bicubic reductions")
     ap.add_argument("--timestep_respacing", default="", help='run K of the T steps: "ddimN", "N" or "n1,n2,..." sections')
     ap.add_argument("--use_ddim", action="store_true", help="DDIM steps instead of ancestral ones")
     ap.add_argument("--eta", type=float, default=0.0, help="DDIM noise scale (0: deterministic)")
@@ -49,7 +60,9 @@ def main():
     ap.add_argument("--batch_size", type=int, default=32)
     ap.add_argument("--seed", type=int, default=1234, help="base seed: batch g draws from seed + g")
     ap.add_argument("--out_dir", default=None)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.downsample == "bicubic" and (args.dpm_solver or args.sigma_y != 0.0):
+        ap.error("--downsample bicubic runs ancestral or DDIM steps on an exact measurement: not with --dpm_solver or --sigma_y")
     if args.dpm_solver and (args.use_ddim or args.eta != 0.0):
         ap.error("--dpm_solver is its own deterministic update: it cannot be combined with --use_ddim or --eta")
     if args.eta < 0 or (args.eta != 0.0 and not args.use_ddim):
@@ -62,7 +75,11 @@ def main():
         ap.error("--sigma_y needs a chain that draws: ancestral steps, or --use_ddim with --eta > 0")
     if args.batch_size < 1 or args.scale < 2:
         ap.error("--batch_size must be >= 1 and --scale >= 2")
+    return args
 
+
+def main():
+    args = parse_args()
     device = "cuda:0"
     torch.cuda.set_device(0)
     if args.synthetic:
@@ -95,7 +112,7 @@ def main():
         raise SystemExit(f"--images: expected uint8 [N, {size // s}, {size // s}, {c}] or [N, {size}, {size}, {c}], got {imgs.dtype} {imgs.shape}")
     y_all = torch.from_numpy(imgs.astype(np.float32)).permute(0, 3, 1, 2) / 255 * 2 - 1
     if imgs.shape[1] == size:
-        y_all = pool(y_all, s)
+        y_all = resize(y_all, s, device) if args.downsample == "bicubic" else pool(y_all, s)
     n = y_all.shape[0]
     lowres = ((y_all + 1) * 127.5).round().clamp(0, 255).permute(0, 2, 3, 1).numpy().astype(np.uint8)
 
@@ -105,6 +122,8 @@ def main():
         kw = dict(respacing=args.timestep_respacing or None, solver="dpm++2m")
     else:
         kw = dict(respacing=args.timestep_respacing or None, ddim=args.use_ddim, eta=args.eta)
+        if args.downsample == "bicubic":
+            kw.update(downsample="bicubic")
     print(f"Upscaling {n} images x{s} ({spec} steps) with {args.saved_model}.")
     stage = OutputStage()
     t0 = time.time()
@@ -122,7 +141,7 @@ def main():
 
     out_dir = args.out_dir or SAMPLE_DIR
     os.makedirs(out_dir, exist_ok=True)
-    base = os.path.join(out_dir, f"{args.saved_model}_sr{s}_{spec}")
+    base = os.path.join(out_dir, output_base(args.saved_model, s, args.downsample, spec))
     np.save(base + ".npy", np.concatenate(batches).astype(np.float32), allow_pickle=False)
     np.save(base + "_lowres.npy", lowres, allow_pickle=False)
     print(f"Upscaled images saved to {base}.npy, low-resolution inputs to {base}_lowres.npy")

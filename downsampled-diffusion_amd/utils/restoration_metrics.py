@@ -18,6 +18,7 @@ DEBLUR_TASK = "deblur"          # evaluate_restoration's fourth task (section 3.
 BLUR_KERNELS = ("uniform", "gauss", "aniso")
 METHODS = ("repaint", "ddnm")
 GRAY_WEIGHTS = {"mean": (1.0 / 3.0, 1.0 / 3.0, 1.0 / 3.0), "luma": (0.299, 0.587, 0.114)}     # DDPM.colorize's two operators
+DOWNSAMPLES = ("mean", "bicubic")     # task "sr": block means (section 3.6) or the antialiased bicubic reduction (section 3.15)
 
 
 # ------------------------------------------------------------------ degradations
@@ -51,6 +52,22 @@ def load_mask(path, n, h, w, c):
 def pool(x, scale):
     """scale x scale average pooling of [N, C, H, W]: the degradation of the super-resolution task (A of section 3.6)."""
     return torch.nn.functional.avg_pool2d(x, scale)
+
+
+def resize_matrices(h, w, scale):
+    """(A_h [h / scale, h], A_w [w / scale, w]) fp32: the antialiased bicubic reduction of section 3.15, one matrix per axis"""
+    from models.diffusion import blur
+    return tuple(torch.tensor(blur.resize_matrix(n, scale), dtype=torch.float32) for n in (h, w))
+
+
+def resize(x, scale, device, batch_size=256):
+    """the antialiased bicubic reduction by ``scale`` of [N, C, H, W] (A of section 3.15), on ``device`` through
+    ops.separable_apply_rect: what DDPM.super_resolve(downsample="bicubic") inverts.  Returns a CPU tensor [N, C, H/scale, W/scale]."""
+    from ddk import ops
+    A_h, A_w = (m.to(device) for m in resize_matrices(x.shape[2], x.shape[3], scale))
+    out = [ops.nhwc_to_nchw(ops.separable_apply_rect(ops.nchw_to_nhwc(x[i:i + batch_size].to(device).float().contiguous()), A_h, A_w)).cpu()
+           for i in range(0, x.shape[0], batch_size)]
+    return torch.cat(out)
 
 
 def gray(x, weights):
@@ -116,7 +133,7 @@ def _score(ops, cand_u8, ref_u8, hidden, device):
 
 @torch.no_grad()
 def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234, mask="center", scale=None, method=None, sr_mask=None,
-                         dpm_solver=False, sigma_y=0.0, **chain):
+                         dpm_solver=False, sigma_y=0.0, downsample="mean", **chain):
     """Degrade, restore and score ``images_uint8`` (uint8 [N, H, W, C] of the model's size).
 
     task "inpaint": ``mask`` is one of MASKS or a {0, 1} tensor broadcastable to [N, 1|C, H, W] (1 = known); ``chain`` goes to
@@ -151,12 +168,20 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
     itself, and "pinv", A+ y clipped to [-1, 1] (the truncated pseudo-inverse alone, no network).  consistency / consistency_u8:
     max |A(x_out) - y| in uint8 levels, which the truncation keeps above zero.  The returned method is "ddnm_blur", and "kernel" and
     "tol" are returned.
+    downsample "bicubic" (task "sr" on a pixel model, without sr_mask, dpm_solver or sigma_y; section 3.15): the images are reduced
+    by the antialiased bicubic matrix (``resize``) instead of pooled and ``model.super_resolve(downsample="bicubic")`` restores them.
+    The baselines stay (replicate, bicubic upsampling); consistency / consistency_u8 are max |A(x_out) - y| in uint8 levels with that
+    matrix, and "downsample" is returned.  The default, "mean", is the result without the argument.
     Batch g draws x_T and its Philox key from seed + g, as the sampling CLIs do.
 
     "method" and "unet_forwards" (UNet forwards per image: the chain's steps; the batch shares each forward) are returned too.
     Returns {"n_images", "methods": {name: {"psnr": [N], "ssim": [N], ...}}, "images": {name: uint8 [N, H, W, C]}} and, for "sr",
     "consistency" / "consistency_u8" [N]; "restored" is the model's entry."""
     from ddk import ops
+    if downsample not in DOWNSAMPLES:
+        raise ValueError(f"unknown downsample {downsample!r}: one of {DOWNSAMPLES}")
+    if downsample != "mean" and (task != "sr" or sr_mask is not None or dpm_solver or sigma_y):
+        raise ValueError("downsample 'bicubic' belongs to task 'sr' without a mask, dpm_solver or sigma_y")
     if task == DEBLUR_TASK:
         if method not in (None, "ddnm") or dpm_solver or sigma_y or sr_mask is not None or scale is not None:
             raise ValueError("task 'deblur' has one method, ddnm on ancestral or DDIM steps, and no mask, scale or sigma_y")
@@ -219,7 +244,15 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
         scale = 4 if scale is None else int(scale)
         if scale < 2 or h % scale or w % scale:
             raise ValueError(f"scale {scale} must be >= 2 and divide the image size {h} x {w}")
-        y_all = pool(x_all, scale)
+        if downsample == "bicubic":
+            A_h, A_w = resize_matrices(h, w, scale)
+            degrade = lambda x: torch.einsum("ih,bchw,jw->bcij", A_h, x, A_w)
+            y_all = resize(x_all, scale, device)
+            chain = dict(chain, downsample="bicubic")
+            extra["downsample"] = "bicubic"
+        else:
+            degrade = lambda x: pool(x, scale)
+            y_all = degrade(x_all)
         y_meas = y_all + noise(y_all) if sigma_y else y_all
         extra["unet_forwards"] = K
         my_all = None
@@ -252,8 +285,8 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
         extra["sigma_y"] = sigma_y
     elif task == "sr":
         meas = 1.0 if my_all is None else my_all      # the constraint holds where y is measured
-        extra["consistency"] = (((pool(x_out, scale) - y_all) * meas).abs().amax(dim=(1, 2, 3)) * 127.5).double().numpy()
-        extra["consistency_u8"] = (((pool(from_u8(images["restored"]), scale) - y_all) * meas).abs().amax(dim=(1, 2, 3)) * 127.5).double().numpy()
+        extra["consistency"] = (((degrade(x_out) - y_all) * meas).abs().amax(dim=(1, 2, 3)) * 127.5).double().numpy()
+        extra["consistency_u8"] = (((degrade(from_u8(images["restored"])) - y_all) * meas).abs().amax(dim=(1, 2, 3)) * 127.5).double().numpy()
     methods = {name: _score(ops, img, ref, hidden, device) for name, img in images.items()}
     return dict(n_images=n, method=method + ("_dpmpp2m" if dpm_solver else "_plus" if sigma_y else ""), methods=methods, images={k: v.numpy() for k, v in images.items()}, **extra)
 

@@ -376,6 +376,16 @@ int ddk_p_sample_update_restore_gray(float* x, const float* eps_hat, const float
  * run to run.  out may be `in`.  H and W multiples of 16 in [16, 256], channels in 1..8, B <= 65535; all four pointers 16-byte aligned.
  * Anything else is DDK_ERR_ARG and runs no kernel. */
 int ddk_separable_apply(const float* in, const float* L, const float* R, float* out, int B, int H, int W, int channels, ddk_stream_t s);
+/* The size-changing form: out[b, :, :, c] = L . in[b, :, :, c] . R^T with L [Ho][Hi] and R [Wo][Wi], row-major;
+ * in is [B][Hi][Wi][channels], out [B][Ho][Wo][channels] and scratch [B][Ho][Wi][channels], which receives T = L . in (the rows product
+ * runs first).  With the matrices of an antialiased bicubic reduction it makes the small image, with their pseudo-inverses it forms A+ y.
+ * The two products have different shapes, so nothing runs in place: in, scratch and out must not overlap.  The kernels are
+ * ddk_separable_apply's tile with guards for a contraction length that is no multiple of 16, a partial last tile and a partial last
+ * strip; one fixed summation order per output, no atomics: bit-identical run to run, and with Hi = Ho, Wi = Wo to ddk_separable_apply.
+ * Hi, Wi, Ho and Wo multiples of 4 in [4, 256], channels in 1..8, B <= 65535; all five pointers 16-byte aligned.  Anything else is
+ * DDK_ERR_ARG and runs no kernel. */
+int ddk_separable_apply_rect(const float* in, const float* L, const float* R, float* out, float* scratch, int B, int Hi, int Wi, int Ho, int Wo,
+                             int channels, ddk_stream_t s);
 /* One DDNM deblurring step on its own (ddk_sampler_run_restore_blur): A(X) = A_h X A_w^T per channel, P_h [H][H]
  * and P_w [W][W] the symmetric projections A+ A of the two axes, Yp = A+ y in x's layout.  Per sample b with row t[b] of the tables:
  *   x0  = clamp(c_recip x - c_recipm1 eps_hat, -1, 1);  s = t > 0 ? sigma : 0;
@@ -672,6 +682,15 @@ size_t ddk_sampler_restore_blur_workspace_bytes(const ddk_unet* u, int B, int H,
 int ddk_sampler_restore_blur_tail_parts(const ddk_unet* u, int B, int H, int W);
 int ddk_sampler_run_restore_blur(const ddk_sampler_args* a, const int64_t* timestep_map, const float* P_h, const float* P_w, const float* Q_h,
                                  const float* Q_w, const float* y, ddk_stream_t s);
+/* DDNM for any separable operator A(X) = A_h X A_w^T with A_h [h][H] and A_w [w][W] of full or truncated row rank -- antialiased
+ * bicubic reduction, blur-then-decimate.  ddk_sampler_run_restore_blur with a measurement of its own size: y is
+ * [B][h][w][channels], Q_h [H][h] and Q_w [W][w] the pseudo-inverses, P_h [H][H] and P_w [W][W] the projections; Yp = Q_h y Q_w^T is
+ * formed by ddk_separable_apply_rect before the first step and outside any captured one, with the workspace's T as its scratch.  The
+ * steps, the chain kind, the workspace (ddk_sampler_restore_blur_workspace_bytes) and the tail query are the deblurring entry's.  h and
+ * w multiples of 4 in [4, H] and [4, W], else DDK_ERR_ARG; with h = H and w = W the result is ddk_sampler_run_restore_blur's bit for
+ * bit. */
+int ddk_sampler_run_restore_sep(const ddk_sampler_args* a, const int64_t* timestep_map, const float* P_h, const float* P_w, const float* Q_h,
+                                const float* Q_w, const float* y, int h, int w, ddk_stream_t s);
 /* Drops the plan's cached sampler and likelihood-sweep graphs and shift table (waits for the device when graphs exist). */
 int ddk_sampler_invalidate(ddk_unet* u);
 /* Drops only the cached graphs (and shift table) that live in / point into `workspace`, after waiting for the launches of

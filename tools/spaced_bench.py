@@ -36,7 +36,13 @@ ancestral step of the same model's respaced "50" chain, timed alternately the sa
 respaced chain, timed alternately the same way, on a 128-wide 3-channel pixel DDPM with 32 x 32 images at B = 32 ("50" steps; the
 one-launch form of the update) and on a 32-wide one with 256 x 256 images at B = 8 ("20" steps; the two-launch form).  Every
 deblurring step ends in the unfused tail (the operator couples a whole plane), so the ratio holds the plain tail's extra launch as
-well as the two matrix products."""
+well as the two matrix products.
+
+--restore-sep: the same two models with the size-changing operator of DESIGN.md section 3.15, antialiased bicubic reduction by 4
+(y 8 x 8 and 64 x 64): the cost of a step of the restore_sep chain against an ancestral step, timed alternately the same way (the step
+is the deblurring step: its figure is expected), and the one-time cost of forming Yp = Q_h y Q_w^T with separable_apply_rect, the
+median of five timings of 200 back-to-back calls each between two device events (two launches per call; where the
+kernels are shorter than a launch takes to enqueue, the figure is the enqueue's)."""
 import argparse
 import json
 import os
@@ -69,6 +75,7 @@ def main():
     ap.add_argument("--restore-noisy", action="store_true", help="DDNM+ step (n = 1, 2; sigma_y 0.1) against an ancestral step, respacing 50")
     ap.add_argument("--restore-gray", action="store_true", help="colourisation step (n = 1, 2; luma) against an ancestral step, respacing 50, on a 3-channel pixel model")
     ap.add_argument("--restore-blur", action="store_true", help="deblurring step (gauss) against an ancestral step on 3x32x32 (B 32) and 3x256x256 (B 8) pixel models")
+    ap.add_argument("--restore-sep", action="store_true", help="bicubic x4 restore_sep step against an ancestral step, and the cost of forming Yp, on the --restore-blur models")
     ap.add_argument("--restore-solver", action="store_true", help="DDNM step on the 2M chain (n = 1 center mask, n = 2) against a 2M step, logsnr20")
     args = ap.parse_args()
     torch.cuda.set_device(0)
@@ -76,6 +83,8 @@ def main():
         return restore_gray_ab()
     if args.restore_blur:
         return restore_blur_ab()
+    if args.restore_sep:
+        return restore_sep_ab()
     cfg = bench.cfg4()
     model = DownsampleDDPM(cfg, Unet(cfg), DEV, 3)
     model.load_state_dict(syn.fill_state_dict(model.state_dict(), skip=syn.SCHEDULE_KEYS))
@@ -386,6 +395,69 @@ def restore_blur_ab():
         res["per_case"][name] = {"ancestral_ms_per_step": round(a, 4), "blur_ms_per_step": round(r, 4), "blur_over_ancestral": round(r / a, 4),
                                  "ancestral_min_max_ms": [round(min(anc), 4), round(max(anc), 4)],
                                  "blur_min_max_ms": [round(min(rst), 4), round(max(rst), 4)], "steps": K}
+        del model, plan
+    print(json.dumps(res), flush=True)
+
+
+def restore_sep_ab():
+    """restore_blur_ab's models and chains with the bicubic x4 operator, and the cost of forming Yp from the small y"""
+    from models.diffusion import blur
+    scale = 4
+    res = {"shape": f"pixel DDPMs, T={T}, restore_sep step (antialiased bicubic x{scale}, tol 3e-2) vs ancestral step of the same respaced chain; "
+                    "form_yp: separable_apply_rect(y, Q_h, Q_w), per call", "reps": REPS, "per_case": {}}
+    for name, chan, size, b, K in (("3x32x32_B32_chan128_from_8x8", 128, 32, 32, 50), ("3x256x256_B8_chan32_from_64x64", 32, 256, 8, 20)):
+        cfg = dict(unet_chan=chan, unet_in=3, unet_dims=(1, 2, 2, 2), unet_dropout=0.0, image_size=size, T=T, loss_type="simple",
+                   beta_schedule="linear", loss_flat="sum")
+        model = DDPM(cfg, Unet(cfg), DEV, 3)
+        model.load_state_dict(syn.fill_state_dict(model.state_dict(), skip=syn.SCHEDULE_KEYS))
+        model = model.to(DEV).eval()
+        plan = model.latent_model.plan()
+        x0 = ops.randn((b, size, size, 3), DEV, seed=1234, step=T, stream_id=0)
+        x = x0.clone()
+        A = blur.resize_matrix(size, scale)
+        m = {k: v.to(DEV) for k, v in zip(("A_h", "A_w", "Q_h", "Q_w", "P_h", "P_w"), blur.separable_operands(A, A)[:6])}
+        y = ops.separable_apply_rect(x0.clamp(-1, 1), m["A_h"], m["A_w"])
+        sp, use = model._spaced_tables(str(K), False, 0.0)
+
+        def chain(kind):
+            x.copy_(x0)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            if kind == "anc":
+                plan.sample_nhwc(x, sp, K - 1, 0, seed=1234, stream_id=0, timesteps=use)
+            else:
+                plan.sample_restore_sep_nhwc(x, y, m["P_h"], m["P_w"], m["Q_h"], m["Q_w"], sp, K - 1, seed=1234, stream_id=0, timesteps=use)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3
+
+        def form_yp(calls=200):
+            out = torch.empty_like(x0)
+            ops.separable_apply_rect(y, m["Q_h"], m["Q_w"], out=out)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(calls):
+                ops.separable_apply_rect(y, m["Q_h"], m["Q_w"], out=out)
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) / calls
+
+        with torch.no_grad():
+            t_settle = time.perf_counter()
+            while time.perf_counter() - t_settle < 2.0:
+                chain("anc")
+            chain("sep")                                 # both chains' graphs are captured outside the timed calls
+            anc, rst = [], []
+            for _ in range(REPS):
+                anc.append(chain("anc") / K)
+                rst.append(chain("sep") / K)
+            yp = [form_yp() for _ in range(REPS)]
+        assert torch.isfinite(x).all() and plan.restore_blur_tail_parts(b, size, size) == 0
+        a, r = statistics.median(anc), statistics.median(rst)
+        res["per_case"][name] = {"ancestral_ms_per_step": round(a, 4), "sep_ms_per_step": round(r, 4), "sep_over_ancestral": round(r / a, 4),
+                                 "ancestral_min_max_ms": [round(min(anc), 4), round(max(anc), 4)],
+                                 "sep_min_max_ms": [round(min(rst), 4), round(max(rst), 4)], "steps": K,
+                                 "form_yp_ms": round(statistics.median(yp), 4), "form_yp_min_max_ms": [round(min(yp), 4), round(max(yp), 4)],
+                                 "form_yp_over_step": round(statistics.median(yp) / r, 4)}
         del model, plan
     print(json.dumps(res), flush=True)
 
