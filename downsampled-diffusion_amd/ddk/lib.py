@@ -172,6 +172,10 @@ SIGNATURES = {
     "ddk_vlb_terms": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _LL, _P, _SZ, _P]),
     "ddk_image_metrics_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "ddk_image_metrics": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
+    "ddk_knn_radii_workspace_bytes": (_SZ, [_I]),
+    "ddk_knn_radii": (_I, [_P, _I, _I, _I, _P, _P, _SZ, _P]),
+    "ddk_manifold_members_workspace_bytes": (_SZ, [_I, _I]),
+    "ddk_manifold_members": (_I, [_P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _SZ, _P]),
     "ddk_unet_create": (_P, [C.POINTER(UnetConfig)]),
     "ddk_unet_destroy": (None, [_P]),
     "ddk_unet_num_slots": (_I, [_P]),

@@ -973,6 +973,92 @@ def image_metrics(a, b, mask=None):
     return dict(psnr=psnr, ssim=ssim.cpu(), mse=mse, sq_sum=sq_sum, count=count)
 
 
+MANIFOLD_MAX_K = 7            # csrc/manifold.hip keeps a row's 8 smallest distances: k + 1 <= 8
+MANIFOLD_TILE = 128           # rows (and columns) of a workgroup's distance tile
+
+
+def _manifold_features(what, name, t):
+    """The checks every feature matrix passes before any device work; returns it with D zero-padded to a multiple of 4."""
+    if not torch.is_tensor(t) or t.dtype != torch.float32:
+        raise ValueError(f"{what}: {name} must be a float32 tensor, got {getattr(t, 'dtype', type(t))}")
+    if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError(f"{what}: {name} must be a non-empty [N, D] matrix, got {tuple(t.shape)}")
+    if not t.is_cuda:
+        raise L.DDKError(f"{what}: HIP kernels need ROCm device tensors; there is no CPU fallback")
+    if not bool(torch.isfinite(t).all()):
+        raise ValueError(f"{what}: {name} holds non-finite features")
+    pad = -t.shape[1] % 4
+    if pad:                                        # zero columns change no norm and no dot product (the `spatial` features: D = 2023)
+        t = torch.nn.functional.pad(t, (0, pad))
+    return t.contiguous()
+
+
+def _manifold_radii_arg(what, name, r, n, device):
+    if r is None:
+        return None
+    if not torch.is_tensor(r) or r.dtype != torch.float32:
+        raise ValueError(f"{what}: {name} must be a float32 tensor or None, got {getattr(r, 'dtype', type(r))}")
+    if tuple(r.shape) != (n,):
+        raise ValueError(f"{what}: {name} must be [{n}], one radius per row, got {tuple(r.shape)}")
+    if not r.is_cuda:
+        raise L.DDKError(f"{what}: HIP kernels need ROCm device tensors; there is no CPU fallback")
+    return r.contiguous()
+
+
+def manifold_radii_splits(n):
+    """How many workgroups share the columns of one 128-row block in manifold_radii at this N (from the entry's workspace size)."""
+    nbytes = L.load().ddk_knn_radii_workspace_bytes(n)
+    return (nbytes // 4 // n - 1) // (MANIFOLD_MAX_K + 1)
+
+
+def manifold_radii(x, k=3):
+    """Squared distance of every row of the float32 device matrix x [N, D] to its k-th nearest neighbour: element k of the row's
+    sorted distances to all N rows, itself included (the reference ManifoldEstimator.manifold_radii with nhood_sizes=(k,)).
+    Returns a float32 [N] device tensor.  DESIGN.md section 3.16."""
+    if not isinstance(k, int) or not 1 <= k <= MANIFOLD_MAX_K:
+        raise ValueError(f"manifold_radii: k must be an integer in 1..{MANIFOLD_MAX_K}, got {k!r}")
+    if torch.is_tensor(x) and x.dim() == 2 and x.shape[0] < k + 1:
+        raise ValueError(f"manifold_radii: N must be at least k + 1 = {k + 1}, got {x.shape[0]}")
+    x = _manifold_features("manifold_radii", "x", x)
+    n, d = x.shape
+    lib = L.load()
+    radii = torch.empty((n,), device=x.device, dtype=torch.float32)
+    nbytes = lib.ddk_knn_radii_workspace_bytes(n)
+    ws = _ws(x.device, nbytes, "manifold")
+    L.check(lib.ddk_knn_radii(L.ptr(x), n, d, k, L.ptr(radii), L.ptr(ws), nbytes, L.stream()), "knn_radii")
+    return radii
+
+
+def manifold_members(a, ra, b, rb):
+    """One pass over the distances between the rows of a [Na, D] and b [Nb, D] (float32 device tensors):
+    a_in[i] = some row j of b has d(a_i, b_j) <= rb[j], b_in[j] = some row i of a has d(a_i, b_j) <= ra[i].
+    ra [Na] / rb [Nb] are float32 device tensors; with ra None b_in is None, with rb None a_in is None.
+    Returns (a_in, b_in), bool device tensors.  DESIGN.md section 3.16."""
+    what = "manifold_members"
+    if ra is None and rb is None:
+        raise ValueError(f"{what}: neither ra nor rb given: nothing to compute")
+    for name, t in (("a", a), ("b", b)):                                  # dtype and shape of both before either touches the device
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise ValueError(f"{what}: {name} must be a float32 tensor, got {getattr(t, 'dtype', type(t))}")
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1]:
+        raise ValueError(f"{what}: a and b must be [Na, D] and [Nb, D] with one D, got {tuple(a.shape)} and {tuple(b.shape)}")
+    na, nb = a.shape[0], b.shape[0]
+    for name, r, n in (("ra", ra, na), ("rb", rb, nb)):
+        if r is not None and (not torch.is_tensor(r) or r.dtype != torch.float32 or tuple(r.shape) != (n,)):
+            raise ValueError(f"{what}: {name} must be a float32 [{n}] tensor or None, got "
+                             f"{getattr(r, 'dtype', type(r))} {tuple(getattr(r, 'shape', ()))}")
+    a, b = _manifold_features(what, "a", a), _manifold_features(what, "b", b)
+    ra, rb = _manifold_radii_arg(what, "ra", ra, na, a.device), _manifold_radii_arg(what, "rb", rb, nb, a.device)
+    lib = L.load()
+    a_in = torch.empty((na,), device=a.device, dtype=torch.uint8) if rb is not None else None
+    b_in = torch.empty((nb,), device=a.device, dtype=torch.uint8) if ra is not None else None
+    nbytes = lib.ddk_manifold_members_workspace_bytes(na, nb)
+    ws = _ws(a.device, nbytes, "manifold")
+    L.check(lib.ddk_manifold_members(L.ptr(a), L.ptr(ra), na, L.ptr(b), L.ptr(rb), nb, a.shape[1], L.ptr(a_in), L.ptr(b_in), L.ptr(ws),
+                                     nbytes, L.stream()), "manifold_members")
+    return (a_in.bool() if a_in is not None else None), (b_in.bool() if b_in is not None else None)
+
+
 # ================================================================== training path (backward kernels)
 CONV4X4_S2 = 4
 _scratch = {}

@@ -9,7 +9,10 @@ printed as null.  Extensions:
   * ``--seed S`` runs the native likelihood sweep (in-kernel Philox draws, batch g keyed by S + g; one C call per batch,
     graph-replayed steps); without it the reference's per-step loop with torch's generator runs;
   * ``--max_batches N`` stops after N test batches; ``--json OUT`` also writes the metrics to a file;
-  * ``--synthetic CONFIG`` builds deterministic synthetic weights when no checkpoint exists (offline boxes).
+  * ``--synthetic CONFIG`` builds deterministic synthetic weights when no checkpoint exists (offline boxes);
+  * ``--sample_acts S.npz --ref_acts R.npz`` (both or neither): Inception activations of the samples and of the reference set,
+    computed elsewhere; the five sample-metric keys are then filled from them (utils/sample_metrics.py), null only where a file
+    lacks the input a metric needs.
 """
 import argparse
 import json
@@ -21,6 +24,7 @@ import torch
 from models import DDPM, DownsampleDDPM, Unet
 from utils import (CHECKPOINT_DIR, DATA_DIR, compute_test_losses, get_color_channels, get_dataloader, get_model_state_dict,
                    load_checkpoint_file)
+from utils.sample_metrics import sample_metrics
 from utils import synthetic as syn
 
 SAMPLE_METRICS = ('is', 'fid', 'sfid', 'precision', 'recall')
@@ -35,7 +39,11 @@ def main():
     ap.add_argument("--max_batches", type=int, default=None, help="stop after this many test batches")
     ap.add_argument("--synthetic", default=None, help="JSON config file: use closed-form synthetic weights, no checkpoint")
     ap.add_argument("--json", default=None, help="also write the metrics to this file")
+    ap.add_argument("--sample_acts", default=None, help=".npz of the samples' Inception activations (pool_3, spatial, softmax)")
+    ap.add_argument("--ref_acts", default=None, help=".npz of the reference set's activations, or its mu / sigma / mu_s / sigma_s")
     args = ap.parse_args()
+    if (args.sample_acts is None) != (args.ref_acts is None):
+        ap.error("--sample_acts and --ref_acts go together")
 
     device = 'cuda'
     step = 0
@@ -82,9 +90,17 @@ def main():
     print(f'Test loss time: {time.time() - time_start}')
     metrics['vlb'] = vlb
     metrics['L_simple'] = L_simple
-    print('Sample metrics (IS, FID, sFID, precision, recall): the TF-Inception evaluator is out of scope; reported as null.')
-    for k in SAMPLE_METRICS:
-        metrics[k] = None
+    if args.sample_acts is None:
+        print('Sample metrics (IS, FID, sFID, precision, recall): the TF-Inception evaluator is out of scope; reported as null.')
+        for k in SAMPLE_METRICS:
+            metrics[k] = None
+    else:
+        print(f'Sample metrics from the activations {args.sample_acts} against {args.ref_acts}')
+        time_start = time.time()
+        scores = sample_metrics(args.ref_acts, args.sample_acts)
+        print(f'Sample metrics time: {time.time() - time_start}')
+        for k in SAMPLE_METRICS:
+            metrics[k] = scores[k]
 
     # Display resulting metrics
     print('\nResults:')

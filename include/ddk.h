@@ -438,6 +438,22 @@ int ddk_sq_err_sum(const float* a, const float* b, float* per_sample, int B, lon
 size_t ddk_image_metrics_workspace_bytes(int N, int H, int W, int C);
 int ddk_image_metrics(const uint8_t* a, const uint8_t* b, const uint8_t* mask, int N, int H, int W, int C,
                       unsigned long long* sq_sum_count, float* ssim, void* workspace, size_t workspace_bytes, ddk_stream_t s);
+/* k-nearest-neighbour manifold estimate behind precision / recall of generated samples (reference utils/evaluator.py:159-383,
+ * ManifoldEstimator and DistanceBlock) on fp32 feature rows [N][D], rows contiguous and 16-byte aligned,
+ * D % 4 == 0 (zero columns change no distance: pad).  Squared distance, everywhere: d(u, v) = max((|u|^2 - 2 u.v) + |v|^2, 0) in
+ * fp32, the reference's _batch_pairwise_distances; the dot products are fp32 MFMA fmaf chains in a fixed order of k.  No distance
+ * is ever stored; the same bits from run to run.
+ *   ddk_knn_radii: radii[i] = element k (from 0) of the ascending distances of row i to every row of x, itself included: the
+ *     reference's np.partition(row, arange(k + 1))[k] with nhood_sizes = (k,).  1 <= k <= 7, N >= k + 1.
+ *   ddk_manifold_members: one pass over the Na x Nb distances; a_in[i] = any_j d(a_i, b_j) <= rb[j], b_in[j] = any_i d(a_i, b_j) <= ra[i]
+ *     (uint8 0 / 1).  A null ra skips b_in and a null rb skips a_in (the skipped output may be null and is not written).
+ * workspace: the matching _workspace_bytes, 16-byte aligned.  ddk_knn_radii's is (N + splits N 8) floats, where splits is the number
+ * of workgroups that share the columns of one block of 128 rows. */
+size_t ddk_knn_radii_workspace_bytes(int N);
+int ddk_knn_radii(const float* x, int N, int D, int k, float* radii, void* workspace, size_t workspace_bytes, ddk_stream_t s);
+size_t ddk_manifold_members_workspace_bytes(int Na, int Nb);
+int ddk_manifold_members(const float* a, const float* ra, int Na, const float* b, const float* rb, int Nb, int D, uint8_t* a_in,
+                         uint8_t* b_in, void* workspace, size_t workspace_bytes, ddk_stream_t s);
 
 /* ------------------------------------------------------------------ whole-UNet plan (unet.py:74-104, eval mode) */
 typedef struct ddk_unet_config {
