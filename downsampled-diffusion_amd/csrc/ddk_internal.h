@@ -333,6 +333,13 @@ struct BlurOps {
     const float *qh, *qw;         // host side only: A+ of the two axes, from which the chain entry forms Yp = Q_h y Q_w^T before the first step
 };
 static_assert(sizeof(BlurOps) <= sizeof(InpaintOps), "BlurOps shares the Inpaint operands' storage: StepRule must not grow");
+// DDNM compressed sensing: the pixel permutation, the scratch form's T and the number of measured coefficients
+struct HadamardOps {
+    const int32_t* perm;          // [H W]: a[j] = X[perm[j]], shared by channels and batch; read as perm[j] & (H W - 1)
+    float* tmp;                   // T [B][C][H W]; read and written only when a plane is too large for the plane form (256 x 256)
+    int m;                        // coefficients 0 .. m - 1 of every plane are measured: rst.y is [B][C][m]
+};
+static_assert(sizeof(HadamardOps) <= sizeof(InpaintOps), "HadamardOps shares the Inpaint operands' storage: StepRule must not grow");
 constexpr uint32_t INPAINT_Z2_BIT = 0x40000000u;   // Philox stream of the known region's draw: stream_id | this
 constexpr uint32_t INPAINT_Z3_BIT = 0x20000000u;   // ... and of the jump's: stream_id | this (so stream_id < 2^29)
 // zero-shot super-resolution (DDNM for A = n x n average pooling): the low-resolution image and the block
@@ -381,14 +388,18 @@ enum class StepKind {
     RestoreGray,  // DDNM / DDNM+ for A = mask o pool_n o grey_w on a 3-channel map, n in {1, 2, 4, 8}: RestoreNoisy's step
                   // with the block mean replaced by the weighted mean of the n x n x 3 group and the correction spread by A+'s per-channel
                   // factor (rst.gray names w; rst.mask may be null at every n): c_recip .. sigma, nsy, rst; Philox only
-    RestoreBlur   // DDNM for a separable blur A(X) = A_h X A_w^T per channel: x0' = (x0 - P_h x0 P_w^T) + Yp with the
+    RestoreBlur,  // DDNM for a separable blur A(X) = A_h X A_w^T per channel: x0' = (x0 - P_h x0 P_w^T) + Yp with the
                   // projections P = A+ A of the two axes and Yp = A+ y, then Restore's update.  The only plane-wide kind: separable.hip's
                   // kernels, never the fused tail: c_recip .. sigma, blr, rst.y = Yp (x's layout), rst.H, rst.W; Philox only
+    RestoreHadamard  // DDNM compressed sensing, A = the first m rows of the orthonormal Walsh-Hadamard transform of the permuted plane
+                  // (DESIGN.md section 3.17): x0' = A^T y + (I - A^T A) x0, a select between two transforms, then Restore's update.
+                  // Plane-wide: hadamard.hip's kernels, never the fused tail: c_recip .. sigma, had, rst.y = y [B][C][m], rst.H, rst.W;
+                  // Philox only
                   // (last, so that the kinds above keep their values and their kernels' names)
 };
 inline bool restore_kind(StepKind k) {       // the kinds whose step carries a DDNM constraint (RestoreOps)
     return k == StepKind::Restore || k == StepKind::RestoreMasked || k == StepKind::RestoreMultistep || k == StepKind::RestoreNoisy ||
-           k == StepKind::RestoreGray || k == StepKind::RestoreBlur;
+           k == StepKind::RestoreGray || k == StepKind::RestoreBlur || k == StepKind::RestoreHadamard;
 }
 struct StepRule {
     StepKind kind;
@@ -406,6 +417,7 @@ struct StepRule {
         InpaintOps inp;
         NoisyTables nsy;          // RestoreNoisy, RestoreGray
         BlurOps blr;              // RestoreBlur
+        HadamardOps had;          // RestoreHadamard
     };
     const VlbStep* vlb;           // host side only
     RestoreOps rst;
@@ -426,7 +438,7 @@ struct ChainHooks {
     uint32_t stream_id;
 };
 // the unfused tail's last kernel, given eps_hat in memory: the rule's update of x (Ancestral, Multistep, Inpaint, Restore, RestoreMasked,
-// RestoreMultistep, RestoreNoisy, RestoreGray, RestoreBlur) or the sweep's
+// RestoreMultistep, RestoreNoisy, RestoreGray, RestoreBlur, RestoreHadamard) or the sweep's
 // reduction of the step's terms (Vlb); `who` names the caller in messages
 int p_update(const StepRule& r, const float* eps_hat, const int64_t* t, int B, long long per, const ChainHooks& h, hipStream_t st,
              const char* who = "p_update");
@@ -436,6 +448,13 @@ int p_update_restore_blur(const StepRule& r, const float* eps_hat, const int64_t
 bool restore_blur_shape_ok(int H, int W, int channels);
 bool restore_blur_one_launch(int H, int W, int channels);
 int separable_init_device();
+// hadamard.hip: the RestoreHadamard kind's step, the shapes it takes (H, W powers of two in [16, 256], 1..8 channels; m a multiple of
+// 4 in [4, H W]) and whether a plane takes the one-launch plane form (else the rule needs had.tmp)
+int p_update_restore_cs(const StepRule& r, const float* eps_hat, const int64_t* t, int B, int channels, const ChainHooks& h, hipStream_t st);
+bool restore_cs_shape_ok(int H, int W, int channels);
+bool restore_cs_rows_ok(int H, int W, int m);
+bool restore_cs_plane_form(int H, int W);
+int hadamard_init_device();
 int randn(float* out, long long n, uint64_t seed, uint32_t step, uint32_t stream_id, hipStream_t st);
 int vlb_sweep_slots_unfused(int B, long long per);
 int vlb_step_input(const VlbStep& v, const float* sqrt_acp, const float* sqrt_1m_acp, const int64_t* chain_state, int B, long long per,

@@ -89,7 +89,8 @@ struct ChainKey {
     const void* noise;                       // also in bufs; injected draws: no 16-step graph (see run_chain)
     int B, H, W, t_start, device;
     unsigned long long pack_epoch;
-    int restore_n = 0;                       // StepKind::Restore, RestoreMasked: the block (y and the mask are staged in the workspace; the kind
+    int restore_n = 0;                       // StepKind::RestoreHadamard: m, the measured coefficients per plane (the kernels are launched with it).
+                                             // StepKind::Restore, RestoreMasked: the block (y and the mask are staged in the workspace; the kind
                                              // says whether a mask is present, so a masked and an unmasked chain never share a graph)
     bool restore_mask = false;               // StepKind::RestoreMultistep, RestoreNoisy, one kind with or without a mask: whether its kernels were given one
     int restore_gray = 0;                    // StepKind::RestoreGray: the weights (rst.gray), so "mean" and "luma" chains never share a graph
@@ -1762,8 +1763,17 @@ static BlurStage blur_stage(size_t n, int H, int W) {
     const size_t ph = 0, pw = ph + al4((size_t)H * H), yp = pw + al4((size_t)W * W);
     return {ph, pw, yp, yp + al4(n)};
 }
+// RestoreHadamard (plane-wide): perm [H W] int32, y [B][C][m] in a place of the latent's size (m <= H W) and T of the latent's size
+struct CsStage {
+    size_t perm, y, tmp;          // offsets in floats from the chain's extra area; total = tmp + al4(n)
+};
+static CsStage cs_stage(size_t n, int H, int W) {
+    const size_t y = al4((size_t)H * W);
+    return {0, y, y + al4(n)};
+}
 static size_t chain_extra_floats(const ddk_unet& u, int B, int H, int W, StepKind kind, int restore_n = 0) {
     const size_t n = al4((size_t)B * H * W * u.cfg.in_ch);
+    if (kind == StepKind::RestoreHadamard) return cs_stage(n, H, W).tmp + al4(n);
     if (kind == StepKind::RestoreBlur) return blur_stage(n, H, W).tmp + al4(n);
     if (kind == StepKind::Restore) return al4(n / 4);
     if (restore_kind(kind)) {
@@ -1786,6 +1796,7 @@ static size_t sampler_bytes(const ddk_unet* u, int B, int H, int W, int t_start,
 //   Inpaint:   known and mask, copied in before the first op
 //   the restore kinds: (RestoreMultistep: the history, zeroed by every call as Multistep's, then) y and, when given, the mask,
 //              copied in before the first step (restore_stage's layout)
+//   RestoreBlur: the projections copied in and Yp formed (blur_stage); RestoreHadamard: perm and y copied in (cs_stage)
 // The graph key: the kind, every table the step reads and the restore block; the staged operands live in the workspace, which is
 // in the key.
 static int sampler_chain(const ddk_sampler_args* a, const char* who, const int64_t* map, StepRule rule, ddk_stream_t s) {
@@ -1820,6 +1831,13 @@ static int sampler_chain(const ddk_sampler_args* a, const char* who, const int64
                                              c.u->cfg.in_ch, s));
         rule.blr = BlurOps{extra + g.ph, extra + g.pw, extra + g.tmp, nullptr, nullptr};
         rule.rst = RestoreOps{extra + g.yp, 0, H, W, 0, nullptr};
+    } else if (rule.kind == StepKind::RestoreHadamard) {
+        // perm and y copied in before the first step and outside any captured one: rule.rst.y and rule.had.perm are the CALLER's
+        const CsStage g = cs_stage(al4(n), H, W);
+        DDK_HIP(hipMemcpyAsync(extra + g.perm, rule.had.perm, (size_t)H * W * sizeof(int32_t), hipMemcpyDeviceToDevice, c.st));
+        DDK_HIP(hipMemcpyAsync(extra + g.y, rule.rst.y, (size_t)B * c.u->cfg.in_ch * rule.had.m * sizeof(float), hipMemcpyDeviceToDevice, c.st));
+        rule.had = HadamardOps{reinterpret_cast<const int32_t*>(extra + g.perm), extra + g.tmp, rule.had.m};
+        rule.rst = RestoreOps{extra + g.y, 0, H, W, 0, nullptr};
     } else if (restore_kind(rule.kind)) {
         const RestoreStage g = restore_stage(n, B, H, W, rule.kind, rule.rst.n);
         const size_t nn = (size_t)rule.rst.n * rule.rst.n, nm = (size_t)B * H * W / nn;      // one float per block: the mask, and the grey y
@@ -1844,12 +1862,14 @@ static int sampler_chain(const ddk_sampler_args* a, const char* who, const int64
 
     // the RestoreNoisy / RestoreGray tables share the Inpaint operands' storage (StepRule): each kind's key names its own
     const bool noisy = rule.kind == StepKind::RestoreNoisy || rule.kind == StepKind::RestoreGray;
-    const InpaintOps ik = noisy || rule.kind == StepKind::RestoreBlur ? InpaintOps{} : rule.inp;      // (the blur operands are staged: the workspace names them)
+    const bool plane = rule.kind == StepKind::RestoreBlur || rule.kind == StepKind::RestoreHadamard;
+    const InpaintOps ik = noisy || plane ? InpaintOps{} : rule.inp;      // (the plane-wide kinds' operands are staged: the workspace names them)
     const NoisyTables nk = noisy ? rule.nsy : NoisyTables{};
     const ChainKey key{rule.kind,
                        {a->packed, a->x, rule.c_recip, rule.c_recipm1, rule.c1, rule.c2, rule.sigma, rule.c3, ik.ka, ik.kb, ik.ja, ik.jb, nk.lam,
                         nk.sgm},
-                       a->workspace, a->noise, B, H, W, a->t_start, c.dev, c.u->pack_epoch, restore_kind(rule.kind) ? rule.rst.n : 0,      // RestoreBlur: 0, the kind says it
+                       a->workspace, a->noise, B, H, W, a->t_start, c.dev, c.u->pack_epoch,
+                       rule.kind == StepKind::RestoreHadamard ? rule.had.m : restore_kind(rule.kind) ? rule.rst.n : 0,      // RestoreBlur: 0, the kind says it
                        (rule.kind == StepKind::RestoreMultistep || noisy) && rule.rst.mask != nullptr,
                        rule.kind == StepKind::RestoreGray ? rule.rst.gray : 0};
     return run_chain(*c.u, key, n_steps, a->use_graph != 0, one_step, c.st, who);
@@ -2086,6 +2106,39 @@ extern "C" int ddk_sampler_run_restore_blur(const ddk_sampler_args* a, const int
 extern "C" int ddk_sampler_run_restore_sep(const ddk_sampler_args* a, const int64_t* timestep_map, const float* P_h, const float* P_w,
                                            const float* Q_h, const float* Q_w, const float* y, int h, int w, ddk_stream_t s) {
     return restore_blur_chain(a, "sampler_restore_sep", timestep_map, P_h, P_w, Q_h, Q_w, y, true, h, w, s);
+}
+
+// DDNM compressed sensing on a pixel-space model (section 3.17): the spaced sampler's chain, every step ending in
+// StepKind::RestoreHadamard.  y [B][C][m] and perm [H W] are the caller's device arrays, copied into the workspace before the first step.
+// Plane-wide like the blur kind: no step takes the fused tail.
+extern "C" size_t ddk_sampler_restore_cs_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start) {
+    if (check_shape(u, B, H, W) != DDK_OK || !restore_cs_shape_ok(H, W, u->cfg.in_ch)) return 0;
+    return sampler_bytes(u, B, H, W, t_start, StepKind::RestoreHadamard);
+}
+extern "C" int ddk_sampler_restore_cs_tail_parts(const ddk_unet* u, int B, int H, int W) {
+    if (check_shape(u, B, H, W) != DDK_OK) return -1;
+    return fused_tail_parts(*u, B, H, W, u->dimp[1], StepKind::RestoreHadamard);      // 0: final_tail_ok takes no plane-wide kind
+}
+extern "C" int ddk_sampler_run_restore_cs(const ddk_sampler_args* a, const int64_t* timestep_map, const float* y, const int32_t* perm, int m,
+                                          ddk_stream_t s) {
+    const char* who = "sampler_restore_cs";
+    auto bad = [who](const char* what) {
+        set_error("bad argument: %s: %s", who, what);
+        return DDK_ERR_ARG;
+    };
+    if (!(a && a->unet && a->packed && a->x && a->workspace && y && perm)) return bad("null pointer");
+    if (!(a->c_recip && a->c_recipm1 && a->c1 && a->c2 && a->sigma)) return bad("null schedule table");
+    if (a->noise) return bad("injected noise is not supported, noise must be NULL (Philox only)");
+    if (!(a->t_start >= a->t_end && a->t_end >= 0)) return bad("need t_start >= t_end >= 0");
+    if (!restore_cs_shape_ok(a->H, a->W, a->unet->cfg.in_ch)) return bad("H and W must be powers of two in [16, 256], the model's channels 1 to 8");
+    if (!restore_cs_rows_ok(a->H, a->W, m)) return bad("m must be a multiple of 4 in [4, H W]");
+    if (!(aligned16(y) && aligned16(perm))) return bad("alignment");
+    DDK_TRY(check_timestep_map(timestep_map, a->t_start, who));
+    StepRule rule{};
+    rule.kind = StepKind::RestoreHadamard;
+    rule.had = HadamardOps{perm, nullptr, m};
+    rule.rst.y = y;
+    return sampler_chain(a, who, timestep_map, rule, s);
 }
 
 // ------------------------------------------------------------------------------------------------ likelihood sweep

@@ -901,6 +901,56 @@ def p_sample_update_restore_blur_(x, eps_hat, P_h, P_w, Yp, t, c_recip, c_recipm
     return x
 
 
+def _cs_operands(who, shape, perm, y, m, device):
+    """The checks the compressed-sensing ops share: NHWC shape [B,H,W,C], perm int32 [H*W], y [B,C,m]."""
+    b, h, w, c = shape
+    if perm is None or tuple(perm.shape) != (h * w,) or perm.dtype != torch.int32 or not perm.is_contiguous() or perm.device != device:
+        raise L.DDKError(f"{who}: perm must be a contiguous int32 [{h * w}] tensor on the image's device")
+    if y is not None and (tuple(y.shape) != (b, c, m) or y.dtype != torch.float32 or not y.is_contiguous() or y.device != device):
+        raise L.DDKError(f"{who}: y must be a contiguous fp32 [{b},{c},{m}] tensor on the image's device, got {tuple(y.shape)} {y.dtype}")
+    # a 256 x 256 plane does not fit in LDS: the transform goes through a scratch of the image's size
+    return torch.empty(shape, device=device, dtype=torch.float32) if h * w > 32768 else None
+
+
+def hadamard_measure(x, perm, m):
+    """y [B,C,m] = the first m coefficients of the orthonormal Walsh-Hadamard transform (natural order) of every plane of x
+    [B,H,W,C] (NHWC fp32) read through perm: a[j] = plane[perm[j]].  perm: int32 [H*W]; H and W powers of
+    two in [16, 256], C in 1..8, m a multiple of 4 in [4, H*W]."""
+    b, h, w, c = x.shape
+    m = int(m)
+    scratch = _cs_operands("hadamard_measure", tuple(x.shape), perm, None, m, x.device)
+    y = torch.empty((b, c, max(m, 0)), device=x.device, dtype=torch.float32)
+    L.check(L.load().ddk_hadamard_measure(L.ptr(_f32(x)), L.ptr(perm), L.ptr(y), L.ptr(scratch), b, h, w, c, m, L.stream()), "hadamard_measure")
+    return y
+
+
+def hadamard_adjoint(y, perm, h, w):
+    """A^T y = A+ y as an NHWC image [B,h,w,C]: y [B,C,m] padded with zeros to h*w coefficients, transformed and scattered through
+    perm."""
+    b, c, m = y.shape
+    out = torch.empty((b, int(h), int(w), c), device=y.device, dtype=torch.float32)
+    scratch = _cs_operands("hadamard_adjoint", tuple(out.shape), perm, y, m, y.device)
+    L.check(L.load().ddk_hadamard_adjoint(L.ptr(y), L.ptr(perm), L.ptr(out), L.ptr(scratch), b, int(h), int(w), c, m, L.stream()),
+            "hadamard_adjoint")
+    return out
+
+
+def p_sample_update_restore_cs_(x, eps_hat, y, perm, t, c_recip, c_recipm1, c1, c2, sigma, seed=0, stream_id=0):
+    """In-place DDNM compressed-sensing step of x [B,H,W,C] (NHWC) per sample row t[b]: the clipped x0's
+    first m Walsh-Hadamard coefficients (of each plane read through perm) are replaced by y [B,C,m], then the ancestral update with
+    Philox draws runs on the result."""
+    if tuple(eps_hat.shape) != tuple(x.shape) or y is None or y.dim() != 3:
+        raise L.DDKError(f"p_sample_update_restore_cs: x {tuple(x.shape)}, eps_hat {tuple(eps_hat.shape)}, "
+                         f"y {None if y is None else tuple(y.shape)}")
+    b, h, w, c = x.shape
+    m = int(y.shape[2])
+    scratch = _cs_operands("p_sample_update_restore_cs", tuple(x.shape), perm, y, m, x.device)
+    L.check(L.load().ddk_p_sample_update_restore_cs(L.ptr(_f32(x)), L.ptr(_f32(eps_hat)), L.ptr(y), L.ptr(perm), L.ptr(scratch), L.ptr(t),
+                                                    L.ptr(c_recip), L.ptr(c_recipm1), L.ptr(c1), L.ptr(c2), L.ptr(sigma), b, h, w, c, m, seed,
+                                                    stream_id, L.stream()), "p_sample_update_restore_cs")
+    return x
+
+
 def randn(shape, device, seed, step, stream_id=0):
     out = torch.empty(shape, device=device, dtype=torch.float32)
     L.check(L.load().ddk_randn(L.ptr(out), out.numel(), seed, step, stream_id, L.stream()), "randn")

@@ -34,6 +34,12 @@ through utils/data.py; ``--max_batches`` keeps the first max_batches * batch_siz
     ``gauss`` or ``aniso``; zero padding; the task has no default kernel) and ``model.deblur`` restores them with ``--tol``, ``--timestep_respacing``, ``--use_ddim`` and
     ``--eta``.  Baselines: the blurred image itself and A+ y clipped to [-1, 1].  The consistency is max |A(x_out) - y| in uint8
     levels; ``method`` reads ``ddnm_blur`` and the settings gain ``kernel`` and ``tol``.
+  * ``--task cs --ratio R [--perm_seed S]`` (DDPM checkpoints; section 3.17): every colour plane is measured by the first
+    m = 4 round(R N / 4) coefficients of the orthonormal Walsh-Hadamard transform of its pixels permuted with seed S (default 0), and
+    ``model.restore_cs`` restores it with ``--timestep_respacing``, ``--use_ddim`` and ``--eta``.  Baseline: ``adjoint``, A^T y clipped
+    to [-1, 1].  The consistency is max |A(x_out) - y| in the measurement's own scale; ``method`` reads ``ddnm_cs`` and the settings
+    gain ``ratio``, ``perm_seed`` and ``m``.  No ``--scale``, ``--mask``, ``--sigma_y``, ``--dpm_solver``, ``--method``, ``--kernel``
+    or ``--tol``.
   * batch g draws x_T and its Philox key from ``--seed`` + g.
 
 Prints one JSON object, the settings that produced it (among them ``method`` and ``unet_forwards``, the UNet forwards per image, so
@@ -48,7 +54,7 @@ import time
 import numpy as np
 import torch
 
-from utils.restoration_metrics import BLUR_KERNELS, DEBLUR_TASK, DOWNSAMPLES, GRAY_WEIGHTS, MASKS, METHODS, TASKS, evaluate_restoration, load_mask, report, to_u8
+from utils.restoration_metrics import BLUR_KERNELS, CS_TASK, DEBLUR_TASK, DOWNSAMPLES, GRAY_WEIGHTS, MASKS, METHODS, TASKS, evaluate_restoration, load_mask, report, to_u8
 
 
 def parse_args(argv=None):
@@ -56,7 +62,7 @@ def parse_args(argv=None):
     ap.add_argument("--saved_model", default="celeba_x2")
     ap.add_argument("--synthetic", default=None, help="JSON config file: use closed-form synthetic weights, no checkpoint")
     ap.add_argument("--images", default=None, help="uint8 [N, H, W, C] .npy of the model's size (default: the dataset's test split)")
-    ap.add_argument("--task", required=True, choices=(*TASKS, DEBLUR_TASK))
+    ap.add_argument("--task", required=True, choices=(*TASKS, DEBLUR_TASK, CS_TASK))
     ap.add_argument("--mask", default=None, help=f"one of {', '.join(MASKS)} or a .npy file of {{0, 1}} (1 = known); inpaint: default "
                                                  "center; sr: masked super-resolution, the mask is of the pooled image (default: none)")
     ap.add_argument("--method", default=None, choices=METHODS, help="inpaint: repaint (default) or ddnm; sr: ddnm")
@@ -65,6 +71,8 @@ def parse_args(argv=None):
     ap.add_argument("--weights", default=None, choices=tuple(GRAY_WEIGHTS), help="colorize: the grey image's channel weights (default mean)")
     ap.add_argument("--kernel", default=None, choices=BLUR_KERNELS, help="deblur: the separable blur (required there)")
     ap.add_argument("--tol", type=float, default=None, help="deblur: singular values below tol * s_max are dropped, per axis (default 0.03)")
+    ap.add_argument("--ratio", type=float, default=None, help="cs: the sampling ratio in (0, 1] (required there)")
+    ap.add_argument("--perm_seed", type=int, default=None, help="cs: seed of the pixel permutation (default 0)")
     ap.add_argument("--timestep_respacing", default="", help='run K of the T steps: "N", "n1,n2,..." sections or (sr) "ddimN"')
     ap.add_argument("--use_ddim", action="store_true", help="sr: DDIM steps instead of ancestral ones")
     ap.add_argument("--eta", type=float, default=0.0, help="sr: DDIM noise scale (0: deterministic)")
@@ -81,6 +89,21 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.batch_size < 1 or (args.max_batches is not None and args.max_batches < 1):
         ap.error("--batch_size and --max_batches must be >= 1")
+    if (args.ratio is not None or args.perm_seed is not None) and args.task != CS_TASK:
+        ap.error("--ratio and --perm_seed belong to --task cs")
+    if args.task == CS_TASK:
+        if args.ratio is None:
+            ap.error("--task cs needs --ratio: the sampling ratio is part of the task, there is no default")
+        if not (0 < args.ratio <= 1):
+            ap.error("--ratio must be in (0, 1]")
+        if args.perm_seed is None:
+            args.perm_seed = 0
+        if args.perm_seed < 0:
+            ap.error("--perm_seed must be >= 0")
+        if args.method is not None or args.dpm_solver or args.sigma_y != 0.0 or args.mask is not None or args.scale is not None or \
+                args.kernel is not None or args.tol is not None:
+            ap.error("--task cs has one method, ddnm on ancestral or DDIM steps, and takes no --method, --mask, --scale, --sigma_y, "
+                     "--dpm_solver, --kernel or --tol")
     if args.method is None:
         args.method = "repaint" if args.task == "inpaint" else "ddnm"
     if args.downsample is not None and args.task != "sr":
@@ -100,6 +123,8 @@ def parse_args(argv=None):
             ap.error("--tol must be in [0, 1)")
         if args.method != "ddnm" or args.dpm_solver or args.sigma_y != 0.0 or args.mask is not None or args.scale is not None:
             ap.error("--task deblur has one method, ddnm on ancestral or DDIM steps, and takes no --mask, --scale or --sigma_y")
+    elif args.task == CS_TASK:
+        pass                      # checked above
     elif args.task == "sr":
         if args.scale is None:
             args.scale = 4
@@ -153,6 +178,8 @@ def chain_options(args):
         kw.update(downsample="bicubic")
     if args.task == DEBLUR_TASK:
         kw.update(kernel=args.kernel, tol=args.tol)
+    if args.task == CS_TASK:
+        kw.update(ratio=args.ratio, perm_seed=args.perm_seed)
     if args.dpm_solver:
         kw.update(dpm_solver=True)
     elif args.method == "ddnm":
@@ -223,7 +250,7 @@ def main():
     kw = chain_options(args)
     if args.task == "inpaint":
         kw["mask"] = args.mask if args.mask in MASKS else load_mask(args.mask, n, h, w, channels)
-    elif args.mask is not None and args.task != DEBLUR_TASK:
+    elif args.mask is not None and args.task not in (DEBLUR_TASK, CS_TASK):
         kw["sr_mask"] = args.mask if args.mask in MASKS else load_mask(args.mask, n, h // args.scale, w // args.scale, 1)
 
     print(f"Scoring {args.task} on {n} images with {'synthetic weights' if args.synthetic else args.saved_model}.")
@@ -237,6 +264,8 @@ def main():
                     seed=args.seed, method=result["method"], unet_forwards=result["unet_forwards"], **chain_options(args))
     if args.mask is not None:
         settings["mask"] = args.mask
+    if "m" in result:
+        settings["m"] = result["m"]
     out = dict(settings=settings, metrics=report(result))
     print(json.dumps(out, indent=4))
     if args.json:

@@ -213,6 +213,11 @@ class DownsampleDDPM(DDPM):
         raise ValueError("restore_separable: a DownsampleDDPM samples in a latent, and a separable operator on the image has no separable "
                          "form there; it needs a pixel model (DDPM)")
 
+    def restore_cs(self, y, perm=None, **kwargs):
+        """Not available, for deblur's reason: a transform of the latent is not a transform of the image.  Always ValueError."""
+        raise ValueError("restore_cs: a DownsampleDDPM samples in a latent, and a Walsh-Hadamard transform of the latent is not one of the "
+                         "image; compressed sensing needs a pixel model (DDPM)")
+
     @torch.no_grad()
     def reconstruct(self, x, n):
         """dddpm.py:33-74 (visualisation only)."""

@@ -18,7 +18,7 @@ from ddk import ops
 from ddk.lib import DDKError
 from utils import flat_bits, reduce_mean, reduce_sum
 from models.utils import discretized_gaussian_log_likelihood, extract, l2_loss, noise_like, normal_kl
-from . import blur, respace
+from . import blur, hadamard, respace
 from .beta_schedule import make_beta_schedule
 
 OBJETIVE_NAMES = ['simple', 'hybrid', 'vlb']
@@ -808,6 +808,62 @@ class DDPM(nn.Module):
             lambda plan, x, yl, mk, tables, k_start, seed, use: plan.sample_restore_sep_nhwc(
                 x, yl, m["P_h"], m["P_w"], m["Q_h"], m["Q_w"], tables, k_start, seed=seed, stream_id=sid, use_graph=self.use_graph,
                 timesteps=use))
+
+    # ------------------------------------------------------------------ DDNM compressed sensing (Walsh-Hadamard)
+    def _cs_args(self, y, perm, perm_seed, ddim, eta, unsupported):
+        """ValueError for anything restore_cs cannot take, before any device work.  Returns (y as float, perm as an int32 array)."""
+        who = "restore_cs"
+        if unsupported:
+            raise ValueError(f"{who}: {sorted(unsupported)} not accepted (DDNM runs ancestral or DDIM steps with Philox draws over the "
+                             f"whole schedule on an exact measurement of the first m coefficients: no {', '.join(self.DEBLUR_UNSUPPORTED)})")
+        if isinstance(eta, bool) or not isinstance(eta, (int, float, np.integer, np.floating)) or eta < 0 or (eta != 0 and not ddim):
+            raise ValueError(f"{who}: eta = {eta!r} needs ddim=True and eta >= 0")
+        C, H, W = self.sample_shape
+        if not hadamard.size_ok(C, H, W):
+            raise ValueError(f"{who}: the image size must be powers of two in [16, 256] with 1 to 8 channels, this model's is {C} x {H} x {W}")
+        N = H * W
+        if perm is None:
+            if isinstance(perm_seed, bool) or not isinstance(perm_seed, (int, np.integer)) or perm_seed < 0:
+                raise ValueError(f"{who}: perm_seed must be a non-negative integer, got {perm_seed!r}")
+            perm = hadamard.cs_perm(N, perm_seed)
+        else:
+            perm = hadamard.check_perm(perm, N, who)
+        if not torch.is_tensor(y) or y.dim() != 3 or y.shape[0] < 1 or y.shape[1] != C or not y.is_floating_point():
+            raise ValueError(f"{who}: y must be a float [B, {C}, m] tensor, got {tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
+        m = int(y.shape[2])
+        if m % 4 or not (4 <= m <= N):
+            raise ValueError(f"{who}: y's m must be a multiple of 4 in [4, {N}], got {m}")
+        if not bool(torch.isfinite(y).all()):
+            raise ValueError(f"{who}: y must be finite")
+        return y.float(), perm
+
+    @torch.no_grad()
+    def restore_cs(self, y, perm=None, *, perm_seed=0, respacing=None, ddim=False, eta=0.0, x_T=None, seed=None, **unsupported):
+        """Zero-shot compressed sensing with DDNM (Wang, Yu, Zhang 2023): an image [B, C, H, W] whose
+        subsampled, permuted Walsh-Hadamard transform is y [B, C, m].  Per channel the plane is flattened row-major, read through perm
+        (an integer array of H W entries, a permutation; default hadamard.cs_perm(H W, perm_seed)) and transformed by the orthonormal
+        Walsh-Hadamard matrix in natural order; y holds its first m coefficients (m is read from y: hadamard.cs_rows(ratio, H W) for a
+        sampling ratio).  Every step of the chain (all T steps, or respacing's K; ancestral, or DDIM with eta) sets the measured
+        coefficients of its clipped x0 to y before the update, so A(x_out) = y up to fp32 rounding and everything else is the
+        model's.  x_T: the start state; seed: the Philox key (default: drawn from torch's generator).  H and W powers of two in
+        [16, 256], m a multiple of 4 in [4, H W].  solver / noise / early_stop / paste / mask / sigma_y raise ValueError, as do a perm
+        that is no permutation, a size off that grid, a bad eta and a non-finite or misshapen y, before any device work."""
+        y, perm = self._cs_args(y, perm, perm_seed, ddim, eta, unsupported)
+        spaced = respacing is not None or ddim or eta != 0
+        sid = int(self.rng_stream_id)
+        pd = []                   # perm on the model's device, placed at the first use (after _ddnm_loop's device check)
+
+        def perm_dev():
+            if not pd:
+                pd.append(torch.from_numpy(perm).to(self.betas.device))
+            return pd[0]
+
+        def op(x, e, yl, mk, t, tables, seed):
+            ops.p_sample_update_restore_cs_(x, e, yl, perm_dev(), t, **tables, seed=seed, stream_id=sid)
+        return self._ddnm_loop(
+            "restore_cs", y, None, lambda: self._spaced_tables(respacing, ddim, eta) if spaced else (self._tables(), None), x_T, seed, op,
+            lambda plan, x, yl, mk, tables, k_start, seed, use: plan.sample_restore_cs_nhwc(
+                x, yl, perm_dev(), tables, k_start, seed=seed, stream_id=sid, use_graph=self.use_graph, timesteps=use))
 
     @torch.no_grad()
     def reconstruct(self, x, n):

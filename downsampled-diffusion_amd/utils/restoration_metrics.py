@@ -16,6 +16,7 @@ MASKS = ("center", "left", "half", "lines")
 TASKS = ("inpaint", "sr", "colorize")
 DEBLUR_TASK = "deblur"          # evaluate_restoration's fourth task (section 3.14), with kernels of its own instead of masks and scales
 BLUR_KERNELS = ("uniform", "gauss", "aniso")
+CS_TASK = "cs"                  # ... and its fifth (section 3.17), with a sampling ratio and a permutation seed
 METHODS = ("repaint", "ddnm")
 GRAY_WEIGHTS = {"mean": (1.0 / 3.0, 1.0 / 3.0, 1.0 / 3.0), "luma": (0.299, 0.587, 0.114)}     # DDPM.colorize's two operators
 DOWNSAMPLES = ("mean", "bicubic")     # task "sr": block means (section 3.6) or the antialiased bicubic reduction (section 3.15)
@@ -168,6 +169,11 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
     itself, and "pinv", A+ y clipped to [-1, 1] (the truncated pseudo-inverse alone, no network).  consistency / consistency_u8:
     max |A(x_out) - y| in uint8 levels, which the truncation keeps above zero.  The returned method is "ddnm_blur", and "kernel" and
     "tol" are returned.
+    task "cs" (pixel models; section 3.17): every plane is measured by the first m = cs_rows(``ratio``, H W) coefficients of the
+    orthonormal Walsh-Hadamard transform of its pixels permuted with ``perm_seed`` (default 0), on the device
+    (ops.hadamard_measure), and ``model.restore_cs`` restores it (``chain``: respacing, ddim, eta).  Baseline: "adjoint", A^T y
+    clipped to [-1, 1].  consistency: per image max |A(x_out) - y| of the model's float output, in the measurement's own scale.  The
+    returned method is "ddnm_cs", and "ratio", "perm_seed" and "m" are returned.
     downsample "bicubic" (task "sr" on a pixel model, without sr_mask, dpm_solver or sigma_y; section 3.15): the images are reduced
     by the antialiased bicubic matrix (``resize``) instead of pooled and ``model.super_resolve(downsample="bicubic")`` restores them.
     The baselines stay (replicate, bicubic upsampling); consistency / consistency_u8 are max |A(x_out) - y| in uint8 levels with that
@@ -190,8 +196,16 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
         return _evaluate_deblur(model, images_uint8, batch_size=batch_size, seed=seed, **chain)
     if "kernel" in chain or "tol" in chain:
         raise ValueError("kernel and tol belong to task 'deblur'")
+    if task == CS_TASK:
+        if method not in (None, "ddnm") or dpm_solver or sigma_y or sr_mask is not None or scale is not None:
+            raise ValueError("task 'cs' has one method, ddnm on ancestral or DDIM steps, and no mask, scale or sigma_y")
+        if "ratio" not in chain or not hasattr(model, "restore_cs"):
+            raise ValueError("task 'cs' needs a ratio and a model with a restore_cs method (a pixel DDPM)")
+        return _evaluate_cs(model, images_uint8, batch_size=batch_size, seed=seed, **chain)
+    if "ratio" in chain or "perm_seed" in chain:
+        raise ValueError("ratio and perm_seed belong to task 'cs'")
     if task not in TASKS:
-        raise ValueError(f"unknown task {task!r}: one of {(*TASKS, DEBLUR_TASK)}")
+        raise ValueError(f"unknown task {task!r}: one of {(*TASKS, DEBLUR_TASK, CS_TASK)}")
     if task == "colorize":
         return _evaluate_colorize(model, images_uint8, batch_size=batch_size, seed=seed, scale=1 if scale is None else scale, method=method,
                                   sr_mask=sr_mask, dpm_solver=dpm_solver, sigma_y=sigma_y, **chain)
@@ -370,6 +384,40 @@ def _evaluate_deblur(model, images_uint8, *, batch_size, seed, kernel, tol=3e-2,
                  consistency_u8=dev(from_u8(images["restored"])))
     methods = {name: _score(ops, img, ref, None, device) for name, img in images.items()}
     return dict(n_images=n, method="ddnm_blur", methods=methods, images={k: v.numpy() for k, v in images.items()}, **extra)
+
+
+@torch.no_grad()
+def _evaluate_cs(model, images_uint8, *, batch_size, seed, ratio, perm_seed=0, **chain):
+    """evaluate_restoration's task "cs" (see there)"""
+    from ddk import ops
+    from models.diffusion import hadamard
+    x_all = from_u8(images_uint8)
+    ref = torch.as_tensor(images_uint8).contiguous()
+    n, c, h, w = x_all.shape
+    if n < 1 or batch_size < 1:
+        raise ValueError("evaluate_restoration needs at least one image and batch_size >= 1")
+    if not hadamard.size_ok(c, h, w):
+        raise ValueError(f"task 'cs' needs H and W powers of two in [16, 256] and 1 to 8 channels, got {c} x {h} x {w}")
+    device = model.betas.device
+    m = hadamard.cs_rows(ratio, h * w)
+    perm = hadamard.cs_perm(h * w, perm_seed)
+    pd = torch.from_numpy(perm).to(device)
+    batches = lambda f, v: torch.cat([f(v[i:i + batch_size].to(device).contiguous()).cpu() for i in range(0, n, batch_size)])
+    A = lambda x: batches(lambda v: ops.hadamard_measure(ops.nchw_to_nhwc(v), pd, m), x)
+    y_all = A(x_all)
+    K = len(model._spaced_tables(chain.get("respacing"), chain.get("ddim", False), chain.get("eta", 0.0))[1]) \
+        if chain.get("respacing") is not None or chain.get("ddim") else int(model.timesteps)
+    images = {"adjoint": to_u8(batches(lambda v: ops.nhwc_to_nchw(ops.hadamard_adjoint(v, pd, h, w)), y_all).clamp(-1, 1))}
+    outs = []
+    for g, i in enumerate(range(0, n, batch_size)):
+        torch.manual_seed(seed + g)               # x_T and the Philox key of batch g
+        outs.append(model.restore_cs(y_all[i:i + batch_size].to(device), perm, **chain).float().cpu())
+    x_out = torch.cat(outs)
+    images = dict(restored=to_u8(x_out), **images)
+    extra = dict(unet_forwards=K, ratio=float(ratio), perm_seed=int(perm_seed), m=m,
+                 consistency=(A(x_out) - y_all).abs().amax(dim=(1, 2)).double().numpy())
+    methods = {name: _score(ops, img, ref, None, device) for name, img in images.items()}
+    return dict(n_images=n, method="ddnm_cs", methods=methods, images={k: v.numpy() for k, v in images.items()}, **extra)
 
 
 def report(result):

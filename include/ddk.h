@@ -400,6 +400,31 @@ int ddk_separable_apply_rect(const float* in, const float* L, const float* R, fl
 int ddk_p_sample_update_restore_blur(float* x, const float* eps_hat, const float* P_h, const float* P_w, const float* Yp, float* scratch,
                                      const int64_t* t, const float* c_recip, const float* c_recipm1, const float* c1, const float* c2,
                                      const float* sigma, int B, int H, int W, int channels, uint64_t seed, uint32_t stream_id, ddk_stream_t s);
+/* The measurement operator of DDNM's compressed-sensing task, per image b and channel c of an NHWC fp32 tensor
+ * x [B][H][W][channels], the plane flattened row-major (j = h W + w, N = H W):
+ *   a[j] = x[perm[j]];  v[k] = s sum_j (-1)^popcount(k & j) a[j],  s = fp32(1 / sqrt(N));  y[b][c][k] = v[k] for k < m.
+ * perm is an int32 device array [N], a permutation shared by channels and batch; the kernels read perm[j] & (N - 1), so a bad array gives
+ * wrong numbers and never an access outside the plane.  The butterflies run unnormalised in a fixed order in LDS, then one multiply by s;
+ * no atomics: results are bit-identical run to run.  A plane of at most 32768 pixels takes one launch; a 256 x 256 plane takes two
+ * through `scratch`, a device array of x's size that may be NULL for the smaller planes.  H and W powers of two in [16, 256], channels in
+ * 1..8, B channels <= 65535, m a multiple of 4 in [4, N]; x, perm, y and scratch 16-byte aligned.  Anything else is DDK_ERR_ARG and runs
+ * no kernel. */
+int ddk_hadamard_measure(const float* x, const int32_t* perm, float* y, float* scratch, int B, int H, int W, int channels, int m, ddk_stream_t s);
+/* Its adjoint, which is its pseudo-inverse (the rows are orthonormal): out[perm[j]] = s sum_k (-1)^popcount(k & j) w[k] with w = y on the
+ * first m coefficients and 0 behind them.  y [B][channels][m], out NHWC [B][H][W][channels]; everything else as ddk_hadamard_measure. */
+int ddk_hadamard_adjoint(const float* y, const int32_t* perm, float* out, float* scratch, int B, int H, int W, int channels, int m, ddk_stream_t s);
+/* One DDNM compressed-sensing step on its own (ddk_sampler_run_restore_cs).  Per sample b with row t[b]:
+ *   x0  = clamp(c_recip x - c_recipm1 eps_hat, -1, 1);  sg = t > 0 ? sigma : 0;
+ *   v   = s H(a), a[j] = x0[perm[j]]                    (per channel; H: the unnormalised butterflies, then one multiply by s)
+ *   w[k] = k < m ? y[b][c][k] : v[k]                    (a select, no arithmetic)
+ *   x0'[perm[j]] = s H(w)[j]                            (not clamped again)
+ *   x   = (c1 x0' + c2 x) + sg z.
+ * z is the Philox draw of ddk_p_sample_update_restore.  A plane of at most 32768 pixels takes one launch, a workgroup per (image,
+ * channel); a 256 x 256 plane takes three through `scratch`, a device array of x's size that may be NULL for the smaller planes.  Shapes
+ * and alignment as ddk_hadamard_measure.  Anything else is DDK_ERR_ARG; on an error x is not touched. */
+int ddk_p_sample_update_restore_cs(float* x, const float* eps_hat, const float* y, const int32_t* perm, float* scratch, const int64_t* t,
+                                   const float* c_recip, const float* c_recipm1, const float* c1, const float* c2, const float* sigma, int B, int H,
+                                   int W, int channels, int m, uint64_t seed, uint32_t stream_id, ddk_stream_t s);
 /* The end of a forward in one launch (unet.py:69-72 behind the final Block's conv; ddpm.py:203-227): GroupNorm from the conv's
  * partials -> Mish -> 1x1 projection to n_out <= 8 channels (w [n_out][C], bias [n_out]) -> eps_hat; eps_out and / or x may be
  * given: eps_out [B][HW][n_out] receives eps_hat, x [B][HW][n_out] gets the reverse-step update of ddk_p_sample_update in place
@@ -707,6 +732,18 @@ int ddk_sampler_run_restore_blur(const ddk_sampler_args* a, const int64_t* times
  * bit. */
 int ddk_sampler_run_restore_sep(const ddk_sampler_args* a, const int64_t* timestep_map, const float* P_h, const float* P_w, const float* Q_h,
                                 const float* Q_w, const float* y, int h, int w, ddk_stream_t s);
+/* Zero-shot compressed sensing on a pixel-space model: DDNM for A = the first m rows of the orthonormal Walsh-Hadamard transform of the
+ * permuted plane.  The chain and tables of ddk_sampler_run_spaced (plain, respaced ancestral or DDIM), every step
+ * being ddk_p_sample_update_restore_cs's.  y [B][channels][m] and perm [H W] (int32) are device arrays read before the first step only:
+ * both are copied into the workspace, outside any captured step, so a loop over image batches replays one cached graph.  The workspace
+ * (ddk_sampler_restore_cs_workspace_bytes; 0 for a shape the kind does not take) holds ddk_sampler_workspace_bytes plus perm (H W words),
+ * y (a place of the latent's size) and the scratch form's T (the latent's size), each rounded up to four floats.  a->noise must be NULL
+ * (Philox only).  H and W powers of two in [16, 256], a model of 1..8 channels, m a multiple of 4 in [4, H W], else DDK_ERR_ARG.  The kind
+ * couples a whole plane, so no step takes the fused tail: ddk_sampler_restore_cs_tail_parts is 0 for every shape (-1 for a shape the plan
+ * does not take).  Graphs are cached under a chain kind of their own, with m in the key. */
+size_t ddk_sampler_restore_cs_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start);
+int ddk_sampler_restore_cs_tail_parts(const ddk_unet* u, int B, int H, int W);
+int ddk_sampler_run_restore_cs(const ddk_sampler_args* a, const int64_t* timestep_map, const float* y, const int32_t* perm, int m, ddk_stream_t s);
 /* Drops the plan's cached sampler and likelihood-sweep graphs and shift table (waits for the device when graphs exist). */
 int ddk_sampler_invalidate(ddk_unet* u);
 /* Drops only the cached graphs (and shift table) that live in / point into `workspace`, after waiting for the launches of

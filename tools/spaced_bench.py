@@ -42,7 +42,12 @@ well as the two matrix products.
 (y 8 x 8 and 64 x 64): the cost of a step of the restore_sep chain against an ancestral step, timed alternately the same way (the step
 is the deblurring step: its figure is expected), and the one-time cost of forming Yp = Q_h y Q_w^T with separable_apply_rect, the
 median of five timings of 200 back-to-back calls each between two device events (two launches per call; where the
-kernels are shorter than a launch takes to enqueue, the figure is the enqueue's)."""
+kernels are shorter than a launch takes to enqueue, the figure is the enqueue's).
+
+--restore-cs: the cost of a DDNM compressed-sensing step (ratio 0.25, perm seed 0) against an ancestral step of
+the same respaced chain on --restore-blur's two models: 3 x 32 x 32 at B = 32 (the plane form, one launch) and 3 x 256 x 256 at B = 8
+(the scratch form, three launches).  The ancestral, compressed-sensing and deblurring chains alternate in one process, medians of
+five each, so the deblurring step's ratio from the same run stands beside it as the natural neighbour."""
 import argparse
 import json
 import os
@@ -76,6 +81,7 @@ def main():
     ap.add_argument("--restore-gray", action="store_true", help="colourisation step (n = 1, 2; luma) against an ancestral step, respacing 50, on a 3-channel pixel model")
     ap.add_argument("--restore-blur", action="store_true", help="deblurring step (gauss) against an ancestral step on 3x32x32 (B 32) and 3x256x256 (B 8) pixel models")
     ap.add_argument("--restore-sep", action="store_true", help="bicubic x4 restore_sep step against an ancestral step, and the cost of forming Yp, on the --restore-blur models")
+    ap.add_argument("--restore-cs", action="store_true", help="compressed-sensing step (ratio 0.25) and deblurring step against an ancestral step on the --restore-blur models")
     ap.add_argument("--restore-solver", action="store_true", help="DDNM step on the 2M chain (n = 1 center mask, n = 2) against a 2M step, logsnr20")
     args = ap.parse_args()
     torch.cuda.set_device(0)
@@ -85,6 +91,8 @@ def main():
         return restore_blur_ab()
     if args.restore_sep:
         return restore_sep_ab()
+    if args.restore_cs:
+        return restore_cs_ab()
     cfg = bench.cfg4()
     model = DownsampleDDPM(cfg, Unet(cfg), DEV, 3)
     model.load_state_dict(syn.fill_state_dict(model.state_dict(), skip=syn.SCHEDULE_KEYS))
@@ -395,6 +403,61 @@ def restore_blur_ab():
         res["per_case"][name] = {"ancestral_ms_per_step": round(a, 4), "blur_ms_per_step": round(r, 4), "blur_over_ancestral": round(r / a, 4),
                                  "ancestral_min_max_ms": [round(min(anc), 4), round(max(anc), 4)],
                                  "blur_min_max_ms": [round(min(rst), 4), round(max(rst), 4)], "steps": K}
+        del model, plan
+    print(json.dumps(res), flush=True)
+
+
+def restore_cs_ab():
+    """restore_blur_ab's models: the ancestral, compressed-sensing and deblurring chains alternating"""
+    from models.diffusion import blur, hadamard
+    ratio = 0.25
+    res = {"shape": f"pixel DDPMs, T={T}, compressed-sensing step (ratio {ratio}, perm seed 0) and deblurring step (gauss kernel, tol 3e-2) vs "
+                    "ancestral step of the same respaced chain", "reps": REPS, "per_case": {}}
+    for name, chan, size, b, K in (("3x32x32_B32_chan128_plane_form", 128, 32, 32, 50), ("3x256x256_B8_chan32_scratch_form", 32, 256, 8, 20)):
+        cfg = dict(unet_chan=chan, unet_in=3, unet_dims=(1, 2, 2, 2), unet_dropout=0.0, image_size=size, T=T, loss_type="simple",
+                   beta_schedule="linear", loss_flat="sum")
+        model = DDPM(cfg, Unet(cfg), DEV, 3)
+        model.load_state_dict(syn.fill_state_dict(model.state_dict(), skip=syn.SCHEDULE_KEYS))
+        model = model.to(DEV).eval()
+        plan = model.latent_model.plan()
+        x0 = ops.randn((b, size, size, 3), DEV, seed=1234, step=T, stream_id=0)
+        x = x0.clone()
+        mats = {k: v.to(DEV) for k, v in zip(("A_h", "A_w", "Q_h", "Q_w", "P_h", "P_w"), blur.blur_operands("gauss", size, size))}
+        y_blur = ops.separable_apply(x0.clamp(-1, 1), mats["A_h"], mats["A_w"])
+        perm = torch.from_numpy(hadamard.cs_perm(size * size, 0)).to(DEV)
+        m = hadamard.cs_rows(ratio, size * size)
+        y_cs = ops.hadamard_measure(x0.clamp(-1, 1), perm, m)
+        sp, use = model._spaced_tables(str(K), False, 0.0)
+
+        def chain(kind):
+            x.copy_(x0)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            if kind == "anc":
+                plan.sample_nhwc(x, sp, K - 1, 0, seed=1234, stream_id=0, timesteps=use)
+            elif kind == "cs":
+                plan.sample_restore_cs_nhwc(x, y_cs, perm, sp, K - 1, seed=1234, stream_id=0, timesteps=use)
+            else:
+                plan.sample_restore_blur_nhwc(x, y_blur, mats["P_h"], mats["P_w"], mats["Q_h"], mats["Q_w"], sp, K - 1, seed=1234, stream_id=0,
+                                              timesteps=use)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3
+
+        with torch.no_grad():
+            t_settle = time.perf_counter()
+            while time.perf_counter() - t_settle < 2.0:
+                chain("anc")
+            chain("cs")                                  # every chain's graphs are captured outside the timed calls
+            chain("blur")
+            times = {"anc": [], "cs": [], "blur": []}
+            for _ in range(REPS):
+                for kind in times:
+                    times[kind].append(chain(kind) / K)
+        assert torch.isfinite(x).all() and plan.restore_cs_tail_parts(b, size, size) == 0
+        a, c, r = (statistics.median(times[k]) for k in ("anc", "cs", "blur"))
+        res["per_case"][name] = {"ancestral_ms_per_step": round(a, 4), "cs_ms_per_step": round(c, 4), "blur_ms_per_step": round(r, 4),
+                                 "cs_over_ancestral": round(c / a, 4), "blur_over_ancestral": round(r / a, 4), "m": m, "steps": K,
+                                 **{f"{k}_min_max_ms": [round(min(v), 4), round(max(v), 4)] for k, v in times.items()}}
         del model, plan
     print(json.dumps(res), flush=True)
 
