@@ -40,6 +40,7 @@ int ensure_device_init() {
     DDK_TRY(wgrad_init_device());
     DDK_TRY(separable_init_device());
     DDK_TRY(hadamard_init_device());
+    DDK_TRY(fft_conv_init_device());
     done.fetch_or(bit, std::memory_order_release);
     return DDK_OK;
 }

@@ -340,6 +340,15 @@ struct HadamardOps {
     int m;                        // coefficients 0 .. m - 1 of every plane are measured: rst.y is [B][C][m]
 };
 static_assert(sizeof(HadamardOps) <= sizeof(InpaintOps), "HadamardOps shares the Inpaint operands' storage: StepRule must not grow");
+// DDNM deconvolution of a 2-D point-spread function with periodic boundary: the kept frequencies, the FFT's
+// twiddles and the multi-launch form's T
+struct FftOps {
+    const float* mask;            // [H][W], natural frequency order: nonzero where the frequency is kept (zeroed in x0's spectrum)
+    const float* tw;              // [max(H, W) / 2] complex (re, im): exp(-2 pi i j / max(H, W)), float64 on the host rounded to fp32
+    float* tmp;                   // T [B][C][H W] complex; read and written only when a plane is too large for the plane form (above 16384 pixels)
+    const float* pinv;            // host side only: P^ [H][W] complex, from which the chain entry forms Yp = A+ y before the first step
+};
+static_assert(sizeof(FftOps) <= sizeof(InpaintOps), "FftOps shares the Inpaint operands' storage: StepRule must not grow");
 constexpr uint32_t INPAINT_Z2_BIT = 0x40000000u;   // Philox stream of the known region's draw: stream_id | this
 constexpr uint32_t INPAINT_Z3_BIT = 0x20000000u;   // ... and of the jump's: stream_id | this (so stream_id < 2^29)
 // zero-shot super-resolution (DDNM for A = n x n average pooling): the low-resolution image and the block
@@ -391,15 +400,18 @@ enum class StepKind {
     RestoreBlur,  // DDNM for a separable blur A(X) = A_h X A_w^T per channel: x0' = (x0 - P_h x0 P_w^T) + Yp with the
                   // projections P = A+ A of the two axes and Yp = A+ y, then Restore's update.  The only plane-wide kind: separable.hip's
                   // kernels, never the fused tail: c_recip .. sigma, blr, rst.y = Yp (x's layout), rst.H, rst.W; Philox only
-    RestoreHadamard  // DDNM compressed sensing, A = the first m rows of the orthonormal Walsh-Hadamard transform of the permuted plane
+    RestoreHadamard, // DDNM compressed sensing, A = the first m rows of the orthonormal Walsh-Hadamard transform of the permuted plane
                   // (DESIGN.md section 3.17): x0' = A^T y + (I - A^T A) x0, a select between two transforms, then Restore's update.
                   // Plane-wide: hadamard.hip's kernels, never the fused tail: c_recip .. sigma, had, rst.y = y [B][C][m], rst.H, rst.W;
                   // Philox only
+    RestoreFFT    // DDNM deconvolution, A = circular convolution with a 2-D point-spread function:
+                  // x0' = Re F2^-1(M ? 0 : F2 x0) / N + Yp, a select between two complex FFTs in LDS, then Restore's update.  Plane-wide:
+                  // fft_conv.hip's kernels, never the fused tail: c_recip .. sigma, fft, rst.y = Yp (x's layout), rst.H, rst.W; Philox only
                   // (last, so that the kinds above keep their values and their kernels' names)
 };
 inline bool restore_kind(StepKind k) {       // the kinds whose step carries a DDNM constraint (RestoreOps)
     return k == StepKind::Restore || k == StepKind::RestoreMasked || k == StepKind::RestoreMultistep || k == StepKind::RestoreNoisy ||
-           k == StepKind::RestoreGray || k == StepKind::RestoreBlur || k == StepKind::RestoreHadamard;
+           k == StepKind::RestoreGray || k == StepKind::RestoreBlur || k == StepKind::RestoreHadamard || k == StepKind::RestoreFFT;
 }
 struct StepRule {
     StepKind kind;
@@ -418,6 +430,7 @@ struct StepRule {
         NoisyTables nsy;          // RestoreNoisy, RestoreGray
         BlurOps blr;              // RestoreBlur
         HadamardOps had;          // RestoreHadamard
+        FftOps fft;               // RestoreFFT
     };
     const VlbStep* vlb;           // host side only
     RestoreOps rst;
@@ -438,7 +451,7 @@ struct ChainHooks {
     uint32_t stream_id;
 };
 // the unfused tail's last kernel, given eps_hat in memory: the rule's update of x (Ancestral, Multistep, Inpaint, Restore, RestoreMasked,
-// RestoreMultistep, RestoreNoisy, RestoreGray, RestoreBlur, RestoreHadamard) or the sweep's
+// RestoreMultistep, RestoreNoisy, RestoreGray, RestoreBlur, RestoreHadamard, RestoreFFT) or the sweep's
 // reduction of the step's terms (Vlb); `who` names the caller in messages
 int p_update(const StepRule& r, const float* eps_hat, const int64_t* t, int B, long long per, const ChainHooks& h, hipStream_t st,
              const char* who = "p_update");
@@ -455,6 +468,15 @@ bool restore_cs_shape_ok(int H, int W, int channels);
 bool restore_cs_rows_ok(int H, int W, int m);
 bool restore_cs_plane_form(int H, int W);
 int hadamard_init_device();
+// fft_conv.hip: the RestoreFFT kind's step, the shapes it takes (H, W powers of two in [16, 256], 1..8 channels), whether a plane takes
+// the one-launch plane form (else the rule needs fft.tmp), and the circular convolution behind ddk_circular_conv (out = Re F2^-1(mul .
+// F2 in) / N), which the chain entry forms Yp with; circular_conv_fault is null for sound arguments
+int p_update_restore_fft(const StepRule& r, const float* eps_hat, const int64_t* t, int B, int channels, const ChainHooks& h, hipStream_t st);
+bool restore_fft_shape_ok(int H, int W, int channels);
+bool restore_fft_plane_form(int H, int W);
+const char* circular_conv_fault(const void* in, const void* mul, const void* tw, const void* out, const void* scratch, int B, int H, int W, int C);
+int circular_conv(const float* in, const float* mul, const float* tw, float* out, float* scratch, int B, int H, int W, int C, hipStream_t st);
+int fft_conv_init_device();
 int randn(float* out, long long n, uint64_t seed, uint32_t step, uint32_t stream_id, hipStream_t st);
 int vlb_sweep_slots_unfused(int B, long long per);
 int vlb_step_input(const VlbStep& v, const float* sqrt_acp, const float* sqrt_1m_acp, const int64_t* chain_state, int B, long long per,

@@ -1,5 +1,5 @@
-// The device arithmetic that diffusion.hip, separable.hip and hadamard.hip share: the Philox draws, the clipped x0 of a restore step and the
-// update behind it.  All three files are compiled with -ffp-contract=off (Makefile): every product below rounds on its own.
+// The device arithmetic that diffusion.hip, separable.hip, hadamard.hip and fft_conv.hip share: the Philox draws, the clipped x0 of a restore step and the
+// update behind it.  All four files are compiled with -ffp-contract=off (Makefile): every product below rounds on its own.
 #pragma once
 #include "ddk_internal.h"
 
@@ -39,8 +39,8 @@ template <StepKind K>
 struct RestoreTraits {
     static constexpr bool RESTORE = K == StepKind::Restore || K == StepKind::RestoreMasked || K == StepKind::RestoreMultistep ||
                                     K == StepKind::RestoreNoisy || K == StepKind::RestoreGray || K == StepKind::RestoreBlur ||
-                                    K == StepKind::RestoreHadamard;
-    static constexpr bool PLANE = K == StepKind::RestoreBlur || K == StepKind::RestoreHadamard;      // the operator couples a whole plane: no n x n block, never the fused tail
+                                    K == StepKind::RestoreHadamard || K == StepKind::RestoreFFT;
+    static constexpr bool PLANE = K == StepKind::RestoreBlur || K == StepKind::RestoreHadamard || K == StepKind::RestoreFFT;      // the operator couples a whole plane: no n x n block, never the fused tail
     static constexpr bool MASK = RESTORE && K != StepKind::Restore && !PLANE;
     static constexpr bool MASK_REQUIRED = K == StepKind::RestoreMasked;
     static constexpr bool HIST = K == StepKind::RestoreMultistep;

@@ -89,7 +89,7 @@ struct ChainKey {
     const void* noise;                       // also in bufs; injected draws: no 16-step graph (see run_chain)
     int B, H, W, t_start, device;
     unsigned long long pack_epoch;
-    int restore_n = 0;                       // StepKind::RestoreHadamard: m, the measured coefficients per plane (the kernels are launched with it).
+    int restore_n = 0;                       // StepKind::RestoreFFT: 0, the kind says it (mask, twiddles and Yp are staged).  StepKind::RestoreHadamard: m, the measured coefficients per plane (the kernels are launched with it).
                                              // StepKind::Restore, RestoreMasked: the block (y and the mask are staged in the workspace; the kind
                                              // says whether a mask is present, so a masked and an unmasked chain never share a graph)
     bool restore_mask = false;               // StepKind::RestoreMultistep, RestoreNoisy, one kind with or without a mask: whether its kernels were given one
@@ -1771,8 +1771,17 @@ static CsStage cs_stage(size_t n, int H, int W) {
     const size_t y = al4((size_t)H * W);
     return {0, y, y + al4(n)};
 }
+// RestoreFFT (plane-wide): the mask [H W], the twiddles (max(H, W) / 2 complex), Yp of the latent's size and the complex T of twice it
+struct FftStage {
+    size_t mask, tw, yp, tmp;     // offsets in floats from the chain's extra area; total = tmp + 2 al4(n)
+};
+static FftStage fft_stage(size_t n, int H, int W) {
+    const size_t tw = al4((size_t)H * W), yp = tw + al4((size_t)(H > W ? H : W));
+    return {0, tw, yp, yp + al4(n)};
+}
 static size_t chain_extra_floats(const ddk_unet& u, int B, int H, int W, StepKind kind, int restore_n = 0) {
     const size_t n = al4((size_t)B * H * W * u.cfg.in_ch);
+    if (kind == StepKind::RestoreFFT) return fft_stage(n, H, W).tmp + 2 * al4(n);
     if (kind == StepKind::RestoreHadamard) return cs_stage(n, H, W).tmp + al4(n);
     if (kind == StepKind::RestoreBlur) return blur_stage(n, H, W).tmp + al4(n);
     if (kind == StepKind::Restore) return al4(n / 4);
@@ -1796,7 +1805,8 @@ static size_t sampler_bytes(const ddk_unet* u, int B, int H, int W, int t_start,
 //   Inpaint:   known and mask, copied in before the first op
 //   the restore kinds: (RestoreMultistep: the history, zeroed by every call as Multistep's, then) y and, when given, the mask,
 //              copied in before the first step (restore_stage's layout)
-//   RestoreBlur: the projections copied in and Yp formed (blur_stage); RestoreHadamard: perm and y copied in (cs_stage)
+//   RestoreBlur: the projections copied in and Yp formed (blur_stage); RestoreHadamard: perm and y copied in (cs_stage);
+//   RestoreFFT: the mask and the twiddles copied in and Yp formed (fft_stage)
 // The graph key: the kind, every table the step reads and the restore block; the staged operands live in the workspace, which is
 // in the key.
 static int sampler_chain(const ddk_sampler_args* a, const char* who, const int64_t* map, StepRule rule, ddk_stream_t s) {
@@ -1838,6 +1848,15 @@ static int sampler_chain(const ddk_sampler_args* a, const char* who, const int64
         DDK_HIP(hipMemcpyAsync(extra + g.y, rule.rst.y, (size_t)B * c.u->cfg.in_ch * rule.had.m * sizeof(float), hipMemcpyDeviceToDevice, c.st));
         rule.had = HadamardOps{reinterpret_cast<const int32_t*>(extra + g.perm), extra + g.tmp, rule.had.m};
         rule.rst = RestoreOps{extra + g.y, 0, H, W, 0, nullptr};
+    } else if (rule.kind == StepKind::RestoreFFT) {
+        // the mask and the twiddles copied in and Yp = Re F2^-1(P^ F2 y) / N formed here, before the first step and outside any captured
+        // one: rule.rst.y is the CALLER's y, rule.fft holds the caller's arrays
+        const FftStage g = fft_stage(al4(n), H, W);
+        DDK_HIP(hipMemcpyAsync(extra + g.mask, rule.fft.mask, (size_t)H * W * sizeof(float), hipMemcpyDeviceToDevice, c.st));
+        DDK_HIP(hipMemcpyAsync(extra + g.tw, rule.fft.tw, (size_t)(H > W ? H : W) * sizeof(float), hipMemcpyDeviceToDevice, c.st));
+        DDK_TRY(circular_conv(rule.rst.y, rule.fft.pinv, extra + g.tw, extra + g.yp, extra + g.tmp, B, H, W, c.u->cfg.in_ch, c.st));
+        rule.fft = FftOps{extra + g.mask, extra + g.tw, extra + g.tmp, nullptr};
+        rule.rst = RestoreOps{extra + g.yp, 0, H, W, 0, nullptr};
     } else if (restore_kind(rule.kind)) {
         const RestoreStage g = restore_stage(n, B, H, W, rule.kind, rule.rst.n);
         const size_t nn = (size_t)rule.rst.n * rule.rst.n, nm = (size_t)B * H * W / nn;      // one float per block: the mask, and the grey y
@@ -1862,14 +1881,14 @@ static int sampler_chain(const ddk_sampler_args* a, const char* who, const int64
 
     // the RestoreNoisy / RestoreGray tables share the Inpaint operands' storage (StepRule): each kind's key names its own
     const bool noisy = rule.kind == StepKind::RestoreNoisy || rule.kind == StepKind::RestoreGray;
-    const bool plane = rule.kind == StepKind::RestoreBlur || rule.kind == StepKind::RestoreHadamard;
+    const bool plane = rule.kind == StepKind::RestoreBlur || rule.kind == StepKind::RestoreHadamard || rule.kind == StepKind::RestoreFFT;
     const InpaintOps ik = noisy || plane ? InpaintOps{} : rule.inp;      // (the plane-wide kinds' operands are staged: the workspace names them)
     const NoisyTables nk = noisy ? rule.nsy : NoisyTables{};
     const ChainKey key{rule.kind,
                        {a->packed, a->x, rule.c_recip, rule.c_recipm1, rule.c1, rule.c2, rule.sigma, rule.c3, ik.ka, ik.kb, ik.ja, ik.jb, nk.lam,
                         nk.sgm},
                        a->workspace, a->noise, B, H, W, a->t_start, c.dev, c.u->pack_epoch,
-                       rule.kind == StepKind::RestoreHadamard ? rule.had.m : restore_kind(rule.kind) ? rule.rst.n : 0,      // RestoreBlur: 0, the kind says it
+                       rule.kind == StepKind::RestoreHadamard ? rule.had.m : restore_kind(rule.kind) ? rule.rst.n : 0,      // RestoreBlur, RestoreFFT: 0, the kind says it
                        (rule.kind == StepKind::RestoreMultistep || noisy) && rule.rst.mask != nullptr,
                        rule.kind == StepKind::RestoreGray ? rule.rst.gray : 0};
     return run_chain(*c.u, key, n_steps, a->use_graph != 0, one_step, c.st, who);
@@ -2137,6 +2156,40 @@ extern "C" int ddk_sampler_run_restore_cs(const ddk_sampler_args* a, const int64
     StepRule rule{};
     rule.kind = StepKind::RestoreHadamard;
     rule.had = HadamardOps{perm, nullptr, m};
+    rule.rst.y = y;
+    return sampler_chain(a, who, timestep_map, rule, s);
+}
+
+// DDNM deconvolution of a 2-D point-spread function with periodic boundary on a pixel-space model (section 3.18): the spaced sampler's
+// chain, every step ending in StepKind::RestoreFFT.  mask [H][W], P^ [H][W] complex, the twiddles and y (x's layout) are the caller's
+// device arrays; mask and twiddles are copied into the workspace and Yp = A+ y is formed there before the first step.  Plane-wide like
+// the blur kind: no step takes the fused tail.
+extern "C" size_t ddk_sampler_restore_fft_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start) {
+    if (check_shape(u, B, H, W) != DDK_OK || !restore_fft_shape_ok(H, W, u->cfg.in_ch)) return 0;
+    return sampler_bytes(u, B, H, W, t_start, StepKind::RestoreFFT);
+}
+extern "C" int ddk_sampler_restore_fft_tail_parts(const ddk_unet* u, int B, int H, int W) {
+    if (check_shape(u, B, H, W) != DDK_OK) return -1;
+    return fused_tail_parts(*u, B, H, W, u->dimp[1], StepKind::RestoreFFT);      // 0: final_tail_ok takes no plane-wide kind
+}
+extern "C" int ddk_sampler_run_restore_fft(const ddk_sampler_args* a, const int64_t* timestep_map, const float* mask, const float* P,
+                                           const float* twiddles, const float* y, ddk_stream_t s) {
+    const char* who = "sampler_restore_fft";
+    auto bad = [who](const char* what) {
+        set_error("bad argument: %s: %s", who, what);
+        return DDK_ERR_ARG;
+    };
+    if (!(a && a->unet && a->packed && a->x && a->workspace && mask && P && twiddles && y)) return bad("null pointer");
+    if (!(a->c_recip && a->c_recipm1 && a->c1 && a->c2 && a->sigma)) return bad("null schedule table");
+    if (a->noise) return bad("injected noise is not supported, noise must be NULL (Philox only)");
+    if (!(a->t_start >= a->t_end && a->t_end >= 0)) return bad("need t_start >= t_end >= 0");
+    if (!restore_fft_shape_ok(a->H, a->W, a->unet->cfg.in_ch)) return bad("H and W must be powers of two in [16, 256], the model's channels 1 to 8");
+    if (!(a->B > 0 && (long long)a->B * a->unet->cfg.in_ch <= 65535)) return bad("B channels must be in [1, 65535]");
+    if (!(aligned16(mask) && aligned16(P) && aligned16(twiddles) && aligned16(y))) return bad("alignment");
+    DDK_TRY(check_timestep_map(timestep_map, a->t_start, who));
+    StepRule rule{};
+    rule.kind = StepKind::RestoreFFT;
+    rule.fft = FftOps{mask, twiddles, nullptr, P};
     rule.rst.y = y;
     return sampler_chain(a, who, timestep_map, rule, s);
 }

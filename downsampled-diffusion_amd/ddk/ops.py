@@ -951,6 +951,59 @@ def p_sample_update_restore_cs_(x, eps_hat, y, perm, t, c_recip, c_recipm1, c1, 
     return x
 
 
+_FFT_TWIDDLES = {}
+
+
+def fft_twiddles(L, device):
+    """The device transform's twiddle table for a longest axis of L: fp32 [L/2, 2] (models/diffusion/psf.py twiddles), kept per
+    (L, device)."""
+    key = (int(L), str(device))
+    if key not in _FFT_TWIDDLES:
+        from models.diffusion.psf import twiddles
+        _FFT_TWIDDLES[key] = torch.from_numpy(twiddles(L)).to(device)
+    return _FFT_TWIDDLES[key]
+
+
+def _fft_operands(who, shape, device, **arrays):
+    """The checks the FFT ops share: NHWC shape [B,H,W,C]; each named array a contiguous fp32 tensor of the
+    given shape on the image's device.  Returns (twiddles, scratch): the scratch is the complex T of twice the image's size for planes
+    above 16384 pixels, else None."""
+    b, h, w, c = shape
+    for what, (v, want) in arrays.items():
+        if v is None or tuple(v.shape) != want or v.dtype != torch.float32 or not v.is_contiguous() or v.device != device:
+            raise L.DDKError(f"{who}: {what} must be a contiguous fp32 [{','.join(map(str, want))}] tensor on the image's device")
+    pow2 = lambda v: 16 <= v <= 256 and v & (v - 1) == 0
+    if not (pow2(h) and pow2(w)):
+        raise L.DDKError(f"{who}: H and W must be powers of two in [16, 256], got [{h},{w}]")
+    return fft_twiddles(max(h, w), device), (torch.empty((2, *shape), device=device, dtype=torch.float32) if h * w > 16384 else None)
+
+
+def circular_conv(x, S):
+    """out [B,H,W,C] = Re F2^-1(S . F2(x)) / (H W) per plane of x [B,H,W,C] (NHWC fp32): circular convolution through a complex FFT in
+    LDS.  S: fp32 [H,W,2], the complex multiplier (re, im) in natural frequency order -- psf.psf_spectrum for
+    the blur A, psf.psf_projection's P^ for A+.  H and W powers of two in [16, 256], C in 1..8."""
+    b, h, w, c = x.shape
+    tw, scratch = _fft_operands("circular_conv", tuple(x.shape), x.device, S=(S, (h, w, 2)))
+    out = torch.empty_like(x, dtype=torch.float32)
+    L.check(L.load().ddk_circular_conv(L.ptr(_f32(x)), L.ptr(S), L.ptr(tw), L.ptr(out), L.ptr(scratch), b, h, w, c, L.stream()), "circular_conv")
+    return out
+
+
+def p_sample_update_restore_fft_(x, eps_hat, mask, Yp, t, c_recip, c_recipm1, c1, c2, sigma, seed=0, stream_id=0):
+    """In-place DDNM deconvolution step of x [B,H,W,C] (NHWC) per sample row t[b]: the kept frequencies
+    (mask [H,W] fp32, nonzero = kept) of the clipped x0's 2-D spectrum are zeroed, Yp = A+ y [B,H,W,C] is added, then the ancestral
+    update with Philox draws runs on the result."""
+    if tuple(eps_hat.shape) != tuple(x.shape) or Yp is None or tuple(Yp.shape) != tuple(x.shape):
+        raise L.DDKError(f"p_sample_update_restore_fft: x {tuple(x.shape)}, eps_hat {tuple(eps_hat.shape)}, "
+                         f"Yp {None if Yp is None else tuple(Yp.shape)}")
+    b, h, w, c = x.shape
+    tw, scratch = _fft_operands("p_sample_update_restore_fft", tuple(x.shape), x.device, mask=(mask, (h, w)), Yp=(Yp, tuple(x.shape)))
+    L.check(L.load().ddk_p_sample_update_restore_fft(L.ptr(_f32(x)), L.ptr(_f32(eps_hat)), L.ptr(mask), L.ptr(tw), L.ptr(Yp), L.ptr(scratch),
+                                                     L.ptr(t), L.ptr(c_recip), L.ptr(c_recipm1), L.ptr(c1), L.ptr(c2), L.ptr(sigma), b, h, w, c,
+                                                     seed, stream_id, L.stream()), "p_sample_update_restore_fft")
+    return x
+
+
 def randn(shape, device, seed, step, stream_id=0):
     out = torch.empty(shape, device=device, dtype=torch.float32)
     L.check(L.load().ddk_randn(L.ptr(out), out.numel(), seed, step, stream_id, L.stream()), "randn")

@@ -32,7 +32,8 @@ SAMPLERS = {"smp": ("sample", "sampler", "sampler"), "sms": ("sample_multistep",
             "srg": ("sample_restore_gray", "sampler_restore_gray", "colourisation sampler"),
             "srb": ("sample_restore_blur", "sampler_restore_blur", "deblurring sampler"),
             "srq": ("sample_restore_sep", "sampler_restore_sep", "separable restoration sampler"),
-            "src": ("sample_restore_cs", "sampler_restore_cs", "compressed-sensing sampler")}
+            "src": ("sample_restore_cs", "sampler_restore_cs", "compressed-sensing sampler"),
+            "srf": ("sample_restore_fft", "sampler_restore_fft", "deconvolution sampler")}
 # workspace kinds whose captured step graphs point into them (the samplers', the likelihood sweep's): UnetPlan._workspace keeps up
 # to 3 of each
 CHAIN_WORKSPACES = (*SAMPLERS, "vsw")
@@ -364,20 +365,21 @@ class UnetPlan:
         "srb": ("sampler_run_restore_blur", "sampler_restore_blur_workspace_bytes", "sampler_restore_blur_tail_parts"),
         # the size-changing entry is the deblurring chain with a y of its own size: its workspace and tail queries serve both
         "srq": ("sampler_run_restore_sep", "sampler_restore_blur_workspace_bytes", "sampler_restore_blur_tail_parts"),
-        "src": ("sampler_run_restore_cs", "sampler_restore_cs_workspace_bytes", "sampler_restore_cs_tail_parts")}
+        "src": ("sampler_run_restore_cs", "sampler_restore_cs_workspace_bytes", "sampler_restore_cs_tail_parts"),
+        "srf": ("sampler_run_restore_fft", "sampler_restore_fft_workspace_bytes", "sampler_restore_fft_tail_parts")}
 
     def _restore_tail_parts(self, kind, b, h, w, n):
         return int(getattr(self._lib, "ddk_" + self.RESTORE_ENTRIES[kind][2])(self.handle, b, h, w, *(() if n is None else (int(n),))))
 
     def _sample_restore(self, kind, x, y, mask, n, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, head=(), masked=True,
-                        weights=None, blur=None, y_size=None, cs=None):
+                        weights=None, blur=None, y_size=None, cs=None, fft=None):
         """What the restoration samplers share: the checks on n, y, mask and the lam / sgm tables, then the chain.
         kind: the entry's key in SAMPLERS and RESTORE_ENTRIES; head: the names of the tables the C entry takes before y; masked: the
         entry takes a mask and n = 1 (which then needs one), and its workspace query takes n; weights: the grey entry's, whose y is
         [B,H/n,W/n] and whose n = 1 needs no mask; blur: the deblurring entry's matrices (P_h, P_w, Q_h, Q_w), whose operator has no
         block (n is None, no mask) and whose y has x's shape -- or, for the size-changing entry, y_size = (h, w) of y [B,h,w,in_ch],
         with Q_h [H,h] and Q_w [W,w]; cs: the compressed-sensing entry's (perm, m), whose operator has no block either and whose y is
-        [B,in_ch,m]."""
+        [B,in_ch,m]; fft: the deconvolution entry's (mask [H,W], P [H,W,2]), whose operator has no block and whose y has x's shape."""
         self._need_packed(kind)
         name = SAMPLERS[kind][0]
         gray = weights is not None
@@ -391,6 +393,13 @@ class UnetPlan:
             if perm is None or tuple(perm.shape) != (h * w,) or perm.dtype != torch.int32 or not perm.is_contiguous() or perm.device != x.device:
                 raise L.DDKError(f"{name}: perm must be a contiguous int32 [{h * w}] tensor on x's device")
             n = 1                 # no block, no mask
+        if fft is not None:
+            if not (h & (h - 1) == 0 and w & (w - 1) == 0 and 16 <= h <= 256 and 16 <= w <= 256 and 1 <= c <= 8):
+                raise L.DDKError(f"{name}: H and W must be powers of two in [16, 256] and the channels 1 to 8, got [{h},{w},{c}]")
+            for what, v, shape in zip(("mask", "P"), fft, ((h, w), (h, w, 2))):
+                if v is None or tuple(v.shape) != shape or v.dtype != torch.float32 or not v.is_contiguous() or v.device != x.device:
+                    raise L.DDKError(f"{name}: {what} must be a contiguous fp32 [{','.join(map(str, shape))}] tensor on x's device")
+            n = 1                 # no block, no mask of pixels: y has x's shape
         if gray and c != 3:
             raise L.DDKError(f"{name}: the grey operator needs a 3-channel map, got {c} channels")
         if gray and weights not in L.GRAY_WEIGHTS:
@@ -405,11 +414,11 @@ class UnetPlan:
                 if v is None or tuple(v.shape) != shape or v.dtype != torch.float32 or not v.is_contiguous() or v.device != x.device:
                     raise L.DDKError(f"{name}: {what} must be a contiguous fp32 [{shape[0]},{shape[1]}] tensor on x's device")
             n = 1                 # y has x's shape, or y_size
-        elif cs is None and (n not in ((1, 2, 4, 8) if masked else (2, 4, 8)) or h % n or w % n):
+        elif cs is None and fft is None and (n not in ((1, 2, 4, 8) if masked else (2, 4, 8)) or h % n or w % n):
             raise L.DDKError(f"{name}: n must be {'1, ' if masked else ''}2, 4 or 8 and divide H = {h} and W = {w}, got {n}")
-        if mask is None and n == 1 and not gray and blur is None and cs is None:
+        if mask is None and n == 1 and not gray and blur is None and cs is None and fft is None:
             raise L.DDKError(f"{name}: n = 1 needs a mask (nothing would be constrained)")
-        y_shape = (b, c, cs[1]) if cs is not None else (b, *y_size, c) if y_size is not None else (b, h // n, w // n) if gray else (b, h // n, w // n, c)
+        y_shape = (b, h, w, c) if fft is not None else (b, c, cs[1]) if cs is not None else (b, *y_size, c) if y_size is not None else (b, h // n, w // n) if gray else (b, h // n, w // n, c)
         for what, v, shape in (("y", y, y_shape), ("mask", mask, (b, h // n, w // n))):
             if v is not None and (tuple(v.shape) != shape or v.dtype != torch.float32 or not v.is_contiguous()):
                 raise L.DDKError(f"{what} must be a contiguous fp32 [{','.join(map(str, shape))}] tensor, got {tuple(v.shape)} {v.dtype}")
@@ -424,6 +433,9 @@ class UnetPlan:
             operands = (*(L.ptr(m) for m in blur), L.ptr(y), *(() if y_size is None else (int(y_size[0]), int(y_size[1]))))
         if cs is not None:
             operands = (L.ptr(y), L.ptr(cs[0]), int(cs[1]))
+        if fft is not None:
+            from . import ops
+            operands = (L.ptr(fft[0]), L.ptr(fft[1]), L.ptr(ops.fft_twiddles(max(h, w), x.device)), L.ptr(y))
         if gray:
             operands += (L.GRAY_WEIGHTS[weights],)
 
@@ -550,6 +562,22 @@ class UnetPlan:
         m = int(y.shape[2]) if y is not None and y.dim() == 3 else 0      # 0: refused below
         return self._sample_restore("src", x, y, None, None, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, masked=False,
                                     cs=(perm, m))
+
+    def restore_fft_tail_parts(self, b, h, w):
+        """Tiles per image of the fused tail of a deconvolution step on [b, h, w]: 0 for every shape (the operator couples a whole
+        plane), -1 for a shape the plan does not take."""
+        return self._restore_tail_parts("srf", b, h, w, None)
+
+    def sample_restore_fft_nhwc(self, x, y, mask, P, tables, t_start, t_end=0, seed=0, stream_id=0, use_graph=True, timesteps=None):
+        """DDNM deconvolution steps, A = circular convolution with a 2-D point-spread function, t_start .. t_end (inclusive), in
+        place on x [B,H,W,in_ch] (ddk_sampler_run_restore_fft).
+
+        y: the blurred images, contiguous fp32 with x's shape; mask: fp32 [H,W], 1 at the kept frequencies; P: fp32 [H,W,2], the
+        truncated reciprocal spectrum (models/diffusion/psf.py psf_operands).  Mask and twiddles are copied into the plan's "srf"
+        workspace and Yp = A+ y is formed there by every call, so a loop over images replays one cached graph.  H and W powers of two
+        in [16, 256].  tables / timesteps: as for sample_nhwc (plain, respaced or DDIM).  Philox only."""
+        return self._sample_restore("srf", x, y, None, None, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, masked=False,
+                                    fft=(mask, P))
 
     # ---------------------------------------------------------------- likelihood sweep
     VLB_STREAM_BIT = 1 << 31     # the sweep's Philox stream id is stream_id | this (csrc/ddk_internal.h VLB_STREAM_BIT)

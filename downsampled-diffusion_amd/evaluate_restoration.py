@@ -40,6 +40,12 @@ through utils/data.py; ``--max_batches`` keeps the first max_batches * batch_siz
     to [-1, 1].  The consistency is max |A(x_out) - y| in the measurement's own scale; ``method`` reads ``ddnm_cs`` and the settings
     gain ``ratio``, ``perm_seed`` and ``m``.  No ``--scale``, ``--mask``, ``--sigma_y``, ``--dpm_solver``, ``--method``, ``--kernel``
     or ``--tol``.
+  * ``--task deconv --psf P [--tol T]`` (DDPM checkpoints; section 3.18): the images are blurred by the 2-D point-spread function P
+    (``diag``, ``disk`` or a ``.npy`` file of a 2-D array with odd sides; periodic boundary) and ``model.deconvolve`` restores them
+    with ``--tol`` (default 0.03), ``--timestep_respacing``, ``--use_ddim`` and ``--eta``.  Baselines: the blurred image itself and
+    ``pinv``, A+ y clipped to [-1, 1].  The consistency is max |A+ A x_out - A+ y|; ``method`` reads ``ddnm_deconv`` and the settings
+    gain ``psf`` and ``tol``.  ``--psf`` belongs to this task alone; it takes no ``--scale``, ``--mask``, ``--sigma_y``,
+    ``--dpm_solver``, ``--method`` or ``--kernel``.
   * batch g draws x_T and its Philox key from ``--seed`` + g.
 
 Prints one JSON object, the settings that produced it (among them ``method`` and ``unet_forwards``, the UNet forwards per image, so
@@ -54,7 +60,7 @@ import time
 import numpy as np
 import torch
 
-from utils.restoration_metrics import BLUR_KERNELS, CS_TASK, DEBLUR_TASK, DOWNSAMPLES, GRAY_WEIGHTS, MASKS, METHODS, TASKS, evaluate_restoration, load_mask, report, to_u8
+from utils.restoration_metrics import BLUR_KERNELS, CS_TASK, DEBLUR_TASK, DECONV_TASK, DOWNSAMPLES, GRAY_WEIGHTS, MASKS, METHODS, TASKS, evaluate_restoration, load_mask, report, to_u8
 
 
 def parse_args(argv=None):
@@ -62,7 +68,7 @@ def parse_args(argv=None):
     ap.add_argument("--saved_model", default="celeba_x2")
     ap.add_argument("--synthetic", default=None, help="JSON config file: use closed-form synthetic weights, no checkpoint")
     ap.add_argument("--images", default=None, help="uint8 [N, H, W, C] .npy of the model's size (default: the dataset's test split)")
-    ap.add_argument("--task", required=True, choices=(*TASKS, DEBLUR_TASK, CS_TASK))
+    ap.add_argument("--task", required=True, choices=(*TASKS, DEBLUR_TASK, CS_TASK, DECONV_TASK))
     ap.add_argument("--mask", default=None, help=f"one of {', '.join(MASKS)} or a .npy file of {{0, 1}} (1 = known); inpaint: default "
                                                  "center; sr: masked super-resolution, the mask is of the pooled image (default: none)")
     ap.add_argument("--method", default=None, choices=METHODS, help="inpaint: repaint (default) or ddnm; sr: ddnm")
@@ -71,6 +77,7 @@ def parse_args(argv=None):
     ap.add_argument("--weights", default=None, choices=tuple(GRAY_WEIGHTS), help="colorize: the grey image's channel weights (default mean)")
     ap.add_argument("--kernel", default=None, choices=BLUR_KERNELS, help="deblur: the separable blur (required there)")
     ap.add_argument("--tol", type=float, default=None, help="deblur: singular values below tol * s_max are dropped, per axis (default 0.03)")
+    ap.add_argument("--psf", default=None, help="deconv: the 2-D point-spread function, diag, disk or a .npy file (required there)")
     ap.add_argument("--ratio", type=float, default=None, help="cs: the sampling ratio in (0, 1] (required there)")
     ap.add_argument("--perm_seed", type=int, default=None, help="cs: seed of the pixel permutation (default 0)")
     ap.add_argument("--timestep_respacing", default="", help='run K of the T steps: "N", "n1,n2,..." sections or (sr) "ddimN"')
@@ -89,6 +96,21 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.batch_size < 1 or (args.max_batches is not None and args.max_batches < 1):
         ap.error("--batch_size and --max_batches must be >= 1")
+    if args.psf is not None and args.task != DECONV_TASK:
+        ap.error("--psf belongs to --task deconv")
+    if args.task == DECONV_TASK:
+        if args.psf is None:
+            ap.error("--task deconv needs --psf: the point-spread function is part of the task, there is no default")
+        if args.psf not in ("diag", "disk") and not args.psf.endswith(".npy"):
+            ap.error("--psf must be diag, disk or a .npy file")
+        if args.method is not None or args.dpm_solver or args.sigma_y != 0.0 or args.mask is not None or args.scale is not None or \
+                args.kernel is not None:
+            ap.error("--task deconv has one method, ddnm on ancestral or DDIM steps, and takes no --method, --mask, --scale, --sigma_y, "
+                     "--dpm_solver or --kernel")
+        if args.tol is None:
+            args.tol = 3e-2
+        if not (0 <= args.tol < 1):
+            ap.error("--tol must be in [0, 1)")
     if (args.ratio is not None or args.perm_seed is not None) and args.task != CS_TASK:
         ap.error("--ratio and --perm_seed belong to --task cs")
     if args.task == CS_TASK:
@@ -112,7 +134,7 @@ def parse_args(argv=None):
         ap.error("--downsample bicubic takes no --mask, --dpm_solver or --sigma_y")
     if args.weights is not None and args.task != "colorize":
         ap.error("--weights belongs to --task colorize")
-    if (args.kernel is not None or args.tol is not None) and args.task != DEBLUR_TASK:
+    if (args.kernel is not None or args.tol is not None) and args.task not in (DEBLUR_TASK, DECONV_TASK):
         ap.error("--kernel and --tol belong to --task deblur")
     if args.task == DEBLUR_TASK:
         if args.kernel is None:
@@ -123,7 +145,7 @@ def parse_args(argv=None):
             ap.error("--tol must be in [0, 1)")
         if args.method != "ddnm" or args.dpm_solver or args.sigma_y != 0.0 or args.mask is not None or args.scale is not None:
             ap.error("--task deblur has one method, ddnm on ancestral or DDIM steps, and takes no --mask, --scale or --sigma_y")
-    elif args.task == CS_TASK:
+    elif args.task in (CS_TASK, DECONV_TASK):
         pass                      # checked above
     elif args.task == "sr":
         if args.scale is None:
@@ -180,6 +202,8 @@ def chain_options(args):
         kw.update(kernel=args.kernel, tol=args.tol)
     if args.task == CS_TASK:
         kw.update(ratio=args.ratio, perm_seed=args.perm_seed)
+    if args.task == DECONV_TASK:
+        kw.update(psf=args.psf, tol=args.tol)
     if args.dpm_solver:
         kw.update(dpm_solver=True)
     elif args.method == "ddnm":
@@ -250,7 +274,7 @@ def main():
     kw = chain_options(args)
     if args.task == "inpaint":
         kw["mask"] = args.mask if args.mask in MASKS else load_mask(args.mask, n, h, w, channels)
-    elif args.mask is not None and args.task not in (DEBLUR_TASK, CS_TASK):
+    elif args.mask is not None and args.task not in (DEBLUR_TASK, CS_TASK, DECONV_TASK):
         kw["sr_mask"] = args.mask if args.mask in MASKS else load_mask(args.mask, n, h // args.scale, w // args.scale, 1)
 
     print(f"Scoring {args.task} on {n} images with {'synthetic weights' if args.synthetic else args.saved_model}.")

@@ -218,6 +218,11 @@ class DownsampleDDPM(DDPM):
         raise ValueError("restore_cs: a DownsampleDDPM samples in a latent, and a Walsh-Hadamard transform of the latent is not one of the "
                          "image; compressed sensing needs a pixel model (DDPM)")
 
+    def deconvolve(self, y, psf=None, **kwargs):
+        """Not available, for deblur's reason: a convolution of the latent is not one of the image.  Always ValueError."""
+        raise ValueError("deconvolve: a DownsampleDDPM samples in a latent, and a point-spread function on the image has no such form there; "
+                         "deconvolution needs a pixel model (DDPM)")
+
     @torch.no_grad()
     def reconstruct(self, x, n):
         """dddpm.py:33-74 (visualisation only)."""

@@ -18,7 +18,7 @@ from ddk import ops
 from ddk.lib import DDKError
 from utils import flat_bits, reduce_mean, reduce_sum
 from models.utils import discretized_gaussian_log_likelihood, extract, l2_loss, noise_like, normal_kl
-from . import blur, hadamard, respace
+from . import blur, hadamard, psf, respace
 from .beta_schedule import make_beta_schedule
 
 OBJETIVE_NAMES = ['simple', 'hybrid', 'vlb']
@@ -864,6 +864,68 @@ class DDPM(nn.Module):
             "restore_cs", y, None, lambda: self._spaced_tables(respacing, ddim, eta) if spaced else (self._tables(), None), x_T, seed, op,
             lambda plan, x, yl, mk, tables, k_start, seed, use: plan.sample_restore_cs_nhwc(
                 x, yl, perm_dev(), tables, k_start, seed=seed, stream_id=sid, use_graph=self.use_graph, timesteps=use))
+
+    # ------------------------------------------------------------------ DDNM deconvolution (2-D point-spread function, periodic)
+    def _psf_operands(self, k, tol):
+        """{K, P, mask} of psf.psf_operands on the model's device (K^ and P^ as fp32 [H, W, 2], the mask as fp32 [H, W]), cached per
+        (taps, tol, device) like the spaced tables: repeated calls pass the same tensors."""
+        C, H, W = self.sample_shape
+        return self._cached_tables(('psf', k.tobytes(), k.shape, float(tol)),
+                                   lambda: ({n: torch.from_numpy(v) for n, v in zip(("K", "P", "mask"), psf.psf_operands(k, H, W, tol))}, None))[0]
+
+    def _deconvolve_args(self, y, k, tol, ddim, eta, unsupported):
+        """ValueError for anything deconvolve cannot take, before any device work.  Returns (y as float, the PSF as a float64 array)."""
+        who = "deconvolve"
+        if unsupported:
+            raise ValueError(f"{who}: {sorted(unsupported)} not accepted (DDNM runs ancestral or DDIM steps with Philox draws over the "
+                             f"whole schedule on an exact, unmasked measurement: no {', '.join(self.DEBLUR_UNSUPPORTED)})")
+        k = psf.psf_array(k)      # its own ValueErrors
+        if isinstance(tol, bool) or not isinstance(tol, (int, float, np.integer, np.floating)) or not (0 <= tol < 1):
+            raise ValueError(f"{who}: tol must be a real number in [0, 1), got {tol!r}")
+        if isinstance(eta, bool) or not isinstance(eta, (int, float, np.integer, np.floating)) or eta < 0 or (eta != 0 and not ddim):
+            raise ValueError(f"{who}: eta = {eta!r} needs ddim=True and eta >= 0")
+        C, H, W = self.sample_shape
+        if not psf.size_ok(C, H, W):
+            raise ValueError(f"{who}: the image size must be powers of two in [16, 256] with 1 to 8 channels, this model's is {C} x {H} x {W}")
+        if k.shape[0] > H or k.shape[1] > W:
+            raise ValueError(f"{who}: a {k.shape[0]} x {k.shape[1]} point-spread function does not fit a {H} x {W} image")
+        if not torch.is_tensor(y) or y.dim() != 4 or y.shape[0] < 1 or list(y.shape[1:]) != [C, H, W] or not y.is_floating_point():
+            raise ValueError(f"{who}: y must be a float [B, {C}, {H}, {W}] tensor, got "
+                             f"{tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
+        if not bool(torch.isfinite(y).all()):
+            raise ValueError(f"{who}: y must be finite")
+        return y.float(), k
+
+    @torch.no_grad()
+    def deconvolve(self, y, psf, *, tol=blur.DEFAULT_TOL, respacing=None, ddim=False, eta=0.0, x_T=None, seed=None, **unsupported):
+        """Zero-shot deconvolution with DDNM (Wang, Yu, Zhang 2023): an image [B, C, H, W] whose circular
+        convolution with a 2-D point-spread function (periodic boundary, correlation form as blur.blur_matrix) is y [B, C, H, W]
+        (in [-1, 1]).  psf: "diag" (9 x 9, a 45 degree motion), "disk" (9 x 9 defocus of radius 3.5) or a 2-D array with odd sides no
+        larger than the image.  tol: frequencies whose |K^| is below tol * max |K^| are dropped from the pseudo-inverse.  Every step
+        of the chain (all T steps, or respacing's K; ancestral, or DDIM with eta) replaces the range-space part of its clipped x0 by
+        A+ y before the update, so the result's projection A+ A x equals A+ y up to fp32 rounding, and A(x) = y as far as the
+        truncation allows.  x_T: the start state; seed: the Philox key (default: drawn from torch's generator).  H and W powers of
+        two in [16, 256].  solver / noise / early_stop / paste / mask / sigma_y raise ValueError, as do an unknown preset, a bad PSF,
+        tol or eta and a non-finite or misshapen y, before any device work."""
+        y, k = self._deconvolve_args(y, psf, tol, ddim, eta, unsupported)
+        spaced = respacing is not None or ddim or eta != 0
+        sid = int(self.rng_stream_id)
+        m, yp = [], []            # the operands on the model's device and the Python loop's Yp = A+ y, made at the first use
+
+        def operands():
+            if not m:
+                m.append(self._psf_operands(k, tol))
+            return m[0]
+
+        def op(x, e, yl, mk, t, tables, seed):
+            if not yp:
+                yp.append(ops.circular_conv(yl, operands()["P"]))
+            ops.p_sample_update_restore_fft_(x, e, operands()["mask"], yp[0], t, **tables, seed=seed, stream_id=sid)
+        return self._ddnm_loop(
+            "deconvolve", y, None, lambda: self._spaced_tables(respacing, ddim, eta) if spaced else (self._tables(), None), x_T, seed, op,
+            lambda plan, x, yl, mk, tables, k_start, seed, use: plan.sample_restore_fft_nhwc(
+                x, yl, operands()["mask"], operands()["P"], tables, k_start, seed=seed, stream_id=sid, use_graph=self.use_graph,
+                timesteps=use))
 
     @torch.no_grad()
     def reconstruct(self, x, n):

@@ -17,6 +17,7 @@ TASKS = ("inpaint", "sr", "colorize")
 DEBLUR_TASK = "deblur"          # evaluate_restoration's fourth task (section 3.14), with kernels of its own instead of masks and scales
 BLUR_KERNELS = ("uniform", "gauss", "aniso")
 CS_TASK = "cs"                  # ... and its fifth (section 3.17), with a sampling ratio and a permutation seed
+DECONV_TASK = "deconv"          # ... and its sixth (section 3.18), with a 2-D point-spread function
 METHODS = ("repaint", "ddnm")
 GRAY_WEIGHTS = {"mean": (1.0 / 3.0, 1.0 / 3.0, 1.0 / 3.0), "luma": (0.299, 0.587, 0.114)}     # DDPM.colorize's two operators
 DOWNSAMPLES = ("mean", "bicubic")     # task "sr": block means (section 3.6) or the antialiased bicubic reduction (section 3.15)
@@ -174,6 +175,10 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
     (ops.hadamard_measure), and ``model.restore_cs`` restores it (``chain``: respacing, ddim, eta).  Baseline: "adjoint", A^T y
     clipped to [-1, 1].  consistency: per image max |A(x_out) - y| of the model's float output, in the measurement's own scale.  The
     returned method is "ddnm_cs", and "ratio", "perm_seed" and "m" are returned.
+    task "deconv" (pixel models; section 3.18): the images are blurred by the 2-D point-spread function ``psf`` ("diag", "disk", a
+    .npy path or an array; periodic boundary) on the device (ops.circular_conv) and ``model.deconvolve`` restores them (``tol``;
+    ``chain``: respacing, ddim, eta).  Baselines: "blurred" and "pinv", A+ y clipped to [-1, 1].  consistency: per image
+    max |A+ A x_out - A+ y| of the model's float output.  The returned method is "ddnm_deconv", and "psf" and "tol" are returned.
     downsample "bicubic" (task "sr" on a pixel model, without sr_mask, dpm_solver or sigma_y; section 3.15): the images are reduced
     by the antialiased bicubic matrix (``resize``) instead of pooled and ``model.super_resolve(downsample="bicubic")`` restores them.
     The baselines stay (replicate, bicubic upsampling); consistency / consistency_u8 are max |A(x_out) - y| in uint8 levels with that
@@ -194,6 +199,14 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
         if "kernel" not in chain or not hasattr(model, "deblur"):
             raise ValueError("task 'deblur' needs a kernel and a model with a deblur method (a pixel DDPM)")
         return _evaluate_deblur(model, images_uint8, batch_size=batch_size, seed=seed, **chain)
+    if task == DECONV_TASK:
+        if method not in (None, "ddnm") or dpm_solver or sigma_y or sr_mask is not None or scale is not None or "kernel" in chain:
+            raise ValueError("task 'deconv' has one method, ddnm on ancestral or DDIM steps, and no mask, scale, kernel or sigma_y")
+        if "psf" not in chain or not hasattr(model, "deconvolve"):
+            raise ValueError("task 'deconv' needs a psf and a model with a deconvolve method (a pixel DDPM)")
+        return _evaluate_deconv(model, images_uint8, batch_size=batch_size, seed=seed, **chain)
+    if "psf" in chain:
+        raise ValueError("psf belongs to task 'deconv'")
     if "kernel" in chain or "tol" in chain:
         raise ValueError("kernel and tol belong to task 'deblur'")
     if task == CS_TASK:
@@ -205,7 +218,7 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
     if "ratio" in chain or "perm_seed" in chain:
         raise ValueError("ratio and perm_seed belong to task 'cs'")
     if task not in TASKS:
-        raise ValueError(f"unknown task {task!r}: one of {(*TASKS, DEBLUR_TASK, CS_TASK)}")
+        raise ValueError(f"unknown task {task!r}: one of {(*TASKS, DEBLUR_TASK, CS_TASK, DECONV_TASK)}")
     if task == "colorize":
         return _evaluate_colorize(model, images_uint8, batch_size=batch_size, seed=seed, scale=1 if scale is None else scale, method=method,
                                   sr_mask=sr_mask, dpm_solver=dpm_solver, sigma_y=sigma_y, **chain)
@@ -418,6 +431,41 @@ def _evaluate_cs(model, images_uint8, *, batch_size, seed, ratio, perm_seed=0, *
                  consistency=(A(x_out) - y_all).abs().amax(dim=(1, 2)).double().numpy())
     methods = {name: _score(ops, img, ref, None, device) for name, img in images.items()}
     return dict(n_images=n, method="ddnm_cs", methods=methods, images={k: v.numpy() for k, v in images.items()}, **extra)
+
+
+@torch.no_grad()
+def _evaluate_deconv(model, images_uint8, *, batch_size, seed, psf, tol=3e-2, **chain):
+    """evaluate_restoration's task "deconv" (see there)"""
+    from ddk import ops
+    from models.diffusion import psf as P
+    x_all = from_u8(images_uint8)
+    ref = torch.as_tensor(images_uint8).contiguous()
+    n, c, h, w = x_all.shape
+    if n < 1 or batch_size < 1:
+        raise ValueError("evaluate_restoration needs at least one image and batch_size >= 1")
+    if not P.size_ok(c, h, w):
+        raise ValueError(f"task 'deconv' needs H and W powers of two in [16, 256] and 1 to 8 channels, got {c} x {h} x {w}")
+    name = psf if isinstance(psf, str) else "custom"
+    k = P.psf_array(np.load(psf) if isinstance(psf, str) and psf.endswith(".npy") else psf)
+    device = model.betas.device
+    Kd, Pd, Md, _ = (torch.from_numpy(v).to(device) for v in P.psf_operands(k, h, w, tol))
+    Md = torch.stack([Md, torch.zeros_like(Md)], dim=-1).contiguous()      # the projection A+ A as a multiplier
+    batches = lambda S, v: torch.cat([ops.nhwc_to_nchw(ops.circular_conv(ops.nchw_to_nhwc(v[i:i + batch_size].to(device).contiguous()), S)).cpu()
+                                      for i in range(0, n, batch_size)])
+    y_all = batches(Kd, x_all)
+    yp_all = batches(Pd, y_all)
+    K = len(model._spaced_tables(chain.get("respacing"), chain.get("ddim", False), chain.get("eta", 0.0))[1]) \
+        if chain.get("respacing") is not None or chain.get("ddim") else int(model.timesteps)
+    images = {"blurred": to_u8(y_all.clamp(-1, 1)), "pinv": to_u8(yp_all.clamp(-1, 1))}
+    outs = []
+    for g, i in enumerate(range(0, n, batch_size)):
+        torch.manual_seed(seed + g)               # x_T and the Philox key of batch g
+        outs.append(model.deconvolve(y_all[i:i + batch_size].to(device), k, tol=tol, **chain).float().cpu())
+    x_out = torch.cat(outs)
+    images = dict(restored=to_u8(x_out), **images)
+    extra = dict(unet_forwards=K, psf=name, tol=float(tol), consistency=(batches(Md, x_out) - yp_all).abs().amax(dim=(1, 2, 3)).double().numpy())
+    methods = {name: _score(ops, img, ref, None, device) for name, img in images.items()}
+    return dict(n_images=n, method="ddnm_deconv", methods=methods, images={k: v.numpy() for k, v in images.items()}, **extra)
 
 
 def report(result):

@@ -425,6 +425,29 @@ int ddk_hadamard_adjoint(const float* y, const int32_t* perm, float* out, float*
 int ddk_p_sample_update_restore_cs(float* x, const float* eps_hat, const float* y, const int32_t* perm, float* scratch, const int64_t* t,
                                    const float* c_recip, const float* c_recipm1, const float* c1, const float* c2, const float* sigma, int B, int H,
                                    int W, int channels, int m, uint64_t seed, uint32_t stream_id, ddk_stream_t s);
+/* Circular convolution through the 2-D Fourier basis, per image b and channel c of an NHWC fp32 tensor
+ * x [B][H][W][channels]:
+ *   out = Re F2^-1(S . F2(x)) / (H W),   F2 the unnormalised 2-D DFT, S [H][W] complex fp32 (re, im interleaved), natural frequency order.
+ * With S = F2 of a point-spread function embedded with its centre at (0, 0) this is the blur A with periodic boundary; with the
+ * truncated reciprocal spectrum it is A+ (models/diffusion/psf.py).  A complex FFT in LDS: decimation in frequency forward, decimation
+ * in time back, radix-2 arithmetic in a fixed order, no atomics: results are bit-identical run to run.  twiddles: max(H, W) / 2 complex
+ * fp32 (re, im), exp(-2 pi i j / max(H, W)), computed in float64 and rounded.  A plane of at most 16384 pixels takes one launch, a
+ * workgroup per (image, channel); a larger one takes three through `scratch`, a device array of twice x's size that may be NULL for
+ * the smaller planes.  out may be x.  H and W powers of two in [16, 256], channels in 1..8, B channels <= 65535; x, S, twiddles, out and
+ * scratch 16-byte aligned.  Anything else is DDK_ERR_ARG and runs no kernel. */
+int ddk_circular_conv(const float* x, const float* S, const float* twiddles, float* out, float* scratch, int B, int H, int W, int channels,
+                      ddk_stream_t s);
+/* One DDNM deconvolution step on its own (ddk_sampler_run_restore_fft).  Per sample b with row t[b]:
+ *   x0  = clamp(c_recip x - c_recipm1 eps_hat, -1, 1);  sg = t > 0 ? sigma : 0;
+ *   X^  = F2(x0);  W^ = mask ? 0 : X^                   (per channel; a select, no arithmetic)
+ *   x0' = Re F2^-1(W^) / (H W) + Yp                     (1 / (H W) is a power of two; not clamped again)
+ *   x   = (c1 x0' + c2 x) + sg z.
+ * mask [H][W] fp32 is nonzero at the kept frequencies (natural order), Yp = A+ y has x's layout, z is the Philox draw of
+ * ddk_p_sample_update_restore.  Launches, scratch, twiddles, shapes and alignment as ddk_circular_conv.  Anything else is DDK_ERR_ARG;
+ * on an error x is not touched. */
+int ddk_p_sample_update_restore_fft(float* x, const float* eps_hat, const float* mask, const float* twiddles, const float* Yp, float* scratch,
+                                    const int64_t* t, const float* c_recip, const float* c_recipm1, const float* c1, const float* c2,
+                                    const float* sigma, int B, int H, int W, int channels, uint64_t seed, uint32_t stream_id, ddk_stream_t s);
 /* The end of a forward in one launch (unet.py:69-72 behind the final Block's conv; ddpm.py:203-227): GroupNorm from the conv's
  * partials -> Mish -> 1x1 projection to n_out <= 8 channels (w [n_out][C], bias [n_out]) -> eps_hat; eps_out and / or x may be
  * given: eps_out [B][HW][n_out] receives eps_hat, x [B][HW][n_out] gets the reverse-step update of ddk_p_sample_update in place
@@ -744,6 +767,21 @@ int ddk_sampler_run_restore_sep(const ddk_sampler_args* a, const int64_t* timest
 size_t ddk_sampler_restore_cs_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start);
 int ddk_sampler_restore_cs_tail_parts(const ddk_unet* u, int B, int H, int W);
 int ddk_sampler_run_restore_cs(const ddk_sampler_args* a, const int64_t* timestep_map, const float* y, const int32_t* perm, int m, ddk_stream_t s);
+/* Zero-shot deconvolution on a pixel-space model: DDNM for A = circular convolution with a 2-D point-spread function (DESIGN.md section
+ * 3.18).  The chain and tables of ddk_sampler_run_spaced (plain, respaced ancestral or DDIM), every step being
+ * ddk_p_sample_update_restore_fft's.  mask [H][W] fp32, P [H][W] complex fp32 (the truncated reciprocal spectrum), twiddles (as
+ * ddk_circular_conv) and y (x's layout) are device arrays read before the first step only: mask and twiddles are copied into the
+ * workspace and Yp = Re F2^-1(P . F2 y) / (H W) is formed there, outside any captured step, so a loop over image batches replays one
+ * cached graph.  The workspace (ddk_sampler_restore_fft_workspace_bytes; 0 for a shape the kind does not take) holds
+ * ddk_sampler_workspace_bytes plus the mask (H W floats), the twiddles (max(H, W) floats), Yp (the latent's size) and the complex T
+ * (twice the latent's size), each rounded up to four floats.  a->noise must be NULL (Philox only).  H and W powers of two in [16, 256],
+ * a model of 1..8 channels, else DDK_ERR_ARG.  The kind couples a whole plane, so no step takes the fused tail:
+ * ddk_sampler_restore_fft_tail_parts is 0 for every shape (-1 for a shape the plan does not take).  Graphs are cached under a chain kind
+ * of their own. */
+size_t ddk_sampler_restore_fft_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start);
+int ddk_sampler_restore_fft_tail_parts(const ddk_unet* u, int B, int H, int W);
+int ddk_sampler_run_restore_fft(const ddk_sampler_args* a, const int64_t* timestep_map, const float* mask, const float* P,
+                                const float* twiddles, const float* y, ddk_stream_t s);
 /* Drops the plan's cached sampler and likelihood-sweep graphs and shift table (waits for the device when graphs exist). */
 int ddk_sampler_invalidate(ddk_unet* u);
 /* Drops only the cached graphs (and shift table) that live in / point into `workspace`, after waiting for the launches of
