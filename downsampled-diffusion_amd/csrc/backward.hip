@@ -115,7 +115,7 @@ __global__ __launch_bounds__(NT) void gn_train_kernel(const float* __restrict__ 
         }
     }
     const float inv_n = 1.0f / (float)(HW * cpg);
-    const float mean = block_sum(s, red) * inv_n;
+    const float mean = block_sum(s, red) / (float)(HW * cpg);      // (divided: the mean of a constant group is that constant exactly)
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < VPT; ++i) {
@@ -125,7 +125,7 @@ __global__ __launch_bounds__(NT) void gn_train_kernel(const float* __restrict__ 
             q += (a * a + bb * bb) + (c * c + d * d);
         }
     }
-    const float var = block_sum(q, red) * inv_n;
+    const float var = block_sum(q, red) / (float)(HW * cpg);
     const float rstd = 1.0f / sqrtf(var + eps);
     const int cu_t = threadIdx.x - div_upr((int)threadIdx.x, upr) * upr;  // NT % upr == 0: every unit of this thread has the same channel quad
     const int c0 = g * cpg + cu_t * 4;
@@ -562,7 +562,8 @@ __global__ __launch_bounds__(256) void chan_layernorm_bwd_kernel(const float* __
         const float sigma = sqrtf(q / (float)C), sden = sigma + eps;
         const float inv_s = 1.0f / sden;
         const float k1 = t1 / (float)C * inv_s;
-        const float k2 = t2 / ((float)C * sigma * sden * sden);
+        // a constant pixel: sigma == 0 and every d == 0, the term d * k2 has the limit 0 (0 / 0 made the whole row NaN)
+        const float k2 = sigma > 0.f ? t2 / ((float)C * sigma * sden * sden) : 0.f;
         if (ok) {
 #pragma unroll
             for (int i = 0; i < VPL; ++i) {
@@ -1203,7 +1204,7 @@ __global__ __launch_bounds__(256) void chan_layernorm_generic_bwd_kernel(const f
         }
         q = wave_sum(q); t1 = wave_sum(t1); t2 = wave_sum(t2);
         const float sigma = sqrtf(q / (float)C), sden = sigma + eps, inv_s = 1.0f / sden;
-        const float k1 = t1 / (float)C * inv_s, k2 = t2 / ((float)C * sigma * sden * sden);
+        const float k1 = t1 / (float)C * inv_s, k2 = sigma > 0.f ? t2 / ((float)C * sigma * sden * sden) : 0.f;   // (constant pixel: limit 0)
 #pragma unroll
         for (int i = 0; i < NS; ++i) {
             const int c = lane + 64 * i;

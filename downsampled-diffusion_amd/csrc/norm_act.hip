@@ -54,8 +54,10 @@ __global__ __launch_bounds__(NT) void gn_mish_resident_kernel(const float* __res
             v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
         }
     }
-    const float inv_n = 1.0f / (float)(HW * cpg);
-    const float mean = block_sum(s, red) * inv_n;
+    // divided, not multiplied by 1 / n: for an n that is no power of two 1 / n is rounded, and the mean of a constant group must be
+    // that constant exactly (x - mean is multiplied by rstd ~ 316 where var << eps)
+    const float n = (float)(HW * cpg);
+    const float mean = block_sum(s, red) / n;
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < VPT; ++i) {
@@ -65,7 +67,7 @@ __global__ __launch_bounds__(NT) void gn_mish_resident_kernel(const float* __res
             q += (a * a + bb * bb) + (c * c + d * d);
         }
     }
-    const float var = block_sum(q, red) * inv_n;
+    const float var = block_sum(q, red) / n;
     const float rstd = 1.0f / sqrtf(var + eps);
 #pragma unroll
     for (int i = 0; i < VPT; ++i) {
