@@ -349,6 +349,17 @@ struct FftOps {
     const float* pinv;            // host side only: P^ [H][W] complex, from which the chain entry forms Yp = A+ y before the first step
 };
 static_assert(sizeof(FftOps) <= sizeof(InpaintOps), "FftOps shares the Inpaint operands' storage: StepRule must not grow");
+// DDNM+ deconvolution of a noisy blurred image: FftOps, then the per-frequency gain and the per-row noise scale.
+// The spectrum of A+ y rides in rst.y.
+struct FftNoisyOps {
+    const float* mask;            // as FftOps
+    const float* tw;              // as FftOps
+    float* tmp;                   // T, and behind it T2 of the same size ([2][B][C][H W] complex); multi-launch form only
+    const float* gain;            // [H][W], natural frequency order: 1 / |K^| where kept, 0 elsewhere
+    const float* nsc;             // per row t[b]: |c1| sigma_y
+    const float* pinv;            // host side only: P^ [H][W] complex, from which the chain entry forms the spectrum of A+ y before the first step
+};
+static_assert(sizeof(FftNoisyOps) <= sizeof(InpaintOps), "FftNoisyOps shares the Inpaint operands' storage: StepRule must not grow");
 constexpr uint32_t INPAINT_Z2_BIT = 0x40000000u;   // Philox stream of the known region's draw: stream_id | this
 constexpr uint32_t INPAINT_Z3_BIT = 0x20000000u;   // ... and of the jump's: stream_id | this (so stream_id < 2^29)
 // zero-shot super-resolution (DDNM for A = n x n average pooling): the low-resolution image and the block
@@ -404,14 +415,19 @@ enum class StepKind {
                   // (DESIGN.md section 3.17): x0' = A^T y + (I - A^T A) x0, a select between two transforms, then Restore's update.
                   // Plane-wide: hadamard.hip's kernels, never the fused tail: c_recip .. sigma, had, rst.y = y [B][C][m], rst.H, rst.W;
                   // Philox only
-    RestoreFFT    // DDNM deconvolution, A = circular convolution with a 2-D point-spread function:
+    RestoreFFT,   // DDNM deconvolution, A = circular convolution with a 2-D point-spread function:
                   // x0' = Re F2^-1(M ? 0 : F2 x0) / N + Yp, a select between two complex FFTs in LDS, then Restore's update.  Plane-wide:
                   // fft_conv.hip's kernels, never the fused tail: c_recip .. sigma, fft, rst.y = Yp (x's layout), rst.H, rst.W; Philox only
-                  // (last, so that the kinds above keep their values and their kernels' names)
+                  // (behind every older kind, so that the kinds above keep their values and their kernels' names)
+    RestoreFFTNoisy  // DDNM+ for RestoreFFT's operator and a blurred image with noise of standard deviation sigma_y (DESIGN.md section
+                  // 3.19): per frequency, the correction scaled by lam and the draw shaped by phi between the same two FFTs.  Plane-wide:
+                  // fft_conv.hip's kernels, never the fused tail: c_recip .. sigma, fnz, rst.y = the spectrum of A+ y ([B][C][H W]
+                  // complex, the transform's order), rst.H, rst.W; Philox only (last, for the same reason)
 };
 inline bool restore_kind(StepKind k) {       // the kinds whose step carries a DDNM constraint (RestoreOps)
     return k == StepKind::Restore || k == StepKind::RestoreMasked || k == StepKind::RestoreMultistep || k == StepKind::RestoreNoisy ||
-           k == StepKind::RestoreGray || k == StepKind::RestoreBlur || k == StepKind::RestoreHadamard || k == StepKind::RestoreFFT;
+           k == StepKind::RestoreGray || k == StepKind::RestoreBlur || k == StepKind::RestoreHadamard || k == StepKind::RestoreFFT ||
+           k == StepKind::RestoreFFTNoisy;
 }
 struct StepRule {
     StepKind kind;
@@ -431,6 +447,7 @@ struct StepRule {
         BlurOps blr;              // RestoreBlur
         HadamardOps had;          // RestoreHadamard
         FftOps fft;               // RestoreFFT
+        FftNoisyOps fnz;          // RestoreFFTNoisy
     };
     const VlbStep* vlb;           // host side only
     RestoreOps rst;
@@ -451,7 +468,7 @@ struct ChainHooks {
     uint32_t stream_id;
 };
 // the unfused tail's last kernel, given eps_hat in memory: the rule's update of x (Ancestral, Multistep, Inpaint, Restore, RestoreMasked,
-// RestoreMultistep, RestoreNoisy, RestoreGray, RestoreBlur, RestoreHadamard, RestoreFFT) or the sweep's
+// RestoreMultistep, RestoreNoisy, RestoreGray, RestoreBlur, RestoreHadamard, RestoreFFT, RestoreFFTNoisy) or the sweep's
 // reduction of the step's terms (Vlb); `who` names the caller in messages
 int p_update(const StepRule& r, const float* eps_hat, const int64_t* t, int B, long long per, const ChainHooks& h, hipStream_t st,
              const char* who = "p_update");
@@ -477,6 +494,10 @@ bool restore_fft_plane_form(int H, int W);
 const char* circular_conv_fault(const void* in, const void* mul, const void* tw, const void* out, const void* scratch, int B, int H, int W, int C);
 int circular_conv(const float* in, const float* mul, const float* tw, float* out, float* scratch, int B, int H, int W, int C, hipStream_t st);
 int fft_conv_init_device();
+// ... the RestoreFFTNoisy kind's step (the same shapes; a plane above the plane form needs fnz.tmp of twice T's size), and the forward
+// half of circular_conv that forms the spectrum of A+ y: out [B][C][H W] complex = mul . F2(in) in the transform's order
+int p_update_restore_fft_noisy(const StepRule& r, const float* eps_hat, const int64_t* t, int B, int channels, const ChainHooks& h, hipStream_t st);
+int circular_spectrum(const float* in, const float* mul, const float* tw, float* out, float* scratch, int B, int H, int W, int C, hipStream_t st);
 int randn(float* out, long long n, uint64_t seed, uint32_t step, uint32_t stream_id, hipStream_t st);
 int vlb_sweep_slots_unfused(int B, long long per);
 int vlb_step_input(const VlbStep& v, const float* sqrt_acp, const float* sqrt_1m_acp, const int64_t* chain_state, int B, long long per,

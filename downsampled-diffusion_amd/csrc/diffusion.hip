@@ -174,6 +174,7 @@ __global__ __launch_bounds__(256) void p_update_kernel(const StepRule r, const f
 //   RestoreBlur       PLANE: no block at all -- A is a separable blur, x0' = (x0 - P_h x0 P_w^T) + Yp, the kernels in separable.hip
 //   RestoreHadamard   PLANE: A is the first m rows of a plane's permuted Walsh-Hadamard transform, the kernels in hadamard.hip
 //   RestoreFFT        PLANE: A is a circular convolution with a 2-D point-spread function, the kernels in fft_conv.hip
+//   RestoreFFTNoisy   PLANE: RestoreFFT's operator, DDNM+ per frequency, the kernels in fft_conv.hip
 // MASK: the block's (n = 1: the pixel's) mask value, 1 where no mask was given, selects between x0' and x0 -- a select, never a blend,
 // so whatever an unmeasured y holds (NaN included) reaches no result.  HIST: DPM-Solver++(2M)'s history term in the place of the draw,
 // the history then holding x0'.  NOISY (DDNM+): the correction scaled by the row's lam and the draw of a measured element by the row's
@@ -762,6 +763,17 @@ static const char* restore_rule_fault(const StepRule& r, long long per) {
         if (!(aligned16(o.y) && aligned16(r.fft.mask) && aligned16(r.fft.tw) && aligned16(r.fft.tmp))) return "alignment";
         return nullptr;
     }
+    if (r.kind == StepKind::RestoreFFTNoisy) {   // plane-wide: rst.y is the spectrum of A+ y, the mask, the twiddles, the scratch, gain and nsc in fnz
+        if (!(o.y && r.sigma && r.fnz.mask && r.fnz.tw && r.fnz.gain && r.fnz.nsc)) return "null pointer";
+        if (r.noise) return "no injected noise (Philox only)";
+        if (!(o.H > 0 && o.W > 0) || per % ((long long)o.H * o.W)) return "per must be H * W * channels";
+        const long long ch = per / ((long long)o.H * o.W);
+        if (ch > 8 || !restore_fft_shape_ok(o.H, o.W, (int)ch)) return "the deconvolution step needs H and W powers of two in [16, 256] and 1 to 8 channels";
+        if (!restore_fft_plane_form(o.H, o.W) && !r.fnz.tmp) return "a plane above 16384 pixels needs the scratch for T and T2";
+        if (!(aligned16(o.y) && aligned16(r.fnz.mask) && aligned16(r.fnz.tw) && aligned16(r.fnz.tmp) && aligned16(r.fnz.gain) && aligned16(r.fnz.nsc)))
+            return "alignment";
+        return nullptr;
+    }
     const bool hist = r.kind == StepKind::RestoreMultistep, gray = r.kind == StepKind::RestoreGray,
                noisy = gray || r.kind == StepKind::RestoreNoisy, n1 = r.kind != StepKind::Restore;
     if (!(o.y && (hist ? r.c3 && r.x0_hist : r.sigma != nullptr) && (!noisy || (r.nsy.lam && r.nsy.sgm)) &&
@@ -799,7 +811,7 @@ bool final_tail_ok(int HW, int C, int groups, int n_out, int np, StepKind kind, 
     if (n_out < 1 || n_out > 8 || (128 * n_out) % 4) return false;
     if (kind == StepKind::RestoreBlur) return false;                     // plane-wide: a 128-pixel tile cannot form P_h x0 P_w^T
     if (kind == StepKind::RestoreHadamard) return false;                 // plane-wide: nor a plane's Walsh-Hadamard transform
-    if (kind == StepKind::RestoreFFT) return false;                      // plane-wide: nor a plane's Fourier transform
+    if (kind == StepKind::RestoreFFT || kind == StepKind::RestoreFFTNoisy) return false;      // plane-wide: nor a plane's Fourier transform
     if (kind == StepKind::RestoreGray && n_out != 3) return false;       // the grey operator is over a pixel's three colours
     // the restore tail forms block means from the tile's x0 in LDS: the 128-pixel tile must hold whole rows of n x n blocks
     // (the masked kind the same for n >= 2; its n = 1 is pointwise)
@@ -865,6 +877,7 @@ int final_tail(const TailIn& in, const StepRule& r, const int64_t* t, const Chai
         case StepKind::RestoreHadamard:
             return fail_arg("final_tail: the compressed-sensing step has no fused tail (final_tail_ok)");
         case StepKind::RestoreFFT:
+        case StepKind::RestoreFFTNoisy:
             return fail_arg("final_tail: the deconvolution step has no fused tail (final_tail_ok)");
         case StepKind::Vlb: {
             DDK_REQUIRE(r.vlb && tables && !r.eps_out && h.chain_state, "final_tail: the VLB epilogue needs the sweep's step, x, t, the tables and the chain state");
@@ -1132,6 +1145,9 @@ int p_update(const StepRule& r, const float* eps_hat, const int64_t* t, int B, l
         case StepKind::RestoreFFT:        // fft_conv.hip: one launch, or three through fft.tmp
             if (B * (per / ((long long)r.rst.H * r.rst.W)) > 65535) return bad("at most 65535 planes");
             return p_update_restore_fft(r, eps_hat, t, B, (int)(per / ((long long)r.rst.H * r.rst.W)), h, st);
+        case StepKind::RestoreFFTNoisy:   // fft_conv.hip: one launch, or three through fnz.tmp
+            if (B * (per / ((long long)r.rst.H * r.rst.W)) > 65535) return bad("at most 65535 planes");
+            return p_update_restore_fft_noisy(r, eps_hat, t, B, (int)(per / ((long long)r.rst.H * r.rst.W)), h, st);
         case StepKind::Vlb:       // no update: the sweep's reduction of the step's terms, a kernel of its own
             if (!r.vlb) return bad("null pointer");
             return vlb_sweep_terms(*r.vlb, t, eps_hat, B, per, h.chain_state, st, h.dec_counter);

@@ -1779,8 +1779,21 @@ static FftStage fft_stage(size_t n, int H, int W) {
     const size_t tw = al4((size_t)H * W), yp = tw + al4((size_t)(H > W ? H : W));
     return {0, tw, yp, yp + al4(n)};
 }
-static size_t chain_extra_floats(const ddk_unet& u, int B, int H, int W, StepKind kind, int restore_n = 0) {
+// RestoreFFTNoisy (plane-wide): RestoreFFT's area (the place of the image Yp stays unused), behind its T the draw's T2 of the same size
+// when a plane takes the multi-launch form, then gain [H W], nsc (one float per row of the chain) and the complex spectrum of A+ y
+struct FftNoisyStage {
+    FftStage f;
+    size_t gain, nsc, yhat, total;
+};
+static FftNoisyStage fft_noisy_stage(size_t n, int H, int W, int t_start) {
+    const FftStage f = fft_stage(n, H, W);
+    const size_t gain = f.tmp + 2 * al4(n) + (restore_fft_plane_form(H, W) ? 0 : 2 * al4(n)), nsc = gain + al4((size_t)H * W),
+                 yhat = nsc + al4((size_t)t_start + 1);
+    return {f, gain, nsc, yhat, yhat + 2 * al4(n)};
+}
+static size_t chain_extra_floats(const ddk_unet& u, int B, int H, int W, StepKind kind, int restore_n = 0, int t_start = 0) {
     const size_t n = al4((size_t)B * H * W * u.cfg.in_ch);
+    if (kind == StepKind::RestoreFFTNoisy) return fft_noisy_stage(n, H, W, t_start).total;
     if (kind == StepKind::RestoreFFT) return fft_stage(n, H, W).tmp + 2 * al4(n);
     if (kind == StepKind::RestoreHadamard) return cs_stage(n, H, W).tmp + al4(n);
     if (kind == StepKind::RestoreBlur) return blur_stage(n, H, W).tmp + al4(n);
@@ -1794,7 +1807,7 @@ static size_t chain_extra_floats(const ddk_unet& u, int B, int H, int W, StepKin
 }
 static size_t sampler_bytes(const ddk_unet* u, int B, int H, int W, int t_start, StepKind kind, int restore_n = 0) {
     if (check_shape(u, B, H, W) != DDK_OK || t_start < 0) return 0;
-    return (sampler_layout(*u, B, H, W, t_start).total + chain_extra_floats(*u, B, H, W, kind, restore_n)) * sizeof(float);
+    return (sampler_layout(*u, B, H, W, t_start).total + chain_extra_floats(*u, B, H, W, kind, restore_n, t_start)) * sizeof(float);
 }
 
 // What the sampler entries share once their own arguments are checked: n_steps reverse steps on a->x, step k at timestep map[k],
@@ -1806,18 +1819,20 @@ static size_t sampler_bytes(const ddk_unet* u, int B, int H, int W, int t_start,
 //   the restore kinds: (RestoreMultistep: the history, zeroed by every call as Multistep's, then) y and, when given, the mask,
 //              copied in before the first step (restore_stage's layout)
 //   RestoreBlur: the projections copied in and Yp formed (blur_stage); RestoreHadamard: perm and y copied in (cs_stage);
-//   RestoreFFT: the mask and the twiddles copied in and Yp formed (fft_stage)
+//   RestoreFFT: the mask and the twiddles copied in and Yp formed (fft_stage); RestoreFFTNoisy: mask, twiddles, gain and nsc copied
+//              in and the spectrum of A+ y formed (fft_noisy_stage)
 // The graph key: the kind, every table the step reads and the restore block; the staged operands live in the workspace, which is
 // in the key.
 static int sampler_chain(const ddk_sampler_args* a, const char* who, const int64_t* map, StepRule rule, ddk_stream_t s) {
     const int B = a->B, H = a->H, W = a->W, n_steps = a->t_start - a->t_end + 1;
     ChainRun c;
     DDK_TRY(begin_chain(c, a, who, a->t_start, a->stream_id, map, n_steps,
-                        [&](const SamplerLayout& sl) { return sl.total + chain_extra_floats(*a->unet, B, H, W, rule.kind, rule.rst.n); }, s));
+                        [&](const SamplerLayout& sl) { return sl.total + chain_extra_floats(*a->unet, B, H, W, rule.kind, rule.rst.n, a->t_start); }, s));
     rule.x = a->x; rule.noise = a->noise; rule.noise_step_stride = a->noise ? B * c.per : 0; rule.t_first = a->t_start;
     rule.c_recip = a->c_recip; rule.c_recipm1 = a->c_recipm1; rule.c1 = a->c1; rule.c2 = a->c2; rule.sigma = a->sigma;
     const size_t n = (size_t)B * c.per;
     float* extra = c.ws + c.sl.total;
+    const float* fnz_key[2] = {nullptr, nullptr};      // RestoreFFTNoisy: the caller's gain and nsc, which name the point-spread function and sigma_y in the graph key
     if (rule.kind == StepKind::Multistep) {
         DDK_HIP(hipMemsetAsync(extra, 0, n * sizeof(float), c.st));
         rule.x0_hist = extra;
@@ -1857,6 +1872,18 @@ static int sampler_chain(const ddk_sampler_args* a, const char* who, const int64
         DDK_TRY(circular_conv(rule.rst.y, rule.fft.pinv, extra + g.tw, extra + g.yp, extra + g.tmp, B, H, W, c.u->cfg.in_ch, c.st));
         rule.fft = FftOps{extra + g.mask, extra + g.tw, extra + g.tmp, nullptr};
         rule.rst = RestoreOps{extra + g.yp, 0, H, W, 0, nullptr};
+    } else if (rule.kind == StepKind::RestoreFFTNoisy) {
+        // as RestoreFFT, with gain and nsc copied in as well and the SPECTRUM of A+ y, P^ . F2 y in the transform's order, formed here:
+        // rule.rst.y is the CALLER's y, rule.fnz holds the caller's arrays
+        const FftNoisyStage g = fft_noisy_stage(al4(n), H, W, a->t_start);
+        DDK_HIP(hipMemcpyAsync(extra + g.f.mask, rule.fnz.mask, (size_t)H * W * sizeof(float), hipMemcpyDeviceToDevice, c.st));
+        DDK_HIP(hipMemcpyAsync(extra + g.f.tw, rule.fnz.tw, (size_t)(H > W ? H : W) * sizeof(float), hipMemcpyDeviceToDevice, c.st));
+        DDK_HIP(hipMemcpyAsync(extra + g.gain, rule.fnz.gain, (size_t)H * W * sizeof(float), hipMemcpyDeviceToDevice, c.st));
+        DDK_HIP(hipMemcpyAsync(extra + g.nsc, rule.fnz.nsc, ((size_t)a->t_start + 1) * sizeof(float), hipMemcpyDeviceToDevice, c.st));
+        DDK_TRY(circular_spectrum(rule.rst.y, rule.fnz.pinv, extra + g.f.tw, extra + g.yhat, extra + g.f.tmp, B, H, W, c.u->cfg.in_ch, c.st));
+        fnz_key[0] = rule.fnz.gain; fnz_key[1] = rule.fnz.nsc;
+        rule.fnz = FftNoisyOps{extra + g.f.mask, extra + g.f.tw, extra + g.f.tmp, extra + g.gain, extra + g.nsc, nullptr};
+        rule.rst = RestoreOps{extra + g.yhat, 0, H, W, 0, nullptr};
     } else if (restore_kind(rule.kind)) {
         const RestoreStage g = restore_stage(n, B, H, W, rule.kind, rule.rst.n);
         const size_t nn = (size_t)rule.rst.n * rule.rst.n, nm = (size_t)B * H * W / nn;      // one float per block: the mask, and the grey y
@@ -1881,9 +1908,10 @@ static int sampler_chain(const ddk_sampler_args* a, const char* who, const int64
 
     // the RestoreNoisy / RestoreGray tables share the Inpaint operands' storage (StepRule): each kind's key names its own
     const bool noisy = rule.kind == StepKind::RestoreNoisy || rule.kind == StepKind::RestoreGray;
-    const bool plane = rule.kind == StepKind::RestoreBlur || rule.kind == StepKind::RestoreHadamard || rule.kind == StepKind::RestoreFFT;
+    const bool plane = rule.kind == StepKind::RestoreBlur || rule.kind == StepKind::RestoreHadamard || rule.kind == StepKind::RestoreFFT ||
+                       rule.kind == StepKind::RestoreFFTNoisy;
     const InpaintOps ik = noisy || plane ? InpaintOps{} : rule.inp;      // (the plane-wide kinds' operands are staged: the workspace names them)
-    const NoisyTables nk = noisy ? rule.nsy : NoisyTables{};
+    const NoisyTables nk = noisy ? rule.nsy : NoisyTables{fnz_key[0], fnz_key[1]};      // (RestoreFFTNoisy: gain and nsc in the tables' two places)
     const ChainKey key{rule.kind,
                        {a->packed, a->x, rule.c_recip, rule.c_recipm1, rule.c1, rule.c2, rule.sigma, rule.c3, ik.ka, ik.kb, ik.ja, ik.jb, nk.lam,
                         nk.sgm},
@@ -2190,6 +2218,40 @@ extern "C" int ddk_sampler_run_restore_fft(const ddk_sampler_args* a, const int6
     StepRule rule{};
     rule.kind = StepKind::RestoreFFT;
     rule.fft = FftOps{mask, twiddles, nullptr, P};
+    rule.rst.y = y;
+    return sampler_chain(a, who, timestep_map, rule, s);
+}
+
+// DDNM+ deconvolution of a noisy blurred image (section 3.19): ddk_sampler_run_restore_fft's chain, every step ending in
+// StepKind::RestoreFFTNoisy.  gain [H][W] and nsc (t_start + 1 floats) join the caller's device arrays; all of them are copied into
+// the workspace and the spectrum of A+ y is formed there before the first step.  The caller's gain and nsc are in the graph key, so a
+// chain of one sigma_y never replays another's graph, and the kind keeps it from a deconvolution chain's.
+extern "C" size_t ddk_sampler_restore_fft_noisy_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start) {
+    if (check_shape(u, B, H, W) != DDK_OK || !restore_fft_shape_ok(H, W, u->cfg.in_ch)) return 0;
+    return sampler_bytes(u, B, H, W, t_start, StepKind::RestoreFFTNoisy);
+}
+extern "C" int ddk_sampler_restore_fft_noisy_tail_parts(const ddk_unet* u, int B, int H, int W) {
+    if (check_shape(u, B, H, W) != DDK_OK) return -1;
+    return fused_tail_parts(*u, B, H, W, u->dimp[1], StepKind::RestoreFFTNoisy);      // 0: final_tail_ok takes no plane-wide kind
+}
+extern "C" int ddk_sampler_run_restore_fft_noisy(const ddk_sampler_args* a, const int64_t* timestep_map, const float* mask, const float* P,
+                                                 const float* gain, const float* nsc, const float* twiddles, const float* y, ddk_stream_t s) {
+    const char* who = "sampler_restore_fft_noisy";
+    auto bad = [who](const char* what) {
+        set_error("bad argument: %s: %s", who, what);
+        return DDK_ERR_ARG;
+    };
+    if (!(a && a->unet && a->packed && a->x && a->workspace && mask && P && gain && nsc && twiddles && y)) return bad("null pointer");
+    if (!(a->c_recip && a->c_recipm1 && a->c1 && a->c2 && a->sigma)) return bad("null schedule table");
+    if (a->noise) return bad("injected noise is not supported, noise must be NULL (Philox only)");
+    if (!(a->t_start >= a->t_end && a->t_end >= 0)) return bad("need t_start >= t_end >= 0");
+    if (!restore_fft_shape_ok(a->H, a->W, a->unet->cfg.in_ch)) return bad("H and W must be powers of two in [16, 256], the model's channels 1 to 8");
+    if (!(a->B > 0 && (long long)a->B * a->unet->cfg.in_ch <= 65535)) return bad("B channels must be in [1, 65535]");
+    if (!(aligned16(mask) && aligned16(P) && aligned16(gain) && aligned16(nsc) && aligned16(twiddles) && aligned16(y))) return bad("alignment");
+    DDK_TRY(check_timestep_map(timestep_map, a->t_start, who));
+    StepRule rule{};
+    rule.kind = StepKind::RestoreFFTNoisy;
+    rule.fnz = FftNoisyOps{mask, twiddles, nullptr, gain, nsc, P};
     rule.rst.y = y;
     return sampler_chain(a, who, timestep_map, rule, s);
 }

@@ -170,6 +170,8 @@ SIGNATURES = {
     "ddk_p_sample_update_restore_cs": (_I, [_P] * 11 + [_I, _I, _I, _I, _I, C.c_uint64, C.c_uint32, _P]),
     "ddk_circular_conv": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "ddk_p_sample_update_restore_fft": (_I, [_P] * 12 + [_I, _I, _I, _I, C.c_uint64, C.c_uint32, _P]),
+    "ddk_circular_spectrum": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "ddk_p_sample_update_restore_fft_noisy": (_I, [_P] * 14 + [_I, _I, _I, _I, C.c_uint64, C.c_uint32, _P]),
     "ddk_randn": (_I, [_P, _LL, C.c_uint64, C.c_uint32, C.c_uint32, _P]),
     "ddk_fix_samples": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "ddk_sq_err_sum": (_I, [_P, _P, _P, _I, _LL, _P]),
@@ -235,6 +237,9 @@ SIGNATURES = {
     "ddk_sampler_restore_fft_workspace_bytes": (_SZ, [_P, _I, _I, _I, _I]),
     "ddk_sampler_restore_fft_tail_parts": (_I, [_P, _I, _I, _I]),
     "ddk_sampler_run_restore_fft": (_I, [C.POINTER(SamplerArgs), C.POINTER(C.c_int64), _P, _P, _P, _P, _P]),
+    "ddk_sampler_restore_fft_noisy_workspace_bytes": (_SZ, [_P, _I, _I, _I, _I]),
+    "ddk_sampler_restore_fft_noisy_tail_parts": (_I, [_P, _I, _I, _I]),
+    "ddk_sampler_run_restore_fft_noisy": (_I, [C.POINTER(SamplerArgs), C.POINTER(C.c_int64), _P, _P, _P, _P, _P, _P, _P]),
     "ddk_sampler_invalidate": (_I, [_P]),
     "ddk_sampler_release_workspace": (_I, [_P, _P]),
     "ddk_vlb_sweep_workspace_bytes": (_SZ, [_P, _I, _I, _I, _I]),

@@ -1004,6 +1004,40 @@ def p_sample_update_restore_fft_(x, eps_hat, mask, Yp, t, c_recip, c_recipm1, c1
     return x
 
 
+def circular_spectrum(x, S):
+    """out [B,C,H W,2] = S . F2(x) per plane of x [B,H,W,C] (NHWC fp32), complex (re, im), left in the device transform's own order:
+    frequency (u, v) at index brev(u) W + brev(v), brev reversing log2 H and log2 W bits.  With S =
+    psf.psf_projection's P^ it is the spectrum of A+ y that p_sample_update_restore_fft_noisy_ reads.  S, shapes: as circular_conv."""
+    b, h, w, c = x.shape
+    tw, scratch = _fft_operands("circular_spectrum", tuple(x.shape), x.device, S=(S, (h, w, 2)))
+    out = torch.empty((b, c, h * w, 2), device=x.device, dtype=torch.float32)
+    L.check(L.load().ddk_circular_spectrum(L.ptr(_f32(x)), L.ptr(S), L.ptr(tw), L.ptr(out), L.ptr(scratch), b, h, w, c, L.stream()),
+            "circular_spectrum")
+    return out
+
+
+def p_sample_update_restore_fft_noisy_(x, eps_hat, mask, gain, nsc, Yhat, t, c_recip, c_recipm1, c1, c2, sigma, seed=0, stream_id=0):
+    """In-place DDNM+ deconvolution step of x [B,H,W,C] (NHWC) per sample row t[b], for a blurred image with
+    noise: per frequency the clipped x0's spectrum moves towards Yhat (circular_spectrum of y with P^, [B,C,H W,2]) by lam, and the
+    Philox draw is shaped by phi, both from the row's sigma, nsc[t[b]] and gain [H,W] (psf.psf_noisy_operands); mask [H,W] fp32 is
+    nonzero at the kept frequencies."""
+    b, h, w, c = x.shape
+    if tuple(eps_hat.shape) != tuple(x.shape) or Yhat is None or tuple(Yhat.shape) != (b, c, h * w, 2):
+        raise L.DDKError(f"p_sample_update_restore_fft_noisy: x {tuple(x.shape)}, eps_hat {tuple(eps_hat.shape)}, "
+                         f"Yhat {None if Yhat is None else tuple(Yhat.shape)}")
+    if nsc is None or nsc.dim() != 1 or tuple(nsc.shape) != tuple(c1.shape):
+        raise L.DDKError("p_sample_update_restore_fft_noisy: nsc must have one entry per row of c1")
+    tw, scratch = _fft_operands("p_sample_update_restore_fft_noisy", tuple(x.shape), x.device, mask=(mask, (h, w)), gain=(gain, (h, w)),
+                                nsc=(nsc, tuple(nsc.shape)), Yhat=(Yhat, (b, c, h * w, 2)))
+    if scratch is not None:       # T and T2
+        scratch = torch.empty((4, *x.shape), device=x.device, dtype=torch.float32)
+    L.check(L.load().ddk_p_sample_update_restore_fft_noisy(
+        L.ptr(_f32(x)), L.ptr(_f32(eps_hat)), L.ptr(mask), L.ptr(gain), L.ptr(nsc), L.ptr(tw), L.ptr(Yhat), L.ptr(scratch), L.ptr(t),
+        L.ptr(c_recip), L.ptr(c_recipm1), L.ptr(c1), L.ptr(c2), L.ptr(sigma), b, h, w, c, seed, stream_id, L.stream()),
+        "p_sample_update_restore_fft_noisy")
+    return x
+
+
 def randn(shape, device, seed, step, stream_id=0):
     out = torch.empty(shape, device=device, dtype=torch.float32)
     L.check(L.load().ddk_randn(L.ptr(out), out.numel(), seed, step, stream_id, L.stream()), "randn")

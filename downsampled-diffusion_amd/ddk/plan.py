@@ -33,7 +33,8 @@ SAMPLERS = {"smp": ("sample", "sampler", "sampler"), "sms": ("sample_multistep",
             "srb": ("sample_restore_blur", "sampler_restore_blur", "deblurring sampler"),
             "srq": ("sample_restore_sep", "sampler_restore_sep", "separable restoration sampler"),
             "src": ("sample_restore_cs", "sampler_restore_cs", "compressed-sensing sampler"),
-            "srf": ("sample_restore_fft", "sampler_restore_fft", "deconvolution sampler")}
+            "srf": ("sample_restore_fft", "sampler_restore_fft", "deconvolution sampler"),
+            "sfn": ("sample_restore_fft_noisy", "sampler_restore_fft_noisy", "noisy deconvolution sampler")}
 # workspace kinds whose captured step graphs point into them (the samplers', the likelihood sweep's): UnetPlan._workspace keeps up
 # to 3 of each
 CHAIN_WORKSPACES = (*SAMPLERS, "vsw")
@@ -366,7 +367,8 @@ class UnetPlan:
         # the size-changing entry is the deblurring chain with a y of its own size: its workspace and tail queries serve both
         "srq": ("sampler_run_restore_sep", "sampler_restore_blur_workspace_bytes", "sampler_restore_blur_tail_parts"),
         "src": ("sampler_run_restore_cs", "sampler_restore_cs_workspace_bytes", "sampler_restore_cs_tail_parts"),
-        "srf": ("sampler_run_restore_fft", "sampler_restore_fft_workspace_bytes", "sampler_restore_fft_tail_parts")}
+        "srf": ("sampler_run_restore_fft", "sampler_restore_fft_workspace_bytes", "sampler_restore_fft_tail_parts"),
+        "sfn": ("sampler_run_restore_fft_noisy", "sampler_restore_fft_noisy_workspace_bytes", "sampler_restore_fft_noisy_tail_parts")}
 
     def _restore_tail_parts(self, kind, b, h, w, n):
         return int(getattr(self._lib, "ddk_" + self.RESTORE_ENTRIES[kind][2])(self.handle, b, h, w, *(() if n is None else (int(n),))))
@@ -379,7 +381,8 @@ class UnetPlan:
         [B,H/n,W/n] and whose n = 1 needs no mask; blur: the deblurring entry's matrices (P_h, P_w, Q_h, Q_w), whose operator has no
         block (n is None, no mask) and whose y has x's shape -- or, for the size-changing entry, y_size = (h, w) of y [B,h,w,in_ch],
         with Q_h [H,h] and Q_w [W,w]; cs: the compressed-sensing entry's (perm, m), whose operator has no block either and whose y is
-        [B,in_ch,m]; fft: the deconvolution entry's (mask [H,W], P [H,W,2]), whose operator has no block and whose y has x's shape."""
+        [B,in_ch,m]; fft: the deconvolution entry's (mask [H,W], P [H,W,2]), whose operator has no block and whose y has x's shape -- or the noisy deconvolution entry's
+        (mask, P, gain [H,W], nsc [t_start + 1])."""
         self._need_packed(kind)
         name = SAMPLERS[kind][0]
         gray = weights is not None
@@ -396,7 +399,7 @@ class UnetPlan:
         if fft is not None:
             if not (h & (h - 1) == 0 and w & (w - 1) == 0 and 16 <= h <= 256 and 16 <= w <= 256 and 1 <= c <= 8):
                 raise L.DDKError(f"{name}: H and W must be powers of two in [16, 256] and the channels 1 to 8, got [{h},{w},{c}]")
-            for what, v, shape in zip(("mask", "P"), fft, ((h, w), (h, w, 2))):
+            for what, v, shape in zip(("mask", "P", "gain", "nsc"), fft, ((h, w), (h, w, 2), (h, w), (t_start + 1,))):
                 if v is None or tuple(v.shape) != shape or v.dtype != torch.float32 or not v.is_contiguous() or v.device != x.device:
                     raise L.DDKError(f"{name}: {what} must be a contiguous fp32 [{','.join(map(str, shape))}] tensor on x's device")
             n = 1                 # no block, no mask of pixels: y has x's shape
@@ -435,7 +438,7 @@ class UnetPlan:
             operands = (L.ptr(y), L.ptr(cs[0]), int(cs[1]))
         if fft is not None:
             from . import ops
-            operands = (L.ptr(fft[0]), L.ptr(fft[1]), L.ptr(ops.fft_twiddles(max(h, w), x.device)), L.ptr(y))
+            operands = (*(L.ptr(v) for v in fft), L.ptr(ops.fft_twiddles(max(h, w), x.device)), L.ptr(y))
         if gray:
             operands += (L.GRAY_WEIGHTS[weights],)
 
@@ -578,6 +581,23 @@ class UnetPlan:
         in [16, 256].  tables / timesteps: as for sample_nhwc (plain, respaced or DDIM).  Philox only."""
         return self._sample_restore("srf", x, y, None, None, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, masked=False,
                                     fft=(mask, P))
+
+    def restore_fft_noisy_tail_parts(self, b, h, w):
+        """As restore_fft_tail_parts, for the noisy deconvolution step: 0 for every shape, -1 for a shape the plan does not take."""
+        return self._restore_tail_parts("sfn", b, h, w, None)
+
+    def sample_restore_fft_noisy_nhwc(self, x, y, mask, P, gain, nsc, tables, t_start, t_end=0, seed=0, stream_id=0, use_graph=True,
+                                      timesteps=None):
+        """DDNM+ deconvolution steps for a blurred image with noise of standard deviation sigma_y, t_start .. t_end (inclusive), in
+        place on x [B,H,W,in_ch] (ddk_sampler_run_restore_fft_noisy).
+
+        y, mask, P: as sample_restore_fft_nhwc; gain: fp32 [H,W], 1 / |K^| at the kept frequencies and 0 elsewhere; nsc: fp32
+        [t_start + 1], |c1| sigma_y per row (models/diffusion/psf.py psf_noisy_operands).  All are copied into the plan's "sfn"
+        workspace and the spectrum of A+ y is formed there by every call.  The cached graph is keyed by the gain and nsc tensors:
+        pass the same tensors to replay it.  tables / timesteps: as for sample_nhwc (respaced ancestral, or DDIM with eta > 0).
+        Philox only."""
+        return self._sample_restore("sfn", x, y, None, None, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, masked=False,
+                                    fft=(mask, P, gain, nsc))
 
     # ---------------------------------------------------------------- likelihood sweep
     VLB_STREAM_BIT = 1 << 31     # the sweep's Philox stream id is stream_id | this (csrc/ddk_internal.h VLB_STREAM_BIT)

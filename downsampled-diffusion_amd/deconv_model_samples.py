@@ -9,6 +9,11 @@ Loads the checkpoint as generate_model_samples.py does (``--synthetic CONFIG`` b
   * ``--images file.npy`` holds uint8 images [N, H, W, C] of the model's size, already blurred; with ``--blur_input`` they are sharp
     images that are blurred here first, on the GPU (ops.circular_conv), so a test set can be blurred and restored in one go;
   * ``--tol``: frequencies whose |K^| is below tol * max |K^| are dropped from the pseudo-inverse (default 0.03);
+  * ``--sigma_y S`` declares that the blurred images carry noise of standard deviation S (in the [-1, 1] scale) and restores them
+    with ``model.deconvolve_noisy`` (DDNM+); with ``--blur_input`` that noise, N(0, S^2) from a generator
+    seeded by ``--seed``, is added here after blurring.  The output names gain ``_sy<S>``.  S = 0 (the default) is the exact
+    measurement: today's chain, outputs and names.  S > 0 needs a chain that draws (not ``--use_ddim`` with ``--eta 0``); keep
+    ``--tol`` at or above S;
   * ``--timestep_respacing``, ``--use_ddim`` and ``--eta`` choose the chain as in generate_model_samples.py;
   * batch g draws x_T and its Philox key from ``--seed`` + g;
   * a dDDPM checkpoint is refused: a convolution of its latent is not a convolution of the image.
@@ -40,6 +45,7 @@ def parse_args(argv=None):
     ap.add_argument("--psf", required=True, help=f"one of {', '.join(psf.PRESETS)} or a .npy file of a 2-D array with odd sides")
     ap.add_argument("--blur_input", action="store_true", help="the file holds sharp images: blur them first")
     ap.add_argument("--tol", type=float, default=blur.DEFAULT_TOL, help="frequencies below tol * max |K^| are dropped (default 0.03)")
+    ap.add_argument("--sigma_y", type=float, default=0.0, help="standard deviation of the noise in the blurred images, [-1, 1] scale (0: exact, DDNM)")
     ap.add_argument("--timestep_respacing", default="", help='run K of the T steps: "ddimN", "N" or "n1,n2,..." sections')
     ap.add_argument("--use_ddim", action="store_true", help="DDIM steps instead of ancestral ones")
     ap.add_argument("--eta", type=float, default=0.0, help="DDIM noise scale (0: deterministic)")
@@ -55,6 +61,10 @@ def parse_args(argv=None):
         ap.error("--tol must be in [0, 1)")
     if args.batch_size < 1:
         ap.error("--batch_size must be >= 1")
+    if not (np.isfinite(args.sigma_y) and args.sigma_y >= 0):
+        ap.error("--sigma_y must be a finite number >= 0")
+    if args.sigma_y > 0 and args.use_ddim and args.eta == 0:
+        ap.error("--sigma_y > 0 needs a chain that draws: ancestral steps, or --use_ddim with --eta > 0")
     return args
 
 
@@ -99,17 +109,24 @@ def main():
         K = torch.from_numpy(psf.interleave(psf.psf_spectrum(k, size, size))).to(device)
         y_all = torch.cat([ops.circular_conv(y_all[i:i + args.batch_size].to(device).contiguous(), K).cpu()
                            for i in range(0, y_all.shape[0], args.batch_size)])
+        if args.sigma_y > 0:
+            y_all = y_all + args.sigma_y * torch.randn(y_all.shape, generator=torch.Generator().manual_seed(args.seed))
     n = y_all.shape[0]
 
     spec = (args.timestep_respacing.replace(",", "-") or "full") + (f"_ddim_eta{args.eta:g}" if args.use_ddim else "")
     kw = dict(tol=args.tol, respacing=args.timestep_respacing or None, ddim=args.use_ddim, eta=args.eta)
     tag = args.psf if args.psf in psf.PRESETS else os.path.splitext(os.path.basename(args.psf))[0]
+    noisy = args.sigma_y > 0
+    if noisy:
+        kw["sigma_y"] = args.sigma_y
+        spec += f"_sy{args.sigma_y:g}"
+    restore = model.deconvolve_noisy if noisy else model.deconvolve
     print(f"Deconvolving {n} images (psf {tag}, tol {args.tol:g}, {spec} steps) with {args.saved_model}.")
     stage = OutputStage()
     t0 = time.time()
     for g, i in enumerate(range(0, n, args.batch_size)):
         torch.manual_seed(args.seed + g)          # x_T and the Philox key of batch g
-        stage.submit(model.deconvolve(y_all[i:i + args.batch_size].permute(0, 3, 1, 2).contiguous().to(device), k, **kw))
+        stage.submit(restore(y_all[i:i + args.batch_size].permute(0, 3, 1, 2).contiguous().to(device), k, **kw))
     batches = stage.finish()
     torch.cuda.synchronize()
     print(f"Total time: {time.time() - t0:.2f} s")

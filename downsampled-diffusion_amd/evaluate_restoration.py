@@ -46,6 +46,12 @@ through utils/data.py; ``--max_batches`` keeps the first max_batches * batch_siz
     ``pinv``, A+ y clipped to [-1, 1].  The consistency is max |A+ A x_out - A+ y|; ``method`` reads ``ddnm_deconv`` and the settings
     gain ``psf`` and ``tol``.  ``--psf`` belongs to this task alone; it takes no ``--scale``, ``--mask``, ``--sigma_y``,
     ``--dpm_solver``, ``--method`` or ``--kernel``.
+  * ``--task deconv_noisy --psf P --sigma_y S [--tol T]`` (DDPM checkpoints; section 3.19), S > 0: the images are blurred as for
+    ``deconv``, N(0, S^2) noise seeded by ``--seed`` is added in the [-1, 1] scale, and ``model.deconvolve_noisy`` (DDNM+ per
+    frequency) restores them.  Baselines, all from the noisy image: the blurred image, ``pinv`` (which shows the amplification of
+    the noise by 1 / |K^|) and ``tikhonov``, conj K^ / (|K^|^2 + S^2).  ``method`` reads ``ddnm_plus``, the settings gain ``psf``,
+    ``tol`` and ``sigma_y``, and the consistency is the RMS of A(x_out) - y_clean in uint8 levels.  Needs a chain that draws; keep
+    ``--tol`` at or above S.  ``--task deconv`` itself keeps refusing ``--sigma_y``.
   * batch g draws x_T and its Philox key from ``--seed`` + g.
 
 Prints one JSON object, the settings that produced it (among them ``method`` and ``unet_forwards``, the UNet forwards per image, so
@@ -60,7 +66,7 @@ import time
 import numpy as np
 import torch
 
-from utils.restoration_metrics import BLUR_KERNELS, CS_TASK, DEBLUR_TASK, DECONV_TASK, DOWNSAMPLES, GRAY_WEIGHTS, MASKS, METHODS, TASKS, evaluate_restoration, load_mask, report, to_u8
+from utils.restoration_metrics import BLUR_KERNELS, CS_TASK, DEBLUR_TASK, DECONV_NOISY_TASK, DECONV_TASK, DOWNSAMPLES, GRAY_WEIGHTS, MASKS, METHODS, TASKS, evaluate_restoration, load_mask, report, to_u8
 
 
 def parse_args(argv=None):
@@ -68,7 +74,7 @@ def parse_args(argv=None):
     ap.add_argument("--saved_model", default="celeba_x2")
     ap.add_argument("--synthetic", default=None, help="JSON config file: use closed-form synthetic weights, no checkpoint")
     ap.add_argument("--images", default=None, help="uint8 [N, H, W, C] .npy of the model's size (default: the dataset's test split)")
-    ap.add_argument("--task", required=True, choices=(*TASKS, DEBLUR_TASK, CS_TASK, DECONV_TASK))
+    ap.add_argument("--task", required=True, choices=(*TASKS, DEBLUR_TASK, CS_TASK, DECONV_TASK, DECONV_NOISY_TASK))
     ap.add_argument("--mask", default=None, help=f"one of {', '.join(MASKS)} or a .npy file of {{0, 1}} (1 = known); inpaint: default "
                                                  "center; sr: masked super-resolution, the mask is of the pooled image (default: none)")
     ap.add_argument("--method", default=None, choices=METHODS, help="inpaint: repaint (default) or ddnm; sr: ddnm")
@@ -96,14 +102,16 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.batch_size < 1 or (args.max_batches is not None and args.max_batches < 1):
         ap.error("--batch_size and --max_batches must be >= 1")
-    if args.psf is not None and args.task != DECONV_TASK:
-        ap.error("--psf belongs to --task deconv")
-    if args.task == DECONV_TASK:
+    if args.psf is not None and args.task not in (DECONV_TASK, DECONV_NOISY_TASK):
+        ap.error("--psf belongs to --task deconv and --task deconv_noisy")
+    if args.task in (DECONV_TASK, DECONV_NOISY_TASK):
         if args.psf is None:
-            ap.error("--task deconv needs --psf: the point-spread function is part of the task, there is no default")
+            ap.error(f"--task {args.task} needs --psf: the point-spread function is part of the task, there is no default")
         if args.psf not in ("diag", "disk") and not args.psf.endswith(".npy"):
             ap.error("--psf must be diag, disk or a .npy file")
-        if args.method is not None or args.dpm_solver or args.sigma_y != 0.0 or args.mask is not None or args.scale is not None or \
+        if args.task == DECONV_NOISY_TASK and not args.sigma_y > 0:
+            ap.error("--task deconv_noisy needs --sigma_y > 0: the noise level is part of the task (--sigma_y 0 is --task deconv)")
+        if args.method is not None or args.dpm_solver or (args.task == DECONV_TASK and args.sigma_y != 0.0) or args.mask is not None or args.scale is not None or \
                 args.kernel is not None:
             ap.error("--task deconv has one method, ddnm on ancestral or DDIM steps, and takes no --method, --mask, --scale, --sigma_y, "
                      "--dpm_solver or --kernel")
@@ -134,7 +142,7 @@ def parse_args(argv=None):
         ap.error("--downsample bicubic takes no --mask, --dpm_solver or --sigma_y")
     if args.weights is not None and args.task != "colorize":
         ap.error("--weights belongs to --task colorize")
-    if (args.kernel is not None or args.tol is not None) and args.task not in (DEBLUR_TASK, DECONV_TASK):
+    if (args.kernel is not None or args.tol is not None) and args.task not in (DEBLUR_TASK, DECONV_TASK, DECONV_NOISY_TASK):
         ap.error("--kernel and --tol belong to --task deblur")
     if args.task == DEBLUR_TASK:
         if args.kernel is None:
@@ -145,7 +153,7 @@ def parse_args(argv=None):
             ap.error("--tol must be in [0, 1)")
         if args.method != "ddnm" or args.dpm_solver or args.sigma_y != 0.0 or args.mask is not None or args.scale is not None:
             ap.error("--task deblur has one method, ddnm on ancestral or DDIM steps, and takes no --mask, --scale or --sigma_y")
-    elif args.task in (CS_TASK, DECONV_TASK):
+    elif args.task in (CS_TASK, DECONV_TASK, DECONV_NOISY_TASK):
         pass                      # checked above
     elif args.task == "sr":
         if args.scale is None:
@@ -202,7 +210,7 @@ def chain_options(args):
         kw.update(kernel=args.kernel, tol=args.tol)
     if args.task == CS_TASK:
         kw.update(ratio=args.ratio, perm_seed=args.perm_seed)
-    if args.task == DECONV_TASK:
+    if args.task in (DECONV_TASK, DECONV_NOISY_TASK):
         kw.update(psf=args.psf, tol=args.tol)
     if args.dpm_solver:
         kw.update(dpm_solver=True)
@@ -274,7 +282,7 @@ def main():
     kw = chain_options(args)
     if args.task == "inpaint":
         kw["mask"] = args.mask if args.mask in MASKS else load_mask(args.mask, n, h, w, channels)
-    elif args.mask is not None and args.task not in (DEBLUR_TASK, CS_TASK, DECONV_TASK):
+    elif args.mask is not None and args.task not in (DEBLUR_TASK, CS_TASK, DECONV_TASK, DECONV_NOISY_TASK):
         kw["sr_mask"] = args.mask if args.mask in MASKS else load_mask(args.mask, n, h // args.scale, w // args.scale, 1)
 
     print(f"Scoring {args.task} on {n} images with {'synthetic weights' if args.synthetic else args.saved_model}.")

@@ -223,6 +223,11 @@ class DownsampleDDPM(DDPM):
         raise ValueError("deconvolve: a DownsampleDDPM samples in a latent, and a point-spread function on the image has no such form there; "
                          "deconvolution needs a pixel model (DDPM)")
 
+    def deconvolve_noisy(self, y, psf=None, **kwargs):
+        """Not available, for deconvolve's reason.  Always ValueError."""
+        raise ValueError("deconvolve_noisy: a DownsampleDDPM samples in a latent, and a point-spread function on the image has no such form "
+                         "there; deconvolution needs a pixel model (DDPM)")
+
     @torch.no_grad()
     def reconstruct(self, x, n):
         """dddpm.py:33-74 (visualisation only)."""

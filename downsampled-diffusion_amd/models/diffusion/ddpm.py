@@ -873,9 +873,9 @@ class DDPM(nn.Module):
         return self._cached_tables(('psf', k.tobytes(), k.shape, float(tol)),
                                    lambda: ({n: torch.from_numpy(v) for n, v in zip(("K", "P", "mask"), psf.psf_operands(k, H, W, tol))}, None))[0]
 
-    def _deconvolve_args(self, y, k, tol, ddim, eta, unsupported):
-        """ValueError for anything deconvolve cannot take, before any device work.  Returns (y as float, the PSF as a float64 array)."""
-        who = "deconvolve"
+    def _deconvolve_args(self, y, k, tol, ddim, eta, unsupported, who="deconvolve"):
+        """ValueError for anything deconvolve (or, as `who`, deconvolve_noisy) cannot take, before any device work.  Returns (y as float,
+        the PSF as a float64 array)."""
         if unsupported:
             raise ValueError(f"{who}: {sorted(unsupported)} not accepted (DDNM runs ancestral or DDIM steps with Philox draws over the "
                              f"whole schedule on an exact, unmasked measurement: no {', '.join(self.DEBLUR_UNSUPPORTED)})")
@@ -926,6 +926,53 @@ class DDPM(nn.Module):
             lambda plan, x, yl, mk, tables, k_start, seed, use: plan.sample_restore_fft_nhwc(
                 x, yl, operands()["mask"], operands()["P"], tables, k_start, seed=seed, stream_id=sid, use_graph=self.use_graph,
                 timesteps=use))
+
+    # ------------------------------------------------------------------ DDNM+ deconvolution (a noisy blurred image)
+    @torch.no_grad()
+    def deconvolve_noisy(self, y, psf, *, sigma_y, tol=blur.DEFAULT_TOL, respacing=None, ddim=False, eta=0.0, x_T=None, seed=None, **unsupported):
+        """deconvolve() for a blurred image that is only known to +- sigma_y (DDNM+, Wang, Yu, Zhang 2023, section 3.3, per frequency;
+        DESIGN.md section 3.19): y = A x + noise of standard deviation sigma_y, in y's own [-1, 1] scale.  Every step moves each kept
+        frequency of its clipped x0 towards that of A+ y by lam <= 1 and shapes its draw by phi <= sigma, so that the noise entering
+        through y, amplified by 1 / |K^|, and the drawn noise add up to the chain's own variance: a frequency with a small |K^|
+        receives a small lam instead of amplified noise.  The last step returns the model's own x0.  y, psf, tol, the other keywords
+        and their ValueErrors: as deconvolve.  sigma_y must be a finite real number >= 0; sigma_y == 0 is deconvolve itself.  With
+        sigma_y > 0 a chain that draws nothing (ddim=True with eta == 0) raises ValueError.  All before any device work.  Keep tol at or
+        above sigma_y (gain sigma_y <= 1 on every kept frequency): y's noise is one fixed draw, and what the steps let in of it below
+        that level adds up along the chain."""
+        sigma_y = self._sigma_y_arg(sigma_y, "deconvolve_noisy")
+        if sigma_y == 0:
+            return self.deconvolve(y, psf, tol=tol, respacing=respacing, ddim=ddim, eta=eta, x_T=x_T, seed=seed, **unsupported)
+        y, k = self._deconvolve_args(y, psf, tol, ddim, eta, unsupported, who="deconvolve_noisy")
+        if ddim and eta == 0:
+            raise ValueError("deconvolve_noisy: sigma_y > 0 needs a chain that draws (ancestral steps, or ddim with eta > 0): with eta = 0 "
+                             "every row's lam is 0 and nothing would be constrained")
+        spaced = respacing is not None or ddim or eta != 0
+        sid = int(self.rng_stream_id)
+        C, H, W = self.sample_shape
+        get_tables = lambda: self._spaced_tables(respacing, ddim, eta) if spaced else (self._tables(), None)
+        m, yh = [], []            # the operands on the model's device and the Python loop's spectrum of A+ y, made at the first use
+
+        def operands(tables):
+            if not m:
+                from . import psf as P_
+                noisy = self._cached_tables(
+                    ('psf_noisy', k.tobytes(), k.shape, float(tol), sigma_y, respacing, bool(ddim), float(eta)),
+                    lambda: ({n: torch.from_numpy(v) for n, v in zip(("gain", "nsc"), P_.psf_noisy_operands(k, H, W, tol, sigma_y, tables["c1"]))},
+                             None))[0]
+                m.append(dict(self._psf_operands(k, tol), **noisy))
+            return m[0]
+
+        def op(x, e, yl, mk, t, tables, seed):
+            o = operands(tables)
+            if not yh:
+                yh.append(ops.circular_spectrum(yl, o["P"]))
+            ops.p_sample_update_restore_fft_noisy_(x, e, o["mask"], o["gain"], o["nsc"], yh[0], t, **tables, seed=seed, stream_id=sid)
+
+        def chain(plan, x, yl, mk, tables, k_start, seed, use):
+            o = operands(tables)
+            plan.sample_restore_fft_noisy_nhwc(x, yl, o["mask"], o["P"], o["gain"], o["nsc"], tables, k_start, seed=seed, stream_id=sid,
+                                               use_graph=self.use_graph, timesteps=use)
+        return self._ddnm_loop("deconvolve_noisy", y, None, get_tables, x_T, seed, op, chain)
 
     @torch.no_grad()
     def reconstruct(self, x, n):

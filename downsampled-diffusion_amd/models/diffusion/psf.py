@@ -98,3 +98,20 @@ def psf_operands(psf, H, W, tol=DEFAULT_TOL):
     twiddles of max(H, W)."""
     P, M, _ = psf_projection(psf, H, W, tol)
     return interleave(psf_spectrum(psf, H, W)), interleave(P), np.ascontiguousarray(M.astype(np.float32)), twiddles(max(int(H), int(W)))
+
+
+def psf_noisy_operands(psf, H, W, tol, sigma_y, c1):
+    """(gain, nsc) of the DDNM+ deconvolution step, formed in float64 and stored as fp32: gain [H, W] is
+    1 / |K^| at the kept frequencies and 0 elsewhere (Hermitian-symmetric like the mask, natural frequency order); nsc [rows] is
+    |c1[k]| sigma_y for the chain's table c1 (an array or a tensor, one entry per row)."""
+    if isinstance(sigma_y, bool) or not isinstance(sigma_y, (int, float, np.integer, np.floating)) or not np.isfinite(sigma_y) or sigma_y < 0:
+        raise ValueError(f"psf: sigma_y must be a finite real number >= 0, got {sigma_y!r}")
+    _, M, _ = psf_projection(psf, H, W, tol)
+    mag = np.abs(psf_spectrum(psf, H, W))
+    mag = 0.5 * (mag + np.roll(mag[::-1, ::-1], (1, 1), axis=(0, 1)))      # |K^(f)| = |K^(-f)| to the last bit
+    gain = np.zeros((int(H), int(W)))
+    gain[M] = 1.0 / mag[M]
+    if hasattr(c1, "detach"):
+        c1 = c1.detach().cpu().numpy()
+    nsc = np.abs(np.asarray(c1, dtype=np.float64).reshape(-1)) * float(sigma_y)
+    return np.ascontiguousarray(gain.astype(np.float32)), np.ascontiguousarray(nsc.astype(np.float32))

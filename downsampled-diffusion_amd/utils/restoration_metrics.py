@@ -18,6 +18,7 @@ DEBLUR_TASK = "deblur"          # evaluate_restoration's fourth task (section 3.
 BLUR_KERNELS = ("uniform", "gauss", "aniso")
 CS_TASK = "cs"                  # ... and its fifth (section 3.17), with a sampling ratio and a permutation seed
 DECONV_TASK = "deconv"          # ... and its sixth (section 3.18), with a 2-D point-spread function
+DECONV_NOISY_TASK = "deconv_noisy"      # ... and its seventh (section 3.19): the blurred image carries noise
 METHODS = ("repaint", "ddnm")
 GRAY_WEIGHTS = {"mean": (1.0 / 3.0, 1.0 / 3.0, 1.0 / 3.0), "luma": (0.299, 0.587, 0.114)}     # DDPM.colorize's two operators
 DOWNSAMPLES = ("mean", "bicubic")     # task "sr": block means (section 3.6) or the antialiased bicubic reduction (section 3.15)
@@ -179,6 +180,11 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
     .npy path or an array; periodic boundary) on the device (ops.circular_conv) and ``model.deconvolve`` restores them (``tol``;
     ``chain``: respacing, ddim, eta).  Baselines: "blurred" and "pinv", A+ y clipped to [-1, 1].  consistency: per image
     max |A+ A x_out - A+ y| of the model's float output.  The returned method is "ddnm_deconv", and "psf" and "tol" are returned.
+    task "deconv_noisy" (pixel models; section 3.19): task "deconv" with N(0, sigma_y^2) noise, sigma_y > 0, from a generator seeded by
+    ``seed`` added to the blurred images, restored by ``model.deconvolve_noisy``.  Baselines, all from the noisy image: "blurred",
+    "pinv" (which shows the amplification) and "tikhonov", conj K^ / (|K^|^2 + sigma_y^2) applied through ops.circular_conv.  The
+    returned method is "ddnm_plus", "sigma_y" is returned, and consistency / consistency_u8 are the RMS of A(x_out) - y_clean in
+    uint8 levels: the result is not meant to reproduce the noisy image.
     downsample "bicubic" (task "sr" on a pixel model, without sr_mask, dpm_solver or sigma_y; section 3.15): the images are reduced
     by the antialiased bicubic matrix (``resize``) instead of pooled and ``model.super_resolve(downsample="bicubic")`` restores them.
     The baselines stay (replicate, bicubic upsampling); consistency / consistency_u8 are max |A(x_out) - y| in uint8 levels with that
@@ -205,6 +211,14 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
         if "psf" not in chain or not hasattr(model, "deconvolve"):
             raise ValueError("task 'deconv' needs a psf and a model with a deconvolve method (a pixel DDPM)")
         return _evaluate_deconv(model, images_uint8, batch_size=batch_size, seed=seed, **chain)
+    if task == DECONV_NOISY_TASK:
+        if method not in (None, "ddnm") or dpm_solver or sr_mask is not None or scale is not None or "kernel" in chain:
+            raise ValueError("task 'deconv_noisy' has one method, ddnm on ancestral or DDIM (eta > 0) steps, and no mask, scale or kernel")
+        if "psf" not in chain or not hasattr(model, "deconvolve_noisy"):
+            raise ValueError("task 'deconv_noisy' needs a psf and a model with a deconvolve_noisy method (a pixel DDPM)")
+        if isinstance(sigma_y, bool) or not isinstance(sigma_y, (int, float, np.integer, np.floating)) or not math.isfinite(sigma_y) or sigma_y <= 0:
+            raise ValueError(f"task 'deconv_noisy' needs a finite sigma_y > 0 (sigma_y = 0 is task 'deconv'), got {sigma_y!r}")
+        return _evaluate_deconv(model, images_uint8, batch_size=batch_size, seed=seed, sigma_y=float(sigma_y), **chain)
     if "psf" in chain:
         raise ValueError("psf belongs to task 'deconv'")
     if "kernel" in chain or "tol" in chain:
@@ -218,7 +232,7 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
     if "ratio" in chain or "perm_seed" in chain:
         raise ValueError("ratio and perm_seed belong to task 'cs'")
     if task not in TASKS:
-        raise ValueError(f"unknown task {task!r}: one of {(*TASKS, DEBLUR_TASK, CS_TASK, DECONV_TASK)}")
+        raise ValueError(f"unknown task {task!r}: one of {(*TASKS, DEBLUR_TASK, CS_TASK, DECONV_TASK, DECONV_NOISY_TASK)}")
     if task == "colorize":
         return _evaluate_colorize(model, images_uint8, batch_size=batch_size, seed=seed, scale=1 if scale is None else scale, method=method,
                                   sr_mask=sr_mask, dpm_solver=dpm_solver, sigma_y=sigma_y, **chain)
@@ -434,8 +448,8 @@ def _evaluate_cs(model, images_uint8, *, batch_size, seed, ratio, perm_seed=0, *
 
 
 @torch.no_grad()
-def _evaluate_deconv(model, images_uint8, *, batch_size, seed, psf, tol=3e-2, **chain):
-    """evaluate_restoration's task "deconv" (see there)"""
+def _evaluate_deconv(model, images_uint8, *, batch_size, seed, psf, tol=3e-2, sigma_y=0.0, **chain):
+    """evaluate_restoration's tasks "deconv" and (sigma_y > 0) "deconv_noisy" (see there)"""
     from ddk import ops
     from models.diffusion import psf as P
     x_all = from_u8(images_uint8)
@@ -452,20 +466,31 @@ def _evaluate_deconv(model, images_uint8, *, batch_size, seed, psf, tol=3e-2, **
     Md = torch.stack([Md, torch.zeros_like(Md)], dim=-1).contiguous()      # the projection A+ A as a multiplier
     batches = lambda S, v: torch.cat([ops.nhwc_to_nchw(ops.circular_conv(ops.nchw_to_nhwc(v[i:i + batch_size].to(device).contiguous()), S)).cpu()
                                       for i in range(0, n, batch_size)])
-    y_all = batches(Kd, x_all)
+    y_clean = batches(Kd, x_all)
+    y_all = y_clean + sigma_y * torch.randn(y_clean.shape, generator=torch.Generator().manual_seed(seed)) if sigma_y else y_clean
     yp_all = batches(Pd, y_all)
     K = len(model._spaced_tables(chain.get("respacing"), chain.get("ddim", False), chain.get("eta", 0.0))[1]) \
         if chain.get("respacing") is not None or chain.get("ddim") else int(model.timesteps)
     images = {"blurred": to_u8(y_all.clamp(-1, 1)), "pinv": to_u8(yp_all.clamp(-1, 1))}
+    if sigma_y:
+        Kc = P.psf_spectrum(k, h, w)
+        Wd = torch.from_numpy(P.interleave(np.conj(Kc) / (np.abs(Kc) ** 2 + sigma_y ** 2))).to(device)
+        images["tikhonov"] = to_u8(batches(Wd, y_all).clamp(-1, 1))
+    restore = (lambda y: model.deconvolve_noisy(y, k, sigma_y=sigma_y, tol=tol, **chain)) if sigma_y else (lambda y: model.deconvolve(y, k, tol=tol, **chain))
     outs = []
     for g, i in enumerate(range(0, n, batch_size)):
         torch.manual_seed(seed + g)               # x_T and the Philox key of batch g
-        outs.append(model.deconvolve(y_all[i:i + batch_size].to(device), k, tol=tol, **chain).float().cpu())
+        outs.append(restore(y_all[i:i + batch_size].to(device)).float().cpu())
     x_out = torch.cat(outs)
     images = dict(restored=to_u8(x_out), **images)
-    extra = dict(unet_forwards=K, psf=name, tol=float(tol), consistency=(batches(Md, x_out) - yp_all).abs().amax(dim=(1, 2, 3)).double().numpy())
+    extra = dict(unet_forwards=K, psf=name, tol=float(tol))
+    if sigma_y:
+        rms = lambda x: ((batches(Kd, x) - y_clean) ** 2).mean(dim=(1, 2, 3)).sqrt() * 127.5
+        extra.update(sigma_y=float(sigma_y), consistency=rms(x_out).double().numpy(), consistency_u8=rms(from_u8(images["restored"])).double().numpy())
+    else:
+        extra.update(consistency=(batches(Md, x_out) - yp_all).abs().amax(dim=(1, 2, 3)).double().numpy())
     methods = {name: _score(ops, img, ref, None, device) for name, img in images.items()}
-    return dict(n_images=n, method="ddnm_deconv", methods=methods, images={k: v.numpy() for k, v in images.items()}, **extra)
+    return dict(n_images=n, method="ddnm_plus" if sigma_y else "ddnm_deconv", methods=methods, images={k: v.numpy() for k, v in images.items()}, **extra)
 
 
 def report(result):

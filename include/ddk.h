@@ -448,6 +448,28 @@ int ddk_circular_conv(const float* x, const float* S, const float* twiddles, flo
 int ddk_p_sample_update_restore_fft(float* x, const float* eps_hat, const float* mask, const float* twiddles, const float* Yp, float* scratch,
                                     const int64_t* t, const float* c_recip, const float* c_recipm1, const float* c1, const float* c2,
                                     const float* sigma, int B, int H, int W, int channels, uint64_t seed, uint32_t stream_id, ddk_stream_t s);
+/* The forward half of ddk_circular_conv: out [B][channels][H W] complex fp32 = S . F2(x), left in the
+ * transform's own order -- frequency (u, v) at row brev(u), column brev(v) of the plane, brev reversing log2 H and log2 W bits.  With
+ * S = P it is the spectrum of A+ y that ddk_p_sample_update_restore_fft_noisy reads.  Arguments, shapes, scratch and errors as
+ * ddk_circular_conv; out is twice x's size and must not overlap x. */
+int ddk_circular_spectrum(const float* x, const float* S, const float* twiddles, float* out, float* scratch, int B, int H, int W, int channels,
+                          ddk_stream_t s);
+/* One DDNM+ deconvolution step on its own (ddk_sampler_run_restore_fft_noisy): ddk_p_sample_update_restore_fft
+ * for a blurred image that carries noise of standard deviation sigma_y.  Per sample b with row k = t[b], s = k > 0 ? sigma[k] : 0, and
+ * per frequency f with g = nsc[k] gain[f], every operation rounded on its own in fp32:
+ *   kept (mask[f]) and s >= g:  lam = 1,     phi = sqrt(max(s s - g g, 0))
+ *   kept and s < g:             lam = s / g, phi = 0
+ *   dropped:                    lam = 0,     phi = s
+ *   x0' = Re F2^-1(X^ + lam (Yhat - X^)) / (H W),   n = Re F2^-1(phi F2(z)) / (H W),   x = (c1 x0' + c2 x) + n
+ * with X^ = F2 of the clipped x0 and z the Philox draw of ddk_p_sample_update_restore (zeros at row 0).  gain [H][W] fp32 is 1 / |K^| at
+ * the kept frequencies (natural order), nsc the per-row table |c1| sigma_y, Yhat ddk_circular_spectrum's output for S = P; at a dropped
+ * frequency Yhat is never read.  A plane of at most 16384 pixels takes one launch (x0 and z ride one complex transform); a larger one
+ * three through `scratch`, a device array of FOUR times x's size (T and T2) that may be NULL for the smaller planes.  Shapes and alignment
+ * as ddk_circular_conv.  Anything else is DDK_ERR_ARG; on an error x is not touched. */
+int ddk_p_sample_update_restore_fft_noisy(float* x, const float* eps_hat, const float* mask, const float* gain, const float* nsc,
+                                          const float* twiddles, const float* Yhat, float* scratch, const int64_t* t, const float* c_recip,
+                                          const float* c_recipm1, const float* c1, const float* c2, const float* sigma, int B, int H, int W,
+                                          int channels, uint64_t seed, uint32_t stream_id, ddk_stream_t s);
 /* The end of a forward in one launch (unet.py:69-72 behind the final Block's conv; ddpm.py:203-227): GroupNorm from the conv's
  * partials -> Mish -> 1x1 projection to n_out <= 8 channels (w [n_out][C], bias [n_out]) -> eps_hat; eps_out and / or x may be
  * given: eps_out [B][HW][n_out] receives eps_hat, x [B][HW][n_out] gets the reverse-step update of ddk_p_sample_update in place
@@ -782,6 +804,18 @@ size_t ddk_sampler_restore_fft_workspace_bytes(const ddk_unet* u, int B, int H, 
 int ddk_sampler_restore_fft_tail_parts(const ddk_unet* u, int B, int H, int W);
 int ddk_sampler_run_restore_fft(const ddk_sampler_args* a, const int64_t* timestep_map, const float* mask, const float* P,
                                 const float* twiddles, const float* y, ddk_stream_t s);
+/* DDNM+ deconvolution of a noisy blurred image: ddk_sampler_run_restore_fft's chain, every step being
+ * ddk_p_sample_update_restore_fft_noisy's.  gain [H][W] fp32 and nsc (t_start + 1 floats) are device arrays like mask and P; all are
+ * copied into the workspace and the spectrum of A+ y is formed there before the first step, outside any captured one.  The workspace
+ * (ddk_sampler_restore_fft_noisy_workspace_bytes; 0 for a shape the kind does not take) holds ddk_sampler_restore_fft_workspace_bytes
+ * plus gain (H W floats), nsc (t_start + 1 floats), the spectrum (twice the latent's size) and, for planes above 16384 pixels, T2 (twice
+ * the latent's size), each rounded up to four floats.  Never the fused tail: ddk_sampler_restore_fft_noisy_tail_parts is 0 for every
+ * shape (-1 for a shape the plan does not take).  Graphs are cached under a chain kind of their own with the caller's gain and nsc in
+ * the key. */
+size_t ddk_sampler_restore_fft_noisy_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start);
+int ddk_sampler_restore_fft_noisy_tail_parts(const ddk_unet* u, int B, int H, int W);
+int ddk_sampler_run_restore_fft_noisy(const ddk_sampler_args* a, const int64_t* timestep_map, const float* mask, const float* P,
+                                      const float* gain, const float* nsc, const float* twiddles, const float* y, ddk_stream_t s);
 /* Drops the plan's cached sampler and likelihood-sweep graphs and shift table (waits for the device when graphs exist). */
 int ddk_sampler_invalidate(ddk_unet* u);
 /* Drops only the cached graphs (and shift table) that live in / point into `workspace`, after waiting for the launches of

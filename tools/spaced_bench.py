@@ -52,7 +52,12 @@ five each, so the deblurring step's ratio from the same run stands beside it as 
 --restore-fft: the cost of a DDNM deconvolution step (the disk point-spread function, tol 3e-2) against an
 ancestral step of the same respaced chain on the same two models: 3 x 32 x 32 at B = 32, "50" steps (the plane form, one launch) and
 3 x 256 x 256 at B = 8, "20" steps (the multi-launch form, three launches).  The ancestral, deconvolution and compressed-sensing
-chains alternate in one process, medians of five each; the result is also written to profiles/restore_fft_bench.json."""
+chains alternate in one process, medians of five each; the result is also written to profiles/restore_fft_bench.json.
+
+--restore-fft-noisy: the cost of a DDNM+ deconvolution step (the disk point-spread function, tol 3e-2, sigma_y
+0.05) against an ancestral step and against the deconvolution step of the same respaced chain, on --restore-fft's two models and
+steps.  The ancestral, deconvolution and noisy deconvolution chains alternate in one process, medians of five each; the result is
+also written to profiles/restore_fft_noisy_bench.json."""
 import argparse
 import json
 import os
@@ -88,6 +93,7 @@ def main():
     ap.add_argument("--restore-sep", action="store_true", help="bicubic x4 restore_sep step against an ancestral step, and the cost of forming Yp, on the --restore-blur models")
     ap.add_argument("--restore-cs", action="store_true", help="compressed-sensing step (ratio 0.25) and deblurring step against an ancestral step on the --restore-blur models")
     ap.add_argument("--restore-fft", action="store_true", help="deconvolution step (disk PSF) and compressed-sensing step against an ancestral step on the --restore-blur models")
+    ap.add_argument("--restore-fft-noisy", action="store_true", help="DDNM+ deconvolution step (disk PSF, sigma_y 0.05) against an ancestral and a deconvolution step on the --restore-blur models")
     ap.add_argument("--restore-solver", action="store_true", help="DDNM step on the 2M chain (n = 1 center mask, n = 2) against a 2M step, logsnr20")
     args = ap.parse_args()
     torch.cuda.set_device(0)
@@ -101,6 +107,8 @@ def main():
         return restore_cs_ab()
     if args.restore_fft:
         return restore_fft_ab()
+    if args.restore_fft_noisy:
+        return restore_fft_noisy_ab()
     cfg = bench.cfg4()
     model = DownsampleDDPM(cfg, Unet(cfg), DEV, 3)
     model.load_state_dict(syn.fill_state_dict(model.state_dict(), skip=syn.SCHEDULE_KEYS))
@@ -522,6 +530,64 @@ def restore_fft_ab():
                                  "steps": K, **{f"{k}_min_max_ms": [round(min(v), 4), round(max(v), 4)] for k, v in times.items()}}
         del model, plan
     out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "restore_fft_bench.json")
+    with open(out, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(res), flush=True)
+
+
+def restore_fft_noisy_ab():
+    """restore_fft_ab's models and steps: the ancestral, deconvolution and noisy deconvolution chains alternating"""
+    from models.diffusion import psf
+    name_psf, tol, sigma_y = "disk", 3e-2, 0.05
+    res = {"shape": f"pixel DDPMs, T={T}, DDNM+ deconvolution step ({name_psf} point-spread function, tol {tol}, sigma_y {sigma_y}) vs deconvolution "
+                    "step and ancestral step of the same respaced chain", "reps": REPS, "per_case": {}}
+    for name, chan, size, b, K in (("3x32x32_B32_chan128_plane_form", 128, 32, 32, 50), ("3x256x256_B8_chan32_multi_launch_form", 32, 256, 8, 20)):
+        cfg = dict(unet_chan=chan, unet_in=3, unet_dims=(1, 2, 2, 2), unet_dropout=0.0, image_size=size, T=T, loss_type="simple",
+                   beta_schedule="linear", loss_flat="sum")
+        model = DDPM(cfg, Unet(cfg), DEV, 3)
+        model.load_state_dict(syn.fill_state_dict(model.state_dict(), skip=syn.SCHEDULE_KEYS))
+        model = model.to(DEV).eval()
+        plan = model.latent_model.plan()
+        x0 = ops.randn((b, size, size, 3), DEV, seed=1234, step=T, stream_id=0)
+        x = x0.clone()
+        Kd, Pd, Md, _ = (torch.from_numpy(v).to(DEV) for v in psf.psf_operands(name_psf, size, size, tol))
+        sp, use = model._spaced_tables(str(K), False, 0.0)
+        gd, nd = (torch.from_numpy(v).to(DEV) for v in psf.psf_noisy_operands(name_psf, size, size, tol, sigma_y, sp["c1"]))
+        y_fft = ops.circular_conv(x0.clamp(-1, 1), Kd)
+        y_noisy = y_fft + sigma_y * ops.randn(tuple(x0.shape), DEV, seed=99, step=1, stream_id=0)
+
+        def chain(kind):
+            x.copy_(x0)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            if kind == "anc":
+                plan.sample_nhwc(x, sp, K - 1, 0, seed=1234, stream_id=0, timesteps=use)
+            elif kind == "fft":
+                plan.sample_restore_fft_nhwc(x, y_fft, Md, Pd, sp, K - 1, seed=1234, stream_id=0, timesteps=use)
+            else:
+                plan.sample_restore_fft_noisy_nhwc(x, y_noisy, Md, Pd, gd, nd, sp, K - 1, seed=1234, stream_id=0, timesteps=use)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3
+
+        with torch.no_grad():
+            t_settle = time.perf_counter()
+            while time.perf_counter() - t_settle < 2.0:
+                chain("anc")
+            chain("fft")                                 # every chain's graphs are captured outside the timed calls
+            chain("noisy")
+            times = {"anc": [], "fft": [], "noisy": []}
+            for _ in range(REPS):
+                for kind in times:
+                    times[kind].append(chain(kind) / K)
+        assert torch.isfinite(x).all() and plan.restore_fft_noisy_tail_parts(b, size, size) == 0
+        a, f, n = (statistics.median(times[k]) for k in ("anc", "fft", "noisy"))
+        res["per_case"][name] = {"ancestral_ms_per_step": round(a, 4), "fft_ms_per_step": round(f, 4), "noisy_ms_per_step": round(n, 4),
+                                 "noisy_over_ancestral": round(n / a, 4), "noisy_over_fft": round(n / f, 4), "fft_over_ancestral": round(f / a, 4),
+                                 "kept": int(Md.sum().item()), "steps": K,
+                                 **{f"{k}_min_max_ms": [round(min(v), 4), round(max(v), 4)] for k, v in times.items()}}
+        del model, plan
+    out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "restore_fft_noisy_bench.json")
     with open(out, "w") as fh:
         json.dump(res, fh, indent=1)
         fh.write("\n")
