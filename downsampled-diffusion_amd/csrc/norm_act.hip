@@ -681,7 +681,9 @@ int chan_layernorm(const float* x, const float* g, const float* b, float* out, l
         default: break;
     }
 #undef LN_CASE
-    return fail_arg("layernorm: unsupported channel count (supported: 32,64,96,128,192,256,384,512,768,1024)");
+    // every other width (160, 224, 320, ... : the plan admits any multiple of 32 up to 512): the one-wave-per-pixel kernel of the
+    // padded widths with pitch == C -- correct, untuned
+    return chan_layernorm_generic(x, g, b, out, M, C, C, eps, st);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -18,8 +18,10 @@ def _grad_slot(p):
     """The tensor a parameter gradient can be accumulated into in place: ``p.grad`` when it already exists as a dense fp32
     buffer (trainers/optim.py gives every parameter a view of ONE flat gradient buffer).  The backward kernels then add
     into it directly and the Function returns None for that input -- no zero-fill, no temporary, no torch add."""
+    if p is None or not p.is_leaf:        # (a padded copy of a parameter is no leaf: reading its .grad only draws a warning)
+        return None
     g = getattr(p, "grad", None)
-    if p is not None and p.is_leaf and g is not None and g.dtype == torch.float32 and g.is_contiguous():
+    if g is not None and g.dtype == torch.float32 and g.is_contiguous():
         return g
     return None
 
@@ -316,13 +318,35 @@ class ConvGNMishFn(torch.autograd.Function):
                 None)
 
 
+def gn_tuned(c, groups=8):
+    """the tuned training GroupNorm (gn_train_launch: a float4 unit count per pixel row that is a power of two <= 8) takes 4, 8, 16 or
+    32 channels per group -- 32, 64, 128, 256 channels at 8 groups.  Every other width that is a multiple of 32 (96, 160, 192, 224,
+    320, 384, 512, ...) runs the generic training kernels with pitch == C (GNMishGenericFn: C / groups <= 256)."""
+    return c % groups == 0 and c // groups in (4, 8, 16, 32)
+
+
+def ln_tuned(c):
+    """the widths ddk_chan_layernorm_bwd has an instantiation for; the others run chan_layernorm_generic_bwd with pitch == C (C <= 512)"""
+    return c in (32, 64, 128, 256, 512)
+
+
 def conv_groupnorm_mish(x, weight, bias, gamma, beta, x2=None, temb=None, addend=None, drop_p=0.0, seed=0, layer=0, groups=8, eps=1e-5,
                         give=None, take=None, dy_link=None, dx_link=None, give2=None):
+    if not gn_tuned(weight.shape[0], groups):
+        # the generic GroupNorm neither hands gradients over nor reads slabs: the caller decides per module (trainers/autograd_unet.py),
+        # so that both ends of a hand-off are on the same path
+        if any(h is not None for h in (give, take, dy_link, dx_link, give2)):
+            raise RuntimeError(f"conv_groupnorm_mish: {weight.shape[0]} channels in {groups} groups run the generic GroupNorm, which takes "
+                               "no gradient hand-off")
+        raw = conv(ops.CONV3X3_S1, x, weight, bias, x2=x2)
+        return GNMishGenericFn.apply(raw, gamma, beta, temb, addend, float(drop_p), int(seed), int(layer), groups, eps)
     return ConvGNMishFn.apply(x, x2, weight, bias, gamma, beta, temb, addend, float(drop_p), int(seed), int(layer), groups, eps, give, take,
                               dy_link, dx_link, give2)
 
 
 def groupnorm_mish(x, gamma, beta, temb=None, addend=None, drop_p=0.0, seed=0, layer=0, groups=8, eps=1e-5):
+    if not gn_tuned(x.shape[-1], groups):
+        return GNMishGenericFn.apply(x, gamma, beta, temb, addend, float(drop_p), int(seed), int(layer), groups, eps)
     return GNMishFn.apply(x, gamma, beta, temb, addend, float(drop_p), int(seed), int(layer), groups, eps)
 
 
@@ -429,6 +453,10 @@ class ChanLayerNormFn(torch.autograd.Function):
         x, g, b = ctx.saved_tensors
         sg, sb = _grad_slot(g), _grad_slot(b)
         extra = ctx.take.take()[0] if ctx.take is not None else None
+        if not ln_tuned(x.shape[-1]):
+            # 96, 160, 192, ...: the generic backward kernel with pitch == C (it adds the Residual's gradient in the same launch too)
+            dx, dg, db = ops.chan_layernorm_generic_bwd(x, g.detach(), _c(dy), ctx.eps, addend=extra)
+            return dx, dg.reshape(g.shape), db.reshape(g.shape), None, None
         dx, dg, db = ops.chan_layernorm_bwd(x, g.detach(), _c(dy), ctx.eps, acc=(sg, sb) if sg is not None and sb is not None else None,
                                             addend=extra)
         if dg is None:

@@ -38,6 +38,15 @@ def _block(blk, x, x2=None, temb=None, addend=None, drop_p=0.0, seeds=None, give
 
 def _resnet(rb, x, temb_slice, x2=None, seeds=None, give2=None):
     """blocks.py:105-115: h = drop(Block1(x) + shift); out = Block2(h) + res(x)"""
+    c_out = rb.block1.block[0].weight.shape[0]
+    if not AG.gn_tuned(c_out, rb.block1.groups):
+        # 96, 160, 192, 384, 512, ... channels: the tuned GroupNorm backward keeps 4, 8, 16 or 32 channels per group, so the WHOLE block --
+        # both ends of its hand-off and of its slab link -- runs the forms of the padded widths with pitch == C.  give2 is not used: the
+        # skip's gradient goes back to autograd, which adds it to the Downsample conv's; that conv's take() of a hand-off nobody gave
+        # to adds nothing (as for the first level's skip, which no up level consumes).
+        c_in2 = None if x2 is None else x2.shape[-1]
+        c_in = rb.block1.block[0].weight.shape[1] - (c_in2 or 0)       # the REAL channels of x (the network's input keeps a padded pitch)
+        return _gresnet(rb, x, c_in, temb_slice, x2=x2, c_in2=c_in2, seeds=seeds)[0]
     p = rb.dropout.p if rb.training else 0.0
     # the gradient of the skip path reaches x (and x2) through Block1's input-gradient conv epilogue, not through an autograd add:
     # identity skip -> Block2 hands its addend gradient over; 1x1 skip -> the skip conv hands its input gradients over
@@ -56,6 +65,8 @@ def _attention(res_mod, x):
     """Residual(PreNorm(LinearAttention)): blocks.py:8-14,63-71,126-134"""
     pre = res_mod.fn
     att = pre.fn
+    if not AG.ln_tuned(x.shape[-1]):
+        return _gattention(res_mod, x, x.shape[-1])       # no tuned LayerNorm backward at this width: generic forms, pitch == C
     hand = AG.GradHandoff()        # the Residual's gradient reaches x inside the LayerNorm backward kernel, not through an autograd add
     xn = AG.ChanLayerNormFn.apply(x, pre.norm.g, pre.norm.b, pre.norm.eps, hand)
     qkv = AG.conv(ops.CONV1X1, xn, att.to_qkv.weight)
