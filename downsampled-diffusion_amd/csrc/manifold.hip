@@ -10,8 +10,14 @@
 // Numerics: a dot product is one fmaf chain over k in a fixed order (within a group of 8 features: 0 4 1 5 2 6 3 7) that depends on
 // nothing but D, so the column split, the launch geometry and the arrival order change no bit.  Selection works on the multiset of a
 // row's distances and flags only ever receive a 1: no atomics, no order anywhere.
+//
+// On the same tiles:
+//   * ddk_manifold_ball_counts counts d <= r per row instead of testing for any (density / coverage, Naeem et al. 2020): integer adds;
+//   * ddk_poly_mmd_sums replaces the distance by the cubic kernel k = (gamma u.v + coef0)^3 and the test by a sum (KID, Binkowski et
+//     al. 2018): fp32 up to k, double from there on, one partial per tile and a finish kernel that adds them in a fixed order.
 #include "ddk_internal.h"
 
+#include <algorithm>
 #include <cmath>
 
 namespace ddk {
@@ -254,6 +260,172 @@ __global__ __launch_bounds__(MF_THREADS) void mf_members_kernel(const float* __r
     }
 }
 
+// workgroup (rb, sp): rows rb 128 .. of a against its column tiles of b; counts[i] += the number of its columns j with
+// d(a_i, b_j) <= ra[i].  counts is zero before the launch; integer adds are exact in any order.
+// Every lane counts its own columns over the whole column walk; a row's columns sit in the 32 lanes of a half wave, which are added
+// once at the end.
+__global__ __launch_bounds__(MF_THREADS) void mf_ball_counts_kernel(const float* __restrict__ a, const float* __restrict__ na,
+                                                                    const float* __restrict__ ra, int Na, const float* __restrict__ b,
+                                                                    const float* __restrict__ nb, int Nb, int D, int col_tiles, int tps,
+                                                                    int* __restrict__ counts) {
+    __shared__ MfSmem sm;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wm = wave >> 1, wn = wave & 1, lr = lane & 31, lh = lane >> 5;
+    const int rbase = blockIdx.x * MF_TILE, sp = blockIdx.y;
+    const int t0 = sp * tps, t1 = min(col_tiles, t0 + tps);
+    int cnt[2][16];
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+        for (int g = 0; g < 16; ++g) cnt[mi][g] = 0;
+    for (int t = t0; t < t1; ++t) {
+        const int cbase = t * MF_TILE;
+        mf_f32x16 acc[2][2];
+        mf_tile_dots(a, Na, rbase, b, Nb, cbase, D, sm, acc);
+        bool cv[2];
+        float nv[2];
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni) {
+            const int col = cbase + wn * 64 + ni * 32 + lr;
+            cv[ni] = col < Nb;
+            nv[ni] = cv[ni] ? nb[col] : 0.0f;
+        }
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+            for (int g = 0; g < 16; ++g) {
+                const int row = rbase + wm * 64 + mi * 32 + (g & 3) + 8 * (g >> 2) + 4 * lh;
+                const bool rv = row < Na;
+                const float nu = rv ? na[row] : 0.0f, ru = rv ? ra[row] : 0.0f;
+#pragma unroll
+                for (int ni = 0; ni < 2; ++ni) cnt[mi][g] += (rv && cv[ni] && mf_dist(nu, acc[mi][ni][g], nv[ni]) <= ru) ? 1 : 0;
+            }
+    }
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+        for (int g = 0; g < 16; ++g) {
+            int c = cnt[mi][g];
+#pragma unroll
+            for (int o = 16; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);       // offsets below 32 stay inside the half wave
+            const int row = rbase + wm * 64 + mi * 32 + (g & 3) + 8 * (g >> 2) + 4 * lh;
+            if (lr == 0 && row < Na && c > 0) atomicAdd(counts + row, c);
+        }
+}
+
+// ---- the kernel-matrix sums of MMD^2 with k(x, y) = (gamma x.y + coef0)^3 (KID)
+// Tiles of one segment, in this order: the upper triangle (ti <= tj, row-major) of the ta x ta tiles of a x a, the same of b x b, then
+// the ta x tb tiles of a x b.  Every tile gives one double partial; an off-diagonal tile of a symmetric matrix counts twice (its mirror
+// image holds the same fmaf chains, bit for bit, so 2 x is the same sum).
+
+// item r of the row-major upper triangle of T x T tiles -> (ti, tj); row ti begins at ti T - ti (ti - 1) / 2
+__device__ __forceinline__ void mf_triangle(long long r, long long T, int* ti, int* tj) {
+    const double w = 2.0 * (double)T + 1.0;
+    long long i = (long long)((w - sqrt(fmax(w * w - 8.0 * (double)r, 0.0))) * 0.5);
+    i = max(0ll, min(T - 1, i));
+    while (i > 0 && i * T - i * (i - 1) / 2 > r) --i;                         // the square root may be off by one either way
+    while (i + 1 < T && (i + 1) * T - (i + 1) * i / 2 <= r) ++i;
+    *ti = (int)i;
+    *tj = (int)(i + (r - (i * T - i * (i - 1) / 2)));
+}
+
+__device__ __forceinline__ double mf_wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// partials[item] for item = blockIdx.x, + gridDim.x, ..: segment item / per, tile item % per in the order above.  Rows of a tile past
+// the segment's end are read as zeros by mf_fetch (its n is the segment's row count) and masked here by index, as is the diagonal.
+__global__ __launch_bounds__(MF_THREADS) void mf_mmd_kernel(const float* __restrict__ a, const float* __restrict__ b, int ma, int mb, int D,
+                                                            float gamma, float coef0, long long total, double* __restrict__ partials) {
+    __shared__ MfSmem sm;
+    __shared__ double red[MF_THREADS / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wm = wave >> 1, wn = wave & 1, lr = lane & 31, lh = lane >> 5;
+    const long long ta = (ma + MF_TILE - 1) / MF_TILE, tb = (mb + MF_TILE - 1) / MF_TILE;
+    const long long naa = ta * (ta + 1) / 2, nbb = tb * (tb + 1) / 2, per = naa + nbb + ta * tb;
+    for (long long item = blockIdx.x; item < total; item += gridDim.x) {
+        const long long seg = item / per;
+        long long r = item - seg * per;
+        const float* pa = a + (size_t)seg * ma * D;
+        const float* pb = b + (size_t)seg * mb * D;
+        const float *u, *v;
+        int nu, nv, ti, tj;
+        bool sym = true;
+        if (r < naa) {
+            u = v = pa;
+            nu = nv = ma;
+            mf_triangle(r, ta, &ti, &tj);
+        } else if (r < naa + nbb) {
+            u = v = pb;
+            nu = nv = mb;
+            mf_triangle(r - naa, tb, &ti, &tj);
+        } else {
+            r -= naa + nbb;
+            sym = false;
+            u = pa, nu = ma;
+            v = pb, nv = mb;
+            ti = (int)(r / tb), tj = (int)(r % tb);
+        }
+        const int rbase = ti * MF_TILE, cbase = tj * MF_TILE;
+        const bool diag = sym && ti == tj;
+        mf_f32x16 acc[2][2];
+        mf_tile_dots(u, nu, rbase, v, nv, cbase, D, sm, acc);
+        double s = 0.0;
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni) {
+            const int col = cbase + wn * 64 + ni * 32 + lr;
+#pragma unroll
+            for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+                for (int g = 0; g < 16; ++g) {
+                    const int row = rbase + wm * 64 + mi * 32 + (g & 3) + 8 * (g >> 2) + 4 * lh;
+                    const float t = fmaf(gamma, acc[mi][ni][g], coef0);
+                    const float k = (t * t) * t;
+                    s += (row < nu && col < nv && !(diag && row == col)) ? (double)k : 0.0;
+                }
+        }
+        s = mf_wave_sum_f64(s);
+        if (lane == 0) red[wave] = s;         // read below before the barrier that opens the next item's mf_tile_dots
+        __syncthreads();
+        if (threadIdx.x == 0) partials[item] = ((sym && !diag) ? 2.0 : 1.0) * (((red[0] + red[1]) + red[2]) + red[3]);
+    }
+}
+
+// sums[seg][m] = the partials of matrix m of the segment: thread t adds partials t, t + 256, .. in that order, then a fixed tree
+__global__ __launch_bounds__(256) void mf_mmd_finish_kernel(const double* __restrict__ partials, long long outputs, long long naa,
+                                                            long long nbb, long long nab, double* __restrict__ sums) {
+    __shared__ double red[256];
+    const long long per = naa + nbb + nab;
+    for (long long o = blockIdx.x; o < outputs; o += gridDim.x) {
+        const long long seg = o / 3;
+        const int m = (int)(o - seg * 3);
+        const long long off = m == 0 ? 0 : (m == 1 ? naa : naa + nbb), n = m == 0 ? naa : (m == 1 ? nbb : nab);
+        const double* p = partials + seg * per + off;
+        double s = 0.0;
+        for (long long i = threadIdx.x; i < n; i += 256) s += p[i];
+        red[threadIdx.x] = s;
+        __syncthreads();
+        for (int w = 128; w > 0; w >>= 1) {
+            if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) sums[o] = red[0];
+        __syncthreads();
+    }
+}
+
+constexpr long long MF_MAX_GRID = 1 << 20;      // workgroups of a launch at most; the kernels above stride over what is left
+
+// tiles of one segment: *naa, *nbb upper triangles, *nab the rectangle; false when the arguments are out of range
+static bool mf_mmd_tiles(int S, int ma, int mb, long long* naa, long long* nbb, long long* nab) {
+    if (S < 1 || ma < 2 || mb < 2 || (long long)S * ma > MF_MAX_ROWS || (long long)S * mb > MF_MAX_ROWS) return false;
+    const long long ta = ceil_div(ma, MF_TILE), tb = ceil_div(mb, MF_TILE);
+    *naa = ta * (ta + 1) / 2;
+    *nbb = tb * (tb + 1) / 2;
+    *nab = ta * tb;
+    return true;
+}
+
 // How the column tiles of a launch with `row_blocks` row blocks are shared out: *tps tiles per workgroup, the return value ranges.
 // A launch of W workgroups runs in ceil(W / MF_RESIDENT_WGS) rounds of the time of one workgroup, tps tiles; the split is the smallest
 // number of ranges that minimises rounds x tps.  N = 10 000: 79 row blocks x 6 ranges = 474 workgroups of 14 tiles, one round, where
@@ -351,5 +523,65 @@ int ddk_manifold_members(const float* a, const float* ra, int Na, const float* b
     hipLaunchKernelGGL(mf_members_kernel, dim3((unsigned)row_blocks, (unsigned)splits), dim3(MF_THREADS), 0, as_stream(s), a, (const float*)na,
                        ra, Na, b, (const float*)nb, rb, Nb, D, (int)col_tiles, tps, a_in, b_in);
     return check_launch("mf_members_kernel");
+}
+
+size_t ddk_manifold_ball_counts_workspace_bytes(int Na, int Nb) { return ddk_manifold_members_workspace_bytes(Na, Nb); }
+
+int ddk_manifold_ball_counts(const float* a, const float* ra, int Na, const float* b, int Nb, int D, int* counts, void* workspace,
+                             size_t workspace_bytes, ddk_stream_t s) {
+    DDK_REQUIRE(a && ra && b && counts, "manifold_ball_counts: null pointer");
+    DDK_REQUIRE(mf_shape_ok(Na, D) && mf_shape_ok(Nb, D), "manifold_ball_counts: Na, Nb in 1..2^24, D positive and a multiple of 4");
+    DDK_REQUIRE(aligned16(a) && aligned16(b), "manifold_ball_counts: a and b must be 16-byte aligned");
+    DDK_REQUIRE((reinterpret_cast<uintptr_t>(counts) & 3u) == 0, "manifold_ball_counts: counts must be 4-byte aligned");
+    DDK_REQUIRE(workspace && workspace_bytes >= ddk_manifold_ball_counts_workspace_bytes(Na, Nb) && aligned16(workspace),
+                "manifold_ball_counts: workspace (ddk_manifold_ball_counts_workspace_bytes, 16-byte aligned)");
+    float* na = static_cast<float*>(workspace);
+    float* nb = na + Na;
+#ifdef DDK_HOST_SANITIZE
+    san::extent("manifold_ball_counts a", a, (long long)Na * D * 4); san::extent("manifold_ball_counts b", b, (long long)Nb * D * 4);
+    san::extent("manifold_ball_counts ra", ra, (long long)Na * 4); san::extent("manifold_ball_counts counts", counts, (long long)Na * 4);
+    san::extent("manifold_ball_counts norms", na, ((long long)Na + Nb) * 4);
+#endif
+    DDK_HIP(hipMemsetAsync(counts, 0, (size_t)Na * sizeof(int), as_stream(s)));
+    DDK_TRY(mf_norms(a, Na, D, na, as_stream(s)));
+    DDK_TRY(mf_norms(b, Nb, D, nb, as_stream(s)));
+    int tps;
+    const long long row_blocks = ceil_div(Na, MF_TILE), col_tiles = ceil_div(Nb, MF_TILE);
+    const int splits = mf_col_splits(row_blocks, col_tiles, &tps);
+    hipLaunchKernelGGL(mf_ball_counts_kernel, dim3((unsigned)row_blocks, (unsigned)splits), dim3(MF_THREADS), 0, as_stream(s), a,
+                       (const float*)na, ra, Na, b, (const float*)nb, Nb, D, (int)col_tiles, tps, counts);
+    return check_launch("mf_ball_counts_kernel");
+}
+
+size_t ddk_poly_mmd_workspace_bytes(int S, int ma, int mb) {
+    long long naa, nbb, nab;
+    if (!mf_mmd_tiles(S, ma, mb, &naa, &nbb, &nab)) return 0;
+    return (size_t)S * (size_t)(naa + nbb + nab) * sizeof(double);
+}
+
+int ddk_poly_mmd_sums(const float* a, const float* b, int S, int ma, int mb, int D, float gamma, float coef0, double* sums, void* workspace,
+                      size_t workspace_bytes, ddk_stream_t s) {
+    DDK_REQUIRE(a && b && sums, "poly_mmd_sums: null pointer");
+    DDK_REQUIRE(D > 0 && D % 4 == 0, "poly_mmd_sums: D positive and a multiple of 4");
+    DDK_REQUIRE(S >= 1 && ma >= 2 && mb >= 2, "poly_mmd_sums: S >= 1 segments of ma >= 2 and mb >= 2 rows");
+    long long naa, nbb, nab;
+    DDK_REQUIRE(mf_mmd_tiles(S, ma, mb, &naa, &nbb, &nab), "poly_mmd_sums: S ma and S mb must be at most 2^24 rows");
+    DDK_REQUIRE(std::isfinite(gamma) && std::isfinite(coef0), "poly_mmd_sums: gamma and coef0 must be finite");
+    DDK_REQUIRE(aligned16(a) && aligned16(b), "poly_mmd_sums: a and b must be 16-byte aligned");
+    DDK_REQUIRE((reinterpret_cast<uintptr_t>(sums) & 7u) == 0, "poly_mmd_sums: sums must be 8-byte aligned");
+    DDK_REQUIRE(workspace && workspace_bytes >= ddk_poly_mmd_workspace_bytes(S, ma, mb) && aligned16(workspace),
+                "poly_mmd_sums: workspace (ddk_poly_mmd_workspace_bytes, 16-byte aligned)");
+    const long long total = (long long)S * (naa + nbb + nab), outputs = 3ll * S;
+    double* partials = static_cast<double*>(workspace);
+#ifdef DDK_HOST_SANITIZE
+    san::extent("poly_mmd_sums a", a, (long long)S * ma * D * 4); san::extent("poly_mmd_sums b", b, (long long)S * mb * D * 4);
+    san::extent("poly_mmd_sums sums", sums, outputs * 8); san::extent("poly_mmd_sums partials", partials, total * 8);
+#endif
+    hipLaunchKernelGGL(mf_mmd_kernel, dim3((unsigned)std::min(total, MF_MAX_GRID)), dim3(MF_THREADS), 0, as_stream(s), a, b, ma, mb, D, gamma,
+                       coef0, total, partials);
+    DDK_TRY(check_launch("mf_mmd_kernel"));
+    hipLaunchKernelGGL(mf_mmd_finish_kernel, dim3((unsigned)std::min(outputs, MF_MAX_GRID)), dim3(256), 0, as_stream(s),
+                       (const double*)partials, outputs, naa, nbb, nab, sums);
+    return check_launch("mf_mmd_finish_kernel");
 }
 }

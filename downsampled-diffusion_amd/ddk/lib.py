@@ -183,6 +183,10 @@ SIGNATURES = {
     "ddk_knn_radii": (_I, [_P, _I, _I, _I, _P, _P, _SZ, _P]),
     "ddk_manifold_members_workspace_bytes": (_SZ, [_I, _I]),
     "ddk_manifold_members": (_I, [_P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _SZ, _P]),
+    "ddk_manifold_ball_counts_workspace_bytes": (_SZ, [_I, _I]),
+    "ddk_manifold_ball_counts": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _SZ, _P]),
+    "ddk_poly_mmd_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "ddk_poly_mmd_sums": (_I, [_P, _P, _I, _I, _I, _I, _F, _F, _P, _P, _SZ, _P]),
     "ddk_unet_create": (_P, [C.POINTER(UnetConfig)]),
     "ddk_unet_destroy": (None, [_P]),
     "ddk_unet_num_slots": (_I, [_P]),

@@ -4,6 +4,7 @@ Tensors are fp32, contiguous, on a ROCm device; activations are [B, H, W, C].  t
 only to allocate outputs / workspaces and to supply the current stream.
 """
 import ctypes as C
+import math
 
 import torch
 
@@ -1194,6 +1195,69 @@ def manifold_members(a, ra, b, rb):
     L.check(lib.ddk_manifold_members(L.ptr(a), L.ptr(ra), na, L.ptr(b), L.ptr(rb), nb, a.shape[1], L.ptr(a_in), L.ptr(b_in), L.ptr(ws),
                                      nbytes, L.stream()), "manifold_members")
     return (a_in.bool() if a_in is not None else None), (b_in.bool() if b_in is not None else None)
+
+
+def manifold_ball_counts(a, ra, b):
+    """counts[i] = the number of rows j of b [Nb, D] with d(a_i, b_j) <= ra[i], for the rows of a [Na, D] (float32 device tensors,
+    ra float32 [Na]): how many samples lie in each reference row's k-NN ball (density / coverage, Naeem et al. 2020).
+    Returns an int32 [Na] device tensor.  DESIGN.md section 3.20."""
+    what = "manifold_ball_counts"
+    for name, t in (("a", a), ("b", b)):
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise ValueError(f"{what}: {name} must be a float32 tensor, got {getattr(t, 'dtype', type(t))}")
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1]:
+        raise ValueError(f"{what}: a and b must be [Na, D] and [Nb, D] with one D, got {tuple(a.shape)} and {tuple(b.shape)}")
+    na, nb = a.shape[0], b.shape[0]
+    if not torch.is_tensor(ra) or ra.dtype != torch.float32 or tuple(ra.shape) != (na,):
+        raise ValueError(f"{what}: ra must be a float32 [{na}] tensor, got {getattr(ra, 'dtype', type(ra))} "
+                         f"{tuple(getattr(ra, 'shape', ()))}")
+    a, b = _manifold_features(what, "a", a), _manifold_features(what, "b", b)
+    ra = _manifold_radii_arg(what, "ra", ra, na, a.device)
+    lib = L.load()
+    counts = torch.empty((na,), device=a.device, dtype=torch.int32)
+    nbytes = lib.ddk_manifold_ball_counts_workspace_bytes(na, nb)
+    ws = _ws(a.device, nbytes, "manifold")
+    L.check(lib.ddk_manifold_ball_counts(L.ptr(a), L.ptr(ra), na, L.ptr(b), nb, a.shape[1], L.ptr(counts), L.ptr(ws), nbytes, L.stream()),
+            "manifold_ball_counts")
+    return counts
+
+
+POLY_MMD_MAX_ROWS = 1 << 24   # csrc/manifold.hip MF_MAX_ROWS: rows of all segments together, per side
+
+
+def poly_mmd_sums(a, b, segments=1, gamma=None, coef0=1.0):
+    """The three kernel-matrix sums of the unbiased MMD^2 with k(x, y) = (gamma x.y + coef0)^3, per segment (KID).
+    a [S ma, D] and b [S mb, D] are float32 device tensors holding S = `segments` consecutive groups of ma and of mb rows
+    (ma, mb >= 2); gamma None means 1 / D.  Returns a float64 [S, 3] device tensor: sum_{i != j} k(a_i, a_j),
+    sum_{i != j} k(b_i, b_j), sum_{i, j} k(a_i, b_j) over the rows of each segment.  fp32 up to k, double sums in a fixed order:
+    the same bits from run to run.  DESIGN.md section 3.20."""
+    what = "poly_mmd_sums"
+    if not isinstance(segments, int) or isinstance(segments, bool) or segments < 1:
+        raise ValueError(f"{what}: segments must be a positive integer, got {segments!r}")
+    for name, t in (("a", a), ("b", b)):
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise ValueError(f"{what}: {name} must be a float32 tensor, got {getattr(t, 'dtype', type(t))}")
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1] or a.shape[1] < 1:
+        raise ValueError(f"{what}: a and b must be [S ma, D] and [S mb, D] with one D, got {tuple(a.shape)} and {tuple(b.shape)}")
+    for name, t in (("a", a), ("b", b)):
+        if t.shape[0] % segments or t.shape[0] // segments < 2:
+            raise ValueError(f"{what}: {name} must hold {segments} segments of at least 2 rows each, got {t.shape[0]} rows")
+        if t.shape[0] > POLY_MMD_MAX_ROWS:
+            raise ValueError(f"{what}: {name} has {t.shape[0]} rows, more than {POLY_MMD_MAX_ROWS}")
+    d = a.shape[1]
+    gamma = 1.0 / d if gamma is None else gamma
+    for name, v in (("gamma", gamma), ("coef0", coef0)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError(f"{what}: {name} must be a finite number, got {v!r}")
+    a, b = _manifold_features(what, "a", a), _manifold_features(what, "b", b)
+    ma, mb = a.shape[0] // segments, b.shape[0] // segments
+    lib = L.load()
+    sums = torch.empty((segments, 3), device=a.device, dtype=torch.float64)
+    nbytes = lib.ddk_poly_mmd_workspace_bytes(segments, ma, mb)
+    ws = _ws(a.device, nbytes, "poly_mmd")
+    L.check(lib.ddk_poly_mmd_sums(L.ptr(a), L.ptr(b), segments, ma, mb, a.shape[1], float(gamma), float(coef0), L.ptr(sums), L.ptr(ws), nbytes,
+                                  L.stream()), "poly_mmd_sums")
+    return sums
 
 
 # ================================================================== training path (backward kernels)

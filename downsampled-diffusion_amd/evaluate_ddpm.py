@@ -12,7 +12,10 @@ printed as null.  Extensions:
   * ``--synthetic CONFIG`` builds deterministic synthetic weights when no checkpoint exists (offline boxes);
   * ``--sample_acts S.npz --ref_acts R.npz`` (both or neither): Inception activations of the samples and of the reference set,
     computed elsewhere; the five sample-metric keys are then filled from them (utils/sample_metrics.py), null only where a file
-    lacks the input a metric needs.
+    lacks the input a metric needs;
+  * ``--kid`` (with ``--kid_subsets``, ``--kid_subset_size``) and ``--density_coverage``, with the activation files: the keys
+    ``kid_mean`` / ``kid_std`` / ``kid_full`` and ``density`` / ``coverage`` follow the seven above (utils/sample_metrics.py
+    extended_sample_metrics).  Without these flags the output is what it was.
 """
 import argparse
 import json
@@ -24,7 +27,7 @@ import torch
 from models import DDPM, DownsampleDDPM, Unet
 from utils import (CHECKPOINT_DIR, DATA_DIR, compute_test_losses, get_color_channels, get_dataloader, get_model_state_dict,
                    load_checkpoint_file)
-from utils.sample_metrics import sample_metrics
+from utils.sample_metrics import extended_sample_metrics, sample_metrics
 from utils import synthetic as syn
 
 SAMPLE_METRICS = ('is', 'fid', 'sfid', 'precision', 'recall')
@@ -41,9 +44,17 @@ def main():
     ap.add_argument("--json", default=None, help="also write the metrics to this file")
     ap.add_argument("--sample_acts", default=None, help=".npz of the samples' Inception activations (pool_3, spatial, softmax)")
     ap.add_argument("--ref_acts", default=None, help=".npz of the reference set's activations, or its mu / sigma / mu_s / sigma_s")
+    ap.add_argument("--kid", action="store_true", help="also report KID (kid_mean, kid_std over subsets; kid_full over all rows)")
+    ap.add_argument("--kid_subsets", type=int, default=100, help="number of KID subsets")
+    ap.add_argument("--kid_subset_size", type=int, default=1000, help="rows per KID subset (clamped to the smaller set)")
+    ap.add_argument("--density_coverage", action="store_true", help="also report density and coverage (Naeem et al. 2020, k = 5)")
     args = ap.parse_args()
     if (args.sample_acts is None) != (args.ref_acts is None):
         ap.error("--sample_acts and --ref_acts go together")
+    if (args.kid or args.density_coverage) and args.sample_acts is None:
+        ap.error("--kid and --density_coverage need --sample_acts and --ref_acts")
+    if args.kid_subsets < 1 or args.kid_subset_size < 2:
+        ap.error("--kid_subsets must be at least 1 and --kid_subset_size at least 2")
 
     device = 'cuda'
     step = 0
@@ -97,9 +108,13 @@ def main():
     else:
         print(f'Sample metrics from the activations {args.sample_acts} against {args.ref_acts}')
         time_start = time.time()
-        scores = sample_metrics(args.ref_acts, args.sample_acts)
+        if args.kid or args.density_coverage:
+            scores = extended_sample_metrics(args.ref_acts, args.sample_acts, kid=args.kid, density_coverage=args.density_coverage,
+                                             kid_subsets=args.kid_subsets, kid_subset_size=args.kid_subset_size)
+        else:
+            scores = sample_metrics(args.ref_acts, args.sample_acts)
         print(f'Sample metrics time: {time.time() - time_start}')
-        for k in SAMPLE_METRICS:
+        for k in scores:                                    # the five SAMPLE_METRICS first, then the requested extensions
             metrics[k] = scores[k]
 
     # Display resulting metrics

@@ -524,6 +524,21 @@ int ddk_knn_radii(const float* x, int N, int D, int k, float* radii, void* works
 size_t ddk_manifold_members_workspace_bytes(int Na, int Nb);
 int ddk_manifold_members(const float* a, const float* ra, int Na, const float* b, const float* rb, int Nb, int D, uint8_t* a_in,
                          uint8_t* b_in, void* workspace, size_t workspace_bytes, ddk_stream_t s);
+/* Density / coverage (Naeem et al. 2020) on the same distances: counts[i] = #{ j : d(a_i, b_j) <= ra[i] }, int32 [Na], exact.
+ * counts is zeroed by the entry: it does not depend on what it held.  workspace as for the members entry. */
+size_t ddk_manifold_ball_counts_workspace_bytes(int Na, int Nb);
+int ddk_manifold_ball_counts(const float* a, const float* ra, int Na, const float* b, int Nb, int D, int* counts, void* workspace,
+                             size_t workspace_bytes, ddk_stream_t s);
+/* The three kernel-matrix sums of the unbiased MMD^2 with k(x, y) = (gamma x.y + coef0)^3 (KID, Binkowski et al. 2018; DESIGN.md
+ * section 3.20), per segment: a is [S ma][D] and b is [S mb][D] fp32 (rows contiguous and 16-byte aligned, D % 4 == 0), segment g
+ * is rows g ma .. of a and rows g mb .. of b, ma >= 2, mb >= 2, S ma and S mb <= 2^24.  sums[g][0] = sum_{i != j} k(a_i, a_j),
+ * sums[g][1] = sum_{i != j} k(b_i, b_j), sums[g][2] = sum_{i, j} k(a_i, b_j), all pairs within segment g, as double (8-byte aligned).
+ * Arithmetic: the dot product is the fp32 fmaf chain of the distance kernels, t = fmaf(gamma, dot, coef0) and k = (t t) t in fp32
+ * (two roundings), every sum from there on in double in an order that depends on the shape only.  The diagonal is excluded by
+ * index.  No floating-point atomics: the same bits from run to run.  workspace: one double per 128 x 128 tile, 16-byte aligned. */
+size_t ddk_poly_mmd_workspace_bytes(int S, int ma, int mb);
+int ddk_poly_mmd_sums(const float* a, const float* b, int S, int ma, int mb, int D, float gamma, float coef0, double* sums, void* workspace,
+                      size_t workspace_bytes, ddk_stream_t s);
 
 /* ------------------------------------------------------------------ whole-UNet plan (unet.py:74-104, eval mode) */
 typedef struct ddk_unet_config {
