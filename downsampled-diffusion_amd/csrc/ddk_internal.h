@@ -424,10 +424,14 @@ enum class StepKind {
                   // fft_conv.hip's kernels, never the fused tail: c_recip .. sigma, fnz, rst.y = the spectrum of A+ y ([B][C][H W]
                   // complex, the transform's order), rst.H, rst.W; Philox only (last, for the same reason)
 };
-inline bool restore_kind(StepKind k) {       // the kinds whose step carries a DDNM constraint (RestoreOps)
+// the restore kinds whose operator couples a whole plane: no n x n block, never the fused tail.  The one list of them (RestoreTraits,
+// restore_rule_fault, final_tail_ok and the chain's staging in unet_plan.hip read it)
+constexpr bool plane_kind(StepKind k) {
+    return k == StepKind::RestoreBlur || k == StepKind::RestoreHadamard || k == StepKind::RestoreFFT || k == StepKind::RestoreFFTNoisy;
+}
+constexpr bool restore_kind(StepKind k) {    // the kinds whose step carries a DDNM constraint (RestoreOps)
     return k == StepKind::Restore || k == StepKind::RestoreMasked || k == StepKind::RestoreMultistep || k == StepKind::RestoreNoisy ||
-           k == StepKind::RestoreGray || k == StepKind::RestoreBlur || k == StepKind::RestoreHadamard || k == StepKind::RestoreFFT ||
-           k == StepKind::RestoreFFTNoisy;
+           k == StepKind::RestoreGray || plane_kind(k);
 }
 struct StepRule {
     StepKind kind;
@@ -452,6 +456,7 @@ struct StepRule {
     const VlbStep* vlb;           // host side only
     RestoreOps rst;
 };
+static_assert(sizeof(StepRule) == 192, "StepRule is a kernel argument: its layout stays byte for byte (see the union's comment)");
 inline StepRule vlb_rule(const VlbStep& v) {
     StepRule r{};
     r.kind = StepKind::Vlb;

@@ -727,52 +727,52 @@ __global__ __launch_bounds__(1024) void final_tail_kernel(const TailParams p) {
     }
 }
 
+// What restore_rule_fault asks of one plane-wide kind beyond the part they share: its operands besides rst.y (all required), its
+// scratch (required when one_launch declines the shape), its shape rule and the two texts
+struct PlaneRule {
+    const void* ops[4];
+    int n_ops;
+    const void* tmp;
+    bool (*shape_ok)(int H, int W, int channels);
+    bool (*one_launch)(int H, int W, int channels);
+    const char *shape_text, *scratch_text;
+};
+static PlaneRule plane_rule(const StepRule& r) {
+    const auto cs_form = [](int H, int W, int) { return restore_cs_plane_form(H, W); };
+    const auto fft_form = [](int H, int W, int) { return restore_fft_plane_form(H, W); };
+    const char* fft_text = "the deconvolution step needs H and W powers of two in [16, 256] and 1 to 8 channels";
+    switch (r.kind) {
+        case StepKind::RestoreBlur:       // rst.y is Yp in x's layout, the projections and the scratch in blr
+            return {{r.blr.ph, r.blr.pw}, 2, r.blr.tmp, restore_blur_shape_ok, restore_blur_one_launch,
+                    "the blur step needs H and W multiples of 16 in [16, 256] and 1 to 8 channels", "an image above 64 KB needs the scratch for T"};
+        case StepKind::RestoreHadamard:   // rst.y is [B][C][m], the permutation, the scratch and m in had
+            return {{r.had.perm}, 1, r.had.tmp, restore_cs_shape_ok, cs_form,
+                    "the compressed-sensing step needs H and W powers of two in [16, 256] and 1 to 8 channels", "a 256 x 256 plane needs the scratch for T"};
+        case StepKind::RestoreFFT:        // rst.y is Yp in x's layout, the mask, the twiddles and the scratch in fft
+            return {{r.fft.mask, r.fft.tw}, 2, r.fft.tmp, restore_fft_shape_ok, fft_form, fft_text, "a plane above 16384 pixels needs the scratch for T"};
+        default:                          // RestoreFFTNoisy: rst.y is the spectrum of A+ y, the mask, the twiddles, the scratch, gain and nsc in fnz
+            return {{r.fnz.mask, r.fnz.tw, r.fnz.gain, r.fnz.nsc}, 4, r.fnz.tmp, restore_fft_shape_ok, fft_form, fft_text,
+                    "a plane above 16384 pixels needs the scratch for T and T2"};
+    }
+}
+
 // What both tails ask of a restore kind's rule beyond x, t and the four common tables, `per` being the elements of one image: null
 // when the rule is sound, else what is wrong with it.  By kind (RestoreTraits): Restore has no n = 1; RestoreMasked needs its mask, the
 // other pointwise kinds need one at n = 1 only (nothing would be constrained), where y is read as float4s.
 static const char* restore_rule_fault(const StepRule& r, long long per) {
     const RestoreOps& o = r.rst;
-    if (r.kind == StepKind::RestoreBlur) {       // plane-wide: no block; rst.y is Yp in x's layout, the projections and the scratch in blr
-        if (!(o.y && r.sigma && r.blr.ph && r.blr.pw)) return "null pointer";
+    if (plane_kind(r.kind)) {      // no block: rst.H x rst.W planes, rst.y and the kind's own operands
+        const PlaneRule k = plane_rule(r);
+        bool there = o.y && r.sigma, aligned = aligned16(o.y) && aligned16(k.tmp);
+        for (int i = 0; i < k.n_ops; ++i) { there = there && k.ops[i]; aligned = aligned && aligned16(k.ops[i]); }
+        if (!there) return "null pointer";
         if (r.noise) return "no injected noise (Philox only)";
         if (!(o.H > 0 && o.W > 0) || per % ((long long)o.H * o.W)) return "per must be H * W * channels";
         const long long ch = per / ((long long)o.H * o.W);
-        if (ch > 8 || !restore_blur_shape_ok(o.H, o.W, (int)ch)) return "the blur step needs H and W multiples of 16 in [16, 256] and 1 to 8 channels";
-        if (!restore_blur_one_launch(o.H, o.W, (int)ch) && !r.blr.tmp) return "an image above 64 KB needs the scratch for T";
-        if (!(aligned16(o.y) && aligned16(r.blr.ph) && aligned16(r.blr.pw) && aligned16(r.blr.tmp))) return "alignment";
-        return nullptr;
-    }
-    if (r.kind == StepKind::RestoreHadamard) {   // plane-wide: rst.y is [B][C][m], the permutation, the scratch and m in had
-        if (!(o.y && r.sigma && r.had.perm)) return "null pointer";
-        if (r.noise) return "no injected noise (Philox only)";
-        if (!(o.H > 0 && o.W > 0) || per % ((long long)o.H * o.W)) return "per must be H * W * channels";
-        const long long ch = per / ((long long)o.H * o.W);
-        if (ch > 8 || !restore_cs_shape_ok(o.H, o.W, (int)ch)) return "the compressed-sensing step needs H and W powers of two in [16, 256] and 1 to 8 channels";
-        if (!restore_cs_rows_ok(o.H, o.W, r.had.m)) return "m must be a multiple of 4 in [4, H W]";
-        if (!restore_cs_plane_form(o.H, o.W) && !r.had.tmp) return "a 256 x 256 plane needs the scratch for T";
-        if (!(aligned16(o.y) && aligned16(r.had.perm) && aligned16(r.had.tmp))) return "alignment";
-        return nullptr;
-    }
-    if (r.kind == StepKind::RestoreFFT) {        // plane-wide: rst.y is Yp in x's layout, the mask, the twiddles and the scratch in fft
-        if (!(o.y && r.sigma && r.fft.mask && r.fft.tw)) return "null pointer";
-        if (r.noise) return "no injected noise (Philox only)";
-        if (!(o.H > 0 && o.W > 0) || per % ((long long)o.H * o.W)) return "per must be H * W * channels";
-        const long long ch = per / ((long long)o.H * o.W);
-        if (ch > 8 || !restore_fft_shape_ok(o.H, o.W, (int)ch)) return "the deconvolution step needs H and W powers of two in [16, 256] and 1 to 8 channels";
-        if (!restore_fft_plane_form(o.H, o.W) && !r.fft.tmp) return "a plane above 16384 pixels needs the scratch for T";
-        if (!(aligned16(o.y) && aligned16(r.fft.mask) && aligned16(r.fft.tw) && aligned16(r.fft.tmp))) return "alignment";
-        return nullptr;
-    }
-    if (r.kind == StepKind::RestoreFFTNoisy) {   // plane-wide: rst.y is the spectrum of A+ y, the mask, the twiddles, the scratch, gain and nsc in fnz
-        if (!(o.y && r.sigma && r.fnz.mask && r.fnz.tw && r.fnz.gain && r.fnz.nsc)) return "null pointer";
-        if (r.noise) return "no injected noise (Philox only)";
-        if (!(o.H > 0 && o.W > 0) || per % ((long long)o.H * o.W)) return "per must be H * W * channels";
-        const long long ch = per / ((long long)o.H * o.W);
-        if (ch > 8 || !restore_fft_shape_ok(o.H, o.W, (int)ch)) return "the deconvolution step needs H and W powers of two in [16, 256] and 1 to 8 channels";
-        if (!restore_fft_plane_form(o.H, o.W) && !r.fnz.tmp) return "a plane above 16384 pixels needs the scratch for T and T2";
-        if (!(aligned16(o.y) && aligned16(r.fnz.mask) && aligned16(r.fnz.tw) && aligned16(r.fnz.tmp) && aligned16(r.fnz.gain) && aligned16(r.fnz.nsc)))
-            return "alignment";
-        return nullptr;
+        if (ch > 8 || !k.shape_ok(o.H, o.W, (int)ch)) return k.shape_text;
+        if (r.kind == StepKind::RestoreHadamard && !restore_cs_rows_ok(o.H, o.W, r.had.m)) return "m must be a multiple of 4 in [4, H W]";
+        if (!k.one_launch(o.H, o.W, (int)ch) && !k.tmp) return k.scratch_text;
+        return aligned ? nullptr : "alignment";
     }
     const bool hist = r.kind == StepKind::RestoreMultistep, gray = r.kind == StepKind::RestoreGray,
                noisy = gray || r.kind == StepKind::RestoreNoisy, n1 = r.kind != StepKind::Restore;
@@ -809,9 +809,7 @@ bool final_tail_ok(int HW, int C, int groups, int n_out, int np, StepKind kind, 
     if (C > 128 && kind != StepKind::Eps && kind != StepKind::Ancestral) return false;
     if (groups <= 0 || groups > 64 || C % groups || (C / groups) % 4) return false;
     if (n_out < 1 || n_out > 8 || (128 * n_out) % 4) return false;
-    if (kind == StepKind::RestoreBlur) return false;                     // plane-wide: a 128-pixel tile cannot form P_h x0 P_w^T
-    if (kind == StepKind::RestoreHadamard) return false;                 // plane-wide: nor a plane's Walsh-Hadamard transform
-    if (kind == StepKind::RestoreFFT || kind == StepKind::RestoreFFTNoisy) return false;      // plane-wide: nor a plane's Fourier transform
+    if (plane_kind(kind)) return false;      // a 128-pixel tile cannot form P_h x0 P_w^T, nor a plane's Walsh-Hadamard or Fourier transform
     if (kind == StepKind::RestoreGray && n_out != 3) return false;       // the grey operator is over a pixel's three colours
     // the restore tail forms block means from the tile's x0 in LDS: the 128-pixel tile must hold whole rows of n x n blocks
     // (the masked kind the same for n >= 2; its n = 1 is pointwise)
@@ -1137,17 +1135,19 @@ int p_update(const StepRule& r, const float* eps_hat, const int64_t* t, int B, l
         case StepKind::RestoreGray:
             return launch_restore<StepKind::RestoreGray>(r, eps_hat, t, B, per, h, st);
         case StepKind::RestoreBlur:       // separable.hip: one launch, or two through blr.tmp
-            if (B > 65535) return bad("at most 65535 images");
-            return p_update_restore_blur(r, eps_hat, t, B, (int)(per / ((long long)r.rst.H * r.rst.W)), h, st);
         case StepKind::RestoreHadamard:   // hadamard.hip: one launch, or three through had.tmp
-            if (B * (per / ((long long)r.rst.H * r.rst.W)) > 65535) return bad("at most 65535 planes");
-            return p_update_restore_cs(r, eps_hat, t, B, (int)(per / ((long long)r.rst.H * r.rst.W)), h, st);
         case StepKind::RestoreFFT:        // fft_conv.hip: one launch, or three through fft.tmp
-            if (B * (per / ((long long)r.rst.H * r.rst.W)) > 65535) return bad("at most 65535 planes");
-            return p_update_restore_fft(r, eps_hat, t, B, (int)(per / ((long long)r.rst.H * r.rst.W)), h, st);
-        case StepKind::RestoreFFTNoisy:   // fft_conv.hip: one launch, or three through fnz.tmp
-            if (B * (per / ((long long)r.rst.H * r.rst.W)) > 65535) return bad("at most 65535 planes");
-            return p_update_restore_fft_noisy(r, eps_hat, t, B, (int)(per / ((long long)r.rst.H * r.rst.W)), h, st);
+        case StepKind::RestoreFFTNoisy: { // fft_conv.hip: one launch, or three through fnz.tmp
+            const long long channels = per / ((long long)r.rst.H * r.rst.W);
+            if (r.kind == StepKind::RestoreBlur) {
+                if (B > 65535) return bad("at most 65535 images");
+                return p_update_restore_blur(r, eps_hat, t, B, (int)channels, h, st);
+            }
+            if (B * channels > 65535) return bad("at most 65535 planes");
+            return r.kind == StepKind::RestoreHadamard ? p_update_restore_cs(r, eps_hat, t, B, (int)channels, h, st)
+                   : r.kind == StepKind::RestoreFFT    ? p_update_restore_fft(r, eps_hat, t, B, (int)channels, h, st)
+                                                       : p_update_restore_fft_noisy(r, eps_hat, t, B, (int)channels, h, st);
+        }
         case StepKind::Vlb:       // no update: the sweep's reduction of the step's terms, a kernel of its own
             if (!r.vlb) return bad("null pointer");
             return vlb_sweep_terms(*r.vlb, t, eps_hat, B, per, h.chain_state, st, h.dec_counter);

@@ -37,11 +37,8 @@ __device__ __forceinline__ float4 philox_normal4(unsigned long long idx4, uint32
 
 template <StepKind K>
 struct RestoreTraits {
-    static constexpr bool RESTORE = K == StepKind::Restore || K == StepKind::RestoreMasked || K == StepKind::RestoreMultistep ||
-                                    K == StepKind::RestoreNoisy || K == StepKind::RestoreGray || K == StepKind::RestoreBlur ||
-                                    K == StepKind::RestoreHadamard || K == StepKind::RestoreFFT || K == StepKind::RestoreFFTNoisy;
-    static constexpr bool PLANE = K == StepKind::RestoreBlur || K == StepKind::RestoreHadamard || K == StepKind::RestoreFFT ||
-                                  K == StepKind::RestoreFFTNoisy;      // the operator couples a whole plane: no n x n block, never the fused tail
+    static constexpr bool RESTORE = restore_kind(K);
+    static constexpr bool PLANE = plane_kind(K);
     static constexpr bool MASK = RESTORE && K != StepKind::Restore && !PLANE;
     static constexpr bool MASK_REQUIRED = K == StepKind::RestoreMasked;
     static constexpr bool HIST = K == StepKind::RestoreMultistep;

@@ -10,6 +10,7 @@
 // (t bookkeeping + UNet + x update) into a hipGraph and replays it, so the T-step loop costs one
 // hipGraphLaunch per step on the host.
 #include <algorithm>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -89,7 +90,7 @@ struct ChainKey {
     const void* noise;                       // also in bufs; injected draws: no 16-step graph (see run_chain)
     int B, H, W, t_start, device;
     unsigned long long pack_epoch;
-    int restore_n = 0;                       // StepKind::RestoreFFT: 0, the kind says it (mask, twiddles and Yp are staged).  StepKind::RestoreHadamard: m, the measured coefficients per plane (the kernels are launched with it).
+    int restore_n = 0;                       // the plane-wide kinds: Stage's key_n (every operand is staged in the workspace).
                                              // StepKind::Restore, RestoreMasked: the block (y and the mask are staged in the workspace; the kind
                                              // says whether a mask is present, so a masked and an unmasked chain never share a graph)
     bool restore_mask = false;               // StepKind::RestoreMultistep, RestoreNoisy, one kind with or without a mask: whether its kernels were given one
@@ -1754,49 +1755,45 @@ static RestoreStage restore_stage(size_t n, int B, int H, int W, StepKind kind, 
     const size_t nn = (size_t)restore_n * restore_n;
     return {kind == StepKind::RestoreMultistep ? al4(n) : 0, al4(n / nn), al4((size_t)B * H * W / nn)};
 }
-// RestoreBlur (plane-wide, no block): P_h [H][H], P_w [W][W], Yp and T, the last two of the latent's size; each part is a multiple of
-// four floats, so each starts on a 16-byte boundary.  Q_h and Q_w are only read while Yp is formed, from the caller's buffers.
-struct BlurStage {
-    size_t ph, pw, yp, tmp;       // offsets in floats from the chain's extra area; total = tmp + al4(n)
+// The plane-wide kinds (no block) lay their staging area out with a bump: every part is a multiple of four floats, so each starts on a
+// 16-byte boundary.  A layout holds its parts' offsets in floats from the chain's extra area, then the total; n is the latent's floats.
+struct Bump {
+    size_t at = 0;
+    size_t take(size_t floats) { const size_t off = at; at += al4(floats); return off; }
 };
+// RestoreBlur: P_h [H][H], P_w [W][W], Yp and T, the last two of the latent's size.  Q_h and Q_w are only read while Yp is formed, from
+// the caller's buffers.
+struct BlurStage { size_t ph, pw, yp, tmp, total; };
 static BlurStage blur_stage(size_t n, int H, int W) {
-    const size_t ph = 0, pw = ph + al4((size_t)H * H), yp = pw + al4((size_t)W * W);
-    return {ph, pw, yp, yp + al4(n)};
+    Bump b;
+    return {b.take((size_t)H * H), b.take((size_t)W * W), b.take(n), b.take(n), b.at};      // (a braced list: left to right)
 }
-// RestoreHadamard (plane-wide): perm [H W] int32, y [B][C][m] in a place of the latent's size (m <= H W) and T of the latent's size
-struct CsStage {
-    size_t perm, y, tmp;          // offsets in floats from the chain's extra area; total = tmp + al4(n)
-};
+// RestoreHadamard: perm [H W] int32, y [B][C][m] in a place of the latent's size (m <= H W) and T of the latent's size
+struct CsStage { size_t perm, y, tmp, total; };
 static CsStage cs_stage(size_t n, int H, int W) {
-    const size_t y = al4((size_t)H * W);
-    return {0, y, y + al4(n)};
+    Bump b;
+    return {b.take((size_t)H * W), b.take(n), b.take(n), b.at};
 }
-// RestoreFFT (plane-wide): the mask [H W], the twiddles (max(H, W) / 2 complex), Yp of the latent's size and the complex T of twice it
-struct FftStage {
-    size_t mask, tw, yp, tmp;     // offsets in floats from the chain's extra area; total = tmp + 2 al4(n)
-};
+// RestoreFFT: the mask [H W], the twiddles (max(H, W) / 2 complex), Yp of the latent's size and the complex T of twice it
+struct FftStage { size_t mask, tw, yp, tmp, total; };
 static FftStage fft_stage(size_t n, int H, int W) {
-    const size_t tw = al4((size_t)H * W), yp = tw + al4((size_t)(H > W ? H : W));
-    return {0, tw, yp, yp + al4(n)};
+    Bump b;
+    return {b.take((size_t)H * W), b.take((size_t)(H > W ? H : W)), b.take(n), b.take(2 * al4(n)), b.at};
 }
-// RestoreFFTNoisy (plane-wide): RestoreFFT's area (the place of the image Yp stays unused), behind its T the draw's T2 of the same size
-// when a plane takes the multi-launch form, then gain [H W], nsc (one float per row of the chain) and the complex spectrum of A+ y
-struct FftNoisyStage {
-    FftStage f;
-    size_t gain, nsc, yhat, total;
-};
+// RestoreFFTNoisy: RestoreFFT's area (the place of the image Yp stays unused), behind its T the draw's T2 of the same size when a plane
+// takes the multi-launch form, then gain [H W], nsc (one float per row of the chain) and the complex spectrum of A+ y
+struct FftNoisyStage { FftStage f; size_t gain, nsc, yhat, total; };
 static FftNoisyStage fft_noisy_stage(size_t n, int H, int W, int t_start) {
     const FftStage f = fft_stage(n, H, W);
-    const size_t gain = f.tmp + 2 * al4(n) + (restore_fft_plane_form(H, W) ? 0 : 2 * al4(n)), nsc = gain + al4((size_t)H * W),
-                 yhat = nsc + al4((size_t)t_start + 1);
-    return {f, gain, nsc, yhat, yhat + 2 * al4(n)};
+    Bump b{f.total + (restore_fft_plane_form(H, W) ? 0 : 2 * al4(n))};
+    return {f, b.take((size_t)H * W), b.take((size_t)t_start + 1), b.take(2 * al4(n)), b.at};
 }
 static size_t chain_extra_floats(const ddk_unet& u, int B, int H, int W, StepKind kind, int restore_n = 0, int t_start = 0) {
     const size_t n = al4((size_t)B * H * W * u.cfg.in_ch);
     if (kind == StepKind::RestoreFFTNoisy) return fft_noisy_stage(n, H, W, t_start).total;
-    if (kind == StepKind::RestoreFFT) return fft_stage(n, H, W).tmp + 2 * al4(n);
-    if (kind == StepKind::RestoreHadamard) return cs_stage(n, H, W).tmp + al4(n);
-    if (kind == StepKind::RestoreBlur) return blur_stage(n, H, W).tmp + al4(n);
+    if (kind == StepKind::RestoreFFT) return fft_stage(n, H, W).total;
+    if (kind == StepKind::RestoreHadamard) return cs_stage(n, H, W).total;
+    if (kind == StepKind::RestoreBlur) return blur_stage(n, H, W).total;
     if (kind == StepKind::Restore) return al4(n / 4);
     if (restore_kind(kind)) {
         const RestoreStage g = restore_stage(n, B, H, W, kind, restore_n);
@@ -1810,17 +1807,82 @@ static size_t sampler_bytes(const ddk_unet* u, int B, int H, int W, int t_start,
     return (sampler_layout(*u, B, H, W, t_start).total + chain_extra_floats(*u, B, H, W, kind, restore_n, t_start)) * sizeof(float);
 }
 
+// A plane-wide kind's operands, staged before the first step and outside any captured one.  On entry rule.rst.y is the CALLER's y and
+// the kind's member of rule (blr, had, fft, fnz) holds the caller's arrays; each function copies them into the chain's extra area, forms
+// Yp or the spectrum there and rewrites rule to point into the workspace.
+struct Stage {                    // the chain's stream, extra area, latent floats, shape, channels and first row; then what the graph key needs of
+    hipStream_t st;               // the staged operands besides the workspace:
+    float* extra;
+    size_t n;
+    int B, H, W, C, t_start;
+    int key_n = 0;                // RestoreHadamard: m, the measured coefficients per plane (the kernels are launched with it); else 0, the kind says it
+    NoisyTables key_tables{};     // RestoreFFTNoisy: the caller's gain and nsc, which name the point-spread function and sigma_y; else null
+    int copy(size_t off, const void* from, size_t bytes) const {
+        DDK_HIP(hipMemcpyAsync(extra + off, from, bytes, hipMemcpyDeviceToDevice, st));
+        return DDK_OK;
+    }
+};
+static int stage_blur(Stage& g, StepRule& rule, ddk_stream_t s) {
+    const BlurStage l = blur_stage(g.n, g.H, g.W);
+    DDK_TRY(g.copy(l.ph, rule.blr.ph, (size_t)g.H * g.H * sizeof(float)));
+    DDK_TRY(g.copy(l.pw, rule.blr.pw, (size_t)g.W * g.W * sizeof(float)));
+    // Yp = Q_h y Q_w^T.  rule.rst.H x rule.rst.W is the size of that y (the entry's h, w): the plane's own takes the square form, in
+    // place on Yp; a smaller one the size-changing form with T as its scratch, [B][H][w][C] never exceeding it
+    if (rule.rst.H == g.H && rule.rst.W == g.W)
+        DDK_TRY(ddk_separable_apply(rule.rst.y, rule.blr.qh, rule.blr.qw, g.extra + l.yp, g.B, g.H, g.W, g.C, s));
+    else
+        DDK_TRY(ddk_separable_apply_rect(rule.rst.y, rule.blr.qh, rule.blr.qw, g.extra + l.yp, g.extra + l.tmp, g.B, rule.rst.H, rule.rst.W, g.H,
+                                         g.W, g.C, s));
+    rule.blr = BlurOps{g.extra + l.ph, g.extra + l.pw, g.extra + l.tmp, nullptr, nullptr};
+    rule.rst = RestoreOps{g.extra + l.yp, 0, g.H, g.W, 0, nullptr};
+    return DDK_OK;
+}
+static int stage_cs(Stage& g, StepRule& rule) {
+    const CsStage l = cs_stage(g.n, g.H, g.W);
+    DDK_TRY(g.copy(l.perm, rule.had.perm, (size_t)g.H * g.W * sizeof(int32_t)));
+    DDK_TRY(g.copy(l.y, rule.rst.y, (size_t)g.B * g.C * rule.had.m * sizeof(float)));
+    g.key_n = rule.had.m;
+    rule.had = HadamardOps{reinterpret_cast<const int32_t*>(g.extra + l.perm), g.extra + l.tmp, rule.had.m};
+    rule.rst = RestoreOps{g.extra + l.y, 0, g.H, g.W, 0, nullptr};
+    return DDK_OK;
+}
+static int stage_fft(Stage& g, StepRule& rule) {
+    const FftStage l = fft_stage(g.n, g.H, g.W);
+    DDK_TRY(g.copy(l.mask, rule.fft.mask, (size_t)g.H * g.W * sizeof(float)));
+    DDK_TRY(g.copy(l.tw, rule.fft.tw, (size_t)(g.H > g.W ? g.H : g.W) * sizeof(float)));
+    // Yp = Re F2^-1(P^ F2 y) / N
+    DDK_TRY(circular_conv(rule.rst.y, rule.fft.pinv, g.extra + l.tw, g.extra + l.yp, g.extra + l.tmp, g.B, g.H, g.W, g.C, g.st));
+    rule.fft = FftOps{g.extra + l.mask, g.extra + l.tw, g.extra + l.tmp, nullptr};
+    rule.rst = RestoreOps{g.extra + l.yp, 0, g.H, g.W, 0, nullptr};
+    return DDK_OK;
+}
+// as stage_fft, with gain and nsc copied in as well and the SPECTRUM of A+ y, P^ . F2 y in the transform's order, in rst.y
+static int stage_fft_noisy(Stage& g, StepRule& rule) {
+    const FftNoisyStage l = fft_noisy_stage(g.n, g.H, g.W, g.t_start);
+    DDK_TRY(g.copy(l.f.mask, rule.fnz.mask, (size_t)g.H * g.W * sizeof(float)));
+    DDK_TRY(g.copy(l.f.tw, rule.fnz.tw, (size_t)(g.H > g.W ? g.H : g.W) * sizeof(float)));
+    DDK_TRY(g.copy(l.gain, rule.fnz.gain, (size_t)g.H * g.W * sizeof(float)));
+    DDK_TRY(g.copy(l.nsc, rule.fnz.nsc, ((size_t)g.t_start + 1) * sizeof(float)));
+    DDK_TRY(circular_spectrum(rule.rst.y, rule.fnz.pinv, g.extra + l.f.tw, g.extra + l.yhat, g.extra + l.f.tmp, g.B, g.H, g.W, g.C, g.st));
+    g.key_tables = NoisyTables{rule.fnz.gain, rule.fnz.nsc};
+    rule.fnz = FftNoisyOps{g.extra + l.f.mask, g.extra + l.f.tw, g.extra + l.f.tmp, g.extra + l.gain, g.extra + l.nsc, nullptr};
+    rule.rst = RestoreOps{g.extra + l.yhat, 0, g.H, g.W, 0, nullptr};
+    return DDK_OK;
+}
+static int stage_plane(Stage& g, StepRule& rule, ddk_stream_t s) {
+    return rule.kind == StepKind::RestoreBlur ? stage_blur(g, rule, s) : rule.kind == StepKind::RestoreHadamard ? stage_cs(g, rule)
+           : rule.kind == StepKind::RestoreFFT ? stage_fft(g, rule) : stage_fft_noisy(g, rule);
+}
+
 // What the sampler entries share once their own arguments are checked: n_steps reverse steps on a->x, step k at timestep map[k],
 // each ending in `rule`.  The entry sets rule.kind and the operands only its kind has (c3; inp, with the CALLER's known / mask; rst, with the CALLER's y);
 // x, the noise and the tables c_recip .. sigma come from *a here.  What a kind keeps in the workspace is staged after begin_chain
 // and outside any captured step, so no chain sees another's and the cached graph points only into the workspace:
 //   Multistep: the history, zeroed by every call (c3[t_start] == 0 makes the first step first order whatever it would hold)
 //   Inpaint:   known and mask, copied in before the first op
-//   the restore kinds: (RestoreMultistep: the history, zeroed by every call as Multistep's, then) y and, when given, the mask,
+//   the block restore kinds: (RestoreMultistep: the history, zeroed by every call as Multistep's, then) y and, when given, the mask,
 //              copied in before the first step (restore_stage's layout)
-//   RestoreBlur: the projections copied in and Yp formed (blur_stage); RestoreHadamard: perm and y copied in (cs_stage);
-//   RestoreFFT: the mask and the twiddles copied in and Yp formed (fft_stage); RestoreFFTNoisy: mask, twiddles, gain and nsc copied
-//              in and the spectrum of A+ y formed (fft_noisy_stage)
+//   the plane-wide restore kinds: stage_plane
 // The graph key: the kind, every table the step reads and the restore block; the staged operands live in the workspace, which is
 // in the key.
 static int sampler_chain(const ddk_sampler_args* a, const char* who, const int64_t* map, StepRule rule, ddk_stream_t s) {
@@ -1832,7 +1894,8 @@ static int sampler_chain(const ddk_sampler_args* a, const char* who, const int64
     rule.c_recip = a->c_recip; rule.c_recipm1 = a->c_recipm1; rule.c1 = a->c1; rule.c2 = a->c2; rule.sigma = a->sigma;
     const size_t n = (size_t)B * c.per;
     float* extra = c.ws + c.sl.total;
-    const float* fnz_key[2] = {nullptr, nullptr};      // RestoreFFTNoisy: the caller's gain and nsc, which name the point-spread function and sigma_y in the graph key
+    const bool plane = plane_kind(rule.kind);
+    Stage pk{c.st, extra, n, B, H, W, c.u->cfg.in_ch, a->t_start};
     if (rule.kind == StepKind::Multistep) {
         DDK_HIP(hipMemsetAsync(extra, 0, n * sizeof(float), c.st));
         rule.x0_hist = extra;
@@ -1841,49 +1904,8 @@ static int sampler_chain(const ddk_sampler_args* a, const char* who, const int64
         DDK_HIP(hipMemcpyAsync(extra + al4(n), rule.inp.mask, n * sizeof(float), hipMemcpyDeviceToDevice, c.st));
         rule.inp.known = extra;
         rule.inp.mask = extra + al4(n);
-    } else if (rule.kind == StepKind::RestoreBlur) {
-        // the projections copied in and Yp = Q_h y Q_w^T formed here, before the first step and outside any captured one: rule.rst.y is
-        // the CALLER's y, rule.blr holds the caller's matrices
-        const BlurStage g = blur_stage(al4(n), H, W);
-        DDK_HIP(hipMemcpyAsync(extra + g.ph, rule.blr.ph, (size_t)H * H * sizeof(float), hipMemcpyDeviceToDevice, c.st));
-        DDK_HIP(hipMemcpyAsync(extra + g.pw, rule.blr.pw, (size_t)W * W * sizeof(float), hipMemcpyDeviceToDevice, c.st));
-        // rule.rst.H x rule.rst.W is the size of that y (the entry's h, w): the plane's own takes the square form, in place on Yp; a smaller
-        // one the size-changing form with T as its scratch, [B][H][w][C] never exceeding it
-        if (rule.rst.H == H && rule.rst.W == W)
-            DDK_TRY(ddk_separable_apply(rule.rst.y, rule.blr.qh, rule.blr.qw, extra + g.yp, B, H, W, c.u->cfg.in_ch, s));
-        else
-            DDK_TRY(ddk_separable_apply_rect(rule.rst.y, rule.blr.qh, rule.blr.qw, extra + g.yp, extra + g.tmp, B, rule.rst.H, rule.rst.W, H, W,
-                                             c.u->cfg.in_ch, s));
-        rule.blr = BlurOps{extra + g.ph, extra + g.pw, extra + g.tmp, nullptr, nullptr};
-        rule.rst = RestoreOps{extra + g.yp, 0, H, W, 0, nullptr};
-    } else if (rule.kind == StepKind::RestoreHadamard) {
-        // perm and y copied in before the first step and outside any captured one: rule.rst.y and rule.had.perm are the CALLER's
-        const CsStage g = cs_stage(al4(n), H, W);
-        DDK_HIP(hipMemcpyAsync(extra + g.perm, rule.had.perm, (size_t)H * W * sizeof(int32_t), hipMemcpyDeviceToDevice, c.st));
-        DDK_HIP(hipMemcpyAsync(extra + g.y, rule.rst.y, (size_t)B * c.u->cfg.in_ch * rule.had.m * sizeof(float), hipMemcpyDeviceToDevice, c.st));
-        rule.had = HadamardOps{reinterpret_cast<const int32_t*>(extra + g.perm), extra + g.tmp, rule.had.m};
-        rule.rst = RestoreOps{extra + g.y, 0, H, W, 0, nullptr};
-    } else if (rule.kind == StepKind::RestoreFFT) {
-        // the mask and the twiddles copied in and Yp = Re F2^-1(P^ F2 y) / N formed here, before the first step and outside any captured
-        // one: rule.rst.y is the CALLER's y, rule.fft holds the caller's arrays
-        const FftStage g = fft_stage(al4(n), H, W);
-        DDK_HIP(hipMemcpyAsync(extra + g.mask, rule.fft.mask, (size_t)H * W * sizeof(float), hipMemcpyDeviceToDevice, c.st));
-        DDK_HIP(hipMemcpyAsync(extra + g.tw, rule.fft.tw, (size_t)(H > W ? H : W) * sizeof(float), hipMemcpyDeviceToDevice, c.st));
-        DDK_TRY(circular_conv(rule.rst.y, rule.fft.pinv, extra + g.tw, extra + g.yp, extra + g.tmp, B, H, W, c.u->cfg.in_ch, c.st));
-        rule.fft = FftOps{extra + g.mask, extra + g.tw, extra + g.tmp, nullptr};
-        rule.rst = RestoreOps{extra + g.yp, 0, H, W, 0, nullptr};
-    } else if (rule.kind == StepKind::RestoreFFTNoisy) {
-        // as RestoreFFT, with gain and nsc copied in as well and the SPECTRUM of A+ y, P^ . F2 y in the transform's order, formed here:
-        // rule.rst.y is the CALLER's y, rule.fnz holds the caller's arrays
-        const FftNoisyStage g = fft_noisy_stage(al4(n), H, W, a->t_start);
-        DDK_HIP(hipMemcpyAsync(extra + g.f.mask, rule.fnz.mask, (size_t)H * W * sizeof(float), hipMemcpyDeviceToDevice, c.st));
-        DDK_HIP(hipMemcpyAsync(extra + g.f.tw, rule.fnz.tw, (size_t)(H > W ? H : W) * sizeof(float), hipMemcpyDeviceToDevice, c.st));
-        DDK_HIP(hipMemcpyAsync(extra + g.gain, rule.fnz.gain, (size_t)H * W * sizeof(float), hipMemcpyDeviceToDevice, c.st));
-        DDK_HIP(hipMemcpyAsync(extra + g.nsc, rule.fnz.nsc, ((size_t)a->t_start + 1) * sizeof(float), hipMemcpyDeviceToDevice, c.st));
-        DDK_TRY(circular_spectrum(rule.rst.y, rule.fnz.pinv, extra + g.f.tw, extra + g.yhat, extra + g.f.tmp, B, H, W, c.u->cfg.in_ch, c.st));
-        fnz_key[0] = rule.fnz.gain; fnz_key[1] = rule.fnz.nsc;
-        rule.fnz = FftNoisyOps{extra + g.f.mask, extra + g.f.tw, extra + g.f.tmp, extra + g.gain, extra + g.nsc, nullptr};
-        rule.rst = RestoreOps{extra + g.yhat, 0, H, W, 0, nullptr};
+    } else if (plane) {
+        DDK_TRY(stage_plane(pk, rule, s));
     } else if (restore_kind(rule.kind)) {
         const RestoreStage g = restore_stage(n, B, H, W, rule.kind, rule.rst.n);
         const size_t nn = (size_t)rule.rst.n * rule.rst.n, nm = (size_t)B * H * W / nn;      // one float per block: the mask, and the grey y
@@ -1906,17 +1928,16 @@ static int sampler_chain(const ddk_sampler_args* a, const char* who, const int64
     // one reverse step: bookkeeping (in the forward's first kernel), UNet, the rule (in its last kernel)
     auto one_step = [&]() -> int { return c.forward(a->x, &step); };
 
-    // the RestoreNoisy / RestoreGray tables share the Inpaint operands' storage (StepRule): each kind's key names its own
+    // the RestoreNoisy / RestoreGray tables share the Inpaint operands' storage (StepRule): each kind's key names its own; the plane-wide
+    // kinds' operands are staged, so the workspace names them (but for pk's key_n and key_tables)
     const bool noisy = rule.kind == StepKind::RestoreNoisy || rule.kind == StepKind::RestoreGray;
-    const bool plane = rule.kind == StepKind::RestoreBlur || rule.kind == StepKind::RestoreHadamard || rule.kind == StepKind::RestoreFFT ||
-                       rule.kind == StepKind::RestoreFFTNoisy;
-    const InpaintOps ik = noisy || plane ? InpaintOps{} : rule.inp;      // (the plane-wide kinds' operands are staged: the workspace names them)
-    const NoisyTables nk = noisy ? rule.nsy : NoisyTables{fnz_key[0], fnz_key[1]};      // (RestoreFFTNoisy: gain and nsc in the tables' two places)
+    const InpaintOps ik = noisy || plane ? InpaintOps{} : rule.inp;
+    const NoisyTables nk = noisy ? rule.nsy : pk.key_tables;
     const ChainKey key{rule.kind,
                        {a->packed, a->x, rule.c_recip, rule.c_recipm1, rule.c1, rule.c2, rule.sigma, rule.c3, ik.ka, ik.kb, ik.ja, ik.jb, nk.lam,
                         nk.sgm},
                        a->workspace, a->noise, B, H, W, a->t_start, c.dev, c.u->pack_epoch,
-                       rule.kind == StepKind::RestoreHadamard ? rule.had.m : restore_kind(rule.kind) ? rule.rst.n : 0,      // RestoreBlur, RestoreFFT: 0, the kind says it
+                       plane ? pk.key_n : restore_kind(rule.kind) ? rule.rst.n : 0,
                        (rule.kind == StepKind::RestoreMultistep || noisy) && rule.rst.mask != nullptr,
                        rule.kind == StepKind::RestoreGray ? rule.rst.gray : 0};
     return run_chain(*c.u, key, n_steps, a->use_graph != 0, one_step, c.st, who);
@@ -2110,40 +2131,75 @@ extern "C" int ddk_sampler_run_restore_gray(const ddk_sampler_args* a, const int
     return restore_chain(a, "sampler_restore_gray", timestep_map, StepKind::RestoreGray, true, false, nullptr, {lam, sgm}, y, mask, n, weights, s);
 }
 
-// DDNM deblurring, A(X) = A_h X A_w^T per channel of a pixel-space model (section 3.14): the spaced sampler's chain, every step ending in
-// StepKind::RestoreBlur.  P = A+ A and Q = A+ of the two axes are the caller's (models/diffusion/blur.py), row-major [H][H] and [W][W]
-// device arrays; y is the blurred image in x's layout.  The kind is plane-wide, so no step takes the fused tail: the forward writes
-// eps_hat to the step's scratch and separable.hip's update follows.
-extern "C" size_t ddk_sampler_restore_blur_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start) {
-    if (check_shape(u, B, H, W) != DDK_OK || !restore_blur_shape_ok(H, W, u->cfg.in_ch)) return 0;
-    return sampler_bytes(u, B, H, W, t_start, StepKind::RestoreBlur);
+// The plane-wide restore kinds (sections 3.14, 3.15, 3.17 - 3.19): the spaced sampler's chain on a pixel-space model, every step ending
+// in a kind whose operator couples a whole plane, so no step takes the fused tail: the forward writes eps_hat to the step's scratch and
+// the kind's own update follows (separable.hip, hadamard.hip, fft_conv.hip).  What their entries share:
+namespace ddk {
+static bool plane_shape_ok(StepKind kind, int H, int W, int channels) {
+    return kind == StepKind::RestoreBlur ? restore_blur_shape_ok(H, W, channels)
+           : kind == StepKind::RestoreHadamard ? restore_cs_shape_ok(H, W, channels) : restore_fft_shape_ok(H, W, channels);
 }
-extern "C" int ddk_sampler_restore_blur_tail_parts(const ddk_unet* u, int B, int H, int W) {
+static size_t plane_bytes(const ddk_unet* u, int B, int H, int W, int t_start, StepKind kind) {
+    if (check_shape(u, B, H, W) != DDK_OK || !plane_shape_ok(kind, H, W, u->cfg.in_ch)) return 0;
+    return sampler_bytes(u, B, H, W, t_start, kind);
+}
+static int plane_tail_parts(const ddk_unet* u, int B, int H, int W, StepKind kind) {
     if (check_shape(u, B, H, W) != DDK_OK) return -1;
-    return fused_tail_parts(*u, B, H, W, u->dimp[1], StepKind::RestoreBlur);      // 0: final_tail_ok takes no plane-wide kind
+    return fused_tail_parts(*u, B, H, W, u->dimp[1], kind);      // 0: final_tail_ok takes no plane-wide kind
 }
-// (both entries: y is [B][h][w][C], Q_h [H][h], Q_w [W][w]; the deblurring entry's h, w are the plane's)
-static int restore_blur_chain(const ddk_sampler_args* a, const char* who, const int64_t* timestep_map, const float* P_h, const float* P_w,
-                              const float* Q_h, const float* Q_w, const float* y, bool sized, int h, int w, ddk_stream_t s) {
+// A run entry: its checks, then the chain.  In this order: null pointers (`ops` are the entry's own operands, all required), null
+// schedule tables, injected noise, t_start >= t_end >= 0, the kind's shape rule, what only the entry checks (own(): null, or its
+// text; it may still write to rule), the operands' alignment, the timestep map
+template <class Own>
+static int plane_chain(const ddk_sampler_args* a, const char* who, const int64_t* map, const StepRule& rule,
+                       std::initializer_list<const void*> ops, Own&& own, ddk_stream_t s) {
     auto bad = [who](const char* what) {
         set_error("bad argument: %s: %s", who, what);
         return DDK_ERR_ARG;
     };
-    if (!(a && a->unet && a->packed && a->x && a->workspace && y && P_h && P_w && Q_h && Q_w)) return bad("null pointer");
+    bool there = a && a->unet && a->packed && a->x && a->workspace, aligned = true;
+    for (const void* p : ops) { there = there && p; aligned = aligned && aligned16(p); }
+    if (!there) return bad("null pointer");
     if (!(a->c_recip && a->c_recipm1 && a->c1 && a->c2 && a->sigma)) return bad("null schedule table");
     if (a->noise) return bad("injected noise is not supported, noise must be NULL (Philox only)");
     if (!(a->t_start >= a->t_end && a->t_end >= 0)) return bad("need t_start >= t_end >= 0");
-    if (!restore_blur_shape_ok(a->H, a->W, a->unet->cfg.in_ch)) return bad("H and W must be multiples of 16 in [16, 256], the model's channels 1 to 8");
-    if (!sized) { h = a->H; w = a->W; }
-    if (!(h >= 4 && h <= a->H && h % 4 == 0 && w >= 4 && w <= a->W && w % 4 == 0)) return bad("h and w must be multiples of 4 in [4, H] and [4, W]");
-    if (!(aligned16(P_h) && aligned16(P_w) && aligned16(Q_h) && aligned16(Q_w) && aligned16(y))) return bad("alignment");
-    DDK_TRY(check_timestep_map(timestep_map, a->t_start, who));
+    if (!plane_shape_ok(rule.kind, a->H, a->W, a->unet->cfg.in_ch))
+        return bad(rule.kind == StepKind::RestoreBlur ? "H and W must be multiples of 16 in [16, 256], the model's channels 1 to 8"
+                                                      : "H and W must be powers of two in [16, 256], the model's channels 1 to 8");
+    if (const char* fault = own()) return bad(fault);
+    if (!aligned) return bad("alignment");
+    DDK_TRY(check_timestep_map(map, a->t_start, who));
+    return sampler_chain(a, who, map, rule, s);
+}
+static StepRule plane_rule(StepKind kind, const float* y) {
     StepRule rule{};
-    rule.kind = StepKind::RestoreBlur;
-    rule.blr = BlurOps{P_h, P_w, nullptr, Q_h, Q_w};
+    rule.kind = kind;
     rule.rst.y = y;
-    rule.rst.H = h; rule.rst.W = w;      // of the caller's y, until sampler_chain has formed Yp
-    return sampler_chain(a, who, timestep_map, rule, s);
+    return rule;
+}
+// (the deconvolution entries: one workgroup row per plane)
+static const char* fft_planes_fault(const ddk_sampler_args* a) {
+    return a->B > 0 && (long long)a->B * a->unet->cfg.in_ch <= 65535 ? nullptr : "B channels must be in [1, 65535]";
+}
+}  // namespace ddk
+
+// DDNM deblurring, A(X) = A_h X A_w^T per channel (section 3.14), StepKind::RestoreBlur.  P = A+ A and Q = A+ of the two axes are the
+// caller's (models/diffusion/blur.py), row-major [H][H] and [W][W] device arrays; y is the blurred image in x's layout.
+extern "C" size_t ddk_sampler_restore_blur_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start) {
+    return plane_bytes(u, B, H, W, t_start, StepKind::RestoreBlur);
+}
+extern "C" int ddk_sampler_restore_blur_tail_parts(const ddk_unet* u, int B, int H, int W) {
+    return plane_tail_parts(u, B, H, W, StepKind::RestoreBlur);
+}
+// (both entries: y is [B][h][w][C], Q_h [H][h], Q_w [W][w]; the deblurring entry's h, w are the plane's)
+static int restore_blur_chain(const ddk_sampler_args* a, const char* who, const int64_t* timestep_map, const float* P_h, const float* P_w,
+                              const float* Q_h, const float* Q_w, const float* y, bool sized, int h, int w, ddk_stream_t s) {
+    StepRule rule = plane_rule(StepKind::RestoreBlur, y);
+    rule.blr = BlurOps{P_h, P_w, nullptr, Q_h, Q_w};
+    return plane_chain(a, who, timestep_map, rule, {y, P_h, P_w, Q_h, Q_w}, [&]() -> const char* {
+        const int hh = rule.rst.H = sized ? h : a->H, ww = rule.rst.W = sized ? w : a->W;      // of the caller's y, until stage_blur has formed Yp
+        return hh >= 4 && hh <= a->H && hh % 4 == 0 && ww >= 4 && ww <= a->W && ww % 4 == 0 ? nullptr : "h and w must be multiples of 4 in [4, H] and [4, W]";
+    }, s);
 }
 extern "C" int ddk_sampler_run_restore_blur(const ddk_sampler_args* a, const int64_t* timestep_map, const float* P_h, const float* P_w,
                                             const float* Q_h, const float* Q_w, const float* y, ddk_stream_t s) {
@@ -2155,71 +2211,36 @@ extern "C" int ddk_sampler_run_restore_sep(const ddk_sampler_args* a, const int6
     return restore_blur_chain(a, "sampler_restore_sep", timestep_map, P_h, P_w, Q_h, Q_w, y, true, h, w, s);
 }
 
-// DDNM compressed sensing on a pixel-space model (section 3.17): the spaced sampler's chain, every step ending in
-// StepKind::RestoreHadamard.  y [B][C][m] and perm [H W] are the caller's device arrays, copied into the workspace before the first step.
-// Plane-wide like the blur kind: no step takes the fused tail.
+// DDNM compressed sensing (section 3.17), StepKind::RestoreHadamard.  y [B][C][m] and perm [H W] are the caller's device arrays, copied
+// into the workspace before the first step.
 extern "C" size_t ddk_sampler_restore_cs_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start) {
-    if (check_shape(u, B, H, W) != DDK_OK || !restore_cs_shape_ok(H, W, u->cfg.in_ch)) return 0;
-    return sampler_bytes(u, B, H, W, t_start, StepKind::RestoreHadamard);
+    return plane_bytes(u, B, H, W, t_start, StepKind::RestoreHadamard);
 }
 extern "C" int ddk_sampler_restore_cs_tail_parts(const ddk_unet* u, int B, int H, int W) {
-    if (check_shape(u, B, H, W) != DDK_OK) return -1;
-    return fused_tail_parts(*u, B, H, W, u->dimp[1], StepKind::RestoreHadamard);      // 0: final_tail_ok takes no plane-wide kind
+    return plane_tail_parts(u, B, H, W, StepKind::RestoreHadamard);
 }
 extern "C" int ddk_sampler_run_restore_cs(const ddk_sampler_args* a, const int64_t* timestep_map, const float* y, const int32_t* perm, int m,
                                           ddk_stream_t s) {
-    const char* who = "sampler_restore_cs";
-    auto bad = [who](const char* what) {
-        set_error("bad argument: %s: %s", who, what);
-        return DDK_ERR_ARG;
-    };
-    if (!(a && a->unet && a->packed && a->x && a->workspace && y && perm)) return bad("null pointer");
-    if (!(a->c_recip && a->c_recipm1 && a->c1 && a->c2 && a->sigma)) return bad("null schedule table");
-    if (a->noise) return bad("injected noise is not supported, noise must be NULL (Philox only)");
-    if (!(a->t_start >= a->t_end && a->t_end >= 0)) return bad("need t_start >= t_end >= 0");
-    if (!restore_cs_shape_ok(a->H, a->W, a->unet->cfg.in_ch)) return bad("H and W must be powers of two in [16, 256], the model's channels 1 to 8");
-    if (!restore_cs_rows_ok(a->H, a->W, m)) return bad("m must be a multiple of 4 in [4, H W]");
-    if (!(aligned16(y) && aligned16(perm))) return bad("alignment");
-    DDK_TRY(check_timestep_map(timestep_map, a->t_start, who));
-    StepRule rule{};
-    rule.kind = StepKind::RestoreHadamard;
+    StepRule rule = plane_rule(StepKind::RestoreHadamard, y);
     rule.had = HadamardOps{perm, nullptr, m};
-    rule.rst.y = y;
-    return sampler_chain(a, who, timestep_map, rule, s);
+    return plane_chain(a, "sampler_restore_cs", timestep_map, rule, {y, perm},
+                       [&]() { return restore_cs_rows_ok(a->H, a->W, m) ? nullptr : "m must be a multiple of 4 in [4, H W]"; }, s);
 }
 
-// DDNM deconvolution of a 2-D point-spread function with periodic boundary on a pixel-space model (section 3.18): the spaced sampler's
-// chain, every step ending in StepKind::RestoreFFT.  mask [H][W], P^ [H][W] complex, the twiddles and y (x's layout) are the caller's
-// device arrays; mask and twiddles are copied into the workspace and Yp = A+ y is formed there before the first step.  Plane-wide like
-// the blur kind: no step takes the fused tail.
+// DDNM deconvolution of a 2-D point-spread function with periodic boundary (section 3.18), StepKind::RestoreFFT.  mask [H][W], P^ [H][W]
+// complex, the twiddles and y (x's layout) are the caller's device arrays; mask and twiddles are copied into the workspace and Yp = A+ y
+// is formed there before the first step.
 extern "C" size_t ddk_sampler_restore_fft_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start) {
-    if (check_shape(u, B, H, W) != DDK_OK || !restore_fft_shape_ok(H, W, u->cfg.in_ch)) return 0;
-    return sampler_bytes(u, B, H, W, t_start, StepKind::RestoreFFT);
+    return plane_bytes(u, B, H, W, t_start, StepKind::RestoreFFT);
 }
 extern "C" int ddk_sampler_restore_fft_tail_parts(const ddk_unet* u, int B, int H, int W) {
-    if (check_shape(u, B, H, W) != DDK_OK) return -1;
-    return fused_tail_parts(*u, B, H, W, u->dimp[1], StepKind::RestoreFFT);      // 0: final_tail_ok takes no plane-wide kind
+    return plane_tail_parts(u, B, H, W, StepKind::RestoreFFT);
 }
 extern "C" int ddk_sampler_run_restore_fft(const ddk_sampler_args* a, const int64_t* timestep_map, const float* mask, const float* P,
                                            const float* twiddles, const float* y, ddk_stream_t s) {
-    const char* who = "sampler_restore_fft";
-    auto bad = [who](const char* what) {
-        set_error("bad argument: %s: %s", who, what);
-        return DDK_ERR_ARG;
-    };
-    if (!(a && a->unet && a->packed && a->x && a->workspace && mask && P && twiddles && y)) return bad("null pointer");
-    if (!(a->c_recip && a->c_recipm1 && a->c1 && a->c2 && a->sigma)) return bad("null schedule table");
-    if (a->noise) return bad("injected noise is not supported, noise must be NULL (Philox only)");
-    if (!(a->t_start >= a->t_end && a->t_end >= 0)) return bad("need t_start >= t_end >= 0");
-    if (!restore_fft_shape_ok(a->H, a->W, a->unet->cfg.in_ch)) return bad("H and W must be powers of two in [16, 256], the model's channels 1 to 8");
-    if (!(a->B > 0 && (long long)a->B * a->unet->cfg.in_ch <= 65535)) return bad("B channels must be in [1, 65535]");
-    if (!(aligned16(mask) && aligned16(P) && aligned16(twiddles) && aligned16(y))) return bad("alignment");
-    DDK_TRY(check_timestep_map(timestep_map, a->t_start, who));
-    StepRule rule{};
-    rule.kind = StepKind::RestoreFFT;
+    StepRule rule = plane_rule(StepKind::RestoreFFT, y);
     rule.fft = FftOps{mask, twiddles, nullptr, P};
-    rule.rst.y = y;
-    return sampler_chain(a, who, timestep_map, rule, s);
+    return plane_chain(a, "sampler_restore_fft", timestep_map, rule, {mask, P, twiddles, y}, [&]() { return fft_planes_fault(a); }, s);
 }
 
 // DDNM+ deconvolution of a noisy blurred image (section 3.19): ddk_sampler_run_restore_fft's chain, every step ending in
@@ -2227,33 +2248,17 @@ extern "C" int ddk_sampler_run_restore_fft(const ddk_sampler_args* a, const int6
 // the workspace and the spectrum of A+ y is formed there before the first step.  The caller's gain and nsc are in the graph key, so a
 // chain of one sigma_y never replays another's graph, and the kind keeps it from a deconvolution chain's.
 extern "C" size_t ddk_sampler_restore_fft_noisy_workspace_bytes(const ddk_unet* u, int B, int H, int W, int t_start) {
-    if (check_shape(u, B, H, W) != DDK_OK || !restore_fft_shape_ok(H, W, u->cfg.in_ch)) return 0;
-    return sampler_bytes(u, B, H, W, t_start, StepKind::RestoreFFTNoisy);
+    return plane_bytes(u, B, H, W, t_start, StepKind::RestoreFFTNoisy);
 }
 extern "C" int ddk_sampler_restore_fft_noisy_tail_parts(const ddk_unet* u, int B, int H, int W) {
-    if (check_shape(u, B, H, W) != DDK_OK) return -1;
-    return fused_tail_parts(*u, B, H, W, u->dimp[1], StepKind::RestoreFFTNoisy);      // 0: final_tail_ok takes no plane-wide kind
+    return plane_tail_parts(u, B, H, W, StepKind::RestoreFFTNoisy);
 }
 extern "C" int ddk_sampler_run_restore_fft_noisy(const ddk_sampler_args* a, const int64_t* timestep_map, const float* mask, const float* P,
                                                  const float* gain, const float* nsc, const float* twiddles, const float* y, ddk_stream_t s) {
-    const char* who = "sampler_restore_fft_noisy";
-    auto bad = [who](const char* what) {
-        set_error("bad argument: %s: %s", who, what);
-        return DDK_ERR_ARG;
-    };
-    if (!(a && a->unet && a->packed && a->x && a->workspace && mask && P && gain && nsc && twiddles && y)) return bad("null pointer");
-    if (!(a->c_recip && a->c_recipm1 && a->c1 && a->c2 && a->sigma)) return bad("null schedule table");
-    if (a->noise) return bad("injected noise is not supported, noise must be NULL (Philox only)");
-    if (!(a->t_start >= a->t_end && a->t_end >= 0)) return bad("need t_start >= t_end >= 0");
-    if (!restore_fft_shape_ok(a->H, a->W, a->unet->cfg.in_ch)) return bad("H and W must be powers of two in [16, 256], the model's channels 1 to 8");
-    if (!(a->B > 0 && (long long)a->B * a->unet->cfg.in_ch <= 65535)) return bad("B channels must be in [1, 65535]");
-    if (!(aligned16(mask) && aligned16(P) && aligned16(gain) && aligned16(nsc) && aligned16(twiddles) && aligned16(y))) return bad("alignment");
-    DDK_TRY(check_timestep_map(timestep_map, a->t_start, who));
-    StepRule rule{};
-    rule.kind = StepKind::RestoreFFTNoisy;
+    StepRule rule = plane_rule(StepKind::RestoreFFTNoisy, y);
     rule.fnz = FftNoisyOps{mask, twiddles, nullptr, gain, nsc, P};
-    rule.rst.y = y;
-    return sampler_chain(a, who, timestep_map, rule, s);
+    return plane_chain(a, "sampler_restore_fft_noisy", timestep_map, rule, {mask, P, gain, nsc, twiddles, y},
+                       [&]() { return fft_planes_fault(a); }, s);
 }
 
 // ------------------------------------------------------------------------------------------------ likelihood sweep

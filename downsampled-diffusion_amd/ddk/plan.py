@@ -7,6 +7,7 @@ runs a whole forward -- or the whole T-step sampling loop -- from a single C cal
 import contextlib
 import ctypes as C
 import math
+import types
 import warnings
 
 import torch
@@ -370,59 +371,72 @@ class UnetPlan:
         "srf": ("sampler_run_restore_fft", "sampler_restore_fft_workspace_bytes", "sampler_restore_fft_tail_parts"),
         "sfn": ("sampler_run_restore_fft_noisy", "sampler_restore_fft_noisy_workspace_bytes", "sampler_restore_fft_noisy_tail_parts")}
 
-    def _restore_tail_parts(self, kind, b, h, w, n):
+    # What each entry takes, keyed like RESTORE_ENTRIES.  q holds b, h, w, c of x, n, the rows of the chain and what `derive` adds.
+    #   blocks: the block sizes n of a block kind; mask_at_1: its n = 1 needs a mask; gray: the grey entry (3 channels, weights, y [B,H/n,W/n])
+    #   grid:   (test of H and of W, its words): the shape rule of a plane-wide kind, which has no block and no mask of pixels
+    #   derive: (q, y, given) -> what the entry reads off its operands; also: q -> None or what is wrong with that, checked behind grid
+    #   ops:    the named extra operands as (name, shape of q, dtype): contiguous tensors on x's device; y: the shape of y
+    #   order:  how the C entry takes y, the operands and the integers of q, behind the tables of `head`; n_query: the workspace query takes n
+    _F, _I = torch.float32, torch.int32
+    _POW2, _MULT16 = (lambda v: v & (v - 1) == 0, "powers of two"), (lambda v: v % 16 == 0, "multiples of 16")
+    _BLOCK_Y, _FULL_Y = (lambda q: (q.b, q.h // q.n, q.w // q.n, q.c)), (lambda q: (q.b, q.h, q.w, q.c))
+    _MASKED = dict(blocks=(1, 2, 4, 8), mask_at_1=True, y=_BLOCK_Y, order=("y", "mask", "n"), n_query=True)
+    _SEP = dict(grid=_MULT16, y=lambda q: (q.b, q.yh, q.yw, q.c),
+                also=lambda q: None if q.yh % 4 == 0 and q.yw % 4 == 0 and 4 <= q.yh <= q.h and 4 <= q.yw <= q.w else
+                f"y's size must be multiples of 4 in [4, {q.h}] and [4, {q.w}], got {q.yh} x {q.yw}",
+                ops=(("P_h", lambda q: (q.h, q.h), _F), ("P_w", lambda q: (q.w, q.w), _F), ("Q_h", lambda q: (q.h, q.yh), _F),
+                     ("Q_w", lambda q: (q.w, q.yw), _F)))
+    _FFT_OPS = (("mask", lambda q: (q.h, q.w), _F), ("P", lambda q: (q.h, q.w, 2), _F), ("gain", lambda q: (q.h, q.w), _F),
+                ("nsc", lambda q: (q.rows,), _F))
+    RESTORE_OPS = {
+        "srs": dict(blocks=(2, 4, 8), y=_BLOCK_Y, order=("y", "n")),
+        "srm": _MASKED, "srx": _MASKED, "srn": _MASKED,
+        "srg": dict(blocks=(1, 2, 4, 8), gray=True, y=lambda q: (q.b, q.h // q.n, q.w // q.n), order=("y", "mask", "n", "weights"), n_query=True),
+        "srb": dict(_SEP, derive=lambda q, y, g: dict(yh=q.h, yw=q.w), order=("P_h", "P_w", "Q_h", "Q_w", "y")),
+        "srq": dict(_SEP, order=("P_h", "P_w", "Q_h", "Q_w", "y", "yh", "yw"),      # a size of 0: refused by `also`
+                    derive=lambda q, y, g: dict(zip(("yh", "yw"), (int(v.shape[1]) if v is not None and v.dim() == 2 else 0
+                                                                   for v in (g["Q_h"], g["Q_w"]))))),
+        "src": dict(grid=_POW2, y=lambda q: (q.b, q.c, q.m), ops=(("perm", lambda q: (q.h * q.w,), _I),), order=("y", "perm", "m"),
+                    derive=lambda q, y, g: dict(m=int(y.shape[2]) if y is not None and y.dim() == 3 else 0),      # 0: refused by `also`
+                    also=lambda q: None if isinstance(q.m, int) and 4 <= q.m <= q.h * q.w and q.m % 4 == 0 else
+                    f"m must be a multiple of 4 in [4, {q.h * q.w}], got {q.m!r}"),
+        "srf": dict(grid=_POW2, y=_FULL_Y, ops=_FFT_OPS[:2], order=("mask", "P", "twiddles", "y")),
+        "sfn": dict(grid=_POW2, y=_FULL_Y, ops=_FFT_OPS, order=("mask", "P", "gain", "nsc", "twiddles", "y"))}
+
+    def _restore_tail_parts(self, kind, b, h, w, n=None):
         return int(getattr(self._lib, "ddk_" + self.RESTORE_ENTRIES[kind][2])(self.handle, b, h, w, *(() if n is None else (int(n),))))
 
-    def _sample_restore(self, kind, x, y, mask, n, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, head=(), masked=True,
-                        weights=None, blur=None, y_size=None, cs=None, fft=None):
-        """What the restoration samplers share: the checks on n, y, mask and the lam / sgm tables, then the chain.
-        kind: the entry's key in SAMPLERS and RESTORE_ENTRIES; head: the names of the tables the C entry takes before y; masked: the
-        entry takes a mask and n = 1 (which then needs one), and its workspace query takes n; weights: the grey entry's, whose y is
-        [B,H/n,W/n] and whose n = 1 needs no mask; blur: the deblurring entry's matrices (P_h, P_w, Q_h, Q_w), whose operator has no
-        block (n is None, no mask) and whose y has x's shape -- or, for the size-changing entry, y_size = (h, w) of y [B,h,w,in_ch],
-        with Q_h [H,h] and Q_w [W,w]; cs: the compressed-sensing entry's (perm, m), whose operator has no block either and whose y is
-        [B,in_ch,m]; fft: the deconvolution entry's (mask [H,W], P [H,W,2]), whose operator has no block and whose y has x's shape -- or the noisy deconvolution entry's
-        (mask, P, gain [H,W], nsc [t_start + 1])."""
+    def _sample_restore(self, kind, x, y, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, head=(), n=1, **given):
+        """What the restoration samplers share: one walk over the entry's description in RESTORE_OPS -- the checks on the shape, n, the
+        named operands, y, the mask and the tables, then the chain.  kind: the entry's key in SAMPLERS, RESTORE_ENTRIES and
+        RESTORE_OPS; head: the names of the tables the C entry takes before its operands; given: the entry's other operands by name."""
         self._need_packed(kind)
-        name = SAMPLERS[kind][0]
-        gray = weights is not None
+        name, d = SAMPLERS[kind][0], self.RESTORE_OPS[kind]
         b, h, w, c = x.shape
-        if cs is not None:
-            perm, m = cs
-            if not (h & (h - 1) == 0 and w & (w - 1) == 0 and 16 <= h <= 256 and 16 <= w <= 256 and 1 <= c <= 8):
-                raise L.DDKError(f"{name}: H and W must be powers of two in [16, 256] and the channels 1 to 8, got [{h},{w},{c}]")
-            if not (isinstance(m, int) and 4 <= m <= h * w and m % 4 == 0):
-                raise L.DDKError(f"{name}: m must be a multiple of 4 in [4, {h * w}], got {m!r}")
-            if perm is None or tuple(perm.shape) != (h * w,) or perm.dtype != torch.int32 or not perm.is_contiguous() or perm.device != x.device:
-                raise L.DDKError(f"{name}: perm must be a contiguous int32 [{h * w}] tensor on x's device")
-            n = 1                 # no block, no mask
-        if fft is not None:
-            if not (h & (h - 1) == 0 and w & (w - 1) == 0 and 16 <= h <= 256 and 16 <= w <= 256 and 1 <= c <= 8):
-                raise L.DDKError(f"{name}: H and W must be powers of two in [16, 256] and the channels 1 to 8, got [{h},{w},{c}]")
-            for what, v, shape in zip(("mask", "P", "gain", "nsc"), fft, ((h, w), (h, w, 2), (h, w), (t_start + 1,))):
-                if v is None or tuple(v.shape) != shape or v.dtype != torch.float32 or not v.is_contiguous() or v.device != x.device:
-                    raise L.DDKError(f"{name}: {what} must be a contiguous fp32 [{','.join(map(str, shape))}] tensor on x's device")
-            n = 1                 # no block, no mask of pixels: y has x's shape
-        if gray and c != 3:
-            raise L.DDKError(f"{name}: the grey operator needs a 3-channel map, got {c} channels")
-        if gray and weights not in L.GRAY_WEIGHTS:
-            raise L.DDKError(f"{name}: weights must be 'mean' or 'luma', got {weights!r}")
-        if blur is not None:
-            if not (h % 16 == 0 and w % 16 == 0 and 16 <= h <= 256 and 16 <= w <= 256 and 1 <= c <= 8):
-                raise L.DDKError(f"{name}: H and W must be multiples of 16 in [16, 256] and the channels 1 to 8, got [{h},{w},{c}]")
-            yh, yw = (h, w) if y_size is None else y_size
-            if not (yh % 4 == 0 and yw % 4 == 0 and 4 <= yh <= h and 4 <= yw <= w):
-                raise L.DDKError(f"{name}: y's size must be multiples of 4 in [4, {h}] and [4, {w}], got {yh} x {yw}")
-            for what, v, shape in zip(("P_h", "P_w", "Q_h", "Q_w"), blur, ((h, h), (w, w), (h, yh), (w, yw))):
-                if v is None or tuple(v.shape) != shape or v.dtype != torch.float32 or not v.is_contiguous() or v.device != x.device:
-                    raise L.DDKError(f"{name}: {what} must be a contiguous fp32 [{shape[0]},{shape[1]}] tensor on x's device")
-            n = 1                 # y has x's shape, or y_size
-        elif cs is None and fft is None and (n not in ((1, 2, 4, 8) if masked else (2, 4, 8)) or h % n or w % n):
-            raise L.DDKError(f"{name}: n must be {'1, ' if masked else ''}2, 4 or 8 and divide H = {h} and W = {w}, got {n}")
-        if mask is None and n == 1 and not gray and blur is None and cs is None and fft is None:
-            raise L.DDKError(f"{name}: n = 1 needs a mask (nothing would be constrained)")
-        y_shape = (b, h, w, c) if fft is not None else (b, c, cs[1]) if cs is not None else (b, *y_size, c) if y_size is not None else (b, h // n, w // n) if gray else (b, h // n, w // n, c)
-        for what, v, shape in (("y", y, y_shape), ("mask", mask, (b, h // n, w // n))):
+        mask = None if "grid" in d else given.get("mask")      # (a plane-wide kind's "mask" is one of its ops: of frequencies, not of pixels)
+        q = types.SimpleNamespace(b=b, h=h, w=w, c=c, n=n, rows=t_start + 1)
+        q.__dict__.update(d["derive"](q, y, given) if "derive" in d else {})
+        if "grid" in d:
+            ok, words = d["grid"]
+            if not (ok(h) and ok(w) and 16 <= h <= 256 and 16 <= w <= 256 and 1 <= c <= 8):
+                raise L.DDKError(f"{name}: H and W must be {words} in [16, 256] and the channels 1 to 8, got [{h},{w},{c}]")
+            if "also" in d and d["also"](q):
+                raise L.DDKError(f"{name}: {d['also'](q)}")
+            for what, shape, dtype in d["ops"]:
+                v, shape = given[what], shape(q)
+                if v is None or tuple(v.shape) != shape or v.dtype != dtype or not v.is_contiguous() or v.device != x.device:
+                    raise L.DDKError(f"{name}: {what} must be a contiguous {'fp32' if dtype == self._F else 'int32'} "
+                                     f"[{','.join(map(str, shape))}] tensor on x's device")
+        else:
+            if d.get("gray") and c != 3:
+                raise L.DDKError(f"{name}: the grey operator needs a 3-channel map, got {c} channels")
+            if d.get("gray") and given["weights"] not in L.GRAY_WEIGHTS:
+                raise L.DDKError(f"{name}: weights must be 'mean' or 'luma', got {given['weights']!r}")
+            if n not in d["blocks"] or h % n or w % n:
+                raise L.DDKError(f"{name}: n must be {'1, ' if 1 in d['blocks'] else ''}2, 4 or 8 and divide H = {h} and W = {w}, got {n}")
+            if mask is None and n == 1 and d.get("mask_at_1"):
+                raise L.DDKError(f"{name}: n = 1 needs a mask (nothing would be constrained)")
+        for what, v, shape in (("y", y, d["y"](q)), ("mask", mask, (b, h // n, w // n))):
             if v is not None and (tuple(v.shape) != shape or v.dtype != torch.float32 or not v.is_contiguous()):
                 raise L.DDKError(f"{what} must be a contiguous fp32 [{','.join(map(str, shape))}] tensor, got {tuple(v.shape)} {v.dtype}")
         for t in head:
@@ -431,23 +445,19 @@ class UnetPlan:
         run_name = self.RESTORE_ENTRIES[kind][0]
         run, workspace_bytes = (getattr(self._lib, "ddk_" + f) for f in self.RESTORE_ENTRIES[kind][:2])
         tmap = self._timestep_map(timesteps, t_start)
-        operands = (L.ptr(y), L.ptr(mask), int(n)) if masked else (L.ptr(y), int(n))
-        if blur is not None:
-            operands = (*(L.ptr(m) for m in blur), L.ptr(y), *(() if y_size is None else (int(y_size[0]), int(y_size[1]))))
-        if cs is not None:
-            operands = (L.ptr(y), L.ptr(cs[0]), int(cs[1]))
-        if fft is not None:
+        given["y"] = y
+        if "twiddles" in d["order"]:
             from . import ops
-            operands = (*(L.ptr(v) for v in fft), L.ptr(ops.fft_twiddles(max(h, w), x.device)), L.ptr(y))
-        if gray:
-            operands += (L.GRAY_WEIGHTS[weights],)
+            given["twiddles"] = ops.fft_twiddles(max(h, w), x.device)
+        operands = tuple(L.GRAY_WEIGHTS[given[o]] if o == "weights" else int(getattr(q, o)) if hasattr(q, o) else L.ptr(given[o])
+                         for o in d["order"])
 
         def call(x, ws, nbytes, stream_ptr):
             a = self._sampler_args(x, None, tables, t_start, t_end, seed, stream_id, use_graph, ws, nbytes)
             L.check(run(C.byref(a), tmap, *(L.ptr(tables[t]) for t in head), *operands, stream_ptr), run_name)
 
         return self._run_sampler(kind, x, t_start, t_end,
-                                 lambda b, h, w: workspace_bytes(self.handle, b, h, w, t_start, *((int(n),) if masked else ())), call,
+                                 lambda b, h, w: workspace_bytes(self.handle, b, h, w, t_start, *((int(n),) if d.get("n_query") else ())), call,
                                  use_graph)
 
     def restore_tail_parts(self, b, h, w, n):
@@ -461,7 +471,7 @@ class UnetPlan:
         y: [B,H/n,W/n,in_ch] fp32 device tensor, copied into the plan's "srs" workspace by every call, so a loop over images replays
         one cached graph; n in {2, 4, 8} divides H and W.  tables / timesteps: as for sample_nhwc (plain, respaced or DDIM).
         Philox only: no injected noise."""
-        return self._sample_restore("srs", x, y, None, n, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, masked=False)
+        return self._sample_restore("srs", x, y, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, n=n)
 
     def restore_masked_tail_parts(self, b, h, w, n):
         """Tiles per image of the fused tail of a masked restoration step on [b, h, w] with block n (1 included), or 0."""
@@ -474,7 +484,7 @@ class UnetPlan:
         y: [B,H/n,W/n,in_ch], mask: [B,H/n,W/n] (nonzero = measured) fp32 device tensors, copied into the plan's "srm" workspace by
         every call, so a loop over images and masks replays one cached graph; n in {1, 2, 4, 8} divides H and W.  mask None (n >= 2
         only) is sample_restore_nhwc's chain.  tables / timesteps: as for sample_nhwc (plain, respaced or DDIM).  Philox only."""
-        return self._sample_restore("srm", x, y, mask, n, tables, t_start, t_end, seed, stream_id, use_graph, timesteps)
+        return self._sample_restore("srm", x, y, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, n=n, mask=mask)
 
     def restore_multistep_tail_parts(self, b, h, w, n):
         """Tiles per image of the fused tail of a restoration-solver step on [b, h, w] with block n (1 included), or 0."""
@@ -487,7 +497,7 @@ class UnetPlan:
         y, mask, n: as for sample_restore_masked_nhwc (mask None at n >= 2: every block measured); they are copied into the plan's
         "srx" workspace by every call, so a loop over images and masks replays one cached graph.  tables / timesteps: as for
         sample_multistep_nhwc.  Deterministic: no noise, no seed; the history is zeroed by every call."""
-        return self._sample_restore("srx", x, y, mask, n, tables, t_start, t_end, 0, stream_id, use_graph, timesteps, head=("c3",))
+        return self._sample_restore("srx", x, y, tables, t_start, t_end, 0, stream_id, use_graph, timesteps, head=("c3",), n=n, mask=mask)
 
     def restore_noisy_tail_parts(self, b, h, w, n):
         """Tiles per image of the fused tail of a noisy restoration step on [b, h, w] with block n (1 included), or 0."""
@@ -500,7 +510,7 @@ class UnetPlan:
         y, mask, n: as for sample_restore_masked_nhwc (mask None at n >= 2: every block measured); they are copied into the plan's
         "srn" workspace by every call.  tables: sample_restore_masked_nhwc's plus the per-row "lam" and "sgm" (respace.noisy_tables);
         they are in the graph key, so chains with different noise levels never replay each other's graph.  Philox only."""
-        return self._sample_restore("srn", x, y, mask, n, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, head=("lam", "sgm"))
+        return self._sample_restore("srn", x, y, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, head=("lam", "sgm"), n=n, mask=mask)
 
     def restore_gray_tail_parts(self, b, h, w, n):
         """Tiles per image of the fused tail of a colourisation step on [b, h, w] with block n (1 included), or 0 (always 0 for a
@@ -515,13 +525,13 @@ class UnetPlan:
         y, mask: contiguous fp32 [B,H/n,W/n] (mask None: every block measured, at any n); weights "mean" or "luma"; they are copied
         into the plan's "srg" workspace by every call.  tables: sample_restore_noisy_nhwc's, "lam" and "sgm" included
         (respace.gray_tables); the tables, n, the mask's presence and the weights are in the graph key.  Philox only."""
-        return self._sample_restore("srg", x, y, mask, n, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, head=("lam", "sgm"),
+        return self._sample_restore("srg", x, y, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, head=("lam", "sgm"), n=n, mask=mask,
                                     weights=weights)
 
     def restore_blur_tail_parts(self, b, h, w):
         """Tiles per image of the fused tail of a deblurring step on [b, h, w]: 0 for every shape (the operator couples a whole
         plane, the tail owns 128-pixel tiles), -1 for a shape the plan does not take."""
-        return self._restore_tail_parts("srb", b, h, w, None)
+        return self._restore_tail_parts("srb", b, h, w)
 
     def sample_restore_blur_nhwc(self, x, y, P_h, P_w, Q_h, Q_w, tables, t_start, t_end=0, seed=0, stream_id=0, use_graph=True,
                                  timesteps=None):
@@ -532,8 +542,7 @@ class UnetPlan:
         pseudo-inverses of the two axes (models/diffusion/blur.py blur_operands).  P_h and P_w are copied into the plan's "srb"
         workspace and Yp = Q_h y Q_w^T is formed there by every call, so a loop over images replays one cached graph.  H and W
         multiples of 16 in [16, 256].  tables / timesteps: as for sample_nhwc (plain, respaced or DDIM).  Philox only."""
-        return self._sample_restore("srb", x, y, None, None, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, masked=False,
-                                    blur=(P_h, P_w, Q_h, Q_w))
+        return self._sample_restore("srb", x, y, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, P_h=P_h, P_w=P_w, Q_h=Q_h, Q_w=Q_w)
 
     def sample_restore_sep_nhwc(self, x, y, P_h, P_w, Q_h, Q_w, tables, t_start, t_end=0, seed=0, stream_id=0, use_graph=True,
                                 timesteps=None):
@@ -545,14 +554,12 @@ class UnetPlan:
         pseudo-inverses of the two axes (models/diffusion/blur.py separable_operands).  The steps are sample_restore_blur_nhwc's;
         Yp = Q_h y Q_w^T is formed in the plan's "srq" workspace by every call, so a loop over images replays one cached graph.
         H and W multiples of 16 in [16, 256], h and w multiples of 4 in [4, H] and [4, W].  Philox only."""
-        y_size = tuple(int(q.shape[1]) if q is not None and q.dim() == 2 else 0 for q in (Q_h, Q_w))      # 0: refused below
-        return self._sample_restore("srq", x, y, None, None, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, masked=False,
-                                    blur=(P_h, P_w, Q_h, Q_w), y_size=y_size)
+        return self._sample_restore("srq", x, y, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, P_h=P_h, P_w=P_w, Q_h=Q_h, Q_w=Q_w)
 
     def restore_cs_tail_parts(self, b, h, w):
         """Tiles per image of the fused tail of a compressed-sensing step on [b, h, w]: 0 for every shape (the operator couples a
         whole plane), -1 for a shape the plan does not take."""
-        return self._restore_tail_parts("src", b, h, w, None)
+        return self._restore_tail_parts("src", b, h, w)
 
     def sample_restore_cs_nhwc(self, x, y, perm, tables, t_start, t_end=0, seed=0, stream_id=0, use_graph=True, timesteps=None):
         """DDNM compressed-sensing steps, A = the first m rows of the orthonormal Walsh-Hadamard transform of each permuted plane,
@@ -562,14 +569,12 @@ class UnetPlan:
         permutation of the pixels (models/diffusion/hadamard.py cs_perm).  Both are copied into the plan's "src" workspace by every
         call, so a loop over images replays one cached graph.  H and W powers of two in [16, 256], m a multiple of 4 in [4, H*W].
         tables / timesteps: as for sample_nhwc (plain, respaced or DDIM).  Philox only."""
-        m = int(y.shape[2]) if y is not None and y.dim() == 3 else 0      # 0: refused below
-        return self._sample_restore("src", x, y, None, None, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, masked=False,
-                                    cs=(perm, m))
+        return self._sample_restore("src", x, y, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, perm=perm)
 
     def restore_fft_tail_parts(self, b, h, w):
         """Tiles per image of the fused tail of a deconvolution step on [b, h, w]: 0 for every shape (the operator couples a whole
         plane), -1 for a shape the plan does not take."""
-        return self._restore_tail_parts("srf", b, h, w, None)
+        return self._restore_tail_parts("srf", b, h, w)
 
     def sample_restore_fft_nhwc(self, x, y, mask, P, tables, t_start, t_end=0, seed=0, stream_id=0, use_graph=True, timesteps=None):
         """DDNM deconvolution steps, A = circular convolution with a 2-D point-spread function, t_start .. t_end (inclusive), in
@@ -579,12 +584,11 @@ class UnetPlan:
         truncated reciprocal spectrum (models/diffusion/psf.py psf_operands).  Mask and twiddles are copied into the plan's "srf"
         workspace and Yp = A+ y is formed there by every call, so a loop over images replays one cached graph.  H and W powers of two
         in [16, 256].  tables / timesteps: as for sample_nhwc (plain, respaced or DDIM).  Philox only."""
-        return self._sample_restore("srf", x, y, None, None, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, masked=False,
-                                    fft=(mask, P))
+        return self._sample_restore("srf", x, y, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, mask=mask, P=P)
 
     def restore_fft_noisy_tail_parts(self, b, h, w):
         """As restore_fft_tail_parts, for the noisy deconvolution step: 0 for every shape, -1 for a shape the plan does not take."""
-        return self._restore_tail_parts("sfn", b, h, w, None)
+        return self._restore_tail_parts("sfn", b, h, w)
 
     def sample_restore_fft_noisy_nhwc(self, x, y, mask, P, gain, nsc, tables, t_start, t_end=0, seed=0, stream_id=0, use_graph=True,
                                       timesteps=None):
@@ -596,8 +600,8 @@ class UnetPlan:
         workspace and the spectrum of A+ y is formed there by every call.  The cached graph is keyed by the gain and nsc tensors:
         pass the same tensors to replay it.  tables / timesteps: as for sample_nhwc (respaced ancestral, or DDIM with eta > 0).
         Philox only."""
-        return self._sample_restore("sfn", x, y, None, None, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, masked=False,
-                                    fft=(mask, P, gain, nsc))
+        return self._sample_restore("sfn", x, y, tables, t_start, t_end, seed, stream_id, use_graph, timesteps, mask=mask, P=P, gain=gain,
+                                    nsc=nsc)
 
     # ---------------------------------------------------------------- likelihood sweep
     VLB_STREAM_BIT = 1 << 31     # the sweep's Philox stream id is stream_id | this (csrc/ddk_internal.h VLB_STREAM_BIT)

@@ -25,6 +25,17 @@ OBJETIVE_NAMES = ['simple', 'hybrid', 'vlb']
 SOLVERS = ('dpm++2m',)
 
 
+def _once(make):
+    """make(*args) at the first call; that first result at every call."""
+    made = []
+
+    def get(*args):
+        if not made:
+            made.append(make(*args))
+        return made[0]
+    return get
+
+
 class DDPM(nn.Module):
     def __init__(self, config: dict, latent_model: nn.Module, device: str, color_channels: int = 3):
         super().__init__()
@@ -344,6 +355,36 @@ class DDPM(nn.Module):
         x, m = self._inpaint_args(x, mask, self.sample_shape, jump_length, jump_n_sample, unsupported)
         return self._inpaint_loop(x, m, respacing, jump_length, jump_n_sample, x_T, seed)
 
+    # ------------------------------------------------------------------ what the DDNM entries' argument checks share
+    @staticmethod
+    def _eta_arg(who, ddim, eta):
+        """ValueError unless eta is a real number >= 0, and 0 without ddim."""
+        if isinstance(eta, bool) or not isinstance(eta, (int, float, np.integer, np.floating)) or eta < 0 or (eta != 0 and not ddim):
+            raise ValueError(f"{who}: eta = {eta!r} needs ddim=True and eta >= 0")
+
+    @staticmethod
+    def _tol_arg(who, tol):
+        """ValueError unless tol is a real number in [0, 1)."""
+        if isinstance(tol, bool) or not isinstance(tol, (int, float, np.integer, np.floating)) or not (0 <= tol < 1):
+            raise ValueError(f"{who}: tol must be a real number in [0, 1), got {tol!r}")
+
+    @staticmethod
+    def _y_arg(who, y, shape, min_batch=0, finite=True):
+        """ValueError unless y is a float [B, *shape] tensor (a str in shape: any size, named so in the message) with B >= min_batch
+        and, with `finite`, no Inf or NaN.  Returns y as float."""
+        if not torch.is_tensor(y) or y.dim() != len(shape) + 1 or y.shape[0] < min_batch or not y.is_floating_point() or \
+                any(not isinstance(s, str) and d != s for d, s in zip(y.shape[1:], shape)):
+            raise ValueError(f"{who}: y must be a float [B, {', '.join(map(str, shape))}] tensor, got "
+                             f"{tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
+        if finite and not bool(torch.isfinite(y).all()):
+            raise ValueError(f"{who}: y must be finite")
+        return y.float()
+
+    def _chain_tables(self, respacing, ddim, eta):
+        """() -> (tables, timestep map or None) of an ancestral or DDIM chain: the spaced tables, or for the plain chain the model's own."""
+        spaced = respacing is not None or ddim or eta != 0
+        return lambda: self._spaced_tables(respacing, ddim, eta) if spaced else (self._tables(), None)
+
     # ------------------------------------------------------------------ DDNM super-resolution (not in the reference)
     RESTORE_UNSUPPORTED = ('solver', 'noise', 'early_stop')
     RESTORE_BLOCKS = (2, 4, 8)
@@ -361,12 +402,7 @@ class DDPM(nn.Module):
         C, H, W = shape
         if H % scale or W % scale:
             raise ValueError(f"super_resolve: scale = {scale} must divide the image size {H} x {W}")
-        if not torch.is_tensor(y) or y.dim() != 4 or list(y.shape[1:]) != [C, H // scale, W // scale] or not y.is_floating_point():
-            raise ValueError(f"super_resolve: y must be a float [B, {C}, {H // scale}, {W // scale}] tensor, got "
-                             f"{tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
-        if not bool(torch.isfinite(y).all()):
-            raise ValueError("super_resolve: y must be finite")
-        return y.float()
+        return self._y_arg("super_resolve", y, (C, H // scale, W // scale))
 
     def _ddnm_loop(self, who, y, mask, get_tables, x_T, seed, op, chain):
         """What the DDNM chains share, over the latent measured as y ([B, C, h, w], or the grey [B, h, w]) where mask [B, h, w] (None:
@@ -407,7 +443,6 @@ class DDPM(nn.Module):
         """DDNM over the latent whose n x n block means are held at y [B, C, H/n, W/n] (UnetPlan.sample_restore_nhwc).  mask
         [B, H/n, W/n] ({0, 1} floats, restore() only): the blocks that are held (n = 1: the pixels that are set to y), by the masked
         op and UnetPlan.sample_restore_masked_nhwc."""
-        spaced = respacing is not None or ddim or eta != 0
         sid, graph = int(self.rng_stream_id), self.use_graph
         if mask is None:
             def op(x, e, yl, mk, t, tables, seed):
@@ -421,8 +456,7 @@ class DDPM(nn.Module):
 
             def chain(plan, x, yl, mk, tables, k_start, seed, use):
                 plan.sample_restore_masked_nhwc(x, yl, mk, n, tables, k_start, seed=seed, stream_id=sid, use_graph=graph, timesteps=use)
-        return self._ddnm_loop(who, y, mask, lambda: self._spaced_tables(respacing, ddim, eta) if spaced else (self._tables(), None), x_T,
-                               seed, op, chain)
+        return self._ddnm_loop(who, y, mask, self._chain_tables(respacing, ddim, eta), x_T, seed, op, chain)
 
     @torch.no_grad()
     def super_resolve(self, y, scale, *, downsample="mean", respacing=None, ddim=False, eta=0.0, x_T=None, seed=None, **unsupported):
@@ -459,18 +493,14 @@ class DDPM(nn.Module):
                              f"over the whole schedule: no {', '.join(self.RESTORE_UNSUPPORTED)})")
         if isinstance(scale, bool) or not isinstance(scale, (int, np.integer)) or scale not in scales:
             raise ValueError(f"restore: scale must be an int in {tuple(scales)}, got {scale!r}")
-        if isinstance(eta, bool) or not isinstance(eta, (int, float, np.integer, np.floating)) or eta < 0 or (eta != 0 and not ddim):
-            raise ValueError(f"restore: eta = {eta!r} needs ddim=True and eta >= 0")
+        self._eta_arg("restore", ddim, eta)
         if mask is None and scale == 1:
             raise ValueError("restore: scale = 1 needs a mask (nothing would be constrained)")
         C, H, W = shape
         if H % scale or W % scale:
             raise ValueError(f"restore: scale = {scale} must divide the image size {H} x {W}")
         h, w = H // scale, W // scale
-        if not torch.is_tensor(y) or y.dim() != 4 or list(y.shape[1:]) != [C, h, w] or not y.is_floating_point():
-            raise ValueError(f"restore: y must be a float [B, {C}, {h}, {w}] tensor, got "
-                             f"{tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
-        return self._measured_args(y.float(), mask, h, w, "restore")
+        return self._measured_args(self._y_arg("restore", y, (C, h, w), finite=False), mask, h, w, "restore")
 
     @staticmethod
     def _measured_args(y, mask, h, w, who):
@@ -642,18 +672,14 @@ class DDPM(nn.Module):
         sigma_y = self._sigma_y_arg(sigma_y, "colorize")
         if isinstance(scale, bool) or not isinstance(scale, (int, np.integer)) or scale not in self.RESTORE_SCALES:
             raise ValueError(f"colorize: scale must be an int in {self.RESTORE_SCALES}, got {scale!r}")
-        if isinstance(eta, bool) or not isinstance(eta, (int, float, np.integer, np.floating)) or eta < 0 or (eta != 0 and not ddim):
-            raise ValueError(f"colorize: eta = {eta!r} needs ddim=True and eta >= 0")
+        self._eta_arg("colorize", ddim, eta)
         if sigma_y > 0 and ddim and eta == 0:
             raise ValueError("colorize: sigma_y > 0 needs a chain that draws (ancestral steps, or ddim with eta > 0): with eta = 0 every "
                              "row's lam is 0 and nothing would be constrained")
         if H % scale or W % scale:
             raise ValueError(f"colorize: scale = {scale} must divide the image size {H} x {W}")
         h, w = H // scale, W // scale
-        if not torch.is_tensor(y) or y.dim() != 4 or list(y.shape[1:]) != [1, h, w] or not y.is_floating_point():
-            raise ValueError(f"colorize: y must be a float [B, 1, {h}, {w}] tensor, got "
-                             f"{tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
-        y, m = self._measured_args(y.float(), mask, h, w, "colorize")
+        y, m = self._measured_args(self._y_arg("colorize", y, (1, h, w), finite=False), mask, h, w, "colorize")
         return y[:, 0].contiguous(), m, sigma_y
 
     def _colorize_loop(self, y, mask, n, weights, sigma_y, respacing, ddim, eta, x_T, seed):
@@ -698,19 +724,12 @@ class DDPM(nn.Module):
             raise ValueError(f"deblur: {sorted(unsupported)} not accepted (DDNM runs ancestral or DDIM steps with Philox draws over the "
                              f"whole schedule on an exact, unmasked measurement: no {', '.join(self.DEBLUR_UNSUPPORTED)})")
         blur.blur_kernel(kernel)      # its own ValueErrors
-        if isinstance(tol, bool) or not isinstance(tol, (int, float, np.integer, np.floating)) or not (0 <= tol < 1):
-            raise ValueError(f"deblur: tol must be a real number in [0, 1), got {tol!r}")
-        if isinstance(eta, bool) or not isinstance(eta, (int, float, np.integer, np.floating)) or eta < 0 or (eta != 0 and not ddim):
-            raise ValueError(f"deblur: eta = {eta!r} needs ddim=True and eta >= 0")
+        self._tol_arg("deblur", tol)
+        self._eta_arg("deblur", ddim, eta)
         C, H, W = self.sample_shape
         if H % 16 or W % 16 or not (16 <= H <= 256 and 16 <= W <= 256 and 1 <= C <= 8):
             raise ValueError(f"deblur: the image size must be multiples of 16 in [16, 256] with 1 to 8 channels, this model's is {C} x {H} x {W}")
-        if not torch.is_tensor(y) or y.dim() != 4 or list(y.shape[1:]) != [C, H, W] or not y.is_floating_point():
-            raise ValueError(f"deblur: y must be a float [B, {C}, {H}, {W}] tensor, got "
-                             f"{tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
-        if not bool(torch.isfinite(y).all()):
-            raise ValueError("deblur: y must be finite")
-        return y.float()
+        return self._y_arg("deblur", y, (C, H, W))
 
     @torch.no_grad()
     def deblur(self, y, kernel="gauss", *, tol=blur.DEFAULT_TOL, respacing=None, ddim=False, eta=0.0, x_T=None, seed=None, **unsupported):
@@ -724,17 +743,14 @@ class DDPM(nn.Module):
         [16, 256].  solver / noise / early_stop / paste / mask / sigma_y raise ValueError, as do an unknown kernel, a bad tol or eta
         and a non-finite or misshapen y, before any device work."""
         y = self._deblur_args(y, kernel, tol, ddim, eta, unsupported)
-        spaced = respacing is not None or ddim or eta != 0
         sid = int(self.rng_stream_id)
         m = self._blur_operands(kernel, tol)
-        yp = []                   # the Python loop's Yp = A+ y, formed at its first step
+        yp = _once(lambda yl: ops.separable_apply(yl, m["Q_h"], m["Q_w"]))      # the Python loop's Yp = A+ y, formed at its first step
 
         def op(x, e, yl, mk, t, tables, seed):
-            if not yp:
-                yp.append(ops.separable_apply(yl, m["Q_h"], m["Q_w"]))
-            ops.p_sample_update_restore_blur_(x, e, m["P_h"], m["P_w"], yp[0], t, **tables, seed=seed, stream_id=sid)
+            ops.p_sample_update_restore_blur_(x, e, m["P_h"], m["P_w"], yp(yl), t, **tables, seed=seed, stream_id=sid)
         return self._ddnm_loop(
-            "deblur", y, None, lambda: self._spaced_tables(respacing, ddim, eta) if spaced else (self._tables(), None), x_T, seed, op,
+            "deblur", y, None, self._chain_tables(respacing, ddim, eta), x_T, seed, op,
             lambda plan, x, yl, mk, tables, k_start, seed, use: plan.sample_restore_blur_nhwc(
                 x, yl, m["P_h"], m["P_w"], m["Q_h"], m["Q_w"], tables, k_start, seed=seed, stream_id=sid, use_graph=self.use_graph,
                 timesteps=use))
@@ -753,10 +769,8 @@ class DDPM(nn.Module):
         if unsupported:
             raise ValueError(f"{who}: {sorted(unsupported)} not accepted (DDNM runs ancestral or DDIM steps with Philox draws over the "
                              f"whole schedule on an exact, unmasked measurement: no {', '.join(self.DEBLUR_UNSUPPORTED)})")
-        if isinstance(tol, bool) or not isinstance(tol, (int, float, np.integer, np.floating)) or not (0 <= tol < 1):
-            raise ValueError(f"{who}: tol must be a real number in [0, 1), got {tol!r}")
-        if isinstance(eta, bool) or not isinstance(eta, (int, float, np.integer, np.floating)) or eta < 0 or (eta != 0 and not ddim):
-            raise ValueError(f"{who}: eta = {eta!r} needs ddim=True and eta >= 0")
+        self._tol_arg(who, tol)
+        self._eta_arg(who, ddim, eta)
         C, H, W = self.sample_shape
         if H % 16 or W % 16 or not (16 <= H <= 256 and 16 <= W <= 256 and 1 <= C <= 8):
             raise ValueError(f"{who}: the image size must be multiples of 16 in [16, 256] with 1 to 8 channels, this model's is {C} x {H} x {W}")
@@ -774,12 +788,7 @@ class DDPM(nn.Module):
                 raise ValueError(f"{who}: {what} must have a multiple of 4 in [4, {side}] rows, got {A.shape[0]}")
             mats.append(A)
         h, w = mats[0].shape[0], mats[1].shape[0]
-        if not torch.is_tensor(y) or y.dim() != 4 or list(y.shape[1:]) != [C, h, w] or not y.is_floating_point():
-            raise ValueError(f"{who}: y must be a float [B, {C}, {h}, {w}] tensor, got "
-                             f"{tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
-        if not bool(torch.isfinite(y).all()):
-            raise ValueError(f"{who}: y must be finite")
-        return y.float(), mats[0], mats[1]
+        return self._y_arg(who, y, (C, h, w)), mats[0], mats[1]
 
     @torch.no_grad()
     def restore_separable(self, y, A_h, A_w, *, tol=blur.DEFAULT_TOL, respacing=None, ddim=False, eta=0.0, x_T=None, seed=None,
@@ -793,18 +802,14 @@ class DDPM(nn.Module):
         sigma_y raise ValueError, as do misshapen or non-finite matrices, sizes off that grid, a bad tol or eta and a non-finite or
         misshapen y, before any device work."""
         y, A_h, A_w = self._separable_args(y, A_h, A_w, tol, ddim, eta, unsupported)
-        spaced = respacing is not None or ddim or eta != 0
         sid = int(self.rng_stream_id)
         m = self._sep_operands(A_h, A_w, tol)
-        yp = []                   # the Python loop's Yp = A+ y, formed at its first step
+        yp = _once(lambda yl: ops.separable_apply_rect(yl, m["Q_h"], m["Q_w"]))      # the Python loop's Yp = A+ y, formed at its first step
 
         def op(x, e, yl, mk, t, tables, seed):
-            if not yp:
-                yp.append(ops.separable_apply_rect(yl, m["Q_h"], m["Q_w"]))
-            ops.p_sample_update_restore_blur_(x, e, m["P_h"], m["P_w"], yp[0], t, **tables, seed=seed, stream_id=sid)
+            ops.p_sample_update_restore_blur_(x, e, m["P_h"], m["P_w"], yp(yl), t, **tables, seed=seed, stream_id=sid)
         return self._ddnm_loop(
-            "restore_separable", y, None, lambda: self._spaced_tables(respacing, ddim, eta) if spaced else (self._tables(), None), x_T,
-            seed, op,
+            "restore_separable", y, None, self._chain_tables(respacing, ddim, eta), x_T, seed, op,
             lambda plan, x, yl, mk, tables, k_start, seed, use: plan.sample_restore_sep_nhwc(
                 x, yl, m["P_h"], m["P_w"], m["Q_h"], m["Q_w"], tables, k_start, seed=seed, stream_id=sid, use_graph=self.use_graph,
                 timesteps=use))
@@ -816,8 +821,7 @@ class DDPM(nn.Module):
         if unsupported:
             raise ValueError(f"{who}: {sorted(unsupported)} not accepted (DDNM runs ancestral or DDIM steps with Philox draws over the "
                              f"whole schedule on an exact measurement of the first m coefficients: no {', '.join(self.DEBLUR_UNSUPPORTED)})")
-        if isinstance(eta, bool) or not isinstance(eta, (int, float, np.integer, np.floating)) or eta < 0 or (eta != 0 and not ddim):
-            raise ValueError(f"{who}: eta = {eta!r} needs ddim=True and eta >= 0")
+        self._eta_arg(who, ddim, eta)
         C, H, W = self.sample_shape
         if not hadamard.size_ok(C, H, W):
             raise ValueError(f"{who}: the image size must be powers of two in [16, 256] with 1 to 8 channels, this model's is {C} x {H} x {W}")
@@ -828,14 +832,11 @@ class DDPM(nn.Module):
             perm = hadamard.cs_perm(N, perm_seed)
         else:
             perm = hadamard.check_perm(perm, N, who)
-        if not torch.is_tensor(y) or y.dim() != 3 or y.shape[0] < 1 or y.shape[1] != C or not y.is_floating_point():
-            raise ValueError(f"{who}: y must be a float [B, {C}, m] tensor, got {tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
+        self._y_arg(who, y, (C, "m"), min_batch=1, finite=False)
         m = int(y.shape[2])
         if m % 4 or not (4 <= m <= N):
             raise ValueError(f"{who}: y's m must be a multiple of 4 in [4, {N}], got {m}")
-        if not bool(torch.isfinite(y).all()):
-            raise ValueError(f"{who}: y must be finite")
-        return y.float(), perm
+        return self._y_arg(who, y, (C, "m")), perm
 
     @torch.no_grad()
     def restore_cs(self, y, perm=None, *, perm_seed=0, respacing=None, ddim=False, eta=0.0, x_T=None, seed=None, **unsupported):
@@ -849,19 +850,13 @@ class DDPM(nn.Module):
         [16, 256], m a multiple of 4 in [4, H W].  solver / noise / early_stop / paste / mask / sigma_y raise ValueError, as do a perm
         that is no permutation, a size off that grid, a bad eta and a non-finite or misshapen y, before any device work."""
         y, perm = self._cs_args(y, perm, perm_seed, ddim, eta, unsupported)
-        spaced = respacing is not None or ddim or eta != 0
         sid = int(self.rng_stream_id)
-        pd = []                   # perm on the model's device, placed at the first use (after _ddnm_loop's device check)
-
-        def perm_dev():
-            if not pd:
-                pd.append(torch.from_numpy(perm).to(self.betas.device))
-            return pd[0]
+        perm_dev = _once(lambda: torch.from_numpy(perm).to(self.betas.device))      # placed at the first use (after _ddnm_loop's device check)
 
         def op(x, e, yl, mk, t, tables, seed):
             ops.p_sample_update_restore_cs_(x, e, yl, perm_dev(), t, **tables, seed=seed, stream_id=sid)
         return self._ddnm_loop(
-            "restore_cs", y, None, lambda: self._spaced_tables(respacing, ddim, eta) if spaced else (self._tables(), None), x_T, seed, op,
+            "restore_cs", y, None, self._chain_tables(respacing, ddim, eta), x_T, seed, op,
             lambda plan, x, yl, mk, tables, k_start, seed, use: plan.sample_restore_cs_nhwc(
                 x, yl, perm_dev(), tables, k_start, seed=seed, stream_id=sid, use_graph=self.use_graph, timesteps=use))
 
@@ -880,21 +875,14 @@ class DDPM(nn.Module):
             raise ValueError(f"{who}: {sorted(unsupported)} not accepted (DDNM runs ancestral or DDIM steps with Philox draws over the "
                              f"whole schedule on an exact, unmasked measurement: no {', '.join(self.DEBLUR_UNSUPPORTED)})")
         k = psf.psf_array(k)      # its own ValueErrors
-        if isinstance(tol, bool) or not isinstance(tol, (int, float, np.integer, np.floating)) or not (0 <= tol < 1):
-            raise ValueError(f"{who}: tol must be a real number in [0, 1), got {tol!r}")
-        if isinstance(eta, bool) or not isinstance(eta, (int, float, np.integer, np.floating)) or eta < 0 or (eta != 0 and not ddim):
-            raise ValueError(f"{who}: eta = {eta!r} needs ddim=True and eta >= 0")
+        self._tol_arg(who, tol)
+        self._eta_arg(who, ddim, eta)
         C, H, W = self.sample_shape
         if not psf.size_ok(C, H, W):
             raise ValueError(f"{who}: the image size must be powers of two in [16, 256] with 1 to 8 channels, this model's is {C} x {H} x {W}")
         if k.shape[0] > H or k.shape[1] > W:
             raise ValueError(f"{who}: a {k.shape[0]} x {k.shape[1]} point-spread function does not fit a {H} x {W} image")
-        if not torch.is_tensor(y) or y.dim() != 4 or y.shape[0] < 1 or list(y.shape[1:]) != [C, H, W] or not y.is_floating_point():
-            raise ValueError(f"{who}: y must be a float [B, {C}, {H}, {W}] tensor, got "
-                             f"{tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
-        if not bool(torch.isfinite(y).all()):
-            raise ValueError(f"{who}: y must be finite")
-        return y.float(), k
+        return self._y_arg(who, y, (C, H, W), min_batch=1), k
 
     @torch.no_grad()
     def deconvolve(self, y, psf, *, tol=blur.DEFAULT_TOL, respacing=None, ddim=False, eta=0.0, x_T=None, seed=None, **unsupported):
@@ -908,21 +896,15 @@ class DDPM(nn.Module):
         two in [16, 256].  solver / noise / early_stop / paste / mask / sigma_y raise ValueError, as do an unknown preset, a bad PSF,
         tol or eta and a non-finite or misshapen y, before any device work."""
         y, k = self._deconvolve_args(y, psf, tol, ddim, eta, unsupported)
-        spaced = respacing is not None or ddim or eta != 0
         sid = int(self.rng_stream_id)
-        m, yp = [], []            # the operands on the model's device and the Python loop's Yp = A+ y, made at the first use
-
-        def operands():
-            if not m:
-                m.append(self._psf_operands(k, tol))
-            return m[0]
+        # the operands on the model's device and the Python loop's Yp = A+ y, made at the first use
+        operands = _once(lambda: self._psf_operands(k, tol))
+        yp = _once(lambda yl: ops.circular_conv(yl, operands()["P"]))
 
         def op(x, e, yl, mk, t, tables, seed):
-            if not yp:
-                yp.append(ops.circular_conv(yl, operands()["P"]))
-            ops.p_sample_update_restore_fft_(x, e, operands()["mask"], yp[0], t, **tables, seed=seed, stream_id=sid)
+            ops.p_sample_update_restore_fft_(x, e, operands()["mask"], yp(yl), t, **tables, seed=seed, stream_id=sid)
         return self._ddnm_loop(
-            "deconvolve", y, None, lambda: self._spaced_tables(respacing, ddim, eta) if spaced else (self._tables(), None), x_T, seed, op,
+            "deconvolve", y, None, self._chain_tables(respacing, ddim, eta), x_T, seed, op,
             lambda plan, x, yl, mk, tables, k_start, seed, use: plan.sample_restore_fft_nhwc(
                 x, yl, operands()["mask"], operands()["P"], tables, k_start, seed=seed, stream_id=sid, use_graph=self.use_graph,
                 timesteps=use))
@@ -946,33 +928,28 @@ class DDPM(nn.Module):
         if ddim and eta == 0:
             raise ValueError("deconvolve_noisy: sigma_y > 0 needs a chain that draws (ancestral steps, or ddim with eta > 0): with eta = 0 "
                              "every row's lam is 0 and nothing would be constrained")
-        spaced = respacing is not None or ddim or eta != 0
         sid = int(self.rng_stream_id)
         C, H, W = self.sample_shape
-        get_tables = lambda: self._spaced_tables(respacing, ddim, eta) if spaced else (self._tables(), None)
-        m, yh = [], []            # the operands on the model's device and the Python loop's spectrum of A+ y, made at the first use
 
+        @_once                    # the operands on the model's device, made at the first use
         def operands(tables):
-            if not m:
-                from . import psf as P_
-                noisy = self._cached_tables(
-                    ('psf_noisy', k.tobytes(), k.shape, float(tol), sigma_y, respacing, bool(ddim), float(eta)),
-                    lambda: ({n: torch.from_numpy(v) for n, v in zip(("gain", "nsc"), P_.psf_noisy_operands(k, H, W, tol, sigma_y, tables["c1"]))},
-                             None))[0]
-                m.append(dict(self._psf_operands(k, tol), **noisy))
-            return m[0]
+            from . import psf as P_
+            noisy = self._cached_tables(
+                ('psf_noisy', k.tobytes(), k.shape, float(tol), sigma_y, respacing, bool(ddim), float(eta)),
+                lambda: ({n: torch.from_numpy(v) for n, v in zip(("gain", "nsc"), P_.psf_noisy_operands(k, H, W, tol, sigma_y, tables["c1"]))},
+                         None))[0]
+            return dict(self._psf_operands(k, tol), **noisy)
+        yh = _once(lambda yl, o: ops.circular_spectrum(yl, o["P"]))      # the Python loop's spectrum of A+ y, likewise
 
         def op(x, e, yl, mk, t, tables, seed):
             o = operands(tables)
-            if not yh:
-                yh.append(ops.circular_spectrum(yl, o["P"]))
-            ops.p_sample_update_restore_fft_noisy_(x, e, o["mask"], o["gain"], o["nsc"], yh[0], t, **tables, seed=seed, stream_id=sid)
+            ops.p_sample_update_restore_fft_noisy_(x, e, o["mask"], o["gain"], o["nsc"], yh(yl, o), t, **tables, seed=seed, stream_id=sid)
 
         def chain(plan, x, yl, mk, tables, k_start, seed, use):
             o = operands(tables)
             plan.sample_restore_fft_noisy_nhwc(x, yl, o["mask"], o["P"], o["gain"], o["nsc"], tables, k_start, seed=seed, stream_id=sid,
                                                use_graph=self.use_graph, timesteps=use)
-        return self._ddnm_loop("deconvolve_noisy", y, None, get_tables, x_T, seed, op, chain)
+        return self._ddnm_loop("deconvolve_noisy", y, None, self._chain_tables(respacing, ddim, eta), x_T, seed, op, chain)
 
     @torch.no_grad()
     def reconstruct(self, x, n):

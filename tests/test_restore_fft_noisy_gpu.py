@@ -430,6 +430,34 @@ def test_noisy_deconvolution_and_ancestral_chains_share_a_workspace(tiny, data, 
         assert lib.ddk_sampler_release_workspace(plan.handle, L.ptr(ws)) == 0
 
 
+def test_the_five_plane_wide_kinds_in_rotation_equal_each_alone(data):
+    """deblur, restore_separable, restore_cs, deconvolve and deconvolve_noisy in rotation on one model and plan, in two orders: each
+    result equals, bit for bit, that of the same call made alone on a freshly built model (every call stages its own operands and
+    the graph key tells the kinds apart, whichever kind used the workspace before)"""
+    from models import DDPM, Unet
+    from models.diffusion import blur
+    y, x_T = data
+    yd = y.to(DEV)
+    A = blur.resize_matrix(16, 2)
+    y_sep = (0.25 * syn.synthetic_normal((2, 3, 8, 8), "rotation.sep")).to(DEV)
+    y_cs = (0.25 * syn.synthetic_normal((2, 3, 100), "rotation.cs")).to(DEV)
+    kw = dict(respacing="8", x_T=x_T, seed=SEED)
+    calls = {"deblur": lambda m: m.deblur(yd, "gauss", **kw),
+             "separable": lambda m: m.restore_separable(y_sep, A, A, **kw),
+             "cs": lambda m: m.restore_cs(y_cs, perm_seed=3, **kw),
+             "deconvolve": lambda m: m.deconvolve(yd, PSF_TINY, **kw),
+             "deconvolve_noisy": lambda m: m.deconvolve_noisy(yd, PSF_TINY, sigma_y=SY, **kw)}
+    fresh = lambda: det_load(DDPM(CFG, Unet(CFG), DEV, 3)).to(DEV).eval()
+    alone = {name: call(fresh()) for name, call in calls.items()}
+    outs = list(alone.values())
+    assert all(torch.isfinite(v).all() for v in outs) and all(not torch.equal(a, b) for i, a in enumerate(outs) for b in outs[i + 1:])
+    m = fresh()
+    names = list(calls)
+    for name in 2 * names + 2 * [names[i] for i in (4, 2, 0, 3, 1)]:
+        got = calls[name](m)
+        assert torch.equal(got, alone[name]), (name, float((got - alone[name]).abs().max()))
+
+
 def test_chain_faults(tiny):
     """the chain entry: injected noise, a null operand, misalignment, a shape the kind does not take and a short workspace"""
     from ddk import lib as L
