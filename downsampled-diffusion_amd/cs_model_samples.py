@@ -19,37 +19,24 @@ Writes ``{saved_model}_cs_r{ratio}_p{perm_seed}_{spec}.npy`` through the samplin
 measurements it started from.  One process, one GPU.
 """
 import argparse
-import json
-import os
-import time
 
 import numpy as np
 import torch
 
 from ddk import ops
-from models import DDPM, Unet
 from models.diffusion import hadamard
-from utils import CHECKPOINT_DIR, SAMPLE_DIR, OutputStage, get_color_channels, get_model_state_dict, load_checkpoint_file
-from utils import synthetic as syn
+from utils import sampling_cli as cli
 
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description="Reconstruct images from Walsh-Hadamard measurements with a trained DDPM checkpoint (DDNM).")
-    ap.add_argument("--saved_model", default="celeba_x2")
-    ap.add_argument("--synthetic", default=None, help="JSON config file: use closed-form synthetic weights, no checkpoint")
+    cli.add_chain_flags(ap)
     ap.add_argument("--images", required=True, help="float32 .npy [N, C, m] of measurements, or uint8 [N, H, W, C] images with --measure_input")
     ap.add_argument("--ratio", type=float, default=0.25, help="sampling ratio in (0, 1]: m = 4 round(ratio H W / 4) coefficients per plane")
     ap.add_argument("--perm_seed", type=int, default=0, help="seed of the pixel permutation")
     ap.add_argument("--measure_input", action="store_true", help="the file holds images: measure them first")
-    ap.add_argument("--timestep_respacing", default="", help='run K of the T steps: "ddimN", "N" or "n1,n2,..." sections')
-    ap.add_argument("--use_ddim", action="store_true", help="DDIM steps instead of ancestral ones")
-    ap.add_argument("--eta", type=float, default=0.0, help="DDIM noise scale (0: deterministic)")
-    ap.add_argument("--batch_size", type=int, default=32)
-    ap.add_argument("--seed", type=int, default=1234, help="base seed: batch g draws from seed + g")
-    ap.add_argument("--out_dir", default=None)
     args = ap.parse_args(argv)
-    if args.eta < 0 or (args.eta != 0.0 and not args.use_ddim):
-        ap.error("--eta needs --use_ddim and a value >= 0")
+    cli.check_chain_flags(ap, args, "eta")
     if not (0 < args.ratio <= 1):
         ap.error("--ratio must be in (0, 1]")
     if args.perm_seed < 0:
@@ -63,63 +50,34 @@ def main():
     args = parse_args()
     device = "cuda:0"
     torch.cuda.set_device(0)
-    if args.synthetic:
-        with open(args.synthetic) as f:
-            config = json.load(f)
-        model_state_dict = None
-    else:
-        save_data = load_checkpoint_file(os.path.join(CHECKPOINT_DIR, f"{args.saved_model}.pt"))
-        model_state_dict = get_model_state_dict(save_data)
-        config = save_data["config"]
-    config["batch_size"] = args.batch_size
-    color_channels = get_color_channels(config["dataset"])
-    if config["model"] != "ddpm":
-        raise SystemExit(f"compressed sensing needs a pixel model (ddpm), this checkpoint is a {config['model']}: a transform of a latent is "
-                         "not a transform of the image")
-    model = DDPM(config, Unet(config), device, color_channels)
-    if model_state_dict is None:
-        model_state_dict = syn.fill_state_dict(model.state_dict(), skip=syn.SCHEDULE_KEYS)
-    model.load_state_dict(model_state_dict)
-    model = model.to(device).eval()
-    model.rng_stream_id = 0
+    model, config, c, _ = cli.load_model(args.saved_model, args.synthetic, args.batch_size, device, pixel_only=(
+        "compressed sensing needs a pixel model (ddpm), this checkpoint is a {model}: a transform of a latent is not a transform of the image"))
 
-    c, size = color_channels, int(config["image_size"])
+    size = int(config["image_size"])
     if not hadamard.size_ok(c, size, size):
         raise SystemExit(f"compressed sensing needs an image size that is a power of two in [16, 256], this model's is {size}")
     N = size * size
     m = hadamard.cs_rows(args.ratio, N)
     perm = hadamard.cs_perm(N, args.perm_seed)
-    data = np.load(args.images)
     if args.measure_input:
-        if data.dtype != np.uint8 or data.ndim != 4 or data.shape[1:] != (size, size, c):
-            raise SystemExit(f"--images: expected uint8 [N, {size}, {size}, {c}] with --measure_input, got {data.dtype} {data.shape}")
-        x_all = torch.from_numpy(data.astype(np.float32)) / 255 * 2 - 1          # NHWC
+        x_all = cli.u8_to_unit(cli.load_uint8_images(args.images, ((size, size, c),), expected=f"[N, {size}, {size}, {c}] with --measure_input"))
         pd = torch.from_numpy(perm).to(device)
-        y_all = torch.cat([ops.hadamard_measure(x_all[i:i + args.batch_size].to(device).contiguous(), pd, m).cpu()
+        y_all = torch.cat([ops.hadamard_measure(x_all[i:i + args.batch_size].to(device).contiguous(), pd, m).cpu()          # (x_all is NHWC)
                            for i in range(0, x_all.shape[0], args.batch_size)])
     else:
+        data = np.load(args.images)
         if data.dtype.kind != "f" or data.ndim != 3 or data.shape[1:] != (c, m):
             raise SystemExit(f"--images: expected float [N, {c}, {m}] measurements (ratio {args.ratio:g} of {N}), got {data.dtype} {data.shape}")
         y_all = torch.from_numpy(data.astype(np.float32))
     n = y_all.shape[0]
 
-    spec = (args.timestep_respacing.replace(",", "-") or "full") + (f"_ddim_eta{args.eta:g}" if args.use_ddim else "")
-    kw = dict(respacing=args.timestep_respacing or None, ddim=args.use_ddim, eta=args.eta)
+    spec = cli.chain_spec(args)
+    kw = cli.chain_kwargs(args)
     print(f"Reconstructing {n} images from {m} of {N} coefficients per plane ({spec} steps) with {args.saved_model}.")
-    stage = OutputStage()
-    t0 = time.time()
-    for g, i in enumerate(range(0, n, args.batch_size)):
-        torch.manual_seed(args.seed + g)          # x_T and the Philox key of batch g
-        stage.submit(model.restore_cs(y_all[i:i + args.batch_size].to(device), perm, **kw))
-    batches = stage.finish()
-    torch.cuda.synchronize()
-    print(f"Total time: {time.time() - t0:.2f} s")
+    restored = cli.run_batches(n, args.batch_size, args.seed, lambda i: model.restore_cs(y_all[i:i + args.batch_size].to(device), perm, **kw))
 
-    out_dir = args.out_dir or SAMPLE_DIR
-    os.makedirs(out_dir, exist_ok=True)
-    base = os.path.join(out_dir, f"{args.saved_model}_cs_r{args.ratio:g}_p{args.perm_seed}_{spec}")
-    np.save(base + ".npy", np.concatenate(batches).astype(np.float32), allow_pickle=False)
-    np.save(base + "_measurements.npy", y_all.numpy().astype(np.float32), allow_pickle=False)
+    base = cli.save_outputs(args.out_dir, f"{args.saved_model}_cs_r{args.ratio:g}_p{args.perm_seed}_{spec}", restored, "_measurements",
+                            y_all.numpy().astype(np.float32))
     print(f"Reconstructions saved to {base}.npy, measurements to {base}_measurements.npy")
 
 

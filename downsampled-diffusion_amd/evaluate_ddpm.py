@@ -19,21 +19,18 @@ printed as null.  Extensions:
 """
 import argparse
 import json
-import os
 import time
 
 import torch
 
-from models import DDPM, DownsampleDDPM, Unet
-from utils import (CHECKPOINT_DIR, DATA_DIR, compute_test_losses, get_color_channels, get_dataloader, get_model_state_dict,
-                   load_checkpoint_file)
+from utils import DATA_DIR, compute_test_losses, get_dataloader
 from utils.sample_metrics import extended_sample_metrics, sample_metrics
-from utils import synthetic as syn
+from utils.sampling_cli import load_model
 
 SAMPLE_METRICS = ('is', 'fid', 'sfid', 'precision', 'recall')
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description="Test-set likelihood (VLB, L_simple) of a trained DDPM / dDDPM checkpoint.")
     ap.add_argument("--saved_model", default="celeba_x2")
     ap.add_argument("--fid_samples", type=int, default=50000, help="kept for the reference's interface (sample metrics are out of scope)")
@@ -48,49 +45,25 @@ def main():
     ap.add_argument("--kid_subsets", type=int, default=100, help="number of KID subsets")
     ap.add_argument("--kid_subset_size", type=int, default=1000, help="rows per KID subset (clamped to the smaller set)")
     ap.add_argument("--density_coverage", action="store_true", help="also report density and coverage (Naeem et al. 2020, k = 5)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if (args.sample_acts is None) != (args.ref_acts is None):
         ap.error("--sample_acts and --ref_acts go together")
     if (args.kid or args.density_coverage) and args.sample_acts is None:
         ap.error("--kid and --density_coverage need --sample_acts and --ref_acts")
     if args.kid_subsets < 1 or args.kid_subset_size < 2:
         ap.error("--kid_subsets must be at least 1 and --kid_subset_size at least 2")
+    return args
 
+
+def main():
+    args = parse_args()
     device = 'cuda'
-    step = 0
-    if args.synthetic:
-        with open(args.synthetic) as f:
-            config = json.load(f)
-        model_state_dict = None
-    else:
-        save_data = load_checkpoint_file(os.path.join(CHECKPOINT_DIR, f'{args.saved_model}.pt'))
-        model_state_dict = get_model_state_dict(save_data)
-        config = save_data['config']
-        step = save_data.get('step', 0)
-    # fix config if missing (reference evaluate_ddpm.py:24-28)
-    if config['model'] == 'dddpm' and 'force_latent' not in config:
-        config['force_latent'] = False
-    if args.batch_size is not None:
-        config['batch_size'] = args.batch_size
-
-    test_loader = get_dataloader(config, data_root=DATA_DIR, device=device, train=False)[0]
-
     print(f'\nLoading model checkpoint {args.saved_model}')
+    # (an old dDDPM config gets its force_latent, reference evaluate_ddpm.py:24-28; the batch size stays the checkpoint's unless given)
+    model, config, _, step = load_model(args.saved_model, args.synthetic, args.batch_size, device, default_force_latent=True)
     print(f'Trained for {step} steps with configuration dict:')
     print(json.dumps(config, sort_keys=False, indent=4, default=str) + '\n')
-    latent_model = Unet(config)
-    color_channels = get_color_channels(config['dataset'])
-    if config['model'] == 'ddpm':
-        model = DDPM(config, latent_model, device, color_channels)
-    elif config['model'] == 'dddpm':
-        model = DownsampleDDPM(config, latent_model, device, color_channels)
-    else:
-        raise NotImplementedError(config['model'])
-    if model_state_dict is None:
-        model_state_dict = syn.fill_state_dict(model.state_dict(), skip=syn.SCHEDULE_KEYS)
-    model.load_state_dict(model_state_dict)
-    model = model.to(device)
-    model.eval()
+    test_loader = get_dataloader(config, data_root=DATA_DIR, device=device, train=False)[0]
 
     ### COMPUTE METRICS ###
     print(f'\nComputing test losses over {args.max_batches if args.max_batches is not None else "all"} test batches')

@@ -60,19 +60,19 @@ one GPU.
 """
 import argparse
 import json
-import os
 import time
 
 import numpy as np
 import torch
 
+from utils import sampling_cli as cli
 from utils.restoration_metrics import BLUR_KERNELS, CS_TASK, DEBLUR_TASK, DECONV_NOISY_TASK, DECONV_TASK, DOWNSAMPLES, GRAY_WEIGHTS, MASKS, METHODS, TASKS, evaluate_restoration, load_mask, report, to_u8
 
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description="PSNR / SSIM of RePaint inpainting or DDNM super-resolution against ground truth.")
-    ap.add_argument("--saved_model", default="celeba_x2")
-    ap.add_argument("--synthetic", default=None, help="JSON config file: use closed-form synthetic weights, no checkpoint")
+    cli.add_chain_flags(ap, solver=True, out_dir=False, prefix="ddnm: ", respacing_help='run K of the T steps: "N", "n1,n2,..." sections or (sr) "ddimN"',
+                        sigma_y="ddnm: add N(0, sigma_y^2) noise to the measurement ([-1, 1] scale) and restore with DDNM+; not with --dpm_solver")
     ap.add_argument("--images", default=None, help="uint8 [N, H, W, C] .npy of the model's size (default: the dataset's test split)")
     ap.add_argument("--task", required=True, choices=(*TASKS, DEBLUR_TASK, CS_TASK, DECONV_TASK, DECONV_NOISY_TASK))
     ap.add_argument("--mask", default=None, help=f"one of {', '.join(MASKS)} or a .npy file of {{0, 1}} (1 = known); inpaint: default "
@@ -86,18 +86,9 @@ def parse_args(argv=None):
     ap.add_argument("--psf", default=None, help="deconv: the 2-D point-spread function, diag, disk or a .npy file (required there)")
     ap.add_argument("--ratio", type=float, default=None, help="cs: the sampling ratio in (0, 1] (required there)")
     ap.add_argument("--perm_seed", type=int, default=None, help="cs: seed of the pixel permutation (default 0)")
-    ap.add_argument("--timestep_respacing", default="", help='run K of the T steps: "N", "n1,n2,..." sections or (sr) "ddimN"')
-    ap.add_argument("--use_ddim", action="store_true", help="sr: DDIM steps instead of ancestral ones")
-    ap.add_argument("--eta", type=float, default=0.0, help="sr: DDIM noise scale (0: deterministic)")
-    ap.add_argument("--dpm_solver", action="store_true",
-                    help='ddnm: DPM-Solver++(2M) steps over the --timestep_respacing grid (e.g. "logsnr20"); not with --use_ddim / --eta')
-    ap.add_argument("--sigma_y", type=float, default=0.0,
-                    help="ddnm: add N(0, sigma_y^2) noise to the measurement ([-1, 1] scale) and restore with DDNM+; not with --dpm_solver")
     ap.add_argument("--jump_length", type=int, default=10, help="inpaint: RePaint jump length")
     ap.add_argument("--jump_n_sample", type=int, default=10, help="inpaint: RePaint resamplings per jump")
-    ap.add_argument("--batch_size", type=int, default=32)
     ap.add_argument("--max_batches", type=int, default=None, help="stop after this many batches of images")
-    ap.add_argument("--seed", type=int, default=1234, help="base seed: batch g draws from seed + g")
     ap.add_argument("--json", default=None, help="also write the result to this file")
     args = ap.parse_args(argv)
     if args.batch_size < 1 or (args.max_batches is not None and args.max_batches < 1):
@@ -176,17 +167,9 @@ def parse_args(argv=None):
             args.scale = 4
         if args.mask is None:
             args.mask = "center"
-    if not np.isfinite(args.sigma_y) or args.sigma_y < 0:
-        ap.error("--sigma_y must be a finite number >= 0")
+    cli.check_chain_flags(ap, args, "sigma_y")
     if args.method == "ddnm":
-        if args.dpm_solver and (args.use_ddim or args.eta != 0.0):
-            ap.error("--dpm_solver is its own deterministic update: it cannot be combined with --use_ddim or --eta")
-        if args.sigma_y != 0.0 and args.dpm_solver:
-            ap.error("--sigma_y and --dpm_solver are exclusive (the solver draws nothing, so there is no variance to trade)")
-        if args.sigma_y != 0.0 and args.use_ddim and args.eta == 0.0:
-            ap.error("--sigma_y needs a chain that draws: ancestral steps, or --use_ddim with --eta > 0")
-        if args.eta < 0 or (args.eta != 0.0 and not args.use_ddim):
-            ap.error("--eta needs --use_ddim and a value >= 0")
+        cli.check_chain_flags(ap, args, "solver sigma_y_solver sigma_y_draws eta")
         if args.jump_length != ap.get_default("jump_length") or args.jump_n_sample != ap.get_default("jump_n_sample"):
             ap.error("--jump_length and --jump_n_sample belong to --method repaint (DDNM has no jumps)")
     else:
@@ -199,7 +182,8 @@ def parse_args(argv=None):
 
 def chain_options(args):
     """the task's keywords for evaluate_restoration, also the chain settings the result records"""
-    kw = dict(respacing=args.timestep_respacing or None)
+    steps = cli.chain_kwargs(args)
+    kw = dict(respacing=steps.pop("respacing"))
     if args.task in ("sr", "colorize"):
         kw.update(scale=args.scale)
     if args.task == "colorize":
@@ -213,9 +197,9 @@ def chain_options(args):
     if args.task in (DECONV_TASK, DECONV_NOISY_TASK):
         kw.update(psf=args.psf, tol=args.tol)
     if args.dpm_solver:
-        kw.update(dpm_solver=True)
+        kw.update(dpm_solver=True)                 # (evaluate_restoration's own keyword for chain_kwargs' solver="dpm++2m")
     elif args.method == "ddnm":
-        kw.update(ddim=args.use_ddim, eta=args.eta)
+        kw.update(steps)
     else:
         kw.update(jump_length=args.jump_length, jump_n_sample=args.jump_n_sample)
     if args.sigma_y != 0.0:
@@ -224,33 +208,7 @@ def chain_options(args):
 
 
 def load_model(args, device):
-    from models import DDPM, DownsampleDDPM, Unet
-    from utils import CHECKPOINT_DIR, get_color_channels, get_model_state_dict, load_checkpoint_file
-    from utils import synthetic as syn
-    if args.synthetic:
-        with open(args.synthetic) as f:
-            config = json.load(f)
-        model_state_dict = None
-    else:
-        save_data = load_checkpoint_file(os.path.join(CHECKPOINT_DIR, f"{args.saved_model}.pt"))
-        model_state_dict = get_model_state_dict(save_data)
-        config = save_data["config"]
-    if config["model"] == "dddpm" and "force_latent" not in config:
-        config["force_latent"] = False
-    config["batch_size"] = args.batch_size
-    color_channels = get_color_channels(config["dataset"])
-    if config["model"] == "ddpm":
-        model = DDPM(config, Unet(config), device, color_channels)
-    elif config["model"] == "dddpm":
-        model = DownsampleDDPM(config, Unet(config), device, color_channels)
-    else:
-        raise NotImplementedError(config["model"])
-    if model_state_dict is None:
-        model_state_dict = syn.fill_state_dict(model.state_dict(), skip=syn.SCHEDULE_KEYS)
-    model.load_state_dict(model_state_dict)
-    model = model.to(device).eval()
-    model.rng_stream_id = 0
-    return model, config, color_channels
+    return cli.load_model(args.saved_model, args.synthetic, args.batch_size, device, default_force_latent=True)[:3]
 
 
 def load_images(args, config, channels):
@@ -258,10 +216,7 @@ def load_images(args, config, channels):
     size = int(config["image_size"])
     limit = None if args.max_batches is None else args.max_batches * args.batch_size
     if args.images:
-        imgs = np.load(args.images)
-        if imgs.dtype != np.uint8 or imgs.ndim != 4 or imgs.shape[1:] != (size, size, channels):
-            raise SystemExit(f"--images: expected uint8 [N, {size}, {size}, {channels}], got {imgs.dtype} {imgs.shape}")
-        return imgs[:limit]
+        return cli.load_uint8_images(args.images, ((size, size, channels),))[:limit]
     from utils import DATA_DIR, get_dataloader
     loader = get_dataloader(config, data_root=DATA_DIR, device="cpu", train=False)[0]
     out = []

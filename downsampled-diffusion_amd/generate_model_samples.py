@@ -26,45 +26,29 @@ import time
 import numpy as np
 import torch
 
-from models import DDPM, DownsampleDDPM, Unet
 from parallel import barrier, broadcast_module_, init_from_env, main_rank_does, shard_sizes
-from utils import (CHECKPOINT_DIR, SAMPLE_DIR, SAMPLE_LATENT_DIR, OutputStage, get_color_channels, get_model_state_dict,
-                   load_checkpoint_file, merge_rank_shards)
-from utils import synthetic as syn
+from utils import SAMPLE_DIR, SAMPLE_LATENT_DIR, OutputStage, merge_rank_shards
+from utils import sampling_cli as cli
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description="Generate samples from a trained DDPM / dDDPM checkpoint.")
+    cli.add_chain_flags(ap, batch_size=192, solver=True, respacing_help='sample K of the T steps: "ddimN", "N" or "n1,n2,..." sections')
+    ap.add_argument("--fid_samples", type=int, default=50000)
+    ap.add_argument("--sample_every", type=int, default=1)
+    ap.add_argument("--early_stop", type=int, default=None)
+    ap.add_argument("--keep_shards", action="store_true", help="keep the per-rank .rank{r}.npy files after the merge")
+    args = ap.parse_args(argv)
+    cli.check_chain_flags(ap, args, "solver eta")
+    return args
 
 
 def main():
-    ap = argparse.ArgumentParser(description="Generate samples from a trained DDPM / dDDPM checkpoint.")
-    ap.add_argument("--saved_model", default="celeba_x2")
-    ap.add_argument("--fid_samples", type=int, default=50000)
-    ap.add_argument("--batch_size", type=int, default=192)
-    ap.add_argument("--sample_every", type=int, default=1)
-    ap.add_argument("--early_stop", type=int, default=None)
-    ap.add_argument("--synthetic", default=None, help="JSON config file: use closed-form synthetic weights, no checkpoint")
-    ap.add_argument("--out_dir", default=None)
-    ap.add_argument("--seed", type=int, default=1234, help="base seed: batch g of the job draws from seed + g")
-    ap.add_argument("--keep_shards", action="store_true", help="keep the per-rank .rank{r}.npy files after the merge")
-    ap.add_argument("--timestep_respacing", default="", help='sample K of the T steps: "ddimN", "N" or "n1,n2,..." sections')
-    ap.add_argument("--use_ddim", action="store_true", help="DDIM steps instead of ancestral ones")
-    ap.add_argument("--eta", type=float, default=0.0, help="DDIM noise scale (0: deterministic)")
-    ap.add_argument("--dpm_solver", action="store_true",
-                    help='DPM-Solver++(2M) steps over the --timestep_respacing grid (e.g. "logsnr20"); not with --use_ddim / --eta')
-    args = ap.parse_args()
-    if args.dpm_solver and (args.use_ddim or args.eta != 0.0):
-        ap.error("--dpm_solver is its own deterministic update: it cannot be combined with --use_ddim or --eta")
-    if args.eta < 0 or (args.eta != 0.0 and not args.use_ddim):
-        ap.error("--eta needs --use_ddim and a value >= 0")
+    args = parse_args()
     spaced = bool(args.timestep_respacing) or args.use_ddim or args.eta != 0.0 or args.dpm_solver
-    sample_kw = {}
-    if args.dpm_solver:
-        sample_kw = dict(respacing=args.timestep_respacing or None, solver="dpm++2m")
-    elif spaced:
-        sample_kw = dict(respacing=args.timestep_respacing or None, ddim=args.use_ddim, eta=args.eta)
+    sample_kw = cli.chain_kwargs(args) if spaced else {}
     # full-chain runs keep the reference's file names; spaced runs write beside them
-    suffix = ""
-    if spaced:
-        suffix = "_" + (args.timestep_respacing.replace(",", "-") or "full") + (f"_ddim_eta{args.eta:g}" if args.use_ddim else "")
-        suffix += "_dpmpp2m" if args.dpm_solver else ""
+    suffix = "_" + cli.chain_spec(args) if spaced else ""
 
     rank, world = init_from_env()
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -83,35 +67,11 @@ def main():
     torch.cuda.set_device(local)
     device = f"cuda:{local}"
 
-    step = 0
-    if args.synthetic:
-        with open(args.synthetic) as f:
-            config = json.load(f)
-        model_state_dict = None
-    else:
-        save_data = load_checkpoint_file(os.path.join(CHECKPOINT_DIR, f"{args.saved_model}.pt"))
-        model_state_dict = get_model_state_dict(save_data)
-        config = save_data["config"]
-        step = save_data.get("step", 0)
-    config["batch_size"] = args.batch_size
-
-    latent_model = Unet(config)
-    color_channels = get_color_channels(config["dataset"])
-    if config["model"] == "ddpm":
-        model = DDPM(config, latent_model, device, color_channels)
-    elif config["model"] == "dddpm":
-        model = DownsampleDDPM(config, latent_model, device, color_channels)
-    else:
-        raise NotImplementedError(config["model"])
-    if rank == 0:
-        if model_state_dict is None:
-            model_state_dict = syn.fill_state_dict(model.state_dict(), skip=syn.SCHEDULE_KEYS)
-        model.load_state_dict(model_state_dict)
-    model = model.to(device).eval()
+    # rank 0 fills the weights and broadcasts them once
+    model, config, _, step = cli.load_model(args.saved_model, args.synthetic, args.batch_size, device, fill=rank == 0)
     broadcast_module_(model, src=0)
-    model.rng_stream_id = 0
     if shared_gpu:
-        latent_model.plan().set_option(latent_model.plan().OPT_CLUSTER_GROUPNORM, 0)
+        model.latent_model.plan().set_option(model.latent_model.plan().OPT_CLUSTER_GROUPNORM, 0)
 
     # the job = ceil(fid_samples / batch) batches; rank r takes a contiguous run of them
     bs = config["batch_size"]

@@ -12,6 +12,8 @@ import math
 import numpy as np
 import torch
 
+from .sampling_cli import seeded_batches
+
 MASKS = ("center", "left", "half", "lines")
 TASKS = ("inpaint", "sr", "colorize")
 DEBLUR_TASK = "deblur"          # evaluate_restoration's fourth task (section 3.14), with kernels of its own instead of masks and scales
@@ -134,6 +136,39 @@ def _score(ops, cand_u8, ref_u8, hidden, device):
     return out
 
 
+# ------------------------------------------------------------------ what the task evaluators share
+def _setup(model, images_uint8, batch_size):
+    """(x_all float [N, C, H, W] in [-1, 1], ref uint8 [N, H, W, C], the model's device) of the ground truth"""
+    x_all = from_u8(images_uint8)
+    if x_all.shape[0] < 1 or batch_size < 1:
+        raise ValueError("evaluate_restoration needs at least one image and batch_size >= 1")
+    return x_all, torch.as_tensor(images_uint8).contiguous(), model.betas.device
+
+
+def _unet_forwards(model, chain, method="ddnm"):
+    """UNet forwards per image of the chain that ``chain``'s keywords choose: the number of its steps"""
+    respacing = chain.get("respacing")
+    if "solver" in chain:
+        return len(model._solver_tables(respacing, chain["solver"])[1])
+    if method == "repaint":
+        return len(model._inpaint_tables(respacing, chain.get("jump_length", 10), chain.get("jump_n_sample", 10))[1])
+    if respacing is not None or chain.get("ddim"):
+        return len(model._spaced_tables(respacing, chain.get("ddim", False), chain.get("eta", 0.0))[1])
+    return int(model.timesteps)
+
+
+def _restore_all(n, batch_size, seed, restore, images):
+    """(x_out, images with "restored" in front): restore(i) over the seeded batches, as the sampling CLIs run them"""
+    x_out = torch.cat([out.float().cpu() for out in seeded_batches(n, batch_size, seed, restore)])
+    return x_out, dict(restored=to_u8(x_out), **images)
+
+
+def _result(images, ref, hidden, device, method, extra):
+    from ddk import ops
+    methods = {name: _score(ops, img, ref, hidden, device) for name, img in images.items()}
+    return dict(n_images=ref.shape[0], method=method, methods=methods, images={k: v.numpy() for k, v in images.items()}, **extra)
+
+
 @torch.no_grad()
 def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234, mask="center", scale=None, method=None, sr_mask=None,
                          dpm_solver=False, sigma_y=0.0, downsample="mean", **chain):
@@ -194,7 +229,6 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
     "method" and "unet_forwards" (UNet forwards per image: the chain's steps; the batch shares each forward) are returned too.
     Returns {"n_images", "methods": {name: {"psnr": [N], "ssim": [N], ...}}, "images": {name: uint8 [N, H, W, C]}} and, for "sr",
     "consistency" / "consistency_u8" [N]; "restored" is the model's entry."""
-    from ddk import ops
     if downsample not in DOWNSAMPLES:
         raise ValueError(f"unknown downsample {downsample!r}: one of {DOWNSAMPLES}")
     if downsample != "mean" and (task != "sr" or sr_mask is not None or dpm_solver or sigma_y):
@@ -238,12 +272,8 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
                                   sr_mask=sr_mask, dpm_solver=dpm_solver, sigma_y=sigma_y, **chain)
     if "weights" in chain:
         raise ValueError("weights belongs to task 'colorize'")
-    x_all = from_u8(images_uint8)
-    ref = torch.as_tensor(images_uint8).contiguous()
+    x_all, ref, device = _setup(model, images_uint8, batch_size)
     n, c, h, w = x_all.shape
-    if n < 1 or batch_size < 1:
-        raise ValueError("evaluate_restoration needs at least one image and batch_size >= 1")
-    device = model.betas.device
     images, extra, hidden = {}, {}, None
     if method is None:
         method = "repaint" if task == "inpaint" else "ddnm"
@@ -258,12 +288,8 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
         if method != "ddnm" or chain.get("ddim") or chain.get("eta", 0.0) != 0.0:
             raise ValueError("dpm_solver runs DDNM on its own deterministic update: method 'ddnm', no ddim, no eta")
         chain = dict({k: v for k, v in chain.items() if k not in ("ddim", "eta")}, solver="dpm++2m")
-        K = len(model._solver_tables(chain.get("respacing"), "dpm++2m")[1])
-        run = model.restore_solver
-    else:
-        K = len(model._spaced_tables(chain.get("respacing"), chain.get("ddim", False), chain.get("eta", 0.0))[1]) \
-            if chain.get("respacing") is not None or chain.get("ddim") else int(model.timesteps)
-        run = model.restore
+    run = model.restore_solver if dpm_solver else model.restore
+    K = _unet_forwards(model, chain, method)
     noise = None
     if sigma_y:
         run = lambda y, m, s, **kw: model.restore_noisy(y, m, s, sigma_y=sigma_y, **kw)
@@ -274,11 +300,9 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
             m_all = m_all.amin(dim=1, keepdim=True)
             x_meas = x_all + noise(x_all) if sigma_y else x_all
             restore = lambda i: run(x_meas[i:i + batch_size].to(device), m_all[i:i + batch_size, 0].to(device), 1, **chain)
-            extra["unet_forwards"] = K
         else:
             restore = lambda i: model.inpaint(x_all[i:i + batch_size].to(device), m_all[i:i + batch_size].to(device), **chain)
-            extra["unet_forwards"] = len(model._inpaint_tables(chain.get("respacing"), chain.get("jump_length", 10),
-                                                               chain.get("jump_n_sample", 10))[1])
+        extra["unet_forwards"] = K
         images["mean_fill"] = to_u8(mean_fill(x_meas if sigma_y else x_all, m_all))
         hidden = (m_all.amin(dim=1) == 0).to(torch.uint8).contiguous()
     else:
@@ -309,13 +333,7 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
             y_base = mean_fill(y_meas, my_all)            # the baselines see the same holes
         images["replicate"] = to_u8(replicate(y_base, scale))
         images["bicubic"] = to_u8(bicubic(y_base, scale))
-    outs = []
-    for g, i in enumerate(range(0, n, batch_size)):
-        torch.manual_seed(seed + g)               # x_T and the Philox key of batch g
-        out = restore(i)
-        outs.append((out[0] if isinstance(out, tuple) else out).float().cpu())      # a dDDPM returns (x_out, z)
-    x_out = torch.cat(outs)
-    images = dict(restored=to_u8(x_out), **images)
+    x_out, images = _restore_all(n, batch_size, seed, restore, images)
     if sigma_y:
         # the result is not meant to reproduce the noisy measurement: its RMS distance from the CLEAN one over the measured pixels
         s1, y_clean = (1, x_all) if task == "inpaint" else (scale, y_all)
@@ -328,19 +346,14 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
         meas = 1.0 if my_all is None else my_all      # the constraint holds where y is measured
         extra["consistency"] = (((degrade(x_out) - y_all) * meas).abs().amax(dim=(1, 2, 3)) * 127.5).double().numpy()
         extra["consistency_u8"] = (((degrade(from_u8(images["restored"])) - y_all) * meas).abs().amax(dim=(1, 2, 3)) * 127.5).double().numpy()
-    methods = {name: _score(ops, img, ref, hidden, device) for name, img in images.items()}
-    return dict(n_images=n, method=method + ("_dpmpp2m" if dpm_solver else "_plus" if sigma_y else ""), methods=methods, images={k: v.numpy() for k, v in images.items()}, **extra)
+    return _result(images, ref, hidden, device, method + ("_dpmpp2m" if dpm_solver else "_plus" if sigma_y else ""), extra)
 
 
 @torch.no_grad()
 def _evaluate_colorize(model, images_uint8, *, batch_size, seed, scale, method, sr_mask, dpm_solver, sigma_y, weights="mean", **chain):
     """evaluate_restoration's task "colorize" (see there)"""
-    from ddk import ops
-    x_all = from_u8(images_uint8)
-    ref = torch.as_tensor(images_uint8).contiguous()
+    x_all, ref, device = _setup(model, images_uint8, batch_size)
     n, c, h, w = x_all.shape
-    if n < 1 or batch_size < 1:
-        raise ValueError("evaluate_restoration needs at least one image and batch_size >= 1")
     if method not in (None, "ddnm") or dpm_solver:
         raise ValueError("task 'colorize' has one method, ddnm on ancestral or DDIM steps (no RePaint, no dpm_solver)")
     if isinstance(sigma_y, bool) or not isinstance(sigma_y, (int, float, np.integer, np.floating)) or not math.isfinite(sigma_y) or sigma_y < 0:
@@ -349,12 +362,10 @@ def _evaluate_colorize(model, images_uint8, *, batch_size, seed, scale, method, 
     scale = int(scale)
     if scale < 1 or h % scale or w % scale:
         raise ValueError(f"scale {scale} must be >= 1 and divide the image size {h} x {w}")
-    device = model.betas.device
     A = lambda x: pool(gray(x, weights), scale) if scale > 1 else gray(x, weights)
     y_all = A(x_all)
     y_meas = y_all + sigma_y * torch.randn(y_all.shape, generator=torch.Generator().manual_seed(seed)) if sigma_y else y_all
-    K = len(model._spaced_tables(chain.get("respacing"), chain.get("ddim", False), chain.get("eta", 0.0))[1]) \
-        if chain.get("respacing") is not None or chain.get("ddim") else int(model.timesteps)
+    K = _unet_forwards(model, chain)
     my_all, y_base = None, y_meas
     if sr_mask is not None:
         hs, ws = h // scale, w // scale
@@ -364,13 +375,9 @@ def _evaluate_colorize(model, images_uint8, *, batch_size, seed, scale, method, 
     images = {"replicate": to_u8(replicate(y_base, scale).expand(-1, 3, -1, -1))}
     if scale > 1:
         images["bicubic"] = to_u8(bicubic(y_base, scale).expand(-1, 3, -1, -1))
-    outs = []
-    for g, i in enumerate(range(0, n, batch_size)):
-        torch.manual_seed(seed + g)               # x_T and the Philox key of batch g
-        mk = None if my_all is None else my_all[i:i + batch_size, 0].to(device)
-        outs.append(model.colorize(y_meas[i:i + batch_size].to(device), mk, scale, weights=weights, sigma_y=sigma_y, **chain).float().cpu())
-    x_out = torch.cat(outs)
-    images = dict(restored=to_u8(x_out), **images)
+    mk = lambda i: None if my_all is None else my_all[i:i + batch_size, 0].to(device)
+    x_out, images = _restore_all(n, batch_size, seed, lambda i: model.colorize(y_meas[i:i + batch_size].to(device), mk(i), scale, weights=weights,
+                                                                               sigma_y=sigma_y, **chain), images)
     meas = torch.ones_like(y_all) if my_all is None else my_all
     extra = dict(unet_forwards=K, weights=weights)
     if sigma_y:
@@ -379,38 +386,24 @@ def _evaluate_colorize(model, images_uint8, *, batch_size, seed, scale, method, 
     else:
         dev = lambda x: (((A(x) - y_all) * meas).abs().amax(dim=(1, 2, 3)) * 127.5).double().numpy()
         extra.update(consistency=dev(x_out), consistency_u8=dev(from_u8(images["restored"])))
-    methods = {name: _score(ops, img, ref, None, device) for name, img in images.items()}
-    return dict(n_images=n, method="ddnm_gray", methods=methods, images={k: v.numpy() for k, v in images.items()}, **extra)
+    return _result(images, ref, None, device, "ddnm_gray", extra)
 
 
 @torch.no_grad()
 def _evaluate_deblur(model, images_uint8, *, batch_size, seed, kernel, tol=3e-2, **chain):
     """evaluate_restoration's task "deblur" (see there)"""
-    from ddk import ops
     from models.diffusion import blur
-    x_all = from_u8(images_uint8)
-    ref = torch.as_tensor(images_uint8).contiguous()
+    x_all, ref, device = _setup(model, images_uint8, batch_size)
     n, c, h, w = x_all.shape
-    if n < 1 or batch_size < 1:
-        raise ValueError("evaluate_restoration needs at least one image and batch_size >= 1")
-    device = model.betas.device
     A_h, A_w, Q_h, Q_w = blur.blur_operands(kernel, h, w, tol)[:4]
     sep = lambda x, L, R: torch.einsum("ih,bchw,jw->bcij", L, x, R)
     y_all = sep(x_all, A_h, A_w)
-    K = len(model._spaced_tables(chain.get("respacing"), chain.get("ddim", False), chain.get("eta", 0.0))[1]) \
-        if chain.get("respacing") is not None or chain.get("ddim") else int(model.timesteps)
     images = {"blurred": to_u8(y_all), "pinv": to_u8(sep(y_all, Q_h, Q_w).clamp(-1, 1))}
-    outs = []
-    for g, i in enumerate(range(0, n, batch_size)):
-        torch.manual_seed(seed + g)               # x_T and the Philox key of batch g
-        outs.append(model.deblur(y_all[i:i + batch_size].to(device), kernel, tol=tol, **chain).float().cpu())
-    x_out = torch.cat(outs)
-    images = dict(restored=to_u8(x_out), **images)
+    x_out, images = _restore_all(n, batch_size, seed, lambda i: model.deblur(y_all[i:i + batch_size].to(device), kernel, tol=tol, **chain), images)
     dev = lambda x: ((sep(x, A_h, A_w) - y_all).abs().amax(dim=(1, 2, 3)) * 127.5).double().numpy()
-    extra = dict(unet_forwards=K, kernel=kernel if isinstance(kernel, str) else "custom", tol=float(tol), consistency=dev(x_out),
-                 consistency_u8=dev(from_u8(images["restored"])))
-    methods = {name: _score(ops, img, ref, None, device) for name, img in images.items()}
-    return dict(n_images=n, method="ddnm_blur", methods=methods, images={k: v.numpy() for k, v in images.items()}, **extra)
+    extra = dict(unet_forwards=_unet_forwards(model, chain), kernel=kernel if isinstance(kernel, str) else "custom", tol=float(tol),
+                 consistency=dev(x_out), consistency_u8=dev(from_u8(images["restored"])))
+    return _result(images, ref, None, device, "ddnm_blur", extra)
 
 
 @torch.no_grad()
@@ -418,33 +411,21 @@ def _evaluate_cs(model, images_uint8, *, batch_size, seed, ratio, perm_seed=0, *
     """evaluate_restoration's task "cs" (see there)"""
     from ddk import ops
     from models.diffusion import hadamard
-    x_all = from_u8(images_uint8)
-    ref = torch.as_tensor(images_uint8).contiguous()
+    x_all, ref, device = _setup(model, images_uint8, batch_size)
     n, c, h, w = x_all.shape
-    if n < 1 or batch_size < 1:
-        raise ValueError("evaluate_restoration needs at least one image and batch_size >= 1")
     if not hadamard.size_ok(c, h, w):
         raise ValueError(f"task 'cs' needs H and W powers of two in [16, 256] and 1 to 8 channels, got {c} x {h} x {w}")
-    device = model.betas.device
     m = hadamard.cs_rows(ratio, h * w)
     perm = hadamard.cs_perm(h * w, perm_seed)
     pd = torch.from_numpy(perm).to(device)
     batches = lambda f, v: torch.cat([f(v[i:i + batch_size].to(device).contiguous()).cpu() for i in range(0, n, batch_size)])
     A = lambda x: batches(lambda v: ops.hadamard_measure(ops.nchw_to_nhwc(v), pd, m), x)
     y_all = A(x_all)
-    K = len(model._spaced_tables(chain.get("respacing"), chain.get("ddim", False), chain.get("eta", 0.0))[1]) \
-        if chain.get("respacing") is not None or chain.get("ddim") else int(model.timesteps)
     images = {"adjoint": to_u8(batches(lambda v: ops.nhwc_to_nchw(ops.hadamard_adjoint(v, pd, h, w)), y_all).clamp(-1, 1))}
-    outs = []
-    for g, i in enumerate(range(0, n, batch_size)):
-        torch.manual_seed(seed + g)               # x_T and the Philox key of batch g
-        outs.append(model.restore_cs(y_all[i:i + batch_size].to(device), perm, **chain).float().cpu())
-    x_out = torch.cat(outs)
-    images = dict(restored=to_u8(x_out), **images)
-    extra = dict(unet_forwards=K, ratio=float(ratio), perm_seed=int(perm_seed), m=m,
+    x_out, images = _restore_all(n, batch_size, seed, lambda i: model.restore_cs(y_all[i:i + batch_size].to(device), perm, **chain), images)
+    extra = dict(unet_forwards=_unet_forwards(model, chain), ratio=float(ratio), perm_seed=int(perm_seed), m=m,
                  consistency=(A(x_out) - y_all).abs().amax(dim=(1, 2)).double().numpy())
-    methods = {name: _score(ops, img, ref, None, device) for name, img in images.items()}
-    return dict(n_images=n, method="ddnm_cs", methods=methods, images={k: v.numpy() for k, v in images.items()}, **extra)
+    return _result(images, ref, None, device, "ddnm_cs", extra)
 
 
 @torch.no_grad()
@@ -452,16 +433,12 @@ def _evaluate_deconv(model, images_uint8, *, batch_size, seed, psf, tol=3e-2, si
     """evaluate_restoration's tasks "deconv" and (sigma_y > 0) "deconv_noisy" (see there)"""
     from ddk import ops
     from models.diffusion import psf as P
-    x_all = from_u8(images_uint8)
-    ref = torch.as_tensor(images_uint8).contiguous()
+    x_all, ref, device = _setup(model, images_uint8, batch_size)
     n, c, h, w = x_all.shape
-    if n < 1 or batch_size < 1:
-        raise ValueError("evaluate_restoration needs at least one image and batch_size >= 1")
     if not P.size_ok(c, h, w):
         raise ValueError(f"task 'deconv' needs H and W powers of two in [16, 256] and 1 to 8 channels, got {c} x {h} x {w}")
     name = psf if isinstance(psf, str) else "custom"
     k = P.psf_array(np.load(psf) if isinstance(psf, str) and psf.endswith(".npy") else psf)
-    device = model.betas.device
     Kd, Pd, Md, _ = (torch.from_numpy(v).to(device) for v in P.psf_operands(k, h, w, tol))
     Md = torch.stack([Md, torch.zeros_like(Md)], dim=-1).contiguous()      # the projection A+ A as a multiplier
     batches = lambda S, v: torch.cat([ops.nhwc_to_nchw(ops.circular_conv(ops.nchw_to_nhwc(v[i:i + batch_size].to(device).contiguous()), S)).cpu()
@@ -469,28 +446,20 @@ def _evaluate_deconv(model, images_uint8, *, batch_size, seed, psf, tol=3e-2, si
     y_clean = batches(Kd, x_all)
     y_all = y_clean + sigma_y * torch.randn(y_clean.shape, generator=torch.Generator().manual_seed(seed)) if sigma_y else y_clean
     yp_all = batches(Pd, y_all)
-    K = len(model._spaced_tables(chain.get("respacing"), chain.get("ddim", False), chain.get("eta", 0.0))[1]) \
-        if chain.get("respacing") is not None or chain.get("ddim") else int(model.timesteps)
     images = {"blurred": to_u8(y_all.clamp(-1, 1)), "pinv": to_u8(yp_all.clamp(-1, 1))}
     if sigma_y:
         Kc = P.psf_spectrum(k, h, w)
         Wd = torch.from_numpy(P.interleave(np.conj(Kc) / (np.abs(Kc) ** 2 + sigma_y ** 2))).to(device)
         images["tikhonov"] = to_u8(batches(Wd, y_all).clamp(-1, 1))
     restore = (lambda y: model.deconvolve_noisy(y, k, sigma_y=sigma_y, tol=tol, **chain)) if sigma_y else (lambda y: model.deconvolve(y, k, tol=tol, **chain))
-    outs = []
-    for g, i in enumerate(range(0, n, batch_size)):
-        torch.manual_seed(seed + g)               # x_T and the Philox key of batch g
-        outs.append(restore(y_all[i:i + batch_size].to(device)).float().cpu())
-    x_out = torch.cat(outs)
-    images = dict(restored=to_u8(x_out), **images)
-    extra = dict(unet_forwards=K, psf=name, tol=float(tol))
+    x_out, images = _restore_all(n, batch_size, seed, lambda i: restore(y_all[i:i + batch_size].to(device)), images)
+    extra = dict(unet_forwards=_unet_forwards(model, chain), psf=name, tol=float(tol))
     if sigma_y:
         rms = lambda x: ((batches(Kd, x) - y_clean) ** 2).mean(dim=(1, 2, 3)).sqrt() * 127.5
         extra.update(sigma_y=float(sigma_y), consistency=rms(x_out).double().numpy(), consistency_u8=rms(from_u8(images["restored"])).double().numpy())
     else:
         extra.update(consistency=(batches(Md, x_out) - yp_all).abs().amax(dim=(1, 2, 3)).double().numpy())
-    methods = {name: _score(ops, img, ref, None, device) for name, img in images.items()}
-    return dict(n_images=n, method="ddnm_plus" if sigma_y else "ddnm_deconv", methods=methods, images={k: v.numpy() for k, v in images.items()}, **extra)
+    return _result(images, ref, None, device, "ddnm_plus" if sigma_y else "ddnm_deconv", extra)
 
 
 def report(result):
