@@ -1067,7 +1067,8 @@ __global__ void clip_coef_kernel(const float* __restrict__ part, int nparts, flo
     if (threadIdx.x == 0) {
         const float norm = sqrtf(s);
         out[0] = norm;
-        out[1] = fminf(1.0f, max_norm / (norm + 1e-6f));
+        const float coef = max_norm / (norm + 1e-6f);
+        out[1] = coef > 1.0f ? 1.0f : coef;        // clamp(max=1): a NaN norm gives a NaN coefficient (fminf would give 1)
     }
 }
 // torch.optim.Adam (no amsgrad / weight decay) on flat buffers; the clip coefficient is read from device memory

@@ -74,7 +74,7 @@ __device__ __forceinline__ float mish_f(float x) {
 // (hardware exp / reciprocal as in mish_f: one v_exp_f32 + one v_rcp_f32 instead of a library exp and two IEEE divides -- this
 // runs per element in conv epilogues (ddk_conv_args.dmish_src) and in the GroupNorm backward)
 __device__ __forceinline__ float mish_grad_f(float u) {
-    if (u > 20.0f) return 1.0f;
+    if (u > 20.0f) return (u - u) + 1.0f;       // 1, and NaN at +Inf as torch's mish backward gives (x * 0 there): a non-finite stays visible
     const float e = __expf(u);
     const float n = e * (e + 2.0f);
     const float r = __frcp_rn(n + 2.0f);

@@ -55,7 +55,7 @@ __global__ __launch_bounds__(256) void q_sample_kernel(const float* __restrict__
 
 __device__ __forceinline__ float p_step(float x, float e, float z, float cr, float crm1, float c1, float c2, float sg) {
     float x0 = __fsub_rn(__fmul_rn(cr, x), __fmul_rn(crm1, e));     // ddpm.py:152-155
-    x0 = fminf(fmaxf(x0, -1.0f), 1.0f);                             // ddpm.py:157 clamp_(-1, 1)
+    x0 = clamp_pm1(x0);                                             // ddpm.py:157 clamp_(-1, 1): a NaN stays a NaN
     const float mean = __fadd_rn(__fmul_rn(c1, x0), __fmul_rn(c2, x));  // ddpm.py:177-180
     return __fadd_rn(mean, __fmul_rn(sg, z));                       // ddpm.py:227 (sg already carries the t>0 mask)
 }
@@ -65,7 +65,7 @@ __device__ __forceinline__ float p_step(float x, float e, float z, float cr, flo
 // unfused tail, so given the same eps_hat they are bit-identical.
 __device__ __forceinline__ float ms_step(float x, float e, float& h, float cr, float crm1, float c1, float c2, float c3) {
     float x0 = __fsub_rn(__fmul_rn(cr, x), __fmul_rn(crm1, e));
-    x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    x0 = clamp_pm1(x0);
     const float mean = __fadd_rn(__fmul_rn(c1, x0), __fmul_rn(c2, x));
     const float out = __fadd_rn(mean, __fmul_rn(c3, h));
     h = x0;
@@ -408,14 +408,15 @@ __device__ __forceinline__ VlbCoef vlb_coef(int64_t tb, const float* c_recip, co
 // t > 0: KL(q(x_{t-1} | x_t, x) || p(x_{t-1} | x_t)) in nats; t == 0: the discretised-Gaussian NLL of x
 __device__ __forceinline__ float vlb_elem(float xv, float xt, float eh, const VlbCoef& k) {
     float x0 = __fsub_rn(__fmul_rn(k.cr, xt), __fmul_rn(k.crm1, eh));
-    x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    x0 = clamp_pm1(x0);
     const float pred = __fadd_rn(__fmul_rn(k.a1, x0), __fmul_rn(k.a2, xt));
     if (k.t0) {
         const float c = xv - pred;
         const float cdf_plus = std_normal_cdf_approx(k.inv_std * (c + 1.0f / 255.0f));
         const float cdf_min = std_normal_cdf_approx(k.inv_std * (c - 1.0f / 255.0f));
-        const float lp = xv < -0.999f ? logf(fmaxf(cdf_plus, 1e-12f))
-                                      : (xv > 0.999f ? logf(fmaxf(1.0f - cdf_min, 1e-12f)) : logf(fmaxf(cdf_plus - cdf_min, 1e-12f)));
+        const float lp = xv < -0.999f ? logf(clamp_min_nan(cdf_plus, 1e-12f))
+                                      : (xv > 0.999f ? logf(clamp_min_nan(1.0f - cdf_min, 1e-12f))
+                                                     : logf(clamp_min_nan(cdf_plus - cdf_min, 1e-12f)));
         return -lp;
     }
     const float tm = __fadd_rn(__fmul_rn(k.a1, xv), __fmul_rn(k.a2, xt));
@@ -1179,13 +1180,17 @@ __global__ __launch_bounds__(1024) void fix_samples_kernel(const float* __restri
     const float* xb = x + (long long)blockIdx.x * per;
     float* ob = out + (long long)blockIdx.x * per;
     float lo = INFINITY, hi = -INFINITY;
+    bool bad = false;
     for (long long i = threadIdx.x; i < per; i += 1024) {
         const float v = xb[i];
+        bad |= v != v;
         lo = fminf(lo, v);
         hi = fmaxf(hi, v);
     }
     hi = block_max(hi, red);
     lo = -block_max(-lo, red);
+    // x.min() / x.max() of an image that holds a NaN are NaN (fminf / fmaxf skip it): the whole image comes out NaN
+    if (block_max(bad ? 1.0f : 0.0f, red) != 0.0f) lo = hi = __builtin_nanf("");
     const float range = hi - lo;
     for (long long p = threadIdx.x; p < HW; p += 1024)
         for (int c = 0; c < C; ++c) ob[p * C + c] = ((xb[c * HW + p] - lo) / range) * 255.0f;

@@ -47,9 +47,16 @@ struct RestoreTraits {
     static constexpr bool POINT = MASK && !GRAY;      // n = 1 is pointwise
 };
 
+// clamp_(-1, 1) as torch computes it: a finite x0 keeps its bits, a NaN stays a NaN (fminf / fmaxf would return the bound: a NaN in
+// eps_hat would leave the step as x0 = -1 and the sample would be finite garbage)
+__device__ __forceinline__ float clamp_pm1(float x0) { return x0 < -1.0f ? -1.0f : (x0 > 1.0f ? 1.0f : x0); }
+
+// max(v, lo) that keeps a NaN in v, as torch's clamp(min=lo)
+__device__ __forceinline__ float clamp_min_nan(float v, float lo) { return v < lo ? lo : v; }
+
 __device__ __forceinline__ float rst_x0(float x, float e, float cr, float crm1) {
     const float x0 = __fsub_rn(__fmul_rn(cr, x), __fmul_rn(crm1, e));     // as p_step
-    return fminf(fmaxf(x0, -1.0f), 1.0f);
+    return clamp_pm1(x0);
 }
 
 // zh: the draw, or (HIST) the history, which leaves holding x0'; a5: sigma, or (HIST) c3; sgm: NOISY

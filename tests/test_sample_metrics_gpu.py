@@ -224,7 +224,7 @@ def test_evaluate_ddpm_cli_with_activations(tmp_path):
         soft = rng.random((24, 10))
         files[name] = tmp_path / f"{name}.npz"
         np.savez(files[name], pool_3=pool, spatial=spatial, softmax=soft / soft.sum(axis=1, keepdims=True))
-    cfg = ddpm_cfg(32, 3, 16, T=20)
+    cfg = ddpm_cfg(32, 3, 16, T=25)      # (at T = 20 the linear schedule ends on beta = 1: alphas_cumprod = 0, the VLB is NaN)
     cfg.update(model="ddpm", dataset="cifar10", batch_size=2)
     (tmp_path / "cfg.json").write_text(json.dumps(cfg))
     out = tmp_path / "metrics.json"
