@@ -306,6 +306,8 @@ SIGNATURES = {
     "ddk_convt_small_s2_dgrad": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "ddk_convt_small_s2_wgrad_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
     "ddk_convt_small_s2_wgrad": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _SZ, _P]),
+    "ddk_image_batch": (_I, [_P, _LL, _I, _I, _I, _P, _I, _P, _P, _I, _P, _P, _I, _I, _I, C.c_uint64, C.c_uint32, _P, _P]),
+    "ddk_image_batch_rows_per_group": (_I, [_I, _I, _I, _I, _I, _I]),
 }
 
 _lib = None

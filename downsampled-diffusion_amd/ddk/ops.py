@@ -2029,3 +2029,34 @@ def convt_small_s2_wgrad(x, dy, want_bias=True):
     L.check(lib.ddk_convt_small_s2_wgrad(xp, dyp, L.ptr(dw), L.ptr(db), b, cin, cout, h, wd, L.ptr(ws), ws.numel() * 4, L.stream()),
             "convt_small_s2_wgrad")
     return dw, db
+
+
+# ------------------------------------------------------------------ training batches from a resident uint8 array
+def image_batch_rows_per_group(hs, ws, c, size, row_taps, col_taps):
+    """output rows one workgroup of image_batch takes for this shape (host arithmetic); 0: the shape is not taken"""
+    return int(L.load().ddk_image_batch_rows_per_group(hs, ws, c, size, row_taps, col_taps))
+
+
+def image_batch(images, index, tables, S, flip=False, seed=0, epoch=0):
+    """[B, C, S, S] fp32 in [-1, 1]: the transform chain of utils/image_batch.py of images[index[b]], one launch.  images: uint8
+    [N, Hs, Ws, C] on the device; index: int64 [B] on the device; tables: (row_start int32 [S], row_w fp32 [S, row_taps], col_start
+    int32 [S], col_w fp32 [S, col_taps]) on the device, utils.image_batch.Transform's.  flip: mirror along W the images that
+    utils.image_batch.flip_bits(index, seed, epoch) names.  An index outside [0, N) gives an all-NaN image."""
+    row_start, row_w, col_start, col_w = tables
+    if images.dtype != torch.uint8 or images.dim() != 4:
+        raise L.DDKError(f"image_batch: images must be uint8 [N, H, W, C], got {images.dtype} {tuple(images.shape)}")
+    if index.dtype != torch.int64 or index.dim() != 1 or index.numel() < 1:
+        raise L.DDKError(f"image_batch: index must be int64 [B], got {index.dtype} {tuple(index.shape)}")
+    n, hs, ws, c = images.shape
+    S = int(S)
+    if (row_start.dtype != torch.int32 or col_start.dtype != torch.int32 or tuple(row_start.shape) != (S,) or tuple(col_start.shape) != (S,)
+            or row_w.dim() != 2 or col_w.dim() != 2 or row_w.shape[0] != S or col_w.shape[0] != S):
+        raise L.DDKError(f"image_batch: the tables of size {S} are (int32 [S], fp32 [S, taps]) per axis, got {tuple(row_start.shape)} "
+                         f"{row_start.dtype}, {tuple(row_w.shape)}, {tuple(col_start.shape)} {col_start.dtype}, {tuple(col_w.shape)}")
+    b = index.numel()
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    out = torch.empty((b, c, S, S), device=images.device, dtype=torch.float32)
+    L.check(L.load().ddk_image_batch(L.ptr(images), n, hs, ws, c, L.ptr(index), b, L.ptr(row_start), L.ptr(_f32(row_w)), row_w.shape[1],
+                                     L.ptr(col_start), L.ptr(_f32(col_w)), col_w.shape[1], S, int(bool(flip)), seed,
+                                     int(epoch) & 0xFFFFFFFF, L.ptr(out), L.stream()), "image_batch")
+    return out

@@ -50,9 +50,12 @@ CONFIG_MODEL = {
 if __name__ == '__main__':
     config, mute = get_args(CONFIG, DATASETS, MODEL_NAMES)
     t_override = config.pop('T_override', None)
+    val_split = config.pop('val_split', None)              # --val_split outranks the model's default, as -T does
     config = modify_config(config, CONFIG_MODEL[config['model']])
     if t_override is not None:
         config['T'] = t_override
+    if val_split is not None:
+        config['val_split'] = val_split
     if config['model'] == 'ddpm' and config['n_downsamples'] > 0:
         config['model'] = 'dddpm'
         config = modify_config(config, CONFIG_MODEL['dddpm'])

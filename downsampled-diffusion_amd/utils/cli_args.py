@@ -24,11 +24,20 @@ def get_args(config: dict, data_names: list, model_names: list, argv=None) -> tu
     ap.add_argument('-T', dest='T_override', type=int, default=None, help='(extension) number of diffusion steps.')
     ap.add_argument('--n_samples', dest='n_samples', type=int, default=None,
                     help='(extension) images in the logged sample grid; must be a square number <= batch size.')
+    ap.add_argument('--data_file', dest='data_file', type=str, default=None,
+                    help='(extension) uint8 [N, H, W, C] .npy of training images (prepare_dataset.py); default: '
+                         '<data>/<dataset>/train.npy when it exists, else the synthetic set.')
+    ap.add_argument('--test_file', dest='test_file', type=str, default=None,
+                    help='(extension) the same for the test split; it travels in the checkpoint config to the evaluators.')
+    ap.add_argument('--rnd_flip', dest='rnd_flip', action='store_const', const=True, default=None,
+                    help='(extension) mirror training images at random (the reference reads config["rnd_flip"] in its transforms).')
+    ap.add_argument('--val_split', dest='val_split', type=float, default=None,
+                    help='(extension) share of the training images held out for validation.')
     args = ap.parse_args(argv)
     for key, value in vars(args).items():
         if key in ('mute', 'n_runs'):
             continue
-        if key in ('T_override', 'n_samples') and value is None:
+        if key in ('T_override', 'n_samples', 'data_file', 'test_file', 'rnd_flip', 'val_split') and value is None:
             continue
         config[key] = value
     if config['model'] != 'ddpm':

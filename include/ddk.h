@@ -1083,6 +1083,23 @@ size_t ddk_convt_small_s2_wgrad_workspace_bytes(int B, int cin, int cout, int H,
 int ddk_convt_small_s2_wgrad(const float* x, const float* dy, float* dw, float* db, int B, int cin, int cout, int H, int W, void* workspace,
                              size_t workspace_bytes, ddk_stream_t s);
 
+/* ------------------------------------------------------------------ training batches from a resident uint8 image array
+ * One launch builds a batch: out[b] = the reference's transform chain of images[index[b]] -- u8 / 255 (correctly rounded), antialiased
+ * bilinear resize of the short side to S, centre crop to S x S, v * 2 - 1, optional horizontal flip -- as fp32 NCHW [B][C][S][S].
+ * images: device uint8 [n_images][Hs][Ws][C] at any byte alignment; index: device int64 [B].  The resize and the crop arrive as two tap
+ * tables (utils/image_batch.py resize_tables): output row y is sum_k row_w[y][k] * T[row_start[y] + k], T the source rows resampled along
+ * W by the col tables in the same way; taps are summed in increasing k, W first, then H, so an image's bits do not depend on its place in
+ * the batch or on the batch.  row_start / col_start: int32 [S] (a start outside [0, n - taps] is clamped: no table can make the kernel
+ * read outside an image); row_w / col_w: fp32 [S][taps].  flip != 0: image id is mirrored along W iff bit 0 of word 0 of Philox4x32-10
+ * with counter (id lo, id hi, epoch, 0x464c4950) and key (seed lo, seed hi) is set.  An index outside [0, n_images) reads nothing and
+ * gives an all-NaN image.  A workgroup takes one image and a band of output rows; ddk_image_batch_rows_per_group is the band's height
+ * (host arithmetic, at most 64 KB of LDS per workgroup; 0: the shape is not taken).  C in 1..4, S a multiple of 4 in [4, 1024], taps in
+ * 1..32 and no more than the source side, B in 1..65535, out 16-byte aligned; anything else is DDK_ERR_ARG and runs no kernel. */
+int ddk_image_batch(const uint8_t* images, long long n_images, int Hs, int Ws, int C, const int64_t* index, int B, const int32_t* row_start,
+                    const float* row_w, int row_taps, const int32_t* col_start, const float* col_w, int col_taps, int S, int flip,
+                    uint64_t seed, uint32_t epoch, float* out, ddk_stream_t s);
+int ddk_image_batch_rows_per_group(int Hs, int Ws, int C, int S, int row_taps, int col_taps);
+
 #ifdef __cplusplus
 }
 #endif
