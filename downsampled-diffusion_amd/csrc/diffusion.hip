@@ -53,12 +53,7 @@ __global__ __launch_bounds__(256) void q_sample_kernel(const float* __restrict__
     }
 }
 
-__device__ __forceinline__ float p_step(float x, float e, float z, float cr, float crm1, float c1, float c2, float sg) {
-    float x0 = __fsub_rn(__fmul_rn(cr, x), __fmul_rn(crm1, e));     // ddpm.py:152-155
-    x0 = clamp_pm1(x0);                                             // ddpm.py:157 clamp_(-1, 1): a NaN stays a NaN
-    const float mean = __fadd_rn(__fmul_rn(c1, x0), __fmul_rn(c2, x));  // ddpm.py:177-180
-    return __fadd_rn(mean, __fmul_rn(sg, z));                       // ddpm.py:227 (sg already carries the t>0 mask)
-}
+// (p_step, the ancestral / DDIM rule, lives in diffusion_step.h: guidance.hip's guided update runs it too)
 
 // DPM-Solver++(2M) (models/diffusion/respace.py dpm_solver_tables): the same clamped x0, then
 // x_prev = (c1 x0 + c2 x) + c3 h with h the previous step's x0, which the step leaves in h.  One function for the fused and the

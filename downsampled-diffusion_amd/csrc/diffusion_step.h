@@ -59,6 +59,15 @@ __device__ __forceinline__ float rst_x0(float x, float e, float cr, float crm1) 
     return clamp_pm1(x0);
 }
 
+// The ancestral / DDIM step rule of ddk_p_sample_update, ddk_final_tail and ddk_p_sample_update_guided: one function, so given the
+// same eps_hat and draw they agree bit for bit.
+__device__ __forceinline__ float p_step(float x, float e, float z, float cr, float crm1, float c1, float c2, float sg) {
+    float x0 = __fsub_rn(__fmul_rn(cr, x), __fmul_rn(crm1, e));     // ddpm.py:152-155
+    x0 = clamp_pm1(x0);                                             // ddpm.py:157 clamp_(-1, 1): a NaN stays a NaN
+    const float mean = __fadd_rn(__fmul_rn(c1, x0), __fmul_rn(c2, x));  // ddpm.py:177-180
+    return __fadd_rn(mean, __fmul_rn(sg, z));                       // ddpm.py:227 (sg already carries the t>0 mask)
+}
+
 // zh: the draw, or (HIST) the history, which leaves holding x0'; a5: sigma, or (HIST) c3; sgm: NOISY
 template <StepKind K>
 __device__ __forceinline__ float rst_finish(float x, float x0p, float mk, float& zh, float c1, float c2, float a5, float sgm) {

@@ -17,8 +17,12 @@ def _c(t):
 def _grad_slot(p):
     """The tensor a parameter gradient can be accumulated into in place: ``p.grad`` when it already exists as a dense fp32
     buffer (trainers/optim.py gives every parameter a view of ONE flat gradient buffer).  The backward kernels then add
-    into it directly and the Function returns None for that input -- no zero-fill, no temporary, no torch add."""
+    into it directly and the Function returns None for that input -- no zero-fill, no temporary, no torch add.
+    A parameter that asks for no gradient has no slot: a backward that runs for the INPUT's gradient alone (the guided sampler,
+    models/diffusion/guidance.py frozen()) must leave every `.grad` as it found it."""
     if p is None or not p.is_leaf:        # (a padded copy of a parameter is no leaf: reading its .grad only draws a warning)
+        return None
+    if not p.requires_grad:
         return None
     g = getattr(p, "grad", None)
     if g is not None and g.dtype == torch.float32 and g.is_contiguous():
@@ -627,6 +631,49 @@ class QSampleFn(torch.autograd.Function):
     def backward(ctx, dy):
         t, sqrt_acp = ctx.saved_tensors
         return ops.scale_per_sample(_c(dy), sqrt_acp[t].contiguous()), None, None, None, None
+
+
+class PredictX0Fn(torch.autograd.Function):
+    """x0 = clamp(c_recip[t] x_t - c_recipm1[t] eps, -1, 1) (ddpm.py:149-158; the clipped x0 of the fused update, bit for bit), with
+    gradients to x_t and eps: c_recip m and -c_recipm1 m times dx0, m = 1 where the unclipped value lies in [-1, 1]."""
+
+    @staticmethod
+    def forward(ctx, x_t, eps, t, c_recip, c_recipm1, clip=True):
+        x_t, eps = _c(x_t), _c(eps)
+        ctx.save_for_backward(x_t, eps, t, c_recip, c_recipm1)
+        ctx.clip = bool(clip)
+        return ops.x0_from_eps(x_t, eps, t, c_recip, c_recipm1, ctx.clip)
+
+    @staticmethod
+    def backward(ctx, dx0):
+        x_t, eps, t, c_recip, c_recipm1 = ctx.saved_tensors
+        dx, deps = ops.x0_from_eps_bwd(x_t, eps, _c(dx0), t, c_recip, c_recipm1, ctx.clip)
+        return (dx if ctx.needs_input_grad[0] else None), (deps if ctx.needs_input_grad[1] else None), None, None, None, None
+
+
+class MeasureDistFn(torch.autograd.Function):
+    """dist [B] = || phi(A img_b) - y_b ||_2 per image of img [B,H,W,C] (NHWC) for an operator of models/diffusion/guidance.py
+    (DESIGN.md section 3.22).  The local operator (kind "mean") is one launch on img; a plane-wide one runs its own transform
+    (operator.transform) and the same launch at n = 1 on the result.  Backward: A^T of the saved r = mask phi' (phi - y), scaled per image
+    by gout[b] / dist[b] on the device (0 where dist[b] == 0)."""
+
+    @staticmethod
+    def forward(ctx, img, y, operator):
+        local = operator.kind == "mean"
+        u = _c(img) if local else operator.transform(_c(img))
+        ctx.n = operator.n if local else 1
+        r, dist = ops.measure_residual(u, y, operator.mask, ctx.n, operator.response, operator.gain)
+        ctx.save_for_backward(r, dist)
+        ctx.operator = operator
+        return dist
+
+    @staticmethod
+    def backward(ctx, gout):
+        r, dist = ctx.saved_tensors
+        v = ops.measure_adjoint(r, dist, _c(gout), ctx.n)
+        if ctx.operator.kind != "mean":
+            v = ctx.operator.transform_adjoint(v)
+        return v, None, None
 
 
 class TimeEmbedFn(torch.autograd.Function):

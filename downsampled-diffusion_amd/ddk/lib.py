@@ -172,6 +172,12 @@ SIGNATURES = {
     "ddk_p_sample_update_restore_fft": (_I, [_P] * 12 + [_I, _I, _I, _I, C.c_uint64, C.c_uint32, _P]),
     "ddk_circular_spectrum": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "ddk_p_sample_update_restore_fft_noisy": (_I, [_P] * 14 + [_I, _I, _I, _I, C.c_uint64, C.c_uint32, _P]),
+    "ddk_measure_residual_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
+    "ddk_measure_residual": (_I, [_P, _P, _P, _I, _I, _F, _P, _P, _I, _I, _I, _I, _P, _SZ, _P]),
+    "ddk_measure_adjoint": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _I, _P]),
+    "ddk_x0_from_eps": (_I, [_P, _P, _P, _P, _P, _I, _P, _I, _LL, _P]),
+    "ddk_x0_from_eps_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _LL, _P]),
+    "ddk_p_sample_update_guided": (_I, [_P] * 11 + [_I, _LL, C.c_uint64, C.c_uint32, _P]),
     "ddk_randn": (_I, [_P, _LL, C.c_uint64, C.c_uint32, C.c_uint32, _P]),
     "ddk_fix_samples": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "ddk_sq_err_sum": (_I, [_P, _P, _P, _I, _LL, _P]),

@@ -1039,6 +1039,86 @@ def p_sample_update_restore_fft_noisy_(x, eps_hat, mask, gain, nsc, Yhat, t, c_r
     return x
 
 
+# ---------------------------------------------------------------- Diffusion Posterior Sampling (csrc/guidance.hip)
+RESPONSES = {"linear": 0, "saturate": 1}      # DDK_RESPONSE_LINEAR, DDK_RESPONSE_SATURATE (include/ddk.h)
+MEASURE_BLOCKS = (1, 2, 4, 8)
+
+
+def measure_residual(img, y, mask=None, n=1, response="linear", gain=1.0):
+    """(r, dist) of the measurement y [B,H/n,W/n,C] of img [B,H,W,C] (NHWC fp32) under A = mask o (n x n block mean) and the pointwise
+    response phi: r = mask phi'(u) (phi(u) - y) with u the block mean, dist [B] = sqrt(sum mask (phi(u) - y)^2) per image, summed in
+    double in a fixed order.  mask [B,H/n,W/n] fp32 (nonzero = measured) or None; response "linear" (phi(u) = u) or "saturate"
+    (phi(u) = clamp(gain u, -1, 1))."""
+    if response not in RESPONSES:
+        raise L.DDKError(f"measure_residual: response must be one of {tuple(RESPONSES)}, got {response!r}")
+    if img.dim() != 4 or n not in MEASURE_BLOCKS or img.shape[1] % n or img.shape[2] % n:
+        raise L.DDKError(f"measure_residual: img {tuple(img.shape)} must be [B,H,W,C] with n = {n!r} in {MEASURE_BLOCKS} dividing H and W")
+    b, h, w, c = img.shape
+    want = (b, h // n, w // n, c)
+    if tuple(y.shape) != want or (mask is not None and tuple(mask.shape) != want[:3]):
+        raise L.DDKError(f"measure_residual: img {tuple(img.shape)} at n = {n} needs y {want} and mask {want[:3]} or None, got "
+                         f"{tuple(y.shape)} and {None if mask is None else tuple(mask.shape)}")
+    r = torch.empty(want, device=img.device, dtype=torch.float32)
+    dist = torch.empty((b,), device=img.device, dtype=torch.float32)
+    lib = L.load()
+    nbytes = lib.ddk_measure_residual_workspace_bytes(b, h, w, c, n)
+    ws = _ws(img.device, nbytes, "measure") if nbytes else None
+    L.check(lib.ddk_measure_residual(L.ptr(_f32(img)), L.ptr(_f32(y)), None if mask is None else L.ptr(_f32(mask)), n, RESPONSES[response],
+                                     float(gain), L.ptr(r), L.ptr(dist), b, h, w, c, L.ptr(ws), nbytes, L.stream()), "measure_residual")
+    return r, dist
+
+
+def measure_adjoint(r, dist, gout, n=1):
+    """v [B,H,W,C] = s[b] r[b, i / n, j / n, c] / n^2 with s[b] = gout[b] / dist[b] (0 where dist[b] == 0): the gradient of
+    sum_b gout[b] dist[b] with respect to img, from measure_residual's r [B,H/n,W/n,C] and dist [B]; gout [B] stays on the device."""
+    if r.dim() != 4 or n not in MEASURE_BLOCKS or tuple(dist.shape) != (r.shape[0],) or tuple(gout.shape) != (r.shape[0],):
+        raise L.DDKError(f"measure_adjoint: r {tuple(r.shape)}, dist {tuple(dist.shape)}, gout {tuple(gout.shape)}, n = {n!r}")
+    b, h, w, c = r.shape
+    v = torch.empty((b, h * n, w * n, c), device=r.device, dtype=torch.float32)
+    L.check(L.load().ddk_measure_adjoint(L.ptr(_f32(r)), L.ptr(_f32(dist)), L.ptr(_f32(gout)), n, L.ptr(v), b, h * n, w * n, c, L.stream()),
+            "measure_adjoint")
+    return v
+
+
+def x0_from_eps(x, eps, t, c_recip, c_recipm1, clip=True):
+    """The x0 estimate of a reverse step per sample row t[b]: c_recip x - c_recipm1 eps, clamped to [-1, 1] with clip -- the clipped x0
+    of p_sample_update_, bit for bit (any layout, as long as x and eps agree)."""
+    if tuple(eps.shape) != tuple(x.shape):
+        raise L.DDKError(f"x0_from_eps: x {tuple(x.shape)} and eps {tuple(eps.shape)} must agree")
+    b = x.shape[0]
+    out = torch.empty_like(x, memory_format=torch.contiguous_format)
+    L.check(L.load().ddk_x0_from_eps(L.ptr(_f32(x)), L.ptr(_f32(eps)), L.ptr(t), L.ptr(c_recip), L.ptr(c_recipm1), int(bool(clip)), L.ptr(out),
+                                     b, x.numel() // b, L.stream()), "x0_from_eps")
+    return out
+
+
+def x0_from_eps_bwd(x, eps, dx0, t, c_recip, c_recipm1, clip=True):
+    """(dx, deps) = (c_recip m dx0, -c_recipm1 m dx0), m = 1 where the unclipped x0 lies in [-1, 1] (everywhere without clip)."""
+    if tuple(eps.shape) != tuple(x.shape) or tuple(dx0.shape) != tuple(x.shape):
+        raise L.DDKError(f"x0_from_eps_bwd: x {tuple(x.shape)}, eps {tuple(eps.shape)} and dx0 {tuple(dx0.shape)} must agree")
+    b = x.shape[0]
+    dx = torch.empty_like(x, memory_format=torch.contiguous_format)
+    deps = torch.empty_like(x, memory_format=torch.contiguous_format)
+    L.check(L.load().ddk_x0_from_eps_bwd(L.ptr(_f32(x)), L.ptr(_f32(eps)), L.ptr(_f32(dx0)), L.ptr(t), L.ptr(c_recip), L.ptr(c_recipm1),
+                                         int(bool(clip)), L.ptr(dx), L.ptr(deps), b, x.numel() // b, L.stream()), "x0_from_eps_bwd")
+    return dx, deps
+
+
+def p_sample_update_guided_(x, eps_hat, g, t, c_recip, c_recipm1, c1, c2, sigma, zeta, noise=None, seed=0, stream_id=0):
+    """p_sample_update_ (same rule, same Philox key or injected noise), then x <- x - zeta[t[b]] g, in place; g has x's layout and zeta
+    is a row table like the others.  A row whose zeta is 0 takes no step: all zero gives p_sample_update_'s bits."""
+    if tuple(eps_hat.shape) != tuple(x.shape) or tuple(g.shape) != tuple(x.shape) or (noise is not None and tuple(noise.shape) != tuple(x.shape)):
+        raise L.DDKError(f"p_sample_update_guided: x {tuple(x.shape)}, eps_hat {tuple(eps_hat.shape)}, g {tuple(g.shape)}, noise "
+                         f"{None if noise is None else tuple(noise.shape)} must agree")
+    if zeta is None or zeta.dim() != 1 or tuple(zeta.shape) != tuple(c1.shape):
+        raise L.DDKError("p_sample_update_guided: zeta must have one entry per row of c1")
+    b = x.shape[0]
+    L.check(L.load().ddk_p_sample_update_guided(L.ptr(_f32(x)), L.ptr(_f32(eps_hat)), L.ptr(noise), L.ptr(_f32(g)), L.ptr(t), L.ptr(c_recip),
+                                                L.ptr(c_recipm1), L.ptr(c1), L.ptr(c2), L.ptr(sigma), L.ptr(_f32(zeta)), b, x.numel() // b,
+                                                seed, stream_id, L.stream()), "p_sample_update_guided")
+    return x
+
+
 def randn(shape, device, seed, step, stream_id=0):
     out = torch.empty(shape, device=device, dtype=torch.float32)
     L.check(L.load().ddk_randn(L.ptr(out), out.numel(), seed, step, stream_id, L.stream()), "randn")

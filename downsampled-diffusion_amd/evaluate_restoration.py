@@ -52,6 +52,12 @@ through utils/data.py; ``--max_batches`` keeps the first max_batches * batch_siz
     the noise by 1 / |K^|) and ``tikhonov``, conj K^ / (|K^|^2 + S^2).  ``method`` reads ``ddnm_plus``, the settings gain ``psf``,
     ``tol`` and ``sigma_y``, and the consistency is the RMS of A(x_out) - y_clean in uint8 levels.  Needs a chain that draws; keep
     ``--tol`` at or above S.  ``--task deconv`` itself keeps refusing ``--sigma_y``.
+  * ``--method dps --zeta Z [--saturate GAIN] [--sigma_y S]`` (DDPM and dDDPM checkpoints; section 3.22), for ``--task inpaint``
+    (``--mask``), ``sr`` (``--scale`` 1, 2, 4 or 8), ``deblur`` (``--kernel``) and ``deconv`` (``--psf``): Diffusion Posterior Sampling,
+    ``model.restore_guided``.  The images are measured by the task's operator, through a sensor that clips at GAIN with ``--saturate``,
+    with N(0, S^2) noise added; every reverse step is followed by a gradient step of size Z.  Baseline: ``measured``.  The consistency
+    is the RMS of phi(A x_out) - y_clean in uint8 levels; ``method`` reads ``dps`` and the settings gain ``zeta`` and
+    ``unet_backwards`` (one input-gradient backward per forward).  No ``--dpm_solver``, ``--downsample``, ``--tol`` or ``--jump_*``.
   * batch g draws x_T and its Philox key from ``--seed`` + g.
 
 Prints one JSON object, the settings that produced it (among them ``method`` and ``unet_forwards``, the UNet forwards per image, so
@@ -66,18 +72,25 @@ import numpy as np
 import torch
 
 from utils import sampling_cli as cli
-from utils.restoration_metrics import BLUR_KERNELS, CS_TASK, DEBLUR_TASK, DECONV_NOISY_TASK, DECONV_TASK, DOWNSAMPLES, GRAY_WEIGHTS, MASKS, METHODS, TASKS, evaluate_restoration, load_mask, report, to_u8
+from utils.restoration_metrics import BLUR_KERNELS, CS_TASK, DEBLUR_TASK, DECONV_NOISY_TASK, DECONV_TASK, DOWNSAMPLES, DPS_METHOD, DPS_TASKS, GRAY_WEIGHTS, MASKS, METHODS, TASKS, evaluate_restoration, load_mask, report, to_u8
 
 
 def parse_args(argv=None):
-    ap = argparse.ArgumentParser(description="PSNR / SSIM of RePaint inpainting or DDNM super-resolution against ground truth.")
+    ap = argparse.ArgumentParser(description="PSNR / SSIM of RePaint inpainting or DDNM super-resolution against ground truth.",
+                                 epilog="--method dps (inpaint, sr, deblur, deconv; DDPM and dDDPM checkpoints) has two options of its own: "
+                                        "--zeta Z, the step size of the gradient step after every reverse step (required there), and "
+                                        "--saturate GAIN, a sensor that clips: y = clamp(GAIN A x, -1, 1).")
     cli.add_chain_flags(ap, solver=True, out_dir=False, prefix="ddnm: ", respacing_help='run K of the T steps: "N", "n1,n2,..." sections or (sr) "ddimN"',
                         sigma_y="ddnm: add N(0, sigma_y^2) noise to the measurement ([-1, 1] scale) and restore with DDNM+; not with --dpm_solver")
     ap.add_argument("--images", default=None, help="uint8 [N, H, W, C] .npy of the model's size (default: the dataset's test split)")
     ap.add_argument("--task", required=True, choices=(*TASKS, DEBLUR_TASK, CS_TASK, DECONV_TASK, DECONV_NOISY_TASK))
     ap.add_argument("--mask", default=None, help=f"one of {', '.join(MASKS)} or a .npy file of {{0, 1}} (1 = known); inpaint: default "
                                                  "center; sr: masked super-resolution, the mask is of the pooled image (default: none)")
-    ap.add_argument("--method", default=None, choices=METHODS, help="inpaint: repaint (default) or ddnm; sr: ddnm")
+    ap.add_argument("--method", default=None, choices=(*METHODS, DPS_METHOD), help="inpaint: repaint (default) or ddnm; sr: ddnm; dps: gradient-"
+                                                                                   "guided restoration of inpaint, sr, deblur and deconv")
+    # (the two options of --method dps are described in the epilog, not in the option list: the list is what every method shares)
+    ap.add_argument("--zeta", type=float, default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--saturate", type=float, default=None, metavar="GAIN", help=argparse.SUPPRESS)
     ap.add_argument("--scale", type=int, default=None, help="sr: the pooling factor (default 4); colorize: default 1")
     ap.add_argument("--downsample", default=None, choices=DOWNSAMPLES, help="sr: how the images are reduced (default mean: average pooling)")
     ap.add_argument("--weights", default=None, choices=tuple(GRAY_WEIGHTS), help="colorize: the grey image's channel weights (default mean)")
@@ -93,6 +106,11 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.batch_size < 1 or (args.max_batches is not None and args.max_batches < 1):
         ap.error("--batch_size and --max_batches must be >= 1")
+    if args.method == DPS_METHOD:
+        return check_dps(ap, args)
+    if args.zeta is not None or args.saturate is not None:
+        ap.error("--zeta and --saturate belong to --method dps")
+    del args.zeta, args.saturate          # the other methods' namespace is what it was: these two exist under --method dps only
     if args.psf is not None and args.task not in (DECONV_TASK, DECONV_NOISY_TASK):
         ap.error("--psf belongs to --task deconv and --task deconv_noisy")
     if args.task in (DECONV_TASK, DECONV_NOISY_TASK):
@@ -180,9 +198,51 @@ def parse_args(argv=None):
     return args
 
 
+def check_dps(ap, args):
+    """--method dps: the four tasks it restores, each with its own operator flag, on ancestral or DDIM steps"""
+    if args.task not in DPS_TASKS:
+        ap.error(f"--method dps restores --task {', '.join(DPS_TASKS)}")
+    if args.zeta is None or not np.isfinite(args.zeta) or args.zeta < 0:
+        ap.error("--method dps needs --zeta, a finite step size >= 0")
+    if args.saturate is not None and not (np.isfinite(args.saturate) and args.saturate > 0):
+        ap.error("--saturate must be a finite gain > 0")
+    own = {"inpaint": "mask", "sr": "scale", DEBLUR_TASK: "kernel", DECONV_TASK: "psf"}
+    for task, flag in own.items():
+        if task != args.task and getattr(args, flag) is not None:
+            ap.error(f"--method dps: --{flag} belongs to --task {task}")
+    if args.dpm_solver or args.downsample is not None or args.weights is not None or args.tol is not None or args.ratio is not None or \
+            args.perm_seed is not None or args.jump_length != ap.get_default("jump_length") or args.jump_n_sample != ap.get_default("jump_n_sample"):
+        ap.error("--method dps takes no --dpm_solver, --downsample, --weights, --tol, --ratio, --perm_seed or --jump_* (it has no pseudo-inverse "
+                 "to truncate and no jumps)")
+    if args.task == "inpaint" and args.mask is None:
+        args.mask = "center"
+    if args.task == "sr":
+        if args.scale is None:
+            args.scale = 4
+        if args.scale not in (1, 2, 4, 8):
+            ap.error("--method dps: --scale must be 1, 2, 4 or 8")
+    if args.task == DEBLUR_TASK and args.kernel is None:
+        ap.error("--task deblur needs --kernel: the blur is part of the task, there is no default")
+    if args.task == DECONV_TASK:
+        if args.psf is None:
+            ap.error("--task deconv needs --psf: the point-spread function is part of the task, there is no default")
+        if args.psf not in ("diag", "disk") and not args.psf.endswith(".npy"):
+            ap.error("--psf must be diag, disk or a .npy file")
+    cli.check_chain_flags(ap, args, "sigma_y eta")
+    return args
+
+
 def chain_options(args):
     """the task's keywords for evaluate_restoration, also the chain settings the result records"""
     steps = cli.chain_kwargs(args)
+    if args.method == DPS_METHOD:
+        kw = dict(steps, zeta=args.zeta)
+        for name in ("saturate", "scale", "kernel", "psf"):
+            if getattr(args, name) is not None:
+                kw[name] = getattr(args, name)
+        if args.sigma_y != 0.0:
+            kw.update(sigma_y=args.sigma_y)
+        return kw
     kw = dict(respacing=steps.pop("respacing"))
     if args.task in ("sr", "colorize"):
         kw.update(scale=args.scale)
@@ -253,6 +313,8 @@ def main():
         settings["mask"] = args.mask
     if "m" in result:
         settings["m"] = result["m"]
+    if "unet_backwards" in result:
+        settings["unet_backwards"] = result["unet_backwards"]
     out = dict(settings=settings, metrics=report(result))
     print(json.dumps(out, indent=4))
     if args.json:

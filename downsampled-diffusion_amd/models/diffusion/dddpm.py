@@ -62,7 +62,8 @@ class DownsampleDDPM(DDPM):
         self._check_device(z)
         if not isinstance(self.upsample, ConvResNet):
             x = self._resample_nchw(self.upsample, z)
-        elif torch.is_grad_enabled() and any(p.requires_grad for p in self.upsample.parameters()):
+        elif torch.is_grad_enabled() and (z.requires_grad or any(p.requires_grad for p in self.upsample.parameters())):
+            # (also for the INPUT's gradient alone, as _resample_nchw: restore_guided differentiates the measurement through the decoder)
             from trainers.autograd_unet import resnet_forward_autograd
             return resnet_forward_autograd(self.upsample, z, self.force_latent)
         else:
@@ -227,6 +228,24 @@ class DownsampleDDPM(DDPM):
         """Not available, for deconvolve's reason.  Always ValueError."""
         raise ValueError("deconvolve_noisy: a DownsampleDDPM samples in a latent, and a point-spread function on the image has no such form "
                          "there; deconvolution needs a pixel model (DDPM)")
+
+    def restore_guided(self, y, operator, *, zeta, mask=None, response="linear", gain=1.0, respacing=None, ddim=False, eta=0.0, x_T=None,
+                       seed=None, noise=None, **unsupported):
+        """DDPM.restore_guided with the chain in the latent and the measurement in pixels: every step decodes
+        its clipped latent x0, img = rescaled_upsample(x0), measures dist = || phi(A img) - y ||_2 there and takes the gradient back
+        through the decoder, the clamp and the UNet to the latent x_t.  So y, operator and mask are the image's -- any operator
+        DDPM.restore_guided takes on an image of x_shape, which the DDNM entries of this class refuse or hold only in the latent --
+        and all three u_modes work (the learned decoder's parameters are frozen like the UNet's).  Returns (x_out, z) like sample;
+        x_T and noise are the latent's."""
+        from ddk import autograd as AG
+        y, op, zt = self._guided_args(y, operator, zeta, mask, response, gain, respacing, ddim, eta, unsupported, self.x_shape)
+
+        def decode(x0):
+            img = self.rescaled_upsample(AG.NhwcToNchwFn.apply(x0, x0.shape[-1]))
+            return AG.NchwToNhwcFn.apply(img.contiguous(), img.shape[1])
+        z = self._guided_loop(y, op, self._guided_tables(respacing, ddim, eta, zt), x_T, seed, noise, decode=decode)
+        with torch.no_grad():
+            return self.rescaled_upsample(z), z
 
     @torch.no_grad()
     def reconstruct(self, x, n):

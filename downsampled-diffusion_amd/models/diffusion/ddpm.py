@@ -951,6 +951,101 @@ class DDPM(nn.Module):
                                                use_graph=self.use_graph, timesteps=use)
         return self._ddnm_loop("deconvolve_noisy", y, None, self._chain_tables(respacing, ddim, eta), x_T, seed, op, chain)
 
+    # ------------------------------------------------------------------ Diffusion Posterior Sampling (gradient-guided restoration)
+    GUIDED_UNSUPPORTED = ('solver', 'early_stop')
+    GUIDED_RULE = ("c_recip", "c_recipm1", "c1", "c2", "sigma")
+
+    def _guided_args(self, y, operator, zeta, mask, response, gain, respacing, ddim, eta, unsupported, image_shape):
+        """ValueError for anything restore_guided cannot take, before any device work.  ``image_shape`` is [C, H, W] of the image the
+        operator acts on.  Returns (y as float with the elements that are not measured set to 0, the guidance.Operator with its mask
+        as {0, 1} floats [B, h, w] or None, zeta as a float64 array with one entry per step of the chain)."""
+        from . import guidance as G
+        who = "restore_guided"
+        if unsupported:
+            raise ValueError(f"{who}: {sorted(unsupported)} not accepted (DPS runs ancestral or DDIM steps over the whole schedule, each "
+                             f"followed by a gradient step: no {', '.join(self.GUIDED_UNSUPPORTED)})")
+        self._eta_arg(who, ddim, eta)
+        op = G.make_operator(operator, tuple(image_shape), response=response, gain=gain)      # its own ValueErrors
+        C, h, w = op.out_shape
+        y, m = self._measured_args(self._y_arg(who, y, (C, h, w), min_batch=1, finite=False), mask, h, w, who)
+        op.mask = m
+        rows = self.timesteps if respacing is None else len(respace.space_timesteps(
+            self.timesteps, respacing, respace.schedule_arrays(self._betas64)['alphas_cumprod']))
+        return y, op, G.zeta_table(zeta, rows)
+
+    def _guided_tables(self, respacing, ddim, eta, zeta):
+        """() -> (the chain's tables plus the step sizes `zeta` as an fp32 row table, timestep map or None), cached per zeta like
+        the spaced tables: repeated calls pass the same tensors."""
+        base = self._chain_tables(respacing, ddim, eta)
+
+        def build():
+            tables, use = base()
+            return dict(tables, zeta=torch.tensor(zeta, dtype=torch.float32)), use
+        return lambda: self._cached_tables(('guided', respacing, bool(ddim), float(eta), zeta.tobytes()), build)
+
+    def _guided_step(self, x, y, op, t_model, t_row, tables, noise=None, seed=0, decode=None):
+        """One DPS step in place on the NHWC state x, inside guidance.frozen(self): the UNet's autograd forward on x as a leaf, the clipped
+        x0 (ddk.autograd.PredictX0Fn), img = decode(x0) (None: x0 itself), dist = MeasureDistFn(img, y, op), g = d(sum dist) / dx by
+        torch.autograd.grad (HIP backward kernels throughout), then ops.p_sample_update_guided_.  Returns (eps_hat, dist, g)."""
+        from ddk import autograd as AG
+        xt = x.detach().requires_grad_(True)
+        with torch.enable_grad():
+            eps_hat = self._eps_model_nhwc().forward_nhwc(xt, t_model)
+            x0 = AG.PredictX0Fn.apply(xt, eps_hat, t_row, tables["c_recip"], tables["c_recipm1"], True)
+            dist = AG.MeasureDistFn.apply(x0 if decode is None else decode(x0), y, op)
+            (g,) = torch.autograd.grad(dist.sum(), xt)
+        eps_hat, dist, g = eps_hat.detach(), dist.detach(), g.contiguous()
+        ops.p_sample_update_guided_(x, eps_hat.contiguous(), g, t_row, **{k: tables[k] for k in self.GUIDED_RULE}, zeta=tables["zeta"],
+                                    noise=noise, seed=seed, stream_id=int(self.rng_stream_id))
+        return eps_hat, dist, g
+
+    def _guided_loop(self, y, op, get_tables, x_T, seed, noise, decode=None):
+        """The DPS chain over the latent [B, *sample_shape] for the measurement y [B, C, h, w] of decode(x0) under op: the device check,
+        the tables, x_T, the Philox seed (drawn from torch's generator when None) or the injected draws, then every step of the tables
+        as a Python loop of _guided_step with all parameters frozen (guidance.frozen).  Returns the NCHW result."""
+        from . import guidance as G
+        who = "restore_guided"
+        device = self.betas.device
+        if device.type != 'cuda':
+            raise DDKError(f"{who}: move the model to a ROCm device first (no CPU fallback)")
+        tables, use = get_tables()
+        shape = (y.shape[0], *self.sample_shape)
+        k_start = (self.timesteps if use is None else len(use)) - 1
+        if x_T is not None and tuple(x_T.shape) != shape:
+            raise ValueError(f"{who}: x_T must be {shape}, got {tuple(x_T.shape)}")
+        if noise is not None and tuple(noise.shape) != (k_start + 1, *shape):
+            raise ValueError(f"{who}: noise must be {(k_start + 1, *shape)} (one draw per step, in run order), got {tuple(noise.shape)}")
+        img = torch.randn(shape, device=device) if x_T is None else x_T.to(device).float()
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        yl = ops.nchw_to_nhwc(y.to(device).float().contiguous())
+        op.to(device)
+        x = ops.nchw_to_nhwc(img.contiguous())
+        nz = None if noise is None else noise.to(device).float().permute(0, 1, 3, 4, 2).contiguous()   # [k,B,C,H,W] -> [k,B,H,W,C]
+        with G.frozen(self):
+            for j, k in enumerate(range(k_start, -1, -1)):
+                t_model = torch.full((shape[0],), k if use is None else use[k], device=device, dtype=torch.long)
+                t_row = torch.full((shape[0],), k, device=device, dtype=torch.long)
+                self._guided_step(x, yl, op, t_model, t_row, tables, noise=None if nz is None else nz[j], seed=seed, decode=decode)
+        return ops.nhwc_to_nchw(x)
+
+    def restore_guided(self, y, operator, *, zeta, mask=None, response="linear", gain=1.0, respacing=None, ddim=False, eta=0.0, x_T=None,
+                       seed=None, noise=None, **unsupported):
+        """Zero-shot restoration with Diffusion Posterior Sampling (Chung et al., ICLR 2023): an image
+        [B, C, H, W] whose measurement phi(A x) is close to y.  After every reverse step (all T, or respacing's K; ancestral, or DDIM
+        with eta) x moves against the gradient, with respect to x_t and through the UNet, of the distance || phi(A x0) - y ||_2 of the
+        step's own clipped x0, taken per image, times zeta: a number >= 0, or one per step of the chain (entry k for row k).
+        operator: ("mean", n) with n in {1, 2, 4, 8} (n x n block means; n = 1 with a mask is inpainting), ("separable", A_h, A_w)
+        (A_h x A_w^T per channel; sizes multiples of 4 in [4, 256]), ("psf", k) (circular convolution; sizes powers of two in
+        [16, 256]) or a name deblur ("uniform", "gauss", "aniso") or deconvolve ("diag", "disk") takes.  mask: as restore's, on the
+        measurement's grid.  response="saturate": the sensor clips, phi(u) = clamp(gain u, -1, 1); "linear" ignores gain.  The
+        measurement is approached, not held: nothing of y is pasted, and y may carry noise of any level.  x_T: the start state;
+        seed: the Philox key (default: drawn from torch's generator); noise: [steps, B, C, H, W] injected draws in run order.
+        Every parameter is frozen for the chain (no `.grad` is touched) and its flags are put back afterwards.  solver / early_stop
+        raise ValueError, as do a bad operator, response, gain, zeta, mask or eta and a misshapen y, before any device work."""
+        y, op, z = self._guided_args(y, operator, zeta, mask, response, gain, respacing, ddim, eta, unsupported, self.sample_shape)
+        return self._guided_loop(y, op, self._guided_tables(respacing, ddim, eta, z), x_T, seed, noise)
+
     @torch.no_grad()
     def reconstruct(self, x, n):
         """ddpm.py:126-147."""

@@ -229,6 +229,13 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
     "method" and "unet_forwards" (UNet forwards per image: the chain's steps; the batch shares each forward) are returned too.
     Returns {"n_images", "methods": {name: {"psnr": [N], "ssim": [N], ...}}, "images": {name: uint8 [N, H, W, C]}} and, for "sr",
     "consistency" / "consistency_u8" [N]; "restored" is the model's entry."""
+    if method == DPS_METHOD:
+        if dpm_solver or sr_mask is not None or downsample != "mean":
+            raise ValueError("method 'dps' runs ancestral or DDIM steps on an unmasked measurement (task 'inpaint': its mask): no dpm_solver, "
+                             "sr_mask or downsample")
+        return _evaluate_dps(model, images_uint8, task, batch_size=batch_size, seed=seed, mask=mask, scale=scale, sigma_y=sigma_y, **chain)
+    if "zeta" in chain or "saturate" in chain:
+        raise ValueError("zeta and saturate belong to method 'dps'")
     if downsample not in DOWNSAMPLES:
         raise ValueError(f"unknown downsample {downsample!r}: one of {DOWNSAMPLES}")
     if downsample != "mean" and (task != "sr" or sr_mask is not None or dpm_solver or sigma_y):
@@ -347,6 +354,86 @@ def evaluate_restoration(model, images_uint8, task, *, batch_size=32, seed=1234,
         extra["consistency"] = (((degrade(x_out) - y_all) * meas).abs().amax(dim=(1, 2, 3)) * 127.5).double().numpy()
         extra["consistency_u8"] = (((degrade(from_u8(images["restored"])) - y_all) * meas).abs().amax(dim=(1, 2, 3)) * 127.5).double().numpy()
     return _result(images, ref, hidden, device, method + ("_dpmpp2m" if dpm_solver else "_plus" if sigma_y else ""), extra)
+
+
+DPS_METHOD = "dps"
+DPS_TASKS = ("inpaint", "sr", DEBLUR_TASK, DECONV_TASK)
+
+
+def dps_operator(task, *, mask=None, scale=None, kernel=None, psf=None):
+    """(restore_guided's `operator` argument, the mask kind or tensor or None) of one of DPS_TASKS"""
+    if task == "inpaint":
+        return ("mean", 1), ("center" if mask is None else mask)
+    if task == "sr":
+        return ("mean", 4 if scale is None else int(scale)), None
+    if task == DEBLUR_TASK:
+        if kernel not in BLUR_KERNELS:
+            raise ValueError(f"task 'deblur' needs a kernel, one of {BLUR_KERNELS}, got {kernel!r}")
+        return kernel, None
+    if task == DECONV_TASK:
+        if psf is None:
+            raise ValueError("task 'deconv' needs a psf")
+        return ("psf", np.load(psf) if isinstance(psf, str) and psf.endswith(".npy") else psf), None
+    raise ValueError(f"method 'dps' restores the tasks {DPS_TASKS}, got {task!r}")
+
+
+@torch.no_grad()
+def _evaluate_dps(model, images_uint8, task, *, batch_size, seed, mask, scale, sigma_y, zeta=None, saturate=None, kernel=None, psf=None,
+                  **chain):
+    """evaluate_restoration with method "dps" (Diffusion Posterior Sampling), for DDPM and dDDPM models alike:
+    the images are measured on the device by the task's operator (guidance.Operator.measure: mask, block means, the separable blur or the
+    circular convolution, then -- with ``saturate`` = GAIN -- clamp(GAIN u, -1, 1)), N(0, sigma_y^2) noise seeded by ``seed`` is added,
+    and ``model.restore_guided(..., zeta=zeta)`` restores them (``chain``: respacing, ddim, eta).  Baseline: "measured", the measurement
+    brought to the image's size (block means replicated; unmeasured pixels mean-filled).  consistency / consistency_u8: per image the RMS
+    of phi(A x_out) - y_clean over the measured elements in uint8 levels (DPS approaches the measurement, it does not hold it).  The
+    returned method is "dps"; "zeta", "unet_forwards" and "unet_backwards" (one input-gradient backward per forward) are returned."""
+    from models.diffusion import guidance as G
+    if zeta is None:
+        raise ValueError("method 'dps' needs zeta, the step size of its gradient step")
+    if isinstance(sigma_y, bool) or not isinstance(sigma_y, (int, float, np.integer, np.floating)) or not math.isfinite(sigma_y) or sigma_y < 0:
+        raise ValueError(f"sigma_y must be a finite real number >= 0, got {sigma_y!r}")
+    if set(chain) - {"respacing", "ddim", "eta"}:
+        raise ValueError(f"method 'dps' takes respacing, ddim and eta, not {sorted(set(chain) - {'respacing', 'ddim', 'eta'})}")
+    spec, mask = dps_operator(task, mask=mask, scale=scale, kernel=kernel, psf=psf)
+    x_all, ref, device = _setup(model, images_uint8, batch_size)
+    n, c, h, w = x_all.shape
+    kw = dict(response="saturate", gain=float(saturate)) if saturate is not None else {}
+    op = G.make_operator(spec, (c, h, w), **kw)
+    m_all = None
+    if mask is not None:
+        m_all = (make_mask(mask, n, h, w) if isinstance(mask, str) else torch.as_tensor(mask).float().expand(n, -1, h, w)).amin(dim=1).contiguous()
+    ys = []
+    for i in range(0, n, batch_size):
+        op.mask = None if m_all is None else m_all[i:i + batch_size].to(device)
+        ys.append(op.measure(x_all[i:i + batch_size].permute(0, 2, 3, 1).contiguous().to(device)).permute(0, 3, 1, 2).cpu())
+    y_clean = torch.cat(ys)
+    meas = torch.ones_like(y_clean[:, :1]) if m_all is None else m_all.unsqueeze(1)
+    y_meas = y_clean
+    if sigma_y:
+        y_meas = y_clean + float(sigma_y) * torch.randn(y_clean.shape, generator=torch.Generator().manual_seed(seed)) * meas
+    restore = lambda i: model.restore_guided(y_meas[i:i + batch_size], spec, zeta=zeta, mask=None if m_all is None else m_all[i:i + batch_size],
+                                             **kw, **chain)
+    s = op.out_shape[1] and h // op.out_shape[1]
+    base = replicate(y_meas, s) if s > 1 else y_meas
+    images = dict(measured=to_u8(base if m_all is None else mean_fill(base, meas)))
+    x_out, images = _restore_all(n, batch_size, seed, restore, images)
+
+    def rms(x):
+        out = []
+        for i in range(0, n, batch_size):
+            op.mask = None if m_all is None else m_all[i:i + batch_size].to(device)
+            out.append(op.measure(x[i:i + batch_size].permute(0, 2, 3, 1).contiguous().to(device)).permute(0, 3, 1, 2).cpu())
+        d = (torch.cat(out) - y_clean) ** 2 * meas
+        return (d.sum(dim=(1, 2, 3)) / meas.expand_as(d).sum(dim=(1, 2, 3)).clamp(min=1)).sqrt() * 127.5
+    K = _unet_forwards(model, chain)
+    extra = dict(unet_forwards=K, unet_backwards=K, zeta=zeta, consistency=rms(x_out).double().numpy(),
+                 consistency_u8=rms(from_u8(images["restored"])).double().numpy())
+    if saturate is not None:
+        extra["saturate"] = float(saturate)
+    if sigma_y:
+        extra["sigma_y"] = float(sigma_y)
+    hidden = None if m_all is None else (m_all == 0).to(torch.uint8).contiguous()
+    return _result(images, ref, hidden, device, DPS_METHOD, extra)
 
 
 @torch.no_grad()

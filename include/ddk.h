@@ -470,6 +470,40 @@ int ddk_p_sample_update_restore_fft_noisy(float* x, const float* eps_hat, const 
                                           const float* twiddles, const float* Yhat, float* scratch, const int64_t* t, const float* c_recip,
                                           const float* c_recipm1, const float* c1, const float* c2, const float* sigma, int B, int H, int W,
                                           int channels, uint64_t seed, uint32_t stream_id, ddk_stream_t s);
+/* ---- Diffusion Posterior Sampling (Chung et al., ICLR 2023; csrc/guidance.hip) ----
+ * The measurement distance of an image for the local operator A = mask o (n x n block mean), n in {1, 2, 4, 8}, behind a pointwise
+ * response phi: DDK_RESPONSE_LINEAR phi(u) = u; DDK_RESPONSE_SATURATE phi(u) = clamp(gain u, -1, 1) (gain finite and > 0), whose slope
+ * is gain where |gain u| <= 1, bounds included, and 0 elsewhere.  img [B][H][W][C], y and r [B][H/n][W/n][C], mask [B][H/n][W/n] fp32
+ * (nonzero = measured, shared by the channels) or NULL, dist [B]:
+ *   u = the block mean (row-major sum, times the exact 1 / n^2);  r = mask phi'(u) (phi(u) - y);  dist[b] = sqrt(sum mask (phi(u) - y)^2)
+ * Where the mask is 0 neither img nor y is read.  The squares are fp32, their sum per image is carried in double and added in a fixed
+ * order (no atomics): the same bits from run to run, and no image's sum sees another image's elements.  An image of at most 2048
+ * measured elements takes one launch; a larger one is spread over min(ceil(elements / 2048), 64) workgroups whose sums a second launch
+ * adds through `workspace` (ddk_measure_residual_workspace_bytes, 8-byte aligned; may be NULL where that is 0).  Plane-wide operators
+ * run their own transform first and this entry at n = 1.  Anything else is DDK_ERR_ARG and runs no kernel. */
+#define DDK_RESPONSE_LINEAR 0
+#define DDK_RESPONSE_SATURATE 1
+size_t ddk_measure_residual_workspace_bytes(int B, int H, int W, int C, int n);
+int ddk_measure_residual(const float* img, const float* y, const float* mask, int n, int response, float gain, float* r, float* dist,
+                         int B, int H, int W, int C, void* workspace, size_t workspace_bytes, ddk_stream_t s);
+/* The gradient of sum_b gout[b] dist[b] with respect to img from ddk_measure_residual's r and dist:
+ *   v[b][i][j][c] = (s[b] r[b][i / n][j / n][c]) / n^2,   s[b] = gout[b] / dist[b], and 0 where dist[b] == 0
+ * v [B][H][W][C]; dist and gout are device arrays [B]: nothing of the step is read on the host. */
+int ddk_measure_adjoint(const float* r, const float* dist, const float* gout, int n, float* v, int B, int H, int W, int C, ddk_stream_t s);
+/* The x0 estimate of a reverse step as an op of its own, per sample b with row t[b]: x0 = c_recip x - c_recipm1 eps, with clip != 0
+ * clamped to [-1, 1] (a NaN stays a NaN) -- the clipped x0 of ddk_p_sample_update, bit for bit.  _bwd: dx = c_recip m dx0 and
+ * deps = -c_recipm1 m dx0 with m = 1 where the unclipped value lies in [-1, 1] (bounds included; everywhere with clip == 0), else 0.
+ * per % 4 == 0, every tensor 16-byte aligned. */
+int ddk_x0_from_eps(const float* x, const float* eps, const int64_t* t, const float* c_recip, const float* c_recipm1, int clip, float* x0,
+                    int B, long long per, ddk_stream_t s);
+int ddk_x0_from_eps_bwd(const float* x, const float* eps, const float* dx0, const int64_t* t, const float* c_recip, const float* c_recipm1,
+                        int clip, float* dx, float* deps, int B, long long per, ddk_stream_t s);
+/* ddk_p_sample_update (the same step rule, ancestral or DDIM rows alike, the same Philox key or injected `noise`), then
+ * x <- x - zeta[t[b]] g, with g in x's layout and zeta a row table like the others.  A row whose zeta is 0 takes no step: with zeta
+ * all zero the result is ddk_p_sample_update's bit for bit, whatever g holds.  g 16-byte aligned. */
+int ddk_p_sample_update_guided(float* x, const float* eps_hat, const float* noise, const float* g, const int64_t* t, const float* c_recip,
+                               const float* c_recipm1, const float* c1, const float* c2, const float* sigma, const float* zeta, int B,
+                               long long per, uint64_t seed, uint32_t stream_id, ddk_stream_t s);
 /* The end of a forward in one launch (unet.py:69-72 behind the final Block's conv; ddpm.py:203-227): GroupNorm from the conv's
  * partials -> Mish -> 1x1 projection to n_out <= 8 channels (w [n_out][C], bias [n_out]) -> eps_hat; eps_out and / or x may be
  * given: eps_out [B][HW][n_out] receives eps_hat, x [B][HW][n_out] gets the reverse-step update of ddk_p_sample_update in place
