@@ -7,21 +7,16 @@ Shapes and bars are those of tests/test_restore_noisy_gpu.py for the correspondi
 and the native sampler to 1e-5; a 128-channel UNet on 3x32x32 images at B = 16 for the fused tail (n = 1, 2 fused, n = 8 not
 eligible), the 64-channel one at B = 32 and the 32-channel one (never fused); fused and unfused tails, and chains that share a workspace: the same bits.  The
 consistency bar of an exact measurement is tests/test_colorize_cpu.py's."""
-import ctypes as C
 import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
+import chain_cases as CC
 import restore_gray_ref as RG
-from helpers import ddpm_cfg, det_load
+from helpers import ddpm_cfg, det_load, to_nhwc
 from oracle import diffusion_ref as D
-from oracle import philox_ref as PR
-from oracle import unet_ref as U
 from utils import synthetic as syn
 
 pytestmark = pytest.mark.gpu
@@ -45,35 +40,14 @@ def _bar(n, weights):
     return (8 if weights == "mean" else 16) * 3 * n * n * 2.0 ** -24
 
 
-def _mask(kind, b, h, w):
-    """[b, h, w] {0, 1}: a checkerboard, a single measured block / pixel, a single hidden one (at another place per image)"""
-    i, j = torch.meshgrid(torch.arange(h), torch.arange(w), indexing="ij")
-    if kind == "checker":
-        return torch.stack([((i + j + k) % 2).float() for k in range(b)])
-    m = torch.zeros(b, h, w) if kind == "one_measured" else torch.ones(b, h, w)
-    for k in range(b):
-        m[k, (k * 3 + 1) % h, (k * 5 + w - 1) % w] = 1.0 - m[k, 0, 0]
-    return m
-
-
 def _y(shape, n, weights, name):
     """the exact-weights grey image of a clamped synthetic one, pooled: [B, 1, H/n, W/n] fp32"""
     return RG.apply_exact(syn.synthetic_normal(shape, name).clamp(-1, 1), n, weights).float().unsqueeze(1).contiguous()
 
 
-def _sel(mk, y):
-    return (mk != 0).unsqueeze(1).expand_as(y)
-
-
-nhwc = lambda v: v.permute(0, 2, 3, 1).contiguous()
-
-
 @pytest.fixture(scope="module")
 def tiny():
-    from models import DDPM, Unet
-    m = det_load(DDPM(CFG, Unet(CFG), DEV, 3)).to(DEV).eval()
-    sd = {k: v.detach().cpu() for k, v in m.state_dict().items()}
-    return m, (lambda x, t: U.unet_forward(sd, CFG, x, t, pre="latent_model."))
+    return CC.tiny_ddpm(CFG)
 
 
 @pytest.fixture(scope="module")
@@ -86,7 +60,7 @@ def data():
         if sy:
             y = y + sy * syn.synthetic_normal(tuple(y.shape), f"colorize.n{n}{weights}")
         ys[n, weights, sy] = y
-        mks[n, weights, sy] = _mask("checker", 2, 16 // n, 16 // n) if masked else None
+        mks[n, weights, sy] = CC.mask("checker", 2, 16 // n, 16 // n) if masked else None
     return ys, mks, x_T
 
 
@@ -104,18 +78,6 @@ def native(tiny, data):
 
 
 # ---------------------------------------------------------------- the lone op, bit for bit
-def _hand_tables(g):
-    """8 rows, made by hand: lam strictly between 0 and 1 in rows 1, 2, 5, 6, 7, exactly 1 in rows 0, 3 and 4, sgm != sigma everywhere"""
-    tab = {k: torch.rand(8, generator=g) * s for k, s in (("c_recip", 3.0), ("c_recipm1", 2.0), ("c1", 1.0), ("c2", 1.0), ("sigma", 0.5))}
-    tab["c1"][0], tab["c2"][0] = 1.0, 0.0
-    tab["lam"] = 0.1 + 0.8 * torch.rand(8, generator=g)
-    tab["lam"][0] = tab["lam"][3] = tab["lam"][4] = 1.0
-    tab["sgm"] = tab["sigma"] * (0.1 + 0.8 * torch.rand(8, generator=g))
-    tab["sgm"][0] = 0.0
-    assert ((tab["lam"][[1, 2, 5, 6, 7]] > 0) & (tab["lam"][[1, 2, 5, 6, 7]] < 1)).all() and (tab["sgm"][1:] != tab["sigma"][1:]).all()
-    return tab
-
-
 @pytest.mark.parametrize("hw", [(16, 16), (8, 32)], ids=["16x16", "8x32"])
 @pytest.mark.parametrize("weights", ["mean", "luma"])
 @pytest.mark.parametrize("n", [1, 2, 4, 8])
@@ -132,22 +94,19 @@ def test_lone_op_equals_restatement_bit_for_bit(n, weights, hw):
     e = torch.randn(shape, generator=g)
     y0 = torch.rand(B, 1, h // n, w // n, generator=g) * 2 - 1
     t = torch.tensor([0, 7, 3])
-    tab = _hand_tables(g)
+    tab = CC.hand_tables(g, noisy=True)
+    tab["lam"][0] = 1.0                  # this kind's row 0 has lam = 1
     seed, stream = 13579, 6
-    z_dev = torch.stack([ops.randn((B, h, w, 3), DEV, seed, int(tb), stream)[b] for b, tb in enumerate(t)]).cpu()
-    z_ref = torch.from_numpy(np.stack([PR.philox_normal(B * h * w * 3, seed, int(tb), stream).reshape(B, h, w, 3)[b]
-                                       for b, tb in enumerate(t)]))
-    assert float((z_dev - z_ref).abs().max()) < 1e-5
+    z = CC.philox_draws(B, 3, h, w, t, seed, stream)
     sg = torch.where(t > 0, tab["sigma"][t], torch.zeros(B))
     dtab = {k: v.to(DEV) for k, v in tab.items()}
     row = lambda k: tab[k][t]
-    cases = [(kind, _mask(kind, B, h // n, w // n)) for kind in ("checker", "one_measured", "one_hidden")] + [("none", None)]
+    cases = [(kind, CC.mask(kind, B, h // n, w // n)) for kind in ("checker", "one_measured", "one_hidden")] + [("none", None)]
     for kind, mk in cases:
-        y = y0 if mk is None else torch.where(_sel(mk, y0), y0, torch.full_like(y0, float("nan")))
-        want = RG.step(x, e, y, mk, n, weights, row("c_recip"), row("c_recipm1"), row("c1"), row("c2"), sg, row("lam"), row("sgm"),
-                       z_dev.permute(0, 3, 1, 2))
-        xs = nhwc(x).to(DEV)
-        ops.p_sample_update_restore_gray_(xs, nhwc(e).to(DEV), y[:, 0].contiguous().to(DEV), None if mk is None else mk.to(DEV), n, weights,
+        y = y0 if mk is None else torch.where(CC.sel(mk, y0), y0, torch.full_like(y0, float("nan")))
+        want = RG.step(x, e, y, mk, n, weights, row("c_recip"), row("c_recipm1"), row("c1"), row("c2"), sg, row("lam"), row("sgm"), z)
+        xs = to_nhwc(x).to(DEV)
+        ops.p_sample_update_restore_gray_(xs, to_nhwc(e).to(DEV), y[:, 0].contiguous().to(DEV), None if mk is None else mk.to(DEV), n, weights,
                                           t.to(DEV), **dtab, seed=seed, stream_id=stream)
         got = xs.cpu().permute(0, 3, 1, 2)
         assert torch.isfinite(got).all(), kind
@@ -201,17 +160,11 @@ def test_tiny_vs_restatement(tiny, data, native, kw, case):
 def test_graph_equals_eager_and_python_loop_is_close(tiny, data, native, kw, case):
     m, _ = tiny
     graphed = native[case, IDS[KINDS.index(kw)]]
-    m.use_graph = False
-    try:
+    with CC.toggled(m, "use_graph", False):
         eager = _run(m, data, case, kw)
-    finally:
-        m.use_graph = True
     assert torch.equal(graphed, eager)
-    m.native_sampler = False
-    try:
+    with CC.toggled(m, "native_sampler", False):
         loop = _run(m, data, case, kw)
-    finally:
-        m.native_sampler = True
     err = float((loop - graphed).abs().max())
     print(f"Python loop vs native, colorize {case} 8 steps {kw}: {err:.3g}")
     assert err < LOOP_TOL
@@ -237,7 +190,7 @@ def test_unmeasured_y_reaches_nothing(tiny, data, native):
     case = CASES[1]
     n, weights, _, sy = case
     y, mk = ys[n, weights, sy], mks[n, weights, sy]
-    y_nan = torch.where(_sel(mk, y), y, torch.full_like(y, float("nan")))
+    y_nan = torch.where(CC.sel(mk, y), y, torch.full_like(y, float("nan")))
     from ddk import ops
     tables, use = m._gray_tables("8", False, 0.0, 0.0)
     plan = m._eps_model_nhwc().plan()
@@ -275,8 +228,8 @@ def test_fused_tail_equals_unfused_bit_for_bit(wide, n, masked, weights):
         assert parts == (0 if n == 8 else 8)
     assert parts >= 0 and (n != 8 or parts == 0)
     y0 = _y(shape, n, weights, f"colorize.wide.{n}")
-    mk = _mask("checker", B, 32 // n, 32 // n) if masked else None
-    y = torch.where(_sel(mk, y0), y0, torch.full_like(y0, float("nan"))) if masked else y0
+    mk = CC.mask("checker", B, 32 // n, 32 // n) if masked else None
+    y = torch.where(CC.sel(mk, y0), y0, torch.full_like(y0, float("nan"))) if masked else y0
     x_T = syn.synthetic_normal(shape, "colorize.wide.xT")
     run = lambda: m.colorize(y.to(DEV), mk, n, weights=weights, respacing="6", ddim=True, eta=0.5, x_T=x_T, seed=SEED).cpu()
     fused = run()
@@ -308,7 +261,6 @@ def test_chains_share_a_workspace_and_each_weighting_has_its_own_graph(tiny, dat
     tables, _ = m._spaced_tables("8", False, 0.0)
     assert all(torch.equal(gtab[k], tables[k]) and torch.equal(ntab[k], tables[k]) for k in tables)
     K = len(use)
-    tmap = (C.c_int64 * K)(*[int(v) for v in use])
     nbytes = max(lib.ddk_sampler_restore_gray_workspace_bytes(plan.handle, 2, 16, 16, K - 1, n) for n in (1, 2))
     assert nbytes == lib.ddk_sampler_restore_masked_workspace_bytes(plan.handle, 2, 16, 16, K - 1, 1)
     assert nbytes >= max(lib.ddk_sampler_restore_noisy_workspace_bytes(plan.handle, 2, 16, 16, K - 1, n) for n in (1, 2))
@@ -317,68 +269,42 @@ def test_chains_share_a_workspace_and_each_weighting_has_its_own_graph(tiny, dat
     yg = {n: RG.apply_exact(img, n, "mean").float().contiguous().to(DEV) for n in (1, 2)}            # [2, 16/n, 16/n]
     yc = {n: ops.nchw_to_nhwc(torch.nn.functional.avg_pool2d(img, n).contiguous().to(DEV)) if n > 1 else ops.nchw_to_nhwc(img.to(DEV))
           for n in (1, 2)}
-    md = {n: _mask("checker", 2, 16 // n, 16 // n).to(DEV) for n in (1, 2)}
+    md = {n: CC.mask("checker", 2, 16 // n, 16 // n).to(DEV) for n in (1, 2)}
     # what -> (weights code, n, with a mask); "nz1": the noisy chain, "anc": the ancestral one
     jobs = {"mean1": (1, 1, False), "luma1": (2, 1, False), "mean1m": (1, 1, True), "luma2": (2, 2, True), "mean2nm": (1, 2, False),
             "nz1": None, "anc": None}
-    x = torch.empty_like(x0)
-    side = torch.cuda.Stream()
 
-    def run(ws, what, graph=1):
-        x.copy_(x0)
-        torch.cuda.synchronize()
-        a = L.SamplerArgs(plan.handle, L.ptr(plan.packed), L.ptr(x), None, L.ptr(tables["c_recip"]), L.ptr(tables["c_recipm1"]),
-                          L.ptr(tables["c1"]), L.ptr(tables["c2"]), L.ptr(tables["sigma"]), 2, 16, 16, K - 1, 0, SEED, 0, graph, L.ptr(ws),
-                          nbytes)
-        with torch.cuda.stream(side):
-            if what == "anc":
-                rc = lib.ddk_sampler_run_spaced(C.byref(a), tmap, side.cuda_stream)
-            elif what == "nz1":
-                rc = lib.ddk_sampler_run_restore_noisy(C.byref(a), tmap, L.ptr(ntab["lam"]), L.ptr(ntab["sgm"]), L.ptr(yc[1]), L.ptr(md[1]), 1,
-                                                       side.cuda_stream)
-            else:
-                wcode, n, masked = jobs[what]
-                rc = lib.ddk_sampler_run_restore_gray(C.byref(a), tmap, L.ptr(gtab["lam"]), L.ptr(gtab["sgm"]), L.ptr(yg[n]),
-                                                      L.ptr(md[n]) if masked else None, n, wcode, side.cuda_stream)
-        assert rc == 0, L.last_error()
-        side.synchronize()
-        return x.clone()
+    def launch(what, a, tmap, stream):
+        if what == "anc":
+            return lib.ddk_sampler_run_spaced(a, tmap, stream)
+        if what == "nz1":
+            return lib.ddk_sampler_run_restore_noisy(a, tmap, L.ptr(ntab["lam"]), L.ptr(ntab["sgm"]), L.ptr(yc[1]), L.ptr(md[1]), 1, stream)
+        wcode, n, masked = jobs[what]
+        return lib.ddk_sampler_run_restore_gray(a, tmap, L.ptr(gtab["lam"]), L.ptr(gtab["sgm"]), L.ptr(yg[n]), L.ptr(md[n]) if masked else None,
+                                                n, wcode, stream)
 
-    fresh = lambda: torch.empty(nbytes // 4 + 4, device=DEV)
-
-    def alone(what):
-        ws = fresh()
-        try:
-            return run(ws, what)
-        finally:      # the plan's cached graphs and shift table point into ws: drop them before the memory goes back
-            assert lib.ddk_sampler_release_workspace(plan.handle, L.ptr(ws)) == 0
-
-    single = {what: alone(what) for what in jobs}
+    sh = CC.SharedWorkspace(plan, tables, use, x0, nbytes, SEED, launch)
+    x, tmap = sh.x, sh.tmap
+    single = {what: sh.alone(what) for what in jobs}
     names = list(jobs)
     for i, p in enumerate(names):
         for q in names[i + 1:]:
             assert not torch.equal(single[p], single[q]), (p, q)
     for order in (("mean1", "luma1", "mean1", "nz1", "anc", "luma2", "mean2nm", "mean1m", "luma1"),
                   ("anc", "mean2nm", "nz1", "luma1", "mean1m", "luma2", "mean1", "anc", "nz1")):
-        ws = fresh()
-        for what in order:
-            got = run(ws, what)
-            assert torch.equal(got, single[what]), (order, what, float((got - single[what]).abs().max()))
-        assert lib.ddk_sampler_release_workspace(plan.handle, L.ptr(ws)) == 0
+        sh.interleaved(order, single)
     # bad weights, a bad n, a null table and injected noise are rejected
-    ws = fresh()
-    a = L.SamplerArgs(plan.handle, L.ptr(plan.packed), L.ptr(x), None, L.ptr(tables["c_recip"]), L.ptr(tables["c_recipm1"]),
-                      L.ptr(tables["c1"]), L.ptr(tables["c2"]), L.ptr(tables["sigma"]), 2, 16, 16, K - 1, 0, SEED, 0, 0, L.ptr(ws), nbytes)
-    call = lambda lam, sgm, y, mk, n, wc: lib.ddk_sampler_run_restore_gray(C.byref(a), tmap, lam, sgm, y, mk, n, wc, L.stream())
-    lam, sgm = L.ptr(gtab["lam"]), L.ptr(gtab["sgm"])
-    assert call(lam, sgm, L.ptr(yg[1]), None, 1, 0) == -1 and "weights" in L.last_error()
-    assert call(lam, sgm, L.ptr(yg[1]), None, 1, 3) == -1 and "weights" in L.last_error()
-    assert call(lam, sgm, L.ptr(yg[1]), None, 3, 1) == -1
-    assert call(None, sgm, L.ptr(yg[1]), None, 1, 1) == -1 and "table" in L.last_error()
-    noise = torch.zeros((K, *x.shape), device=DEV)
-    a.noise = L.ptr(noise)
-    assert call(lam, sgm, L.ptr(yg[1]), None, 1, 1) == -1 and "noise" in L.last_error()
-    assert lib.ddk_sampler_release_workspace(plan.handle, L.ptr(ws)) == 0
+    with CC.workspace(plan, nbytes) as ws:
+        a = CC.sampler_args(plan, x, tables, K - 1, ws, nbytes, seed=SEED)
+        call = lambda lam, sgm, y, mk, n, wc: lib.ddk_sampler_run_restore_gray(a, tmap, lam, sgm, y, mk, n, wc, L.stream())
+        lam, sgm = L.ptr(gtab["lam"]), L.ptr(gtab["sgm"])
+        assert call(lam, sgm, L.ptr(yg[1]), None, 1, 0) == -1 and "weights" in L.last_error()
+        assert call(lam, sgm, L.ptr(yg[1]), None, 1, 3) == -1 and "weights" in L.last_error()
+        assert call(lam, sgm, L.ptr(yg[1]), None, 3, 1) == -1
+        assert call(None, sgm, L.ptr(yg[1]), None, 1, 1) == -1 and "table" in L.last_error()
+        noise = torch.zeros((K, *x.shape), device=DEV)
+        a.noise = L.ptr(noise)
+        assert call(lam, sgm, L.ptr(yg[1]), None, 1, 1) == -1 and "noise" in L.last_error()
     assert ops.cluster_timeouts() == before
 
 
@@ -396,13 +322,12 @@ def test_a_model_with_other_than_three_channels_is_refused_by_the_chain_entry():
     lib = plan._lib
     plan._need_packed("srg")
     K = len(use)
-    tmap = (C.c_int64 * K)(*[int(v) for v in use])
+    tmap = CC.timestep_map(use)
     nbytes = lib.ddk_sampler_restore_masked_workspace_bytes(plan.handle, 2, 16, 16, K - 1, 1)
-    ws = torch.empty(nbytes // 4 + 4, device=DEV)
-    a = L.SamplerArgs(plan.handle, L.ptr(plan.packed), L.ptr(x), None, L.ptr(tables["c_recip"]), L.ptr(tables["c_recipm1"]),
-                      L.ptr(tables["c1"]), L.ptr(tables["c2"]), L.ptr(tables["sigma"]), 2, 16, 16, K - 1, 0, SEED, 0, 0, L.ptr(ws), nbytes)
+    ws = CC.fresh_workspace(nbytes)
+    a = CC.sampler_args(plan, x, tables, K - 1, ws, nbytes, seed=SEED)
     y = torch.zeros(2, 16, 16, device=DEV)
-    assert lib.ddk_sampler_run_restore_gray(C.byref(a), tmap, L.ptr(tables["lam"]), L.ptr(tables["sgm"]), L.ptr(y), None, 1, 1, L.stream()) == -1
+    assert lib.ddk_sampler_run_restore_gray(a, tmap, L.ptr(tables["lam"]), L.ptr(tables["sgm"]), L.ptr(y), None, 1, 1, L.stream()) == -1
     assert "3-channel" in L.last_error()
     torch.cuda.synchronize()
 
@@ -438,30 +363,16 @@ def test_evaluator_colorize(tiny):
     assert set(sr) == {"n_images", "method", "methods", "images", "unet_forwards", "consistency", "consistency_u8"} and sr["method"] == "ddnm"
 
 
-def _cli_setup(tmp_path):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cfg = ddpm_cfg(32, 3, 16, T=100)
-    cfg.update(model="ddpm", dataset="celeba")
-    (tmp_path / "cfg.json").write_text(json.dumps(cfg))
-    imgs = (np.random.default_rng(0).random((3, 16, 16, 3)) * 255).astype(np.uint8)
-    np.save(tmp_path / "imgs.npy", imgs)
-    env = dict(os.environ, PYTHONPATH=os.path.join(root, "downsampled-diffusion_amd"))
-    return root, env, imgs
-
-
 def test_evaluate_cli_colorize_and_sr_settings(tmp_path):
-    root, env, _ = _cli_setup(tmp_path)
-    script = os.path.join(root, "downsampled-diffusion_amd", "evaluate_restoration.py")
-    base = [sys.executable, script, "--synthetic", str(tmp_path / "cfg.json"), "--images", str(tmp_path / "imgs.npy"), "--timestep_respacing",
-            "5", "--batch_size", "2", "--seed", "9", "--json", str(tmp_path / "out.json")]
-    r = subprocess.run(base + ["--task", "colorize", "--weights", "luma"], capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
+    cfg_path, images_path, _, env = CC.cli_files(tmp_path, CC.cli_cfg(), 3, 16)
+    base = ["evaluate_restoration.py", "--synthetic", cfg_path, "--images", images_path, "--timestep_respacing", "5", "--batch_size", "2",
+            "--seed", "9", "--json", tmp_path / "out.json"]
+    CC.run_script(*base, "--task", "colorize", "--weights", "luma", env=env)
     out = json.loads((tmp_path / "out.json").read_text())
     st, me = out["settings"], out["metrics"]
     assert (st["task"], st["method"], st["weights"], st["scale"], st["unet_forwards"], st["respacing"]) == ("colorize", "ddnm_gray", "luma", 1, 5, "5")
     assert set(me) == {"restored", "replicate", "consistency", "consistency_u8"} and me["consistency"]["max"] <= 127.5 * 2 * _bar(1, "luma")
-    r = subprocess.run(base + ["--task", "sr", "--scale", "2"], capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
+    CC.run_script(*base, "--task", "sr", "--scale", "2", env=env)
     out = json.loads((tmp_path / "out.json").read_text())
     assert set(out["settings"]) == {"checkpoint", "synthetic", "model", "task", "images", "n_images", "batch_size", "seed", "method",
                                     "unet_forwards", "respacing", "scale", "ddim", "eta"}
@@ -470,14 +381,11 @@ def test_evaluate_cli_colorize_and_sr_settings(tmp_path):
 
 
 def test_colorize_cli(tmp_path):
-    root, env, imgs = _cli_setup(tmp_path)
-    script = os.path.join(root, "downsampled-diffusion_amd", "colorize_model_samples.py")
+    cfg_path, _, imgs, env = CC.cli_files(tmp_path, CC.cli_cfg(), 3, 16)
     grey = imgs.mean(axis=3).round().astype(np.uint8)
     np.save(tmp_path / "grey.npy", grey)
-    r = subprocess.run([sys.executable, script, "--synthetic", str(tmp_path / "cfg.json"), "--saved_model", "clitest", "--images",
-                        str(tmp_path / "grey.npy"), "--timestep_respacing", "5", "--batch_size", "2", "--seed", "3", "--out_dir", str(tmp_path)],
-                       capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
+    CC.run_script("colorize_model_samples.py", "--synthetic", cfg_path, "--saved_model", "clitest", "--images", tmp_path / "grey.npy",
+                  "--timestep_respacing", "5", "--batch_size", "2", "--seed", "3", "--out_dir", tmp_path, env=env)
     out = np.load(tmp_path / "clitest_color1_mean_5.npy")
     back = np.load(tmp_path / "clitest_color1_mean_5_gray.npy")
     assert out.shape == (3, 16, 16, 3) and out.dtype == np.float32 and np.isfinite(out).all() and out.min() >= 0 and out.max() <= 255

@@ -4,15 +4,11 @@ final_tail_kernel's multistep mode) against tests/dpm_solver_ref.py, Algorithm 2
 The tiny DDPM (unet_chan 32, 3x16x16, linear schedule, T = 1000) has no Winograd final conv, so its steps end in the unfused
 p_update_kernel<StepKind::Multistep>; the cfg4 window at B = 32 ends in final_tail_kernel's multistep instantiation.  Bars as for the spaced chains:
 1e-4 abs against the restatement with the same argmax, 1e-5 between the Python loop and the native sampler."""
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 import torch
 
+import chain_cases as CC
 import dpm_solver_ref as DR
 import spaced_ref as SR
 from helpers import dddpm_cfg, ddpm_cfg, det_load, golden_keys, unet_cfg
@@ -31,10 +27,7 @@ SOLVER = "dpm++2m"
 
 @pytest.fixture(scope="module")
 def tiny():
-    from models import DDPM, Unet
-    m = det_load(DDPM(CFG, Unet(CFG), DEV, 3)).to(DEV).eval()
-    sd = {k: v.detach().cpu() for k, v in m.state_dict().items()}
-    return m, (lambda x, t: U.unet_forward(sd, CFG, x, t, pre="latent_model."))
+    return CC.tiny_ddpm(CFG)
 
 
 @pytest.fixture(scope="module")
@@ -42,15 +35,11 @@ def x_T():
     return syn.synthetic_normal(SHAPE, "dpm.xT")
 
 
-def _argmax(x):
-    return x.reshape(x.shape[0], -1).argmax(dim=1)
-
-
 def _check(got, want, tol=TOL):
     err = float((got.cpu() - want).abs().max())
     assert torch.isfinite(got).all()
     assert err < tol, err
-    assert torch.equal(_argmax(got.cpu()), _argmax(want))
+    assert torch.equal(CC.argmax(got.cpu()), CC.argmax(want))
     return err
 
 
@@ -83,22 +72,16 @@ def test_order1_tables_miss_the_2m_restatement(tiny, x_T):
 def test_graph_equals_eager_bit_for_bit(tiny, x_T):
     m, _ = tiny
     graphed = m.p_sample_loop(SHAPE, x_T=x_T, respacing="ddim50", solver=SOLVER)
-    m.use_graph = False
-    try:
+    with CC.toggled(m, "use_graph", False):
         eager = m.p_sample_loop(SHAPE, x_T=x_T, respacing="ddim50", solver=SOLVER)
-    finally:
-        m.use_graph = True
     assert torch.equal(graphed, eager)
 
 
 def test_python_loop_equals_native(tiny, x_T):
     m, _ = tiny
     native = m.p_sample_loop(SHAPE, x_T=x_T, respacing="logsnr20", solver=SOLVER)
-    m.native_sampler = False
-    try:
+    with CC.toggled(m, "native_sampler", False):
         loop = m.p_sample_loop(SHAPE, x_T=x_T, respacing="logsnr20", solver=SOLVER)
-    finally:
-        m.native_sampler = True
     err = float((loop - native).abs().max())
     print(f"Python loop vs native, 2M logsnr20: {err:.3g}")
     assert err < 1e-5
@@ -135,7 +118,6 @@ def test_ddim_and_2m_chains_alternate(tiny, x_T):
 
 
 def test_injected_noise_is_rejected_by_the_library(tiny, x_T):
-    import ctypes as C
     from ddk import lib as L
     from ddk import ops
     m, _ = tiny
@@ -146,10 +128,8 @@ def test_injected_noise_is_rejected_by_the_library(tiny, x_T):
     nbytes = plan._lib.ddk_sampler_multistep_workspace_bytes(plan.handle, 2, 16, 16, 19)
     assert nbytes > plan._lib.ddk_sampler_workspace_bytes(plan.handle, 2, 16, 16, 19)
     ws = torch.empty(nbytes // 4, device=DEV)
-    a = L.SamplerArgs(plan.handle, L.ptr(plan.packed), L.ptr(x), L.ptr(noise), L.ptr(tables["c_recip"]), L.ptr(tables["c_recipm1"]),
-                      L.ptr(tables["c1"]), L.ptr(tables["c2"]), None, 2, 16, 16, 19, 0, 0, 0, 0, L.ptr(ws), nbytes)
-    tmap = (C.c_int64 * 20)(*use)
-    assert plan._lib.ddk_sampler_run_multistep(C.byref(a), tmap, L.ptr(tables["c3"]), L.stream()) == -1     # DDK_ERR_ARG
+    a = CC.sampler_args(plan, x, tables, 19, ws, nbytes, seed=0, noise=noise)        # the solver's tables have no sigma: NULL
+    assert plan._lib.ddk_sampler_run_multistep(a, CC.timestep_map(use), L.ptr(tables["c3"]), L.stream()) == -1     # DDK_ERR_ARG
     assert "noise" in L.last_error()
 
 
@@ -219,17 +199,9 @@ def test_state_dict_keys_unchanged_after_2m_sample():
 
 
 def test_generate_model_samples_dpm_solver_cli(tmp_path):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cfg = dddpm_cfg(32, 32, 2)
-    cfg.update(model="dddpm", dataset="celeba", T=100)
-    cfg_path = tmp_path / "cfg.json"
-    cfg_path.write_text(json.dumps(cfg))
-    env = dict(os.environ, PYTHONPATH=os.path.join(root, "downsampled-diffusion_amd"))
-    script = os.path.join(root, "downsampled-diffusion_amd", "generate_model_samples.py")
-    r = subprocess.run([sys.executable, script, "--synthetic", str(cfg_path), "--saved_model", "clitest", "--fid_samples", "4",
-                        "--batch_size", "2", "--out_dir", str(tmp_path), "--timestep_respacing", "logsnr10", "--dpm_solver"],
-                       capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
+    cfg_path, _, _, env = CC.cli_files(tmp_path, CC.cli_cfg("dddpm"), 0, 32)
+    CC.run_script("generate_model_samples.py", "--synthetic", cfg_path, "--saved_model", "clitest", "--fid_samples", "4", "--batch_size", "2",
+                  "--out_dir", tmp_path, "--timestep_respacing", "logsnr10", "--dpm_solver", env=env)
     imgs = np.load(tmp_path / "clitest_logsnr10_dpmpp2m.npy")
     assert imgs.shape == (2, 2, 32, 32, 3) and imgs.min() == 0.0 and abs(imgs.max() - 255.0) < 1e-3
     assert np.load(tmp_path / "clitest_logsnr10_dpmpp2m_latent.npy").shape == (2, 2, 8, 8, 8)

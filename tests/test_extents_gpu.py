@@ -212,14 +212,12 @@ def _restore_case(kind):
     and test_colorize_gpu.py: the restatement's step on the same inputs and the device's own draws, bit for bit; y is NaN wherever the
     mask is 0"""
     def build(ops):
+        import chain_cases as CC
         import restore_gray_ref as RG
         import restore_masked_ref as RM
         import restore_noisy_ref as RN
         import restore_ref as RR
         import restore_solver_ref as RS
-        from test_colorize_gpu import _hand_tables as gray_tables
-        from test_restore_noisy_gpu import _hand_tables as noisy_tables
-        from test_restore_noisy_gpu import _mask, _sel
         B, c, h, w, n = 3, 3, 16, 16, 2
         g = torch.Generator().manual_seed(17 * n + c + h)
         shape = (B, c, h, w)
@@ -231,13 +229,15 @@ def _restore_case(kind):
             tab = _hand(g, ("c_recip", "c_recipm1", "c1", "c2", "c3"))
             tab["c1"][0], tab["c2"][0], tab["c3"][0], tab["c3"][3] = 1.0, 0.0, 0.0, 0.0
         elif kind in ("noisy", "gray"):
-            tab = (noisy_tables if kind == "noisy" else gray_tables)(g)
+            tab = CC.hand_tables(g, noisy=True)
+            if kind == "gray":              # as tests/test_colorize_gpu.py: this kind's row 0 has lam = 1
+                tab["lam"][0] = 1.0
         else:
             tab = _hand(g, ("c_recip", "c_recipm1", "c1", "c2", "sigma"))
             tab["c1"][0], tab["c2"][0] = 1.0, 0.0
         seed, stream = 24680, 5
-        mk = None if kind == "plain" else _mask("checker", B, h // n, w // n)
-        y = y0 if mk is None else torch.where(_sel(mk, y0), y0, torch.full_like(y0, float("nan")))
+        mk = None if kind == "plain" else CC.mask("checker", B, h // n, w // n)
+        y = y0 if mk is None else torch.where(CC.sel(mk, y0), y0, torch.full_like(y0, float("nan")))
         ed, td, dtab = nhwc(e).to(DEV), t.to(DEV), _to_dev(tab)
         yd = (y[:, 0].contiguous() if kind == "gray" else nhwc(y)).to(DEV)
         md = None if mk is None else mk.to(DEV)

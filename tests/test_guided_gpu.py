@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import chain_cases as CC
 import guidance_ref as GR
 from guard import guard_bands, rehouse
 from helpers import dddpm_cfg, ddpm_cfg, det_load, rel_err, to_nchw, to_nhwc
@@ -543,23 +544,10 @@ def test_the_evaluator_scores_the_method_on_both_model_kinds(task, kw):
 def test_guided_cli(tmp_path):
     """guided_model_samples.py on a dDDPM with synthetic weights: clean images measured here through a sensor that clips, with noise,
     restored in three steps; both files written"""
-    import json
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cfg = dddpm_cfg(32, 32, 2)
-    cfg.update(model="dddpm", dataset="celeba", T=100)
-    (tmp_path / "cfg.json").write_text(json.dumps(cfg))
-    imgs = (np.random.default_rng(0).random((3, 32, 32, 3)) * 255).astype(np.uint8)
-    np.save(tmp_path / "imgs.npy", imgs)
-    env = dict(os.environ, PYTHONPATH=os.path.join(root, "downsampled-diffusion_amd"))
-    script = os.path.join(root, "downsampled-diffusion_amd", "guided_model_samples.py")
-    r = subprocess.run([sys.executable, script, "--synthetic", str(tmp_path / "cfg.json"), "--saved_model", "clitest", "--images",
-                        str(tmp_path / "imgs.npy"), "--task", "sr", "--scale", "4", "--measure_input", "--saturate", "2.5", "--sigma_y", "0.05",
-                        "--zeta", "0.5", "--timestep_respacing", "3", "--batch_size", "2", "--out_dir", str(tmp_path)], capture_output=True,
-                       text=True, env=env, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
+    cfg_path, images_path, _, env = CC.cli_files(tmp_path, CC.cli_cfg("dddpm"), 3, 32)
+    CC.run_script("guided_model_samples.py", "--synthetic", cfg_path, "--saved_model", "clitest", "--images", images_path, "--task", "sr",
+                  "--scale", "4", "--measure_input", "--saturate", "2.5", "--sigma_y", "0.05", "--zeta", "0.5", "--timestep_respacing", "3",
+                  "--batch_size", "2", "--out_dir", tmp_path, env=env)
     name = "clitest_guided_sr_x4_sat2.5_z0.5_3_sy0.05"
     out, measured = np.load(tmp_path / f"{name}.npy"), np.load(tmp_path / f"{name}_measured.npy")
     assert out.shape == (3, 32, 32, 3) and out.dtype == np.float32 and out.min() >= 0 and out.max() <= 255 and np.isfinite(out).all()

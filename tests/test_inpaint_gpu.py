@@ -6,15 +6,11 @@ The tiny DDPM (unet_chan 32, 3x16x16) has no Winograd final conv, so its ops end
 "20", j = 5, r = 3 chain has 50 ops, so the one-step and the 16-step graphs both run.  The cfg4 latent at B = 32 ends in
 final_tail_kernel's inpainting instantiation.  Bars as for the spaced chains: 1e-4 abs against the restatement, 1e-5 between the
 Python loop and the native sampler."""
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 import torch
 
+import chain_cases as CC
 import repaint_ref as RP
 from helpers import dddpm_cfg, ddpm_cfg, det_load, unet_cfg
 from oracle import diffusion_ref as D
@@ -33,10 +29,7 @@ KW = dict(respacing="20", jump_length=5, jump_n_sample=3)
 
 @pytest.fixture(scope="module")
 def tiny():
-    from models import DDPM, Unet
-    m = det_load(DDPM(CFG, Unet(CFG), DEV, 3)).to(DEV).eval()
-    sd = {k: v.detach().cpu() for k, v in m.state_dict().items()}
-    return m, (lambda x, t: U.unet_forward(sd, CFG, x, t, pre="latent_model."))
+    return CC.tiny_ddpm(CFG)
 
 
 @pytest.fixture(scope="module")
@@ -48,15 +41,11 @@ def data():
     return x, mask, syn.synthetic_normal(SHAPE, "inpaint.xT")
 
 
-def _argmax(x):
-    return x.reshape(x.shape[0], -1).argmax(dim=1)
-
-
 def _check(got, want, tol=TOL):
     err = float((got.cpu() - want).abs().max())
     assert torch.isfinite(got).all()
     assert err < tol, err
-    assert torch.equal(_argmax(got.cpu()), _argmax(want))
+    assert torch.equal(CC.argmax(got.cpu()), CC.argmax(want))
     return err
 
 
@@ -86,11 +75,8 @@ def test_graph_equals_eager_bit_for_bit(tiny, data):
     m, _ = tiny
     x, mask, x_T = data
     graphed = m.inpaint(x.to(DEV), mask.to(DEV), x_T=x_T, seed=SEED, **KW)
-    m.use_graph = False
-    try:
+    with CC.toggled(m, "use_graph", False):
         eager = m.inpaint(x.to(DEV), mask.to(DEV), x_T=x_T, seed=SEED, **KW)
-    finally:
-        m.use_graph = True
     assert torch.equal(graphed, eager)
 
 
@@ -98,11 +84,8 @@ def test_python_loop_equals_native(tiny, data):
     m, _ = tiny
     x, mask, x_T = data
     native = m.inpaint(x.to(DEV), mask.to(DEV), x_T=x_T, seed=SEED, **KW)
-    m.native_sampler = False
-    try:
+    with CC.toggled(m, "native_sampler", False):
         loop = m.inpaint(x.to(DEV), mask.to(DEV), x_T=x_T, seed=SEED, **KW)
-    finally:
-        m.native_sampler = True
     err = float((loop - native).abs().max())
     print(f"Python loop vs native, RePaint 50 ops: {err:.3g}")
     assert err < 1e-5
@@ -186,9 +169,7 @@ def test_library_rejects_bad_arguments(tiny, data):
     ws = torch.empty(nbytes // 4, device=DEV)
 
     def run(tmap, noise=None, stream_id=0):
-        a = L.SamplerArgs(plan.handle, L.ptr(plan.packed), L.ptr(x), L.ptr(noise), L.ptr(tables["c_recip"]), L.ptr(tables["c_recipm1"]),
-                          L.ptr(tables["c1"]), L.ptr(tables["c2"]), L.ptr(tables["sigma"]), 2, 16, 16, n - 1, 0, 0, stream_id, 0,
-                          L.ptr(ws), nbytes)
+        a = CC.sampler_args(plan, x, tables, n - 1, ws, nbytes, seed=0, stream_id=stream_id, noise=noise)
         ip = L.InpaintArgs((C.c_int64 * n)(*tmap), L.ptr(known), L.ptr(known), L.ptr(tables["ka"]), L.ptr(tables["kb"]),
                            L.ptr(tables["ja"]), L.ptr(tables["jb"]))
         return plan._lib.ddk_sampler_run_inpaint(C.byref(a), C.byref(ip), L.stream())
@@ -248,20 +229,9 @@ def test_dddpm_inpaint_hidden_pixels_never_read():
 
 
 def test_inpaint_cli(tmp_path):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cfg = dddpm_cfg(32, 32, 2)
-    cfg.update(model="dddpm", dataset="celeba", T=100)
-    cfg_path = tmp_path / "cfg.json"
-    cfg_path.write_text(json.dumps(cfg))
-    imgs = (np.random.default_rng(0).random((3, 32, 32, 3)) * 255).astype(np.uint8)
-    np.save(tmp_path / "imgs.npy", imgs)
-    env = dict(os.environ, PYTHONPATH=os.path.join(root, "downsampled-diffusion_amd"))
-    script = os.path.join(root, "downsampled-diffusion_amd", "inpaint_model_samples.py")
-    r = subprocess.run([sys.executable, script, "--synthetic", str(cfg_path), "--saved_model", "clitest", "--images",
-                        str(tmp_path / "imgs.npy"), "--mask", "center", "--timestep_respacing", "10", "--jump_length", "3",
-                        "--jump_n_sample", "2", "--batch_size", "2", "--out_dir", str(tmp_path)], capture_output=True, text=True,
-                       env=env, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
+    cfg_path, images_path, imgs, env = CC.cli_files(tmp_path, CC.cli_cfg("dddpm"), 3, 32)
+    CC.run_script("inpaint_model_samples.py", "--synthetic", cfg_path, "--saved_model", "clitest", "--images", images_path, "--mask", "center",
+                  "--timestep_respacing", "10", "--jump_length", "3", "--jump_n_sample", "2", "--batch_size", "2", "--out_dir", tmp_path, env=env)
     out = np.load(tmp_path / "clitest_inpaint_center_10_j3r2.npy")
     masked = np.load(tmp_path / "clitest_inpaint_center_10_j3r2_masked.npy")
     assert out.shape == (3, 32, 32, 3) and masked.shape == (3, 32, 32, 3)

@@ -12,21 +12,16 @@ same three magnitudes.  c1 scales that into the result; the update's own five ro
 elementwise, every element compared.  Shapes: both forms (an image of at most 64 KB takes one launch, a larger one two), one and
 eight channels, W != H, sizes that are not a power of two.  Chains: 1e-4 abs against the restatement with the same argmax and 1e-5
 between the Python loop and the native sampler, as for the other restore kinds; graph replay equals eager launches bit for bit."""
-import ctypes as C
 import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import blur_ref as BR
-from helpers import ddpm_cfg, det_load
+import chain_cases as CC
+from helpers import ddpm_cfg, to_nchw as nchw, to_nhwc as nhwc
 from oracle import diffusion_ref as D
-from oracle import philox_ref as PR
-from oracle import unet_ref as U
 from utils import synthetic as syn
 
 pytestmark = pytest.mark.gpu
@@ -41,9 +36,6 @@ IDS = ["ancestral", "ddim"]
 U24 = 2.0 ** -24
 ONE_LAUNCH = [(3, 16, 16), (1, 16, 16), (4, 32, 32), (3, 64, 64), (3, 16, 48), (8, 32, 16)]
 TWO_LAUNCH = [(3, 128, 128), (3, 256, 256), (8, 64, 64), (3, 80, 144)]
-
-nhwc = lambda v: v.permute(0, 2, 3, 1).contiguous()
-nchw = lambda v: v.permute(0, 3, 1, 2).contiguous()
 
 
 def _first_term(P_h, P_w, x0_abs, Yp, H, W):
@@ -64,19 +56,7 @@ def _inputs(c, h, w, B, seed):
     e = torch.randn(shape, generator=g)
     yp = torch.rand(shape, generator=g) * 2 - 1
     t = torch.tensor([0, 7, 3])[:B]
-    tab = {k: torch.rand(8, generator=g) * s for k, s in (("c_recip", 3.0), ("c_recipm1", 2.0), ("c1", 1.0), ("c2", 1.0), ("sigma", 0.5))}
-    tab["c1"][0], tab["c2"][0] = 1.0, 0.0
-    return x, e, yp, t, tab
-
-
-def _draws(B, c, h, w, t, seed, stream):
-    """the device's own draws (ddk_randn: the op's Philox call and keying), checked against oracle/philox_ref"""
-    from ddk import ops
-    z_dev = torch.stack([ops.randn((B, h, w, c), DEV, seed, int(tb), stream)[b] for b, tb in enumerate(t)]).cpu()
-    z_ref = torch.from_numpy(np.stack([PR.philox_normal(B * h * w * c, seed, int(tb), stream).reshape(B, h, w, c)[b]
-                                       for b, tb in enumerate(t)]))
-    assert float((z_dev - z_ref).abs().max()) < 1e-5
-    return nchw(z_dev)
+    return x, e, yp, t, CC.hand_tables(g)
 
 
 # ---------------------------------------------------------------- the lone op against the restatement
@@ -86,7 +66,7 @@ def test_lone_op_within_the_derived_bar(c, h, w):
     B = 1 if h * w >= 256 * 256 else 3
     x, e, yp, t, tab = _inputs(c, h, w, B, 31 * c + h + w)
     seed, stream = 97531, 4
-    z = _draws(B, c, h, w, t, seed, stream)
+    z = CC.philox_draws(B, c, h, w, t, seed, stream)
     m, md = _mats("uniform" if h >= 32 else "gauss", h, w)
     sg = torch.where(t > 0, tab["sigma"][t], torch.zeros(B))
     want, x0, x0p = BR.step(x, e, m["P_h"].double(), m["P_w"].double(), yp, tab["c_recip"][t], tab["c_recipm1"][t], tab["c1"][t],
@@ -197,30 +177,23 @@ def test_chain_faults(tiny):
     plan = m._eps_model_nhwc().plan()
     lib = plan._lib
     K = len(use)
-    tmap = (C.c_int64 * K)(*[int(v) for v in use])
+    tmap = CC.timestep_map(use)
     nbytes = lib.ddk_sampler_restore_blur_workspace_bytes(plan.handle, 2, 16, 16, K - 1)
     assert nbytes > 0
     _, md = _mats("gauss", 16, 16)
     x = torch.zeros(2, 16, 16, 3, device=DEV)
     y = torch.zeros_like(x)
-    ws = torch.empty(nbytes // 4 + 4, device=DEV)
+    ws = CC.fresh_workspace(nbytes)
     noise = torch.zeros((K, *x.shape), device=DEV)
-
-    def args(noise=None, H=16, W=16):
-        return L.SamplerArgs(plan.handle, L.ptr(plan.packed), L.ptr(x), L.ptr(noise), L.ptr(tables["c_recip"]), L.ptr(tables["c_recipm1"]),
-                             L.ptr(tables["c1"]), L.ptr(tables["c2"]), L.ptr(tables["sigma"]), 2, H, W, K - 1, 0, SEED, 0, 0, L.ptr(ws), nbytes)
+    args = lambda noise=None, H=16: CC.sampler_args(plan, x, tables, K - 1, ws, nbytes, seed=SEED, noise=noise, shape=(2, H, 16))
     mats = [L.ptr(md[k]) for k in ("P_h", "P_w", "Q_h", "Q_w")]
-    a = args(noise)
-    assert lib.ddk_sampler_run_restore_blur(C.byref(a), tmap, *mats, L.ptr(y), L.stream()) == -1 and "noise" in L.last_error()
+    assert lib.ddk_sampler_run_restore_blur(args(noise), tmap, *mats, L.ptr(y), L.stream()) == -1 and "noise" in L.last_error()
     for i in range(4):
-        a = args()
         bad = list(mats)
         bad[i] = None
-        assert lib.ddk_sampler_run_restore_blur(C.byref(a), tmap, *bad, L.ptr(y), L.stream()) == -1 and "null" in L.last_error()
-    a = args()
-    assert lib.ddk_sampler_run_restore_blur(C.byref(a), tmap, *mats, None, L.stream()) == -1
-    a = args(H=24)
-    assert lib.ddk_sampler_run_restore_blur(C.byref(a), tmap, *mats, L.ptr(y), L.stream()) == -1 and "multiples of 16" in L.last_error()
+        assert lib.ddk_sampler_run_restore_blur(args(), tmap, *bad, L.ptr(y), L.stream()) == -1 and "null" in L.last_error()
+    assert lib.ddk_sampler_run_restore_blur(args(), tmap, *mats, None, L.stream()) == -1
+    assert lib.ddk_sampler_run_restore_blur(args(H=24), tmap, *mats, L.ptr(y), L.stream()) == -1 and "multiples of 16" in L.last_error()
     torch.cuda.synchronize()
     assert float(x.abs().max()) == 0.0
     with pytest.raises(L.DDKError):
@@ -230,10 +203,7 @@ def test_chain_faults(tiny):
 # ---------------------------------------------------------------- the tiny DDPM, "20" steps
 @pytest.fixture(scope="module")
 def tiny():
-    from models import DDPM, Unet
-    m = det_load(DDPM(CFG, Unet(CFG), DEV, 3)).to(DEV).eval()
-    sd = {k: v.detach().cpu() for k, v in m.state_dict().items()}
-    return m, (lambda x, t: U.unet_forward(sd, CFG, x, t, pre="latent_model."))
+    return CC.tiny_ddpm(CFG)
 
 
 KERNELS = ["gauss", "uniform"]      # at 16 x 16 the gauss kernel keeps all 16 singular values of an axis (x_out is A+ y whatever the
@@ -258,10 +228,6 @@ def reference(tiny, data):
     return {(k, i): BR.Deblur(BETAS, "20").run(eps, x_T, ys[k], k, SEED, **kw) for k in KERNELS for i, kw in zip(IDS, KINDS)}
 
 
-def _argmax(x):
-    return x.reshape(x.shape[0], -1).argmax(dim=1)
-
-
 @pytest.mark.parametrize("kernel", KERNELS)
 @pytest.mark.parametrize("kw", KINDS, ids=IDS)
 def test_tiny_vs_restatement(tiny, data, reference, kw, kernel):
@@ -273,7 +239,7 @@ def test_tiny_vs_restatement(tiny, data, reference, kw, kernel):
     print(f"DDNM deblur ({kernel}) tiny DDPM, 20 steps {kw}: max abs error {err:.3g}")
     assert torch.isfinite(got).all() and got.shape == SHAPE
     assert err < TOL, err
-    assert torch.equal(_argmax(got), _argmax(want))
+    assert torch.equal(CC.argmax(got), CC.argmax(want))
     # the invariant: the range-space part of the result is A+ y.  Row 0 has c1 = 1 and |x0| <= 1 (clamped), which bounds the first term.
     mm = {k: v.float().double() for k, v in BR.operands(kernel, 16, 16).items()}
     Yp = BR.apply(y, mm["Q_h"], mm["Q_w"])
@@ -293,11 +259,8 @@ def test_graph_equals_eager_bit_for_bit(tiny, data, kw, kernel):
     m, _ = tiny
     y, x_T = data[0][kernel], data[1]
     graphed = m.deblur(y.to(DEV), kernel, respacing="20", x_T=x_T, seed=SEED, **kw)
-    m.use_graph = False
-    try:
+    with CC.toggled(m, "use_graph", False):
         eager = m.deblur(y.to(DEV), kernel, respacing="20", x_T=x_T, seed=SEED, **kw)
-    finally:
-        m.use_graph = True
     assert torch.equal(graphed, eager)
 
 
@@ -307,11 +270,8 @@ def test_python_loop_equals_native(tiny, data, kw, kernel):
     m, _ = tiny
     y, x_T = data[0][kernel], data[1]
     native = m.deblur(y.to(DEV), kernel, respacing="20", x_T=x_T, seed=SEED, **kw)
-    m.native_sampler = False
-    try:
+    with CC.toggled(m, "native_sampler", False):
         loop = m.deblur(y.to(DEV), kernel, respacing="20", x_T=x_T, seed=SEED, **kw)
-    finally:
-        m.native_sampler = True
     err = float((loop - native).abs().max())
     print(f"Python loop vs native, deblur ({kernel}) 20 steps {kw}: {err:.3g}")
     assert err < 1e-5
@@ -342,35 +302,23 @@ def test_blur_and_ancestral_chains_share_a_workspace(tiny, data):
     plan = m._eps_model_nhwc().plan()
     lib = plan._lib
     K = len(use)
-    tmap = (C.c_int64 * K)(*[int(v) for v in use])
     nbytes = lib.ddk_sampler_restore_blur_workspace_bytes(plan.handle, 2, 16, 16, K - 1)
     assert nbytes == lib.ddk_sampler_workspace_bytes(plan.handle, 2, 16, 16, K - 1) + 4 * (2 * 16 * 16 + 2 * 2 * 16 * 16 * 3)
     md = m._blur_operands("uniform", 3e-2)       # the model's own cached operands
     mats = [L.ptr(md[k]) for k in ("P_h", "P_w", "Q_h", "Q_w")]
     x0 = ops.nchw_to_nhwc(x_T.to(DEV).contiguous())
     ys = {"a": ops.nchw_to_nhwc(y.to(DEV)), "b": ops.nchw_to_nhwc((0.5 * y).to(DEV))}
-    x = torch.empty_like(x0)
-    ws = torch.empty(nbytes // 4 + 4, device=DEV)
-    side = torch.cuda.Stream()
 
-    def run(what):
-        x.copy_(x0)
-        torch.cuda.synchronize()
-        a = L.SamplerArgs(plan.handle, L.ptr(plan.packed), L.ptr(x), None, L.ptr(tables["c_recip"]), L.ptr(tables["c_recipm1"]),
-                          L.ptr(tables["c1"]), L.ptr(tables["c2"]), L.ptr(tables["sigma"]), 2, 16, 16, K - 1, 0, SEED, 0, 1, L.ptr(ws), nbytes)
-        with torch.cuda.stream(side):
-            if what is None:
-                rc = lib.ddk_sampler_run_spaced(C.byref(a), tmap, side.cuda_stream)
-            else:
-                rc = lib.ddk_sampler_run_restore_blur(C.byref(a), tmap, *mats, L.ptr(ys[what]), side.cuda_stream)
-        assert rc == 0, L.last_error()
-        side.synchronize()
-        return x.clone()
+    def launch(what, a, tmap, stream):
+        if what is None:
+            return lib.ddk_sampler_run_spaced(a, tmap, stream)
+        return lib.ddk_sampler_run_restore_blur(a, tmap, *mats, L.ptr(ys[what]), stream)
 
-    try:
+    sh = CC.SharedWorkspace(plan, tables, use, x0, nbytes, SEED, launch)
+    with CC.workspace(plan, nbytes) as ws:
         first = {}
         for what in ("a", None, "a", None, "b", "a", None, "b"):
-            got = run(what)
+            got = sh.run(ws, what)
             if what not in first:
                 first[what] = got
             assert torch.equal(got, first[what]), (what, float((got - first[what]).abs().max()))
@@ -378,29 +326,16 @@ def test_blur_and_ancestral_chains_share_a_workspace(tiny, data):
         # the library's own entry and the model's method are the same chain
         via_model = m.deblur(y.to(DEV), "uniform", respacing="20", x_T=x_T, seed=SEED)
         assert torch.equal(ops.nhwc_to_nchw(first["a"]), via_model)
-    finally:      # the plan's cached graphs and shift table point into ws: drop them before the memory goes back
-        assert lib.ddk_sampler_release_workspace(plan.handle, L.ptr(ws)) == 0
 
 
 # ---------------------------------------------------------------- the command line
 def test_deblur_cli_and_evaluator(tmp_path):
     """deblur_model_samples.py (already blurred input, then --blur_input) and evaluate_restoration.py --task deblur with synthetic
     weights on four 16 x 16 images, each in a fresh process: the files, their shapes and the JSON keys"""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cfg = ddpm_cfg(32, 3, 16, T=100)
-    cfg.update(model="ddpm", dataset="celeba")
-    cfg_path = tmp_path / "cfg.json"
-    cfg_path.write_text(json.dumps(cfg))
-    rng = np.random.default_rng(0)
-    imgs = (rng.random((4, 16, 16, 3)) * 255).astype(np.uint8)
-    np.save(tmp_path / "imgs.npy", imgs)
-    env = dict(os.environ, PYTHONPATH=os.path.join(root, "downsampled-diffusion_amd"))
-    script = os.path.join(root, "downsampled-diffusion_amd", "deblur_model_samples.py")
+    cfg_path, images_path, imgs, env = CC.cli_files(tmp_path, CC.cli_cfg(), 4, 16)
     for extra, kernel, spec in (([], "gauss", "10"), (["--blur_input", "--kernel", "uniform", "--use_ddim", "--eta", "0.5"], "uniform", "10_ddim_eta0.5")):
-        r = subprocess.run([sys.executable, script, "--synthetic", str(cfg_path), "--saved_model", "clitest", "--images", str(tmp_path / "imgs.npy"),
-                            "--timestep_respacing", "10", "--batch_size", "3", "--seed", "3", "--out_dir", str(tmp_path), *extra],
-                           capture_output=True, text=True, env=env, timeout=300)
-        assert r.returncode == 0, r.stderr[-2000:]
+        CC.run_script("deblur_model_samples.py", "--synthetic", cfg_path, "--saved_model", "clitest", "--images", images_path,
+                      "--timestep_respacing", "10", "--batch_size", "3", "--seed", "3", "--out_dir", tmp_path, *extra, env=env)
         out = np.load(tmp_path / f"clitest_deblur_{kernel}_{spec}.npy")
         blurred = np.load(tmp_path / f"clitest_deblur_{kernel}_{spec}_blurred.npy")
         assert out.shape == (4, 16, 16, 3) and out.dtype == np.float32
@@ -413,11 +348,8 @@ def test_deblur_cli_and_evaluator(tmp_path):
             want = BR.apply(torch.from_numpy(imgs.astype(np.float64)).permute(0, 3, 1, 2) / 255 * 2 - 1, m["A_h"], m["A_w"])
             want = ((want + 1) * 127.5).round().clamp(0, 255).permute(0, 2, 3, 1).numpy()
             assert np.abs(blurred.astype(np.float64) - want).max() <= 1      # a rounding tie may fall either way in fp32
-    script = os.path.join(root, "downsampled-diffusion_amd", "evaluate_restoration.py")
-    r = subprocess.run([sys.executable, script, "--synthetic", str(cfg_path), "--images", str(tmp_path / "imgs.npy"), "--task", "deblur",
-                        "--kernel", "uniform", "--timestep_respacing", "10", "--batch_size", "3", "--json", str(tmp_path / "score.json")],
-                       capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
+    CC.run_script("evaluate_restoration.py", "--synthetic", cfg_path, "--images", images_path, "--task", "deblur", "--kernel", "uniform",
+                  "--timestep_respacing", "10", "--batch_size", "3", "--json", tmp_path / "score.json", env=env)
     res = json.loads((tmp_path / "score.json").read_text())
     s, mt = res["settings"], res["metrics"]
     assert (s["task"], s["method"], s["kernel"], s["tol"], s["unet_forwards"], s["n_images"]) == ("deblur", "ddnm_blur", "uniform", 0.03, 10, 4)

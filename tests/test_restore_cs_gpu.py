@@ -16,22 +16,17 @@ L u sum |input| / sqrt(N).
 Shapes: both kernel forms (a plane of at most 32768 pixels takes one launch, a 256 x 256 plane three), one, three and eight channels,
 W != H, N = 512 where s is no power of two.  Chains: 1e-4 abs against the restatement with the same argmax and 1e-5 between the
 Python loop and the native sampler, as for the other restore kinds; graph replay equals eager launches bit for bit."""
-import ctypes as C
 import json
 import math
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
+import chain_cases as CC
 import hadamard_ref as HR
-from helpers import ddpm_cfg, det_load
+from helpers import ddpm_cfg, to_nchw as nchw, to_nhwc as nhwc
 from oracle import diffusion_ref as D
-from oracle import philox_ref as PR
-from oracle import unet_ref as U
 from utils import synthetic as syn
 
 pytestmark = pytest.mark.gpu
@@ -56,9 +51,6 @@ def _rows(N):
 CASES = [(c, h, w, b, m) for c, h, w, b in SHAPES for m in _rows(h * w)]
 EXACT_CASES = [(c, h, w, b, m) for c, h, w, b in EXACT for m in _rows(h * w)]
 
-nhwc = lambda v: v.permute(0, 2, 3, 1).contiguous()
-nchw = lambda v: v.permute(0, 3, 1, 2).contiguous()
-
 
 def _perm(N, seed=0):
     return np.random.default_rng(seed).permutation(N).astype(np.int32)
@@ -75,19 +67,7 @@ def _inputs(c, h, w, B, m, seed):
     e = torch.randn(shape, generator=g)
     y = (torch.rand((B, c, m), generator=g) * 2 - 1).contiguous()
     t = torch.tensor([0, 7, 3])[:B]
-    tab = {k: torch.rand(8, generator=g) * s for k, s in (("c_recip", 3.0), ("c_recipm1", 2.0), ("c1", 1.0), ("c2", 1.0), ("sigma", 0.5))}
-    tab["c1"][0], tab["c2"][0] = 1.0, 0.0
-    return x, e, y, t, tab
-
-
-def _draws(B, c, h, w, t, seed, stream):
-    """the device's own draws (ddk_randn: the op's Philox call and keying), checked against oracle/philox_ref"""
-    from ddk import ops
-    z_dev = torch.stack([ops.randn((B, h, w, c), DEV, seed, int(tb), stream)[b] for b, tb in enumerate(t)]).cpu()
-    z_ref = torch.from_numpy(np.stack([PR.philox_normal(B * h * w * c, seed, int(tb), stream).reshape(B, h, w, c)[b]
-                                       for b, tb in enumerate(t)]))
-    assert float((z_dev - z_ref).abs().max()) < 1e-5
-    return nchw(z_dev)
+    return x, e, y, t, CC.hand_tables(g)
 
 
 def _plane_sum(v):
@@ -192,7 +172,7 @@ def test_lone_op_within_the_derived_bar(c, h, w, B, m):
     N = h * w
     x, e, y, t, tab = _inputs(c, h, w, B, m, 31 * c + h + w + m)
     seed, stream = 97531, 4
-    z = _draws(B, c, h, w, t, seed, stream)
+    z = CC.philox_draws(B, c, h, w, t, seed, stream)
     perm = _perm(N, m)
     sg = torch.where(t > 0, tab["sigma"][t], torch.zeros(B))
     want, x0, x0p, wsel = HR.step(x, e, y.double().numpy(), perm, tab["c_recip"][t], tab["c_recipm1"][t], tab["c1"][t], tab["c2"][t], sg, z)
@@ -300,10 +280,7 @@ def test_argument_faults_run_no_kernel():
 # ---------------------------------------------------------------- 4. the tiny DDPM, "8" steps
 @pytest.fixture(scope="module")
 def tiny():
-    from models import DDPM, Unet
-    m = det_load(DDPM(CFG, Unet(CFG), DEV, 3)).to(DEV).eval()
-    sd = {k: v.detach().cpu() for k, v in m.state_dict().items()}
-    return m, (lambda x, t: U.unet_forward(sd, CFG, x, t, pre="latent_model."))
+    return CC.tiny_ddpm(CFG)
 
 
 M_TINY = 100
@@ -326,10 +303,6 @@ def reference(tiny, data):
     return {i: HR.CS(BETAS, "8").run(eps, x_T, y, PERM_TINY, SEED, **kw) for i, kw in zip(IDS, KINDS)}
 
 
-def _argmax(x):
-    return x.reshape(x.shape[0], -1).argmax(dim=1)
-
-
 @pytest.mark.parametrize("kw", KINDS, ids=IDS)
 def test_tiny_vs_restatement(tiny, data, reference, kw):
     m, _ = tiny
@@ -340,7 +313,7 @@ def test_tiny_vs_restatement(tiny, data, reference, kw):
     print(f"DDNM cs tiny DDPM, 8 steps {kw}: max abs error {err:.3g}")
     assert torch.isfinite(got).all() and got.shape == SHAPE
     assert err < TOL, err
-    assert torch.equal(_argmax(got), _argmax(want))
+    assert torch.equal(CC.argmax(got), CC.argmax(want))
     # the invariant.  The last row has c1 = 1 and |x0| <= 1 (clamped): alpha <= sqrt(N); w is the result's own transform
     N = 256
     wsel = HR.fwht(HR.planes(got)[..., PERM_TINY.astype(np.int64)])
@@ -357,11 +330,8 @@ def test_graph_equals_eager_bit_for_bit(tiny, data, kw):
     m, _ = tiny
     y, x_T = data
     graphed = m.restore_cs(y.to(DEV), PERM_TINY, respacing="8", x_T=x_T, seed=SEED, **kw)
-    m.use_graph = False
-    try:
+    with CC.toggled(m, "use_graph", False):
         eager = m.restore_cs(y.to(DEV), PERM_TINY, respacing="8", x_T=x_T, seed=SEED, **kw)
-    finally:
-        m.use_graph = True
     assert torch.equal(graphed, eager)
 
 
@@ -370,11 +340,8 @@ def test_python_loop_equals_native(tiny, data, kw):
     m, _ = tiny
     y, x_T = data
     native = m.restore_cs(y.to(DEV), respacing="8", x_T=x_T, seed=SEED, **kw)
-    m.native_sampler = False
-    try:
+    with CC.toggled(m, "native_sampler", False):
         loop = m.restore_cs(y.to(DEV), respacing="8", x_T=x_T, seed=SEED, **kw)
-    finally:
-        m.native_sampler = True
     err = float((loop - native).abs().max())
     print(f"Python loop vs native, cs 8 steps {kw}: {err:.3g}")
     assert err < 1e-5
@@ -404,34 +371,22 @@ def test_cs_and_ancestral_chains_share_a_workspace(tiny, data, reference):
     plan = m._eps_model_nhwc().plan()
     lib = plan._lib
     K = len(use)
-    tmap = (C.c_int64 * K)(*[int(v) for v in use])
     nbytes = lib.ddk_sampler_restore_cs_workspace_bytes(plan.handle, 2, 16, 16, K - 1)
     assert nbytes == lib.ddk_sampler_workspace_bytes(plan.handle, 2, 16, 16, K - 1) + 4 * (16 * 16 + 2 * 2 * 16 * 16 * 3)
     pd = _dev(PERM_TINY)
     x0 = ops.nchw_to_nhwc(x_T.to(DEV).contiguous())
     ys = {"a": y.to(DEV), "b": (0.5 * y).to(DEV).contiguous()}
-    x = torch.empty_like(x0)
-    ws = torch.empty(nbytes // 4 + 4, device=DEV)
-    side = torch.cuda.Stream()
 
-    def run(what):
-        x.copy_(x0)
-        torch.cuda.synchronize()
-        a = L.SamplerArgs(plan.handle, L.ptr(plan.packed), L.ptr(x), None, L.ptr(tables["c_recip"]), L.ptr(tables["c_recipm1"]),
-                          L.ptr(tables["c1"]), L.ptr(tables["c2"]), L.ptr(tables["sigma"]), 2, 16, 16, K - 1, 0, SEED, 0, 1, L.ptr(ws), nbytes)
-        with torch.cuda.stream(side):
-            if what is None:
-                rc = lib.ddk_sampler_run_spaced(C.byref(a), tmap, side.cuda_stream)
-            else:
-                rc = lib.ddk_sampler_run_restore_cs(C.byref(a), tmap, L.ptr(ys[what]), L.ptr(pd), M_TINY, side.cuda_stream)
-        assert rc == 0, L.last_error()
-        side.synchronize()
-        return x.clone()
+    def launch(what, a, tmap, stream):
+        if what is None:
+            return lib.ddk_sampler_run_spaced(a, tmap, stream)
+        return lib.ddk_sampler_run_restore_cs(a, tmap, L.ptr(ys[what]), L.ptr(pd), M_TINY, stream)
 
-    try:
+    sh = CC.SharedWorkspace(plan, tables, use, x0, nbytes, SEED, launch)
+    with CC.workspace(plan, nbytes) as ws:
         first = {}
         for what in ("a", None, "a", None, "b", "a", None, "b"):
-            got = run(what)
+            got = sh.run(ws, what)
             if what not in first:
                 first[what] = got
             assert torch.equal(got, first[what]), (what, float((got - first[what]).abs().max()))
@@ -443,8 +398,6 @@ def test_cs_and_ancestral_chains_share_a_workspace(tiny, data, reference):
         assert float((ops.nhwc_to_nchw(first["a"]).cpu() - reference["ancestral"]).abs().max()) < TOL
         want_b = HR.CS(BETAS, "8").run(eps, x_T, 0.5 * y, PERM_TINY, SEED)
         assert float((ops.nhwc_to_nchw(first["b"]).cpu() - want_b).abs().max()) < TOL
-    finally:      # the plan's cached graphs and shift table point into ws: drop them before the memory goes back
-        assert lib.ddk_sampler_release_workspace(plan.handle, L.ptr(ws)) == 0
 
 
 def test_chain_faults(tiny):
@@ -455,25 +408,22 @@ def test_chain_faults(tiny):
     plan = m._eps_model_nhwc().plan()
     lib = plan._lib
     K = len(use)
-    tmap = (C.c_int64 * K)(*[int(v) for v in use])
+    tmap = CC.timestep_map(use)
     nbytes = lib.ddk_sampler_restore_cs_workspace_bytes(plan.handle, 2, 16, 16, K - 1)
     assert nbytes > 0 and lib.ddk_sampler_restore_cs_workspace_bytes(plan.handle, 2, 16, 48, K - 1) == 0
     x = torch.zeros(2, 16, 16, 3, device=DEV)
     y = torch.zeros(2, 3, 100, device=DEV)
     pd = _dev(PERM_TINY)
-    ws = torch.empty(nbytes // 4 + 4, device=DEV)
+    ws = CC.fresh_workspace(nbytes)
     noise = torch.zeros((K, *x.shape), device=DEV)
-
-    def args(noise=None, H=16, W=16):
-        return L.SamplerArgs(plan.handle, L.ptr(plan.packed), L.ptr(x), L.ptr(noise), L.ptr(tables["c_recip"]), L.ptr(tables["c_recipm1"]),
-                             L.ptr(tables["c1"]), L.ptr(tables["c2"]), L.ptr(tables["sigma"]), 2, H, W, K - 1, 0, SEED, 0, 0, L.ptr(ws), nbytes)
+    args = lambda noise=None, H=16: CC.sampler_args(plan, x, tables, K - 1, ws, nbytes, seed=SEED, noise=noise, shape=(2, H, 16))
     run = lib.ddk_sampler_run_restore_cs
-    assert run(C.byref(args(noise)), tmap, L.ptr(y), L.ptr(pd), 100, L.stream()) == -1 and "noise" in L.last_error()
-    assert run(C.byref(args()), tmap, None, L.ptr(pd), 100, L.stream()) == -1 and "null" in L.last_error()
-    assert run(C.byref(args()), tmap, L.ptr(y), None, 100, L.stream()) == -1 and "null" in L.last_error()
+    assert run(args(noise), tmap, L.ptr(y), L.ptr(pd), 100, L.stream()) == -1 and "noise" in L.last_error()
+    assert run(args(), tmap, None, L.ptr(pd), 100, L.stream()) == -1 and "null" in L.last_error()
+    assert run(args(), tmap, L.ptr(y), None, 100, L.stream()) == -1 and "null" in L.last_error()
     for bad in (0, 2, 102, 260):
-        assert run(C.byref(args()), tmap, L.ptr(y), L.ptr(pd), bad, L.stream()) == -1 and "multiple of 4" in L.last_error()
-    assert run(C.byref(args(H=48)), tmap, L.ptr(y), L.ptr(pd), 100, L.stream()) == -1 and "powers of two" in L.last_error()
+        assert run(args(), tmap, L.ptr(y), L.ptr(pd), bad, L.stream()) == -1 and "multiple of 4" in L.last_error()
+    assert run(args(H=48), tmap, L.ptr(y), L.ptr(pd), 100, L.stream()) == -1 and "powers of two" in L.last_error()
     torch.cuda.synchronize()
     assert float(x.abs().max()) == 0.0
     with pytest.raises(L.DDKError):
@@ -483,9 +433,7 @@ def test_chain_faults(tiny):
 def test_scratch_form_chain_256():
     """two steps at 3 x 256 x 256, B = 1, on a 32-wide model: the three-launch form inside a chain.  The native chain against the
     Python loop over the lone op, graph replay against eager launches, and the invariant"""
-    from models import DDPM, Unet
-    cfg = ddpm_cfg(32, 3, 256)
-    m = det_load(DDPM(cfg, Unet(cfg), DEV, 3)).to(DEV).eval()
+    m, _ = CC.tiny_ddpm(ddpm_cfg(32, 3, 256))
     N, mm = 65536, 16384
     shape = (1, 3, 256, 256)
     perm = _perm(N, 1)
@@ -493,17 +441,11 @@ def test_scratch_form_chain_256():
     y = torch.from_numpy(HR.measure(clean, perm, mm)).float().contiguous()
     x_T = syn.synthetic_normal(shape, "cs256.xT")
     native = m.restore_cs(y.to(DEV), perm, respacing="2", x_T=x_T, seed=SEED)
-    m.use_graph = False
-    try:
+    with CC.toggled(m, "use_graph", False):
         eager = m.restore_cs(y.to(DEV), perm, respacing="2", x_T=x_T, seed=SEED)
-    finally:
-        m.use_graph = True
     assert torch.equal(native, eager)
-    m.native_sampler = False
-    try:
+    with CC.toggled(m, "native_sampler", False):
         loop = m.restore_cs(y.to(DEV), perm, respacing="2", x_T=x_T, seed=SEED)
-    finally:
-        m.native_sampler = True
     err = float((loop - native).abs().max())
     print(f"Python loop vs native, cs 256 x 256, 2 steps: {err:.3g}")
     assert torch.isfinite(native).all() and err < 1e-5
@@ -519,20 +461,10 @@ def test_scratch_form_chain_256():
 def test_cs_cli_and_evaluator(tmp_path):
     """cs_model_samples.py --measure_input and evaluate_restoration.py --task cs with synthetic weights on four 16 x 16 images, each in
     a fresh process: the files, their shapes and the JSON keys"""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cfg = ddpm_cfg(32, 3, 16, T=100)
-    cfg.update(model="ddpm", dataset="celeba")
-    cfg_path = tmp_path / "cfg.json"
-    cfg_path.write_text(json.dumps(cfg))
-    rng = np.random.default_rng(0)
-    imgs = (rng.random((4, 16, 16, 3)) * 255).astype(np.uint8)
-    np.save(tmp_path / "imgs.npy", imgs)
-    env = dict(os.environ, PYTHONPATH=os.path.join(root, "downsampled-diffusion_amd"))
-    script = os.path.join(root, "downsampled-diffusion_amd", "cs_model_samples.py")
-    r = subprocess.run([sys.executable, script, "--synthetic", str(cfg_path), "--saved_model", "clitest", "--images", str(tmp_path / "imgs.npy"),
-                        "--measure_input", "--ratio", "0.25", "--perm_seed", "2", "--timestep_respacing", "10", "--batch_size", "3", "--seed", "3",
-                        "--out_dir", str(tmp_path)], capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
+    cfg_path, images_path, imgs, env = CC.cli_files(tmp_path, CC.cli_cfg(), 4, 16)
+    CC.run_script("cs_model_samples.py", "--synthetic", cfg_path, "--saved_model", "clitest", "--images", images_path, "--measure_input",
+                  "--ratio", "0.25", "--perm_seed", "2", "--timestep_respacing", "10", "--batch_size", "3", "--seed", "3", "--out_dir", tmp_path,
+                  env=env)
     out = np.load(tmp_path / "clitest_cs_r0.25_p2_10.npy")
     meas = np.load(tmp_path / "clitest_cs_r0.25_p2_10_measurements.npy")
     assert out.shape == (4, 16, 16, 3) and out.dtype == np.float32
@@ -540,11 +472,8 @@ def test_cs_cli_and_evaluator(tmp_path):
     assert meas.shape == (4, 3, 64) and meas.dtype == np.float32
     want = HR.measure(torch.from_numpy(imgs.astype(np.float64)).permute(0, 3, 1, 2) / 255 * 2 - 1, _perm(256, 2), 64)
     assert np.abs(meas - want).max() < 1e-5
-    script = os.path.join(root, "downsampled-diffusion_amd", "evaluate_restoration.py")
-    r = subprocess.run([sys.executable, script, "--synthetic", str(cfg_path), "--images", str(tmp_path / "imgs.npy"), "--task", "cs",
-                        "--ratio", "0.25", "--timestep_respacing", "10", "--batch_size", "3", "--json", str(tmp_path / "score.json")],
-                       capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
+    CC.run_script("evaluate_restoration.py", "--synthetic", cfg_path, "--images", images_path, "--task", "cs", "--ratio", "0.25",
+                  "--timestep_respacing", "10", "--batch_size", "3", "--json", tmp_path / "score.json", env=env)
     res = json.loads((tmp_path / "score.json").read_text())
     s, mt = res["settings"], res["metrics"]
     assert (s["task"], s["method"], s["ratio"], s["perm_seed"], s["m"], s["unet_forwards"], s["n_images"]) == ("cs", "ddnm_cs", 0.25, 0, 64, 10, 4)

@@ -19,22 +19,17 @@ The bars, per plane in the 2-norm, with u = 2^-24, N = H W and L = log2 N:
 Shapes: both kernel forms (a plane of at most 16384 pixels takes one launch, a larger one three), one to three channels, W != H both
 ways.  Chains: 1e-4 abs against the restatement with the same argmax and 1e-5 between the Python loop and the native sampler, as for
 the other restore kinds; graph replay equals eager launches bit for bit."""
-import ctypes as C
 import json
 import math
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
+import chain_cases as CC
 import fft_conv_ref as FR
-from helpers import ddpm_cfg, det_load
+from helpers import ddpm_cfg, to_nchw as nchw, to_nhwc as nhwc
 from oracle import diffusion_ref as D
-from oracle import philox_ref as PR
-from oracle import unet_ref as U
 from utils import synthetic as syn
 
 pytestmark = pytest.mark.gpu
@@ -52,9 +47,6 @@ PRESETS = ("diag", "disk")
 SHAPES = [(3, 16, 16, 3), (1, 32, 16, 3), (2, 16, 64, 2), (3, 64, 64, 2), (2, 128, 128, 2), (1, 128, 256, 2), (2, 256, 256, 1)]
 PSF_TOL = 3e-2
 
-nhwc = lambda v: v.permute(0, 2, 3, 1).contiguous()
-nchw = lambda v: v.permute(0, 3, 1, 2).contiguous()
-
 
 def _c2f(S):
     """complex [H, W] -> fp32 tensor [H, W, 2] (re, im), and the complex128 array the device then reads"""
@@ -66,16 +58,6 @@ def _norm(v):
     """2-norm per plane of a [B, C, H, W] tensor or array, as a float64 array [B, C]"""
     v = v.detach().double().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float64)
     return np.sqrt((v ** 2).sum(axis=(-2, -1)))
-
-
-def _draws(B, c, h, w, t, seed, stream):
-    """the device's own draws (ddk_randn: the op's Philox call and keying), checked against oracle/philox_ref"""
-    from ddk import ops
-    z_dev = torch.stack([ops.randn((B, h, w, c), DEV, seed, int(tb), stream)[b] for b, tb in enumerate(t)]).cpu()
-    z_ref = torch.from_numpy(np.stack([PR.philox_normal(B * h * w * c, seed, int(tb), stream).reshape(B, h, w, c)[b]
-                                       for b, tb in enumerate(t)]))
-    assert float((z_dev - z_ref).abs().max()) < 1e-5
-    return nchw(z_dev)
 
 
 def _tables(ddim):
@@ -127,7 +109,7 @@ def test_lone_step_within_the_derived_bar(c, h, w, B, name, ddim):
     clean = (0.5 * torch.randn(shape, generator=g)).clamp(-1, 1)
     Yp = torch.from_numpy(FR.apply(FR.apply(clean, FR.spectrum(k, h, w)), FR.pinv_spectrum(k, h, w, PSF_TOL))).float()
     seed, stream = 97531, 4
-    z = _draws(B, c, h, w, t, seed, stream)
+    z = CC.philox_draws(B, c, h, w, t, seed, stream)
     sg = torch.where(t > 0, tab["sigma"][t], torch.zeros(B))
     want, x0, x0p = FR.step(x, e, M, Yp, tab["c_recip"][t], tab["c_recipm1"][t], tab["c1"][t], tab["c2"][t], sg, z)
     col = lambda v: v.reshape(-1, 1).double().numpy()
@@ -219,10 +201,7 @@ def test_argument_faults_run_no_kernel():
 # ---------------------------------------------------------------- 5. the tiny DDPM, "8" steps
 @pytest.fixture(scope="module")
 def tiny():
-    from models import DDPM, Unet
-    m = det_load(DDPM(CFG, Unet(CFG), DEV, 3)).to(DEV).eval()
-    sd = {k: v.detach().cpu() for k, v in m.state_dict().items()}
-    return m, (lambda x, t: U.unet_forward(sd, CFG, x, t, pre="latent_model."))
+    return CC.tiny_ddpm(CFG)
 
 
 PSF_TINY = "disk"
@@ -243,10 +222,6 @@ def reference(tiny, data):
     _, eps = tiny
     y, x_T = data
     return {i: FR.Deconv(BETAS, "8").run(eps, x_T, y, K_TINY, PSF_TOL, SEED, **kw) for i, kw in zip(IDS, KINDS)}
-
-
-def _argmax(x):
-    return x.reshape(x.shape[0], -1).argmax(dim=1)
 
 
 def _invariant(got, y, k, tol):
@@ -273,7 +248,7 @@ def test_tiny_vs_restatement(tiny, data, reference, kw):
     print(f"DDNM deconvolution tiny DDPM, 8 steps {kw}: max abs error {err:.3g}")
     assert torch.isfinite(got).all() and got.shape == SHAPE
     assert err < TOL, err
-    assert torch.equal(_argmax(got), _argmax(want))
+    assert torch.equal(CC.argmax(got), CC.argmax(want))
     inv, bar, Yp = _invariant(got, y, K_TINY, PSF_TOL)
     print(f"  ||A+A x_out - A+y|| worst ratio to the bar {float((inv / bar).max()):.3g}")
     assert (inv <= bar).all()
@@ -286,11 +261,8 @@ def test_graph_equals_eager_bit_for_bit(tiny, data, kw):
     m, _ = tiny
     y, x_T = data
     graphed = m.deconvolve(y.to(DEV), PSF_TINY, respacing="8", x_T=x_T, seed=SEED, **kw)
-    m.use_graph = False
-    try:
+    with CC.toggled(m, "use_graph", False):
         eager = m.deconvolve(y.to(DEV), PSF_TINY, respacing="8", x_T=x_T, seed=SEED, **kw)
-    finally:
-        m.use_graph = True
     assert torch.equal(graphed, eager)
 
 
@@ -299,11 +271,8 @@ def test_python_loop_equals_native(tiny, data, kw):
     m, _ = tiny
     y, x_T = data
     native = m.deconvolve(y.to(DEV), K_TINY, respacing="8", x_T=x_T, seed=SEED, **kw)      # the preset as an array: the same chain
-    m.native_sampler = False
-    try:
+    with CC.toggled(m, "native_sampler", False):
         loop = m.deconvolve(y.to(DEV), PSF_TINY, respacing="8", x_T=x_T, seed=SEED, **kw)
-    finally:
-        m.native_sampler = True
     err = float((loop - native).abs().max())
     print(f"Python loop vs native, deconvolution 8 steps {kw}: {err:.3g}")
     assert err < 1e-5
@@ -342,34 +311,22 @@ def test_deconvolution_and_ancestral_chains_share_a_workspace(tiny, data, refere
     plan = m._eps_model_nhwc().plan()
     lib = plan._lib
     K = len(use)
-    tmap = (C.c_int64 * K)(*[int(v) for v in use])
     nbytes = lib.ddk_sampler_restore_fft_workspace_bytes(plan.handle, 2, 16, 16, K - 1)
     assert nbytes == lib.ddk_sampler_workspace_bytes(plan.handle, 2, 16, 16, K - 1) + 4 * (16 * 16 + 16 + 3 * 2 * 16 * 16 * 3)
     Md, Pd, tw = _chain_operands(m, K_TINY, PSF_TOL, 16, 16)
     x0 = ops.nchw_to_nhwc(x_T.to(DEV).contiguous())
     ys = {"a": ops.nchw_to_nhwc(y.to(DEV).contiguous()), "b": ops.nchw_to_nhwc((0.5 * y).to(DEV).contiguous())}
-    x = torch.empty_like(x0)
-    ws = torch.empty(nbytes // 4 + 4, device=DEV)
-    side = torch.cuda.Stream()
 
-    def run(what):
-        x.copy_(x0)
-        torch.cuda.synchronize()
-        a = L.SamplerArgs(plan.handle, L.ptr(plan.packed), L.ptr(x), None, L.ptr(tables["c_recip"]), L.ptr(tables["c_recipm1"]),
-                          L.ptr(tables["c1"]), L.ptr(tables["c2"]), L.ptr(tables["sigma"]), 2, 16, 16, K - 1, 0, SEED, 0, 1, L.ptr(ws), nbytes)
-        with torch.cuda.stream(side):
-            if what is None:
-                rc = lib.ddk_sampler_run_spaced(C.byref(a), tmap, side.cuda_stream)
-            else:
-                rc = lib.ddk_sampler_run_restore_fft(C.byref(a), tmap, L.ptr(Md), L.ptr(Pd), L.ptr(tw), L.ptr(ys[what]), side.cuda_stream)
-        assert rc == 0, L.last_error()
-        side.synchronize()
-        return x.clone()
+    def launch(what, a, tmap, stream):
+        if what is None:
+            return lib.ddk_sampler_run_spaced(a, tmap, stream)
+        return lib.ddk_sampler_run_restore_fft(a, tmap, L.ptr(Md), L.ptr(Pd), L.ptr(tw), L.ptr(ys[what]), stream)
 
-    try:
+    sh = CC.SharedWorkspace(plan, tables, use, x0, nbytes, SEED, launch)
+    with CC.workspace(plan, nbytes) as ws:
         first = {}
         for what in ("a", None, "a", None, "b", "a", None, "b"):
-            got = run(what)
+            got = sh.run(ws, what)
             if what not in first:
                 first[what] = got
             assert torch.equal(got, first[what]), (what, float((got - first[what]).abs().max()))
@@ -381,8 +338,6 @@ def test_deconvolution_and_ancestral_chains_share_a_workspace(tiny, data, refere
         assert float((ops.nhwc_to_nchw(first["a"]).cpu() - reference["ancestral"]).abs().max()) < TOL
         want_b = FR.Deconv(BETAS, "8").run(eps, x_T, 0.5 * y, K_TINY, PSF_TOL, SEED)
         assert float((ops.nhwc_to_nchw(first["b"]).cpu() - want_b).abs().max()) < TOL
-    finally:      # the plan's cached graphs and shift table point into ws: drop them before the memory goes back
-        assert lib.ddk_sampler_release_workspace(plan.handle, L.ptr(ws)) == 0
 
 
 def test_chain_faults(tiny):
@@ -393,26 +348,23 @@ def test_chain_faults(tiny):
     plan = m._eps_model_nhwc().plan()
     lib = plan._lib
     K = len(use)
-    tmap = (C.c_int64 * K)(*[int(v) for v in use])
+    tmap = CC.timestep_map(use)
     nbytes = lib.ddk_sampler_restore_fft_workspace_bytes(plan.handle, 2, 16, 16, K - 1)
     assert nbytes > 0 and lib.ddk_sampler_restore_fft_workspace_bytes(plan.handle, 2, 16, 48, K - 1) == 0
     x = torch.zeros(2, 16, 16, 3, device=DEV)
     y = torch.zeros(2, 16, 16, 3, device=DEV)
     Md, Pd, tw = _chain_operands(m, K_TINY, PSF_TOL, 16, 16)
-    ws = torch.empty(nbytes // 4 + 4, device=DEV)
+    ws = CC.fresh_workspace(nbytes)
     noise = torch.zeros((K, *x.shape), device=DEV)
-
-    def args(noise=None, H=16, W=16, nbytes=nbytes):
-        return L.SamplerArgs(plan.handle, L.ptr(plan.packed), L.ptr(x), L.ptr(noise), L.ptr(tables["c_recip"]), L.ptr(tables["c_recipm1"]),
-                             L.ptr(tables["c1"]), L.ptr(tables["c2"]), L.ptr(tables["sigma"]), 2, H, W, K - 1, 0, SEED, 0, 0, L.ptr(ws), nbytes)
+    args = lambda noise=None, H=16, nbytes=nbytes: CC.sampler_args(plan, x, tables, K - 1, ws, nbytes, seed=SEED, noise=noise, shape=(2, H, 16))
     run = lib.ddk_sampler_run_restore_fft
     ops4 = (L.ptr(Md), L.ptr(Pd), L.ptr(tw), L.ptr(y))
-    assert run(C.byref(args(noise)), tmap, *ops4, L.stream()) == -1 and "noise" in L.last_error()
+    assert run(args(noise), tmap, *ops4, L.stream()) == -1 and "noise" in L.last_error()
     for i in range(4):
-        assert run(C.byref(args()), tmap, *(None if j == i else p for j, p in enumerate(ops4)), L.stream()) == -1 and "null" in L.last_error()
-    assert run(C.byref(args()), tmap, L.ptr(Md) + 4, *ops4[1:], L.stream()) == -1 and "alignment" in L.last_error()
-    assert run(C.byref(args(H=48)), tmap, *ops4, L.stream()) == -1 and "powers of two" in L.last_error()
-    assert run(C.byref(args(nbytes=nbytes - 4)), tmap, *ops4, L.stream()) != 0      # a short workspace
+        assert run(args(), tmap, *(None if j == i else p for j, p in enumerate(ops4)), L.stream()) == -1 and "null" in L.last_error()
+    assert run(args(), tmap, L.ptr(Md) + 4, *ops4[1:], L.stream()) == -1 and "alignment" in L.last_error()
+    assert run(args(H=48), tmap, *ops4, L.stream()) == -1 and "powers of two" in L.last_error()
+    assert run(args(nbytes=nbytes - 4), tmap, *ops4, L.stream()) != 0      # a short workspace
     torch.cuda.synchronize()
     assert float(x.abs().max()) == 0.0
     with pytest.raises(L.DDKError):
@@ -424,26 +376,18 @@ def test_chain_faults(tiny):
 def test_multi_launch_chain_256():
     """three steps at 3 x 256 x 256, B = 1, on a 32-wide model: the three-launch form inside a chain.  The native chain against the
     Python loop over the lone op, graph replay against eager launches, and the invariant"""
-    from models import DDPM, Unet
-    cfg = ddpm_cfg(32, 3, 256)
-    m = det_load(DDPM(cfg, Unet(cfg), DEV, 3)).to(DEV).eval()
+    m, _ = CC.tiny_ddpm(ddpm_cfg(32, 3, 256))
     shape = (1, 3, 256, 256)
     k = FR.preset("diag")
     clean = 0.25 * syn.synthetic_normal(shape, "deconv256.x")
     y = torch.from_numpy(FR.apply(clean, FR.spectrum(k, 256, 256))).float().contiguous()
     x_T = syn.synthetic_normal(shape, "deconv256.xT")
     native = m.deconvolve(y.to(DEV), "diag", respacing="3", x_T=x_T, seed=SEED)
-    m.use_graph = False
-    try:
+    with CC.toggled(m, "use_graph", False):
         eager = m.deconvolve(y.to(DEV), "diag", respacing="3", x_T=x_T, seed=SEED)
-    finally:
-        m.use_graph = True
     assert torch.equal(native, eager)
-    m.native_sampler = False
-    try:
+    with CC.toggled(m, "native_sampler", False):
         loop = m.deconvolve(y.to(DEV), "diag", respacing="3", x_T=x_T, seed=SEED)
-    finally:
-        m.native_sampler = True
     err = float((loop - native).abs().max())
     print(f"Python loop vs native, deconvolution 256 x 256, 3 steps: {err:.3g}")
     assert torch.isfinite(native).all() and err < 1e-5
@@ -456,22 +400,13 @@ def test_multi_launch_chain_256():
 def test_deconv_cli_and_evaluator(tmp_path):
     """deconv_model_samples.py --blur_input and evaluate_restoration.py --task deconv with synthetic weights on four 16 x 16 images,
     each in a fresh process: the files, their shapes and the JSON keys"""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cfg = ddpm_cfg(32, 3, 16, T=100)
-    cfg.update(model="ddpm", dataset="celeba")
-    cfg_path = tmp_path / "cfg.json"
-    cfg_path.write_text(json.dumps(cfg))
+    cfg_path, images_path, imgs, env = CC.cli_files(tmp_path, CC.cli_cfg(), 4, 16)
     rng = np.random.default_rng(0)
-    imgs = (rng.random((4, 16, 16, 3)) * 255).astype(np.uint8)
-    np.save(tmp_path / "imgs.npy", imgs)
+    rng.random((4, 16, 16, 3))                  # the images are the generator's first draw, the measured PSF its second
     kfile = tmp_path / "measured.npy"
     np.save(kfile, rng.random((5, 3)))
-    env = dict(os.environ, PYTHONPATH=os.path.join(root, "downsampled-diffusion_amd"))
-    script = os.path.join(root, "downsampled-diffusion_amd", "deconv_model_samples.py")
-    r = subprocess.run([sys.executable, script, "--synthetic", str(cfg_path), "--saved_model", "clitest", "--images", str(tmp_path / "imgs.npy"),
-                        "--blur_input", "--psf", "disk", "--tol", "0.1", "--timestep_respacing", "10", "--batch_size", "3", "--seed", "3",
-                        "--out_dir", str(tmp_path)], capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
+    CC.run_script("deconv_model_samples.py", "--synthetic", cfg_path, "--saved_model", "clitest", "--images", images_path, "--blur_input",
+                  "--psf", "disk", "--tol", "0.1", "--timestep_respacing", "10", "--batch_size", "3", "--seed", "3", "--out_dir", tmp_path, env=env)
     out = np.load(tmp_path / "clitest_deconv_disk_10.npy")
     blurred = np.load(tmp_path / "clitest_deconv_disk_10_blurred.npy")
     assert out.shape == (4, 16, 16, 3) and out.dtype == np.float32
@@ -479,11 +414,8 @@ def test_deconv_cli_and_evaluator(tmp_path):
     assert blurred.shape == (4, 16, 16, 3) and blurred.dtype == np.uint8
     want = FR.apply(torch.from_numpy(imgs.astype(np.float64)).permute(0, 3, 1, 2) / 255 * 2 - 1, FR.spectrum(FR.preset("disk"), 16, 16))
     assert np.abs(blurred.astype(np.float64) - (np.transpose(want, (0, 2, 3, 1)) + 1) * 127.5).max() <= 0.5 + 1e-3
-    script = os.path.join(root, "downsampled-diffusion_amd", "evaluate_restoration.py")
-    r = subprocess.run([sys.executable, script, "--synthetic", str(cfg_path), "--images", str(tmp_path / "imgs.npy"), "--task", "deconv",
-                        "--psf", str(kfile), "--timestep_respacing", "10", "--batch_size", "3", "--json", str(tmp_path / "score.json")],
-                       capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
+    CC.run_script("evaluate_restoration.py", "--synthetic", cfg_path, "--images", images_path, "--task", "deconv", "--psf", kfile,
+                  "--timestep_respacing", "10", "--batch_size", "3", "--json", tmp_path / "score.json", env=env)
     res = json.loads((tmp_path / "score.json").read_text())
     s, mt = res["settings"], res["metrics"]
     assert (s["task"], s["method"], s["psf"], s["tol"], s["unet_forwards"], s["n_images"]) == ("deconv", "ddnm_deconv", str(kfile), 0.03, 10, 4)

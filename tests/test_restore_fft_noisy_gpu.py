@@ -15,19 +15,18 @@ The bar of the lone step, per plane in the 2-norm, with u = 2^-24, N = H W and L
 Shapes: the plane form with W != H both ways and an odd channel count, the largest plane it holds, and the multi-launch form.  Chains:
 1e-4 abs against the restatement with the same argmax and 1e-5 between the Python loop and the native sampler, as for the other
 restore kinds; graph replay equals eager launches bit for bit."""
-import ctypes as C
+import json
 import math
 
 import numpy as np
 import pytest
 import torch
 
+import chain_cases as CC
 import fft_conv_ref as FR
 import fft_noisy_ref as FN
-from helpers import ddpm_cfg, det_load
+from helpers import ddpm_cfg, to_nchw as nchw, to_nhwc as nhwc
 from oracle import diffusion_ref as D
-from oracle import philox_ref as PR
-from oracle import unet_ref as U
 from utils import synthetic as syn
 
 pytestmark = pytest.mark.gpu
@@ -45,9 +44,6 @@ PSF_TOL = 3e-2
 KINDS = [dict(), dict(ddim=True, eta=0.5)]
 IDS = ["ancestral", "ddim_eta0.5"]
 
-nhwc = lambda v: v.permute(0, 2, 3, 1).contiguous()
-nchw = lambda v: v.permute(0, 3, 1, 2).contiguous()
-
 
 def _norm(v):
     """2-norm per plane of a [B, C, H, W] tensor or array, as a float64 array [B, C]"""
@@ -56,13 +52,8 @@ def _norm(v):
 
 
 def _draws(B, c, h, w, t, seed, stream):
-    """the device's own draws (ddk_randn: the op's Philox call and keying), checked against oracle/philox_ref; zeros at row 0"""
-    from ddk import ops
-    z_dev = torch.stack([ops.randn((B, h, w, c), DEV, seed, int(tb), stream)[b] for b, tb in enumerate(t)]).cpu()
-    z_ref = torch.from_numpy(np.stack([PR.philox_normal(B * h * w * c, seed, int(tb), stream).reshape(B, h, w, c)[b]
-                                       for b, tb in enumerate(t)]))
-    assert float((z_dev - z_ref).abs().max()) < 1e-5
-    z = nchw(z_dev)
+    """chain_cases.philox_draws with zeros at row 0, which this op's restatement multiplies by its own factor"""
+    z = CC.philox_draws(B, c, h, w, t, seed, stream)
     z[torch.as_tensor(t) == 0] = 0.0
     return z
 
@@ -276,10 +267,7 @@ def test_argument_faults_run_no_kernel():
 # ---------------------------------------------------------------- 5. the tiny DDPM, "8" steps
 @pytest.fixture(scope="module")
 def tiny():
-    from models import DDPM, Unet
-    m = det_load(DDPM(CFG, Unet(CFG), DEV, 3)).to(DEV).eval()
-    sd = {k: v.detach().cpu() for k, v in m.state_dict().items()}
-    return m, (lambda x, t: U.unet_forward(sd, CFG, x, t, pre="latent_model."))
+    return CC.tiny_ddpm(CFG)
 
 
 PSF_TINY = "disk"
@@ -331,17 +319,11 @@ def test_graph_equals_eager_and_python_loop_equals_native(tiny, data, kw):
     m, _ = tiny
     y, x_T = data
     native = m.deconvolve_noisy(y.to(DEV), PSF_TINY, sigma_y=SY, respacing="8", x_T=x_T, seed=SEED, **kw)
-    m.use_graph = False
-    try:
+    with CC.toggled(m, "use_graph", False):
         eager = m.deconvolve_noisy(y.to(DEV), PSF_TINY, sigma_y=SY, respacing="8", x_T=x_T, seed=SEED, **kw)
-    finally:
-        m.use_graph = True
     assert torch.equal(native, eager)
-    m.native_sampler = False
-    try:
+    with CC.toggled(m, "native_sampler", False):
         loop = m.deconvolve_noisy(y.to(DEV), K_TINY, sigma_y=SY, respacing="8", x_T=x_T, seed=SEED, **kw)      # the preset as an array: the same chain
-    finally:
-        m.native_sampler = True
     err = float((loop - native).abs().max())
     print(f"Python loop vs native, DDNM+ deconvolution 8 steps {kw}: {err:.3g}")
     assert err < 1e-5
@@ -384,7 +366,6 @@ def test_noisy_deconvolution_and_ancestral_chains_share_a_workspace(tiny, data, 
     plan = m._eps_model_nhwc().plan()
     lib = plan._lib
     K = len(use)
-    tmap = (C.c_int64 * K)(*[int(v) for v in use])
     nbytes = lib.ddk_sampler_restore_fft_noisy_workspace_bytes(plan.handle, 2, 16, 16, K - 1)
     n = 2 * 16 * 16 * 3
     assert nbytes == lib.ddk_sampler_restore_fft_workspace_bytes(plan.handle, 2, 16, 16, K - 1) + 4 * (256 + 8 + 2 * n)
@@ -394,31 +375,20 @@ def test_noisy_deconvolution_and_ancestral_chains_share_a_workspace(tiny, data, 
     gn = {sy: tuple(torch.from_numpy(v).to(DEV) for v in psf.psf_noisy_operands(K_TINY, 16, 16, PSF_TOL, sy, tables["c1"])) for sy in (SY, 0.5)}
     x0 = ops.nchw_to_nhwc(x_T.to(DEV).contiguous())
     yd = ops.nchw_to_nhwc(y.to(DEV).contiguous())
-    x = torch.empty_like(x0)
-    ws = torch.empty(nbytes // 4 + 4, device=DEV)
-    side = torch.cuda.Stream()
 
-    def run(what):
-        x.copy_(x0)
-        torch.cuda.synchronize()
-        a = L.SamplerArgs(plan.handle, L.ptr(plan.packed), L.ptr(x), None, L.ptr(tables["c_recip"]), L.ptr(tables["c_recipm1"]),
-                          L.ptr(tables["c1"]), L.ptr(tables["c2"]), L.ptr(tables["sigma"]), 2, 16, 16, K - 1, 0, SEED, 0, 1, L.ptr(ws), nbytes)
-        with torch.cuda.stream(side):
-            if what is None:
-                rc = lib.ddk_sampler_run_spaced(C.byref(a), tmap, side.cuda_stream)
-            elif what == "deconv":
-                rc = lib.ddk_sampler_run_restore_fft(C.byref(a), tmap, L.ptr(Md), L.ptr(Pd), L.ptr(tw), L.ptr(yd), side.cuda_stream)
-            else:
-                rc = lib.ddk_sampler_run_restore_fft_noisy(C.byref(a), tmap, L.ptr(Md), L.ptr(Pd), L.ptr(gn[what][0]), L.ptr(gn[what][1]),
-                                                           L.ptr(tw), L.ptr(yd), side.cuda_stream)
-        assert rc == 0, L.last_error()
-        side.synchronize()
-        return x.clone()
+    def launch(what, a, tmap, stream):
+        if what is None:
+            return lib.ddk_sampler_run_spaced(a, tmap, stream)
+        if what == "deconv":
+            return lib.ddk_sampler_run_restore_fft(a, tmap, L.ptr(Md), L.ptr(Pd), L.ptr(tw), L.ptr(yd), stream)
+        return lib.ddk_sampler_run_restore_fft_noisy(a, tmap, L.ptr(Md), L.ptr(Pd), L.ptr(gn[what][0]), L.ptr(gn[what][1]), L.ptr(tw), L.ptr(yd),
+                                                     stream)
 
-    try:
+    sh = CC.SharedWorkspace(plan, tables, use, x0, nbytes, SEED, launch)
+    with CC.workspace(plan, nbytes) as ws:
         first = {}
         for what in (SY, "deconv", None, SY, 0.5, None, "deconv", 0.5, SY, None, 0.5, "deconv", SY):
-            got = run(what)
+            got = sh.run(ws, what)
             assert torch.equal(got, first.setdefault(what, got)), (what, float((got - first[what]).abs().max()))
         outs = list(first.values())
         assert all(not torch.equal(a, b) for i, a in enumerate(outs) for b in outs[i + 1:])
@@ -426,15 +396,12 @@ def test_noisy_deconvolution_and_ancestral_chains_share_a_workspace(tiny, data, 
         assert torch.equal(ops.nhwc_to_nchw(first[SY]), via_model)
         assert float((ops.nhwc_to_nchw(first[SY]).cpu() - reference["ancestral"]).abs().max()) < TOL
         assert torch.equal(ops.nhwc_to_nchw(first["deconv"]), m.deconvolve(y.to(DEV), PSF_TINY, respacing="8", x_T=x_T, seed=SEED))
-    finally:      # the plan's cached graphs and shift table point into ws: drop them before the memory goes back
-        assert lib.ddk_sampler_release_workspace(plan.handle, L.ptr(ws)) == 0
 
 
 def test_the_five_plane_wide_kinds_in_rotation_equal_each_alone(data):
     """deblur, restore_separable, restore_cs, deconvolve and deconvolve_noisy in rotation on one model and plan, in two orders: each
     result equals, bit for bit, that of the same call made alone on a freshly built model (every call stages its own operands and
     the graph key tells the kinds apart, whichever kind used the workspace before)"""
-    from models import DDPM, Unet
     from models.diffusion import blur
     y, x_T = data
     yd = y.to(DEV)
@@ -447,7 +414,7 @@ def test_the_five_plane_wide_kinds_in_rotation_equal_each_alone(data):
              "cs": lambda m: m.restore_cs(y_cs, perm_seed=3, **kw),
              "deconvolve": lambda m: m.deconvolve(yd, PSF_TINY, **kw),
              "deconvolve_noisy": lambda m: m.deconvolve_noisy(yd, PSF_TINY, sigma_y=SY, **kw)}
-    fresh = lambda: det_load(DDPM(CFG, Unet(CFG), DEV, 3)).to(DEV).eval()
+    fresh = lambda: CC.tiny_ddpm(CFG)[0]
     alone = {name: call(fresh()) for name, call in calls.items()}
     outs = list(alone.values())
     assert all(torch.isfinite(v).all() for v in outs) and all(not torch.equal(a, b) for i, a in enumerate(outs) for b in outs[i + 1:])
@@ -468,7 +435,7 @@ def test_chain_faults(tiny):
     plan = m._eps_model_nhwc().plan()
     lib = plan._lib
     K = len(use)
-    tmap = (C.c_int64 * K)(*[int(v) for v in use])
+    tmap = CC.timestep_map(use)
     nbytes = lib.ddk_sampler_restore_fft_noisy_workspace_bytes(plan.handle, 2, 16, 16, K - 1)
     assert nbytes > 0 and lib.ddk_sampler_restore_fft_noisy_workspace_bytes(plan.handle, 2, 16, 48, K - 1) == 0
     x = torch.zeros(2, 16, 16, 3, device=DEV)
@@ -477,20 +444,17 @@ def test_chain_faults(tiny):
     gd, nd = (torch.from_numpy(v).to(DEV) for v in psf.psf_noisy_operands(K_TINY, 16, 16, PSF_TOL, SY, tables["c1"]))
     Md, Pd = torch.from_numpy(Mf).to(DEV), torch.from_numpy(Pf).to(DEV)
     tw = ops.fft_twiddles(16, Md.device)
-    ws = torch.empty(nbytes // 4 + 4, device=DEV)
+    ws = CC.fresh_workspace(nbytes)
     noise = torch.zeros((K, *x.shape), device=DEV)
-
-    def args(noise=None, H=16, W=16, nbytes=nbytes):
-        return L.SamplerArgs(plan.handle, L.ptr(plan.packed), L.ptr(x), L.ptr(noise), L.ptr(tables["c_recip"]), L.ptr(tables["c_recipm1"]),
-                             L.ptr(tables["c1"]), L.ptr(tables["c2"]), L.ptr(tables["sigma"]), 2, H, W, K - 1, 0, SEED, 0, 0, L.ptr(ws), nbytes)
+    args = lambda noise=None, H=16, nbytes=nbytes: CC.sampler_args(plan, x, tables, K - 1, ws, nbytes, seed=SEED, noise=noise, shape=(2, H, 16))
     run = lib.ddk_sampler_run_restore_fft_noisy
     ops6 = (L.ptr(Md), L.ptr(Pd), L.ptr(gd), L.ptr(nd), L.ptr(tw), L.ptr(y))
-    assert run(C.byref(args(noise)), tmap, *ops6, L.stream()) == -1 and "noise" in L.last_error()
+    assert run(args(noise), tmap, *ops6, L.stream()) == -1 and "noise" in L.last_error()
     for i in range(6):
-        assert run(C.byref(args()), tmap, *(None if j == i else p for j, p in enumerate(ops6)), L.stream()) == -1 and "null" in L.last_error()
-        assert run(C.byref(args()), tmap, *(p + 4 if j == i else p for j, p in enumerate(ops6)), L.stream()) == -1 and "alignment" in L.last_error()
-    assert run(C.byref(args(H=48)), tmap, *ops6, L.stream()) == -1 and "powers of two" in L.last_error()
-    assert run(C.byref(args(nbytes=nbytes - 4)), tmap, *ops6, L.stream()) != 0      # a short workspace
+        assert run(args(), tmap, *(None if j == i else p for j, p in enumerate(ops6)), L.stream()) == -1 and "null" in L.last_error()
+        assert run(args(), tmap, *(p + 4 if j == i else p for j, p in enumerate(ops6)), L.stream()) == -1 and "alignment" in L.last_error()
+    assert run(args(H=48), tmap, *ops6, L.stream()) == -1 and "powers of two" in L.last_error()
+    assert run(args(nbytes=nbytes - 4), tmap, *ops6, L.stream()) != 0      # a short workspace
     torch.cuda.synchronize()
     assert float(x.abs().max()) == 0.0
     with pytest.raises(L.DDKError):
@@ -502,26 +466,18 @@ def test_chain_faults(tiny):
 def test_multi_launch_chain_256():
     """three steps at 3 x 256 x 256, B = 1, on a 32-wide model: the three-launch form with T2 inside a chain.  Graph replay against eager
     launches, and the native chain against the Python loop over the lone op"""
-    from models import DDPM, Unet
-    cfg = ddpm_cfg(32, 3, 256)
-    m = det_load(DDPM(cfg, Unet(cfg), DEV, 3)).to(DEV).eval()
+    m, _ = CC.tiny_ddpm(ddpm_cfg(32, 3, 256))
     shape = (1, 3, 256, 256)
     k = FR.preset("diag")
     clean = 0.25 * syn.synthetic_normal(shape, "deconv_noisy256.x")
     y = (torch.from_numpy(FR.apply(clean, FR.spectrum(k, 256, 256))).float() + SY * syn.synthetic_normal(shape, "deconv_noisy256.n")).contiguous()
     x_T = syn.synthetic_normal(shape, "deconv_noisy256.xT")
     native = m.deconvolve_noisy(y.to(DEV), "diag", sigma_y=SY, respacing="3", x_T=x_T, seed=SEED)
-    m.use_graph = False
-    try:
+    with CC.toggled(m, "use_graph", False):
         eager = m.deconvolve_noisy(y.to(DEV), "diag", sigma_y=SY, respacing="3", x_T=x_T, seed=SEED)
-    finally:
-        m.use_graph = True
     assert torch.equal(native, eager)
-    m.native_sampler = False
-    try:
+    with CC.toggled(m, "native_sampler", False):
         loop = m.deconvolve_noisy(y.to(DEV), "diag", sigma_y=SY, respacing="3", x_T=x_T, seed=SEED)
-    finally:
-        m.native_sampler = True
     err = float((loop - native).abs().max())
     print(f"Python loop vs native, DDNM+ deconvolution 256 x 256, 3 steps: {err:.3g}")
     assert torch.isfinite(native).all() and err < 1e-5
@@ -531,24 +487,10 @@ def test_multi_launch_chain_256():
 def test_deconv_noisy_cli_and_evaluator(tmp_path):
     """deconv_model_samples.py --blur_input --sigma_y and evaluate_restoration.py --task deconv_noisy with synthetic weights on four
     16 x 16 images, each in a fresh process: the files, their names and shapes, and the JSON keys"""
-    import json
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cfg = ddpm_cfg(32, 3, 16, T=100)
-    cfg.update(model="ddpm", dataset="celeba")
-    cfg_path = tmp_path / "cfg.json"
-    cfg_path.write_text(json.dumps(cfg))
-    rng = np.random.default_rng(0)
-    imgs = (rng.random((4, 16, 16, 3)) * 255).astype(np.uint8)
-    np.save(tmp_path / "imgs.npy", imgs)
-    env = dict(os.environ, PYTHONPATH=os.path.join(root, "downsampled-diffusion_amd"))
-    script = os.path.join(root, "downsampled-diffusion_amd", "deconv_model_samples.py")
-    r = subprocess.run([sys.executable, script, "--synthetic", str(cfg_path), "--saved_model", "clitest", "--images", str(tmp_path / "imgs.npy"),
-                        "--blur_input", "--psf", "disk", "--tol", "0.1", "--sigma_y", "0.05", "--timestep_respacing", "10", "--batch_size", "3",
-                        "--seed", "3", "--out_dir", str(tmp_path)], capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
+    cfg_path, images_path, imgs, env = CC.cli_files(tmp_path, CC.cli_cfg(), 4, 16)
+    CC.run_script("deconv_model_samples.py", "--synthetic", cfg_path, "--saved_model", "clitest", "--images", images_path, "--blur_input",
+                  "--psf", "disk", "--tol", "0.1", "--sigma_y", "0.05", "--timestep_respacing", "10", "--batch_size", "3", "--seed", "3",
+                  "--out_dir", tmp_path, env=env)
     out = np.load(tmp_path / "clitest_deconv_disk_10_sy0.05.npy")
     blurred = np.load(tmp_path / "clitest_deconv_disk_10_sy0.05_blurred.npy")
     assert out.shape == (4, 16, 16, 3) and out.dtype == np.float32 and np.isfinite(out).all() and out.min() >= 0 and out.max() <= 255
@@ -556,11 +498,8 @@ def test_deconv_noisy_cli_and_evaluator(tmp_path):
     clean = FR.apply(torch.from_numpy(imgs.astype(np.float64)).permute(0, 3, 1, 2) / 255 * 2 - 1, FR.spectrum(FR.preset("disk"), 16, 16))
     dev = blurred.astype(np.float64) - (np.transpose(clean, (0, 2, 3, 1)) + 1) * 127.5
     assert 0.5 * 0.05 * 127.5 < dev.std() < 1.5 * 0.05 * 127.5      # the noise that was asked for is in the saved measurement
-    script = os.path.join(root, "downsampled-diffusion_amd", "evaluate_restoration.py")
-    r = subprocess.run([sys.executable, script, "--synthetic", str(cfg_path), "--images", str(tmp_path / "imgs.npy"), "--task", "deconv_noisy",
-                        "--psf", "disk", "--sigma_y", "0.05", "--timestep_respacing", "10", "--batch_size", "3", "--json", str(tmp_path / "score.json")],
-                       capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
+    CC.run_script("evaluate_restoration.py", "--synthetic", cfg_path, "--images", images_path, "--task", "deconv_noisy", "--psf", "disk",
+                  "--sigma_y", "0.05", "--timestep_respacing", "10", "--batch_size", "3", "--json", tmp_path / "score.json", env=env)
     res = json.loads((tmp_path / "score.json").read_text())
     s, mt = res["settings"], res["metrics"]
     assert (s["task"], s["method"], s["psf"], s["tol"], s["sigma_y"], s["unet_forwards"], s["n_images"]) == ("deconv_noisy", "ddnm_plus", "disk", 0.03, 0.05, 10, 4)

@@ -6,20 +6,14 @@ The tiny DDPM (unet_chan 32, 3x16x16) has no Winograd final conv, so its steps e
 latent at B = 32 ends in the fused tail for n = 2 and 4.  Bars: the lone op bit for bit (the order of the fp32 operations is
 pinned); chains 1e-4 abs against the restatement with the same argmax and 1e-5 between the Python loop and the native sampler, as
 for the spaced and RePaint chains; the block means of the output within 8 n^2 2^-24 of y (derived worst case (n^2 + 4) 2^-24)."""
-import ctypes as C
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 import torch
 
+import chain_cases as CC
 import restore_ref as RR
-from helpers import dddpm_cfg, ddpm_cfg, det_load, unet_cfg
+from helpers import dddpm_cfg, ddpm_cfg, det_load, to_nhwc, unet_cfg
 from oracle import diffusion_ref as D
-from oracle import philox_ref as PR
 from oracle import unet_ref as U
 from utils import synthetic as syn
 
@@ -38,26 +32,14 @@ def _bar(n):
     return 8 * n * n * 2.0 ** -24
 
 
-def _y(shape, n, name):
-    b, c, h, w = shape
-    return RR.pool(syn.synthetic_normal(shape, name).clamp(-1, 1), n).contiguous()
-
-
 @pytest.fixture(scope="module")
 def tiny():
-    from models import DDPM, Unet
-    m = det_load(DDPM(CFG, Unet(CFG), DEV, 3)).to(DEV).eval()
-    sd = {k: v.detach().cpu() for k, v in m.state_dict().items()}
-    return m, (lambda x, t: U.unet_forward(sd, CFG, x, t, pre="latent_model."))
+    return CC.tiny_ddpm(CFG)
 
 
 @pytest.fixture(scope="module")
 def data():
-    return _y(SHAPE, 4, "restore.x"), syn.synthetic_normal(SHAPE, "restore.xT")
-
-
-def _argmax(x):
-    return x.reshape(x.shape[0], -1).argmax(dim=1)
+    return CC.pooled_y(SHAPE, 4, "restore.x"), syn.synthetic_normal(SHAPE, "restore.xT")
 
 
 # ---------------------------------------------------------------- the lone op, bit for bit
@@ -75,18 +57,13 @@ def test_lone_op_equals_restatement_bit_for_bit(n, c, h, w):
     e = torch.randn(shape, generator=g)
     y = torch.rand(B, c, h // n, w // n, generator=g) * 2 - 1
     t = torch.tensor([0, 7, 3])
-    tab = {k: torch.rand(8, generator=g) * s for k, s in (("c_recip", 3.0), ("c_recipm1", 2.0), ("c1", 1.0), ("c2", 1.0), ("sigma", 0.5))}
-    tab["c1"][0], tab["c2"][0] = 1.0, 0.0
+    tab = CC.hand_tables(g)
     seed, stream = 24680, 5
-    nhwc = lambda v: v.permute(0, 2, 3, 1).contiguous()
-    z_dev = torch.stack([ops.randn((B, h, w, c), DEV, seed, int(tb), stream)[b] for b, tb in enumerate(t)]).cpu()
-    z_ref = torch.from_numpy(np.stack([PR.philox_normal(B * h * w * c, seed, int(tb), stream).reshape(B, h, w, c)[b]
-                                       for b, tb in enumerate(t)]))
-    assert float((z_dev - z_ref).abs().max()) < 1e-5
+    z = CC.philox_draws(B, c, h, w, t, seed, stream)
     sg = torch.where(t > 0, tab["sigma"][t], torch.zeros(B))
-    want = RR.step(x, e, y, n, tab["c_recip"][t], tab["c_recipm1"][t], tab["c1"][t], tab["c2"][t], sg, z_dev.permute(0, 3, 1, 2))
-    xs = nhwc(x).to(DEV)
-    ops.p_sample_update_restore_(xs, nhwc(e).to(DEV), nhwc(y).to(DEV), n, t.to(DEV), **{k: v.to(DEV) for k, v in tab.items()},
+    want = RR.step(x, e, y, n, tab["c_recip"][t], tab["c_recipm1"][t], tab["c1"][t], tab["c2"][t], sg, z)
+    xs = to_nhwc(x).to(DEV)
+    ops.p_sample_update_restore_(xs, to_nhwc(e).to(DEV), to_nhwc(y).to(DEV), n, t.to(DEV), **{k: v.to(DEV) for k, v in tab.items()},
                                  seed=seed, stream_id=stream)
     got = xs.cpu().permute(0, 3, 1, 2)
     diff = float((got - want).abs().max())
@@ -121,7 +98,7 @@ def test_tiny_vs_restatement(tiny, data, kw):
     print(f"DDNM x4 tiny DDPM, 20 steps {kw}: max abs error {err:.3g}")
     assert torch.isfinite(got).all() and got.shape == SHAPE
     assert err < TOL, err
-    assert torch.equal(_argmax(got), _argmax(want))
+    assert torch.equal(CC.argmax(got), CC.argmax(want))
 
 
 @pytest.mark.parametrize("kw", KINDS, ids=IDS)
@@ -129,11 +106,8 @@ def test_graph_equals_eager_bit_for_bit(tiny, data, kw):
     m, _ = tiny
     y, x_T = data
     graphed = m.super_resolve(y.to(DEV), 4, respacing="20", x_T=x_T, seed=SEED, **kw)
-    m.use_graph = False
-    try:
+    with CC.toggled(m, "use_graph", False):
         eager = m.super_resolve(y.to(DEV), 4, respacing="20", x_T=x_T, seed=SEED, **kw)
-    finally:
-        m.use_graph = True
     assert torch.equal(graphed, eager)
 
 
@@ -142,11 +116,8 @@ def test_python_loop_equals_native(tiny, data, kw):
     m, _ = tiny
     y, x_T = data
     native = m.super_resolve(y.to(DEV), 4, respacing="20", x_T=x_T, seed=SEED, **kw)
-    m.native_sampler = False
-    try:
+    with CC.toggled(m, "native_sampler", False):
         loop = m.super_resolve(y.to(DEV), 4, respacing="20", x_T=x_T, seed=SEED, **kw)
-    finally:
-        m.native_sampler = True
     err = float((loop - native).abs().max())
     print(f"Python loop vs native, DDNM 20 steps {kw}: {err:.3g}")
     assert err < 1e-5
@@ -156,7 +127,7 @@ def test_python_loop_equals_native(tiny, data, kw):
 @pytest.mark.parametrize("kw", KINDS, ids=IDS)
 def test_output_block_means_equal_y(tiny, n, kw):
     m, _ = tiny
-    y = _y(SHAPE, n, f"restore.cons.{n}")
+    y = CC.pooled_y(SHAPE, n, f"restore.cons.{n}")
     out = m.super_resolve(y.to(DEV), n, respacing="20", x_T=syn.synthetic_normal(SHAPE, "restore.xT"), seed=SEED + n, **kw).cpu()
     assert out.dtype == torch.float32
     err = float((RR.pool(out.double(), n) - y.double()).abs().max())
@@ -187,7 +158,7 @@ def test_cfg4_b32_fused_tail(cfg4, n):
     before, cluster = ops.cluster_timeouts(), plan._cluster
     shape = (32, 8, 32, 32)
     assert plan.restore_tail_parts(32, 32, 32, n) == 8
-    y = _y(shape, n, f"restore.cfg4.{n}")
+    y = CC.pooled_y(shape, n, f"restore.cfg4.{n}")
     x_T = syn.synthetic_normal(shape, "restore.cfg4.xT")
     run = lambda: DDPM.super_resolve(m, y.to(DEV), n, respacing="8", x_T=x_T, seed=SEED)
     fused = run()
@@ -198,11 +169,8 @@ def test_cfg4_b32_fused_tail(cfg4, n):
     finally:
         plan.set_option(plan.OPT_RESTORE_FUSED_TAIL, 1)
     assert torch.equal(fused, unfused), float((fused - unfused).abs().max())
-    m.native_sampler = False
-    try:
+    with CC.toggled(m, "native_sampler", False):
         loop = run()
-    finally:
-        m.native_sampler = True
     err_loop = float((loop - fused).abs().max())
     torch.cuda.synchronize()
     err_means = float((RR.pool(fused.cpu().double(), n) - y.double()).abs().max())
@@ -228,15 +196,12 @@ def test_cfg4_n8_takes_the_unfused_tail(cfg4):
     before = ops.cluster_timeouts()
     assert plan.restore_tail_parts(4, 32, 32, 8) == 0
     shape = (4, 8, 32, 32)
-    y = _y(shape, 8, "restore.cfg4.8")
+    y = CC.pooled_y(shape, 8, "restore.cfg4.8")
     x_T = syn.synthetic_normal(shape, "restore.cfg4.xT8")
     run = lambda: DDPM.super_resolve(m, y.to(DEV), 8, respacing="8", x_T=x_T, seed=SEED)
     native = run()
-    m.native_sampler = False
-    try:
+    with CC.toggled(m, "native_sampler", False):
         loop = run()
-    finally:
-        m.native_sampler = True
     assert float((loop - native).abs().max()) < 1e-5
     assert float((RR.pool(native.cpu().double(), 8) - y.double()).abs().max()) <= _bar(8)
     assert ops.cluster_timeouts() == before
@@ -255,54 +220,28 @@ def test_restore_and_ancestral_chains_share_a_workspace(tiny, data):
     plan = m._eps_model_nhwc().plan()
     lib = plan._lib
     K = len(use)
-    tmap = (C.c_int64 * K)(*[int(v) for v in use])
     nbytes = lib.ddk_sampler_restore_workspace_bytes(plan.handle, 2, 16, 16, K - 1)
     assert nbytes >= lib.ddk_sampler_workspace_bytes(plan.handle, 2, 16, 16, K - 1) + 2 * 4 * 4 * 3 * 4
     x0 = ops.nchw_to_nhwc(x_T.to(DEV).contiguous())
-    ys = {4: ops.nchw_to_nhwc(y.to(DEV)), 2: ops.nchw_to_nhwc(_y(SHAPE, 2, "restore.other").to(DEV)),
-          -4: ops.nchw_to_nhwc(_y(SHAPE, 4, "restore.third").to(DEV))}
-    x = torch.empty_like(x0)
-    side = torch.cuda.Stream()
+    ys = {4: ops.nchw_to_nhwc(y.to(DEV)), 2: ops.nchw_to_nhwc(CC.pooled_y(SHAPE, 2, "restore.other").to(DEV)),
+          -4: ops.nchw_to_nhwc(CC.pooled_y(SHAPE, 4, "restore.third").to(DEV))}
 
-    def run(ws, what):
-        x.copy_(x0)
-        torch.cuda.synchronize()
-        a = L.SamplerArgs(plan.handle, L.ptr(plan.packed), L.ptr(x), None, L.ptr(tables["c_recip"]), L.ptr(tables["c_recipm1"]),
-                          L.ptr(tables["c1"]), L.ptr(tables["c2"]), L.ptr(tables["sigma"]), 2, 16, 16, K - 1, 0, SEED, 0, 1, L.ptr(ws),
-                          nbytes)
-        with torch.cuda.stream(side):
-            if what is None:
-                rc = lib.ddk_sampler_run_spaced(C.byref(a), tmap, side.cuda_stream)
-            else:
-                rc = lib.ddk_sampler_run_restore(C.byref(a), tmap, L.ptr(ys[what]), abs(what), side.cuda_stream)
-        assert rc == 0, L.last_error()
-        side.synchronize()
-        return x.clone()
+    def launch(what, a, tmap, stream):
+        if what is None:
+            return lib.ddk_sampler_run_spaced(a, tmap, stream)
+        return lib.ddk_sampler_run_restore(a, tmap, L.ptr(ys[what]), abs(what), stream)
 
-    fresh = lambda: torch.empty(nbytes // 4 + 4, device=DEV)
-
-    def alone(what):
-        ws = fresh()
-        try:
-            return run(ws, what)
-        finally:      # the plan's cached graphs and shift table point into ws: drop them before the memory goes back
-            assert lib.ddk_sampler_release_workspace(plan.handle, L.ptr(ws)) == 0
-
-    single = {what: alone(what) for what in (4, None, 2, -4)}
+    sh = CC.SharedWorkspace(plan, tables, use, x0, nbytes, SEED, launch)
+    x, tmap = sh.x, sh.tmap
+    single = {what: sh.alone(what) for what in (4, None, 2, -4)}
     assert not torch.equal(single[4], single[None]) and not torch.equal(single[4], single[-4])
     for order in ((4, None, -4, 2, None), (None, 4, None, 2, -4, 4)):
-        ws = fresh()
-        for what in order:
-            got = run(ws, what)
-            assert torch.equal(got, single[what]), (order, what, float((got - single[what]).abs().max()))
-        assert lib.ddk_sampler_release_workspace(plan.handle, L.ptr(ws)) == 0
+        sh.interleaved(order, single)
     # injected noise is rejected
-    a = L.SamplerArgs(plan.handle, L.ptr(plan.packed), L.ptr(x), L.ptr(torch.zeros((K, *x.shape), device=DEV)), L.ptr(tables["c_recip"]),
-                      L.ptr(tables["c_recipm1"]), L.ptr(tables["c1"]), L.ptr(tables["c2"]), L.ptr(tables["sigma"]), 2, 16, 16, K - 1, 0,
-                      SEED, 0, 0, L.ptr(fresh()), nbytes)
-    assert lib.ddk_sampler_run_restore(C.byref(a), tmap, L.ptr(ys[4]), 4, L.stream()) == -1 and "noise" in L.last_error()
+    a = CC.sampler_args(plan, x, tables, K - 1, CC.fresh_workspace(nbytes), nbytes, seed=SEED, noise=torch.zeros((K, *x.shape), device=DEV))
+    assert lib.ddk_sampler_run_restore(a, tmap, L.ptr(ys[4]), 4, L.stream()) == -1 and "noise" in L.last_error()
     a.noise = None
-    assert lib.ddk_sampler_run_restore(C.byref(a), tmap, L.ptr(ys[4]), 3, L.stream()) == -1 and "n must be" in L.last_error()
+    assert lib.ddk_sampler_run_restore(a, tmap, L.ptr(ys[4]), 3, L.stream()) == -1 and "n must be" in L.last_error()
 
 
 # ---------------------------------------------------------------- dDDPM and the command line
@@ -310,7 +249,7 @@ def test_dddpm_super_resolve_holds_the_latent_constraint():
     from models import DownsampleDDPM, Unet
     cfg = dddpm_cfg(32, 32, 2)
     m = det_load(DownsampleDDPM(cfg, Unet(cfg), DEV, 3)).to(DEV).eval()
-    y = _y((2, 3, 32, 32), 8, "restore.dd.x")
+    y = CC.pooled_y((2, 3, 32, 32), 8, "restore.dd.x")
     z_T = syn.synthetic_normal((2, 8, 8, 8), "restore.dd.zT")
     x_out, z = m.super_resolve(y.to(DEV), 8, respacing="10", x_T=z_T, seed=SEED)
     assert x_out.shape == (2, 3, 32, 32) and z.shape == (2, 8, 8, 8)
@@ -325,23 +264,14 @@ def test_dddpm_super_resolve_holds_the_latent_constraint():
 
 
 def test_upscale_cli(tmp_path):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cfg = ddpm_cfg(32, 3, 16, T=100)
-    cfg.update(model="ddpm", dataset="celeba")
-    cfg_path = tmp_path / "cfg.json"
-    cfg_path.write_text(json.dumps(cfg))
+    cfg_path, _, _, env = CC.cli_files(tmp_path, CC.cli_cfg(), 3, 16)      # imgs.npy: the full-size images, from the generator's first draw
     rng = np.random.default_rng(0)
-    full = (rng.random((3, 16, 16, 3)) * 255).astype(np.uint8)
-    low = (rng.random((3, 4, 4, 3)) * 255).astype(np.uint8)
-    np.save(tmp_path / "full.npy", full)
+    rng.random((3, 16, 16, 3))
+    low = (rng.random((3, 4, 4, 3)) * 255).astype(np.uint8)             # its second draw
     np.save(tmp_path / "low.npy", low)
-    env = dict(os.environ, PYTHONPATH=os.path.join(root, "downsampled-diffusion_amd"))
-    script = os.path.join(root, "downsampled-diffusion_amd", "upscale_model_samples.py")
-    for images, extra, spec in (("low.npy", [], "10"), ("full.npy", ["--use_ddim", "--eta", "0.5"], "10_ddim_eta0.5")):
-        r = subprocess.run([sys.executable, script, "--synthetic", str(cfg_path), "--saved_model", "clitest", "--images",
-                            str(tmp_path / images), "--scale", "4", "--timestep_respacing", "10", "--batch_size", "2", "--seed", "3",
-                            "--out_dir", str(tmp_path), *extra], capture_output=True, text=True, env=env, timeout=300)
-        assert r.returncode == 0, r.stderr[-2000:]
+    for images, extra, spec in (("low.npy", [], "10"), ("imgs.npy", ["--use_ddim", "--eta", "0.5"], "10_ddim_eta0.5")):
+        CC.run_script("upscale_model_samples.py", "--synthetic", cfg_path, "--saved_model", "clitest", "--images", tmp_path / images, "--scale",
+                      "4", "--timestep_respacing", "10", "--batch_size", "2", "--seed", "3", "--out_dir", tmp_path, *extra, env=env)
         out = np.load(tmp_path / f"clitest_sr4_{spec}.npy")
         lowres = np.load(tmp_path / f"clitest_sr4_{spec}_lowres.npy")
         assert out.shape == (3, 16, 16, 3) and out.dtype == np.float32

@@ -8,22 +8,17 @@ its GroupNorm partials, which the fused tail needs, only unsplit, i.e. from 16 i
 operations is pinned, the added operation is a select); chains 1e-4 abs against the restatement and 1e-5 between the Python loop
 and the native sampler, as for the unmasked chain; measured pixels of the output equal y exactly at n = 1, measured block means
 within 8 n^2 2^-24 at n >= 2; fused and unfused tails, graph and eager, masked-with-ones and unmasked: the same bits."""
-import ctypes as C
 import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
+import chain_cases as CC
 import restore_masked_ref as RM
 import restore_ref as RR
-from helpers import dddpm_cfg, ddpm_cfg, det_load, unet_cfg
+from helpers import dddpm_cfg, ddpm_cfg, det_load, to_nhwc
 from oracle import diffusion_ref as D
-from oracle import philox_ref as PR
-from oracle import unet_ref as U
 from utils import synthetic as syn
 
 pytestmark = pytest.mark.gpu
@@ -41,44 +36,22 @@ def _bar(n):
     return 8 * n * n * 2.0 ** -24
 
 
-def _mask(kind, b, h, w):
-    """[b, h, w] {0, 1}: a checkerboard, a single measured block / pixel, a single hidden one (at another place per image)"""
-    i, j = torch.meshgrid(torch.arange(h), torch.arange(w), indexing="ij")
-    if kind == "checker":
-        return torch.stack([((i + j + k) % 2).float() for k in range(b)])
-    m = torch.zeros(b, h, w) if kind == "one_measured" else torch.ones(b, h, w)
-    for k in range(b):
-        m[k, (k * 3 + 1) % h, (k * 5 + w - 1) % w] = 1.0 - m[k, 0, 0]
-    return m
-
-
-def _y(shape, n, name):
-    return RR.pool(syn.synthetic_normal(shape, name).clamp(-1, 1), n).contiguous()
-
-
-def _sel(mk, y):
-    return (mk != 0).unsqueeze(1).expand_as(y)
-
-
 def _means_err(out, y, mk, n):
     """max over the measured blocks of |block mean of out - y| (n = 1: of |out - y|)"""
-    return float((RR.pool(out.double(), n) - y.double())[_sel(mk, y)].abs().max())
+    return float((RR.pool(out.double(), n) - y.double())[CC.sel(mk, y)].abs().max())
 
 
 @pytest.fixture(scope="module")
 def tiny():
-    from models import DDPM, Unet
-    m = det_load(DDPM(CFG, Unet(CFG), DEV, 3)).to(DEV).eval()
-    sd = {k: v.detach().cpu() for k, v in m.state_dict().items()}
-    return m, (lambda x, t: U.unet_forward(sd, CFG, x, t, pre="latent_model."))
+    return CC.tiny_ddpm(CFG)
 
 
 @pytest.fixture(scope="module")
 def data():
     """y and mask per block, one start state: computed once, never changed"""
     x_T = syn.synthetic_normal(SHAPE, "restore_masked.xT")
-    ys = {n: _y(SHAPE, n, f"restore_masked.x{n}") for n in (1, 2, 4, 8)}
-    mks = {n: _mask("checker", 2, 16 // n, 16 // n) for n in (1, 2, 4, 8)}
+    ys = {n: CC.pooled_y(SHAPE, n, f"restore_masked.x{n}") for n in (1, 2, 4, 8)}
+    mks = {n: CC.mask("checker", 2, 16 // n, 16 // n) for n in (1, 2, 4, 8)}
     return ys, mks, x_T
 
 
@@ -108,37 +81,32 @@ def test_lone_op_equals_restatement_bit_for_bit(n, c, hw):
     e = torch.randn(shape, generator=g)
     y0 = torch.rand(B, c, h // n, w // n, generator=g) * 2 - 1
     t = torch.tensor([0, 7, 3])
-    tab = {k: torch.rand(8, generator=g) * s for k, s in (("c_recip", 3.0), ("c_recipm1", 2.0), ("c1", 1.0), ("c2", 1.0), ("sigma", 0.5))}
-    tab["c1"][0], tab["c2"][0] = 1.0, 0.0
+    tab = CC.hand_tables(g)
     seed, stream = 24680, 5
-    nhwc = lambda v: v.permute(0, 2, 3, 1).contiguous()
-    z_dev = torch.stack([ops.randn((B, h, w, c), DEV, seed, int(tb), stream)[b] for b, tb in enumerate(t)]).cpu()
-    z_ref = torch.from_numpy(np.stack([PR.philox_normal(B * h * w * c, seed, int(tb), stream).reshape(B, h, w, c)[b]
-                                       for b, tb in enumerate(t)]))
-    assert float((z_dev - z_ref).abs().max()) < 1e-5
+    z = CC.philox_draws(B, c, h, w, t, seed, stream)
     sg = torch.where(t > 0, tab["sigma"][t], torch.zeros(B))
     dtab = {k: v.to(DEV) for k, v in tab.items()}
     for kind in ("checker", "one_measured", "one_hidden"):
-        mk = _mask(kind, B, h // n, w // n)
-        y = torch.where(_sel(mk, y0), y0, torch.full_like(y0, float("nan")))
-        want = RM.step(x, e, y, mk, n, tab["c_recip"][t], tab["c_recipm1"][t], tab["c1"][t], tab["c2"][t], sg, z_dev.permute(0, 3, 1, 2))
-        xs = nhwc(x).to(DEV)
-        ops.p_sample_update_restore_masked_(xs, nhwc(e).to(DEV), nhwc(y).to(DEV), mk.to(DEV), n, t.to(DEV), **dtab, seed=seed,
+        mk = CC.mask(kind, B, h // n, w // n)
+        y = torch.where(CC.sel(mk, y0), y0, torch.full_like(y0, float("nan")))
+        want = RM.step(x, e, y, mk, n, tab["c_recip"][t], tab["c_recipm1"][t], tab["c1"][t], tab["c2"][t], sg, z)
+        xs = to_nhwc(x).to(DEV)
+        ops.p_sample_update_restore_masked_(xs, to_nhwc(e).to(DEV), to_nhwc(y).to(DEV), mk.to(DEV), n, t.to(DEV), **dtab, seed=seed,
                                             stream_id=stream)
         got = xs.cpu().permute(0, 3, 1, 2)
         assert torch.isfinite(got).all(), kind
         assert torch.equal(got, want), (kind, float((got - want).abs().max()))
         # row 0 returns x0' itself: measured pixels are y (n = 1: exactly), measured block means are y
         if n == 1:
-            assert torch.equal(got[0:1][_sel(mk[0:1], y[0:1])], y[0:1][_sel(mk[0:1], y[0:1])])
+            assert torch.equal(got[0:1][CC.sel(mk[0:1], y[0:1])], y[0:1][CC.sel(mk[0:1], y[0:1])])
         else:
             assert _means_err(got[0:1], y[0:1], mk[0:1], n) <= _bar(n)
     if n > 1:   # no mask: the unmasked op, bit for bit
-        a, b = nhwc(x).to(DEV), nhwc(x).to(DEV)
-        ops.p_sample_update_restore_masked_(a, nhwc(e).to(DEV), nhwc(y0).to(DEV), None, n, t.to(DEV), **dtab, seed=seed, stream_id=stream)
-        ops.p_sample_update_restore_(b, nhwc(e).to(DEV), nhwc(y0).to(DEV), n, t.to(DEV), **dtab, seed=seed, stream_id=stream)
+        a, b = to_nhwc(x).to(DEV), to_nhwc(x).to(DEV)
+        ops.p_sample_update_restore_masked_(a, to_nhwc(e).to(DEV), to_nhwc(y0).to(DEV), None, n, t.to(DEV), **dtab, seed=seed, stream_id=stream)
+        ops.p_sample_update_restore_(b, to_nhwc(e).to(DEV), to_nhwc(y0).to(DEV), n, t.to(DEV), **dtab, seed=seed, stream_id=stream)
         assert torch.equal(a, b)
-        ops.p_sample_update_restore_masked_(b.copy_(nhwc(x)), nhwc(e).to(DEV), nhwc(y0).to(DEV), torch.ones(B, h // n, w // n, device=DEV), n,
+        ops.p_sample_update_restore_masked_(b.copy_(to_nhwc(x)), to_nhwc(e).to(DEV), to_nhwc(y0).to(DEV), torch.ones(B, h // n, w // n, device=DEV), n,
                                             t.to(DEV), **dtab, seed=seed, stream_id=stream)
         assert torch.equal(a, b)
 
@@ -188,17 +156,11 @@ def test_graph_equals_eager_and_python_loop_is_close(tiny, data, native, kw, n):
     ys, mks, x_T = data
     graphed = native[n, IDS[KINDS.index(kw)]]
     run = lambda: m.restore(ys[n].to(DEV), mks[n], n, respacing="20", x_T=x_T, seed=SEED, **kw).cpu()
-    m.use_graph = False
-    try:
+    with CC.toggled(m, "use_graph", False):
         eager = run()
-    finally:
-        m.use_graph = True
     assert torch.equal(graphed, eager)
-    m.native_sampler = False
-    try:
+    with CC.toggled(m, "native_sampler", False):
         loop = run()
-    finally:
-        m.native_sampler = True
     err = float((loop - graphed).abs().max())
     print(f"Python loop vs native, masked DDNM n={n} 20 steps {kw}: {err:.3g}")
     assert err < 1e-5
@@ -212,7 +174,7 @@ def test_constraint_and_agreement_with_the_unmasked_entry(tiny, data, native, kw
     ys, mks, x_T = data
     i = IDS[KINDS.index(kw)]
     out = native[1, i]
-    s1 = _sel(mks[1], ys[1])
+    s1 = CC.sel(mks[1], ys[1])
     assert torch.equal(out[s1], ys[1][s1]) and float((out - ys[1])[~s1].abs().max()) > 1e-2
     y_nan = torch.where(s1, ys[1], torch.full_like(ys[1], float("nan"))).to(DEV)
     plan = m._eps_model_nhwc().plan()
@@ -252,9 +214,9 @@ def test_fused_tail_equals_unfused_bit_for_bit(wide, n):
     shape = (B, 8, 32, 32)
     assert plan.restore_masked_tail_parts(B, 32, 32, n) == (0 if n == 8 else 8)
     assert plan.restore_masked_tail_parts(B, 32, 32, 1) > 0 and plan.restore_masked_tail_parts(B, 32, 32, 8) == 0
-    y0 = _y(shape, n, f"restore_masked.wide.{n}")
-    mk = _mask("checker", B, 32 // n, 32 // n)
-    y = torch.where(_sel(mk, y0), y0, torch.full_like(y0, float("nan")))
+    y0 = CC.pooled_y(shape, n, f"restore_masked.wide.{n}")
+    mk = CC.mask("checker", B, 32 // n, 32 // n)
+    y = torch.where(CC.sel(mk, y0), y0, torch.full_like(y0, float("nan")))
     x_T = syn.synthetic_normal(shape, "restore_masked.wide.xT")
     run = lambda: m.restore(y.to(DEV), mk, n, respacing="6", ddim=True, eta=0.5, x_T=x_T, seed=SEED).cpu()
     fused = run()
@@ -267,7 +229,7 @@ def test_fused_tail_equals_unfused_bit_for_bit(wide, n):
     assert torch.isfinite(fused).all()
     assert torch.equal(fused, unfused), float((fused - unfused).abs().max())
     if n == 1:
-        assert torch.equal(fused[_sel(mk, y)], y[_sel(mk, y)])
+        assert torch.equal(fused[CC.sel(mk, y)], y[CC.sel(mk, y)])
     else:
         assert _means_err(fused, y, mk, n) <= _bar(n)
     assert ops.cluster_timeouts() == before
@@ -287,7 +249,6 @@ def test_chains_share_a_workspace_and_masks_share_a_graph(tiny, data):
     lib = plan._lib
     before = ops.cluster_timeouts()
     K = len(use)
-    tmap = (C.c_int64 * K)(*[int(v) for v in use])
     nbytes = lib.ddk_sampler_restore_masked_workspace_bytes(plan.handle, 2, 16, 16, K - 1, 1)
     assert nbytes >= lib.ddk_sampler_workspace_bytes(plan.handle, 2, 16, 16, K - 1) + (2 * 16 * 16 * 3 + 2 * 16 * 16) * 4
     assert nbytes >= lib.ddk_sampler_restore_workspace_bytes(plan.handle, 2, 16, 16, K - 1)
@@ -295,64 +256,39 @@ def test_chains_share_a_workspace_and_masks_share_a_graph(tiny, data):
     yd = {n: ops.nchw_to_nhwc(ys[n].to(DEV)) for n in (1, 2)}
     md = {"m1": mks[1].to(DEV), "m1b": (1 - mks[1]).to(DEV), "m2": mks[2].to(DEV)}
     jobs = {"m1": (1, "m1"), "m1b": (1, "m1b"), "m2": (2, "m2"), "r2": (2, None), "anc": None}
-    x = torch.empty_like(x0)
-    side = torch.cuda.Stream()
 
-    def run(ws, what):
-        x.copy_(x0)
-        torch.cuda.synchronize()
-        a = L.SamplerArgs(plan.handle, L.ptr(plan.packed), L.ptr(x), None, L.ptr(tables["c_recip"]), L.ptr(tables["c_recipm1"]),
-                          L.ptr(tables["c1"]), L.ptr(tables["c2"]), L.ptr(tables["sigma"]), 2, 16, 16, K - 1, 0, SEED, 0, 1, L.ptr(ws),
-                          nbytes)
-        with torch.cuda.stream(side):
-            if jobs[what] is None:
-                rc = lib.ddk_sampler_run_spaced(C.byref(a), tmap, side.cuda_stream)
-            elif what == "r2":
-                rc = lib.ddk_sampler_run_restore(C.byref(a), tmap, L.ptr(yd[2]), 2, side.cuda_stream)
-            else:
-                n, mk = jobs[what]
-                rc = lib.ddk_sampler_run_restore_masked(C.byref(a), tmap, L.ptr(yd[n]), L.ptr(md[mk]), n, side.cuda_stream)
-        assert rc == 0, L.last_error()
-        side.synchronize()
-        return x.clone()
+    def launch(what, a, tmap, stream):
+        if jobs[what] is None:
+            return lib.ddk_sampler_run_spaced(a, tmap, stream)
+        if what == "r2":
+            return lib.ddk_sampler_run_restore(a, tmap, L.ptr(yd[2]), 2, stream)
+        n, mk = jobs[what]
+        return lib.ddk_sampler_run_restore_masked(a, tmap, L.ptr(yd[n]), L.ptr(md[mk]), n, stream)
 
-    fresh = lambda: torch.empty(nbytes // 4 + 4, device=DEV)
-
-    def alone(what):
-        ws = fresh()
-        try:
-            return run(ws, what)
-        finally:      # the plan's cached graphs and shift table point into ws: drop them before the memory goes back
-            assert lib.ddk_sampler_release_workspace(plan.handle, L.ptr(ws)) == 0
-
-    single = {what: alone(what) for what in jobs}
+    sh = CC.SharedWorkspace(plan, tables, use, x0, nbytes, SEED, launch)
+    x, tmap = sh.x, sh.tmap
+    single = {what: sh.alone(what) for what in jobs}
     assert not torch.equal(single["m1"], single["m1b"]) and not torch.equal(single["m2"], single["r2"])
     assert not torch.equal(single["m1"], single["anc"])
     for order in (("m1", "r2", "anc", "m1b", "m2", "m1"), ("anc", "m2", "r2", "m1b", "m1", "anc")):
-        ws = fresh()
-        for what in order:
-            got = run(ws, what)
-            assert torch.equal(got, single[what]), (order, what, float((got - single[what]).abs().max()))
-        assert lib.ddk_sampler_release_workspace(plan.handle, L.ptr(ws)) == 0
+        sh.interleaved(order, single)
     # the measured pixels of the two masks' results are their own
     for what in ("m1", "m1b"):
         out = ops.nhwc_to_nchw(single[what]).cpu()
-        s = _sel(md[what].cpu(), ys[1])
+        s = CC.sel(md[what].cpu(), ys[1])
         assert torch.equal(out[s], ys[1][s])
     # a null mask on this entry is the unmasked chain; n = 1 without a mask, injected noise and a bad n are rejected
-    ws = fresh()
-    a = L.SamplerArgs(plan.handle, L.ptr(plan.packed), L.ptr(x), None, L.ptr(tables["c_recip"]), L.ptr(tables["c_recipm1"]),
-                      L.ptr(tables["c1"]), L.ptr(tables["c2"]), L.ptr(tables["sigma"]), 2, 16, 16, K - 1, 0, SEED, 0, 0, L.ptr(ws), nbytes)
-    x.copy_(x0)                                           # eager (the legacy stream cannot be captured): the same bits as the graph
-    assert lib.ddk_sampler_run_restore_masked(C.byref(a), tmap, L.ptr(yd[2]), None, 2, L.stream()) == 0, L.last_error()
-    torch.cuda.synchronize()
-    assert torch.equal(x, single["r2"])
-    assert lib.ddk_sampler_run_restore_masked(C.byref(a), tmap, L.ptr(yd[1]), None, 1, L.stream()) == -1 and "mask" in L.last_error()
-    assert lib.ddk_sampler_run_restore_masked(C.byref(a), tmap, L.ptr(yd[1]), L.ptr(md["m1"]), 3, L.stream()) == -1
-    noise = torch.zeros((K, *x.shape), device=DEV)
-    a.noise = L.ptr(noise)
-    assert lib.ddk_sampler_run_restore_masked(C.byref(a), tmap, L.ptr(yd[1]), L.ptr(md["m1"]), 1, L.stream()) == -1 and "noise" in L.last_error()
-    assert lib.ddk_sampler_release_workspace(plan.handle, L.ptr(ws)) == 0
+    with CC.workspace(plan, nbytes) as ws:
+        a = CC.sampler_args(plan, x, tables, K - 1, ws, nbytes, seed=SEED)
+        x.copy_(x0)                                       # eager (the legacy stream cannot be captured): the same bits as the graph
+        assert lib.ddk_sampler_run_restore_masked(a, tmap, L.ptr(yd[2]), None, 2, L.stream()) == 0, L.last_error()
+        torch.cuda.synchronize()
+        assert torch.equal(x, single["r2"])
+        assert lib.ddk_sampler_run_restore_masked(a, tmap, L.ptr(yd[1]), None, 1, L.stream()) == -1 and "mask" in L.last_error()
+        assert lib.ddk_sampler_run_restore_masked(a, tmap, L.ptr(yd[1]), L.ptr(md["m1"]), 3, L.stream()) == -1
+        noise = torch.zeros((K, *x.shape), device=DEV)
+        a.noise = L.ptr(noise)
+        assert lib.ddk_sampler_run_restore_masked(a, tmap, L.ptr(yd[1]), L.ptr(md["m1"]), 1, L.stream()) == -1 and "noise" in L.last_error()
     assert ops.cluster_timeouts() == before
 
 
@@ -380,11 +316,11 @@ def test_dddpm_restore_holds_the_latent_constraint_and_pastes():
     raw, _ = m.restore(img.to(DEV), mk, 1, respacing="10", ddim=True, x_T=z_T, seed=SEED, paste=False)
     assert not torch.equal(raw.cpu()[sel], img[sel]) and torch.equal(raw.cpu()[~sel], x_out.cpu()[~sel])
     # scale 8: a 4 x 4 low-resolution image with holes, latent block 2
-    y = _y((2, 3, 32, 32), 8, "restore_masked.dd.y")
-    mk8 = _mask("checker", 2, 4, 4)
+    y = CC.pooled_y((2, 3, 32, 32), 8, "restore_masked.dd.y")
+    mk8 = CC.mask("checker", 2, 4, 4)
     x8, z8 = m.restore(y.to(DEV), mk8, 8, respacing="10", x_T=z_T, seed=SEED)
     with torch.no_grad():
-        zr = m.rescaled_downsample(RR.replicate(torch.where(_sel(mk8, y), y, torch.zeros_like(y)), 8).to(DEV))
+        zr = m.rescaled_downsample(RR.replicate(torch.where(CC.sel(mk8, y), y, torch.zeros_like(y)), 8).to(DEV))
         y_lat = torch.nn.functional.avg_pool2d(zr, 2).cpu()
         assert torch.equal(x8, m.rescaled_upsample(z8))
     err = _means_err(z8.cpu(), y_lat, mk8, 2)
@@ -393,43 +329,26 @@ def test_dddpm_restore_holds_the_latent_constraint_and_pastes():
 
 
 # ---------------------------------------------------------------- the command line (a fresh child process each)
-def _cli_setup(tmp_path):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cfg = ddpm_cfg(32, 3, 16, T=100)
-    cfg.update(model="ddpm", dataset="celeba")
-    (tmp_path / "cfg.json").write_text(json.dumps(cfg))
-    imgs = (np.random.default_rng(0).random((3, 16, 16, 3)) * 255).astype(np.uint8)
-    np.save(tmp_path / "imgs.npy", imgs)
-    env = dict(os.environ, PYTHONPATH=os.path.join(root, "downsampled-diffusion_amd"))
-    return root, env, imgs
-
-
 def test_inpaint_cli_with_ddnm(tmp_path):
-    root, env, imgs = _cli_setup(tmp_path)
-    script = os.path.join(root, "downsampled-diffusion_amd", "inpaint_model_samples.py")
-    base = [sys.executable, script, "--synthetic", str(tmp_path / "cfg.json"), "--saved_model", "clitest", "--images",
-            str(tmp_path / "imgs.npy"), "--mask", "left", "--timestep_respacing", "10", "--batch_size", "2", "--seed", "3", "--out_dir",
-            str(tmp_path), "--method", "ddnm"]
-    r = subprocess.run(base + ["--use_ddim", "--eta", "0.5"], capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
+    cfg_path, images_path, imgs, env = CC.cli_files(tmp_path, CC.cli_cfg(), 3, 16)
+    base = ["inpaint_model_samples.py", "--synthetic", cfg_path, "--saved_model", "clitest", "--images", images_path, "--mask", "left",
+            "--timestep_respacing", "10", "--batch_size", "2", "--seed", "3", "--out_dir", tmp_path, "--method", "ddnm"]
+    CC.run_script(*base, "--use_ddim", "--eta", "0.5", env=env)
     out = np.load(tmp_path / "clitest_inpaint_left_10_ddnm_ddim_eta0.5.npy")
     masked = np.load(tmp_path / "clitest_inpaint_left_10_ddnm_ddim_eta0.5_masked.npy")
     assert out.shape == (3, 16, 16, 3) and out.dtype == np.float32 and np.isfinite(out).all() and out.min() >= 0 and out.max() <= 255
     assert np.abs(out[:, :, 8:] - imgs[:, :, 8:]).max() < 1e-3             # the known half comes back
     assert np.abs(out[:, :, :8] - imgs[:, :, :8]).max() > 1 and (masked[:, :, :8] == 0).all()
-    r = subprocess.run(base + ["--jump_length", "5"], capture_output=True, text=True, env=env, timeout=300)
+    r = CC.run_script(*base, "--jump_length", "5", env=env, check=False)
     assert r.returncode != 0 and "jump" in r.stderr
 
 
 def test_evaluate_cli_with_ddnm(tmp_path):
-    root, env, imgs = _cli_setup(tmp_path)
+    cfg_path, images_path, _, env = CC.cli_files(tmp_path, CC.cli_cfg(), 3, 16)
     np.save(tmp_path / "ones.npy", np.ones((16, 16), dtype=np.float32))
-    script = os.path.join(root, "downsampled-diffusion_amd", "evaluate_restoration.py")
-    r = subprocess.run([sys.executable, script, "--synthetic", str(tmp_path / "cfg.json"), "--images", str(tmp_path / "imgs.npy"), "--task",
-                        "inpaint", "--method", "ddnm", "--use_ddim", "--mask", str(tmp_path / "ones.npy"), "--timestep_respacing", "10",
-                        "--batch_size", "2", "--seed", "9", "--json", str(tmp_path / "out.json")],
-                       capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
+    CC.run_script("evaluate_restoration.py", "--synthetic", cfg_path, "--images", images_path, "--task", "inpaint", "--method", "ddnm",
+                  "--use_ddim", "--mask", tmp_path / "ones.npy", "--timestep_respacing", "10", "--batch_size", "2", "--seed", "9", "--json",
+                  tmp_path / "out.json", env=env)
     out = json.loads((tmp_path / "out.json").read_text())
     st, me = out["settings"], out["metrics"]
     assert (st["task"], st["method"], st["unet_forwards"], st["respacing"], st["ddim"], st["eta"]) == ("inpaint", "ddnm", 10, "10", True, 0.0)

@@ -7,18 +7,14 @@ Shapes and bars are those of tests/test_restore_masked_gpu.py for the correspond
 restatement's chain to 1e-4 and between the Python loop and the native sampler to 1e-5; a 128-channel UNet on 8x32x32 latents at
 B = 16 for the fused tail (n = 1, 2 fused, n = 8 not eligible); fused and unfused tails, and chains that share a workspace: the same
 bits."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
+import chain_cases as CC
 import restore_noisy_ref as RN
-import restore_ref as RR
-from helpers import dddpm_cfg, ddpm_cfg, det_load
+from helpers import dddpm_cfg, ddpm_cfg, det_load, to_nhwc
 from oracle import diffusion_ref as D
-from oracle import philox_ref as PR
-from oracle import unet_ref as U
 from utils import synthetic as syn
 
 pytestmark = pytest.mark.gpu
@@ -34,44 +30,19 @@ KINDS = [dict(), dict(ddim=True, eta=0.5)]
 IDS = ["ancestral", "ddim_eta0.5"]
 
 
-def _mask(kind, b, h, w):
-    """[b, h, w] {0, 1}: a checkerboard, a single measured block / pixel, a single hidden one (at another place per image)"""
-    i, j = torch.meshgrid(torch.arange(h), torch.arange(w), indexing="ij")
-    if kind == "checker":
-        return torch.stack([((i + j + k) % 2).float() for k in range(b)])
-    m = torch.zeros(b, h, w) if kind == "one_measured" else torch.ones(b, h, w)
-    for k in range(b):
-        m[k, (k * 3 + 1) % h, (k * 5 + w - 1) % w] = 1.0 - m[k, 0, 0]
-    return m
-
-
-def _y(shape, n, name):
-    return RR.pool(syn.synthetic_normal(shape, name).clamp(-1, 1), n).contiguous()
-
-
-def _sel(mk, y):
-    return (mk != 0).unsqueeze(1).expand_as(y)
-
-
-nhwc = lambda v: v.permute(0, 2, 3, 1).contiguous()
-
-
 @pytest.fixture(scope="module")
 def tiny():
-    from models import DDPM, Unet
-    m = det_load(DDPM(CFG, Unet(CFG), DEV, 3)).to(DEV).eval()
-    sd = {k: v.detach().cpu() for k, v in m.state_dict().items()}
-    return m, (lambda x, t: U.unet_forward(sd, CFG, x, t, pre="latent_model."))
+    return CC.tiny_ddpm(CFG)
 
 
 @pytest.fixture(scope="module")
 def data():
     """a noisy y and a mask per block, one start state: computed once, never changed"""
     x_T = syn.synthetic_normal(SHAPE, "restore_noisy.xT")
-    mks = {n: _mask("checker", 2, 16 // n, 16 // n) for n in (1, 2)}
+    mks = {n: CC.mask("checker", 2, 16 // n, 16 // n) for n in (1, 2)}
     ys = {}
     for n in (1, 2):
-        y0 = _y(SHAPE, n, f"restore_noisy.x{n}") + SIGMA_Y * syn.synthetic_normal((2, 3, 16 // n, 16 // n), f"restore_noisy.n{n}")
+        y0 = CC.pooled_y(SHAPE, n, f"restore_noisy.x{n}") + SIGMA_Y * syn.synthetic_normal((2, 3, 16 // n, 16 // n), f"restore_noisy.n{n}")
         ys[n] = y0
     return ys, mks, x_T
 
@@ -86,19 +57,6 @@ def native(tiny, data):
 
 
 # ---------------------------------------------------------------- the lone op, bit for bit
-def _hand_tables(g):
-    """8 rows, made by hand: lam strictly between 0 and 1 in rows 1, 2, 5, 6, 7, exactly 1 in rows 3 and 4, sgm != sigma everywhere"""
-    tab = {k: torch.rand(8, generator=g) * s for k, s in (("c_recip", 3.0), ("c_recipm1", 2.0), ("c1", 1.0), ("c2", 1.0), ("sigma", 0.5))}
-    tab["c1"][0], tab["c2"][0] = 1.0, 0.0
-    tab["lam"] = 0.1 + 0.8 * torch.rand(8, generator=g)
-    tab["lam"][3] = tab["lam"][4] = 1.0
-    tab["lam"][0] = 0.0
-    tab["sgm"] = tab["sigma"] * (0.1 + 0.8 * torch.rand(8, generator=g))
-    tab["sgm"][0] = 0.0
-    assert ((tab["lam"][[1, 2, 5, 6, 7]] > 0) & (tab["lam"][[1, 2, 5, 6, 7]] < 1)).all() and (tab["sgm"][1:] != tab["sigma"][1:]).all()
-    return tab
-
-
 @pytest.mark.parametrize("hw", [(16, 16), (8, 32)], ids=["16x16", "8x32"])
 @pytest.mark.parametrize("c", [3, 4, 8])
 @pytest.mark.parametrize("n", [1, 2, 4, 8])
@@ -116,22 +74,18 @@ def test_lone_op_equals_restatement_bit_for_bit(n, c, hw):
     e = torch.randn(shape, generator=g)
     y0 = torch.rand(B, c, h // n, w // n, generator=g) * 2 - 1
     t = torch.tensor([0, 7, 3])
-    tab = _hand_tables(g)
+    tab = CC.hand_tables(g, noisy=True)
     seed, stream = 24680, 5
-    z_dev = torch.stack([ops.randn((B, h, w, c), DEV, seed, int(tb), stream)[b] for b, tb in enumerate(t)]).cpu()
-    z_ref = torch.from_numpy(np.stack([PR.philox_normal(B * h * w * c, seed, int(tb), stream).reshape(B, h, w, c)[b]
-                                       for b, tb in enumerate(t)]))
-    assert float((z_dev - z_ref).abs().max()) < 1e-5
+    z = CC.philox_draws(B, c, h, w, t, seed, stream)
     sg = torch.where(t > 0, tab["sigma"][t], torch.zeros(B))
     dtab = {k: v.to(DEV) for k, v in tab.items()}
     row = lambda k: tab[k][t]
-    cases = [(kind, _mask(kind, B, h // n, w // n)) for kind in ("checker", "one_measured", "one_hidden")] + ([("none", None)] if n > 1 else [])
+    cases = [(kind, CC.mask(kind, B, h // n, w // n)) for kind in ("checker", "one_measured", "one_hidden")] + ([("none", None)] if n > 1 else [])
     for kind, mk in cases:
-        y = y0 if mk is None else torch.where(_sel(mk, y0), y0, torch.full_like(y0, float("nan")))
-        want = RN.step(x, e, y, mk, n, row("c_recip"), row("c_recipm1"), row("c1"), row("c2"), sg, row("lam"), row("sgm"),
-                       z_dev.permute(0, 3, 1, 2))
-        xs = nhwc(x).to(DEV)
-        ops.p_sample_update_restore_noisy_(xs, nhwc(e).to(DEV), nhwc(y).to(DEV), None if mk is None else mk.to(DEV), n, t.to(DEV), **dtab,
+        y = y0 if mk is None else torch.where(CC.sel(mk, y0), y0, torch.full_like(y0, float("nan")))
+        want = RN.step(x, e, y, mk, n, row("c_recip"), row("c_recipm1"), row("c1"), row("c2"), sg, row("lam"), row("sgm"), z)
+        xs = to_nhwc(x).to(DEV)
+        ops.p_sample_update_restore_noisy_(xs, to_nhwc(e).to(DEV), to_nhwc(y).to(DEV), None if mk is None else mk.to(DEV), n, t.to(DEV), **dtab,
                                            seed=seed, stream_id=stream)
         got = xs.cpu().permute(0, 3, 1, 2)
         assert torch.isfinite(got).all(), kind
@@ -153,7 +107,7 @@ def test_lam_one_and_sgm_sigma_is_the_masked_op_bit_for_bit(n):
     tab = {k: (torch.rand(8, generator=g) * s).to(DEV) for k, s in (("c_recip", 3.0), ("c_recipm1", 2.0), ("c1", 1.0), ("c2", 1.0), ("sigma", 0.5))}
     sgm = tab["sigma"].clone()
     sgm[0] = 0.0                      # the kernels apply sigma as (row > 0 ? sigma : 0)
-    for mk in (_mask("checker", B, h // n, w // n).to(DEV), None):
+    for mk in (CC.mask("checker", B, h // n, w // n).to(DEV), None):
         a, b = x.to(DEV), x.to(DEV)
         ops.p_sample_update_restore_noisy_(a, e.to(DEV), y.to(DEV), mk, n, t, **tab, lam=torch.ones(8, device=DEV), sgm=sgm, seed=9, stream_id=2)
         ops.p_sample_update_restore_masked_(b, e.to(DEV), y.to(DEV), mk, n, t, **tab, seed=9, stream_id=2)
@@ -169,7 +123,7 @@ def test_point_op_with_lam_one_returns_y_within_one_rounding(c):
     B, h, w = 2, 16, 16
     x, e = 2 * torch.randn(B, h, w, c, generator=g), torch.randn(B, h, w, c, generator=g)
     y = torch.rand(B, h, w, c, generator=g) * 2 - 1
-    mk = _mask("checker", B, h, w)
+    mk = CC.mask("checker", B, h, w)
     one, zero = torch.ones(1, device=DEV), torch.zeros(1, device=DEV)
     tab = dict(c_recip=torch.full((1,), 1.7, device=DEV), c_recipm1=torch.full((1,), 0.9, device=DEV), c1=one, c2=zero, sigma=one, lam=one, sgm=zero)
     out = x.to(DEV)
@@ -219,17 +173,11 @@ def test_graph_equals_eager_and_python_loop_is_close(tiny, data, native, kw, n):
     ys, mks, x_T = data
     graphed = native[n, IDS[KINDS.index(kw)]]
     run = lambda: m.restore_noisy(ys[n].to(DEV), mks[n], n, sigma_y=SIGMA_Y, respacing="8", x_T=x_T, seed=SEED, **kw).cpu()
-    m.use_graph = False
-    try:
+    with CC.toggled(m, "use_graph", False):
         eager = run()
-    finally:
-        m.use_graph = True
     assert torch.equal(graphed, eager)
-    m.native_sampler = False
-    try:
+    with CC.toggled(m, "native_sampler", False):
         loop = run()
-    finally:
-        m.native_sampler = True
     err = float((loop - graphed).abs().max())
     print(f"Python loop vs native, DDNM+ n={n} 8 steps {kw}: {err:.3g}")
     assert err < LOOP_TOL
@@ -239,7 +187,7 @@ def test_unmeasured_y_reaches_nothing_and_the_measurement_is_not_pasted(tiny, da
     m, _ = tiny
     ys, mks, x_T = data
     out = native[1, "ancestral"]
-    s1 = _sel(mks[1], ys[1])
+    s1 = CC.sel(mks[1], ys[1])
     y_nan = torch.where(s1, ys[1], torch.full_like(ys[1], float("nan")))
     from ddk import ops
     tables, use = m._noisy_tables("8", False, 0.0, SIGMA_Y)
@@ -255,8 +203,8 @@ def test_unmeasured_y_reaches_nothing_and_the_measurement_is_not_pasted(tiny, da
 def test_sigma_y_zero_is_restore_bit_for_bit(tiny, n, kw):
     m, _ = tiny
     kw = dict(dict(respacing="8"), **kw)
-    y = _y(SHAPE, n, f"restore_noisy.zero{n}")
-    mk = _mask("checker", 2, 16 // n, 16 // n)
+    y = CC.pooled_y(SHAPE, n, f"restore_noisy.zero{n}")
+    mk = CC.mask("checker", 2, 16 // n, 16 // n)
     x_T = syn.synthetic_normal(SHAPE, "restore_noisy.zero.xT")
     want = m.restore(y.to(DEV), mk, n, x_T=x_T, seed=SEED, **kw)
     assert torch.equal(m.restore_noisy(y.to(DEV), mk, n, sigma_y=0, x_T=x_T, seed=SEED, **kw), want)
@@ -283,9 +231,9 @@ def test_fused_tail_equals_unfused_bit_for_bit(wide, n, masked):
     B = 16
     shape = (B, 8, 32, 32)
     assert plan.restore_noisy_tail_parts(B, 32, 32, n) == (0 if n == 8 else 8)
-    y0 = _y(shape, n, f"restore_noisy.wide.{n}") + SIGMA_Y * syn.synthetic_normal((B, 8, 32 // n, 32 // n), f"restore_noisy.wide.n{n}")
-    mk = _mask("checker", B, 32 // n, 32 // n) if masked else None
-    y = torch.where(_sel(mk, y0), y0, torch.full_like(y0, float("nan"))) if masked else y0
+    y0 = CC.pooled_y(shape, n, f"restore_noisy.wide.{n}") + SIGMA_Y * syn.synthetic_normal((B, 8, 32 // n, 32 // n), f"restore_noisy.wide.n{n}")
+    mk = CC.mask("checker", B, 32 // n, 32 // n) if masked else None
+    y = torch.where(CC.sel(mk, y0), y0, torch.full_like(y0, float("nan"))) if masked else y0
     x_T = syn.synthetic_normal(shape, "restore_noisy.wide.xT")
     run = lambda: m.restore_noisy(y.to(DEV), mk, n, sigma_y=SIGMA_Y, respacing="6", ddim=True, eta=0.5, x_T=x_T, seed=SEED).cpu()
     fused = run()
@@ -317,7 +265,6 @@ def test_chains_share_a_workspace_and_each_sigma_y_has_its_own_graph(tiny, data)
     for tb, _ in tabs.values():
         assert all(torch.equal(tb[k], tables[k]) for k in tables)
     K = len(use)
-    tmap = (C.c_int64 * K)(*[int(v) for v in use])
     nbytes = max(lib.ddk_sampler_restore_noisy_workspace_bytes(plan.handle, 2, 16, 16, K - 1, n) for n in (1, 2))
     assert nbytes == lib.ddk_sampler_restore_masked_workspace_bytes(plan.handle, 2, 16, 16, K - 1, 1)
     x0 = ops.nchw_to_nhwc(x_T.to(DEV).contiguous())
@@ -325,62 +272,37 @@ def test_chains_share_a_workspace_and_each_sigma_y_has_its_own_graph(tiny, data)
     md = {n: mks[n].to(DEV) for n in (1, 2)}
     # what -> (sigma_y, n, with a mask); "m1": the masked chain, "anc": the ancestral one
     jobs = {"a1": (0.1, 1, True), "b1": (0.4, 1, True), "a2": (0.1, 2, True), "a2nm": (0.1, 2, False), "m1": None, "anc": None}
-    x = torch.empty_like(x0)
-    side = torch.cuda.Stream()
 
-    def run(ws, what, graph=1, stream=None):
-        x.copy_(x0)
-        torch.cuda.synchronize()
-        a = L.SamplerArgs(plan.handle, L.ptr(plan.packed), L.ptr(x), None, L.ptr(tables["c_recip"]), L.ptr(tables["c_recipm1"]),
-                          L.ptr(tables["c1"]), L.ptr(tables["c2"]), L.ptr(tables["sigma"]), 2, 16, 16, K - 1, 0, SEED, 0, graph, L.ptr(ws),
-                          nbytes)
-        with torch.cuda.stream(side):
-            if what == "anc":
-                rc = lib.ddk_sampler_run_spaced(C.byref(a), tmap, side.cuda_stream)
-            elif what == "m1":
-                rc = lib.ddk_sampler_run_restore_masked(C.byref(a), tmap, L.ptr(yd[1]), L.ptr(md[1]), 1, side.cuda_stream)
-            else:
-                sy, n, masked = jobs[what]
-                tb = tabs[sy][0]
-                rc = lib.ddk_sampler_run_restore_noisy(C.byref(a), tmap, L.ptr(tb["lam"]), L.ptr(tb["sgm"]), L.ptr(yd[n]),
-                                                       L.ptr(md[n]) if masked else None, n, side.cuda_stream)
-        assert rc == 0, L.last_error()
-        side.synchronize()
-        return x.clone()
+    def launch(what, a, tmap, stream):
+        if what == "anc":
+            return lib.ddk_sampler_run_spaced(a, tmap, stream)
+        if what == "m1":
+            return lib.ddk_sampler_run_restore_masked(a, tmap, L.ptr(yd[1]), L.ptr(md[1]), 1, stream)
+        sy, n, masked = jobs[what]
+        tb = tabs[sy][0]
+        return lib.ddk_sampler_run_restore_noisy(a, tmap, L.ptr(tb["lam"]), L.ptr(tb["sgm"]), L.ptr(yd[n]), L.ptr(md[n]) if masked else None, n,
+                                                 stream)
 
-    fresh = lambda: torch.empty(nbytes // 4 + 4, device=DEV)
-
-    def alone(what):
-        ws = fresh()
-        try:
-            return run(ws, what)
-        finally:      # the plan's cached graphs and shift table point into ws: drop them before the memory goes back
-            assert lib.ddk_sampler_release_workspace(plan.handle, L.ptr(ws)) == 0
-
-    single = {what: alone(what) for what in jobs}
+    sh = CC.SharedWorkspace(plan, tables, use, x0, nbytes, SEED, launch)
+    x, tmap = sh.x, sh.tmap
+    single = {what: sh.alone(what) for what in jobs}
     names = list(jobs)
     for i, p in enumerate(names):
         for q in names[i + 1:]:
             assert not torch.equal(single[p], single[q]), (p, q)
     for order in (("a1", "b1", "a1", "m1", "anc", "a2", "a2nm", "b1"), ("anc", "a2nm", "m1", "b1", "a2", "a1", "anc", "m1")):
-        ws = fresh()
-        for what in order:
-            got = run(ws, what)
-            assert torch.equal(got, single[what]), (order, what, float((got - single[what]).abs().max()))
-        assert lib.ddk_sampler_release_workspace(plan.handle, L.ptr(ws)) == 0
+        sh.interleaved(order, single)
     # n = 1 without a mask, a bad n, a null table and injected noise are rejected
-    ws = fresh()
     tb = tabs[0.1][0]
-    a = L.SamplerArgs(plan.handle, L.ptr(plan.packed), L.ptr(x), None, L.ptr(tables["c_recip"]), L.ptr(tables["c_recipm1"]),
-                      L.ptr(tables["c1"]), L.ptr(tables["c2"]), L.ptr(tables["sigma"]), 2, 16, 16, K - 1, 0, SEED, 0, 0, L.ptr(ws), nbytes)
-    call = lambda lam, sgm, y, mk, n: lib.ddk_sampler_run_restore_noisy(C.byref(a), tmap, lam, sgm, y, mk, n, L.stream())
-    assert call(L.ptr(tb["lam"]), L.ptr(tb["sgm"]), L.ptr(yd[1]), None, 1) == -1 and "mask" in L.last_error()
-    assert call(L.ptr(tb["lam"]), L.ptr(tb["sgm"]), L.ptr(yd[1]), L.ptr(md[1]), 3) == -1
-    assert call(None, L.ptr(tb["sgm"]), L.ptr(yd[1]), L.ptr(md[1]), 1) == -1 and "table" in L.last_error()
-    noise = torch.zeros((K, *x.shape), device=DEV)
-    a.noise = L.ptr(noise)
-    assert call(L.ptr(tb["lam"]), L.ptr(tb["sgm"]), L.ptr(yd[1]), L.ptr(md[1]), 1) == -1 and "noise" in L.last_error()
-    assert lib.ddk_sampler_release_workspace(plan.handle, L.ptr(ws)) == 0
+    with CC.workspace(plan, nbytes) as ws:
+        a = CC.sampler_args(plan, x, tables, K - 1, ws, nbytes, seed=SEED)
+        call = lambda lam, sgm, y, mk, n: lib.ddk_sampler_run_restore_noisy(a, tmap, lam, sgm, y, mk, n, L.stream())
+        assert call(L.ptr(tb["lam"]), L.ptr(tb["sgm"]), L.ptr(yd[1]), None, 1) == -1 and "mask" in L.last_error()
+        assert call(L.ptr(tb["lam"]), L.ptr(tb["sgm"]), L.ptr(yd[1]), L.ptr(md[1]), 3) == -1
+        assert call(None, L.ptr(tb["sgm"]), L.ptr(yd[1]), L.ptr(md[1]), 1) == -1 and "table" in L.last_error()
+        noise = torch.zeros((K, *x.shape), device=DEV)
+        a.noise = L.ptr(noise)
+        assert call(L.ptr(tb["lam"]), L.ptr(tb["sgm"]), L.ptr(yd[1]), L.ptr(md[1]), 1) == -1 and "noise" in L.last_error()
     assert ops.cluster_timeouts() == before
 
 
@@ -401,8 +323,8 @@ def test_dddpm_restore_noisy_returns_image_and_latent_and_never_pastes():
     with torch.no_grad():
         assert torch.equal(x_out, m.rescaled_upsample(z))
     # scale 8: a 4 x 4 noisy low-resolution image with holes, latent block 2
-    y = _y((2, 3, 32, 32), 8, "restore_noisy.dd.y") + 0.1 * syn.synthetic_normal((2, 3, 4, 4), "restore_noisy.dd.ny")
-    x8, z8 = m.restore_noisy(y.to(DEV), _mask("checker", 2, 4, 4), 8, sigma_y=0.1, respacing="8", x_T=z_T, seed=SEED)
+    y = CC.pooled_y((2, 3, 32, 32), 8, "restore_noisy.dd.y") + 0.1 * syn.synthetic_normal((2, 3, 4, 4), "restore_noisy.dd.ny")
+    x8, z8 = m.restore_noisy(y.to(DEV), CC.mask("checker", 2, 4, 4), 8, sigma_y=0.1, respacing="8", x_T=z_T, seed=SEED)
     assert x8.shape == (2, 3, 32, 32) and z8.shape == (2, 8, 8, 8) and torch.isfinite(x8).all()
 
 

@@ -8,21 +8,17 @@ The bars.  u = 2^-24.  L . in . R^T is a dot product of length Hi of dot product
 accumulators' final adds).  The lone op's bar is test_restore_blur_gpu.py's.  Chains: 1e-4 abs against the restatement with the same
 argmax, the TOL of the deblurring tests for the same model and the same step kernels, and 1e-5 between the Python loop and the native
 sampler; graph replay equals eager launches bit for bit."""
-import ctypes as C
 import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import blur_ref as BR
+import chain_cases as CC
 import resize_ref as ZR
-from helpers import dddpm_cfg, ddpm_cfg, det_load
+from helpers import dddpm_cfg, ddpm_cfg, to_nchw as nchw, to_nhwc as nhwc
 from oracle import diffusion_ref as D
-from oracle import unet_ref as U
 from utils import synthetic as syn
 
 pytestmark = pytest.mark.gpu
@@ -41,9 +37,6 @@ U24 = 2.0 ** -24
 RECT = [(3, 8, 8, 32, 32), (1, 4, 4, 16, 16), (3, 12, 20, 48, 80), (3, 16, 16, 64, 64), (3, 64, 64, 256, 256), (3, 32, 32, 8, 8),
         (1, 16, 16, 4, 4), (8, 64, 32, 16, 8), (3, 256, 256, 64, 64)]
 B = 2
-
-nhwc = lambda v: v.permute(0, 2, 3, 1).contiguous()
-nchw = lambda v: v.permute(0, 3, 1, 2).contiguous()
 
 
 def _rect_inputs(c, hi, wi, ho, wo):
@@ -179,8 +172,7 @@ def test_plane_wide_op_agrees_with_the_block_local_op(c, h, w, n):
     x, e = 2 * torch.randn(shape, generator=g), torch.randn(shape, generator=g)
     y = torch.rand((Bn, c, h // n, w // n), generator=g) * 2 - 1
     t = torch.tensor([0, 7, 3])
-    tab = {k: torch.rand(8, generator=g) * s for k, s in (("c_recip", 3.0), ("c_recipm1", 2.0), ("c1", 1.0), ("c2", 1.0), ("sigma", 0.5))}
-    tab["c1"][0], tab["c2"][0] = 1.0, 0.0
+    tab = CC.hand_tables(g)
     seed, stream = 97531, 4
     m = dict(zip(("A_h", "A_w", "Q_h", "Q_w", "P_h", "P_w"), blur.separable_operands(blur.resize_matrix(h, n, "mean"), blur.resize_matrix(w, n, "mean"))))
     assert float((m["Q_h"] - torch.eye(h // n).repeat_interleave(n, dim=0)).abs().max()) <= 1e-6       # A+ repeats
@@ -210,10 +202,7 @@ def test_plane_wide_op_agrees_with_the_block_local_op(c, h, w, n):
 # ---------------------------------------------------------------- the tiny DDPM, "20" steps
 @pytest.fixture(scope="module")
 def tiny():
-    from models import DDPM, Unet
-    m = det_load(DDPM(CFG, Unet(CFG), DEV, 3)).to(DEV).eval()
-    sd = {k: v.detach().cpu() for k, v in m.state_dict().items()}
-    return m, (lambda x, t: U.unet_forward(sd, CFG, x, t, pre="latent_model."))
+    return CC.tiny_ddpm(CFG)
 
 
 @pytest.fixture(scope="module")
@@ -235,10 +224,6 @@ def reference(tiny, data):
             for n in SCALES for i, kw in zip(IDS, KINDS)}
 
 
-def _argmax(x):
-    return x.reshape(x.shape[0], -1).argmax(dim=1)
-
-
 @pytest.mark.parametrize("n", SCALES)
 @pytest.mark.parametrize("kw", KINDS, ids=IDS)
 def test_tiny_vs_restatement(tiny, data, reference, kw, n):
@@ -250,7 +235,7 @@ def test_tiny_vs_restatement(tiny, data, reference, kw, n):
     print(f"DDNM bicubic x{n} tiny DDPM, 20 steps {kw}: max abs error {err:.3g}")
     assert torch.isfinite(got).all() and got.shape == SHAPE
     assert err < TOL, err
-    assert torch.equal(_argmax(got), _argmax(want))
+    assert torch.equal(CC.argmax(got), CC.argmax(want))
     # full row rank: A P = A, so A(x_out) = y as far as fp32 goes.  Whatever the chain's distance from the restatement (< TOL per
     # element) does to the gap is at most the largest absolute row sums of the two matrices times TOL.
     mm = {k: v.float().double() for k, v in ZR.operands(ZR.matrix(16, n), ZR.matrix(16, n)).items()}
@@ -269,11 +254,8 @@ def test_graph_equals_eager_bit_for_bit(tiny, data, kw, n):
     y, x_T = data[0][n], data[1]
     run = lambda: m.super_resolve(y.to(DEV), n, downsample="bicubic", respacing="20", x_T=x_T, seed=SEED, **kw)
     graphed = run()
-    m.use_graph = False
-    try:
+    with CC.toggled(m, "use_graph", False):
         eager = run()
-    finally:
-        m.use_graph = True
     assert torch.equal(graphed, eager)
 
 
@@ -284,11 +266,8 @@ def test_python_loop_equals_native(tiny, data, kw, n):
     y, x_T = data[0][n], data[1]
     run = lambda: m.super_resolve(y.to(DEV), n, downsample="bicubic", respacing="20", x_T=x_T, seed=SEED, **kw)
     native = run()
-    m.native_sampler = False
-    try:
+    with CC.toggled(m, "native_sampler", False):
         loop = run()
-    finally:
-        m.native_sampler = True
     err = float((loop - native).abs().max())
     print(f"Python loop vs native, bicubic x{n} 20 steps {kw}: {err:.3g}")
     assert err < 1e-5
@@ -328,19 +307,18 @@ def test_chain_faults(tiny, data):
     plan = m._eps_model_nhwc().plan()
     lib = plan._lib
     K = len(use)
-    tmap = (C.c_int64 * K)(*[int(v) for v in use])
+    tmap = CC.timestep_map(use)
     nbytes = lib.ddk_sampler_restore_blur_workspace_bytes(plan.handle, 2, 16, 16, K - 1)
     md = m._sep_operands(ZR.matrix(16, 2), ZR.matrix(16, 2), 3e-2)
     x = torch.zeros(2, 16, 16, 3, device=DEV)
     y = torch.zeros(2, 8, 8, 3, device=DEV)
-    ws = torch.empty(nbytes // 4 + 4, device=DEV)
+    ws = CC.fresh_workspace(nbytes)
     noise = torch.zeros((K, *x.shape), device=DEV)
     mats = [L.ptr(md[k]) for k in ("P_h", "P_w", "Q_h", "Q_w")]
 
     def run(mats=mats, noise=None, h=8, w=8):
-        a = L.SamplerArgs(plan.handle, L.ptr(plan.packed), L.ptr(x), L.ptr(noise), L.ptr(tables["c_recip"]), L.ptr(tables["c_recipm1"]),
-                          L.ptr(tables["c1"]), L.ptr(tables["c2"]), L.ptr(tables["sigma"]), 2, 16, 16, K - 1, 0, SEED, 0, 0, L.ptr(ws), nbytes)
-        return lib.ddk_sampler_run_restore_sep(C.byref(a), tmap, *mats, L.ptr(y), h, w, L.stream())
+        a = CC.sampler_args(plan, x, tables, K - 1, ws, nbytes, seed=SEED, noise=noise)
+        return lib.ddk_sampler_run_restore_sep(a, tmap, *mats, L.ptr(y), h, w, L.stream())
     assert run(noise=noise) == -1 and "noise" in L.last_error()
     for h, w in ((6, 8), (8, 2), (0, 8), (20, 8), (8, 32)):
         assert run(h=h, w=w) == -1 and "multiples of 4" in L.last_error()
@@ -367,36 +345,23 @@ def test_sep_and_ancestral_chains_share_a_workspace(tiny, data):
     tables, use = m._spaced_tables("20", False, 0.0)
     plan = m._eps_model_nhwc().plan()
     lib = plan._lib
-    K = len(use)
-    tmap = (C.c_int64 * K)(*[int(v) for v in use])
-    nbytes = lib.ddk_sampler_restore_blur_workspace_bytes(plan.handle, 2, 16, 16, K - 1)
+    nbytes = lib.ddk_sampler_restore_blur_workspace_bytes(plan.handle, 2, 16, 16, len(use) - 1)
     md = {n: m._sep_operands(blur.resize_matrix(16, n), blur.resize_matrix(16, n), 3e-2) for n in SCALES}       # the model's own cached operands
     x0 = ops.nchw_to_nhwc(x_T.to(DEV).contiguous())
     runs = {"a": (2, ops.nchw_to_nhwc(ys[2].to(DEV))), "b": (2, ops.nchw_to_nhwc((0.5 * ys[2]).to(DEV))), "c": (4, ops.nchw_to_nhwc(ys[4].to(DEV)))}
-    x = torch.empty_like(x0)
-    ws = torch.empty(nbytes // 4 + 4, device=DEV)
-    side = torch.cuda.Stream()
 
-    def run(what):
-        x.copy_(x0)
-        torch.cuda.synchronize()
-        a = L.SamplerArgs(plan.handle, L.ptr(plan.packed), L.ptr(x), None, L.ptr(tables["c_recip"]), L.ptr(tables["c_recipm1"]),
-                          L.ptr(tables["c1"]), L.ptr(tables["c2"]), L.ptr(tables["sigma"]), 2, 16, 16, K - 1, 0, SEED, 0, 1, L.ptr(ws), nbytes)
-        with torch.cuda.stream(side):
-            if what is None:
-                rc = lib.ddk_sampler_run_spaced(C.byref(a), tmap, side.cuda_stream)
-            else:
-                n, y = runs[what]
-                mats = [L.ptr(md[n][k]) for k in ("P_h", "P_w", "Q_h", "Q_w")]
-                rc = lib.ddk_sampler_run_restore_sep(C.byref(a), tmap, *mats, L.ptr(y), 16 // n, 16 // n, side.cuda_stream)
-        assert rc == 0, L.last_error()
-        side.synchronize()
-        return x.clone()
+    def launch(what, a, tmap, stream):
+        if what is None:
+            return lib.ddk_sampler_run_spaced(a, tmap, stream)
+        n, y = runs[what]
+        mats = [L.ptr(md[n][k]) for k in ("P_h", "P_w", "Q_h", "Q_w")]
+        return lib.ddk_sampler_run_restore_sep(a, tmap, *mats, L.ptr(y), 16 // n, 16 // n, stream)
 
-    try:
+    sh = CC.SharedWorkspace(plan, tables, use, x0, nbytes, SEED, launch)
+    with CC.workspace(plan, nbytes) as ws:
         first = {}
         for what in ("a", None, "a", "c", None, "b", "a", "c", None, "b"):
-            got = run(what)
+            got = sh.run(ws, what)
             if what not in first:
                 first[what] = got
             assert torch.equal(got, first[what]), (what, float((got - first[what]).abs().max()))
@@ -404,8 +369,6 @@ def test_sep_and_ancestral_chains_share_a_workspace(tiny, data):
         # the library's own entry and the model's method are the same chain
         via_model = m.super_resolve(ys[2].to(DEV), 2, downsample="bicubic", respacing="20", x_T=x_T, seed=SEED)
         assert torch.equal(ops.nhwc_to_nchw(first["a"]), via_model)
-    finally:      # the plan's cached graphs and shift table point into ws: drop them before the memory goes back
-        assert lib.ddk_sampler_release_workspace(plan.handle, L.ptr(ws)) == 0
 
 
 def test_the_downsampled_model_refuses():
@@ -424,20 +387,10 @@ def test_the_downsampled_model_refuses():
 def test_upscale_cli_and_evaluator_with_bicubic(tmp_path):
     """upscale_model_samples.py and evaluate_restoration.py --task sr with synthetic weights on three 16 x 16 images, each in a fresh
     process, with --downsample bicubic and with the defaults: the files, their names, the reduced images and the JSON keys"""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cfg = ddpm_cfg(32, 3, 16, T=100)
-    cfg.update(model="ddpm", dataset="celeba")
-    cfg_path = tmp_path / "cfg.json"
-    cfg_path.write_text(json.dumps(cfg))
-    imgs = (np.random.default_rng(0).random((3, 16, 16, 3)) * 255).astype(np.uint8)
-    np.save(tmp_path / "imgs.npy", imgs)
-    env = dict(os.environ, PYTHONPATH=os.path.join(root, "downsampled-diffusion_amd"))
-    script = os.path.join(root, "downsampled-diffusion_amd", "upscale_model_samples.py")
+    cfg_path, images_path, imgs, env = CC.cli_files(tmp_path, CC.cli_cfg(), 3, 16)
     for extra, name in ((["--downsample", "bicubic"], "clitest_sr2_bicubic_5"), ([], "clitest_sr2_5")):
-        r = subprocess.run([sys.executable, script, "--synthetic", str(cfg_path), "--saved_model", "clitest", "--images", str(tmp_path / "imgs.npy"),
-                            "--scale", "2", "--timestep_respacing", "5", "--batch_size", "2", "--seed", "3", "--out_dir", str(tmp_path), *extra],
-                           capture_output=True, text=True, env=env, timeout=300)
-        assert r.returncode == 0, r.stderr[-2000:]
+        CC.run_script("upscale_model_samples.py", "--synthetic", cfg_path, "--saved_model", "clitest", "--images", images_path, "--scale", "2",
+                      "--timestep_respacing", "5", "--batch_size", "2", "--seed", "3", "--out_dir", tmp_path, *extra, env=env)
         out, lowres = np.load(tmp_path / f"{name}.npy"), np.load(tmp_path / f"{name}_lowres.npy")
         assert out.shape == (3, 16, 16, 3) and out.dtype == np.float32 and np.isfinite(out).all() and out.min() >= 0 and out.max() <= 255
         assert lowres.shape == (3, 8, 8, 3) and lowres.dtype == np.uint8
@@ -447,14 +400,12 @@ def test_upscale_cli_and_evaluator_with_bicubic(tmp_path):
         assert np.abs(lowres.astype(np.float64) - want).max() <= 1      # a rounding tie may fall either way in fp32
     assert sorted(p.name for p in tmp_path.glob("clitest_*")) == ["clitest_sr2_5.npy", "clitest_sr2_5_lowres.npy", "clitest_sr2_bicubic_5.npy",
                                                                  "clitest_sr2_bicubic_5_lowres.npy"]
-    script = os.path.join(root, "downsampled-diffusion_amd", "evaluate_restoration.py")
-    base = [sys.executable, script, "--synthetic", str(cfg_path), "--images", str(tmp_path / "imgs.npy"), "--task", "sr", "--scale", "2",
-            "--timestep_respacing", "5", "--batch_size", "2", "--json", str(tmp_path / "score.json")]
+    base = ["evaluate_restoration.py", "--synthetic", cfg_path, "--images", images_path, "--task", "sr", "--scale", "2",
+            "--timestep_respacing", "5", "--batch_size", "2", "--json", tmp_path / "score.json"]
     keys = {"checkpoint", "synthetic", "model", "task", "images", "n_images", "batch_size", "seed", "method", "unet_forwards", "respacing",
             "scale", "ddim", "eta"}
     for extra in (["--downsample", "bicubic"], []):
-        r = subprocess.run(base + extra, capture_output=True, text=True, env=env, timeout=300)
-        assert r.returncode == 0, r.stderr[-2000:]
+        CC.run_script(*base, *extra, env=env)
         res = json.loads((tmp_path / "score.json").read_text())
         s, mt = res["settings"], res["metrics"]
         assert set(s) == (keys | {"downsample"} if extra else keys)

@@ -8,22 +8,18 @@ history (the order of the fp32 operations is pinned); chains at that file's TOL 
 between the Python loop and the native sampler; order 1 against the merged DDIM eta 0 chain bit for bit (their fp32 tables are
 bitwise equal); measured pixels exact at n = 1, measured block means within 8 n^2 2^-24 at n >= 2; fused and unfused tails, graph
 and eager, a mask that measures nothing and the plain 2M chain: the same bits."""
-import ctypes as C
 import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
+import chain_cases as CC
 import restore_ref as RR
 import restore_solver_ref as RS
-from helpers import dddpm_cfg, ddpm_cfg, det_load
+from helpers import dddpm_cfg, ddpm_cfg, det_load, to_nchw, to_nhwc
 from oracle import diffusion_ref as D
-from oracle import unet_ref as U
-from test_restore_masked_gpu import TOL, _bar, _mask, _means_err, _sel, _y
+from test_restore_masked_gpu import TOL, _bar, _means_err
 from utils import synthetic as syn
 
 pytestmark = pytest.mark.gpu
@@ -38,18 +34,15 @@ CASE_IDS = ["n1-mask", "n2-mask", "n2-nomask"]
 
 @pytest.fixture(scope="module")
 def tiny():
-    from models import DDPM, Unet
-    m = det_load(DDPM(CFG, Unet(CFG), DEV, 3)).to(DEV).eval()
-    sd = {k: v.detach().cpu() for k, v in m.state_dict().items()}
-    return m, (lambda x, t: U.unet_forward(sd, CFG, x, t, pre="latent_model."))
+    return CC.tiny_ddpm(CFG)
 
 
 @pytest.fixture(scope="module")
 def data():
     """y and mask per block, one start state: computed once, never changed"""
     x_T = syn.synthetic_normal(SHAPE, "restore_solver.xT")
-    ys = {n: _y(SHAPE, n, f"restore_solver.x{n}") for n in (1, 2)}
-    mks = {n: _mask("checker", 2, 16 // n, 16 // n) for n in (1, 2)}
+    ys = {n: CC.pooled_y(SHAPE, n, f"restore_solver.x{n}") for n in (1, 2)}
+    mks = {n: CC.mask("checker", 2, 16 // n, 16 // n) for n in (1, 2)}
     return ys, mks, x_T
 
 
@@ -84,17 +77,15 @@ def test_lone_op_equals_restatement_bit_for_bit(n, c, hw):
     tab["c1"][0], tab["c2"][0], tab["c3"][0], tab["c3"][3] = 1.0, 0.0, 0.0, 0.0
     assert float(tab["c3"][7]) != 0.0
     dtab = {k: v.to(DEV) for k, v in tab.items()}
-    nhwc = lambda v: v.permute(0, 2, 3, 1).contiguous()
-    nchw = lambda v: v.cpu().permute(0, 3, 1, 2)
     rows = [tab[k][t] for k in ("c_recip", "c_recipm1", "c1", "c2", "c3")]
-    masks = [_mask(kind, B, h // n, w // n) for kind in ("checker", "one_measured", "one_hidden")] + ([None] if n > 1 else [])
+    masks = [CC.mask(kind, B, h // n, w // n) for kind in ("checker", "one_measured", "one_hidden")] + ([None] if n > 1 else [])
     for mk in masks:
-        y = y0 if mk is None else torch.where(_sel(mk, y0), y0, torch.full_like(y0, float("nan")))
+        y = y0 if mk is None else torch.where(CC.sel(mk, y0), y0, torch.full_like(y0, float("nan")))
         want_x, want_h = RS.step(x, e, hist, y, mk, n, *rows)
-        xs, hs = nhwc(x).to(DEV), nhwc(hist).to(DEV)
-        ops.p_sample_update_restore_multistep_(xs, nhwc(e).to(DEV), hs, nhwc(y).to(DEV), None if mk is None else mk.to(DEV), n, t.to(DEV),
+        xs, hs = to_nhwc(x).to(DEV), to_nhwc(hist).to(DEV)
+        ops.p_sample_update_restore_multistep_(xs, to_nhwc(e).to(DEV), hs, to_nhwc(y).to(DEV), None if mk is None else mk.to(DEV), n, t.to(DEV),
                                                **dtab)
-        got_x, got_h = nchw(xs), nchw(hs)
+        got_x, got_h = to_nchw(xs.cpu()), to_nchw(hs.cpu())
         assert torch.isfinite(got_x).all() and torch.isfinite(got_h).all()
         assert torch.equal(got_x, want_x), float((got_x - want_x).abs().max())
         assert torch.equal(got_h, want_h), float((got_h - want_h).abs().max())
@@ -102,12 +93,12 @@ def test_lone_op_equals_restatement_bit_for_bit(n, c, hw):
         assert torch.equal(got_x[0], got_h[0])
         m0 = torch.ones(1, h // n, w // n) if mk is None else mk[0:1]
         if n == 1:
-            assert torch.equal(got_x[0:1][_sel(m0, y[0:1])], y[0:1][_sel(m0, y[0:1])])
+            assert torch.equal(got_x[0:1][CC.sel(m0, y[0:1])], y[0:1][CC.sel(m0, y[0:1])])
         else:
             assert _means_err(got_x[0:1], y[0:1], m0, n) <= _bar(n)
     if n > 1:   # an all-ones mask is no mask
-        a, ha = nhwc(x).to(DEV), nhwc(hist).to(DEV)
-        ops.p_sample_update_restore_multistep_(a, nhwc(e).to(DEV), ha, nhwc(y0).to(DEV), torch.ones(B, h // n, w // n, device=DEV), n,
+        a, ha = to_nhwc(x).to(DEV), to_nhwc(hist).to(DEV)
+        ops.p_sample_update_restore_multistep_(a, to_nhwc(e).to(DEV), ha, to_nhwc(y0).to(DEV), torch.ones(B, h // n, w // n, device=DEV), n,
                                                t.to(DEV), **dtab)
         assert torch.equal(a, xs) and torch.equal(ha, hs)
 
@@ -155,7 +146,7 @@ def test_tiny_vs_restatement(tiny, data, native, n, masked):
     assert err < TOL, err
     mk = mks[n] if masked else torch.ones(2, 16 // n, 16 // n)
     if n == 1:
-        assert torch.equal(got[_sel(mk, ys[n])], ys[n][_sel(mk, ys[n])]) and float((got - ys[n])[~_sel(mk, ys[n])].abs().max()) > 1e-2
+        assert torch.equal(got[CC.sel(mk, ys[n])], ys[n][CC.sel(mk, ys[n])]) and float((got - ys[n])[~CC.sel(mk, ys[n])].abs().max()) > 1e-2
     else:
         assert _means_err(got, ys[n], mk, n) <= _bar(n)
 
@@ -166,17 +157,11 @@ def test_graph_equals_eager_and_python_loop_is_close(tiny, data, native, n, mask
     ys, mks, x_T = data
     graphed = native[n, masked]
     run = lambda: m.restore_solver(ys[n].to(DEV), mks[n] if masked else None, n, respacing=SPEC, x_T=x_T).cpu()
-    m.use_graph = False
-    try:
+    with CC.toggled(m, "use_graph", False):
         eager = run()
-    finally:
-        m.use_graph = True
     assert torch.equal(graphed, eager)
-    m.native_sampler = False
-    try:
+    with CC.toggled(m, "native_sampler", False):
         loop = run()
-    finally:
-        m.native_sampler = True
     err = float((loop - graphed).abs().max())
     print(f"Python loop vs native, DDNM on 2M n={n} mask={masked} {SPEC}: {err:.3g}")
     assert err < 1e-5
@@ -238,9 +223,9 @@ def test_fused_tail_equals_unfused_bit_for_bit(wide, n):
     B = 16
     shape = (B, 8, 32, 32)
     assert plan.restore_multistep_tail_parts(B, 32, 32, n) == (0 if n == 8 else 8)
-    y0 = _y(shape, n, f"restore_solver.wide.{n}")
-    mk = _mask("checker", B, 32 // n, 32 // n)
-    y = torch.where(_sel(mk, y0), y0, torch.full_like(y0, float("nan")))
+    y0 = CC.pooled_y(shape, n, f"restore_solver.wide.{n}")
+    mk = CC.mask("checker", B, 32 // n, 32 // n)
+    y = torch.where(CC.sel(mk, y0), y0, torch.full_like(y0, float("nan")))
     x_T = syn.synthetic_normal(shape, "restore_solver.wide.xT")
     run = lambda: m.restore_solver(y.to(DEV), mk, n, respacing="logsnr6", x_T=x_T).cpu()
     fused = run()
@@ -253,7 +238,7 @@ def test_fused_tail_equals_unfused_bit_for_bit(wide, n):
     assert torch.isfinite(fused).all()
     assert torch.equal(fused, unfused), float((fused - unfused).abs().max())
     if n == 1:
-        assert torch.equal(fused[_sel(mk, y)], y[_sel(mk, y)])
+        assert torch.equal(fused[CC.sel(mk, y)], y[CC.sel(mk, y)])
     else:
         assert _means_err(fused, y, mk, n) <= _bar(n)
     if n == 2:      # without a mask: the fused tail's null-mask path against the unfused kernel's
@@ -285,7 +270,6 @@ def test_chains_share_a_workspace_and_masks_share_a_graph(tiny, data):
     lib = plan._lib
     before = ops.cluster_timeouts()
     K = len(use)
-    tmap = (C.c_int64 * K)(*[int(v) for v in use])
     nbytes = lib.ddk_sampler_restore_multistep_workspace_bytes(plan.handle, 2, 16, 16, K - 1, 1)
     lat = 2 * 16 * 16 * 3 * 4
     assert nbytes == lib.ddk_sampler_workspace_bytes(plan.handle, 2, 16, 16, K - 1) + 2 * lat + 2 * 16 * 16 * 4
@@ -295,70 +279,44 @@ def test_chains_share_a_workspace_and_masks_share_a_graph(tiny, data):
     yd = {n: ops.nchw_to_nhwc(ys[n].to(DEV)) for n in (1, 2)}
     md = {"s1": mks[1].to(DEV), "s1b": (1 - mks[1]).to(DEV), "s2": mks[2].to(DEV), "s2full": None}
     jobs = {"s1": 1, "s1b": 1, "s2": 2, "s2full": 2, "2m": None, "ddim_m1": None, "anc": None}
-    x = torch.empty_like(x0)
-    side = torch.cuda.Stream()
 
-    def args(tab, ws, graph=1):
-        return L.SamplerArgs(plan.handle, L.ptr(plan.packed), L.ptr(x), None, L.ptr(tab["c_recip"]), L.ptr(tab["c_recipm1"]), L.ptr(tab["c1"]),
-                             L.ptr(tab["c2"]), L.ptr(tab.get("sigma")), 2, 16, 16, K - 1, 0, 7, 0, graph, L.ptr(ws), nbytes)
+    def launch(what, a, tmap, s):
+        if what == "anc":
+            return lib.ddk_sampler_run_spaced(a, tmap, s)
+        if what == "ddim_m1":
+            return lib.ddk_sampler_run_restore_masked(a, tmap, L.ptr(yd[1]), L.ptr(md["s1"]), 1, s)
+        if what == "2m":
+            return lib.ddk_sampler_run_multistep(a, tmap, L.ptr(sol["c3"]), s)
+        n = jobs[what]
+        return lib.ddk_sampler_run_restore_multistep(a, tmap, L.ptr(sol["c3"]), L.ptr(yd[n]), L.ptr(md[what]), n, s)
 
-    def run(ws, what):
-        x.copy_(x0)
-        torch.cuda.synchronize()
-        s = side.cuda_stream
-        with torch.cuda.stream(side):
-            if what == "anc":
-                rc = lib.ddk_sampler_run_spaced(C.byref(args(anc, ws)), tmap, s)
-            elif what == "ddim_m1":
-                rc = lib.ddk_sampler_run_restore_masked(C.byref(args(ddim, ws)), tmap, L.ptr(yd[1]), L.ptr(md["s1"]), 1, s)
-            elif what == "2m":
-                rc = lib.ddk_sampler_run_multistep(C.byref(args(sol, ws)), tmap, L.ptr(sol["c3"]), s)
-            else:
-                n = jobs[what]
-                rc = lib.ddk_sampler_run_restore_multistep(C.byref(args(sol, ws)), tmap, L.ptr(sol["c3"]), L.ptr(yd[n]), L.ptr(md[what]), n, s)
-        assert rc == 0, L.last_error()
-        side.synchronize()
-        return x.clone()
-
-    fresh = lambda: torch.empty(nbytes // 4 + 4, device=DEV)
-
-    def alone(what):
-        ws = fresh()
-        try:
-            return run(ws, what)
-        finally:      # the plan's cached graphs and shift table point into ws: drop them before the memory goes back
-            assert lib.ddk_sampler_release_workspace(plan.handle, L.ptr(ws)) == 0
-
-    single = {what: alone(what) for what in jobs}
+    sh = CC.SharedWorkspace(plan, lambda what: {"anc": anc, "ddim_m1": ddim}.get(what, sol), use, x0, nbytes, 7, launch)
+    x, tmap = sh.x, sh.tmap
+    single = {what: sh.alone(what) for what in jobs}
     names = list(jobs)
     for i, a in enumerate(names):
         for b in names[i + 1:]:
             assert not torch.equal(single[a], single[b]), (a, b)
     for order in (("s1", "2m", "ddim_m1", "anc", "s1b", "s2", "s2full", "s1"), ("anc", "s2full", "s2", "ddim_m1", "s1b", "2m", "s1", "anc")):
-        ws = fresh()
-        for what in order:
-            got = run(ws, what)
-            assert torch.equal(got, single[what]), (order, what, float((got - single[what]).abs().max()))
-        assert lib.ddk_sampler_release_workspace(plan.handle, L.ptr(ws)) == 0
+        sh.interleaved(order, single)
     for what in ("s1", "s1b"):      # the measured pixels of the two masks' results are their own
         out = ops.nhwc_to_nchw(single[what]).cpu()
-        s = _sel(md[what].cpu(), ys[1])
+        s = CC.sel(md[what].cpu(), ys[1])
         assert torch.equal(out[s], ys[1][s])
     # eager on the legacy stream: the same bits; n = 1 without a mask, a bad n and injected noise are rejected
-    ws = fresh()
-    a = args(sol, ws, graph=0)
-    x.copy_(x0)
-    assert lib.ddk_sampler_run_restore_multistep(C.byref(a), tmap, L.ptr(sol["c3"]), L.ptr(yd[2]), None, 2, L.stream()) == 0, L.last_error()
-    torch.cuda.synchronize()
-    assert torch.equal(x, single["s2full"])
-    assert lib.ddk_sampler_run_restore_multistep(C.byref(a), tmap, L.ptr(sol["c3"]), L.ptr(yd[1]), None, 1, L.stream()) == -1 and "mask" in L.last_error()
-    assert lib.ddk_sampler_run_restore_multistep(C.byref(a), tmap, L.ptr(sol["c3"]), L.ptr(yd[1]), L.ptr(md["s1"]), 3, L.stream()) == -1
-    assert lib.ddk_sampler_run_restore_multistep(C.byref(a), tmap, None, L.ptr(yd[1]), L.ptr(md["s1"]), 1, L.stream()) == -1
-    noise = torch.zeros((K, *x.shape), device=DEV)
-    a.noise = L.ptr(noise)
-    assert lib.ddk_sampler_run_restore_multistep(C.byref(a), tmap, L.ptr(sol["c3"]), L.ptr(yd[1]), L.ptr(md["s1"]), 1, L.stream()) == -1 and \
-        "noise" in L.last_error()
-    assert lib.ddk_sampler_release_workspace(plan.handle, L.ptr(ws)) == 0
+    with CC.workspace(plan, nbytes) as ws:
+        a = CC.sampler_args(plan, x, sol, K - 1, ws, nbytes, seed=7)
+        x.copy_(x0)
+        assert lib.ddk_sampler_run_restore_multistep(a, tmap, L.ptr(sol["c3"]), L.ptr(yd[2]), None, 2, L.stream()) == 0, L.last_error()
+        torch.cuda.synchronize()
+        assert torch.equal(x, single["s2full"])
+        assert lib.ddk_sampler_run_restore_multistep(a, tmap, L.ptr(sol["c3"]), L.ptr(yd[1]), None, 1, L.stream()) == -1 and "mask" in L.last_error()
+        assert lib.ddk_sampler_run_restore_multistep(a, tmap, L.ptr(sol["c3"]), L.ptr(yd[1]), L.ptr(md["s1"]), 3, L.stream()) == -1
+        assert lib.ddk_sampler_run_restore_multistep(a, tmap, None, L.ptr(yd[1]), L.ptr(md["s1"]), 1, L.stream()) == -1
+        noise = torch.zeros((K, *x.shape), device=DEV)
+        a.noise = L.ptr(noise)
+        assert lib.ddk_sampler_run_restore_multistep(a, tmap, L.ptr(sol["c3"]), L.ptr(yd[1]), L.ptr(md["s1"]), 1, L.stream()) == -1 and \
+            "noise" in L.last_error()
     assert ops.cluster_timeouts() == before
 
 
@@ -385,68 +343,49 @@ def test_dddpm_restore_solver_holds_the_latent_constraint_and_pastes():
     assert torch.equal(raw.cpu()[~sel], x_out.cpu()[~sel])
     print(f"dDDPM inpainting on 2M: pixel-space gap on the measured pixels before the paste {float((raw.cpu() - img)[sel].abs().max()):.3g}")
     # scale 8: a 4 x 4 low-resolution image with holes, latent block 2
-    y = _y((2, 3, 32, 32), 8, "restore_solver.dd.y")
-    mk8 = _mask("checker", 2, 4, 4)
+    y = CC.pooled_y((2, 3, 32, 32), 8, "restore_solver.dd.y")
+    mk8 = CC.mask("checker", 2, 4, 4)
     x8, z8 = m.restore_solver(y.to(DEV), mk8, 8, respacing=SPEC, x_T=z_T)
     with torch.no_grad():
-        zr = m.rescaled_downsample(RR.replicate(torch.where(_sel(mk8, y), y, torch.zeros_like(y)), 8).to(DEV))
+        zr = m.rescaled_downsample(RR.replicate(torch.where(CC.sel(mk8, y), y, torch.zeros_like(y)), 8).to(DEV))
         y_lat = torch.nn.functional.avg_pool2d(zr, 2).cpu()
         assert torch.equal(x8, m.rescaled_upsample(z8))
     err = _means_err(z8.cpu(), y_lat, mk8, 2)
-    gap = float((RR.pool(x8.cpu().double(), 8) - y.double())[_sel(mk8, y)].abs().max())
+    gap = float((RR.pool(x8.cpu().double(), 8) - y.double())[CC.sel(mk8, y)].abs().max())
     print(f"dDDPM x8 with holes on 2M (latent n = 2): measured latent block means off by {err:.3g} (bar {_bar(2):.3g}); pixel-space gap {gap:.3g}")
     assert err <= _bar(2), err
 
 
 # ---------------------------------------------------------------- the command line (a fresh child process each) and the scorer
-def _cli_setup(tmp_path):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cfg = ddpm_cfg(32, 3, 16, T=100)
-    cfg.update(model="ddpm", dataset="celeba")
-    (tmp_path / "cfg.json").write_text(json.dumps(cfg))
-    imgs = (np.random.default_rng(0).random((3, 16, 16, 3)) * 255).astype(np.uint8)
-    np.save(tmp_path / "imgs.npy", imgs)
-    env = dict(os.environ, PYTHONPATH=os.path.join(root, "downsampled-diffusion_amd"))
-    return root, env, imgs
-
-
 def test_inpaint_cli_with_the_solver(tmp_path):
-    root, env, imgs = _cli_setup(tmp_path)
-    script = os.path.join(root, "downsampled-diffusion_amd", "inpaint_model_samples.py")
-    base = [sys.executable, script, "--synthetic", str(tmp_path / "cfg.json"), "--saved_model", "clitest", "--images",
-            str(tmp_path / "imgs.npy"), "--mask", "left", "--timestep_respacing", "logsnr8", "--batch_size", "2", "--seed", "3", "--out_dir",
-            str(tmp_path)]
-    r = subprocess.run(base + ["--method", "ddnm", "--dpm_solver"], capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
+    cfg_path, images_path, imgs, env = CC.cli_files(tmp_path, CC.cli_cfg(), 3, 16)
+    base = ["inpaint_model_samples.py", "--synthetic", cfg_path, "--saved_model", "clitest", "--images", images_path, "--mask", "left",
+            "--timestep_respacing", "logsnr8", "--batch_size", "2", "--seed", "3", "--out_dir", tmp_path]
+    CC.run_script(*base, "--method", "ddnm", "--dpm_solver", env=env)
     out = np.load(tmp_path / "clitest_inpaint_left_logsnr8_ddnm_dpmpp2m.npy")
     assert (tmp_path / "clitest_inpaint_left_logsnr8_ddnm_dpmpp2m_masked.npy").exists()
     assert out.shape == (3, 16, 16, 3) and out.dtype == np.float32 and np.isfinite(out).all() and out.min() >= 0 and out.max() <= 255
     assert np.abs(out[:, :, 8:] - imgs[:, :, 8:]).max() < 1e-3             # the known half comes back
     assert np.abs(out[:, :, :8] - imgs[:, :, :8]).max() > 1
     for extra in (["--method", "ddnm", "--dpm_solver", "--use_ddim"], ["--method", "ddnm", "--dpm_solver", "--eta", "0.5"], ["--dpm_solver"]):
-        r = subprocess.run(base + extra, capture_output=True, text=True, env=env, timeout=300)      # argparse errors: no device work
+        r = CC.run_script(*base, *extra, env=env, check=False)      # argparse errors: no device work
         assert r.returncode != 0 and "dpm_solver" in r.stderr
 
 
 def test_upscale_and_evaluate_clis_with_the_solver(tmp_path):
-    root, env, imgs = _cli_setup(tmp_path)
-    script = os.path.join(root, "downsampled-diffusion_amd", "upscale_model_samples.py")
-    base = [sys.executable, script, "--synthetic", str(tmp_path / "cfg.json"), "--saved_model", "clitest", "--images", str(tmp_path / "imgs.npy"),
-            "--scale", "2", "--timestep_respacing", "logsnr8", "--batch_size", "2", "--seed", "3", "--out_dir", str(tmp_path), "--dpm_solver"]
-    r = subprocess.run(base, capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
+    cfg_path, images_path, _, env = CC.cli_files(tmp_path, CC.cli_cfg(), 3, 16)
+    base = ["upscale_model_samples.py", "--synthetic", cfg_path, "--saved_model", "clitest", "--images", images_path, "--scale", "2",
+            "--timestep_respacing", "logsnr8", "--batch_size", "2", "--seed", "3", "--out_dir", tmp_path, "--dpm_solver"]
+    CC.run_script(*base, env=env)
     out = np.load(tmp_path / "clitest_sr2_logsnr8_dpmpp2m.npy")
     assert (tmp_path / "clitest_sr2_logsnr8_dpmpp2m_lowres.npy").exists()
     assert out.shape == (3, 16, 16, 3) and np.isfinite(out).all()
-    r = subprocess.run(base + ["--use_ddim"], capture_output=True, text=True, env=env, timeout=300)
+    r = CC.run_script(*base, "--use_ddim", env=env, check=False)
     assert r.returncode != 0 and "dpm_solver" in r.stderr
     np.save(tmp_path / "ones.npy", np.ones((16, 16), dtype=np.float32))
-    script = os.path.join(root, "downsampled-diffusion_amd", "evaluate_restoration.py")
-    r = subprocess.run([sys.executable, script, "--synthetic", str(tmp_path / "cfg.json"), "--images", str(tmp_path / "imgs.npy"), "--task",
-                        "inpaint", "--method", "ddnm", "--dpm_solver", "--mask", str(tmp_path / "ones.npy"), "--timestep_respacing", "logsnr8",
-                        "--batch_size", "2", "--seed", "9", "--json", str(tmp_path / "out.json")],
-                       capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
+    CC.run_script("evaluate_restoration.py", "--synthetic", cfg_path, "--images", images_path, "--task", "inpaint", "--method", "ddnm",
+                  "--dpm_solver", "--mask", tmp_path / "ones.npy", "--timestep_respacing", "logsnr8", "--batch_size", "2", "--seed", "9",
+                  "--json", tmp_path / "out.json", env=env)
     res = json.loads((tmp_path / "out.json").read_text())
     st, me = res["settings"], res["metrics"]
     assert (st["task"], st["method"], st["unet_forwards"], st["respacing"], st["dpm_solver"]) == ("inpaint", "ddnm_dpmpp2m", 8, "logsnr8", True)

@@ -5,15 +5,11 @@ The tiny DDPM (unet_chan 32, 3x16x16, linear schedule, T = 1000) has no Winograd
 p_update_kernel; the cfg4 window at B = 32 ends in final_tail_kernel.  Bars as for the plain chains: 1e-4 abs against the
 restatement with the same argmax, 1e-6 between full respacing and the plain chain, 1e-5 between the Python loop and the
 native sampler.  Each comparison with injected draws has a negative control."""
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 import torch
 
+import chain_cases as CC
 import spaced_ref as SR
 from helpers import dddpm_cfg, ddpm_cfg, det_load, golden_keys, unet_cfg
 from oracle import diffusion_ref as D
@@ -30,10 +26,7 @@ CFG = ddpm_cfg(32, 3, 16)
 
 @pytest.fixture(scope="module")
 def tiny():
-    from models import DDPM, Unet
-    m = det_load(DDPM(CFG, Unet(CFG), DEV, 3)).to(DEV).eval()
-    sd = {k: v.detach().cpu() for k, v in m.state_dict().items()}
-    return m, (lambda x, t: U.unet_forward(sd, CFG, x, t, pre="latent_model."))
+    return CC.tiny_ddpm(CFG)
 
 
 @pytest.fixture(scope="module")
@@ -49,15 +42,11 @@ def _ref(spec, x_T, noise, ddim=False, eta=0.0, k_end=0):
     return sd, (lambda eps: sd.run(eps, x_T, lambda j: noise[j], k_end=k_end, ddim=ddim, eta=eta))
 
 
-def _argmax(x):
-    return x.reshape(x.shape[0], -1).argmax(dim=1)
-
-
 def _check(got, want, tol=TOL):
     err = float((got.cpu() - want).abs().max())
     assert torch.isfinite(got).all()
     assert err < tol, err
-    assert torch.equal(_argmax(got.cpu()), _argmax(want))
+    assert torch.equal(CC.argmax(got.cpu()), CC.argmax(want))
     return err
 
 
@@ -129,11 +118,8 @@ def test_python_loop_equals_native(tiny, draws, spec, ddim, eta):
     x_T, noise = draws
     K = len(SR.space_timesteps(1000, spec))
     native = m.p_sample_loop(SHAPE, x_T=x_T, noise=noise[:K], respacing=spec, ddim=ddim, eta=eta)
-    m.native_sampler = False
-    try:
+    with CC.toggled(m, "native_sampler", False):
         loop = m.p_sample_loop(SHAPE, x_T=x_T, noise=noise[:K], respacing=spec, ddim=ddim, eta=eta)
-    finally:
-        m.native_sampler = True
     err = float((loop - native).abs().max())
     print(f"Python loop vs native, {spec} ddim={ddim}: {err:.3g}")
     assert err < 1e-5
@@ -146,11 +132,8 @@ def test_spaced_philox_seed_and_stream(tiny, draws):
     a = m.p_sample_loop(SHAPE, seed=77, **kw)
     b = m.p_sample_loop(SHAPE, seed=77, **kw)
     assert torch.equal(a, b)
-    m.rng_stream_id = 1
-    try:
+    with CC.toggled(m, "rng_stream_id", 1):
         c = m.p_sample_loop(SHAPE, seed=77, **kw)
-    finally:
-        m.rng_stream_id = 0
     assert float((a - c).abs().max()) > 1e-3
 
 
@@ -273,21 +256,13 @@ def test_dddpm_sample_ddim50():
 
 
 def test_generate_model_samples_respacing_cli(tmp_path):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cfg = dddpm_cfg(32, 32, 2)
-    cfg.update(model="dddpm", dataset="celeba", T=100)
-    cfg_path = tmp_path / "cfg.json"
-    cfg_path.write_text(json.dumps(cfg))
-    env = dict(os.environ, PYTHONPATH=os.path.join(root, "downsampled-diffusion_amd"))
-    script = os.path.join(root, "downsampled-diffusion_amd", "generate_model_samples.py")
-    base = [sys.executable, script, "--synthetic", str(cfg_path), "--saved_model", "clitest", "--fid_samples", "4",
-            "--batch_size", "2", "--out_dir", str(tmp_path)]
-    r = subprocess.run(base + ["--timestep_respacing", "ddim50", "--use_ddim"], capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
+    cfg_path, _, _, env = CC.cli_files(tmp_path, CC.cli_cfg("dddpm"), 0, 32)
+    base = ["generate_model_samples.py", "--synthetic", cfg_path, "--saved_model", "clitest", "--fid_samples", "4", "--batch_size", "2",
+            "--out_dir", tmp_path]
+    CC.run_script(*base, "--timestep_respacing", "ddim50", "--use_ddim", env=env)
     imgs = np.load(tmp_path / "clitest_ddim50_ddim_eta0.npy")
     assert imgs.shape == (2, 2, 32, 32, 3) and imgs.min() == 0.0 and abs(imgs.max() - 255.0) < 1e-3
     assert np.load(tmp_path / "clitest_ddim50_ddim_eta0_latent.npy").shape == (2, 2, 8, 8, 8)
     assert not (tmp_path / "clitest.npy").exists()
-    r = subprocess.run(base + ["--early_stop", "95"], capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0, r.stderr[-2000:]
+    CC.run_script(*base, "--early_stop", "95", env=env)
     assert np.load(tmp_path / "clitest.npy").shape == (2, 2, 32, 32, 3)
