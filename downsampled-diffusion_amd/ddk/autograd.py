@@ -8,6 +8,7 @@ trainers/trainer_ddpm.py:124-128 calls ``objective.backward()``.
 import torch
 
 from . import ops
+from .forms import gn_tuned, ln_tuned          # which widths the tuned normalisation kernels take: ddk/forms.py decides
 
 
 def _c(t):
@@ -322,23 +323,10 @@ class ConvGNMishFn(torch.autograd.Function):
                 None)
 
 
-def gn_tuned(c, groups=8):
-    """the tuned training GroupNorm (gn_train_launch: a float4 unit count per pixel row that is a power of two <= 8) takes 4, 8, 16 or
-    32 channels per group -- 32, 64, 128, 256 channels at 8 groups.  Every other width that is a multiple of 32 (96, 160, 192, 224,
-    320, 384, 512, ...) runs the generic training kernels with pitch == C (GNMishGenericFn: C / groups <= 256)."""
-    return c % groups == 0 and c // groups in (4, 8, 16, 32)
-
-
-def ln_tuned(c):
-    """the widths ddk_chan_layernorm_bwd has an instantiation for; the others run chan_layernorm_generic_bwd with pitch == C (C <= 512)"""
-    return c in (32, 64, 128, 256, 512)
-
-
 def conv_groupnorm_mish(x, weight, bias, gamma, beta, x2=None, temb=None, addend=None, drop_p=0.0, seed=0, layer=0, groups=8, eps=1e-5,
                         give=None, take=None, dy_link=None, dx_link=None, give2=None):
+    """one Block for a caller that has not chosen (trainers/autograd_unet.py has, per module): by gn_tuned of the weight's width"""
     if not gn_tuned(weight.shape[0], groups):
-        # the generic GroupNorm neither hands gradients over nor reads slabs: the caller decides per module (trainers/autograd_unet.py),
-        # so that both ends of a hand-off are on the same path
         if any(h is not None for h in (give, take, dy_link, dx_link, give2)):
             raise RuntimeError(f"conv_groupnorm_mish: {weight.shape[0]} channels in {groups} groups run the generic GroupNorm, which takes "
                                "no gradient hand-off")
@@ -430,6 +418,12 @@ class GNMishGenericFn(torch.autograd.Function):
         return dx, sums[0], sums[1], (dtemb if has_temb else None), (dy if has_add else None), None, None, None, None, None
 
 
+def _chan_layernorm_generic_bwd(x, g, dy, eps, addend=None):
+    """the generic LayerNorm backward (any C <= 512 at any pitch >= C); it adds the Residual's gradient in the same launch"""
+    dx, dg, db = ops.chan_layernorm_generic_bwd(x, g.detach(), _c(dy), eps, addend=addend)
+    return dx, dg.reshape(g.shape), db.reshape(g.shape)
+
+
 class ChanLayerNormGenericFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, g, b, eps):
@@ -440,8 +434,7 @@ class ChanLayerNormGenericFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, g = ctx.saved_tensors
-        dx, dg, db = ops.chan_layernorm_generic_bwd(x, g.detach(), _c(dy), ctx.eps)
-        return dx, dg.reshape(g.shape), db.reshape(g.shape), None
+        return (*_chan_layernorm_generic_bwd(x, g, dy, ctx.eps), None)
 
 
 class ChanLayerNormFn(torch.autograd.Function):
@@ -455,12 +448,10 @@ class ChanLayerNormFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, g, b = ctx.saved_tensors
-        sg, sb = _grad_slot(g), _grad_slot(b)
         extra = ctx.take.take()[0] if ctx.take is not None else None
-        if not ln_tuned(x.shape[-1]):
-            # 96, 160, 192, ...: the generic backward kernel with pitch == C (it adds the Residual's gradient in the same launch too)
-            dx, dg, db = ops.chan_layernorm_generic_bwd(x, g.detach(), _c(dy), ctx.eps, addend=extra)
-            return dx, dg.reshape(g.shape), db.reshape(g.shape), None, None
+        if not ln_tuned(x.shape[-1]):         # 96, 160, 192, ...: pitch == C
+            return (*_chan_layernorm_generic_bwd(x, g, dy, ctx.eps, addend=extra), None, None)
+        sg, sb = _grad_slot(g), _grad_slot(b)
         dx, dg, db = ops.chan_layernorm_bwd(x, g.detach(), _c(dy), ctx.eps, acc=(sg, sb) if sg is not None and sb is not None else None,
                                             addend=extra)
         if dg is None:

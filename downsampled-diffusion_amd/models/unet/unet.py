@@ -105,11 +105,8 @@ class Unet(nn.Module):
     def forward_nhwc(self, x, time):
         """x [B,H,W,C_in] fp32 on the device, time [B] integer -> eps_hat [B,H,W,C_in]."""
         if self._wants_grad(x):
-            if self.dim % 32 != 0:
-                # other multiples of 8 (blocks.py:75): the same HIP kernels on a zero-padded channel pitch, generic normalisations
-                from trainers.autograd_unet import unet_forward_autograd_generic
-                return unet_forward_autograd_generic(self, x, time)
-            from trainers.autograd_unet import unet_forward_autograd   # training path: HIP forward + backward kernels
+            # training path: HIP forward + backward kernels, each module in its tuned or its generic form (ddk/forms.py)
+            from trainers.autograd_unet import unet_forward_autograd
             return unet_forward_autograd(self, x, time)
         if self.training and self.downs[0][0].dropout.p > 0:
             raise DDKError("Unet in train() mode with dropout > 0 outside autograd: call model.eval() for inference")

@@ -4,12 +4,18 @@ reference trainers/trainer_ddpm.py:124-128 works unchanged on the drop-in module
 
 Follows reference models/unet/unet.py:74-104 (train mode: Dropout(p) between the two Blocks of the down-path
 ResnetBlocks, unet.py:46-47 vs :54-63) and models/downsampled/convblocks.py:112-159.
+
+One walk of the UNet for every unet_chan % 8 == 0 (blocks.py:75).  Each module runs its tuned or its generic form, as
+ddk.forms.training_forms says (the forms are described there); the walk carries the REAL channel count of the current tensor next
+to it, because a tensor on the padded pitch (the network's input, every tensor of a model whose unet_chan is no multiple of 32)
+does not show it.
 """
 import torch
 from torch import nn
 
 from ddk import autograd as AG
 from ddk import ops
+from ddk.forms import training_forms
 from ddk.plan import sinusoidal_freqs
 
 HEADS = 4
@@ -28,45 +34,58 @@ class _Seeds:
         return self.seed, self.layer
 
 
-def _block(blk, x, x2=None, temb=None, addend=None, drop_p=0.0, seeds=None, give=None, take=None, dy_link=None, dx_link=None, give2=None):
+def _in_real(c_in, c_in2):
+    return [c_in] if c_in2 is None else [c_in, c_in2]
+
+
+def _block(blk, x, c_in, tuned, x2=None, c_in2=None, temb=None, addend=None, drop_p=0.0, seeds=None, pad=True, **handoffs):
+    """blocks.py:74-84.  c_in, c_in2: the real channels of x and x2.  handoffs (give, take, dy_link, dx_link, give2): tuned form only."""
     conv, norm = blk.block[0], blk.block[1]
     seed, layer = seeds.next() if (seeds is not None and drop_p > 0) else (0, 0)
-    return AG.conv_groupnorm_mish(x, conv.weight, conv.bias, norm.weight, norm.bias, x2=x2, temb=temb, addend=addend, drop_p=drop_p,
-                                  seed=seed, layer=layer, groups=blk.groups, eps=norm.eps, give=give, take=take, dy_link=dy_link,
-                                  dx_link=dx_link, give2=give2)
+    if tuned or not pad:          # (not pad: the generic GroupNorm at pitch == C on the parameters as they are, which that entry chooses)
+        return AG.conv_groupnorm_mish(x, conv.weight, conv.bias, norm.weight, norm.bias, x2=x2, temb=temb, addend=addend, drop_p=drop_p,
+                                      seed=seed, layer=layer, groups=blk.groups, eps=norm.eps, **handoffs)
+    w = AG.pad_param(conv.weight, out_real=True, in_real=_in_real(c_in, c_in2))
+    raw = AG.conv(ops.CONV3X3_S1, x, w, AG.pad_param(conv.bias, out_real=True), x2=x2)
+    return AG.GNMishGenericFn.apply(raw, norm.weight, norm.bias, temb, addend, float(drop_p), int(seed), int(layer), blk.groups, norm.eps)
 
 
-def _resnet(rb, x, temb_slice, x2=None, seeds=None, give2=None):
+def _resnet(rb, x, c_in, temb_slice, tuned, x2=None, c_in2=None, seeds=None, give2=None):
     """blocks.py:105-115: h = drop(Block1(x) + shift); out = Block2(h) + res(x)"""
-    c_out = rb.block1.block[0].weight.shape[0]
-    if not AG.gn_tuned(c_out, rb.block1.groups):
-        # 96, 160, 192, 384, 512, ... channels: the tuned GroupNorm backward keeps 4, 8, 16 or 32 channels per group, so the WHOLE block --
-        # both ends of its hand-off and of its slab link -- runs the forms of the padded widths with pitch == C.  give2 is not used: the
-        # skip's gradient goes back to autograd, which adds it to the Downsample conv's; that conv's take() of a hand-off nobody gave
-        # to adds nothing (as for the first level's skip, which no up level consumes).
-        c_in2 = None if x2 is None else x2.shape[-1]
-        c_in = rb.block1.block[0].weight.shape[1] - (c_in2 or 0)       # the REAL channels of x (the network's input keeps a padded pitch)
-        return _gresnet(rb, x, c_in, temb_slice, x2=x2, c_in2=c_in2, seeds=seeds)[0]
     p = rb.dropout.p if rb.training else 0.0
+    c_out = rb.block1.block[0].weight.shape[0]
+    skip_conv = not isinstance(rb.res_conv, nn.Identity)
+    if not tuned:
+        # give2 is not used: the skip's gradient goes back to autograd, which adds it to the Downsample conv's; that conv's take() of a
+        # hand-off nobody gave to adds nothing (as for the first level's skip, which no up level consumes)
+        h = _block(rb.block1, x, c_in, False, x2=x2, c_in2=c_in2, temb=temb_slice, drop_p=p, seeds=seeds)
+        res = x
+        if skip_conv:
+            w = AG.pad_param(rb.res_conv.weight, out_real=True, in_real=_in_real(c_in, c_in2))
+            res = AG.conv(ops.CONV1X1, x, w, AG.pad_param(rb.res_conv.bias, out_real=True), x2=x2)
+        return _block(rb.block2, h, c_out, False, addend=res)
     # the gradient of the skip path reaches x (and x2) through Block1's input-gradient conv epilogue, not through an autograd add:
     # identity skip -> Block2 hands its addend gradient over; 1x1 skip -> the skip conv hands its input gradients over
     hand = AG.GradHandoff()
     # h has one consumer (Block2's conv): its gradient may travel from that conv's input-gradient launch to Block1's GroupNorm
     # backward as unreduced split-K slabs
     link = AG.SlabLink()
-    h = _block(rb.block1, x, x2=x2, temb=temb_slice, drop_p=p, seeds=seeds, take=hand, dy_link=link, give2=give2)
-    if isinstance(rb.res_conv, nn.Identity):
-        return _block(rb.block2, h, addend=x, give=hand, dx_link=link)
+    h = _block(rb.block1, x, c_in, True, x2=x2, temb=temb_slice, drop_p=p, seeds=seeds, take=hand, dy_link=link, give2=give2)
+    if not skip_conv:
+        return _block(rb.block2, h, c_out, True, addend=x, give=hand, dx_link=link)
     res = AG.conv(ops.CONV1X1, x, rb.res_conv.weight, rb.res_conv.bias, x2=x2, handoff=hand)
-    return _block(rb.block2, h, addend=res, dx_link=link)
+    return _block(rb.block2, h, c_out, True, addend=res, dx_link=link)
 
 
-def _attention(res_mod, x):
+def _attention(res_mod, x, c, tuned):
     """Residual(PreNorm(LinearAttention)): blocks.py:8-14,63-71,126-134"""
     pre = res_mod.fn
     att = pre.fn
-    if not AG.ln_tuned(x.shape[-1]):
-        return _gattention(res_mod, x, x.shape[-1])       # no tuned LayerNorm backward at this width: generic forms, pitch == C
+    if not tuned:
+        xn = AG.ChanLayerNormGenericFn.apply(x, pre.norm.g, pre.norm.b, pre.norm.eps)
+        qkv = AG.conv(ops.CONV1X1, xn, AG.pad_param(att.to_qkv.weight, in_real=[c]))
+        o = AG.LinAttnFn.apply(qkv, att.heads)
+        return AG.conv(ops.CONV1X1, o, AG.pad_param(att.to_out.weight, out_real=True), AG.pad_param(att.to_out.bias, out_real=True), resid=x)
     hand = AG.GradHandoff()        # the Residual's gradient reaches x inside the LayerNorm backward kernel, not through an autograd add
     xn = AG.ChanLayerNormFn.apply(x, pre.norm.g, pre.norm.b, pre.norm.eps, hand)
     qkv = AG.conv(ops.CONV1X1, xn, att.to_qkv.weight)
@@ -74,148 +93,72 @@ def _attention(res_mod, x):
     return AG.conv(ops.CONV1X1, o, att.to_out.weight, att.to_out.bias, resid=x, resid_handoff=hand)
 
 
-def _resnet_blocks(unet):
-    """All ResnetBlocks in forward order (the order of the time-shift table's column blocks)."""
-    blocks = []
-    for lvl in unet.downs:
-        blocks += [lvl[0], lvl[1]]
-    blocks += [unet.mid_block1, unet.mid_block2]
-    for lvl in unet.ups:
-        blocks += [lvl[0], lvl[1]]
-    return blocks
+def _resample(kind, mod, x, c, tuned, take=None):
+    """Downsample (3x3 stride 2) / Upsample (ConvTranspose2d 4x4 stride 2, weight (in, out, 4, 4): both channel axes padded)"""
+    w, b = mod.conv.weight, mod.conv.bias
+    if not tuned:
+        w, b = AG.pad_param(w, out_real=True, in_real=[c]), AG.pad_param(b, out_real=True)
+        if kind == ops.CONVT4X4_S2:
+            w = w.contiguous()
+    return AG.conv(kind, x, w, b, take=take)
+
+
+def _time_shifts(unet, time, rbs, dev):
+    """{ResnetBlock: its [B, C_out] time shift} -- REAL channels in either form: one column range of ONE product per block, in forward
+    order (blocks.py:22-29,92-95)"""
+    freqs = getattr(unet, "_freqs_dev", None)
+    if freqs is None or freqs.device != dev:
+        freqs = sinusoidal_freqs(unet.dim).to(dev)
+        unet._freqs_dev = freqs
+    mlp_args = []
+    for rb in rbs:
+        mlp_args += [rb.mlp[1].weight, rb.mlp[1].bias]
+    shifts = AG.TimeEmbedFn.apply(time.to(torch.int64).contiguous(), freqs, unet.time_mlp[1].weight, unet.time_mlp[1].bias,
+                                  unet.time_mlp[3].weight, unet.time_mlp[3].bias, *mlp_args)
+    return dict(zip(rbs, shifts))
 
 
 def unet_forward_autograd(unet, x, time):
     """x [B,H,W,C_in] (NHWC, unpadded), time [B] -> eps_hat [B,H,W,C_in], differentiable w.r.t. x and every parameter."""
-    dev = x.device
     seeds = _Seeds(unet.training)
-    rbs = _resnet_blocks(unet)
-    freqs = getattr(unet, "_freqs_dev", None)
-    if freqs is None or freqs.device != dev:
-        freqs = sinusoidal_freqs(unet.dim).to(dev)
-        unet._freqs_dev = freqs
-    mlp_args = []
-    for rb in rbs:
-        mlp_args += [rb.mlp[1].weight, rb.mlp[1].bias]
-    shifts = AG.TimeEmbedFn.apply(time.to(torch.int64).contiguous(), freqs, unet.time_mlp[1].weight, unet.time_mlp[1].bias,
-                                  unet.time_mlp[3].weight, unet.time_mlp[3].bias, *mlp_args)
-    shift_of = {id(rb): s for rb, s in zip(rbs, shifts)}      # one [B, C_out] column range per ResnetBlock
-
-    def shift(rb):
-        return shift_of[id(rb)]
-
-    c_in = x.shape[-1]
-    if c_in % 32:
-        h = AG.NhwcToNchwFn.apply(x, c_in)                   # pad channels through the layout kernels (differentiable)
-        h = AG.NchwToNhwcFn.apply(h, ops.pad32(c_in))
-    else:
-        h = x
-    skips = []
-    for lvl in unet.downs:
-        rb1, rb2, attn, down = lvl
-        h = _resnet(rb1, h, shift(rb1), seeds=seeds)
-        h = _resnet(rb2, h, shift(rb2), seeds=seeds)
-        h = _attention(attn, h)
-        # the skip tensor has two consumers: the Downsample conv here and the up path's first Block; the latter's gradient is added by the
-        # former's input-gradient launch (the last level has no Downsample: autograd adds there)
-        carry = None if isinstance(down, nn.Identity) else AG.GradHandoff()
-        skips.append((h, carry))
-        if not isinstance(down, nn.Identity):
-            h = AG.conv(ops.CONV3X3_S2, h, down.conv.weight, down.conv.bias, take=carry)
-    h = _resnet(unet.mid_block1, h, shift(unet.mid_block1), seeds=seeds)
-    h = _attention(unet.mid_attn, h)
-    h = _resnet(unet.mid_block2, h, shift(unet.mid_block2), seeds=seeds)
-    for lvl in unet.ups:
-        rb1, rb2, attn, up = lvl
-        skip, carry = skips.pop()
-        h = _resnet(rb1, h, shift(rb1), x2=skip, seeds=seeds, give2=carry)
-        h = _resnet(rb2, h, shift(rb2), seeds=seeds)
-        h = _attention(attn, h)
-        h = AG.conv(ops.CONVT4X4_S2, h, up.conv.weight, up.conv.bias)
-    h = _block(unet.final_conv[0], h)
-    last = unet.final_conv[1]
-    return AG.SmallNConvFn.apply(h, last.weight, last.bias)
-
-
-# ---------------------------------------------------------------- widths that are not multiples of 32 (blocks.py:75: any C % 8 == 0)
-# Every tensor keeps a pitch of pad32(C) channels with zero padding; the conv family runs unchanged on zero-padded copies of the
-# parameters (AG.pad_param: the padding rows / columns get no gradient back), GroupNorm and the channel LayerNorm on kernels that
-# see the real channel count.  The tuned path's hand-offs (gradients riding on conv epilogues, split-K slabs summed by their
-# consumer) are not used here: autograd adds where two gradients meet.  Correct and complete, untuned.
-def _gblock(blk, x, c_in, x2=None, c_in2=None, temb=None, addend=None, drop_p=0.0, seeds=None):
-    conv, norm = blk.block[0], blk.block[1]
-    seed, layer = seeds.next() if (seeds is not None and drop_p > 0) else (0, 0)
-    w = AG.pad_param(conv.weight, out_real=True, in_real=[c_in] if c_in2 is None else [c_in, c_in2])
-    raw = AG.conv(ops.CONV3X3_S1, x, w, AG.pad_param(conv.bias, out_real=True), x2=x2)
-    return AG.GNMishGenericFn.apply(raw, norm.weight, norm.bias, temb, addend, float(drop_p), int(seed), int(layer), blk.groups, norm.eps)
-
-
-def _gresnet(rb, x, c_in, temb_slice, x2=None, c_in2=None, seeds=None):
-    p = rb.dropout.p if rb.training else 0.0
-    h = _gblock(rb.block1, x, c_in, x2=x2, c_in2=c_in2, temb=temb_slice, drop_p=p, seeds=seeds)
-    c_out = rb.block1.block[0].weight.shape[0]
-    if isinstance(rb.res_conv, nn.Identity):
-        res = x
-    else:
-        w = AG.pad_param(rb.res_conv.weight, out_real=True, in_real=[c_in] if c_in2 is None else [c_in, c_in2])
-        res = AG.conv(ops.CONV1X1, x, w, AG.pad_param(rb.res_conv.bias, out_real=True), x2=x2)
-    return _gblock(rb.block2, h, c_out, addend=res), c_out
-
-
-def _gattention(res_mod, x, c):
-    pre = res_mod.fn
-    att = pre.fn
-    xn = AG.ChanLayerNormGenericFn.apply(x, pre.norm.g, pre.norm.b, pre.norm.eps)
-    qkv = AG.conv(ops.CONV1X1, xn, AG.pad_param(att.to_qkv.weight, in_real=[c]))
-    o = AG.LinAttnFn.apply(qkv, att.heads)
-    return AG.conv(ops.CONV1X1, o, AG.pad_param(att.to_out.weight, out_real=True), AG.pad_param(att.to_out.bias, out_real=True), resid=x)
-
-
-def unet_forward_autograd_generic(unet, x, time):
-    """unet_forward_autograd for unet_chan % 8 == 0 that is not a multiple of 32 (24, 40, 72, ...): same network, padded pitch."""
-    dev = x.device
-    seeds = _Seeds(unet.training)
-    rbs = _resnet_blocks(unet)
-    freqs = getattr(unet, "_freqs_dev", None)
-    if freqs is None or freqs.device != dev:
-        freqs = sinusoidal_freqs(unet.dim).to(dev)
-        unet._freqs_dev = freqs
-    mlp_args = []
-    for rb in rbs:
-        mlp_args += [rb.mlp[1].weight, rb.mlp[1].bias]
-    shifts = AG.TimeEmbedFn.apply(time.to(torch.int64).contiguous(), freqs, unet.time_mlp[1].weight, unet.time_mlp[1].bias,
-                                  unet.time_mlp[3].weight, unet.time_mlp[3].bias, *mlp_args)
-    shift_of = {id(rb): sft for rb, sft in zip(rbs, shifts)}      # [B, C_out] REAL channels per block (the GroupNorm kernel indexes them so)
+    forms = training_forms(unet)
+    tuned = {f.module: f.tuned for f in forms}
+    shift = _time_shifts(unet, time, [f.module for f in forms if f.kind == "resnet"], x.device)
     c = x.shape[-1]
     if c % 32:
-        h = AG.NhwcToNchwFn.apply(x, c)
+        h = AG.NhwcToNchwFn.apply(x, c)                      # pad channels through the layout kernels (differentiable)
         h = AG.NchwToNhwcFn.apply(h, ops.pad32(c))
     else:
         h = x
+
+    def resnet(rb, h, c, x2=None, c2=None, give2=None):
+        out = _resnet(rb, h, c, shift[rb], tuned[rb], x2=x2, c_in2=c2, seeds=seeds, give2=give2)
+        return out, rb.block1.block[0].weight.shape[0]
+
     skips = []
-    for lvl in unet.downs:
-        rb1, rb2, attn, down = lvl
-        h, c = _gresnet(rb1, h, c, shift_of[id(rb1)], seeds=seeds)
-        h, c = _gresnet(rb2, h, c, shift_of[id(rb2)], seeds=seeds)
-        h = _gattention(attn, h, c)
-        skips.append((h, c))
-        if not isinstance(down, nn.Identity):
-            h = AG.conv(ops.CONV3X3_S2, h, AG.pad_param(down.conv.weight, out_real=True, in_real=[c]), AG.pad_param(down.conv.bias, out_real=True))
-    h, c = _gresnet(unet.mid_block1, h, c, shift_of[id(unet.mid_block1)], seeds=seeds)
-    h = _gattention(unet.mid_attn, h, c)
-    h, c = _gresnet(unet.mid_block2, h, c, shift_of[id(unet.mid_block2)], seeds=seeds)
-    for lvl in unet.ups:
-        rb1, rb2, attn, up = lvl
-        skip, cs = skips.pop()
-        h, c = _gresnet(rb1, h, c, shift_of[id(rb1)], x2=skip, c_in2=cs, seeds=seeds)
-        h, c = _gresnet(rb2, h, c, shift_of[id(rb2)], seeds=seeds)
-        h = _gattention(attn, h, c)
-        # ConvTranspose2d weight is (in, out, 4, 4): both channel axes padded
-        h = AG.conv(ops.CONVT4X4_S2, h, AG.pad_param(up.conv.weight, out_real=True, in_real=[c]).contiguous(),
-                    AG.pad_param(up.conv.bias, out_real=True))
-    h = _gblock(unet.final_conv[0], h, c)
-    last = unet.final_conv[1]
-    return AG.SmallNConvFn.apply(h, AG.pad_param(last.weight, in_real=[c]), last.bias)
+    for rb1, rb2, attn, down in unet.downs:
+        h, c = resnet(rb1, h, c)
+        h, c = resnet(rb2, h, c)
+        h = _attention(attn, h, c, tuned[attn])
+        # the skip tensor has two consumers: the Downsample conv here and the up path's first Block; in the tuned form the latter's
+        # gradient is added by the former's input-gradient launch (the last level has no Downsample: autograd adds there)
+        carry = AG.GradHandoff() if tuned.get(down) else None
+        skips.append((h, c, carry))
+        if down in tuned:
+            h = _resample(ops.CONV3X3_S2, down, h, c, tuned[down], take=carry)
+    h, c = resnet(unet.mid_block1, h, c)
+    h = _attention(unet.mid_attn, h, c, tuned[unet.mid_attn])
+    h, c = resnet(unet.mid_block2, h, c)
+    for rb1, rb2, attn, up in unet.ups:
+        skip, c2, carry = skips.pop()
+        h, c = resnet(rb1, h, c, x2=skip, c2=c2, give2=carry)
+        h, c = resnet(rb2, h, c)
+        h = _attention(attn, h, c, tuned[attn])
+        h = _resample(ops.CONVT4X4_S2, up, h, c, tuned[up])
+    block, last = unet.final_conv
+    # (the final Block of a model at pitch == C has always run on its own parameters, also where its GroupNorm is generic: 96, 160, ...)
+    h = _block(block, h, c, tuned[block], pad=not tuned[last])
+    return AG.SmallNConvFn.apply(h, last.weight if tuned[last] else AG.pad_param(last.weight, in_real=[c]), last.bias)
 
 
 def sq_err_sum_autograd(a, b):

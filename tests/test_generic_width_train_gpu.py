@@ -149,6 +149,47 @@ def test_unet_training_at_widths_that_are_not_multiples_of_32(chan, cin, size, d
     assert rel_err(y_plan.cpu(), out.detach().cpu()) < 5e-5
 
 
+def test_unet_training_generic_width_with_tuned_eligible_levels():
+    """unet_chan = 16, dims (1, 2, 4): levels of 16, 32 and 64 channels -- the smallest model in which a network on the padded pitch
+    holds widths (32, 64) that the tuned GroupNorm / LayerNorm backward would take.  Every module runs the generic forms there and no
+    gradient is handed over (ddk.autograd.resnet_tuned / attention_tuned / pitch_tuned); a walk that mixed the two forms would show
+    here.  The output, the input gradient and the gradient of EVERY parameter against torch-CPU autograd of oracle.unet_ref at the
+    bars of test_unet_training_at_widths_that_are_not_multiples_of_32 (forward 5e-5, gradients 2e-4 of each tensor's max; two channels
+    per group at the first level), and the eval-mode plan against the training forward (5e-5)."""
+    from models import Unet
+    cfg = dict(unet_chan=16, unet_in=3, unet_dims=(1, 2, 4), unet_dropout=0.0)
+    model = Unet(cfg)
+    sd = syn.fill_state_dict(model.state_dict(), 91)
+    model.load_state_dict(sd)
+    model = model.to(DEV).train()
+    x = syn.synthetic_input((2, 3, 8, 8), "gw16.x")
+    t = torch.tensor([11, 640])
+    wgt = syn.synthetic_normal((2, 3, 8, 8), "gw16.w")
+    ref_sd = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
+    xr = x.clone().requires_grad_(True)
+    out_ref = U.unet_forward(ref_sd, cfg, xr, t)
+    (out_ref * wgt).sum().backward()
+    xd = x.to(DEV).requires_grad_(True)
+    out = model(xd, t.to(DEV))
+    e = rel_err(out.detach().cpu(), out_ref.detach())
+    (out * wgt.to(DEV)).sum().backward()
+    ex = rel_err(xd.grad.cpu(), xr.grad)
+    errs = {}
+    for k, p in model.named_parameters():
+        assert p.grad is not None, k
+        errs[k] = rel_err(p.grad.cpu(), ref_sd[k].grad)
+    worst = max(errs, key=errs.get)
+    print(f"unet training chan 16 dims (1, 2, 4): forward {e:.3e} input gradient {ex:.3e} worst parameter {worst} {errs[worst]:.3e}")
+    assert e < 5e-5 and ex < 2e-4
+    assert len(errs) == len(ref_sd)
+    for k, v in errs.items():
+        assert v < 2e-4, (k, v)
+    model.eval()
+    with torch.no_grad():
+        y_plan = model(x.to(DEV), t.to(DEV))
+    assert rel_err(y_plan.cpu(), out.detach().cpu()) < 5e-5
+
+
 def test_unet_generic_width_dropout_trains(tmp_path):
     """unet_dropout > 0 at width 24: two optimiser steps through the product trainer (device-graph capture included) stay finite and
     move the weights -- the Dropout mask of the generic GroupNorm kernel is drawn in the forward and regenerated in the backward"""
