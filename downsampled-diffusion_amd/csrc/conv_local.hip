@@ -418,7 +418,17 @@ constexpr int WL_VBUF = 16 * 16 * WL_VP;        // one V buffer: [position][tile
 
 __host__ __device__ static inline size_t wlocal_lds_bytes(int cin) { return ((size_t)65 * (cin + 4) + 2 * WL_VBUF) * 4 + 256; }
 
+// NCH = 0: any eligible cin, chunk count at run time.  NCH > 0 (8: the sampler's 256 -> 256 Blocks): cin = 32 NCH at compile time,
+// both wave kinds' chunk loops fully unrolled -- every LDS address in them is a per-lane base register plus an immediate (the DS
+// offset field is 16 bits: asserted below), the weight pointer advances by constants, and the order of a chunk's instructions is
+// pinned.  The arithmetic of both forms is the same, operation for operation.
+template <int NCH>
 __global__ __launch_bounds__(1024) void conv3x3_gn_wlocal_kernel(const WLocalParams p) {
+    static_assert(NCH >= 0 && NCH <= 10, "cin <= 320");
+    // the immediates of the unrolled form's DS instructions (bytes, last byte touched); the per-lane base register holds the rest
+    static_assert((NCH > 0 ? NCH - 1 : 0) * 128 + 15 < 65536, "transform reads: 128 bytes per chunk");
+    static_assert((WL_VBUF + 3 * 16 * WL_VP) * 4 + 15 < 65536, "transform writes: buffer parity + position row");
+    static_assert((WL_VBUF + 16 * WL_VP + 4) * 4 + 15 < 65536, "fragment reads: buffer parity + position + k half");
     extern __shared__ __align__(16) float lds[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // 0..7 matrix waves, 8..15 transform waves
@@ -426,9 +436,10 @@ __global__ __launch_bounds__(1024) void conv3x3_gn_wlocal_kernel(const WLocalPar
     const int NT = p.N >> 5;
     const int nt = blockIdx.x % NT, b = blockIdx.x / NT;
     const int n0 = nt << 5;
-    const int cin = p.c0 + p.c1;
+    const int cin = NCH > 0 ? NCH * 32 : p.c0 + p.c1;
     const int pitch = cin + 4;
     const int nch = cin >> 5;
+    constexpr int UNROLL_T = NCH > 0 ? NCH : 1, UNROLL_M = NCH > 0 ? (NCH + 1) / 2 : 1;      // the chunk loops: whole, or as written
     float* V = lds + 65 * pitch;
     float* red = V + 2 * WL_VBUF;
     auto lds_barrier = [] {   // LDS traffic only: __syncthreads() would also wait (vmcnt) for the weight loads deliberately in flight
@@ -445,18 +456,21 @@ __global__ __launch_bounds__(1024) void conv3x3_gn_wlocal_kernel(const WLocalPar
     //      still takes 19.7 of 20.8 us, with the transform ablated 18.7.  What is left is the per-chunk barrier with two matrix waves
     //      per SIMD parked at it together, and ~8 us of launch + image staging + output transform + GroupNorm tail around the loop.
     //      (Rotating the n tiles over the XCDs so that an XCD's workgroups stream different bytes is slower: 23.1 us.)
-    const float* wl = p.w + ((size_t)nt * nch * 16 + 2 * (wave & 7)) * 1024 + lane * 4;
+    const float* wu = p.w + ((size_t)nt * nch * 16 + 2 * (wave & 7)) * 1024;       // uniform over the wave: a scalar base ...
+    const unsigned wlane = lane * 16;                                               // ... plus one 32-bit lane offset (bytes), the same for every load
+    auto ldw = [&](const float* up) { return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(up) + wlane); };
     float4 bA[2][2][2], bB[2][2][2];            // [position of the pair][n block][k half]
+    auto load_b1 = [&](int chunk, int pp, float4 (&bq)[2][2]) {
+        const float* wp = wu + ((size_t)chunk * 16 + pp) * 1024;
+        bq[0][0] = ldw(wp);
+        bq[0][1] = ldw(wp + 256);
+        bq[1][0] = ldw(wp + 512);
+        bq[1][1] = ldw(wp + 768);
+    };
     auto load_b = [&](int chunk, float4 (&bq)[2][2][2]) {
-        chunk = chunk < nch ? chunk : nch - 1;  // past the end: harmless re-read, no load under a condition
-        const float* wp = wl + (size_t)chunk * 16 * 1024;
-#pragma unroll
-        for (int pp = 0; pp < 2; ++pp) {
-            bq[pp][0][0] = *reinterpret_cast<const float4*>(wp + pp * 1024);
-            bq[pp][0][1] = *reinterpret_cast<const float4*>(wp + pp * 1024 + 256);
-            bq[pp][1][0] = *reinterpret_cast<const float4*>(wp + pp * 1024 + 512);
-            bq[pp][1][1] = *reinterpret_cast<const float4*>(wp + pp * 1024 + 768);
-        }
+        if (NCH == 0) chunk = chunk < nch ? chunk : nch - 1;     // run-time form past the end: harmless re-read, no load under a condition
+        load_b1(chunk, 0, bq[0]);
+        load_b1(chunk, 1, bq[1]);
     };
     if (wave < 8) {
         load_b(0, bA);
@@ -486,7 +500,9 @@ __global__ __launch_bounds__(1024) void conv3x3_gn_wlocal_kernel(const WLocalPar
         // History (tools/wl_clock.py): one channel per item on 4 waves (32 + 32 four-byte LDS operations per thread and chunk) kept the
         // transform busy 2961 cycles per chunk where the MFMAs need 2048 -- it, not weight delivery, was this kernel's critical
         // path; float4 items on 4 waves 2720; 8 waves: see profiles/r03_wl_clock.txt.
-        __builtin_amdgcn_s_setprio(3);          // a short burst the matrix waves wait for: it goes first on its SIMD
+        // run-time form: a short burst the matrix waves wait for, it goes first on its SIMD.  Unrolled form: the matrix waves hold the
+        // priority instead (below) -- the transform needs a quarter of a chunk's time and fills the slots they leave
+        if (NCH == 0) __builtin_amdgcn_s_setprio(3);
         const int t2 = tid - 512;
         const int tt = t2 >> 5, ri = (t2 >> 3) & 3, q4 = t2 & 7;
         const int tty = tt / TW, ttx = tt - tty * TW;
@@ -505,21 +521,29 @@ __global__ __launch_bounds__(1024) void conv3x3_gn_wlocal_kernel(const WLocalPar
         auto f4 = [](const float* q) { return *reinterpret_cast<const float4*>(q); };
         auto sub = [](float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); };
         auto add = [](float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); };
-        auto transform = [&](int chunk, int buf) {
-            float4 r[4];
+        // 8 read bases and 1 write base per lane; in the unrolled form everything else is an immediate, and the 8 reads of a chunk are
+        // requested together (the compiler otherwise waits for the first 4 before it asks for the rest)
+        const float* pr[8];
 #pragma unroll
-            for (int x = 0; x < 4; ++x) {
-                const float4 a = f4(lds + poff[x] + (chunk << 5)), b = f4(lds + poff[4 + x] + (chunk << 5));
-                r[x] = make_float4(fmaf(sgn, b.x, a.x), fmaf(sgn, b.y, a.y), fmaf(sgn, b.z, a.z), fmaf(sgn, b.w, a.w));
-            }
-            float* vb = V + buf * WL_VBUF + voff;
+        for (int x = 0; x < 8; ++x) pr[x] = lds + poff[x];
+        float* const vw = V + voff;
+        auto transform = [&](int chunk, int buf) {
+            float4 a[4], bb[4], r[4];
+#pragma unroll
+            for (int x = 0; x < 4; ++x) a[x] = f4(pr[x] + chunk * 32), bb[x] = f4(pr[4 + x] + chunk * 32);
+            if (NCH > 0) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int x = 0; x < 4; ++x)
+                r[x] = make_float4(fmaf(sgn, bb[x].x, a[x].x), fmaf(sgn, bb[x].y, a[x].y), fmaf(sgn, bb[x].z, a[x].z), fmaf(sgn, bb[x].w, a[x].w));
+            float* vb = vw + buf * WL_VBUF;
             *reinterpret_cast<float4*>(vb + 0 * (16 * WL_VP)) = sub(r[0], r[2]);
             *reinterpret_cast<float4*>(vb + 1 * (16 * WL_VP)) = add(r[1], r[2]);
             *reinterpret_cast<float4*>(vb + 2 * (16 * WL_VP)) = sub(r[2], r[1]);
             *reinterpret_cast<float4*>(vb + 3 * (16 * WL_VP)) = sub(r[1], r[3]);
         };
         transform(0, 0);
-        for (int c = 0; c < nch; ++c) {
+#pragma unroll UNROLL_T
+        for (int c = 0; c < nch; ++c) {         // nch is the constant NCH in the unrolled form
             lds_barrier();                      // V[c & 1] complete, V[(c + 1) & 1] consumed
             WL_STAMP(st_a);
             if (c + 1 < nch) transform(c + 1, (c + 1) & 1);
@@ -543,36 +567,57 @@ __global__ __launch_bounds__(1024) void conv3x3_gn_wlocal_kernel(const WLocalPar
     const TailPre<4> pre = tail_prefetch<4>(o_t, c, b, p);
     f32x4 acc[2][2];
     acc[0][0] = acc[0][1] = acc[1][0] = acc[1][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-    auto chunk_step = [&](int chunk, const float4 (&bq)[2][2][2]) {
+    auto mfma_run = [&](int pp, const float4 (&a)[2], const float4 (&bq)[2][2]) {      // one position's 16 MFMAs of a chunk
+#pragma unroll
+        for (int kk = 0; kk < 8; ++kk) {
+            const float av = reinterpret_cast<const float*>(&a[0])[kk];
+#if defined(DDK_TUNING) && defined(DDK_WL_NO_MFMA)     /* ablation, tuning build only (wrong results): how long does the transform take when the matrix pipe is idle? */
+            acc[pp][0][0] += av * reinterpret_cast<const float*>(&bq[0][0])[kk];
+            acc[pp][1][0] += av * reinterpret_cast<const float*>(&bq[1][0])[kk];
+#else
+            acc[pp][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, reinterpret_cast<const float*>(&bq[0][0])[kk], acc[pp][0], 0, 0, 0);
+            acc[pp][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, reinterpret_cast<const float*>(&bq[1][0])[kk], acc[pp][1], 0, 0, 0);
+#endif
+        }
+    };
+    // One chunk of a matrix wave.  Run-time form: the compiler orders reads and MFMAs, the chunk's weight registers are reloaded behind
+    // them (two chunks ahead).  Unrolled form, order pinned: one fragment base per lane with buffer parity / position / k half as
+    // immediates; the four fragment reads are requested together right after the barrier, so both positions' MFMAs run back to back
+    // behind one LDS latency; a position's next weights are requested as soon as its MFMAs have issued, the first position's before
+    // the second's MFMAs, and the last two chunks request none.  Nothing reads V[(c + 1) & 1] before barrier c + 1.
+    const float* const vb0 = V + ((2 * wave) * 16 + m) * WL_VP + kq * 8;
+    auto chunk_step = [&](int chunk, float4 (&bq)[2][2][2]) {
         WL_STAMP(st_a);
         lds_barrier();
         WL_STAMP(st_b);
         st_wait += st_b - st_a;
-        const float* vb = V + (chunk & 1) * WL_VBUF + ((2 * wave) * 16 + m) * WL_VP + kq * 8;
+        const float* vb = vb0 + (chunk & 1) * WL_VBUF;
+        float4 a[2][2];
 #pragma unroll
         for (int pp = 0; pp < 2; ++pp) {
-            float4 a[2];
-            a[0] = *reinterpret_cast<const float4*>(vb + pp * (16 * WL_VP));
-            a[1] = *reinterpret_cast<const float4*>(vb + pp * (16 * WL_VP) + 4);
+            a[pp][0] = *reinterpret_cast<const float4*>(vb + pp * (16 * WL_VP));
+            a[pp][1] = *reinterpret_cast<const float4*>(vb + pp * (16 * WL_VP) + 4);
+        }
 #pragma unroll
-            for (int kk = 0; kk < 8; ++kk) {
-                const float av = reinterpret_cast<const float*>(&a[0])[kk];
-#if defined(DDK_TUNING) && defined(DDK_WL_NO_MFMA)     /* ablation, tuning build only (wrong results): how long does the transform take when the matrix pipe is idle? */
-                acc[pp][0][0] += av * reinterpret_cast<const float*>(&bq[pp][0][0])[kk];
-                acc[pp][1][0] += av * reinterpret_cast<const float*>(&bq[pp][1][0])[kk];
-#else
-                acc[pp][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, reinterpret_cast<const float*>(&bq[pp][0][0])[kk], acc[pp][0], 0, 0, 0);
-                acc[pp][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, reinterpret_cast<const float*>(&bq[pp][1][0])[kk], acc[pp][1], 0, 0, 0);
-#endif
+        for (int pp = 0; pp < 2; ++pp) {
+            if (NCH > 0) __builtin_amdgcn_sched_barrier(0);
+            mfma_run(pp, a[pp], bq[pp]);
+            if (NCH > 0) {
+                __builtin_amdgcn_sched_barrier(0);
+                if (chunk + 2 < NCH) load_b1(chunk + 2, pp, bq[pp]);
             }
         }
+        if (NCH == 0) load_b(chunk + 2, bq);
     };
+    // unrolled form: the matrix waves hold the priority -- their fragment reads go ahead of the transform waves' 12 LDS operations per
+    // lane, their MFMAs ahead of its arithmetic (profiles/wlocal_loop_clock.txt: every other order is slower)
+    if (NCH > 0) __builtin_amdgcn_s_setprio(3);
+#pragma unroll UNROLL_M
     for (int c = 0; c < nch; c += 2) {
         chunk_step(c, bA);
-        load_b(c + 2, bA);
         if (c + 1 < nch) chunk_step(c + 1, bB);
-        load_b(c + 3, bB);
     }
+    if (NCH > 0) __builtin_amdgcn_s_setprio(0);
 
     // ---- M[position][tile][n] of the 8 waves into LDS (over the V buffers; the transform waves have finished)
     WL_STAMP(st_loop);
@@ -701,7 +746,11 @@ int conv_gn_wlocal(const float* src0, int c0, const float* src1, int c1, const f
     DDK_TRY(ensure_device_init());
     WLocalParams p{src0, src1, c0, c1, w, bias, gamma, beta, temb, temb_stride, temb_rows, addend, out, H, W, N, N / groups, eps,
                    as.n, as.stride, as.bias, ss.n, ss.stride, ss.bias};
-    hipLaunchKernelGGL(conv3x3_gn_wlocal_kernel, dim3((unsigned)((long long)B * (N / 32))), dim3(1024), wlocal_lds_bytes(c0 + c1), st, p);
+    const dim3 grid((unsigned)((long long)B * (N / 32)));
+    if (c0 + c1 == 256)     // the sampler's 8x8 Blocks: compile-time chunk loop
+        hipLaunchKernelGGL(conv3x3_gn_wlocal_kernel<8>, grid, dim3(1024), wlocal_lds_bytes(256), st, p);
+    else
+        hipLaunchKernelGGL(conv3x3_gn_wlocal_kernel<0>, grid, dim3(1024), wlocal_lds_bytes(c0 + c1), st, p);
     return check_launch("conv3x3_gn_wlocal_kernel");
 }
 
@@ -725,7 +774,9 @@ int conv_gn_local_init_device() {
                                 160 * 1024));
     DDK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_gn_local_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 160 * 1024));
-    DDK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_gn_wlocal_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+    DDK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_gn_wlocal_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                160 * 1024));
+    DDK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_gn_wlocal_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 160 * 1024));
     return DDK_OK;
 }
