@@ -1344,12 +1344,19 @@ int conv_forward(const ddk_conv_args& a, hipStream_t st, const ConvLnFold* ln, c
         san::extent("conv mish_out", a.mish_out, pix_out * a.N * 4);
         san::extent("conv dmish_src", a.dmish_src, pix_out * a.N * 4);
         if (a.gn_partials && a.gn_groups > 0) san::extent("conv gn_partials", a.gn_partials, (pix_out / 128) * a.gn_groups * 8);
+        if (a.skip_slab_stride == 0) san::extent("conv skip_out", a.skip_out, pix_out * a.N * 4);
+        san::extent("conv skip_bias", a.skip_bias, (long long)a.N * 4);
+        san::extent("conv skip_weight", a.skip_weight, (long long)a.N * (a.c0 + a.c1) * 4);
     }
 #endif
     DDK_REQUIRE(aligned16(a.mish_out) && aligned16(a.dmish_src), "conv: mish_out / dmish_src alignment");
     DDK_REQUIRE(!(a.mish_out || a.dmish_src) || !(a.defer_reduce || a.gn_partials || fuse || ln),
                 "conv: mish_out / dmish_src go with a plain conv (no deferred reduce, GroupNorm partials or LayerNorm folding)");
     const bool act_epilogue = a.mish_out || a.dmish_src;     // only the im2col / halo epilogues and the slab reduce implement these
+    // the skip fold exists in the Winograd kernel alone: anything else is an error, not a silent second conv
+    DDK_REQUIRE(!a.skip_out || (a.weight_wino && !a.pre_mish && !act_epilogue && !ln && a.kind == DDK_CONV3X3_S1 &&
+                                conv_wino_skip_ok(a.B, a.H, a.W, a.c0 + a.c1, a.N)),
+                "conv: skip_out needs the Winograd path on a shape with ddk_conv_wino_skip_ok()");
     if (a.weight_wino && !a.pre_mish && !act_epilogue && conv_wino_ok(a.kind, a.H, a.W, a.c0 + a.c1, a.N)) {
         // Winograd F(2x2, 3x3) path (conv_wino.hip): same slab / reduce conventions as the direct kernels
         DDK_REQUIRE(aligned16(a.weight_wino), "conv: weight_wino alignment");
@@ -1357,7 +1364,9 @@ int conv_forward(const ddk_conv_args& a, hipStream_t st, const ConvLnFold* ln, c
         const int ws = conv_wino_splits(a.B, a.H, a.W, a.c0 + a.c1, a.N);
         const long long slab = (long long)a.B * a.H * a.W * a.N;
         if (ws > 1) {
-            const size_t need = (size_t)(fuse ? ws - 1 : ws) * slab * sizeof(float);    // fuse: only the partners' partial tiles
+            // fuse: only the partners' partial tiles.  Skip fold: its partials likewise, behind the conv's (unless the caller names a slab area)
+            const bool sk_ws = a.skip_out && (fuse || a.skip_slab_stride == 0);
+            const size_t need = (size_t)(fuse ? ws - 1 : ws) * (sk_ws ? 2 : 1) * slab * sizeof(float);
             if (!a.workspace || a.workspace_bytes < need) {
                 set_error("conv(wino): split-K workspace too small (%zu < %zu)", a.workspace_bytes, need);
                 return DDK_ERR_WORKSPACE;
@@ -1372,6 +1381,14 @@ int conv_forward(const ddk_conv_args& a, hipStream_t st, const ConvLnFold* ln, c
             hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, static_cast<const float*>(a.workspace), ws, slab, a.bias,
                                a.resid, a.out, n4, a.N, a.post_mish, static_cast<float*>(nullptr), static_cast<const float*>(nullptr));
             DDK_TRY(check_launch("splitk_reduce_kernel"));
+        }
+        if (ws > 1 && a.skip_out && !fuse && a.skip_slab_stride == 0) {     // the skip slabs behind the conv's (conv_wino_forward)
+            const long long n4 = slab / 4;
+            const int blocks = (int)(ceil_div(n4, 256) < 2048 ? ceil_div(n4, 256) : 2048);
+            hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, static_cast<const float*>(a.workspace) + (long long)ws * slab, ws,
+                               slab, a.skip_bias, static_cast<const float*>(nullptr), a.skip_out, n4, a.N, 0, static_cast<float*>(nullptr),
+                               static_cast<const float*>(nullptr));
+            DDK_TRY(check_launch("splitk_reduce_kernel<skip>"));
         }
         return DDK_OK;
     }

@@ -73,6 +73,11 @@ struct WinoParams {
     const float* r1_w;             // ... with weight rows [N][r1_ld] and bias r1_b [N] (WinoGnFuse::res_*)
     const float* r1_b;
     int r1_cin, r1_ld;
+    // skip fold (the SK instantiations of conv3x3_wino2_kernel): the 1x1 conv of the same input, computed from the inner V positions
+    const float* sk_w;             // W1 / 4 in operand order (ddk_pack_conv_skip_weight_wino)
+    const float* sk_bias;          // [N] or null
+    float* sk_out;                 // [B][H][W][N]; slab form: the skip slabs [splits][sk_stride] (partial sums, no bias)
+    long long sk_stride;
 };
 
 constexpr int WBT = 32, WBN = 64;                        // tiles and output channels per workgroup
@@ -92,6 +97,21 @@ __global__ __launch_bounds__(256) void pack_conv_weight_wino_kernel(const float*
                                                                      int i_pad, long long total, int lo, int wi) {
     for (long long idx = blockIdx.x * 256LL + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256)
         pack_wino_elem<DGRAD>(w, dst, idx, O, I, i_pad, lo, wi);
+}
+
+// The 1x1 skip weight [O][I] for the skip fold of conv3x3_wino2_kernel: dst[i_pad / 32][O / 32][4 quarters][64 lanes][4] -- lane l of
+// quarter q holds W[32 nblk + (l & 31)][32 chunk + 8 q + 4 (l >> 5) + j] / 4, the B fragment of the four MFMAs of that quarter
+// (the factor 1/4 undoes the 2x2 Hadamard transform of the inner Winograd positions; a power of two, so exact)
+__global__ __launch_bounds__(256) void pack_conv_skip_weight_wino_kernel(const float* __restrict__ w, float* __restrict__ dst, int O, int I,
+                                                                          long long total) {
+    for (long long idx = blockIdx.x * 256LL + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
+        const unsigned u = (unsigned)idx;
+        const int j = (int)(u & 3u), l = (int)((u >> 2) & 63u), q = (int)((u >> 8) & 3u);
+        const unsigned r = u >> 10;
+        const int nblk = (int)(r % (unsigned)(O >> 5)), chunk = (int)(r / (unsigned)(O >> 5));
+        const int n = 32 * nblk + (l & 31), c = 32 * chunk + 8 * q + 4 * (l >> 5) + j;
+        dst[idx] = c < I ? 0.25f * w[(long long)n * I + c] : 0.f;
+    }
 }
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -628,6 +648,12 @@ int conv_wino_stats_parts(int B, int H, int W, int cin, int N, int groups) {
     return wino_stats_shape_parts(B, H, W, cin, N, groups);
 }
 
+// Can the conv of this shape carry a ResnetBlock's 1x1 skip conv of the same input (the SK instantiations)?  Variant D and whole input
+// chunks (conv_wino_ok); the skip's output channels are the conv's.
+bool conv_wino_skip_ok(int B, int H, int W, int cin, int N) {
+    return conv_wino_ok(DDK_CONV3X3_S1, H, W, cin, N) && wino_variant(B, H, W, N) == WINO_V_D;
+}
+
 // ---- transpose conv (conv_winoT_kernel.inc)
 bool convT_wino_ok(int H, int W, int cin, int N) {
     return H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0 && cin > 0 && cin % 32 == 0 && N > 0 && N % WT_NT == 0;
@@ -684,6 +710,10 @@ int conv_wino_init_device() {
     DDK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino2_kernel<4, 0, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)(W2<4>::LDS_FL * sizeof(float))));
     DDK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino2_kernel<4, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)(W2<4>::LDS_FL * sizeof(float))));
+    DDK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino2_kernel<4, 0, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)(W2<4>::LDS_FL * sizeof(float))));
+    DDK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino2_kernel<4, 0, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)(W2<4>::LDS_FL * sizeof(float))));
 #ifdef DDK_TUNING   // 1: stamps; 2: + loaders exit after the prologue; 3: + loaders at priority 0; 4: + no U DMA in the loop (2-4: wrong results)
 #define W2_DBG_ATTR(P_, D_) DDK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino2_kernel<P_, D_, false>), \
@@ -811,6 +841,20 @@ int conv_wino_forward(const ddk_conv_args& a, int splits, hipStream_t st, const 
     p.dTH = make_fastdiv_u((unsigned)p.TH);
     if (p.splits > 1 && !fuse) p.out = static_cast<float*>(a.workspace);
     const int variant = wino_variant(a.B, a.H, a.W, a.N);
+    if (a.skip_out) {
+        DDK_REQUIRE(conv_wino_skip_ok(a.B, a.H, a.W, p.cin, a.N) && variant == WINO_V_D,
+                    "conv(wino): shape not eligible for the skip fold (ddk_conv_wino_skip_ok)");
+        DDK_REQUIRE(a.skip_weight && aligned16(a.skip_weight) && aligned16(a.skip_bias) && aligned16(a.skip_out) && !a.post_mish &&
+                        a.skip_slab_stride % 4 == 0 && (a.skip_slab_stride == 0 || (a.skip_slab_stride >= p.slab_stride && p.splits > 1 && !fuse)),
+                    "conv(wino): skip fold arguments");
+        p.sk_w = a.skip_weight; p.sk_bias = a.skip_bias; p.sk_out = a.skip_out; p.sk_stride = p.slab_stride;
+        if (p.splits > 1 && !fuse) {
+            // slab form: the caller's slab area (skip_slab_stride > 0; its reader adds the bias), or the workspace behind the conv's own
+            // slabs, which conv_forward sums into skip_out
+            if (a.skip_slab_stride > 0) p.sk_stride = a.skip_slab_stride;
+            else p.sk_out = static_cast<float*>(a.workspace) + (long long)p.splits * p.slab_stride;
+        }
+    }
     if (variant != WINO_V_OLD) {
         dim3 grid2((unsigned)ceil_div(p.tiles, WBT), (unsigned)(a.N / wino_nt(variant)), (unsigned)p.splits);
         const bool f = variant == WINO_V_F;
@@ -831,6 +875,11 @@ int conv_wino_forward(const ddk_conv_args& a, int splits, hipStream_t st, const 
             return check_launch("conv3x3_wino2_kernel<dbg>");
         }
 #endif
+        if (p.sk_out) {        // (variant D, one pass: checked above)
+            if (fuse) hipLaunchKernelGGL((conv3x3_wino2_kernel<4, 0, true, true>), grid2, dim3(768), lds, st, p);
+            else hipLaunchKernelGGL((conv3x3_wino2_kernel<4, 0, false, true>), grid2, dim3(768), lds, st, p);
+            return check_launch("conv3x3_wino2_kernel<skip>");
+        }
         if (fuse) {
             if (f) hipLaunchKernelGGL((conv3x3_wino2_kernel<2, 0, true>), grid2, dim3(768), lds, st, p);
             else hipLaunchKernelGGL((conv3x3_wino2_kernel<4, 0, true>), grid2, dim3(768), lds, st, p);
@@ -893,6 +942,19 @@ extern "C" int ddk_pack_conv_weight_wino(const float* w_oihw, float* dst, int O,
                        dst, O, I, i_pad, total, 0, I);
     return check_launch("pack_conv_weight_wino_kernel");
 }
+
+extern "C" int ddk_pack_conv_skip_weight_wino(const float* w_oi, float* dst, int O, int I, int i_pad, ddk_stream_t s) {
+    using namespace ddk;
+    DDK_REQUIRE(w_oi && dst && O > 0 && O % 32 == 0 && I > 0 && i_pad >= I && i_pad % 32 == 0,
+                "pack_conv_skip_weight_wino: arguments (O % 32 == 0, i_pad % 32 == 0)");
+    const long long total = (long long)O * i_pad;
+    DDK_REQUIRE(total < (1LL << 31), "pack_conv_skip_weight_wino: 2^31 elements or more");
+    const long long blocks = ceil_div(total, 256);
+    hipLaunchKernelGGL(pack_conv_skip_weight_wino_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, as_stream(s), w_oi, dst,
+                       O, I, total);
+    return check_launch("pack_conv_skip_weight_wino_kernel");
+}
+extern "C" int ddk_conv_wino_skip_ok(int B, int H, int W, int cin, int N) { return ddk::conv_wino_skip_ok(B, H, W, cin, N) ? 1 : 0; }
 
 extern "C" int ddk_pack_convT_weight_wino(const float* w_iohw, float* dst, int I, int O, int i_pad, ddk_stream_t s) {
     using namespace ddk;
@@ -978,16 +1040,18 @@ extern "C" int ddk_debug_occupy(int workgroups, int lds_bytes, int microseconds,
     return check_launch("occupy_kernel");
 }
 
-extern "C" int ddk_conv3x3_gn_mish_cluster(const float* src0, int c0, const float* src1, int c1, const float* weight_wino, const float* bias,
-                                           const float* gamma, const float* beta, const float* temb, int temb_stride, const float* addend,
-                                           float* out, int B, int H, int W, int N, int groups, float eps, void* workspace,
-                                           size_t workspace_bytes, ddk_stream_t s) {
+static int gn_mish_cluster(const float* src0, int c0, const float* src1, int c1, const float* weight_wino, const float* bias,
+                           const float* gamma, const float* beta, const float* temb, int temb_stride, const float* addend, float* out, int B,
+                           int H, int W, int N, int groups, float eps, void* workspace, size_t workspace_bytes, const float* skip_weight,
+                           const float* skip_bias, float* skip_out, ddk_stream_t s) {
     using namespace ddk;
     DDK_REQUIRE(src0 && weight_wino && gamma && beta && out && workspace, "conv3x3_gn_mish_cluster: null pointer");
     DDK_REQUIRE(conv_wino_cluster_device_ok() && ddk_conv3x3_gn_mish_cluster_ok(B, H, W, c0 + c1, N, groups) > 0,
                 "conv3x3_gn_mish_cluster: shape or device not eligible (ddk_conv3x3_gn_mish_cluster_ok)");
     const size_t plain_bytes = ddk_conv3x3_gn_mish_cluster_workspace_bytes(B, H, W, N);
-    const size_t split_bytes = ddk_conv3x3_gn_mish_cluster_split_workspace_bytes(B, H, W, c0 + c1, N, groups);
+    size_t split_bytes = ddk_conv3x3_gn_mish_cluster_split_workspace_bytes(B, H, W, c0 + c1, N, groups);
+    // (the skip fold's partial tiles follow the conv's: as many slabs again)
+    if (split_bytes && skip_out) split_bytes += (size_t)(conv_wino_splits(B, H, W, c0 + c1, N) - 1) * B * H * W * N * sizeof(float);
     DDK_REQUIRE(workspace_bytes >= (split_bytes ? split_bytes : plain_bytes) && aligned16(workspace), "conv3x3_gn_mish_cluster: workspace");
     float* ws = static_cast<float*>(workspace);
     // counters + the sticky give-up word behind them: zeroed per call here (a plan zeroes them once per forward / chain)
@@ -1003,6 +1067,7 @@ extern "C" int ddk_conv3x3_gn_mish_cluster(const float* src0, int c0, const floa
     a.resid = addend;
     a.out = out;
     a.B = B; a.H = H; a.W = W; a.N = N;
+    a.skip_weight = skip_weight; a.skip_bias = skip_bias; a.skip_out = skip_out;
     const ClWords w = cl_words(ws, B);
     WinoGnFuse f{gamma, beta, temb, nullptr, temb_stride, eps, groups, ws + cl_front_floats(B), w.counters, w.fail};
     if (split_bytes) {
@@ -1011,5 +1076,22 @@ extern "C" int ddk_conv3x3_gn_mish_cluster(const float* src0, int c0, const floa
         a.workspace_bytes = split_bytes - plain_bytes - conv_wino_cluster_pair_words(B, H, W, N) * sizeof(float);
     }
     return conv_forward(a, as_stream(s), nullptr, &f);
+}
+extern "C" int ddk_conv3x3_gn_mish_cluster(const float* src0, int c0, const float* src1, int c1, const float* weight_wino, const float* bias,
+                                           const float* gamma, const float* beta, const float* temb, int temb_stride, const float* addend,
+                                           float* out, int B, int H, int W, int N, int groups, float eps, void* workspace,
+                                           size_t workspace_bytes, ddk_stream_t s) {
+    return gn_mish_cluster(src0, c0, src1, c1, weight_wino, bias, gamma, beta, temb, temb_stride, addend, out, B, H, W, N, groups, eps, workspace,
+                           workspace_bytes, nullptr, nullptr, nullptr, s);
+}
+/* ... whose launch also writes the 1x1 skip conv of the same input (ddk_conv_args.skip_out; ddk_conv_wino_skip_ok() shapes) */
+extern "C" int ddk_conv3x3_gn_mish_cluster_skip(const float* src0, int c0, const float* src1, int c1, const float* weight_wino, const float* bias,
+                                                const float* gamma, const float* beta, const float* temb, int temb_stride, const float* addend,
+                                                float* out, int B, int H, int W, int N, int groups, float eps, void* workspace,
+                                                size_t workspace_bytes, const float* skip_weight, const float* skip_bias, float* skip_out,
+                                                ddk_stream_t s) {
+    DDK_REQUIRE(skip_weight && skip_out, "conv3x3_gn_mish_cluster_skip: null pointer");
+    return gn_mish_cluster(src0, c0, src1, c1, weight_wino, bias, gamma, beta, temb, temb_stride, addend, out, B, H, W, N, groups, eps, workspace,
+                           workspace_bytes, skip_weight, skip_bias, skip_out, s);
 }
 

@@ -60,9 +60,15 @@ constexpr bool W2_STAGGER = DDK_WINO2_STAGGER != 0;  // waves 4..7 run one quart
 // workgroup 0 (stages 8..15) into g_wino_timeline
 __device__ unsigned long long g_wino_timeline[12 * 8 * 2];
 
-template <int P, int DBG, bool CL>
+// SK (variant D only): the ResnetBlock's 1x1 skip conv of the SAME input rides along (DESIGN.md 3.1l).  The four
+// inner positions 5, 6, 9, 10 of V = B^T d B are a 2x2 Hadamard transform of the patch centre -- the tile's own four pixels -- so
+// S_p = (W1 / 4) . V_p for those p, combined with the transform's signs, is the 1x1 conv at those pixels.  The waves that own these
+// positions (pp = 1, 2; stages 1, 2) multiply their A fragments a second time, against W1 fragments streamed from L2 into registers.
+template <int P, int DBG, bool CL, bool SK = false>
 __global__ __launch_bounds__(768) void conv3x3_wino2_kernel(const WinoParams p) {
     using G = W2<P>;
+    static_assert(!SK || (P == 4 && DBG == 0), "the skip fold exists on variant D");
+    static_assert(!SK || G::T_FL + 320 + 2 * 2 * WBT * G::TP <= G::LDS_FL, "the skip tile is staged behind the conv's");
     constexpr int NT = G::NT, SPC = G::SPC, SPR = G::SPR, STAGE = G::STAGE, V_FL = G::V_FL;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     unsigned long long r_entry = 0;
@@ -268,7 +274,18 @@ __global__ __launch_bounds__(768) void conv3x3_wino2_kernel(const WinoParams p) 
     }
 
     // ================================================================ matrix wave (pp, nb)
-    const int pp = wid % P, nb = wid / P;
+    // SK: waves w and w + 4 share a SIMD; the extra multiplies belong to pp = 1, 2, so waves 4..7 swap pp pairwise and every SIMD
+    // carries exactly one such wave (pp only names the position a wave owns: a_img, b_img and its staging block below follow it)
+    const int pp = (SK && wid >= 4) ? ((wid % P) ^ 1) : wid % P, nb = wid / P;
+    const bool skw = SK && (pp == 1 || pp == 2);                        // wave-uniform
+    f32x16 sk[2];                                                       // SK: S_(4 + pp) (stage 1), S_(8 + pp) (stage 2)
+    f32x4 w1[4];                                                        // SK: this chunk's W1 / 4 fragments of n block nb, one per quarter
+    if constexpr (SK) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) sk[i][r] = 0.f;
+    }
     f32x16 acc[SPC];
 #pragma unroll
     for (int i = 0; i < SPC; ++i)
@@ -280,11 +297,30 @@ __global__ __launch_bounds__(768) void conv3x3_wino2_kernel(const WinoParams p) 
 #pragma unroll
         for (int q = 0; q < 4; ++q) foff[q] = (lane & 31) * 32 + (((2 * q + fh) ^ fsw) << 2);
         const int a_img = pp * (WBT * 32), b_img = V_FL + (pp * NT + nb * 32) * 32;
+        // W1 / 4 in MFMA operand order, [chunk][N / 32][quarter][lane] float4 (ddk_pack_conv_skip_weight_wino): 4 loads of 1 KiB per chunk
+        // and wave.  Chunk 0 here, chunk c + 1 in stage 3 of chunk c in FRONT of that stage's U pieces: the counted waits below
+        // (wait_vmcnt<LPM> = "all but my last LPM operations") then cover these loads too -- they are older than the pieces the count
+        // leaves in flight -- so the existing counts hold unchanged, and the registers are complete one stage before their first use.
+        const float* w1p = nullptr;
+        auto load_w1 = [&](int chunk) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(w1[q]) : "v"(w1p + ((long long)chunk * (p.N >> 5) * 4 + q) * 256) : "memory");
+        };
+        auto pin_w1 = [&] {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) asm volatile("" : "+v"(w1[q]));
+        };
+        if constexpr (SK) {
+            w1p = p.sk_w + ((long long)((n0 >> 5) + nb) * 4 * 64 + lane) * 4;
+            load_w1(c_begin);
+        }
         if (G::LPM > 0 && !(DBG & 4)) {
             issue_u(0, 0, 4 * G::LPL + wid * G::LPM, std::integral_constant<int, G::LPM>{});
             issue_u(1, 1, 4 * G::LPL + wid * G::LPM, std::integral_constant<int, G::LPM>{});
             wait_vmcnt<G::LPM>();                                           // U(0); its pieces of U(1) land before B(1)
         }
+        if constexpr (SK) { if (G::LPM == 0) wait_vmcnt<0>(); pin_w1(); }
         __builtin_amdgcn_s_barrier();                                       // B0: stages 0, 1 complete
         unsigned long long r_loop0 = 0, c_wait = 0, c_mma = 0;
         if (DBG) r_loop0 = __builtin_amdgcn_s_memrealtime();
@@ -297,8 +333,8 @@ __global__ __launch_bounds__(768) void conv3x3_wino2_kernel(const WinoParams p) 
         //     with (S, q2).  The two waves of a SIMD so never reach their LDS bursts, their exposed waits and the barrier in lockstep,
         //     and the pipe has the deferred quarter to run while waves 0..3 wait for their first fragments (profiles/r04_wino_clock.txt:
         //     unstaggered, waves 0..3 arrived at the barrier 700 cycles before their partners, with the pipe 26 % idle before that).
-        auto mloop = [&](auto stgc) {
-            constexpr bool STG = decltype(stgc)::value;
+        auto mloop = [&](auto stgc, auto skc) {
+            constexpr bool STG = decltype(stgc)::value, SKW = decltype(skc)::value;
             float4 a[2], b[2];
             int buf = 0, S = 0;
             auto frag = [&](float4& av, float4& bv, const float* As, const float* Bs, int q) {
@@ -316,6 +352,21 @@ __global__ __launch_bounds__(768) void conv3x3_wino2_kernel(const WinoParams p) 
             for (int c = 0; c < n_chunks; ++c) {
                 static_for<SPC>([&](auto sc) {
                     constexpr int s = decltype(sc)::value;
+                    // SKW: quarter q of stage st in {1, 2} also goes into sk[st - 1], against W1 fragment q
+                    auto skq = [&](auto stc, auto qc, const float4& av) {
+                        constexpr int st = decltype(stc)::value, q = decltype(qc)::value;
+                        if constexpr (SKW && (st == 1 || st == 2))
+                            mma4(sk[st - 1], av, make_float4(w1[q].x, w1[q].y, w1[q].z, w1[q].w));
+                    };
+                    using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
+                    using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
+                    using IS = std::integral_constant<int, s>; using IP = std::integral_constant<int, (s + SPC - 1) % SPC>;
+                    auto next_w1 = [&] {        // next chunk's fragments (the last chunk reloads its own: no branch joins the registers)
+                        if constexpr (SKW && s == SPC - 1) {
+                            __builtin_amdgcn_sched_barrier(0);
+                            load_w1(c_begin + (c + 1 < n_chunks ? c + 1 : c));
+                        }
+                    };
                     const float* As = smem + buf * STAGE + a_img;
                     const float* Bs = smem + buf * STAGE + b_img;
                     const int nbuf = buf == 2 ? 0 : buf + 1, pbuf = buf == 0 ? 2 : buf - 1;
@@ -332,34 +383,45 @@ __global__ __launch_bounds__(768) void conv3x3_wino2_kernel(const WinoParams p) 
                         frag(a[1], b[1], As, Bs, 1);
                         __builtin_amdgcn_sched_barrier(0);
                         mma4(acc[s], a[0], b[0]);
+                        skq(IS{}, I0{}, a[0]);
                         frag(a[0], b[0], As, Bs, 2);
                         __builtin_amdgcn_sched_barrier(0);
                         mma4(acc[s], a[1], b[1]);
+                        skq(IS{}, I1{}, a[1]);
+                        next_w1();
                         dma();
                         frag(a[1], b[1], As, Bs, 3);
                         __builtin_amdgcn_sched_barrier(0);
                         mma4(acc[s], a[0], b[0]);
+                        skq(IS{}, I2{}, a[0]);
                         a[0] = *reinterpret_cast<const float4*>(smem + nbuf * STAGE + a_img + foff[0]);     // V of stage S+1: complete since B(S)
                         __builtin_amdgcn_sched_barrier(0);
                         mma4(acc[s], a[1], b[1]);
+                        skq(IS{}, I3{}, a[1]);
                     } else {
                         if (s > 0 || c > 0) {                                    // the deferred quarter (S-1, q3); [1] <- (S, q0)
                             frag(a[1], b[1], As, Bs, 0);
                             __builtin_amdgcn_sched_barrier(0);
                             mma4(acc[(s + SPC - 1) % SPC], a[0], b[0]);
+                            skq(IP{}, I3{}, a[0]);
                         }
                         frag(a[0], b[0], As, Bs, 1);
                         __builtin_amdgcn_sched_barrier(0);
                         mma4(acc[s], a[1], b[1]);
+                        skq(IS{}, I0{}, a[1]);
+                        next_w1();                                               // (behind the deferred quarter, the last reader of w1[3])
                         dma();
                         frag(a[1], b[1], As, Bs, 2);
                         __builtin_amdgcn_sched_barrier(0);
                         mma4(acc[s], a[0], b[0]);
+                        skq(IS{}, I1{}, a[0]);
                         frag(a[0], b[0], As, Bs, 3);                             // kept across the barrier
                         __builtin_amdgcn_sched_barrier(0);
                         mma4(acc[s], a[1], b[1]);
+                        skq(IS{}, I2{}, a[1]);
                     }
                     if (more && !(DBG & 4)) wait_vmcnt<G::LPM>(); else wait_vmcnt<0>();       // my pieces of U(S+1), issued during stage S-1, have landed
+                    if constexpr (SKW && s == SPC - 1) pin_w1();                // ... and the W1 fragments requested in front of this stage's pieces
                     unsigned long long tA = 0, tB = 0;
                     if (DBG) { asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tA)::"memory"); }
                     __builtin_amdgcn_s_barrier();                               // B(S+1): stage S released; V <= S+2, U <= S+1 complete
@@ -374,7 +436,12 @@ __global__ __launch_bounds__(768) void conv3x3_wino2_kernel(const WinoParams p) 
             }
             if (STG) mma4(acc[SPC - 1], a[0], b[0]);                             // the last stage's deferred quarter
         };
-        if (W2_STAGGER && wid >= 4) mloop(std::true_type{}); else mloop(std::false_type{});
+        if constexpr (SK) {
+            if (skw) { if (W2_STAGGER && wid >= 4) mloop(std::true_type{}, std::true_type{}); else mloop(std::false_type{}, std::true_type{}); }
+            else { if (W2_STAGGER && wid >= 4) mloop(std::true_type{}, std::false_type{}); else mloop(std::false_type{}, std::false_type{}); }
+        } else {
+            if (W2_STAGGER && wid >= 4) mloop(std::true_type{}, std::false_type{}); else mloop(std::false_type{}, std::false_type{});
+        }
         if (DBG && lane == 0 && wid == 0) {
             const int wg = (blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z)) & 1023;
             unsigned long long tE;
@@ -402,6 +469,15 @@ __global__ __launch_bounds__(768) void conv3x3_wino2_kernel(const WinoParams p) 
                 const float m0 = acc[0][r], m1 = acc[1][r], m2 = acc[2][r], m3 = acc[3][r];
                 Ts[row * TP + col] = (m0 + m1) + m2;
                 Ts[(WBT + row) * TP + col] = (m1 - m2) - m3;
+                if constexpr (SK) {
+                    // rows of the Hadamard transform back: pp = 1 holds S5, S9, pp = 2 holds S6, S10; output row a = 0: S(4 + pp) - S(8 + pp),
+                    // a = 1: their sum.  Two blocks behind the conv's staging area and its GroupNorm scratch.
+                    if (skw) {
+                        float* Ks = smem + G::T_FL + 320 + (pp - 1) * (2 * WBT * TP);
+                        Ks[row * TP + col] = sk[0][r] - sk[1][r];
+                        Ks[(WBT + row) * TP + col] = sk[0][r] + sk[1][r];
+                    }
+                }
             } else {
                 const float l0 = acc[0][r], l1 = acc[2][r], l2 = acc[4][r], l3 = acc[6][r];      // column pp     (h = 0)
                 const float h0 = acc[1][r], h1 = acc[3][r], h2 = acc[5][r], h3 = acc[7][r];      // column pp + 2 (h = 1)
@@ -431,6 +507,7 @@ __global__ __launch_bounds__(768) void conv3x3_wino2_kernel(const WinoParams p) 
     const bool direct = p.splits == 1 || (CLS && !partner);
     float* outp = p.splits == 1 ? p.out : CLS ? p.cl_slab + (long long)(split - 1) * p.slab_stride : p.out + (long long)split * p.slab_stride;
     float4 keep[ITEMS][2];
+    float4 sz[ITEMS][2];                   // SK: the skip tile (only the hand-off's finishing workgroup reads it again)
     long long oo[ITEMS];
     int opix[ITEMS];                       // pixel index of an item's first output (the second is the next pixel of the row)
     const int cq = tid & (QUADS - 1);
@@ -464,6 +541,31 @@ __global__ __launch_bounds__(768) void conv3x3_wino2_kernel(const WinoParams p) 
         const long long o0 = ((((long long)bq * p.H + 2 * ty + a) * p.W) + 2 * tx) * p.N + gn;
         oo[it] = o0;
         opix[it] = ((int)bq * p.H + 2 * ty + a) * p.W + 2 * tx;
+        if constexpr (SK) {
+            // the skip conv's two pixels of this item: columns of the Hadamard transform back, y(a, 0) = R1 - R2, y(a, 1) = R1 + R2
+            const float* kp = smem + G::T_FL + 320 + (a * WBT + t) * TP + cq * 4;
+            const float4 k1 = *reinterpret_cast<const float4*>(kp);
+            const float4 k2 = *reinterpret_cast<const float4*>(kp + 2 * WBT * TP);
+            float4 z0 = f4sub(k1, k2), z1 = f4add(k1, k2);
+            if (direct && p.sk_bias) {
+                const float4 bb = *reinterpret_cast<const float4*>(p.sk_bias + gn);
+                z0 = f4add(z0, bb);
+                z1 = f4add(z1, bb);
+            }
+            // like the conv tile: the result, a slab of partial sums (host: sk_out is then the skip slab area), or -- partner hand-off --
+            // a partial tile behind the conv partials of cl_slab, summed by the tile's first workgroup below
+            if (!CLS || p.splits == 1) {
+                float* so = p.splits == 1 ? p.sk_out : p.sk_out + (long long)split * p.sk_stride;
+                *reinterpret_cast<float4*>(so + o0) = z0;
+                *reinterpret_cast<float4*>(so + o0 + p.N) = z1;
+            } else if (partner) {
+                float* so = p.cl_slab + (long long)(p.splits - 1 + split - 1) * p.slab_stride;
+                st_sc1_f4(so + o0, z0);
+                st_sc1_f4(so + o0 + p.N, z1);
+            }
+            sz[it][0] = z0;
+            sz[it][1] = z1;
+        }
         if (direct) {
             if (p.bias) {
                 const float4 bb = *reinterpret_cast<const float4*>(p.bias + gn);
@@ -522,6 +624,27 @@ __global__ __launch_bounds__(768) void conv3x3_wino2_kernel(const WinoParams p) 
         if (pair_poisoned) {
 #pragma unroll
             for (int it = 0; it < ITEMS; ++it) keep[it][0].x = __builtin_nanf("");
+        }
+        if constexpr (SK) {
+            // the partners' skip partials, in split order like the conv's; a give-up poisons this tile too
+            for (int s = 1; s < p.splits; ++s) {
+                const float* sl = p.cl_slab + (long long)(p.splits - 1 + s - 1) * p.slab_stride;
+#pragma unroll
+                for (int it = 0; it < ITEMS; it += 2) {
+                    float4 a0, a1, b0, b1;
+                    ld_sc1_f4x4(a0, a1, b0, b1, sl + oo[it], sl + oo[it] + p.N, sl + oo[it + 1], sl + oo[it + 1] + p.N);
+                    sz[it][0] = f4add(sz[it][0], a0);
+                    sz[it][1] = f4add(sz[it][1], a1);
+                    sz[it + 1][0] = f4add(sz[it + 1][0], b0);
+                    sz[it + 1][1] = f4add(sz[it + 1][1], b1);
+                }
+            }
+#pragma unroll
+            for (int it = 0; it < ITEMS; ++it) {
+                if (pair_poisoned) sz[it][0].x = __builtin_nanf("");
+                *reinterpret_cast<float4*>(p.sk_out + oo[it]) = sz[it][0];
+                *reinterpret_cast<float4*>(p.sk_out + oo[it] + p.N) = sz[it][1];
+            }
         }
     }
     // ---- optional GroupNorm statistics of this tile (host: every m tile full and inside one image): per group {mean, M2 about that

@@ -170,6 +170,7 @@ int conv_splits(int kind, int B, int H, int W, int cin, int N);
 // conv_wino.hip
 bool conv_wino_ok(int kind, int H, int W, int cin, int N);
 int conv_wino_splits(int B, int H, int W, int cin, int N);
+bool conv_wino_skip_ok(int B, int H, int W, int cin, int N);   // the conv can carry a 1x1 skip conv of its input (ddk_conv_args.skip_out)
 int conv_wino_forward(const ddk_conv_args& a, int splits, hipStream_t st, const WinoGnFuse* fuse = nullptr);
 int conv_wino_cluster_np(int B, int H, int W, int cin, int N, int groups);    // m tiles per image when eligible, else 0
 int conv_wino_cluster_split_np(int B, int H, int W, int cin, int N, int groups, int* splits_out);   // the same for k-split shapes

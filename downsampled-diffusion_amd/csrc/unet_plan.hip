@@ -29,7 +29,8 @@ static inline int pad32(int c) { return (c + 31) / 32 * 32; }
 
 enum PackKind { PK_COPY = 0, PK_CONV = 1, PK_CONVT = 2, PK_LINEAR_T = 3, PK_WINO = 4, PK_LOCAL = 5, PK_WLOCAL = 6, PK_FIRST = 7, PK_CONVT_WINO = 8,
                 PK_ROWS = 9 /* [O][I] rows into rows of pitch ld */, PK_LOCAL1 = 10 /* a 1x1 filter in conv_local.hip's operand order */,
-                PK_CONVT_LOCAL = 11 /* a transpose-conv filter in the level chain's operand order */ };
+                PK_CONVT_LOCAL = 11 /* a transpose-conv filter in the level chain's operand order */,
+                PK_SKIP_WINO = 12 /* a res_conv's 1x1 filter as the skip-fold operand of the Winograd kernel */ };
 
 struct Slot {
     std::string name;
@@ -57,6 +58,8 @@ struct ConvW {
     bool has_wl1 = false;
     size_t wtl = 0;         // a transpose-conv filter in the level chain's operand order (CH_UPT); has_wtl
     bool has_wtl = false;
+    size_t wsk = 0;         // a res_conv's 1x1 filter / 4 in the Winograd kernel's operand order (the skip fold, DDK_OPT_SKIP_FOLD); has_wsk
+    bool has_wsk = false;
 };
 struct NormW { size_t g = 0, b = 0; int c_real = 0; };
 struct ResW {
@@ -137,6 +140,8 @@ struct ddk_unet {
     bool attn_split = true;                  // 16x16 / 8x8 maps: to_qkv + core in one launch, an (image, head) split over two workgroups that
                                              // exchange their context partials in the launch (DDK_OPT_ATTENTION_SPLIT) -- wherever the
                                              // in-launch GroupNorm may run; 0: the projection and linattn_small_kernel as two launches
+    bool skip_fold = true;                   // a ResnetBlock's res_conv computed inside its first 3x3 conv's Winograd launch where that conv runs
+                                             // on the 64-channel tile (DDK_OPT_SKIP_FOLD; conv_wino_skip_ok)
     bool fold_down_reduce = false;           // Downsample conv's split-K slabs summed by the image-local ResnetBlock behind it (no reduce launch).
                                              // OFF by default: measured 6 us per step SLOWER (each of an image's eight workgroups re-sums the slabs:
                                              // +6.3 / +5.9 us on the two consumers against reduce launches of 5.2 / 4.9 us; tools/fold_ab.py)
@@ -278,6 +283,12 @@ struct ddk_unet {
         r.n2 = add_norm(p + "block2.block.1.weight", p + "block2.block.1.bias", co);
         r.has_res = ci != co;
         if (r.has_res) r.res = add_conv(p + "res_conv.", co, ci, 1, true, false, split);
+        if (r.has_res && !generic && r.c1.has_wu && r.res.cin_pad == ci) {
+            // the same tensor also as the operand of the skip fold, next to the Winograd copy of the 3x3 conv it rides on
+            r.res.wsk = alloc((size_t)co * r.res.cin_pad);
+            r.res.has_wsk = true;
+            slots.push_back(Slot{p + "res_conv.weight", (long long)co * ci, PK_SKIP_WINO, r.res.wsk, co, ci, 1, 1, r.res.cin_pad, 0, 0});
+        }
         return r;
     }
     int n_attn = 0;
@@ -472,6 +483,7 @@ extern "C" int ddk_unet_set_option(ddk_unet* u, int option, int value) {
         {DDK_OPT_FIRST_GROUPNORM, true, [](ddk_unet& p, int v) { p.first_gn = v != 0; }},
         {DDK_OPT_RESTORE_FUSED_TAIL, true, [](ddk_unet& p, int v) { p.restore_fused = v != 0; }},
         {DDK_OPT_ATTENTION_SPLIT, true, [](ddk_unet& p, int v) { p.attn_split = v != 0; }},
+        {DDK_OPT_SKIP_FOLD, true, [](ddk_unet& p, int v) { p.skip_fold = v != 0; }},
         // 0 off, 1 (default): the 4x4 level with its Downsample / Upsample convs, 2: the 4x4 level alone, 3: the 8x8 levels as well,
         // 4: the 8x8 levels only, 8 / 16: only downs[-2] / only ups[1]
         {DDK_OPT_LEVEL_CHAIN, true, [](ddk_unet& p, int v) {
@@ -583,6 +595,7 @@ extern "C" int ddk_unet_pack_slot(const ddk_unet* u, int slot, const float* cano
         case PK_WINO: rc = ddk_pack_conv_weight_wino(canonical, dst, sl.O, sl.I, sl.i_pad, s); break;
         case PK_LOCAL: rc = ddk_pack_conv_weight_local(canonical, dst, sl.O, sl.I, sl.i_pad, s); break;
         case PK_LOCAL1: rc = ddk_pack_conv1x1_weight_local(canonical, dst, sl.O, sl.I, sl.i_pad, s); break;
+        case PK_SKIP_WINO: rc = ddk_pack_conv_skip_weight_wino(canonical, dst, sl.O, sl.I, sl.i_pad, s); break;
         case PK_CONVT_LOCAL: rc = ddk_pack_convT_weight_local(canonical, dst, sl.I, sl.O, s); break;
         case PK_WLOCAL: rc = ddk_pack_conv_weight_wino_local(canonical, dst, sl.O, sl.I, sl.i_pad, s); break;
         case PK_FIRST: rc = ddk_pack_conv_weight_first(canonical, dst, sl.O, sl.I, s); break;
@@ -637,7 +650,8 @@ constexpr int CHAIN8_BUFS = 5;                // ... inside an 8x8 chain, [B][64
 static void res_sizes(const ResW& r, int B, int H, int W, Layout& ly) {
     const size_t M = (size_t)B * H * W;
     upd(ly.act, M * r.co);
-    upd(ly.splitk, conv3_ws_floats(r.c1, B, H, W, r.ci_pad, r.co));
+    // (a first conv that carries the skip fold keeps the skip conv's partial slabs behind its own: DDK_OPT_SKIP_FOLD)
+    upd(ly.splitk, (r.has_res && r.res.has_wsk ? 2 : 1) * conv3_ws_floats(r.c1, B, H, W, r.ci_pad, r.co));
     upd(ly.splitk, conv3_ws_floats(r.c2, B, H, W, r.co, r.co));
     if (r.has_res) upd(ly.splitk, conv_workspace_bytes(DDK_CONV1X1, B, H, W, r.ci_pad, r.co) / 4);
     upd(ly.gn_ws, groupnorm_workspace_bytes(B, H * W, r.co, GROUPS) / 4);
@@ -781,25 +795,46 @@ struct Ctx {
     }
 };
 
+// The skip fold's operands (ddk_conv_args.skip_*): a res_conv computed inside the 3x3 conv launch that reads the same input
+struct SkipFold {
+    const float* w = nullptr;
+    const float* b = nullptr;
+    float* out = nullptr;
+    bool want_slabs = false;    // where the conv leaves split-K slabs for its GroupNorm (CG_SLABS), leave the skip partials as slabs too,
+                                // behind the conv's in the workspace: the caller has a reader that sums them (+ bias)
+    mutable int left = 0;       // > 1: that many skip slabs were left there and `out` is unwritten
+    void put(ddk_conv_args& a) const { a.skip_weight = w; a.skip_bias = b; a.skip_out = out; }
+};
 static int run_conv(Ctx& c, int kind, const ConvW& cw, const float* src0, int c0, const float* src1, int c1, const float* resid,
-                    float* out, int H, int W, int N, const float* weight_override = nullptr, const ConvLnFold* ln = nullptr) {
+                    float* out, int H, int W, int N, const float* weight_override = nullptr, const ConvLnFold* ln = nullptr,
+                    const SkipFold& sk = SkipFold()) {
     ddk_conv_args a = c.conv_args(kind, cw, src0, c0, src1, c1, out, H, W, N, weight_override);
     a.resid = resid;
+    sk.put(a);
     return conv_forward(a, c.st, ln);
 }
 // ... leaving its `splits` split-K slabs in the workspace (`out` is not written) for a reader that sums them and adds the bias: `left`
 static int run_conv_slabs(Ctx& c, int kind, const ConvW& cw, const float* src0, int c0, const float* src1, int c1, float* out, int H, int W, int N,
-                          int splits, AddendSlabs& left) {
+                          int splits, AddendSlabs& left, const SkipFold& sk = SkipFold()) {
     ddk_conv_args a = c.conv_args(kind, cw, src0, c0, src1, c1, out, H, W, N);
     a.bias = nullptr;
     a.defer_reduce = 1;
+    sk.put(a);
+    if (sk.out && sk.want_slabs) {
+        const long long slab = (long long)c.B * H * W * N;
+        a.skip_out = c.W + c.ly.off_splitk + (long long)splits * slab;
+        a.skip_slab_stride = slab;
+        sk.left = splits;
+    }
     const int s = kind == DDK_CONV3X3_S2 ? 2 : 1;
     left = AddendSlabs{splits, (long long)c.B * (H / s) * (W / s) * N, cw.has_bias ? c.P + cw.b : nullptr};
     return conv_forward(a, c.st);
 }
 // ... as a one-pass Winograd conv whose epilogue leaves per-tile {mean, M2} in the GroupNorm area (shapes with conv_wino_stats_parts() > 0)
-static int run_conv_parts(Ctx& c, const ConvW& cw, const float* src0, int c0, const float* src1, int c1, float* raw, int H, int W, int N) {
+static int run_conv_parts(Ctx& c, const ConvW& cw, const float* src0, int c0, const float* src1, int c1, float* raw, int H, int W, int N,
+                          const SkipFold& sk = SkipFold()) {
     ddk_conv_args a = c.conv_args(DDK_CONV3X3_S1, cw, src0, c0, src1, c1, raw, H, W, N);
+    sk.put(a);
     a.gn_partials = c.W + c.ly.off_gn;
     a.gn_groups = GROUPS;
     return conv_forward(a, c.st);
@@ -862,9 +897,12 @@ static bool conv_gn_is_local(const ddk_unet& u, const ConvW& cw, int B, int H, i
 
 static int run_conv_gn(Ctx& c, const ConvW& cw, const float* src0, int c0, const float* src1, int c1, float* raw, const NormW& n,
                        const float* temb, const float* addend, float* out, int H, int W, int N, const AddendSlabs& as = AddendSlabs(),
-                       const AddendSlabs& ss = AddendSlabs()) {
+                       const AddendSlabs& ss = AddendSlabs(), const SkipFold& sk = SkipFold()) {
     const ConvGnChoice k = classify_conv_gn(c.u, cw, c.B, H, W, c0, c1, N, c.x_first && src0 == c.x_padded && !src1,
                                             c.allow_cluster && c.n_cluster < c.u.cluster_limit, c.ly.splitk);
+    // (res_folds_skip admits exactly the shapes whose every choice here is one of these Winograd forms)
+    if (sk.out && !(k.wino && (k.path == CG_CLUSTER || k.path == CG_CLUSTER_SPLIT || k.path == CG_PARTS || k.path == CG_SLABS || k.path == CG_PLAIN)))
+        return fail_arg("run_conv_gn: skip fold on a path that cannot carry it");
     if (ss.n > 1 && !k.local()) return fail_arg("run_conv_gn: slab source on a path that cannot sum it");
     if (as.n > 1 && !k.local())
         return fail_arg(k.path == CG_GENERIC ? "run_conv_gn: slab addend / source on the generic path"
@@ -888,21 +926,22 @@ static int run_conv_gn(Ctx& c, const ConvW& cw, const float* src0, int c0, const
             ++c.n_cluster;
             ddk_conv_args a = c.conv_args(DDK_CONV3X3_S1, cw, src0, c0, src1, c1, out, H, W, N);
             a.resid = addend;
+            sk.put(a);
             WinoGnFuse f = c.gn_fuse(n, temb, c.temb_rows);
             if (k.path == CG_CLUSTER_SPLIT) f.pairs = reinterpret_cast<unsigned*>(c.W + c.ly.off_cl + cl_pair_offset(c.B));
             return conv_forward(a, c.st, nullptr, &f);
         }
         case CG_PARTS:
-            DDK_TRY(run_conv_parts(c, cw, src0, c0, src1, c1, raw, H, W, N));
+            DDK_TRY(run_conv_parts(c, cw, src0, c0, src1, c1, raw, H, W, N, sk));
             return groupnorm_mish_parts(raw, gnp, k.np, g, b, temb, c.u.temb_total, addend, out, c.B, H * W, N, GROUPS, GN_EPS, c.st, c.temb_rows);
         case CG_SLABS: {
             AddendSlabs sl;
-            DDK_TRY(run_conv_slabs(c, DDK_CONV3X3_S1, cw, src0, c0, src1, c1, raw, H, W, N, k.splits, sl));
+            DDK_TRY(run_conv_slabs(c, DDK_CONV3X3_S1, cw, src0, c0, src1, c1, raw, H, W, N, k.splits, sl, sk));
             return groupnorm_mish_ex(c.W + c.ly.off_splitk, sl.n, sl.stride, sl.bias, g, b, temb, c.u.temb_total, addend, out, c.B, H * W, N,
                                      GROUPS, GN_EPS, nullptr, 0, c.st, c.temb_rows);
         }
         case CG_PLAIN:
-            DDK_TRY(run_conv(c, DDK_CONV3X3_S1, cw, src0, c0, src1, c1, nullptr, raw, H, W, N));
+            DDK_TRY(run_conv(c, DDK_CONV3X3_S1, cw, src0, c0, src1, c1, nullptr, raw, H, W, N, nullptr, nullptr, sk));
             break;
     }
     return groupnorm_mish(raw, g, b, temb, c.u.temb_total, addend, out, c.B, H * W, N, GROUPS, GN_EPS, gnp, c.ly.gn_ws * sizeof(float), c.st,
@@ -914,6 +953,15 @@ static int run_conv_gn(Ctx& c, const ConvW& cw, const float* src0, int c0, const
 // Block's staging loop and the second Block's residual -- sum the slabs (+ that conv's bias) in splitk_reduce_kernel's order
 static bool res_takes_slab_source(const ddk_unet& u, const ResW& r, int B, int H, int W, int c0) {
     return !u.generic && !r.has_res && conv_gn_is_local(u, r.c1, B, H, W, c0, 0, r.co) && conv_gn_is_local(u, r.c2, B, H, W, r.co, 0, r.co);
+}
+
+// The skip fold (DDK_OPT_SKIP_FOLD): the block's first conv is a Winograd launch on the 64-channel tile, whichever of its GroupNorm
+// forms it takes (in-launch, with or without the partner hand-off; partials; slabs; plain).  Shape and kernel decide, not whether this
+// call may exchange in the launch: the sampler, ddk_unet_forward and a step loop over it run the same arithmetic.
+static bool res_folds_skip(const Ctx& c, const ResW& r, const float* src0, int c0, const float* src1, int c1, int H, int W) {
+    if (!r.has_res || !c.u.skip_fold || !r.res.has_wsk || c.u.generic || r.res.cin_pad != c0 + c1) return false;
+    const ConvGnChoice k = classify_conv_gn(c.u, r.c1, c.B, H, W, c0, c1, r.co, c.x_first && src0 == c.x_padded && !src1, false, 0);
+    return k.wino && (k.path == CG_PARTS || k.path == CG_SLABS || k.path == CG_PLAIN) && conv_wino_skip_ok(c.B, H, W, c0 + c1, r.co);
 }
 
 static int run_res(Ctx& c, const ResW& r, const float* src0, int c0, const float* src1, int c1, float* out, int H, int W,
@@ -928,7 +976,13 @@ static int run_res(Ctx& c, const ResW& r, const float* src0, int c0, const float
         if (r.has_res || src1) return fail_arg("run_res: slab source with a skip conv or a second source");
         as = ss;
     }
-    if (r.has_res) {
+    SkipFold sk;
+    if (res_folds_skip(c, r, src0, c0, src1, c1, H, W)) {
+        sk.w = c.P + r.res.wsk; sk.b = r.res.has_bias ? c.P + r.res.b : nullptr; sk.out = res;
+        // an image-local second Block sums an addend in slab form and leaves the split-K workspace alone: skip slabs can wait for it
+        sk.want_slabs = conv_gn_is_local(c.u, r.c2, c.B, H, W, r.co, 0, r.co);
+        addend = res;
+    } else if (r.has_res) {
         const int rs = conv_splits(DDK_CONV1X1, c.B, H, W, c0 + c1, r.co);
         if (rs > 1 && !conv1x1_sm_ok((long long)c.B * H * W, c0, c1, r.co) && conv_gn_is_local(c.u, r.c1, c.B, H, W, c0, c1, r.co) &&
             conv_gn_is_local(c.u, r.c2, c.B, H, W, r.co, 0, r.co)) {
@@ -941,7 +995,12 @@ static int run_res(Ctx& c, const ResW& r, const float* src0, int c0, const float
             addend = res;
         }
     }
-    DDK_TRY(run_conv_gn(c, r.c1, src0, c0, src1, c1, raw, r.n1, c.temb + r.temb_off, nullptr, a1, H, W, r.co, AddendSlabs(), ss));
+    DDK_TRY(run_conv_gn(c, r.c1, src0, c0, src1, c1, raw, r.n1, c.temb + r.temb_off, nullptr, a1, H, W, r.co, AddendSlabs(), ss, sk));
+    if (sk.left > 1) {
+        const long long slab = (long long)c.B * H * W * r.co;
+        as = AddendSlabs{sk.left, slab, sk.b};
+        addend = c.W + c.ly.off_splitk + (long long)sk.left * slab;
+    }
     return run_conv_gn(c, r.c2, a1, r.co, nullptr, 0, raw, r.n2, nullptr, addend, out, H, W, r.co, as);
 }
 

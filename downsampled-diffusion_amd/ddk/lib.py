@@ -28,6 +28,7 @@ class ConvArgs(C.Structure):
         ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("N", C.c_int), ("pre_mish", C.c_int), ("post_mish", C.c_int), ("defer_reduce", C.c_int),
         ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("weight_wino", C.c_void_p),
         ("gn_partials", C.c_void_p), ("gn_groups", C.c_int), ("mish_out", C.c_void_p), ("dmish_src", C.c_void_p),
+        ("skip_weight", C.c_void_p), ("skip_bias", C.c_void_p), ("skip_out", C.c_void_p), ("skip_slab_stride", C.c_longlong),
     ]
 
 
@@ -102,6 +103,8 @@ SIGNATURES = {
     "ddk_pack_conv_weight_wino": (_I, [_P, _P, _I, _I, _I, _P]),
     "ddk_pack_conv_weight_wino_dgrad": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "ddk_conv_wino_splits": (_I, [_I, _I, _I, _I, _I]),
+    "ddk_pack_conv_skip_weight_wino": (_I, [_P, _P, _I, _I, _I, _P]),
+    "ddk_conv_wino_skip_ok": (_I, [_I, _I, _I, _I, _I]),
     "ddk_pack_convT_weight_wino": (_I, [_P, _P, _I, _I, _I, _P]),
     "ddk_convT_wino_splits": (_I, [_I, _I, _I, _I, _I]),
     "ddk_conv_gn_partials": (_I, [_I, _I, _I, _I, _I, _I]),
@@ -207,6 +210,7 @@ SIGNATURES = {
     "ddk_conv3x3_gn_mish_cluster_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "ddk_conv3x3_gn_mish_cluster_split_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I, _I]),
     "ddk_conv3x3_gn_mish_cluster": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _P, _SZ, _P]),
+    "ddk_conv3x3_gn_mish_cluster_skip": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _P, _SZ, _P, _P, _P, _P]),
     "ddk_unet_set_option": (_I, [_P, _I, _I]),
     "ddk_debug_cluster_timeouts": (C.c_uint, []),
     "ddk_conv3x3_gn_mish_cluster_check": (_I, [_P, _I, _P]),

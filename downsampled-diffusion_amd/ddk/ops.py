@@ -212,6 +212,18 @@ def pack_conv_weight_wino(w):
     return out
 
 
+def pack_conv_skip_weight_wino(w):
+    """1x1 weight [O, I] (or [O, I, 1, 1]) of a res_conv -> the skip-fold operand of the Winograd kernel, W / 4 in MFMA operand order
+    [pad32(I)/32][O/32][4][64][4] (ddk_pack_conv_skip_weight_wino); pass as conv(..., skip_w=...)."""
+    o, i = w.shape[0], w.shape[1]
+    if w.numel() != o * i or o % 32:
+        raise L.DDKError("pack_conv_skip_weight_wino: a 1x1 filter with O % 32 == 0")
+    out = torch.empty((pad32(i) // 32, o // 32, 4, 64, 4), device=w.device, dtype=torch.float32)
+    L.check(L.load().ddk_pack_conv_skip_weight_wino(L.ptr(_f32(w.contiguous())), L.ptr(out), o, i, pad32(i), L.stream()),
+            "pack_conv_skip_weight_wino")
+    return out
+
+
 def pack_convT_weight_wino(w):
     """ConvTranspose2d weight (I, O, 4, 4) -> Winograd F(2x2, 2x2) filters per output phase [4][pad32(I)/32][9][O][32]
     (ddk_pack_convT_weight_wino); pass as conv(CONVT4X4_S2, ..., w_wino=...)."""
@@ -271,8 +283,11 @@ def wino_weight(weight, x_shape, c_lo=None, c_hi=None, dgrad=False):
 
 # ------------------------------------------------------------------ conv family
 def conv(kind, x, w_packed, bias=None, n_out=None, x2=None, resid=None, pre_mish=False, post_mish=False, w_wino=None, mish_out=None,
-         dmish_src=None, leave_slabs=False):
+         dmish_src=None, leave_slabs=False, skip_w=None, skip_bias=None, skip_out=None, out=None):
     """Implicit-GEMM conv on NHWC x (optionally channel-concatenated with x2 without materialising it).
+    skip_w (pack_conv_skip_weight_wino; shapes with ddk_conv_wino_skip_ok only, with w_wino): the launch also computes the 1x1 conv of
+    the same input with that weight (+ skip_bias) -- returns (out, skip); skip_out: the tensor that receives it (else a new one).
+    out: the tensor to write into (else a new one).
     w_wino: the same 3x3 filter in the Winograd domain -> the F(2x2,3x3) kernel runs when the shape is eligible.
     mish_out: tensor that also receives Mish(out); dmish_src: out = (conv + bias) * Mish'(dmish_src) (+ resid) (ddk_conv_args).
     leave_slabs (plain convs only: no resid / Mish): returns (out, slabs) -- when the launch splits k, `slabs` [S,B,Ho,Wo,N] holds the
@@ -289,7 +304,8 @@ def conv(kind, x, w_packed, bias=None, n_out=None, x2=None, resid=None, pre_mish
         ho, wo = h // 2, w_ // 2
     else:
         ho, wo = h, w_
-    out = torch.empty((b, ho, wo, n), device=x.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty((b, ho, wo, n), device=x.device, dtype=torch.float32)
     lib = L.load()
     ws_bytes = lib.ddk_conv_workspace_bytes(kind, b, h, w_, c0 + c1, n)
     if mish_out is not None or dmish_src is not None:
@@ -299,6 +315,8 @@ def conv(kind, x, w_packed, bias=None, n_out=None, x2=None, resid=None, pre_mish
         wsplits = lib.ddk_conv_wino_splits(b, h, w_, c0 + c1, n)
         if wsplits > 0:
             ws_bytes = wsplits * out.numel() * 4 if wsplits > 1 else 0
+            if skip_w is not None:
+                ws_bytes *= 2                           # the skip conv's slabs follow the conv's
     nslab = 1
     if leave_slabs:
         if resid is not None or pre_mish or post_mish or mish_out is not None or dmish_src is not None:
@@ -310,7 +328,15 @@ def conv(kind, x, w_packed, bias=None, n_out=None, x2=None, resid=None, pre_mish
     a = L.ConvArgs(kind, L.ptr(_f32(x)), L.ptr(x2), c0, c1, L.ptr(w_packed), L.ptr(bias), L.ptr(resid), L.ptr(out),
                    b, h, w_, n, int(pre_mish), int(post_mish), int(leave_slabs and nslab > 1), L.ptr(ws), ws_bytes, L.ptr(w_wino), None, 0,
                    L.ptr(mish_out), L.ptr(dmish_src))
+    if skip_w is not None:
+        if skip_out is None:
+            skip_out = torch.empty((b, ho, wo, n), device=x.device, dtype=torch.float32)
+        a.skip_weight, a.skip_bias, a.skip_out = L.ptr(skip_w), L.ptr(skip_bias), L.ptr(skip_out)
+        if wsplits > 1 and leave_slabs:
+            raise L.DDKError("conv(skip_w): not with leave_slabs")
     L.check(lib.ddk_conv_forward(C.byref(a), L.stream()), "conv_forward")
+    if skip_w is not None:
+        return out, skip_out
     if leave_slabs:
         return out, (ws[:nslab * out.numel()].view(nslab, b, ho, wo, n) if nslab > 1 else None)
     return out
@@ -469,11 +495,14 @@ def final_tail(raw, part, tiles_per_image, gamma, beta, w, bias, x=None, t=None,
     return eps_out
 
 
-def conv3x3_gn_mish_cluster(x, w_wino, bias, gamma, beta, x2=None, temb=None, addend=None, groups=GN_GROUPS, eps=GN_EPS, check=True):
+def conv3x3_gn_mish_cluster(x, w_wino, bias, gamma, beta, x2=None, temb=None, addend=None, groups=GN_GROUPS, eps=GN_EPS, check=True,
+                            skip_w=None, skip_bias=None, skip_out=None, out=None):
     """Block (conv3x3 + GroupNorm + Mish + shift + residual) in ONE Winograd launch whose workgroups exchange tile statistics
     (ddk_conv3x3_gn_mish_cluster); raises when the shape or the device is not eligible.  check=True (default) waits for the
     stream and raises DDKError when an exchange timed out (shared GPU): the output then holds NaN tiles and must not be used;
-    timing loops pass check=False and call cluster_check() once at their end."""
+    timing loops pass check=False and call cluster_check() once at their end.
+    skip_w (pack_conv_skip_weight_wino; ddk_conv_wino_skip_ok shapes): the launch also writes the 1x1 conv of the same input
+    (+ skip_bias) -> returns (out, skip).  out / skip_out: tensors to write into (else new ones)."""
     b, h, w_, c0 = x.shape
     c1 = 0 if x2 is None else x2.shape[-1]
     n = w_wino.shape[2]
@@ -482,15 +511,24 @@ def conv3x3_gn_mish_cluster(x, w_wino, bias, gamma, beta, x2=None, temb=None, ad
         raise L.DDKError(f"conv3x3_gn_mish_cluster: shape {tuple(x.shape)} (+{c1}) -> {n} not eligible")
     nbytes = max(lib.ddk_conv3x3_gn_mish_cluster_workspace_bytes(b, h, w_, n),
                  lib.ddk_conv3x3_gn_mish_cluster_split_workspace_bytes(b, h, w_, c0 + c1, n, groups))      # (the k-split kind of shape)
+    if skip_w is not None:
+        nbytes += max(lib.ddk_conv_wino_splits(b, h, w_, c0 + c1, n) - 1, 0) * b * h * w_ * n * 4     # the skip fold's partial tiles
     ws = _ws(x.device, nbytes, "cluster")
-    out = torch.empty((b, h, w_, n), device=x.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty((b, h, w_, n), device=x.device, dtype=torch.float32)
     stride = temb.stride(0) if temb is not None else 0
-    L.check(lib.ddk_conv3x3_gn_mish_cluster(L.ptr(_f32(x)), c0, L.ptr(x2), c1, L.ptr(w_wino), L.ptr(bias), L.ptr(gamma), L.ptr(beta),
-                                            temb.data_ptr() if temb is not None else None, stride, L.ptr(addend), L.ptr(out), b, h, w_, n,
-                                            groups, eps, L.ptr(ws), nbytes, L.stream()), "conv3x3_gn_mish_cluster")
+    args = (L.ptr(_f32(x)), c0, L.ptr(x2), c1, L.ptr(w_wino), L.ptr(bias), L.ptr(gamma), L.ptr(beta),
+            temb.data_ptr() if temb is not None else None, stride, L.ptr(addend), L.ptr(out), b, h, w_, n, groups, eps, L.ptr(ws), nbytes)
+    if skip_w is not None:
+        if skip_out is None:
+            skip_out = torch.empty((b, h, w_, n), device=x.device, dtype=torch.float32)
+        L.check(lib.ddk_conv3x3_gn_mish_cluster_skip(*args, L.ptr(skip_w), L.ptr(skip_bias), L.ptr(skip_out), L.stream()),
+                "conv3x3_gn_mish_cluster_skip")
+    else:
+        L.check(lib.ddk_conv3x3_gn_mish_cluster(*args, L.stream()), "conv3x3_gn_mish_cluster")
     if check:
         L.check(lib.ddk_conv3x3_gn_mish_cluster_check(L.ptr(ws), b, L.stream()), "conv3x3_gn_mish_cluster")
-    return out
+    return out if skip_w is None else (out, skip_out)
 
 
 def cluster_check(device, b):

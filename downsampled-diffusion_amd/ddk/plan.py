@@ -129,6 +129,7 @@ class UnetPlan:
     OPT_FIRST_GROUPNORM = 8
     OPT_RESTORE_FUSED_TAIL = 12
     OPT_ATTENTION_SPLIT = 13
+    OPT_SKIP_FOLD = 14
 
     def set_option(self, option, value):
         """ddk_unet_set_option: e.g. (OPT_CLUSTER_GROUPNORM, 0) keeps conv + GroupNorm-apply as two launches

@@ -99,10 +99,29 @@ typedef struct ddk_conv_args {
                           * while `out` keeps the pre-activation its backward needs (training path of convblocks.py:112-130) */
     const float* dmish_src; /* optional [B][Ho][Wo][N]: out = (conv + bias) * Mish'(dmish_src) (+ resid): an input-gradient conv that
                              * hands back the gradient of the PRE-activation (replaces a separate Mish-backward launch) */
+    /* optional skip fold (Winograd path, ddk_conv_wino_skip_ok() == 1, no post_mish): the launch also writes the 1x1 conv of the SAME
+     * input (a ResnetBlock's res_conv, blocks.py:103) -- skip_out [B][H][W][N] = skip_weight . x + skip_bias -- from the Winograd
+     * input transform it has in LDS anyway: no second read of x, no second launch.  skip_weight is packed by
+     * ddk_pack_conv_skip_weight_wino; skip_bias [N] or NULL.  `out` is bit-identical with and without it.
+     * Where the conv splits its channel chunks (ddk_conv_wino_splits() > 1) the skip conv is a sum of partial tiles like the conv:
+     * `workspace` then takes 2 * splits * B*H*W*N floats (the skip slabs follow the conv's; the call sums them into skip_out) --
+     * or, with skip_slab_stride > 0 (>= B*H*W*N floats, a multiple of 4), skip_out IS a slab area [splits][skip_slab_stride] that
+     * receives the partial sums without the bias, for a reader that sums them (ddk_conv3x3_gn_mish_slabs' addend slabs), and
+     * `workspace` keeps its size. */
+    const float* skip_weight;
+    const float* skip_bias;
+    float* skip_out;
+    long long skip_slab_stride;
 } ddk_conv_args;
 
 /* Conv2d 3x3 weight OIHW -> Winograd-domain filter U = G g G^T, [I_pad/32][16 positions][O][32] (blocks.py:78). */
 int ddk_pack_conv_weight_wino(const float* w_oihw, float* dst, int O, int I, int i_pad, ddk_stream_t s);
+/* Conv2d 1x1 weight [O][I] of a ResnetBlock's res_conv -> ddk_conv_args.skip_weight: W / 4 in the MFMA operand order of the Winograd
+ * kernel, [i_pad/32][O/32][4][64][4] (O * i_pad floats; O % 32 == 0).  The input channels are those of the 3x3 conv it rides on,
+ * both sources of a concat in order (each a multiple of 32). */
+int ddk_pack_conv_skip_weight_wino(const float* w_oi, float* dst, int O, int I, int i_pad, ddk_stream_t s);
+/* 1: a 3x3 conv of this shape can carry the skip fold (a Winograd shape on the 64-channel tile) */
+int ddk_conv_wino_skip_ok(int B, int H, int W, int cin, int N);
 /* > 0: the Winograd kernel can emit GroupNorm partials for this shape (the value = 128-pixel tiles per image); 0: it cannot
  * (channel-chunk splits, ragged tiles, groups that straddle a 64-channel tile). */
 int ddk_conv_gn_partials(int B, int H, int W, int cin, int N, int groups);
@@ -212,6 +231,13 @@ int ddk_conv3x3_gn_mish_cluster(const float* src0, int c0, const float* src1, in
                                 const float* gamma, const float* beta, const float* temb, int temb_stride, const float* addend,
                                 float* out, int B, int H, int W, int N, int groups, float eps, void* workspace, size_t workspace_bytes,
                                 ddk_stream_t s);
+/* The same launch carrying the skip fold (ddk_conv_args.skip_weight / skip_bias / skip_out) on shapes with ddk_conv_wino_skip_ok():
+ * skip_out [B][H][W][N] receives the 1x1 conv of the (concatenated) input, `out` is what ddk_conv3x3_gn_mish_cluster writes.  A shape
+ * of the k-split kind needs (ddk_conv_wino_splits() - 1) * B*H*W*N floats more workspace than _split_workspace_bytes() says. */
+int ddk_conv3x3_gn_mish_cluster_skip(const float* src0, int c0, const float* src1, int c1, const float* weight_wino, const float* bias,
+                                     const float* gamma, const float* beta, const float* temb, int temb_stride, const float* addend,
+                                     float* out, int B, int H, int W, int N, int groups, float eps, void* workspace, size_t workspace_bytes,
+                                     const float* skip_weight, const float* skip_bias, float* skip_out, ddk_stream_t s);
 /* per-pixel channel LayerNorm, (x-mean)/(sqrt(var)+eps)*g+b, biased var (blocks.py:57-60). */
 int ddk_chan_layernorm(const float* x, const float* g, const float* b, float* out, long long M, int C,
                        float eps, ddk_stream_t s);
@@ -647,6 +673,11 @@ int ddk_unet_forward(const ddk_unet* u, const void* packed, const float* x, cons
  * (ddk_attention_split_from_x) wherever DDK_OPT_CLUSTER_GROUPNORM lets the in-launch exchanges run; 0 keeps the projection and the
  * core as two launches with the qkv tensor between them.  Same arithmetic up to summation order. */
 #define DDK_OPT_ATTENTION_SPLIT 13
+/* DDK_OPT_SKIP_FOLD (default 1): where a ResnetBlock has a res_conv and its first 3x3 conv runs as a one-pass Winograd launch on the
+ * 64-channel tile (ddk_conv_wino_skip_ok), that launch computes the 1x1 skip conv as well (ddk_conv_args.skip_out): one launch and one
+ * read of the block's input fewer.  The choice depends on the shape alone, so ddk_unet_forward and ddk_sampler_run agree; 0 keeps the
+ * 1x1 launch.  Same result up to fp32 summation order of the skip conv. */
+#define DDK_OPT_SKIP_FOLD 14
 int ddk_unet_set_option(ddk_unet* u, int option, int value);
 /* Waits for `s`, then reads and clears the sticky give-up count of the launches issued on `workspace` (a ddk_unet_forward or
  * ddk_sampler_run workspace of this shape): DDK_OK, or DDK_ERR_CLUSTER when any in-launch GroupNorm exchange timed out. */

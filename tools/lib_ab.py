@@ -2,17 +2,24 @@
 """A/B of two builds of the kernel library on the cfg4 reverse step (batch 32, graph replay), the way tools/fold_ab.py alternates a
 plan option:  python tools/lib_ab.py A=path/to/libddk.so B=other/libddk.so [rounds]  -- ms per step, alternating, `rounds` (3) rounds
 of 200 steps each, both libraries in this one process (same clocks, same allocator state).  ddk.lib binds one library per import
-(DDK_LIB), so each arm imports the Python layer afresh: the project's modules are dropped from sys.modules between the two."""
+(DDK_LIB), so each arm imports the Python layer afresh: the project's modules are dropped from sys.modules between the two.
+An arm whose library has other entry points than this tree's Python layer binds names its own tree: A=lib.so@path/to/that/checkout
+(the Python layer, bench.py and the models are then imported from there)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "downsampled-diffusion_amd"), ROOT]
 import torch
+ROOTS = {ROOT}
 
 
 def load_arm(path):
     """model, plan and inputs on the library at `path`; returns run(k) = k graph-replayed reverse steps"""
+    path, _, root = path.partition("@")
+    root = os.path.abspath(root) if root else ROOT
+    ROOTS.add(root)
+    sys.path[:2] = [os.path.join(root, "downsampled-diffusion_amd"), root]
     os.environ["DDK_LIB"] = os.path.abspath(path)
-    for k in [k for k, m in sys.modules.items() if (getattr(m, "__file__", None) or "").startswith(ROOT + os.sep)]:
+    for k in [k for k, m in sys.modules.items() if any((getattr(m, "__file__", None) or "").startswith(r + os.sep) for r in ROOTS)]:
         del sys.modules[k]
     from bench import cfg4
     from ddk import lib, ops

@@ -3,7 +3,7 @@
 (`rocprofv3 --kernel-trace --pmc ... -- python3 tools/pmc_one.py <case>`; counters and --stats in separate passes).
 cases: cls16 (the k-split in-launch GroupNorm conv of the 16x16 up level), wino (conv3x3 128->128 @32x32 B=32, Winograd), gn (GroupNorm-apply from partials, 32x32x32x128), local4 (conv+GroupNorm+Mish
 one launch, 256->256 @4x4), wlocal8 (the same @8x8, Winograd form), first (conv_first 8->128 @32x32), tail (final_tail_kernel),
-cluster16 (conv3x3 256->256 @16x16 with GroupNorm finished in the launch), ws (to_out 1x1 128->128 + bias + residual @32x32,
+cluster16 (conv3x3 256->256 @16x16 with GroupNorm finished in the launch), skip16 (conv3x3 128->256 @16x16 likewise, carrying the 1x1 skip conv), ws (to_out 1x1 128->128 + bias + residual @32x32,
 weights-stationary kernel), fold (attn_fold_kernel), halo32 (wgrad3x3_halo32_kernel), gnbig (gn_apply_kernel on the 256x256 tensor),
 kvctx (attn_kvctx_kernel: k, v projection + context @32x32), c32 (conv3x3 32->32 @64x64 B=64 with the filter in registers), stream (conv1x1 32->64 @64x64 B=64 with Mish' and residual: conv1x1_stream.hip), attnsplit (attn_split_kernel: to_qkv + attention core
 @16x16, C = 256)."""
@@ -111,6 +111,13 @@ elif case == "cluster16":
     wu, b = ops.pack_conv_weight_wino(w), torch.zeros(256, device=dev)
     gam, bet, temb = torch.ones(256, device=dev), torch.zeros(256, device=dev), torch.randn(B, 256, device=dev)
     fn = lambda: ops.conv3x3_gn_mish_cluster(x, wu, b, gam, bet, temb=temb, check=False)
+elif case == "skip16":         # conv3x3 128->256 @16x16, GroupNorm in the launch, carrying the block's 1x1 skip conv
+    x, w = torch.randn(B, 16, 16, 128, device=dev), rw(256, 128)
+    wu, b = ops.pack_conv_weight_wino(w), torch.zeros(256, device=dev)
+    wsk, bs = ops.pack_conv_skip_weight_wino(rw(256, 128, 1)), torch.zeros(256, device=dev)
+    gam, bet, temb = torch.ones(256, device=dev), torch.zeros(256, device=dev), torch.randn(B, 256, device=dev)
+    out, sk = torch.empty(B, 16, 16, 256, device=dev), torch.empty(B, 16, 16, 256, device=dev)
+    fn = lambda: ops.conv3x3_gn_mish_cluster(x, wu, b, gam, bet, temb=temb, check=False, skip_w=wsk, skip_bias=bs, skip_out=sk, out=out)
 elif case == "cls16":          # conv3x3 128->128 @16x16, k split over two workgroups per tile, partner tile summed + GroupNorm in the launch (round 6)
     x, w = torch.randn(B, 16, 16, 128, device=dev), rw(128, 128)
     wu, b = ops.pack_conv_weight_wino(w), torch.zeros(128, device=dev)
