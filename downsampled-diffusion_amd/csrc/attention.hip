@@ -1287,6 +1287,123 @@ __global__ __launch_bounds__(256) void attn_fold_kernel(const float* __restrict_
     }
 }
 
+// The same A, a1, a2 straight from the split records {max[32], den[32], ctx[32][32]} that attn_kvctx_kernel / linattn_context_kernel
+// leave -- no merge launch, no ctx tensor -- with the product reassociated so that no workgroup builds T:
+//   P[n][h 32 + d] = sum_e W_out[n][h 32 + e] ctx[h][d][e],   A = P . Wqg,   a1 = P c1q,   a2 = P c2q + b_out
+// Workgroup (b, quarter) needs only ITS 32 rows of P: 16 MFMAs per wave (wave = head) where attn_fold_kernel spends 64 on the shared T,
+// then the same 64 for its 32 x 32 block of A (wave = column block).  Every global word a lane uses -- its Wqg column fragments, its
+// W_out row fragment, its c1q / c2q terms and its share of the head's S records -- is requested before the first use (one memory
+// latency for the launch; the round-4 form of this merge paid one per split).  The merge is linattn_merge_kernel's arithmetic in
+// split order, so the merged context has the bits of the two-launch path; it goes to LDS transposed ([e][d], pitch 34: the P phase's
+// column operand reads it conflict-free), P goes to LDS at pitch 130 (row operand of the A phase: bank = 2 n + k parity).
+// The k index of the P phase runs e = 16 (lane / 32) + s so that a lane's W_out fragment is 16 contiguous floats.
+constexpr int FP_CT = 34, FP_PP = FOLD_C + 2;
+template <int S>
+__global__ __launch_bounds__(256) void attn_fold_parts_kernel(const float* __restrict__ part, const float* __restrict__ wqg,
+                                                              const float* __restrict__ c1q, const float* __restrict__ c2q,
+                                                              const float* __restrict__ wout, const float* __restrict__ bout,
+                                                              float* __restrict__ A, float* __restrict__ a1, float* __restrict__ a2) {
+    __shared__ float ctxT[4 * DH * FP_CT];      // merged context, [h][e][d]
+    __shared__ float Ps[32 * FP_PP];            // P rows of this quarter, [n][h 32 + d]
+    const int b = blockIdx.x, nq = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l31 = lane & 31, kh = lane >> 5;
+    // constant weights first: they do not wait for the launch in front
+    float bw[FOLD_C / 2];                       // A phase column operand: Wqg[2 s + kh][32 wave + l31]
+#pragma unroll
+    for (int s2 = 0; s2 < FOLD_C / 2; ++s2) bw[s2] = wqg[(2 * s2 + kh) * FOLD_C + wave * 32 + l31];
+    float aw[DH / 2];                           // P phase row operand: W_out[32 nq + l31][32 wave + 16 kh + s]
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const float4 v = *reinterpret_cast<const float4*>(wout + (long long)(nq * 32 + l31) * FOLD_C + wave * DH + kh * 16 + 4 * q);
+        aw[4 * q] = v.x; aw[4 * q + 1] = v.y; aw[4 * q + 2] = v.z; aw[4 * q + 3] = v.w;
+    }
+    const int vn = tid >> 3, vp = tid & 7;      // a1 / a2: row vn of P, terms k = 8 i + vp
+    float cv1[FOLD_C / 8], cv2[FOLD_C / 8];
+#pragma unroll
+    for (int i = 0; i < FOLD_C / 8; ++i) {
+        cv1[i] = c1q[8 * i + vp];
+        cv2[i] = c2q[8 * i + vp];
+    }
+    const float bo = bout ? bout[nq * 32 + vn] : 0.f;
+    // wave = head: lane (dl, e0) merges rows d = dl + 8 j of the head's context, columns e0 .. e0 + 3
+    const float* pp = part + ((long long)b * 4 + wave) * S * PART;
+    const int dl = lane >> 3, e0 = (lane & 7) * 4;
+    float mv[S][4], dv[S][4];
+    float4 rv[S][4];
+#pragma unroll
+    for (int s = 0; s < S; ++s)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int d = dl + 8 * j;
+            mv[s][j] = pp[s * PART + d];
+            dv[s][j] = pp[s * PART + DH + d];
+            rv[s][j] = *reinterpret_cast<const float4*>(pp + s * PART + 2 * DH + d * DH + e0);
+        }
+    __builtin_amdgcn_sched_barrier(0);          // every load above is in flight before the first use below
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int d = dl + 8 * j;
+        float M = -INFINITY;
+#pragma unroll
+        for (int s = 0; s < S; ++s) M = fmaxf(M, mv[s][j]);
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        float den = 0.f;
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            const float w = expf(mv[s][j] - M);
+            const float4 a = rv[s][j];
+            den += dv[s][j] * w;
+            acc.x += a.x * w; acc.y += a.y * w; acc.z += a.z * w; acc.w += a.w * w;
+        }
+        const float inv = 1.0f / den;
+        acc.x *= inv; acc.y *= inv; acc.z *= inv; acc.w *= inv;
+        float* ct = ctxT + (wave * DH + e0) * FP_CT + d;
+        ct[0] = acc.x; ct[FP_CT] = acc.y; ct[2 * FP_CT] = acc.z; ct[3 * FP_CT] = acc.w;
+    }
+    __syncthreads();
+    {   // P phase: P_h [32 n][32 d] = W_out [32 n][32 e of head h] . ctx_h^T [32 e][32 d], 16 k-pairs
+        f32x16_att acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+        for (int s2 = 0; s2 < DH / 2; ++s2)
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aw[s2], ctxT[(wave * DH + kh * 16 + s2) * FP_CT + l31], acc, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) Ps[((r & 3) + 8 * (r >> 2) + 4 * kh) * FP_PP + wave * DH + l31] = acc[r];
+    }
+    __syncthreads();
+    {   // A phase: rows [32 nq, +32) x column block `wave`: A = P [32 n][128 hd] . Wqg [128 hd][32 c], 64 k-pairs
+        f32x16_att acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+        for (int s2 = 0; s2 < FOLD_C / 2; ++s2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(Ps[l31 * FP_PP + 2 * s2 + kh], bw[s2], acc, 0, 0, 0);
+        float* Ab = A + ((long long)b * FOLD_C + nq * 32) * FOLD_C + wave * 32 + l31;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) Ab[((r & 3) + 8 * (r >> 2) + 4 * kh) * FOLD_C] = acc[r];
+    }
+    {   // a1, a2: eight lanes per row of P, 16 terms each, summed over the eight in a fixed tree
+        float u1 = 0.f, u2 = 0.f;
+#pragma unroll
+        for (int i = 0; i < FOLD_C / 8; ++i) {
+            const float p = Ps[vn * FP_PP + 8 * i + vp];
+            u1 += p * cv1[i];
+            u2 += p * cv2[i];
+        }
+#pragma unroll
+        for (int m = 1; m < 8; m *= 2) {
+            u1 += __shfl_xor(u1, m, 64);
+            u2 += __shfl_xor(u2, m, 64);
+        }
+        if (vp == 0) {
+            const int n = nq * 32 + vn;
+            a1[(long long)b * FOLD_C + n] = u1;
+            a2[(long long)b * FOLD_C + n] = u2 + bo;
+        }
+    }
+}
+
 int linattn_small_qkv_init_device() {
     DDK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_kvctx_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)(KC_LDS_FLOATS * sizeof(float))));
@@ -1337,12 +1454,13 @@ int attn_kvctx_splits(int B, int HW) {
 size_t attn_kvctx_workspace_bytes(int B, int HW) { return (size_t)B * 4 * attn_kvctx_splits(B, HW) * PART * sizeof(float); }
 
 // x [B*HW][128]; w_kv [256][128] = the k and v rows of the LayerNorm-folded to_qkv weight (W o g), c1 / c2 [256] = (W g, W b) of those
-// rows -> ctx [B][4][32][32] (softmax over the pixels of k, then k v^T), bit-stable; workspace: attn_kvctx_workspace_bytes
-int attn_kvctx(const float* x, const float* w_kv, const float* c1, const float* c2, float ln_eps, float* ctx, int B, int HW, void* workspace,
-               size_t workspace_bytes, hipStream_t st) {
-    DDK_REQUIRE(x && w_kv && c1 && c2 && ctx && workspace, "attn_kvctx: null pointer");
+// rows -> the attn_kvctx_splits(B, HW) records {max, denominator, unnormalised ctx} per (image, head) in `workspace`
+// (attn_kvctx_workspace_bytes), for linattn_merge_kernel or attn_fold_parts
+int attn_kvctx_parts(const float* x, const float* w_kv, const float* c1, const float* c2, float ln_eps, int B, int HW, void* workspace,
+                     size_t workspace_bytes, hipStream_t st) {
+    DDK_REQUIRE(x && w_kv && c1 && c2 && workspace, "attn_kvctx: null pointer");
     DDK_REQUIRE(attn_kvctx_ok(B, HW, KC_K, 4), "attn_kvctx: needs 128 channels, 4 heads, H*W a multiple of 64 and >= 256");
-    DDK_REQUIRE(aligned16(x) && aligned16(w_kv) && aligned16(c1) && aligned16(c2) && aligned16(ctx) && aligned16(workspace), "attn_kvctx: alignment");
+    DDK_REQUIRE(aligned16(x) && aligned16(w_kv) && aligned16(c1) && aligned16(c2) && aligned16(workspace), "attn_kvctx: alignment");
     DDK_REQUIRE((long long)B * HW * KC_K * 4 < (1LL << 32) && B <= 65535, "attn_kvctx: input of 4 GiB or more, or more than 65535 images");
     const int s = attn_kvctx_splits(B, HW);
     if (workspace_bytes < attn_kvctx_workspace_bytes(B, HW)) {
@@ -1352,8 +1470,24 @@ int attn_kvctx(const float* x, const float* w_kv, const float* c1, const float* 
     DDK_TRY(ensure_device_init());
     KvCtxParams p{x, w_kv, c1, c2, ln_eps, static_cast<float*>(workspace), HW / KC_BM, HW / KC_BM / s, s};
     hipLaunchKernelGGL(attn_kvctx_kernel, dim3((unsigned)s, 2, (unsigned)B), dim3(512), KC_LDS_FLOATS * sizeof(float), st, p);
-    DDK_TRY(check_launch("attn_kvctx_kernel"));
-    hipLaunchKernelGGL(linattn_merge_kernel, dim3(B * 4), dim3(256), 0, st, static_cast<const float*>(workspace), ctx, s);
+    return check_launch("attn_kvctx_kernel");
+}
+
+// ... merged -> ctx [B][4][32][32] (softmax over the pixels of k, then k v^T), bit-stable
+int attn_kvctx(const float* x, const float* w_kv, const float* c1, const float* c2, float ln_eps, float* ctx, int B, int HW, void* workspace,
+               size_t workspace_bytes, hipStream_t st) {
+    DDK_REQUIRE(ctx && aligned16(ctx), "attn_kvctx: ctx null or misaligned");
+    DDK_TRY(attn_kvctx_parts(x, w_kv, c1, c2, ln_eps, B, HW, workspace, workspace_bytes, st));
+    hipLaunchKernelGGL(linattn_merge_kernel, dim3(B * 4), dim3(256), 0, st, static_cast<const float*>(workspace), ctx,
+                       attn_kvctx_splits(B, HW));
+    return check_launch("linattn_merge_kernel");
+}
+
+// the merge launch on its own: part [B * heads][splits][PART] -> ctx [B][heads][32][32]
+int linattn_merge(const float* part, float* ctx, int B, int heads, int splits, hipStream_t st) {
+    DDK_REQUIRE(part && ctx && B > 0 && heads > 0 && splits > 0, "linattn_merge: arguments");
+    DDK_REQUIRE(aligned16(part) && aligned16(ctx), "linattn_merge: alignment");
+    hipLaunchKernelGGL(linattn_merge_kernel, dim3(B * heads), dim3(256), 0, st, part, ctx, splits);
     return check_launch("linattn_merge_kernel");
 }
 
@@ -1402,6 +1536,30 @@ int attn_fold(const float* ctx, const float* wqg, const float* c1q, const float*
     return check_launch("attn_fold_kernel");
 }
 
+// attn_fold from the split records (attn_fold_parts_kernel keeps a lane's share of all S records in registers: S of 1, 2, 4, 8)
+bool attn_fold_parts_ok(int C, int heads, int splits) {
+    return attn_fold_ok(C, heads) && heads == 4 && (splits == 1 || splits == 2 || splits == 4 || splits == 8);
+}
+template <int S>
+static void attn_fold_parts_launch(const float* part, const float* wqg, const float* c1q, const float* c2q, const float* wout,
+                                   const float* bout, float* A, float* a1, float* a2, int B, hipStream_t st) {
+    hipLaunchKernelGGL(attn_fold_parts_kernel<S>, dim3(B, 4), dim3(256), 0, st, part, wqg, c1q, c2q, wout, bout, A, a1, a2);
+}
+// part [(b * 4 + head) * splits + split][PART]; the weights and the outputs of attn_fold
+int attn_fold_parts(const float* part, int splits, const float* wqg, const float* c1q, const float* c2q, const float* wout, const float* bout,
+                    float* A, float* a1, float* a2, int B, int C, int heads, hipStream_t st) {
+    DDK_REQUIRE(part && wqg && c1q && c2q && wout && A && a1 && a2 && B > 0, "attn_fold_parts: arguments");
+    DDK_REQUIRE(attn_fold_parts_ok(C, heads, splits), "attn_fold_parts: C == 128, 4 heads and 1, 2, 4 or 8 splits only");
+    DDK_REQUIRE(aligned16(part) && aligned16(wout) && aligned16(A), "attn_fold_parts: alignment");
+    switch (splits) {
+        case 1: attn_fold_parts_launch<1>(part, wqg, c1q, c2q, wout, bout, A, a1, a2, B, st); break;
+        case 2: attn_fold_parts_launch<2>(part, wqg, c1q, c2q, wout, bout, A, a1, a2, B, st); break;
+        case 4: attn_fold_parts_launch<4>(part, wqg, c1q, c2q, wout, bout, A, a1, a2, B, st); break;
+        default: attn_fold_parts_launch<8>(part, wqg, c1q, c2q, wout, bout, A, a1, a2, B, st); break;
+    }
+    return check_launch("attn_fold_parts_kernel");
+}
+
 int linattn_apply(const float* qkv, const float* ctx, float* out, int B, int HW, int heads, hipStream_t st) {
     DDK_REQUIRE(qkv && ctx && out && B > 0 && HW > 0, "linattn_apply: arguments");
     DDK_REQUIRE(heads >= 1 && heads <= 8, "linattn_apply: heads must be in 1..8");
@@ -1427,6 +1585,22 @@ int ddk_attention_kv_context_ok(int B, int HW, int C, int heads) { return ddk::a
 int ddk_attention_kv_context(const float* x, const float* w_kv, const float* c1, const float* c2, float ln_eps, float* ctx, int B, int HW,
                              void* workspace, size_t workspace_bytes, ddk_stream_t s) {
     return ddk::attn_kvctx(x, w_kv, c1, c2, ln_eps, ctx, B, HW, workspace, workspace_bytes, ddk::as_stream(s));
+}
+int ddk_attention_kv_context_splits(int B, int HW) { return ddk::attn_kvctx_ok(B, HW, ddk::KC_K, 4) ? ddk::attn_kvctx_splits(B, HW) : 0; }
+int ddk_attention_kv_partials(const float* x, const float* w_kv, const float* c1, const float* c2, float ln_eps, int B, int HW, void* workspace,
+                              size_t workspace_bytes, int* splits, ddk_stream_t s) {
+    DDK_REQUIRE(splits, "attention_kv_partials: null split count");
+    DDK_TRY(ddk::attn_kvctx_parts(x, w_kv, c1, c2, ln_eps, B, HW, workspace, workspace_bytes, ddk::as_stream(s)));
+    *splits = ddk::attn_kvctx_splits(B, HW);
+    return DDK_OK;
+}
+int ddk_linattn_merge(const float* part, float* ctx, int B, int heads, int splits, ddk_stream_t s) {
+    return ddk::linattn_merge(part, ctx, B, heads, splits, ddk::as_stream(s));
+}
+int ddk_attention_fold_partials_ok(int C, int heads, int splits) { return ddk::attn_fold_parts_ok(C, heads, splits) ? 1 : 0; }
+int ddk_attention_fold_partials(const float* part, int splits, const float* wqg, const float* c1q, const float* c2q, const float* wout,
+                                const float* bout, float* A, float* a1, float* a2, int B, int C, int heads, ddk_stream_t s) {
+    return ddk::attn_fold_parts(part, splits, wqg, c1q, c2q, wout, bout, A, a1, a2, B, C, heads, ddk::as_stream(s));
 }
 size_t ddk_attention_split_workspace_bytes(int B) { return ddk::attn_split_workspace_bytes(B); }
 int ddk_attention_split_ok(int B, int HW, int C, int heads) { return ddk::attn_split_ok(B, HW, C, heads) ? 1 : 0; }

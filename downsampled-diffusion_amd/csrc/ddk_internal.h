@@ -292,6 +292,13 @@ bool attn_kvctx_ok(int B, int HW, int C, int heads);     // k, v projection + co
 size_t attn_kvctx_workspace_bytes(int B, int HW);
 int attn_kvctx(const float* x, const float* w_kv, const float* c1, const float* c2, float ln_eps, float* ctx, int B, int HW, void* workspace,
                size_t workspace_bytes, hipStream_t st);
+// ... leaving the split records in the workspace (no merge, no ctx) for attn_fold_parts, which folds A, a1, a2 straight from them
+int attn_kvctx_splits(int B, int HW);
+int attn_kvctx_parts(const float* x, const float* w_kv, const float* c1, const float* c2, float ln_eps, int B, int HW, void* workspace,
+                     size_t workspace_bytes, hipStream_t st);
+bool attn_fold_parts_ok(int C, int heads, int splits);
+int attn_fold_parts(const float* part, int splits, const float* wqg, const float* c1q, const float* c2q, const float* wout, const float* bout,
+                    float* A, float* a1, float* a2, int B, int C, int heads, hipStream_t st);
 size_t attn_fold_out_floats(int B);
 int attn_fold(const float* ctx, const float* wqg, const float* c1q, const float* c2q, const float* wout, const float* bout, float* A,
               float* a1, float* a2, int B, int C, int heads, hipStream_t st);

@@ -137,6 +137,8 @@ struct ddk_unet {
     bool cluster_split = true;               // ... also on shapes whose channel chunks are split over 2-4 workgroups (conv_wino_cluster_split_np):
                                              // a tile's first workgroup sums its partners' partial tiles in the launch (diagnostic option 11)
     bool attn_kvctx = true;                  // folded attention block: k, v projection + context in one launch (no kv tensor)
+    bool attn_fold_parts = true;             // ... and the per-image matrix folded straight from that launch's split records: no merge launch, no
+                                             // ctx tensor (DDK_OPT_ATTENTION_FOLD_PARTIALS; attn_fold_parts_ok)
     bool attn_split = true;                  // 16x16 / 8x8 maps: to_qkv + core in one launch, an (image, head) split over two workgroups that
                                              // exchange their context partials in the launch (DDK_OPT_ATTENTION_SPLIT) -- wherever the
                                              // in-launch GroupNorm may run; 0: the projection and linattn_small_kernel as two launches
@@ -484,6 +486,7 @@ extern "C" int ddk_unet_set_option(ddk_unet* u, int option, int value) {
         {DDK_OPT_RESTORE_FUSED_TAIL, true, [](ddk_unet& p, int v) { p.restore_fused = v != 0; }},
         {DDK_OPT_ATTENTION_SPLIT, true, [](ddk_unet& p, int v) { p.attn_split = v != 0; }},
         {DDK_OPT_SKIP_FOLD, true, [](ddk_unet& p, int v) { p.skip_fold = v != 0; }},
+        {DDK_OPT_ATTENTION_FOLD_PARTIALS, true, [](ddk_unet& p, int v) { p.attn_fold_parts = v != 0; }},
         // 0 off, 1 (default): the 4x4 level with its Downsample / Upsample convs, 2: the 4x4 level alone, 3: the 8x8 levels as well,
         // 4: the 8x8 levels only, 8 / 16: only downs[-2] / only ups[1]
         {DDK_OPT_LEVEL_CHAIN, true, [](ddk_unet& p, int v) {
@@ -1030,24 +1033,33 @@ static int run_attn(Ctx& c, const AttnW& a, const float* x, float* out, int H, i
         // q is linear in this attention: project k and v only, build the context, fold to_out . ctx^T . W_q (and the LayerNorm)
         // into one C x C matrix per image and apply it to x as a per-image 1x1 conv with the residual -- no q third of to_qkv, no
         // apply kernel, no separate to_out
+        float* A = o;                                   // [B][C][C], then a1, a2 [B][C] (the apply output buffer is free on this path)
+        float* a1 = A + (size_t)c.B * a.c * a.c;
+        float* a2 = a1 + (size_t)c.B * a.c;
+        const float *wqg = c.P + a.qkv_lnw, *bout = a.out.has_bias ? c.P + a.out.b : nullptr;
+        const ConvLnFold lnA{a1, a2, LN_EPS};
         if (c.u.attn_kvctx && attn_kvctx_ok(c.B, H * W, a.c, HEADS) && c.ly.splitk * sizeof(float) >= attn_kvctx_workspace_bytes(c.B, H * W)) {
             // round 5: projection and context in one launch -- the 33.5 MB kv tensor of the 32x32 level is never written
-            DDK_TRY(attn_kvctx(x, c.P + a.qkv_lnw + (size_t)HIDDEN * a.c, c.P + a.ln_c1 + HIDDEN, c.P + a.ln_c2 + HIDDEN, LN_EPS, ctx, c.B, H * W,
-                               c.W + c.ly.off_splitk, c.ly.splitk * sizeof(float), c.st));
+            const float *wkv = wqg + (size_t)HIDDEN * a.c, *c1kv = c.P + a.ln_c1 + HIDDEN, *c2kv = c.P + a.ln_c2 + HIDDEN;
+            float* part = c.W + c.ly.off_splitk;
+            const int splits = attn_kvctx_splits(c.B, H * W);
+            if (c.u.attn_fold_parts && attn_fold_parts_ok(a.c, HEADS, splits)) {
+                // the matrix straight from the split records, which stay in the workspace until this launch has read them
+                DDK_TRY(attn_kvctx_parts(x, wkv, c1kv, c2kv, LN_EPS, c.B, H * W, part, c.ly.splitk * sizeof(float), c.st));
+                DDK_TRY(attn_fold_parts(part, splits, wqg, c.P + a.ln_c1, c.P + a.ln_c2, c.P + a.out.w, bout, A, a1, a2, c.B, a.c, HEADS, c.st));
+                return conv1x1_ws(x, A, nullptr, x, out, M, a.c, &lnA, c.st, c.B);
+            }
+            DDK_TRY(attn_kvctx(x, wkv, c1kv, c2kv, LN_EPS, ctx, c.B, H * W, part, c.ly.splitk * sizeof(float), c.st));
         } else {
             const ConvLnFold lnkv{c.P + a.ln_c1 + HIDDEN, c.P + a.ln_c2 + HIDDEN, LN_EPS};
             DDK_TRY(run_conv(c, DDK_CONV1X1, a.qkv, x, a.c, nullptr, 0, nullptr, qkv, H, W, 2 * HIDDEN, c.P + a.qkv_lnw + (size_t)HIDDEN * a.c,
                              &lnkv));
             // (round 4: merging the split context partials inside attn_fold_kernel instead of the 5.5 us merge launch made that kernel 13.0 ->
-            //  25.6 us -- each of an image's four workgroups redoes the 4 x 8 partial reads -- so the merge launch stays)
+            //  25.6 us -- each of an image's four workgroups redoes the 4 x 8 partial reads, one memory latency per split -- so the merge
+            //  launch stays on this diagnostic path)
             DDK_TRY(linattn_context(qkv, ctx, c.B, H * W, HEADS, c.W + c.ly.off_splitk, c.ly.splitk * sizeof(float), c.st, true));
         }
-        float* A = o;                                   // [B][C][C], then a1, a2 [B][C] (the apply output buffer is free on this path)
-        float* a1 = A + (size_t)c.B * a.c * a.c;
-        float* a2 = a1 + (size_t)c.B * a.c;
-        DDK_TRY(attn_fold(ctx, c.P + a.qkv_lnw, c.P + a.ln_c1, c.P + a.ln_c2, c.P + a.out.w, a.out.has_bias ? c.P + a.out.b : nullptr, A, a1,
-                          a2, c.B, a.c, HEADS, c.st));
-        const ConvLnFold lnA{a1, a2, LN_EPS};
+        DDK_TRY(attn_fold(ctx, wqg, c.P + a.ln_c1, c.P + a.ln_c2, c.P + a.out.w, bout, A, a1, a2, c.B, a.c, HEADS, c.st));
         return conv1x1_ws(x, A, nullptr, x, out, M, a.c, &lnA, c.st, c.B);
     }
     if (!c.u.generic && c.u.attn_split && c.allow_cluster && a.c >= 128 && attn_split_ok(c.B, H * W, a.c, HEADS)) {
@@ -1547,9 +1559,12 @@ extern "C" double ddk_unet_flops_executed(const ddk_unet* u, int B, int H0, int 
     };
     auto attn = [&](const AttnW& a, int H, int W) {
         if (attn_fold_eligible(*u, a, B, H, W)) {
-            // k, v projection + context + the per-image fold (T four times per image, A once) + the per-image C x C conv
+            // k, v projection + context + the per-image fold (T four times per image, or P once from the split records; A once) + the
+            // per-image C x C conv
+            const bool parts = u->attn_kvctx && u->attn_fold_parts && attn_kvctx_ok(B, H * W, a.c, HEADS) &&
+                               attn_fold_parts_ok(a.c, HEADS, attn_kvctx_splits(B, H * W));
             f += conv_flops(DDK_CONV1X1, B, H, W, a.c, 2 * HIDDEN) + 2.0 * B * HEADS * 32.0 * 32.0 * H * W;
-            f += 2.0 * B * (4.0 * HIDDEN * 32.0 * a.c + (double)a.c * HIDDEN * a.c) + conv_flops(DDK_CONV1X1, B, H, W, a.c, a.c);
+            f += 2.0 * B * ((parts ? 1.0 : 4.0) * HIDDEN * 32.0 * a.c + (double)a.c * HIDDEN * a.c) + conv_flops(DDK_CONV1X1, B, H, W, a.c, a.c);
             return;
         }
         f += conv_flops(DDK_CONV1X1, B, H, W, a.c, 3 * HIDDEN) + conv_flops(DDK_CONV1X1, B, H, W, HIDDEN, a.c);

@@ -129,6 +129,11 @@ SIGNATURES = {
     "ddk_attention_kv_context_workspace_bytes": (_SZ, [_I, _I]),
     "ddk_attention_kv_context_ok": (_I, [_I, _I, _I, _I]),
     "ddk_attention_kv_context": (_I, [_P, _P, _P, _P, _F, _P, _I, _I, _P, _SZ, _P]),
+    "ddk_attention_kv_context_splits": (_I, [_I, _I]),
+    "ddk_attention_kv_partials": (_I, [_P, _P, _P, _P, _F, _I, _I, _P, _SZ, C.POINTER(C.c_int), _P]),
+    "ddk_linattn_merge": (_I, [_P, _P, _I, _I, _I, _P]),
+    "ddk_attention_fold_partials_ok": (_I, [_I, _I, _I]),
+    "ddk_attention_fold_partials": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "ddk_attention_split_workspace_bytes": (_SZ, [_I]),
     "ddk_attention_split_ok": (_I, [_I, _I, _I, _I]),
     "ddk_attention_split_from_x": (_I, [_P, _P, _P, _P, _F, _P, _P, _I, _I, _I, _I, _P, _SZ, _P]),

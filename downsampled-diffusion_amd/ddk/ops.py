@@ -464,6 +464,51 @@ def attention_kv_context(x, w_qkv, ln_g, ln_b, heads=4, eps=LN_EPS):
     return ctx
 
 
+def attention_kv_partials(x, w_qkv, ln_g, ln_b, heads=4, eps=LN_EPS):
+    """attention_kv_context without the merge (ddk_attention_kv_partials): the split records [B,4,splits,1088] = {max[32], den[32],
+    unnormalised ctx[32][32]} per (image, head, pixel split), for linattn_merge or attention_fold_partials."""
+    b, h, w_, c = x.shape
+    hc = heads * 32
+    lib = L.load()
+    if not lib.ddk_attention_kv_context_ok(b, h * w_, c, heads):
+        raise L.DDKError(f"attention_kv_partials: shape {tuple(x.shape)} with {heads} heads not eligible (C = 128, 4 heads, H*W % 64 == 0)")
+    wq = w_qkv.reshape(3 * hc, c).to(torch.float32)
+    g, be = ln_g.reshape(-1).to(torch.float32), ln_b.reshape(-1).to(torch.float32)
+    wkv = (wq * g.view(1, c))[hc:].contiguous()
+    c1, c2 = (wq @ g)[hc:].contiguous(), (wq @ be)[hc:].contiguous()
+    nbytes = lib.ddk_attention_kv_context_workspace_bytes(b, h * w_)
+    part = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32)
+    splits = C.c_int(0)
+    L.check(lib.ddk_attention_kv_partials(L.ptr(_f32(x)), L.ptr(wkv), L.ptr(c1), L.ptr(c2), eps, b, h * w_, L.ptr(part), nbytes,
+                                          C.byref(splits), L.stream()), "attention_kv_partials")
+    return part.view(b, heads, splits.value, 2 * 32 + 32 * 32)
+
+
+def linattn_merge(part):
+    """ctx [B,heads,32,32] from split records [B,heads,splits,1088] (ddk_linattn_merge), in split order"""
+    b, heads, splits, _ = part.shape
+    ctx = torch.empty((b, heads, 32, 32), device=part.device, dtype=torch.float32)
+    L.check(L.load().ddk_linattn_merge(L.ptr(_f32(part)), L.ptr(ctx), b, heads, splits, L.stream()), "linattn_merge")
+    return ctx
+
+
+def attention_fold_partials(part, wqg, c1q, c2q, w_out, b_out=None, out=None):
+    """(A [B,128,128], a1 [B,128], a2 [B,128]) of ddk_attention_fold straight from the split records [B,4,splits,1088] in one launch
+    (ddk_attention_fold_partials); wqg [128,128], c1q / c2q [128], w_out [128,128] packed, b_out [128] or None; out = (A, a1, a2) to
+    write into given tensors."""
+    b, heads, splits, _ = part.shape
+    c = wqg.shape[1]
+    lib = L.load()
+    if not lib.ddk_attention_fold_partials_ok(c, heads, splits):
+        raise L.DDKError(f"attention_fold_partials: C = {c}, {heads} heads, {splits} splits not eligible (C = 128, 4 heads, 1 / 2 / 4 / 8 splits)")
+    a_mat, a1, a2 = out if out is not None else (torch.empty((b, c, c), device=part.device, dtype=torch.float32),
+                                                 torch.empty((b, c), device=part.device, dtype=torch.float32),
+                                                 torch.empty((b, c), device=part.device, dtype=torch.float32))
+    L.check(lib.ddk_attention_fold_partials(L.ptr(_f32(part)), splits, L.ptr(wqg), L.ptr(c1q), L.ptr(c2q), L.ptr(w_out), L.ptr(b_out),
+                                            L.ptr(a_mat), L.ptr(a1), L.ptr(a2), b, c, heads, L.stream()), "attention_fold_partials")
+    return a_mat, a1, a2
+
+
 def groupnorm_mish_from_partials_res1x1(x, part, tiles_per_image, gamma, beta, res_x, res_w, res_b, temb=None, groups=GN_GROUPS,
                                         eps=GN_EPS):
     """groupnorm_mish_from_partials with the addend res_b + res_x @ res_w^T (a 1x1 conv of a <= 8-channel tensor) computed on the

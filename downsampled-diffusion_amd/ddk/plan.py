@@ -130,6 +130,7 @@ class UnetPlan:
     OPT_RESTORE_FUSED_TAIL = 12
     OPT_ATTENTION_SPLIT = 13
     OPT_SKIP_FOLD = 14
+    OPT_ATTENTION_FOLD_PARTIALS = 15
 
     def set_option(self, option, value):
         """ddk_unet_set_option: e.g. (OPT_CLUSTER_GROUPNORM, 0) keeps conv + GroupNorm-apply as two launches

@@ -275,6 +275,22 @@ size_t ddk_attention_kv_context_workspace_bytes(int B, int HW);
 int ddk_attention_kv_context_ok(int B, int HW, int C, int heads);
 int ddk_attention_kv_context(const float* x, const float* w_kv, const float* c1, const float* c2, float ln_eps, float* ctx, int B, int HW,
                              void* workspace, size_t workspace_bytes, ddk_stream_t s);
+/* ddk_attention_kv_context without its merge launch: the records {max[32], den[32], unnormalised ctx[32][32]} (1088 floats) of every
+ * (image, head, pixel split) stay in `workspace`, [(b * 4 + head) * *splits + split], and *splits is set to their number per (image, head).
+ * ddk_linattn_merge combines such records (also those ddk_linattn_context leaves in its workspace) into ctx [B][heads][32][32], in split
+ * order: M = max_s m_s, w_s = exp(m_s - M), ctx = (sum_s w_s c_s) / (sum_s w_s den_s).  ddk_attention_kv_context_splits: the split count
+ * of a shape (a function of B and HW alone; 0 where ddk_attention_kv_context_ok is 0). */
+int ddk_attention_kv_context_splits(int B, int HW);
+int ddk_attention_kv_partials(const float* x, const float* w_kv, const float* c1, const float* c2, float ln_eps, int B, int HW,
+                              void* workspace, size_t workspace_bytes, int* splits, ddk_stream_t s);
+int ddk_linattn_merge(const float* part, float* ctx, int B, int heads, int splits, ddk_stream_t s);
+/* ddk_attention_fold straight from those records in ONE launch: ddk_linattn_merge's arithmetic (the merged context has the same bits,
+ * and is never written), then A = P . Wqg, a1 = P c1q, a2 = P c2q + b_out with P[n][h 32 + d] = sum_e W_out[n][h 32 + e] ctx[h][d][e] --
+ * the product of ddk_attention_fold reassociated, equal up to fp32 summation order.  C = 128, 4 heads, splits of 1, 2, 4 or 8
+ * (_ok() == 0 otherwise: the entry returns an error and launches nothing).  Weights and outputs as for ddk_attention_fold. */
+int ddk_attention_fold_partials_ok(int C, int heads, int splits);
+int ddk_attention_fold_partials(const float* part, int splits, const float* wqg, const float* c1q, const float* c2q, const float* wout,
+                                const float* bout, float* A, float* a1, float* a2, int B, int C, int heads, ddk_stream_t s);
 /* to_qkv (PreNorm LayerNorm folded in) + the attention core in ONE launch on 16x16 and 8x8 maps (H*W = 256 or 64; C % 32 == 0, C <= 256,
  * 4 heads, 8 * B <= the 256 CUs of a whole MI355X): workgroup = (image, head, half of the pixels); the two halves exchange their softmax
  * partials inside the launch and merge them in a fixed order, so the result is bit-stable (blocks.py:57-60, 123, 126-131).  No qkv tensor.
@@ -678,6 +694,12 @@ int ddk_unet_forward(const ddk_unet* u, const void* packed, const float* x, cons
  * read of the block's input fewer.  The choice depends on the shape alone, so ddk_unet_forward and ddk_sampler_run agree; 0 keeps the
  * 1x1 launch.  Same result up to fp32 summation order of the skip conv. */
 #define DDK_OPT_SKIP_FOLD 14
+/* DDK_OPT_ATTENTION_FOLD_PARTIALS (default 1): inside the folded attention block with DDK_OPT_ATTENTION_KV_CONTEXT on, the per-image matrix
+ * is built straight from the context's split records (ddk_attention_kv_partials -> ddk_attention_fold_partials) wherever
+ * ddk_attention_fold_partials_ok admits the split count: one launch in place of the merge and ddk_attention_fold, and no ctx tensor.  The
+ * choice depends on the shape alone, so ddk_unet_forward and ddk_sampler_run agree; 0 keeps the two launches.  Same result up to fp32
+ * summation order. */
+#define DDK_OPT_ATTENTION_FOLD_PARTIALS 15
 int ddk_unet_set_option(ddk_unet* u, int option, int value);
 /* Waits for `s`, then reads and clears the sticky give-up count of the launches issued on `workspace` (a ddk_unet_forward or
  * ddk_sampler_run workspace of this shape): DDK_OK, or DDK_ERR_CLUSTER when any in-launch GroupNorm exchange timed out. */

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""A/B of a plan option on the cfg4 reverse step (batch 32, graph replay): python tools/fold_ab.py [option id] -- ms per step with the
-option off / on, alternating, 3 rounds of 200 steps each.  Default option: DDK_OPT_FOLD_DOWNSAMPLE_REDUCE (5)."""
+"""A/B of a plan option on the cfg4 reverse step (batch 32, graph replay): python tools/fold_ab.py [option id] [values] [rounds] -- ms per step with
+the option off / on (or at the comma-separated `values`), alternating, `rounds` (3) rounds of 200 steps each.  Default option: DDK_OPT_FOLD_DOWNSAMPLE_REDUCE (5)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "downsampled-diffusion_amd"), ROOT]
@@ -12,6 +12,7 @@ from utils import synthetic as syn
 
 opt = int(sys.argv[1]) if len(sys.argv) > 1 else 5
 vals = [int(v) for v in sys.argv[2].split(",")] if len(sys.argv) > 2 else [0, 1]       # option values to alternate between
+rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 3
 dev = torch.device("cuda", 0)
 cfg = cfg4()
 model = DownsampleDDPM(cfg, Unet(cfg), "cuda", 3)
@@ -27,7 +28,7 @@ def run(k):
 
 
 with torch.no_grad():
-    for rnd in range(3):
+    for rnd in range(rounds):
         for val in vals:
             plan.set_option(opt, val)
             run(40)
